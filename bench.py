@@ -11,10 +11,18 @@ iterate() -> boundary-pose exchange -> update()  (dist_pgo.cpp:496-521).
   python bench.py --gpus 1 --steps 20 --warmup 5
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0) with the throughput, a `roofline` object for the dominant kernel family
-(launch durations measured with HIP events on the launch stream in an instrumented pass that repeats the
-timed region; a solve sweep's back-to-back launches share one event pair) and, at N = 1, a `cpu_baseline`
-object (the C++ CPU restatement timed on a bounded sample).
+Prints ONE JSON line (rank 0) with the throughput.  A plain run sets up, warms up, times --steps steps and prints
+the line.  With --full the line also carries a `roofline` object for the dominant kernel family (launch durations
+measured with HIP events on the launch stream in an instrumented pass that repeats the timed region; a solve
+sweep's back-to-back launches share one event pair), a `kernels` table, a `convergence` block and, at N = 1, a
+`cpu_baseline` object (the C++ CPU restatement timed on a bounded sample).
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it, to DIR/<name>.npy
+(float64): X, the global iterate ((d+1) n x d, the layout of dpgo_amd.DistPGO.X()), and fobj / gradFnorm, one entry
+per node.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -213,6 +221,12 @@ def main():
     ap.add_argument("--nodes", type=int, default=8)
     ap.add_argument("--grid", type=str, default="50,50,40,400000")
     ap.add_argument("--loss", type=str, default="huber")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the instrumented pass (roofline, kernels), "
+                         "the rocprofv3 traffic passes (--traffic), the CPU baseline and the convergence run (--converge); "
+                         "--no-prof / --no-cpu / --converge 0 / --traffic off leave parts of it out")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (X, fobj, gradFnorm) as DIR/<name>.npy")
     ap.add_argument("--prof-steps", type=int, default=5)
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--no-cpu", action="store_true")
@@ -226,14 +240,14 @@ def main():
                          "neighbours and no exchange, to see the per-GPU step time of that run on one GPU")
     ap.add_argument("--emulate-rank", type=int, default=0)
     ap.add_argument("--converge", type=int, default=400,
-                    help="second half of the metric (N = 1): after the timed region, restart from the chordal "
+                    help="with --full, the second half of the metric: after the timed region, restart from the chordal "
                          "initialisation, run this many iterations and report when the objective first came within 1e-6 "
                          "(relative) of the lowest one reached (SURVEY 8d: iterations and wall time to the reference "
                          "objective), the whole-run mean ms/iter and the ms/iter + CG steps/iter of the last 20 "
                          "iterations (the interior-step regime); 0 skips it")
     ap.add_argument("--traffic", type=str, default="auto",
-                    help="auto: measure roofline.traffic with two rocprofv3 --pmc passes over a short child run before the "
-                         "timed run (N = 1, about 40 s); off: quote the committed summary")
+                    help="with --full, auto: measure roofline.traffic with two rocprofv3 --pmc passes over a short child run "
+                         "before the timed run (N = 1, about 40 s); off: quote the committed summary")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="stop after the ranks have met (no GPU needed): checks the launcher")
     ap.add_argument("--rank-timeout", type=float, default=600.0,
@@ -251,6 +265,8 @@ def main():
                     help="diagnostic: run the boundary exchange (pack, all-gather, unpack) even with one rank, to see "
                          "what it adds to a step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     starved = None
@@ -259,7 +275,7 @@ def main():
         import starve
         starved = starve.prepare(args.starve_host)      # (the spinners start after the untimed set-up)
     measured_traffic = None
-    if (args.traffic == "auto" and world == 1 and args.gpus == 1 and not args.no_prof and args.prof_steps > 0
+    if (args.full and args.traffic == "auto" and world == 1 and args.gpus == 1 and not args.no_prof and args.prof_steps > 0
             and not args.rendezvous_only and args.starve_host < 0):
         measured_traffic = measure_traffic(args)       # (child processes; this one has not touched the GPU yet)
 
@@ -483,6 +499,9 @@ def main():
         spin1 = starve.cpu_seconds()
         starved = dict(starved, wall_s=wall, own_cpu_s=time.process_time() - cpu0,
                        spinners_cpu_s=[(b - a) if a is not None and b is not None else None for a, b in zip(spin0, spin1)])
+    if args.dump_outputs:
+        # (here, before the instrumented pass or the convergence run step the group again)
+        dump_outputs(args.dump_outputs, G, grp, my_nodes, args.nodes, dist if world > 1 else None, rank)
     per_rank = None
     if do_exchange:
         # every rank's own time over the timed region and what it hands to the transport per exchange (the N > 1 line
@@ -513,7 +532,7 @@ def main():
     # ---- instrumented pass: per-launch kernel durations with HIP events on the launch stream
     roofline = None
     kernels = {}
-    if not args.no_prof and args.prof_steps > 0:
+    if args.full and not args.no_prof and args.prof_steps > 0:
         dpgo_amd.prof_enable(True)
         for _ in range(args.prof_steps):
             step()
@@ -565,11 +584,11 @@ def main():
 
     # ---- CPU baseline: the C++ restatement of the path (tools/cpu_baseline) on a bounded sample, rank 0, N = 1 only
     cpu = None
-    if world == 1 and not args.no_cpu and args.cpu_steps > 0:
+    if args.full and world == 1 and not args.no_cpu and args.cpu_steps > 0:
         cpu = cpu_baseline(g, args.nodes, loss, X0, args.cpu_steps)
 
     convergence = None
-    if args.converge > 0 and not args.emulate_world:
+    if args.full and args.converge > 0 and not args.emulate_world:
         # every rank steps (the exchange included when there are several); each keeps ITS clock and ITS nodes' sums per
         # iteration, and the ranks' traces are combined once after the loop (reduce_trace: objective = sum over the ranks,
         # time = the slowest rank's) -- no collective inside the timed iterations beyond the exchange itself.  The reference
@@ -625,6 +644,44 @@ def main():
         comm.close()
     if do_exchange:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, G, grp, my_nodes, num_nodes, dist, rank):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- X, the global iterate ((d+1) n x d,
+    the layout of dpgo_amd.DistPGO.X()), and every node's fobj and gradFnorm (the terms of DistPGO.evaluate()) -- as
+    DIR/<name>.npy, float64.  A rank holds only its own nodes' rows and entries, every other one is 0, so the job's
+    arrays are the sums over the ranks (dist: the gloo control plane, or None for one rank).  Where X would take more than
+    half of the 64 MB budget, a fixed, seeded sample of poses is written instead: X_sample (each pose's translation row
+    and its d rotation rows) and X_sample_poses (their indices)."""
+    X = np.zeros(((G.d + 1) * G.num_poses, G.d), order="F")
+    if grp.scatter_global(X) != 0:
+        raise SystemExit("reading back the iterate failed")
+    per_node = np.zeros((2, num_nodes))
+    for k, a in enumerate(my_nodes):
+        r = grp.results(k)
+        per_node[:, a] = r.fobj, r.gradFnorm
+    if dist is not None:
+        import torch
+        flat = torch.from_numpy(np.concatenate([X.ravel(order="F"), per_node.ravel()]))
+        dist.all_reduce(flat)
+        flat = flat.numpy()
+        X, per_node = flat[:X.size].reshape(X.shape, order="F"), flat[X.size:].reshape(per_node.shape)
+    if rank != 0:
+        return
+    out = {"fobj": per_node[0], "gradFnorm": per_node[1]}
+    if X.nbytes <= DUMP_MAX_BYTES // 2:
+        out["X"] = X
+    else:
+        n, d = G.num_poses, G.d
+        poses = np.sort(np.random.default_rng(0).choice(n, size=(DUMP_MAX_BYTES // 2) // (8 * (d + 1) * d), replace=False))
+        rows = np.concatenate([poses[:, None], n + d * poses[:, None] + np.arange(d)], axis=1).ravel()
+        out["X_sample"], out["X_sample_poses"] = X[rows], poses.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def reduce_trace(trace, dist, num_nodes):

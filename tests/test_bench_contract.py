@@ -11,7 +11,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _check(j, n1=True):
+def _check(j, n1=True, full=True):
+    """full: a line of `bench.py --full` (roofline, cpu_baseline, convergence); otherwise a plain line, which has none."""
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config"):
         assert k in j, k
@@ -19,6 +20,9 @@ def _check(j, n1=True):
     assert j["vs_baseline"] is None                       # BASELINE.md publishes no number for this metric
     assert "workload" in j["config"] and "model" not in j["config"]
     assert abs(j["value"] * j["ms_per_step"] * 1e-3 - 1.0) < 1e-6      # iterations / s and ms / iteration agree
+    if not full:
+        assert j["roofline"] is None and not j["kernels"] and j["cpu_baseline"] is None and "convergence" not in j
+        return
     r = j["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
@@ -136,11 +140,83 @@ def test_convergence_block_of_the_two_rank_line():
         assert k in cv
 
 
+_DUMP_WORKER = r"""
+import os, sys, types
+import numpy as np
+sys.path.insert(0, %r)
+import bench
+n, d, nodes = 1000, 3, 4
+bench.DUMP_MAX_BYTES = 2 * 8 * (d + 1) * d * 50         # room for a sample of 50 poses
+G = types.SimpleNamespace(d=d, num_poses=n)
+class Group:
+    def scatter_global(self, X):
+        X[:] = np.arange(X.size, dtype=np.float64).reshape(X.shape, order="F")
+        return 0
+    def results(self, k):
+        return types.SimpleNamespace(fobj=10.0 + k, gradFnorm=0.5 * k)
+for out in sys.argv[1:]:
+    bench.dump_outputs(out, G, Group(), [1, 3], nodes, None, 0)
+"""
+
+
+def test_dump_outputs_of_a_large_iterate_are_a_seeded_sample(tmp_path):
+    """--dump-outputs stays within its 64 MB: an iterate larger than half of that is written as a fixed, seeded sample of
+    poses (each pose's translation row and its rotation rows, and the poses' indices), the same one every time."""
+    import numpy as np
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    out = subprocess.run([sys.executable, "-c", _DUMP_WORKER % ROOT] + dirs, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    n, d = 1000, 3
+    X = np.arange((d + 1) * n * d, dtype=np.float64).reshape(((d + 1) * n, d), order="F")
+    got = [{f: np.load(os.path.join(p, f + ".npy")) for f in ("X_sample", "X_sample_poses", "fobj", "gradFnorm")} for p in dirs]
+    g = got[0]
+    assert sorted(os.listdir(dirs[0])) == ["X_sample.npy", "X_sample_poses.npy", "fobj.npy", "gradFnorm.npy"]
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in os.listdir(dirs[0])) <= 2 * 8 * (d + 1) * d * 50
+    assert all(a.dtype == np.float64 for a in g.values())
+    poses = g["X_sample_poses"].astype(int)
+    assert len(poses) == 50 and len(set(poses)) == 50 and poses.min() >= 0 and poses.max() < n
+    rows = np.concatenate([[p] + [n + d * p + r for r in range(d)] for p in poses])
+    assert np.array_equal(g["X_sample"], X[rows])
+    # the nodes this rank hosts (1 and 3) carry their results, the others 0
+    assert np.array_equal(g["fobj"], [0.0, 10.0, 0.0, 11.0]) and np.array_equal(g["gradFnorm"], [0.0, 0.0, 0.0, 0.5])
+    for f in g:
+        assert np.array_equal(g[f], got[1][f]), f
+
+
 @pytest.mark.gpu
 def test_fresh_bench_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "20,20,16,25000", "--steps", "5",
-                          "--warmup", "2", "--converge", "40", "--cpu-steps", "1"], capture_output=True, text=True, cwd=ROOT)
+                          "--warmup", "2", "--full", "--converge", "40", "--cpu-steps", "1"], capture_output=True, text=True, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                # ONE JSON line
     _check(json.loads(lines[0]))
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline line only; --dump-outputs writes what the last
+    timed step computed (float64), and the same arguments give the same outputs in a second process."""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--grid", "20,20,16,25000",
+                              "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / str(k))],
+                             capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append([l for l in out.stdout.splitlines() if l.startswith("{")])
+        assert len(lines[k]) == 1
+        j = json.loads(lines[k][0])
+        _check(j, full=False)
+        assert j["steps"] == 7 and j["warmup"] == 2
+    dumped = [{f: np.load(str(tmp_path / str(k) / (f + ".npy"))) for f in ("X", "fobj", "gradFnorm")} for k in range(2)]
+    d = dumped[0]
+    assert d["X"].shape == (4 * 20 * 20 * 16, 3) and d["fobj"].shape == d["gradFnorm"].shape == (8,)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in d.values())
+    # the objective of the line is the sum of the nodes' fobj, and the rotation rows of X are rotations
+    assert abs(d["fobj"].sum() - 0.5 * j["objective_2F"]) <= 1e-12 * abs(j["objective_2F"])
+    n = 20 * 20 * 16
+    R = d["X"][n:].reshape(n, 3, 3)
+    assert np.abs(np.einsum("nij,nkj->nik", R, R) - np.eye(3)).max() < 1e-8
+    for f in d:
+        assert np.array_equal(d[f], dumped[1][f]), f

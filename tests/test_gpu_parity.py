@@ -274,9 +274,9 @@ def test_multiprocess_path_matches_single_process(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--grid", "10,10,8,2400", "--steps", "6", "--warmup", "2", "--no-prof", "--no-cpu", "--converge", "30"]
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True,
-                         timeout=600, cwd=root)
+    common = ["--grid", "10,10,8,2400", "--steps", "6", "--warmup", "2", "--full", "--no-prof", "--no-cpu", "--converge", "30"]
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(tmp_path / "one")],
+                         capture_output=True, text=True, timeout=600, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
     j1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     import socket
@@ -285,10 +285,11 @@ def test_multiprocess_path_matches_single_process(tmp_path):
         port = sk.getsockname()[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     # (a) under the launcher the driver uses, (b) started directly: bench.py spawns its own two ranks
-    for cmd in ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
-                 "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py")],
-                [sys.executable, os.path.join(root, "bench.py")]):
-        two = subprocess.run(cmd + ["--gpus", "2", "--backend", "gloo", "--share-gpu"] + common,
+    for k, cmd in enumerate(([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py")],
+                             [sys.executable, os.path.join(root, "bench.py")])):
+        dump = tmp_path / ("two%d" % k)
+        two = subprocess.run(cmd + ["--gpus", "2", "--backend", "gloo", "--share-gpu"] + common + ["--dump-outputs", str(dump)],
                              capture_output=True, text=True, timeout=900, cwd=root, env=env)
         assert two.returncode == 0, two.stderr[-3000:]
         lines = [l for l in two.stdout.splitlines() if l.startswith("{")]
@@ -296,6 +297,11 @@ def test_multiprocess_path_matches_single_process(tmp_path):
         j2 = json.loads(lines[0])
         assert j2["n_gpus"] == 2 and j2["config"]["nodes_per_gpu"] == 4
         assert abs(j1["objective_2F"] - j2["objective_2F"]) <= 1e-10 * abs(j1["objective_2F"])
+        # --dump-outputs: the two ranks' nodes gathered into the job's iterate and per-node results, those of one rank
+        for f in ("X", "fobj", "gradFnorm"):
+            a1, a2 = np.load(str(tmp_path / "one" / (f + ".npy"))), np.load(str(dump / (f + ".npy")))
+            assert a1.shape == a2.shape and a2.dtype == np.float64, f
+            np.testing.assert_allclose(a2, a1, rtol=1e-9, atol=1e-12, err_msg=f)
         # round 5: the N > 1 line carries the second half of the metric too -- the same trajectory, so the same
         # objectives at the same iterations as the one-rank line (the clocks differ)
         c1, c2 = j1["convergence"], j2["convergence"]

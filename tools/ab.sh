@@ -13,7 +13,7 @@ for rep in $(seq $reps); do i=0; for cfg in "$@"; do i=$((i+1))
   for w in $cfg; do case $w in lib=cur) ;; lib=*) lib=$PWD/.ab/lib_${w#lib=}.so ;; *) envs+=("$w") ;; esac; done
   run() { env DPGO_AMD_LIB=$lib "${envs[@]}" timeout 600 python bench.py --no-cpu --no-prof --traffic off "$@" 2>/dev/null; }
   if [ "$CONV" = 1 ]; then
-    run --steps 20 --warmup 5 | python3 -c "
+    run --full --steps 20 --warmup 5 | python3 -c "
 import json,sys; j=json.loads(sys.stdin.read()); c=j['convergence']; print('n1 $i %.4f' % j['ms_per_step']); print('conv $i %.4f' % c['seconds_to_1e-6'])" >> gpurun_out/$tag/raw.txt
   else
     run --converge 0 --steps 40 --warmup 10 | python3 -c "

@@ -16,8 +16,8 @@ has() { case " $stages " in *" $1 "*) return 0;; esac; return 1; }
 prof() { ( cd /tmp && TMPDIR=/tmp "$@" ); }
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$PWD
 if has bench; then
-  timeout 900 python bench.py > $out/${tag}_bench_n1.json 2> $out/bench_n1.err
-  timeout 600 python bench.py --emulate-world 8 --emulate-rank 3 --no-cpu > $out/${tag}_bench_emulated_rank3of8.json 2> $out/bench_emu.err
+  timeout 900 python bench.py --full > $out/${tag}_bench_n1.json 2> $out/bench_n1.err
+  timeout 600 python bench.py --full --emulate-world 8 --emulate-rank 3 --no-cpu > $out/${tag}_bench_emulated_rank3of8.json 2> $out/bench_emu.err
   cut -c1-400 $out/${tag}_bench_n1.json
 fi
 if has stats; then
