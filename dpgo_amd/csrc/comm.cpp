@@ -210,6 +210,7 @@ void Comm::release() {
       grp_->flush_pending_recv();   // (a lazy unpack reads this communicator's receive buffer)
       grp_->set_exchange_pack(nullptr, 0, nullptr);
       grp_->set_stuck_handler(nullptr, nullptr);
+      grp_->recv_lists_changed();   // (its receive lists are freed below: a later communicator's may get their address)
       attached_ = false;
     }
     if (lent_) {
@@ -322,6 +323,7 @@ int Comm::setup_p2p(const std::vector<std::vector<PoseKey>> &exported) {
     x.send_rows.upload(srows);
     x.recv_dst.upload(rdst);
     x.recv_src.upload(rsrc);
+    grp->recv_lists_changed();
     x.send.alloc(std::max<size_t>(x.plan.send_keys.size(), 1) * RS);
     x.recv.alloc(std::max<size_t>(x.plan.recv_keys.size(), 1) * RS);
     // self-check records: (node, pose) of their key in the first two entries
@@ -517,6 +519,7 @@ int Comm::enable_self_exchange() {
   x.send_rows.upload(rows);
   x.recv_dst.upload(rows);      // (into the same rows of the SCRATCH array)
   x.recv_src.upload(ident);
+  grp->recv_lists_changed();
   x.send.alloc((size_t)n * RS);
   x.recv.alloc((size_t)n * RS);
   HIP_OK(hipDeviceSynchronize());

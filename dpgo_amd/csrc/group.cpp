@@ -1946,6 +1946,7 @@ void Group::join_exchange() {
 }
 
 int Group::set_recv_layout(int nranks, int stride, const int *counts, const int *nodes, const int *poses) {
+  flush_pending_recv();   // (a lazy unpack still pending reads the lists re-uploaded below: it lands as the old lay-out said)
   std::map<std::pair<int, int>, int> slot;
   int off = 0;
   for (int r = 0; r < nranks; r++) {
@@ -1967,6 +1968,7 @@ int Group::set_recv_layout(int nranks, int stride, const int *counts, const int 
     }
   recv_dst_.upload(dst);
   recv_src_.upload(src);
+  recv_lists_changed();   // (upload() frees and re-allocates: the same size very likely comes back at the same address)
   return 0;
 }
 
@@ -1986,7 +1988,7 @@ int Group::set_pending_recv(const double *buf, int count, const int *dst_dev, co
   flush_pending_recv();
   static const bool lazy = env_int("DPGO_LAZY_UNPACK", 1) != 0;   // (A/B hook)
   if (!lazy || !fused_ || opt_.loss == 0 || star_ || count <= 0 || e_rec_host_.empty()) return -1;
-  if (recv_key_ != dst_dev || recv_count_ != count) {
+  if (recv_key_ != dst_dev || recv_count_ != count || recv_key_gen_ != recv_gen_) {
     std::vector<int> dst(count), src(count), nsrc((size_t)std::max(P1_, 1), -1);
     HIP_CHECK(hipMemcpy(dst.data(), dst_dev, sizeof(int) * count, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(src.data(), src_dev, sizeof(int) * count, hipMemcpyDeviceToHost));
@@ -2000,7 +2002,7 @@ int Group::set_pending_recv(const double *buf, int count, const int *dst_dev, co
     HIP_CHECK(hipMemcpyAsync(e_rec_.p, rec.data(), sizeof(InterInc) * rec.size(), hipMemcpyHostToDevice, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     recv_nsrc_.upload(nsrc);
-    recv_key_ = dst_dev; recv_count_ = count;
+    recv_key_ = dst_dev; recv_count_ = count; recv_key_gen_ = recv_gen_;
     recv_dst_dev_ = dst_dev; recv_src_dev_ = src_dev;
   }
   pending_recv_ = buf;
@@ -2831,14 +2833,25 @@ int Group::amm(const std::vector<int> &locals) {
 
 namespace dpgo {
 
-// Single operators on reference-layout inputs, for the parity tests.
+// Single operators on reference-layout inputs, for the parity tests.  Each enqueues the launches the iteration uses for it
+// (tnt.cpp, update(), iterate()).  "op" runs under the node's own mask (the compacted live-segment mapping, live_mask);
+// "op:all" under the whole group's (the whole-grid mapping of the iteration's common case), with the other nodes' rows zero.
 int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, double *out, int ld_out) {
   finish_update();
   if (a < 0 || a >= num_local()) return -1;
-  const std::string op(op_c);
+  std::string op(op_c);
+  const bool whole = op.size() > 4 && op.compare(op.size() - 4, 4, ":all") == 0;
+  if (whole) op.resize(op.size() - 4);
   const int n0 = info_[a].n[0], n1 = info_[a].n[1];
+  const int R0 = (d_ + 1) * n0;   // rows of one stacked operand
   sync();
-  set_mask({a});
+  for (auto &t : tmp_) HIP_CHECK(hipMemsetAsync(t.p, 0, sizeof(double) * t.n, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));   // (before the inputs are copied in on the null stream)
+  if (whole) {
+    std::vector<int> all(num_local());
+    for (int b = 0; b < num_local(); b++) all[b] = b;
+    set_mask(all);
+  } else set_mask({a});
   auto put_own = [&](double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t) {
     std::vector<double> rec((size_t)n0 * RS_, 0.0);
     for (int k = 0; k < n0; k++)
@@ -2884,6 +2897,63 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     put_own(Bv, in, ld_in, zr, zr + n0, true);
     launch_proximal(d_, st_, T_, cur_mask_, A, Bv, Tinv_.p, N_.p, V_.p, C, nullptr, nullptr, 0);
     get_own(C, out, ld_out, 0, n0, true);
+  } else if (op == "hess") {
+    // in = [Y ; nabla ; Ydot ; r]; out = [Hess[Ydot] (rotation rows) ; <p,Hp>, <Hp,Hp>, <p,p>, <p,r> in column 0], p = Ydot:
+    // a CG step's first half (tnt.cpp, stepA) with the sums reduced as k_cg_scal reduces them (k_reduce's order)
+    double *X = tmp_[0].p, *nabla = tmp_[1].p, *pk = tmp_[2].p, *rk = tmp_[3].p, *w1 = tmp_[4].p, *w3 = tmp_[5].p, *Hp = tmp_[6].p;
+    put_own(X, in, ld_in, 0, n0, true);
+    put_own(nabla, in, ld_in, R0, R0 + n0, true);
+    put_own(pk, in, ld_in, 0, 2 * R0 + n0, false);   // (tangent vectors carry no translation: p.x = r.x = 0 in the iteration)
+    put_own(rk, in, ld_in, 0, 3 * R0 + n0, false);
+    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, pk, true, nullptr, w1, nullptr, 0, nullptr, nullptr, 0);   // G [0 ; p.R]
+    solve_tt(w1, w3, -1.0);
+    apply_tcol(w3, w1, nullptr, 2, X, nabla, pk, Hp, rk, partials_.p);
+    fetch(4, false);
+    get_own(Hp, out, ld_out, 0, n0, false);
+    for (int q = 0; q < 4; q++) out[R0 + q] = scal(a, q);
+  } else if (op == "rgrad") {
+    // in = [Y ; g]; out = [Y' ; nabla' ; grad' ; nabla ; grad ; 4 sums], rows R0 each.  nabla = G Y + g, grad = Proj_Y(nabla.R)
+    // at Y as given (launch_bsr + launch_tangent_rot, tnt.cpp quad_model); the primed ones at Y' = [t recovered from Y.R and
+    // g ; Y.R] (recover_translations + apply_tcol mode 1, quad_model's from_base path) with its epilogue sums
+    // |grad'|^2, <Y', nabla'>, <Y', g>, <Y', g> in column 0 of the last 4 rows
+    double *X = tmp_[0].p, *g = tmp_[1].p, *nab = tmp_[2].p, *grad = tmp_[3].p, *nab1 = tmp_[4].p, *grad1 = tmp_[5].p;
+    put_own(X, in, ld_in, 0, n0, true);
+    put_own(g, in, ld_in, R0, R0 + n0, true);
+    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, X, false, g, nab, nullptr, 0, nullptr, nullptr, 0);
+    launch_tangent_rot(d_, st_, T_, cur_mask_, X, nab, grad);
+    recover_translations(X, g);
+    apply_tcol(X, T1_.p, nab1, 1, X, nullptr, nullptr, grad1, nullptr, partials_.p, g, g);
+    fetch(4, false);
+    get_own(X, out, ld_out, 0, n0, true);
+    get_own(nab1, out, ld_out, R0, R0 + n0, true);
+    get_own(grad1, out, ld_out, 2 * R0, 2 * R0 + n0, true);
+    get_own(nab, out, ld_out, 3 * R0, 3 * R0 + n0, true);
+    get_own(grad, out, ld_out, 4 * R0, 4 * R0 + n0, true);
+    for (int q = 0; q < 4; q++) out[5 * R0 + q] = scal(a, q);
+  } else if (op == "precon") {
+    // in = [Y ; v]; out = [Proj_Y(M^-1 v.R) (rotation rows) ; <v, out> in column 0]: the preconditioner of a CG step (tnt.cpp,
+    // stepB), M = G_RR + lambda I (RegularizedCholesky) or diag(G_RR) (Jacobi), whichever the group was built with
+    double *X = tmp_[0].p, *v = tmp_[1].p, *w1 = tmp_[2].p, *pv = tmp_[3].p;
+    put_own(X, in, ld_in, 0, n0, true);
+    put_own(v, in, ld_in, 0, R0 + n0, false);
+    if (opt_.preconditioner == 1 && jacobi_.n > 0) launch_rot_rowscale(d_, st_, T_, cur_mask_, jacobi_.p, v, w1);
+    else if (Lrr_.F.n > 0) solve_rr(v, w1, 1.0);
+    else return -1;
+    launch_tangent_rot(d_, st_, T_, cur_mask_, X, w1, pv, v, partials_.p, 0);
+    fetch(1, false);
+    get_own(pv, out, ld_out, 0, n0, false);
+    out[R0] = scal(a, 0);
+  } else if (op == "retract") {
+    // in = [Y ; Ydot ; g]; out = [-G_tt^-1 (g_t + G_tR R+) ; R+ = proj(Y.R + Ydot.R)] (tnt.cpp, enqueue_trial)
+    double *X = tmp_[0].p, *sk = tmp_[1].p, *g = tmp_[2].p, *xprop = tmp_[3].p;
+    put_own(X, in, ld_in, 0, n0, true);
+    put_own(sk, in, ld_in, 0, R0 + n0, false);
+    put_own(g, in, ld_in, 2 * R0, 2 * R0 + n0, true);
+    launch_retract_rot(d_, st_, T_, cur_mask_, X, sk, xprop);
+    recover_translations(xprop, g);
+    get_own(xprop, out, ld_out, 0, n0, true);
+  } else if (op == "lambda_max") {
+    out[0] = lambda_max_[a];   // (the host's Lanczos estimate the shift of G_RR was formed with)
   } else {
     fprintf(stderr, "[dpgo_amd] ERROR: debug_apply: unknown operator %s\n", op_c);
     return -1;

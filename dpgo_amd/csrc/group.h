@@ -243,6 +243,9 @@ class Group {
   // a lazy unpack of buf through the lists dst (neighbour rows) / src (slots), device arrays (group.cpp); -1: not taken
   int set_pending_recv(const double *buf, int count, const int *dst_dev, const int *src_dev);
   void flush_pending_recv();
+  // receive lists (set_recv_layout's or a communicator's) were uploaded or released: the digest set_pending_recv keeps is stale
+  // even where the new lists got the old ones' address
+  void recv_lists_changed() { recv_gen_++; }
   // the exchange's pack rides on the tail of iterate(): rows (device) of the records to pack, how many, where to (null: off);
   // take_packed(): whether the last iterate() did it (and forgets it)
   void set_exchange_pack(const int *rows_dev, int n, double *dst) { pack_rows_ = rows_dev; pack_n_ = n; pack_dst_ = dst; packed_ = false; }
@@ -469,6 +472,7 @@ class Group {
   const double *pending_recv_ = nullptr;  // a lazy unpack nobody has consumed yet (set_pending_recv)
   const int *recv_key_ = nullptr, *recv_dst_dev_ = nullptr, *recv_src_dev_ = nullptr;
   int recv_count_ = 0;
+  unsigned long long recv_gen_ = 1, recv_key_gen_ = 0;   // the digest is valid for generation recv_key_gen_ of the lists
   DevBuf<int> recv_nsrc_;                 // per neighbour row: its slot in the receive buffer, -1: none
   std::vector<InterInc> e_rec_host_;      // host copy of the incidence records (their osrc field follows the receive lay-out)
   const int *pack_rows_ = nullptr;

@@ -111,3 +111,70 @@ def write_g2o(path, g):
             info = "%g 0 0 0 0 0 %g 0 0 0 0 %g 0 0 0 %g 0 0 %g 0 %g" % (ti, ti, ti, ki, ki, ki)
             fh.write("EDGE_SE3:QUAT %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %s\n" % (
                 g["I"][e], g["J"][e], *g["t"][e], *q, info))
+
+
+LADDER_SIZES = (81, 1, 63, 64, 65, 129)   # own poses of the nodes of ladder(); node 0 holds the ladder itself
+LADDER_SPAN = 130                          # ids per node (the contiguous partition); ids a node does not use have no edge
+LADDER_TOP = 40
+
+
+def _random_rotations_d(rng, n, d):
+    if d == 3:
+        return _random_rotations(rng, n)
+    th = rng.uniform(-np.pi, np.pi, n)
+    c, s = np.cos(th), np.sin(th)
+    return np.stack([np.stack([c, -s], 1), np.stack([s, c], 1)], 1)
+
+
+def ladder(d=3, seed=7):
+    """A 6-node SE(d) graph whose rows cover every length the row kernels split differently (for operator tests).
+
+    Node 0: ladder poses L_k = k (k = 0..40), pose L_k with exactly k distinct intra-node neighbours -- the fillers
+    F_0..F_{k-1} (ids 41 + j), so filler F_j has 40 - j of them; L_0 has inter-node edges only.  A pose's block row of G
+    has 1 + (distinct intra neighbours) blocks: lengths 1..41, each residue mod 8 and mod 16 at least twice.  Some edges
+    are written reversed (head before tail) and some twice (parallel measurements of one pair).
+    Nodes 1..5: LADDER_SIZES[1:] own poses (the 64-row segment boundaries), a chain plus random closures, again with
+    reversed and parallel edges.  Neighbouring nodes share a few inter-node edges; L_0 and F_0 have some.
+    Returns the dict of grid() plus num_nodes."""
+    rng = np.random.default_rng(seed)
+    nn = len(LADDER_SIZES)
+    N = nn * LADDER_SPAN
+    I, J = [], []
+
+    def add(i, j):
+        I.append(i); J.append(j)
+
+    for k in range(1, LADDER_TOP + 1):
+        for j in range(k):
+            f = LADDER_TOP + 1 + j
+            if (k + j) % 3 == 0:
+                add(f, k)          # reversed
+            else:
+                add(k, f)
+            if j == 0 and k % 4 == 0:
+                add(k, f)          # parallel
+    first = [a * LADDER_SPAN for a in range(nn)]
+    for a in range(1, nn):
+        n, b = LADDER_SIZES[a], first[a]
+        for k in range(n - 1):
+            add(b + k + 1, b + k) if k % 5 == 0 else add(b + k, b + k + 1)
+        for _ in range(n // 2 if n > 2 else 0):
+            u, v = rng.choice(n, 2, replace=False)
+            add(b + u, b + v)
+            if rng.random() < 0.2:
+                add(b + v, b + u)  # parallel, reversed
+    # inter-node edges: L_0 and F_0 of the ladder, the single pose of node 1, and a few per neighbouring pair
+    add(0, first[1]); add(first[2], 0); add(LADDER_TOP + 1, first[5] + 3)
+    add(first[1], first[2] + 5)
+    for a in range(nn - 1):
+        for _ in range(3):
+            u = first[a] + rng.integers(LADDER_SIZES[a])
+            v = first[a + 1] + rng.integers(LADDER_SIZES[a + 1])
+            add(u, v) if rng.random() < 0.5 else add(v, u)
+    I = np.asarray(I, np.int64)
+    J = np.asarray(J, np.int64)
+    M = len(I)
+    R = _random_rotations_d(rng, M, d)
+    t = rng.standard_normal((M, d))
+    return dict(d=d, num_poses=N, num_nodes=nn, I=I, J=J, R=R, t=t, kappa=rng.uniform(1.0, 100.0, M),
+                tau=rng.uniform(1.0, 100.0, M), outlier=np.zeros(M, bool))

@@ -320,7 +320,10 @@ int dpgo_debug_p2p_plan(int rank, int nranks, const int *exp_counts, const int *
                         int *recv_keys, int *sizes);
 /* Device: single operators of one node on reference-layout inputs:
  *  "project" (d n0 x d -> nearest rotations), "solve_tt" ((d+1) n0 x d, translation rows),
- *  "solve_rr" (rotation rows), "G" ((d+1) n0 x d -> G X), "proximal" (in = [Z ; Df] stacked). */
+ *  "solve_rr" (rotation rows), "G" ((d+1) n0 x d -> G X), "proximal" (in = [Z ; Df] stacked),
+ *  "hess" (in = [Y ; nabla ; Ydot ; r] -> Hessian-vector product and 4 CG sums), "rgrad" (in = [Y ; g] -> both gradient
+ *  paths), "precon" (in = [Y ; v]), "retract" (in = [Y ; Ydot ; g]), "lambda_max" (out[0]); Group::debug_apply lists the
+ *  layouts.  A suffix ":all" runs the operator under the whole group's launch mask. */
 int dpgo_group_debug_apply(dpgo_group_t *grp, int local, const char *op, const double *in, int ld_in,
                            double *out, int ld_out);
 

@@ -77,9 +77,22 @@ def test_device_spd_solves_and_G(fixtures_dir):
         np.testing.assert_allclose(out, p.mat.G @ X, rtol=1e-12, atol=1e-9)
         out = grp.debug_apply(a, "solve_tt", X, 4 * n0)
         np.testing.assert_allclose(out[:n0], p.L.solve(X[:n0]), rtol=1e-9, atol=1e-9)
+        # G_RR + lambda I with the device's lambda (host Lanczos; the oracle's eigsh(tol=1e-4) differs): backward error
+        # against that matrix, forward error against its solve within 10 kappa_1 u (test_gpu_operators.py)
+        import scipy.sparse as sp
+        import scipy.sparse.linalg as spla
+        from oracle.problem import SpdSolver
+        lam = grp.debug_apply(a, "lambda_max", np.zeros((1, 3)), 1)[0, 0]
+        A = (p.mat.GRR + (lam / opt.reg_Cholesky_precon_max_condition_number) * sp.eye(3 * n0)).tocsr()
+        S = SpdSolver(A)
         out = grp.debug_apply(a, "solve_rr", X, 4 * n0)
-        ref = p.precon.solve(X[n0:])
-        np.testing.assert_allclose(out[n0:], ref, rtol=1e-6, atol=1e-8 * abs(ref).max())
+        x, b = out[n0:], X[n0:]
+        Ainf = abs(A).sum(axis=1).max()
+        assert np.all(np.abs(A @ x - b).max(axis=0) <= 1e-13 * (Ainf * np.abs(x).max(axis=0) + np.abs(b).max(axis=0)))
+        inv = spla.onenormest(spla.LinearOperator(A.shape, matvec=S.solve, rmatvec=S.solve, matmat=S.solve, dtype=np.float64))
+        kappa = Ainf * inv   # (symmetric: |A|_1 = |A|_inf)
+        ref = S.solve(b)
+        assert np.all(np.abs(x - ref).sum(axis=0) <= 10 * kappa * 2.0 ** -53 * np.abs(ref).sum(axis=0))
 
 
 CASES = [
