@@ -452,8 +452,8 @@ int dpgo_debug_spd_stats(int n, const int *ptr, const int *col, const double *va
   A.val.assign(val, val + ptr[n]);
   dpgo::SpdFactor F;
   if (dpgo::spd_factor(A, F, leaf) != 0) return -1;
-  if (const char *path = getenv("DPGO_SPD_DUMP_FRONTS")) {   // analysis hook: w u height depth per front
-    if (FILE *fp = fopen(path, "w")) {
+  if (!dpgo::settings().spd_dump_fronts.empty()) {   // analysis hook: w u height depth per front
+    if (FILE *fp = fopen(dpgo::settings().spd_dump_fronts.c_str(), "w")) {
       for (int f = 0; f < F.nfronts; f++) fprintf(fp, "%d %d %d %d\n", F.w[f], F.u[f], F.height[f], F.depth[f]);
       fclose(fp);
     }

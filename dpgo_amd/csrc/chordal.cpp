@@ -16,6 +16,7 @@
 #include <omp.h>
 
 #include "graph.h"
+#include "settings.h"
 
 namespace dpgo {
 
@@ -267,7 +268,7 @@ int chordal_initialization(const Graph &g, double *X, int ld) {
   int it2 = pcg(N, d, applyT, dg, bt, xsol, 1e-13, 50000);
   // the reference solves both least-squares problems directly (SPQR); an iteration that ran into its cap has
   // not reached the 1e-13 residual target, and the caller must know (disconnected or badly scaled graph)
-  if (getenv("DPGO_SETUP_TIMING"))
+  if (settings().setup_timing)
     fprintf(stderr, "[setup] chordal initialisation: %d PCG iterations for the rotations, %d for the translations\n", it1, it2);
   if (it1 >= 50000 || it2 >= 50000) {
     fprintf(stderr, "[dpgo_amd] ERROR: chordal initialisation: PCG did not converge (rotations %d, translations %d of 50000 "

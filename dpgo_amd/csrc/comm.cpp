@@ -182,8 +182,7 @@ void Comm::init(const void *id128, bool layout) {
     // Whether the neighbour-to-neighbour path is even tried is decided per PROCESS (environment, the symbols this
     // process's RCCL exports), so the ranks agree on it first: one dissenting rank and everybody keeps the all-gather --
     // nobody may enter setup_p2p()'s collectives alone.
-    const char *kind = getenv("DPGO_EXCHANGE");
-    const bool want = !(kind && std::string(kind) == "allgather") && rccl().Send && rccl().Recv && rccl().GroupStart && rccl().GroupEnd;
+    const bool want = settings().exchange != "allgather" && rccl().Send && rccl().Recv && rccl().GroupStart && rccl().GroupEnd;
     if (nranks > 1) {
       double against = want ? 0.0 : 1.0;
       if (allreduce_impl(&against, 1) != 0) return;
@@ -419,8 +418,7 @@ int Comm::run_p2p(P2P &x, const double *src_records, double *dst_records, hipStr
 void Comm::sync_comm_stream() { sync_stream(cs_); }
 
 void Comm::sync_stream(hipStream_t st) {
-  double limit = 120.0;
-  if (const char *e = getenv("DPGO_COMM_TIMEOUT")) limit = std::max(1.0, atof(e));
+  const double limit = std::max(1.0, settings().comm_timeout);
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t q = hipStreamQuery(st);
@@ -590,7 +588,7 @@ void Comm::cb_stuck(void *user) {
 int Comm::exchange() {
   if (!ok_) return -1;
   {   // DPGO_DEBUG_FAIL_EXCHANGE=n (test hook): the n-th exchange of this process fails the way an RCCL error would
-    static const int fail_at = getenv("DPGO_DEBUG_FAIL_EXCHANGE") ? atoi(getenv("DPGO_DEBUG_FAIL_EXCHANGE")) : 0;
+    const int fail_at = settings().debug_fail_exchange;
     static int calls = 0;
     if (fail_at > 0 && ++calls == fail_at) {
       fprintf(stderr, "[dpgo_amd] ERROR: rank %d: exchange %d failed (DPGO_DEBUG_FAIL_EXCHANGE)\n", rank_, calls);

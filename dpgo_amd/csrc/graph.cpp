@@ -1,4 +1,5 @@
 #include "graph.h"
+#include "settings.h"
 
 #include <algorithm>
 #include <cmath>
@@ -16,10 +17,7 @@ namespace dpgo {
 int host_threads() {
   static int cached = 0;
   if (cached) return cached;
-  if (const char *e = getenv("DPGO_HOST_THREADS")) {
-    const int v = atoi(e);
-    if (v > 0) return cached = v;
-  }
+  if (settings().host_threads > 0) return cached = settings().host_threads;
   int n = (int)std::thread::hardware_concurrency();
   cpu_set_t set;
   if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);

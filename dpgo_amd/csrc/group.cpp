@@ -66,12 +66,6 @@ template struct DevBuf<RootDesc>;
 template struct DevBuf<RootRow>;
 template struct DevBuf<float>;
 
-// tuning hooks (tools/env_ab.sh): an integer from the environment, or the default
-static int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
 // The factor stores explicit inverses of the pivot blocks: a pivot range beyond 1e13 (a badly scaled dataset: information
 // matrices that differ by many orders of magnitude, or a regulariser far below the weights) leaves few correct digits.
 static void warn_conditioning(const char *what, const SpdFactor &F) {
@@ -132,10 +126,10 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
   // at first (d_kk = 1 / Linv_kk^2, within the spectrum of the complement), and a factor with a root whose pivots span
   // more than 1e9 -- G_tt of a graph hosted by ONE node is the Laplacian + 1e-11 I, singular along the gauge -- keeps
   // the two sweeps.
-  fused_root = env_int("DPGO_SPD_FUSE_ROOT", 1) != 0;
+  fused_root = settings().spd_fuse_root;
   // a factor that is re-done every iteration or so (Rescale::Dynamic, G_tt): forming the roots' products again costs 0.5 ms
   // per refactorisation at the headline size, the launch it saves 10 us per solve
-  if (F.keep_numeric && env_int("DPGO_SPD_FUSE_ROOT_DYNAMIC", 0) == 0) fused_root = false;
+  if (F.keep_numeric && !settings().spd_fuse_root_dynamic) fused_root = false;
   if (fused_root) {
     double worst = 1.0;
     std::vector<double> diag;
@@ -151,8 +145,8 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
       if (!(lo > 0.0) || !std::isfinite(hi)) { fused_root = false; break; }
       worst = std::max(worst, (hi / lo) * (hi / lo));
     }
-    if (worst > std::pow(10.0, env_int("DPGO_SPD_FUSE_ROOT_MAXLOG", 9))) fused_root = false;
-    if (getenv("DPGO_SPD_DUMP")) fprintf(stderr, "[spd] dof %d roots: pivot range %.2e -> %s\n", dof, worst, fused_root ? "fused" : "two sweeps");
+    if (worst > std::pow(10.0, settings().spd_fuse_root_maxlog)) fused_root = false;
+    if (settings().spd_dump) fprintf(stderr, "[spd] dof %d roots: pivot range %.2e -> %s\n", dof, worst, fused_root ? "fused" : "two sweeps");
   }
   auto is_root = [&](int f) { return fused_root && F.parent[f] < 0 && F.u[f] == 0 && F.w[f] > 0; };
   int nnodes = 1;
@@ -177,8 +171,9 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
       const int wide_tiles = tiles64(lvl, fwd, true) + (merge ? tiles64(lvl, fwd, false) : 0);
       int longest = 0;
       for (int f : lvl) longest = std::max(longest, F.w[f] + F.u[f]);
-      const bool fine = fwd ? wide_tiles < env_int("DPGO_SPD_FINE_FWD", 192)
-                            : (wide_tiles < env_int("DPGO_SPD_FINE_BWD", 256) || (wide_tiles < env_int("DPGO_SPD_FINE_BWD_TALL", 800) && longest >= 1000));
+      const Settings &s = settings();
+      const bool fine = fwd ? wide_tiles < s.spd_fine_fwd
+                            : (wide_tiles < s.spd_fine_bwd || (wide_tiles < s.spd_fine_bwd_tall && longest >= 1000));
       const int rows = (wide_tiles > 0 && fine) ? 16 : 64;
       // node by node; within a node the wide tiles first (one workgroup each, longest first), then the narrow ones
       // (one wave each): a launch picks the ranges of the nodes that are still live (Level::map)
@@ -223,7 +218,7 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
       items[i] = it;
       total += t.len * ld;
     }
-    if (getenv("DPGO_SPD_DUMP")) {
+    if (settings().spd_dump) {
       int64_t used = 0;
       for (const Tile &t : tiles) used += t.len * t.count;
       fprintf(stderr, "[spd] dof %d %s panels: %.1f MB stored, %.1f MB of entries (padding %.1f %%), %zu tiles\n", dof, fwd ? "fwd" : "bwd",
@@ -285,9 +280,9 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
     double largest_mb = 0;
     for (int f = 0; f < F.nfronts; f++)
       if (is_root(f)) { roots.push_back(f); largest_mb = std::max(largest_mb, 8e-6 * (double)F.w[f] * F.w[f]); }
-    const int force = env_int("DPGO_SPD_ROOT_SYM", -1);
+    const int force = settings().spd_root_sym.value_or(-1);
     root_sym = !roots.empty() && nnodes <= MAX_LOCAL_NODES &&
-               (force == 1 || (force != 0 && largest_mb >= env_int("DPGO_SPD_ROOT_SYM_MB", 32)));
+               (force == 1 || (force != 0 && largest_mb >= settings().spd_root_sym_mb));
   }
   if (fused_root && root_sym) {
     std::vector<int> roots;
@@ -297,7 +292,7 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
     for (int f : roots) { const long long nb = (F.w[f] + 63) / 64; nblocks += nb * (nb + 1) / 2; }
     // blocks per item (a workgroup each, one dependent gather per item): as many as still leave the chip three workgroups
     // per CU, at most ROOT_SYM_MAXJ
-    const int S = (int)std::min<long long>(ROOT_SYM_MAXJ, std::max<long long>(1, env_int("DPGO_SPD_ROOT_SYM_BLOCKS", (int)(nblocks / 768))));
+    const int S = (int)std::min<long long>(ROOT_SYM_MAXJ, std::max<long long>(1, settings().spd_root_sym_blocks.value_or((int)(nblocks / 768))));
     root_sym_level = Level{0, 0, 0, 64, std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0),
                            std::vector<int>(nnodes, 0), std::vector<double>(nnodes, 0.0)};
     root_rows_level = root_sym_level;
@@ -375,7 +370,7 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
     launch_pack_panels(nullptr, root_pack.p, root_srcs.p, (int)pack.size(), Proot.p, Wroot.p);
     HIP_CHECK(hipDeviceSynchronize());
     if (!F.keep_numeric) Proot.release();
-    if (getenv("DPGO_SPD_DUMP"))
+    if (settings().spd_dump)
       fprintf(stderr, "[spd] dof %d fused roots as one triangle: %zu fronts, %zu items of <= %d blocks, %zu block rows, %d slots, %.1f MB of panels\n",
               dof, roots.size(), items.size(), S, rows.size(), nslots, total * 8e-6);
   } else if (fused_root) {
@@ -385,7 +380,7 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
     int t64 = 0;
     for (int f : roots) t64 += (F.w[f] + 63) / 64;
     // few tiles: 16-row tiles reach 4x more CUs; a single root per GPU (one node per GPU): 8-row tiles, 8x
-    const int rows = (t64 < env_int("DPGO_SPD_FINE_ROOT8", 64)) ? 8 : (t64 < env_int("DPGO_SPD_FINE_ROOT", 192) ? 16 : 64);
+    const int rows = t64 < settings().spd_fine_root8 ? 8 : (t64 < settings().spd_fine_root ? 16 : 64);
     root_level.rows = rows;
     std::vector<Tile> tiles;
     for (int a = 0; a < nnodes; a++) {
@@ -490,12 +485,12 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
         HIP_CHECK(hipDeviceSynchronize());
         root_fine_rows = fine;
         // (live tiles of the coarse class below which the fine one is taken: the thresholds the class itself was chosen by)
-        root_fine_below = rows == 64 ? env_int("DPGO_SPD_FINE_ROOT", 192) : env_int("DPGO_SPD_FINE_ROOT8", 64);
+        root_fine_below = rows == 64 ? settings().spd_fine_root : settings().spd_fine_root8;
       }
       HIP_CHECK(hipDeviceSynchronize());
       if (!F.keep_numeric) Proot.release();   // (kept for repack() when the factor is re-done with new values)
     }
-    if (getenv("DPGO_SPD_DUMP"))
+    if (settings().spd_dump)
       fprintf(stderr, "[spd] dof %d fused roots: %zu fronts, %zu tiles x %d rows, %.1f MB of panels\n", dof, roots.size(), tiles.size(), rows, total * 8e-6);
   }
   spd_release_device(F);
@@ -504,9 +499,7 @@ void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
   std::vector<double>().swap(F.WT);
   // both panel sets of a factor this small can live in the 256 MiB Infinity Cache from one solve to the next
   // (measured: G_tt with 177 MB of panels at two nodes per GPU still gains 2 % from staying; 288 MB does not)
-  size_t keep = 200u << 20;
-  if (const char *e = getenv("DPGO_SPD_KEEP_MB")) keep = (size_t)atol(e) << 20;
-  stream_once = sizeof(double) * (W.n + WT.n + Wroot.n) > keep;
+  stream_once = sizeof(double) * (W.n + WT.n + Wroot.n) > ((size_t)settings().spd_keep_mb << 20);
   dev.piv_idx = piv_idx.p; dev.upd_idx = upd_idx.p; dev.asm_ptr = asm_ptr.p; dev.ubuf_dst = ubuf_dst.p;
   dev.W = W.p; dev.WT = WT.p; dev.fwd_items = fwd_items.p; dev.bwd_items = bwd_items.p; dev.ubuf = ubuf.p;
   dev.root_items = root_items.p; dev.Wroot = Wroot.p;
@@ -704,7 +697,7 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
   h_gate_[0] = -1.0;
   for (int i = 0; i < std::max(L, 1) * (CG_SUMMARY + TNT_SUMMARY + 1); i++) h_cg_[i] = 0.0;
   reduce_arrived_.alloc(1);
-  fused_ = env_int("DPGO_FUSED", 1) != 0;
+  fused_ = settings().fused;
   partials_.alloc((size_t)MAX_SLOTS * std::max(T_.nseg_all, 1));
   cg_.alloc(MAX_LOCAL_NODES);
   dmask_.alloc(4);
@@ -712,7 +705,7 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
   go_.alloc(1);
   dev_sums_.alloc((size_t)MAX_LOCAL_NODES * MAX_SLOTS);
   dev_tnt_.alloc((size_t)MAX_LOCAL_NODES * TNT_SUMMARY);
-  spec_update_enabled_ = env_int("DPGO_SPEC_UPDATE", 1) != 0;
+  spec_update_enabled_ = settings().spec_update;
   coefs_dev_.alloc(MAX_LOCAL_NODES);
 
   upload_operators();
@@ -818,8 +811,8 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
     Arr.n = (int)Arr.ptr.size() - 1;
     clk.lap("G_RR: lambda_max (Lanczos) + shifted matrix");
     if (Arr.n > 0) {
-      if (spd_factor(Arr, Lrr_.F, env_int("DPGO_SPD_LEAF_RR", 96), env_int("DPGO_SPD_COLLAPSE_RR", 0), env_int("DPGO_SPD_QUOTIENT", 1) ? d_ : 1,
-                     env_int("DPGO_SPD_DEVICE_PANELS", 1) != 0) != 0) return;
+      const Settings &s = settings();
+      if (spd_factor(Arr, Lrr_.F, s.spd_leaf_rr, s.spd_collapse_rr, s.spd_quotient ? d_ : 1, s.spd_device_panels) != 0) return;
       clk.lap("G_RR: ordering + symbolic + numeric factor");
       warn_conditioning("G_RR + lambda I", Lrr_.F);
       Lrr_.dof = d_;
@@ -872,7 +865,7 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
   for (DevBuf<double> *b : {&Xak_, &Xakh_, &gc_, &gp_, &Dfc_, &Dfp_, &gx_, &Dfx_, &T1_}) b->alloc(nown);
   if (keep_gx()) { GXc_.alloc(nown); GXp_.alloc(nown); }
   for (auto &b : tmp_) b.alloc(nown);
-  if (getenv("DPGO_SPD_DUMP")) {
+  if (settings().spd_dump) {
     spd_profile(d_, st_, Ltt_, T1_.p);
     if (Lrr_.F.n > 0) spd_profile(d_, st_, Lrr_, T1_.p);
     HIP_CHECK(hipMemsetAsync(T1_.p, 0, sizeof(double) * nown, st_));
@@ -938,8 +931,8 @@ int Group::refactor_tt() {
   SetupClock clk;
   // Rescale::Dynamic re-factors G_tt every few iterations: the numeric phase keeps its device state, and the values it
   // reads stay on the GPU where k_rescale_apply rewrites the diagonal (att_pos_: where each pose's diagonal entry is)
-  const bool keep = dynamic() && env_int("DPGO_RESCALE_HOST", 0) == 0 && env_int("DPGO_SPD_DEVICE_PANELS", 1) != 0 &&
-                    env_int("DPGO_SPD_HOST_FACTOR", 0) == 0;
+  const Settings &s = settings();
+  const bool keep = dynamic() && !s.rescale_host && s.spd_device_panels && !s.spd_host_factor;
   Ltt_.F.keep_numeric = keep;
   if (keep && att_pos_.n == 0) {
     std::vector<int> pos(std::max(Att.n, 1), 0);
@@ -957,8 +950,8 @@ int Group::refactor_tt() {
     // dependent block columns there -- 33 at the merged roots of the headline, two launches each -- is what a
     // refactorisation costs (5.29 -> 4.17 ms per iteration at the headline size; the cost model of
     // spd_factor knows solves only).
-    const int leaf = env_int("DPGO_SPD_LEAF_TT", keep ? 64 : 128), collapse = env_int("DPGO_SPD_COLLAPSE_TT", keep ? 1 : 0);
-    if (spd_factor(Att, Ltt_.F, leaf, collapse, 1, env_int("DPGO_SPD_DEVICE_PANELS", 1) != 0) != 0) return -1;
+    const int leaf = s.spd_leaf_tt.value_or(keep ? 64 : 128), collapse = s.spd_collapse_tt.value_or(keep ? 1 : 0);
+    if (spd_factor(Att, Ltt_.F, leaf, collapse, 1, s.spd_device_panels) != 0) return -1;
   }
   clk.lap("G_tt: ordering + symbolic + numeric factor");
   warn_conditioning("G_tt", Ltt_.F);
@@ -1073,8 +1066,7 @@ void Group::check_tt_verdict(bool wait) const {
   if (!tt_verdict_pending_) return;
   tt_verdict_pending_ = false;
   // (DPGO_DEBUG_FAIL_REFACTOR=1, a test hook: the verdict counts as "not positive definite")
-  static const bool forced = env_int("DPGO_DEBUG_FAIL_REFACTOR", 0) != 0;
-  if (spd_refactor_finish(const_cast<SpdFactor &>(Ltt_.F), wait) != 0 || forced) {
+  if (spd_refactor_finish(const_cast<SpdFactor &>(Ltt_.F), wait) != 0 || settings().debug_fail_refactor) {
     failed_ = true;
     fprintf(stderr, "[dpgo_amd] ERROR: G_tt is not positive definite after a rescale; the group cannot go on (create a new one).\n");
     throw DeviceError("G_tt is not positive definite after a rescale");
@@ -1176,8 +1168,7 @@ void Group::check_gate(bool host_common) {
 // update()'s closing reduction left for the next refinement's k_cg_scal_begin (group.h: UpdLazy): eager launches of the fused
 // sequence only (a replayed segment is a fixed list of launches)
 bool Group::lazy_update_reduce() const {
-  static const bool on = env_int("DPGO_LAZY_UPDATE_REDUCE", 1) != 0;   // (A/B hook)
-  return on && fused_ && keep_gx() && !star_ && !capturing_ && !iter_graph_wanted();
+  return settings().lazy_update_reduce && fused_ && keep_gx() && !star_ && !capturing_ && !iter_graph_wanted();
 }
 
 void Group::flush_pending_tail() {
@@ -1191,7 +1182,7 @@ void Group::flush_pending_tail() {
 // Segments of an iteration as graph replays (group.h)
 // ---------------------------------------------------------------------------
 bool Group::iter_graph_wanted() const {
-  static const int force = env_int("DPGO_ITER_GRAPH", -1);
+  const int force = settings().iter_graph.value_or(-1);
   if (graphs_broken_ || force == 0 || prof_enabled()) return false;   // (never while launches are timed)
   if (force == 1) return true;
   // Where a segment streams gigabytes (the headline's eight nodes on one GPU) the host is never what bounds it, and its
@@ -1207,7 +1198,7 @@ bool Group::iter_graph_wanted() const {
 // cg_graph_wanted.)
 void Group::host_bound_tick() {
   if (host_bound_ || ++win_iters_ < 32) return;
-  static const double below = getenv("DPGO_HOST_BOUND_BELOW") ? atof(getenv("DPGO_HOST_BOUND_BELOW")) : 0.40;   // (test hook)
+  const double below = settings().host_bound_below;
   // (round 6: ... and at least half of its waits found the flag already raised -- the GPU had been waiting for the HOST.  A host
   // that enqueues ahead of the GPU's decisions -- SpecUpdate -- spends less of its time waiting without being the slower side)
   const bool late = below >= 1.0 || 2 * win_nlate_ >= win_nwait_;
@@ -1417,7 +1408,7 @@ void Group::wait_flag(unsigned long long seq) {
   }
   // (debug hook: a host that comes late to every read-back -- the stream runs ahead of it by that much; the results must not
   // depend on it, tests/test_gpu_parity.py)
-  static const int late_us = [] { const char *e = getenv("DPGO_DEBUG_LATE_HOST_US"); return e ? atoi(e) : 0; }();
+  const int late_us = settings().debug_late_host_us;
   if (late_us > 0) {
     const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(late_us);
     while (std::chrono::steady_clock::now() < until) __builtin_ia32_pause();
@@ -1526,7 +1517,7 @@ static void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec) {
   HIP_CHECK(hipEventCreate(&e1));
   double tot_us = 0, tot_mb = 0;
   unsigned long long *trace = nullptr;
-  if (getenv("DPGO_SPD_TRACE")) {
+  if (settings().spd_trace) {
     size_t most = 1;
     for (const auto &v : S.fwd_levels) most = std::max(most, (size_t)(v.nwide + v.nnarrow));
     for (const auto &v : S.bwd_levels) most = std::max(most, (size_t)(v.nwide + v.nnarrow));
@@ -1986,8 +1977,7 @@ int Group::unpack_recv(const double *dev_gathered, hipStream_t st) {
 // no inter-edge pass); -1: not taken, the caller unpacks as before.
 int Group::set_pending_recv(const double *buf, int count, const int *dst_dev, const int *src_dev) {
   flush_pending_recv();
-  static const bool lazy = env_int("DPGO_LAZY_UNPACK", 1) != 0;   // (A/B hook)
-  if (!lazy || !fused_ || opt_.loss == 0 || star_ || count <= 0 || e_rec_host_.empty()) return -1;
+  if (!settings().lazy_unpack || !fused_ || opt_.loss == 0 || star_ || count <= 0 || e_rec_host_.empty()) return -1;
   if (recv_key_ != dst_dev || recv_count_ != count || recv_key_gen_ != recv_gen_) {
     std::vector<int> dst(count), src(count), nsrc((size_t)std::max(P1_, 1), -1);
     HIP_CHECK(hipMemcpy(dst.data(), dst_dev, sizeof(int) * count, hipMemcpyDeviceToHost));
@@ -2299,8 +2289,7 @@ int Group::update(const std::vector<int> &locals_in) {
   for (int a : locals) ((res_[a].iters == 0 || star_) ? first : later).push_back(a);
   // the closing read-back is deferred to the next reader (finish_update) where there is exactly one of them and nothing
   // depends on it at once: not for AMM-PGO* (the master decides on the sums right away) nor with Dynamic rescale
-  static const bool defer_enabled = env_int("DPGO_DEFER_UPDATE", 1) != 0;
-  const bool can_defer = defer_enabled && !star_ && !dynamic() && (first.empty() != later.empty());
+  const bool can_defer = settings().defer_update && !star_ && !dynamic() && (first.empty() != later.empty());
   // `launches`: the rest of the surrogate build of the nodes in `set`, ending with the reduction of its sums -- a branch-free
   // sequence, replayed from a captured graph where the host's launch rate would bound it (segment()); it may be empty when
   // the caller has already enqueued everything but the reduction
@@ -2666,8 +2655,7 @@ int Group::amm(const std::vector<int> &locals) {
   };
   // (where the refinement starts unasked -- below -- and segments are replayed, the two sequences are ONE segment: the
   // head of the iteration rides at the front of the refinement's head, one graph launch and one start-up less)
-  static const bool spec_on = env_int("DPGO_SPEC_REFINE", 1) != 0;
-  const bool speculate = spec_on && spec_refined_ && (int)locals.size() == num_local() && pending_update_ && !star_ && !dynamic();
+  const bool speculate = settings().spec_refine && spec_refined_ && (int)locals.size() == num_local() && pending_update_ && !star_ && !dynamic();
   // (the closure below refers to this frame: whatever happens -- an exception on its way to the C ABI before a segment has
   // taken it -- it does not outlive the frame)
   struct DropHead {

@@ -26,6 +26,7 @@
 #include "assemble.h"
 #include "graph.h"
 #include "kernels.h"
+#include "settings.h"
 #include "spd.h"
 
 namespace dpgo {
@@ -110,7 +111,7 @@ struct DevBuf {
 
 // DPGO_SETUP_TIMING=1: wall time of the set-up phases on stderr
 struct SetupClock {
-  const bool on = getenv("DPGO_SETUP_TIMING") != nullptr;
+  const bool on = settings().setup_timing;
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void lap(const char *what) {
     if (!on) return;
@@ -351,7 +352,7 @@ class Group {
   bool capture_cap_warned_ = false;
   // DPGO_HOST_TIMING=1: where the host's time goes (seconds in hipGraphLaunch, in eagerly launched segments, in waits), on
   // stderr when the group goes
-  bool host_timing_ = getenv("DPGO_HOST_TIMING") != nullptr;
+  bool host_timing_ = settings().host_timing;
   double t_graph_launch_ = 0, t_eager_seg_ = 0, t_wait_ = 0;
   long n_wait_ = 0, holes_total_ = 0, wait_hist_[6] = {0, 0, 0, 0, 0, 0};   // waits of < 50 us, < 200 us, < 1 ms, < 5 ms, < 50 ms, longer
   // the sequence number the next flag-raising launch carries: a fresh one, or 0 under capture (the kernel then takes the

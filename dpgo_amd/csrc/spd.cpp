@@ -3,6 +3,7 @@
 #include <omp.h>
 
 #include "graph.h"
+#include "settings.h"
 
 #include <algorithm>
 #include <cmath>
@@ -335,8 +336,8 @@ struct Dissector {
     // Every cut that leaves both sides at least `window` of the vertices is tried, in the level structures of both
     // ends of the pseudo-diameter; the smallest cover wins.  window = 0.45 (measured: 0.3 gives 2 % fewer entries but
     // 20 % more tree levels, i.e. slower solves; more than two roots change nothing).
-    static const double window = [] { const char *e = getenv("DPGO_ND_WINDOW"); return e ? atof(e) : 0.45; }();
-    static const int nroots = [] { const char *e = getenv("DPGO_ND_ROOTS"); return e ? atoi(e) : 2; }();
+    const double window = settings().nd_window;
+    const int nroots = settings().nd_roots;
     const double total = (double)order.size();
     std::vector<int> sep, lo, hi, best_cover, lp;
     size_t best_size = (size_t)-1;
@@ -370,22 +371,9 @@ struct Dissector {
     // Spectral candidate (Pothen, Simon, Liou 1990): split along the Fiedler vector of the subgraph, again with a
     // minimum vertex cover of the cut as the separator.  On lattice-like graphs it finds the flat cross-sections
     // that level sets grown from a corner (diagonal planes) miss.
-    static const int spectral = [] { const char *e = getenv("DPGO_ND_SPECTRAL"); return e ? atoi(e) : 1; }();
-    if (spectral && order.size() >= 64) {
-      static const std::vector<int> depths = [] {
-        std::vector<int> d;
-        const char *e = getenv("DPGO_ND_LANCZOS");
-        std::string str = e ? e : "40,60,90,120";
-        for (size_t p = 0; p < str.size();) {
-          size_t c = str.find(',', p);
-          if (c == std::string::npos) c = str.size();
-          d.push_back(atoi(str.substr(p, c - p).c_str()));
-          p = c + 1;
-        }
-        return d;
-      }();
+    if (settings().nd_spectral && order.size() >= 64) {
       std::vector<std::vector<double>> fvs;
-      fiedler(order, depths, fvs);
+      fiedler(order, settings().nd_lanczos, fvs);
       std::vector<int> perm(order.size());
       for (const std::vector<double> &fv : fvs)
       for (double q : {0.5, 0.49, 0.51, 0.48, 0.52, 0.47, 0.53, 0.46, 0.54, 0.45, 0.55}) {
@@ -449,7 +437,7 @@ struct Dissector {
 // empty it is computed here and stored there.
 static double setup_lap(double &t0, const char *what) {   // DPGO_SETUP_TIMING=1: phase times on stderr
   const double t = omp_get_wtime();
-  if (getenv("DPGO_SETUP_TIMING")) fprintf(stderr, "[setup]   spd: %-37s %8.3f s\n", what, t - t0);
+  if (settings().setup_timing) fprintf(stderr, "[setup]   spd: %-37s %8.3f s\n", what, t - t0);
   t0 = t;
   return t;
 }
@@ -716,7 +704,7 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
 #ifndef DPGO_NO_DEVICE
   {
     int ndev = 0;
-    device_numeric = !getenv("DPGO_SPD_HOST_FACTOR") && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+    device_numeric = !settings().spd_host_factor && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
   }
 #endif
   if (!(device_numeric && F.keep_device)) {   // (the device numeric phase allocates the host copies it needs itself)
@@ -897,9 +885,9 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
 #ifndef DPGO_NO_DEVICE
   {
     int ndev = 0;
-    if (!getenv("DPGO_SPD_HOST_FACTOR") && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
+    if (!settings().spd_host_factor && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
       double flops = 0, ms = 0;
-      const bool report = getenv("DPGO_SPD_DUMP") != nullptr;
+      const bool report = settings().spd_dump;
       if (spd_factor_numeric_device(A, F, children, report ? &flops : nullptr, report ? &ms : nullptr) != 0) return -1;
       if (report)
         fprintf(stderr, "[spd] device factorisation: %.2f GFLOP in the MFMA tile kernel, %.2f ms there = %.1f TFLOP/s fp64\n",
@@ -954,7 +942,7 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
 int spd_refactor(const CsrMatrix &A, SpdFactor &F) {
 #ifndef DPGO_NO_DEVICE
   int ndev = 0;
-  if (F.n == A.n && (int)F.children.size() == F.nfronts && !getenv("DPGO_SPD_HOST_FACTOR") &&
+  if (F.n == A.n && (int)F.children.size() == F.nfronts && !settings().spd_host_factor &&
       hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0)
     return spd_factor_numeric_device(A, F, F.children, nullptr, nullptr);
 #endif
@@ -965,7 +953,7 @@ int spd_refactor(const CsrMatrix &A, SpdFactor &F) {
 
 int spd_factor(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int block, bool keep_device) {
   std::vector<TreeNode> tree;   // dissected once, reused for every merge depth tried below
-  if (const char *e = getenv("DPGO_SPD_COLLAPSE")) collapse = atoi(e);
+  collapse = settings().spd_collapse.value_or(collapse);
   if (collapse <= 0) {
     // choose the number of merged levels from the measured cost of one sweep on MI355X: a level costs
     // ~12 us whatever it holds (launch, gather chain, drain) plus its bytes at ~7 TB/s.  (With the 3 TB/s of a whole

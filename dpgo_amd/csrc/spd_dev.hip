@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "settings.h"
 #include "spd.h"
 
 namespace dpgo {
@@ -823,7 +824,7 @@ int SpdNumericCtx::build(const CsrMatrix &A, const SpdFactor &F, const std::vect
   // the children of a front in slot order with the inverse of their maps (k_fa_extend_rows), if every map ascends
   std::vector<ExtendRow> xrows;
   std::vector<int> xrow_ptr(nt + 1, 0), inv;
-  extend_by_rows = getenv("DPGO_SPD_EXTEND_SLOTS") == nullptr;
+  extend_by_rows = !settings().spd_extend_slots;
   for (int f = 0; f < nt && extend_by_rows; f++) {
     xrow_ptr[f] = (int)xrows.size();
     for (int c : children[f]) {
@@ -967,15 +968,14 @@ int SpdNumericCtx::factor(SpdFactor &F, const double *aval_host, double *flops_o
       }
       return 0;
     };
-    static const bool ll_enabled = getenv("DPGO_SPD_LEFT_LOOKING") ? atoi(getenv("DPGO_SPD_LEFT_LOOKING")) != 0 : true;
     // right-looking levels: up to this many workgroups factor the diagonal block themselves, beside their rows' loads (one
     // launch per block column instead of two); beyond, one wave per front does it first (measured on the leaf level of the
     // headline's G_tt, 1 256 workgroups: 63-110 us fused against 22 + 39 us in two launches -- three workgroups per CU
     // each bring a factoring wave)
-    static const long long fuse_limit = getenv("DPGO_SPD_FUSE_POTRF_WGS") ? atoll(getenv("DPGO_SPD_FUSE_POTRF_WGS")) : 768;
+    const long long fuse_limit = settings().spd_fuse_potrf_wgs;
     // (measured in round 5 with the limit raised so that the leaf level -- 1 256 workgroups at the headline -- runs
     // left-looking too: a Dynamic iteration goes from 5.15 to 5.47 ms)
-    const bool left_looking = ll_enabled && (long long)((max_m + 255) / 256) * nf <= 768;
+    const bool left_looking = settings().spd_left_looking && (long long)((max_m + 255) / 256) * nf <= 768;
     for (int sb = 0; sb < max_w; sb += SB) {
       const int se = sb + SB;
       for (int kb = sb; kb < std::min(se, max_w); kb += NB) {

@@ -57,9 +57,7 @@ struct NodeTnt {
 // city10000 -- from the start for groups of at least two nodes and at most 40 000 poses, whose steps are bound by the host's
 // launch rate.  DPGO_CG_GRAPH=0 keeps just these eager (A/B hook), DPGO_ITER_GRAPH=0 everything.
 bool Group::cg_graph_wanted() const {
-  static const int force = [] { const char *e = getenv("DPGO_CG_GRAPH"); return e ? atoi(e) : -1; }();
-  static const int iter_force = [] { const char *e = getenv("DPGO_ITER_GRAPH"); return e ? atoi(e) : -1; }();
-  if (force == 0 || iter_force == 0 || graphs_broken_ || prof_enabled()) return false;
+  if (!settings().cg_graph || settings().iter_graph == 0 || graphs_broken_ || prof_enabled()) return false;
   if (iter_graph_wanted()) return true;
   return P0_ <= 40000 && num_local() >= 2;
 }

@@ -113,10 +113,11 @@ def test_spd_solver_disconnected_and_tiny():
     np.testing.assert_allclose(A @ X, B, atol=1e-12)
 
 
-def test_spd_solver_large_components_and_separator_quality():
+def test_spd_solver_large_components_and_separator_quality_in_child_process(tmp_path):
     """Two large disconnected lattice Laplacians (the situation of a group with several nodes): the components are
     dissected in parallel with minimum-vertex-cover / spectral separators; the solve is exact, and the top separator
-    of a 16 x 16 x 12 lattice is close to its smallest cross-section (16 x 12 = 192), not a diagonal level set."""
+    of a 16 x 16 x 12 lattice is close to its smallest cross-section (16 x 12 = 192), not a diagonal level set.  The
+    separator is looked at with DPGO_SPD_COLLAPSE=1 in a child process: the library reads its settings once per process."""
     def lattice(nx, ny, nz):
         idx = np.arange(nx * ny * nz).reshape(nx, ny, nz)
         e = [(idx[:-1].ravel(), idx[1:].ravel()), (idx[:, :-1].ravel(), idx[:, 1:].ravel()),
@@ -130,11 +131,13 @@ def test_spd_solver_large_components_and_separator_quality():
     B = rng.standard_normal((A.shape[0], 3))
     X = dpgo_amd.spd_solve_host(A, B, leaf=64)
     np.testing.assert_allclose(A @ X, B, atol=1e-9)
-    os.environ["DPGO_SPD_COLLAPSE"] = "1"
-    try:
-        _, _, max_front = dpgo_amd.spd_stats(lattice(16, 16, 12), 64)
-    finally:
-        del os.environ["DPGO_SPD_COLLAPSE"]
+    import subprocess
+    import sys
+    path = str(tmp_path / "lattice.npz")
+    sp.save_npz(path, lattice(16, 16, 12))
+    code = ("import sys, scipy.sparse as sp; sys.path.insert(0, %r); import dpgo_amd; "
+            "print(dpgo_amd.spd_stats(sp.load_npz(sys.argv[1]), 64)[2])" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    max_front = int(subprocess.check_output([sys.executable, "-c", code, path], env=dict(os.environ, DPGO_SPD_COLLAPSE="1")))
     assert max_front <= 1.35 * 192
 
 
