@@ -11,6 +11,8 @@ inner step of ``dist_pgo``:
     initialize/update/iterate/communicate           same names, return 0 / -1
     results()               DPGO_types.h:204-322  .results() (scalars), .Xk(), .Xak()
   dist_pgo driver loop      dist_pgo.cpp:446-531  DistPGO
+  DPGO::PCM                 PCM.h:10-71           PCM(device).update(graph, alpha, beta, X) / solve_exact / ...;
+                                                  pcm_inliers(graph, X) -> keep mask, Graph.filter_edges(keep)
 
 All compute runs in hand-written HIP kernels behind the C ABI of
 include/dpgo_amd.h.  There is NO CPU fallback: creating a NodeGroup without a
@@ -197,6 +199,16 @@ SYMBOLS = {
     "dpgo_debug_spd_stats": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.POINTER(C.c_long), _IP, _IP]),
     "dpgo_debug_p2p_plan": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
+    "dpgo_pcm_options_default": (None, [C.c_void_p]),
+    "dpgo_pcm_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "dpgo_pcm_free": (None, [C.c_void_p]),
+    "dpgo_pcm_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP, C.c_int, C.c_void_p]),
+    "dpgo_pcm_measurements": (C.c_int, [C.c_void_p, _IP]),
+    "dpgo_pcm_adjacency": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dpgo_pcm_errors": (C.c_int, [C.c_void_p, _DP]),
+    "dpgo_pcm_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dpgo_max_clique": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "dpgo_graph_filter_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
 }
 
 
@@ -342,6 +354,17 @@ class Graph:
         shape = {"G": (D1 * n0, D1 * n0), "D": (D1 * n0, D1 * n0), "S": (D1 * n0, D1 * (n0 + n1))}.get(
             name, (D1 * (n0 + n1), D1 * (n0 + n1)))
         return sp.coo_matrix((v, (r, c)), shape=shape).tocsr()
+
+    def filter_edges(self, keep):
+        """The same poses and partition with only the edges where keep (length num_edges) is true, in order
+        (dpgo_graph_filter_edges): how the closures PCM rejected are dropped before building groups."""
+        keep = np.ascontiguousarray(np.asarray(keep, bool).astype(np.uint8))
+        if keep.shape != (self.num_edges,):
+            raise ValueError("keep must have one entry per edge (%d)" % self.num_edges)
+        h = C.c_void_p()
+        if lib().dpgo_graph_filter_edges(self._h, keep.ctypes.data_as(C.c_void_p), C.byref(h)) != 0:
+            raise ValueError("filter_edges failed (no edge kept?)")
+        return Graph(h)
 
     def node_proximal(self, node, opt):
         n0 = self.node_sizes(node)[0]
@@ -848,3 +871,110 @@ class DPGOStar:
         X = np.zeros(((self.graph.d + 1) * self.graph.num_poses, self.graph.d), order="F")
         self.group.scatter_global(X)
         return X
+
+
+class PCMOptions(C.Structure):
+    """DPGO::PCM::Options (C++/DPGO/include/DPGO/PCM.h:13-19)."""
+    _fields_ = [("tolerance", C.c_double), ("weighted", C.c_int)]
+
+
+class PCM:
+    """DPGO::PCM (C++/DPGO/include/DPGO/PCM.h, C++/DPGO/src/PCM.cpp:5-235): pairwise consistency of the measurements
+    between two nodes, tested on the GPU (fp64), and the maximum clique of consistent ones (host).  update() takes the
+    graph and the GLOBAL iterate X ((d+1)N x d) instead of the reference's measurements + index; measurements() are
+    edge indices of the graph.  There is no CPU path: constructing one without a HIP device raises."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        if lib().dpgo_pcm_create(int(device), C.byref(h)) != 0:
+            raise RuntimeError("dpgo_pcm_create failed (no HIP device?); there is no CPU path")
+        self._h = h
+        self.m = 0
+        self.tolerance, self.weighted = 0.2, False
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().dpgo_pcm_free(self._h)
+            self._h = None
+
+    def update(self, graph, alpha, beta, X, tolerance=0.2, weighted=False):
+        """PCM::update: returns m, the number of alpha-beta measurements (-1 raises ValueError)."""
+        X, ld = _fcol(X)
+        o = PCMOptions(float(tolerance), int(bool(weighted)))
+        m = lib().dpgo_pcm_update(self._h, graph._h, int(alpha), int(beta), _dp(X), ld, C.byref(o))
+        if m < 0:
+            self.m = 0
+            raise ValueError("PCM.update(%d, %d) failed" % (alpha, beta))
+        self.m, self.tolerance, self.weighted = m, float(tolerance), bool(weighted)
+        return m
+
+    def measurements(self):
+        ids = np.zeros(max(self.m, 1), np.int32)
+        lib().dpgo_pcm_measurements(self._h, _ip(ids))
+        return ids[:self.m]
+
+    def adjacency(self):
+        """PCM::adjancecy_matrix: m x m 0/1 (uint8), symmetric, diagonal 1."""
+        A = np.zeros((self.m, self.m), np.uint8)
+        if self.m and lib().dpgo_pcm_adjacency(self._h, A.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("dpgo_pcm_adjacency failed")
+        return A
+
+    def errors(self):
+        """Debug: the m x m pair errors (m <= 4096)."""
+        E = np.zeros((self.m, self.m))
+        if self.m and lib().dpgo_pcm_errors(self._h, _dp(E)) != 0:
+            raise RuntimeError("dpgo_pcm_errors failed (m = %d > 4096?)" % self.m)
+        return E
+
+    def _solve(self, exact):
+        out = np.zeros(max(self.m, 1), np.uint8)
+        if lib().dpgo_pcm_solve(self._h, int(exact), out.ctypes.data_as(C.c_void_p)) < 0:
+            raise RuntimeError("dpgo_pcm_solve failed")
+        return out[:self.m].astype(bool)
+
+    def solve_exact(self):
+        """PCM::solveExact -> results(): one bool per measurement (a maximum clique)."""
+        return self._solve(True)
+
+    def solve_heuristic(self):
+        """PCM::solveHeuristic -> results(): one bool per measurement (a clique)."""
+        return self._solve(False)
+
+
+def max_clique(A, exact=True):
+    """Host max clique (dpgo_max_clique) of the 0/1 matrix A (A | A^T used, diagonal ignored): bool per vertex."""
+    A = np.ascontiguousarray(np.asarray(A) != 0, np.uint8)
+    m = A.shape[0]
+    if A.shape != (m, m):
+        raise ValueError("A must be square")
+    out = np.zeros(max(m, 1), np.uint8)
+    if lib().dpgo_max_clique(m, A.ctypes.data_as(C.c_void_p), int(bool(exact)), out.ctypes.data_as(C.c_void_p)) < 0:
+        raise RuntimeError("dpgo_max_clique failed")
+    return out[:m].astype(bool)
+
+
+def pose_nodes(graph):
+    """Node of every global pose id under the graph's contiguous partition."""
+    off = np.asarray([graph.node_offset(a) for a in range(graph.num_nodes)])
+    return np.searchsorted(off, np.arange(graph.num_poses), side="right") - 1
+
+
+def pcm_inliers(graph, X, tolerance=0.2, weighted=False, exact=True, device=0):
+    """PCM over every pair of nodes that shares edges: a keep-mask over all edges of the graph (intra-node edges
+    are always kept; an inter-node edge is kept when it is in the clique of its pair).  graph.filter_edges(mask)
+    gives the graph without the rejected closures."""
+    I, J = graph.edges()[:2]
+    node = pose_nodes(graph)
+    ni, nj = node[I], node[J]
+    keep = np.ones(graph.num_edges, bool)
+    inter = ni != nj
+    pairs = sorted(set(zip(np.minimum(ni, nj)[inter].tolist(), np.maximum(ni, nj)[inter].tolist())))
+    pcm = PCM(device)
+    for a, b in pairs:
+        if pcm.update(graph, a, b, X, tolerance, weighted) == 0:
+            continue
+        ids = pcm.measurements()
+        inl = pcm.solve_exact() if exact else pcm.solve_heuristic()
+        keep[ids[~inl]] = False
+    return keep

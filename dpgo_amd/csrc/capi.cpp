@@ -13,6 +13,7 @@
 
 #include "comm.h"
 #include "group.h"
+#include "pcm.h"
 
 namespace dpgo {
 int chordal_initialization(const Graph &g, double *X, int ld);
@@ -778,6 +779,121 @@ int dpgo_group_dist_chordal_initialization(dpgo_group_t *h, const dpgo_dchordal_
       *num_objectives = (int)obj.size();
     }
     return rc;
+  });
+}
+
+// ---- PCM (C++/DPGO/include/DPGO/PCM.h, C++/DPGO/src/PCM.cpp:5-235) ------------------------------------------------
+struct dpgo_pcm {
+  dpgo::Pcm *p = nullptr;
+};
+
+void dpgo_pcm_options_default(dpgo_pcm_options_t *o) {
+  if (!o) return;
+  o->tolerance = 0.2;   // PCM.h:14
+  o->weighted = 0;      // PCM.h:15
+}
+
+int dpgo_pcm_create(int device, dpgo_pcm_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  return guarded([&] {
+    auto *h = new dpgo_pcm();
+    try {
+      h->p = new dpgo::Pcm(device);
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+    return 0;
+  });
+}
+
+void dpgo_pcm_free(dpgo_pcm_t *h) {
+  if (!h) return;
+  delete h->p;
+  delete h;
+}
+
+// PCM::update (PCM.cpp:5-235)
+int dpgo_pcm_update(dpgo_pcm_t *h, const dpgo_graph_t *g, int alpha, int beta, const double *X, int ld,
+                    const dpgo_pcm_options_t *opts) {
+  if (!h || !g) return -1;
+  dpgo_pcm_options_t o;
+  dpgo_pcm_options_default(&o);
+  if (opts) o = *opts;
+  return guarded([&] { return h->p->update(g->g, alpha, beta, X, ld, o.tolerance, o.weighted != 0); });
+}
+
+// PCM::measurements (PCM.h:39), as edge indices of the graph
+int dpgo_pcm_measurements(const dpgo_pcm_t *h, int *edge_ids) {
+  if (!h) return -1;
+  if (edge_ids) std::copy(h->p->edge_ids.begin(), h->p->edge_ids.end(), edge_ids);
+  return h->p->m;
+}
+
+// PCM::adjancecy_matrix (PCM.h:37)
+int dpgo_pcm_adjacency(const dpgo_pcm_t *h, unsigned char *dense) {
+  if (!h || (!dense && h->p->m > 0)) return -1;
+  const int m = h->p->m, W = (m + 63) / 64;
+  const uint64_t *b = h->p->bits.data();
+  for (int r = 0; r < m; r++)
+    for (int c = 0; c < m; c++) dense[(size_t)r * m + c] = (b[(size_t)r * W + c / 64] >> (c % 64)) & 1;
+  return 0;
+}
+
+int dpgo_pcm_errors(dpgo_pcm_t *h, double *E) {
+  if (!h) return -1;
+  return guarded([&] { return h->p->errors(E); });
+}
+
+// PCM::solveExact / solveHeuristic (PCM.cpp:232-246)
+int dpgo_pcm_solve(dpgo_pcm_t *h, int exact, unsigned char *inlier) {
+  if (!h || (!inlier && h->p->m > 0)) return -1;
+  return guarded([&] {
+    std::vector<uint8_t> out;
+    const int m = h->p->m;
+    const int n = exact ? dpgo::max_clique_exact(m, h->p->bits.data(), out) : dpgo::max_clique_heuristic(m, h->p->bits.data(), out);
+    std::copy(out.begin(), out.end(), inlier);
+    return n;
+  });
+}
+
+// ::PCM::PattabiramanMaxCliqueSolver{Exact,Heuristic}::find_max_clique (C++/PCM/include/PCM/PCM.hpp:29-66) on a dense
+// 0/1 matrix, host only
+int dpgo_max_clique(int m, const unsigned char *dense, int exact, unsigned char *out) {
+  if (m < 0 || (m > 0 && (!dense || !out))) return -1;
+  if (m > dpgo::PCM_MAX_M) return -1;
+  return guarded([&] {
+    const int W = (m + 63) / 64;
+    std::vector<uint64_t> bits((size_t)m * W, 0);
+    for (int r = 0; r < m; r++)
+      for (int c = 0; c < m; c++)
+        if (r == c || dense[(size_t)r * m + c] || dense[(size_t)c * m + r]) bits[(size_t)r * W + c / 64] |= 1ull << (c % 64);
+    std::vector<uint8_t> o;
+    const int n = exact ? dpgo::max_clique_exact(m, bits.data(), o) : dpgo::max_clique_heuristic(m, bits.data(), o);
+    std::copy(o.begin(), o.end(), out);
+    return n;
+  });
+}
+
+int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dpgo_graph_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!g || !keep) return -1;
+  return guarded([&] {
+    auto *f = new dpgo_graph();
+    f->g.d = g->g.d;
+    f->g.num_poses = g->g.num_poses;
+    for (size_t e = 0; e < g->g.all.size(); e++)
+      if (keep[e]) f->g.all.push_back(g->g.all[e]);
+    if (dpgo::partition(f->g, g->g.num_nodes) != 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: dpgo_graph_filter_edges: no edge kept.\n");
+      delete f;
+      return -1;
+    }
+    *out = f;
+    return 0;
   });
 }
 

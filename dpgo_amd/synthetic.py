@@ -178,3 +178,47 @@ def ladder(d=3, seed=7):
     t = rng.standard_normal((M, d))
     return dict(d=d, num_poses=N, num_nodes=nn, I=I, J=J, R=R, t=t, kappa=rng.uniform(1.0, 100.0, M),
                 tau=rng.uniform(1.0, 100.0, M), outlier=np.zeros(M, bool))
+
+
+def two_node(m, poses_per_node=256, seed=1, sigma_t=0.05, sigma_r=0.02, outlier_frac=0.1, extent=10.0):
+    """A two-node SE(3) graph with m inter-node edges (the PCM test and benchmark instance).  Ground-truth poses:
+    random rotations, translations uniform in [0, extent)^3; node 0 holds poses [0, P), node 1 [P, 2P) (the
+    contiguous partition with num_nodes = 2).  Edges: an odometry chain inside each node, then m cross edges between
+    random poses of the two nodes, every second one written from node 1 to node 0; their relative poses carry
+    N(0, sigma_t^2) translation and exp(N(0, sigma_r^2)) rotation noise, and `outlier_frac` of them are random.
+    Returns the dict of grid() plus Rg, tg (the ground truth)."""
+    rng = np.random.default_rng(seed)
+    P = poses_per_node
+    N = 2 * P
+    Rg = _random_rotations(rng, N)
+    tg = rng.uniform(0, extent, (N, 3))
+    chain = [(k, k + 1) for k in range(P - 1)] + [(P + k, P + k + 1) for k in range(P - 1)]
+    a = rng.integers(0, P, m)
+    b = rng.integers(P, N, m)
+    flip = (np.arange(m) % 2) == 1
+    I = np.concatenate([np.array([c[0] for c in chain]), np.where(flip, b, a)])
+    J = np.concatenate([np.array([c[1] for c in chain]), np.where(flip, a, b)])
+    M = len(I)
+    R = np.einsum("eba,ebc->eac", Rg[I], Rg[J])                       # R_i^T R_j
+    t = np.einsum("eba,eb->ea", Rg[I], tg[J] - tg[I])                 # R_i^T (t_j - t_i)
+    R = R @ _exp_so3(sigma_r * rng.standard_normal((M, 3)))
+    t = t + sigma_t * rng.standard_normal((M, 3))
+    outlier = np.zeros(M, bool)
+    n_out = int(round(outlier_frac * m))
+    if n_out:
+        sel = len(chain) + rng.choice(m, n_out, replace=False)
+        outlier[sel] = True
+        R[sel] = _random_rotations(rng, n_out)
+        t[sel] = rng.uniform(-extent, extent, (n_out, 3))
+    return dict(d=3, num_poses=N, I=I, J=J, R=R, t=t, kappa=np.full(M, 200.0), tau=np.full(M, 100.0),
+                outlier=outlier, Rg=Rg, tg=tg)
+
+
+def global_X(R, t):
+    """The library's global layout ((d+1)N x d) of poses R (N x d x d), t (N x d): rows [0, N) t_i, rows
+    [N + d i, N + d i + d) R_i^T."""
+    N, d = t.shape
+    X = np.zeros(((d + 1) * N, d))
+    X[:N] = t
+    X[N:] = np.swapaxes(R, 1, 2).reshape(N * d, d)
+    return X

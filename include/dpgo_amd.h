@@ -296,6 +296,43 @@ int dpgo_group_solver_stats(const dpgo_group_t *grp, long *nnz_tt, long *nnz_rr,
  * segments replayed, graphs captured, segments launched eagerly since the group was created. */
 int dpgo_group_graph_stats(const dpgo_group_t *grp, long *replays, long *captures, long *eager);
 
+/* ---- PCM: pairwise consistency maximisation (outlier rejection for inter-node loop closures) ----------------
+ * DPGO::PCM -- C++/DPGO/include/DPGO/PCM.h, C++/DPGO/src/PCM.cpp:5-235.  For two nodes alpha != beta the measurement
+ * list is the graph's alpha-beta edges (either direction) in graph edge order (dpgo_graph_edges order); X is the
+ * GLOBAL iterate ((d+1)N x d, column-major, leading dimension ld), not the reference's two-node stacked X with its
+ * index / num_s offsets (both pick the same poses).  The m x m consistency test runs on the device in fp64; the max
+ * clique on the host.  Deviations: alpha == beta or a node out of range returns -1 (the reference would run on
+ * alpha's intra-node edges); nothing calls exit(); rounding is not Eigen's, so only decisions away from the
+ * tolerance are promised to match. */
+typedef struct dpgo_pcm_options {
+  double tolerance;   /* PCM.h:14, 0.2 */
+  int weighted;       /* PCM.h:15, 0: kappa = tau = 1; 1: the pair's means of the edges' kappa and tau */
+} dpgo_pcm_options_t;
+typedef struct dpgo_pcm dpgo_pcm_t;
+void dpgo_pcm_options_default(dpgo_pcm_options_t *opt);
+/* PCM() (PCM.h:27-31) on HIP device `device`; -1 when there is no device (there is no CPU path). */
+int dpgo_pcm_create(int device, dpgo_pcm_t **out);
+void dpgo_pcm_free(dpgo_pcm_t *pcm);
+/* PCM::update (PCM.cpp:5-235): returns m (0 for a pair without common edges), -1 on error (alpha == beta, a node out
+ * of range, X NULL or ld < (d+1)N, m > 65536).  opts NULL: the defaults. */
+int dpgo_pcm_update(dpgo_pcm_t *pcm, const dpgo_graph_t *g, int alpha, int beta, const double *X, int ld,
+                    const dpgo_pcm_options_t *opts);
+/* PCM::measurements (PCM.h:39): the m measurements as edge indices of the graph */
+int dpgo_pcm_measurements(const dpgo_pcm_t *pcm, int *edge_ids);
+/* PCM::adjancecy_matrix (PCM.h:37): the m x m 0/1 matrix (symmetric, diagonal 1) */
+int dpgo_pcm_adjacency(const dpgo_pcm_t *pcm, unsigned char *dense);
+/* Debug: the m x m pair errors of PCM.cpp:226-228 (row-major, symmetric, diagonal 0); m <= 4096 */
+int dpgo_pcm_errors(dpgo_pcm_t *pcm, double *E);
+/* PCM::solveExact / solveHeuristic (PCM.cpp:232-246) -> results() (PCM.h:41): inlier[k] = 1 for the members of the
+ * clique found over the m measurements.  Returns the clique size. */
+int dpgo_pcm_solve(dpgo_pcm_t *pcm, int exact, unsigned char *inlier);
+/* Host only (no device): maximum clique (exact != 0) or the greedy heuristic on an m x m 0/1 matrix (row-major; the
+ * symmetric matrix A | A^T is used, the diagonal is ignored).  out[k] = 1 for the members; returns the size. */
+int dpgo_max_clique(int m, const unsigned char *dense, int exact, unsigned char *out);
+/* The same poses and partition as g with only the edges e for which keep[e] != 0 (in order): how a caller drops the
+ * closures PCM rejected before building groups.  -1 if no edge is kept. */
+int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dpgo_graph_t **out);
+
 /* ---- test hooks ------------------------------------------------------------------------- */
 /* Host: the assembled operator `name` in {"G","S","P","P0","Q","D"} of a node as COO triplets in
  * the REFERENCE row/column order.  Call with rows == NULL to get the count. */

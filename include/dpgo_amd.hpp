@@ -13,6 +13,9 @@
 //     initialize / update / iterate / communicate / receive / results / options
 //   vector<shared_ptr<DPGOHash>>   dist_pgo.cpp:96      DPGOHashGroup (the nodes one GPU hosts; batched calls)
 //   DPGOStar                       DPGOStar.h:13-61     DPGOStar (AMM-PGO*, all nodes in one group)
+//   PCM (outlier rejection)        PCM.h:10-71          PCM: update(alpha, beta, graph, global X, opts) instead of
+//                                                       (measurements, num_n, num_s, index, X); measurements() are
+//                                                       edge indices of the graph
 //
 // Return codes follow the reference: 0 ok, -1 error (a line on stderr).  Constructors throw
 // std::runtime_error (there is no CPU fallback: no HIP device => no group).
@@ -253,6 +256,78 @@ class DPGOStar {
  private:
   std::shared_ptr<Graph> graph_;
   std::unique_ptr<DPGOHashGroup> group_;
+};
+
+// Pairwise consistency maximisation (PCM.h:10-71, PCM.cpp:5-235): the consistency test of the alpha-beta measurements
+// runs on the GPU, the max clique on the host.  update() takes the graph and the GLOBAL iterate X ((d+1) N x d) instead
+// of the reference's measurements_t + num_n / num_s / index; measurements() are edge indices of the graph, and
+// adjancecy_matrix() (sic, the reference's name) is the m x m 0/1 matrix (symmetric, so row- or column-major alike).
+class PCM {
+ public:
+  struct Options {
+    Scalar tolerance = 0.2;
+    bool weighted = false;
+    Options() {}
+  };
+
+  explicit PCM(int device = 0) {
+    if (dpgo_pcm_create(device, &h_) != 0) throw std::runtime_error("dpgo_pcm_create failed (no HIP device); there is no CPU path");
+  }
+  ~PCM() { dpgo_pcm_free(h_); }
+  PCM(const PCM &) = delete;
+  PCM &operator=(const PCM &) = delete;
+
+  Scalar tolerance() const { return opts_.tolerance; }
+  bool weighted() const { return opts_.weighted; }
+  const std::vector<unsigned char> &adjancecy_matrix() const { return adjacency_; }
+  const std::vector<int> &measurements() const { return measurements_; }
+  const std::vector<bool> &results() const { return results_; }
+  int num_m() const { return num_m_; }
+
+  // 0 ok, -1 error (alpha == beta, a node out of range, X too small)
+  int update(int alpha, int beta, const Graph &graph, const Matrix &X, const Options &opts = Options()) {
+    reset();
+    dpgo_pcm_options_t o;
+    o.tolerance = opts.tolerance;
+    o.weighted = opts.weighted ? 1 : 0;
+    const int m = dpgo_pcm_update(h_, graph.handle(), alpha, beta, X.data(), X.rows(), &o);
+    if (m < 0) return -1;
+    opts_ = opts;
+    num_m_ = m;
+    measurements_.resize(m);
+    adjacency_.resize((size_t)m * m);
+    if (m > 0) {
+      dpgo_pcm_measurements(h_, measurements_.data());
+      dpgo_pcm_adjacency(h_, adjacency_.data());
+    }
+    return 0;
+  }
+  const std::vector<bool> &solveExact() const { return solve(1); }
+  const std::vector<bool> &solveHeuristic() const { return solve(0); }
+
+  int reset() {
+    opts_ = Options();
+    num_m_ = 0;
+    measurements_.clear();
+    adjacency_.clear();
+    results_.clear();
+    return 0;
+  }
+
+ private:
+  const std::vector<bool> &solve(int exact) const {
+    std::vector<unsigned char> in(num_m_ > 0 ? num_m_ : 1, 0);
+    results_.assign(num_m_, false);
+    if (num_m_ > 0 && dpgo_pcm_solve(h_, exact, in.data()) >= 0)
+      for (int k = 0; k < num_m_; k++) results_[k] = in[k] != 0;
+    return results_;
+  }
+  dpgo_pcm_t *h_ = nullptr;
+  Options opts_;
+  int num_m_ = 0;
+  std::vector<int> measurements_;
+  std::vector<unsigned char> adjacency_;
+  mutable std::vector<bool> results_;
 };
 
 }  // namespace DPGO
