@@ -78,14 +78,6 @@ Rccl &rccl() {
       throw DeviceError("RCCL call failed");                                                        \
     }                                                                                               \
   } while (0)
-#define HIP_OK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) {                                                                         \
-      fprintf(stderr, "[dpgo_amd] ERROR: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      throw DeviceError(hipGetErrorString(e_));                                                     \
-    }                                                                                               \
-  } while (0)
 }  // namespace
 
 P2PPlan p2p_plan(int rank, const std::vector<std::vector<PoseKey>> &exported, const std::vector<std::vector<PoseKey>> &needed) {
@@ -136,16 +128,16 @@ void Comm::init(const void *id128, bool layout) {
   const int rank = rank_, nranks = nranks_;
   ncclUniqueId id;
   std::memcpy(&id, id128, sizeof(id));
-  HIP_OK(hipSetDevice(grp->device()));
+  HIP_CHECK(hipSetDevice(grp->device()));
   ncclComm_t c = nullptr;
   NCCL_OK(rccl().CommInitRank(&c, nranks, id, rank));
   comm_ = c;
-  HIP_OK(hipStreamCreateWithFlags(&cs_, hipStreamNonBlocking));
-  HIP_OK(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
+  HIP_CHECK(hipStreamCreateWithFlags(&cs_, hipStreamNonBlocking));
+  HIP_CHECK(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming));
+  HIP_CHECK(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming));
   const int RS = (grp->d() + 1) * grp->d();
   red_.alloc(64);
-  HIP_OK(hipHostMalloc((void **)&h_red_, sizeof(double) * 64, hipHostMallocDefault));
+  HIP_CHECK(hipHostMalloc((void **)&h_red_, sizeof(double) * 64, hipHostMallocDefault));
   if (!layout) return;   // (ok_ stays false: no exchange, no collectives lent to the group)
   // ---- who exports what: all-gather of the key counts, then of the (node, pose) keys, through RCCL itself
   const auto &keys = grp->sent_keys();
@@ -375,11 +367,11 @@ int Comm::setup_p2p(const std::vector<std::vector<PoseKey>> &exported) {
 int Comm::small_allgather(int mine, std::vector<int> &all) {
   if (2 * nranks_ + 2 > 128) return -1;
   int *dev = reinterpret_cast<int *>(red_.p);
-  HIP_OK(hipMemcpyAsync(dev, &mine, sizeof(int), hipMemcpyHostToDevice, cs_));   // (pageable source: returns when staged)
+  HIP_CHECK(hipMemcpyAsync(dev, &mine, sizeof(int), hipMemcpyHostToDevice, cs_));   // (pageable source: returns when staged)
   NCCL_OK(rccl().AllGather(dev, dev + 2, 1, ncclInt32, (ncclComm_t)comm_, cs_));
   sync_comm_stream();
   all.assign(nranks_, 0);
-  HIP_OK(hipMemcpy(all.data(), dev + 2, sizeof(int) * nranks_, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(all.data(), dev + 2, sizeof(int) * nranks_, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -423,7 +415,7 @@ void Comm::sync_stream(hipStream_t st) {
   for (;;) {
     const hipError_t q = hipStreamQuery(st);
     if (q == hipSuccess) return;
-    if (q != hipErrorNotReady) HIP_OK(q);
+    if (q != hipErrorNotReady) HIP_CHECK(q);
     if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) {
       fprintf(stderr, "[dpgo_amd] ERROR: rank %d: an RCCL collective did not finish within %.0f s (a peer is gone or "
                       "never joined); the communicator is abandoned.\n", rank_, limit);
@@ -482,7 +474,7 @@ int Comm::p2p_self_check() {
   DevBuf<double> src_d, dst_d;
   src_d.upload(probe);
   dst_d.upload(std::vector<double>((size_t)nrec * RS, -7.0));
-  HIP_OK(hipDeviceSynchronize());   // (the uploads ran on the null stream; cs_ does not wait for it)
+  HIP_CHECK(hipDeviceSynchronize());   // (the uploads ran on the null stream; cs_ does not wait for it)
   if (run_p2p(x, src_d.p, dst_d.p) != 0) return -1;
   sync_comm_stream();
   dst_d.download(back);
@@ -520,7 +512,7 @@ int Comm::enable_self_exchange() {
   grp->recv_lists_changed();
   x.send.alloc((size_t)n * RS);
   x.recv.alloc((size_t)n * RS);
-  HIP_OK(hipDeviceSynchronize());
+  HIP_CHECK(hipDeviceSynchronize());
   p2p_ = true;
   self_ = true;
   attach_p2p();
@@ -535,8 +527,8 @@ int Comm::enable_timing() {
   if (ev_done_) (void)hipEventDestroy(ev_done_);
   ev_ready_ = ev_done_ = nullptr;
   grp_->set_pending_exchange(nullptr);
-  HIP_OK(hipEventCreate(&ev_ready_));
-  HIP_OK(hipEventCreate(&ev_done_));
+  HIP_CHECK(hipEventCreate(&ev_ready_));
+  HIP_CHECK(hipEventCreate(&ev_done_));
   timing_ = true; timed_pending_ = false; time_sum_us_ = 0; time_n_ = 0;
   return 0;
 }
@@ -608,7 +600,7 @@ int Comm::exchange() {
     // (Group::set_exchange_pack) unless that ran before this communicator existed; the unpack is the next update()'s
     // inter-edge pass reading the receive buffer (Group::set_pending_recv), or -- trivial loss -- one indexed copy.
     hipStream_t gs = grp_->stream();
-    if (timing_) HIP_OK(hipEventRecord(ev_ready_, gs));
+    if (timing_) HIP_CHECK(hipEventRecord(ev_ready_, gs));
     const bool packed = grp_->take_packed();
     P2P &x = p2p_state_;
     if (run_p2p(x, packed ? nullptr : grp_->Xk_records(), nullptr, gs) != 0) return -1;
@@ -618,18 +610,18 @@ int Comm::exchange() {
     } else if (x.recv_dst.n > 0 && grp_->set_pending_recv(x.recv.p, (int)x.recv_dst.n, x.recv_dst.p, x.recv_src.p) != 0) {
       grp_->copy_records(gs, (int)x.recv_dst.n, x.recv_dst.p, x.recv_src.p, x.recv.p, grp_->Xk_records());
     }
-    if (timing_) HIP_OK(hipEventRecord(ev_done_, gs));
+    if (timing_) HIP_CHECK(hipEventRecord(ev_done_, gs));
     timed_pending_ = timing_;
     return 0;
   }
-  HIP_OK(hipEventRecord(ev_ready_, grp_->stream()));      // Xk of this iteration is final
-  HIP_OK(hipStreamWaitEvent(cs_, ev_ready_, 0));
+  HIP_CHECK(hipEventRecord(ev_ready_, grp_->stream()));      // Xk of this iteration is final
+  HIP_CHECK(hipStreamWaitEvent(cs_, ev_ready_, 0));
   {
     grp_->pack_sent(send_.p, cs_);
     NCCL_OK(rccl().AllGather(send_.p, gathered_.p, (size_t)stride_ * RS, ncclFloat64, (ncclComm_t)comm_, cs_));
     grp_->unpack_recv(gathered_.p, cs_);
   }
-  HIP_OK(hipEventRecord(ev_done_, cs_));
+  HIP_CHECK(hipEventRecord(ev_done_, cs_));
   timed_pending_ = timing_;
   grp_->set_pending_exchange(ev_done_);
   return 0;
@@ -647,9 +639,9 @@ int Comm::allreduce_impl(double *vals, int n) {
   for (int off = 0; off < n; off += 64) {
     const int m = std::min(64, n - off);
     std::memcpy(h_red_, vals + off, sizeof(double) * m);
-    HIP_OK(hipMemcpyAsync(red_.p, h_red_, sizeof(double) * m, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(red_.p, h_red_, sizeof(double) * m, hipMemcpyHostToDevice, st));
     NCCL_OK(rccl().AllReduce(red_.p, red_.p, m, ncclFloat64, ncclSum, (ncclComm_t)comm_, st));
-    HIP_OK(hipMemcpyAsync(h_red_, red_.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(h_red_, red_.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
     sync_stream(st);
     std::memcpy(vals + off, h_red_, sizeof(double) * m);
   }
@@ -662,9 +654,9 @@ int Comm::allreduce_large(double *vals, size_t n) {
   DevBuf<double> buf;
   buf.alloc(n, false);
   hipStream_t st = grp_->stream();
-  HIP_OK(hipMemcpyAsync(buf.p, vals, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(buf.p, vals, sizeof(double) * n, hipMemcpyHostToDevice, st));
   NCCL_OK(rccl().AllReduce(buf.p, buf.p, n, ncclFloat64, ncclSum, (ncclComm_t)comm_, st));
-  HIP_OK(hipMemcpyAsync(vals, buf.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(vals, buf.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   sync_stream(st);
   return 0;
 }

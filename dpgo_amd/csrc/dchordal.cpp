@@ -32,15 +32,6 @@ int chordal_initialization(const Graph &g, double *X, int ld);
 void project_to_SOd_host(int d, double *M);
 
 namespace {
-#define HIP_OK(x)                                                                                  \
-  do {                                                                                             \
-    hipError_t e_ = (x);                                                                           \
-    if (e_ != hipSuccess) {                                                                        \
-      fprintf(stderr, "[dpgo_amd] ERROR: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      throw DeviceError(hipGetErrorString(e_));                                                    \
-    }                                                                                              \
-  } while (0)
-
 // C (d x d) = A^T B, C = A B, C = A B^T on row-major d x d blocks
 void mul_tn(int d, const double *A, const double *B, double *C) {
   for (int r = 0; r < d; r++)
@@ -293,8 +284,7 @@ int Group::chordal_setup(int kind, double xi, const std::vector<std::vector<doub
                     "(a node without inter-node edges, or a node whose poses are not connected?).\n");
     return -1;
   }
-  ch_->L.dof = dof;
-  ch_->L.upload(d, node_of_unknown);
+  ch_->L.upload(dof, d, node_of_unknown);
   std::vector<const BsrMatrix *> v(L);
   for (int a = 0; a < L; a++) v[a] = &Sn[a];
   upload_bsr(v, false, ch_->S);
@@ -316,7 +306,7 @@ int Group::chordal_initialize(const std::vector<std::vector<double>> &X) {
     }
   }
   sync();
-  for (double *dst : {Xk_.p, Zc_.p, Zp_.p}) HIP_OK(hipMemcpy(dst, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
+  for (double *dst : {Xk_.p, Zc_.p, Zp_.p}) HIP_CHECK(hipMemcpy(dst, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice));
   ch_->nes = Nesterov();
   return 0;
 }
@@ -349,7 +339,7 @@ double Group::chordal_objective() {
   if (!ch_) return NAN;
   sync();
   std::vector<double> rec((size_t)(P0_ + P1_) * RS_);
-  HIP_OK(hipMemcpy(rec.data(), Xk_.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(rec.data(), Xk_.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
   const int d = d_;
   double f = 0;
   for (int a = 0; a < num_local(); a++) {
@@ -386,7 +376,7 @@ int Group::chordal_get(std::vector<std::vector<double>> &Xak) {
   sync();
   const int d = d_, bs = ch_->kind == 0 ? d * d : d, off = ch_->kind == 0 ? d : 0;
   std::vector<double> rec((size_t)P0_ * RS_);
-  HIP_OK(hipMemcpy(rec.data(), Xk_.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(rec.data(), Xk_.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost));
   Xak.assign(num_local(), {});
   for (int a = 0; a < num_local(); a++) {
     const int n0 = info_[a].n[0];

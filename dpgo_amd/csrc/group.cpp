@@ -13,17 +13,6 @@
 
 namespace dpgo {
 
-// A failed HIP call never aborts the host process (this is a shared library): it is logged and thrown as
-// DeviceError, which every entry point of the C ABI (capi.cpp) turns into the reference's `return -1`.
-#define HIP_CHECK(x)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) {                                                                       \
-      fprintf(stderr, "[dpgo_amd] ERROR: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      throw DeviceError(hipGetErrorString(e_));                                                   \
-    }                                                                                             \
-  } while (0)
-
 static bool g_leak_device_buffers = false;
 void dev_leak_buffers(bool on) { g_leak_device_buffers = on; }
 template <class T>
@@ -65,462 +54,6 @@ template struct DevBuf<InterInc>;
 template struct DevBuf<RootDesc>;
 template struct DevBuf<RootRow>;
 template struct DevBuf<float>;
-
-// The factor stores explicit inverses of the pivot blocks: a pivot range beyond 1e13 (a badly scaled dataset: information
-// matrices that differ by many orders of magnitude, or a regulariser far below the weights) leaves few correct digits.
-static void warn_conditioning(const char *what, const SpdFactor &F) {
-  if (F.pivot_min > 0.0 && F.pivot_max / F.pivot_min > 1e13)
-    fprintf(stderr, "[dpgo_amd] WARNING: %s is badly conditioned (pivots %.3e .. %.3e, ratio %.1e): expect about %d correct "
-                    "digits from its solves.\n", what, F.pivot_min, F.pivot_max, F.pivot_max / F.pivot_min,
-            std::max(0, 16 - (int)std::ceil(std::log10(F.pivot_max / F.pivot_min))));
-}
-
-// Device layout of a factor.  The solve streams every W_s once per sweep, so the matrices are re-packed
-// into PANELS: the entries one tile reads, contiguous, in the order it reads them.
-//   forward tile (rows p0 .. p0+count of [y ; dupd], all columns k < kend):  panel[k][r] = WT_s[k][p0 + r]
-//   backward tile (pivot columns k0 .. k0+count, rows p >= k0):              panel[p - k0][r] = W_s[p][k0 + r]
-// (rows of a panel are ld = count rounded up to 16 doubles apart).  The zero triangle of L11^-1 is simply not
-// stored, a wave's consecutive loads are consecutive in memory, and every tile is a pure sequential stream.
-// Within a launch the tiles are ordered by decreasing length, so the long ones start first and the short
-// ones fill the tail.
-void SpdSolverDev::upload(int dcols, const std::vector<int> &node_of_unknown) {
-  piv_idx.upload(F.piv_idx);
-  upd_idx.upload(F.upd_idx);
-  asm_ptr.upload(F.asm_ptr);
-  {
-    // pull-ordered update buffer: the a-th entry of the assembly lists is row a; the child row that feeds it
-    // (F.asm_src[a]) is told where to write.  Every update row has exactly one reader (its parent).
-    std::vector<int> dst(std::max(F.total_upd, 1), 0);
-    for (size_t a = 0; a < F.asm_src.size(); a++) dst[F.asm_src[a]] = (int)a;
-    ubuf_dst.upload(dst);
-  }
-  ubuf.alloc((size_t)std::max(F.total_upd, 1) * dcols);
-  ytmp.alloc((size_t)std::max(F.n, 1) * dcols);
-  fwd_level_bytes.clear();
-  bwd_level_bytes.clear();
-  // algorithmic bytes of one level: every front entry once (8 B) + its in/out vector entries
-  auto lvl_bytes = [&](const std::vector<int> &lvl) {
-    double b = 0;
-    // (the pivot block L11^-1 is triangular: w(w+1)/2 entries)
-    for (int f : lvl) b += 8.0 * ((double)F.u[f] * F.w[f] + 0.5 * (double)F.w[f] * (F.w[f] + 1)) + 2.0 * 8.0 * dcols * (F.w[f] + F.u[f]);
-    return b;
-  };
-  for (const auto &lvl : F.by_height) fwd_level_bytes.push_back(lvl_bytes(lvl));
-  for (const auto &lvl : F.by_depth) bwd_level_bytes.push_back(lvl_bytes(lvl));
-  // two classes of tiles: small fronts (one wave per tile) and wide fronts (8 waves per tile, the columns /
-  // rows of the reduction split between the waves).
-  // The reduction length decides: columns (w) in the forward sweep, rows (w+u) in the backward sweep.
-  const int wide_above = 96;   // (<= 128: a narrow tile's reduction is one LDS chunk)
-  auto wide = [&](int f, bool fwd) { return (fwd ? F.w[f] : F.w[f] + F.u[f]) > wide_above; };
-  // a small narrow class joins the wide class (whole workgroups are cheap when there are few of them)
-  auto tiles64 = [&](const std::vector<int> &lvl, bool fwd, bool want_wide) {
-    int cnt = 0;
-    for (int f : lvl)
-      if (wide(f, fwd) == want_wide) cnt += ((fwd ? F.w[f] + F.u[f] : F.w[f]) + 63) / 64;
-    return cnt;
-  };
-  const int MERGE_BELOW = 1024;
-  // The roots are applied through the EXPLICIT inverse of their Schur complement (one launch instead of two, below),
-  // which is only as good as that complement is conditioned: cancellation costs kappa * eps in every component, where
-  // the two triangular sweeps confine the damage to the near-null direction.  So the pivots of every root are looked
-  // at first (d_kk = 1 / Linv_kk^2, within the spectrum of the complement), and a factor with a root whose pivots span
-  // more than 1e9 -- G_tt of a graph hosted by ONE node is the Laplacian + 1e-11 I, singular along the gauge -- keeps
-  // the two sweeps.
-  fused_root = settings().spd_fuse_root;
-  // a factor that is re-done every iteration or so (Rescale::Dynamic, G_tt): forming the roots' products again costs 0.5 ms
-  // per refactorisation at the headline size, the launch it saves 10 us per solve
-  if (F.keep_numeric && !settings().spd_fuse_root_dynamic) fused_root = false;
-  if (fused_root) {
-    double worst = 1.0;
-    std::vector<double> diag;
-    for (int f = 0; f < F.nfronts && fused_root; f++) {
-      if (!(F.parent[f] < 0 && F.u[f] == 0 && F.w[f] > 0)) continue;
-      const int w = F.w[f], ld = F.ldw[f];
-      diag.assign(w, 0.0);
-      if (F.dev_W) HIP_CHECK(hipMemcpy2D(diag.data(), sizeof(double), F.dev_W + F.w_off[f], sizeof(double) * (ld + 1), sizeof(double), w, hipMemcpyDeviceToHost));
-      else if (!F.W.empty()) for (int k = 0; k < w; k++) diag[k] = F.W[F.w_off[f] + (size_t)k * ld + k];
-      else { fused_root = false; break; }
-      double lo = 1e300, hi = 0.0;
-      for (int k = 0; k < w; k++) { lo = std::min(lo, std::fabs(diag[k])); hi = std::max(hi, std::fabs(diag[k])); }
-      if (!(lo > 0.0) || !std::isfinite(hi)) { fused_root = false; break; }
-      worst = std::max(worst, (hi / lo) * (hi / lo));
-    }
-    if (worst > std::pow(10.0, settings().spd_fuse_root_maxlog)) fused_root = false;
-    if (settings().spd_dump) fprintf(stderr, "[spd] dof %d roots: pivot range %.2e -> %s\n", dof, worst, fused_root ? "fused" : "two sweeps");
-  }
-  auto is_root = [&](int f) { return fused_root && F.parent[f] < 0 && F.u[f] == 0 && F.w[f] > 0; };
-  int nnodes = 1;
-  for (int a : node_of_unknown) nnodes = std::max(nnodes, a + 1);
-  auto node_of_front = [&](int f) { return node_of_unknown[F.piv_idx[F.piv_ptr[f]]]; };   // a front never spans two nodes (they are disconnected)
-  struct Tile { int f, first, count, rows; int64_t len; };   // rows: tile height of its class; len: panel rows
-  auto sweep = [&](bool fwd, std::vector<Level> &out_levels, DevBuf<SpdItem> &items_dev, DevBuf<double> &panels_dev) {
-    const auto &levels = fwd ? F.by_height : F.by_depth;
-    std::vector<Tile> tiles;
-    out_levels.clear();
-    for (const auto &lvl_all : levels) {
-      std::vector<int> lvl;   // (the roots have a launch of their own)
-      for (int f : lvl_all)
-        if (!is_root(f)) lvl.push_back(f);
-      const bool merge = tiles64(lvl, fwd, true) > 0 && tiles64(lvl, fwd, false) < MERGE_BELOW;
-      // Few wide tiles at this level: 16-row tiles put 4x more workgroups (CUs) on them.  A workgroup streams
-      // ~30-45 GB/s, so a level is as slow as its longest tile whenever it has fewer tiles than the chip has
-      // workgroup slots.  Forward tiles re-assemble the front's input vector once per tile, which makes small
-      // tiles expensive: 16 rows only below 192 tiles; backward tiles pay off up to 800 tiles when the
-      // reduction (front height) is long.  Thresholds from the per-launch table (DPGO_SPD_DUMP) of the
-      // headline instance at 8 and at 1 node per GPU.
-      const int wide_tiles = tiles64(lvl, fwd, true) + (merge ? tiles64(lvl, fwd, false) : 0);
-      int longest = 0;
-      for (int f : lvl) longest = std::max(longest, F.w[f] + F.u[f]);
-      const Settings &s = settings();
-      const bool fine = fwd ? wide_tiles < s.spd_fine_fwd
-                            : (wide_tiles < s.spd_fine_bwd || (wide_tiles < s.spd_fine_bwd_tall && longest >= 1000));
-      const int rows = (wide_tiles > 0 && fine) ? 16 : 64;
-      // node by node; within a node the wide tiles first (one workgroup each, longest first), then the narrow ones
-      // (one wave each): a launch picks the ranges of the nodes that are still live (Level::map)
-      Level lev{(int)tiles.size(), 0, 0, rows, std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0),
-                std::vector<int>(nnodes, 0), std::vector<double>(nnodes, 0.0)};
-      for (int f : lvl) lev.node_bytes[node_of_front(f)] += lvl_bytes(std::vector<int>{f});
-      for (int a = 0; a < nnodes; a++)
-        for (int pass = 1; pass >= 0; pass--) {
-          const size_t begin = tiles.size();
-          const int th = pass == 1 ? rows : 64;
-          for (int f : lvl) {
-            if (node_of_front(f) != a || (int)(wide(f, fwd) || merge) != pass) continue;
-            const int w = F.w[f], m = w + F.u[f], ext = fwd ? m : w;
-            for (int r = 0; r < ext; r += th) {
-              const int cnt = std::min(th, ext - r);
-              // forward: columns k < kend of rows r..; backward: rows p >= r of columns r..
-              const int64_t len = fwd ? ((r + th <= w) ? r + th : w) : (m - r);
-              tiles.push_back({f, r, cnt, th, len});
-            }
-          }
-          std::stable_sort(tiles.begin() + begin, tiles.end(), [](const Tile &x, const Tile &y) { return x.len * x.count > y.len * y.count; });
-          (pass == 1 ? lev.wstart : lev.nstart)[a] = (int)begin;
-          (pass == 1 ? lev.wcount : lev.ncount)[a] = (int)(tiles.size() - begin);
-          (pass == 1 ? lev.nwide : lev.nnarrow) += (int)(tiles.size() - begin);
-        }
-      out_levels.push_back(lev);
-    }
-    // panel offsets
-    std::vector<SpdItem> items(tiles.size());
-    int64_t total = 0;
-    for (size_t i = 0; i < tiles.size(); i++) {
-      const Tile &t = tiles[i];
-      const int f = t.f, ld = (t.count + 15) / 16 * 16;
-      SpdItem it;
-      it.front = f; it.first = t.first; it.count = t.count; it.w = F.w[f];
-      it.u = F.u[f]; it.ld = ld; it.piv_ptr = F.piv_ptr[f]; it.upd_ptr = F.upd_ptr[f];
-      it.pos_off = F.pos_off[f]; it.ubuf_off = F.ubuf_off[f];
-      it.node = node_of_front(f);
-      it.wait_ctr = -1;
-      it.mat_off = total;
-      it.wait_need = 0; it.signal_ctr = -1;
-      items[i] = it;
-      total += t.len * ld;
-    }
-    if (settings().spd_dump) {
-      int64_t used = 0;
-      for (const Tile &t : tiles) used += t.len * t.count;
-      fprintf(stderr, "[spd] dof %d %s panels: %.1f MB stored, %.1f MB of entries (padding %.1f %%), %zu tiles\n", dof, fwd ? "fwd" : "bwd",
-              total * 8e-6, used * 8e-6, 100.0 * (total - used) / std::max<int64_t>(used, 1), tiles.size());
-    }
-    items_dev.upload(items);
-    if (F.dev_W && F.dev_WT) {
-      // the factor is still on the device: the panels are cut out of it there (no trip through the host)
-      std::vector<PanelSrc> srcs(tiles.size());
-      for (size_t i = 0; i < tiles.size(); i++) {
-        const Tile &t = tiles[i];
-        if (fwd) srcs[i] = PanelSrc{(long long)(F.wt_off[t.f] + t.first), F.ldm[t.f], (int)t.len};
-        else srcs[i] = PanelSrc{(long long)(F.w_off[t.f] + (int64_t)t.first * F.ldw[t.f] + t.first), F.ldw[t.f], (int)t.len};
-      }
-      DevBuf<PanelSrc> &srcs_dev = fwd ? fwd_srcs : bwd_srcs;   // kept: repack() cuts the panels again after a refactorisation
-      srcs_dev.upload(srcs);
-      panels_dev.alloc((size_t)std::max<int64_t>(total, 1));   // (zero-filled: the padding of a panel row stays zero)
-      launch_pack_panels(nullptr, items_dev.p, srcs_dev.p, (int)tiles.size(), fwd ? F.dev_WT : F.dev_W, panels_dev.p);
-      HIP_CHECK(hipDeviceSynchronize());
-      return;
-    }
-    std::vector<double> panels((size_t)std::max<int64_t>(total, 1), 0.0);
-#pragma omp parallel for schedule(dynamic, 16)
-    for (size_t i = 0; i < tiles.size(); i++) {
-      const Tile &t = tiles[i];
-      const SpdItem &it = items[i];
-      double *dst = panels.data() + it.mat_off;
-      if (fwd) {
-        const double *src = F.WT.data() + F.wt_off[t.f] + t.first;
-        const int ldm = F.ldm[t.f];
-        for (int64_t k = 0; k < t.len; k++)
-          for (int r = 0; r < t.count; r++) dst[k * it.ld + r] = src[(size_t)k * ldm + r];
-      } else {
-        const double *src = F.W.data() + F.w_off[t.f] + (size_t)t.first * F.ldw[t.f] + t.first;
-        const int ldw = F.ldw[t.f];
-        for (int64_t p = 0; p < t.len; p++)
-          for (int r = 0; r < t.count; r++) dst[p * it.ld + r] = src[(size_t)p * ldw + r];
-      }
-    }
-    panels_dev.upload(panels);
-  };
-  sweep(true, fwd_levels, fwd_items, WT);
-  sweep(false, bwd_levels, bwd_items, W);
-  // ---- the roots: tiles of the full w x w product L11^-T L11^-1, forward-style (rows of the front, all columns)
-  root_level = Level{0, 0, 0, 64, std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0),
-                     std::vector<int>(nnodes, 0), std::vector<double>(nnodes, 0.0)};
-  root_items.release();
-  Wroot.release();
-  root_sym = false;
-  root_rows.release();
-  root_part.release();
-  root_pack.release();
-  if (fused_root) {
-    // one triangle instead of the full product when the roots are big enough for the second (combine) launch to pay
-    // (measured, DESIGN 3.4: an item pays three dependent loads for its inputs before 32 KB of stream, and the second
-    // launch costs 5 us -- the form wins where ONE root holds tens of megabytes (a single node per GPU: 19.5 -> 15.8 us
-    // for G_tt's 44 MB root) and is a wash on eight roots of 8-23 MB each, which keep the full product)
-    std::vector<int> roots;
-    double largest_mb = 0;
-    for (int f = 0; f < F.nfronts; f++)
-      if (is_root(f)) { roots.push_back(f); largest_mb = std::max(largest_mb, 8e-6 * (double)F.w[f] * F.w[f]); }
-    const int force = settings().spd_root_sym.value_or(-1);
-    root_sym = !roots.empty() && nnodes <= MAX_LOCAL_NODES &&
-               (force == 1 || (force != 0 && largest_mb >= settings().spd_root_sym_mb));
-  }
-  if (fused_root && root_sym) {
-    std::vector<int> roots;
-    for (int f = 0; f < F.nfronts; f++)
-      if (is_root(f)) roots.push_back(f);
-    long long nblocks = 0;
-    for (int f : roots) { const long long nb = (F.w[f] + 63) / 64; nblocks += nb * (nb + 1) / 2; }
-    // blocks per item (a workgroup each, one dependent gather per item): as many as still leave the chip three workgroups
-    // per CU, at most ROOT_SYM_MAXJ
-    const int S = (int)std::min<long long>(ROOT_SYM_MAXJ, std::max<long long>(1, settings().spd_root_sym_blocks.value_or((int)(nblocks / 768))));
-    root_sym_level = Level{0, 0, 0, 64, std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0),
-                           std::vector<int>(nnodes, 0), std::vector<double>(nnodes, 0.0)};
-    root_rows_level = root_sym_level;
-    std::vector<SpdItem> items, pack;
-    std::vector<PanelSrc> srcs;
-    std::vector<RootRow> rows;
-    std::vector<RootDesc> rdesc;
-    std::vector<double> host_src;
-    std::vector<int64_t> p_off(F.nfronts, 0);
-    int64_t ptotal = 0, total = 0;
-    int nslots = 0;
-    root_max_w = 0;
-    for (int f : roots) {
-      RootDesc rd;
-      rd.src_off = F.dev_W ? F.w_off[f] : (long long)host_src.size();
-      if (!F.dev_W) host_src.insert(host_src.end(), F.W.begin() + F.w_off[f], F.W.begin() + F.w_off[f] + (size_t)F.w[f] * F.ldw[f]);
-      rd.dst_off = ptotal; rd.ld = F.ldw[f]; rd.w = F.w[f];
-      p_off[f] = ptotal;
-      ptotal += (int64_t)F.w[f] * F.w[f];
-      root_max_w = std::max(root_max_w, F.w[f]);
-      rdesc.push_back(rd);
-    }
-    for (int a = 0; a < nnodes; a++) {
-      root_sym_level.nstart[a] = (int)items.size();
-      root_rows_level.wstart[a] = (int)rows.size();
-      for (int f : roots) {
-        if (node_of_front(f) != a) continue;
-        const int w = F.w[f], nb = (w + 63) / 64;
-        const int tbase = nslots;               // transposed slot of block (I, J), J < I: tbase + I (I - 1) / 2 + J
-        nslots += nb * (nb - 1) / 2;
-        for (int I = 0; I < nb; I++) {
-          RootRow rr;
-          rr.piv_ptr = F.piv_ptr[f]; rr.first = I * 64; rr.count = std::min(64, w - I * 64); rr.node = a;
-          rr.dslot = nslots; rr.ndslots = 0; rr.tbase = tbase; rr.nb = nb; rr.R = I; rr.pad0 = rr.pad1 = rr.pad2 = 0;
-          for (int J0 = 0; J0 <= I; J0 += S) {
-            const int nJ = std::min(S, I + 1 - J0);
-            SpdItem it;
-            it.front = f; it.first = I * 64; it.count = rr.count; it.w = w;
-            it.u = J0; it.ld = nJ; it.piv_ptr = F.piv_ptr[f]; it.upd_ptr = nslots++;   // its direct slot
-            it.pos_off = F.pos_off[f]; it.ubuf_off = tbase + I * (I - 1) / 2 + J0;     // its first transposed slot
-            it.node = a; it.wait_ctr = -1; it.mat_off = total; it.wait_need = 0; it.signal_ctr = -1;
-            items.push_back(it);
-            rr.ndslots++;
-            for (int J = J0; J < J0 + nJ; J++) {
-              // block (I, J) k-major: row k of the panel = entries (I*64 .. , J*64 + k) of P = row J*64 + k of the symmetric P
-              SpdItem pk = it;
-              pk.mat_off = total; pk.ld = 64; pk.count = rr.count;
-              pack.push_back(pk);
-              srcs.push_back(PanelSrc{(long long)(p_off[f] + (int64_t)(J * 64) * w + I * 64), w, std::min(64, w - J * 64)});
-              total += 4096;
-            }
-          }
-          rows.push_back(rr);
-          root_sym_level.node_bytes[a] += 8.0 * 4096.0 * (I + 1);
-        }
-        root_sym_level.node_bytes[a] += 2.0 * 8.0 * dcols * w;
-      }
-      root_sym_level.ncount[a] = (int)items.size() - root_sym_level.nstart[a];
-      root_sym_level.nnarrow += root_sym_level.ncount[a];
-      root_rows_level.wcount[a] = (int)rows.size() - root_rows_level.wstart[a];
-      root_rows_level.nwide += root_rows_level.wcount[a];
-    }
-    root_level = root_sym_level;   // (what the dumps and the byte counts look at)
-    root_items.upload(items);
-    root_pack.upload(pack);
-    root_srcs.upload(srcs);
-    root_rows.upload(rows);
-    root_desc.upload(rdesc);
-    root_part.alloc((size_t)std::max(nslots, 1) * 64 * dcols);
-    DevBuf<double> src_dev;
-    if (!F.dev_W) src_dev.upload(host_src);
-    Proot.alloc((size_t)ptotal, false);
-    Wroot.alloc((size_t)total);   // (zero-filled: rows and columns of a block past w stay zero)
-    launch_root_syrk(nullptr, root_desc.p, (int)rdesc.size(), root_max_w, F.dev_W ? F.dev_W : src_dev.p, Proot.p);
-    launch_pack_panels(nullptr, root_pack.p, root_srcs.p, (int)pack.size(), Proot.p, Wroot.p);
-    HIP_CHECK(hipDeviceSynchronize());
-    if (!F.keep_numeric) Proot.release();
-    if (settings().spd_dump)
-      fprintf(stderr, "[spd] dof %d fused roots as one triangle: %zu fronts, %zu items of <= %d blocks, %zu block rows, %d slots, %.1f MB of panels\n",
-              dof, roots.size(), items.size(), S, rows.size(), nslots, total * 8e-6);
-  } else if (fused_root) {
-    std::vector<int> roots;
-    for (int f = 0; f < F.nfronts; f++)
-      if (is_root(f)) roots.push_back(f);
-    int t64 = 0;
-    for (int f : roots) t64 += (F.w[f] + 63) / 64;
-    // few tiles: 16-row tiles reach 4x more CUs; a single root per GPU (one node per GPU): 8-row tiles, 8x
-    const int rows = t64 < settings().spd_fine_root8 ? 8 : (t64 < settings().spd_fine_root ? 16 : 64);
-    root_level.rows = rows;
-    std::vector<Tile> tiles;
-    for (int a = 0; a < nnodes; a++) {
-      const size_t begin = tiles.size();
-      for (int f : roots) {
-        if (node_of_front(f) != a) continue;
-        for (int r = 0; r < F.w[f]; r += rows) tiles.push_back({f, r, std::min(rows, F.w[f] - r), rows, (int64_t)F.w[f]});
-        root_level.node_bytes[a] += 8.0 * (double)F.w[f] * F.w[f] + 2.0 * 8.0 * dcols * F.w[f];
-      }
-      root_level.wstart[a] = (int)begin;
-      root_level.wcount[a] = (int)(tiles.size() - begin);
-      root_level.nwide += (int)(tiles.size() - begin);
-    }
-    std::vector<SpdItem> items(tiles.size());
-    std::vector<PanelSrc> srcs(tiles.size());
-    // where the roots' W_s = L11^-1 are: still on the device after a device factorisation, else uploaded here; the dense
-    // products P_f = L11^-T L11^-1 go to a buffer of their own (Proot), the tiles' panels are cut out of it
-    std::vector<double> host_src;
-    std::vector<RootDesc> rdesc;
-    std::vector<int64_t> p_off(F.nfronts, 0);
-    int64_t ptotal = 0;
-    root_max_w = 0;
-    for (int f : roots) {
-      RootDesc rd;
-      rd.src_off = F.dev_W ? F.w_off[f] : (long long)host_src.size();
-      if (!F.dev_W) host_src.insert(host_src.end(), F.W.begin() + F.w_off[f], F.W.begin() + F.w_off[f] + (size_t)F.w[f] * F.ldw[f]);
-      rd.dst_off = ptotal; rd.ld = F.ldw[f]; rd.w = F.w[f];
-      p_off[f] = ptotal;
-      ptotal += (int64_t)F.w[f] * F.w[f];
-      root_max_w = std::max(root_max_w, F.w[f]);
-      rdesc.push_back(rd);
-    }
-    int64_t total = 0;
-    for (size_t i = 0; i < tiles.size(); i++) {
-      const Tile &t = tiles[i];
-      const int f = t.f, ld = rows == 8 ? 8 : (t.count + 15) / 16 * 16;   // (8-row tiles: a wave's load spans 8 consecutive 64-byte rows)
-      SpdItem it;
-      it.front = f; it.first = t.first; it.count = t.count; it.w = F.w[f];
-      it.u = 0; it.ld = ld; it.piv_ptr = F.piv_ptr[f]; it.upd_ptr = F.upd_ptr[f];
-      it.pos_off = F.pos_off[f]; it.ubuf_off = F.ubuf_off[f];
-      it.node = node_of_front(f);
-      it.wait_ctr = -1;
-      it.mat_off = total;
-      it.wait_need = 0; it.signal_ctr = -1;
-      items[i] = it;
-      srcs[i] = PanelSrc{(long long)(p_off[f] + t.first), F.w[f], F.w[f]};   // columns first.. of the dense w x w product
-      total += (int64_t)F.w[f] * ld;
-    }
-    if (!tiles.empty()) {
-      root_items.upload(items);
-      root_srcs.upload(srcs);
-      root_desc.upload(rdesc);
-      DevBuf<double> src_dev;
-      if (!F.dev_W) src_dev.upload(host_src);
-      Proot.alloc((size_t)ptotal, false);
-      Wroot.alloc((size_t)total);   // (zero-filled: the padding of a panel row stays zero)
-      launch_root_syrk(nullptr, root_desc.p, (int)rdesc.size(), root_max_w, F.dev_W ? F.dev_W : src_dev.p, Proot.p);
-      launch_pack_panels(nullptr, root_items.p, root_srcs.p, (int)tiles.size(), Proot.p, Wroot.p);
-      // The tile height above fits ALL roots of the group.  The late steps of the truncated CG run on one to four of the
-      // group's nodes: a launch over so few roots gets the next finer class (64 -> 16, 16 -> 8 rows: four / two times the
-      // workgroups on the same bytes), cut from the same products -- spd_run picks by the number of live tiles.  Not for
-      // a factor that is re-done (its panels would have to be cut twice) nor for the fp32 experiment.
-      root_fine_rows = 0;
-      root_fine_items.release();
-      Wroot_fine.release();
-      const int fine = rows == 64 ? 16 : (rows == 16 ? 8 : 0);
-      if (fine && nnodes > 1 && !F.keep_numeric) {
-        std::vector<Tile> ft;
-        root_fine_level = Level{0, 0, 0, fine, std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0), std::vector<int>(nnodes, 0),
-                                std::vector<int>(nnodes, 0), root_level.node_bytes};
-        for (int a = 0; a < nnodes; a++) {
-          const size_t begin = ft.size();
-          for (int f : roots) {
-            if (node_of_front(f) != a) continue;
-            for (int r = 0; r < F.w[f]; r += fine) ft.push_back({f, r, std::min(fine, F.w[f] - r), fine, (int64_t)F.w[f]});
-          }
-          root_fine_level.wstart[a] = (int)begin;
-          root_fine_level.wcount[a] = (int)(ft.size() - begin);
-          root_fine_level.nwide += (int)(ft.size() - begin);
-        }
-        std::vector<SpdItem> fitems(ft.size());
-        std::vector<PanelSrc> fsrcs(ft.size());
-        int64_t ftotal = 0;
-        for (size_t i = 0; i < ft.size(); i++) {
-          const Tile &t = ft[i];
-          const int f = t.f, ld = fine == 8 ? 8 : (t.count + 15) / 16 * 16;
-          SpdItem it;
-          it.front = f; it.first = t.first; it.count = t.count; it.w = F.w[f];
-          it.u = 0; it.ld = ld; it.piv_ptr = F.piv_ptr[f]; it.upd_ptr = F.upd_ptr[f];
-          it.pos_off = F.pos_off[f]; it.ubuf_off = F.ubuf_off[f];
-          it.node = node_of_front(f);
-          it.wait_ctr = -1; it.mat_off = ftotal; it.wait_need = 0; it.signal_ctr = -1;
-          fitems[i] = it;
-          fsrcs[i] = PanelSrc{(long long)(p_off[f] + t.first), F.w[f], F.w[f]};
-          ftotal += (int64_t)F.w[f] * ld;
-        }
-        DevBuf<PanelSrc> fsrcs_dev;
-        root_fine_items.upload(fitems);
-        fsrcs_dev.upload(fsrcs);
-        Wroot_fine.alloc((size_t)ftotal);
-        launch_pack_panels(nullptr, root_fine_items.p, fsrcs_dev.p, (int)ft.size(), Proot.p, Wroot_fine.p);
-        HIP_CHECK(hipDeviceSynchronize());
-        root_fine_rows = fine;
-        // (live tiles of the coarse class below which the fine one is taken: the thresholds the class itself was chosen by)
-        root_fine_below = rows == 64 ? settings().spd_fine_root : settings().spd_fine_root8;
-      }
-      HIP_CHECK(hipDeviceSynchronize());
-      if (!F.keep_numeric) Proot.release();   // (kept for repack() when the factor is re-done with new values)
-    }
-    if (settings().spd_dump)
-      fprintf(stderr, "[spd] dof %d fused roots: %zu fronts, %zu tiles x %d rows, %.1f MB of panels\n", dof, roots.size(), tiles.size(), rows, total * 8e-6);
-  }
-  spd_release_device(F);
-  // the panels are on the device now: the host copy of the factor (gigabytes at the headline size) can go
-  std::vector<double>().swap(F.W);
-  std::vector<double>().swap(F.WT);
-  // both panel sets of a factor this small can live in the 256 MiB Infinity Cache from one solve to the next
-  // (measured: G_tt with 177 MB of panels at two nodes per GPU still gains 2 % from staying; 288 MB does not)
-  stream_once = sizeof(double) * (W.n + WT.n + Wroot.n) > ((size_t)settings().spd_keep_mb << 20);
-  dev.piv_idx = piv_idx.p; dev.upd_idx = upd_idx.p; dev.asm_ptr = asm_ptr.p; dev.ubuf_dst = ubuf_dst.p;
-  dev.W = W.p; dev.WT = WT.p; dev.fwd_items = fwd_items.p; dev.bwd_items = bwd_items.p; dev.ubuf = ubuf.p;
-  dev.root_items = root_items.p; dev.Wroot = Wroot.p;
-}
-
-static void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec);
-
-// New values in the same factor (F.dev_W / F.dev_WT after spd_refactor_device): the panels of every tile are cut out
-// again on the device, with the tile lists and sources the first upload() left there.  Enqueued on `st`.
-int SpdSolverDev::repack(hipStream_t st) {
-  if (!F.dev_W || !F.dev_WT || fwd_srcs.n != fwd_items.n || bwd_srcs.n != bwd_items.n) return -1;
-  launch_pack_panels(st, fwd_items.p, fwd_srcs.p, (int)fwd_items.n, F.dev_WT, WT.p);
-  launch_pack_panels(st, bwd_items.p, bwd_srcs.p, (int)bwd_items.n, F.dev_W, W.p);
-  if (fused_root && root_items.n > 0) {
-    const DevBuf<SpdItem> &cut = root_sym ? root_pack : root_items;   // (one triangle: a descriptor per block)
-    if (root_srcs.n != cut.n || Proot.n == 0) return -1;
-    launch_root_syrk(st, root_desc.p, (int)root_desc.n, root_max_w, F.dev_W, Proot.p);
-    launch_pack_panels(st, cut.p, root_srcs.p, (int)cut.n, Proot.p, Wroot.p);
-  }
-  return 0;
-}
 
 // lambda_max of a symmetric matrix by Lanczos with full reorthogonalisation (stands in for the
 // Spectra call of DPGOProblem.cpp:106-118, tolerance 1e-4).
@@ -815,11 +348,10 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
       if (spd_factor(Arr, Lrr_.F, s.spd_leaf_rr, s.spd_collapse_rr, s.spd_quotient ? d_ : 1, s.spd_device_panels) != 0) return;
       clk.lap("G_RR: ordering + symbolic + numeric factor");
       warn_conditioning("G_RR + lambda I", Lrr_.F);
-      Lrr_.dof = d_;
       std::vector<int> node_of_row((size_t)P0_ * d_);
       for (int a = 0; a < L; a++)
         for (int p = 0; p < info_[a].n[0] * d_; p++) node_of_row[(size_t)own_off_[a] * d_ + p] = a;
-      Lrr_.upload(d_, node_of_row);
+      Lrr_.upload(d_, d_, node_of_row);
       clk.lap("G_RR: panels (pack + upload)");
     }
   }
@@ -955,12 +487,11 @@ int Group::refactor_tt() {
   }
   clk.lap("G_tt: ordering + symbolic + numeric factor");
   warn_conditioning("G_tt", Ltt_.F);
-  Ltt_.dof = 1;
   std::vector<int> node_of_pose(P0_);
   for (int a = 0; a < L; a++)
     for (int p = 0; p < info_[a].n[0]; p++) node_of_pose[own_off_[a] + p] = a;
   graphs_invalidate();   // (... and the panels')
-  Ltt_.upload(d_, node_of_pose);
+  Ltt_.upload(1, d_, node_of_pose);
   clk.lap("G_tt: panels (pack + upload)");
   return 0;
 }
@@ -1428,176 +959,6 @@ void Group::wait_flag(unsigned long long seq) {
 
 void Group::copy_rows(double *dst, const double *src, bool all_rows, int part) {
   launch_axpby(d_, st_, T_, all_rows, cur_mask_, 1.0, src, 0.0, nullptr, dst, part);
-}
-
-// out <- scale * A^-1 in (the unknowns' entries of the records; everything else in `out` is left alone).
-// The forward sweep only reads `in`, the backward sweep only touches `out`: in == out solves in place.
-bool SpdSolverDev::Level::map(NodeBits bits, SpdLevelMap &M, double *bytes) const {
-  const int nw = spd_waves(rows);
-  M.nlive = 0;
-  M.pad = tile0;
-  int maxw = 0, maxn = 0;
-  double b = 0;
-  for (int a = 0; a < (int)wcount.size() && a < MAX_LOCAL_NODES; a++) {
-    if (!((bits >> a) & 1ull) || wcount[a] + ncount[a] == 0) continue;
-    const int j = M.nlive++;
-    M.node[j] = (unsigned char)a;
-    M.wstart[j] = wstart[a]; M.wcount[j] = wcount[a];
-    M.nstart[j] = nstart[a]; M.ncount[j] = ncount[a];
-    maxw = std::max(maxw, wcount[a]);
-    maxn = std::max(maxn, ncount[a]);
-    b += node_bytes[a];
-  }
-  M.wide_wgs = M.nlive * maxw;
-  M.narrow_wgs = M.nlive * ((maxn + nw - 1) / nw);
-  if (bytes) *bytes = b;
-  return M.nlive > 0;
-}
-
-// The tile class of the fused roots for a launch over the nodes `v`: the finer one where few roots are live.  The two classes
-// split a row's sum differently (their results differ in the last bits), so the choice must be a function of what the
-// ALGORITHM knows -- the nodes live after the last step the host has read (tnt.cpp: live_after) -- never of the launch's
-// geometry: a captured CG step, whose launches cover every node, asks with the eager step's node set (class_of below).
-bool SpdSolverDev::fine_root_for(NodeBits v) const {
-  if (root_sym || !root_fine_rows) return false;
-  SpdLevelMap rm;
-  if (!root_level.map(v, rm)) return false;
-  int live_tiles = 0;
-  for (int j = 0; j < rm.nlive; j++) live_tiles += rm.wcount[j];
-  return live_tiles * root_level.rows / 64 < root_fine_below;
-}
-
-void spd_run(int d, hipStream_t st, SpdSolverDev &S, NodeMask mask, double *in, double *out, double scale, const NodeBits *class_of) {
-  // the launches of the nodes in mask.v (what the host knows); mask.p, if any, is the device's more recent word
-  std::vector<SpdLevelMap> fm(S.fwd_levels.size()), bm(S.bwd_levels.size());
-  std::vector<double> fby(fm.size(), 0.0), bby(bm.size(), 0.0);
-  std::vector<char> fon(fm.size(), 0), bon(bm.size(), 0);
-  double bf = 0, bb = 0;
-  int nf = 0, nb = 0;
-  for (size_t l = 0; l < fm.size(); l++)
-    if ((fon[l] = S.fwd_levels[l].map(mask.v, fm[l], &fby[l]))) { bf += fby[l]; nf++; }
-  for (size_t l = 0; l < bm.size(); l++)
-    if ((bon[l] = S.bwd_levels[l].map(mask.v, bm[l], &bby[l]))) { bb += bby[l]; nb++; }
-  SpdLevelMap rm, rrm;
-  double rby = 0;
-  bool ron = S.root_sym ? (S.root_sym_level.map(mask.v, rm, &rby) && S.root_rows_level.map(mask.v, rrm)) : S.root_level.map(mask.v, rm, &rby);
-  // few live roots: the finer tile class (upload()), counted in 64-row tiles as the classes are chosen
-  bool fine_root = false;
-  if (ron && S.fine_root_for(class_of ? *class_of : mask.v)) {
-    fine_root = S.root_fine_level.map(mask.v, rm, &rby);
-    ron = fine_root;
-  }
-  if (ron && in == out) throw DeviceError("spd_run: the fused root step cannot solve in place");
-  {
-  ProfSweep sweep(true, st, bf + rby, nf + (ron ? (S.root_sym ? 2 : 1) : 0));
-  for (size_t l = 0; l < fm.size(); l++)
-    if (fon[l]) launch_spd_level(d, S.dof, st, S.dev, 0, fm[l], S.fwd_levels[l].rows, in, S.ytmp.p, scale, fby[l], S.stream_once, mask);
-  // the roots: right-hand side from `in` (+ the children's updates), solution straight into `out`
-  if (ron && S.root_sym) {
-    launch_root_sym(d, S.dof, st, S.dev, rm, in, S.root_part.p, rby, S.stream_once, mask);
-    launch_root_combine(d, S.dof, st, S.dev, rrm, S.root_rows.p, S.root_part.p, scale, out, mask);
-  } else if (ron && fine_root) {
-    SpdDev dv = S.dev;
-    dv.root_items = S.root_fine_items.p;
-    dv.Wroot = S.Wroot_fine.p;
-    launch_spd_level(d, S.dof, st, dv, 2, rm, S.root_fine_rows, in, out, scale, rby, S.stream_once, mask);
-  } else if (ron) launch_spd_level(d, S.dof, st, S.dev, 2, rm, S.root_level.rows, in, out, scale, rby, S.stream_once, mask);
-  }
-  ProfSweep sweep(false, st, bb, nb);
-  for (size_t l = 0; l < bm.size(); l++)
-    if (bon[l]) launch_spd_level(d, S.dof, st, S.dev, 1, bm[l], S.bwd_levels[l].rows, out, S.ytmp.p, scale, bby[l], S.stream_once, mask);
-}
-
-// DPGO_SPD_DUMP=1: time every launch of one solve on a zero vector (HIP events, best of 5) and print its
-// algorithmic bytes and rate -- the per-level view behind bench.py's per-family roofline numbers.
-static void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec) {
-  const SpdFactor &F = S.F;
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  double tot_us = 0, tot_mb = 0;
-  unsigned long long *trace = nullptr;
-  if (settings().spd_trace) {
-    size_t most = 1;
-    for (const auto &v : S.fwd_levels) most = std::max(most, (size_t)(v.nwide + v.nnarrow));
-    for (const auto &v : S.bwd_levels) most = std::max(most, (size_t)(v.nwide + v.nnarrow));
-    most = std::max(most, (size_t)S.root_level.nwide);
-    HIP_CHECK(hipMalloc(&trace, most * 6 * 8));
-    HIP_CHECK(hipMemset(trace, 0, most * 6 * 8));
-    spd_trace_set(trace);
-  }
-  auto is_root = [&](int f) { return S.fused_root && F.parent[f] < 0 && F.u[f] == 0 && F.w[f] > 0; };
-  auto run = [&](int mode, size_t l, const SpdSolverDev::Level &v, const std::vector<int> &fronts_all) {
-    if (v.nwide + v.nnarrow == 0) return;
-    const bool fwd = mode != 1;
-    int wmax = 0, mmax = 0;
-    std::vector<int> fronts;
-    for (int f : fronts_all)
-      if (is_root(f) == (mode == 2)) fronts.push_back(f);
-    for (int f : fronts) { wmax = std::max(wmax, F.w[f]); mmax = std::max(mmax, F.w[f] + F.u[f]); }
-    double bytes = 0;
-    for (double b : v.node_bytes) bytes += b;
-    float best = 1e30f;
-    for (int rep = 0; rep < 6; rep++) {
-      HIP_CHECK(hipEventRecord(e0, st));
-      SpdLevelMap M;
-      v.map(~0ull, M);
-      // (mode 2 on a zero vector: in and out may be the same array here, nothing is compared)
-      if (mode == 2 && S.root_sym) {
-        SpdLevelMap R;
-        S.root_rows_level.map(~0ull, R);
-        launch_root_sym(d, S.dof, st, S.dev, M, vec, S.root_part.p, 0.0, S.stream_once, ALL_NODES);
-        launch_root_combine(d, S.dof, st, S.dev, R, S.root_rows.p, S.root_part.p, 1.0, vec, ALL_NODES);
-      } else
-      launch_spd_level(d, S.dof, st, S.dev, mode, M, v.rows, vec, mode == 2 ? vec : S.ytmp.p, 1.0, 0.0, S.stream_once, ALL_NODES);
-      HIP_CHECK(hipEventRecord(e1, st));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      if (rep > 0) best = std::min(best, ms);
-    }
-    tot_us += best * 1e3;
-    tot_mb += bytes / 1e6;
-    if (trace) {   // (-DSPD_TRACE builds) phase timestamps of the last repetition, 100 MHz ticks -> us
-      const int nt = v.nwide + v.nnarrow;
-      std::vector<unsigned long long> h((size_t)nt * 6);
-      HIP_CHECK(hipMemcpy(h.data(), trace, h.size() * 8, hipMemcpyDeviceToHost));
-      unsigned long long tmin = ~0ull;
-      for (int t = 0; t < nt; t++) if (h[(size_t)t * 6]) tmin = std::min(tmin, h[(size_t)t * 6]);
-      auto pct = [](std::vector<double> &x, double q) { if (x.empty()) return 0.0; std::sort(x.begin(), x.end()); return x[std::min(x.size() - 1, (size_t)(q * x.size()))]; };
-      for (int cls = 0; cls < 2; cls++) {
-        const int a = cls == 0 ? 0 : v.nwide, b = cls == 0 ? v.nwide : nt;
-        if (a == b) continue;
-        std::vector<double> ph[5], start, end;
-        for (int t = a; t < b; t++) {
-          const unsigned long long *q = &h[(size_t)t * 6];
-          if (!q[0] || !q[5]) continue;
-          for (int i = 0; i < 5; i++) ph[i].push_back((double)(q[i + 1] - q[i]) * 0.01);
-          start.push_back((double)(q[0] - tmin) * 0.01);
-          end.push_back((double)(q[5] - tmin) * 0.01);
-        }
-        fprintf(stderr, "[trace]   %s tiles %5zu: item %.2f/%.2f  gather %.2f/%.2f  stream %.2f/%.2f  reduce %.2f/%.2f  write %.2f/%.2f us (median/p90);"
-                " start p10 %.1f p50 %.1f p90 %.1f max %.1f, end p10 %.1f p50 %.1f p90 %.1f max %.1f us\n", cls == 0 ? "wide  " : "narrow", start.size(),
-                pct(ph[0], .5), pct(ph[0], .9), pct(ph[1], .5), pct(ph[1], .9), pct(ph[2], .5), pct(ph[2], .9), pct(ph[3], .5), pct(ph[3], .9),
-                pct(ph[4], .5), pct(ph[4], .9), pct(start, .1), pct(start, .5), pct(start, .9), pct(start, 1.0), pct(end, .1), pct(end, .5),
-                pct(end, .9), pct(end, 1.0));
-      }
-    }
-    fprintf(stderr, "[spd] dof %d %s level %2zu fronts %5zu wide tiles %5d x %2d rows, narrow tiles %5d, max_w %4d max_m %4d  %7.2f MB %6.1f us %6.0f GB/s\n",
-            S.dof, mode == 2 ? "root" : (fwd ? "fwd" : "bwd"), l, fronts.size(), v.nwide, v.rows, v.nnarrow, wmax, mmax, bytes / 1e6, best * 1e3, bytes / (best * 1e-3) / 1e9);
-  };
-  std::vector<int> every(F.nfronts);
-  for (int f = 0; f < F.nfronts; f++) every[f] = f;
-  for (size_t l = 0; l < S.fwd_levels.size(); l++) run(0, l, S.fwd_levels[l], F.by_height[l]);
-  run(2, 0, S.root_level, every);
-  for (size_t l = 0; l < S.bwd_levels.size(); l++) run(1, l, S.bwd_levels[l], F.by_depth[l]);
-  fprintf(stderr, "[spd] dof %d total %.1f MB %.1f us %.0f GB/s (launches timed one by one)\n", S.dof, tot_mb, tot_us, tot_mb / tot_us * 1e3);
-  if (trace) {
-    spd_trace_set(nullptr);
-    HIP_CHECK(hipFree(trace));
-  }
-  HIP_CHECK(hipEventDestroy(e0));
-  HIP_CHECK(hipEventDestroy(e1));
 }
 
 // (fronts of nodes outside the current mask are skipped: their entries of `out` stay as they are)

@@ -18,7 +18,6 @@
 
 #include <cstdint>
 #include <map>
-#include <stdexcept>
 #include <utility>
 #include <string>
 #include <vector>
@@ -27,14 +26,9 @@
 #include "graph.h"
 #include "kernels.h"
 #include "settings.h"
-#include "spd.h"
+#include "spd_solve.h"
 
 namespace dpgo {
-
-// thrown by the host layer when a HIP call fails; the C ABI catches it and returns -1
-struct DeviceError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
 
 // DPGO::Options (C++/DPGO/include/DPGO/DPGO_types.h:78-201), plain data.
 struct Options {
@@ -91,24 +85,6 @@ struct DChordalOptions {
   double reg_G = 1e-12;
 };
 
-// After this, DevBuf never calls hipFree again in this process: a stuck RCCL kernel that cannot be aborted would make
-// every hipFree wait for ever (comm.cpp: Comm::abandon).
-void dev_leak_buffers(bool on);
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() {}
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  void release();
-  void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); }
-  void alloc(size_t count, bool zero = true);
-  void upload(const std::vector<T> &h);
-  void download(std::vector<T> &h) const;
-};
-
 // DPGO_SETUP_TIMING=1: wall time of the set-up phases on stderr
 struct SetupClock {
   const bool on = settings().setup_timing;
@@ -120,59 +96,6 @@ struct SetupClock {
     t = n;
   }
 };
-
-struct SpdSolverDev {
-  SpdFactor F;   // host copy kept for sizes / host solves
-  ~SpdSolverDev() { spd_release_device(F); spd_release_numeric(F); }
-  DevBuf<int> piv_idx, upd_idx, asm_ptr, ubuf_dst;
-  DevBuf<double> W, WT, ubuf, ytmp;   // W / WT: backward / forward panels (see upload)
-  DevBuf<SpdItem> fwd_items, bwd_items;
-  // one launch.  Tiles [tile0, tile0 + nwide + nnarrow) of the sweep's item list, stored node by node: node a's wide
-  // tiles (rows high) are [wstart[a], wstart[a] + wcount[a]), its narrow ones [nstart[a], nstart[a] + ncount[a])
-  struct Level {
-    int tile0, nwide, nnarrow, rows;
-    std::vector<int> wstart, wcount, nstart, ncount;
-    std::vector<double> node_bytes;   // algorithmic bytes of the level per node
-    // the launch for the nodes of `bits` (false: none of them has a tile here); bytes: their share of the level
-    bool map(NodeBits bits, SpdLevelMap &M, double *bytes = nullptr) const;
-  };
-  std::vector<Level> fwd_levels, bwd_levels;   // (without the roots of the trees)
-  // the roots: forward and backward step fused into one launch over the explicit inverse of the root's Schur
-  // complement (k_spd_level MODE 2); DPGO_SPD_FUSE_ROOT=0 keeps them in the two sweeps
-  Level root_level{0, 0, 0, 64, {}, {}, {}, {}, {}};
-  bool fused_root = false;
-  DevBuf<SpdItem> root_items;
-  // The fused roots stored as ONE TRIANGLE of 64 x 64 blocks (kernels.h: RootRow; k_root_sym + k_root_combine): half the
-  // bytes of the level for one small launch more, taken when a single root holds at least DPGO_SPD_ROOT_SYM_MB (32) megabytes
-  // (DPGO_SPD_ROOT_SYM=1 / 0 forces it on / off).  root_items are then the wave-sized items, root_sym_level / root_rows_level
-  // their and the block rows' per-node ranges, root_part the partial-sum slots, root_pack the per-block descriptors the
-  // panels are cut with (also by repack()).
-  // the next finer tile class of the full-product roots, for launches over few live roots (upload(), spd_run)
-  Level root_fine_level{0, 0, 0, 16, {}, {}, {}, {}, {}};
-  DevBuf<SpdItem> root_fine_items;
-  DevBuf<double> Wroot_fine;
-  int root_fine_rows = 0, root_fine_below = 0;
-  bool fine_root_for(NodeBits v) const;
-  bool root_sym = false;
-  Level root_sym_level{0, 0, 0, 64, {}, {}, {}, {}, {}}, root_rows_level{0, 0, 0, 64, {}, {}, {}, {}, {}};
-  DevBuf<RootRow> root_rows;
-  DevBuf<double> root_part;
-  DevBuf<SpdItem> root_pack;
-  DevBuf<double> Wroot, Proot;   // the root tiles' panels; the dense products they are cut from (kept with keep_numeric)
-  DevBuf<RootDesc> root_desc;
-  int root_max_w = 0;
-  std::vector<double> fwd_level_bytes, bwd_level_bytes;
-  SpdDev dev;
-  int dof = 1;
-  bool stream_once = true;   // panels read with non-temporal loads (see upload)
-  void upload(int dcols, const std::vector<int> &node_of_unknown);   // node_of_unknown: local node of every row of A
-  DevBuf<PanelSrc> fwd_srcs, bwd_srcs, root_srcs;   // where every tile's panel comes from in the front-major factor
-  int repack(hipStream_t st);   // the panels again from F.dev_W / F.dev_WT (same pattern, new values)
-};
-
-// out <- scale * A^-1 in on the unknowns' entries of the records (everything else in `out` is left alone); in != out
-// class_of: the node set the roots' tile class is chosen for, if not mask.v (SpdSolverDev::fine_root_for)
-void spd_run(int d, hipStream_t st, SpdSolverDev &S, NodeMask mask, double *in, double *out, double scale, const NodeBits *class_of = nullptr);
 
 class Group {
  public:

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace dpgo {
@@ -340,11 +341,11 @@ bool prof_enabled();
 struct alignas(16) SpdItem {
   int front, first, count, w;            // first row (forward) / pivot column (backward) of the tile, rows in it
   int u, ld, piv_ptr, upd_ptr;           // ld: doubles between consecutive rows of the tile's panel
-  int pos_off, ubuf_off, node, wait_ctr; // node: local node the front belongs to (launch masks)
+  int pos_off, ubuf_off, node, pad0;    // node: local node the front belongs to (launch masks)
   int64_t mat_off;                       // offset of the tile's panel
-  int wait_need, signal_ctr;             // (reserved: with wait_ctr, the counters of the one-launch solve that round 5 removed)
+  int pad1, pad2;
 };
-static_assert(sizeof(SpdItem) == 64, "SpdItem is loaded as four int4");
+static_assert(sizeof(SpdItem) == 64 && offsetof(SpdItem, mat_off) == 48, "SpdItem is loaded as four int4");
 
 struct SpdDev {
   const int *piv_idx = nullptr, *upd_idx = nullptr;   // matrix indices of the pivots / update rows of every front

@@ -1,0 +1,42 @@
+// The device side of the multifrontal solve (spd.h): the factor's panels, the tile plan of both sweeps and of the fused
+// roots (spd_solve.cpp), and the launches of one solve (k_spd_level, k_root_sym / k_root_combine in kernels.hip).
+#pragma once
+#include <memory>
+#include <vector>
+
+#include "devbuf.h"
+#include "kernels.h"
+#include "spd.h"
+
+namespace dpgo {
+
+class SpdSolverDev;
+
+// out <- scale * A^-1 in on the unknowns' entries of the records (everything else in `out` is left alone); in != out
+// class_of: the node set the roots' tile class is chosen for, if not mask.v (SpdSolverDev::fine_root_for)
+void spd_run(int d, hipStream_t st, SpdSolverDev &S, NodeMask mask, double *in, double *out, double scale, const NodeBits *class_of = nullptr);
+// DPGO_SPD_DUMP=1: the tile plan's per-launch table on stderr, every launch timed on `vec` (a zero vector; overwritten)
+void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec);
+// a warning on stderr when F's pivots span so many orders of magnitude that its solves lose digits
+void warn_conditioning(const char *what, const SpdFactor &F);
+
+class SpdSolverDev {
+ public:
+  SpdFactor F;   // host copy kept for sizes / host solves
+  SpdSolverDev();
+  ~SpdSolverDev();
+  // F's panels and tile plan on the device; F's host copy of the factor goes.  dof: unknowns per record (1: the
+  // translation, d: the rotation rows); dcols: columns of a right-hand side; node_of_unknown: local node of every row of A
+  void upload(int dof, int dcols, const std::vector<int> &node_of_unknown);
+  int repack(hipStream_t st);   // the panels again from F.dev_W / F.dev_WT (same pattern, new values)
+  // the finer tile class of the fused roots for a launch over the nodes `v` (few live roots)
+  bool fine_root_for(NodeBits v) const;
+
+ private:
+  struct Plan;   // device buffers and tile plan (spd_solve.cpp)
+  std::unique_ptr<Plan> plan_;
+  friend void spd_run(int, hipStream_t, SpdSolverDev &, NodeMask, double *, double *, double, const NodeBits *);
+  friend void spd_profile(int, hipStream_t, SpdSolverDev &, double *);
+};
+
+}  // namespace dpgo

@@ -28,15 +28,6 @@
 
 namespace dpgo {
 
-#define HIP_CHECK(x)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) {                                                                       \
-      fprintf(stderr, "[dpgo_amd] ERROR: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      throw DeviceError(hipGetErrorString(e_));                                                   \
-    }                                                                                             \
-  } while (0)
-
 namespace {
 enum { ST_GRADIENT = 0, ST_PRECON_GRADIENT, ST_REL_DECREASE, ST_STEPSIZE, ST_TRUST_REGION, ST_ITER_LIMIT };
 
