@@ -19,10 +19,8 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <iterator>
-#include <thread>
 #include <map>
 #include <cstdio>
 #include <cstring>
@@ -411,19 +409,13 @@ void Comm::sync_comm_stream() { sync_stream(cs_); }
 
 void Comm::sync_stream(hipStream_t st) {
   const double limit = std::max(1.0, settings().comm_timeout);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t q = hipStreamQuery(st);
-    if (q == hipSuccess) return;
-    if (q != hipErrorNotReady) HIP_CHECK(q);
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) {
-      fprintf(stderr, "[dpgo_amd] ERROR: rank %d: an RCCL collective did not finish within %.0f s (a peer is gone or "
-                      "never joined); the communicator is abandoned.\n", rank_, limit);
-      abandon(st);
-      throw DeviceError("RCCL collective timed out");
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(50));
-  }
+  const hipError_t q = poll_stream(st, limit);
+  if (q == hipSuccess) return;
+  if (q != hipErrorNotReady) HIP_CHECK(q);
+  fprintf(stderr, "[dpgo_amd] ERROR: rank %d: an RCCL collective did not finish within %.0f s (a peer is gone or "
+                  "never joined); the communicator is abandoned.\n", rank_, limit);
+  abandon(st);
+  throw DeviceError("RCCL collective timed out");
 }
 
 // A wait ran into its deadline: an RCCL kernel is spinning on `st` and will never end by itself.  The unwinding that
@@ -562,7 +554,7 @@ size_t Comm::bytes_sent_per_exchange() const {
 
 // What the neighbour-to-neighbour exchange asks of the group it serves: the pack rides on the tail of iterate(), and a
 // collective of ours that never ends on the group's stream (a peer is gone) is aborted when the group's wait for that
-// stream runs into its deadline (Group::wait_flag), as sync_stream() does for the communicator's own stream.
+// stream runs into its deadline (Schedule::wait), as sync_stream() does for the communicator's own stream.
 void Comm::attach_p2p() {
   grp_->set_exchange_pack(p2p_state_.send_rows.p, (int)p2p_state_.send_rows.n, p2p_state_.send.p);
   grp_->set_stuck_handler(&Comm::cb_stuck, this);

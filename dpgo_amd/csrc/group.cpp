@@ -5,11 +5,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <set>
-#include <thread>
 
 namespace dpgo {
 
@@ -150,7 +148,6 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
     return;
   }
   HIP_CHECK(hipSetDevice(device));
-  HIP_CHECK(hipStreamCreate(&st_));
   const int L = (int)nodes_.size();
   const bool trivial = (opt.loss == 0);
   info_.resize(L);
@@ -216,25 +213,22 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
     return;
   }
   cur_mask_ = ALL_NODES;
-  // pinned: [scalars of k_reduce | a cache line | the flag's cache line | CG summaries | TNT summaries]
+  // pinned: [scalars of k_reduce | the schedule's flag | CG summaries | TNT summaries | rescale decisions | update()'s sums | gate]
   const size_t nsc = (size_t)std::max(L, 1) * MAX_SLOTS;
-  HIP_CHECK(hipHostMalloc((void **)&h_scal_, sizeof(double) * (nsc + 16 + (size_t)std::max(L, 1) * (CG_SUMMARY + TNT_SUMMARY + 1) + nsc + 8),
-                          hipHostMallocMapped | hipHostMallocCoherent));
-  h_flag_ = reinterpret_cast<unsigned long long *>(h_scal_ + nsc + 8);
-  *h_flag_ = 0;
-  h_cg_ = h_scal_ + nsc + 16;
+  sched_.open(nsc, (size_t)std::max(L, 1) * (CG_SUMMARY + TNT_SUMMARY + 1) + nsc + 8, P0_, L);
+  st_ = sched_.stream();
+  h_scal_ = sched_.pinned_front();
+  h_cg_ = sched_.pinned_back();
   h_tnt_ = h_cg_ + (size_t)std::max(L, 1) * CG_SUMMARY;
   h_rs_ = h_tnt_ + (size_t)std::max(L, 1) * TNT_SUMMARY;
   h_upd_ = h_rs_ + std::max(L, 1);   // update()'s sums have a block of their own: the next refinement's sums may arrive before the host has read them
   h_gate_ = h_upd_ + nsc;            // the verdict of k_reduce_gate (group.h: SpecUpdate)
   h_gate_[0] = -1.0;
   for (int i = 0; i < std::max(L, 1) * (CG_SUMMARY + TNT_SUMMARY + 1); i++) h_cg_[i] = 0.0;
-  reduce_arrived_.alloc(1);
   fused_ = settings().fused;
   partials_.alloc((size_t)MAX_SLOTS * std::max(T_.nseg_all, 1));
   cg_.alloc(MAX_LOCAL_NODES);
   dmask_.alloc(4);
-  dev_seq_.alloc(1);
   go_.alloc(1);
   dev_sums_.alloc((size_t)MAX_LOCAL_NODES * MAX_SLOTS);
   dev_tnt_.alloc((size_t)MAX_LOCAL_NODES * TNT_SUMMARY);
@@ -409,7 +403,7 @@ Group::Group(const Graph &g, const std::vector<int> &node_ids, const Options &op
 // The operators of every local node on the device (block-CSR G, S, P, P0, Q; the per-pose arrays D, T, N, V, robust Q).
 // Called at construction and after a Dynamic rescale.
 void Group::upload_operators() {
-  graphs_invalidate();   // (captured launches carry the operators' addresses)
+  sched_.invalidate();   // (captured launches carry the operators' addresses)
   const int L = num_local();
   const bool trivial = (opt_.loss == 0);
   auto uni = [&](int a, int p) { return p < info_[a].n[0] ? own_off_[a] + p : P0_ + nbr_off_[a] + (p - info_[a].n[0]); };
@@ -490,49 +484,22 @@ int Group::refactor_tt() {
   std::vector<int> node_of_pose(P0_);
   for (int a = 0; a < L; a++)
     for (int p = 0; p < info_[a].n[0]; p++) node_of_pose[own_off_[a] + p] = a;
-  graphs_invalidate();   // (... and the panels')
+  sched_.invalidate();   // (... and the panels')
   Ltt_.upload(1, d_, node_of_pose);
   clk.lap("G_tt: panels (pack + upload)");
   return 0;
 }
 
-// Wait until the group's stream is idle, for at most `seconds`: true when it is.  (hipStreamSynchronize would wait for
-// ever behind an exchange whose peer is gone.)
-bool Group::drain(double seconds) const {
-  if (!st_) return true;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t q = hipStreamQuery(st_);
-    if (q != hipErrorNotReady) return q == hipSuccess;
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > seconds) return false;
-    std::this_thread::sleep_for(std::chrono::microseconds(50));
-  }
-}
-
 Group::~Group() {
-  // A replay may still be running (its executable graph goes next), a kernel may still write the pinned block.  A group
-  // whose stream never drains -- it waits for an exchange whose peer is gone, or a kernel faulted -- LEAKS what the
-  // device might still touch instead of freeing it under the device's feet (or waiting for ever).
-  if (host_timing_)
-    fprintf(stderr, "[host] node group of %d: %ld replays %.3f s in hipGraphLaunch (%.1f us each), %ld eager segments %.3f s, %ld waits %.3f s (%.1f us each)\n",
-            num_local(), seg_replays_, t_graph_launch_, seg_replays_ ? 1e6 * t_graph_launch_ / seg_replays_ : 0.0, seg_eager_, t_eager_seg_,
-            n_wait_, t_wait_, n_wait_ ? 1e6 * t_wait_ / n_wait_ : 0.0);
-  if (host_timing_)
+  if (sched_.host_timing()) {
+    sched_.report_launches(num_local());
     fprintf(stderr, "[host] updates enqueued ahead of the host's decision: %ld, of which the decision let stand: %ld\n", n_spec_enqueued_, n_spec_stood_);
-  if (host_timing_)
-    fprintf(stderr, "[host] waits of < 50 us / 200 us / 1 ms / 5 ms / 50 ms / longer: %ld %ld %ld %ld %ld %ld; segments replayed since the host was found to be the slower side: %s\n",
-            wait_hist_[0], wait_hist_[1], wait_hist_[2], wait_hist_[3], wait_hist_[4], wait_hist_[5], host_bound_ ? "yes" : "no");
-  const bool idle = drain(failed_ ? 2.0 : 60.0);
-  if (!idle) dev_leak_buffers(true);   // (the members' buffers are destroyed after this body: hipFree would wait for the stuck stream)
-  if (idle) {
-    graphs_destroy();
-  } else {
-    fprintf(stderr, "[dpgo_amd] WARNING: the group's stream did not drain; its graphs, pinned block and stream are leaked.\n");
-    seg_graphs_.clear();
+    sched_.report_waits();
   }
+  // A replay may still be running, a kernel may still write the pinned block: the schedule waits for the stream with a bound
+  // before any buffer goes, and leaks what the device might still touch where it never drains (schedule.h: close)
+  sched_.close(failed_ ? 2.0 : 60.0);
   chordal_release();
-  if (h_scal_ && idle) (void)hipHostFree(h_scal_);
-  if (st_ && idle) (void)hipStreamDestroy(st_);
 }
 
 void Group::upload_bsr(const std::vector<const BsrMatrix *> &per_node, bool rows_all, BsrBufs &out) {
@@ -638,8 +605,8 @@ NodeMask Group::live_mask(NodeBits bits, const NodeBits *p) const {
 // them by value) and enqueues that reduction WITH the gate in one launch, then the continuation.
 bool Group::spec_update_possible(const double *xprop) const {
   const int L = num_local();
-  if (!spec_update_armed_ || !spec_update_enabled_ || !fused_ || !keep_gx() || star_ || capturing_ || iter_graph_wanted() ||
-      xchg_done_ || pending_recv_ || !deferred_.empty() || pending_tail_.on || xprop != tmp_[7].p || L == 0)
+  if (!spec_update_armed_ || !spec_update_enabled_ || !fused_ || !keep_gx() || star_ || sched_.capturing() || sched_.iter_graph_wanted() ||
+      xchg_done_ || pending_recv_ || sched_.has_deferred() || pending_tail_.on || xprop != tmp_[7].p || L == 0)
     return false;
   for (int a = 0; a < L; a++)
     if (res_[a].iters < 1 || !res_[a].updated) return false;   // (every node: a later update, never a node's first)
@@ -661,9 +628,8 @@ void Group::speculate_update(const double *xprop, int nslots_trial) {
     G.hits0[a] = in ? res_[a].soft_restart_hits[0] : 0; G.hits1[a] = in ? res_[a].soft_restart_hits[1] : 0;
   }
   // the trial point's sums to the host (k_reduce's work, its flag) and the gate's verdict, one launch
-  launch_reduce_gate(st_, T_, L, nslots_trial, partials_.p, h_scal_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p, dev_sums_.p, G,
-                     dev_tnt_.p, cg_.p, go_.p, h_gate_);
-  spec_upd_.seq_trial = fetch_seq_;
+  launch_reduce_gate(st_, T_, L, nslots_trial, partials_.p, h_scal_, sched_.flag(), dev_sums_.p, G, dev_tnt_.p, cg_.p, go_.p, h_gate_);
+  spec_upd_.seq_trial = sched_.last_seq();
   // the common course from here: the accepted point is the trial buffer; iterate()'s tail and the local halo copy; the history
   // rotates (X[iter] <- what is X[iter-1] now, and so on); update()'s later-iteration sequence for the static robust surrogate
   const double *nxak = xprop, *zp = Zc_.p;
@@ -678,9 +644,9 @@ void Group::speculate_update(const double *xprop, int nslots_trial) {
                nullptr, nullptr, Xk_.p, nullptr, &fz);
   // (the closing reduction: left to the next refinement where update() itself would leave it, group.h: UpdLazy)
   spec_upd_.lazy = lazy_update_reduce();
-  if (!spec_upd_.lazy) launch_reduce(st_, T_, L, true, 6, pupd, h_upd_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+  if (!spec_upd_.lazy) launch_reduce(st_, T_, L, true, 6, pupd, h_upd_, sched_.flag());
   n_spec_enqueued_++;
-  spec_upd_.on = true; spec_upd_.seq_last = fetch_seq_;
+  spec_upd_.on = true; spec_upd_.seq_last = sched_.last_seq();
   spec_upd_.xak = nxak; spec_upd_.zc = zc; spec_upd_.gc = gc; spec_upd_.dfc = dfc; spec_upd_.gx = gx;
 }
 
@@ -699,7 +665,7 @@ void Group::check_gate(bool host_common) {
 // update()'s closing reduction left for the next refinement's k_cg_scal_begin (group.h: UpdLazy): eager launches of the fused
 // sequence only (a replayed segment is a fixed list of launches)
 bool Group::lazy_update_reduce() const {
-  return settings().lazy_update_reduce && fused_ && keep_gx() && !star_ && !capturing_ && !iter_graph_wanted();
+  return settings().lazy_update_reduce && fused_ && keep_gx() && !star_ && !sched_.capturing() && !sched_.iter_graph_wanted();
 }
 
 void Group::flush_pending_tail() {
@@ -709,170 +675,32 @@ void Group::flush_pending_tail() {
   launch_axpby(d_, st_, T_, false, p.m, 1.0, p.xak, 0.0, nullptr, p.xk, 0, p.z);
 }
 
-// ---------------------------------------------------------------------------
-// Segments of an iteration as graph replays (group.h)
-// ---------------------------------------------------------------------------
-bool Group::iter_graph_wanted() const {
-  const int force = settings().iter_graph.value_or(-1);
-  if (graphs_broken_ || force == 0 || prof_enabled()) return false;   // (never while launches are timed)
-  if (force == 1) return true;
-  // Where a segment streams gigabytes (the headline's eight nodes on one GPU) the host is never what bounds it, and its
-  // launches shrink with the set of nodes that still iterate, which a replay's frozen grids cannot do.  Below that size:
-  // replays once the host has been seen to be the slower side (host_bound_tick).
-  return P0_ <= 40000 && host_bound_;
-}
-
-// Every 32 iterations: the share of its time inside iterate() / update() that this group's host thread spent waiting for
-// read-backs.  Measured: 0.68 at one node per GPU of the headline on an idle host (eager launches are the faster way there:
-// replays cost 4-8 %), between 0.4 and 0.55 for the same on a slower box, 0.06-0.15 for sphere2500, city10000, M3500.  Below
-// 0.4 the host is what bounds the group.  (The CG steps of small multi-node groups are replayed whatever this says:
-// cg_graph_wanted.)
-void Group::host_bound_tick() {
-  if (host_bound_ || ++win_iters_ < 32) return;
-  const double below = settings().host_bound_below;
-  // (round 6: ... and at least half of its waits found the flag already raised -- the GPU had been waiting for the HOST.  A host
-  // that enqueues ahead of the GPU's decisions -- SpecUpdate -- spends less of its time waiting without being the slower side)
-  const bool late = below >= 1.0 || 2 * win_nlate_ >= win_nwait_;
-  if (win_lib_s_ > 0 && win_wait_s_ < below * win_lib_s_ && late) host_bound_ = true;
-  win_iters_ = 0;
-  win_wait_s_ = 0;
-  win_lib_s_ = 0;
-  win_nwait_ = win_nlate_ = 0;
-}
-
-void Group::graphs_destroy() {
-  for (auto &g : seg_graphs_)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  seg_graphs_.clear();
-}
-
-// Whatever a captured launch carries by value has changed (operators re-uploaded, panels re-cut, options set): the
-// graphs go.  A graph that may still be executing must not be destroyed, so the stream is drained first -- bounded;
-// a stream that never drains keeps (leaks) its graphs.
-void Group::graphs_invalidate() {
-  graph_gen_++;
-  seg_captures_live_ = 0;   // (the cap below is on captures of one generation of arguments, not of the group's life)
-  if (seg_graphs_.empty()) return;
-  if (drain(60.0)) graphs_destroy();
-  else seg_graphs_.clear();
-}
-
-void Group::defer_or_launch(unsigned long long key, std::function<void()> fn) {
-  if (!defer_armed_) { fn(); return; }
-  deferred_.push_back(std::move(fn));
-  deferred_key_ = deferred_key_ * 1000003ull + key;
-}
-
-void Group::flush_deferred() {
-  if (deferred_.empty()) return;
-  std::vector<std::function<void()>> d;
-  d.swap(deferred_);
-  deferred_key_ = 0;
-  for (auto &f : d) f();
-}
-
-void Group::segment(int id, NodeBits bits, std::initializer_list<unsigned long long> extra, const std::function<void()> &body_in,
-                    int wanted_in) {
-  if (capturing_) { body_in(); return; }   // (a segment inside a segment is part of it)
-  // launches that were waiting for a segment to carry them (step()) become its head
-  std::vector<std::function<void()>> pro;
-  pro.swap(deferred_);
-  const unsigned long long pro_key = pro.empty() ? 0ull : deferred_key_;
-  deferred_key_ = 0;
-  const std::function<void()> with_pro = [&] {
-    for (auto &f : pro) f();
-    body_in();
-  };
-  const std::function<void()> &body = pro.empty() ? body_in : with_pro;
-  const bool wanted = wanted_in < 0 ? iter_graph_wanted() : wanted_in != 0;
-  if (!wanted || bits != all_bits()) {
-    seg_eager_++;
-    const auto t0 = std::chrono::steady_clock::now();
-    body();
-    if (host_timing_) t_eager_seg_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+// The segments of an iteration (group.h): the key of a replay is built here, the schedule runs it
+void Group::segment(int id, NodeBits bits, std::initializer_list<unsigned long long> extra, const std::function<void()> &body,
+                    int wanted) {
+  if (sched_.capturing()) { body(); return; }   // (a segment inside a segment is part of it)
+  if (!(wanted < 0 ? sched_.iter_graph_wanted() : wanted != 0) || bits != all_bits()) {
+    sched_.segment(nullptr, body);
     return;
   }
   std::vector<unsigned long long> key;
   key.reserve(16 + extra.size());
   key.push_back((unsigned long long)id);
-  key.push_back(graph_gen_);
+  key.push_back(sched_.graph_gen());
   // the buffers that rotate with the history or swap with an accepted step
   for (const DevBuf<double> *b : {&Zc_, &Zp_, &gc_, &gp_, &Dfc_, &Dfp_, &GXc_, &GXp_, &Xak_, &tmp_[7]})
     key.push_back((unsigned long long)(uintptr_t)b->p);
   key.insert(key.end(), extra.begin(), extra.end());
-  key.push_back(pro_key);
-  SegGraph *hit = nullptr;
-  for (auto &g : seg_graphs_)
-    if (g.key == key) { hit = &g; break; }
-  if (!hit && seg_captures_live_ >= 256) {
-    if (!capture_cap_warned_) {
-      capture_cap_warned_ = true;
-      fprintf(stderr, "[dpgo_amd] WARNING: more than 256 segment variants captured without the arguments changing; further new variants "
-                      "run eagerly (the replayed ones stay).\n");
-    }
-    // (more variants than a steady state has: whatever keeps changing, capturing it again and again is not the cure)
-    seg_eager_++;
-    body();
-    return;
-  }
-  if (!hit) {
-    hipGraph_t graph = nullptr;
-    capturing_ = true;
-    captured_flags_ = 0;
-    bool ok = hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal) == hipSuccess;
-    if (ok) {
-      try {
-        body();
-      } catch (...) {
-        ok = false;
-      }
-      if (hipStreamEndCapture(st_, &graph) != hipSuccess) ok = false;
-    }
-    capturing_ = false;
-    hipGraphExec_t exec = nullptr;
-    if (ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-    if (graph) (void)hipGraphDestroy(graph);
-    if (!ok) {
-      // nothing of the body has run (a capture only records): run it eagerly, and stop trying
-      (void)hipGetLastError();
-      graphs_broken_ = true;
-      fprintf(stderr, "[dpgo_amd] WARNING: a segment of the iteration could not be captured as a graph; eager launches from here on.\n");
-      seg_eager_++;
-      body();
-      return;
-    }
-    if (seg_graphs_.size() >= 32) {   // (a handful of keys per segment is normal: the history rotates, the iterate swaps)
-      size_t old = 0;
-      for (size_t i = 1; i < seg_graphs_.size(); i++)
-        if (seg_graphs_[i].used < seg_graphs_[old].used) old = i;
-      // (never destroy a graph that may be executing: the least recently used one was replayed many read-backs ago -- the
-      // flag says so -- and only if it does not is the stream waited for)
-      if (__atomic_load_n(h_flag_, __ATOMIC_ACQUIRE) >= seg_graphs_[old].done_seq || drain(60.0)) (void)hipGraphExecDestroy(seg_graphs_[old].exec);
-      seg_graphs_.erase(seg_graphs_.begin() + old);
-    }
-    seg_graphs_.push_back(SegGraph{key, exec, captured_flags_, 0, 0});
-    hit = &seg_graphs_.back();
-    seg_captures_++;
-    seg_captures_live_++;
-  }
-  hit->used = ++seg_clock_;
-  if (host_timing_) {
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_CHECK(hipGraphLaunch(hit->exec, st_));
-    t_graph_launch_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  } else
-  HIP_CHECK(hipGraphLaunch(hit->exec, st_));
-  fetch_seq_ += hit->flags;   // the flag-raising kernels of the replay count on from the device's own word
-  hit->done_seq = fetch_seq_ + 1;   // (a flag raised BEHIND the replay says it is over: its own flag need not be its last kernel)
-  seg_replays_++;
+  key.push_back(sched_.deferred_key());   // (the launches that become the segment's head)
+  sched_.segment(&key, body);
 }
 
 unsigned long long Group::fetch_async(int nslots, bool all_rows) {
   finish_update();
   nslots = std::max(nslots, deferred_slots_);
   deferred_slots_ = 0;
-  launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
-  return fetch_seq_;   // (under capture: the caller adds the replay's flags itself, segment())
+  launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, sched_.flag());
+  return sched_.last_seq();   // (under capture: the schedule adds the replay's flags itself, Schedule::segment())
 }
 
 // The deferred end of update(): wait for its reduction, then the scalar logic that needs the numbers.
@@ -880,9 +708,8 @@ void Group::finish_update() {
   if (!pending_update_) return;
   if (upd_lazy_.pending) {   // (nobody has taken update()'s reduction along: launch it now)
     upd_lazy_.pending = false;
-    launch_reduce(st_, T_, num_local(), true, upd_lazy_.nslots, partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all, h_upd_, reduce_arrived_.p, h_flag_,
-                  next_seq(), dev_seq_.p);
-    pending_seq_ = fetch_seq_;
+    launch_reduce(st_, T_, num_local(), true, upd_lazy_.nslots, partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all, h_upd_, sched_.flag());
+    pending_seq_ = sched_.last_seq();
   }
   std::function<void()> f;
   f.swap(pending_update_);
@@ -894,56 +721,12 @@ void Group::fetch(int nslots, bool all_rows) {
   finish_update();   // (its scalars sit in the pinned slots the next reduction overwrites)
   nslots = std::max(nslots, deferred_slots_);
   deferred_slots_ = 0;
-  launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
-  wait_flag(fetch_seq_);
+  launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, sched_.flag());
+  wait_flag(sched_.last_seq());
 }
 
-// Wait until the kernel that raises the pinned flag to `seq` (or a later one of the in-order stream) has run: seeing
-// the flag means everything enqueued before that kernel is done.
 void Group::wait_flag(unsigned long long seq) {
-  const auto t0 = std::chrono::steady_clock::now();
-  struct Acc {   // (what the host-bound test and DPGO_HOST_TIMING need: the time spent in here)
-    Group *g; std::chrono::steady_clock::time_point t;
-    ~Acc() {
-      const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-      g->win_wait_s_ += dt;
-      if (!g->host_timing_) return;
-      g->t_wait_ += dt; g->n_wait_++;
-      g->wait_hist_[dt < 50e-6 ? 0 : dt < 200e-6 ? 1 : dt < 1e-3 ? 2 : dt < 5e-3 ? 3 : dt < 50e-3 ? 4 : 5]++;
-    }
-  } acc{this, t0};
-  auto arrived = [&] { return __atomic_load_n(h_flag_, __ATOMIC_ACQUIRE) >= seq; };
-  win_nwait_++;
-  if (arrived()) win_nlate_++;
-  auto last = t0;
-  for (unsigned spins = 0; !arrived(); spins++) {
-    __builtin_ia32_pause();
-    if ((spins & 0xfffff) != 0xfffff) continue;
-    const auto now = std::chrono::steady_clock::now();
-    if (host_timing_ && now - last > std::chrono::milliseconds(1)) holes_total_++;   // (the thread was off its core: diagnostic)
-    last = now;
-    if (now - t0 > std::chrono::seconds(60)) {
-      // surfaces a kernel fault, if that is why the flag never came -- without waiting for ever on a stream that is itself
-      // waiting for an exchange whose peer is gone
-      hipError_t q = hipStreamQuery(st_);
-      for (int i = 0; i < 600 && q == hipErrorNotReady && !arrived(); i++) {
-        std::this_thread::sleep_for(std::chrono::milliseconds(100));
-        q = hipStreamQuery(st_);
-      }
-      if (q != hipErrorNotReady) HIP_CHECK(q);
-      if (arrived()) break;
-      fprintf(stderr, "[dpgo_amd] ERROR: read-back flag never arrived\n");
-      if (stuck_fn_) stuck_fn_(stuck_user_);   // (a collective on this stream that never ends: its communicator aborts it now)
-      throw DeviceError("read-back flag never arrived");
-    }
-  }
-  // (debug hook: a host that comes late to every read-back -- the stream runs ahead of it by that much; the results must not
-  // depend on it, tests/test_gpu_parity.py)
-  const int late_us = settings().debug_late_host_us;
-  if (late_us > 0) {
-    const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(late_us);
-    while (std::chrono::steady_clock::now() < until) __builtin_ia32_pause();
-  }
+  sched_.wait(seq);
   if (tt_verdict_pending_ && seq >= tt_verdict_seq_) check_tt_verdict(false);   // (the stream has passed the factorisation)
   if (spec_verdict_pending_ && seq >= spec_verdict_seq_) {   // (... and the gate of a speculative update)
     spec_verdict_pending_ = false;
@@ -1149,7 +932,7 @@ int Group::set_options(const Options &o) {
     return -1;
   }
   opt_ = o;
-  graphs_invalidate();   // (captured launches carry tolerances and iteration limits by value)
+  sched_.invalidate();   // (captured launches carry tolerances and iteration limits by value)
   spec_refined_ = false;
   return 0;
 }
@@ -1205,29 +988,29 @@ int Group::communicate_local() {
     // Xk's own rows are still on their way (they ride on the next update()'s product with G): the neighbour rows come
     // from Xak, which holds the same records
     const double *src = pending_tail_.xak;
-    defer_or_launch(0x6c6f63ull, [this, src] { launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, src, Xk_.p); });
+    sched_.submit(0x6c6f63ull, [this, src] { launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, src, Xk_.p); });
     return 0;
   }
-  defer_or_launch(0x6c6f63ull, [this] { launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, Xk_.p, Xk_.p); });
+  sched_.submit(0x6c6f63ull, [this] { launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, Xk_.p, Xk_.p); });
   return 0;
 }
 
 int Group::step(const std::vector<int> &locals, const std::function<int()> &exchange) {
   struct Disarm {   // (whatever happens in between -- an error return, an exception on its way to the C ABI -- nothing stays deferred)
     Group *g;
-    ~Disarm() { g->defer_armed_ = false; g->tail_fusable_ = false; g->spec_update_armed_ = false; g->pending_tail_.on = false; g->deferred_.clear(); g->deferred_key_ = 0; }
+    ~Disarm() { g->sched_.arm_defer(false); g->tail_fusable_ = false; g->spec_update_armed_ = false; g->pending_tail_.on = false; g->sched_.drop_deferred(); }
   } disarm{this};
-  defer_armed_ = !exchange && iter_graph_wanted();
+  sched_.arm_defer(!exchange && sched_.iter_graph_wanted());
   tail_fusable_ = !exchange;
   spec_update_armed_ = !exchange;
   int rc = iterate(locals);
   tail_fusable_ = false;
   if (rc == 0 && exchange) rc = exchange();
   if (rc == 0) rc = communicate_local();
-  defer_armed_ = false;
+  sched_.arm_defer(false);
   if (rc == 0) rc = update(locals);
   flush_pending_tail();   // (nothing, unless update() had nothing to do)
-  flush_deferred();
+  sched_.flush_deferred();
   return rc;
 }
 
@@ -1349,7 +1132,7 @@ int Group::set_pending_recv(const double *buf, int count, const int *dst_dev, co
     }
     std::vector<InterInc> rec = e_rec_host_;
     for (auto &r : rec) r.osrc = r.other >= P0_ ? nsrc[r.other - P0_] : -1;
-    graphs_invalidate();   // (captured launches carry the records' address -- unchanged -- but let nothing replay mid-upload)
+    sched_.invalidate();   // (captured launches carry the records' address -- unchanged -- but let nothing replay mid-upload)
     HIP_CHECK(hipMemcpyAsync(e_rec_.p, rec.data(), sizeof(InterInc) * rec.size(), hipMemcpyHostToDevice, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     recv_nsrc_.upload(nsrc);
@@ -1578,7 +1361,7 @@ std::vector<int> Group::rescale_device(const std::vector<int> &set) {
   if (Ltt_.repack(st_) != 0) throw DeviceError("repack");
   // the verdict is read at the next read-back that was enqueued behind the factorisation: nothing waits for it here
   tt_verdict_pending_ = true;
-  tt_verdict_seq_ = fetch_seq_ + 1;
+  tt_verdict_seq_ = sched_.last_seq() + 1;
   if (clk.on) {
     sync();
     fprintf(stderr, "[setup] rescale: %zu of %zu nodes\n", changed.size(), set.size());
@@ -1588,15 +1371,15 @@ std::vector<int> Group::rescale_device(const std::vector<int> &set) {
 }
 
 int Group::update(const std::vector<int> &locals_in) {
-  InLib in_lib(this);
-  if (failed_) { flush_pending_tail(); flush_deferred(); pending_recv_ = nullptr; return -1; }
+  Schedule::InLib in_lib(sched_);
+  if (failed_) { flush_pending_tail(); sched_.flush_deferred(); pending_recv_ = nullptr; return -1; }
   finish_update();
   std::vector<int> locals;
   for (int a : locals_in)
     if (!res_[a].updated) locals.push_back(a);
   if (locals.empty()) {
     flush_pending_tail();
-    flush_deferred();
+    sched_.flush_deferred();
     flush_pending_recv();
     join_exchange();   // a pending exchange must still be ordered before whatever the caller does next on this stream
     return 0;
@@ -1606,7 +1389,7 @@ int Group::update(const std::vector<int> &locals_in) {
   // k_cg_scal_begin to reduce them (`lazy` below) while that refinement's passes use the first slots.  Not with Dynamic
   // rescale (its fetch() in the middle reads the first slots) nor when parked sums ride along (they are in the first slots)
   double *const pupd = (dynamic() || deferred_slots_ != 0) ? partials_.p : partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all;
-  host_bound_tick();
+  sched_.count_iteration();
   set_mask(locals);
   // history: X[iter-1] <- X[iter], X[iter] <- Xk ; same for g and Dfobj (masked nodes only).  A node whose
   // history already stands at this iteration (update() ran, then receive() cleared `updated`) only refreshes
@@ -1618,7 +1401,7 @@ int Group::update(const std::vector<int> &locals_in) {
   NodeBits mask_locals_bits = 0;
   for (int a : locals) mask_locals_bits |= 1ull << a;
   // (launches that wait for this update()'s first segment -- step() -- go now if something eager comes before it)
-  if ((int)adv.size() != num_local() || !zc_ready_ || xchg_done_ || dynamic() || star_) flush_deferred();
+  if ((int)adv.size() != num_local() || !zc_ready_ || xchg_done_ || dynamic() || star_) sched_.flush_deferred();
   const double *lazy_recv = nullptr;   // (robust losses: the receive buffer the inter-edge pass unpacks on the way)
   // the tail of iterate() rides on the product with G (group.h: PendingTail) where that product reads the very records the
   // tail copies: every node advances, the copy's second target is the buffer that becomes X[iter] below
@@ -1665,21 +1448,21 @@ int Group::update(const std::vector<int> &locals_in) {
     // (only where the next iterate() starts its refinement unasked -- every node was refined in this one: otherwise the host
     // wants these sums before it enqueues anything that could carry them)
     bool lazy = can_defer && lazy_update_reduce() && spec_refined_ && pupd != partials_.p && nslots <= 6 && bits == all_bits();
-    // (launches that went out ahead decided for themselves: the policy may have changed since -- host_bound_tick above)
+    // (launches that went out ahead decided for themselves: the policy may have changed since -- count_iteration() above)
     if (spec_upd_.on) lazy = spec_upd_.lazy;
     if (spec_upd_.on) {
       // the launches of this sequence went out ahead of the host's decision (speculate_update) and the decision was the
       // common one: what they were given must be what this call would have given them
       const SpecUpdate sp = spec_upd_;
       spec_upd_ = SpecUpdate();
-      const bool same = seg_id == 4 && fuse_copy && nslots == 6 && bits == all_bits() && !xchg_done_ && !lazy_recv && sp.seq_last == fetch_seq_ && can_defer && pupd != partials_.p &&
+      const bool same = seg_id == 4 && fuse_copy && nslots == 6 && bits == all_bits() && !xchg_done_ && !lazy_recv && sp.seq_last == sched_.last_seq() && can_defer && pupd != partials_.p &&
                         sp.xak == Xak_.p && sp.zc == Zc_.p && sp.gc == gc_.p && sp.dfc == Dfc_.p && sp.gx == GXc_.p && pending_tail_.on;
       if (!same) {
         failed_ = true;
         fprintf(stderr, "[dpgo_amd] ERROR: a speculative update was enqueued for another state than update() found (segment %d, copy %d, slots %d, "
                         "nodes %d, exchange %d, receive %d, flags %llu / %llu, deferred %d, own slots %d, tail %d, buffers %d %d %d %d %d)\n",
                 seg_id, (int)fuse_copy, nslots, (int)(bits == all_bits()), (int)(xchg_done_ != nullptr), (int)(lazy_recv != nullptr), sp.seq_last,
-                fetch_seq_, (int)can_defer, (int)(pupd != partials_.p), (int)pending_tail_.on, (int)(sp.xak == Xak_.p), (int)(sp.zc == Zc_.p),
+                sched_.last_seq(), (int)can_defer, (int)(pupd != partials_.p), (int)pending_tail_.on, (int)(sp.xak == Xak_.p), (int)(sp.zc == Zc_.p),
                 (int)(sp.gc == gc_.p), (int)(sp.dfc == Dfc_.p), (int)(sp.gx == GXc_.p));
         throw DeviceError("a speculative update was enqueued for another state than update() found");
       }
@@ -1687,18 +1470,18 @@ int Group::update(const std::vector<int> &locals_in) {
     } else
     segment(seg_id, bits & mask_locals_bits, {bits, mask_locals_bits, variant, (unsigned long long)nslots, fuse_copy ? 1ull : 0ull, (unsigned long long)(uintptr_t)lazy_recv}, [&] {
       launches();
-      if (!lazy) launch_reduce(st_, T_, num_local(), true, nslots, pupd, h_upd_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+      if (!lazy) launch_reduce(st_, T_, num_local(), true, nslots, pupd, h_upd_, sched_.flag());
     });
     if (lazy) { upd_lazy_.pending = true; upd_lazy_.nslots = nslots; }
     if (can_defer) {
-      pending_seq_ = lazy ? 0ull : fetch_seq_;   // (lazy: whoever launches the reduction sets it -- run_tnt, or finish_update)
+      pending_seq_ = lazy ? 0ull : sched_.last_seq();   // (lazy: whoever launches the reduction sets it -- run_tnt, or finish_update)
       for (int a : set) {
         host_update_pre(a);
         res_[a].updated = 1;
       }
       pending_update_ = std::move(logic);
     } else {
-      wait_flag(fetch_seq_);
+      wait_flag(sched_.last_seq());
       logic();
     }
   };
@@ -1738,7 +1521,7 @@ int Group::update(const std::vector<int> &locals_in) {
       launch_bsr(d_, st_, T_, false, cur_mask_, S_.dev, Zc_.p, false, nullptr, gc_.p, Xak_.p, 1.0, nullptr, pupd, 1);
     };
     const bool both = !first.empty() && !later.empty();
-    if (both) flush_deferred();
+    if (both) sched_.flush_deferred();
     if (both) common();   // (nodes at different iterations: two read-backs, nothing deferred, the shared part goes first)
     if (!first.empty()) {
       end_with(1, (split ? 1ull : 0ull) | (both ? 2ull : 0ull), 6, first, [&] {
@@ -1779,7 +1562,7 @@ int Group::update(const std::vector<int> &locals_in) {
       else flush_pending_recv();
     }
     if (both || dynamic()) {   // (the product covers every node of `locals`: it cannot sit inside one of two segments)
-      flush_deferred();
+      sched_.flush_deferred();
       head();
     }
     const bool head_inside = !(both || dynamic());
@@ -1866,7 +1649,7 @@ int Group::update(const std::vector<int> &locals_in) {
 // DPGOHash::iterate  (DPGOHash.cpp:583-628)
 // ---------------------------------------------------------------------------
 int Group::iterate(const std::vector<int> &locals) {
-  InLib in_lib(this);
+  Schedule::InLib in_lib(sched_);
   if (failed_) return -1;
   for (int a : locals)
     if (!res_[a].updated) {
@@ -1891,12 +1674,12 @@ int Group::iterate(const std::vector<int> &locals) {
     if (tail_fusable_ && fused_ && zc_ready_ && opt_.loss != 0) {
       // the next update()'s product with G takes it along (group.h: PendingTail)
       pending_tail_.on = true; pending_tail_.m = m; pending_tail_.xak = xak; pending_tail_.xk = xk; pending_tail_.z = z;
-    } else if (pack_dst_ && !defer_armed_) {
+    } else if (pack_dst_ && !sched_.defer_armed()) {
       // an exchange follows (step()): its pack rides on this launch (kernels.h: launch_tail_pack), Comm::exchange() finds it done
       launch_tail_pack(d_, st_, T_, m, xak, xk, z, pack_rows_, pack_n_, pack_dst_);
       packed_ = true;
     } else
-    defer_or_launch(0x7461696cull ^ m.v, [this, m, xak, xk, z] { launch_axpby(d_, st_, T_, false, m, 1.0, xak, 0.0, nullptr, xk, 0, z); });
+    sched_.submit(0x7461696cull ^ m.v, [this, m, xak, xk, z] { launch_axpby(d_, st_, T_, false, m, 1.0, xak, 0.0, nullptr, xk, 0, z); });
   }
   for (int a : locals) {
     res_[a].iters++;
@@ -1996,7 +1779,7 @@ int Group::amm(const std::vector<int> &locals) {
   // The head of the iteration -- extrapolation, proximal half step, translation solve -- is branch-free: one replay where
   // the host's launch rate would bound it.  The gammas then come from device memory, written by the eager launch in front.
   const double *gam_dev = nullptr;
-  if (iter_graph_wanted()) {
+  if (sched_.iter_graph_wanted()) {
     NodeCoefs gam;
     for (int a = 0; a < num_local(); a++) gam.a[a] = gam.b[a] = res_[a].gamma;
     launch_set_coefs(st_, gam, num_local(), coefs_dev_.p);
@@ -2020,12 +1803,11 @@ int Group::amm(const std::vector<int> &locals) {
   // (the closure below refers to this frame: whatever happens -- an exception on its way to the C ABI before a segment has
   // taken it -- it does not outlive the frame)
   struct DropHead {
-    Group *g; bool armed = false;
-    ~DropHead() { if (armed && !g->deferred_.empty()) { g->deferred_.clear(); g->deferred_key_ = 0; } }
-  } drop_head{this};
-  if (speculate && iter_graph_wanted() && deferred_.empty()) {
-    deferred_.push_back(head_of_iteration);
-    deferred_key_ = 0x68656164ull ^ mask_locals.v;
+    Schedule &s; bool armed = false;
+    ~DropHead() { if (armed) s.drop_deferred(); }
+  } drop_head{sched_};
+  if (speculate && sched_.iter_graph_wanted() && !sched_.has_deferred()) {
+    sched_.defer(0x68656164ull ^ mask_locals.v, head_of_iteration);
     drop_head.armed = true;
   } else {
     segment(10, cur_mask_.v, {}, head_of_iteration);
@@ -2073,9 +1855,9 @@ int Group::amm(const std::vector<int> &locals) {
     if (ref.empty()) {   // (the regime once the gradient is small: the pass and its read-back as one segment)
       segment(11, cur_mask_.v, {}, [&] {
         eval_G(Xak_.p, gc_.p, DS + 2);
-        launch_reduce(st_, T_, num_local(), false, DS + 3, partials_.p, h_scal_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+        launch_reduce(st_, T_, num_local(), false, DS + 3, partials_.p, h_scal_, sched_.flag());
       });
-      wait_flag(fetch_seq_);
+      wait_flag(sched_.last_seq());
     } else {
       if (!plain.empty()) eval_G(Xak_.p, gc_.p, DS + 2);
       deferred_slots_ = DS + 3;
@@ -2357,8 +2139,8 @@ int Group::star_sums(const double *X1_own, const double *X2_own, const double *r
   launch_star_sums(st_, T_, num_local(), valid, slots, partials_.p, star_vals_.p);
   const bool dev_sum = coll_allreduce_dev_ != nullptr;
   if (dev_sum && coll_allreduce_dev_(coll_user_, star_vals_.p, 4) != 0) return -1;
-  launch_publish(st_, star_vals_.p, 4, h_scal_, h_flag_, next_seq(), dev_seq_.p);
-  wait_flag(fetch_seq_);
+  launch_publish(st_, star_vals_.p, 4, h_scal_, sched_.flag());
+  wait_flag(sched_.last_seq());
   double v[4] = {h_scal_[0], h_scal_[1], h_scal_[2], h_scal_[3]};
   if (!dev_sum && coll_allreduce_ && coll_allreduce_(coll_user_, v, 4) != 0) return -1;
   if (F1) *F1 = v[0];
@@ -2398,7 +2180,7 @@ int Group::star_update() {
 }
 
 int Group::star_iterate() {
-  InLib in_lib(this);
+  Schedule::InLib in_lib(sched_);
   finish_update();
   if (!star_) return -1;
   const Options &o = opt_;

@@ -25,6 +25,7 @@
 #include "assemble.h"
 #include "graph.h"
 #include "kernels.h"
+#include "schedule.h"
 #include "settings.h"
 #include "spd_solve.h"
 
@@ -126,7 +127,8 @@ class Group {
   // the driver's loop body (C++/examples/dist_pgo.cpp:496-521) for the nodes in `locals`: iterate -> exchange (the caller's:
   // an RCCL exchange on the communicator's stream, or none) -> communicate_local -> update.  Without an exchange the tail
   // of iterate() (Xk <- Xak) and the local halo copy are not launched on their own but become the head of update()'s first
-  // segment (deferred_): one submission less per iteration where the host's launch rate is what bounds the group.
+  // segment (the schedule's deferred launches): one submission less per iteration where the host's launch rate is what bounds
+  // the group.
   int step(const std::vector<int> &locals, const std::function<int()> &exchange);
   // DPGOHash::receive (DPGOHash.cpp:45-82): msg for neighbour node beta is ((d+1) |recv[beta]|) x d,
   // [t rows ; R rows], poses in the order of recv[beta]; send() builds the message node `local` owes beta
@@ -175,7 +177,7 @@ class Group {
   void set_exchange_pack(const int *rows_dev, int n, double *dst) { pack_rows_ = rows_dev; pack_n_ = n; pack_dst_ = dst; packed_ = false; }
   bool take_packed() { const bool p = packed_; packed_ = false; return p; }
   // a wait for the group's stream ran into its deadline (a collective enqueued on it never ends): called before the error is raised
-  void set_stuck_handler(void (*fn)(void *), void *user) { stuck_fn_ = fn; stuck_user_ = user; }
+  void set_stuck_handler(void (*fn)(void *), void *user) { sched_.set_stuck_handler(fn, user); }
   // an exchange running on another stream (comm.cpp): `done` is recorded behind its unpack.  update() queues the
   // part of the surrogate build that needs no neighbour row, then makes the group's stream wait for it.
   void set_pending_exchange(hipEvent_t done) { xchg_done_ = done; }
@@ -232,6 +234,8 @@ class Group {
   // unified rows
   int P0_ = 0, P1_ = 0;
   std::vector<int> own_off_, nbr_off_;
+  // how the launches reach the GPU and how the host learns they are done (schedule.h); st_: its stream (not owned)
+  Schedule sched_;
   hipStream_t st_ = nullptr;
 
   // device data
@@ -241,85 +245,33 @@ class Group {
   // masks and per-node coefficients live in rings (device + pinned host), so changing them never
   // needs a stream synchronisation
   NodeMask cur_mask_ = ALL_NODES;  // the nodes the launches work on (set_mask), passed to the kernels by value
-  double *h_scal_ = nullptr;       // pinned, written by k_reduce; the flag (one cache line further) follows the scalars
-  unsigned long long *h_flag_ = nullptr, fetch_seq_ = 0;
+  double *h_scal_ = nullptr;       // pinned (the schedule's block, in front of its flag), written by k_reduce
   // a refactorisation of G_tt whose verdict (positive definite or not) has not been read yet: it is read at the first
   // wait for a read-back that was enqueued behind it (sequence number >= tt_verdict_seq_), or at sync()
   mutable bool tt_verdict_pending_ = false;
   unsigned long long tt_verdict_seq_ = 0;
   void check_tt_verdict(bool wait) const;
-  double *h_cg_ = nullptr, *h_tnt_ = nullptr;   // pinned summaries of k_cg_scal / k_tnt_begin (same allocation as h_scal_)
+  double *h_cg_ = nullptr, *h_tnt_ = nullptr;   // pinned summaries of k_cg_scal / k_tnt_begin (the block behind the flag)
   bool zc_ready_ = false;       // iterate() wrote Xk's own rows into the buffer the next update() rotates into X[iter]
   bool tnt_speculate_ = true;   // run_tnt: take the trial point behind the first CG step without waiting for its outcome
-  // A whole CG step (Hessian product, both solves, the scalar kernels: ~20 launches with fixed arguments once masks, step
-  // lengths and the flag's sequence number live on the device) captured as a HIP graph and replayed with ONE submission per
-  // step (tnt.cpp).  For groups whose steps are bound by the host's launch rate (small graphs, one node per GPU);
-  // DPGO_CG_GRAPH=0 / 1 forces it off / on.  Keyed by every pointer a step carries (the iterate's buffers swap).
-  DevBuf<unsigned long long> dev_seq_;   // the device's copy of the last sequence number a kernel raised the flag to
-  bool cg_graph_wanted() const;
-  // ---- The branch-free SEGMENTS of an iteration as graph replays (round 5).  Between two read-backs an iteration is a fixed
-  // sequence of launches -- update() behind the exchange, the start of iterate() up to the translation solve, a refinement
-  // from its model gradient to the trial point's sums -- whose arguments are pointers, node sets and constants: everything
-  // that changes from one iteration to the next lives in device memory (the Nesterov gammas: coefs_dev_, written by the one
-  // eager launch of update(); the flag's sequence number: dev_seq_; the CG's masks and step lengths, as before).  segment()
-  // runs such a sequence eagerly, or -- when the host's launch rate is what bounds the group (iter_graph_wanted) -- captures
-  // it once per key (the buffers it touches, which rotate; the node set; the variant) and replays it with ONE submission.
-  // Rare branches (a rejected step, a restart, a fallback, a Dynamic rescale) stay eager.  Bitwise the same results.
-  // done_seq: once the read-back flag has reached it, the graph's last replay is over (it may be destroyed)
-  struct SegGraph { std::vector<unsigned long long> key; hipGraphExec_t exec = nullptr; int flags = 0; unsigned long long used = 0, done_seq = 0; };
-  std::vector<SegGraph> seg_graphs_;
-  unsigned long long seg_clock_ = 0, graph_gen_ = 0;   // graph_gen_: bumped by whatever invalidates captured arguments
-  bool capturing_ = false, graphs_broken_ = false;
-  int captured_flags_ = 0;
-  long seg_replays_ = 0, seg_captures_ = 0, seg_eager_ = 0, seg_captures_live_ = 0;   // _live_: since the last graphs_invalidate()
-  bool capture_cap_warned_ = false;
-  // DPGO_HOST_TIMING=1: where the host's time goes (seconds in hipGraphLaunch, in eagerly launched segments, in waits), on
-  // stderr when the group goes
-  bool host_timing_ = settings().host_timing;
-  double t_graph_launch_ = 0, t_eager_seg_ = 0, t_wait_ = 0;
-  long n_wait_ = 0, holes_total_ = 0, wait_hist_[6] = {0, 0, 0, 0, 0, 0};   // waits of < 50 us, < 200 us, < 1 ms, < 5 ms, < 50 ms, longer
-  // the sequence number the next flag-raising launch carries: a fresh one, or 0 under capture (the kernel then takes the
-  // device's count + 1, and the host counts along when the graph is replayed)
-  unsigned long long next_seq() {
-    if (capturing_) { captured_flags_++; return 0ull; }
-    return ++fetch_seq_;
-  }
-  // ---- Whether segments are replayed (iter_graph_wanted), decided by MEASUREMENT: a group starts with eager launches and
-  // keeps an eye on how much of the time it spends inside iterate() / update() is waiting for the GPU.  A host that waits most of the time (more than
-  // 40 % of it) keeps up with eager launches, which are the faster way then (a replay costs the GPU ~8 us of start-up); a
-  // host that waits less is what bounds the group -- a slow or busy box, a small graph whose kernels are shorter than a launch -- and its
-  // segments are replayed from then on.  Looked at every 32 iterations; DPGO_ITER_GRAPH=0 / 1 forces either.
-  bool host_bound_ = false;
-  double win_wait_s_ = 0, win_lib_s_ = 0;   // of the window: seconds waiting for read-backs / seconds inside iterate() and update()
-  int win_iters_ = 0;
-  long win_nwait_ = 0, win_nlate_ = 0;   // of the window: waits for a read-back, and those that found it there already
-  void host_bound_tick();        // once per iteration (update())
-  struct InLib {                 // (the caller's own time between the calls is not the library's host being slow)
-    Group *g; std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    explicit InLib(Group *gg) : g(gg) {}
-    ~InLib() { g->win_lib_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
-  };
-  // launches that wait for the next segment to carry them (step()): captured pointer values, launched in order
-  std::vector<std::function<void()>> deferred_;
-  unsigned long long deferred_key_ = 0;
-  bool defer_armed_ = false;
-  void defer_or_launch(unsigned long long key, std::function<void()> fn);
-  void flush_deferred();
-  bool iter_graph_wanted() const;
+  // ---- The branch-free SEGMENTS of an iteration as graph replays (schedule.h).  Between two read-backs an iteration is a fixed
+  // sequence of launches -- update() behind the exchange, the start of iterate() up to the translation solve, a refinement from
+  // its model gradient to the trial point's sums, a whole CG step (tnt.cpp) -- whose arguments are pointers, node sets and
+  // constants: everything that changes from one iteration to the next lives in device memory (the Nesterov gammas: coefs_dev_,
+  // written by the one eager launch of update(); the flag's sequence number; the CG's masks and step lengths).  segment() runs
+  // such a sequence through the schedule, keyed by the buffers it touches (which rotate), the node set and the variant.  Rare
+  // branches (a rejected step, a restart, a fallback, a Dynamic rescale) stay eager.  Bitwise the same results.
   // bits: the nodes the sequence works on.  Only sequences over ALL the group's nodes are replayed: a partial set is a group
   // whose nodes are taking different branches, where the sets change from one iteration to the next and every new set
   // would be a new capture (measured: city10000 / 8 nodes with every subset captured ran 4 x slower than eagerly)
-  // wanted: -1 = by iter_graph_wanted(), 0 / 1 = the caller's own policy (the CG steps: cg_graph_wanted)
+  // wanted: -1 = by the schedule's iter_graph_wanted(), 0 / 1 = the caller's own policy (the CG steps: cg_graph_wanted)
   void segment(int id, NodeBits bits, std::initializer_list<unsigned long long> extra, const std::function<void()> &body,
                int wanted = -1);
   NodeBits all_bits() const { const int L = num_local(); return L >= 64 ? ~0ull : ((1ull << L) - 1); }
-  void graphs_invalidate();   // waits (bounded) for the stream, destroys every captured graph, bumps graph_gen_
-  void graphs_destroy();      // (the stream is known to be idle)
-  bool drain(double seconds) const;
   DevBuf<double> coefs_dev_;  // per local node: gamma of the iteration under way (k_set_coefs)
  public:
   // (counters for the tests and the API-trace summary: replays, captures, segments run eagerly)
-  void graph_stats(long *replays, long *captures, long *eager) const { *replays = seg_replays_; *captures = seg_captures_; *eager = seg_eager_; }
+  void graph_stats(long *replays, long *captures, long *eager) const { sched_.stats(replays, captures, eager); }
  private:
   // the mask of the nodes in `bits` (and-ed on the device with *p, if any) with the map that lets own-segment launches
   // cover these nodes only (kernels.h: NodeMask::nlive) when they are few
@@ -371,7 +323,6 @@ class Group {
   void check_gate(bool host_common);
   bool tail_fusable_ = false;
   void flush_pending_tail();
-  DevBuf<unsigned> reduce_arrived_;
   DevBuf<double> partials_;
   DevBuf<CgNode> cg_;       // device-resident state of the truncated CG (tnt.cpp, k_cg_scal)
   DevBuf<double> jacobi_;   // Preconditioner::Jacobi: 1 / diag(G_RR), one entry per rotation row
@@ -403,8 +354,6 @@ class Group {
   int pack_n_ = 0;
   double *pack_dst_ = nullptr;
   bool packed_ = false;
-  void (*stuck_fn_)(void *) = nullptr;
-  void *stuck_user_ = nullptr;
   // vectors (records)
   DevBuf<double> Xk_, Zc_, Zp_, Y_, DfE_, Tall_;                 // P0+P1 rows
   DevBuf<double> Xak_, Xakh_, gc_, gp_, Dfc_, Dfp_, gx_, Dfx_, T1_;   // P0 rows
@@ -457,7 +406,7 @@ class Group {
   std::vector<int> maybe_rescale(const std::vector<int> &set);
   void set_mask(const std::vector<int> &locals);
   void fetch(int nslots, bool all_rows);                  // -> h_scal_[local * MAX_SLOTS + s]
-  void wait_flag(unsigned long long seq);
+  void wait_flag(unsigned long long seq);   // the schedule's wait, then the verdicts that were enqueued in front of that flag
   int deferred_slots_ = 0;   // slots written earlier that ride along with the next fetch (saves a host round trip)
   double scal(int local, int s) const { return h_scal_[local * MAX_SLOTS + s]; }
   double *h_upd_ = nullptr;   // pinned (same allocation): the sums update() ends with

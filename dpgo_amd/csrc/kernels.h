@@ -271,11 +271,20 @@ void launch_copy_indexed(int d, hipStream_t st, int count, const int *didx, cons
 void launch_bdiag_dot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Dd, const double *x,
                       double coef, const double *add, double addcoef, double *partials, int slot);
 
+// The read-back flag a launch raises once its sums are in pinned host memory (schedule.h): the last of its workgroups to
+// arrive at the zeroed device counter `arrived` sets *host = seq.  seq == 0 (a launch captured into a graph): the flag is
+// raised to *dev_seq + 1; *dev_seq always ends up holding the value used.
+struct ReadbackFlag {
+  unsigned *arrived;
+  unsigned long long *host;
+  unsigned long long seq;
+  unsigned long long *dev_seq;
+};
+
 // host_scalars[node * MAX_SLOTS + s] = sum of the node's partials, s < nslots, written straight to pinned host
-// memory; *host_flag = seq once all of them are there (arrived: a zeroed device counter)
+// memory; then the flag
 void launch_reduce(hipStream_t st, const SegTable &T, int nnodes, bool all_rows, int nslots, const double *partials,
-                   double *host_scalars, unsigned *arrived, unsigned long long *host_flag, unsigned long long seq,
-                   unsigned long long *dev_seq);   // seq == 0: *dev_seq + 1 (a replayed launch); *dev_seq ends up holding the value used
+                   double *host_scalars, ReadbackFlag flag);
 
 // ---- the gate of a speculative update (k_reduce_gate): the per-node scalars the host knows when it enqueues the gate, by value
 struct AmmGate {
@@ -288,15 +297,14 @@ struct AmmGate {
 // tnt: the refinement's start per node (TNT_SUMMARY each, launch_cg_scal_begin's dev_tnt); *go = ~0 / 0, host_out[0] = 1.0 / 0.0
 // (pinned), both set before the flag is raised
 void launch_reduce_gate(hipStream_t st, const SegTable &T, int nnodes, int nslots, const double *partials, double *host_scalars,
-                        unsigned *arrived, unsigned long long *host_flag, unsigned long long seq, unsigned long long *dev_seq,
-                        double *dev_scalars, const AmmGate &G, const double *tnt, const CgNode *cg, NodeBits *go, double *host_out);
+                        ReadbackFlag flag, double *dev_scalars, const AmmGate &G, const double *tnt, const CgNode *cg, NodeBits *go,
+                        double *host_out);
 
 // AMM-PGO*'s master sums (k_star_sums): out[0..3] (device) from the partial slots 0..5; launch_publish: n <= 64 device values
-// to pinned host memory, then *host_flag = seq
+// to pinned host memory, then the flag (one workgroup: flag.arrived is not used)
 void launch_star_sums(hipStream_t st, const SegTable &T, int nnodes, unsigned valid_slots, const int *slots6, const double *partials,
                       double *out);   // valid_slots: bit q = sum q was produced; slots6[q]: the partial-sum slot it is in
-void launch_publish(hipStream_t st, const double *vals, int n, double *host, unsigned long long *host_flag, unsigned long long seq,
-                    unsigned long long *dev_seq);
+void launch_publish(hipStream_t st, const double *vals, int n, double *host, ReadbackFlag flag);
 
 // ---- device-side control of the truncated CG (tnt.cpp) ----
 constexpr int CG_SUMMARY = 4;    // doubles per node k_cg_scal writes to pinned memory: stop ordinal, |h|_M, iterations
@@ -314,8 +322,8 @@ void launch_tnt_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bi
 // slots 0..3 and MAX_DOTS.., the step's four from slot cg_first_slot() on; the flag protocol of launch_cg_scal
 void launch_cg_scal_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
                            double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                           NodeBits *dmask, double *host_tnt, double *host_scalars, unsigned *arrived, unsigned long long *host_flag,
-                           unsigned long long seq, unsigned long long *dev_seq, double *dev_tnt = nullptr,   // dev_tnt: host_tnt's numbers in device memory too
+                           NodeBits *dmask, double *host_tnt, double *host_scalars, ReadbackFlag flag,
+                           double *dev_tnt = nullptr,   // dev_tnt: host_tnt's numbers in device memory too
                            // carry: the reduction that closes the LAST update() rides along (k_reduce's work: upd_nslots sums per node over
                            // own and neighbour segments of the partial sums from slot UPD_SLOT0 on, to upd_host[node * MAX_SLOTS + s])
                            int upd_nslots = 0, double *upd_host = nullptr);
@@ -329,11 +337,9 @@ void launch_cg_begin(hipStream_t st, int nnodes, NodeBits bits, const CgStart &S
 // stopping test of the next step (:285-291); nodes that stop are cleared from dmask[1], then dmask[0] = dmask[1].
 // dmask[2] collects the nodes whose CG has ended (their trial point may be taken).
 // Either phase ends by writing, per node, (stop ordinal or CG_LIVE_ORD, h_M_norm, cg_it) to host_scalars[node * CG_SUMMARY + 0..2] and
-// raising *host_flag to seq (same protocol as launch_reduce).
-// seq == 0 (a launch captured into a graph): the flag is raised to *dev_seq + 1; *dev_seq always ends up holding the value used.
+// raising the flag.
 void launch_cg_scal(hipStream_t st, const SegTable &T, int nnodes, int phase, const double *partials, CgNode *cg,
-                    NodeBits *dmask, double *host_scalars, unsigned *arrived, unsigned long long *host_flag,
-                    unsigned long long seq, unsigned long long *dev_seq);
+                    NodeBits *dmask, double *host_scalars, ReadbackFlag flag);
 bool prof_enabled();
 
 // ---- multifrontal SPD solve (spd.h) ----

@@ -1660,7 +1660,7 @@ __device__ __forceinline__ void cg_scal_node(int a, int phase, bool mine, const 
 // the last of `expected` arrivals raises the host's flag (shared by k_reduce's successors; one thread)
 // seq: the value the host's flag is raised to.  A launch replayed from a captured graph cannot carry a fresh value in its
 // arguments: with seq == 0 the value is the device word *dev_seq + 1; either way *dev_seq ends up holding the value used,
-// so that eager launches and replays can follow each other (the host counts along: Group::fetch_seq_).
+// so that eager launches and replays can follow each other (the host counts along: Schedule::segment).
 __device__ __forceinline__ void flag_arrive(unsigned *arrived, unsigned expected, int phase, NodeBits *dmask,
                                             unsigned long long *host_flag, unsigned long long seq, unsigned long long *dev_seq) {
   __atomic_thread_fence(__ATOMIC_RELEASE);
@@ -2703,8 +2703,8 @@ void launch_tnt_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bi
 
 void launch_cg_scal_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
                            double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                           NodeBits *dmask, double *host_tnt, double *host_scalars, unsigned *arrived, unsigned long long *host_flag,
-                           unsigned long long seq, unsigned long long *dev_seq, double *dev_tnt, int upd_nslots, double *upd_host) {
+                           NodeBits *dmask, double *host_tnt, double *host_scalars, ReadbackFlag flag, double *dev_tnt, int upd_nslots,
+                           double *upd_host) {
   TntBegin B;
   B.bits = bits; B.use_precon = use_precon; B.max_it = max_it;
   B.grad_tol = grad_tol; B.pgrad_tol = pgrad_tol; B.kappa = kappa; B.theta = theta;
@@ -2712,16 +2712,15 @@ void launch_cg_scal_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBit
   if (upd_nslots > 6) { fprintf(stderr, "[dpgo_amd] ERROR: k_cg_scal_begin carries at most six sums of an update.\n"); return; }
   ProfScope ps(PK_REDUCE, st, 8.0 * (10 * T.nseg_own + upd_nslots * T.nseg_all));
   hipLaunchKernelGGL(k_cg_scal_begin, dim3(nnodes), dim3(upd_nslots > 0 ? 1024 : 640), 0, st, T, B, partials, cg, dmask, host_tnt, host_scalars,
-                     arrived, host_flag, seq, dev_seq, dev_tnt, upd_nslots, upd_host);
+                     flag.arrived, flag.host, flag.seq, flag.dev_seq, dev_tnt, upd_nslots, upd_host);
 }
 int cg_first_slot() { return CG_FIRST_SLOT; }
 
 void launch_cg_scal(hipStream_t st, const SegTable &T, int nnodes, int phase, const double *partials, CgNode *cg,
-                    NodeBits *dmask, double *host_scalars, unsigned *arrived, unsigned long long *host_flag,
-                    unsigned long long seq, unsigned long long *dev_seq) {
+                    NodeBits *dmask, double *host_scalars, ReadbackFlag flag) {
   ProfScope ps(PK_REDUCE, st, 8.0 * (phase == 0 ? 4 : 1) * T.nseg_own);
-  hipLaunchKernelGGL(k_cg_scal, dim3(nnodes), dim3(256), 0, st, T, phase, partials, cg, dmask, host_scalars, arrived,
-                     host_flag, seq, dev_seq);
+  hipLaunchKernelGGL(k_cg_scal, dim3(nnodes), dim3(256), 0, st, T, phase, partials, cg, dmask, host_scalars, flag.arrived,
+                     flag.host, flag.seq, flag.dev_seq);
 }
 
 void launch_dots(int d, hipStream_t st, const SegTable &T, NodeMask mask, int n, const double *const *a,
@@ -2849,10 +2848,9 @@ void launch_star_sums(hipStream_t st, const SegTable &T, int nnodes, unsigned va
   for (int q = 0; q < 6; q++) sl.s[q] = slots6[q];
   hipLaunchKernelGGL(k_star_sums, dim3(1), dim3(384), 0, st, T, nnodes, valid_slots, sl, partials, out);
 }
-void launch_publish(hipStream_t st, const double *vals, int n, double *host, unsigned long long *host_flag, unsigned long long seq,
-                    unsigned long long *dev_seq) {
+void launch_publish(hipStream_t st, const double *vals, int n, double *host, ReadbackFlag flag) {
   ProfScope ps(PK_REDUCE, st, 8.0 * n);
-  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, vals, n, host, host_flag, seq, dev_seq);
+  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, vals, n, host, flag.host, flag.seq, flag.dev_seq);
 }
 
 // ---- the gate of a speculative update (Group::speculate_update): one lane per node evaluates, from the trial point's sums, the refinement's start (k_cg_scal_begin) and the CG's state, whether the iteration
@@ -2925,18 +2923,17 @@ __global__ __launch_bounds__(64) void k_reduce_gate(SegTable T, int nslots, cons
   }
 }
 void launch_reduce_gate(hipStream_t st, const SegTable &T, int nnodes, int nslots, const double *partials, double *host_scalars,
-                        unsigned *arrived, unsigned long long *host_flag, unsigned long long seq, unsigned long long *dev_seq,
-                        double *dev_scalars, const AmmGate &G, const double *tnt, const CgNode *cg, NodeBits *go, double *host_out) {
+                        ReadbackFlag flag, double *dev_scalars, const AmmGate &G, const double *tnt, const CgNode *cg, NodeBits *go,
+                        double *host_out) {
   ProfScope ps(PK_REDUCE, st, 8.0 * nslots * T.nseg_own);
-  hipLaunchKernelGGL(k_reduce_gate, dim3(nnodes * nslots), dim3(64), 0, st, T, nslots, partials, host_scalars, arrived, host_flag, seq,
-                     dev_seq, dev_scalars, G, tnt, cg, go, host_out);
+  hipLaunchKernelGGL(k_reduce_gate, dim3(nnodes * nslots), dim3(64), 0, st, T, nslots, partials, host_scalars, flag.arrived, flag.host,
+                     flag.seq, flag.dev_seq, dev_scalars, G, tnt, cg, go, host_out);
 }
 void launch_reduce(hipStream_t st, const SegTable &T, int nnodes, bool all_rows, int nslots, const double *partials,
-                   double *host_scalars, unsigned *arrived, unsigned long long *host_flag, unsigned long long seq,
-                   unsigned long long *dev_seq) {
+                   double *host_scalars, ReadbackFlag flag) {
   ProfScope ps(PK_REDUCE, st, 8.0 * nslots * T.nseg_all);
   hipLaunchKernelGGL(k_reduce, dim3(nnodes * nslots), dim3(64), 0, st, T, all_rows ? 1 : 0, nslots, partials, host_scalars,
-                     arrived, host_flag, seq, dev_seq);
+                     flag.arrived, flag.host, flag.seq, flag.dev_seq);
 }
 
 void launch_set_coefs(hipStream_t st, const NodeCoefs &C, int n, double *dev) {

@@ -43,16 +43,6 @@ struct NodeTnt {
 };
 }  // namespace
 
-// The CG steps of a group go out as one graph replay each (a step is 13-21 launches with fixed arguments): wherever the
-// segments of the iteration are replayed (Group::segment, iter_graph_wanted), and -- round 4's default, measured +8..13 % on
-// city10000 -- from the start for groups of at least two nodes and at most 40 000 poses, whose steps are bound by the host's
-// launch rate.  DPGO_CG_GRAPH=0 keeps just these eager (A/B hook), DPGO_ITER_GRAPH=0 everything.
-bool Group::cg_graph_wanted() const {
-  if (!settings().cg_graph || settings().iter_graph == 0 || graphs_broken_ || prof_enabled()) return false;
-  if (iter_graph_wanted()) return true;
-  return P0_ <= 40000 && num_local() >= 2;
-}
-
 bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, const double *g_alt, bool base_ready,
                     const std::function<bool()> *confirm) {
   if (!confirm) finish_update();
@@ -148,7 +138,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     // <s,s>, <grad,s>, <s,Hs>, <x+,g>, <x+,g_alt>, <x+,nprop> in the partial slots 0..5
     apply_tcol(xprop, T1_.p, nprop, 0, nullptr, nullptr, nullptr, nullptr, nullptr, partials_.p, g, ga, sk, grad, hh);
     // (with_reduce = false: the caller launches the reduction itself, with the gate of a speculative update: group.h)
-    if (with_reduce) launch_reduce(st_, T_, L, false, nslots, partials_.p, h_scal_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+    if (with_reduce) launch_reduce(st_, T_, L, false, nslots, partials_.p, h_scal_, sched_.flag());
   };
   // acceptance test and trust-region update of node a from the sums of its trial point (TNT.h:537-607)
   std::vector<int> acc, requad;
@@ -210,7 +200,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     apply_tcol(w3, w1, nullptr, 2, X, nabla, pk, Hp, first ? grad : rk, sums);   // Hp and <p,Hp>, <Hp,Hp>, <p,p>, <p,r>
     // the step-length logic
     if (begin) (*begin)(sums);
-    else launch_cg_scal(st_, T_, L, 0, partials_.p, cg_.p, dmask_.p, h_cg_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+    else launch_cg_scal(st_, T_, L, 0, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
     // s += c1 p, H s += c1 H p for every node of the step (a node that stops here takes its boundary step), r += alpha H p
     // for those that go on
     launch_cg_step(d_, st_, T_, first ? NodeMask{bitsA, nullptr} : mA, NodeCoefs(), pk, Hp, sk, hh, rk, cg_.p, first ? grad : nullptr,
@@ -228,7 +218,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       const double *pa[MAX_DOTS] = {rk}, *pb[MAX_DOTS] = {vk};
       launch_dots(d_, st_, T_, cur_mask_, 1, pa, pb, P2, partials_.p, 0);
     }
-    launch_cg_scal(st_, T_, L, 1, partials_.p, cg_.p, dmask_.p, h_cg_, reduce_arrived_.p, h_flag_, next_seq(), dev_seq_.p);
+    launch_cg_scal(st_, T_, L, 1, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
     launch_cg_dir(d_, st_, T_, cur_mask_, cg_.p, vk, pk);
   };
   // what a segment's key must hold beside the rotating buffers (segment()): the vectors of this call and its variant
@@ -257,7 +247,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     }, 1);
     mA = sA; mB = sB;
   };
-  const bool use_graph = cg_graph_wanted();
+  const bool use_graph = sched_.cg_graph_wanted();
   // The nodes still iterating after scalar step `w` of this run (phase 0 / 1 of step j: 2 j - 1 / 2 j).  The summary of a
   // later step may already have overwritten the one waited for; it carries the ordinal each node stopped at (kernels.h,
   // CG_LIVE_ORD), so the answer -- and with it the node sets and tile classes of the next launches -- is the same however
@@ -308,11 +298,11 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       for (int a : nodes) Delta[a] = S[a].Delta;
       const std::function<void(const double *)> begin = [&](const double *) {
         // (update()'s reduction, if it is still waiting for somebody to take it along: group.h, UpdLazy)
-        const int carry = (upd_lazy_.pending && !capturing_) ? upd_lazy_.nslots : 0;
+        const int carry = (upd_lazy_.pending && !sched_.capturing()) ? upd_lazy_.nslots : 0;
         launch_cg_scal_begin(st_, T_, L, bitsA, use_precon, o.max_tCG_iterations, o.grad_norm_tol, o.preconditioned_grad_norm_tol,
-                             o.STPCG_kappa, o.STPCG_theta, Delta.data(), partials_.p, cg_.p, dmask_.p, h_tnt_, h_cg_, reduce_arrived_.p,
-                             h_flag_, next_seq(), dev_seq_.p, dev_tnt_.p, carry, h_upd_);
-        if (carry) { upd_lazy_.pending = false; pending_seq_ = fetch_seq_; }
+                             o.STPCG_kappa, o.STPCG_theta, Delta.data(), partials_.p, cg_.p, dmask_.p, h_tnt_, h_cg_, sched_.flag(),
+                             dev_tnt_.p, carry, h_upd_);
+        if (carry) { upd_lazy_.pending = false; pending_seq_ = sched_.last_seq(); }
       };
       merged = fused_;
       if (!merged)
@@ -326,7 +316,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     mA = live_mask(bitsA, dmask_.p);   // (a replay does not run the body: the host's copies)
     mB = live_mask(bitsA, dmask_.p + 1);
     cur_mask_ = live_mask(bits_nodes, nullptr);
-    seq_first = fetch_seq_;   // (the flag of the last launch of the segment: the trial point's reduction, or the first step's scalars)
+    seq_first = sched_.last_seq();   // (the flag of the last launch of the segment: the trial point's reduction, or the first step's scalars)
     // the caller's read-back (the scalars that decide whether these nodes are refined at all) is taken NOW, with the start
     // of the refinement already on the GPU: the stream never waits for that decision
     if (confirm && !(*confirm)()) return false;
@@ -336,7 +326,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       seq_first = spec_upd_.seq_trial;
     } else seqA = seq_first - (spec ? 1 : 0);
   } else {
-    flush_deferred();   // (launches that were waiting for this refinement's first segment: there is none on this path)
+    sched_.flush_deferred();   // (launches that were waiting for this refinement's first segment: there is none on this path)
     if (confirm && !(*confirm)()) return false;
     const bool have_sums = quad_model(X, base_ready);
     norms(nodes, true, have_sums);
@@ -380,7 +370,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       mA = live_mask(bitsA, dmask_.p);
       mB = live_mask(bitsA, dmask_.p + 1);
       stepA(true);
-      seqA = fetch_seq_;
+      seqA = sched_.last_seq();
     }
     // The first step (enqueued above, or -- with `dev` -- in front of the loop).
     if (dev && spec) wait_flag(seq_first);   // (the trial point's reduction: everything before it is there too)
@@ -408,11 +398,11 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     if (dev) tnt_speculate_ = !more_steps;   // speculate next time if nobody needed a second step this time
     if (more_steps) {
       stepB();
-      unsigned long long seqB = fetch_seq_;
+      unsigned long long seqB = sched_.last_seq();
       for (int w = 2;; w += 2) {
         if (use_graph) graph_step();
         else { stepA(false); stepB(); }
-        const unsigned long long next = fetch_seq_;
+        const unsigned long long next = sched_.last_seq();
         wait_flag(seqB);   // the outcome of the step before the one just enqueued (its phase 1: scalar step w)
         if (!any_live(w)) break;
         seqB = next;
@@ -436,7 +426,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       int nslots = std::max((int)NSUM, deferred_slots_);
       deferred_slots_ = 0;
       segment(22, mrest.v, {K(X), kg, kga, (unsigned long long)nslots}, [&] { enqueue_trial(mrest, false, nslots); });
-      wait_flag(fetch_seq_);
+      wait_flag(sched_.last_seq());
       for (int a : rest)
         for (int q = 0; q < NSUM; q++) tsum[(size_t)a * NSUM + q] = scal(a, q);
     }

@@ -6,7 +6,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=/tmp/dpgo_asan
 mkdir -p $out
 cd $root/dpgo_amd/csrc
-for f in settings graph spd assemble chordal group spd_solve tnt dchordal comm pcm capi; do
+for f in settings graph spd assemble chordal schedule group spd_solve tnt dchordal comm pcm capi; do
   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -fPIC -fopenmp -fsanitize=address -fno-omit-frame-pointer -Wno-option-ignored -c $f.cpp -o $out/$f.o
 done
 hipcc --offload-arch=gfx950 -std=c++17 -O1 -fPIC -fopenmp -c kernels.hip -o $out/kernels.o
