@@ -13,6 +13,8 @@ inner step of ``dist_pgo``:
   dist_pgo driver loop      dist_pgo.cpp:446-531  DistPGO
   DPGO::PCM                 PCM.h:10-71           PCM(device).update(graph, alpha, beta, X) / solve_exact / ...;
                                                   pcm_inliers(graph, X) -> keep mask, Graph.filter_edges(keep)
+  SESyncProblem::verify_solution                  NodeGroup.certify(X) -> (CertResult, x); cert_lambda, cert_apply
+                            SESyncProblem.cpp:375-468, SESync_utils.cpp:721-830 (fast_verification STEP 2)
 
 All compute runs in hand-written HIP kernels behind the C ABI of
 include/dpgo_amd.h.  There is NO CPU fallback: creating a NodeGroup without a
@@ -209,6 +211,11 @@ SYMBOLS = {
     "dpgo_pcm_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "dpgo_max_clique": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dpgo_graph_filter_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "dpgo_cert_options_default": (None, [C.c_void_p]),
+    "dpgo_group_certify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int]),
+    "dpgo_group_cert_lambda": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP]),
+    "dpgo_group_cert_apply": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
+    "dpgo_debug_rayleigh_ritz": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _IP]),
 }
 
 
@@ -617,6 +624,54 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_evaluate failed")
         return (F.value, g2.value, G) if want_grad else (F.value, g2.value)
 
+    def certify(self, X, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True, stop_on_negative=True, seed=0, V0=None,
+                refresh_every=50):
+        """Is X the global minimum of the trivial-loss problem?  LOBPCG with block size d on the certificate matrix
+        S = M - Lambda(X) (SESyncProblem::verify_solution, C++/SESync/src/SESyncProblem.cpp:375-468; fast_verification
+        STEP 2, C++/SESync/src/SESync_utils.cpp:765-826).  Returns (CertResult, x): x is a unit vector of length (d+1)N,
+        theta = x' S x and residual = |S x - theta x| come from one fresh product with it, and status is
+        CERT_NEGATIVE (theta < -eta/2: x proves lambda_min(S) < -eta/2), CERT_NONNEGATIVE (column 0 converged with
+        theta >= -eta/2 -- evidence, NOT proof: a converged Ritz pair need not be the smallest one, and the reference's
+        proof, a Cholesky factorisation of S + eta I, is not part of this library) or CERT_UNDECIDED (max_iters
+        reached).  stationarity = |S X|_F is the Riemannian gradient norm: the certificate only means something at a
+        critical point.  The group must have the trivial loss and host every node; the optimiser's state is untouched.
+        V0: the initial block ((d+1)N x d), default seeded Gaussians."""
+        X, ld = _fcol(X)
+        o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
+                        stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
+        v0, ldv0 = None, 0
+        if V0 is not None:
+            V0 = np.asarray(V0)
+            if V0.shape != X.shape:
+                raise ValueError("certify: V0 must have the shape of X, %r" % (X.shape,))
+            V0, ldv0 = _fcol(V0)
+            v0 = _dp(V0)
+        res = CertResult()
+        x = np.zeros(X.shape[0])
+        if lib().dpgo_group_certify(self._h, _dp(X), ld, C.byref(o), v0, ldv0, C.byref(res), _dp(x), x.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_certify failed (robust loss, a group that does not host every node, or bad sizes)")
+        return res, x
+
+    def cert_lambda(self, X):
+        """compute_Lambda_blocks (SESyncProblem.cpp:375-395): the N symmetric d x d blocks of Lambda(X), (N, d, d)."""
+        X, ld = _fcol(X)
+        L = np.zeros((self.graph.num_poses, self.d, self.d))
+        if lib().dpgo_group_cert_lambda(self._h, _dp(X), ld, _dp(L)) != 0:
+            raise RuntimeError("dpgo_group_cert_lambda failed")
+        return L
+
+    def cert_apply(self, X, V):
+        """S(X) V for a block V of the shape of X (the operator of verify_solution alone)."""
+        X, ld = _fcol(X)
+        V = np.asarray(V)
+        if V.shape != X.shape:
+            raise ValueError("cert_apply: V must have the shape of X, %r" % (X.shape,))
+        V, ldv = _fcol(V)
+        SV = np.zeros_like(X, order="F")
+        if lib().dpgo_group_cert_apply(self._h, _dp(X), ld, _dp(V), ldv, _dp(SV), SV.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_cert_apply failed")
+        return SV
+
     def set_options(self, options):
         rc = lib().dpgo_group_set_options(self._h, C.byref(options))
         if rc == 0:
@@ -871,6 +926,44 @@ class DPGOStar:
         X = np.zeros(((self.graph.d + 1) * self.graph.num_poses, self.graph.d), order="F")
         self.group.scatter_global(X)
         return X
+
+
+CERT_UNDECIDED, CERT_NONNEGATIVE, CERT_NEGATIVE = 0, 1, 2
+CERT_NAMES = {0: "UNDECIDED", 1: "NONNEGATIVE", 2: "NEGATIVE"}
+
+
+class CertOptions(C.Structure):
+    """dpgo_cert_options_t: eta (SESync.h:88), tau (LOBPCG.h:138), max_iters, precondition, stop_on_negative, refresh_every, seed."""
+    _fields_ = [("eta", C.c_double), ("tau", C.c_double), ("max_iters", C.c_int), ("precondition", C.c_int),
+                ("stop_on_negative", C.c_int), ("refresh_every", C.c_int), ("seed", C.c_ulonglong)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().dpgo_cert_options_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class CertResult(C.Structure):
+    """dpgo_cert_result_t."""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("restarts", C.c_int), ("theta", C.c_double),
+                ("residual", C.c_double), ("S_norm_est", C.c_double), ("stationarity", C.c_double)]
+
+
+def rayleigh_ritz(A, B, nblk):
+    """The host's Rayleigh-Ritz step (dpgo_debug_rayleigh_ritz): A, B symmetric n x n, n = ns * nblk.  Returns (theta, C, used):
+    the ns smallest Ritz values, C (n x ns) with C' B C = I and C' A C = diag(theta), and the number of blocks used (a
+    mass-matrix pivot below 1e-12 after scaling drops the last block)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    n = A.shape[0]
+    if A.shape != (n, n) or B.shape != (n, n) or n % nblk:
+        raise ValueError("rayleigh_ritz: A and B must be square of a size divisible by nblk")
+    ns = n // nblk
+    theta, Cm, used = np.zeros(ns), np.zeros((n, ns)), np.zeros(1, np.int32)
+    if lib().dpgo_debug_rayleigh_ritz(ns, int(nblk), _dp(A), _dp(B), _dp(theta), _dp(Cm), _ip(used)) != 0:
+        raise RuntimeError("dpgo_debug_rayleigh_ritz failed")
+    return theta, Cm, int(used[0])
 
 
 class PCMOptions(C.Structure):

@@ -11,6 +11,7 @@
 #include <numeric>
 #include <set>
 
+#include "cert.h"
 #include "comm.h"
 #include "group.h"
 #include "pcm.h"
@@ -895,6 +896,46 @@ int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dp
     *out = f;
     return 0;
   });
+}
+
+// ---- solution certificate (cert.h): SESyncProblem::verify_solution / fast_verification STEP 2
+// (C++/SESync/src/SESyncProblem.cpp:375-468, C++/SESync/src/SESync_utils.cpp:721-830) ----
+void dpgo_cert_options_default(dpgo_cert_options_t *o) {
+  if (!o) return;
+  const dpgo::CertOptions c;
+  o->eta = c.eta; o->tau = c.tau; o->max_iters = c.max_iters; o->precondition = c.precondition;
+  o->stop_on_negative = c.stop_on_negative; o->refresh_every = c.refresh_every; o->seed = c.seed;
+}
+
+int dpgo_group_certify(dpgo_group_t *h, const double *X, int ld, const dpgo_cert_options_t *opts, const double *V0, int ldv0,
+                       dpgo_cert_result_t *result, double *x, int ldx) {
+  if (!h || !h->grp || !X || !opts || !result) return -1;
+  return guarded([&] {
+    dpgo::CertOptions o;
+    o.eta = opts->eta; o.tau = opts->tau; o.max_iters = opts->max_iters; o.precondition = opts->precondition;
+    o.stop_on_negative = opts->stop_on_negative; o.refresh_every = opts->refresh_every; o.seed = opts->seed;
+    dpgo::CertResult r;
+    const int rc = h->grp->certify(X, ld, o, V0, ldv0, r, x, ldx);
+    result->status = r.status; result->iterations = r.iterations; result->restarts = r.restarts;
+    result->theta = r.theta; result->residual = r.residual; result->S_norm_est = r.S_norm_est;
+    result->stationarity = r.stationarity;
+    return rc;
+  });
+}
+
+int dpgo_group_cert_lambda(dpgo_group_t *h, const double *X, int ld, double *Lambda) {
+  if (!h || !h->grp || !X || !Lambda) return -1;
+  return guarded([&] { return h->grp->cert_lambda(X, ld, Lambda); });
+}
+
+int dpgo_group_cert_apply(dpgo_group_t *h, const double *X, int ld, const double *V, int ldv, double *SV, int ldsv) {
+  if (!h || !h->grp || !X || !V || !SV) return -1;
+  return guarded([&] { return h->grp->cert_apply(X, ld, V, ldv, SV, ldsv); });
+}
+
+int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {
+  if (!A || !B || !theta || !C || !used) return -1;
+  return guarded([&] { return dpgo::rayleigh_ritz(ns, nblk, A, B, theta, C, used); });
 }
 
 }  // extern "C"

@@ -1,0 +1,96 @@
+// Solution certification: is the point X the optimiser stopped at the global minimum of the trivial-loss problem?
+//
+// The reference answers this in its SE-Sync tree: SESyncProblem::compute_Lambda_blocks / verify_solution
+// (C++/SESync/src/SESyncProblem.cpp:375-468) build the certificate matrix S = M - Lambda(X), and fast_verification
+// (C++/SESync/src/SESync_utils.cpp:721-830) looks for its smallest eigenvalue with LOBPCG
+// (C++/Optimization/include/Optimization/LinearAlgebra/LOBPCG.h:131-337).  Here:
+//
+//  * X is (d+1)N x d, column-major, rows 0..N-1 the translations, rows N + d p + r the rows of Y_p = R_p^T
+//    (C++/DPGO/include/DPGO/DPGOProblem.h:167-171); M is the global data matrix of the trivial loss
+//    (construct_data_matrix, C++/DPGO/src/DPGO_utils.cpp:440-718; F = 1/2 tr(X^T M X)).
+//  * Lambda_p = 1/2 (P + P^T), P = (M X)[rows of Y_p] (X[rows of Y_p])^T (SESyncProblem.cpp:375-395 with Y = X^T), and
+//    S = M - blkdiag(0_N, Lambda_0, ..., Lambda_{N-1}) (:444-447, the translation-explicit form).  On a record array V
+//    (one (d+1) x d record per pose): (S V)_p.x = (M V)_p.x, (S V)_p.Y = (M V)_p.Y - Lambda_p V_p.Y.
+//  * |S X|_F is the norm of the Riemannian gradient: the certificate only means something at a critical point, so the
+//    result carries it as `stationarity`.
+//  * The search is LOBPCG on S with block size d, basis [V W P] (LOBPCG.h:131-337; fast_verification STEP 2,
+//    SESync_utils.cpp:765-826): |S| is estimated as |S Omega|_F / |Omega|_F on a Gaussian block (LOBPCG.h:199-214),
+//    column 0 counts as converged when r_0 <= tau (|S|_est + |theta_0|) |x_0| (:298-307), and with stop_on_negative
+//    the search ends at once when theta_0 < -eta / 2 (SESync_utils.cpp:775-793).
+//  * theta and residual of the result are recomputed from ONE fresh product S x of the returned unit vector x
+//    (theta = x^T S x, residual = |S x - theta x|), and the status is decided from those two numbers:
+//      NEGATIVE     theta < -eta / 2: x proves lambda_min(S) < -eta / 2;
+//      NONNEGATIVE  otherwise, and residual <= tau (|S|_est + |theta|): column 0 converged.  EVIDENCE, NOT PROOF: a
+//                   converged Ritz pair need not be the smallest one (the reference proves lambda_min >= -eta with a
+//                   Cholesky factorisation of S + eta I, fast_verification STEP 1, :731-754 -- not part of this code);
+//      UNDECIDED    max_iters reached without either.
+//
+// Stated deviations from the reference:
+//  - the block size is fixed to d: a block of d vectors of length (d+1)N IS a pose-record array, so the search runs
+//    on the group's record layout, its block-sparse operators, its segment table and its halo copy;
+//  - the preconditioner is block Jacobi, T_p = (M_pp)^-1 with M_pp the pose's (d+1) x (d+1) diagonal block of M
+//    (identity for a pose without an edge), where the reference uses an incomplete LDL^T factor (STEP 3);
+//  - trivial loss only: a group created with a robust loss returns -1 (its S operator is not assembled,
+//    Group::upload_operators, and the certificate theory is that of the quadratic objective).  Whoever optimised with
+//    a robust loss creates a second group with LOSS_NONE and max_iterations = 0;
+//  - the group must host every node of the graph (-1 otherwise: the products would need the boundary exchange);
+//  - the Rayleigh-Ritz step is a scaled Cholesky reduction + cyclic Jacobi on the host; rounding is not Eigen's.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace dpgo {
+
+enum { CERT_UNDECIDED = 0, CERT_NONNEGATIVE = 1, CERT_NEGATIVE = 2 };
+
+struct CertOptions {
+  double eta = 1e-3;   // min_eig_num_tol, C++/SESync/include/SESync/SESync.h:88
+  double tau = 1e-6;   // LOBPCG.h:138
+  int max_iters = 2000;
+  int precondition = 1;
+  int stop_on_negative = 1;
+  int refresh_every = 50;   // S V, S P by real products every so many iterations (drift of the recurrences)
+  unsigned long long seed = 0;
+};
+
+struct CertResult {
+  int status = CERT_UNDECIDED, iterations = 0, restarts = 0;
+  double theta = 0, residual = 0, S_norm_est = 0, stationarity = 0;
+};
+
+// ---- the host's Rayleigh-Ritz step (cert.cpp; no device) ----
+// A, B: n x n row-major symmetric, n = ns * nblk (the Gram matrices B^T S B and B^T B of the basis, nblk blocks of ns
+// columns).  Both are scaled by diag(B)^-1/2, B is Cholesky-factored; a pivot below 1e-12 drops the LAST block (the
+// usual LOBPCG restart without P) and the step is redone on the leading blocks.  theta: the ns smallest Ritz values,
+// ascending; C: n x ns row-major, C^T B C = I, C^T A C = diag(theta), rows of dropped blocks zero; *used: blocks used.
+// -1 when not even the first block has a positive definite mass matrix.
+int rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used);
+
+// ---- kernels (cert.hip) ----
+constexpr int cert_ntri(int d) { return 3 * d * (3 * d + 1) / 2; }          // upper triangle of a 3d x 3d matrix
+constexpr int cert_nsums(int d) { return 2 * cert_ntri(d) + 2 * d; }        // both Gram matrices + the stopping test's norms
+constexpr int cert_tri(int n, int a, int b) { return a * n - a * (a - 1) / 2 + (b - a); }   // a <= b
+struct CertCoef {
+  double C[27];      // 3d x d row-major: rows [0, d) multiply V, [d, 2d) W, [2d, 3d) P
+  double theta[3];
+};
+// All over the own rows, one workgroup per own segment; partial sums are stored at partials[s * T.nseg_own + segment].
+// Lam[p] (d x d row-major) from the records of X and M X; with SX: (S X) stored; partial 0 = |(S X)_p|^2
+void launch_cert_lambda(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X, const double *MX, double *Lam,
+                        double *SX, double *partials);
+// out = MV - [0 ; Lam V.Y]  (out may be MV)
+void launch_cert_apply(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *MV,
+                       double *out);
+// SW <- SW - [0 ; Lam W.Y] (SW holds M W on entry), then the upper triangles of B^T B (sums [0, ntri)) and B^T (S B)
+// (sums [ntri, 2 ntri)), B = [V W P]
+void launch_cert_gram(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *W,
+                      const double *P, const double *SV, double *SW, const double *SP, double *partials);
+// P' = W C_w + P C_p, V' = V C_v + P', the same for S V', S P'; R' = S V' - V' diag(theta); W' = Tp R' (Tp: (d+1)^2 per
+// pose, null: R'); sums 2 ntri + j = |R'_j|^2, 2 ntri + d + j = |V'_j|^2
+void launch_cert_update(int d, hipStream_t st, const SegTable &T, NodeMask mask, const CertCoef &c, const double *Tp, double *V,
+                        double *W, double *P, double *SV, const double *SW, double *SP, double *partials);
+// host[s] = sum over the own segments of partial s, s < nsums, in segment order; then the flag
+void launch_cert_reduce(hipStream_t st, const SegTable &T, int nsums, const double *partials, double *host, ReadbackFlag flag);
+
+}  // namespace dpgo

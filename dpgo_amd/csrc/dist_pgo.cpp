@@ -3,6 +3,11 @@
 // Mirrors C++/examples/dist_pgo.cpp:
 //   flags      --dataset --num_nodes --iters[1000] --dist_init[true] --loss[trivial|huber|welsch]
 //              --accelerated[true] --save[true]                                     (:23-47)
+//              --certify (not in the reference's driver; off: every output is as without it)  after the loop, for the trivial
+//              loss and a world of one rank, one more line on stdout
+//                  certificate: <status> <theta> <residual> <iterations> <stationarity>
+//              from dpgo_group_certify (SESyncProblem::verify_solution, C++/SESync/src/SESyncProblem.cpp:397-468); with a
+//              robust loss or several ranks a line that says why not
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -38,7 +43,7 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true;
+  bool dist_init = true, accelerated = true, save = true, certify = false;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -53,7 +58,9 @@ int main(int argc, char **argv) {
       printf("Program options:\n  --dataset arg\n  --num_nodes arg\n  --iters arg (=1000)\n  --dist_init arg (=true)\n"
              "  --loss arg (=trivial)   trivial, huber or welsch\n  --accelerated arg (=true)\n  --save arg (=true)\n  --gpu arg (=0)\n");
       return 0;
-    } else if (const char *v = val("--dataset")) dataset = v;
+    } else if (a == "--certify") certify = true;
+    else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
+    else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
     else if (const char *v = val("--dist_init")) dist_init = parse_bool(v);
@@ -163,6 +170,23 @@ int main(int argc, char **argv) {
   if (root)
     printf("---------------------------------------\nfinal objective: %.20g\nfinal gradient: %.20g\ntime: %.20g s/node.\n", fobj,
            grad, time / per);
+  if (certify) {
+    if (loss != 0) {
+      if (root) printf("certificate: not computed (the certificate is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("certificate: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0);
+      dpgo_cert_options_t co;
+      dpgo_cert_options_default(&co);
+      dpgo_cert_result_t cr;
+      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 || dpgo_group_certify(grp, Xc.data(), ld, &co, nullptr, 0, &cr, nullptr, 0) != 0)
+        return -1;
+      printf("certificate: %s %.16g %.16g %d %.16g\n",
+             cr.status == DPGO_CERT_NEGATIVE ? "NEGATIVE" : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED", cr.theta,
+             cr.residual, cr.iterations, cr.stationarity);
+    }
+  }
   if (save) {
     std::fill(X.begin(), X.end(), 0.0);
     dpgo_group_scatter_global(grp, X.data(), ld);

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "assemble.h"
+#include "cert.h"
 #include "graph.h"
 #include "kernels.h"
 #include "schedule.h"
@@ -159,6 +160,12 @@ class Group {
   double star_fobj() const { return star_fobj_; }
   double star_fobjh() const { return star_fobjh_; }
   int star_branches() const { return star_branches_; }   // bit 0 pm, bit 1 mm, bit 2 phi fallback
+  // ---- solution certificate (cert.h, cert.cpp): LOBPCG on S = M - Lambda(X) (C++/SESync/src/SESyncProblem.cpp:375-468,
+  // C++/SESync/src/SESync_utils.cpp:721-830).  X: global (d+1)N x d; trivial loss, every node of the graph local; the
+  // optimiser's state is untouched.  V0 (optional): the initial block, (d+1)N x d; x (optional): the returned unit vector
+  int certify(const double *X, int ld, const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x, int ldx);
+  int cert_lambda(const double *X, int ld, double *Lambda);   // N blocks d x d, row-major, by global pose
+  int cert_apply(const double *X, int ld, const double *V, int ldv, double *SV, int ldsv);   // SV = S(X) V
   // boundary exchange across groups: records of the poses other groups need
   int num_sent() const { return (int)sent_rows_.size(); }
   // device buffer, num_sent()*RS doubles; st: the stream to enqueue on (default: the group's)
@@ -366,6 +373,16 @@ class Group {
   void join_exchange();              // the group's stream waits for it
   struct ChordalState;
   ChordalState *ch_ = nullptr;
+  struct CertState;   // the certificate's buffers (cert.cpp), allocated by the first call
+  CertState *cert_ = nullptr;
+  void cert_release();
+  int cert_begin(const double *X, int ld);
+  int cert_prepare(const double *X, int ld, double *stationarity);
+  void cert_upload(const double *M, int ld, int ncols, double *dev_all);
+  void cert_download(const double *dev_own, double *M, int ld, int ncols);
+  void cert_apply_M(double *in_all, double *out_own);
+  void cert_apply_S(double *in_all, double *out_own);
+  void cert_build_precon();
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

@@ -1,8 +1,10 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
-// Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).
+// Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
+// point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
+//   certificate: <NEGATIVE|NONNEGATIVE|UNDECIDED|FAILED> <theta> <residual> <iterations> <stationarity>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -48,6 +50,18 @@ int main(int argc, char **argv) {
   for (int it = 1; it <= iters; it++) {
     if (dpgo_hash.iterate() != 0 || dpgo_hash.communicate() != 0 || dpgo_hash.update() != 0) return 1;
     report(it);
+  }
+  if (argc > 6 && !strcmp(argv[6], "certify")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), x;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    double theta = 0;
+    int its = 0, status = -1;
+    dpgo_cert_result_t r = {};
+    dpgo_hash.verify_solution(X, 1e-3, theta, x, its, &status, &r);
+    const char *name = status == DPGO_CERT_NEGATIVE ? "NEGATIVE" : status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE"
+                       : status == DPGO_CERT_UNDECIDED ? "UNDECIDED" : "FAILED";
+    fprintf(stderr, "certificate: %s %.10e %.10e %d %.10e\n", name, theta, r.residual, its, r.stationarity);
+    if (status < 0) return 1;
   }
   return 0;
 }

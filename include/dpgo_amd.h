@@ -333,6 +333,61 @@ int dpgo_max_clique(int m, const unsigned char *dense, int exact, unsigned char 
  * closures PCM rejected before building groups.  -1 if no edge is kept. */
 int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dpgo_graph_t **out);
 
+/* ---- solution certificate: is the point the optimiser stopped at the global minimum? -------------------------
+ * The reference answers this in its SE-Sync tree: SESyncProblem::compute_Lambda_blocks / verify_solution
+ * (C++/SESync/src/SESyncProblem.cpp:375-468) and fast_verification (C++/SESync/src/SESync_utils.cpp:721-830) with LOBPCG
+ * (C++/Optimization/include/Optimization/LinearAlgebra/LOBPCG.h:131-337).  X is the GLOBAL iterate ((d+1)N x d,
+ * column-major, rows 0..N-1 translations, rows N + d p + r the rows of Y_p = R_p^T; DPGOProblem.h:167-171), M the data
+ * matrix of the trivial loss (construct_data_matrix, DPGO_utils.cpp:440-718; F = 1/2 tr(X^T M X)).
+ *   Lambda_p = 1/2 (P + P^T), P = (M X)[rows of Y_p] (X[rows of Y_p])^T           (SESyncProblem.cpp:375-395)
+ *   S = M - blkdiag(0_N, Lambda_0, ..., Lambda_{N-1})                              (:444-447)
+ * The search is LOBPCG on S with block size d, basis [V W P], on the device (fast_verification STEP 2, :765-826): |S| is
+ * estimated on a Gaussian block (LOBPCG.h:199-214), column 0 has converged when r_0 <= tau (|S|_est + |theta_0|) |x_0|
+ * (:298-307), and with stop_on_negative the search ends at once when theta_0 < -eta / 2 (SESync_utils.cpp:775-793).
+ * `theta` and `residual` are recomputed from ONE fresh product S x of the returned unit vector x (theta = x^T S x,
+ * residual = |S x - theta x|) and `status` is decided from them:
+ *   DPGO_CERT_NEGATIVE     theta < -eta / 2: x PROVES lambda_min(S) < -eta / 2, X is not certified;
+ *   DPGO_CERT_NONNEGATIVE  otherwise, and residual <= tau (|S|_est + |theta|).  This is EVIDENCE, NOT PROOF: a converged
+ *                          Ritz pair need not be the smallest one.  The reference gets its proof from a Cholesky
+ *                          factorisation of S + eta I (STEP 1, :731-754), which this library does not have;
+ *   DPGO_CERT_UNDECIDED    max_iters reached without either.
+ * `stationarity` is |S X|_F, the norm of the Riemannian gradient at X: the certificate only means something at a
+ * critical point.  Deviations: the block size is fixed to d (a block IS a pose-record array); the preconditioner is
+ * block Jacobi on the (d+1) x (d+1) diagonal blocks of M where the reference uses ILDL (STEP 3); trivial loss only -- a
+ * group created with a robust loss returns -1 (create a second group with loss = 0 (None) and max_iterations = 0, which
+ * skips the optimiser's factorisation); the group must host every node of the graph (-1 otherwise); rounding is not
+ * Eigen's.  The optimiser's state is untouched. */
+#define DPGO_CERT_UNDECIDED 0
+#define DPGO_CERT_NONNEGATIVE 1
+#define DPGO_CERT_NEGATIVE 2
+typedef struct dpgo_cert_options {
+  double eta;            /* min_eig_num_tol, C++/SESync/include/SESync/SESync.h:88, 1e-3 */
+  double tau;            /* LOBPCG.h:138, 1e-6 */
+  int max_iters;         /* 2000 */
+  int precondition;      /* 1: block Jacobi */
+  int stop_on_negative;  /* 1 */
+  int refresh_every;     /* 50: S V and S P by real products every so many iterations; 0: never */
+  unsigned long long seed;   /* of the Gaussian blocks (the norm estimate's, and the initial block when V0 is NULL) */
+} dpgo_cert_options_t;
+typedef struct dpgo_cert_result {
+  int status, iterations, restarts;   /* restarts: Rayleigh-Ritz steps that dropped P (mass matrix pivot < 1e-12) */
+  double theta, residual, S_norm_est, stationarity;
+} dpgo_cert_result_t;
+void dpgo_cert_options_default(dpgo_cert_options_t *opt);
+/* fast_verification STEP 2 (SESync_utils.cpp:765-826).  V0: the initial block, (d+1)N x d, leading dimension ldv0, or
+ * NULL (seeded Gaussians); x: receives the unit vector, (d+1)N entries, ldx >= (d+1)N, or NULL.  -1 on bad arguments. */
+int dpgo_group_certify(dpgo_group_t *grp, const double *X, int ld, const dpgo_cert_options_t *opts, const double *V0,
+                       int ldv0, dpgo_cert_result_t *result, double *x, int ldx);
+/* compute_Lambda_blocks (SESyncProblem.cpp:375-395): Lambda receives N blocks d x d, row-major, by global pose */
+int dpgo_group_cert_lambda(dpgo_group_t *grp, const double *X, int ld, double *Lambda);
+/* SV = S(X) V, V and SV (d+1)N x d in the layout of X (the operator of verify_solution, :444-447, alone) */
+int dpgo_group_cert_apply(dpgo_group_t *grp, const double *X, int ld, const double *V, int ldv, double *SV, int ldsv);
+/* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
+ * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
+ * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:
+ * n x ns row-major with C^T B C = I, C^T A C = diag(theta), rows of dropped blocks zero; *used: blocks used. */
+int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used);
+
 /* ---- test hooks ------------------------------------------------------------------------- */
 /* Host: the assembled operator `name` in {"G","S","P","P0","Q","D"} of a node as COO triplets in
  * the REFERENCE row/column order.  Call with rows == NULL to get the count. */

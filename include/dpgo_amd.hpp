@@ -184,6 +184,27 @@ class DPGOHashGroup {
     grad.resize(X.rows(), X.cols());
     return dpgo_group_evaluate(h_, X.data(), X.rows(), nullptr, nullptr, grad.data(), grad.rows());
   }
+  // SESyncProblem::verify_solution (C++/SESync/include/SESync/SESyncProblem.h:345, SESyncProblem.cpp:397-468) without its
+  // block-size and ILDL arguments: LOBPCG on the certificate matrix S = M - Lambda(X), block size d, block-Jacobi
+  // preconditioner (dpgo_group_certify).  theta: x' S x of the returned unit vector x ((d+1)N x 1); num_iters: LOBPCG
+  // iterations.  Returns true when the search converged with theta >= -eta / 2 (DPGO_CERT_NONNEGATIVE) -- evidence, NOT
+  // proof, that X is a global minimiser: a converged Ritz pair need not be the smallest, and the reference's proof (a
+  // Cholesky factorisation of S + eta I) is not part of this library.  status (optional): the DPGO_CERT_* outcome, -1
+  // when the call itself failed (robust loss, a group that does not host every node).
+  bool verify_solution(const Matrix &X, Scalar eta, Scalar &theta, Matrix &x, int &num_iters, int *status = nullptr,
+                       dpgo_cert_result_t *result = nullptr) const {
+    dpgo_cert_options_t o;
+    dpgo_cert_options_default(&o);
+    o.eta = eta;
+    dpgo_cert_result_t r;
+    x.resize(X.rows(), 1);
+    const int rc = dpgo_group_certify(h_, X.data(), X.rows(), &o, nullptr, 0, &r, x.data(), x.rows());
+    theta = r.theta;
+    num_iters = r.iterations;
+    if (status) *status = rc == 0 ? r.status : -1;
+    if (result) *result = r;
+    return rc == 0 && r.status == DPGO_CERT_NONNEGATIVE;
+  }
   const Graph &graph() const { return *graph_; }
   dpgo_group_t *handle() const { return h_; }
 
