@@ -237,12 +237,12 @@ void Group::cert_download(const double *dev_own, double *M, int ld, int ncols) {
 void Group::cert_apply_M(double *in_all, double *out_own) {
   const NodeMask all{all_bits(), nullptr};
   if (gather_dst_.n) launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, in_all, in_all);
-  launch_bsr(d_, st_, T_, false, all, S_.dev, in_all, 0, nullptr, cert_->tmp.p, nullptr, 0, nullptr, nullptr, 0);
-  launch_bsr(d_, st_, T_, false, all, G_.dev, in_all, 0, cert_->tmp.p, out_own, nullptr, 0, nullptr, nullptr, 0);
+  launch_bsr(lc(all), S_.dev, {.x = in_all, .y = cert_->tmp.p});
+  launch_bsr(lc(all), G_.dev, {.x = in_all, .addv = cert_->tmp.p, .y = out_own});
 }
 void Group::cert_apply_S(double *in_all, double *out_own) {
   cert_apply_M(in_all, out_own);
-  launch_cert_apply(d_, st_, T_, NodeMask{all_bits(), nullptr}, cert_->Lam.p, in_all, out_own, out_own);
+  launch_cert_apply(lc(NodeMask{all_bits(), nullptr}), cert_->Lam.p, in_all, out_own, out_own);
 }
 
 // X on the device, M X, the Lambda blocks and |S X|_F
@@ -250,7 +250,7 @@ int Group::cert_prepare(const double *X, int ld, double *stationarity) {
   CertState &c = *cert_;
   cert_upload(X, ld, d_, c.X.p);
   cert_apply_M(c.X.p, c.MX.p);
-  launch_cert_lambda(d_, st_, T_, NodeMask{all_bits(), nullptr}, c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
+  launch_cert_lambda(lc(NodeMask{all_bits(), nullptr}), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
   launch_cert_reduce(st_, T_, 1, c.partials.p, c.h_sums, sched_.flag());
   wait_flag(sched_.last_seq());
   if (stationarity) *stationarity = std::sqrt(c.h_sums[0]);
@@ -382,7 +382,7 @@ int Group::certify(const double *X, int ld, const CertOptions &o, const double *
   for (;;) {
     while (res.iterations < o.max_iters) {
       if (have_W) cert_apply_M(c.W.p, c.SW.p);   // (S W is finished by k_cert_gram)
-      launch_cert_gram(d, st_, T_, all, c.Lam.p, c.V.p, c.W.p, c.P.p, c.SV.p, c.SW.p, c.SP.p, c.partials.p);
+      launch_cert_gram(lc(all), c.Lam.p, c.V.p, c.W.p, c.P.p, c.SV.p, c.SW.p, c.SP.p, c.partials.p);
       launch_cert_reduce(st_, T_, nsums, c.partials.p, c.h_sums, sched_.flag());
       wait_flag(sched_.last_seq());
       // the stopping test of the LAST update, one product late (LOBPCG.h:298-307)
@@ -408,7 +408,7 @@ int Group::certify(const double *X, int ld, const CertOptions &o, const double *
       for (int i = 0; i < n; i++)
         for (int j = 0; j < d; j++) K.C[i * d + j] = C[i * d + j];
       for (int j = 0; j < d; j++) K.theta[j] = th[j];
-      launch_cert_update(d, st_, T_, all, K, o.precondition ? c.Tp.p : nullptr, c.V.p, c.W.p, c.P.p, c.SV.p, c.SW.p, c.SP.p,
+      launch_cert_update(lc(all), K, o.precondition ? c.Tp.p : nullptr, c.V.p, c.W.p, c.P.p, c.SV.p, c.SW.p, c.SP.p,
                          c.partials.p);
       res.iterations++;
       theta0 = th[0];

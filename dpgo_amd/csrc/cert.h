@@ -77,18 +77,16 @@ struct CertCoef {
 };
 // All over the own rows, one workgroup per own segment; partial sums are stored at partials[s * T.nseg_own + segment].
 // Lam[p] (d x d row-major) from the records of X and M X; with SX: (S X) stored; partial 0 = |(S X)_p|^2
-void launch_cert_lambda(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X, const double *MX, double *Lam,
-                        double *SX, double *partials);
+void launch_cert_lambda(const LaunchCtx &lc, const double *X, const double *MX, double *Lam, double *SX, double *partials);
 // out = MV - [0 ; Lam V.Y]  (out may be MV)
-void launch_cert_apply(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *MV,
-                       double *out);
+void launch_cert_apply(const LaunchCtx &lc, const double *Lam, const double *V, const double *MV, double *out);
 // SW <- SW - [0 ; Lam W.Y] (SW holds M W on entry), then the upper triangles of B^T B (sums [0, ntri)) and B^T (S B)
 // (sums [ntri, 2 ntri)), B = [V W P]
-void launch_cert_gram(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *W,
+void launch_cert_gram(const LaunchCtx &lc, const double *Lam, const double *V, const double *W,
                       const double *P, const double *SV, double *SW, const double *SP, double *partials);
 // P' = W C_w + P C_p, V' = V C_v + P', the same for S V', S P'; R' = S V' - V' diag(theta); W' = Tp R' (Tp: (d+1)^2 per
 // pose, null: R'); sums 2 ntri + j = |R'_j|^2, 2 ntri + d + j = |V'_j|^2
-void launch_cert_update(int d, hipStream_t st, const SegTable &T, NodeMask mask, const CertCoef &c, const double *Tp, double *V,
+void launch_cert_update(const LaunchCtx &lc, const CertCoef &c, const double *Tp, double *V,
                         double *W, double *P, double *SV, const double *SW, double *SP, double *partials);
 // host[s] = sum over the own segments of partial s, s < nsums, in segment order; then the flag
 void launch_cert_reduce(hipStream_t st, const SegTable &T, int nsums, const double *partials, double *host, ReadbackFlag flag);

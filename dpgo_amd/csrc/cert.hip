@@ -352,28 +352,30 @@ __global__ __launch_bounds__(64) void k_cert_reduce(int nseg, const double *part
     }                                  \
   } while (0)
 
-void launch_cert_lambda(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X, const double *MX, double *Lam,
-                        double *SX, double *partials) {
+void launch_cert_lambda(const LaunchCtx &lc, const double *X, const double *MX, double *Lam, double *SX, double *partials) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_lambda<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, X, MX, Lam, SX,
                                         partials, T.nseg_own));
 }
 
-void launch_cert_apply(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *MV,
-                       double *out) {
+void launch_cert_apply(const LaunchCtx &lc, const double *Lam, const double *V, const double *MV, double *out) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_apply<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, Lam, V, MV, out));
 }
 
-void launch_cert_gram(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Lam, const double *V, const double *W,
+void launch_cert_gram(const LaunchCtx &lc, const double *Lam, const double *V, const double *W,
                       const double *P, const double *SV, double *SW, const double *SP, double *partials) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_gram<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, Lam, V, W, P, SV, SW,
                                         SP, partials, T.nseg_own));
 }
 
-void launch_cert_update(int d, hipStream_t st, const SegTable &T, NodeMask mask, const CertCoef &c, const double *Tp, double *V,
+void launch_cert_update(const LaunchCtx &lc, const CertCoef &c, const double *Tp, double *V,
                         double *W, double *P, double *SV, const double *SW, double *SP, double *partials) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   CoefArg K{c};
   CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_update<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, K, Tp, V, W, P, SV,

@@ -322,8 +322,8 @@ int Group::chordal_step() {
   NodeCoefs gam;
   const double gm = ch_->nes.next_gamma();
   for (int a = 0; a < MAX_LOCAL_NODES; a++) gam.a[a] = gam.b[a] = gm;
-  launch_extrapolate(d_, st_, T_, true, cur_mask_, gam, Zc_.p, Zp_.p, Y_.p);
-  launch_bsr(d_, st_, T_, false, cur_mask_, ch_->S.dev, Y_.p, false, ch_->gconst.p, T1_.p, nullptr, 0, nullptr, nullptr, 0);
+  launch_extrapolate(lc(), true, gam, Zc_.p, Zp_.p, Y_.p);
+  launch_bsr(lc(), ch_->S.dev, {.x = Y_.p, .addv = ch_->gconst.p, .y = T1_.p});
   spd_run(d_, st_, ch_->L, cur_mask_, T1_.p, Xk_.p, -1.0);   // Xak = -G^-1 (g_ + S Y), straight into Xk's own rows
   if (communicate_local() != 0) return -1;
   if (coll_allgather_) {   // neighbours hosted by other groups: the boundary rows travel like the iterate's (DChordal.h:26-84)

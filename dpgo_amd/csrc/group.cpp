@@ -638,11 +638,11 @@ void Group::speculate_update(const double *xprop, int nslots_trial) {
   const NodeMask m{all_bits(), go_.p};
   if (gather_dst_.n > 0) launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, nxak, Xk_.p, go_.p);
   double *const pupd = partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all;   // (update()'s own slots: deferred_slots_ is 0 here, Dynamic is off)
-  launch_bsr(d_, st_, T_, false, m, G_.dev, nxak, false, nullptr, gx, nxak, 0.5, nullptr, pupd, 5, Xk_.p, zc);
-  InterFuse fz;
-  fz.GX = gx; fz.X = nxak; fz.Df = dfc; fz.gn_slot = 4;
-  launch_inter(d_, st_, T_, m, E_, opt_.loss, opt_.loss_reg, 0, true, zc, zp, Qd_.p, Dd_.p, DfE_.p, gc, pupd, nullptr, nullptr, nullptr,
-               nullptr, nullptr, Xk_.p, nullptr, &fz);
+  launch_bsr(lc(m), G_.dev, {.x = nxak, .y = gx, .dot = {.v = nxak, .coef = 0.5, .partials = pupd, .slot = 5},
+                             .copy = {.to1 = Xk_.p, .to2 = zc}});
+  launch_inter_update(lc(m), E_, opt_.loss, opt_.loss_reg,
+                      {.quad = true, .Z = zc, .Zprev = zp, .Qdiag = Qd_.p, .Ddiag = Dd_.p, .DfE = DfE_.p, .g = gc, .partials = pupd,
+                       .Znbr = Xk_.p, .GX = gx, .X = nxak, .Df = dfc, .gn_slot = 4});
   // (the closing reduction: left to the next refinement where update() itself would leave it, group.h: UpdLazy)
   spec_upd_.lazy = lazy_update_reduce();
   if (!spec_upd_.lazy) launch_reduce(st_, T_, L, true, 6, pupd, h_upd_, sched_.flag());
@@ -673,7 +673,7 @@ void Group::flush_pending_tail() {
   if (!pending_tail_.on) return;
   const PendingTail p = pending_tail_;
   pending_tail_.on = false;
-  launch_axpby(d_, st_, T_, false, p.m, 1.0, p.xak, 0.0, nullptr, p.xk, 0, p.z);
+  launch_axpby(lc(p.m), false, 1.0, p.xak, 0.0, nullptr, p.xk, 0, p.z);
 }
 
 // The segments of an iteration (group.h): the key of a replay is built here, the schedule runs it
@@ -742,7 +742,7 @@ void Group::wait_flag(unsigned long long seq) {
 }
 
 void Group::copy_rows(double *dst, const double *src, bool all_rows, int part) {
-  launch_axpby(d_, st_, T_, all_rows, cur_mask_, 1.0, src, 0.0, nullptr, dst, part);
+  launch_axpby(lc(), all_rows, 1.0, src, 0.0, nullptr, dst, part);
 }
 
 // (fronts of nodes outside the current mask are skipped: their entries of `out` stay as they are)
@@ -751,24 +751,16 @@ void Group::solve_rr(double *in, double *out, double scale) { spd_run(d_, st_, L
 
 // X.t = -G_tt^-1 (g_t + G_tR X.R)    (DPGOProblem.h:275-294)
 // Leaves T1_ = G [0 ; X.R] + g on all rows (its translation rows are the right-hand side of the solve):
-// with the new translations, G X + g = T1_ + G_{:,t} X.t, which apply_tcol() adds at a quarter of the
+// with the new translations, G X + g = T1_ + G_{:,t} X.t, which launch_bsr_tcol() adds at a quarter of the
 // cost of another G X.
 void Group::recover_translations(double *X, const double *g) {
-  launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, X, true, g, T1_.p, nullptr, 0.0, nullptr, nullptr, 0);
+  launch_bsr(lc(), G_.dev, {.x = X, .mode = BsrMode::NoTrans, .addv = g, .y = T1_.p});
   solve_tt(T1_.p, X, -1.0);
-}
-
-// y = base + G_{:,t} xt.t, with the row-local epilogues of launch_bsr_tcol
-void Group::apply_tcol(const double *xt, const double *base, double *y, int mode, const double *X, const double *nabla,
-                       const double *Rdot, double *out2, const double *rres, double *partials, const double *dg,
-                       const double *dga, const double *ds, const double *dgrad, const double *dhs) {
-  launch_bsr_tcol(d_, st_, T_, cur_mask_, G_.dev, G_.tcol.p, xt, base, y, mode, X, nabla, Rdot, out2, rres, partials, dg, dga,
-                  ds, dgrad, dhs);
 }
 
 // partial[slot] = tr(X^T (g + 1/2 G X))     (DPGOProblem.cpp:180-205; + f on the host)
 void Group::eval_G(const double *X, const double *g, int slot) {
-  launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, X, false, nullptr, nullptr, X, 0.5, g, partials_.p, slot);
+  launch_bsr(lc(), G_.dev, {.x = X, .dot = {.v = X, .coef = 0.5, .add = g, .partials = partials_.p, .slot = slot}});
 }
 
 // ---------------------------------------------------------------------------
@@ -884,13 +876,12 @@ int Group::evaluate_global(const double *X, int ld, double *F, double *grad_sqno
   set_mask(all);
   double *g = tmp_[0].p, *Df = tmp_[1].p, *gr = tmp_[2].p;
   if (opt_.loss == 0)   // g = S Z
-    launch_bsr(d_, st_, T_, false, cur_mask_, S_.dev, Tall_.p, false, nullptr, g, nullptr, 0, nullptr, nullptr, 0);
+    launch_bsr(lc(), S_.dev, {.x = Tall_.p, .y = g});
   else                  // g = (B1^T W B1 Z)_own - D X   (weights at X)
-    launch_inter(d_, st_, T_, cur_mask_, E_, opt_.loss, opt_.loss_reg, 1, false, Tall_.p, nullptr, nullptr, Dd_.p, nullptr, g,
-                 partials_.p);
-  launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Tall_.p, false, g, Df, nullptr, 0, nullptr, nullptr, 0);
-  launch_cost(d_, st_, T_, cur_mask_, Ei_, E_, opt_.loss == 0, opt_.loss, opt_.loss_reg, Tall_.p, partials_.p, 0);
-  launch_tangent_full(d_, st_, T_, cur_mask_, Tall_.p, Df, gr, partials_.p, 2);
+    launch_inter_iterate(lc(), E_, opt_.loss, opt_.loss_reg, {.Z = Tall_.p, .Ddiag = Dd_.p, .g = g, .partials = partials_.p});
+  launch_bsr(lc(), G_.dev, {.x = Tall_.p, .addv = g, .y = Df});
+  launch_cost(lc(), Ei_, E_, opt_.loss == 0, opt_.loss, opt_.loss_reg, Tall_.p, partials_.p, 0);
+  launch_tangent_full(lc(), Tall_.p, Df, gr, partials_.p, 2);
   fetch(3, true);
   double v[2] = {0, 0};
   for (int a = 0; a < num_local(); a++) {
@@ -1494,13 +1485,14 @@ int Group::update(const std::vector<int> &locals_in) {
   const bool split = xchg_done_ != nullptr;
   auto product_with_G = [&] {
     if (trivial)   // T1 = G Xak and <Xak, 1/2 G Xak>   (half of evaluate_G, DPGOProblem.cpp:180-205)
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Xak_.p, false, nullptr, T1_.p, Xak_.p, 0.5, nullptr, pupd, 5);
+      launch_bsr(lc(), G_.dev, {.x = Xak_.p, .y = T1_.p, .dot = {.v = Xak_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
     else if (fuse_copy) {   // ... on Xak's records (the same numbers), which go to Xk and X[iter] on the way
       const PendingTail pt = pending_tail_;
       pending_tail_.on = false;
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, pt.xak, false, nullptr, GX, pt.xak, 0.5, nullptr, pupd, 5, pt.xk, pt.z);
+      launch_bsr(lc(), G_.dev, {.x = pt.xak, .y = GX, .dot = {.v = pt.xak, .coef = 0.5, .partials = pupd, .slot = 5},
+                                .copy = {.to1 = pt.xk, .to2 = pt.z}});
     } else         // T1 = G X and <X, 1/2 G X>  (kept as G X[k] where the next extrapolation reuses it)
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Zc_.p, false, nullptr, GX, Zc_.p, 0.5, nullptr, pupd, 5);
+      launch_bsr(lc(), G_.dev, {.x = Zc_.p, .y = GX, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
   };
   const NodeMask mask_locals = cur_mask_;
   if (split) {
@@ -1518,8 +1510,8 @@ int Group::update(const std::vector<int> &locals_in) {
     auto common = [&] {
       head();
       cur_mask_ = mask_locals;
-      launch_copy_nbr_rows(d_, st_, T_, cur_mask_, Xk_.p, Zc_.p);
-      launch_bsr(d_, st_, T_, false, cur_mask_, S_.dev, Zc_.p, false, nullptr, gc_.p, Xak_.p, 1.0, nullptr, pupd, 1);
+      launch_copy_nbr_rows(lc(), Xk_.p, Zc_.p);
+      launch_bsr(lc(), S_.dev, {.x = Zc_.p, .y = gc_.p, .dot = {.v = Xak_.p, .coef = 1.0, .partials = pupd, .slot = 1}});
     };
     const bool both = !first.empty() && !later.empty();
     if (both) sched_.flush_deferred();
@@ -1528,9 +1520,10 @@ int Group::update(const std::vector<int> &locals_in) {
       end_with(1, (split ? 1ull : 0ull) | (both ? 2ull : 0ull), 6, first, [&] {
         if (!both) common();
         set_mask(first);
-        launch_bsr(d_, st_, T_, true, cur_mask_, P0m_.dev, Zc_.p, false, nullptr, nullptr, Zc_.p, 0.5, nullptr, pupd, 0);
+        launch_bsr(lc(), P0m_.dev, {.all_rows = true, .x = Zc_.p,
+                                    .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 0}});
         // fobj = G(Xak | g, f0) = f0 + <Xak, g> + <Xak, 1/2 G Xak>: slots 1 and 5; Dfobj = g + G Xak
-        launch_tangent_full(d_, st_, T_, cur_mask_, Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
+        launch_tangent_full(lc(), Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
       }, [this, first] {
         for (int a : first) {
           const double f0 = uscal(a, 0);
@@ -1542,10 +1535,11 @@ int Group::update(const std::vector<int> &locals_in) {
       end_with(2, (split ? 1ull : 0ull) | (both ? 2ull : 0ull), 4, later, [&] {
         if (!both) common();
         set_mask(later);
-        launch_axpby(d_, st_, T_, true, cur_mask_, 1.0, Zc_.p, -1.0, Zp_.p, Tall_.p, 0);
-        launch_bsr(d_, st_, T_, true, cur_mask_, Q_.dev, Tall_.p, false, nullptr, nullptr, Tall_.p, 0.5, nullptr, pupd, 0);
-        launch_bsr(d_, st_, T_, true, cur_mask_, P_.dev, Zc_.p, false, nullptr, nullptr, Zc_.p, 0.5, nullptr, pupd, 3);
-        launch_tangent_full(d_, st_, T_, cur_mask_, Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
+        launch_axpby(lc(), true, 1.0, Zc_.p, -1.0, Zp_.p, Tall_.p, 0);
+        launch_bsr(lc(), Q_.dev, {.all_rows = true, .x = Tall_.p,
+                                  .dot = {.v = Tall_.p, .coef = 0.5, .partials = pupd, .slot = 0}});
+        launch_bsr(lc(), P_.dev, {.all_rows = true, .x = Zc_.p, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 3}});
+        launch_tangent_full(lc(), Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
       }, [this, later] {
         for (int a : later) {
           const double fobj = res_[a].Gk + uscal(a, 0);
@@ -1571,16 +1565,18 @@ int Group::update(const std::vector<int> &locals_in) {
       const std::vector<int> &set = pass == 0 ? first : later;
       if (set.empty()) continue;
       std::vector<double> rho(num_local(), 0.0), gap(num_local(), 0.0);
-      // fz: what the pass does on the way (Dfobj and |grad F|^2)
-      auto inter_pass = [&](const InterFuse *fz) {
+      // with_Df: Dfobj and |grad F|^2 on the way
+      auto inter_pass = [&](bool with_Df) {
         InterEdgesDev E = E_;
         if (lazy_recv) { E.recv = lazy_recv; E.nsrc = recv_nsrc_.p; }
-        launch_inter(d_, st_, T_, cur_mask_, E, opt_.loss, opt_.loss_reg, 0, pass == 1, Zc_.p, Zp_.p, Qd_.p, Dd_.p, DfE_.p,
-                     gc_.p, pupd, dynamic() ? e_w_.p : nullptr, nullptr, nullptr, nullptr, nullptr, Xk_.p, nullptr, fz);   // slots 0, 1 and 2 = <X, g>
+        InterUpdate up = {.quad = pass == 1, .Z = Zc_.p, .Zprev = Zp_.p, .Qdiag = Qd_.p, .Ddiag = Dd_.p, .DfE = DfE_.p, .g = gc_.p,
+                          .partials = pupd, .wout = dynamic() ? e_w_.p : nullptr, .Znbr = Xk_.p};
+        if (with_Df) { up.GX = GX; up.X = Xak_.p; up.Df = Dfc_.p; up.gn_slot = 4; }
+        launch_inter_update(lc(), E, opt_.loss, opt_.loss_reg, up);   // slots 0, 1 and 2 = <X, g>
       };
       if (dynamic()) {
         set_mask(set);
-        inter_pass(nullptr);
+        inter_pass(false);
         if (device_rescale_)   // the rescale test on the weights just computed; its verdict rides with the sums below
           launch_rescale_decide(st_, num_local(), cur_mask_.v, e_off_dev_.p, e_w_.p, e_scale_.p, rs_count_.p, opt_.max_rescale_count,
                                 rs_flags_.p, h_rs_);
@@ -1592,9 +1588,9 @@ int Group::update(const std::vector<int> &locals_in) {
         const std::vector<int> changed = device_rescale_ ? rescale_device(set) : maybe_rescale(set);
         if (!changed.empty()) {
           set_mask(changed);
-          launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Zc_.p, false, nullptr, GX, Zc_.p, 0.5, nullptr, pupd, 5);
-          launch_inter(d_, st_, T_, cur_mask_, E_, opt_.loss, opt_.loss_reg, 1, false, Zc_.p, nullptr, nullptr, Dd_.p, nullptr,
-                       gc_.p, pupd);   // g = DfobjE_own - D X with the new D (slot 2 = <X, g> again)
+          launch_bsr(lc(), G_.dev, {.x = Zc_.p, .y = GX, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
+          // g = DfobjE_own - D X with the new D (slot 2 = <X, g> again)
+          launch_inter_iterate(lc(), E_, opt_.loss, opt_.loss_reg, {.Z = Zc_.p, .Ddiag = Dd_.p, .g = gc_.p, .partials = pupd});
           set_mask(set);
         }
       }
@@ -1609,15 +1605,11 @@ int Group::update(const std::vector<int> &locals_in) {
       end_with(3 + pass, (split ? 1ull : 0ull) | (head_inside ? 2ull : 0ull) | (dyn ? 4ull : 0ull) | (fused_ ? 8ull : 0ull) | (lazy_recv ? 16ull : 0ull) | (fresh_bits << 5), 6, set, [&] {
         if (head_inside) head();
         set_mask(set);
-        // Dfobj = G X + g, its tangent projection and norm: inside the inter-edge pass (kernels.h: InterFuse), or k_tangent_full
+        // Dfobj = G X + g, its tangent projection and norm: inside the inter-edge pass (kernels.h: InterUpdate::Df), or k_tangent_full
         const bool in_pass = !dyn && fused_;
-        if (!dyn) {
-          InterFuse fz;
-          fz.GX = GX; fz.X = Xak_.p; fz.Df = Dfc_.p; fz.gn_slot = 4;
-          inter_pass(in_pass ? &fz : nullptr);
-        }
-        if (pass == 0) launch_bdiag_dot(d_, st_, T_, cur_mask_, Dd_.p, Zc_.p, 0.5, DfE_.p, -1.0, pupd, 3);
-        if (!in_pass) launch_tangent_full(d_, st_, T_, cur_mask_, Xak_.p, GX, nullptr, pupd, 4, gc_.p, Dfc_.p);   // Dfobj = G X + g
+        if (!dyn) inter_pass(in_pass);
+        if (pass == 0) launch_bdiag_dot(lc(), Dd_.p, Zc_.p, 0.5, DfE_.p, -1.0, pupd, 3);
+        if (!in_pass) launch_tangent_full(lc(), Xak_.p, GX, nullptr, pupd, 4, gc_.p, Dfc_.p);   // Dfobj = G X + g
         if (!fresh.empty()) {
           set_mask(fresh);
           copy_rows(GXp_.p, GXc_.p, false);
@@ -1677,10 +1669,10 @@ int Group::iterate(const std::vector<int> &locals) {
       pending_tail_.on = true; pending_tail_.m = m; pending_tail_.xak = xak; pending_tail_.xk = xk; pending_tail_.z = z;
     } else if (pack_dst_ && !sched_.defer_armed()) {
       // an exchange follows (step()): its pack rides on this launch (kernels.h: launch_tail_pack), Comm::exchange() finds it done
-      launch_tail_pack(d_, st_, T_, m, xak, xk, z, pack_rows_, pack_n_, pack_dst_);
+      launch_tail_pack(lc(m), xak, xk, z, pack_rows_, pack_n_, pack_dst_);
       packed_ = true;
     } else
-    sched_.submit(0x7461696cull ^ m.v, [this, m, xak, xk, z] { launch_axpby(d_, st_, T_, false, m, 1.0, xak, 0.0, nullptr, xk, 0, z); });
+    sched_.submit(0x7461696cull ^ m.v, [this, m, xak, xk, z] { launch_axpby(lc(m), false, 1.0, xak, 0.0, nullptr, xk, 0, z); });
   }
   for (int a : locals) {
     res_[a].iters++;
@@ -1694,7 +1686,7 @@ int Group::mm(const std::vector<int> &locals) {
   const Options &o = opt_;
   set_mask(locals);
   segment(12, cur_mask_.v, {}, [&] {
-    launch_proximal(d_, st_, T_, cur_mask_, Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
+    launch_proximal(lc(), Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
     recover_translations(Xakh_.p, gc_.p);
     copy_rows(Xak_.p, Xakh_.p, false);
   });
@@ -1725,7 +1717,7 @@ int Group::mm(const std::vector<int> &locals) {
 // (gam_dev: the same gammas in device memory -- the launches may be replayed from a captured graph, whose by-value
 // arguments are frozen: amm())
 // prox_slot >= 0: the caller's next step is Xakh = proximal(Y, Df) with |Xakh - Xak|^2 into that partial slot and Xak's
-// rotations <- Xakh's (amm()); returns true when the inter-edge pass took it along (kernels.h: InterFuse::Xout)
+// rotations <- Xakh's (amm()); returns true when the inter-edge pass took it along (kernels.h: InterIterate::Xout)
 bool Group::prepare_extrapolated(const double *gam_dev, int prox_slot) {
   const Options &o = opt_;
   const bool trivial = (o.loss == 0);
@@ -1735,38 +1727,39 @@ bool Group::prepare_extrapolated(const double *gam_dev, int prox_slot) {
   if (!trivial && fused_) {
     // ... inside the inter-edge pass: it forms Y's records as it reads them (its own row, which it stores -- the proximal
     // step reads Y's own rows --, and the pose at the other end of every incidence): no pass of its own over X[k], X[k-1]
-    InterFuse fz;
-    fz.Zc = Zc_.p; fz.Zp = Zp_.p; fz.Yout = Y_.p;
-    if (keep_gx()) {
+    if (keep_gx()) {   // ... and Df from the kept products, stored -- or handed straight to the proximal step
       const bool prox = prox_slot >= 0;
-      if (prox) { fz.Xout = Xakh_.p; fz.Xref = Xak_.p; fz.Tinv = Tinv_.p; fz.Nv = N_.p; fz.Vb = V_.p; fz.gn_slot = prox_slot; }
-      launch_inter(d_, st_, T_, cur_mask_, E_, o.loss, o.loss_reg, 1, false, Y_.p, nullptr, nullptr, Dd_.p, nullptr, gx_.p,
-                   partials_.p, nullptr, GXc_.p, GXp_.p, &gam, prox ? nullptr : Dfx_.p, nullptr, gam_dev, &fz);
+      InterIterate it = {.Z = Y_.p, .Ddiag = Dd_.p, .g = gx_.p, .partials = partials_.p, .gamma = &gam, .gamma_dev = gam_dev,
+                         .GXc = GXc_.p, .GXp = GXp_.p, .Zc = Zc_.p, .Zp = Zp_.p, .Yout = Y_.p};
+      if (prox) { it.Xout = Xakh_.p; it.Xref = Xak_.p; it.Tinv = Tinv_.p; it.Nv = N_.p; it.Vb = V_.p; it.gn_slot = prox_slot; }
+      else it.Df_out = Dfx_.p;
+      launch_inter_iterate(lc(), E_, o.loss, o.loss_reg, it);
       return prox;
     } else {
-      launch_inter(d_, st_, T_, cur_mask_, E_, o.loss, o.loss_reg, 1, false, Y_.p, nullptr, nullptr, Dd_.p, nullptr, gx_.p,
-                   partials_.p, nullptr, nullptr, nullptr, &gam, nullptr, nullptr, gam_dev, &fz);
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Y_.p, false, gx_.p, Dfx_.p, nullptr, 0, nullptr, nullptr, 0);
+      launch_inter_iterate(lc(), E_, o.loss, o.loss_reg,
+                           {.Z = Y_.p, .Ddiag = Dd_.p, .g = gx_.p, .partials = partials_.p, .gamma = &gam, .gamma_dev = gam_dev,
+                            .Zc = Zc_.p, .Zp = Zp_.p, .Yout = Y_.p});
+      launch_bsr(lc(), G_.dev, {.x = Y_.p, .addv = gx_.p, .y = Dfx_.p});
     }
     return false;
   }
   if (trivial && fused_) {   // Y, g and Dfobj at the extrapolated point in one launch (:255-262)
-    launch_extrapolate3(d_, st_, T_, cur_mask_, gam, gam_dev, Zc_.p, Zp_.p, Y_.p, gc_.p, gp_.p, gx_.p, Dfc_.p, Dfp_.p, Dfx_.p);
+    launch_extrapolate3(lc(), gam, gam_dev, Zc_.p, Zp_.p, Y_.p, gc_.p, gp_.p, gx_.p, Dfc_.p, Dfp_.p, Dfx_.p);
     return false;
   }
-  launch_extrapolate(d_, st_, T_, true, cur_mask_, gam, Zc_.p, Zp_.p, Y_.p, gam_dev);
+  launch_extrapolate(lc(), true, gam, Zc_.p, Zp_.p, Y_.p, gam_dev);
   if (trivial) {
-    launch_extrapolate(d_, st_, T_, false, cur_mask_, gam, gc_.p, gp_.p, gx_.p, gam_dev);      // :259-262
-    launch_extrapolate(d_, st_, T_, false, cur_mask_, gam, Dfc_.p, Dfp_.p, Dfx_.p, gam_dev);
+    launch_extrapolate(lc(), false, gam, gc_.p, gp_.p, gx_.p, gam_dev);      // :259-262
+    launch_extrapolate(lc(), false, gam, Dfc_.p, Dfp_.p, Dfx_.p, gam_dev);
   } else {
     // evaluate_g_and_Df(Y) (:264 -> DPGOProblem.cpp:683-749)
     if (keep_gx()) {   // G Y = G X[k] + gamma (G X[k] - G X[k-1]): Df comes out of the inter-edge pass
-      launch_inter(d_, st_, T_, cur_mask_, E_, o.loss, o.loss_reg, 1, false, Y_.p, nullptr, nullptr, Dd_.p, nullptr, gx_.p,
-                   partials_.p, nullptr, GXc_.p, GXp_.p, &gam, Dfx_.p, nullptr, gam_dev);
+      launch_inter_iterate(lc(), E_, o.loss, o.loss_reg,
+                           {.Z = Y_.p, .Ddiag = Dd_.p, .g = gx_.p, .partials = partials_.p, .gamma = &gam, .gamma_dev = gam_dev,
+                            .GXc = GXc_.p, .GXp = GXp_.p, .Df_out = Dfx_.p});
     } else {
-      launch_inter(d_, st_, T_, cur_mask_, E_, o.loss, o.loss_reg, 1, false, Y_.p, nullptr, nullptr, Dd_.p, nullptr, gx_.p,
-                   partials_.p);
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Y_.p, false, gx_.p, Dfx_.p, nullptr, 0, nullptr, nullptr, 0);
+      launch_inter_iterate(lc(), E_, o.loss, o.loss_reg, {.Z = Y_.p, .Ddiag = Dd_.p, .g = gx_.p, .partials = partials_.p});
+      launch_bsr(lc(), G_.dev, {.x = Y_.p, .addv = gx_.p, .y = Dfx_.p});
     }
   }
   return false;
@@ -1792,10 +1785,11 @@ int Group::amm(const std::vector<int> &locals) {
     // Xakh = proximal(Y, Df); Gkh = G(Xakh | g[k], f); |Xakh - Xak|^2    (:363-367)
     // (these three scalars sit in slots DS.. and are read back together with the first scalars of TNT)
     if (!prepare_extrapolated(gam_dev, DS))
-      launch_proximal(d_, st_, T_, cur_mask_, Y_.p, Dfx_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, Xak_.p, partials_.p, DS);
+      launch_proximal(lc(), Y_.p, Dfx_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, Xak_.p, partials_.p, DS);
     // Gkh = G(Xakh | g[k]) needs G Xakh; the translations of Xak = [. ; Xakh.R] need G [0 ; Xakh.R] + g: one pass over
     // G gives both (T1_ = G [0 ; R] + gx, slot DS + 1 = <Xakh, 1/2 G Xakh + gc>), then the solve   (:363-372)
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Xakh_.p, 2, gx_.p, T1_.p, Xakh_.p, 0.5, gc_.p, partials_.p, DS + 1);
+    launch_bsr(lc(), G_.dev, {.x = Xakh_.p, .mode = BsrMode::NoTransFullDot, .addv = gx_.p, .y = T1_.p,
+                              .dot = {.v = Xakh_.p, .coef = 0.5, .add = gc_.p, .partials = partials_.p, .slot = DS + 1}});
     solve_tt(T1_.p, Xak_.p, -1.0);
   };
   // (where the refinement starts unasked -- below -- and segments are replayed, the two sequences are ONE segment: the
@@ -1845,7 +1839,8 @@ int Group::amm(const std::vector<int> &locals) {
       // of the trajectory.
       deferred_slots_ = 0;
       cur_mask_ = mask_locals;
-      launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Xakh_.p, 2, gx_.p, T1_.p, Xakh_.p, 0.5, gc_.p, partials_.p, DS + 1);
+      launch_bsr(lc(), G_.dev, {.x = Xakh_.p, .mode = BsrMode::NoTransFullDot, .addv = gx_.p, .y = T1_.p,
+                                .dot = {.v = Xakh_.p, .coef = 0.5, .add = gc_.p, .partials = partials_.p, .slot = DS + 1}});
     }
   }
   std::vector<int> plain, ref;
@@ -1883,7 +1878,7 @@ int Group::amm(const std::vector<int> &locals) {
     if (Gkh[a] > minG[a]) redo.push_back(a);
   if (!redo.empty()) {
     set_mask(redo);
-    launch_proximal(d_, st_, T_, cur_mask_, Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
+    launch_proximal(lc(), Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
     eval_G(Xakh_.p, gc_.p, 0);
     fetch(1, false);
     for (int a : redo) Gkh[a] = scal(a, 0) + res_[a].f;
@@ -1910,7 +1905,7 @@ int Group::amm(const std::vector<int> &locals) {
     }
     if (!use_prox.empty()) {
       set_mask(use_prox);
-      launch_proximal(d_, st_, T_, cur_mask_, Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xak_.p, nullptr, nullptr, 0);
+      launch_proximal(lc(), Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xak_.p, nullptr, nullptr, 0);
     }
     set_mask(restart);
     recover_translations(Xak_.p, gc_.p);
@@ -2007,7 +2002,7 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
   if (op == "project") {
     (void)hipMemset(A + (size_t)own_off_[a] * RS_, 0, sizeof(double) * n0 * RS_);
     put_own(Bv, in, ld_in, 0, 0, false);
-    launch_retract_rot(d_, st_, T_, cur_mask_, A, Bv, C);
+    launch_retract_rot(lc(), A, Bv, C);
     get_own(C, out, ld_out, 0, 0, false);
   } else if (op == "solve_tt" || op == "solve_rr") {
     put_own(A, in, ld_in, 0, n0, true);
@@ -2020,14 +2015,14 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     get_own(Bv, out, ld_out, 0, n0, true);
   } else if (op == "G") {
     put_own(A, in, ld_in, 0, n0, true);
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, A, false, nullptr, Bv, nullptr, 0, nullptr, nullptr, 0);
+    launch_bsr(lc(), G_.dev, {.x = A, .y = Bv});
     get_own(Bv, out, ld_out, 0, n0, true);
   } else if (op == "proximal") {
     // in = [Z ((d+1)(n0+n1) rows) ; Df ((d+1) n0 rows)]
     const int zr = (d_ + 1) * (n0 + n1);
     put_own(A, in, ld_in, 0, n0, true);
     put_own(Bv, in, ld_in, zr, zr + n0, true);
-    launch_proximal(d_, st_, T_, cur_mask_, A, Bv, Tinv_.p, N_.p, V_.p, C, nullptr, nullptr, 0);
+    launch_proximal(lc(), A, Bv, Tinv_.p, N_.p, V_.p, C, nullptr, nullptr, 0);
     get_own(C, out, ld_out, 0, n0, true);
   } else if (op == "hess") {
     // in = [Y ; nabla ; Ydot ; r]; out = [Hess[Ydot] (rotation rows) ; <p,Hp>, <Hp,Hp>, <p,p>, <p,r> in column 0], p = Ydot:
@@ -2037,24 +2032,26 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     put_own(nabla, in, ld_in, R0, R0 + n0, true);
     put_own(pk, in, ld_in, 0, 2 * R0 + n0, false);   // (tangent vectors carry no translation: p.x = r.x = 0 in the iteration)
     put_own(rk, in, ld_in, 0, 3 * R0 + n0, false);
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, pk, true, nullptr, w1, nullptr, 0, nullptr, nullptr, 0);   // G [0 ; p.R]
+    launch_bsr(lc(), G_.dev, {.x = pk, .mode = BsrMode::NoTrans, .y = w1});   // G [0 ; p.R]
     solve_tt(w1, w3, -1.0);
-    apply_tcol(w3, w1, nullptr, 2, X, nabla, pk, Hp, rk, partials_.p);
+    launch_bsr_tcol_hess(lc(), g_tcol(),
+                         {.xt = w3, .base = w1, .X = X, .nabla = nabla, .p = pk, .Hp = Hp, .r = rk, .partials = partials_.p});
     fetch(4, false);
     get_own(Hp, out, ld_out, 0, n0, false);
     for (int q = 0; q < 4; q++) out[R0 + q] = scal(a, q);
   } else if (op == "rgrad") {
     // in = [Y ; g]; out = [Y' ; nabla' ; grad' ; nabla ; grad ; 4 sums], rows R0 each.  nabla = G Y + g, grad = Proj_Y(nabla.R)
     // at Y as given (launch_bsr + launch_tangent_rot, tnt.cpp quad_model); the primed ones at Y' = [t recovered from Y.R and
-    // g ; Y.R] (recover_translations + apply_tcol mode 1, quad_model's from_base path) with its epilogue sums
+    // g ; Y.R] (recover_translations + launch_bsr_tcol_begin, quad_model's from_base path) with its epilogue sums
     // |grad'|^2, <Y', nabla'>, <Y', g>, <Y', g> in column 0 of the last 4 rows
     double *X = tmp_[0].p, *g = tmp_[1].p, *nab = tmp_[2].p, *grad = tmp_[3].p, *nab1 = tmp_[4].p, *grad1 = tmp_[5].p;
     put_own(X, in, ld_in, 0, n0, true);
     put_own(g, in, ld_in, R0, R0 + n0, true);
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, X, false, g, nab, nullptr, 0, nullptr, nullptr, 0);
-    launch_tangent_rot(d_, st_, T_, cur_mask_, X, nab, grad);
+    launch_bsr(lc(), G_.dev, {.x = X, .addv = g, .y = nab});
+    launch_tangent_rot(lc(), {.X = X, .in = nab, .out = grad});
     recover_translations(X, g);
-    apply_tcol(X, T1_.p, nab1, 1, X, nullptr, nullptr, grad1, nullptr, partials_.p, g, g);
+    launch_bsr_tcol_begin(lc(), g_tcol(),
+                          {.xt = X, .base = T1_.p, .y = nab1, .X = X, .grad = grad1, .partials = partials_.p, .g = g, .ga = g});
     fetch(4, false);
     get_own(X, out, ld_out, 0, n0, true);
     get_own(nab1, out, ld_out, R0, R0 + n0, true);
@@ -2068,10 +2065,10 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     double *X = tmp_[0].p, *v = tmp_[1].p, *w1 = tmp_[2].p, *pv = tmp_[3].p;
     put_own(X, in, ld_in, 0, n0, true);
     put_own(v, in, ld_in, 0, R0 + n0, false);
-    if (opt_.preconditioner == 1 && jacobi_.n > 0) launch_rot_rowscale(d_, st_, T_, cur_mask_, jacobi_.p, v, w1);
+    if (opt_.preconditioner == 1 && jacobi_.n > 0) launch_rot_rowscale(lc(), jacobi_.p, v, w1);
     else if (Lrr_.F.n > 0) solve_rr(v, w1, 1.0);
     else return -1;
-    launch_tangent_rot(d_, st_, T_, cur_mask_, X, w1, pv, v, partials_.p, 0);
+    launch_tangent_rot(lc(), {.X = X, .in = w1, .out = pv, .dotv = v, .partials = partials_.p});
     fetch(1, false);
     get_own(pv, out, ld_out, 0, n0, false);
     out[R0] = scal(a, 0);
@@ -2081,7 +2078,7 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     put_own(X, in, ld_in, 0, n0, true);
     put_own(sk, in, ld_in, 0, R0 + n0, false);
     put_own(g, in, ld_in, 2 * R0, 2 * R0 + n0, true);
-    launch_retract_rot(d_, st_, T_, cur_mask_, X, sk, xprop);
+    launch_retract_rot(lc(), X, sk, xprop);
     recover_translations(xprop, g);
     get_own(xprop, out, ld_out, 0, n0, true);
   } else if (op == "lambda_max") {
@@ -2112,7 +2109,7 @@ void Group::enqueue_objective(const double *X_own, int slot0) {
     if (coll_allgather_(coll_user_) != 0) throw DeviceError("all-gather callback failed");
     launch_copy_indexed(d_, st_, (int)recv_dst_.n, recv_dst_.p, recv_src_.p, coll_gathered_, Tall_.p);
   }
-  launch_cost(d_, st_, T_, cur_mask_, Ei_, E_, opt_.loss == 0, opt_.loss, opt_.loss_reg, Tall_.p, partials_.p, slot0);
+  launch_cost(lc(), Ei_, E_, opt_.loss == 0, opt_.loss, opt_.loss_reg, Tall_.p, partials_.p, slot0);
 }
 
 // Everything the master's tests of one AMM-PGO* iteration need (DPGOStar.cpp:147-192), enqueued back to back and read
@@ -2134,8 +2131,8 @@ int Group::star_sums(const double *X1_own, const double *X2_own, const double *r
   if (F1) { enqueue_objective(X1_own, slots[0]); valid |= 0x3; }
   if (X2_own && F2) { enqueue_objective(X2_own, slots[2]); valid |= 0xc; }
   if (ref_own) {
-    if (d1) { launch_sqdist(d_, st_, T_, cur_mask_, X1_own, ref_own, partials_.p, slots[4]); valid |= 0x10; }
-    if (X2_own && d2) { launch_sqdist(d_, st_, T_, cur_mask_, X2_own, ref_own, partials_.p, slots[5]); valid |= 0x20; }
+    if (d1) { launch_sqdist(lc(), X1_own, ref_own, partials_.p, slots[4]); valid |= 0x10; }
+    if (X2_own && d2) { launch_sqdist(lc(), X2_own, ref_own, partials_.p, slots[5]); valid |= 0x20; }
   }
   launch_star_sums(st_, T_, num_local(), valid, slots, partials_.p, star_vals_.p);
   const bool dev_sum = coll_allreduce_dev_ != nullptr;
@@ -2203,7 +2200,7 @@ int Group::star_iterate() {
     r.refined = (r.gradFnorm * r.gradFnorm / r.fobj) > o.accepted_delta;   // :515-516
     if (r.refined) ref.push_back(a);
   }
-  launch_proximal(d_, st_, T_, cur_mask_, Y_.p, Dfx_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
+  launch_proximal(lc(), Y_.p, Dfx_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
   copy_rows(Xak_.p, Xakh_.p, false, 2);
   recover_translations(Xak_.p, gx_.p);
   if (!ref.empty()) run_tnt(ref, Xak_.p, gx_.p, nullptr, true);
@@ -2214,7 +2211,7 @@ int Group::star_iterate() {
   set_mask(all);
   if (fobjh > starF_ - o.psi * sqh) {
     star_branches_ |= 1;   // pm_pgo_n (:685-711)
-    launch_proximal(d_, st_, T_, cur_mask_, Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
+    launch_proximal(lc(), Zc_.p, Dfc_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, nullptr, nullptr, 0);
     fobjh = global_objective(Xakh_.p);
   }
   set_mask(all);

@@ -434,11 +434,10 @@ class Group {
   const NodeBits *class_tt_ = nullptr, *class_rr_ = nullptr;
   void solve_tt(double *in, double *out, double scale);   // out.t <- scale * G_tt^-1 in.t
   void solve_rr(double *in, double *out, double scale);   // out.R <- scale * (G_RR + lambda I)^-1 in.R
-  void apply_tcol(const double *xt, const double *base, double *y, int mode = 0, const double *X = nullptr,
-                  const double *nabla = nullptr, const double *Rdot = nullptr, double *out2 = nullptr,
-                  const double *rres = nullptr, double *partials = nullptr, const double *dg = nullptr,
-                  const double *dga = nullptr, const double *ds = nullptr, const double *dgrad = nullptr,
-                  const double *dhs = nullptr);
+  // the context of this group's launches (kernels.h) over the nodes of m / of cur_mask_
+  LaunchCtx lc(const NodeMask &m) const { return {d_, st_, T_, m}; }
+  LaunchCtx lc() const { return lc(cur_mask_); }
+  TcolOp g_tcol() const { return {G_.dev, G_.tcol.p}; }   // G's translation column: y = base + G_{:,t} xt.t (launch_bsr_tcol*)
   void recover_translations(double *X, const double *g);  // X.t = -Gtt^-1 (g_t + G_tR X.R) for masked nodes
   void eval_G(const double *X, const double *g, int slot);
   void host_update_logic(int local, double fobj, double f, double gradFnorm);

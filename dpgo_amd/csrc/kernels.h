@@ -118,67 +118,129 @@ struct SegTable {
   const int *nbr_ptr = nullptr;   // per node: [nbr_ptr[a], nbr_ptr[a+1]) neighbour segments (indices into segs)
 };
 
-// y = A x (+ addv) ; partial[slot] = sum_p < dotv_p , coef * (A x)_p + dotadd_p >
-// mode 1 (true): the translation row of x is treated as zero (G_tR R products).  mode 2: y as in mode 1, but the
-// dot product sees the full A x -- one pass for "G [0 ; R] + g" and "<x, 1/2 G x + g'>" (DPGOHash.cpp:363-372).
-void launch_bsr(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask, const BsrDev &A,
-                const double *x, int mode, const double *addv, double *y, const double *dotv,
-                double coef, const double *dotadd, double *partials, int slot,
-                // copy1 / copy2: the own rows' records of x are stored there on the way (the tail of iterate(): Xk <- Xak)
-                double *copy1 = nullptr, double *copy2 = nullptr);
+// What a segment launcher needs before its operands: the pose dimension, the stream, the segment table and the nodes the launch
+// works on.  Group::lc() builds it; the launchers take it as their first parameter.
+struct LaunchCtx {
+  int d;
+  hipStream_t st;
+  const SegTable &T;
+  NodeMask mask;
+};
 
-// y = base + A[:, translation column] t over own rows; tval: the first column of every block of A ((d+1) doubles per
-// block), xt: records whose translation row is t.  A quarter of the traffic of launch_bsr.
-// mode 1: also out2 = [0 ; Proj_X(y.R)]; mode 2: y not stored, out2 = [0 ; Proj_X(y.R - sym(nabla.R X.R^T) Rdot.R)], the Hessian-vector product (DPGOProblem.cpp:570-574)
-// mode 2 with partials: slots 0..3 = <Rdot, out2>, <out2, out2>, <Rdot, Rdot>, <Rdot, rres> (the four scalars of a
-// CG step, IterativeSolvers.h:296-347) in the same pass
-// mode 1 with partials and dg / dga: slots 0..3 = |out2|^2, <X, y>, <X, dg>, <X, dga> (the start of a refinement: gradient
-// norm and f from the model gradient y)
-// mode 0 with partials and ds / dgrad / dhs / dg / dga: slots 0..5 = <ds,ds>, <dgrad,ds>, <ds,dhs> (rotation rows),
-// <xt,dg>, <xt,dga>, <xt,y> (the sums of a trial point xt, TNT.h:505-536)
-// (the epilogue sums always occupy 6 consecutive slots)
-void launch_bsr_tcol(int d, hipStream_t st, const SegTable &T, NodeMask mask, const BsrDev &A, const double *tval,
-                     const double *xt, const double *base, double *y, int mode = 0, const double *X = nullptr,
-                     const double *nabla = nullptr, const double *Rdot = nullptr, double *out2 = nullptr,
-                     const double *rres = nullptr, double *partials = nullptr, const double *dg = nullptr,
-                     const double *dga = nullptr, const double *ds = nullptr, const double *dgrad = nullptr,
-                     const double *dhs = nullptr);
+// ---- y = A x (+ addv), with an optional dot product and optional copies of x in the same pass (k_bsr) ----
+enum class BsrMode {
+  Full = 0,          // the full product
+  NoTrans = 1,       // the translation row of x is taken as zero (G_tR R products)
+  NoTransFullDot = 2 // y as NoTrans, but the dot product sees the full A x -- one pass for "G [0 ; R] + g" and
+                     // "<x, 1/2 G x + g'>" (DPGOHash.cpp:363-372)
+};
+// partial[slot] = sum_p < v_p , coef * (A x)_p + add_p >; produced when v and partials are both there
+struct BsrDot {
+  const double *v = nullptr;
+  double coef = 0.0;
+  const double *add = nullptr;
+  double *partials = nullptr;
+  int slot = 0;
+};
+// the own rows' records of x are stored there on the way (the tail of iterate(): Xk <- Xak)
+struct BsrCopy {
+  double *to1 = nullptr, *to2 = nullptr;
+};
+struct BsrArgs {
+  bool all_rows = false;   // own and neighbour rows (own rows only otherwise)
+  const double *x = nullptr;
+  BsrMode mode = BsrMode::Full;
+  const double *addv = nullptr;
+  double *y = nullptr;     // null: not stored
+  BsrDot dot;
+  BsrCopy copy;
+};
+void launch_bsr(const LaunchCtx &lc, const BsrDev &A, const BsrArgs &a);
 
-// what the robust inter-edge pass does on the way, instead of a launch of its own
-struct InterFuse {
-  // mode 0 (update()): Dfobj = G X + g from the product that is there already, its tangent projection and |grad F|^2 into
-  // partial slot gn_slot -- k_tangent_full's job (DPGOProblem.cpp:145-162); X: the own rows' records
+// ---- y = base + A[:, translation column] t over own rows (k_bsr_tcol): a quarter of the traffic of launch_bsr ----
+// the operator: A's block index and tval, the first column of every block of A ((d+1) doubles per block)
+struct TcolOp {
+  const BsrDev &A;
+  const double *tval;
+};
+// The three modes of the kernel have disjoint epilogues, hence one struct and one entry point each.  In all of them xt holds
+// the records whose translation row is t; the epilogue sums, where produced, occupy 6 consecutive slots from `partials` on.
+// plain (no sums), or -- with partials and s -- a trial point xt (TNT.h:505-536): slots 0..5 = <s,s>, <grad,s>, <s,hs>
+// (rotation rows), <xt,g>, <xt,ga>, <xt,y>
+struct TcolTrial {
+  const double *xt = nullptr, *base = nullptr;
+  double *y = nullptr;
+  double *partials = nullptr;
+  const double *g = nullptr, *ga = nullptr;                   // the linear terms of f and of the caller's second surrogate
+  const double *s = nullptr, *grad = nullptr, *hs = nullptr;  // the step, the tangent gradient, H s
+};
+void launch_bsr_tcol(const LaunchCtx &lc, const TcolOp &op, const TcolTrial &a);
+// the start of a refinement: y (the model gradient) and grad = [0 ; Proj_X(y.R)]; with partials and g: slots 0..3 = |grad|^2,
+// <X, y>, <X, g>, <X, ga> (gradient norm and f)
+struct TcolBegin {
+  const double *xt = nullptr, *base = nullptr;
+  double *y = nullptr;
+  const double *X = nullptr;
+  double *grad = nullptr;
+  double *partials = nullptr;
+  const double *g = nullptr, *ga = nullptr;
+};
+void launch_bsr_tcol_begin(const LaunchCtx &lc, const TcolOp &op, const TcolBegin &a);
+// the Hessian-vector product (DPGOProblem.cpp:570-574): with y = base + A[:, t] t (not stored),
+// Hp = [0 ; Proj_X(y.R - sym(nabla.R X.R^T) p.R)]; with partials and r: slots 0..3 = <p, Hp>, <Hp, Hp>, <p, p>, <p, r>
+// (the four scalars of a CG step, IterativeSolvers.h:296-347)
+struct TcolHess {
+  const double *xt = nullptr, *base = nullptr;
+  const double *X = nullptr, *nabla = nullptr, *p = nullptr;
+  double *Hp = nullptr;
+  const double *r = nullptr;
+  double *partials = nullptr;
+};
+void launch_bsr_tcol_hess(const LaunchCtx &lc, const TcolOp &op, const TcolHess &a);
+
+// ---- Robust inter-edge pass (B-form, DPGOProblem.cpp:634-725; k_inter) ----
+// update(): all rows.  DfE <- B1^T W B1 Z; own rows also g <- DfE - D z.
+//   slot 0: sum of rho_e (tail incidences); if quad: slot 1 = sum tr(dZ^T (DfE_old + 1/2 Q dZ)); slot 2: <z, g> over own rows
+//   (always written: three consecutive slots).
+//   A lazy unpack (InterEdgesDev::recv / nsrc) is taken by this pass only.
+struct InterUpdate {
+  bool quad = false;
+  const double *Z = nullptr, *Zprev = nullptr;
+  const double *Qdiag = nullptr, *Ddiag = nullptr;
+  double *DfE = nullptr, *g = nullptr, *partials = nullptr;
+  double *wout = nullptr;         // the loss weight of every edge
+  const double *Znbr = nullptr;   // the neighbour rows are read from Znbr and copied into Z on the way (the halo copy of update())
+  // Dfobj = G X + g from the product that is there already, its tangent projection and |grad F|^2 into partial slot gn_slot --
+  // k_tangent_full's job (DPGOProblem.cpp:145-162); X: the own rows' records
   const double *GX = nullptr, *X = nullptr;
   double *Df = nullptr;
   int gn_slot = 0;
-  // mode 1 (iterate()): the point itself is formed on the way, Z = Zc + gamma (Zc - Zp) -- k_extrapolate's job
-  // (DPGOHash.cpp:255-256), for the row and for every pose its incidences reach; the own rows are stored to Yout
+};
+void launch_inter_update(const LaunchCtx &lc, const InterEdgesDev &E, int loss, double loss_reg, const InterUpdate &a);
+// iterate() (evaluate_g): own rows only, g <- (B1^T W B1 Z)_own - D z; slot 2: <z, g>.
+struct InterIterate {
+  const double *Z = nullptr, *Ddiag = nullptr;
+  double *g = nullptr, *partials = nullptr;
+  // gamma: the extrapolation coefficients by value; gamma_dev: the same in device memory (launch_set_coefs) -- read instead of
+  // `gamma` by a launch that may be replayed from a captured graph, whose by-value arguments are frozen
+  const NodeCoefs *gamma = nullptr;
+  const double *gamma_dev = nullptr;
+  // with GXc, GXp and gamma: Df = g + GXc + gamma[node] (GXc - GXp) over own rows is formed -- Df at the extrapolated point from
+  // the products G X[k], G X[k-1] the last two update()s left (no pass over G) -- and stored to Df_out, if given
+  const double *GXc = nullptr, *GXp = nullptr;
+  double *Df_out = nullptr;
+  // with gamma: the point itself is formed on the way, Z = Zc + gamma (Zc - Zp) -- k_extrapolate's job (DPGOHash.cpp:255-256),
+  // for the row and for every pose its incidences reach; the own rows are stored to Yout
   const double *Zc = nullptr, *Zp = nullptr;
   double *Yout = nullptr;
-  // mode 1 with the kept products (GXc / GXp: the pass forms Df itself): the proximal half step on the way -- k_proximal's job
-  // (DPGOProblem.cpp:600-632): Xout = proximal(Y, Df), |Xout - Xref|^2 into partial slot gn_slot, Xref's rotations <- Xout's;
-  // Df itself is then only stored if the caller asks for it
+  // the proximal half step on the way -- k_proximal's job (DPGOProblem.cpp:600-632): Xout = proximal(Y, Df), |Xout - Xref|^2
+  // into partial slot gn_slot, Xref's rotations <- Xout's.  It needs the Df this pass forms and takes over its store: the
+  // launcher takes it only with GXc, GXp and gamma there and Df_out null, and drops these six fields otherwise
   double *Xout = nullptr, *Xref = nullptr;
   const double *Tinv = nullptr, *Nv = nullptr, *Vb = nullptr;
+  int gn_slot = 0;
 };
-// Robust inter-edge pass (B-form, DPGOProblem.cpp:634-725).
-//  mode 0 (update): all rows.  DfE <- B1^T W B1 Z; own rows also g <- DfE - D z.
-//     slot 0: sum of rho_e (tail incidences); if quad: slot 1 = sum tr(dZ^T (DfE_old + 1/2 Q dZ)); slot 2: <z, g> over
-//     own rows (always written: three consecutive slots).
-//  mode 1 (evaluate_g): own rows only, g <- (B1^T W B1 Z)_own - D z.
-void launch_inter(int d, hipStream_t st, const SegTable &T, NodeMask mask, const InterEdgesDev &E, int loss,
-                  double loss_reg, int mode, bool quad, const double *Z, const double *Zprev,
-                  const double *Qdiag, const double *Ddiag, double *DfE, double *g, double *partials,
-                  double *wout = nullptr,   // wout (mode 0): the loss weight of every edge
-                  // mode 1 with all four: also Df_out = g + GXc + gamma[node] (GXc - GXp) over own rows -- Df at the extrapolated
-                  // point from the products G X[k], G X[k-1] the last two update()s left (no pass over G)
-                  const double *GXc = nullptr, const double *GXp = nullptr, const NodeCoefs *gamma = nullptr, double *Df_out = nullptr,
-                  // mode 0 with Znbr: the neighbour rows are read from Znbr and copied into Z on the way (the halo copy of update())
-                  const double *Znbr = nullptr,
-                  // gamma_dev: the same gammas in device memory (launch_set_coefs) -- read instead of `gamma` by a launch that may be
-                  // replayed from a captured graph, whose by-value arguments are frozen
-                  const double *gamma_dev = nullptr,
-                  const InterFuse *fuse = nullptr);
+void launch_inter_iterate(const LaunchCtx &lc, const InterEdgesDev &E, int loss, double loss_reg, const InterIterate &a);
 
 // ---- Rescale::Dynamic on the device (see k_rescale_decide / k_rescale_apply) ----
 // decide: flags[a] / host_flags[a] = node a (of `nodes`) is rescaled; its scales and counter are updated
@@ -197,23 +259,20 @@ void launch_rescale_apply(int d, hipStream_t st, const SegTable &T, const InterE
 
 // Objective of every node at Z (own + neighbour rows): partial[slot0] = sum of intra-edge costs,
 // partial[slot0 + 1] = sum of rho over inter-edge costs; eform selects the data-matrix form (trivial loss).
-void launch_cost(int d, hipStream_t st, const SegTable &T, NodeMask mask, const InterEdgesDev &Ei,
-                 const InterEdgesDev &Ee, bool eform, int loss, double loss_reg, const double *Z, double *partials,
-                 int slot0);
+void launch_cost(const LaunchCtx &lc, const InterEdgesDev &Ei, const InterEdgesDev &Ee, bool eform, int loss, double loss_reg,
+                 const double *Z, double *partials, int slot0);
 // partial[slot] = sum |a_p - b_p|^2 over own rows
-void launch_sqdist(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *a, const double *b,
-                   double *partials, int slot);
+void launch_sqdist(const LaunchCtx &lc, const double *a, const double *b, double *partials, int slot);
 // Xout = proximal(Z, Df) per own pose (DPGOProblem.cpp:600-632).  With Xref: partial ||Xout - Xref||^2, after which
 // Xref takes over Xout's rotation rows (the next step recovers its translations: DPGOHash.cpp:369-372).
-void launch_proximal(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Z, const double *Df,
-                     const double *Tinv, const double *N, const double *V, double *Xout, double *Xref,
-                     double *partials, int slot);
+void launch_proximal(const LaunchCtx &lc, const double *Z, const double *Df, const double *Tinv, const double *N,
+                     const double *V, double *Xout, double *Xref, double *partials, int slot);
 
 // out = a + gamma[node] * (a - b) over all rows (own + neighbour)      (DPGOHash.cpp:255-262)
-void launch_extrapolate(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask,
-                        const NodeCoefs &gamma, const double *a, const double *b, double *out, const double *gamma_dev = nullptr);
+void launch_extrapolate(const LaunchCtx &lc, bool all_rows, const NodeCoefs &gamma, const double *a, const double *b, double *out,
+                        const double *gamma_dev = nullptr);
 // the same for three pairs in one launch: (za, zb) -> zout over all rows, (ga, gb) -> gout and (da, db) -> dout over the own rows
-void launch_extrapolate3(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &gamma, const double *gamma_dev,
+void launch_extrapolate3(const LaunchCtx &lc, const NodeCoefs &gamma, const double *gamma_dev,
                          const double *za, const double *zb, double *zout, const double *ga, const double *gb, double *gout,
                          const double *da, const double *db, double *dout);
 // dev[a] = C.a[a], a < n: the per-iteration coefficients where replayed launches find them (k_set_coefs)
@@ -221,54 +280,65 @@ void launch_set_coefs(hipStream_t st, const NodeCoefs &C, int n, double *dev);
 // The tail of iterate() with the exchange's pack on the way: xk = xak (and z = xak, if given) over the own rows of the masked
 // nodes, and -- further workgroups of the same launch -- pack[k] = xak[pack_rows[k]], k < npack, whatever the mask (the send
 // buffer of the boundary exchange, DPGOHash.h:64-82: own rows of nodes outside the mask have not changed, and xak holds them)
-void launch_tail_pack(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *xak, double *xk, double *z,
+void launch_tail_pack(const LaunchCtx &lc, const double *xak, double *xk, double *z,
                       const int *pack_rows, int npack, double *pack);
 // out = alpha * a + beta * b  (b may be null); parts: 0 whole record, 1 translation only, 2 rotation only
 // out2 (part 0 only): a second copy of the result
-void launch_axpby(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask, double alpha,
+void launch_axpby(const LaunchCtx &lc, bool all_rows, double alpha,
                   const double *a, double beta, const double *b, double *out, int part, double *out2 = nullptr);
 // out = C.a[node] * a + C.b[node] * b over own rows
-void launch_axpby_node(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &C, const double *a,
-                       const double *b, double *out);
+void launch_axpby_node(const LaunchCtx &lc, const NodeCoefs &C, const double *a, const double *b, double *out);
 // p = -v + cg[node].be * p (the CG direction update with the device-resident beta)
-void launch_cg_dir(int d, hipStream_t st, const SegTable &T, NodeMask mask, const CgNode *cg, const double *v, double *p);
+void launch_cg_dir(const LaunchCtx &lc, const CgNode *cg, const double *v, double *p);
 // n <= MAX_DOTS dot products in one pass over own rows: partial[slot0 + q] = sum <a_q, b_q> over parts[q]
 // (0 whole record, 1 translation row, 2 rotation rows); always writes MAX_DOTS slots
-void launch_dots(int d, hipStream_t st, const SegTable &T, NodeMask mask, int n, const double *const *a,
+void launch_dots(const LaunchCtx &lc, int n, const double *const *a,
                  const double *const *b, const int *parts, double *partials, int slot0);
-// one CG step (IterativeSolvers.h:340-390): s += C.a[node] p, hs += C.a[node] Hp, and r += C.b[node] Hp where C.b != 0
-void launch_cg_step(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &C, const double *p,
-                    const double *Hp, double *s, double *hs, double *r, const CgNode *cg = nullptr,   // cg: coefficients from the device state
-                    const double *r0 = nullptr,    // r0: first step of a run -- s = hs = 0 (not read), r = r0
-                    // xprop: the nodes of *rmask (device) also get xprop.Y = proj_SO(d)(X.Y + s.Y), xprop.x = 0 (launch_retract_rot)
-                    const double *X = nullptr, double *xprop = nullptr, const NodeBits *rmask = nullptr);
+// one CG step (IterativeSolvers.h:340-390): s += a[node] p, hs += a[node] Hp, and r += b[node] Hp where b != 0
+struct CgStepArgs {
+  const NodeCoefs *C = nullptr;   // the coefficients a, b by value (null: zeros) ...
+  const CgNode *cg = nullptr;     // ... or from the device state (c1, cr)
+  const double *p = nullptr, *Hp = nullptr;
+  double *s = nullptr, *hs = nullptr, *r = nullptr;
+  const double *r0 = nullptr;     // first step of a run -- s = hs = 0 (not read), r = r0
+  // xprop: the nodes of *rmask (device) also get xprop.Y = proj_SO(d)(X.Y + s.Y), xprop.x = 0 (launch_retract_rot)
+  const double *X = nullptr;
+  double *xprop = nullptr;
+  const NodeBits *rmask = nullptr;
+};
+void launch_cg_step(const LaunchCtx &lc, const CgStepArgs &a);
 // start of a truncated CG (IterativeSolvers.h:230-260): s = 0, hs = 0, r = grad, v = pgrad, p = -pgrad; with s == nullptr
 // only p = -pgrad (the first launch_cg_step, given r0 = grad, supplies the rest)
-void launch_cg_init(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *grad, const double *pgrad,
+void launch_cg_init(const LaunchCtx &lc, const double *grad, const double *pgrad,
                     double *s, double *hs, double *r, double *v, double *p);
 // gradF = [V.x ; Proj_R(V.Y)] (DPGOProblem.cpp:145-162); partial ||gradF||^2; out may be null
 // with add: the vector is V + add, stored to sum_out if given (Dfobj = G X + g from its two halves)
-void launch_tangent_full(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
-                         const double *V, double *out, double *partials, int slot, const double *add = nullptr,
-                         double *sum_out = nullptr);
+void launch_tangent_full(const LaunchCtx &lc, const double *X, const double *V, double *out, double *partials, int slot,
+                         const double *add = nullptr, double *sum_out = nullptr);
 // dst = src on the neighbour rows only
-void launch_copy_nbr_rows(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *src, double *dst);
+void launch_copy_nbr_rows(const LaunchCtx &lc, const double *src, double *dst);
 // out.Y = Proj_R(in.Y), out.x = 0                                       (DPGOProblem.cpp:164-178)
-// with dotv: partial[slot] = <dotv.Y, out.Y> in the same pass; two: partial[slot] = |out.Y|^2, partial[slot + 1] = <dotv.Y, out.Y>
-// neg: also neg = -out (the first CG direction)
-void launch_tangent_rot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
-                        const double *in, double *out, const double *dotv = nullptr, double *partials = nullptr,
-                        int slot = 0, bool two = false, double *neg = nullptr);
+struct TangentRotArgs {
+  const double *X = nullptr, *in = nullptr;
+  double *out = nullptr;
+  // with dotv and partials: partial[slot] = <dotv.Y, out.Y> in the same pass; two: partial[slot] = |out.Y|^2,
+  // partial[slot + 1] = <dotv.Y, out.Y>
+  const double *dotv = nullptr;
+  double *partials = nullptr;
+  int slot = 0;
+  bool two = false;
+  double *neg = nullptr;   // also neg = -out (the first CG direction)
+};
+void launch_tangent_rot(const LaunchCtx &lc, const TangentRotArgs &a);
 // out.Y rows = dinv (one entry per rotation row) * in.Y rows: Preconditioner::Jacobi   (DPGOProblem.cpp:96-98, 583-585)
-void launch_rot_rowscale(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *dinv, const double *in, double *out);
+void launch_rot_rowscale(const LaunchCtx &lc, const double *dinv, const double *in, double *out);
 // out.Y = proj_SO(d)(X.Y + V.Y); out.x = 0                              (SOdProduct.h:111-116)
-void launch_retract_rot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
-                        const double *V, double *out);
+void launch_retract_rot(const LaunchCtx &lc, const double *X, const double *V, double *out);
 // dst[didx[k]] = src[sidx[k]] (didx may be null: dst[k]); halo copy, pack, unpack (DPGOHash.h:28-86)
 void launch_copy_indexed(int d, hipStream_t st, int count, const int *didx, const int *sidx, const double *src,
                          double *dst, const NodeBits *gate = nullptr);   // gate: a device word; 0 switches the launch off
 // partial[slot] = sum_p < x_p , coef * (D_p x_p) + addcoef * add_p > over own rows
-void launch_bdiag_dot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Dd, const double *x,
+void launch_bdiag_dot(const LaunchCtx &lc, const double *Dd, const double *x,
                       double coef, const double *add, double addcoef, double *partials, int slot);
 
 // The read-back flag a launch raises once its sums are in pinned host memory (schedule.h): the last of its workgroups to
@@ -314,19 +384,29 @@ constexpr int CG_SUMMARY = 4;    // doubles per node k_cg_scal writes to pinned 
 // on how far the stream has run ahead of it.
 constexpr double CG_LIVE_ORD = 1e18;
 constexpr int TNT_SUMMARY = 8;   // doubles per node k_tnt_begin writes: the six sums it reduced, then `active`
+// the start of a refinement, as launch_tnt_begin and launch_cg_scal_begin take it: the nodes, the tolerances of the gradient
+// tests and of the CG, the trust-region radii (host, one per node), where the six sums are and where the results go
+struct TntStart {
+  int nnodes = 0;
+  NodeBits bits = 0;
+  bool use_precon = false;
+  int max_it = 0;
+  double grad_tol = 0, pgrad_tol = 0, kappa = 0, theta = 0;
+  const double *Delta = nullptr;
+  const double *partials = nullptr;
+  CgNode *cg = nullptr;
+  NodeBits *dmask = nullptr;
+  double *host_tnt = nullptr;
+};
 // tnt_begin: the first trust-region iteration's norms, gradient tests and CG start values, all on the device (see k_tnt_begin)
-void launch_tnt_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
-                      double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                      NodeBits *dmask, double *host_tnt);
+void launch_tnt_begin(hipStream_t st, const SegTable &T, const TntStart &S);
 // tnt_begin and the phase-0 step of the first CG step in one launch (k_cg_scal_begin): the refinement's six sums in the partial
 // slots 0..3 and MAX_DOTS.., the step's four from slot cg_first_slot() on; the flag protocol of launch_cg_scal
-void launch_cg_scal_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
-                           double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                           NodeBits *dmask, double *host_tnt, double *host_scalars, ReadbackFlag flag,
-                           double *dev_tnt = nullptr,   // dev_tnt: host_tnt's numbers in device memory too
-                           // carry: the reduction that closes the LAST update() rides along (k_reduce's work: upd_nslots sums per node over
-                           // own and neighbour segments of the partial sums from slot UPD_SLOT0 on, to upd_host[node * MAX_SLOTS + s])
-                           int upd_nslots = 0, double *upd_host = nullptr);
+void launch_cg_scal_begin(hipStream_t st, const SegTable &T, const TntStart &S, double *host_scalars, ReadbackFlag flag,
+                          double *dev_tnt = nullptr,   // dev_tnt: host_tnt's numbers in device memory too
+                          // carry: the reduction that closes the LAST update() rides along (k_reduce's work: upd_nslots sums per node over
+                          // own and neighbour segments of the partial sums from slot UPD_SLOT0 on, to upd_host[node * MAX_SLOTS + s])
+                          int upd_nslots = 0, double *upd_host = nullptr);
 int cg_first_slot();
 // cg_begin: state of the nodes in `bits` from the start values; dmask[0] = dmask[1] = the live ones, dmask[2] = the others.
 void launch_cg_begin(hipStream_t st, int nnodes, NodeBits bits, const CgStart &S, int max_it, CgNode *cg, NodeBits *dmask);

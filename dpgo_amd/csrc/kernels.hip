@@ -14,6 +14,17 @@
 #include <vector>
 
 namespace dpgo {
+// what k_inter does on the way, instead of a launch of its own: the fusion fields of InterUpdate (GX, X, Df, gn_slot) or of
+// InterIterate (the rest), as the kernel takes them
+struct InterFuse {
+  const double *GX = nullptr, *X = nullptr;
+  double *Df = nullptr;
+  int gn_slot = 0;
+  const double *Zc = nullptr, *Zp = nullptr;
+  double *Yout = nullptr;
+  double *Xout = nullptr, *Xref = nullptr;
+  const double *Tinv = nullptr, *Nv = nullptr, *Vb = nullptr;
+};
 namespace {
 
 template <int D>
@@ -2484,34 +2495,33 @@ static inline int own_grid(const SegTable &T, const NodeMask &m) {
 }
 static inline NodeMask whole_grid(NodeMask m) { m.nlive = 0; return m; }   // (launches that also cover the neighbour segments)
 
-void launch_bsr(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask, const BsrDev &A,
-                const double *x, int mode, const double *addv, double *y, const double *dotv,
-                double coef, const double *dotadd, double *partials, int slot, double *copy1, double *copy2) {
-  if (all_rows) mask = whole_grid(mask);
-  const int nb = all_rows ? T.nseg_all : own_grid(T, mask);
+void launch_bsr(const LaunchCtx &lc, const BsrDev &A, const BsrArgs &a) {
+  const auto &[d, st, T, ctx_mask] = lc;
+  const NodeMask mask = a.all_rows ? whole_grid(ctx_mask) : ctx_mask;
+  const int nb = a.all_rows ? T.nseg_all : own_grid(T, mask);
   if (nb == 0) return;
-  double *part = (dotv && partials) ? partials + (size_t)slot * T.nseg_all : nullptr;
+  double *part = (a.dot.v && a.dot.partials) ? a.dot.partials + (size_t)a.dot.slot * T.nseg_all : nullptr;
   ProfScope ps(PK_BSR, st, (double)A.nnzb * (8.0 * (d + 1) * (d + 1) + 4) + 2.0 * A.nrows * 8.0 * (d + 1) * d);
+#define DPGO_BSR_LAUNCH(MODE)                                                                                                  \
+  hipLaunchKernelGGL((k_bsr<D, MODE>), dim3(nb), dim3(BSR_LPR * SEG_ROWS), 0, st, T.segs, mask, A, a.x, a.addv, a.y, a.dot.v, a.dot.coef, \
+                     a.dot.add, part, a.copy.to1, a.copy.to2)
   DPGO_DISPATCH_D(d, {
-    if (mode == 1)
-      hipLaunchKernelGGL((k_bsr<D, 1>), dim3(nb), dim3(BSR_LPR * SEG_ROWS), 0, st, T.segs, mask, A, x, addv, y, dotv, coef, dotadd,
-                         part, copy1, copy2);
-    else if (mode == 2)
-      hipLaunchKernelGGL((k_bsr<D, 2>), dim3(nb), dim3(BSR_LPR * SEG_ROWS), 0, st, T.segs, mask, A, x, addv, y, dotv, coef, dotadd,
-                         part, copy1, copy2);
-    else
-      hipLaunchKernelGGL((k_bsr<D, 0>), dim3(nb), dim3(BSR_LPR * SEG_ROWS), 0, st, T.segs, mask, A, x, addv, y, dotv, coef, dotadd,
-                         part, copy1, copy2);
+    if (a.mode == BsrMode::NoTrans) DPGO_BSR_LAUNCH(1);
+    else if (a.mode == BsrMode::NoTransFullDot) DPGO_BSR_LAUNCH(2);
+    else DPGO_BSR_LAUNCH(0);
   });
+#undef DPGO_BSR_LAUNCH
 }
 
-void launch_bsr_tcol(int d, hipStream_t st, const SegTable &T, NodeMask mask, const BsrDev &A, const double *tval,
-                     const double *xt, const double *base, double *y, int mode, const double *X, const double *nabla,
-                     const double *Rdot, double *out2, const double *rres, double *partials, const double *dg,
-                     const double *dga, const double *ds, const double *dgrad, const double *dhs) {
+// the three entry points of k_bsr_tcol end here; sums: whether the mode's epilogue sums are produced
+static void bsr_tcol(const LaunchCtx &lc, const TcolOp &op, const double *xt, const double *base, double *y, int mode, const double *X,
+                     const double *nabla, const double *Rdot, double *out2, const double *rres, double *partials, bool sums,
+                     const TcolDots &E) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
-  // which epilogue sums are produced: mode 2 with rres (a CG step's four), mode 1 with dg (a refinement's start), mode 0 with ds (a trial point's six)
-  const bool sums = partials && ((mode == 2 && rres) || (mode == 1 && dg) || (mode == 0 && ds));
+  const BsrDev &A = op.A;
+  const double *dg = E.g, *dga = E.ga;
+  sums = sums && partials;
   // SURVEY 8(d)'s formula prices the bare pass (the blocks' first columns, the gathered translations, two vectors).  What
   // the fused pass moves, operand by operand: per block its first column and index; per row the translation its
   // neighbours gather (once: the rest are cache hits), `base`, y where it is stored, and the epilogue's vectors -- mode 1
@@ -2525,49 +2535,73 @@ void launch_bsr_tcol(int d, hipStream_t st, const SegTable &T, NodeMask mask, co
   if (mode == 0 && sums) per_row += 3.0 * Pr + P + (dg ? P : 0.0) + ((dga && dga != dg) ? P : 0.0);
   ProfScope ps(PK_BSR_TCOL, st, (double)A.nnzb * (8.0 * (d + 1) + 4 + 8.0 * d) + 2.0 * A.nrows * 8.0 * (d + 1) * d, 1,
                (double)A.nnzb * (8.0 * (d + 1) + 4) + (double)A.nrows * per_row);
-  TcolDots E;
-  E.g = dg; E.ga = dga; E.s = ds; E.grad = dgrad; E.hs = dhs;
-  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_bsr_tcol<D>), dim3(own_grid(T, mask)), dim3(4 * SEG_ROWS), 0, st, T.segs, mask, A, tval,
+  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_bsr_tcol<D>), dim3(own_grid(T, mask)), dim3(4 * SEG_ROWS), 0, st, T.segs, mask, A, op.tval,
                                         xt, base, y, mode, X, nabla, Rdot, out2, rres, sums ? partials : nullptr, T.nseg_all, E));
 }
+void launch_bsr_tcol(const LaunchCtx &lc, const TcolOp &op, const TcolTrial &a) {
+  TcolDots E;
+  E.g = a.g; E.ga = a.ga; E.s = a.s; E.grad = a.grad; E.hs = a.hs;
+  bsr_tcol(lc, op, a.xt, a.base, a.y, 0, nullptr, nullptr, nullptr, nullptr, nullptr, a.partials, a.s != nullptr, E);
+}
+void launch_bsr_tcol_begin(const LaunchCtx &lc, const TcolOp &op, const TcolBegin &a) {
+  TcolDots E;
+  E.g = a.g; E.ga = a.ga;
+  bsr_tcol(lc, op, a.xt, a.base, a.y, 1, a.X, nullptr, nullptr, a.grad, nullptr, a.partials, a.g != nullptr, E);
+}
+void launch_bsr_tcol_hess(const LaunchCtx &lc, const TcolOp &op, const TcolHess &a) {
+  bsr_tcol(lc, op, a.xt, a.base, nullptr, 2, a.X, a.nabla, a.p, a.Hp, a.r, a.partials, a.r != nullptr, TcolDots());
+}
 
-void launch_inter(int d, hipStream_t st, const SegTable &T, NodeMask mask, const InterEdgesDev &E, int loss,
-                  double loss_reg, int mode, bool quad, const double *Z, const double *Zprev,
-                  const double *Qdiag, const double *Ddiag, double *DfE, double *g, double *partials, double *wout,
-                  const double *GXc, const double *GXp, const NodeCoefs *gamma, double *Df_out, const double *Znbr,
-                  const double *gamma_dev, const InterFuse *fuse) {
-  const int nb = mode == 0 ? T.nseg_all : T.nseg_own;
-  if (nb == 0) return;
-  InterFuse F;
-  if (fuse) {
-    if (mode == 0) { F.GX = fuse->GX; F.X = fuse->X; F.Df = fuse->Df; F.gn_slot = fuse->gn_slot; }
-    else {
-      F.Zc = fuse->Zc; F.Zp = fuse->Zp; F.Yout = fuse->Yout;
-      if (fuse->Xout && Df_out == nullptr && GXc && GXp && gamma) {   // (the proximal step needs the Df this pass forms)
-        F.Xout = fuse->Xout; F.Xref = fuse->Xref; F.Tinv = fuse->Tinv; F.Nv = fuse->Nv; F.Vb = fuse->Vb; F.gn_slot = fuse->gn_slot;
-      }
-    }
-  }
-  // operand by operand: per incidence its 128-byte record and the other endpoint's pose; per own pose its record, the previous
-  // iterate (majorisation gap), the previous DfobjE read and the new one written, the Q and D blocks, g written, the
-  // incidence pointer, and (iterate()) the two kept products G X read and Df written; per neighbour row the same without
-  // D and g but with the halo copy it performs on the way
-  const double P = 8.0 * (d + 1) * d, B = 8.0 * (d + 1) * (d + 1);
-  const double own_b = P + (Zprev ? P : 0) + (DfE ? 2 * P : 0) + (Qdiag ? B : 0) + (Ddiag ? B : 0) + (g ? P : 0) + 8 +
-                       ((mode == 1 && Df_out && GXc && GXp) ? 3 * P : 0) +
-                       ((fuse && mode == 0 && fuse->Df) ? 3 * P : 0) +     // the product G X and the own record read, Dfobj written
-                       ((fuse && mode == 1 && fuse->Zc) ? 2 * P : 0);      // X[k-1] read, the extrapolated record written
-  const double prox_b = (fuse && mode == 1 && fuse->Xout) ? (2 * P + 8.0 * (1 + d + d * d) + 8.0 * d * d - P) : 0.0;   // Xakh written, Xak read and its rotations written, T / N / V; Df no longer written
-  const double nbr_b = P + (Zprev ? P : 0) + (DfE ? 2 * P : 0) + (Qdiag ? B : 0) + 8 + (Znbr ? 2 * P : 0);
-  const double operands = (double)E.m * (mode == 0 ? 2 : 1) * (128.0 + ((fuse && mode == 1 && fuse->Zc) ? 2 * P : P)) + (double)E.nrows_own * (own_b + prox_b) +
+// the two entry points of k_inter end here (mode 0: update, 1: iterate); operands: the bytes the pass moves per incidence,
+// per own pose and per neighbour row, counted by the caller operand by operand
+static void inter(const LaunchCtx &lc, const InterEdgesDev &E, int loss, double loss_reg, int mode, bool quad, const double *Z,
+                  const double *Zprev, const double *Qdiag, const double *Ddiag, double *DfE, double *g, double *partials,
+                  double *wout, const InterLin &lin, const double *Znbr, const InterFuse &F, double inc_b, double own_b,
+                  double nbr_b) {
+  const auto &[d, st, T, mask] = lc;
+  const double operands = (double)E.m * (mode == 0 ? 2 : 1) * inc_b + (double)E.nrows_own * own_b +
                           (mode == 0 ? (double)(E.nrows_all - E.nrows_own) * nbr_b : 0.0);
   ProfScope ps(PK_INTER, st, (double)E.m * (8.0 * (d * d + d + 2) + 8) + 2.0 * (mode == 0 ? E.nrows_all : E.nrows_own) * 8.0 * (d + 1) * d, 1, operands);
+  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_inter<D>), dim3(mode == 0 ? T.nseg_all : T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, E,
+                                        loss, loss_reg, mode, quad ? 1 : 0, T.nseg_own, Z, Zprev, Qdiag, Ddiag, DfE, g, partials,
+                                        T.nseg_all, wout, lin, Znbr, F));
+}
+// operand by operand: per incidence its 128-byte record and the other endpoint's pose; per own pose its record, the previous
+// iterate (majorisation gap), the previous DfobjE read and the new one written, the Q and D blocks, g written, the
+// incidence pointer, and (iterate()) the two kept products G X read and Df written; per neighbour row the same without
+// D and g but with the halo copy it performs on the way
+void launch_inter_update(const LaunchCtx &lc, const InterEdgesDev &E, int loss, double loss_reg, const InterUpdate &a) {
+  const auto &[d, st, T, mask] = lc;
+  if (T.nseg_all == 0) return;
+  InterFuse F;
+  F.GX = a.GX; F.X = a.X; F.Df = a.Df; F.gn_slot = a.gn_slot;
+  const double P = 8.0 * (d + 1) * d, B = 8.0 * (d + 1) * (d + 1);
+  const double own_b = P + (a.Zprev ? P : 0) + (a.DfE ? 2 * P : 0) + (a.Qdiag ? B : 0) + (a.Ddiag ? B : 0) + (a.g ? P : 0) + 8 +
+                       (a.Df ? 3 * P : 0);   // the product G X and the own record read, Dfobj written
+  const double nbr_b = P + (a.Zprev ? P : 0) + (a.DfE ? 2 * P : 0) + (a.Qdiag ? B : 0) + 8 + (a.Znbr ? 2 * P : 0);
+  InterLin lin;   // (not used by this mode)
+  inter(lc, E, loss, loss_reg, 0, a.quad, a.Z, a.Zprev, a.Qdiag, a.Ddiag, a.DfE, a.g, a.partials, a.wout, lin, a.Znbr, F, 128.0 + P,
+        own_b, nbr_b);
+}
+void launch_inter_iterate(const LaunchCtx &lc, const InterEdgesDev &E, int loss, double loss_reg, const InterIterate &a) {
+  const auto &[d, st, T, mask] = lc;
+  if (T.nseg_own == 0) return;
+  const bool kept = a.GXc && a.GXp && a.gamma;   // Df is formed from the kept products
+  InterFuse F;
+  F.Zc = a.Zc; F.Zp = a.Zp; F.Yout = a.Yout;
+  if (a.Xout && a.Df_out == nullptr && kept) {   // (the proximal step needs the Df this pass forms)
+    F.Xout = a.Xout; F.Xref = a.Xref; F.Tinv = a.Tinv; F.Nv = a.Nv; F.Vb = a.Vb; F.gn_slot = a.gn_slot;
+  }
   InterLin lin;
-  if (mode == 1 && (Df_out || F.Xout) && GXc && GXp && gamma) { lin.GXc = GXc; lin.GXp = GXp; lin.out = Df_out; lin.gamma = *gamma; lin.gamma_dev = gamma_dev; }
-  else if (mode == 1 && F.Zc && gamma) { lin.gamma = *gamma; lin.gamma_dev = gamma_dev; }   // (the extrapolation's gamma alone)
-  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_inter<D>), dim3(nb), dim3(SEG_ROWS), 0, st, T.segs, mask, E, loss, loss_reg,
-                                        mode, quad ? 1 : 0, T.nseg_own, Z, Zprev, Qdiag, Ddiag, DfE, g, partials,
-                                        T.nseg_all, mode == 0 ? wout : nullptr, lin, mode == 0 ? Znbr : nullptr, F));
+  if ((a.Df_out || F.Xout) && kept) { lin.GXc = a.GXc; lin.GXp = a.GXp; lin.out = a.Df_out; lin.gamma = *a.gamma; lin.gamma_dev = a.gamma_dev; }
+  else if (F.Zc && a.gamma) { lin.gamma = *a.gamma; lin.gamma_dev = a.gamma_dev; }   // (the extrapolation's gamma alone)
+  const double P = 8.0 * (d + 1) * d, B = 8.0 * (d + 1) * (d + 1);
+  const double own_b = P + (a.Ddiag ? B : 0) + (a.g ? P : 0) + 8 + ((a.Df_out && a.GXc && a.GXp) ? 3 * P : 0) +
+                       (a.Zc ? 2 * P : 0);   // X[k-1] read, the extrapolated record written
+  // Xakh written, Xak read and its rotations written, the coefficients T / N / V; Df no longer written
+  const double prox_b = a.Xout ? (2 * P + 8.0 * (1 + d + d * d) + 8.0 * d * d - P) : 0.0;
+  inter(lc, E, loss, loss_reg, 1, false, a.Z, nullptr, nullptr, a.Ddiag, nullptr, a.g, a.partials, nullptr, lin, nullptr, F,
+        128.0 + (a.Zc ? 2 * P : P), own_b + prox_b, 0.0);
 }
 
 void launch_rescale_decide(hipStream_t st, int nnodes, NodeBits nodes, const int *e_off, const double *w, double *scale,
@@ -2583,9 +2617,9 @@ void launch_rescale_apply(int d, hipStream_t st, const SegTable &T, const InterE
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_rescale_apply<D>), dim3(T.nseg_all), dim3(SEG_ROWS), 0, st, T.segs, E, R, T.nseg_own));
 }
 
-void launch_cost(int d, hipStream_t st, const SegTable &T, NodeMask mask, const InterEdgesDev &Ei,
-                 const InterEdgesDev &Ee, bool eform, int loss, double loss_reg, const double *Z, double *partials,
-                 int slot0) {
+void launch_cost(const LaunchCtx &lc, const InterEdgesDev &Ei, const InterEdgesDev &Ee, bool eform, int loss, double loss_reg,
+                 const double *Z, double *partials, int slot0) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_all == 0) return;
   ProfScope ps(PK_INTER, st, (double)(Ei.m + Ee.m) * (8.0 * (d * d + d + 2) + 8) + 1.0 * T.rows_all * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_cost<D>), dim3(T.nseg_all), dim3(SEG_ROWS), 0, st, T.segs, mask, Ei, Ee,
@@ -2593,17 +2627,17 @@ void launch_cost(int d, hipStream_t st, const SegTable &T, NodeMask mask, const 
                                         T.nseg_all));
 }
 
-void launch_sqdist(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *a, const double *b,
-                   double *partials, int slot) {
+void launch_sqdist(const LaunchCtx &lc, const double *a, const double *b, double *partials, int slot) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_DOT, st, 2.0 * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_sqdist<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, a, b,
                                         partials + (size_t)slot * T.nseg_all));
 }
 
-void launch_proximal(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Z, const double *Df,
-                     const double *Tinv, const double *N, const double *V, double *Xout, double *Xref,
-                     double *partials, int slot) {
+void launch_proximal(const LaunchCtx &lc, const double *Z, const double *Df, const double *Tinv, const double *N,
+                     const double *V, double *Xout, double *Xref, double *partials, int slot) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   double *part = (Xref && partials) ? partials + (size_t)slot * T.nseg_all : nullptr;
   // operand by operand: Z, Df and Xout records, the coefficients T (1), N (d), V (d x d) and, with Xref, its record read and
@@ -2614,8 +2648,9 @@ void launch_proximal(int d, hipStream_t st, const SegTable &T, NodeMask mask, co
                                         Tinv, N, V, Xout, part ? Xref : nullptr, part));
 }
 
-void launch_extrapolate(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask,
-                        const NodeCoefs &gamma, const double *a, const double *b, double *out, const double *gamma_dev) {
+void launch_extrapolate(const LaunchCtx &lc, bool all_rows, const NodeCoefs &gamma, const double *a, const double *b, double *out,
+                        const double *gamma_dev) {
+  const auto &[d, st, T, mask] = lc;
   const int nb = nseg(T, all_rows);
   if (nb == 0) return;
   ProfScope ps(PK_AXPBY, st, 3.0 * (all_rows ? T.rows_all : T.rows_own) * 8.0 * (d + 1) * d);
@@ -2623,9 +2658,10 @@ void launch_extrapolate(int d, hipStream_t st, const SegTable &T, bool all_rows,
                                         a, b, out));
 }
 
-void launch_extrapolate3(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &gamma, const double *gamma_dev,
+void launch_extrapolate3(const LaunchCtx &lc, const NodeCoefs &gamma, const double *gamma_dev,
                          const double *za, const double *zb, double *zout, const double *ga, const double *gb, double *gout,
                          const double *da, const double *db, double *dout) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_all == 0) return;
   Extrap3 E;
   E.a[0] = za; E.b[0] = zb; E.out[0] = zout;
@@ -2636,8 +2672,9 @@ void launch_extrapolate3(int d, hipStream_t st, const SegTable &T, NodeMask mask
                                         gamma_dev, T.nseg_own, E));
 }
 
-void launch_axpby(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeMask mask, double alpha,
+void launch_axpby(const LaunchCtx &lc, bool all_rows, double alpha,
                   const double *a, double beta, const double *b, double *out, int part, double *out2) {
+  const auto &[d, st, T, mask] = lc;
   const int nb = nseg(T, all_rows);
   if (nb == 0) return;
   ProfScope ps(PK_AXPBY, st, (b ? 3.0 : 2.0) * (all_rows ? T.rows_all : T.rows_own) * 8.0 * (d + 1) * d);
@@ -2648,8 +2685,9 @@ void launch_axpby(int d, hipStream_t st, const SegTable &T, bool all_rows, NodeM
   });
 }
 
-void launch_tail_pack(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *xak, double *xk, double *z,
+void launch_tail_pack(const LaunchCtx &lc, const double *xak, double *xk, double *z,
                       const int *pack_rows, int npack, double *pack) {
+  const auto &[d, st, T, mask] = lc;
   const int nb = T.nseg_own + (npack + SEG_ROWS - 1) / SEG_ROWS;
   if (nb == 0) return;
   ProfScope ps(PK_AXPBY, st, (2.0 * T.rows_own + 2.0 * npack) * 8.0 * (d + 1) * d);
@@ -2657,30 +2695,31 @@ void launch_tail_pack(int d, hipStream_t st, const SegTable &T, NodeMask mask, c
                                         pack_rows, npack, pack));
 }
 
-void launch_axpby_node(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &C, const double *a,
-                       const double *b, double *out) {
+void launch_axpby_node(const LaunchCtx &lc, const NodeCoefs &C, const double *a, const double *b, double *out) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_AXPBY, st, 3.0 * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_axpby_node<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, C, a, b,
                                         out));
 }
 
-void launch_rot_rowscale(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *dinv, const double *in, double *out) {
+void launch_rot_rowscale(const LaunchCtx &lc, const double *dinv, const double *in, double *out) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_AXPBY, st, 2.0 * T.rows_own * 8.0 * d * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_rot_rowscale<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, dinv, in, out));
 }
 
-void launch_cg_step(int d, hipStream_t st, const SegTable &T, NodeMask mask, const NodeCoefs &C, const double *p,
-                    const double *Hp, double *s, double *hs, double *r, const CgNode *cg, const double *r0, const double *X,
-                    double *xprop, const NodeBits *rmask) {
+void launch_cg_step(const LaunchCtx &lc, const CgStepArgs &a) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
-  ProfScope ps(PK_AXPBY, st, ((r0 ? 6.0 : 8.0) + (xprop ? 2.0 : 0.0)) * T.rows_own * 8.0 * (d + 1) * d);
-  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_cg_step<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask, C, p, Hp, s, hs,
-                                        r, cg, r0, X, xprop, rmask));
+  ProfScope ps(PK_AXPBY, st, ((a.r0 ? 6.0 : 8.0) + (a.xprop ? 2.0 : 0.0)) * T.rows_own * 8.0 * (d + 1) * d);
+  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_cg_step<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask,
+                                        a.C ? *a.C : NodeCoefs(), a.p, a.Hp, a.s, a.hs, a.r, a.cg, a.r0, a.X, a.xprop, a.rmask));
 }
 
-void launch_cg_dir(int d, hipStream_t st, const SegTable &T, NodeMask mask, const CgNode *cg, const double *v, double *p) {
+void launch_cg_dir(const LaunchCtx &lc, const CgNode *cg, const double *v, double *p) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_AXPBY, st, 3.0 * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_cg_dir<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask, cg, v, p));
@@ -2690,29 +2729,26 @@ void launch_cg_begin(hipStream_t st, int nnodes, NodeBits bits, const CgStart &S
   hipLaunchKernelGGL(k_cg_begin, dim3(1), dim3(64), 0, st, nnodes, bits, S, max_it, cg, dmask);
 }
 
-void launch_tnt_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
-                      double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                      NodeBits *dmask, double *host_tnt) {
+static TntBegin tnt_begin_arg(const TntStart &S) {
   TntBegin B;
-  B.bits = bits; B.use_precon = use_precon; B.max_it = max_it;
-  B.grad_tol = grad_tol; B.pgrad_tol = pgrad_tol; B.kappa = kappa; B.theta = theta;
-  for (int a = 0; a < MAX_LOCAL_NODES; a++) B.Delta[a] = a < nnodes ? Delta[a] : 0.0;
+  B.bits = S.bits; B.use_precon = S.use_precon; B.max_it = S.max_it;
+  B.grad_tol = S.grad_tol; B.pgrad_tol = S.pgrad_tol; B.kappa = S.kappa; B.theta = S.theta;
+  for (int a = 0; a < MAX_LOCAL_NODES; a++) B.Delta[a] = a < S.nnodes ? S.Delta[a] : 0.0;
+  return B;
+}
+void launch_tnt_begin(hipStream_t st, const SegTable &T, const TntStart &S) {
+  const TntBegin B = tnt_begin_arg(S);
   ProfScope ps(PK_REDUCE, st, 8.0 * 6 * T.nseg_own);
-  hipLaunchKernelGGL(k_tnt_begin, dim3(nnodes), dim3(384), 0, st, T, nnodes, B, partials, cg, dmask, host_tnt);
+  hipLaunchKernelGGL(k_tnt_begin, dim3(S.nnodes), dim3(384), 0, st, T, S.nnodes, B, S.partials, S.cg, S.dmask, S.host_tnt);
 }
 
-void launch_cg_scal_begin(hipStream_t st, const SegTable &T, int nnodes, NodeBits bits, bool use_precon, int max_it, double grad_tol,
-                           double pgrad_tol, double kappa, double theta, const double *Delta, const double *partials, CgNode *cg,
-                           NodeBits *dmask, double *host_tnt, double *host_scalars, ReadbackFlag flag, double *dev_tnt, int upd_nslots,
-                           double *upd_host) {
-  TntBegin B;
-  B.bits = bits; B.use_precon = use_precon; B.max_it = max_it;
-  B.grad_tol = grad_tol; B.pgrad_tol = pgrad_tol; B.kappa = kappa; B.theta = theta;
-  for (int a = 0; a < MAX_LOCAL_NODES; a++) B.Delta[a] = a < nnodes ? Delta[a] : 0.0;
+void launch_cg_scal_begin(hipStream_t st, const SegTable &T, const TntStart &S, double *host_scalars, ReadbackFlag flag, double *dev_tnt,
+                          int upd_nslots, double *upd_host) {
+  const TntBegin B = tnt_begin_arg(S);
   if (upd_nslots > 6) { fprintf(stderr, "[dpgo_amd] ERROR: k_cg_scal_begin carries at most six sums of an update.\n"); return; }
   ProfScope ps(PK_REDUCE, st, 8.0 * (10 * T.nseg_own + upd_nslots * T.nseg_all));
-  hipLaunchKernelGGL(k_cg_scal_begin, dim3(nnodes), dim3(upd_nslots > 0 ? 1024 : 640), 0, st, T, B, partials, cg, dmask, host_tnt, host_scalars,
-                     flag.arrived, flag.host, flag.seq, flag.dev_seq, dev_tnt, upd_nslots, upd_host);
+  hipLaunchKernelGGL(k_cg_scal_begin, dim3(S.nnodes), dim3(upd_nslots > 0 ? 1024 : 640), 0, st, T, B, S.partials, S.cg, S.dmask, S.host_tnt,
+                     host_scalars, flag.arrived, flag.host, flag.seq, flag.dev_seq, dev_tnt, upd_nslots, upd_host);
 }
 int cg_first_slot() { return CG_FIRST_SLOT; }
 
@@ -2723,8 +2759,9 @@ void launch_cg_scal(hipStream_t st, const SegTable &T, int nnodes, int phase, co
                      flag.host, flag.seq, flag.dev_seq);
 }
 
-void launch_dots(int d, hipStream_t st, const SegTable &T, NodeMask mask, int n, const double *const *a,
+void launch_dots(const LaunchCtx &lc, int n, const double *const *a,
                  const double *const *b, const int *parts, double *partials, int slot0) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0 || n <= 0) return;
   DotPairs P;
   P.n = n;
@@ -2738,16 +2775,18 @@ void launch_dots(int d, hipStream_t st, const SegTable &T, NodeMask mask, int n,
                                         partials + (size_t)slot0 * T.nseg_all, T.nseg_all));
 }
 
-void launch_cg_init(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *grad, const double *pgrad,
+void launch_cg_init(const LaunchCtx &lc, const double *grad, const double *pgrad,
                     double *s, double *hs, double *r, double *v, double *p) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_AXPBY, st, (s ? 7.0 : 2.0) * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_cg_init<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, grad,
                                         pgrad, s, hs, r, v, p));
 }
 
-void launch_tangent_full(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
+void launch_tangent_full(const LaunchCtx &lc, const double *X,
                          const double *V, double *out, double *partials, int slot, const double *add, double *sum_out) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   double *part = partials ? partials + (size_t)slot * T.nseg_all : nullptr;
   ProfScope ps(PK_ROTOP, st, (add ? 4.0 : 2.0) * T.rows_own * 8.0 * (d + 1) * d);
@@ -2755,7 +2794,8 @@ void launch_tangent_full(int d, hipStream_t st, const SegTable &T, NodeMask mask
                                         V, add, sum_out, out, part));
 }
 
-void launch_copy_nbr_rows(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *src, double *dst) {
+void launch_copy_nbr_rows(const LaunchCtx &lc, const double *src, double *dst) {
+  const auto &[d, st, T, mask] = lc;
   const int nb = T.nseg_all - T.nseg_own;
   if (nb <= 0) return;
   ProfScope ps(PK_AXPBY, st, 2.0 * (T.rows_all - T.rows_own) * 8.0 * (d + 1) * d);
@@ -2763,17 +2803,17 @@ void launch_copy_nbr_rows(int d, hipStream_t st, const SegTable &T, NodeMask mas
                                         0.0, nullptr, dst, nullptr));
 }
 
-void launch_tangent_rot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
-                        const double *in, double *out, const double *dotv, double *partials, int slot, bool two, double *neg) {
+void launch_tangent_rot(const LaunchCtx &lc, const TangentRotArgs &a) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
-  ProfScope ps(PK_ROTOP, st, (dotv ? 4.0 : 3.0) * T.rows_own * 8.0 * (d + 1) * d);
-  double *part = (dotv && partials) ? partials + (size_t)slot * T.nseg_all : nullptr;
-  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_rot_op<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask, 0, X, in,
-                                        dotv, part, out, T.nseg_all, two ? 1 : 0, neg));
+  ProfScope ps(PK_ROTOP, st, (a.dotv ? 4.0 : 3.0) * T.rows_own * 8.0 * (d + 1) * d);
+  double *part = (a.dotv && a.partials) ? a.partials + (size_t)a.slot * T.nseg_all : nullptr;
+  DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_rot_op<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask, 0,
+                                        a.X, a.in, a.dotv, part, a.out, T.nseg_all, a.two ? 1 : 0, a.neg));
 }
 
-void launch_retract_rot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *X,
-                        const double *V, double *out) {
+void launch_retract_rot(const LaunchCtx &lc, const double *X, const double *V, double *out) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_ROTOP, st, 3.0 * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_rot_op<D>), dim3(own_grid(T, mask)), dim3(SEG_ROWS), 0, st, T.segs, mask, 2, X, V,
@@ -2788,8 +2828,9 @@ void launch_copy_indexed(int d, hipStream_t st, int count, const int *didx, cons
                                         didx, sidx, src, dst, gate));
 }
 
-void launch_bdiag_dot(int d, hipStream_t st, const SegTable &T, NodeMask mask, const double *Dd, const double *x,
+void launch_bdiag_dot(const LaunchCtx &lc, const double *Dd, const double *x,
                       double coef, const double *add, double addcoef, double *partials, int slot) {
+  const auto &[d, st, T, mask] = lc;
   if (T.nseg_own == 0) return;
   ProfScope ps(PK_BDIAG, st, 3.0 * T.rows_own * 8.0 * (d + 1) * d);
   DPGO_DISPATCH_D(d, hipLaunchKernelGGL((k_bdiag_dot<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, Dd, x,

@@ -68,19 +68,22 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
   const double *ga = g_alt ? g_alt : g;
   auto quad_model = [&](const double *Y, bool from_base) {
     if (from_base) {
-      apply_tcol(Y, T1_.p, nabla, 1, Y, nullptr, nullptr, grad, nullptr, partials_.p, g, ga);   // nabla, grad and the sums in one pass
+      // nabla, grad and the sums in one pass
+      launch_bsr_tcol_begin(lc(), g_tcol(),
+                            {.xt = Y, .base = T1_.p, .y = nabla, .X = Y, .grad = grad, .partials = partials_.p, .g = g, .ga = ga});
       return true;
     }
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, Y, false, g, nabla, nullptr, 0, nullptr, nullptr, 0);
-    launch_tangent_rot(d_, st_, T_, cur_mask_, Y, nabla, grad);
+    launch_bsr(lc(), G_.dev, {.x = Y, .addv = g, .y = nabla});
+    launch_tangent_rot(lc(), {.X = Y, .in = nabla, .out = grad});
     return false;
   };
   // out = P(v) = Proj_Y(M^-1 v) with |out|^2 and <v, out> in the partial slots MAX_DOTS, MAX_DOTS + 1, and -out in pk
   // (the first CG direction); only called with a preconditioner
   auto precon_with_sums = [&](const double *Y, const double *v, double *out) {
-    if (jacobi) launch_rot_rowscale(d_, st_, T_, cur_mask_, jacobi_.p, v, w1);
+    if (jacobi) launch_rot_rowscale(lc(), jacobi_.p, v, w1);
     else solve_rr(const_cast<double *>(v), w1, 1.0);   // w1.R = (G_RR + lambda I)^-1 v.R; the forward sweep only reads v
-    launch_tangent_rot(d_, st_, T_, cur_mask_, Y, w1, out, v, partials_.p, MAX_DOTS, true, pk);
+    launch_tangent_rot(lc(), {.X = Y, .in = w1, .out = out, .dotv = v, .partials = partials_.p, .slot = MAX_DOTS, .two = true,
+                              .neg = pk});
   };
   // gnorm, pgnorm (and rv0 = <grad, P grad>, the first CG scalar) of the nodes in `set` (mask == set).
   // with_f: f(X | g) in the same read-back, from the model gradient nabla = G X + g that is there anyway:
@@ -94,10 +97,10 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     if (!have_sums) {
       const double *pa[MAX_DOTS] = {grad, X, X, X}, *pb[MAX_DOTS] = {grad, nabla, g, ga};
       const int parts[MAX_DOTS] = {2, 0, 0, 0, 0, 0};
-      launch_dots(d_, st_, T_, cur_mask_, with_f ? 4 : 1, pa, pb, parts, partials_.p, 0);
+      launch_dots(lc(), with_f ? 4 : 1, pa, pb, parts, partials_.p, 0);
     }
     if (use_precon) precon_with_sums(X, grad, pg);
-    else launch_cg_init(d_, st_, T_, cur_mask_, grad, grad, nullptr, nullptr, nullptr, nullptr, pk);
+    else launch_cg_init(lc(), grad, grad, nullptr, nullptr, nullptr, nullptr, pk);
   };
   auto norms_take = [&](int a, bool with_f, double g2, double xn, double xg, double xga, double pg2, double gpg) {
     S[a].gnorm = S[a].pgnorm = std::sqrt(g2);
@@ -132,11 +135,12 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
   // retracted: the rotations of x+ are there already (the CG step's vector update took them along, stepA)
   auto enqueue_trial = [&](NodeMask m, bool retracted, int nslots, bool with_reduce = true) {
     cur_mask_ = m;
-    if (!retracted) launch_retract_rot(d_, st_, T_, cur_mask_, X, sk, xprop);
+    if (!retracted) launch_retract_rot(lc(), X, sk, xprop);
     recover_translations(xprop, g);
     // nprop = G xprop + g: gives f(xprop) and, if accepted, the next model; its epilogue leaves the six sums
     // <s,s>, <grad,s>, <s,Hs>, <x+,g>, <x+,g_alt>, <x+,nprop> in the partial slots 0..5
-    apply_tcol(xprop, T1_.p, nprop, 0, nullptr, nullptr, nullptr, nullptr, nullptr, partials_.p, g, ga, sk, grad, hh);
+    launch_bsr_tcol(lc(), g_tcol(),
+                    {.xt = xprop, .base = T1_.p, .y = nprop, .partials = partials_.p, .g = g, .ga = ga, .s = sk, .grad = grad, .hs = hh});
     // (with_reduce = false: the caller launches the reduction itself, with the gate of a speculative update: group.h)
     if (with_reduce) launch_reduce(st_, T_, L, false, nslots, partials_.p, h_scal_, sched_.flag());
   };
@@ -194,32 +198,35 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
   // the product then runs for every candidate, and leaves its sums where the refinement's are not
   auto stepA = [&](bool first, bool retract = false, const std::function<void(const double *)> *begin = nullptr) {
     cur_mask_ = begin ? live_mask(bitsA, nullptr) : mA;
-    launch_bsr(d_, st_, T_, false, cur_mask_, G_.dev, pk, true, nullptr, w1, nullptr, 0, nullptr, nullptr, 0);   // G [0 ; p.R]
+    launch_bsr(lc(), G_.dev, {.x = pk, .mode = BsrMode::NoTrans, .y = w1});   // G [0 ; p.R]
     solve_tt(w1, w3, -1.0);
     double *sums = partials_.p + (begin ? (size_t)cg_first_slot() * T_.nseg_all : 0);
-    apply_tcol(w3, w1, nullptr, 2, X, nabla, pk, Hp, first ? grad : rk, sums);   // Hp and <p,Hp>, <Hp,Hp>, <p,p>, <p,r>
+    // Hp and <p,Hp>, <Hp,Hp>, <p,p>, <p,r>
+    launch_bsr_tcol_hess(lc(), g_tcol(),
+                         {.xt = w3, .base = w1, .X = X, .nabla = nabla, .p = pk, .Hp = Hp, .r = first ? grad : rk, .partials = sums});
     // the step-length logic
     if (begin) (*begin)(sums);
     else launch_cg_scal(st_, T_, L, 0, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
     // s += c1 p, H s += c1 H p for every node of the step (a node that stops here takes its boundary step), r += alpha H p
     // for those that go on
-    launch_cg_step(d_, st_, T_, first ? NodeMask{bitsA, nullptr} : mA, NodeCoefs(), pk, Hp, sk, hh, rk, cg_.p, first ? grad : nullptr,
-                   retract ? X : nullptr, retract ? xprop : nullptr, retract ? dmask_.p + 2 : nullptr);
+    CgStepArgs step = {.cg = cg_.p, .p = pk, .Hp = Hp, .s = sk, .hs = hh, .r = rk, .r0 = first ? grad : nullptr};
+    if (retract) { step.X = X; step.xprop = xprop; step.rmask = dmask_.p + 2; }
+    launch_cg_step(lc(first ? NodeMask{bitsA, nullptr} : mA), step);
   };
   // second half: preconditioner; beta and the recurrences, next stopping test (:364-390, :285-291)
   auto stepB = [&]() {
     cur_mask_ = mB;
     if (use_precon) {
-      if (jacobi) launch_rot_rowscale(d_, st_, T_, cur_mask_, jacobi_.p, rk, w1);
+      if (jacobi) launch_rot_rowscale(lc(), jacobi_.p, rk, w1);
       else solve_rr(rk, w1, 1.0);
-      launch_tangent_rot(d_, st_, T_, cur_mask_, X, w1, vk, rk, partials_.p, 0);   // v = Proj(M^-1 r) and <r, v>
+      launch_tangent_rot(lc(), {.X = X, .in = w1, .out = vk, .dotv = rk, .partials = partials_.p});   // v = Proj(M^-1 r) and <r, v>
     } else {
       copy_rows(vk, rk, false, 0);
       const double *pa[MAX_DOTS] = {rk}, *pb[MAX_DOTS] = {vk};
-      launch_dots(d_, st_, T_, cur_mask_, 1, pa, pb, P2, partials_.p, 0);
+      launch_dots(lc(), 1, pa, pb, P2, partials_.p, 0);
     }
     launch_cg_scal(st_, T_, L, 1, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
-    launch_cg_dir(d_, st_, T_, cur_mask_, cg_.p, vk, pk);
+    launch_cg_dir(lc(), cg_.p, vk, pk);
   };
   // what a segment's key must hold beside the rotating buffers (segment()): the vectors of this call and its variant
   // (X is looked up at the time of use: an accepted step swaps the iterate's buffers)
@@ -296,18 +303,18 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       norms_enqueue(true, have_sums);
       std::vector<double> Delta(L, 0.0);
       for (int a : nodes) Delta[a] = S[a].Delta;
+      const TntStart start = {.nnodes = L, .bits = bitsA, .use_precon = use_precon, .max_it = o.max_tCG_iterations,
+                              .grad_tol = o.grad_norm_tol, .pgrad_tol = o.preconditioned_grad_norm_tol, .kappa = o.STPCG_kappa,
+                              .theta = o.STPCG_theta, .Delta = Delta.data(), .partials = partials_.p, .cg = cg_.p, .dmask = dmask_.p,
+                              .host_tnt = h_tnt_};
       const std::function<void(const double *)> begin = [&](const double *) {
         // (update()'s reduction, if it is still waiting for somebody to take it along: group.h, UpdLazy)
         const int carry = (upd_lazy_.pending && !sched_.capturing()) ? upd_lazy_.nslots : 0;
-        launch_cg_scal_begin(st_, T_, L, bitsA, use_precon, o.max_tCG_iterations, o.grad_norm_tol, o.preconditioned_grad_norm_tol,
-                             o.STPCG_kappa, o.STPCG_theta, Delta.data(), partials_.p, cg_.p, dmask_.p, h_tnt_, h_cg_, sched_.flag(),
-                             dev_tnt_.p, carry, h_upd_);
+        launch_cg_scal_begin(st_, T_, start, h_cg_, sched_.flag(), dev_tnt_.p, carry, h_upd_);
         if (carry) { upd_lazy_.pending = false; pending_seq_ = sched_.last_seq(); }
       };
       merged = fused_;
-      if (!merged)
-        launch_tnt_begin(st_, T_, L, bitsA, use_precon, o.max_tCG_iterations, o.grad_norm_tol, o.preconditioned_grad_norm_tol,
-                         o.STPCG_kappa, o.STPCG_theta, Delta.data(), partials_.p, cg_.p, dmask_.p, h_tnt_);
+      if (!merged) launch_tnt_begin(st_, T_, start);
       mA = live_mask(bitsA, dmask_.p);
       mB = live_mask(bitsA, dmask_.p + 1);
       stepA(true, spec && fused_, merged ? &begin : nullptr);
@@ -357,7 +364,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
       bitsA = cur_mask_.v;
       // p_0 = -v_0, v_0 = P(grad): written by the pass that took the preconditioned gradient norm (norms_enqueue).
       // A later iteration of a node whose step was rejected starts from the same gradient: p_0 again (pk was overwritten)
-      if (!first_iteration) launch_cg_init(d_, st_, T_, cur_mask_, grad, use_precon ? pg : grad, nullptr, nullptr, nullptr, nullptr, pk);
+      if (!first_iteration) launch_cg_init(lc(), grad, use_precon ? pg : grad, nullptr, nullptr, nullptr, nullptr, pk);
       CgStart cs;
       for (int a = 0; a < L; a++) cs.rv[a] = cs.Delta[a] = cs.target[a] = 0.0;
       for (int a : A) {
@@ -450,7 +457,7 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
     if (!requad.empty()) {
       set_mask(requad);
       copy_rows(nabla, nprop, false, 0);   // the model gradient at the accepted point
-      launch_tangent_rot(d_, st_, T_, cur_mask_, X, nabla, grad);
+      launch_tangent_rot(lc(), {.X = X, .in = nabla, .out = grad});
       norms(requad, false, false);
     }
   }

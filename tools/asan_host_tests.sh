@@ -6,12 +6,13 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=/tmp/dpgo_asan
 mkdir -p $out
 cd $root/dpgo_amd/csrc
-for f in settings graph spd assemble chordal schedule group spd_solve tnt dchordal comm pcm capi; do
-  hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -fPIC -fopenmp -fsanitize=address -fno-omit-frame-pointer -Wno-option-ignored -c $f.cpp -o $out/$f.o
+rm -f $out/*.o
+for f in $(make -s print-SRCS); do   # the Makefile's lists: host sources with the sanitizer, device code without
+  hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -fPIC -fopenmp -fsanitize=address -fno-omit-frame-pointer -Wno-option-ignored -c $f -o $out/${f%.cpp}.o
 done
-hipcc --offload-arch=gfx950 -std=c++17 -O1 -fPIC -fopenmp -c kernels.hip -o $out/kernels.o
-hipcc --offload-arch=gfx950 -std=c++17 -O1 -fPIC -fopenmp -c spd_dev.hip -o $out/spd_dev.o
-hipcc --offload-arch=gfx950 -std=c++17 -O1 -fPIC -fopenmp -c pcm.hip -o $out/pcm_dev.o
+for f in $(make -s print-HIPSRCS); do
+  hipcc --offload-arch=gfx950 -std=c++17 -O1 -fPIC -fopenmp -c $f -o $out/${f%.hip}_hip.o
+done
 hipcc --offload-arch=gfx950 -shared -fopenmp -fsanitize=address -shared-libsan -o $out/libdpgo_amd.so $out/*.o -ldl
 rt=$(ldd $out/libdpgo_amd.so | awk '/asan/ {print $3}')
 cp $root/dpgo_amd/libdpgo_amd.so $out/keep.so
