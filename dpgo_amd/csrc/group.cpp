@@ -601,81 +601,6 @@ NodeMask Group::live_mask(NodeBits bits, const NodeBits *p) const {
   return m;
 }
 
-// group.h: SpecUpdate.  spec_update_possible: asked by run_tnt() before it enqueues the head of a refinement -- the trial
-// point's reduction then waits for speculate_update(), which is called once update(k-1)'s scalars are taken (the gate gets
-// them by value) and enqueues that reduction WITH the gate in one launch, then the continuation.
-bool Group::spec_update_possible(const double *xprop) const {
-  const int L = num_local();
-  if (!spec_update_armed_ || !spec_update_enabled_ || !fused_ || !keep_gx() || star_ || sched_.capturing() || sched_.iter_graph_wanted() ||
-      xchg_done_ || pending_recv_ || sched_.has_deferred() || pending_tail_.on || xprop != tmp_[7].p || L == 0)
-    return false;
-  for (int a = 0; a < L; a++)
-    if (res_[a].iters < 1 || !res_[a].updated) return false;   // (every node: a later update, never a node's first)
-  return true;
-}
-
-void Group::speculate_update(const double *xprop, int nslots_trial) {
-  spec_upd_ = SpecUpdate();
-  const int L = num_local();
-  AmmGate G;
-  G.nnodes = L; G.ds = 2 * MAX_DOTS; G.max_it = opt_.max_iterations; G.max_acc = opt_.max_iterations_accepted;
-  G.max_hits0 = opt_.max_soft_restart_hits[0]; G.max_hits1 = opt_.max_soft_restart_hits[1];
-  G.sqrt_eps = std::sqrt(std::numeric_limits<double>::epsilon()); G.eta1 = .05;   // TNT.h:83 (run_tnt's constants)
-  G.rel_tol = opt_.rel_func_decrease_tol; G.step_tol = opt_.stepsize_tol; G.psi = opt_.psi; G.phi = opt_.phi;
-  for (int a = 0; a < MAX_LOCAL_NODES; a++) {
-    const bool in = a < L;
-    G.f[a] = in ? res_[a].f : 0.0; G.Fk0[a] = in ? res_[a].Fk[0] : 0.0; G.Fk1[a] = in ? res_[a].Fk[1] : 0.0;
-    G.fobj[a] = in ? res_[a].fobj : 0.0;
-    G.hits0[a] = in ? res_[a].soft_restart_hits[0] : 0; G.hits1[a] = in ? res_[a].soft_restart_hits[1] : 0;
-  }
-  // the trial point's sums to the host (k_reduce's work, its flag) and the gate's verdict, one launch
-  launch_reduce_gate(st_, T_, L, nslots_trial, partials_.p, h_scal_, sched_.flag(), dev_sums_.p, G, dev_tnt_.p, cg_.p, go_.p, h_gate_);
-  spec_upd_.seq_trial = sched_.last_seq();
-  // the common course from here: the accepted point is the trial buffer; iterate()'s tail and the local halo copy; the history
-  // rotates (X[iter] <- what is X[iter-1] now, and so on); update()'s later-iteration sequence for the static robust surrogate
-  const double *nxak = xprop, *zp = Zc_.p;
-  double *zc = Zp_.p, *gc = gp_.p, *dfc = Dfp_.p, *gx = GXp_.p;
-  const NodeMask m{all_bits(), go_.p};
-  if (gather_dst_.n > 0) launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, nxak, Xk_.p, go_.p);
-  double *const pupd = partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all;   // (update()'s own slots: deferred_slots_ is 0 here, Dynamic is off)
-  launch_bsr(lc(m), G_.dev, {.x = nxak, .y = gx, .dot = {.v = nxak, .coef = 0.5, .partials = pupd, .slot = 5},
-                             .copy = {.to1 = Xk_.p, .to2 = zc}});
-  launch_inter_update(lc(m), E_, opt_.loss, opt_.loss_reg,
-                      {.quad = true, .Z = zc, .Zprev = zp, .Qdiag = Qd_.p, .Ddiag = Dd_.p, .DfE = DfE_.p, .g = gc, .partials = pupd,
-                       .Znbr = Xk_.p, .GX = gx, .X = nxak, .Df = dfc, .gn_slot = 4});
-  // (the closing reduction: left to the next refinement where update() itself would leave it, group.h: UpdLazy)
-  spec_upd_.lazy = lazy_update_reduce();
-  if (!spec_upd_.lazy) launch_reduce(st_, T_, L, true, 6, pupd, h_upd_, sched_.flag());
-  n_spec_enqueued_++;
-  spec_upd_.on = true; spec_upd_.seq_last = sched_.last_seq();
-  spec_upd_.xak = nxak; spec_upd_.zc = zc; spec_upd_.gc = gc; spec_upd_.dfc = dfc; spec_upd_.gx = gx;
-}
-
-// The host has taken its decision: the enqueued continuation stands (the common course) or is forgotten (its launches fell
-// through); either way the gate's verdict, which arrives behind the trial point's flag, is compared at the next wait that
-// covers it.
-void Group::check_gate(bool host_common) {
-  if (!spec_upd_.on) return;
-  spec_verdict_pending_ = true;
-  spec_verdict_expected_ = host_common;
-  spec_verdict_seq_ = spec_upd_.seq_trial;   // (the verdict is written in front of that flag)
-  if (!host_common) spec_upd_ = SpecUpdate();
-  else n_spec_stood_++;
-}
-
-// update()'s closing reduction left for the next refinement's k_cg_scal_begin (group.h: UpdLazy): eager launches of the fused
-// sequence only (a replayed segment is a fixed list of launches)
-bool Group::lazy_update_reduce() const {
-  return settings().lazy_update_reduce && fused_ && keep_gx() && !star_ && !sched_.capturing() && !sched_.iter_graph_wanted();
-}
-
-void Group::flush_pending_tail() {
-  if (!pending_tail_.on) return;
-  const PendingTail p = pending_tail_;
-  pending_tail_.on = false;
-  launch_axpby(lc(p.m), false, 1.0, p.xak, 0.0, nullptr, p.xk, 0, p.z);
-}
-
 // The segments of an iteration (group.h): the key of a replay is built here, the schedule runs it
 void Group::segment(int id, NodeBits bits, std::initializer_list<unsigned long long> extra, const std::function<void()> &body,
                     int wanted) {
@@ -697,34 +622,14 @@ void Group::segment(int id, NodeBits bits, std::initializer_list<unsigned long l
 }
 
 unsigned long long Group::fetch_async(int nslots, bool all_rows) {
-  finish_update();
+  finish_update();   // (its scalars sit in the pinned slots the next reduction overwrites)
   nslots = std::max(nslots, deferred_slots_);
   deferred_slots_ = 0;
   launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, sched_.flag());
   return sched_.last_seq();   // (under capture: the schedule adds the replay's flags itself, Schedule::segment())
 }
 
-// The deferred end of update(): wait for its reduction, then the scalar logic that needs the numbers.
-void Group::finish_update() {
-  if (!pending_update_) return;
-  if (upd_lazy_.pending) {   // (nobody has taken update()'s reduction along: launch it now)
-    upd_lazy_.pending = false;
-    launch_reduce(st_, T_, num_local(), true, upd_lazy_.nslots, partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all, h_upd_, sched_.flag());
-    pending_seq_ = sched_.last_seq();
-  }
-  std::function<void()> f;
-  f.swap(pending_update_);
-  wait_flag(pending_seq_);
-  f();
-}
-
-void Group::fetch(int nslots, bool all_rows) {
-  finish_update();   // (its scalars sit in the pinned slots the next reduction overwrites)
-  nslots = std::max(nslots, deferred_slots_);
-  deferred_slots_ = 0;
-  launch_reduce(st_, T_, num_local(), all_rows, nslots, partials_.p, h_scal_, sched_.flag());
-  wait_flag(sched_.last_seq());
-}
+void Group::fetch(int nslots, bool all_rows) { wait_flag(fetch_async(nslots, all_rows)); }
 
 void Group::wait_flag(unsigned long long seq) {
   sched_.wait(seq);
@@ -1169,87 +1074,6 @@ int Group::set_collectives(double *send_dev, double *gathered_dev, AllGatherFn a
   return 0;
 }
 
-// ---------------------------------------------------------------------------
-// DPGOHash::update  (DPGOHash.cpp:84-228)
-// ---------------------------------------------------------------------------
-// The part of the scalar logic that does not need the numbers update() reads back: the Nesterov sequence s[iter],
-// s[iter+1] and gamma (DPGOHash.cpp:150-160, 206-216).  The next iterate() may start with it.
-void Group::host_update_pre(int a) {
-  NodeResults &r = res_[a];
-  const int it = r.iters;
-  r.pre_repeat = (r.hist_iter == it);
-  r.pre_done = true;
-  if (opt_.scheme == 1) {
-    if (it == 0) r.s0 = 1.0;
-    else if (!r.pre_repeat) r.s0 = r.s1;
-    r.s1 = 0.5 + 0.5 * std::sqrt(4.0 * r.s0 * r.s0 + 1.0);
-    r.gamma = (r.s0 - 1) / r.s1;
-  } else {
-    r.gamma = 0;
-  }
-}
-
-void Group::host_update_logic(int a, double fobj, double f, double gradFnorm) {
-  NodeResults &r = res_[a];
-  const Options &o = opt_;
-  const int it = r.iters;
-  // update() may run again at the same iteration (update -> receive() -> update): X[iter-1], fobj[iter-1] and
-  // s[iter] are those of the first call, everything else is re-done as the reference does (DPGOHash.cpp:99-225)
-  const bool pre = r.pre_done;   // the Nesterov sequence was already advanced by host_update_pre
-  const bool repeat = pre ? r.pre_repeat : (r.hist_iter == it);
-  r.pre_done = false;
-  r.hist_iter = it;
-  if (!repeat) r.fobj_prev = r.fobj;
-  r.fobj = fobj;
-  r.f = f;
-  r.gradFnorm = gradFnorm;
-  if (star_) {   // update_n (DPGOStar.cpp:339-385): no restart counters, Gk = Fk = fobj every iteration
-    r.Gk = fobj;
-    if (o.scheme == 1) {
-      if (!repeat) r.s0 = it == 0 ? 1.0 : r.s1;
-      r.s1 = 0.5 + 0.5 * std::sqrt(4.0 * r.s0 * r.s0 + 1.0);
-      r.gamma = (r.s0 - 1) / r.s1;
-    }
-    r.Fk[0] = r.Fk[1] = fobj;
-    r.updated = 1;
-    return;
-  }
-  if (it == 0) {
-    r.Fk[0] = r.Fk[1] = fobj;
-    r.Gk = fobj;
-  }
-  if (o.scheme == 1) {
-    if (it == 0) {
-      if (!pre) r.s0 = 1.0;
-      if (!repeat) r.oscillations.assign(1, 1);
-      else r.oscillations.push_back(1);   // the reference pushes again (DPGOHash.cpp:168-171)
-    } else if (!repeat && !pre) {
-      r.s0 = r.s1;
-    }
-    if (!pre) {
-      r.s1 = 0.5 + 0.5 * std::sqrt(4.0 * r.s0 * r.s0 + 1.0);
-      r.gamma = (r.s0 - 1) / r.s1;
-    }
-    if (fobj <= r.Fk[1]) r.soft_restart_hits[0] = r.soft_restart_hits[0] > 2 ? r.soft_restart_hits[0] - 2 : 0;
-    else r.soft_restart_hits[0]++;
-    if (it > 0) {
-      if (fobj <= r.fobj_prev) { r.soft_restart_hits[1] = 0; r.oscillations.push_back(1); }
-      else { r.soft_restart_hits[1]++; r.oscillations.push_back(0); }
-      r.num_oscillations += (r.oscillations[it] != r.oscillations[it - 1]);
-    }
-    if (it > o.oscillation_cnt_period) {
-      const int k = it - o.oscillation_cnt_period;
-      r.num_oscillations -= (r.oscillations[k] != r.oscillations[k - 1]);
-    }
-    r.Fk[0] = r.Fk[0] * (1 - o.eta[0]) + fobj * o.eta[0];
-    r.Fk[1] = std::max(fobj, r.Fk[1] * (1 - o.eta[1]) + fobj * o.eta[1]);
-  } else {
-    r.Fk[0] = r.Fk[1] = fobj;
-    if (!pre) r.gamma = 0;
-  }
-  r.updated = 1;
-}
-
 // The rescale test of evaluate_g_and_f*_rescale (DPGOProblem.cpp:300-321, 464-485) for the nodes of `set`: a node
 // is rescaled when its counter has reached max_rescale_count or some edge weight exceeds the edge's scale; its new
 // scales are clamp(1.25 w, min_rescale_, max_rescale_) (DPGOProblem.h:17-18), update_quadratic_mat (:751-840) and
@@ -1360,282 +1184,6 @@ std::vector<int> Group::rescale_device(const std::vector<int> &set) {
   }
   clk.lap("rescale: block-diagonal terms, numeric factorisation of G_tt, panels (device)");
   return changed;
-}
-
-int Group::update(const std::vector<int> &locals_in) {
-  Schedule::InLib in_lib(sched_);
-  if (failed_) { flush_pending_tail(); sched_.flush_deferred(); pending_recv_ = nullptr; return -1; }
-  finish_update();
-  std::vector<int> locals;
-  for (int a : locals_in)
-    if (!res_[a].updated) locals.push_back(a);
-  if (locals.empty()) {
-    flush_pending_tail();
-    sched_.flush_deferred();
-    flush_pending_recv();
-    join_exchange();   // a pending exchange must still be ordered before whatever the caller does next on this stream
-    return 0;
-  }
-  const bool trivial = (opt_.loss == 0);
-  // update()'s partial sums have slots of their own (UPD_SLOT0 ..): they may wait there for the next refinement's
-  // k_cg_scal_begin to reduce them (`lazy` below) while that refinement's passes use the first slots.  Not with Dynamic
-  // rescale (its fetch() in the middle reads the first slots) nor when parked sums ride along (they are in the first slots)
-  double *const pupd = (dynamic() || deferred_slots_ != 0) ? partials_.p : partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all;
-  sched_.count_iteration();
-  set_mask(locals);
-  // history: X[iter-1] <- X[iter], X[iter] <- Xk ; same for g and Dfobj (masked nodes only).  A node whose
-  // history already stands at this iteration (update() ran, then receive() cleared `updated`) only refreshes
-  // X[iter]: the reference overwrites X[iter] / g[iter] in place and leaves X[iter-1] alone (DPGOHash.cpp:99-106).
-  std::vector<int> adv;
-  for (int a : locals)
-    if (res_[a].hist_iter != res_[a].iters) adv.push_back(a);
-  bool zc_done = false;
-  NodeBits mask_locals_bits = 0;
-  for (int a : locals) mask_locals_bits |= 1ull << a;
-  // (launches that wait for this update()'s first segment -- step() -- go now if something eager comes before it)
-  if ((int)adv.size() != num_local() || !zc_ready_ || xchg_done_ || dynamic() || star_) sched_.flush_deferred();
-  const double *lazy_recv = nullptr;   // (robust losses: the receive buffer the inter-edge pass unpacks on the way)
-  // the tail of iterate() rides on the product with G (group.h: PendingTail) where that product reads the very records the
-  // tail copies: every node advances, the copy's second target is the buffer that becomes X[iter] below
-  bool fuse_copy = false;
-  if (pending_tail_.on) {
-    fuse_copy = !trivial && (int)adv.size() == num_local() && zc_ready_ && !xchg_done_ && !star_ && pending_tail_.m.v == mask_locals_bits &&
-                pending_tail_.z == Zp_.p && pending_tail_.xk == Xk_.p && pending_tail_.xak == Xak_.p;
-    if (!fuse_copy) flush_pending_tail();
-  }
-  if ((int)adv.size() == num_local()) {
-    // every node advances: rotate the buffers instead of copying them
-    Zp_.swap(Zc_);
-    gp_.swap(gc_);
-    Dfp_.swap(Dfc_);
-    if (keep_gx()) GXp_.swap(GXc_);
-    zc_done = zc_ready_;   // iterate() already left Xk's own rows in what is X[iter] now
-  } else if (!adv.empty()) {
-    set_mask(adv);
-    copy_rows(Zp_.p, Zc_.p, true);
-    copy_rows(gp_.p, gc_.p, false);
-    copy_rows(Dfp_.p, Dfc_.p, false);
-    if (keep_gx()) copy_rows(GXp_.p, GXc_.p, false);
-    set_mask(locals);
-  }
-  // The new linearisation point needs the neighbours' poses, which may still be on their way (an exchange on the
-  // communicator's stream, comm.cpp).  What needs no neighbour row goes first -- X[iter] own rows and the product
-  // with G, a third of the surrogate build -- then the stream waits for the exchange and takes the neighbour rows.
-  std::vector<int> first, later;
-  for (int a : locals) ((res_[a].iters == 0 || star_) ? first : later).push_back(a);
-  // the closing read-back is deferred to the next reader (finish_update) where there is exactly one of them and nothing
-  // depends on it at once: not for AMM-PGO* (the master decides on the sums right away) nor with Dynamic rescale
-  const bool can_defer = settings().defer_update && !star_ && !dynamic() && (first.empty() != later.empty());
-  // `launches`: the rest of the surrogate build of the nodes in `set`, ending with the reduction of its sums -- a branch-free
-  // sequence, replayed from a captured graph where the host's launch rate would bound it (segment()); it may be empty when
-  // the caller has already enqueued everything but the reduction
-  auto end_with = [&](int seg_id, unsigned long long variant, int nslots, const std::vector<int> &set,
-                      const std::function<void()> &launches, std::function<void()> logic) {
-    nslots = std::max(nslots, deferred_slots_);
-    deferred_slots_ = 0;
-    NodeBits bits = 0;
-    for (int a : set) bits |= 1ull << a;
-    // the closing reduction is left to the next refinement's k_cg_scal_begin (group.h: UpdLazy) where the read-back is
-    // deferred anyway and the launches are eager: one launch less on the stream
-    // (only where the next iterate() starts its refinement unasked -- every node was refined in this one: otherwise the host
-    // wants these sums before it enqueues anything that could carry them)
-    bool lazy = can_defer && lazy_update_reduce() && spec_refined_ && pupd != partials_.p && nslots <= 6 && bits == all_bits();
-    // (launches that went out ahead decided for themselves: the policy may have changed since -- count_iteration() above)
-    if (spec_upd_.on) lazy = spec_upd_.lazy;
-    if (spec_upd_.on) {
-      // the launches of this sequence went out ahead of the host's decision (speculate_update) and the decision was the
-      // common one: what they were given must be what this call would have given them
-      const SpecUpdate sp = spec_upd_;
-      spec_upd_ = SpecUpdate();
-      const bool same = seg_id == 4 && fuse_copy && nslots == 6 && bits == all_bits() && !xchg_done_ && !lazy_recv && sp.seq_last == sched_.last_seq() && can_defer && pupd != partials_.p &&
-                        sp.xak == Xak_.p && sp.zc == Zc_.p && sp.gc == gc_.p && sp.dfc == Dfc_.p && sp.gx == GXc_.p && pending_tail_.on;
-      if (!same) {
-        failed_ = true;
-        fprintf(stderr, "[dpgo_amd] ERROR: a speculative update was enqueued for another state than update() found (segment %d, copy %d, slots %d, "
-                        "nodes %d, exchange %d, receive %d, flags %llu / %llu, deferred %d, own slots %d, tail %d, buffers %d %d %d %d %d)\n",
-                seg_id, (int)fuse_copy, nslots, (int)(bits == all_bits()), (int)(xchg_done_ != nullptr), (int)(lazy_recv != nullptr), sp.seq_last,
-                sched_.last_seq(), (int)can_defer, (int)(pupd != partials_.p), (int)pending_tail_.on, (int)(sp.xak == Xak_.p), (int)(sp.zc == Zc_.p),
-                (int)(sp.gc == gc_.p), (int)(sp.dfc == Dfc_.p), (int)(sp.gx == GXc_.p));
-        throw DeviceError("a speculative update was enqueued for another state than update() found");
-      }
-      pending_tail_.on = false;   // (it rode on the enqueued product with G)
-    } else
-    segment(seg_id, bits & mask_locals_bits, {bits, mask_locals_bits, variant, (unsigned long long)nslots, fuse_copy ? 1ull : 0ull, (unsigned long long)(uintptr_t)lazy_recv}, [&] {
-      launches();
-      if (!lazy) launch_reduce(st_, T_, num_local(), true, nslots, pupd, h_upd_, sched_.flag());
-    });
-    if (lazy) { upd_lazy_.pending = true; upd_lazy_.nslots = nslots; }
-    if (can_defer) {
-      pending_seq_ = lazy ? 0ull : sched_.last_seq();   // (lazy: whoever launches the reduction sets it -- run_tnt, or finish_update)
-      for (int a : set) {
-        host_update_pre(a);
-        res_[a].updated = 1;
-      }
-      pending_update_ = std::move(logic);
-    } else {
-      wait_flag(sched_.last_seq());
-      logic();
-    }
-  };
-  zc_ready_ = false;
-  if (!zc_done) copy_rows(Zc_.p, Xk_.p, false);
-  double *GX = (!trivial && keep_gx()) ? GXc_.p : T1_.p;
-  // the product with G: the part of the build that needs no neighbour row, ahead of the exchange's arrival.  Without a
-  // pending exchange it is simply the head of the segment below.
-  const bool split = xchg_done_ != nullptr;
-  auto product_with_G = [&] {
-    if (trivial)   // T1 = G Xak and <Xak, 1/2 G Xak>   (half of evaluate_G, DPGOProblem.cpp:180-205)
-      launch_bsr(lc(), G_.dev, {.x = Xak_.p, .y = T1_.p, .dot = {.v = Xak_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
-    else if (fuse_copy) {   // ... on Xak's records (the same numbers), which go to Xk and X[iter] on the way
-      const PendingTail pt = pending_tail_;
-      pending_tail_.on = false;
-      launch_bsr(lc(), G_.dev, {.x = pt.xak, .y = GX, .dot = {.v = pt.xak, .coef = 0.5, .partials = pupd, .slot = 5},
-                                .copy = {.to1 = pt.xk, .to2 = pt.z}});
-    } else         // T1 = G X and <X, 1/2 G X>  (kept as G X[k] where the next extrapolation reuses it)
-      launch_bsr(lc(), G_.dev, {.x = Zc_.p, .y = GX, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
-  };
-  const NodeMask mask_locals = cur_mask_;
-  if (split) {
-    product_with_G();
-    join_exchange();
-  }
-  auto head = [&] {   // (what a segment starts with when the product has not gone ahead)
-    if (!split) { cur_mask_ = mask_locals; product_with_G(); }
-  };
-  if (trivial) {
-    flush_pending_recv();
-    // X[iter]'s neighbour rows <- Xk's: a launch of its own for the trivial loss; the robust losses' inter-edge pass does it
-    // on the way (it reads the neighbour rows from Xk and stores them)
-    // g = S Z  (evaluate_none_g_and_f0 / _f, DPGOProblem.cpp:269-287, 516-542), with <Xak, g> alongside
-    auto common = [&] {
-      head();
-      cur_mask_ = mask_locals;
-      launch_copy_nbr_rows(lc(), Xk_.p, Zc_.p);
-      launch_bsr(lc(), S_.dev, {.x = Zc_.p, .y = gc_.p, .dot = {.v = Xak_.p, .coef = 1.0, .partials = pupd, .slot = 1}});
-    };
-    const bool both = !first.empty() && !later.empty();
-    if (both) sched_.flush_deferred();
-    if (both) common();   // (nodes at different iterations: two read-backs, nothing deferred, the shared part goes first)
-    if (!first.empty()) {
-      end_with(1, (split ? 1ull : 0ull) | (both ? 2ull : 0ull), 6, first, [&] {
-        if (!both) common();
-        set_mask(first);
-        launch_bsr(lc(), P0m_.dev, {.all_rows = true, .x = Zc_.p,
-                                    .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 0}});
-        // fobj = G(Xak | g, f0) = f0 + <Xak, g> + <Xak, 1/2 G Xak>: slots 1 and 5; Dfobj = g + G Xak
-        launch_tangent_full(lc(), Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
-      }, [this, first] {
-        for (int a : first) {
-          const double f0 = uscal(a, 0);
-          host_update_logic(a, f0 + (uscal(a, 1) + uscal(a, 5)), f0, std::sqrt(uscal(a, 2)));
-        }
-      });
-    }
-    if (!later.empty()) {
-      end_with(2, (split ? 1ull : 0ull) | (both ? 2ull : 0ull), 4, later, [&] {
-        if (!both) common();
-        set_mask(later);
-        launch_axpby(lc(), true, 1.0, Zc_.p, -1.0, Zp_.p, Tall_.p, 0);
-        launch_bsr(lc(), Q_.dev, {.all_rows = true, .x = Tall_.p,
-                                  .dot = {.v = Tall_.p, .coef = 0.5, .partials = pupd, .slot = 0}});
-        launch_bsr(lc(), P_.dev, {.all_rows = true, .x = Zc_.p, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 3}});
-        launch_tangent_full(lc(), Xak_.p, T1_.p, nullptr, pupd, 2, gc_.p, Dfc_.p);
-      }, [this, later] {
-        for (int a : later) {
-          const double fobj = res_[a].Gk + uscal(a, 0);
-          host_update_logic(a, fobj, fobj + uscal(a, 3), std::sqrt(uscal(a, 2)));
-        }
-      });
-    }
-  } else {
-    // evaluate_g_and_f0 / evaluate_g_and_f (DPGOProblem.cpp:222-267, 360-424); _rescale variants (:289-358, :426-514)
-    const bool both = !first.empty() && !later.empty();
-    // a lazy unpack is taken by the one inter-edge pass that covers every node of the group (it delivers all neighbour rows
-    // at once); anything else gets the plain copy first
-    if (pending_recv_) {
-      if (!both && !dynamic() && mask_locals_bits == all_bits()) { lazy_recv = pending_recv_; pending_recv_ = nullptr; }
-      else flush_pending_recv();
-    }
-    if (both || dynamic()) {   // (the product covers every node of `locals`: it cannot sit inside one of two segments)
-      sched_.flush_deferred();
-      head();
-    }
-    const bool head_inside = !(both || dynamic());
-    for (int pass = 0; pass < 2; pass++) {
-      const std::vector<int> &set = pass == 0 ? first : later;
-      if (set.empty()) continue;
-      std::vector<double> rho(num_local(), 0.0), gap(num_local(), 0.0);
-      // with_Df: Dfobj and |grad F|^2 on the way
-      auto inter_pass = [&](bool with_Df) {
-        InterEdgesDev E = E_;
-        if (lazy_recv) { E.recv = lazy_recv; E.nsrc = recv_nsrc_.p; }
-        InterUpdate up = {.quad = pass == 1, .Z = Zc_.p, .Zprev = Zp_.p, .Qdiag = Qd_.p, .Ddiag = Dd_.p, .DfE = DfE_.p, .g = gc_.p,
-                          .partials = pupd, .wout = dynamic() ? e_w_.p : nullptr, .Znbr = Xk_.p};
-        if (with_Df) { up.GX = GX; up.X = Xak_.p; up.Df = Dfc_.p; up.gn_slot = 4; }
-        launch_inter_update(lc(), E, opt_.loss, opt_.loss_reg, up);   // slots 0, 1 and 2 = <X, g>
-      };
-      if (dynamic()) {
-        set_mask(set);
-        inter_pass(false);
-        if (device_rescale_)   // the rescale test on the weights just computed; its verdict rides with the sums below
-          launch_rescale_decide(st_, num_local(), cur_mask_.v, e_off_dev_.p, e_w_.p, e_scale_.p, rs_count_.p, opt_.max_rescale_count,
-                                rs_flags_.p, h_rs_);
-        // Rescale::Dynamic: the sum of rho and the majorisation gap (under the OLD Q) are final; whether the
-        // surrogate is rescaled depends on the edge weights just computed (:300-321, :464-485).  Rescaled nodes get
-        // their D, G, T, N, V, Q and the factor of G_tt rebuilt, and g, G X are taken again with the new operators.
-        fetch(3, true);
-        for (int a : set) { rho[a] = scal(a, 0); gap[a] = scal(a, 1); }
-        const std::vector<int> changed = device_rescale_ ? rescale_device(set) : maybe_rescale(set);
-        if (!changed.empty()) {
-          set_mask(changed);
-          launch_bsr(lc(), G_.dev, {.x = Zc_.p, .y = GX, .dot = {.v = Zc_.p, .coef = 0.5, .partials = pupd, .slot = 5}});
-          // g = DfobjE_own - D X with the new D (slot 2 = <X, g> again)
-          launch_inter_iterate(lc(), E_, opt_.loss, opt_.loss_reg, {.Z = Zc_.p, .Ddiag = Dd_.p, .g = gc_.p, .partials = pupd});
-          set_mask(set);
-        }
-      }
-      // (a node's first update: there is no X[k-1] yet -- gamma is 0 there, but the buffer must hold numbers)
-      std::vector<int> fresh;
-      if (keep_gx())
-        for (int a : set)
-          if (res_[a].iters == 0) fresh.push_back(a);
-      const bool dyn = dynamic();
-      NodeBits fresh_bits = 0;
-      for (int a : fresh) fresh_bits |= 1ull << a;
-      end_with(3 + pass, (split ? 1ull : 0ull) | (head_inside ? 2ull : 0ull) | (dyn ? 4ull : 0ull) | (fused_ ? 8ull : 0ull) | (lazy_recv ? 16ull : 0ull) | (fresh_bits << 5), 6, set, [&] {
-        if (head_inside) head();
-        set_mask(set);
-        // Dfobj = G X + g, its tangent projection and norm: inside the inter-edge pass (kernels.h: InterUpdate::Df), or k_tangent_full
-        const bool in_pass = !dyn && fused_;
-        if (!dyn) inter_pass(in_pass);
-        if (pass == 0) launch_bdiag_dot(lc(), Dd_.p, Zc_.p, 0.5, DfE_.p, -1.0, pupd, 3);
-        if (!in_pass) launch_tangent_full(lc(), Xak_.p, GX, nullptr, pupd, 4, gc_.p, Dfc_.p);   // Dfobj = G X + g
-        if (!fresh.empty()) {
-          set_mask(fresh);
-          copy_rows(GXp_.p, GXc_.p, false);
-          set_mask(set);
-        }
-      }, [this, set, pass, dyn, rho, gap] {
-        for (int a : set) {
-          NodeResults &r = res_[a];
-          const double fobjE = 0.5 * (dyn ? rho[a] : uscal(a, 0));
-          const double quad = uscal(a, 2) + uscal(a, 5);   // tr(X^T (g + 1/2 G X))
-          double fobj, f;
-          if (pass == 0) {
-            f = 0.5 * fobjE + uscal(a, 3);
-            fobj = f + quad;
-          } else {
-            fobj = r.Gk - 0.5 * r.fobjE - 0.5 * (dyn ? gap[a] : uscal(a, 1)) + 0.5 * fobjE;
-            f = fobj - quad;
-          }
-          r.fobjE = fobjE;
-          host_update_logic(a, fobj, f, std::sqrt(uscal(a, 4)));
-        }
-      });
-    }
-  }
-  flush_pending_tail();   // (nothing, unless the product with G never came)
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1765,6 +1313,13 @@ bool Group::prepare_extrapolated(const double *gam_dev, int prox_slot) {
   return false;
 }
 
+// Gkh = G(Xakh | g[k]) needs G Xakh; the translations of Xak = [. ; Xakh.R] need G [0 ; Xakh.R] + g: one pass over
+// G gives both (T1_ = G [0 ; R] + gx, slot 2 MAX_DOTS + 1 = <Xakh, 1/2 G Xakh + gc>) for the masked nodes   (DPGOHash.cpp:363-372)
+void Group::half_step_product() {
+  launch_bsr(lc(), G_.dev, {.x = Xakh_.p, .mode = BsrMode::NoTransFullDot, .addv = gx_.p, .y = T1_.p,
+                            .dot = {.v = Xakh_.p, .coef = 0.5, .add = gc_.p, .partials = partials_.p, .slot = 2 * MAX_DOTS + 1}});
+}
+
 // DPGOHash::amm_pgo  (DPGOHash.cpp:230-444)
 int Group::amm(const std::vector<int> &locals) {
   const Options &o = opt_;
@@ -1786,10 +1341,8 @@ int Group::amm(const std::vector<int> &locals) {
     // (these three scalars sit in slots DS.. and are read back together with the first scalars of TNT)
     if (!prepare_extrapolated(gam_dev, DS))
       launch_proximal(lc(), Y_.p, Dfx_.p, Tinv_.p, N_.p, V_.p, Xakh_.p, Xak_.p, partials_.p, DS);
-    // Gkh = G(Xakh | g[k]) needs G Xakh; the translations of Xak = [. ; Xakh.R] need G [0 ; Xakh.R] + g: one pass over
-    // G gives both (T1_ = G [0 ; R] + gx, slot DS + 1 = <Xakh, 1/2 G Xakh + gc>), then the solve   (:363-372)
-    launch_bsr(lc(), G_.dev, {.x = Xakh_.p, .mode = BsrMode::NoTransFullDot, .addv = gx_.p, .y = T1_.p,
-                              .dot = {.v = Xakh_.p, .coef = 0.5, .add = gc_.p, .partials = partials_.p, .slot = DS + 1}});
+    // (T1_ is the right-hand side of the solve)   (:363-372)
+    half_step_product();
     solve_tt(T1_.p, Xak_.p, -1.0);
   };
   // (where the refinement starts unasked -- below -- and segments are replayed, the two sequences are ONE segment: the
@@ -1835,12 +1388,11 @@ int Group::amm(const std::vector<int> &locals) {
     } else {
       // A wrong guess.  What the abandoned head wrote is scratch -- except T1_, which the trial point's translation recovery
       // has overwritten and the refinement of the nodes that ARE refined starts from: the pass that made it runs again
-      // (same operands, same bits; its sum lands in the same slot), so that a guess, right or wrong, never changes a bit
+      // (half_step_product again: same operands, same bits; its sum lands in the same slot), so that a guess, right or wrong, never changes a bit
       // of the trajectory.
       deferred_slots_ = 0;
       cur_mask_ = mask_locals;
-      launch_bsr(lc(), G_.dev, {.x = Xakh_.p, .mode = BsrMode::NoTransFullDot, .addv = gx_.p, .y = T1_.p,
-                                .dot = {.v = Xakh_.p, .coef = 0.5, .add = gc_.p, .partials = partials_.p, .slot = DS + 1}});
+      half_step_product();
     }
   }
   std::vector<int> plain, ref;

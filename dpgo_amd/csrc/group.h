@@ -287,12 +287,34 @@ class Group {
   // the fusions of round 6 (extrapolation and Dfobj inside the inter-edge pass, iterate()'s tail on the product with G, the
   // first CG step's vector update with the retraction): DPGO_FUSED=0 gives round 5's launch sequence (A/B hook; same bits)
   bool fused_ = true;
+  // ---- update() and what it shares with iterate() and run_tnt() (update.cpp).  Its launches take the buffers by ROLE -- the
+  // own records' source, Xk, X[iter], X[iter-1], g, Dfobj, the kept product G X (T1_ where it is not kept), the base of its partial
+  // sums -- so that update() (the roles as they stand) and speculate_update() (as they will stand) share one statement of them
+  struct UpdateRoles {
+    const double *xak = nullptr, *zp = nullptr;
+    double *xk = nullptr, *zc = nullptr, *gc = nullptr, *dfc = nullptr, *gx = nullptr, *pupd = nullptr;
+    const char *differs(const UpdateRoles &o) const;   // the first role that differs, null: none
+    bool operator==(const UpdateRoles &o) const { return !differs(o); }
+  };
+  UpdateRoles roles_now() const;                           // from the members as they stand
+  UpdateRoles roles_accepted(const double *xprop) const;   // ... once the trial point xprop is accepted and the history has rotated
+  // What a sequence that closes an update() is enqueued with: the roles and the scalar facts that shape it
+  struct UpdateDesc {
+    UpdateRoles roles;
+    int seg_id = 0, nslots = 0;
+    NodeBits bits = 0;                  // the nodes of the sequence
+    bool fuse_copy = false, split = false, lazy_recv = false, deferred = false, tail = false;
+    unsigned long long seq_last = 0;    // the last sequence number given out when the sequence was complete
+    const char *differs(const UpdateDesc &o) const;
+  };
   // The tail of iterate() -- Xk <- Xak, and the buffer the next update() rotates into X[iter] -- waits for that update()'s
   // product with G, which reads the same records anyway and stores them on the way (k_bsr's copy1 / copy2): armed by step()
   // when no exchange stands between the two (the exchange's pack reads Xk); anything else launches it on its own.
   struct PendingTail { bool on = false; NodeMask m = ALL_NODES; const double *xak = nullptr; double *xk = nullptr, *z = nullptr; };
   PendingTail pending_tail_;
-  // ---- The next update() enqueued AHEAD of the host's decision (round 6).  Between the trial point's read-back and the first
+  bool tail_fusable_ = false;
+  void flush_pending_tail();
+  // The next update() enqueued AHEAD of the host's decision (round 6).  Between the trial point's read-back and the first
   // launch of update() the GPU used to idle for the host's acceptance test and bookkeeping (~13-17 us of an iteration of
   // 0.35-1.25 ms).  In the regime where that decision always comes out the same way -- every node refined, its CG over after
   // one step, the step accepted, no redo, no restart, no fallback: the whole early regime -- run_tnt() enqueues, right behind
@@ -305,18 +327,12 @@ class Group {
   // two verdicts come from the same bits through the same operations; the host checks that they agree when it next waits
   // (finish_update).  Armed by step() without an exchange; eager launches only; DPGO_SPEC_UPDATE=0 switches it off.
   struct SpecUpdate {
-    bool on = false, consumed_copy = false;
-    unsigned long long seq_trial = 0, seq_last = 0;  // the flags of the trial point's reduction (+ gate) and of the continuation's last flag-raising launch
-    bool lazy = false;                               // the continuation left update()'s reduction to the next refinement (UpdLazy)
-    const double *xak = nullptr; double *zc = nullptr, *gc = nullptr, *dfc = nullptr, *gx = nullptr;   // the roles it was enqueued with
+    bool on = false;
+    unsigned long long seq_trial = 0;  // the flag of the trial point's reduction (+ gate)
+    bool lazy = false;                 // the continuation left update()'s reduction to the next refinement (UpdLazy)
+    UpdateDesc what;                   // what the continuation was enqueued with (update() compares it with what it finds)
   };
   SpecUpdate spec_upd_;
-  // update()'s closing reduction is only read by the host, late (finish_update): where the read-back is deferred the
-  // reduction is not launched at all but rides on the next refinement's k_cg_scal_begin (one workgroup per node anyway),
-  // from partial-sum slots of its own; if no refinement comes, finish_update() launches it
-  struct UpdLazy { bool pending = false; int nslots = 0; };
-  UpdLazy upd_lazy_;
-  bool lazy_update_reduce() const;
   long n_spec_enqueued_ = 0, n_spec_stood_ = 0;   // (DPGO_HOST_TIMING=1 prints them)
   bool spec_update_armed_ = false, spec_update_enabled_ = true;
   bool tnt_common_ = false;          // run_tnt: the refinement took the common course (one step, accepted by every node, over)
@@ -328,8 +344,46 @@ class Group {
   bool spec_update_possible(const double *xprop) const;
   void speculate_update(const double *xprop, int nslots_trial);   // run_tnt: the trial point's reduction + gate, then the continuation
   void check_gate(bool host_common);
-  bool tail_fusable_ = false;
-  void flush_pending_tail();
+  // update()'s closing reduction is only read by the host, late (finish_update): where the read-back is deferred the
+  // reduction is not launched at all but rides on the next refinement's k_cg_scal_begin (one workgroup per node anyway),
+  // from partial-sum slots of its own; if no refinement comes, finish_update() launches it
+  struct UpdLazy { bool pending = false; int nslots = 0; };
+  UpdLazy upd_lazy_;
+  bool lazy_update_reduce() const;
+  double *upd_slots() const { return partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all; }   // update()'s own partial-sum slots
+  // the stated sequence (m: the nodes, possibly under the gate's word; r: the roles)
+  void update_product(const NodeMask &m, const UpdateRoles &r, bool from_xak, bool carry_tail);   // G X and <X, 1/2 G X> (slot 5)
+  void update_inter_pass(const NodeMask &m, const UpdateRoles &r, bool quad, bool with_Df, const double *lazy_recv);
+  void update_reduce(int nslots, const double *pupd);   // the closing reduction into h_upd_
+  // The host-side facts of one update() call, computed once (plan_update); the phases below run over it
+  struct UpdatePlan {
+    std::vector<int> locals, adv, first, later;   // the nodes to update; whose history advances; at their first / a later iteration
+    NodeBits bits = 0;                            // of locals
+    NodeMask mask = ALL_NODES;                    // ... and their mask
+    bool trivial = false, rotate = false, both = false, can_defer = false, fuse_copy = false, split = false;
+    const double *lazy_recv = nullptr;            // the receive buffer the inter-edge pass unpacks on the way (robust losses)
+  };
+  UpdatePlan plan_update(const std::vector<int> &locals_in) const;
+  void advance_history(const UpdatePlan &p);      // the rotation or copy, and X[iter]'s own rows
+  void update_head(const UpdatePlan &p, const UpdateRoles &r);   // the product with G where it has not gone ahead of an exchange
+  void build_trivial(const UpdatePlan &p, const UpdateRoles &r);
+  void trivial_common(const UpdatePlan &p, const UpdateRoles &r);
+  void trivial_launches(const UpdatePlan &p, const UpdateRoles &r, bool later);
+  void build_robust(const UpdatePlan &p, const UpdateRoles &r);
+  void dynamic_detour(const UpdateRoles &r, const std::vector<int> &set, bool quad, std::vector<double> &rho, std::vector<double> &gap);
+  void robust_launches(const UpdatePlan &p, const UpdateRoles &r, const std::vector<int> &set, const std::vector<int> &fresh, bool quad, bool head_inside);
+  void close_update(const UpdatePlan &p, const UpdateRoles &r, int seg_id, unsigned long long variant, int nslots,
+                    const std::vector<int> &set, const std::function<void()> &launches, std::function<void()> logic);
+  void host_update_logic(int local, double fobj, double f, double gradFnorm);
+  // The read-back that ends update() is deferred where nothing has to be decided yet: update() enqueues the reduction,
+  // advances the Nesterov sequence (host_update_pre: s, gamma -- they do not depend on the numbers read back) and
+  // returns; the next iterate() queues its extrapolation, proximal step and translation solve and only then waits
+  // (finish_update), so the GPU does not idle while the host takes the scalars.  Every other reader of the node state
+  // or of the pinned scalars calls finish_update() first.
+  void host_update_pre(int local);
+  void finish_update();
+  std::function<void()> pending_update_;
+  unsigned long long pending_seq_ = 0;
   DevBuf<double> partials_;
   DevBuf<CgNode> cg_;       // device-resident state of the truncated CG (tnt.cpp, k_cg_scal)
   DevBuf<double> jacobi_;   // Preconditioner::Jacobi: 1 / diag(G_RR), one entry per rotation row
@@ -393,6 +447,7 @@ class Group {
   double starF_ = 0, star_fobj_ = 0, star_fobjh_ = 0;
   int star_branches_ = 0;
   void node_rows_of_global(int a, const double *X, int ld, std::vector<double> &Z) const;
+  void half_step_product();   // amm(): T1_ = G [0 ; Xakh.R] + gx and the sum of Gkh, one pass
   bool prepare_extrapolated(const double *gam_dev = nullptr, int prox_slot = -1);   // Y, g_x, Df_x for the masked nodes (+ the proximal step)
   double global_objective(const double *X_own);           // F at the point whose own rows are X_own
   // the master's numbers in ONE read-back: F(X1) [, F(X2)] [, |X1 - ref|^2, |X2 - ref|^2] (null pointers: not wanted)
@@ -440,17 +495,7 @@ class Group {
   TcolOp g_tcol() const { return {G_.dev, G_.tcol.p}; }   // G's translation column: y = base + G_{:,t} xt.t (launch_bsr_tcol*)
   void recover_translations(double *X, const double *g);  // X.t = -Gtt^-1 (g_t + G_tR X.R) for masked nodes
   void eval_G(const double *X, const double *g, int slot);
-  void host_update_logic(int local, double fobj, double f, double gradFnorm);
-  // The read-back that ends update() is deferred where nothing has to be decided yet: update() enqueues the reduction,
-  // advances the Nesterov sequence (host_update_pre: s, gamma -- they do not depend on the numbers read back) and
-  // returns; the next iterate() queues its extrapolation, proximal step and translation solve and only then waits
-  // (finish_update), so the GPU does not idle while the host takes the scalars.  Every other reader of the node state
-  // or of the pinned scalars calls finish_update() first.
-  void host_update_pre(int local);
-  void finish_update();
   unsigned long long fetch_async(int nslots, bool all_rows);
-  std::function<void()> pending_update_;
-  unsigned long long pending_seq_ = 0;
   int amm(const std::vector<int> &locals);
   int mm(const std::vector<int> &locals);
   // refine X in place (TNT on G(. | g)); sets Gk = G(X | g) and, with g_alt, Gk_alt = G(X | g_alt)
