@@ -10,10 +10,13 @@
 // adaptive-restart counters) stays on the host exactly as in the reference; a
 // per-node device mask lets nodes that take different branches share launches.
 #pragma once
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <functional>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -85,6 +88,13 @@ struct DChordalOptions {
   int iters[4] = {100, 400, 150, 250};   // reduced R, R, reduced t, t
   int local_iters = 30;
   double reg_G = 1e-12;
+};
+
+// TNTParams as DPGOHash leaves them (TNT.h:81-97, 129): the acceptance test and trust-region update of run_tnt() (tnt.cpp) and
+// the same test in the gate of a speculative update (speculate_update)
+struct TntConst {
+  static constexpr double eta1 = .05, eta2 = .9, alpha1 = .25, alpha2 = 2.5, Delta_tol = 1e-6, Delta0 = 1.0;
+  static double sqrt_eps() { return std::sqrt(std::numeric_limits<double>::epsilon()); }
 };
 
 // DPGO_SETUP_TIMING=1: wall time of the set-up phases on stderr
@@ -447,7 +457,30 @@ class Group {
   double starF_ = 0, star_fobj_ = 0, star_fobjh_ = 0;
   int star_branches_ = 0;
   void node_rows_of_global(int a, const double *X, int ld, std::vector<double> &Z) const;
+  // ---- iterate() (iterate.cpp)
   void half_step_product();   // amm(): T1_ = G [0 ; Xakh.R] + gx and the sum of Gkh, one pass
+  // Gk <- the surrogate value G(X | g[k]) of the nodes of `set`, one pass and one read-back (nothing for an empty set);
+  // into (optional, indexed by local node): the values go there instead of Gk
+  void surrogate_at(const std::vector<int> &set, const double *X, double *into = nullptr);
+  // Gk of the nodes of `set` at Xak, whose translations were just recovered with g: the refined ones are refined against g
+  // (run_tnt), then the others are evaluated (surrogate_at)
+  void refine_or_evaluate(const std::vector<int> &set, const double *g);
+  // The per-call facts of one amm(), and its phases in their order
+  struct AmmIter {
+    const std::vector<int> &locals;
+    NodeMask mask;                              // of locals
+    std::vector<double> Gkh;                    // G(Xakh | g[k]) per local node
+    std::vector<int> redo, restart, fb_x, fb_c; // the half step taken again; restarted; fallen back (g extrapolated / g[k])
+    std::vector<char> g_is_current;             // a restart re-based the node's Xak on g[k]
+    bool done_tnt = false, abandoned = false;   // the unasked refinement stood / was abandoned
+  };
+  void amm_head(const double *gam_dev, const NodeMask &mask);   // extrapolation, proximal half step, translation solve
+  bool decide_refined(const std::vector<int> &locals);          // `refined` of every node; true: all of them are
+  void refine_unasked(AmmIter &it);
+  void refine_asked(AmmIter &it);
+  void redo_half_step(AmmIter &it);
+  void restart(AmmIter &it);
+  void fall_back(AmmIter &it);
   bool prepare_extrapolated(const double *gam_dev = nullptr, int prox_slot = -1);   // Y, g_x, Df_x for the masked nodes (+ the proximal step)
   double global_objective(const double *X_own);           // F at the point whose own rows are X_own
   // the master's numbers in ONE read-back: F(X1) [, F(X2)] [, |X1 - ref|^2, |X2 - ref|^2] (null pointers: not wanted)
@@ -480,6 +513,8 @@ class Group {
   void fetch(int nslots, bool all_rows);                  // -> h_scal_[local * MAX_SLOTS + s]
   void wait_flag(unsigned long long seq);   // the schedule's wait, then the verdicts that were enqueued in front of that flag
   int deferred_slots_ = 0;   // slots written earlier that ride along with the next fetch (saves a host round trip)
+  // ... taken along by a reduction of nslots slots: how many it reduces.  Consumed once: by the first reduction after they were parked
+  int take_deferred_slots(int nslots) { const int n = std::max(nslots, deferred_slots_); deferred_slots_ = 0; return n; }
   double scal(int local, int s) const { return h_scal_[local * MAX_SLOTS + s]; }
   double *h_upd_ = nullptr;   // pinned (same allocation): the sums update() ends with
   double uscal(int local, int s) const { return h_upd_[local * MAX_SLOTS + s]; }
@@ -505,6 +540,7 @@ class Group {
   // enqueued only touched work vectors, and T1_)
   bool run_tnt(const std::vector<int> &locals, double *X, const double *g, const double *g_alt = nullptr,
                bool base_ready = false, const std::function<bool()> *confirm = nullptr);
+  struct TntRun;   // the state and the phases of one run_tnt() call (tnt.cpp)
 };
 
 }  // namespace dpgo

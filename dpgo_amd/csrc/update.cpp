@@ -82,7 +82,7 @@ void Group::speculate_update(const double *xprop, int nslots_trial) {
   AmmGate G;
   G.nnodes = L; G.ds = 2 * MAX_DOTS; G.max_it = opt_.max_iterations; G.max_acc = opt_.max_iterations_accepted;
   G.max_hits0 = opt_.max_soft_restart_hits[0]; G.max_hits1 = opt_.max_soft_restart_hits[1];
-  G.sqrt_eps = std::sqrt(std::numeric_limits<double>::epsilon()); G.eta1 = .05;   // TNT.h:83 (run_tnt's constants)
+  G.sqrt_eps = TntConst::sqrt_eps(); G.eta1 = TntConst::eta1;
   G.rel_tol = opt_.rel_func_decrease_tol; G.step_tol = opt_.stepsize_tol; G.psi = opt_.psi; G.phi = opt_.phi;
   for (int a = 0; a < MAX_LOCAL_NODES; a++) {
     const bool in = a < L;
@@ -420,8 +420,7 @@ void Group::build_robust(const UpdatePlan &p, const UpdateRoles &r) {
 // now or deferred (it outlives this call: it captures by value).
 void Group::close_update(const UpdatePlan &p, const UpdateRoles &r, int seg_id, unsigned long long variant, int nslots,
                          const std::vector<int> &set, const std::function<void()> &launches, std::function<void()> logic) {
-  nslots = std::max(nslots, deferred_slots_);
-  deferred_slots_ = 0;
+  nslots = take_deferred_slots(nslots);
   NodeBits bits = 0;
   for (int a : set) bits |= 1ull << a;
   // the closing reduction is left to the next refinement's k_cg_scal_begin (group.h: UpdLazy) where the read-back is
