@@ -15,6 +15,8 @@ inner step of ``dist_pgo``:
                                                   pcm_inliers(graph, X) -> keep mask, Graph.filter_edges(keep)
   SESyncProblem::verify_solution                  NodeGroup.certify(X) -> (CertResult, x); cert_lambda, cert_apply
                             SESyncProblem.cpp:375-468, SESync_utils.cpp:721-830 (fast_verification STEP 2)
+  fast_verification         SESync_utils.cpp:721-830  NodeGroup.verify(X) -> (CertResult, x, CertFactor); cert_factor (STEP 1
+                                                  alone: the device Cholesky of S + eta I), cert_matrix
 
 All compute runs in hand-written HIP kernels behind the C ABI of
 include/dpgo_amd.h.  There is NO CPU fallback: creating a NodeGroup without a
@@ -214,6 +216,11 @@ SYMBOLS = {
     "dpgo_cert_options_default": (None, [C.c_void_p]),
     "dpgo_group_certify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int]),
     "dpgo_group_cert_lambda": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP]),
+    "dpgo_group_cert_factor": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, C.c_longlong, C.c_void_p]),
+    "dpgo_group_verify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, C.c_void_p, _DP, C.c_int,
+                                    C.c_void_p]),
+    "dpgo_group_cert_matrix": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
+                                         C.POINTER(C.c_longlong)]),
     "dpgo_group_cert_apply": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_debug_rayleigh_ritz": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _IP]),
 }
@@ -631,8 +638,8 @@ class NodeGroup:
         STEP 2, C++/SESync/src/SESync_utils.cpp:765-826).  Returns (CertResult, x): x is a unit vector of length (d+1)N,
         theta = x' S x and residual = |S x - theta x| come from one fresh product with it, and status is
         CERT_NEGATIVE (theta < -eta/2: x proves lambda_min(S) < -eta/2), CERT_NONNEGATIVE (column 0 converged with
-        theta >= -eta/2 -- evidence, NOT proof: a converged Ritz pair need not be the smallest one, and the reference's
-        proof, a Cholesky factorisation of S + eta I, is not part of this library) or CERT_UNDECIDED (max_iters
+        theta >= -eta/2 -- evidence, NOT proof: a converged Ritz pair need not be the smallest one; the proof, a
+        Cholesky factorisation of S + eta I, is cert_factor / verify) or CERT_UNDECIDED (max_iters
         reached).  stationarity = |S X|_F is the Riemannian gradient norm: the certificate only means something at a
         critical point.  The group must have the trivial loss and host every node; the optimiser's state is untouched.
         V0: the initial block ((d+1)N x d), default seeded Gaussians."""
@@ -651,6 +658,58 @@ class NodeGroup:
         if lib().dpgo_group_certify(self._h, _dp(X), ld, C.byref(o), v0, ldv0, C.byref(res), _dp(x), x.shape[0]) != 0:
             raise RuntimeError("dpgo_group_certify failed (robust loss, a group that does not host every node, or bad sizes)")
         return res, x
+
+    def cert_factor(self, X, eta=1e-3, max_factor_bytes=0):
+        """The proof: fast_verification STEP 1 (C++/SESync/src/SESync_utils.cpp:731-754), the Cholesky factorisation of
+        S(X) + eta I on the device.  Returns a CertFactor: outcome CERT_FACTOR_PD (lambda_min(S) > -eta, up to the
+        rounding of the factorisation), CERT_FACTOR_NOT_PD (a non-positive pivot: lambda_min(S) <= -eta) or
+        CERT_FACTOR_SKIPPED (the analysis predicts more device memory than max_factor_bytes, when > 0, or than half of
+        what is free: nothing was allocated), with the elimination tree's sizes, the pivot range, stationarity =
+        |S X|_F and the host seconds of the analysis and of the numeric phase."""
+        X, ld = _fcol(X)
+        f = CertFactor()
+        if lib().dpgo_group_cert_factor(self._h, _dp(X), ld, float(eta), int(max_factor_bytes), C.byref(f)) != 0:
+            raise RuntimeError("dpgo_group_cert_factor failed (robust loss, a group that does not host every node, or bad sizes)")
+        return f
+
+    def verify(self, X, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True, stop_on_negative=True, seed=0, V0=None,
+               refresh_every=50, max_factor_bytes=0):
+        """fast_verification (SESync_utils.cpp:721-830): cert_factor first, certify's search only when the factorisation
+        did not succeed.  Returns (CertResult, x, CertFactor).  CERT_FACTOR_PD: status CERT_PROVEN, iterations 0, x zero;
+        CERT_FACTOR_NOT_PD: certify's result, except that NONNEGATIVE -- which the factorisation has just refuted --
+        becomes UNDECIDED (theta and residual kept); CERT_FACTOR_SKIPPED: certify's result unchanged.  PROVEN is a
+        floating-point statement about S(X) and means "global minimum" only where stationarity is small (the header
+        include/dpgo_amd.h has the warning example)."""
+        X, ld = _fcol(X)
+        o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
+                        stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
+        v0, ldv0 = None, 0
+        if V0 is not None:
+            V0 = np.asarray(V0)
+            if V0.shape != X.shape:
+                raise ValueError("verify: V0 must have the shape of X, %r" % (X.shape,))
+            V0, ldv0 = _fcol(V0)
+            v0 = _dp(V0)
+        res, f = CertResult(), CertFactor()
+        x = np.zeros(X.shape[0])
+        if lib().dpgo_group_verify(self._h, _dp(X), ld, C.byref(o), int(max_factor_bytes), v0, ldv0, C.byref(res), _dp(x),
+                                   x.shape[0], C.byref(f)) != 0:
+            raise RuntimeError("dpgo_group_verify failed (robust loss, a group that does not host every node, or bad sizes)")
+        return res, x, f
+
+    def cert_matrix(self, X, eta):
+        """Debug: the matrix cert_factor factors, S(X) + eta I, read back from the device: CSR (ptr, col, val) on the
+        unknowns (d+1) g + r of the global poses g (r = 0 the translation, r = 1..d the rows of Y_g), every stored
+        (d+1) x (d+1) block dense."""
+        X, ld = _fcol(X)
+        nnz = C.c_longlong(0)
+        if lib().dpgo_group_cert_matrix(self._h, _dp(X), ld, float(eta), None, None, None, 0, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_cert_matrix failed")
+        n = (self.d + 1) * self.graph.num_poses
+        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+        if lib().dpgo_group_cert_matrix(self._h, _dp(X), ld, float(eta), _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_cert_matrix failed")
+        return ptr, col, val
 
     def cert_lambda(self, X):
         """compute_Lambda_blocks (SESyncProblem.cpp:375-395): the N symmetric d x d blocks of Lambda(X), (N, d, d)."""
@@ -928,8 +987,10 @@ class DPGOStar:
         return X
 
 
-CERT_UNDECIDED, CERT_NONNEGATIVE, CERT_NEGATIVE = 0, 1, 2
-CERT_NAMES = {0: "UNDECIDED", 1: "NONNEGATIVE", 2: "NEGATIVE"}
+CERT_UNDECIDED, CERT_NONNEGATIVE, CERT_NEGATIVE, CERT_PROVEN = 0, 1, 2, 3   # PROVEN: NodeGroup.verify only
+CERT_NAMES = {0: "UNDECIDED", 1: "NONNEGATIVE", 2: "NEGATIVE", 3: "PROVEN"}
+CERT_FACTOR_NOT_PD, CERT_FACTOR_PD, CERT_FACTOR_SKIPPED = 0, 1, 2
+CERT_FACTOR_NAMES = {0: "NOT_PD", 1: "PD", 2: "SKIPPED"}
 
 
 class CertOptions(C.Structure):
@@ -948,6 +1009,14 @@ class CertResult(C.Structure):
     """dpgo_cert_result_t."""
     _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("restarts", C.c_int), ("theta", C.c_double),
                 ("residual", C.c_double), ("S_norm_est", C.c_double), ("stationarity", C.c_double)]
+
+
+class CertFactor(C.Structure):
+    """dpgo_cert_factor_t: the outcome of fast_verification STEP 1 and the sizes of its factorisation."""
+    _fields_ = [("outcome", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("factor_entries", C.c_longlong), ("factor_bytes", C.c_longlong), ("eta", C.c_double),
+                ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("stationarity", C.c_double),
+                ("symbolic_s", C.c_double), ("numeric_s", C.c_double)]
 
 
 def rayleigh_ritz(A, B, nblk):

@@ -933,6 +933,49 @@ int dpgo_group_cert_apply(dpgo_group_t *h, const double *X, int ld, const double
   return guarded([&] { return h->grp->cert_apply(X, ld, V, ldv, SV, ldsv); });
 }
 
+// ---- fast_verification STEP 1 and the whole of it (C++/SESync/src/SESync_utils.cpp:731-754, :721-830) ----
+static void put_factor(const dpgo::CertFactor &f, dpgo_cert_factor_t *o) {
+  o->outcome = f.outcome; o->fronts = f.fronts; o->levels = f.levels; o->max_front = f.max_front;
+  o->factor_entries = f.factor_entries; o->factor_bytes = f.factor_bytes;
+  o->eta = f.eta; o->pivot_min = f.pivot_min; o->pivot_max = f.pivot_max; o->stationarity = f.stationarity;
+  o->symbolic_s = f.symbolic_s; o->numeric_s = f.numeric_s;
+}
+
+int dpgo_group_cert_factor(dpgo_group_t *h, const double *X, int ld, double eta, long long max_factor_bytes,
+                           dpgo_cert_factor_t *factor) {
+  if (!h || !h->grp || !X || !factor) return -1;
+  return guarded([&] {
+    dpgo::CertFactor f;
+    const int rc = h->grp->cert_factor(X, ld, eta, max_factor_bytes, f);
+    put_factor(f, factor);
+    return rc;
+  });
+}
+
+int dpgo_group_verify(dpgo_group_t *h, const double *X, int ld, const dpgo_cert_options_t *opts, long long max_factor_bytes,
+                      const double *V0, int ldv0, dpgo_cert_result_t *result, double *x, int ldx, dpgo_cert_factor_t *factor) {
+  if (!h || !h->grp || !X || !opts || !result || !factor) return -1;
+  return guarded([&] {
+    dpgo::CertOptions o;
+    o.eta = opts->eta; o.tau = opts->tau; o.max_iters = opts->max_iters; o.precondition = opts->precondition;
+    o.stop_on_negative = opts->stop_on_negative; o.refresh_every = opts->refresh_every; o.seed = opts->seed;
+    dpgo::CertResult r;
+    dpgo::CertFactor f;
+    const int rc = h->grp->verify(X, ld, o, max_factor_bytes, V0, ldv0, r, x, ldx, f);
+    result->status = r.status; result->iterations = r.iterations; result->restarts = r.restarts;
+    result->theta = r.theta; result->residual = r.residual; result->S_norm_est = r.S_norm_est;
+    result->stationarity = r.stationarity;
+    put_factor(f, factor);
+    return rc;
+  });
+}
+
+int dpgo_group_cert_matrix(dpgo_group_t *h, const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap,
+                           long long *nnz) {
+  if (!h || !h->grp || !X || !nnz) return -1;
+  return guarded([&] { return h->grp->cert_matrix(X, ld, eta, ptr, col, val, cap, nnz); });
+}
+
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {
   if (!A || !B || !theta || !C || !used) return -1;
   return guarded([&] { return dpgo::rayleigh_ritz(ns, nblk, A, B, theta, C, used); });

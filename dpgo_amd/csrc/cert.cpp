@@ -1,9 +1,13 @@
 // Host side of the solution certificate (cert.h): the Rayleigh-Ritz step, the block-Jacobi preconditioner and the
 // LOBPCG loop of Group::certify (fast_verification STEP 2, C++/SESync/src/SESync_utils.cpp:765-826;
-// C++/Optimization/include/Optimization/LinearAlgebra/LOBPCG.h:131-337).
+// C++/Optimization/include/Optimization/LinearAlgebra/LOBPCG.h:131-337), and STEP 1 (:731-754): the pattern of S on
+// pose-major unknowns, its multifrontal analysis, and the calls that factor S + eta I on the device (Group::cert_factor,
+// Group::verify).
 #include "cert.h"
 
 #include <algorithm>
+#include <array>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -131,8 +135,19 @@ struct Group::CertState {
   double *h_sums = nullptr;             // pinned: what k_cert_reduce writes
   bool have_Tp = false;
   std::vector<int> gid;                 // unified own row -> global pose
+  // STEP 1: the pattern of S on the unknowns (d+1) p + r (p the unified own row), M's values in that order, the factor
+  CsrMatrix A;                          // ptr / col only: the values are written on the device
+  std::vector<int> bptr_h;
+  DevBuf<int> bptr, diag_pose;
+  DevBuf<double> Mval;
+  SpdFactor F;
+  bool have_pattern = false, have_symbolic = false;
+  double symbolic_s = 0;                // of the analysis, reported by the call that ran it
+  long long factor_bytes = 0;
   ~CertState() {
     if (h_sums) (void)hipHostFree(h_sums);
+    spd_release_numeric(F);
+    spd_release_device(F);
   }
 };
 
@@ -330,6 +345,221 @@ void Group::cert_build_precon() {
     }
   c.Tp.upload(Tp);
   c.have_Tp = true;
+}
+
+// ---------------------------------------------------------------------------
+// STEP 1: the Cholesky factorisation of S + eta I (SESync_utils.cpp:731-754)
+// ---------------------------------------------------------------------------
+// The pattern of M = G + S on pose-major unknowns, once per group: one dense B x B block per pair (p, q) that has a block
+// in a node's G or S (the walk of cert_build_precon over every block, the neighbour columns of S at their unified own
+// rows; the inter-node and xi terms cancel between the two), the diagonal block always, and the transposed pair of every
+// pair, so that the pattern is symmetric whatever the assembly stored.  Structural zeros are explicit: the quotient
+// graph of B consecutive unknowns is then exactly the pose graph.
+void Group::cert_build_pattern() {
+  CertState &c = *cert_;
+  if (c.have_pattern) return;
+  const int B = B_, BB = B * B, N = P0_;
+  std::vector<int> nbr_row(std::max(P1_, 1), -1);   // neighbour record -> the unified own row of the pose it copies
+  for (int a = 0; a < num_local(); a++)
+    for (int k = 0; k < info_[a].n[1]; k++) {
+      const auto key = info_[a].nbr_key[k];
+      const int b = local_of_node_.at(key.first);
+      nbr_row[nbr_off_[a] + k] = own_off_[b] + info_[b].index.at(key);
+    }
+  typedef std::pair<int, std::array<double, 16>> Blk;
+  std::vector<std::vector<Blk>> rows(N);
+  auto at = [&](int p, int q) -> std::array<double, 16> & {
+    for (Blk &b : rows[p])
+      if (b.first == q) return b.second;
+    rows[p].push_back({q, {}});
+    rows[p].back().second.fill(0.0);
+    return rows[p].back().second;
+  };
+  for (int a = 0; a < num_local(); a++) {
+    const int n0 = info_[a].n[0];
+    for (int r = 0; r < n0; r++) {
+      const int p = own_off_[a] + r;
+      at(p, p);
+      for (const BsrMatrix *A : {&ops_[a].G, &ops_[a].S})
+        for (int k = A->ptr[r]; k < A->ptr[r + 1]; k++) {
+          const int cl = A->col[k], q = cl < n0 ? own_off_[a] + cl : nbr_row[nbr_off_[a] + cl - n0];
+          std::array<double, 16> &m = at(p, q);
+          for (int e = 0; e < BB; e++) m[e] += A->val[(size_t)k * BB + e];
+        }
+    }
+  }
+  for (int p = 0; p < N; p++)
+    for (size_t k = 0; k < rows[p].size(); k++) at(rows[p][k].first, p);
+  c.bptr_h.assign(N + 1, 0);
+  for (int p = 0; p < N; p++) {
+    std::sort(rows[p].begin(), rows[p].end(), [](const Blk &x, const Blk &y) { return x.first < y.first; });
+    c.bptr_h[p + 1] = c.bptr_h[p] + (int)rows[p].size();
+  }
+  const size_t nblk = c.bptr_h[N], nnz = nblk * BB;
+  if (nnz > (size_t)0x7fffffff) throw DeviceError("certificate: the matrix has more than 2^31 entries");
+  std::vector<int> diag(nblk, -1);
+  std::vector<double> Mval(nnz);
+  c.A.n = B * N;
+  c.A.ptr.assign((size_t)B * N + 1, 0);
+  c.A.col.resize(nnz);
+  for (int p = 0; p < N; p++) {
+    const int nb = (int)rows[p].size();
+    const size_t base = (size_t)BB * c.bptr_h[p];
+    for (int r = 0; r < B; r++) {
+      c.A.ptr[(size_t)B * p + r + 1] = (int)(base + (size_t)(r + 1) * B * nb);
+      for (int j = 0; j < nb; j++)
+        for (int cc = 0; cc < B; cc++) {
+          const size_t e = base + (size_t)r * B * nb + (size_t)j * B + cc;
+          c.A.col[e] = B * rows[p][j].first + cc;
+          Mval[e] = rows[p][j].second[r * B + cc];
+        }
+    }
+    for (int j = 0; j < nb; j++)
+      if (rows[p][j].first == p) diag[c.bptr_h[p] + j] = p;
+  }
+  c.bptr.upload(c.bptr_h);
+  c.diag_pose.upload(diag);
+  c.Mval.upload(Mval);
+  c.have_pattern = true;
+}
+
+// The analysis (first call), the prediction, the refusal, the numeric context (first call that is not refused).
+int Group::cert_factor_setup(long long max_factor_bytes, CertFactor &out) {
+  CertState &c = *cert_;
+  cert_build_pattern();
+  if (!c.have_symbolic) {
+    const auto t0 = std::chrono::steady_clock::now();
+    // collapse = 1: the merge model of spd_factor prices solves, and nothing is solved here.  leaf: 64 unknowns, 16 poses
+    // at d = 3 -- the 125 poses of smallGrid3D come apart into four levels, the 9 of tinyGrid3D stay one front -- and more
+    // where that many leaves would not fit the 65535 fronts a level's launch can index (two leaves per `leaf` unknowns
+    // at the worst)
+    const long long n = c.A.n;
+    const int leaf = (int)std::max<long long>(64, B_ * ((2 * n / B_ + 59999) / 60000));
+    c.F.quiet = true;         // a non-positive pivot is a verdict here
+    c.F.factor_only = true;   // no W / WT: nothing is solved with this factor
+    if (spd_symbolic(c.A, c.F, leaf, 1, B_) != 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: certificate: the symbolic analysis of S failed.\n");
+      return -1;
+    }
+    c.factor_bytes = (long long)spd_numeric_bytes(c.F, (long long)c.A.col.size());
+    c.symbolic_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    out.symbolic_s = c.symbolic_s;
+    c.have_symbolic = true;
+  }
+  out.fronts = c.F.nfronts;
+  out.levels = (int)c.F.by_height.size();
+  out.max_front = c.F.max_front;
+  out.factor_entries = c.F.entries;
+  out.factor_bytes = c.factor_bytes;
+  out.outcome = CERT_FACTOR_SKIPPED;
+  if (max_factor_bytes > 0 && c.factor_bytes > max_factor_bytes) return 1;
+  if (!c.F.numeric) {
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if ((unsigned long long)c.factor_bytes > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
+    if (spd_prepare_device(c.A, c.F) != 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: certificate: the device state of the factorisation could not be set up.\n");
+      return -1;
+    }
+  }
+  return 0;
+}
+
+int Group::cert_factor(const double *X, int ld, double eta, long long max_factor_bytes, CertFactor &out) {
+  out = CertFactor();
+  out.eta = eta;
+  if (!std::isfinite(eta)) {
+    fprintf(stderr, "[dpgo_amd] ERROR: certificate: eta is not finite.\n");
+    return -1;
+  }
+  if (cert_begin(X, ld) != 0) return -1;
+  CertState &c = *cert_;
+  const int ready = cert_factor_setup(max_factor_bytes, out);
+  if (ready < 0) return -1;
+  cert_prepare(X, ld, &out.stationarity);
+  if (ready != 0) return 0;   // SKIPPED, with what the analysis predicts
+  const auto t0 = std::chrono::steady_clock::now();
+  launch_cert_matrix(d_, st_, P0_, c.bptr.p, c.diag_pose.p, c.Mval.p, c.Lam.p, eta, spd_numeric_values(c.F));
+  const int rc = spd_refactor_device(c.F, st_, false);   // (returns with the verdict read: the stream has drained)
+  out.numeric_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (rc != 0 && !c.F.not_pd) {
+    fprintf(stderr, "[dpgo_amd] ERROR: certificate: the factorisation failed on the device.\n");
+    return -1;
+  }
+  out.outcome = rc == 0 ? CERT_FACTOR_PD : CERT_FACTOR_NOT_PD;
+  out.pivot_max = c.F.pivot_max;
+  out.pivot_min = c.F.pivot_max > 0 ? c.F.pivot_min : 0.0;   // (no front factored: nothing recorded)
+  return 0;
+}
+
+int Group::cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap, long long *nnz) {
+  if (!nnz || !std::isfinite(eta) || cert_begin(X, ld) != 0) return -1;
+  CertState &c = *cert_;
+  cert_build_pattern();
+  *nnz = (long long)c.A.col.size();
+  if (!ptr && !col && !val) return 0;   // (the size alone)
+  if (!ptr || !col || !val || cap < *nnz) {
+    fprintf(stderr, "[dpgo_amd] ERROR: certificate: cert_matrix needs room for %lld entries.\n", *nnz);
+    return -1;
+  }
+  CertFactor f;
+  if (cert_factor_setup(0, f) != 0) {
+    fprintf(stderr, "[dpgo_amd] ERROR: certificate: the value array of the factorisation does not fit the device.\n");
+    return -1;
+  }
+  cert_prepare(X, ld, nullptr);
+  launch_cert_matrix(d_, st_, P0_, c.bptr.p, c.diag_pose.p, c.Mval.p, c.Lam.p, eta, spd_numeric_values(c.F));
+  std::vector<double> v(c.A.col.size());
+  HIP_CHECK(hipMemcpyAsync(v.data(), spd_numeric_values(c.F), sizeof(double) * v.size(), hipMemcpyDeviceToHost, st_));
+  HIP_CHECK(hipStreamSynchronize(st_));
+  // handed out on GLOBAL poses -- unknown (d+1) g + r, g = gid[p] -- rows in that order, a row's blocks by ascending pose
+  const int B = B_, BB = B * B, N = P0_;
+  std::vector<int> row_of(N), order;
+  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
+  size_t e = 0;
+  ptr[0] = 0;
+  for (int g = 0; g < N; g++) {
+    const int p = row_of[g], b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
+    const size_t base = (size_t)BB * b0;
+    auto pose_of = [&](int j) { return c.gid[c.A.col[base + (size_t)j * B] / B]; };
+    order.resize(nb);
+    for (int j = 0; j < nb; j++) order[j] = j;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return pose_of(x) < pose_of(y); });
+    for (int r = 0; r < B; r++) {
+      for (int j : order)
+        for (int cc = 0; cc < B; cc++, e++) {
+          col[e] = B * pose_of(j) + cc;
+          val[e] = v[base + (size_t)r * B * nb + (size_t)j * B + cc];
+        }
+      ptr[(size_t)B * g + r + 1] = (int)e;
+    }
+  }
+  return 0;
+}
+
+static bool cert_options_ok(const CertOptions &o, int rows, const double *V0, int ldv0, const double *x_out, int ldx) {
+  return o.eta >= 0 && o.tau > 0 && o.max_iters >= 0 && o.refresh_every >= 0 && !(V0 && ldv0 < rows) && !(x_out && ldx < rows);
+}
+
+// fast_verification (SESync_utils.cpp:721-830): STEP 1, and STEP 2 only when it did not succeed
+int Group::verify(const double *X, int ld, const CertOptions &o, long long max_factor_bytes, const double *V0, int ldv0,
+                  CertResult &res, double *x_out, int ldx, CertFactor &fac) {
+  res = CertResult();
+  fac = CertFactor();
+  if (!cert_options_ok(o, (d_ + 1) * num_poses_global_, V0, ldv0, x_out, ldx)) {
+    fprintf(stderr, "[dpgo_amd] ERROR: verify: bad options or inconsistent size of V0 / x.\n");
+    return -1;
+  }
+  if (cert_factor(X, ld, o.eta, max_factor_bytes, fac) != 0) return -1;
+  if (fac.outcome == CERT_FACTOR_PD) {
+    res.status = CERT_PROVEN;
+    res.stationarity = fac.stationarity;
+    return 0;
+  }
+  const int rc = certify(X, ld, o, V0, ldv0, res, x_out, ldx);
+  // a search that converged to a Ritz value >= -eta / 2 has just been refuted by the factorisation
+  if (rc == 0 && fac.outcome == CERT_FACTOR_NOT_PD && res.status == CERT_NONNEGATIVE) res.status = CERT_UNDECIDED;
+  return rc;
 }
 
 int Group::certify(const double *X, int ld, const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x_out, int ldx) {

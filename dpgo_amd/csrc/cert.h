@@ -21,9 +21,20 @@
 //    (theta = x^T S x, residual = |S x - theta x|), and the status is decided from those two numbers:
 //      NEGATIVE     theta < -eta / 2: x proves lambda_min(S) < -eta / 2;
 //      NONNEGATIVE  otherwise, and residual <= tau (|S|_est + |theta|): column 0 converged.  EVIDENCE, NOT PROOF: a
-//                   converged Ritz pair need not be the smallest one (the reference proves lambda_min >= -eta with a
-//                   Cholesky factorisation of S + eta I, fast_verification STEP 1, :731-754 -- not part of this code);
+//                   converged Ritz pair need not be the smallest one (the proof is STEP 1 below);
 //      UNDECIDED    max_iters reached without either.
+//  * The proof is fast_verification STEP 1 (SESync_utils.cpp:731-754): a Cholesky factorisation of S + eta I, which
+//    exists exactly when the matrix is positive definite.  Group::cert_factor writes S + eta I on the device
+//    (k_cert_matrix, cert.hip) as a CSR matrix on pose-major unknowns (d+1) p + r -- r = 0 the translation, r = 1..d
+//    the rows of Y_p; S acts alike on every column, so the matrix is (d+1)N x (d+1)N -- with one explicit dense
+//    (d+1) x (d+1) block per pair of poses M couples, straight into the value array of the multifrontal
+//    factorisation (spd.h: spd_symbolic on the quotient graph of the poses, spd_prepare_device, spd_refactor_device in
+//    factor-only mode), and reads the verdict: FACTOR_PD, FACTOR_NOT_PD (a non-positive pivot: an answer, not an
+//    error), or FACTOR_SKIPPED when the symbolic analysis predicts more device memory than the caller or the device
+//    allows.  Group::verify is fast_verification itself: STEP 1, and the LOBPCG search only when it did not succeed.
+//    PROVEN is a statement in floating point, as in the reference: the factorisation succeeds for S + eta I + E with
+//    |E| of the order n^(3/2) u |S| (Higham, Accuracy and Stability of Numerical Algorithms, thm 10.7), and it says
+//    "global minimum" only where `stationarity` is small (dpgo_amd.h has the warning example).
 //
 // Stated deviations from the reference:
 //  - the block size is fixed to d: a block of d vectors of length (d+1)N IS a pose-record array, so the search runs
@@ -42,7 +53,8 @@
 
 namespace dpgo {
 
-enum { CERT_UNDECIDED = 0, CERT_NONNEGATIVE = 1, CERT_NEGATIVE = 2 };
+enum { CERT_UNDECIDED = 0, CERT_NONNEGATIVE = 1, CERT_NEGATIVE = 2, CERT_PROVEN = 3 };   // PROVEN: Group::verify only
+enum { CERT_FACTOR_NOT_PD = 0, CERT_FACTOR_PD = 1, CERT_FACTOR_SKIPPED = 2 };
 
 struct CertOptions {
   double eta = 1e-3;   // min_eig_num_tol, C++/SESync/include/SESync/SESync.h:88
@@ -57,6 +69,17 @@ struct CertOptions {
 struct CertResult {
   int status = CERT_UNDECIDED, iterations = 0, restarts = 0;
   double theta = 0, residual = 0, S_norm_est = 0, stationarity = 0;
+};
+
+// STEP 1 (SESync_utils.cpp:731-754).  fronts, levels, max_front, factor_entries (sum (w + u) w over the fronts) and
+// factor_bytes (the device bytes of the numeric phase: every front matrix at once, the value array, the maps) come from
+// the symbolic analysis and are filled for SKIPPED too; pivot_min / pivot_max: the range of the pivots d_kk of the
+// fronts that factored (all of them for PD); symbolic_s: host seconds of the analysis (0 after the first call of a
+// group), numeric_s: host seconds from the launch of k_cert_matrix to the verdict.
+struct CertFactor {
+  int outcome = CERT_FACTOR_SKIPPED, fronts = 0, levels = 0, max_front = 0;
+  long long factor_entries = 0, factor_bytes = 0;
+  double eta = 0, pivot_min = 0, pivot_max = 0, stationarity = 0, symbolic_s = 0, numeric_s = 0;
 };
 
 // ---- the host's Rayleigh-Ritz step (cert.cpp; no device) ----
@@ -88,6 +111,11 @@ void launch_cert_gram(const LaunchCtx &lc, const double *Lam, const double *V, c
 // pose, null: R'); sums 2 ntri + j = |R'_j|^2, 2 ntri + d + j = |V'_j|^2
 void launch_cert_update(const LaunchCtx &lc, const CertCoef &c, const double *Tp, double *V,
                         double *W, double *P, double *SV, const double *SW, double *SP, double *partials);
+// out = S + eta I in the CSR order of the pose-major matrix: the (d+1)^2 nb_p values of pose p's rows are one run starting
+// at (d+1)^2 bptr[p] (row r, block j, column c at r (d+1) nb_p + j (d+1) + c); Mval: M in the same order; diag_pose[k]: p
+// for the diagonal block of pose p, -1 for every other block
+void launch_cert_matrix(int d, hipStream_t st, int nposes, const int *bptr, const int *diag_pose, const double *Mval,
+                        const double *Lam, double eta, double *out);
 // host[s] = sum over the own segments of partial s, s < nsums, in segment order; then the flag
 void launch_cert_reduce(hipStream_t st, const SegTable &T, int nsums, const double *partials, double *host, ReadbackFlag flag);
 

@@ -316,6 +316,28 @@ __global__ __launch_bounds__(SEG_ROWS) void k_cert_update(const Seg *segs, NodeM
   }
 }
 
+// The matrix STEP 1 factors, written where the factorisation reads it: one wave per pose, its lanes striding the pose's
+// run of values -- a coalesced copy of M with Lambda_p and eta applied to the diagonal block.
+template <int D>
+__global__ __launch_bounds__(256) void k_cert_matrix(int nposes, const int *__restrict__ bptr, const int *__restrict__ diag_pose,
+                                                     const double *__restrict__ Mval, const double *__restrict__ Lam, double eta,
+                                                     double *__restrict__ out) {
+  constexpr int B = D + 1;
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= nposes) return;
+  const int b0 = bptr[p], nb = bptr[p + 1] - b0, rowlen = B * nb, len = B * rowlen;
+  const size_t base = (size_t)B * B * b0;
+  for (int l = lane; l < len; l += 64) {
+    const int r = l / rowlen, rem = l - r * rowlen, j = rem / B, c = rem - j * B;
+    double v = Mval[base + l];
+    if (diag_pose[b0 + j] >= 0) {
+      if (r >= 1 && c >= 1) v -= Lam[(size_t)p * D * D + (r - 1) * D + (c - 1)];
+      if (r == c) v += eta;
+    }
+    out[base + l] = v;
+  }
+}
+
 // One wave per sum: the segments' partials in a fixed order, the result straight into pinned host memory; the last wave
 // to arrive raises the group's read-back flag (the protocol of k_reduce, kernels.hip).
 __global__ __launch_bounds__(64) void k_cert_reduce(int nseg, const double *partials, double *host, unsigned *arrived,
@@ -380,6 +402,13 @@ void launch_cert_update(const LaunchCtx &lc, const CertCoef &c, const double *Tp
   CoefArg K{c};
   CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_update<D>), dim3(T.nseg_own), dim3(SEG_ROWS), 0, st, T.segs, mask, K, Tp, V, W, P, SV,
                                         SW, SP, partials, T.nseg_own));
+}
+
+void launch_cert_matrix(int d, hipStream_t st, int nposes, const int *bptr, const int *diag_pose, const double *Mval,
+                        const double *Lam, double eta, double *out) {
+  if (nposes == 0) return;
+  CERT_DISPATCH_D(d, hipLaunchKernelGGL((k_cert_matrix<D>), dim3((nposes + 3) / 4), dim3(256), 0, st, nposes, bptr, diag_pose, Mval, Lam,
+                                        eta, out));
 }
 
 void launch_cert_reduce(hipStream_t st, const SegTable &T, int nsums, const double *partials, double *host, ReadbackFlag flag) {

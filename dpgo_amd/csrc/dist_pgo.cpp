@@ -8,6 +8,10 @@
 //                  certificate: <status> <theta> <residual> <iterations> <stationarity>
 //              from dpgo_group_certify (SESyncProblem::verify_solution, C++/SESync/src/SESyncProblem.cpp:397-468); with a
 //              robust loss or several ranks a line that says why not
+//              --verify (likewise)  after the summary (and after --certify's line), one more line on stdout
+//                  verification: <status> <outcome> <pivot_min> <theta> <residual> <iterations> <stationarity>
+//              from dpgo_group_verify (fast_verification, C++/SESync/src/SESync_utils.cpp:721-830: the Cholesky factorisation
+//              of S + eta I first, the search only when it does not succeed); the same reasons when it is not computed
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -43,7 +47,7 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true, certify = false;
+  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -60,6 +64,8 @@ int main(int argc, char **argv) {
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
+    else if (a == "--verify") verify = true;
+    else if (a.compare(0, 9, "--verify=") == 0) verify = parse_bool(argv[i] + 9);
     else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
@@ -185,6 +191,27 @@ int main(int argc, char **argv) {
       printf("certificate: %s %.16g %.16g %d %.16g\n",
              cr.status == DPGO_CERT_NEGATIVE ? "NEGATIVE" : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED", cr.theta,
              cr.residual, cr.iterations, cr.stationarity);
+    }
+  }
+  if (verify) {
+    if (loss != 0) {
+      if (root) printf("verification: not computed (the certificate is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("verification: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0);
+      dpgo_cert_options_t co;
+      dpgo_cert_options_default(&co);
+      dpgo_cert_result_t cr;
+      dpgo_cert_factor_t cf;
+      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+          dpgo_group_verify(grp, Xc.data(), ld, &co, 0, nullptr, 0, &cr, nullptr, 0, &cf) != 0)
+        return -1;
+      printf("verification: %s %s %.16g %.16g %.16g %d %.16g\n",
+             cr.status == DPGO_CERT_PROVEN ? "PROVEN" : cr.status == DPGO_CERT_NEGATIVE ? "NEGATIVE"
+             : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED",
+             cf.outcome == DPGO_CERT_FACTOR_PD ? "PD" : cf.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED", cf.pivot_min,
+             cr.theta, cr.residual, cr.iterations, cr.stationarity);
     }
   }
   if (save) {

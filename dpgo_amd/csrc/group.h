@@ -176,6 +176,12 @@ class Group {
   int certify(const double *X, int ld, const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x, int ldx);
   int cert_lambda(const double *X, int ld, double *Lambda);   // N blocks d x d, row-major, by global pose
   int cert_apply(const double *X, int ld, const double *V, int ldv, double *SV, int ldsv);   // SV = S(X) V
+  // fast_verification STEP 1 (C++/SESync/src/SESync_utils.cpp:731-754): the device Cholesky of S(X) + eta I; verify: STEP 1,
+  // then the search of certify only when it did not succeed (:721-830); cert_matrix: what is factored, read back
+  int cert_factor(const double *X, int ld, double eta, long long max_factor_bytes, CertFactor &out);
+  int verify(const double *X, int ld, const CertOptions &o, long long max_factor_bytes, const double *V0, int ldv0, CertResult &res,
+             double *x, int ldx, CertFactor &fac);
+  int cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap, long long *nnz);
   // boundary exchange across groups: records of the poses other groups need
   int num_sent() const { return (int)sent_rows_.size(); }
   // device buffer, num_sent()*RS doubles; st: the stream to enqueue on (default: the group's)
@@ -447,6 +453,8 @@ class Group {
   void cert_apply_M(double *in_all, double *out_own);
   void cert_apply_S(double *in_all, double *out_own);
   void cert_build_precon();
+  void cert_build_pattern();
+  int cert_factor_setup(long long max_factor_bytes, CertFactor &out);   // 0: ready to factor, 1: SKIPPED, -1: error
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

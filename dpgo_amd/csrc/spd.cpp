@@ -448,12 +448,14 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
   double t_lap = omp_get_wtime();
   omp_set_num_threads(host_threads());
   spd_release_device(F);
-  const bool keep_numeric = F.keep_numeric;
+  const bool keep_numeric = F.keep_numeric, quiet = F.quiet, factor_only = F.factor_only;
   spd_release_numeric(F);   // (a kept numeric context belongs to the pattern that is about to be replaced)
   F = SpdFactor();
   F.n = n;
   F.keep_device = keep_device;
   F.keep_numeric = keep_numeric;
+  F.quiet = quiet;
+  F.factor_only = factor_only;
   // adjacency without the diagonal
   CsrMatrix adj;
   adj.n = n;
@@ -767,7 +769,7 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
       for (int k = kb; k < ke; k++) {   // diagonal block, unblocked
         double dkk = Fm[(size_t)k * m + k];
         if (!(dkk > 0.0)) {
-          fprintf(stderr, "[dpgo_amd] ERROR: spd_factor: non-positive pivot %g (front %d, col %d)\n", dkk, f, k);
+          if (!F.quiet) fprintf(stderr, "[dpgo_amd] ERROR: spd_factor: non-positive pivot %g (front %d, col %d)\n", dkk, f, k);
           fail = 1;
           break;
         }
@@ -977,6 +979,20 @@ int spd_factor(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int blo
   F.collapse = collapse;   // (the merge depth actually used)
   F.block = block;
   return rc;
+}
+
+int spd_symbolic(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int block) {
+  collapse = std::max(collapse, 1);
+  const int rc = spd_factor_impl(A, F, leaf, collapse, true, nullptr, block, true);
+  F.leaf = leaf;
+  F.collapse = collapse;
+  F.block = block;
+  if (rc != 0) return rc;
+  // (the elimination tree as lists of children, in the order the full factorisation builds them)
+  F.children.assign(F.nfronts, {});
+  for (int f = 0; f < F.nfronts; f++)
+    if (F.parent[f] >= 0) F.children[F.parent[f]].push_back(f);
+  return 0;
 }
 
 void spd_solve_host(const SpdFactor &F, double *X, int nc) {

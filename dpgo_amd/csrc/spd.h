@@ -59,6 +59,13 @@ struct SpdFactorData {
   // keep_numeric (with keep_device): the device state of the numeric phase stays with the factor (`numeric`), dev_W / dev_WT
   // are borrowed from it, and spd_refactor_device() re-factors from values that are already on the GPU
   bool keep_numeric = false, dev_borrowed = false;
+  // quiet: a non-positive pivot is reported by the return value alone, without the ERROR line -- for a caller to whom "not
+  // positive definite" is an answer (the certificate's factorisation; the reference: MChol.cholmod().print = 0,
+  // C++/SESync/src/SESync_utils.cpp:746-748)
+  // factor_only (spd_prepare_device): the numeric phase ends with the verdict and the pivot range -- W / WT are neither
+  // allocated nor written, and nothing can be solved with the factor
+  bool quiet = false, factor_only = false;
+  bool not_pd = false;   // the last device numeric phase met a non-positive pivot (a -1 with this unset is a device error)
   struct SpdNumericCtx *numeric = nullptr;
   int leaf = 32, collapse = 0, block = 1;   // the parameters this factor was built with (spd_refactor's host path repeats them)
   double *dev_W = nullptr, *dev_WT = nullptr;
@@ -106,6 +113,19 @@ double *spd_numeric_values(SpdFactor &F);
 int spd_refactor_device(SpdFactor &F, void *stream = nullptr, bool defer = false);
 int spd_refactor_finish(SpdFactor &F, bool wait = true);   // wait = false: the stream is known to have passed the factorisation
 void spd_release_numeric(SpdFactor &F);
+
+// The three steps of spd_factor taken apart, for a caller that wants to know what a factorisation will cost before it
+// allocates anything and whose values are written on the device (the certificate's S + eta I, cert.cpp):
+//   spd_symbolic        ordering, fronts, update rows -- from the PATTERN of A alone (A.val is not read; F.quiet and
+//                       F.factor_only are kept); F.entries, F.max_front, F.by_height.size() (tree levels) are then known
+//   spd_numeric_bytes   the device bytes spd_prepare_device will allocate for that pattern: all front matrices at once,
+//                       the value array and the maps into the fronts (+ the padded panels W / WT unless factor_only)
+//   spd_prepare_device  the numeric context, kept with the factor (keep_numeric), nothing factored: the caller fills
+//                       spd_numeric_values(F) and calls spd_refactor_device.  The context does not depend on any values, so
+//                       it survives a factorisation that meets a non-positive pivot: the next call is the kernels again.
+int spd_symbolic(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int block);
+int64_t spd_numeric_bytes(const SpdFactor &F, int64_t nnz);
+int spd_prepare_device(const CsrMatrix &A, SpdFactor &F);
 
 // Host solve (setup paths and tests): X (n x ncols, row-major) <- A^-1 X.
 void spd_solve_host(const SpdFactor &F, double *X, int ncols);

@@ -715,6 +715,7 @@ struct SpdNumericCtx {
   int n_wtop_items = 0, n_wbot_items = 0, max_ent = 0;
   hipStream_t st = nullptr;
   bool outputs_zeroed = false;
+  bool factor_only = false;   // SpdFactor::factor_only: no W / WT, the verdict and the pivots are all there is
   ~SpdNumericCtx() {
     for (void *q : {(void *)d_fd, (void *)d_dst, (void *)d_src, (void *)d_cmap, (void *)d_lvl, (void *)d_fail, (void *)d_aval,
                     (void *)d_Fm, (void *)d_dinv, (void *)d_W, (void *)d_WT, (void *)d_pairs, (void *)d_wtop_items, (void *)d_wbot_items, (void *)d_xrows, (void *)d_xrow_ptr, (void *)d_inv})
@@ -735,6 +736,7 @@ struct SpdNumericCtx {
 int SpdNumericCtx::build(const CsrMatrix &A, const SpdFactor &F, const std::vector<std::vector<int>> &children) {
   nt = F.nfronts;
   const int n = A.n;
+  factor_only = F.factor_only;
   fd.assign(nt, FrontDesc());
   std::vector<int> height(nt, 0);
   for (int f = 0; f < nt; f++)
@@ -862,7 +864,7 @@ int SpdNumericCtx::build(const CsrMatrix &A, const SpdFactor &F, const std::vect
   }
   n_wtop_items = (int)wtop_items.size() / 2;
   n_wbot_items = (int)wbot_items.size() / 2;
-  n_aval = A.val.size();
+  n_aval = A.col.size();   // (the pattern decides: a caller that writes the values on the device brings none)
   if (extend_by_rows) {
     FA_OK(hipMalloc((void **)&d_xrows, sizeof(ExtendRow) * std::max<size_t>(xrows.size(), 1)));
     FA_OK(hipMalloc((void **)&d_xrow_ptr, sizeof(int) * xrow_ptr.size()));
@@ -879,8 +881,10 @@ int SpdNumericCtx::build(const CsrMatrix &A, const SpdFactor &F, const std::vect
   FA_OK(hipMalloc((void **)&d_aval, sizeof(double) * std::max<size_t>(n_aval, 1)));
   FA_OK(hipMalloc((void **)&d_Fm, sizeof(double) * std::max<long long>(fm_total, 1)));
   FA_OK(hipMalloc((void **)&d_dinv, sizeof(double) * max_lvl * NB * NB));
-  FA_OK(hipMalloc((void **)&d_W, sizeof(double) * std::max<int64_t>(w_total, 1)));
-  FA_OK(hipMalloc((void **)&d_WT, sizeof(double) * std::max<int64_t>(wt_total, 1)));
+  if (!factor_only) {
+    FA_OK(hipMalloc((void **)&d_W, sizeof(double) * std::max<int64_t>(w_total, 1)));
+    FA_OK(hipMalloc((void **)&d_WT, sizeof(double) * std::max<int64_t>(wt_total, 1)));
+  }
   FA_OK(hipMalloc((void **)&d_pairs, sizeof(ExtendPair) * std::max<size_t>(pairs.size(), 1)));
   FA_OK(hipStreamCreate(&st));
   FA_OK(hipMemcpyAsync(d_fd, fd.data(), sizeof(FrontDesc) * nt, hipMemcpyHostToDevice, st));
@@ -918,7 +922,7 @@ int SpdNumericCtx::factor(SpdFactor &F, const double *aval_host, double *flops_o
   if (aval_host && n_aval) FA_OK(hipMemcpyAsync(d_aval, aval_host, sizeof(double) * n_aval, hipMemcpyHostToDevice, st));
   FA_OK(hipMemcpyAsync(d_fail, h_io, sizeof(unsigned long long) * NIO, hipMemcpyHostToDevice, st));   // (pinned, kept: no wait)
   FA_OK(hipMemsetAsync(d_Fm, 0, sizeof(double) * std::max<long long>(fm_total, 1), st));
-  if (!outputs_zeroed) {
+  if (!outputs_zeroed && !factor_only) {
     // (what the kernels do not write -- the padding of a row, a zero triangle -- they never write: once is enough for a
     // context that is used again, Rescale::Dynamic)
     FA_OK(hipMemsetAsync(d_W, 0, sizeof(double) * std::max<int64_t>(w_total, 1), st));
@@ -1024,8 +1028,8 @@ int SpdNumericCtx::factor(SpdFactor &F, const double *aval_host, double *flops_o
     }
   }
   // the outputs: W = [L11^-1 ; -L21 L11^-1] and its transpose, of every front at once
-  if (n_wtop_items > 0) hipLaunchKernelGGL(k_fa_wtop, dim3(n_wtop_items), dim3(256), 0, st, d_fd, d_wtop_items, d_Fm, d_W, d_WT);
-  if (n_wbot_items > 0) {
+  if (n_wtop_items > 0 && !factor_only) hipLaunchKernelGGL(k_fa_wtop, dim3(n_wtop_items), dim3(256), 0, st, d_fd, d_wtop_items, d_Fm, d_W, d_WT);
+  if (n_wbot_items > 0 && !factor_only) {
     hipEvent_t a = nullptr, b = nullptr;
     if (mfma_ms_out) {
       FA_OK(hipEventCreate(&a)); FA_OK(hipEventCreate(&b));
@@ -1080,8 +1084,9 @@ int SpdNumericCtx::finish(SpdFactor &F, bool wait) {
     F.pivot_max = hi;
   }
   FA_OK(hipGetLastError());
+  F.not_pd = fail != 0;
   if (fail) {
-    fprintf(stderr, "[dpgo_amd] ERROR: spd_factor (device): non-positive pivot in front %d\n", fail - 1);
+    if (!F.quiet) fprintf(stderr, "[dpgo_amd] ERROR: spd_factor (device): non-positive pivot in front %d\n", fail - 1);
     return -1;
   }
   return 0;
@@ -1095,7 +1100,7 @@ int spd_factor_numeric_device(const CsrMatrix &A, SpdFactor &F, const std::vecto
                               double *flops_out, double *mfma_ms_out) {
   spd_release_device(F);
   SpdNumericCtx *ctx = F.numeric;
-  if (ctx && (ctx->nt != F.nfronts || ctx->n_aval != A.val.size())) { spd_release_numeric(F); ctx = nullptr; }
+  if (ctx && (ctx->nt != F.nfronts || ctx->n_aval != A.col.size())) { spd_release_numeric(F); ctx = nullptr; }
   if (!ctx) {
     ctx = new SpdNumericCtx();
     if (ctx->build(A, F, children) != 0) { delete ctx; return -1; }
@@ -1132,12 +1137,54 @@ int spd_factor_numeric_device(const CsrMatrix &A, SpdFactor &F, const std::vecto
   return rc;
 }
 
+// What build() allocates for the fronts of F and a matrix of nnz entries, from the symbolic analysis alone (the same sums).
+int64_t spd_numeric_bytes(const SpdFactor &F, int64_t nnz) {
+  const int nt = F.nfronts;
+  int64_t fm = 0, ent = 0, inv = 0;
+  std::vector<int> height(nt, 0);
+  std::vector<int64_t> per_level;
+  for (int f = 0; f < nt; f++) {
+    const int64_t w = F.w[f], m = w + F.u[f];
+    fm += (m + w) * m;
+    if (F.parent[f] >= 0) {
+      height[F.parent[f]] = std::max(height[F.parent[f]], height[f] + 1);
+      if (F.u[f] > 0) inv += F.w[F.parent[f]] + F.u[F.parent[f]];
+    }
+  }
+  for (int f = 0; f < nt; f++) {
+    if ((int)per_level.size() <= height[f]) per_level.resize(height[f] + 1, 0);
+    per_level[height[f]]++;
+  }
+  int64_t max_lvl = 1;
+  for (int64_t c : per_level) max_lvl = std::max(max_lvl, c);
+  // the entries of A that land in a front are those of its lower triangle (symmetric pattern: half of the off-diagonal
+  // ones and the diagonal), plus one per identity row
+  ent = (nnz - F.n) / 2 + 2 * (int64_t)F.n;
+  int64_t bytes = 8 * fm + 8 * nnz + 12 * ent + 4 * (int64_t)F.total_upd + 4 * inv + 8 * max_lvl * NB * NB + (int64_t)sizeof(FrontDesc) * nt;
+  if (!F.factor_only) bytes += 8 * (F.w_off[nt] + F.wt_off[nt]);
+  return bytes;
+}
+
+// The numeric context for the pattern of A with the factor (keep_numeric), nothing factored: spd_numeric_values(F) is
+// there to be written, spd_refactor_device() factors from it.  F comes from spd_symbolic of the same pattern.
+int spd_prepare_device(const CsrMatrix &A, SpdFactor &F) {
+  if ((int)F.children.size() != F.nfronts || F.n != A.n) return -1;
+  spd_release_device(F);
+  spd_release_numeric(F);
+  SpdNumericCtx *ctx = new SpdNumericCtx();
+  if (ctx->build(A, F, F.children) != 0) { delete ctx; return -1; }
+  F.keep_device = F.keep_numeric = true;
+  F.numeric = ctx;
+  return 0;
+}
+
 double *spd_numeric_values(SpdFactor &F) { return F.numeric ? F.numeric->d_aval : nullptr; }
 
 // the numeric phase again, from the values in spd_numeric_values(F); dev_W / dev_WT (borrowed) hold the new factor
 int spd_refactor_device(SpdFactor &F, void *stream, bool defer) {
   if (!F.numeric) return -1;
   if (F.numeric->factor(F, nullptr, nullptr, nullptr, (hipStream_t)stream, defer) != 0) return -1;
+  if (F.numeric->factor_only) return 0;
   F.dev_W = F.numeric->d_W;
   F.dev_WT = F.numeric->d_WT;
   F.dev_borrowed = true;

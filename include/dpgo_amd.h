@@ -348,8 +348,8 @@ int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dp
  * residual = |S x - theta x|) and `status` is decided from them:
  *   DPGO_CERT_NEGATIVE     theta < -eta / 2: x PROVES lambda_min(S) < -eta / 2, X is not certified;
  *   DPGO_CERT_NONNEGATIVE  otherwise, and residual <= tau (|S|_est + |theta|).  This is EVIDENCE, NOT PROOF: a converged
- *                          Ritz pair need not be the smallest one.  The reference gets its proof from a Cholesky
- *                          factorisation of S + eta I (STEP 1, :731-754), which this library does not have;
+ *                          Ritz pair need not be the smallest one.  The proof is a Cholesky factorisation of
+ *                          S + eta I (STEP 1, :731-754): dpgo_group_cert_factor / dpgo_group_verify below;
  *   DPGO_CERT_UNDECIDED    max_iters reached without either.
  * `stationarity` is |S X|_F, the norm of the Riemannian gradient at X: the certificate only means something at a
  * critical point.  Deviations: the block size is fixed to d (a block IS a pose-record array); the preconditioner is
@@ -382,6 +382,57 @@ int dpgo_group_certify(dpgo_group_t *grp, const double *X, int ld, const dpgo_ce
 int dpgo_group_cert_lambda(dpgo_group_t *grp, const double *X, int ld, double *Lambda);
 /* SV = S(X) V, V and SV (d+1)N x d in the layout of X (the operator of verify_solution, :444-447, alone) */
 int dpgo_group_cert_apply(dpgo_group_t *grp, const double *X, int ld, const double *V, int ldv, double *SV, int ldsv);
+/* ---- the proof: fast_verification STEP 1 (SESync_utils.cpp:731-754), a Cholesky factorisation of S + eta I ------------
+ * The factorisation exists exactly when the matrix is positive definite, so its success proves lambda_min(S) > -eta and a
+ * non-positive pivot proves lambda_min(S) <= -eta.  S + eta I is written on the device as a CSR matrix on the unknowns
+ * (d+1) p + r (pose p; r = 0 the translation, r = 1..d the rows of Y_p -- S acts alike on every column, so the matrix is
+ * (d+1)N x (d+1)N), one explicit dense (d+1) x (d+1) block per pair of poses M couples, and factored by the library's
+ * multifrontal Cholesky (nested dissection of the pose graph, MFMA fronts) in a factor-only mode: nothing is solved.
+ * The symbolic analysis runs first, on the host, once per group; if it predicts more device memory than
+ * max_factor_bytes (when > 0) or than half of what hipMemGetInfo reports free, nothing is allocated and the outcome is
+ * DPGO_CERT_FACTOR_SKIPPED with the predicted sizes filled in.  A non-positive pivot is an outcome, not an error: nothing
+ * is printed, and the next call factors again (the analysis and the device state do not depend on the values).
+ *
+ * What DPGO_CERT_PROVEN means.  It is a floating-point factorisation, as in the reference: its success proves that
+ * S + eta I + E is positive definite for some E with |E|_2 of the order n^(3/2) u |S|_2 (Higham, Accuracy and Stability
+ * of Numerical Algorithms, thm 10.7; n = (d+1)N, u = 2^-53), i.e. lambda_min(S) > -eta - |E|.  pivot_min, the smallest
+ * pivot d_kk, bounds lambda_min(S + eta I) from ABOVE (pivots are diagonal entries of Schur complements), so a tiny
+ * pivot_min says how close the call was.  And it says "X is a global minimum" ONLY where `stationarity` = |S X|_F is
+ * small: S is built from X whether or not X is a critical point.  The warning example is sphere2500's chordal
+ * initialisation on 4 nodes: lambda_min(S) = -5.65e-4, so eta = 1e-3 gives PROVEN -- at a point whose gradient norm
+ * |S X|_F is 265 and which is nowhere near a minimum (eta = 1e-5 gives NOT_PD there).  Read both numbers.
+ * Same restrictions as dpgo_group_certify (trivial loss, a group that hosts every node); the optimiser's state is
+ * untouched. */
+#define DPGO_CERT_PROVEN 3            /* only dpgo_group_verify returns it */
+#define DPGO_CERT_FACTOR_NOT_PD 0
+#define DPGO_CERT_FACTOR_PD 1
+#define DPGO_CERT_FACTOR_SKIPPED 2
+typedef struct dpgo_cert_factor {
+  int outcome, fronts, levels, max_front;   /* fronts / tree levels / largest front (rows) of the elimination tree */
+  long long factor_entries, factor_bytes;   /* sum (w + u) w over the fronts; device bytes of the numeric phase (every front
+                                               matrix at once, the value array, the maps): both predicted by the analysis */
+  double eta, pivot_min, pivot_max;         /* the pivot range of the fronts that factored (all of them for PD) */
+  double stationarity;                      /* |S X|_F */
+  double symbolic_s, numeric_s;             /* host seconds: the analysis (0 after a group's first call); matrix + factorisation */
+} dpgo_cert_factor_t;
+/* STEP 1 alone (SESync_utils.cpp:731-754).  eta: any finite shift.  -1 on bad arguments or a device error. */
+int dpgo_group_cert_factor(dpgo_group_t *grp, const double *X, int ld, double eta, long long max_factor_bytes,
+                           dpgo_cert_factor_t *factor);
+/* fast_verification (SESync_utils.cpp:721-830): STEP 1 with opts->eta, then STEP 2 only when it did not succeed.
+ *   FACTOR_PD       status = DPGO_CERT_PROVEN; the search does not run (iterations = 0, theta = residual = 0, x untouched),
+ *                   stationarity is filled;
+ *   FACTOR_NOT_PD   the search of dpgo_group_certify as it is (:756-826).  NEGATIVE stays NEGATIVE; a search that comes back
+ *                   NONNEGATIVE has just been refuted by the factorisation and is returned as UNDECIDED, theta and
+ *                   residual kept;
+ *   FACTOR_SKIPPED  the search's own status, unchanged: dpgo_group_certify's answer, named as such by factor->outcome.
+ * Arguments as for dpgo_group_certify. */
+int dpgo_group_verify(dpgo_group_t *grp, const double *X, int ld, const dpgo_cert_options_t *opts, long long max_factor_bytes,
+                      const double *V0, int ldv0, dpgo_cert_result_t *result, double *x, int ldx, dpgo_cert_factor_t *factor);
+/* Debug: the matrix that is factored, S + eta I, read back from the device value array of the factorisation: CSR with
+ * (d+1)N + 1 row pointers on the unknowns (d+1) g + r of the GLOBAL poses g, every stored block dense (structural zeros
+ * explicit), *nnz = (d+1)^2 blocks.  With ptr = col = val = NULL only *nnz is set; otherwise cap >= *nnz. */
+int dpgo_group_cert_matrix(dpgo_group_t *grp, const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap,
+                           long long *nnz);
 /* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
  * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
  * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:

@@ -188,8 +188,8 @@ class DPGOHashGroup {
   // block-size and ILDL arguments: LOBPCG on the certificate matrix S = M - Lambda(X), block size d, block-Jacobi
   // preconditioner (dpgo_group_certify).  theta: x' S x of the returned unit vector x ((d+1)N x 1); num_iters: LOBPCG
   // iterations.  Returns true when the search converged with theta >= -eta / 2 (DPGO_CERT_NONNEGATIVE) -- evidence, NOT
-  // proof, that X is a global minimiser: a converged Ritz pair need not be the smallest, and the reference's proof (a
-  // Cholesky factorisation of S + eta I) is not part of this library.  status (optional): the DPGO_CERT_* outcome, -1
+  // proof, that X is a global minimiser: a converged Ritz pair need not be the smallest; the proof (a Cholesky
+  // factorisation of S + eta I) is fast_verification below.  status (optional): the DPGO_CERT_* outcome, -1
   // when the call itself failed (robust loss, a group that does not host every node).
   bool verify_solution(const Matrix &X, Scalar eta, Scalar &theta, Matrix &x, int &num_iters, int *status = nullptr,
                        dpgo_cert_result_t *result = nullptr) const {
@@ -204,6 +204,29 @@ class DPGOHashGroup {
     if (status) *status = rc == 0 ? r.status : -1;
     if (result) *result = r;
     return rc == 0 && r.status == DPGO_CERT_NONNEGATIVE;
+  }
+  // fast_verification (C++/SESync/src/SESync_utils.cpp:721-830) without its ILDL arguments: STEP 1, the Cholesky
+  // factorisation of S + eta I on the device, and the LOBPCG search of verify_solution only when it did not succeed
+  // (dpgo_group_verify).  Returns true when the factorisation PROVED lambda_min(S) > -eta (DPGO_CERT_PROVEN; theta, x and
+  // num_iters are then 0 / untouched) -- which says "global minimiser" only where result->stationarity is small.
+  // max_factor_bytes > 0 caps the device memory of the factorisation (beyond it STEP 1 is skipped and the answer is
+  // verify_solution's).  status: the DPGO_CERT_* outcome, -1 when the call itself failed.
+  bool fast_verification(const Matrix &X, Scalar eta, Scalar &theta, Matrix &x, int &num_iters, int *status = nullptr,
+                         dpgo_cert_result_t *result = nullptr, dpgo_cert_factor_t *factor = nullptr,
+                         long long max_factor_bytes = 0) const {
+    dpgo_cert_options_t o;
+    dpgo_cert_options_default(&o);
+    o.eta = eta;
+    dpgo_cert_result_t r = {};
+    dpgo_cert_factor_t f = {};
+    x.resize(X.rows(), 1);
+    const int rc = dpgo_group_verify(h_, X.data(), X.rows(), &o, max_factor_bytes, nullptr, 0, &r, x.data(), x.rows(), &f);
+    theta = r.theta;
+    num_iters = r.iterations;
+    if (status) *status = rc == 0 ? r.status : -1;
+    if (result) *result = r;
+    if (factor) *factor = f;
+    return rc == 0 && r.status == DPGO_CERT_PROVEN;
   }
   const Graph &graph() const { return *graph_; }
   dpgo_group_t *handle() const { return h_; }
