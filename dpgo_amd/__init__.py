@@ -201,6 +201,10 @@ SYMBOLS = {
     "dpgo_debug_node_proximal": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Options), _DP, _DP, _DP]),
     "dpgo_debug_spd_solve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int]),
     "dpgo_debug_spd_stats": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.POINTER(C.c_long), _IP, _IP]),
+    "dpgo_debug_spd_factor": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "dpgo_debug_spd_factor_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _DP, _IP, C.POINTER(C.c_longlong), _IP, _IP,
+                                            _DP, _DP, _DP, _DP]),
+    "dpgo_debug_spd_factor_free": (None, [C.c_void_p]),
     "dpgo_debug_p2p_plan": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_pcm_options_default": (None, [C.c_void_p]),
@@ -450,6 +454,67 @@ def spd_stats(A_csr, leaf):
     if lib().dpgo_debug_spd_stats(A.shape[0], _ip(ptr), _ip(col), _dp(val), leaf, C.byref(nnz), C.byref(lv), C.byref(mf)) != 0:
         raise RuntimeError("spd_stats failed")
     return nnz.value, lv.value, mf.value
+
+
+def spd_factor_debug(A_csr, leaf, collapse=1, block=1, factor_only=False, refactor_values=None):
+    """The multifrontal factor of a CSR matrix, front by front (test hook, dpgo_debug_spd_factor).
+
+    It bypasses nothing: spd_factor(A, F, leaf, collapse, block) runs as a group calls it (quiet), with the numeric phase
+    on the device where there is one and on the host otherwise or under DPGO_SPD_HOST_FACTOR=1.  refactor_values: a second
+    value array in the order of A.tocsr() with sorted indices, factored afterwards through the kept numeric context
+    (keep_device + keep_numeric, spd_refactor_device -- the path of a Dynamic rescale and of the certificate).
+    factor_only: the certificate's route (spd_symbolic, spd_prepare_device, spd_refactor_device); verdicts and pivots only.
+
+    Returns a dict: status (0 factored, 1 not positive definite), fail_front, pivot_min, pivot_max, on_device, nfronts,
+    the per-front arrays w, u, parent, height, ldw, ldm, w_off, wt_off, the lists piv_idx / upd_idx (one array per front),
+    W / WT (flat, as SpdFactor holds them; None when the factorisation failed or factor_only), and with refactor_values
+    status2, fail_front2, pivot_min2, pivot_max2, W2, WT2."""
+    A = A_csr.tocsr()
+    A.sort_indices()
+    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    val2 = None
+    if refactor_values is not None:
+        val2 = np.ascontiguousarray(refactor_values, np.float64)
+        if val2.shape != val.shape:
+            raise ValueError("refactor_values must have one value per stored entry of A")
+    n = A.shape[0]
+    h = C.c_void_p()
+    if lib().dpgo_debug_spd_factor(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
+                                   int(collapse), int(block), int(bool(factor_only)), C.byref(h)) != 0:
+        raise RuntimeError("spd_factor_debug failed")
+    try:
+        get = lib().dpgo_debug_spd_factor_get
+        sizes = np.zeros(8, np.int64)
+        status = np.zeros(4, np.int32)
+        piv = np.zeros(4)
+        LLP = C.POINTER(C.c_longlong)
+        get(h, sizes.ctypes.data_as(LLP), _ip(status), _dp(piv), None, None, None, None, None, None, None, None)
+        nt = int(sizes[0])
+        fronts = np.zeros((nt, 6), np.int32)
+        offs = np.zeros((nt, 2), np.int64)
+        piv_idx = np.zeros(n, np.int32)
+        upd_idx = np.zeros(max(int(sizes[1]), 1), np.int32)
+        W = np.zeros(int(sizes[2])) if sizes[4] else None
+        WT = np.zeros(int(sizes[3])) if sizes[4] else None
+        W2 = np.zeros(int(sizes[2])) if sizes[5] else None
+        WT2 = np.zeros(int(sizes[3])) if sizes[5] else None
+        opt = lambda a: None if a is None or a.size == 0 else _dp(a)
+        get(h, None, None, None, _ip(fronts), offs.ctypes.data_as(LLP), _ip(piv_idx), _ip(upd_idx), opt(W), opt(WT), opt(W2),
+            opt(WT2))
+    finally:
+        lib().dpgo_debug_spd_factor_free(h)
+    w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
+    pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+    out = {"status": int(status[0]), "fail_front": int(status[1]), "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
+           "on_device": bool(sizes[7]), "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(),
+           "height": fronts[:, 3].copy(), "ldw": fronts[:, 4].copy(), "ldm": fronts[:, 5].copy(), "w_off": offs[:, 0].copy(),
+           "wt_off": offs[:, 1].copy(), "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
+           "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)], "W": W, "WT": WT}
+    if sizes[6]:
+        out.update(status2=int(status[2]), fail_front2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
+                   W2=W2, WT2=WT2)
+    return out
 
 
 class NodeGroup:

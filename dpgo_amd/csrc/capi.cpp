@@ -466,6 +466,127 @@ int dpgo_debug_spd_stats(int n, const int *ptr, const int *col, const double *va
   return 0;
 }
 
+// ---- test hook: the factor itself, front by front ----
+struct dpgo_spd_debug {
+  dpgo::SpdFactor F;
+  int status[2] = {-1, -1}, fail_front[2] = {-1, -1};   // [0] the factorisation, [1] the one through the kept context
+  double pivots[4] = {0, 0, 0, 0};
+  bool has_second = false, factor_only = false, on_device = false;
+  std::vector<int> height;
+  std::vector<double> W, WT, W2, WT2;
+  ~dpgo_spd_debug() {   // (a factor does not release what it owns by itself: spd.h)
+    dpgo::spd_release_device(F);
+    dpgo::spd_release_numeric(F);
+  }
+};
+
+namespace {
+bool spd_debug_device_numeric() {
+  int ndev = 0;
+  return !dpgo::settings().spd_host_factor && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+}
+// rc of spd_factor / spd_refactor_device -> 0 factored, 1 not positive definite, -1 error
+int spd_debug_status(int rc, const dpgo::SpdFactor &F) { return rc == 0 ? 0 : (F.not_pd ? 1 : -1); }
+// W / WT of F to the host: the host vectors where the numeric phase filled them, else the device copies
+int spd_debug_fetch(const dpgo::SpdFactor &F, std::vector<double> &W, std::vector<double> &WT) {
+  const int nt = F.nfronts;
+  if (!F.dev_W) { W = F.W; WT = F.WT; return 0; }
+  W.assign(F.w_off[nt], 0.0);
+  WT.assign(F.wt_off[nt], 0.0);
+  if (!W.empty() && hipMemcpy(W.data(), F.dev_W, sizeof(double) * W.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (!WT.empty() && hipMemcpy(WT.data(), F.dev_WT, sizeof(double) * WT.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return 0;
+}
+}  // namespace
+
+int dpgo_debug_spd_factor(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int factor_only, dpgo_spd_debug_t **out) {
+  if (!out || !ptr || !col || !val || n <= 0) return -1;
+  *out = nullptr;
+  return guarded([&] {
+    dpgo::CsrMatrix A;
+    A.n = n;
+    A.ptr.assign(ptr, ptr + n + 1);
+    A.col.assign(col, col + ptr[n]);
+    A.val.assign(val, val + ptr[n]);
+    std::unique_ptr<dpgo_spd_debug> h(new dpgo_spd_debug());
+    dpgo::SpdFactor &F = h->F;
+    h->factor_only = factor_only != 0;
+    h->on_device = spd_debug_device_numeric();
+    F.quiet = true;
+    auto record = [&](int k, int rc) {
+      h->status[k] = spd_debug_status(rc, F);
+      h->fail_front[k] = F.not_pd ? F.fail_front : -1;
+      h->pivots[2 * k] = F.pivot_min;
+      h->pivots[2 * k + 1] = F.pivot_max;
+    };
+    if (h->factor_only && h->on_device) {
+      // the certificate's route (cert.cpp): analysis, context, values written on the device, numeric phase from them
+      F.factor_only = true;
+      if (dpgo::spd_symbolic(A, F, leaf, collapse, block) != 0 || dpgo::spd_prepare_device(A, F) != 0) return -1;
+      for (int k = 0; k < (refactor_val ? 2 : 1); k++) {
+        const double *v = k == 0 ? val : refactor_val;
+        if (hipMemcpy(dpgo::spd_numeric_values(F), v, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        record(k, dpgo::spd_refactor_device(F));
+      }
+      h->has_second = refactor_val != nullptr;
+    } else {
+      F.keep_numeric = refactor_val != nullptr && h->on_device;   // (Group::factor_tt for a Dynamic rescale)
+      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/F.keep_numeric);
+      record(0, rc);
+      if (rc == 0 && !h->factor_only && spd_debug_fetch(F, h->W, h->WT) != 0) return -1;
+      if (refactor_val) {   // (also behind a non-positive pivot: the context does not depend on the values)
+        int rc2;
+        if (F.numeric) {   // the kept context: new values on the device, the kernels again
+          if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+          rc2 = dpgo::spd_refactor_device(F);
+        } else {           // no GPU: spd_refactor redoes the factorisation on the host
+          A.val.assign(refactor_val, refactor_val + ptr[n]);
+          rc2 = dpgo::spd_refactor(A, F);
+        }
+        record(1, rc2);
+        h->has_second = true;
+        if (rc2 == 0 && !h->factor_only && spd_debug_fetch(F, h->W2, h->WT2) != 0) return -1;
+      }
+    }
+    if (h->status[0] < 0 || (h->has_second && h->status[1] < 0)) return -1;
+    h->height.assign(F.nfronts, 0);
+    for (int f = 0; f < F.nfronts; f++)
+      if (F.parent[f] >= 0) h->height[F.parent[f]] = std::max(h->height[F.parent[f]], h->height[f] + 1);
+    *out = h.release();
+    return 0;
+  });
+}
+
+int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
+                              long long *offsets, int *piv_idx, int *upd_idx, double *W, double *WT, double *W2, double *WT2) {
+  if (!h) return -1;
+  const dpgo::SpdFactor &F = h->F;
+  const int nt = F.nfronts;
+  if (sizes) {
+    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = F.w_off[nt]; sizes[3] = F.wt_off[nt];
+    sizes[4] = (long long)h->W.size(); sizes[5] = (long long)h->W2.size(); sizes[6] = h->has_second; sizes[7] = h->on_device;
+  }
+  if (status) { status[0] = h->status[0]; status[1] = h->fail_front[0]; status[2] = h->status[1]; status[3] = h->fail_front[1]; }
+  if (pivots) std::copy(h->pivots, h->pivots + 4, pivots);
+  for (int f = 0; f < nt; f++) {
+    if (fronts) {
+      int *q = fronts + 6 * f;
+      q[0] = F.w[f]; q[1] = F.u[f]; q[2] = F.parent[f]; q[3] = h->height[f]; q[4] = F.ldw[f]; q[5] = F.ldm[f];
+    }
+    if (offsets) { offsets[2 * f] = F.w_off[f]; offsets[2 * f + 1] = F.wt_off[f]; }
+  }
+  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
+  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
+  if (W) std::copy(h->W.begin(), h->W.end(), W);
+  if (WT) std::copy(h->WT.begin(), h->WT.end(), WT);
+  if (W2) std::copy(h->W2.begin(), h->W2.end(), W2);
+  if (WT2) std::copy(h->WT2.begin(), h->WT2.end(), WT2);
+  return 0;
+}
+
+void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h) { delete h; }
+
 int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const double *in, int ld_in, double *out,
                            int ld_out) {
   return guarded([&] { return h->grp->debug_apply(local, op, in, ld_in, out, ld_out); });

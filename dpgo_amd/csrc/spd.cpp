@@ -728,6 +728,7 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
   std::vector<std::vector<int>> asm_lists(F.total_pos);
   int fail = 0;
   const int BIG = 384;
+  double piv_lo = 1e300, piv_hi = 0.0;   // the pivot range of the fronts that factored (as the device numeric phase records it)
 
   auto factor_front = [&](int f, std::vector<int> &loc, std::vector<double> &Fm, std::vector<double> &Linv,
                           bool inner_par) {
@@ -764,15 +765,19 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
     }
     // blocked right-looking partial Cholesky of the first w columns (lower triangle, row-major)
     const int NB = 48;
-    for (int kb = 0; kb < w && !fail; kb += NB) {
+    double dmin = 1e300, dmax = 0.0;
+    bool bad = false;
+    for (int kb = 0; kb < w && !bad; kb += NB) {
       const int ke = std::min(kb + NB, w);
       for (int k = kb; k < ke; k++) {   // diagonal block, unblocked
         double dkk = Fm[(size_t)k * m + k];
         if (!(dkk > 0.0)) {
           if (!F.quiet) fprintf(stderr, "[dpgo_amd] ERROR: spd_factor: non-positive pivot %g (front %d, col %d)\n", dkk, f, k);
-          fail = 1;
+          bad = true;
           break;
         }
+        dmin = std::min(dmin, dkk);
+        dmax = std::max(dmax, dkk);
         const double lkk = std::sqrt(dkk), inv = 1.0 / lkk;
         Fm[(size_t)k * m + k] = lkk;
         for (int i = k + 1; i < ke; i++) Fm[(size_t)i * m + k] *= inv;
@@ -781,7 +786,7 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
           for (int j = k + 1; j <= i; j++) Fm[(size_t)i * m + j] -= lik * Fm[(size_t)j * m + k];
         }
       }
-      if (fail) break;
+      if (bad) break;
       // panel: rows below the block, L[i, kb:ke] = F[i, kb:ke] L_kk^-T
 #pragma omp parallel for schedule(static) if (inner_par)
       for (int i = ke; i < m; i++) {
@@ -807,7 +812,17 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
         }
       }
     }
-    if (fail) return;
+#pragma omp critical(spd_factor_verdict)
+    {
+      if (bad) {
+        fail = 1;
+        if (F.fail_front < 0 || f < F.fail_front) F.fail_front = f;
+      } else {
+        piv_lo = std::min(piv_lo, dmin);
+        piv_hi = std::max(piv_hi, dmax);
+      }
+    }
+    if (bad) return;
     if (u) {   // Schur complement for the parent
       Umat[f].resize((size_t)u * u);
       for (int a = 0; a < u; a++)
@@ -914,6 +929,11 @@ static int spd_factor_impl(const CsrMatrix &A, SpdFactor &F, int leaf, int colla
       std::vector<double> Fm, Linv;
       for (int f : big) factor_front(f, loc, Fm, Linv, true);
     }
+  }
+  if (!on_device) {
+    F.not_pd = fail != 0;
+    F.pivot_min = piv_hi > 0.0 ? piv_lo : 0.0;
+    F.pivot_max = piv_hi;
   }
   if (fail) return -1;
   F.children = children;

@@ -52,7 +52,7 @@ struct SpdFactorData {
   int total_pos = 0, total_upd = 0, max_front = 0;
   // keep_device: the numeric phase leaves W / WT on the GPU (dev_W / dev_WT, same per-front layout as W / WT, owned by
   // the factor until spd_release_device) and does not fill the host copies -- for callers that only solve on the device
-  // smallest / largest pivot d_kk of the factorisation (device numeric phase; 0 / 0 when not recorded): their ratio is a
+  // smallest / largest pivot d_kk of the factorisation (0 / 0 when not recorded): their ratio is a
   // lower bound of the condition number -- W_s holds the explicit L11^-1, so a huge ratio costs digits in every solve
   double pivot_min = 0.0, pivot_max = 0.0;
   bool keep_device = false;
@@ -65,7 +65,8 @@ struct SpdFactorData {
   // factor_only (spd_prepare_device): the numeric phase ends with the verdict and the pivot range -- W / WT are neither
   // allocated nor written, and nothing can be solved with the factor
   bool quiet = false, factor_only = false;
-  bool not_pd = false;   // the last device numeric phase met a non-positive pivot (a -1 with this unset is a device error)
+  bool not_pd = false;   // the last numeric phase met a non-positive pivot (a -1 with this unset is a device error)
+  int fail_front = -1;   // ... and the front it named (one of them, when several fronts of a level failed); -1 when not_pd is unset
   struct SpdNumericCtx *numeric = nullptr;
   int leaf = 32, collapse = 0, block = 1;   // the parameters this factor was built with (spd_refactor's host path repeats them)
   double *dev_W = nullptr, *dev_WT = nullptr;

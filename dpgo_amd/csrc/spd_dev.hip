@@ -1085,6 +1085,7 @@ int SpdNumericCtx::finish(SpdFactor &F, bool wait) {
   }
   FA_OK(hipGetLastError());
   F.not_pd = fail != 0;
+  F.fail_front = fail - 1;
   if (fail) {
     if (!F.quiet) fprintf(stderr, "[dpgo_amd] ERROR: spd_factor (device): non-positive pivot in front %d\n", fail - 1);
     return -1;

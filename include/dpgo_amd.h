@@ -453,6 +453,31 @@ int dpgo_debug_spd_solve(int n, const int *ptr, const int *col, const double *va
 /* Host: size of the multifrontal factor of a CSR SPD matrix for a given nested-dissection leaf size. */
 int dpgo_debug_spd_stats(int n, const int *ptr, const int *col, const double *val, int leaf, long *nnz, int *levels,
                          int *max_front);
+/* The factor itself, front by front (tests/test_factor_fronts_host.py, tests/test_gpu_factor_fronts.py).  Bypasses nothing:
+ * spd_factor(A, F, leaf, collapse, block) as a group calls it (quiet: a non-positive pivot is an answer, nothing is
+ * printed), the numeric phase on the device where there is one (DPGO_SPD_HOST_FACTOR=1 or no device: the host loop).
+ * refactor_val (optional): a second value array of the same pattern, factored after the first through the KEPT context
+ *   (keep_device + keep_numeric, the values copied into spd_numeric_values, spd_refactor_device: the path of a Dynamic
+ *   rescale and of the certificate); without a device spd_refactor's host path.
+ * factor_only: the certificate's route (spd_symbolic, spd_prepare_device, spd_refactor_device; collapse < 1 counts as 1):
+ *   the verdicts and the pivot ranges only, W / WT are never allocated.  Without a device: spd_factor, W / WT dropped.
+ * Returns 0 and a handle when every factorisation ended with a verdict, -1 on an error.
+ * dpgo_debug_spd_factor_get copies out what the handle holds; every pointer may be NULL:
+ *   sizes[8]    nfronts, |upd_idx|, |W|, |WT| (doubles, padding included), doubles held of the first factor's W (0: failed
+ *               or factor_only), of the second, whether a second factorisation ran, whether the device numeric phase ran
+ *   status[4]   first verdict (0 factored, 1 not positive definite), the front the numeric phase named (-1: none); the same
+ *               for the second factorisation (-1, -1 when none ran)
+ *   pivots[4]   pivot_min, pivot_max of the first and of the second factorisation
+ *   fronts      6 ints per front: w, u, parent, height, ldw, ldm;  offsets: 2 per front: w_off, wt_off
+ *   piv_idx     n matrix indices, the fronts' pivots one after the other (the elimination order: fronts are in post-order)
+ *   upd_idx     the fronts' update rows one after the other (u each)
+ *   W, WT       SpdFactor::W / WT as the first numeric phase left them; W2, WT2: the second's */
+typedef struct dpgo_spd_debug dpgo_spd_debug_t;
+int dpgo_debug_spd_factor(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int factor_only, dpgo_spd_debug_t **out);
+int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
+                              long long *offsets, int *piv_idx, int *upd_idx, double *W, double *WT, double *W2, double *WT2);
+void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h);
 /* Host: the neighbour-to-neighbour exchange plan of `rank` (what dpgo_comm_exchange uses with more than one rank) from
  * every rank's exported and needed (node, pose) keys (dpgo_graph_exchange_plan of its nodes): per peer 5 ints (rank,
  * send_off, send_cnt, recv_off, recv_cnt), the send and receive keys (node, pose interleaved, concatenated over the peers
