@@ -205,6 +205,14 @@ SYMBOLS = {
     "dpgo_debug_spd_factor_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _DP, _IP, C.POINTER(C.c_longlong), _IP, _IP,
                                             _DP, _DP, _DP, _DP]),
     "dpgo_debug_spd_factor_free": (None, [C.c_void_p]),
+    "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
+                                               C.POINTER(C.c_void_p)]),
+    "dpgo_debug_spd_solver_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _IP, _IP, _IP, _IP, _IP]),
+    "dpgo_debug_spd_solver_fine_root": (C.c_int, [C.c_void_p, C.c_ulonglong]),
+    "dpgo_debug_spd_solver_run": (C.c_int, [C.c_void_p, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                            C.c_double, C.c_int, _DP, _DP]),
+    "dpgo_debug_spd_solver_refactor": (C.c_int, [C.c_void_p, _DP]),
+    "dpgo_debug_spd_solver_free": (None, [C.c_void_p]),
     "dpgo_debug_p2p_plan": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_pcm_options_default": (None, [C.c_void_p]),
@@ -515,6 +523,96 @@ def spd_factor_debug(A_csr, leaf, collapse=1, block=1, factor_only=False, refact
         out.update(status2=int(status[2]), fail_front2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
                    W2=W2, WT2=WT2)
     return out
+
+
+class SpdSolverDebug:
+    """The device multifrontal solve on a given CSR matrix (test hook, dpgo_debug_spd_solver_*): spd_factor and
+    SpdSolverDev::upload(dof, d, node_of_unknown) as a group runs them for G_tt (dof 1) and G_RR + lambda I (dof d), then
+    spd_run.  Raises RuntimeError("no HIP device") without a GPU.
+
+    plan()      what upload() decided: fused_root, root_sym, root_rows, root_fine_rows, root_fine_below, stream_once, the
+                lists fwd / bwd and the entries root, root_fine, root_rows of dicts (rows, nwide, nnarrow, wcount, ncount --
+                the last two per local node), and the front table w, u, parent, height, piv_idx, upd_idx
+    run(...)    out <- scale * A^-1 in on the unknowns of the live nodes; returns the out array ((d + 1) d doubles per
+                record), or None where spd_run itself refuses (in place with fused roots)
+    refactor()  new values through the kept numeric context, then repack() (keep_numeric=True only)"""
+
+    def __init__(self, A_csr, leaf, collapse=1, block=1, d=3, dof=1, node_of_unknown=None, keep_numeric=False):
+        A = A_csr.tocsr()
+        A.sort_indices()
+        n = A.shape[0]
+        ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+        val = np.ascontiguousarray(A.data, np.float64)
+        node = np.zeros(n, np.int32) if node_of_unknown is None else np.ascontiguousarray(node_of_unknown, np.int32)
+        if node.shape != (n,):
+            raise ValueError("node_of_unknown must have one entry per unknown")
+        self._h = C.c_void_p()
+        self.n, self.d, self.dof, self.nval = n, int(d), int(dof), len(val)
+        rc = lib().dpgo_debug_spd_solver_create(n, _ip(ptr), _ip(col), _dp(val), int(leaf), int(collapse), int(block), int(d),
+                                                int(dof), _ip(node), int(bool(keep_numeric)), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise RuntimeError("no HIP device" if rc == -2 else "dpgo_debug_spd_solver_create failed")
+        self.records = (n + self.dof - 1) // self.dof
+        self.shape = (self.records * (self.d + 1), self.d)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dpgo_debug_spd_solver_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def plan(self):
+        get = lib().dpgo_debug_spd_solver_plan
+        LLP = C.POINTER(C.c_longlong)
+        sizes = np.zeros(8, np.int64)
+        flags = np.zeros(8, np.int32)
+        get(self._h, sizes.ctypes.data_as(LLP), _ip(flags), None, None, None, None, None)
+        nt, nupd, nf, nb, nn = (int(v) for v in sizes[:5])
+        L = nf + nb + 3
+        levels = np.zeros((L, 3), np.int32)
+        counts = np.zeros((L, nn, 2), np.int32)
+        fronts = np.zeros((nt, 4), np.int32)
+        piv_idx = np.zeros(self.n, np.int32)
+        upd_idx = np.zeros(max(nupd, 1), np.int32)
+        get(self._h, None, None, _ip(levels), _ip(counts), _ip(fronts), _ip(piv_idx), _ip(upd_idx))
+        lv = [dict(rows=int(levels[l, 0]), nwide=int(levels[l, 1]), nnarrow=int(levels[l, 2]), wcount=counts[l, :, 0].copy(),
+                   ncount=counts[l, :, 1].copy()) for l in range(L)]
+        w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
+        pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+        return {"fused_root": bool(flags[0]), "root_sym": bool(flags[1]), "root_rows": int(flags[2]),
+                "root_fine_rows": int(flags[3]), "root_fine_below": int(flags[4]), "stream_once": bool(flags[5]),
+                "nnodes": nn, "fwd": lv[:nf], "bwd": lv[nf:nf + nb], "root": lv[-3], "root_fine": lv[-2], "root_rows_level": lv[-1],
+                "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(), "height": fronts[:, 3].copy(),
+                "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
+                "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)]}
+
+    def fine_root_for(self, nodes):
+        return bool(lib().dpgo_debug_spd_solver_fine_root(self._h, int(nodes)))
+
+    def run(self, rhs, out, mask=~0, mask_word=None, class_of=None, scale=1.0, in_place=False):
+        a = np.ascontiguousarray(rhs, np.float64)
+        o = np.ascontiguousarray(out, np.float64).copy()
+        if a.shape != self.shape or o.shape != self.shape:
+            raise ValueError("record arrays must be %r" % (self.shape,))
+        word = None if mask_word is None else C.byref(C.c_ulonglong(int(mask_word) & (2 ** 64 - 1)))
+        cls = None if class_of is None else C.byref(C.c_ulonglong(int(class_of) & (2 ** 64 - 1)))
+        rc = lib().dpgo_debug_spd_solver_run(self._h, int(mask) & (2 ** 64 - 1), word, cls, float(scale), int(bool(in_place)),
+                                             _dp(a), _dp(o))
+        if rc == -2:
+            return None
+        if rc != 0:
+            raise RuntimeError("dpgo_debug_spd_solver_run failed")
+        return o
+
+    def refactor(self, values):
+        v = np.ascontiguousarray(values, np.float64)
+        if v.shape != (self.nval,):
+            raise ValueError("one value per stored entry of A")
+        rc = lib().dpgo_debug_spd_solver_refactor(self._h, _dp(v))
+        if rc != 0:
+            raise RuntimeError("not positive definite" if rc == 1 else "dpgo_debug_spd_solver_refactor failed")
 
 
 class NodeGroup:

@@ -587,6 +587,141 @@ int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *
 
 void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h) { delete h; }
 
+// ---- test hook: the device solve (spd_solve.cpp) on a given matrix ----
+using dpgo::DeviceError;   // (what HIP_CHECK throws)
+struct dpgo_spd_solver_debug {
+  dpgo::SpdSolverDev S;
+  int n = 0, d = 0, dof = 0, nnodes = 1;
+  size_t nval = 0, len = 0;   // stored entries of A; doubles of a record array
+  std::vector<int> height;
+  hipStream_t st = nullptr;
+  dpgo::DevBuf<double> in, out;
+  dpgo::DevBuf<dpgo::NodeBits> word;
+  ~dpgo_spd_solver_debug() { if (st) (void)hipStreamDestroy(st); }
+};
+
+int dpgo_debug_spd_solver_create(int n, const int *ptr, const int *col, const double *val, int leaf, int collapse, int block,
+                                 int d, int dof, const int *node_of_unknown, int keep_numeric, dpgo_spd_solver_debug_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!ptr || !col || !val || !node_of_unknown || n <= 0 || (d != 2 && d != 3) || (dof != 1 && dof != d)) return -1;
+  for (int i = 0; i < n; i++)
+    if (node_of_unknown[i] < 0 || node_of_unknown[i] >= dpgo::MAX_LOCAL_NODES) return -1;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -2;   // the solve has no host form
+  const dpgo::Settings &s = dpgo::settings();
+  if (keep_numeric && (!s.spd_device_panels || s.spd_host_factor)) return -1;   // (Group::refactor_tt keeps the context under the same condition)
+  return guarded([&] {
+    dpgo::CsrMatrix A;
+    A.n = n;
+    A.ptr.assign(ptr, ptr + n + 1);
+    A.col.assign(col, col + ptr[n]);
+    A.val.assign(val, val + ptr[n]);
+    std::unique_ptr<dpgo_spd_solver_debug> h(new dpgo_spd_solver_debug());
+    h->n = n; h->d = d; h->dof = dof; h->nval = A.val.size();
+    h->len = (size_t)((n + dof - 1) / dof) * (d + 1) * d;   // (a last record may hold fewer than dof unknowns)
+    std::vector<int> node(node_of_unknown, node_of_unknown + n);
+    for (int a : node) h->nnodes = std::max(h->nnodes, a + 1);
+    dpgo::SpdFactor &F = h->S.F;
+    F.keep_numeric = keep_numeric != 0;
+    if (dpgo::spd_factor(A, F, leaf, collapse, block, s.spd_device_panels) != 0) return -1;
+    h->height.assign(F.nfronts, 0);
+    for (int f = 0; f < F.nfronts; f++)
+      if (F.parent[f] >= 0) h->height[F.parent[f]] = std::max(h->height[F.parent[f]], h->height[f] + 1);
+    h->S.upload(dof, d, node);
+    HIP_CHECK(hipStreamCreate(&h->st));
+    h->in.alloc(h->len);
+    h->out.alloc(h->len);
+    h->word.alloc(1);
+    *out = h.release();
+    return 0;
+  });
+}
+
+int dpgo_debug_spd_solver_plan(const dpgo_spd_solver_debug_t *h, long long *sizes, int *flags, int *levels, int *node_counts,
+                               int *fronts, int *piv_idx, int *upd_idx) {
+  if (!h) return -1;
+  const dpgo::SpdFactor &F = h->S.F;
+  const dpgo::SpdPlanInfo I = h->S.plan_info();
+  const int nt = F.nfronts, nn = h->nnodes;
+  if (sizes) {
+    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = (long long)I.fwd.size(); sizes[3] = (long long)I.bwd.size();
+    sizes[4] = nn; sizes[5] = h->n; sizes[6] = (long long)h->len; sizes[7] = (long long)h->nval;
+  }
+  if (flags) {
+    flags[0] = I.fused_root; flags[1] = I.root_sym; flags[2] = I.root.rows; flags[3] = I.root_fine_rows;
+    flags[4] = I.root_fine_below; flags[5] = I.stream_once; flags[6] = h->dof; flags[7] = h->d;
+  }
+  std::vector<const dpgo::SpdPlanInfo::Level *> all;
+  for (const auto &v : I.fwd) all.push_back(&v);
+  for (const auto &v : I.bwd) all.push_back(&v);
+  all.push_back(&I.root); all.push_back(&I.root_fine); all.push_back(&I.root_rows);
+  for (size_t l = 0; l < all.size(); l++) {
+    const dpgo::SpdPlanInfo::Level &v = *all[l];
+    if (levels) { levels[3 * l] = v.rows; levels[3 * l + 1] = v.nwide; levels[3 * l + 2] = v.nnarrow; }
+    if (node_counts)
+      for (int a = 0; a < nn; a++) {   // (a level nobody built -- no fused root, no finer class -- has no nodes: zeros)
+        node_counts[(l * nn + a) * 2] = a < (int)v.wcount.size() ? v.wcount[a] : 0;
+        node_counts[(l * nn + a) * 2 + 1] = a < (int)v.ncount.size() ? v.ncount[a] : 0;
+      }
+  }
+  if (fronts)
+    for (int f = 0; f < nt; f++) { fronts[4 * f] = F.w[f]; fronts[4 * f + 1] = F.u[f]; fronts[4 * f + 2] = F.parent[f]; fronts[4 * f + 3] = h->height[f]; }
+  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
+  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
+  return 0;
+}
+
+int dpgo_debug_spd_solver_fine_root(const dpgo_spd_solver_debug_t *h, unsigned long long nodes) {
+  if (!h) return -1;
+  return h->S.fine_root_for(nodes) ? 1 : 0;
+}
+
+int dpgo_debug_spd_solver_run(dpgo_spd_solver_debug_t *h, unsigned long long mask_v, const unsigned long long *mask_word,
+                              const unsigned long long *class_of, double scale, int in_place, const double *in, double *out) {
+  if (!h || !in || !out || (scale != 1.0 && scale != -1.0)) return -1;
+  return guarded([&] {
+    // the out array first: what the solve leaves alone is what the caller put there (in place: the in array is both)
+    HIP_CHECK(hipMemcpy(h->in.p, in, sizeof(double) * h->len, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(h->out.p, out, sizeof(double) * h->len, hipMemcpyHostToDevice));
+    dpgo::NodeMask mask{mask_v, nullptr};
+    if (mask_word) {
+      HIP_CHECK(hipMemcpy(h->word.p, mask_word, sizeof(dpgo::NodeBits), hipMemcpyHostToDevice));
+      mask.p = h->word.p;
+    }
+    const dpgo::NodeBits cls = class_of ? *class_of : 0;
+    double *res = in_place ? h->in.p : h->out.p;
+    try {
+      dpgo::spd_run(h->d, h->st, h->S, mask, h->in.p, res, scale, class_of ? &cls : nullptr);
+    } catch (const dpgo::DeviceError &) {
+      return -2;   // spd_run's own refusal (in == out with fused roots); nothing was launched
+    }
+    HIP_CHECK(hipStreamSynchronize(h->st));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out, res, sizeof(double) * h->len, hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+int dpgo_debug_spd_solver_refactor(dpgo_spd_solver_debug_t *h, const double *val) {
+  if (!h || !val) return -1;
+  return guarded([&] {
+    dpgo::SpdFactor &F = h->S.F;
+    double *dst = dpgo::spd_numeric_values(F);
+    if (!dst) return -1;   // (not created with keep_numeric)
+    // what Group::rescale_device does behind k_rescale_apply: the new values are on the device, the numeric phase and the
+    // panels follow on the same stream
+    HIP_CHECK(hipMemcpyAsync(dst, val, sizeof(double) * h->nval, hipMemcpyHostToDevice, h->st));
+    if (dpgo::spd_refactor_device(F, (void *)h->st, true) != 0) return -1;
+    if (h->S.repack(h->st) != 0) return -1;
+    if (dpgo::spd_refactor_finish(F, true) != 0) return F.not_pd ? 1 : -1;
+    HIP_CHECK(hipStreamSynchronize(h->st));
+    return 0;
+  });
+}
+
+void dpgo_debug_spd_solver_free(dpgo_spd_solver_debug_t *h) { delete h; }
+
 int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const double *in, int ld_in, double *out,
                            int ld_out) {
   return guarded([&] { return h->grp->debug_apply(local, op, in, ld_in, out, ld_out); });

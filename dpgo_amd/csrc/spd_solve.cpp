@@ -481,6 +481,25 @@ bool SpdSolverDev::fine_root_for(NodeBits v) const {
   return live_tiles * P.root_level.rows / 64 < P.root_fine_below;
 }
 
+SpdPlanInfo SpdSolverDev::plan_info() const {
+  const Plan &P = *plan_;
+  auto level = [](const Plan::Level &v) {
+    SpdPlanInfo::Level o;
+    o.rows = v.rows; o.nwide = v.nwide; o.nnarrow = v.nnarrow; o.wcount = v.wcount; o.ncount = v.ncount;
+    return o;
+  };
+  SpdPlanInfo I;
+  I.fused_root = P.fused_root; I.root_sym = P.root_sym; I.stream_once = P.stream_once;
+  I.dof = P.dof; I.root_fine_rows = P.root_fine_rows; I.root_fine_below = P.root_fine_below;
+  for (const auto &v : P.fwd_levels) I.fwd.push_back(level(v));
+  for (const auto &v : P.bwd_levels) I.bwd.push_back(level(v));
+  I.root = level(P.root_level);
+  I.root_fine = level(P.root_fine_level);
+  I.root_rows = level(P.root_rows_level);
+  I.nnodes = (int)(I.fwd.empty() ? P.root_level.wcount.size() : I.fwd[0].wcount.size());
+  return I;
+}
+
 // out <- scale * A^-1 in (the unknowns' entries of the records; everything else in `out` is left alone).
 // The forward sweep only reads `in`, the backward sweep only touches `out`: in == out solves in place.
 void spd_run(int d, hipStream_t st, SpdSolverDev &S, NodeMask mask, double *in, double *out, double scale, const NodeBits *class_of) {

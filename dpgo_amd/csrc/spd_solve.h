@@ -20,6 +20,15 @@ void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec);
 // a warning on stderr when F's pivots span so many orders of magnitude that its solves lose digits
 void warn_conditioning(const char *what, const SpdFactor &F);
 
+// What upload() decided, for the tests to read back (dpgo_debug_spd_solver_plan): a launch's tile class and counts
+struct SpdPlanInfo {
+  struct Level { int rows = 0, nwide = 0, nnarrow = 0; std::vector<int> wcount, ncount; };   // (wcount / ncount: per local node)
+  bool fused_root = false, root_sym = false, stream_once = false;
+  int dof = 0, nnodes = 0, root_fine_rows = 0, root_fine_below = 0;
+  std::vector<Level> fwd, bwd;
+  Level root, root_fine, root_rows;   // the fused roots' launch, its finer class, the triangle's block rows (k_root_combine)
+};
+
 class SpdSolverDev {
  public:
   SpdFactor F;   // host copy kept for sizes / host solves
@@ -31,6 +40,7 @@ class SpdSolverDev {
   int repack(hipStream_t st);   // the panels again from F.dev_W / F.dev_WT (same pattern, new values)
   // the finer tile class of the fused roots for a launch over the nodes `v` (few live roots)
   bool fine_root_for(NodeBits v) const;
+  SpdPlanInfo plan_info() const;
 
  private:
   struct Plan;   // device buffers and tile plan (spd_solve.cpp)

@@ -478,6 +478,38 @@ int dpgo_debug_spd_factor(int n, const int *ptr, const int *col, const double *v
 int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
                               long long *offsets, int *piv_idx, int *upd_idx, double *W, double *WT, double *W2, double *WT2);
 void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h);
+/* The device solve on a given matrix (tests/test_gpu_solve_tiles.py): an SpdSolverDev built as a group builds its own --
+ * spd_factor(A, F, leaf, collapse, block) with the factor left on the device unless DPGO_SPD_DEVICE_PANELS=0, then
+ * upload(dof, d, node_of_unknown) -- and spd_run on it.  The hook calls what exists; it adds nothing to spd_run or the kernels.
+ * create    d in {2, 3}, dof in {1, d} (1: unknown i is the translation row of record i; d: the rotation row i % d of record
+ *           i / d), node_of_unknown[n]: the local node (< 64) of every unknown -- unknowns of different nodes must not be
+ *           coupled; keep_numeric: the numeric context stays (a Dynamic rescale's G_tt), which refactor needs.
+ *           Returns 0, -1 on a bad argument or a failed factorisation, -2 without a HIP device (nothing is touched).
+ * plan      what upload() decided; every pointer may be NULL.  L = sizes[2] + sizes[3] + 3 launches: the forward levels, the
+ *           backward levels, then the fused roots, their finer class and the triangle's block rows.
+ *   sizes[8]     nfronts, |upd_idx|, forward levels, backward levels, local nodes, n, doubles of a record array, stored entries
+ *   flags[8]     fused_root, root_sym, tile height of the roots, root_fine_rows, root_fine_below, stream_once, dof, d
+ *   levels       3 ints per launch: rows (height of its wide tiles), nwide, nnarrow
+ *   node_counts  per launch and local node 2 ints: wcount, ncount
+ *   fronts       4 ints per front: w, u, parent, height;  piv_idx / upd_idx as dpgo_debug_spd_factor_get gives them
+ * fine_root 1 / 0: SpdSolverDev::fine_root_for(nodes)
+ * run       in, out: host record arrays, (d + 1) x d doubles per record.  out is uploaded first (the solve writes the
+ *           unknowns of the live nodes and nothing else) and read back.  mask_word (optional): the value of the device mask
+ *           word (NodeMask::p); class_of (optional): the node set the roots' tile class is chosen for; scale: +1 or -1;
+ *           in_place: in == out on the device (out receives the array).  Returns 0, -1 on an error, -2 when spd_run itself
+ *           refuses (in place with fused roots).
+ * refactor  new values (the order of create's val) to the device, spd_refactor_device, repack().  Returns 0, 1 when the new
+ *           matrix is not positive definite, -1 on an error (also: created without keep_numeric). */
+typedef struct dpgo_spd_solver_debug dpgo_spd_solver_debug_t;
+int dpgo_debug_spd_solver_create(int n, const int *ptr, const int *col, const double *val, int leaf, int collapse, int block,
+                                 int d, int dof, const int *node_of_unknown, int keep_numeric, dpgo_spd_solver_debug_t **out);
+int dpgo_debug_spd_solver_plan(const dpgo_spd_solver_debug_t *h, long long *sizes, int *flags, int *levels, int *node_counts,
+                               int *fronts, int *piv_idx, int *upd_idx);
+int dpgo_debug_spd_solver_fine_root(const dpgo_spd_solver_debug_t *h, unsigned long long nodes);
+int dpgo_debug_spd_solver_run(dpgo_spd_solver_debug_t *h, unsigned long long mask_v, const unsigned long long *mask_word,
+                              const unsigned long long *class_of, double scale, int in_place, const double *in, double *out);
+int dpgo_debug_spd_solver_refactor(dpgo_spd_solver_debug_t *h, const double *val);
+void dpgo_debug_spd_solver_free(dpgo_spd_solver_debug_t *h);
 /* Host: the neighbour-to-neighbour exchange plan of `rank` (what dpgo_comm_exchange uses with more than one rank) from
  * every rank's exported and needed (node, pose) keys (dpgo_graph_exchange_plan of its nodes): per peer 5 ints (rank,
  * send_off, send_cnt, recv_off, recv_cnt), the send and receive keys (node, pose interleaved, concatenated over the peers

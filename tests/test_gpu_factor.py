@@ -26,13 +26,21 @@ def _grid_laplacian(shape, rng, diag=1e-3):
     return A + diag * sp.eye(n)
 
 
-@pytest.mark.parametrize("shape,leaf", [((9, 9), 8), ((37, 41), 16), ((70, 70), 32), ((13, 14, 15), 32), ((21, 22, 23), 64),
-                                        ((30, 31, 29), 128)])
-def test_device_factor_solves_like_scipy(shape, leaf):
+GRIDS = [((9, 9), 8), ((37, 41), 16), ((70, 70), 32), ((13, 14, 15), 32), ((21, 22, 23), 64), ((30, 31, 29), 128)]
+
+
+def _grid_case(shape):
     rng = np.random.default_rng(sum(shape))
     A = _grid_laplacian(shape, rng)
+    return A, rng.standard_normal((A.shape[0], 3))
+
+
+@pytest.mark.parametrize("shape,leaf", GRIDS)
+def test_device_factor_with_host_sweeps_solves_like_scipy(shape, leaf):
+    """dpgo_debug_spd_solve: spd_factor with its numeric phase on the device, then spd_solve_host -- the sweeps are the
+    host's.  (The device sweeps on the same matrices: the next test.)"""
+    A, B = _grid_case(shape)
     n = A.shape[0]
-    B = rng.standard_normal((n, 3))
     nnz, levels, max_front = dpgo_amd.spd_stats(A, leaf)
     X = dpgo_amd.spd_solve_host(A, B, leaf=leaf)            # factorisation on the GPU, sweeps on the host
     ref = spla.splu(A.tocsc()).solve(B)
@@ -40,6 +48,22 @@ def test_device_factor_solves_like_scipy(shape, leaf):
     assert np.abs(A @ X - B).max() <= 1e-10 * max(1.0, np.abs(B).max()) * n
     if len(shape) == 3 and min(shape) >= 21:
         assert max_front > 256                              # the wide (K = 128) pass was exercised
+
+
+@pytest.mark.parametrize("shape,leaf", GRIDS)
+def test_device_factor_with_device_sweeps_solves_like_scipy(shape, leaf):
+    """The same matrices, right-hand sides and tolerances through dpgo_amd.SpdSolverDebug: spd_factor, SpdSolverDev::upload and
+    spd_run as a group runs them for G_tt (the ordering's merge depth chosen by the cost model, as there)."""
+    A, B = _grid_case(shape)
+    n = A.shape[0]
+    S = dpgo_amd.SpdSolverDebug(A, leaf, collapse=0, d=3, dof=1)
+    vin = np.zeros(S.shape)
+    vin[::4] = B
+    X = S.run(vin, np.zeros(S.shape))[::4]
+    S.close()
+    ref = spla.splu(A.tocsc()).solve(B)
+    np.testing.assert_allclose(X, ref, rtol=0, atol=1e-9 * np.abs(ref).max())
+    assert np.abs(A @ X - B).max() <= 1e-10 * max(1.0, np.abs(B).max()) * n
 
 
 @pytest.mark.parametrize("blocks", ["1", "3", "8"])

@@ -243,6 +243,53 @@ def test_c_abi_rejects_bad_input(fixtures_dir):
     assert dpgo_amd.Options.driver(LOSS_HUBER).rescale == dpgo_amd.RESCALE_STATIC  # dist_pgo.cpp:105
 
 
+def test_spd_solver_hook_rejects_bad_arguments_and_needs_a_device():
+    """dpgo_debug_spd_solver_*: bad arguments return -1 before any device work; without a HIP device create returns -2 (the
+    wrapper's RuntimeError("no HIP device")) and leaves no handle; NULL handles are errors, freeing one is a no-op."""
+    import ctypes as C
+    L = dpgo_amd.lib()
+    A = sp.csr_matrix(np.array([[2.0, -1.0, 0.0, 0.0], [-1.0, 2.0, 0.0, 0.0], [0.0, 0.0, 2.0, -1.0], [0.0, 0.0, -1.0, 2.0]]))
+    ptr, col, val = A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+    node = np.zeros(4, np.int32)
+    ip, dp = dpgo_amd._ip, dpgo_amd._dp
+
+    def create(n=4, ptr_=ip(ptr), col_=ip(col), val_=dp(val), d=3, dof=1, node_=None, with_out=True):
+        h = C.c_void_p(12345)
+        rc = L.dpgo_debug_spd_solver_create(n, ptr_, col_, val_, 2, 1, 1, d, dof, ip(node) if node_ is None else node_, 0,
+                                            C.byref(h) if with_out else None)
+        if with_out and rc != 0:
+            assert h.value is None     # a failed call leaves no handle behind
+        return rc, h
+
+    assert create(with_out=False)[0] == -1
+    assert create(n=0)[0] == -1
+    assert create(ptr_=None)[0] == -1 and create(col_=None)[0] == -1 and create(val_=None)[0] == -1
+    assert create(d=4)[0] == -1 and create(d=1)[0] == -1
+    assert create(d=3, dof=2)[0] == -1 and create(d=2, dof=3)[0] == -1
+    bad = np.array([0, 0, 64, 0], np.int32)
+    assert create(node_=ip(bad))[0] == -1
+    bad[2] = -1
+    assert create(node_=ip(bad))[0] == -1
+    assert L.dpgo_debug_spd_solver_plan(None, None, None, None, None, None, None, None) == -1
+    assert L.dpgo_debug_spd_solver_fine_root(None, 1) == -1
+    assert L.dpgo_debug_spd_solver_run(None, 1, None, None, 1.0, 0, dp(val), dp(val)) == -1
+    assert L.dpgo_debug_spd_solver_refactor(None, dp(val)) == -1
+    L.dpgo_debug_spd_solver_free(None)
+    rc, h = create()
+    assert rc in (0, -2)
+    if rc == -2:
+        with pytest.raises(RuntimeError, match="no HIP device"):
+            dpgo_amd.SpdSolverDebug(A, 2)
+    else:   # (a machine with a GPU: the remaining argument checks of run and refactor)
+        x = np.zeros(4 * 4 * 3)
+        assert L.dpgo_debug_spd_solver_run(h, 1, None, None, 2.0, 0, dp(x), dp(x)) == -1      # scale is +1 or -1
+        assert L.dpgo_debug_spd_solver_run(h, 1, None, None, 1.0, 0, None, dp(x)) == -1
+        assert L.dpgo_debug_spd_solver_refactor(h, dp(val)) == -1                            # created without keep_numeric
+        L.dpgo_debug_spd_solver_free(h)
+    with pytest.raises(ValueError):
+        dpgo_amd.SpdSolverDebug(A, 2, node_of_unknown=np.zeros(3, np.int32))
+
+
 def test_chordal_initialization_does_not_depend_on_the_thread_count(fixtures_dir, tmp_path):
     """The host PCG applies its operators pose by pose and sums in fixed chunks (chordal.cpp): 1 thread and 4 threads
     give bit-identical initial guesses (the thread count is read once per process: two subprocesses)."""
