@@ -17,6 +17,9 @@ inner step of ``dist_pgo``:
                             SESyncProblem.cpp:375-468, SESync_utils.cpp:721-830 (fast_verification STEP 2)
   fast_verification         SESync_utils.cpp:721-830  NodeGroup.verify(X) -> (CertResult, x, CertFactor); cert_factor (STEP 1
                                                   alone: the device Cholesky of S + eta I), cert_matrix
+  DPGOProblem::evaluate_E   DPGOProblem.cpp:634-681  EdgeEval(graph).run(X, loss, loss_reg): s_rot, s_trans, rho, w of EVERY
+                                                  edge at a global X; Graph.scale_edges(w); verify_reweighted(graph, X,
+                                                  loss, loss_reg): the certificate of the problem re-weighted at X
 
 All compute runs in hand-written HIP kernels behind the C ABI of
 include/dpgo_amd.h.  There is NO CPU fallback: creating a NodeGroup without a
@@ -235,6 +238,14 @@ SYMBOLS = {
                                          C.POINTER(C.c_longlong)]),
     "dpgo_group_cert_apply": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_debug_rayleigh_ritz": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _IP]),
+    "dpgo_edge_eval_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "dpgo_edge_eval_free": (None, [C.c_void_p]),
+    "dpgo_edge_eval_run": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_edge_eval_kernel_ms": (C.c_int, [C.c_void_p, _DP]),
+    "dpgo_debug_edge_eval_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_graph_scale_edges": (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_void_p)]),
+    "dpgo_graph_verify_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_longlong,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, _DP, C.c_int]),
 }
 
 
@@ -390,6 +401,18 @@ class Graph:
         h = C.c_void_p()
         if lib().dpgo_graph_filter_edges(self._h, keep.ctypes.data_as(C.c_void_p), C.byref(h)) != 0:
             raise ValueError("filter_edges failed (no edge kept?)")
+        return Graph(h)
+
+    def scale_edges(self, w):
+        """The same poses, partition, R, t and edge order with kappa_e, tau_e multiplied by w[e] (dpgo_graph_scale_edges):
+        the graph of the re-weighted problem.  w[e] = 0 is legal (the edge stays, with zero values); a negative or
+        non-finite weight raises ValueError."""
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.num_edges,):
+            raise ValueError("w must have one entry per edge (%d)" % self.num_edges)
+        h = C.c_void_p()
+        if lib().dpgo_graph_scale_edges(self._h, _dp(w), C.byref(h)) != 0:
+            raise ValueError("scale_edges failed (a negative or non-finite weight)")
         return Graph(h)
 
     def node_proximal(self, node, opt):
@@ -1303,3 +1326,80 @@ def pcm_inliers(graph, X, tolerance=0.2, weighted=False, exact=True, device=0):
         inl = pcm.solve_exact() if exact else pcm.solve_heuristic()
         keep[ids[~inl]] = False
     return keep
+
+
+class EdgeSummary(C.Structure):
+    """dpgo_edge_summary_t: F = F_intra + F_inter, the smallest weight, the inter-node edges and those with w < 1."""
+    _fields_ = [("F", C.c_double), ("F_intra", C.c_double), ("F_inter", C.c_double), ("weight_min", C.c_double),
+                ("num_inter", C.c_int), ("num_downweighted", C.c_int)]
+
+
+class EdgeEval:
+    """Per-edge residuals, loss values and loss weights of a whole graph at a global X, on the GPU (dpgo_edge_eval_*;
+    the definitions are in include/dpgo_amd.h).  The edge records are uploaded once; run() uploads X and returns
+    (s_rot, s_trans, rho, weight, EdgeSummary), arrays of num_edges doubles in graph order.  There is no CPU path:
+    constructing one without a HIP device raises."""
+
+    def __init__(self, graph, device=0):
+        h = C.c_void_p()
+        if lib().dpgo_edge_eval_create(graph._h, int(device), C.byref(h)) != 0:
+            raise RuntimeError("dpgo_edge_eval_create failed (no HIP device?); there is no CPU path")
+        self._h = h
+        self.graph = graph
+        self.m = graph.num_edges
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().dpgo_edge_eval_free(self._h)
+            self._h = None
+
+    def run(self, X, loss=LOSS_NONE, loss_reg=0.25):
+        X, ld = _fcol(X)
+        out = [np.zeros(self.m) for _ in range(4)]
+        s = EdgeSummary()
+        if lib().dpgo_edge_eval_run(self._h, _dp(X), ld, int(loss), float(loss_reg), *[_dp(a) for a in out], C.byref(s)) != 0:
+            raise ValueError("dpgo_edge_eval_run failed (a short X, an unknown loss, or a bad loss_reg)")
+        return out[0], out[1], out[2], out[3], s
+
+    def summary(self, X, loss=LOSS_NONE, loss_reg=0.25):
+        """The summary alone: nothing but 40 bytes is read back."""
+        X, ld = _fcol(X)
+        s = EdgeSummary()
+        if lib().dpgo_edge_eval_run(self._h, _dp(X), ld, int(loss), float(loss_reg), None, None, None, None, C.byref(s)) != 0:
+            raise ValueError("dpgo_edge_eval_run failed (a short X, an unknown loss, or a bad loss_reg)")
+        return s
+
+    def kernel_ms(self):
+        """Device time of the last run's kernels (HIP events around the two launches)."""
+        ms = C.c_double()
+        lib().dpgo_edge_eval_kernel_ms(self._h, C.byref(ms))
+        return ms.value
+
+
+def edge_eval_host(graph, X, loss=LOSS_NONE, loss_reg=0.25):
+    """Debug, no GPU: the edge kernel's computation on the host, lane by lane in the device's order of summation
+    (dpgo_debug_edge_eval_host).  Returns what EdgeEval.run returns."""
+    X, ld = _fcol(X)
+    out = [np.zeros(graph.num_edges) for _ in range(4)]
+    s = EdgeSummary()
+    if lib().dpgo_debug_edge_eval_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), *[_dp(a) for a in out], C.byref(s)) != 0:
+        raise ValueError("dpgo_debug_edge_eval_host failed (a short X, an unknown loss, or a bad loss_reg)")
+    return out[0], out[1], out[2], out[3], s
+
+
+def verify_reweighted(graph, X, loss, loss_reg=0.25, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True,
+                      stop_on_negative=True, seed=0, refresh_every=50, max_factor_bytes=0, device=0):
+    """The certificate of the RE-WEIGHTED problem at X (dpgo_graph_verify_reweighted): the loss weights w_e = w(s_e(X)) are
+    frozen, the inter-node kappa_e, tau_e scaled by them, and NodeGroup.verify runs on a trivial-loss group of that graph.
+    Returns (CertResult, x, CertFactor, EdgeSummary).  stationarity is the robust gradient norm.  CERT_PROVEN says that X is
+    the global minimiser of its own quadratic surrogate -- a fixed point of an exact MM step -- NOT that it is the global
+    minimum of the robust objective (include/dpgo_amd.h)."""
+    X, ld = _fcol(X)
+    o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
+                    stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
+    res, f, s = CertResult(), CertFactor(), EdgeSummary()
+    x = np.zeros(X.shape[0])
+    if lib().dpgo_graph_verify_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), C.byref(o),
+                                          int(max_factor_bytes), C.byref(res), C.byref(f), C.byref(s), _dp(x), x.shape[0]) != 0:
+        raise RuntimeError("dpgo_graph_verify_reweighted failed (no HIP device, a short X, or a bad loss)")
+    return res, x, f, s

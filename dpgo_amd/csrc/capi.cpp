@@ -13,6 +13,7 @@
 
 #include "cert.h"
 #include "comm.h"
+#include "edges.h"
 #include "group.h"
 #include "pcm.h"
 
@@ -1230,6 +1231,106 @@ int dpgo_group_cert_matrix(dpgo_group_t *h, const double *X, int ld, double eta,
                            long long *nnz) {
   if (!h || !h->grp || !X || !nnz) return -1;
   return guarded([&] { return h->grp->cert_matrix(X, ld, eta, ptr, col, val, cap, nnz); });
+}
+
+// ---- per-edge residuals / weights (edges.h) and the certificate of the re-weighted problem ----
+struct dpgo_edge_eval {
+  dpgo::EdgeEval *p = nullptr;
+};
+
+int dpgo_edge_eval_create(const dpgo_graph_t *g, int device, dpgo_edge_eval_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!g) return -1;
+  return guarded([&] {
+    auto h = std::make_unique<dpgo_edge_eval>();
+    h->p = new dpgo::EdgeEval(g->g, device);
+    *out = h.release();
+    return 0;
+  });
+}
+
+void dpgo_edge_eval_free(dpgo_edge_eval_t *h) {
+  if (!h) return;
+  delete h->p;
+  delete h;
+}
+
+int dpgo_edge_eval_run(dpgo_edge_eval_t *h, const double *X, int ld, int loss, double loss_reg, double *s_rot, double *s_trans,
+                       double *rho, double *weight, dpgo_edge_summary_t *sum) {
+  if (!h || !h->p) return -1;
+  return guarded([&] {
+    dpgo::EdgeSummary s;
+    const int rc = h->p->run(X, ld, loss, loss_reg, s_rot, s_trans, rho, weight, &s);
+    if (rc == 0 && sum) {
+      sum->F = s.F; sum->F_intra = s.F_intra; sum->F_inter = s.F_inter; sum->weight_min = s.weight_min;
+      sum->num_inter = s.num_inter; sum->num_downweighted = s.num_downweighted;
+    }
+    return rc;
+  });
+}
+
+int dpgo_debug_edge_eval_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *s_rot,
+                              double *s_trans, double *rho, double *weight, dpgo_edge_summary_t *sum) {
+  if (!g) return -1;
+  return guarded([&] {
+    dpgo::EdgeSummary s;
+    const int rc = dpgo::edge_eval_host(g->g, X, ld, loss, loss_reg, s_rot, s_trans, rho, weight, &s);
+    if (rc == 0 && sum) {
+      sum->F = s.F; sum->F_intra = s.F_intra; sum->F_inter = s.F_inter; sum->weight_min = s.weight_min;
+      sum->num_inter = s.num_inter; sum->num_downweighted = s.num_downweighted;
+    }
+    return rc;
+  });
+}
+
+int dpgo_edge_eval_kernel_ms(const dpgo_edge_eval_t *h, double *ms) {
+  if (!h || !h->p || !ms) return -1;
+  *ms = h->p->kernel_ms;
+  return 0;
+}
+
+int dpgo_graph_scale_edges(const dpgo_graph_t *g, const double *w, dpgo_graph_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!g || !w) return -1;
+  return guarded([&] {
+    auto f = std::make_unique<dpgo_graph>();
+    if (dpgo::scale_edges(g->g, w, f->g) != 0) return -1;
+    *out = f.release();
+    return 0;
+  });
+}
+
+int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                 const dpgo_cert_options_t *cert_opts, long long max_factor_bytes,
+                                 dpgo_cert_result_t *cert_result, dpgo_cert_factor_t *cert_factor,
+                                 dpgo_edge_summary_t *edge_summary, double *x, int ldx) {
+  if (!g || !X || !cert_result || !cert_factor) return -1;
+  dpgo_cert_options_t co;
+  dpgo_cert_options_default(&co);
+  if (cert_opts) co = *cert_opts;
+  const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
+  std::vector<double> w((size_t)std::max(m, 1));
+  dpgo_edge_eval_t *ev = nullptr;
+  dpgo_graph_t *gw = nullptr;
+  dpgo_group_t *grp = nullptr;
+  int rc = dpgo_edge_eval_create(g, device, &ev);
+  if (rc == 0) rc = dpgo_edge_eval_run(ev, X, ld, loss, loss_reg, nullptr, nullptr, nullptr, w.data(), edge_summary);
+  dpgo_edge_eval_free(ev);
+  if (rc == 0) rc = dpgo_graph_scale_edges(g, w.data(), &gw);
+  if (rc == 0) {
+    dpgo_options_t opt;
+    dpgo_options_driver(&opt, 0, 1);
+    opt.max_iterations = 0;
+    std::vector<int> ids(nn);
+    std::iota(ids.begin(), ids.end(), 0);
+    rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
+  }
+  if (rc == 0) rc = dpgo_group_verify(grp, X, ld, &co, max_factor_bytes, nullptr, 0, cert_result, x, ldx, cert_factor);
+  dpgo_group_free(grp);
+  dpgo_graph_free(gw);
+  return rc == 0 ? 0 : -1;
 }
 
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {

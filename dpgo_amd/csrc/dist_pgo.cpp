@@ -12,6 +12,14 @@
 //                  verification: <status> <outcome> <pivot_min> <theta> <residual> <iterations> <stationarity>
 //              from dpgo_group_verify (fast_verification, C++/SESync/src/SESync_utils.cpp:721-830: the Cholesky factorisation
 //              of S + eta I first, the search only when it does not succeed); the same reasons when it is not computed
+//              --edge_report FILE (likewise; empty: off)  after the loop, one row per edge of the graph in file order,
+//                  edge i j inter s_rot s_trans rho weight        (16 digits)
+//              from dpgo_edge_eval_run at the final X with the run's loss: what the robust loss did to every measurement
+//              --verify_reweighted (likewise)  after the summary (and the lines above), one more line on stdout
+//                  reweighted verification: <status> <outcome> <pivot_min> <theta> <residual> <iterations> <stationarity>
+//                                           <num_downweighted>/<num_inter> <weight_min>
+//              from dpgo_graph_verify_reweighted: the certificate of the problem re-weighted by the loss weights at the
+//              final X (any loss); with several ranks a line that says why not
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -47,7 +55,8 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false;
+  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false;
+  std::string edge_report;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -66,6 +75,9 @@ int main(int argc, char **argv) {
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
     else if (a == "--verify") verify = true;
     else if (a.compare(0, 9, "--verify=") == 0) verify = parse_bool(argv[i] + 9);
+    else if (a == "--verify_reweighted") verify_reweighted = true;
+    else if (a.compare(0, 20, "--verify_reweighted=") == 0) verify_reweighted = parse_bool(argv[i] + 20);
+    else if (const char *v = val("--edge_report")) edge_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
@@ -212,6 +224,51 @@ int main(int argc, char **argv) {
              : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED",
              cf.outcome == DPGO_CERT_FACTOR_PD ? "PD" : cf.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED", cf.pivot_min,
              cr.theta, cr.residual, cr.iterations, cr.stationarity);
+    }
+  }
+  if (!edge_report.empty() || verify_reweighted) {
+    if (world > 1) {
+      if (root && !edge_report.empty()) printf("edge report: not written (the edge evaluation needs the whole X on one rank; %d ranks)\n", world);
+      if (root && verify_reweighted) printf("reweighted verification: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0);
+      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0) return -1;
+      if (!edge_report.empty()) {
+        std::vector<int> I(m), J(m);
+        std::vector<double> sr(m), st(m), rho(m), w(m);
+        dpgo_edge_eval_t *ev = nullptr;
+        if (dpgo_graph_edges(g, I.data(), J.data(), nullptr, nullptr, nullptr, nullptr) != 0 || dpgo_edge_eval_create(g, gpu, &ev) != 0) return -1;
+        const int rc = dpgo_edge_eval_run(ev, Xc.data(), ld, loss, opt.loss_reg, sr.data(), st.data(), rho.data(), w.data(), nullptr);
+        dpgo_edge_eval_free(ev);
+        if (rc != 0) return -1;
+        // (inter: the weight of an intra-node edge is 1 by definition, so the flag is the partition's, from the node ranges)
+        std::vector<int> first(nn);
+        for (int a = 0; a < nn; a++) first[a] = dpgo_graph_node_offset(g, a);   // (-1: a node without an edge)
+        auto node_of = [&](int p) {
+          int r = 0;
+          for (int a = 0; a < nn; a++)
+            if (first[a] >= 0 && p >= first[a]) r = a;
+          return r;
+        };
+        FILE *f = fopen(edge_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", edge_report.c_str()); return -1; }
+        for (int e = 0; e < m; e++)
+          fprintf(f, "%d %d %d %d %.16g %.16g %.16g %.16g\n", e, I[e], J[e], node_of(I[e]) != node_of(J[e]) ? 1 : 0, sr[e], st[e], rho[e], w[e]);
+        fclose(f);
+      }
+      if (verify_reweighted) {
+        dpgo_cert_options_t co;
+        dpgo_cert_options_default(&co);
+        dpgo_cert_result_t cr;
+        dpgo_cert_factor_t cf;
+        dpgo_edge_summary_t es;
+        if (dpgo_graph_verify_reweighted(g, gpu, Xc.data(), ld, loss, opt.loss_reg, &co, 0, &cr, &cf, &es, nullptr, 0) != 0) return -1;
+        printf("reweighted verification: %s %s %.16g %.16g %.16g %d %.16g %d/%d %.16g\n",
+               cr.status == DPGO_CERT_PROVEN ? "PROVEN" : cr.status == DPGO_CERT_NEGATIVE ? "NEGATIVE"
+               : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED",
+               cf.outcome == DPGO_CERT_FACTOR_PD ? "PD" : cf.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED", cf.pivot_min,
+               cr.theta, cr.residual, cr.iterations, cr.stationarity, es.num_downweighted, es.num_inter, es.weight_min);
+      }
     }
   }
   if (save) {

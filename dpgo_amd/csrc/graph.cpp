@@ -152,6 +152,27 @@ int read_g2o(const std::string &filename, int num_nodes, Graph &g) {
   return partition(g, num_nodes);
 }
 
+// The same poses, partition, R, t and edge order as g with kappa_e, tau_e multiplied by w[e] (dpgo_graph_scale_edges): the
+// graph of the re-weighted problem, the loss weights frozen at a point.  w[e] = 0 is legal: the edge stays in the pattern with
+// zero values.  -1 on a negative or non-finite weight.
+int scale_edges(const Graph &g, const double *w, Graph &out) {
+  if (!w) return -1;
+  for (size_t e = 0; e < g.all.size(); e++)
+    if (!(w[e] >= 0.0) || !std::isfinite(w[e])) {
+      fprintf(stderr, "[dpgo_amd] ERROR: dpgo_graph_scale_edges: weight %zu is negative or not finite.\n", e);
+      return -1;
+    }
+  out = Graph();
+  out.d = g.d;
+  out.num_poses = g.num_poses;
+  out.all = g.all;
+  for (size_t e = 0; e < out.all.size(); e++) {
+    out.all[e].kappa *= w[e];
+    out.all[e].tau *= w[e];
+  }
+  return partition(out, g.num_nodes);
+}
+
 int DataInfo::tail(const Measurement &mm) const {
   int k = index.at({mm.inode, mm.ipose});
   return mm.inode == node ? k : n[0] + k;

@@ -38,6 +38,8 @@ int read_g2o_file(const std::string &filename, int &num_poses, int &d, measureme
 // Partition `all` into num_nodes contiguous ranges (DPGO_utils.cpp:147-158).
 int partition(Graph &g, int num_nodes);
 int read_g2o(const std::string &filename, int num_nodes, Graph &g);
+// g with kappa_e, tau_e multiplied by w[e] >= 0 (same poses, partition, R, t, edge order); -1 on a bad weight.
+int scale_edges(const Graph &g, const double *w, Graph &out);
 
 // generate_data_info (DPGO_utils.cpp:326-438).
 struct DataInfo {

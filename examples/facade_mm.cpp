@@ -1,12 +1,14 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
 //   certificate: <NEGATIVE|NONNEGATIVE|UNDECIDED|FAILED> <theta> <residual> <iterations> <stationarity>
 // and with `verify` through DPGOHashGroup::fast_verification (the Cholesky proof first, the search only if it fails):
 //   verification: <PROVEN|NEGATIVE|NONNEGATIVE|UNDECIDED|FAILED> <PD|NOT_PD|SKIPPED> <pivot_min> <theta> <residual> <iterations> <stationarity>
+// and with `reweighted` (any loss) through DPGO::EdgeEvaluation, Graph::scale_edges and DPGO::fast_verification_reweighted:
+//   reweighted verification: <status> <outcome> <pivot_min> <theta> <iterations> <stationarity> <num_downweighted>/<num_inter> <weight_min> <scaled edges>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -26,7 +28,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -78,6 +80,25 @@ int main(int argc, char **argv) {
     const char *oc = f.outcome == DPGO_CERT_FACTOR_PD ? "PD" : f.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED";
     fprintf(stderr, "verification: %s %s %.10e %.10e %.10e %d %.10e\n", name, oc, f.pivot_min, theta, r.residual, its, r.stationarity);
     if (status < 0) return 1;
+  }
+  if (argc > 6 && !strcmp(argv[6], "reweighted")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), x;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    const double loss_reg = DPGO::Options::driver(l, acc).loss_reg;
+    DPGO::EdgeEvaluation edges(*graph, 0);
+    if (edges.run(X, l, loss_reg) != 0) return 1;
+    auto scaled = graph->scale_edges(edges.weight());
+    double theta = 0, stat = 0;
+    int its = 0, status = -1;
+    dpgo_cert_factor_t f = {};
+    dpgo_edge_summary_t es = {};
+    DPGO::fast_verification_reweighted(*graph, X, l, loss_reg, 1e-3, theta, x, its, &status, &f, &es, &stat);
+    const char *name = status == DPGO_CERT_PROVEN ? "PROVEN" : status == DPGO_CERT_NEGATIVE ? "NEGATIVE"
+                       : status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : status == DPGO_CERT_UNDECIDED ? "UNDECIDED" : "FAILED";
+    const char *oc = f.outcome == DPGO_CERT_FACTOR_PD ? "PD" : f.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED";
+    fprintf(stderr, "reweighted verification: %s %s %.10e %.10e %d %.10e %d/%d %.10e %d\n", name, oc, f.pivot_min, theta, its, stat,
+            es.num_downweighted, es.num_inter, es.weight_min, scaled->num_edges());
+    if (status < 0 || es.num_downweighted != edges.summary().num_downweighted) return 1;
   }
   return 0;
 }

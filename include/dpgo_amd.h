@@ -355,7 +355,8 @@ int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dp
  * critical point.  Deviations: the block size is fixed to d (a block IS a pose-record array); the preconditioner is
  * block Jacobi on the (d+1) x (d+1) diagonal blocks of M where the reference uses ILDL (STEP 3); trivial loss only -- a
  * group created with a robust loss returns -1 (create a second group with loss = 0 (None) and max_iterations = 0, which
- * skips the optimiser's factorisation); the group must host every node of the graph (-1 otherwise); rounding is not
+ * skips the optimiser's factorisation -- at a ROBUST solution that group answers another question; its certificate is
+ * dpgo_graph_verify_reweighted below); the group must host every node of the graph (-1 otherwise); rounding is not
  * Eigen's.  The optimiser's state is untouched. */
 #define DPGO_CERT_UNDECIDED 0
 #define DPGO_CERT_NONNEGATIVE 1
@@ -433,6 +434,63 @@ int dpgo_group_verify(dpgo_group_t *grp, const double *X, int ld, const dpgo_cer
  * explicit), *nnz = (d+1)^2 blocks.  With ptr = col = val = NULL only *nnz is set; otherwise cap >= *nnz. */
 int dpgo_group_cert_matrix(dpgo_group_t *grp, const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap,
                            long long *nnz);
+/* ---- per-edge residuals, loss values and loss weights; the certificate of the re-weighted problem ----------------
+ * What a robust loss did to every measurement at a global X ((d+1)N x d, the layout above: t_p = row p, Y_p = R_p^T =
+ * rows N + d p ..).  For edge e = (i, j, R_e, t_e, kappa_e, tau_e), in graph (file) order:
+ *   s_rot_e   = kappa_e |Y_j - R_e^T Y_i|_F^2
+ *   s_trans_e = tau_e |t_j - t_i - t_e^T Y_i|^2
+ *   s_e       = s_rot_e + s_trans_e       (the squared norm of the edge's residual rows, DPGO_utils.cpp:1643-1677)
+ * An edge is INTER when its endpoints lie in different nodes of the graph's partition.  Intra edges, and every edge under
+ * loss 0 (None): rho = s, w = 1.  Inter edges (DPGOProblem.cpp:651-670, delta = loss_reg):
+ *   1 Huber          w = sqrt(delta) / sqrt(max(s, delta)),   rho = min(2 sqrt(delta) sqrt(max(s, delta)) - delta, s)
+ *   2 GemanMcClure   w = delta^2 / (s + delta)^2,             rho = delta s / (s + delta)
+ *   3 Welsch         w = exp(-s / delta),                     rho = delta - delta w
+ *   F = 1/2 sum_intra s_e + 1/2 sum_inter rho_e               (DPGOStar::evaluate_f, DPGOStar.cpp:713-761)
+ * One fp64 kernel, one lane per edge; the sums are reduced in a fixed order without atomics, so a second call returns the
+ * same bits.  A stand-alone handle, as PCM is: no group is needed and any partition works.  There is no CPU path. */
+typedef struct dpgo_edge_summary {
+  double F, F_intra, F_inter;   /* F = F_intra + F_inter */
+  double weight_min;            /* the smallest weight over all edges */
+  int num_inter;
+  int num_downweighted;         /* edges with w < 1 */
+} dpgo_edge_summary_t;
+typedef struct dpgo_edge_eval dpgo_edge_eval_t;
+/* uploads the graph's edge records once; -1 without a HIP device, or on a NULL argument */
+int dpgo_edge_eval_create(const dpgo_graph_t *g, int device, dpgo_edge_eval_t **out);
+void dpgo_edge_eval_free(dpgo_edge_eval_t *h);
+/* s_rot, s_trans, rho, weight: num_edges doubles each, any of them may be NULL; sum may be NULL.  -1 on X NULL,
+ * ld < (d+1)N, a loss outside 0..3, or a robust loss with loss_reg not finite and positive. */
+int dpgo_edge_eval_run(dpgo_edge_eval_t *h, const double *X, int ld, int loss, double loss_reg, double *s_rot,
+                       double *s_trans, double *rho, double *weight, dpgo_edge_summary_t *sum);
+/* device time of the last run's kernels in milliseconds (HIP events around the two launches; tools/edge_bench.py) */
+int dpgo_edge_eval_kernel_ms(const dpgo_edge_eval_t *h, double *ms);
+/* Debug, host only (no GPU needed): the kernel's computation lane by lane, from the same records through the same code,
+ * summed in the device's order.  The host's exp / expm1 and its unfused multiply-adds round differently, so the values agree
+ * with the device's to rounding, not to the bit.  Arguments as for dpgo_edge_eval_run. */
+int dpgo_debug_edge_eval_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *s_rot,
+                              double *s_trans, double *rho, double *weight, dpgo_edge_summary_t *sum);
+/* The sibling of dpgo_graph_filter_edges: the same poses, partition, R, t and edge order, kappa_e and tau_e multiplied by
+ * w[e] (num_edges weights).  w[e] = 0 is legal -- the edge stays in the pattern with zero values (Welsch reaches exactly
+ * 0.0) -- a negative or non-finite weight returns -1. */
+int dpgo_graph_scale_edges(const dpgo_graph_t *g, const double *w, dpgo_graph_t **out);
+/* The certificate of the RE-WEIGHTED problem at X, in one call: the edge evaluation at X, dpgo_graph_scale_edges by its
+ * weights w_e = w(s_e(X)), a group hosting every node of the scaled graph with dpgo_options_driver(0 (None), 1) and
+ * max_iterations = 0, dpgo_group_verify on it (V0 = NULL), everything released.  S_w(X) is the certificate matrix of the
+ * data matrix M_w = M_intra + sum_inter w_e M_e.
+ *
+ * What DPGO_CERT_PROVEN means HERE.  The gradient of the robust objective at X is M_w X (evaluate_grad,
+ * DPGOStar.cpp:763-829), so `stationarity` = |S_w X|_F is the robust Riemannian gradient norm.  rho is concave in s for
+ * the three losses, so the quadratic surrogate F_w(Z) + c >= F_robust(Z) for every Z, with equality at X.  S_w(X) >= -eta I
+ * together with a small stationarity therefore says: X is the GLOBAL minimiser of its own surrogate F_w -- a fixed point of
+ * an exact majorisation-minimisation step.  It does NOT say that X is the global minimum of the robust objective (the
+ * surrogate of another point may reach lower).  With loss 0, or a partition of one node, every weight is 1 and the results
+ * equal dpgo_group_verify's on the graph itself.  SKIPPED and max_factor_bytes as in dpgo_group_verify.  A second group is
+ * built per call (seconds of set-up at 100 000 poses); cert_opts NULL: the defaults; edge_summary, x may be NULL. */
+int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                 const dpgo_cert_options_t *cert_opts, long long max_factor_bytes,
+                                 dpgo_cert_result_t *cert_result, dpgo_cert_factor_t *cert_factor,
+                                 dpgo_edge_summary_t *edge_summary, double *x, int ldx);
+
 /* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
  * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
  * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:

@@ -104,6 +104,14 @@ class Graph {
     if (dpgo_chordal_initialization(h_, X.data(), X.rows()) != 0) throw std::runtime_error("chordal_initialization");
     return X;
   }
+  // dpgo_graph_scale_edges: the same poses, partition, R, t and edge order with kappa_e, tau_e multiplied by w[e] >= 0 (the
+  // graph of the re-weighted problem; w[e] = 0 keeps the edge with zero values).  Throws on a bad weight or a wrong length.
+  std::shared_ptr<Graph> scale_edges(const std::vector<Scalar> &w) const {
+    dpgo_graph_t *h = nullptr;
+    if ((int)w.size() != num_edges_ || dpgo_graph_scale_edges(h_, w.data(), &h) != 0)
+      throw std::runtime_error("DPGO::Graph::scale_edges: one finite weight >= 0 per edge");
+    return std::shared_ptr<Graph>(new Graph(h));
+  }
   const dpgo_graph_t *handle() const { return h_; }
 
  private:
@@ -373,6 +381,66 @@ class PCM {
   std::vector<unsigned char> adjacency_;
   mutable std::vector<bool> results_;
 };
+
+// What a robust loss did to every measurement at a global X ((d+1) N x d): per edge, in file order, the rotation and
+// translation parts of the squared residual, the loss value and the loss weight (DPGOProblem::evaluate_E,
+// DPGOProblem.cpp:634-681, for every edge of the graph), on the GPU (dpgo_edge_eval_*).  Intra-node edges: rho = s, w = 1.
+class EdgeEvaluation {
+ public:
+  explicit EdgeEvaluation(const Graph &graph, int device = 0) : m_(graph.num_edges()) {
+    if (dpgo_edge_eval_create(graph.handle(), device, &h_) != 0)
+      throw std::runtime_error("dpgo_edge_eval_create failed (no HIP device); there is no CPU path");
+  }
+  ~EdgeEvaluation() { dpgo_edge_eval_free(h_); }
+  EdgeEvaluation(const EdgeEvaluation &) = delete;
+  EdgeEvaluation &operator=(const EdgeEvaluation &) = delete;
+
+  // 0 ok, -1 error (X too small, a robust loss with loss_reg <= 0)
+  int run(const Matrix &X, Loss loss, Scalar loss_reg) {
+    for (auto *v : {&s_rot_, &s_trans_, &rho_, &weight_}) v->assign(m_, 0.0);
+    return dpgo_edge_eval_run(h_, X.data(), X.rows(), (int)loss, loss_reg, s_rot_.data(), s_trans_.data(), rho_.data(),
+                              weight_.data(), &summary_);
+  }
+  const std::vector<Scalar> &s_rot() const { return s_rot_; }
+  const std::vector<Scalar> &s_trans() const { return s_trans_; }
+  const std::vector<Scalar> &rho() const { return rho_; }
+  const std::vector<Scalar> &weight() const { return weight_; }
+  const dpgo_edge_summary_t &summary() const { return summary_; }
+
+ private:
+  dpgo_edge_eval_t *h_ = nullptr;
+  int m_ = 0;
+  std::vector<Scalar> s_rot_, s_trans_, rho_, weight_;
+  dpgo_edge_summary_t summary_{};
+};
+
+// fast_verification of the RE-WEIGHTED problem (dpgo_graph_verify_reweighted): the loss weights are frozen at X, the
+// inter-node kappa, tau scaled by them, and DPGOHashGroup::fast_verification runs on a trivial-loss group of that graph.
+// true: X is PROVEN to be the global minimiser of its own quadratic surrogate (a fixed point of an exact MM step) up to eta --
+// NOT the global minimum of the robust objective; read `stationarity` (the robust gradient norm) with it.
+inline bool fast_verification_reweighted(const Graph &graph, const Matrix &X, Loss loss, Scalar loss_reg, Scalar eta,
+                                         Scalar &theta, Matrix &x, int &num_iters, int *status = nullptr,
+                                         dpgo_cert_factor_t *factor = nullptr, dpgo_edge_summary_t *edges = nullptr,
+                                         Scalar *stationarity = nullptr, long long max_factor_bytes = 0, int device = 0) {
+  dpgo_cert_options_t o;
+  dpgo_cert_options_default(&o);
+  o.eta = eta;
+  dpgo_cert_result_t r;
+  dpgo_cert_factor_t f;
+  x.resize(X.rows(), 1);
+  const int rc = dpgo_graph_verify_reweighted(graph.handle(), device, X.data(), X.rows(), (int)loss, loss_reg, &o,
+                                              max_factor_bytes, &r, &f, edges, x.data(), x.rows());
+  if (rc != 0) {
+    if (status) *status = -1;
+    return false;
+  }
+  theta = r.theta;
+  num_iters = r.iterations;
+  if (status) *status = r.status;
+  if (factor) *factor = f;
+  if (stationarity) *stationarity = r.stationarity;
+  return r.status == DPGO_CERT_PROVEN;
+}
 
 }  // namespace DPGO
 
