@@ -208,6 +208,9 @@ SYMBOLS = {
     "dpgo_debug_spd_factor_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _DP, _IP, C.POINTER(C.c_longlong), _IP, _IP,
                                             _DP, _DP, _DP, _DP]),
     "dpgo_debug_spd_factor_free": (None, [C.c_void_p]),
+    "dpgo_debug_spd_selinv": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "dpgo_debug_spd_selinv_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _DP, _IP, _IP, _IP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_spd_selinv_free": (None, [C.c_void_p]),
     "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
                                                C.POINTER(C.c_void_p)]),
     "dpgo_debug_spd_solver_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _IP, _IP, _IP, _IP, _IP]),
@@ -232,6 +235,10 @@ SYMBOLS = {
     "dpgo_group_certify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int, C.c_void_p, _DP, C.c_int]),
     "dpgo_group_cert_lambda": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP]),
     "dpgo_group_cert_factor": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, C.c_longlong, C.c_void_p]),
+    "dpgo_group_covariance": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _IP, C.c_int, _DP, _DP, C.c_void_p]),
+    "dpgo_group_cov_hessian": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, _IP, _IP, _DP, C.c_longlong, C.POINTER(C.c_longlong)]),
+    "dpgo_graph_covariance_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong,
+                                                   _IP, C.c_int, _DP, _DP, C.c_void_p, C.c_void_p]),
     "dpgo_group_verify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, C.c_void_p, _DP, C.c_int,
                                     C.c_void_p]),
     "dpgo_group_cert_matrix": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
@@ -545,6 +552,63 @@ def spd_factor_debug(A_csr, leaf, collapse=1, block=1, factor_only=False, refact
     if sizes[6]:
         out.update(status2=int(status[2]), fail_front2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
                    W2=W2, WT2=WT2)
+    return out
+
+
+def spd_selinv_debug(A_csr, leaf, collapse=1, block=1, host=False, refactor_values=None):
+    """Selected inversion of an SPD CSR matrix, front by front (test hook, dpgo_debug_spd_selinv): the entries of A^-1 inside
+    the factor's pattern, from spd_selinv_device where there is a HIP device and host is not asked for, else from
+    spd_selinv_host.  refactor_values: a second value array in the order of A.tocsr() with sorted indices, factored through
+    the kept numeric context and inverted afterwards.
+
+    Returns a dict: status / selinv_status (0; 1: not positive definite, and then nothing was inverted), pivot_min,
+    pivot_max, on_device, nfronts, w, u, parent, depth, piv_idx / upd_idx (one array per front), sigma (a list: per front
+    the (w + u) x (w + u) block of A^-1 on [pivots; update rows], None when not inverted), sigma_again (a second call's),
+    W_before / W_after (the factor's W ahead of the inversion and from a factorisation of the same values behind it), and
+    with refactor_values status2, selinv_status2, pivot_min2, pivot_max2, sigma2."""
+    A = A_csr.tocsr()
+    A.sort_indices()
+    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    val2 = None
+    if refactor_values is not None:
+        val2 = np.ascontiguousarray(refactor_values, np.float64)
+        if val2.shape != val.shape:
+            raise ValueError("refactor_values must have one value per stored entry of A")
+    n = A.shape[0]
+    h = C.c_void_p()
+    if lib().dpgo_debug_spd_selinv(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
+                                   int(collapse), int(block), int(bool(host)), C.byref(h)) != 0:
+        raise RuntimeError("spd_selinv_debug failed")
+    try:
+        get = lib().dpgo_debug_spd_selinv_get
+        sizes = np.zeros(8, np.int64)
+        status = np.zeros(4, np.int32)
+        piv = np.zeros(4)
+        LLP = C.POINTER(C.c_longlong)
+        get(h, sizes.ctypes.data_as(LLP), _ip(status), _dp(piv), None, None, None, None, None, None, None, None)
+        nt = int(sizes[0])
+        fronts = np.zeros((nt, 4), np.int32)
+        piv_idx = np.zeros(n, np.int32)
+        upd_idx = np.zeros(max(int(sizes[1]), 1), np.int32)
+        flat = [np.zeros(int(sizes[k])) if sizes[k] else None for k in (3, 4, 5, 6, 6)]
+        opt = lambda a: None if a is None else _dp(a)
+        get(h, None, None, None, _ip(fronts), _ip(piv_idx), _ip(upd_idx), *[opt(a) for a in flat])
+    finally:
+        lib().dpgo_debug_spd_selinv_free(h)
+    w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
+    pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+    m = (w + u).astype(np.int64)
+    so = np.concatenate([[0], np.cumsum(m * m)])
+    blocks = lambda a: None if a is None else [a[so[s]:so[s + 1]].reshape(m[s], m[s]) for s in range(nt)]
+    out = {"status": int(status[0]), "selinv_status": int(status[1]), "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
+           "on_device": bool(sizes[7]), "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(), "depth": fronts[:, 3].copy(),
+           "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
+           "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)],
+           "sigma": blocks(flat[0]), "sigma_again": blocks(flat[1]), "W_before": flat[3], "W_after": flat[4]}
+    if refactor_values is not None:
+        out.update(status2=int(status[2]), selinv_status2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
+                   sigma2=blocks(flat[2]))
     return out
 
 
@@ -897,6 +961,42 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_cert_matrix failed")
         return ptr, col, val
 
+    def covariance(self, X, anchor=0, pairs=None, max_bytes=0):
+        """Marginal pose covariances at X (dpgo_group_covariance): the inverse of the Riemannian Hessian in tangent
+        coordinates -- dof = d + d (d - 1) / 2 per pose: the translation increment in the world frame, then omega with
+        R <- R Exp(hat(omega)) in the body frame -- with the global pose `anchor` held fixed.  Trivial-loss groups that host
+        every node, like the certificate.  pairs: (npairs, 2) global poses, each an edge of the graph (anything else
+        raises).  Returns (marginals (N, dof, dof), cross (npairs, dof, dof), CovResult); the blocks that involve the anchor
+        are zero.  outcome COV_OK, COV_NOT_PD (the anchored Hessian is not positive definite; zero blocks) or COV_SKIPPED
+        (the analysis predicts more device bytes than max_bytes, when > 0, or than half of what is free: nothing of the
+        factor was allocated, the predicted sizes are filled in)."""
+        X, ld = _fcol(X)
+        dof = self.d + self.d * (self.d - 1) // 2
+        P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+        marg = np.zeros((self.graph.num_poses, dof, dof))
+        cross = np.zeros((len(P), dof, dof))
+        r = CovResult()
+        if lib().dpgo_group_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P),
+                                       _dp(marg), _dp(cross) if len(P) else None, C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_covariance failed (robust loss, a group that does not host every node, an anchor or "
+                               "pair outside the graph, a pair that is not an edge, or bad sizes)")
+        return marg, cross, r
+
+    def cov_hessian(self, X, anchor=0):
+        """Debug: the matrix covariance factors, the anchored tangent-space Hessian, read back from the device: CSR (ptr, col,
+        val) on the unknowns dof g + a of the global poses g, every stored dof x dof block dense, the anchor's row and
+        column those of the identity."""
+        X, ld = _fcol(X)
+        dof = self.d + self.d * (self.d - 1) // 2
+        nnz = C.c_longlong(0)
+        if lib().dpgo_group_cov_hessian(self._h, _dp(X), ld, int(anchor), None, None, None, 0, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_cov_hessian failed")
+        n = dof * self.graph.num_poses
+        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+        if lib().dpgo_group_cov_hessian(self._h, _dp(X), ld, int(anchor), _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_cov_hessian failed")
+        return ptr, col, val
+
     def cert_lambda(self, X):
         """compute_Lambda_blocks (SESyncProblem.cpp:375-395): the N symmetric d x d blocks of Lambda(X), (N, d, d)."""
         X, ld = _fcol(X)
@@ -1179,6 +1279,18 @@ CERT_FACTOR_NOT_PD, CERT_FACTOR_PD, CERT_FACTOR_SKIPPED = 0, 1, 2
 CERT_FACTOR_NAMES = {0: "NOT_PD", 1: "PD", 2: "SKIPPED"}
 
 
+COV_OK, COV_NOT_PD, COV_SKIPPED = 0, 1, 2
+COV_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+
+
+class CovResult(C.Structure):
+    """dpgo_cov_result_t: the outcome of NodeGroup.covariance and the sizes of its factorisation."""
+    _fields_ = [("outcome", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("device_bytes", C.c_longlong), ("pivot_min", C.c_double), ("pivot_max", C.c_double),
+                ("stationarity", C.c_double), ("symbolic_s", C.c_double), ("numeric_ms", C.c_double),
+                ("factor_ms", C.c_double), ("selinv_ms", C.c_double), ("selinv_flops", C.c_double)]
+
+
 class CertOptions(C.Structure):
     """dpgo_cert_options_t: eta (SESync.h:88), tau (LOBPCG.h:138), max_iters, precondition, stop_on_negative, refresh_every, seed."""
     _fields_ = [("eta", C.c_double), ("tau", C.c_double), ("max_iters", C.c_int), ("precondition", C.c_int),
@@ -1403,3 +1515,21 @@ def verify_reweighted(graph, X, loss, loss_reg=0.25, eta=1e-3, tau=1e-6, max_ite
                                           int(max_factor_bytes), C.byref(res), C.byref(f), C.byref(s), _dp(x), x.shape[0]) != 0:
         raise RuntimeError("dpgo_graph_verify_reweighted failed (no HIP device, a short X, or a bad loss)")
     return res, x, f, s
+
+
+def covariance_reweighted(graph, X, loss, loss_reg=0.25, anchor=0, pairs=None, max_bytes=0, device=0):
+    """The covariances of the RE-WEIGHTED problem at X (dpgo_graph_covariance_reweighted), by verify_reweighted's recipe: the
+    loss weights frozen at X, the inter-node edges scaled by them, NodeGroup.covariance on a trivial-loss group of that
+    graph.  Returns (marginals, cross, CovResult, EdgeSummary).  This is the covariance of the MM surrogate at its fixed
+    point, NOT of the robust objective (include/dpgo_amd.h)."""
+    X, ld = _fcol(X)
+    d = graph.d
+    dof = d + d * (d - 1) // 2
+    P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    marg, cross = np.zeros((graph.num_poses, dof, dof)), np.zeros((len(P), dof, dof))
+    r, s = CovResult(), EdgeSummary()
+    if lib().dpgo_graph_covariance_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), int(anchor),
+                                              int(max_bytes), _ip(P) if len(P) else None, len(P), _dp(marg),
+                                              _dp(cross) if len(P) else None, C.byref(r), C.byref(s)) != 0:
+        raise RuntimeError("dpgo_graph_covariance_reweighted failed (no HIP device, a short X, a bad loss, or a pair that is no edge)")
+    return marg, cross, r, s

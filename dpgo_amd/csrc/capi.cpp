@@ -588,6 +588,134 @@ int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *
 
 void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h) { delete h; }
 
+// ---- test hook: selected inversion, front by front ----
+struct dpgo_spd_selinv_debug {
+  dpgo::SpdFactor F;
+  int status[4] = {-1, -1, -1, -1};
+  double pivots[4] = {0, 0, 0, 0};
+  bool on_device = false;
+  std::vector<int> depth;
+  std::vector<double> sigma, sigma_again, sigma2, W_before, W_after;
+  ~dpgo_spd_selinv_debug() {
+    dpgo::spd_release_device(F);
+    dpgo::spd_release_numeric(F);
+  }
+};
+
+int dpgo_debug_spd_selinv(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, dpgo_spd_selinv_debug_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!ptr || !col || !val || n <= 0 || leaf < 1 || block < 1 || collapse < 0 || n % block != 0 || ptr[0] != 0) return -1;
+  for (int i = 0; i < n; i++)
+    if (ptr[i + 1] < ptr[i]) return -1;
+  for (int e = 0; e < ptr[n]; e++)
+    if (col[e] < 0 || col[e] >= n) return -1;
+  return guarded([&] {
+    dpgo::CsrMatrix A;
+    A.n = n;
+    A.ptr.assign(ptr, ptr + n + 1);
+    A.col.assign(col, col + ptr[n]);
+    A.val.assign(val, val + ptr[n]);
+    std::unique_ptr<dpgo_spd_selinv_debug> h(new dpgo_spd_selinv_debug());
+    dpgo::SpdFactor &F = h->F;
+    h->on_device = !host && spd_debug_device_numeric();
+    F.quiet = true;
+    std::vector<double> WT;
+    // the blocks the device holds, to the host
+    auto fetch_sigma = [&](std::vector<double> &S) -> int {
+      S.assign(dpgo::spd_selinv_offsets(F).back(), 0.0);
+      if (hipDeviceSynchronize() != hipSuccess) return -1;
+      if (!S.empty() && hipMemcpy(S.data(), dpgo::spd_selinv_values(F), sizeof(double) * S.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+      return 0;
+    };
+    if (h->on_device) {
+      F.keep_numeric = true;
+      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
+      h->status[0] = spd_debug_status(rc, F);
+      h->pivots[0] = F.pivot_min; h->pivots[1] = F.pivot_max;
+      if (h->status[0] < 0 || !F.numeric) return -1;
+      if (rc == 0 && spd_debug_fetch(F, h->W_before, WT) != 0) return -1;
+      const int si = dpgo::spd_selinv_device(F);
+      h->status[1] = si == 0 ? 0 : (F.not_pd ? 1 : -1);
+      if (h->status[1] < 0) return -1;
+      if (si == 0) {
+        if (fetch_sigma(h->sigma) != 0 || dpgo::spd_selinv_device(F) != 0 || fetch_sigma(h->sigma_again) != 0) return -1;
+        // the same values through the kept context, behind the inversion
+        if (hipMemcpy(dpgo::spd_numeric_values(F), val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        if (dpgo::spd_refactor_device(F) != 0 || spd_debug_fetch(F, h->W_after, WT) != 0) return -1;
+      }
+      if (refactor_val) {
+        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        const int rc2 = dpgo::spd_refactor_device(F);
+        h->status[2] = spd_debug_status(rc2, F);
+        h->pivots[2] = F.pivot_min; h->pivots[3] = F.pivot_max;
+        if (h->status[2] < 0) return -1;
+        const int si2 = dpgo::spd_selinv_device(F);
+        h->status[3] = si2 == 0 ? 0 : (F.not_pd ? 1 : -1);
+        if (h->status[3] < 0) return -1;
+        if (si2 == 0 && fetch_sigma(h->sigma2) != 0) return -1;
+      }
+    } else {
+      // (with a device and host != 0 the numeric phase still runs where spd_factor puts it; W comes to the host)
+      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
+      h->status[0] = spd_debug_status(rc, F);
+      h->pivots[0] = F.pivot_min; h->pivots[1] = F.pivot_max;
+      if (h->status[0] < 0) return -1;
+      h->status[1] = rc == 0 ? 0 : 1;
+      if (rc == 0) {
+        h->W_before = F.W;
+        if (dpgo::spd_selinv_host(F, F.W.data(), h->sigma) != 0 || dpgo::spd_selinv_host(F, F.W.data(), h->sigma_again) != 0) return -1;
+        h->W_after = F.W;
+      }
+      if (refactor_val) {
+        A.val.assign(refactor_val, refactor_val + ptr[n]);
+        const int rc2 = dpgo::spd_refactor(A, F);
+        h->status[2] = spd_debug_status(rc2, F);
+        h->pivots[2] = F.pivot_min; h->pivots[3] = F.pivot_max;
+        if (h->status[2] < 0) return -1;
+        h->status[3] = rc2 == 0 ? 0 : 1;
+        if (rc2 == 0 && dpgo::spd_selinv_host(F, F.W.data(), h->sigma2) != 0) return -1;
+      }
+    }
+    h->depth.assign(F.nfronts, 0);
+    for (int f = F.nfronts - 1; f >= 0; f--)
+      if (F.parent[f] >= 0) h->depth[f] = h->depth[F.parent[f]] + 1;
+    *out = h.release();
+    return 0;
+  });
+}
+
+int dpgo_debug_spd_selinv_get(const dpgo_spd_selinv_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
+                              int *piv_idx, int *upd_idx, double *sigma, double *sigma_again, double *sigma2,
+                              double *W_before, double *W_after) {
+  if (!h) return -1;
+  const dpgo::SpdFactor &F = h->F;
+  const int nt = F.nfronts;
+  if (sizes) {
+    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = dpgo::spd_selinv_offsets(F).back();
+    sizes[3] = (long long)h->sigma.size(); sizes[4] = (long long)h->sigma_again.size(); sizes[5] = (long long)h->sigma2.size();
+    sizes[6] = (long long)std::min(h->W_before.size(), h->W_after.size()); sizes[7] = h->on_device;
+  }
+  if (status) std::copy(h->status, h->status + 4, status);
+  if (pivots) std::copy(h->pivots, h->pivots + 4, pivots);
+  if (fronts)
+    for (int f = 0; f < nt; f++) {
+      int *q = fronts + 4 * f;
+      q[0] = F.w[f]; q[1] = F.u[f]; q[2] = F.parent[f]; q[3] = h->depth[f];
+    }
+  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
+  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
+  if (sigma) std::copy(h->sigma.begin(), h->sigma.end(), sigma);
+  if (sigma_again) std::copy(h->sigma_again.begin(), h->sigma_again.end(), sigma_again);
+  if (sigma2) std::copy(h->sigma2.begin(), h->sigma2.end(), sigma2);
+  if (W_before) std::copy(h->W_before.begin(), h->W_before.end(), W_before);
+  if (W_after) std::copy(h->W_after.begin(), h->W_after.end(), W_after);
+  return 0;
+}
+
+void dpgo_debug_spd_selinv_free(dpgo_spd_selinv_debug_t *h) { delete h; }
+
 // ---- test hook: the device solve (spd_solve.cpp) on a given matrix ----
 using dpgo::DeviceError;   // (what HIP_CHECK throws)
 struct dpgo_spd_solver_debug {
@@ -1328,6 +1456,55 @@ int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double
     rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
   }
   if (rc == 0) rc = dpgo_group_verify(grp, X, ld, &co, max_factor_bytes, nullptr, 0, cert_result, x, ldx, cert_factor);
+  dpgo_group_free(grp);
+  dpgo_graph_free(gw);
+  return rc == 0 ? 0 : -1;
+}
+
+// ---- marginal pose covariances (cov.h) ----
+int dpgo_group_covariance(dpgo_group_t *h, const double *X, int ld, int anchor, long long max_bytes, const int *pairs,
+                          int npairs, double *marginals, double *cross, dpgo_cov_result_t *result) {
+  if (!h || !h->grp || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
+  return guarded([&] {
+    dpgo::CovResult r;
+    const int rc = h->grp->covariance(X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, r);
+    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
+    result->max_front = r.max_front; result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min;
+    result->pivot_max = r.pivot_max; result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s;
+    result->numeric_ms = r.numeric_ms; result->factor_ms = r.factor_ms; result->selinv_ms = r.selinv_ms;
+    result->selinv_flops = r.selinv_flops;
+    return rc;
+  });
+}
+
+int dpgo_group_cov_hessian(dpgo_group_t *h, const double *X, int ld, int anchor, int *ptr, int *col, double *val, long long cap,
+                           long long *nnz) {
+  if (!h || !h->grp || !X || !nnz) return -1;
+  return guarded([&] { return h->grp->cov_hessian(X, ld, anchor, ptr, col, val, cap, nnz); });
+}
+
+int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                     int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
+                                     double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary) {
+  if (!g || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
+  const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
+  std::vector<double> w((size_t)std::max(m, 1));
+  dpgo_edge_eval_t *ev = nullptr;
+  dpgo_graph_t *gw = nullptr;
+  dpgo_group_t *grp = nullptr;
+  int rc = dpgo_edge_eval_create(g, device, &ev);
+  if (rc == 0) rc = dpgo_edge_eval_run(ev, X, ld, loss, loss_reg, nullptr, nullptr, nullptr, w.data(), edge_summary);
+  dpgo_edge_eval_free(ev);
+  if (rc == 0) rc = dpgo_graph_scale_edges(g, w.data(), &gw);
+  if (rc == 0) {
+    dpgo_options_t opt;
+    dpgo_options_driver(&opt, 0, 1);
+    opt.max_iterations = 0;
+    std::vector<int> ids(nn);
+    std::iota(ids.begin(), ids.end(), 0);
+    rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
+  }
+  if (rc == 0) rc = dpgo_group_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, result);
   dpgo_group_free(grp);
   dpgo_graph_free(gw);
   return rc == 0 ? 0 : -1;

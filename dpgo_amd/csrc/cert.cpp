@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "cert_state.h"
 #include "group.h"
 
 namespace dpgo {
@@ -128,29 +129,6 @@ int rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *th
 // ---------------------------------------------------------------------------
 // the group's certificate state
 // ---------------------------------------------------------------------------
-struct Group::CertState {
-  DevBuf<double> X, V, W, P;            // P0 + P1 rows: what a product with M reads (neighbour rows by the halo copy)
-  DevBuf<double> MX, SV, SW, SP, tmp;   // P0 rows
-  DevBuf<double> Lam, Tp, partials;
-  double *h_sums = nullptr;             // pinned: what k_cert_reduce writes
-  bool have_Tp = false;
-  std::vector<int> gid;                 // unified own row -> global pose
-  // STEP 1: the pattern of S on the unknowns (d+1) p + r (p the unified own row), M's values in that order, the factor
-  CsrMatrix A;                          // ptr / col only: the values are written on the device
-  std::vector<int> bptr_h;
-  DevBuf<int> bptr, diag_pose;
-  DevBuf<double> Mval;
-  SpdFactor F;
-  bool have_pattern = false, have_symbolic = false;
-  double symbolic_s = 0;                // of the analysis, reported by the call that ran it
-  long long factor_bytes = 0;
-  ~CertState() {
-    if (h_sums) (void)hipHostFree(h_sums);
-    spd_release_numeric(F);
-    spd_release_device(F);
-  }
-};
-
 void Group::cert_release() {
   delete cert_;
   cert_ = nullptr;

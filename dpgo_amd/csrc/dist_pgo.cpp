@@ -20,6 +20,13 @@
 //                                           <num_downweighted>/<num_inter> <weight_min>
 //              from dpgo_graph_verify_reweighted: the certificate of the problem re-weighted by the loss weights at the
 //              final X (any loss); with several ranks a line that says why not
+//              --covariance FILE (likewise; empty: off)  after the summary (and the lines above), for the trivial loss and a
+//              world of one rank, one line per pose in FILE,
+//                  p  S[0][0] S[0][1] ... S[dof-1][dof-1]       (the upper triangle of Sigma_pp row by row, 17 digits)
+//              -- the marginal covariance of pose p relative to pose 0 from dpgo_group_covariance at the final X, tangent
+//              coordinates (translation in the world frame, rotation in the body frame) -- and one more line on stdout
+//                  covariance: <outcome> <unknowns> <fronts> <levels> <max_front> <device_bytes> <pivot_min> <stationarity>
+//              (NOT_PD or SKIPPED: FILE is not written); the same reasons as --certify when it is not computed
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -56,7 +63,7 @@ int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false;
-  std::string edge_report;
+  std::string edge_report, covariance;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -78,6 +85,7 @@ int main(int argc, char **argv) {
     else if (a == "--verify_reweighted") verify_reweighted = true;
     else if (a.compare(0, 20, "--verify_reweighted=") == 0) verify_reweighted = parse_bool(argv[i] + 20);
     else if (const char *v = val("--edge_report")) edge_report = v;
+    else if (const char *v = val("--covariance")) covariance = v;
     else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
@@ -268,6 +276,34 @@ int main(int argc, char **argv) {
                : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED",
                cf.outcome == DPGO_CERT_FACTOR_PD ? "PD" : cf.outcome == DPGO_CERT_FACTOR_NOT_PD ? "NOT_PD" : "SKIPPED", cf.pivot_min,
                cr.theta, cr.residual, cr.iterations, cr.stationarity, es.num_downweighted, es.num_inter, es.weight_min);
+      }
+    }
+  }
+  if (!covariance.empty()) {
+    if (loss != 0) {
+      if (root) printf("covariance: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("covariance: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      const int dof = d + d * (d - 1) / 2;
+      std::vector<double> Xc((size_t)ld * d, 0.0), marg((size_t)N * dof * dof, 0.0);
+      dpgo_cov_result_t cv;
+      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+          dpgo_group_covariance(grp, Xc.data(), ld, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0)
+        return -1;
+      printf("covariance: %s %d %d %d %d %lld %.16g %.16g\n",
+             cv.outcome == DPGO_COV_OK ? "OK" : cv.outcome == DPGO_COV_NOT_PD ? "NOT_PD" : "SKIPPED", cv.unknowns, cv.fronts, cv.levels,
+             cv.max_front, cv.device_bytes, cv.pivot_min, cv.stationarity);
+      if (cv.outcome == DPGO_COV_OK) {
+        FILE *f = fopen(covariance.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", covariance.c_str()); return -1; }
+        for (int p = 0; p < N; p++) {
+          fprintf(f, "%d", p);
+          for (int a = 0; a < dof; a++)
+            for (int b = a; b < dof; b++) fprintf(f, " %.17g", marg[((size_t)p * dof + a) * dof + b]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
       }
     }
   }

@@ -27,6 +27,7 @@
 
 #include "assemble.h"
 #include "cert.h"
+#include "cov.h"
 #include "graph.h"
 #include "kernels.h"
 #include "schedule.h"
@@ -182,6 +183,13 @@ class Group {
   int verify(const double *X, int ld, const CertOptions &o, long long max_factor_bytes, const double *V0, int ldv0, CertResult &res,
              double *x, int ldx, CertFactor &fac);
   int cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, double *val, long long cap, long long *nnz);
+  // ---- marginal pose covariances (cov.h, cov.cpp): the anchored tangent-space Hessian written on the device, factored,
+  // and inverted inside the factor's pattern (spd.h: spd_selinv_device).  marginals: N blocks dof x dof row-major by global
+  // pose; cross: one block per requested pair (p, q) of global poses, S_pq -- every pair must be an edge of the graph (or
+  // p == q); cov_hessian: the matrix that is factored, read back as CSR on global poses (as cert_matrix)
+  int covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
+                 double *cross, CovResult &out);
+  int cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz);
   // boundary exchange across groups: records of the poses other groups need
   int num_sent() const { return (int)sent_rows_.size(); }
   // device buffer, num_sent()*RS doubles; st: the stream to enqueue on (default: the group's)
@@ -455,6 +463,11 @@ class Group {
   void cert_build_precon();
   void cert_build_pattern();
   int cert_factor_setup(long long max_factor_bytes, CertFactor &out);   // 0: ready to factor, 1: SKIPPED, -1: error
+  struct CovState;    // the covariance's pattern, factor and blocks (cov.cpp), allocated by the first call
+  CovState *cov_ = nullptr;
+  void cov_release();
+  int cov_begin(const double *X, int ld, int anchor);
+  int cov_setup(long long max_bytes, CovResult &out);   // 0: ready, 1: SKIPPED, -1: error
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

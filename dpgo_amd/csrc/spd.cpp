@@ -1015,6 +1015,73 @@ int spd_symbolic(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int b
   return 0;
 }
 
+std::vector<int64_t> spd_selinv_offsets(const SpdFactor &F) {
+  std::vector<int64_t> off(F.nfronts + 1, 0);
+  for (int f = 0; f < F.nfronts; f++) {
+    const int64_t m = F.w[f] + F.u[f];
+    off[f + 1] = off[f] + m * m;
+  }
+  return off;
+}
+
+// The recursion of spd.h in plain loops (the path without a GPU, and the check of the index maps): fronts are stored in
+// post-order, so walking them backwards meets every parent before its children.
+int spd_selinv_host(const SpdFactor &F, const double *W, std::vector<double> &Sigma) {
+  const int nt = F.nfronts;
+  if (!W || (int)F.parent.size() != nt) return -1;
+  const std::vector<int64_t> off = spd_selinv_offsets(F);
+  Sigma.assign(off[nt], 0.0);
+  std::vector<int> loc(F.n, -1), map;
+  std::vector<double> T;
+  for (int f = nt - 1; f >= 0; f--) {
+    const int w = F.w[f], u = F.u[f], m = w + u, ldw = F.ldw[f];
+    if (m == 0) continue;
+    double *S = &Sigma[off[f]];
+    const double *Wf = W + F.w_off[f];
+    if (u > 0) {
+      const int p = F.parent[f];
+      if (p <= f || p >= nt) return -1;
+      const int wp = F.w[p], up = F.u[p], mp = wp + up;
+      const int *pv = &F.piv_idx[F.piv_ptr[p]];
+      const int *pu = up ? &F.upd_idx[F.upd_ptr[p]] : nullptr;
+      for (int k = 0; k < wp; k++) loc[pv[k]] = k;
+      for (int k = 0; k < up; k++) loc[pu[k]] = wp + k;
+      const int *cu = &F.upd_idx[F.upd_ptr[f]];
+      map.assign(u, -1);
+      bool held = true;
+      for (int a = 0; a < u; a++) held = held && (map[a] = loc[cu[a]]) >= 0;
+      for (int k = 0; k < wp; k++) loc[pv[k]] = -1;
+      for (int k = 0; k < up; k++) loc[pu[k]] = -1;
+      if (!held) return -1;   // an update row its parent does not hold: not a factor of spd_factor
+      const double *P = &Sigma[off[p]];
+      for (int a = 0; a < u; a++)
+        for (int b = 0; b < u; b++) S[(size_t)(w + a) * m + w + b] = P[(size_t)map[a] * mp + map[b]];
+      // T = S_uu W_bot, stored as T and as T^T
+#pragma omp parallel for schedule(static) if ((int64_t)u * u * w > 100000)
+      for (int a = 0; a < u; a++) {
+        const double *sa = &S[(size_t)(w + a) * m + w];
+        for (int j = 0; j < w; j++) {
+          double s = 0.0;
+          for (int b = 0; b < u; b++) s += sa[b] * Wf[(size_t)(w + b) * ldw + j];
+          S[(size_t)(w + a) * m + j] = s;
+          S[(size_t)j * m + w + a] = s;
+        }
+      }
+    }
+    // S_pp = W_top^T W_top + W_bot^T T: the lower triangle, mirrored (W_top is lower triangular: k from i on)
+#pragma omp parallel for schedule(dynamic, 8) if ((int64_t)w * w * m > 100000)
+    for (int i = 0; i < w; i++)
+      for (int j = 0; j <= i; j++) {
+        double s = 0.0;
+        for (int k = i; k < w; k++) s += Wf[(size_t)k * ldw + i] * Wf[(size_t)k * ldw + j];
+        for (int a = 0; a < u; a++) s += Wf[(size_t)(w + a) * ldw + i] * S[(size_t)(w + a) * m + j];
+        S[(size_t)i * m + j] = s;
+        S[(size_t)j * m + i] = s;
+      }
+  }
+  return 0;
+}
+
 void spd_solve_host(const SpdFactor &F, double *X, int nc) {
   std::vector<double> ubuf((size_t)F.total_upd * nc, 0.0), f, out;
   for (int s = 0; s < F.nfronts; s++) {  // post-order == forward order

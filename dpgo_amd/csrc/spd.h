@@ -128,6 +128,30 @@ int spd_symbolic(const CsrMatrix &A, SpdFactor &F, int leaf, int collapse, int b
 int64_t spd_numeric_bytes(const SpdFactor &F, int64_t nnz);
 int spd_prepare_device(const CsrMatrix &A, SpdFactor &F);
 
+// Selected inversion (Takahashi): the entries of A^-1 inside the factor's pattern, front by front, from the explicit
+// W_s = [W_top ; W_bot] = [L11^-1 ; -L21 L11^-1].  With S_uu the inverse's block on a front's update rows, taken from its
+// parent's finished block through the child -> parent position map of the assembly read the other way:
+//     T = S_uu W_bot (u x w),   S_pp = W_top^T W_top + W_bot^T T (w x w),   S_front = [[S_pp, T^T], [T, S_uu]]
+// and S_front = W_top^T W_top for a root: dense products, no triangular solve, top-down by tree depth.
+// S_front is (w + u) x (w + u) row-major, pivots first, then the update rows, as in W; the fronts lie one after the other
+// (spd_selinv_offsets: nfronts + 1 entries).  S_pp is computed for its lower triangle and mirrored, T is stored both ways
+// from one product and S_uu is copied from a symmetric block: every S_front is symmetric bit for bit.
+//   spd_selinv_host    plain loops over a host copy of W (F.W, or what was read back from dev_W)
+//   spd_selinv_bytes   device bytes spd_selinv_device allocates on its first call (the blocks at once, the tile lists)
+//   spd_selinv_device  for a factor with keep_device + keep_numeric that is not factor_only, behind a numeric phase that
+//                      succeeded (-1, and nothing computed, when the last one met a non-positive pivot); runs on `stream`
+//                      (nullptr: the factorisation's own) and returns once it is enqueued.  Fixed summation order, no
+//                      atomics: the same bits on every call.  The blocks have storage of their own, so a later
+//                      spd_refactor_device gives the bits it gave before.
+//   spd_selinv_values  the device blocks (nullptr before the first spd_selinv_device)
+//   spd_selinv_release frees them; spd_release_numeric does so too
+std::vector<int64_t> spd_selinv_offsets(const SpdFactor &F);
+int spd_selinv_host(const SpdFactor &F, const double *W, std::vector<double> &Sigma);
+int64_t spd_selinv_bytes(const SpdFactor &F);
+int spd_selinv_device(SpdFactor &F, void *stream = nullptr);
+const double *spd_selinv_values(const SpdFactor &F);
+void spd_selinv_release(SpdFactor &F);
+
 // Host solve (setup paths and tests): X (n x ncols, row-major) <- A^-1 X.
 void spd_solve_host(const SpdFactor &F, double *X, int ncols);
 

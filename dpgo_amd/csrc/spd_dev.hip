@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "settings.h"
@@ -686,7 +687,130 @@ __global__ __launch_bounds__(256) void k_fa_wtop(const FrontDesc *fd, const int 
     }
   }
 }
+
+// ---- selected inversion (spd.h): S_front = [[S_pp, T^T], [T, S_uu]] of every front, top-down by tree depth ----
+struct SelinvDesc {
+  int w, u, m, ldm;           // ldm: row length of WT_s
+  long long wt_off, sig_off;  // WT_s in WT; S_front ((w + u) x (w + u), row-major) in the block storage
+  long long par_sig_off;      // the parent's S_front
+  int par_m, cmap_off;        // its size; this front's update row a sits at position cmap[cmap_off + a] of the parent
+};
+
+// S_uu <- the parent's finished block at the positions of this front's update rows (both triangles: the parent's block is
+// symmetric bit for bit, so this one is).  One workgroup per update row.
+__global__ __launch_bounds__(256) void k_si_gather(const SelinvDesc *sd, const int *lvl, const int *cmap, double *Sig) {
+  const SelinvDesc f = sd[lvl[blockIdx.y]];
+  const int a = blockIdx.x;
+  if (a >= f.u) return;
+  const double *prow = Sig + f.par_sig_off + (long long)cmap[f.cmap_off + a] * f.par_m;
+  double *row = Sig + f.sig_off + (long long)(f.w + a) * f.m + f.w;
+  for (int b = threadIdx.x; b < f.u; b += 256) row[b] = prow[cmap[f.cmap_off + b]];
+}
+
+// C[I, J] = A[I, K] B[J, K]^T on 64 x 64 tiles with v_mfma_f64_16x16x4_f64: the tile scheme of k_fa_abt (four waves of
+// 32 x 32, operands staged through LDS 32 columns of K at a time, the next step's loads in flight behind the products).
+//  MODE 0 (T = S_uu W_bot):  rows a over [0, u), columns j over [0, w), K = u;  A[a, k] = S_uu[a, k],
+//         B[j, k] = W_bot[k, j] = WT[j, w + k];  written to S_front[w + a, j] and, the same value, to S_front[j, w + a].
+//  MODE 1 (S_pp = W^T [W_top ; T]):  rows i and columns j over [0, w), tiles on and below the diagonal, K = w + u;
+//         A[i, k] = WT[i, k];  B[j, k] = WT[j, k] for k < w (W_top) and S_front[j, k] for k >= w (T^T, from MODE 0);
+//         entries j <= i are written and mirrored.
+//  items = (front, tile row << 16 | tile column) pairs, one per workgroup.  Every sum runs over k in ascending order inside
+//  the instruction sequence of one wave: the same bits on every call.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_si_abt(const SelinvDesc *sd, const int *items, const double *WT, double *Sig) {
+  const SelinvDesc f = sd[items[2 * blockIdx.x]];
+  const int code = items[2 * blockIdx.x + 1];
+  const int i0 = (code >> 16) * TS, j0 = (code & 0xffff) * TS;
+  const int ilim = MODE == 0 ? f.u : f.w, jlim = f.w, kend = MODE == 0 ? f.u : f.m;
+  if (i0 >= ilim || j0 >= jlim) return;
+  __shared__ double As[TS][LDT], Bs[TS][LDT];
+  const double *Wt = WT + f.wt_off;
+  double *S = Sig + f.sig_off;
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  const int wr = (wv >> 1) * 32, wc = (wv & 1) * 32;
+  v4d acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; a++)
+#pragma unroll
+    for (int b = 0; b < 2; b++) acc[a][b] = v4d{0.0, 0.0, 0.0, 0.0};
+  double pa[TS * NB / 256], pb[TS * NB / 256];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int j = 0; j < TS * NB / 256; j++) {
+      const int idx = t + 256 * j, r = idx / NB, k = k0 + idx % NB;
+      const int ia = i0 + r, jb = j0 + r;
+      const bool ona = ia < ilim && k < kend, onb = jb < jlim && k < kend;
+      if (MODE == 0) {
+        pa[j] = ona ? S[(long long)(f.w + ia) * f.m + f.w + k] : 0.0;
+        pb[j] = onb ? Wt[(long long)jb * f.ldm + f.w + k] : 0.0;
+      } else {
+        pa[j] = ona ? Wt[(long long)ia * f.ldm + k] : 0.0;
+        pb[j] = onb ? (k < f.w ? Wt[(long long)jb * f.ldm + k] : S[(long long)jb * f.m + k]) : 0.0;
+      }
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < kend; k0 += NB) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TS * NB / 256; j++) {
+      const int idx = t + 256 * j;
+      As[idx / NB][idx % NB] = pa[j];
+      Bs[idx / NB][idx % NB] = pb[j];
+    }
+    __syncthreads();
+    if (k0 + NB < kend) fetch(k0 + NB);
+#pragma unroll
+    for (int kk = 0; kk < NB; kk += 4) {
+      const int kq = kk + (lane >> 4), rr = lane & 15;
+      double av[2], bv[2];
+#pragma unroll
+      for (int a = 0; a < 2; a++) av[a] = As[wr + a * 16 + rr][kq];
+#pragma unroll
+      for (int b = 0; b < 2; b++) bv[b] = Bs[wc + b * 16 + rr][kq];
+#pragma unroll
+      for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
+    }
+  }
+  // C/D lay-out of v_mfma_f64_16x16x4_f64: register r of lane l = C[(l >> 4) + 4 r][l & 15]
+#pragma unroll
+  for (int a = 0; a < 2; a++)
+#pragma unroll
+    for (int b = 0; b < 2; b++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int ii = i0 + wr + a * 16 + (lane >> 4) + 4 * r, jj = j0 + wc + b * 16 + (lane & 15);
+        const double v = acc[a][b][r];
+        if (ii >= ilim || jj >= jlim) continue;
+        if (MODE == 0) {
+          S[(long long)(f.w + ii) * f.m + jj] = v;
+          S[(long long)jj * f.m + f.w + ii] = v;
+        } else if (jj <= ii) {
+          S[(long long)ii * f.m + jj] = v;
+          if (jj < ii) S[(long long)jj * f.m + ii] = v;
+        }
+      }
+}
+
+// what the first spd_selinv_device builds and every later one runs: descriptors, the fronts of every depth, tile lists
+struct SelinvLevel {
+  int lvl_off = 0, nf_u = 0, max_u = 0;            // the level's fronts that have update rows: d_lvl + lvl_off, nf_u of them
+  int t_off = 0, n_t = 0, pp_off = 0, n_pp = 0;    // (front, tile) pairs of MODE 0 / MODE 1 in d_items (counted in pairs)
+};
 }  // namespace
+
+struct SpdSelinvCtx {
+  std::vector<SelinvLevel> levels;
+  SelinvDesc *d_sd = nullptr;
+  int *d_lvl = nullptr, *d_items = nullptr;
+  double *d_Sig = nullptr;
+  ~SpdSelinvCtx() {
+    for (void *q : {(void *)d_sd, (void *)d_lvl, (void *)d_items, (void *)d_Sig})
+      if (q) (void)hipFree(q);
+  }
+};
 
 // The state of a numeric factorisation on the device: the maps from the entries of A into the fronts, the front
 // storage, the outputs W / WT.  One-shot callers build it, run it and drop it; a factor that is re-done with new values
@@ -722,7 +846,10 @@ struct SpdNumericCtx {
       if (q) (void)hipFree(q);
     if (st) (void)hipStreamDestroy(st);
     if (h_io) (void)hipHostFree(h_io);
+    delete selinv;
   }
+  SpdSelinvCtx *selinv = nullptr;   // spd_selinv_device: built on its first call
+  std::vector<int> cmap_host;       // the child -> parent position maps, kept for it (cmap_off[c] = F.ubuf_off[c])
   int build(const CsrMatrix &A, const SpdFactor &F, const std::vector<std::vector<int>> &children);
   // on: the stream to run on (nullptr: the context's own); defer: return once everything is enqueued -- finish() waits
   // and reads the verdict (a caller that has more to enqueue behind the factorisation, Rescale::Dynamic)
@@ -901,6 +1028,7 @@ int SpdNumericCtx::build(const CsrMatrix &A, const SpdFactor &F, const std::vect
   if (!wtop_items.empty()) FA_OK(hipMemcpyAsync(d_wtop_items, wtop_items.data(), sizeof(int) * wtop_items.size(), hipMemcpyHostToDevice, st));
   if (!wbot_items.empty()) FA_OK(hipMemcpyAsync(d_wbot_items, wbot_items.data(), sizeof(int) * wbot_items.size(), hipMemcpyHostToDevice, st));
   FA_OK(hipStreamSynchronize(st));   // (the host vectors go out of scope)
+  cmap_host.swap(cmap);
   return 0;
 }
 
@@ -1192,6 +1320,112 @@ int spd_refactor_device(SpdFactor &F, void *stream, bool defer) {
   return 0;
 }
 int spd_refactor_finish(SpdFactor &F, bool wait) { return F.numeric ? F.numeric->finish(F, wait) : -1; }
+
+// ---- selected inversion ----
+namespace {
+// tiles of a front: MODE 0 covers u x w, MODE 1 the tiles on and below the diagonal of w x w
+int64_t selinv_tiles_t(int64_t w, int64_t u) { return u > 0 ? ((u + TS - 1) / TS) * ((w + TS - 1) / TS) : 0; }
+int64_t selinv_tiles_pp(int64_t w) { const int64_t q = (w + TS - 1) / TS; return q * (q + 1) / 2; }
+}  // namespace
+
+int64_t spd_selinv_bytes(const SpdFactor &F) {
+  int64_t sig = 0, tiles = 0;
+  for (int f = 0; f < F.nfronts; f++) {
+    const int64_t w = F.w[f], u = F.u[f];
+    sig += (w + u) * (w + u);
+    tiles += selinv_tiles_t(w, u) + selinv_tiles_pp(w);
+  }
+  return 8 * sig + 8 * tiles + (int64_t)(sizeof(SelinvDesc) + 4) * F.nfronts;
+}
+
+int spd_selinv_device(SpdFactor &F, void *stream) {
+  SpdNumericCtx *ctx = F.numeric;
+  if (!ctx || ctx->factor_only || !ctx->d_WT) return -1;
+  if (ctx->pending && ctx->finish(F) != 0) return -1;
+  if (F.not_pd) return -1;   // a factorisation that met a non-positive pivot is not inverted
+  const int nt = ctx->nt;
+  if (!ctx->selinv) {
+    std::unique_ptr<SpdSelinvCtx> sc(new SpdSelinvCtx());
+    const std::vector<int64_t> off = spd_selinv_offsets(F);
+    std::vector<int> depth(nt, 0);
+    int maxd = 0;
+    for (int f = nt - 1; f >= 0; f--) {   // (post-order: a parent comes after its children)
+      if (F.parent[f] >= 0) depth[f] = depth[F.parent[f]] + 1;
+      maxd = std::max(maxd, depth[f]);
+    }
+    std::vector<SelinvDesc> sd(std::max(nt, 1));
+    std::vector<std::vector<int>> by_depth(maxd + 1);
+    for (int f = 0; f < nt; f++) {
+      const FrontDesc &d = ctx->fd[f];
+      SelinvDesc &s = sd[f];
+      s.w = d.w; s.u = d.u; s.m = d.m; s.ldm = d.ldm;
+      s.wt_off = d.wt_off; s.sig_off = off[f];
+      s.par_sig_off = 0; s.par_m = 0; s.cmap_off = F.ubuf_off[f];
+      if (d.u > 0) {
+        const int p = F.parent[f];
+        if (p < 0 || p >= nt) return -1;
+        s.par_sig_off = off[p];
+        s.par_m = ctx->fd[p].m;
+        for (int a = 0; a < d.u; a++) {   // (the gather reads the parent's block at these positions)
+          const int la = ctx->cmap_host[s.cmap_off + a];
+          if (la < 0 || la >= s.par_m) return -1;
+        }
+      }
+      if (d.m > 0) by_depth[depth[f]].push_back(f);
+    }
+    std::vector<int> lvl, items;
+    for (int dp = 0; dp <= maxd; dp++) {
+      SelinvLevel L;
+      L.lvl_off = (int)lvl.size();
+      for (int f : by_depth[dp])
+        if (sd[f].u > 0) { lvl.push_back(f); L.max_u = std::max(L.max_u, sd[f].u); }
+      L.nf_u = (int)lvl.size() - L.lvl_off;
+      L.t_off = (int)items.size() / 2;
+      for (int f : by_depth[dp])
+        if (sd[f].u > 0)
+          for (int ti = 0; ti * TS < sd[f].u; ti++)
+            for (int tj = 0; tj * TS < sd[f].w; tj++) { items.push_back(f); items.push_back(ti << 16 | tj); }
+      L.n_t = (int)items.size() / 2 - L.t_off;
+      L.pp_off = (int)items.size() / 2;
+      for (int f : by_depth[dp])
+        for (int ti = 0; ti * TS < sd[f].w; ti++)
+          for (int tj = 0; tj <= ti; tj++) { items.push_back(f); items.push_back(ti << 16 | tj); }
+      L.n_pp = (int)items.size() / 2 - L.pp_off;
+      if (L.nf_u > 65535) {   // (the gather indexes a level's fronts with the grid's y extent)
+        fprintf(stderr, "[dpgo_amd] ERROR: spd_selinv: %d fronts in one tree level; at most 65535 are handled.\n", L.nf_u);
+        return -1;
+      }
+      sc->levels.push_back(L);
+    }
+    for (const SelinvDesc &s : sd)
+      if (s.w > 0 && (s.w + TS - 1) / TS > 0xffff) return -1;   // (a tile index has 16 bits)
+    FA_OK(hipMalloc((void **)&sc->d_sd, sizeof(SelinvDesc) * sd.size()));
+    FA_OK(hipMalloc((void **)&sc->d_lvl, sizeof(int) * std::max<size_t>(lvl.size(), 1)));
+    FA_OK(hipMalloc((void **)&sc->d_items, sizeof(int) * std::max<size_t>(items.size(), 2)));
+    FA_OK(hipMalloc((void **)&sc->d_Sig, sizeof(double) * std::max<int64_t>(off[nt], 1)));
+    FA_OK(hipMemcpy(sc->d_sd, sd.data(), sizeof(SelinvDesc) * sd.size(), hipMemcpyHostToDevice));
+    if (!lvl.empty()) FA_OK(hipMemcpy(sc->d_lvl, lvl.data(), sizeof(int) * lvl.size(), hipMemcpyHostToDevice));
+    if (!items.empty()) FA_OK(hipMemcpy(sc->d_items, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+    ctx->selinv = sc.release();
+  }
+  const SpdSelinvCtx &sc = *ctx->selinv;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->st;
+  for (const SelinvLevel &L : sc.levels) {
+    if (L.nf_u > 0) hipLaunchKernelGGL(k_si_gather, dim3(L.max_u, L.nf_u), dim3(256), 0, st, sc.d_sd, sc.d_lvl + L.lvl_off, ctx->d_cmap, sc.d_Sig);
+    if (L.n_t > 0) hipLaunchKernelGGL((k_si_abt<0>), dim3(L.n_t), dim3(256), 0, st, sc.d_sd, sc.d_items + 2 * L.t_off, ctx->d_WT, sc.d_Sig);
+    if (L.n_pp > 0) hipLaunchKernelGGL((k_si_abt<1>), dim3(L.n_pp), dim3(256), 0, st, sc.d_sd, sc.d_items + 2 * L.pp_off, ctx->d_WT, sc.d_Sig);
+  }
+  FA_OK(hipGetLastError());
+  return 0;
+}
+
+const double *spd_selinv_values(const SpdFactor &F) { return F.numeric && F.numeric->selinv ? F.numeric->selinv->d_Sig : nullptr; }
+
+void spd_selinv_release(SpdFactor &F) {
+  if (!F.numeric) return;
+  delete F.numeric->selinv;
+  F.numeric->selinv = nullptr;
+}
 
 void spd_release_numeric(SpdFactor &F) {
   if (F.dev_borrowed) { F.dev_W = F.dev_WT = nullptr; F.dev_borrowed = false; }

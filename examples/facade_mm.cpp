@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -9,6 +9,8 @@
 //   verification: <PROVEN|NEGATIVE|NONNEGATIVE|UNDECIDED|FAILED> <PD|NOT_PD|SKIPPED> <pivot_min> <theta> <residual> <iterations> <stationarity>
 // and with `reweighted` (any loss) through DPGO::EdgeEvaluation, Graph::scale_edges and DPGO::fast_verification_reweighted:
 //   reweighted verification: <status> <outcome> <pivot_min> <theta> <iterations> <stationarity> <num_downweighted>/<num_inter> <weight_min> <scaled edges>
+// and with `covariance` through DPGOHashGroup::marginal_covariances (trivial loss; pose 0 is the anchor), one line per pose:
+//   covariance: <p> <upper triangle of Sigma_pp row by row, 17 digits>       then   covariance: <OK|NOT_PD|SKIPPED|FAILED> <fronts> <levels> <stationarity>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -28,7 +30,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -99,6 +101,24 @@ int main(int argc, char **argv) {
     fprintf(stderr, "reweighted verification: %s %s %.10e %.10e %d %.10e %d/%d %.10e %d\n", name, oc, f.pivot_min, theta, its, stat,
             es.num_downweighted, es.num_inter, es.weight_min, scaled->num_edges());
     if (status < 0 || es.num_downweighted != edges.summary().num_downweighted) return 1;
+  }
+  if (argc > 6 && !strcmp(argv[6], "covariance")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d());
+    if (dpgo_hash.gather(X) != 0) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2;
+    std::vector<double> marg;
+    int status = -1;
+    dpgo_cov_result_t r = {};
+    const bool ok = dpgo_hash.marginal_covariances(X, marg, 0, &r, &status);
+    for (int p = 0; ok && p < graph->num_poses(); p++) {
+      fprintf(stderr, "covariance: %d", p);
+      for (int a = 0; a < dof; a++)
+        for (int b = a; b < dof; b++) fprintf(stderr, " %.17g", marg[((size_t)p * dof + a) * dof + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "covariance: %s %d %d %.10e\n", status == DPGO_COV_OK ? "OK" : status == DPGO_COV_NOT_PD ? "NOT_PD"
+            : status == DPGO_COV_SKIPPED ? "SKIPPED" : "FAILED", r.fronts, r.levels, r.stationarity);
+    if (status < 0) return 1;
   }
   return 0;
 }

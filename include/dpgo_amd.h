@@ -491,6 +491,58 @@ int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double
                                  dpgo_cert_result_t *cert_result, dpgo_cert_factor_t *cert_factor,
                                  dpgo_edge_summary_t *edge_summary, double *x, int ldx);
 
+/* ---- marginal pose covariances ------------------------------------------------------------------------------------
+ * How uncertain is each pose at X?  The inverse of the Riemannian Hessian of F = 1/2 tr(X^T M X) in tangent coordinates,
+ * with pose `anchor` (a global pose index) held fixed: the covariance relative to the anchor, as g2o and GTSAM report
+ * marginal covariances.  Unknowns dof p + a with dof = d + d (d - 1) / 2 (6 for SE(3), 3 for SE(2)): a < d the translation
+ * increment t_p + dt in the world frame, then omega with R_p <- R_p Exp(hat(omega)) in the body frame (on the record:
+ * Ydot_p = -hat(omega) Y_p); hat(omega) = [[0, -omega], [omega, 0]] for d = 2.  H_pq[a, b] = tr(E_a(p)^T S_pq E_b(q)) with
+ * E_i = e_0 e_i^T, E_{d+k} = [0 ; -hat(e_k) Y_p] and S_pq the block of S = M - blkdiag(0, Lambda(X)) (no eta).
+ *
+ * The same restrictions as the certificate, for the same reasons: the TRIVIAL LOSS only (a group created with a robust
+ * loss returns -1; dpgo_graph_covariance_reweighted below is the route for whoever optimised with one), and the group must
+ * HOST EVERY NODE of the graph (-1 otherwise).  The optimiser's state is not touched.
+ *
+ * The device writes H into the value array of a multifrontal factor of its own (k_cov_hessian), factors it, and a selected
+ * inversion (products on the fp64 matrix cores, top-down through the elimination tree) gives the entries of H^-1 inside the
+ * factor's pattern, which holds every pose's diagonal block and the block of every edge.
+ *   marginals  N x dof x dof doubles by global pose, each block row-major
+ *   cross      npairs x dof x dof: Sigma_pq of the requested pairs (pairs: 2 npairs global poses).  Every pair must be an
+ *              edge of the graph (or p == q): a pair that is not returns -1.  pairs, cross may be NULL with npairs = 0.
+ *   Every block that involves the anchor is zero.
+ *   result     outcome COV_OK; COV_NOT_PD when the anchored H is not positive definite (a saddle or a maximum; the
+ *              blocks are zero); COV_SKIPPED when the analysis predicts more device bytes than max_bytes (> 0) or than half
+ *              of the free device memory (the outputs are not written, nothing of the factor is allocated).  unknowns,
+ *              fronts, levels, max_front, device_bytes are filled for SKIPPED too; stationarity = |S X|_F says whether X
+ *              is a critical point at all; symbolic_s: host seconds of the analysis (0 after a group's first call);
+ *              numeric_ms: host milliseconds from the launch of k_cov_hessian to the finished blocks on the device.
+ * A local minimum has covariances even where its certificate is NEGATIVE. */
+#define DPGO_COV_OK 0
+#define DPGO_COV_NOT_PD 1
+#define DPGO_COV_SKIPPED 2
+typedef struct dpgo_cov_result {
+  int outcome, unknowns, fronts, levels, max_front;
+  long long device_bytes;
+  double pivot_min, pivot_max, stationarity, symbolic_s, numeric_ms;
+  double factor_ms, selinv_ms;   /* numeric_ms taken apart: up to the factorisation's verdict; the selected inversion */
+  double selinv_flops;           /* useful flops of its products: sum over the fronts of 2 u^2 w + 2 u w^2 + w^3 */
+} dpgo_cov_result_t;
+int dpgo_group_covariance(dpgo_group_t *grp, const double *X, int ld, int anchor, long long max_bytes, const int *pairs,
+                          int npairs, double *marginals, double *cross, dpgo_cov_result_t *result);
+/* Debug: the anchored H as the device wrote it, read back from the value array of the factorisation: CSR with dof N + 1 row
+ * pointers on the unknowns dof g + a of the GLOBAL poses g, every stored block dense, the anchor's row and column those of
+ * the identity.  With ptr = col = val = NULL only *nnz is set; otherwise cap >= *nnz. */
+int dpgo_group_cov_hessian(dpgo_group_t *grp, const double *X, int ld, int anchor, int *ptr, int *col, double *val,
+                           long long cap, long long *nnz);
+/* The covariances of the RE-WEIGHTED problem at X, by the recipe of dpgo_graph_verify_reweighted: the edge evaluation at X,
+ * dpgo_graph_scale_edges by its weights (frozen at X), a trivial-loss group hosting every node of the scaled graph,
+ * dpgo_group_covariance on it, everything released.  This is the covariance of the majorisation-minimisation SURROGATE
+ * F_w at its fixed point X -- the information matrix a re-weighted least-squares solver would report -- NOT that of the
+ * robust objective, whose true Hessian also has the derivative of the weights.  edge_summary may be NULL. */
+int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                     int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
+                                     double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary);
+
 /* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
  * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
  * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:
@@ -536,6 +588,34 @@ int dpgo_debug_spd_factor(int n, const int *ptr, const int *col, const double *v
 int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
                               long long *offsets, int *piv_idx, int *upd_idx, double *W, double *WT, double *W2, double *WT2);
 void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h);
+/* Selected inversion of a given SPD CSR matrix, front by front (tests/test_covariance_host.py, tests/test_gpu_selinv_fronts.py):
+ * the entries of A^-1 inside the factor's pattern from the explicit W_s = [L11^-1 ; -L21 L11^-1] (spd.h: spd_selinv_*).
+ * spd_factor(A, F, leaf, collapse, block), quiet, then
+ *   on the device (host == 0 and a HIP device): keep_device + keep_numeric, spd_selinv_device twice (the second call's
+ *     blocks are kept beside the first's), then spd_refactor_device from the SAME values (W before the inversion and after
+ *     this factorisation are both kept) and, with refactor_val, from the second values through the kept context and
+ *     spd_selinv_device again;
+ *   on the host (host != 0, or no device): spd_selinv_host on the factor's W, and with refactor_val spd_refactor and
+ *     spd_selinv_host again.
+ * A factorisation that meets a non-positive pivot is not inverted: its verdict is 1 and its blocks are not there.
+ * Returns 0 and a handle when every step ended with a verdict, -1 on an error or a bad argument.
+ * dpgo_debug_spd_selinv_get copies out what the handle holds; every pointer may be NULL:
+ *   sizes[8]    nfronts, |upd_idx|, doubles of all S_front (sum of (w + u)^2), doubles held of the first inversion (0: not
+ *               inverted), of its repetition, of the second values' inversion, doubles of W held before / after, whether the
+ *               device ran (sizes[7])
+ *   status[4]   verdict of the first factorisation (0 factored, 1 not positive definite), of its inversion (0 done, 1 refused
+ *               because not positive definite), the same two for the second values (-1, -1 when none were given)
+ *   pivots[4]   pivot_min, pivot_max of the first and of the second factorisation
+ *   fronts      4 ints per front: w, u, parent, depth;  piv_idx, upd_idx: as dpgo_debug_spd_factor_get gives them
+ *   sigma, sigma_again, sigma2   S_front of every front one after the other, (w + u) x (w + u) row-major, pivots first
+ *   W_before, W_after            SpdFactor::W (padding included) of the first factorisation and of the one behind the inversion */
+typedef struct dpgo_spd_selinv_debug dpgo_spd_selinv_debug_t;
+int dpgo_debug_spd_selinv(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, dpgo_spd_selinv_debug_t **out);
+int dpgo_debug_spd_selinv_get(const dpgo_spd_selinv_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
+                              int *piv_idx, int *upd_idx, double *sigma, double *sigma_again, double *sigma2,
+                              double *W_before, double *W_after);
+void dpgo_debug_spd_selinv_free(dpgo_spd_selinv_debug_t *h);
 /* The device solve on a given matrix (tests/test_gpu_solve_tiles.py): an SpdSolverDev built as a group builds its own --
  * spd_factor(A, F, leaf, collapse, block) with the factor left on the device unless DPGO_SPD_DEVICE_PANELS=0, then
  * upload(dof, d, node_of_unknown) -- and spd_run on it.  The hook calls what exists; it adds nothing to spd_run or the kernels.

@@ -236,6 +236,26 @@ class DPGOHashGroup {
     if (factor) *factor = f;
     return rc == 0 && r.status == DPGO_CERT_PROVEN;
   }
+  // Marginal pose covariances at X relative to the pose `anchor` (dpgo_group_covariance).  marginals is resized to
+  // N dof dof doubles: block p, row-major, is Sigma_pp in tangent coordinates (translation in the world frame, then rotation
+  // in the body frame; dof = d + d (d - 1) / 2).  pairs / cross (optional): 2 npairs global poses, each an edge of the
+  // graph, and their blocks Sigma_pq (npairs dof dof doubles).  Returns true for DPGO_COV_OK; result (optional) carries the
+  // outcome (NOT_PD, SKIPPED: the blocks are zero) and the sizes; status: the DPGO_COV_* outcome, -1 when the call itself
+  // failed (robust loss, a group that does not host every node, a pair that is not an edge).
+  bool marginal_covariances(const Matrix &X, std::vector<Scalar> &marginals, int anchor = 0, dpgo_cov_result_t *result = nullptr,
+                            int *status = nullptr, const std::vector<int> *pairs = nullptr, std::vector<Scalar> *cross = nullptr,
+                            long long max_bytes = 0) const {
+    const int d = graph_->d(), N = graph_->num_poses();
+    const int dof = d + d * (d - 1) / 2, npairs = pairs && cross ? (int)pairs->size() / 2 : 0;
+    marginals.assign((size_t)N * dof * dof, 0.0);
+    if (cross) cross->assign((size_t)npairs * dof * dof, 0.0);
+    dpgo_cov_result_t r = {};
+    const int rc = dpgo_group_covariance(h_, X.data(), X.rows(), anchor, max_bytes, npairs ? pairs->data() : nullptr, npairs,
+                                         marginals.data(), npairs ? cross->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_COV_OK;
+  }
   const Graph &graph() const { return *graph_; }
   dpgo_group_t *handle() const { return h_; }
 
