@@ -211,6 +211,8 @@ SYMBOLS = {
     "dpgo_debug_spd_selinv": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dpgo_debug_spd_selinv_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _DP, _IP, _IP, _IP, _DP, _DP, _DP, _DP, _DP]),
     "dpgo_debug_spd_selinv_free": (None, [C.c_void_p]),
+    "dpgo_debug_spd_vsolve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _IP, _DP]),
+    "dpgo_debug_spd_vsolve_chunk": (C.c_int, [C.c_int]),
     "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
                                                C.POINTER(C.c_void_p)]),
     "dpgo_debug_spd_solver_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _IP, _IP, _IP, _IP, _IP]),
@@ -239,6 +241,8 @@ SYMBOLS = {
     "dpgo_group_cov_hessian": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, _IP, _IP, _DP, C.c_longlong, C.POINTER(C.c_longlong)]),
     "dpgo_graph_covariance_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong,
                                                    _IP, C.c_int, _DP, _DP, C.c_void_p, C.c_void_p]),
+    "dpgo_polish_options_default": (None, [C.c_void_p]),
+    "dpgo_group_polish": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, C.c_void_p]),
     "dpgo_group_verify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, C.c_void_p, _DP, C.c_int,
                                     C.c_void_p]),
     "dpgo_group_cert_matrix": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
@@ -612,6 +616,54 @@ def spd_selinv_debug(A_csr, leaf, collapse=1, block=1, host=False, refactor_valu
     return out
 
 
+def spd_vsolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor_values=None, chunk=None):
+    """A^-1 rhs for one plain vector (test hook, dpgo_debug_spd_vsolve): spd_factor, then spd_vsolve_device on the factor as the
+    numeric phase leaves it where there is a HIP device and host is not asked for, else spd_solve_host.  refactor_values: a
+    second value array in the order of A.tocsr() with sorted indices, factored through the kept numeric context and solved
+    with afterwards.  chunk: for the length of the call, the entries of a front's input vector the device stages at a time
+    (dpgo_debug_spd_vsolve_chunk; default 2048).
+
+    Returns a dict: status (0; 1: not positive definite, and then nothing was solved), on_device, pivot_min, pivot_max, out (the
+    solution, None when not solved), out_again (a second call's), raw (the 3 n doubles the hook was handed, filled with `fill`
+    first -- what it did not write is still there), and with refactor_values status2, pivot_min2, pivot_max2, out2."""
+    A = A_csr.tocsr()
+    A.sort_indices()
+    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    n = A.shape[0]
+    b = np.ascontiguousarray(rhs, np.float64)
+    if b.shape != (n,):
+        raise ValueError("rhs must have one entry per unknown")
+    val2 = None
+    if refactor_values is not None:
+        val2 = np.ascontiguousarray(refactor_values, np.float64)
+        if val2.shape != val.shape:
+            raise ValueError("refactor_values must have one value per stored entry of A")
+    raw = np.full(3 * n, VSOLVE_FILL)
+    status = np.zeros(2, np.int32)
+    piv = np.zeros(4)
+    before = lib().dpgo_debug_spd_vsolve_chunk(int(chunk)) if chunk is not None else None
+    try:
+        rc = lib().dpgo_debug_spd_vsolve(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
+                                         int(collapse), int(block), int(bool(host)), _dp(b), _dp(raw), _ip(status), _dp(piv))
+    finally:
+        if before is not None:
+            lib().dpgo_debug_spd_vsolve_chunk(before)
+    if rc < 0:
+        raise RuntimeError("spd_vsolve_debug failed")
+    ok = status[0] == 0
+    out = {"status": int(status[0]), "on_device": rc == 1, "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
+           "out": raw[:n].copy() if ok else None, "out_again": raw[n:2 * n].copy() if ok else None, "raw": raw}
+    if refactor_values is not None:
+        out.update(status2=int(status[1]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
+                   out2=raw[2 * n:].copy() if status[1] == 0 else None)
+    return out
+
+
+# what spd_vsolve_debug fills its output with before the call: a quiet NaN with a payload (tests/solve_restatement.py: SENT_OUT)
+VSOLVE_FILL = np.array([0x7ff8_0000_beef_0002], np.uint64).view(np.float64)[0]
+
+
 class SpdSolverDebug:
     """The device multifrontal solve on a given CSR matrix (test hook, dpgo_debug_spd_solver_*): spd_factor and
     SpdSolverDev::upload(dof, d, node_of_unknown) as a group runs them for G_tt (dof 1) and G_RR + lambda I (dof d), then
@@ -982,6 +1034,26 @@ class NodeGroup:
                                "pair outside the graph, a pair that is not an edge, or bad sizes)")
         return marg, cross, r
 
+    def polish(self, X, anchor=0, max_bytes=0, **opts):
+        """Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored
+        tangent-space Hessian of `covariance`, factored and solved on the device -- until the tangent gradient is at rounding
+        level (|g| <= rel_tol hmax, or grad_tol when > 0) or max_steps are spent.  Trivial-loss groups that host every node;
+        the global pose `anchor` is held fixed.  opts: the fields of PolishOptions (max_steps 20, max_tries 8, rel_tol 1e-9,
+        grad_tol 0).  Returns (Xout, PolishResult, log): the new point (X itself for POLISH_SKIPPED), the result struct, and
+        one row per iteration of (F0, |g|, mu at entry, rho of the accepted try, tries).  The optimiser's state is not
+        touched."""
+        X, ld = _fcol(X)
+        o = PolishOptions(anchor=int(anchor), **opts)
+        Xout = np.array(X, order="F")
+        log = np.zeros((max(int(o.max_steps), 0) + 1, 5))
+        r = PolishResult()
+        if lib().dpgo_group_polish(self._h, _dp(X), ld, C.byref(o), int(max_bytes), _dp(Xout), Xout.shape[0], _dp(log), len(log),
+                                   C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_polish failed (robust loss, a group that does not host every node, an anchor outside "
+                               "the graph, or bad sizes or options)")
+        rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
+        return Xout, r, log[:rows].copy()
+
     def cov_hessian(self, X, anchor=0):
         """Debug: the matrix covariance factors, the anchored tangent-space Hessian, read back from the device: CSR (ptr, col,
         val) on the unknowns dof g + a of the global poses g, every stored dof x dof block dense, the anchor's row and
@@ -1289,6 +1361,35 @@ class CovResult(C.Structure):
                 ("device_bytes", C.c_longlong), ("pivot_min", C.c_double), ("pivot_max", C.c_double),
                 ("stationarity", C.c_double), ("symbolic_s", C.c_double), ("numeric_ms", C.c_double),
                 ("factor_ms", C.c_double), ("selinv_ms", C.c_double), ("selinv_flops", C.c_double)]
+
+
+POLISH_CONVERGED, POLISH_MAX_STEPS, POLISH_STALLED, POLISH_SKIPPED = 0, 1, 2, 3
+POLISH_NAMES = {0: "CONVERGED", 1: "MAX_STEPS", 2: "STALLED", 3: "SKIPPED"}
+
+
+class PolishOptions(C.Structure):
+    """dpgo_polish_options_t: max_steps, max_tries, rel_tol, grad_tol, anchor."""
+    _fields_ = [("max_steps", C.c_int), ("max_tries", C.c_int), ("rel_tol", C.c_double), ("grad_tol", C.c_double),
+                ("anchor", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().dpgo_polish_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("PolishOptions has no field %r" % k)
+            setattr(self, k, v)
+
+
+class PolishResult(C.Structure):
+    """dpgo_polish_result_t: the outcome of NodeGroup.polish, its counts, F and |g| at both ends, the sizes of its factorisation
+    and its times."""
+    _fields_ = [("outcome", C.c_int), ("steps", C.c_int), ("factorisations", C.c_int), ("indefinite", C.c_int),
+                ("F_initial", C.c_double), ("F_final", C.c_double), ("grad_initial", C.c_double), ("grad_final", C.c_double),
+                ("hmax", C.c_double), ("mu_final", C.c_double), ("pivot_min", C.c_double), ("pivot_max", C.c_double),
+                ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("device_bytes", C.c_longlong), ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("factor_ms", C.c_double),
+                ("solve_ms", C.c_double), ("other_ms", C.c_double)]
 
 
 class CertOptions(C.Structure):

@@ -716,6 +716,85 @@ int dpgo_debug_spd_selinv_get(const dpgo_spd_selinv_debug_t *h, long long *sizes
 
 void dpgo_debug_spd_selinv_free(dpgo_spd_selinv_debug_t *h) { delete h; }
 
+// ---- test hook: the device solve for one plain vector (spd.h: spd_vsolve_*) ----
+int dpgo_debug_spd_vsolve_chunk(int chunk) { return dpgo::spd_vsolve_chunk(chunk); }
+
+int dpgo_debug_spd_vsolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, const double *rhs, double *out, int *status, double *pivots) {
+  if (!ptr || !col || !val || !rhs || !out || !status || !pivots || n <= 0 || leaf < 1 || block < 1 || collapse < 0 ||
+      n % block != 0 || ptr[0] != 0)
+    return -1;
+  for (int i = 0; i < n; i++)
+    if (ptr[i + 1] < ptr[i]) return -1;
+  for (int e = 0; e < ptr[n]; e++)
+    if (col[e] < 0 || col[e] >= n) return -1;
+  return guarded([&] {
+    dpgo::CsrMatrix A;
+    A.n = n;
+    A.ptr.assign(ptr, ptr + n + 1);
+    A.col.assign(col, col + ptr[n]);
+    A.val.assign(val, val + ptr[n]);
+    struct Holder {
+      dpgo::SpdFactor F;
+      double *d_x = nullptr;
+      ~Holder() {
+        if (d_x) (void)hipFree(d_x);
+        dpgo::spd_release_device(F);
+        dpgo::spd_release_numeric(F);
+      }
+    } H;
+    dpgo::SpdFactor &F = H.F;
+    const bool on_device = !host && spd_debug_device_numeric();
+    F.quiet = true;
+    status[0] = status[1] = -1;
+    std::fill(pivots, pivots + 4, 0.0);
+    const size_t nb = sizeof(double) * (size_t)n;
+    if (on_device) {
+      F.keep_numeric = true;
+      if (hipMalloc((void **)&H.d_x, nb) != hipSuccess) return -1;
+      // out + k n <- A^-1 rhs through spd_vsolve_device
+      auto solve = [&](int k) -> int {
+        if (hipMemcpy(H.d_x, rhs, nb, hipMemcpyHostToDevice) != hipSuccess) return -1;
+        if (dpgo::spd_vsolve_device(F, H.d_x) != 0 || hipDeviceSynchronize() != hipSuccess) return -1;
+        return hipMemcpy(out + (size_t)k * n, H.d_x, nb, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+      };
+      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
+      status[0] = spd_debug_status(rc, F);
+      pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
+      if (status[0] < 0 || !F.numeric) return -1;
+      if (rc == 0 && (solve(0) != 0 || solve(1) != 0)) return -1;
+      if (rc != 0 && dpgo::spd_vsolve_device(F, H.d_x) != -1) return -1;   // (a failed factorisation solves nothing)
+      if (refactor_val) {
+        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        const int rc2 = dpgo::spd_refactor_device(F);
+        status[1] = spd_debug_status(rc2, F);
+        pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
+        if (status[1] < 0) return -1;
+        if (rc2 == 0 && solve(2) != 0) return -1;
+      }
+      return 1;
+    }
+    auto solve_host = [&](int k) {
+      std::copy(rhs, rhs + n, out + (size_t)k * n);
+      dpgo::spd_solve_host(F, out + (size_t)k * n, 1);
+    };
+    const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
+    status[0] = spd_debug_status(rc, F);
+    pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
+    if (status[0] < 0) return -1;
+    if (rc == 0) { solve_host(0); solve_host(1); }
+    if (refactor_val) {
+      A.val.assign(refactor_val, refactor_val + ptr[n]);
+      const int rc2 = dpgo::spd_refactor(A, F);
+      status[1] = spd_debug_status(rc2, F);
+      pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
+      if (status[1] < 0) return -1;
+      if (rc2 == 0) solve_host(2);
+    }
+    return 0;
+  });
+}
+
 // ---- test hook: the device solve (spd_solve.cpp) on a given matrix ----
 using dpgo::DeviceError;   // (what HIP_CHECK throws)
 struct dpgo_spd_solver_debug {
@@ -1508,6 +1587,33 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
   dpgo_group_free(grp);
   dpgo_graph_free(gw);
   return rc == 0 ? 0 : -1;
+}
+
+// ---- Newton polish (polish.h) ----
+void dpgo_polish_options_default(dpgo_polish_options_t *opt) {
+  if (!opt) return;
+  const dpgo::PolishOptions o;
+  opt->max_steps = o.max_steps; opt->max_tries = o.max_tries; opt->rel_tol = o.rel_tol; opt->grad_tol = o.grad_tol;
+  opt->anchor = 0;
+}
+
+int dpgo_group_polish(dpgo_group_t *h, const double *X, int ld, const dpgo_polish_options_t *opt, long long max_bytes,
+                      double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result) {
+  if (!h || !h->grp || !X || !Xout || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::PolishOptions o;
+    if (opt) { o.max_steps = opt->max_steps; o.max_tries = opt->max_tries; o.rel_tol = opt->rel_tol; o.grad_tol = opt->grad_tol; }
+    dpgo::PolishResult r;
+    const int rc = h->grp->polish(X, ld, opt ? opt->anchor : 0, o, max_bytes, Xout, ldout, log, log_cap, r);
+    result->outcome = r.outcome; result->steps = r.steps; result->factorisations = r.factorisations;
+    result->indefinite = r.indefinite; result->F_initial = r.F_initial; result->F_final = r.F_final;
+    result->grad_initial = r.grad_initial; result->grad_final = r.grad_final; result->hmax = r.hmax;
+    result->mu_final = r.mu_final; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
+    result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels; result->max_front = r.max_front;
+    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
+    result->factor_ms = r.factor_ms; result->solve_ms = r.solve_ms; result->other_ms = r.other_ms;
+    return rc;
+  });
 }
 
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {

@@ -10,24 +10,10 @@
 #include <numeric>
 
 #include "cert_state.h"
+#include "cov_state.h"
 #include "group.h"
 
 namespace dpgo {
-
-struct Group::CovState {
-  CsrMatrix A;                 // ptr / col only, unknowns dof p + a (p the unified own row): the values are written on the device
-  std::vector<int> bcol_h;     // per block of the certificate's pattern: the unified own row of its columns
-  DevBuf<int> bcol;
-  SpdFactor F;
-  std::vector<int> piv_front, piv_loc;   // per unknown: the front that eliminates it, its position among that front's pivots
-  bool have_symbolic = false;
-  double symbolic_s = 0;
-  long long bytes = 0;
-  ~CovState() {
-    spd_release_numeric(F);
-    spd_release_device(F);
-  }
-};
 
 void Group::cov_release() {
   delete cov_;
@@ -44,9 +30,8 @@ int Group::cov_begin(const double *X, int ld, int anchor) {
   return 0;
 }
 
-// The analysis (first call), the prediction, the refusal, the numeric context (first call that is not refused):
-// cert_factor_setup's rule.
-int Group::cov_setup(long long max_bytes, CovResult &out) {
+// The analysis (first call) and what it predicts: the pattern of H from the certificate's, its multifrontal analysis.
+int Group::cov_analyse(CovResult &out) {
   CertState &c = *cert_;
   CovState &s = *cov_;
   cert_build_pattern();
@@ -100,6 +85,13 @@ int Group::cov_setup(long long max_bytes, CovResult &out) {
     out.selinv_flops += 2 * u * u * w + 2 * u * w * w + w * w * w;
   }
   out.outcome = COV_SKIPPED;
+  return 0;
+}
+
+// The analysis, the refusal, the numeric context (first call that is not refused): cert_factor_setup's rule.
+int Group::cov_setup(long long max_bytes, CovResult &out) {
+  if (cov_analyse(out) != 0) return -1;
+  CovState &s = *cov_;
   if (max_bytes > 0 && s.bytes > max_bytes) return 1;
   if (!s.F.numeric) {
     size_t free_b = 0, total_b = 0;

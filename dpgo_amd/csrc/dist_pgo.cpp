@@ -27,6 +27,11 @@
 //              coordinates (translation in the world frame, rotation in the body frame) -- and one more line on stdout
 //                  covariance: <outcome> <unknowns> <fronts> <levels> <max_front> <device_bytes> <pivot_min> <stationarity>
 //              (NOT_PD or SKIPPED: FILE is not written); the same reasons as --certify when it is not computed
+//              --polish (likewise)  after the loop and ahead of --certify / --verify / --covariance, which then act on the polished
+//              point, for the trivial loss and a world of one rank: dpgo_group_polish (damped Riemannian Newton steps, pose 0
+//              the anchor) from the final X, and one more line on stdout
+//                  polish: <outcome> <steps> <factorisations> <indefinite> <F_initial> <F_final> <grad_initial> <grad_final>
+//              the result files then hold the polished X; the same reasons as --covariance when it is not computed
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -42,6 +47,7 @@
 // dpgo_group_dist_chordal_initialization and prints the stage objectives the reference prints every 20
 // iterations (:206-210); its stage 0 (a per-node SE-Sync solve in the reference) is the library's stand-in.
 // --dist_init false is the centralised chordal initialisation (:416-444).
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -62,7 +68,7 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false;
+  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false;
   std::string edge_report, covariance;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
@@ -80,6 +86,8 @@ int main(int argc, char **argv) {
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
+    else if (a == "--polish") polish = true;
+    else if (a.compare(0, 9, "--polish=") == 0) polish = parse_bool(argv[i] + 9);
     else if (a == "--verify") verify = true;
     else if (a.compare(0, 9, "--verify=") == 0) verify = parse_bool(argv[i] + 9);
     else if (a == "--verify_reweighted") verify_reweighted = true;
@@ -196,6 +204,33 @@ int main(int argc, char **argv) {
   if (root)
     printf("---------------------------------------\nfinal objective: %.20g\nfinal gradient: %.20g\ntime: %.20g s/node.\n", fobj,
            grad, time / per);
+  // the point every later step acts on: the optimiser's, or the polished one
+  std::vector<double> Xpol;
+  auto final_point = [&](double *out) -> int {
+    if (!Xpol.empty()) {
+      std::copy(Xpol.begin(), Xpol.end(), out);
+      return 0;
+    }
+    return dpgo_group_scatter_global(grp, out, ld);
+  };
+  if (polish) {
+    if (loss != 0) {
+      if (root) printf("polish: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("polish: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0);
+      dpgo_polish_result_t pr;
+      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+          dpgo_group_polish(grp, Xc.data(), ld, nullptr, 0, Z.data(), ld, nullptr, 0, &pr) != 0)
+        return -1;
+      printf("polish: %s %d %d %d %.17g %.17g %.17g %.17g\n",
+             pr.outcome == DPGO_POLISH_CONVERGED ? "CONVERGED" : pr.outcome == DPGO_POLISH_MAX_STEPS ? "MAX_STEPS"
+             : pr.outcome == DPGO_POLISH_STALLED ? "STALLED" : "SKIPPED",
+             pr.steps, pr.factorisations, pr.indefinite, pr.F_initial, pr.F_final, pr.grad_initial, pr.grad_final);
+      if (pr.outcome != DPGO_POLISH_SKIPPED) Xpol.swap(Z);
+    }
+  }
   if (certify) {
     if (loss != 0) {
       if (root) printf("certificate: not computed (the certificate is that of the trivial loss; --loss %s)\n", loss_type.c_str());
@@ -206,7 +241,7 @@ int main(int argc, char **argv) {
       dpgo_cert_options_t co;
       dpgo_cert_options_default(&co);
       dpgo_cert_result_t cr;
-      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 || dpgo_group_certify(grp, Xc.data(), ld, &co, nullptr, 0, &cr, nullptr, 0) != 0)
+      if (final_point(Xc.data()) != 0 || dpgo_group_certify(grp, Xc.data(), ld, &co, nullptr, 0, &cr, nullptr, 0) != 0)
         return -1;
       printf("certificate: %s %.16g %.16g %d %.16g\n",
              cr.status == DPGO_CERT_NEGATIVE ? "NEGATIVE" : cr.status == DPGO_CERT_NONNEGATIVE ? "NONNEGATIVE" : "UNDECIDED", cr.theta,
@@ -224,7 +259,7 @@ int main(int argc, char **argv) {
       dpgo_cert_options_default(&co);
       dpgo_cert_result_t cr;
       dpgo_cert_factor_t cf;
-      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+      if (final_point(Xc.data()) != 0 ||
           dpgo_group_verify(grp, Xc.data(), ld, &co, 0, nullptr, 0, &cr, nullptr, 0, &cf) != 0)
         return -1;
       printf("verification: %s %s %.16g %.16g %.16g %d %.16g\n",
@@ -240,7 +275,7 @@ int main(int argc, char **argv) {
       if (root && verify_reweighted) printf("reweighted verification: not computed (the group must host every node; %d ranks)\n", world);
     } else {
       std::vector<double> Xc((size_t)ld * d, 0.0);
-      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0) return -1;
+      if (final_point(Xc.data()) != 0) return -1;
       if (!edge_report.empty()) {
         std::vector<int> I(m), J(m);
         std::vector<double> sr(m), st(m), rho(m), w(m);
@@ -288,7 +323,7 @@ int main(int argc, char **argv) {
       const int dof = d + d * (d - 1) / 2;
       std::vector<double> Xc((size_t)ld * d, 0.0), marg((size_t)N * dof * dof, 0.0);
       dpgo_cov_result_t cv;
-      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+      if (final_point(Xc.data()) != 0 ||
           dpgo_group_covariance(grp, Xc.data(), ld, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0)
         return -1;
       printf("covariance: %s %d %d %d %d %lld %.16g %.16g\n",
@@ -309,7 +344,7 @@ int main(int argc, char **argv) {
   }
   if (save) {
     std::fill(X.begin(), X.end(), 0.0);
-    dpgo_group_scatter_global(grp, X.data(), ld);
+    final_point(X.data());
     if (comm) dpgo_comm_allreduce_sum(comm, X.data(), (long)X.size());   // every rank contributes its own poses
   }
   if (save && root) {

@@ -30,6 +30,7 @@
 #include "cov.h"
 #include "graph.h"
 #include "kernels.h"
+#include "polish.h"
 #include "schedule.h"
 #include "settings.h"
 #include "spd_solve.h"
@@ -190,6 +191,11 @@ class Group {
   int covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                  double *cross, CovResult &out);
   int cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz);
+  // Newton polish (polish.h): damped Riemannian Newton steps from X on the anchored tangent-space Hessian, factored in the
+  // covariance's numeric context and solved with spd_vsolve_device; Xout (ldout >= (d+1) N): the new point, written unless
+  // SKIPPED; log (optional, log_cap rows of POLISH_LOG_COLS doubles): one row per iteration
+  int polish(const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout, int ldout, double *log,
+             int log_cap, PolishResult &out);
   // boundary exchange across groups: records of the poses other groups need
   int num_sent() const { return (int)sent_rows_.size(); }
   // device buffer, num_sent()*RS doubles; st: the stream to enqueue on (default: the group's)
@@ -467,7 +473,9 @@ class Group {
   CovState *cov_ = nullptr;
   void cov_release();
   int cov_begin(const double *X, int ld, int anchor);
+  int cov_analyse(CovResult &out);                      // the pattern and the symbolic analysis (first call), the sizes
   int cov_setup(long long max_bytes, CovResult &out);   // 0: ready, 1: SKIPPED, -1: error
+  int polish_setup(long long max_bytes, PolishResult &out);   // likewise, for what polish allocates (polish.cpp)
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

@@ -152,6 +152,28 @@ int spd_selinv_device(SpdFactor &F, void *stream = nullptr);
 const double *spd_selinv_values(const SpdFactor &F);
 void spd_selinv_release(SpdFactor &F);
 
+// The device solve for ONE plain vector with the factor as the numeric phase leaves it (dev_W / dev_WT: row-major
+// (w + u) x ldw and w x ldm per front, no repacking into SpdSolverDev's panels): x (n doubles, device) <- A^-1 x.
+//   forward   one launch per tree height: [y_s ; upd_s] = W_s f_s, f_s the right-hand side on the pivots plus the children's
+//             update rows, pulled through per-position lists; y has a buffer of its own
+//   backward  one launch per tree depth: x_s = WT_s [y_s ; x(upd_idx)]: reads y and the parents' finished entries of x,
+//             writes pivots only
+// A workgroup takes 32 rows of one front and stages the front's input vector in LDS (2048 entries at a time); a wave does
+// whole rows, lanes striding the row, then a fixed shuffle tree.  No atomics: the same bits on every call.
+//   spd_vsolve_bytes    device bytes spd_vsolve_device allocates on its first call (y, the update buffer, the lists)
+//   spd_vsolve_device   for a factor with keep_device + keep_numeric that is not factor_only, behind a numeric phase that
+//                       succeeded (-1, and nothing computed, otherwise); runs on `stream` (nullptr: the factorisation's own)
+//                       and returns once it is enqueued
+//   spd_vsolve_release  frees what it allocated; spd_release_numeric does so too
+//   spd_vsolve_chunk    how many entries of a front's input vector the launches stage at a time: 1 ... 2048, anything else:
+//                       2048, the default and the size of the LDS array; returns the value before.  Process-wide; for the
+//                       tests, which want a chunk's edge inside fronts of a few hundred rows.  A multiple of 64 gives the bits
+//                       of the default (a lane's terms and their order do not change).
+int64_t spd_vsolve_bytes(const SpdFactor &F);
+int spd_vsolve_chunk(int chunk);
+int spd_vsolve_device(SpdFactor &F, double *x, void *stream = nullptr);
+void spd_vsolve_release(SpdFactor &F);
+
 // Host solve (setup paths and tests): X (n x ncols, row-major) <- A^-1 X.
 void spd_solve_host(const SpdFactor &F, double *X, int ncols);
 

@@ -799,7 +799,127 @@ struct SelinvLevel {
   int lvl_off = 0, nf_u = 0, max_u = 0;            // the level's fronts that have update rows: d_lvl + lvl_off, nf_u of them
   int t_off = 0, n_t = 0, pp_off = 0, n_pp = 0;    // (front, tile) pairs of MODE 0 / MODE 1 in d_items (counted in pairs)
 };
+
+// ---- the solve for one plain vector (spd.h: spd_vsolve_*) on W / WT as the factorisation leaves them ----
+struct VsolveDesc {
+  int w, u, ldw, ldm;
+  long long w_off, wt_off;
+  int piv_ptr, upd_ptr, pos_off, ubuf_off;   // first pivot in piv_idx, update row in upd_idx, position in asm_ptr, row of ub
+};
+constexpr int VS_ROWS = 32;      // rows of one front per workgroup: eight per wave
+constexpr int VS_CHUNK = 2048;   // doubles of a front's input vector staged in LDS at a time (16 KiB); a launch may ask for fewer
+int vs_chunk = VS_CHUNK;         // spd_vsolve_chunk: what the launches ask for
+
+__device__ __forceinline__ double vs_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// position p of front f's assembled vector: the right-hand side on a pivot, plus the children's update rows in list order
+__device__ __forceinline__ double vs_assembled(const VsolveDesc &f, int p, const int *__restrict__ piv_idx,
+                                               const int *__restrict__ asm_ptr, const int *__restrict__ asm_src,
+                                               const double *__restrict__ x, const double *ub) {
+  double v = p < f.w ? x[piv_idx[f.piv_ptr + p]] : 0.0;
+  for (int a = asm_ptr[f.pos_off + p]; a < asm_ptr[f.pos_off + p + 1]; a++) v += ub[asm_src[a]];
+  return v;
+}
+
+// Forward: [y_s ; upd_s] = W_s f_s (+ f_s on the update rows), the fronts of one tree height.  items = (front, first row)
+// pairs, one per workgroup; the pivots' part of f_s goes through LDS VS_CHUNK entries at a time, each wave keeps the
+// partial sums of its eight rows per lane across the chunks (lanes stride the row: coalesced), then one fixed shuffle tree
+// per row and one lane stores.  y and ub are written, x and the children's ub (an earlier launch) are read.
+__global__ __launch_bounds__(256) void k_vs_forward(const VsolveDesc *__restrict__ vd, const int *__restrict__ items,
+                                                    const double *__restrict__ W, const int *__restrict__ piv_idx,
+                                                    const int *__restrict__ asm_ptr, const int *__restrict__ asm_src,
+                                                    const double *__restrict__ x, double *__restrict__ y, double *ub, int chunk) {
+  constexpr int RW = VS_ROWS / 4;
+  const VsolveDesc f = vd[items[2 * blockIdx.x]];
+  const int r0 = items[2 * blockIdx.x + 1], m = f.w + f.u;
+  __shared__ double fs[VS_CHUNK];
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  double acc[RW];
+#pragma unroll
+  for (int i = 0; i < RW; i++) acc[i] = 0.0;
+  for (int k0 = 0; k0 < f.w; k0 += chunk) {
+    const int kn = min(chunk, f.w - k0);
+    __syncthreads();
+    for (int k = t; k < kn; k += 256) fs[k] = vs_assembled(f, k0 + k, piv_idx, asm_ptr, asm_src, x, ub);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RW; i++) {
+      const int p = r0 + wv * RW + i;
+      if (p < m) {
+        const double *row = W + f.w_off + (long long)p * f.ldw + k0;
+        double s = acc[i];
+        for (int k = lane; k < kn; k += 64) s = fma(row[k], fs[k], s);
+        acc[i] = s;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < RW; i++) {
+    const int p = r0 + wv * RW + i;
+    const double v = vs_wave_sum(acc[i]);
+    if (lane == 0 && p < m) {
+      if (p < f.w) y[piv_idx[f.piv_ptr + p]] = v;
+      else ub[f.ubuf_off + p - f.w] = v + vs_assembled(f, p, piv_idx, asm_ptr, asm_src, x, ub);
+    }
+  }
+}
+
+// Backward: x_s = WT_s [y_s ; x(upd_idx)], the fronts of one tree depth; the same shape over the rows of WT_s (w of them,
+// w + u long).  Reads y and the entries of x that fronts of smaller depth have finished, writes the pivots of x.
+__global__ __launch_bounds__(256) void k_vs_backward(const VsolveDesc *__restrict__ vd, const int *__restrict__ items,
+                                                     const double *__restrict__ WT, const int *__restrict__ piv_idx,
+                                                     const int *__restrict__ upd_idx, const double *__restrict__ y, double *x, int chunk) {
+  constexpr int RW = VS_ROWS / 4;
+  const VsolveDesc f = vd[items[2 * blockIdx.x]];
+  const int r0 = items[2 * blockIdx.x + 1], m = f.w + f.u;
+  __shared__ double fs[VS_CHUNK];
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  double acc[RW];
+#pragma unroll
+  for (int i = 0; i < RW; i++) acc[i] = 0.0;
+  for (int k0 = 0; k0 < m; k0 += chunk) {
+    const int kn = min(chunk, m - k0);
+    __syncthreads();
+    for (int k = t; k < kn; k += 256) {
+      const int p = k0 + k;
+      fs[k] = p < f.w ? y[piv_idx[f.piv_ptr + p]] : x[upd_idx[f.upd_ptr + p - f.w]];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RW; i++) {
+      const int r = r0 + wv * RW + i;
+      if (r < f.w) {
+        const double *row = WT + f.wt_off + (long long)r * f.ldm + k0;
+        double s = acc[i];
+        for (int k = lane; k < kn; k += 64) s = fma(row[k], fs[k], s);
+        acc[i] = s;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < RW; i++) {
+    const int r = r0 + wv * RW + i;
+    const double v = vs_wave_sum(acc[i]);
+    if (lane == 0 && r < f.w) x[piv_idx[f.piv_ptr + r]] = v;
+  }
+}
 }  // namespace
+
+// what the first spd_vsolve_device builds and every later one runs
+struct SpdVsolveCtx {
+  std::vector<std::pair<int, int>> fwd, bwd;   // per tree height / depth: (first pair in d_items, pairs)
+  VsolveDesc *d_vd = nullptr;
+  int *d_items = nullptr, *d_piv = nullptr, *d_upd = nullptr, *d_asm_ptr = nullptr, *d_asm_src = nullptr;
+  double *d_y = nullptr, *d_ub = nullptr;
+  ~SpdVsolveCtx() {
+    for (void *q : {(void *)d_vd, (void *)d_items, (void *)d_piv, (void *)d_upd, (void *)d_asm_ptr, (void *)d_asm_src, (void *)d_y, (void *)d_ub})
+      if (q) (void)hipFree(q);
+  }
+};
 
 struct SpdSelinvCtx {
   std::vector<SelinvLevel> levels;
@@ -847,8 +967,10 @@ struct SpdNumericCtx {
     if (st) (void)hipStreamDestroy(st);
     if (h_io) (void)hipHostFree(h_io);
     delete selinv;
+    delete vsolve;
   }
   SpdSelinvCtx *selinv = nullptr;   // spd_selinv_device: built on its first call
+  SpdVsolveCtx *vsolve = nullptr;   // spd_vsolve_device: likewise
   std::vector<int> cmap_host;       // the child -> parent position maps, kept for it (cmap_off[c] = F.ubuf_off[c])
   int build(const CsrMatrix &A, const SpdFactor &F, const std::vector<std::vector<int>> &children);
   // on: the stream to run on (nullptr: the context's own); defer: return once everything is enqueued -- finish() waits
@@ -1425,6 +1547,130 @@ void spd_selinv_release(SpdFactor &F) {
   if (!F.numeric) return;
   delete F.numeric->selinv;
   F.numeric->selinv = nullptr;
+}
+
+// ---- the solve for one plain vector ----
+namespace {
+int64_t vsolve_items(const SpdFactor &F) {
+  int64_t items = 0;
+  for (int f = 0; f < F.nfronts; f++) items += (F.w[f] + F.u[f] + VS_ROWS - 1) / VS_ROWS + (F.w[f] + VS_ROWS - 1) / VS_ROWS;
+  return items;
+}
+}  // namespace
+
+int64_t spd_vsolve_bytes(const SpdFactor &F) {
+  const int nt = F.nfronts;
+  if ((int)F.upd_ptr.size() != nt + 1) return 0;
+  return 8 * ((int64_t)F.n + F.total_upd) + 4 * ((int64_t)F.n + F.upd_ptr[nt] + F.total_pos + 1 + F.total_upd) +
+         (int64_t)sizeof(VsolveDesc) * nt + 8 * vsolve_items(F);
+}
+
+int spd_vsolve_device(SpdFactor &F, double *x, void *stream) {
+  SpdNumericCtx *ctx = F.numeric;
+  if (!x || !ctx || ctx->factor_only || !ctx->d_W || !ctx->d_WT || !ctx->outputs_zeroed) return -1;
+  if (ctx->pending && ctx->finish(F) != 0) return -1;
+  if (F.not_pd) return -1;   // nothing is solved with a factorisation that met a non-positive pivot
+  const int nt = ctx->nt;
+  if (!ctx->vsolve) {
+    std::unique_ptr<SpdVsolveCtx> vc(new SpdVsolveCtx());
+    if ((int)F.parent.size() != nt || (int)F.pos_off.size() != nt + 1 || (int)F.ubuf_off.size() != nt + 1) return -1;
+    std::vector<int> height(nt, 0), depth(nt, 0);
+    int maxh = 0, maxd = 0;
+    for (int f = 0; f < nt; f++)
+      if (F.parent[f] >= 0) {
+        if (F.parent[f] <= f || F.parent[f] >= nt) return -1;   // (post-order: a parent comes after its children)
+        height[F.parent[f]] = std::max(height[F.parent[f]], height[f] + 1);
+      }
+    for (int f = nt - 1; f >= 0; f--) {
+      if (F.parent[f] >= 0) depth[f] = depth[F.parent[f]] + 1;
+      maxh = std::max(maxh, height[f]);
+      maxd = std::max(maxd, depth[f]);
+    }
+    // the pull lists: per front position the rows of the update buffer to add, the children in ascending order (the child
+    // -> parent position maps the factorisation already has, read the other way)
+    std::vector<VsolveDesc> vd(std::max(nt, 1));
+    std::vector<int> asm_cnt(F.total_pos + 1, 0);
+    for (int c = 0; c < nt; c++) {
+      VsolveDesc &d = vd[c];
+      d.w = F.w[c]; d.u = F.u[c]; d.ldw = F.ldw[c]; d.ldm = F.ldm[c];
+      d.w_off = F.w_off[c]; d.wt_off = F.wt_off[c];
+      d.piv_ptr = F.piv_ptr[c]; d.upd_ptr = F.upd_ptr[c]; d.pos_off = F.pos_off[c]; d.ubuf_off = F.ubuf_off[c];
+      if (d.u == 0) continue;
+      const int p = F.parent[c];
+      if (p < 0) return -1;
+      const int mp = F.w[p] + F.u[p];
+      for (int a = 0; a < d.u; a++) {
+        const int la = ctx->cmap_host[d.ubuf_off + a];
+        if (la < 0 || la >= mp) return -1;
+        asm_cnt[F.pos_off[p] + la + 1]++;
+      }
+    }
+    std::vector<int> asm_ptr(asm_cnt);
+    for (int p = 0; p < F.total_pos; p++) asm_ptr[p + 1] += asm_ptr[p];
+    std::vector<int> asm_src(std::max(asm_ptr[F.total_pos], 1), 0), fill(asm_ptr.begin(), asm_ptr.end() - 1);
+    for (int c = 0; c < nt; c++)
+      for (int a = 0; a < F.u[c]; a++)
+        asm_src[fill[F.pos_off[F.parent[c]] + ctx->cmap_host[F.ubuf_off[c] + a]]++] = F.ubuf_off[c] + a;
+    for (int v : F.piv_idx)
+      if (v < 0 || v >= F.n) return -1;
+    for (int v : F.upd_idx)
+      if (v < 0 || v >= F.n) return -1;
+    if ((int)F.piv_idx.size() != F.n) return -1;
+    std::vector<int> items;
+    for (int h = 0; h <= maxh; h++) {
+      const int first = (int)items.size() / 2;
+      for (int f = 0; f < nt; f++)
+        if (height[f] == h)
+          for (int r0 = 0; r0 < F.w[f] + F.u[f]; r0 += VS_ROWS) { items.push_back(f); items.push_back(r0); }
+      vc->fwd.push_back({first, (int)items.size() / 2 - first});
+    }
+    for (int dp = 0; dp <= maxd; dp++) {
+      const int first = (int)items.size() / 2;
+      for (int f = 0; f < nt; f++)
+        if (depth[f] == dp)
+          for (int r0 = 0; r0 < F.w[f]; r0 += VS_ROWS) { items.push_back(f); items.push_back(r0); }
+      vc->bwd.push_back({first, (int)items.size() / 2 - first});
+    }
+    FA_OK(hipMalloc((void **)&vc->d_vd, sizeof(VsolveDesc) * vd.size()));
+    FA_OK(hipMalloc((void **)&vc->d_items, sizeof(int) * std::max<size_t>(items.size(), 2)));
+    FA_OK(hipMalloc((void **)&vc->d_piv, sizeof(int) * std::max<size_t>(F.piv_idx.size(), 1)));
+    FA_OK(hipMalloc((void **)&vc->d_upd, sizeof(int) * std::max<size_t>(F.upd_idx.size(), 1)));
+    FA_OK(hipMalloc((void **)&vc->d_asm_ptr, sizeof(int) * asm_ptr.size()));
+    FA_OK(hipMalloc((void **)&vc->d_asm_src, sizeof(int) * asm_src.size()));
+    FA_OK(hipMalloc((void **)&vc->d_y, sizeof(double) * std::max(F.n, 1)));
+    FA_OK(hipMalloc((void **)&vc->d_ub, sizeof(double) * std::max(F.total_upd, 1)));
+    FA_OK(hipMemcpy(vc->d_vd, vd.data(), sizeof(VsolveDesc) * vd.size(), hipMemcpyHostToDevice));
+    if (!items.empty()) FA_OK(hipMemcpy(vc->d_items, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+    if (!F.piv_idx.empty()) FA_OK(hipMemcpy(vc->d_piv, F.piv_idx.data(), sizeof(int) * F.piv_idx.size(), hipMemcpyHostToDevice));
+    if (!F.upd_idx.empty()) FA_OK(hipMemcpy(vc->d_upd, F.upd_idx.data(), sizeof(int) * F.upd_idx.size(), hipMemcpyHostToDevice));
+    FA_OK(hipMemcpy(vc->d_asm_ptr, asm_ptr.data(), sizeof(int) * asm_ptr.size(), hipMemcpyHostToDevice));
+    FA_OK(hipMemcpy(vc->d_asm_src, asm_src.data(), sizeof(int) * asm_src.size(), hipMemcpyHostToDevice));
+    ctx->vsolve = vc.release();
+  }
+  const SpdVsolveCtx &vc = *ctx->vsolve;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->st;
+  for (const auto &L : vc.fwd)
+    if (L.second > 0)
+      hipLaunchKernelGGL(k_vs_forward, dim3(L.second), dim3(256), 0, st, vc.d_vd, vc.d_items + 2 * L.first, ctx->d_W, vc.d_piv,
+                         vc.d_asm_ptr, vc.d_asm_src, x, vc.d_y, vc.d_ub, vs_chunk);
+  for (const auto &L : vc.bwd)
+    if (L.second > 0)
+      hipLaunchKernelGGL(k_vs_backward, dim3(L.second), dim3(256), 0, st, vc.d_vd, vc.d_items + 2 * L.first, ctx->d_WT, vc.d_piv,
+                         vc.d_upd, vc.d_y, x, vs_chunk);
+  FA_OK(hipGetLastError());
+  return 0;
+}
+
+int spd_vsolve_chunk(int chunk) {
+  const int before = vs_chunk;
+  vs_chunk = chunk >= 1 && chunk <= VS_CHUNK ? chunk : VS_CHUNK;
+  return before;
+}
+
+void spd_vsolve_release(SpdFactor &F) {
+  if (!F.numeric) return;
+  delete F.numeric->vsolve;
+  F.numeric->vsolve = nullptr;
 }
 
 void spd_release_numeric(SpdFactor &F) {

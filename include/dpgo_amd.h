@@ -543,6 +543,57 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
                                      int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                      double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary);
 
+/* ---- Newton polish: from the point the optimiser stopped at to a critical point ----------- */
+/* AMM-PGO# is a first-order method; the certificate and the covariances above mean something only at a critical point.
+ * dpgo_group_polish takes damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored tangent-space Hessian
+ * H of dpgo_group_covariance, written, factored and solved on the device -- until the tangent gradient g is at rounding
+ * level or the step budget is spent:
+ *     mu = 0;  for k = 0 ... max_steps:
+ *         g, |g|, F0, H, hmax at X                      (hmax: the largest diagonal entry of H over the non-anchor unknowns)
+ *         |g| <= (grad_tol > 0 ? grad_tol : rel_tol hmax) -> CONVERGED;   k == max_steps -> MAX_STEPS
+ *         at most max_tries times:  factor H + mu I;  not positive definite: indefinite += 1 if mu == 0,
+ *                                   mu = max(10 mu, 1e-3 hmax), next try
+ *             delta = -(H + mu I)^-1 g;  Z = retract(X, delta);  F1 = F(Z)
+ *             pred = -1/2 g'delta + 1/2 mu |delta|^2;  rho = pred > 0 ? (F0 - F1) / pred : -1
+ *             accept if rho >= 0.1 or |F0 - F1| <= 1e-13 |F0|:  X = Z;  rho > 0.75: mu /= 10, and mu = 0 once mu < 1e-8 hmax
+ *             else mu = max(10 mu, 1e-3 hmax)
+ *         no try accepted -> STALLED (the last accepted point is returned)
+ * retract: t_p + dt, R_p Exp(hat(omega)) in the coordinates of dpgo_group_covariance.  F never increases except through the
+ * rounding clause.  The same restrictions as the covariance: the TRIVIAL LOSS only, the group must HOST EVERY NODE, the global
+ * pose opt->anchor is held fixed (its rows of Xout are those of X bit for bit); -1 otherwise.  The optimiser's state is not touched.
+ *   opt     NULL: the defaults
+ *   Xout    (d+1) N x d column-major, ldout >= (d+1) N: the new point (not written for SKIPPED); may be X itself
+ *   log     optional, log_cap rows of 5 doubles: per iteration k its F0, |g|, mu at entry, rho of the accepted try, tries
+ *   result  outcome; steps (accepted), factorisations, indefinite (factorisations at mu = 0 that met a non-positive pivot:
+ *           the starting region was not convex); F and |g| at the first and the last point, hmax and mu at the end, the pivot
+ *           range of the last factor; unknowns, fronts, levels, max_front, device_bytes from the symbolic analysis (filled for
+ *           SKIPPED too); symbolic_s: host seconds of the analysis (0 after a group's first covariance or polish call);
+ *           total_ms and its parts: factor_ms (the Hessian from its launch to the read-back behind it, and the
+ *           factorisations up to their verdicts), solve_ms (the vector
+ *           solves with the retraction and F(Z) behind them), other_ms.
+ * SKIPPED when what polish allocates -- the numeric phase, the vector solve, three vectors; not the blocks of the selected
+ * inversion -- is more than max_bytes (> 0), or what of it is still to be allocated is more than half of the free device
+ * memory: nothing is allocated then. */
+#define DPGO_POLISH_CONVERGED 0
+#define DPGO_POLISH_MAX_STEPS 1
+#define DPGO_POLISH_STALLED 2
+#define DPGO_POLISH_SKIPPED 3
+typedef struct dpgo_polish_options {
+  int max_steps, max_tries;   /* 20, 8 */
+  double rel_tol, grad_tol;   /* 1e-9, 0 */
+  int anchor;                 /* 0: the global pose held fixed */
+} dpgo_polish_options_t;
+typedef struct dpgo_polish_result {
+  int outcome, steps, factorisations, indefinite;
+  double F_initial, F_final, grad_initial, grad_final, hmax, mu_final, pivot_min, pivot_max;
+  int unknowns, fronts, levels, max_front;
+  long long device_bytes;
+  double symbolic_s, total_ms, factor_ms, solve_ms, other_ms;
+} dpgo_polish_result_t;
+void dpgo_polish_options_default(dpgo_polish_options_t *opt);
+int dpgo_group_polish(dpgo_group_t *grp, const double *X, int ld, const dpgo_polish_options_t *opt, long long max_bytes,
+                      double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result);
+
 /* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
  * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
  * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:
@@ -616,6 +667,21 @@ int dpgo_debug_spd_selinv_get(const dpgo_spd_selinv_debug_t *h, long long *sizes
                               int *piv_idx, int *upd_idx, double *sigma, double *sigma_again, double *sigma2,
                               double *W_before, double *W_after);
 void dpgo_debug_spd_selinv_free(dpgo_spd_selinv_debug_t *h);
+/* The device solve for ONE plain vector on a given SPD CSR matrix (tests/test_polish_host.py, tests/test_gpu_vsolve_fronts.py):
+ * spd_factor(A, F, leaf, collapse, block), quiet, then
+ *   on the device (host == 0 and a HIP device): keep_device + keep_numeric, spd_vsolve_device on a copy of rhs, twice;
+ *   on the host (host != 0, or no device): spd_solve_host, twice;
+ * and with refactor_val the second values through the kept context (spd_refactor_device; on the host spd_refactor) and one
+ * more solve.  out holds 3 n doubles: the first solution, its repetition, the second values' solution.  A part whose
+ * factorisation met a non-positive pivot is not written.
+ *   status[2]   verdict of the first factorisation (0 factored, 1 not positive definite) and of the second (-1: none given)
+ *   pivots[4]   pivot_min, pivot_max of the first and of the second factorisation
+ * Returns 1 when the device ran, 0 when the host did, -1 on an error or a bad argument. */
+int dpgo_debug_spd_vsolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, const double *rhs, double *out, int *status, double *pivots);
+/* How many entries of a front's input vector spd_vsolve_device stages in LDS at a time: 1 ... 2048, anything else restores the
+ * default 2048.  Process-wide; returns the value before.  For the tests: a chunk's edge inside fronts of a few hundred rows. */
+int dpgo_debug_spd_vsolve_chunk(int chunk);
 /* The device solve on a given matrix (tests/test_gpu_solve_tiles.py): an SpdSolverDev built as a group builds its own --
  * spd_factor(A, F, leaf, collapse, block) with the factor left on the device unless DPGO_SPD_DEVICE_PANELS=0, then
  * upload(dof, d, node_of_unknown) -- and spd_run on it.  The hook calls what exists; it adds nothing to spd_run or the kernels.

@@ -22,6 +22,7 @@
 #ifndef DPGO_AMD_HPP
 #define DPGO_AMD_HPP
 
+#include <algorithm>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -255,6 +256,27 @@ class DPGOHashGroup {
     if (status) *status = rc == 0 ? r.outcome : -1;
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_COV_OK;
+  }
+  // Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X on the anchored tangent-space Hessian of
+  // marginal_covariances, until the tangent gradient is at rounding level or the step budget is spent.  Xout: the new point
+  // (X itself when the call is SKIPPED or fails).  opt (optional): the rule's parameters and the anchor; log (optional): per
+  // iteration F0, |g|, mu at entry, rho of the accepted try, tries.  Returns true for DPGO_POLISH_CONVERGED; status: the
+  // DPGO_POLISH_* outcome, -1 when the call itself failed (robust loss, a group that does not host every node, a bad anchor).
+  bool newton_polish(const Matrix &X, Matrix &Xout, dpgo_polish_result_t *result = nullptr, int *status = nullptr,
+                     const dpgo_polish_options_t *opt = nullptr, long long max_bytes = 0, std::vector<Scalar> *log = nullptr) const {
+    dpgo_polish_options_t o;
+    dpgo_polish_options_default(&o);
+    if (opt) o = *opt;
+    Xout = X;
+    const int cap = o.max_steps >= 0 ? o.max_steps + 1 : 0;
+    if (log) log->assign((size_t)cap * 5, 0.0);
+    dpgo_polish_result_t r = {};
+    const int rc = dpgo_group_polish(h_, X.data(), X.rows(), &o, max_bytes, Xout.data(), Xout.rows(), log ? log->data() : nullptr,
+                                     log ? cap : 0, &r);
+    if (log) log->resize(rc == 0 && r.outcome != DPGO_POLISH_SKIPPED ? (size_t)std::min(cap, r.steps + 1) * 5 : 0);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
   const Graph &graph() const { return *graph_; }
   dpgo_group_t *handle() const { return h_; }
