@@ -243,6 +243,13 @@ SYMBOLS = {
                                                    _IP, C.c_int, _DP, _DP, C.c_void_p, C.c_void_p]),
     "dpgo_polish_options_default": (None, [C.c_void_p]),
     "dpgo_group_polish": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, C.c_void_p]),
+    "dpgo_staircase_options_default": (None, [C.c_void_p]),
+    "dpgo_group_staircase": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int,
+                                       C.c_void_p]),
+    "dpgo_group_stair_eval": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP, _DP, C.c_int]),
+    "dpgo_group_stair_hess": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
+    "dpgo_group_stair_retract": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
+    "dpgo_group_stair_round": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP, C.c_int]),
     "dpgo_group_verify": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, C.c_void_p, _DP, C.c_int,
                                     C.c_void_p]),
     "dpgo_group_cert_matrix": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
@@ -1054,6 +1061,69 @@ class NodeGroup:
         rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
         return Xout, r, log[:rows].copy()
 
+    def staircase(self, X, max_bytes=0, **opts):
+        """The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- TNT at
+        rank r, verify at Lambda(Y), an escape along the certificate's direction one rank up, until the certificate is not
+        NEGATIVE or r = r_max <= 2d; then the rounding back to SO(d)^N and a polish.  Trivial-loss groups that host every
+        node.  opts: the fields of StaircaseOptions.  Returns (Xhat, StaircaseResult, log, Y): the result (X itself for
+        STAIR_SKIPPED; never worse than X), the result struct, one row per level of (rank, F in, F out, |grad|, TNT iterations,
+        Hessian products, certificate status, theta, accepted alpha, halvings), and the final lifted point (d+1)N x 2d.
+        result.gap = F_final - F_sdp bounds the distance to the global minimum only where cert_status is CERT_PROVEN and
+        stationarity is small.  The optimiser's state is not touched."""
+        X, ld = _fcol(X)
+        o = StaircaseOptions(**opts)
+        Xhat = np.array(X, order="F")
+        Y = np.zeros((X.shape[0], 2 * self.d), order="F")
+        log = np.zeros((self.d + 1, 10))
+        r = StaircaseResult()
+        if lib().dpgo_group_staircase(self._h, _dp(X), ld, C.byref(o), int(max_bytes), _dp(Xhat), Xhat.shape[0], _dp(Y), Y.shape[0],
+                                      _dp(log), len(log), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_staircase failed (robust loss, a group that does not host every node, r_max outside "
+                               "[d, 2d], or bad sizes or options)")
+        return Xhat, r, log[:min(len(log), r.levels)].copy(), Y
+
+    def _lifted(self, Y, what):
+        Y, ld = _fcol(Y)
+        if Y.shape[1] != 2 * self.d:
+            raise ValueError("%s: a lifted point is (d+1)N x 2d" % what)
+        return Y, ld
+
+    def stair_eval(self, Y):
+        """Debug: (F, |grad F|, Lambda (N, d, d), grad = S Y) at the lifted point Y, (d+1)N x 2d with zero columns >= r."""
+        Y, ld = self._lifted(Y, "stair_eval")
+        N = Y.shape[0] // (self.d + 1)
+        F, gn = C.c_double(0), C.c_double(0)
+        Lam, G = np.zeros((N, self.d, self.d)), np.zeros(Y.shape, order="F")
+        if lib().dpgo_group_stair_eval(self._h, _dp(Y), ld, C.byref(F), C.byref(gn), _dp(Lam), _dp(G), G.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_stair_eval failed")
+        return F.value, gn.value, Lam, G
+
+    def stair_hess(self, Y, V):
+        """Debug: Hess[V] = Proj_Y(S(Y) V) at the lifted point Y."""
+        Y, ld = self._lifted(Y, "stair_hess")
+        V, ldv = self._lifted(V, "stair_hess")
+        out = np.zeros(Y.shape, order="F")
+        if lib().dpgo_group_stair_hess(self._h, _dp(Y), ld, _dp(V), ldv, _dp(out), out.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_stair_hess failed")
+        return out
+
+    def stair_retract(self, Y, V):
+        """Debug: the polar retraction of Y + V."""
+        Y, ld = self._lifted(Y, "stair_retract")
+        V, ldv = self._lifted(V, "stair_retract")
+        Z = np.zeros(Y.shape, order="F")
+        if lib().dpgo_group_stair_retract(self._h, _dp(Y), ld, _dp(V), ldv, _dp(Z), Z.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_stair_retract failed")
+        return Z
+
+    def stair_round(self, Y):
+        """Debug: the rounding of the lifted point Y: (B (2d, d), the 2d singular values, Xhat before any polish)."""
+        Y, ld = self._lifted(Y, "stair_round")
+        B, sig, Xh = np.zeros((2 * self.d, self.d)), np.zeros(2 * self.d), np.zeros((Y.shape[0], self.d), order="F")
+        if lib().dpgo_group_stair_round(self._h, _dp(Y), ld, _dp(B), _dp(sig), _dp(Xh), Xh.shape[0]) != 0:
+            raise RuntimeError("dpgo_group_stair_round failed")
+        return B, sig, Xh
+
     def cov_hessian(self, X, anchor=0):
         """Debug: the matrix covariance factors, the anchored tangent-space Hessian, read back from the device: CSR (ptr, col,
         val) on the unknowns dof g + a of the global poses g, every stored dof x dof block dense, the anchor's row and
@@ -1390,6 +1460,38 @@ class PolishResult(C.Structure):
                 ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
                 ("device_bytes", C.c_longlong), ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("factor_ms", C.c_double),
                 ("solve_ms", C.c_double), ("other_ms", C.c_double)]
+
+
+STAIR_SOLVED, STAIR_MAX_RANK, STAIR_SADDLE, STAIR_SKIPPED = 0, 1, 2, 3
+STAIR_NAMES = {0: "SOLVED", 1: "MAX_RANK", 2: "SADDLE", 3: "SKIPPED"}
+
+
+class StaircaseOptions(C.Structure):
+    """dpgo_staircase_options_t: the optimiser's options under SESyncOpts' names, r_max (0: 2d), precondition, polish,
+    min_eig_num_tol, max_factor_bytes."""
+    _fields_ = [("grad_norm_tol", C.c_double), ("preconditioned_grad_norm_tol", C.c_double), ("rel_func_decrease_tol", C.c_double),
+                ("stepsize_tol", C.c_double), ("max_iterations", C.c_int), ("max_tCG_iterations", C.c_int),
+                ("STPCG_kappa", C.c_double), ("STPCG_theta", C.c_double), ("r_max", C.c_int), ("precondition", C.c_int),
+                ("polish", C.c_int), ("reserved", C.c_int), ("min_eig_num_tol", C.c_double), ("max_factor_bytes", C.c_longlong)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().dpgo_staircase_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("StaircaseOptions has no field %r" % k)
+            setattr(self, k, v)
+
+
+class StaircaseResult(C.Structure):
+    """dpgo_staircase_result_t: the outcome of NodeGroup.staircase, the last certificate, the ranks, the counts, F at the four
+    points, gap, the singular values, the bytes and the times."""
+    _fields_ = [("outcome", C.c_int), ("cert_status", C.c_int), ("final_rank", C.c_int), ("levels", C.c_int),
+                ("tnt_iterations", C.c_int), ("hess_products", C.c_int), ("replaced_by_input", C.c_int), ("polish_outcome", C.c_int),
+                ("theta", C.c_double), ("stationarity", C.c_double), ("F_initial", C.c_double), ("F_sdp", C.c_double),
+                ("F_rounded", C.c_double), ("F_final", C.c_double), ("gap", C.c_double), ("sigma", C.c_double * 6),
+                ("device_bytes", C.c_longlong), ("optimise_ms", C.c_double), ("verify_ms", C.c_double), ("round_ms", C.c_double),
+                ("total_ms", C.c_double)]
 
 
 class CertOptions(C.Structure):

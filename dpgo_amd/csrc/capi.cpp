@@ -1616,6 +1616,61 @@ int dpgo_group_polish(dpgo_group_t *h, const double *X, int ld, const dpgo_polis
   });
 }
 
+// ---- the Riemannian staircase (stair.h) ----
+void dpgo_staircase_options_default(dpgo_staircase_options_t *opt) {
+  if (!opt) return;
+  const dpgo::StairOptions o;
+  opt->grad_norm_tol = o.grad_norm_tol; opt->preconditioned_grad_norm_tol = o.preconditioned_grad_norm_tol;
+  opt->rel_func_decrease_tol = o.rel_func_decrease_tol; opt->stepsize_tol = o.stepsize_tol;
+  opt->max_iterations = o.max_iterations; opt->max_tCG_iterations = o.max_tCG_iterations;
+  opt->STPCG_kappa = o.STPCG_kappa; opt->STPCG_theta = o.STPCG_theta; opt->r_max = o.r_max; opt->precondition = o.precondition;
+  opt->polish = o.polish; opt->reserved = 0; opt->min_eig_num_tol = o.min_eig_num_tol; opt->max_factor_bytes = o.max_factor_bytes;
+}
+
+int dpgo_group_staircase(dpgo_group_t *h, const double *X, int ld, const dpgo_staircase_options_t *opt, long long max_bytes,
+                         double *Xhat, int ldx, double *Y, int ldy, double *log, int log_cap, dpgo_staircase_result_t *result) {
+  if (!h || !h->grp || !X || !Xhat || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::StairOptions o;
+    if (opt) {
+      o.grad_norm_tol = opt->grad_norm_tol; o.preconditioned_grad_norm_tol = opt->preconditioned_grad_norm_tol;
+      o.rel_func_decrease_tol = opt->rel_func_decrease_tol; o.stepsize_tol = opt->stepsize_tol;
+      o.max_iterations = opt->max_iterations; o.max_tCG_iterations = opt->max_tCG_iterations;
+      o.STPCG_kappa = opt->STPCG_kappa; o.STPCG_theta = opt->STPCG_theta; o.r_max = opt->r_max; o.precondition = opt->precondition;
+      o.polish = opt->polish; o.min_eig_num_tol = opt->min_eig_num_tol; o.max_factor_bytes = opt->max_factor_bytes;
+    }
+    dpgo::StairResult r;
+    const int rc = h->grp->staircase(X, ld, o, max_bytes, Xhat, ldx, Y, ldy, log, log_cap, r);
+    result->outcome = r.outcome; result->cert_status = r.cert_status; result->final_rank = r.final_rank; result->levels = r.levels;
+    result->tnt_iterations = r.tnt_iterations; result->hess_products = r.hess_products;
+    result->replaced_by_input = r.replaced_by_input; result->polish_outcome = r.polish_outcome; result->theta = r.theta;
+    result->stationarity = r.stationarity; result->F_initial = r.F_initial; result->F_sdp = r.F_sdp;
+    result->F_rounded = r.F_rounded; result->F_final = r.F_final; result->gap = r.gap;
+    for (int i = 0; i < 6; i++) result->sigma[i] = r.sigma[i];
+    result->device_bytes = r.device_bytes; result->optimise_ms = r.optimise_ms; result->verify_ms = r.verify_ms;
+    result->round_ms = r.round_ms; result->total_ms = r.total_ms;
+    return rc;
+  });
+}
+
+int dpgo_group_stair_eval(dpgo_group_t *h, const double *Y, int ldy, double *F, double *grad_norm, double *Lambda, double *grad,
+                          int ldg) {
+  if (!h || !h->grp || !Y || !F || !grad_norm) return -1;
+  return guarded([&] { return h->grp->stair_eval(Y, ldy, F, grad_norm, Lambda, grad, ldg); });
+}
+int dpgo_group_stair_hess(dpgo_group_t *h, const double *Y, int ldy, const double *V, int ldv, double *out, int ldo) {
+  if (!h || !h->grp || !Y || !V || !out) return -1;
+  return guarded([&] { return h->grp->stair_hess(Y, ldy, V, ldv, out, ldo); });
+}
+int dpgo_group_stair_retract(dpgo_group_t *h, const double *Y, int ldy, const double *V, int ldv, double *Z, int ldz) {
+  if (!h || !h->grp || !Y || !V || !Z) return -1;
+  return guarded([&] { return h->grp->stair_retract(Y, ldy, V, ldv, Z, ldz); });
+}
+int dpgo_group_stair_round(dpgo_group_t *h, const double *Y, int ldy, double *B, double *sigma, double *Xhat, int ldx) {
+  if (!h || !h->grp || !Y || !B || !sigma || !Xhat) return -1;
+  return guarded([&] { return h->grp->stair_round(Y, ldy, B, sigma, Xhat, ldx); });
+}
+
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {
   if (!A || !B || !theta || !C || !used) return -1;
   return guarded([&] { return dpgo::rayleigh_ritz(ns, nblk, A, B, theta, C, used); });

@@ -61,6 +61,17 @@ void jacobi_eig(int n, double A[RR_MAX][RR_MAX], double Z[RR_MAX][RR_MAX], doubl
 }
 }  // namespace
 
+int sym_eig(int n, const double *A, double *Z, double *w) {
+  if (n < 1 || n > RR_MAX || !A || !Z || !w) return -1;
+  double As[RR_MAX][RR_MAX], Zv[RR_MAX][RR_MAX];
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) As[i][j] = 0.5 * (A[(size_t)i * n + j] + A[(size_t)j * n + i]);
+  jacobi_eig(n, As, Zv, w);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) Z[(size_t)i * n + j] = Zv[i][j];
+  return 0;
+}
+
 int rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used_out) {
   const int nfull = ns * nblk;
   if (ns < 1 || nblk < 1 || nfull > RR_MAX || !A || !B || !theta || !C) return -1;
@@ -451,11 +462,16 @@ int Group::cert_factor(const double *X, int ld, double eta, long long max_factor
     return -1;
   }
   if (cert_begin(X, ld) != 0) return -1;
-  CertState &c = *cert_;
   const int ready = cert_factor_setup(max_factor_bytes, out);
   if (ready < 0) return -1;
   cert_prepare(X, ld, &out.stationarity);
   if (ready != 0) return 0;   // SKIPPED, with what the analysis predicts
+  return cert_factor_numeric(eta, out);
+}
+
+// S + eta I from the Lambda in CertState, factored: the verdict
+int Group::cert_factor_numeric(double eta, CertFactor &out) {
+  CertState &c = *cert_;
   const auto t0 = std::chrono::steady_clock::now();
   launch_cert_matrix(d_, st_, P0_, c.bptr.p, c.diag_pose.p, c.Mval.p, c.Lam.p, eta, spd_numeric_values(c.F));
   const int rc = spd_refactor_device(c.F, st_, false);   // (returns with the verdict read: the stream has drained)
@@ -540,19 +556,46 @@ int Group::verify(const double *X, int ld, const CertOptions &o, long long max_f
   return rc;
 }
 
+// verify on the Lambda in CertState (the staircase's: Lambda of a lifted point); cert_begin has run
+int Group::verify_lambda(const CertOptions &o, long long max_factor_bytes, double stationarity, CertResult &res, double *x_out,
+                         int ldx, CertFactor &fac) {
+  res = CertResult();
+  fac = CertFactor();
+  fac.eta = o.eta;
+  if (!cert_options_ok(o, (d_ + 1) * num_poses_global_, nullptr, 0, x_out, ldx)) return -1;
+  const int ready = cert_factor_setup(max_factor_bytes, fac);
+  if (ready < 0) return -1;
+  fac.stationarity = res.stationarity = stationarity;
+  if (ready == 0 && cert_factor_numeric(o.eta, fac) != 0) return -1;
+  if (fac.outcome == CERT_FACTOR_PD) {
+    res.status = CERT_PROVEN;
+    return 0;
+  }
+  if (o.precondition) cert_build_precon();
+  const int rc = cert_search(o, nullptr, 0, res, x_out, ldx);
+  if (rc == 0 && fac.outcome == CERT_FACTOR_NOT_PD && res.status == CERT_NONNEGATIVE) res.status = CERT_UNDECIDED;
+  return rc;
+}
+
 int Group::certify(const double *X, int ld, const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x_out, int ldx) {
-  const int N = num_poses_global_, rows = (d_ + 1) * N, d = d_;
+  const int rows = (d_ + 1) * num_poses_global_;
   res = CertResult();
   if (!(o.eta >= 0) || !(o.tau > 0) || o.max_iters < 0 || o.refresh_every < 0 || (V0 && ldv0 < rows) || (x_out && ldx < rows)) {
     fprintf(stderr, "[dpgo_amd] ERROR: certify: bad options or inconsistent size of V0 / x.\n");
     return -1;
   }
   if (cert_begin(X, ld) != 0) return -1;
+  if (o.precondition) cert_build_precon();
+  cert_prepare(X, ld, &res.stationarity);
+  return cert_search(o, V0, ldv0, res, x_out, ldx);
+}
+
+// The search on S = M - Lambda with the Lambda in CertState (res.stationarity is the caller's)
+int Group::cert_search(const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x_out, int ldx) {
+  const int N = num_poses_global_, rows = (d_ + 1) * N, d = d_;
   CertState &c = *cert_;
   const NodeMask all{all_bits(), nullptr};
   const int NT = cert_ntri(d), n3 = 3 * d, nsums = cert_nsums(d);
-  if (o.precondition) cert_build_precon();
-  cert_prepare(X, ld, &res.stationarity);
 
   // |S| ~ |S Omega|_F / |Omega|_F on a Gaussian block (LOBPCG.h:199-214)
   std::vector<double> blk((size_t)rows * d), tmp((size_t)rows * d);

@@ -89,6 +89,9 @@ struct CertFactor {
 // ascending; C: n x ns row-major, C^T B C = I, C^T A C = diag(theta), rows of dropped blocks zero; *used: blocks used.
 // -1 when not even the first block has a positive definite mass matrix.
 int rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used);
+// the cyclic Jacobi of that step on its own: A (n x n row-major, symmetric, n <= 9) = Z diag(w) Z^T, Z row-major with the
+// eigenvectors in its columns, w in no particular order
+int sym_eig(int n, const double *A, double *Z, double *w);
 
 // ---- kernels (cert.hip) ----
 constexpr int cert_ntri(int d) { return 3 * d * (3 * d + 1) / 2; }          // upper triangle of a 3d x 3d matrix

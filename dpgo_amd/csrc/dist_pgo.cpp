@@ -32,6 +32,12 @@
 //              the anchor) from the final X, and one more line on stdout
 //                  polish: <outcome> <steps> <factorisations> <indefinite> <F_initial> <F_final> <grad_initial> <grad_final>
 //              the result files then hold the polished X; the same reasons as --covariance when it is not computed
+//              --staircase (likewise)  after --polish and ahead of --certify / --verify / --covariance, which then act on its
+//              result, for the trivial loss and a world of one rank: dpgo_group_staircase (the Riemannian staircase: TNT at rank
+//              r, verify, an escape along the certificate's direction, the rounding and a polish) from the point so far, and
+//              one more line on stdout
+//                  staircase: <outcome> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
+//              the result files then hold its Xhat; the same reasons as --polish when it is not computed
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -68,7 +74,7 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false;
+  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false;
   std::string edge_report, covariance;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
@@ -88,6 +94,8 @@ int main(int argc, char **argv) {
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
     else if (a == "--polish") polish = true;
     else if (a.compare(0, 9, "--polish=") == 0) polish = parse_bool(argv[i] + 9);
+    else if (a == "--staircase") staircase = true;
+    else if (a.compare(0, 12, "--staircase=") == 0) staircase = parse_bool(argv[i] + 12);
     else if (a == "--verify") verify = true;
     else if (a.compare(0, 9, "--verify=") == 0) verify = parse_bool(argv[i] + 9);
     else if (a == "--verify_reweighted") verify_reweighted = true;
@@ -229,6 +237,24 @@ int main(int argc, char **argv) {
              : pr.outcome == DPGO_POLISH_STALLED ? "STALLED" : "SKIPPED",
              pr.steps, pr.factorisations, pr.indefinite, pr.F_initial, pr.F_final, pr.grad_initial, pr.grad_final);
       if (pr.outcome != DPGO_POLISH_SKIPPED) Xpol.swap(Z);
+    }
+  }
+  if (staircase) {
+    if (loss != 0) {
+      if (root) printf("staircase: not computed (the relaxation is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("staircase: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0);
+      dpgo_staircase_result_t sr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_staircase(grp, Xc.data(), ld, nullptr, 0, Z.data(), ld, nullptr, 0, nullptr, 0, &sr) != 0)
+        return -1;
+      printf("staircase: %s %d %.17g %.17g %.17g %.17g\n",
+             sr.outcome == DPGO_STAIR_SOLVED ? "SOLVED" : sr.outcome == DPGO_STAIR_MAX_RANK ? "MAX_RANK"
+             : sr.outcome == DPGO_STAIR_SADDLE ? "SADDLE" : "SKIPPED",
+             sr.final_rank, sr.F_initial, sr.F_sdp, sr.F_final, sr.gap);
+      if (sr.outcome != DPGO_STAIR_SKIPPED) Xpol.swap(Z);
     }
   }
   if (certify) {

@@ -500,6 +500,7 @@ Group::~Group() {
   // before any buffer goes, and leaks what the device might still touch where it never drains (schedule.h: close)
   sched_.close(failed_ ? 2.0 : 60.0);
   chordal_release();
+  stair_release();
   cov_release();
   cert_release();
 }

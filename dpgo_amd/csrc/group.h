@@ -34,6 +34,7 @@
 #include "schedule.h"
 #include "settings.h"
 #include "spd_solve.h"
+#include "stair.h"
 
 namespace dpgo {
 
@@ -196,6 +197,17 @@ class Group {
   // SKIPPED; log (optional, log_cap rows of POLISH_LOG_COLS doubles): one row per iteration
   int polish(const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout, int ldout, double *log,
              int log_cap, PolishResult &out);
+  // ---- the Riemannian staircase (stair.h, stair.cpp): TNT at rank r, verify on Lambda(Y), the escape along the certificate's
+  // direction, the rounding, the polish.  X: global (d+1)N x d; Xhat (ldx >= (d+1) N): the result, written unless SKIPPED; Y
+  // (optional, (d+1)N x 2d): the final lifted point; log (optional, log_cap rows of STAIR_LOG_COLS doubles): one row per level
+  int staircase(const double *X, int ld, const StairOptions &o, long long max_bytes, double *Xhat, int ldx, double *Y, int ldy,
+                double *log, int log_cap, StairResult &out);
+  // operator hooks on a lifted point Y ((d+1)N x 2d, zero columns >= r): F, |grad|, Lambda (N blocks d x d by global pose) and
+  // grad (optional); Hess[V]; retract(Y, V); the rounding (B: 2d x d row-major, sigma: 2d, Xhat before any polish)
+  int stair_eval(const double *Y, int ldy, double *F, double *gnorm, double *Lambda, double *grad, int ldg);
+  int stair_hess(const double *Y, int ldy, const double *V, int ldv, double *out, int ldo);
+  int stair_retract(const double *Y, int ldy, const double *V, int ldv, double *Z, int ldz);
+  int stair_round(const double *Y, int ldy, double *B, double *sigma, double *Xhat, int ldx);
   // boundary exchange across groups: records of the poses other groups need
   int num_sent() const { return (int)sent_rows_.size(); }
   // device buffer, num_sent()*RS doubles; st: the stream to enqueue on (default: the group's)
@@ -469,6 +481,23 @@ class Group {
   void cert_build_precon();
   void cert_build_pattern();
   int cert_factor_setup(long long max_factor_bytes, CertFactor &out);   // 0: ready to factor, 1: SKIPPED, -1: error
+  int cert_factor_numeric(double eta, CertFactor &out);                 // S + eta I from the Lambda in place, factored
+  int cert_search(const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x, int ldx);   // LOBPCG, likewise
+  int verify_lambda(const CertOptions &o, long long max_factor_bytes, double stationarity, CertResult &res, double *x, int ldx,
+                    CertFactor &fac);
+  struct StairState;  // the staircase's lifted vectors (stair.cpp), allocated by the first call that is not refused
+  StairState *stair_ = nullptr;
+  void stair_release();
+  int stair_begin(const double *X, int ld, long long max_bytes, long long *bytes);   // 0: ready, 1: SKIPPED, -1: error
+  struct StairPoint;  // the buffers of one lifted point: Y, M Y, grad, Lambda
+  void stair_upload(const double *X, int ld, int ncols, const struct Lifted &dst);
+  void stair_download(const struct LiftedC &src, double *X, int ld);
+  void stair_apply_M(const struct Lifted &in_all, const struct Lifted &out_own, int rank);
+  void stair_eval_point(StairPoint &p, int rank, bool store_grad, double *F, double *gnorm);
+  double stair_hess_product(StairPoint &p, int rank, const struct Lifted &V_all, const struct Lifted &MV, const struct Lifted &out,
+                            double *ww, double *vv);
+  int stair_tnt(const StairOptions &o, int rank, double *F, double *gnorm, int *iters, int *products);
+  int stair_round_point(int rank, double *Bout, double *sigma, double *Xhat, int ldx);
   struct CovState;    // the covariance's pattern, factor and blocks (cov.cpp), allocated by the first call
   CovState *cov_ = nullptr;
   void cov_release();

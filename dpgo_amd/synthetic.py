@@ -214,6 +214,47 @@ def two_node(m, poses_per_node=256, seed=1, sigma_t=0.05, sigma_r=0.02, outlier_
                 outlier=outlier, Rg=Rg, tg=tg)
 
 
+def _planar(d, angle):
+    """The rotation by `angle` about the first two axes of R^d."""
+    R = np.eye(d)
+    c, s = np.cos(angle), np.sin(angle)
+    R[0, 0], R[0, 1], R[1, 0], R[1, 1] = c, -s, s, c
+    return R
+
+
+def twisted_ring(d=3, n=12, noise=0.02, seed=1, twist=1):
+    """A single loop of n poses and a start that winds once too often around it (the staircase's test instance).
+
+    Ground truth: pose k at angle 2 pi k / n on a circle of radius n / 2 pi in the plane of the first two axes, heading
+    rotated by the same angle about them.  Edges k -> (k + 1) mod n with kappa = tau = 10.  Per edge, in edge order, from
+    default_rng(seed): the rotation noise first -- d = 2: one normal times `noise` as an angle; d = 3: three normals times
+    `noise` as a rotation vector -- applied on the right of the true relative rotation, then d normals times `noise` added
+    to the true relative translation.  The start has the true translations and the rotations R_k Rot(twist 2 pi k / n):
+    `twist` extra turns of the heading along the loop, a local minimum's basin away from the truth.
+    Returns (the dict of grid() plus num_nodes = 1, the start in the library's global layout)."""
+    rng = np.random.default_rng(seed)
+    ang = 2 * np.pi * np.arange(n) / n
+    Rg = np.stack([_planar(d, a) for a in ang])
+    tg = np.zeros((n, d))
+    tg[:, 0], tg[:, 1] = n / (2 * np.pi) * np.cos(ang), n / (2 * np.pi) * np.sin(ang)
+    I = np.arange(n, dtype=np.int64)
+    J = (I + 1) % n
+    R, t = np.empty((n, d, d)), np.empty((n, d))
+    for e in range(n):
+        Rt = Rg[I[e]].T @ Rg[J[e]]
+        tt = Rg[I[e]].T @ (tg[J[e]] - tg[I[e]])
+        if d == 2:
+            E = _planar(2, noise * rng.standard_normal())
+        else:
+            E = _exp_so3(noise * rng.standard_normal((1, 3)))[0]
+        R[e] = Rt @ E
+        t[e] = tt + noise * rng.standard_normal(d)
+    g = dict(d=d, num_poses=n, num_nodes=1, I=I, J=J, R=R, t=t, kappa=np.full(n, 10.0), tau=np.full(n, 10.0),
+             outlier=np.zeros(n, bool))
+    Rs = np.stack([Rg[k] @ _planar(d, twist * ang[k]) for k in range(n)])
+    return g, global_X(Rs, tg)
+
+
 def global_X(R, t):
     """The library's global layout ((d+1)N x d) of poses R (N x d x d), t (N x d): rows [0, N) t_i, rows
     [N + d i, N + d i + d) R_i^T."""

@@ -594,6 +594,77 @@ void dpgo_polish_options_default(dpgo_polish_options_t *opt);
 int dpgo_group_polish(dpgo_group_t *grp, const double *X, int ld, const dpgo_polish_options_t *opt, long long max_bytes,
                       double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result);
 
+/* ---- the Riemannian staircase: escape a NEGATIVE certificate -------------------------------- */
+/* When dpgo_group_verify says NEGATIVE the point is a saddle or a local minimum of the rank-d problem, and the unit vector x it
+ * returns is a direction of descent one rank up.  dpgo_group_staircase is the loop of SE-Sync (C++/SESync/src/SESync.cpp:280-440,
+ * escape_saddle :575-680, round_solution) on the device.  A point at rank r, d <= r <= 2d, is (d+1)N x r in the reference's row
+ * order with Y_p Y_p^T = I_d; F = 1/2 tr(Y^T M Y), grad F = S Y, Hess[V] = Proj_Y(S V), the retraction is the polar factor.
+ *     r = d;  Y = X
+ *     repeat:  Y = TNT(Y) at rank r     (the reference's truncated-Newton trust-region method; preconditioner Proj o T_p o Proj
+ *                                        with the certificate's block-Jacobi T_p)
+ *              verdict, theta, x = verify at Lambda(Y)     (Cholesky of S + eta I, then LOBPCG only when it did not succeed)
+ *              verdict != NEGATIVE -> SOLVED;   r == r_max -> MAX_RANK
+ *              Ydot = x in the zero column r;  alpha = 1; at most 30 times: Z = retract(Y, alpha Ydot), accepted when
+ *              F(Z) <= F(Y) + 1/4 alpha^2 theta, else alpha /= 2;   none accepted -> SADDLE;   Y = Z, r += 1
+ *     round:   B = the d leading eigenvectors of sum_p Y_p^T Y_p, each signed so that its entry of largest magnitude is positive;
+ *              Xhat = Y B with every Y_p B projected onto SO(d), the last column of B negated first where most determinants are
+ *              negative (at final rank d the point is taken as it is)
+ *     Xhat = polish(Xhat) (opt->polish, anchor 0; left alone where the polish is SKIPPED)
+ *     F(Xhat) > F(X) -> Xhat = X, replaced_by_input = 1:  the result is never worse than what was handed in
+ * Deviations from the reference: the escape's line search (the reference starts at 10 tol / |theta| and adds a gradient test),
+ * r_max <= 2d (the reference: 10), the start at rank d from the caller's point (the reference: r0 = 5 from chordal).
+ * The restrictions of the certificate: the TRIVIAL LOSS only, the group must HOST EVERY NODE; -1 otherwise.  The optimiser's
+ * state is not touched.
+ *   opt     NULL: the defaults.  The optimiser's options are named as in SESyncOpts; r_max 0 means 2d, and must lie in [d, 2d]
+ *   Xhat    (d+1) N x d column-major, ldx >= (d+1) N (not written for SKIPPED)
+ *   Y       optional, (d+1) N x 2d, ldy >= (d+1) N: the final lifted point, zero columns >= final_rank
+ *   log     optional, log_cap rows of 10 doubles, one per level: rank, F in, F out, |grad|, TNT iterations, Hessian products,
+ *           certificate status, theta, accepted alpha (0: no escape from this level), halvings
+ *   result  outcome; cert_status, theta, stationarity (|grad F| at the final Y) of the last verify; final_rank, levels; the
+ *           TNT iterations and Hessian products of all levels; F_initial (at X), F_sdp (at the final Y), F_rounded (before
+ *           the polish), F_final (at Xhat); gap = F_final - F_sdp; sigma: the 2d singular values of the rotation rows of the
+ *           final Y, descending (more than d of them away from zero: the relaxation is not tight); replaced_by_input;
+ *           polish_outcome; device_bytes (filled for SKIPPED too); optimise_ms, verify_ms, round_ms (with the polish), total_ms
+ * gap is the reference's suboptimality_bound: F_sdp bounds F of EVERY feasible point from below -- so gap bounds how far Xhat
+ * is from the global minimum -- only where cert_status is PROVEN and stationarity is small.  Otherwise it is the difference
+ * of two numbers.
+ * SKIPPED when the record arrays this allocates (device_bytes) are more than max_bytes (> 0) or more than half of the free
+ * device memory: nothing is allocated then. */
+#define DPGO_STAIR_SOLVED 0
+#define DPGO_STAIR_MAX_RANK 1
+#define DPGO_STAIR_SADDLE 2
+#define DPGO_STAIR_SKIPPED 3
+typedef struct dpgo_staircase_options {
+  double grad_norm_tol, preconditioned_grad_norm_tol, rel_func_decrease_tol, stepsize_tol;   /* 1e-2, 1e-4, 1e-6, 1e-3 */
+  int max_iterations, max_tCG_iterations;   /* 1000, 10000 */
+  double STPCG_kappa, STPCG_theta;          /* 0.1, 0.5 */
+  int r_max, precondition;                  /* 0 (2d), 1 */
+  int polish, reserved;                     /* 1 */
+  double min_eig_num_tol;                   /* 1e-3: eta of the certificate */
+  long long max_factor_bytes;               /* 0: of verify's factorisation */
+} dpgo_staircase_options_t;
+typedef struct dpgo_staircase_result {
+  int outcome, cert_status, final_rank, levels;
+  int tnt_iterations, hess_products, replaced_by_input, polish_outcome;
+  double theta, stationarity, F_initial, F_sdp, F_rounded, F_final, gap;
+  double sigma[6];
+  long long device_bytes;
+  double optimise_ms, verify_ms, round_ms, total_ms;
+} dpgo_staircase_result_t;
+void dpgo_staircase_options_default(dpgo_staircase_options_t *opt);
+int dpgo_group_staircase(dpgo_group_t *grp, const double *X, int ld, const dpgo_staircase_options_t *opt, long long max_bytes,
+                         double *Xhat, int ldx, double *Y, int ldy, double *log, int log_cap, dpgo_staircase_result_t *result);
+/* Operator hooks on a lifted point Y handed in as (d+1) N x 2d with zero columns >= r (tests/test_gpu_stair_ops.py):
+ *   eval     F, |grad F|, Lambda (optional: N blocks d x d row-major by global pose), grad = S Y (optional, (d+1) N x 2d)
+ *   hess     out = Hess[V] = Proj_Y(S V)
+ *   retract  Z = the polar retraction of Y + V
+ *   round    B (2d x d row-major), sigma (2d), Xhat ((d+1) N x d) before any polish */
+int dpgo_group_stair_eval(dpgo_group_t *grp, const double *Y, int ldy, double *F, double *grad_norm, double *Lambda, double *grad,
+                          int ldg);
+int dpgo_group_stair_hess(dpgo_group_t *grp, const double *Y, int ldy, const double *V, int ldv, double *out, int ldo);
+int dpgo_group_stair_retract(dpgo_group_t *grp, const double *Y, int ldy, const double *V, int ldv, double *Z, int ldz);
+int dpgo_group_stair_round(dpgo_group_t *grp, const double *Y, int ldy, double *B, double *sigma, double *Xhat, int ldx);
+
 /* Host only: the Rayleigh-Ritz step of the search (LOBPCG.h:236-262).  A, B: n x n row-major symmetric, n = ns nblk.
  * Both are scaled by diag(B)^-1/2, B is Cholesky-factored -- a pivot below 1e-12 drops the last block and the step is
  * redone on the others -- and the reduced problem is solved by cyclic Jacobi.  theta: the ns smallest Ritz values; C:

@@ -278,6 +278,31 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
+  // The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- the reference's
+  // truncated-Newton method at rank r, fast_verification at the lifted point, an escape along the certificate's direction one
+  // rank up, until the certificate is not NEGATIVE or r = r_max <= 2d; then the rounding and a polish.  Xhat: the result, never
+  // worse than X (X itself when the call is SKIPPED or fails).  result->gap = F_final - F_sdp bounds the distance to the global
+  // minimum only where result->cert_status is DPGO_CERT_PROVEN and result->stationarity is small.  log (optional): per level
+  // rank, F in, F out, |grad|, TNT iterations, Hessian products, certificate status, theta, accepted alpha, halvings.  Returns
+  // true for DPGO_STAIR_SOLVED; status: the DPGO_STAIR_* outcome, -1 when the call itself failed.
+  bool riemannian_staircase(const Matrix &X, Matrix &Xhat, dpgo_staircase_result_t *result = nullptr, int *status = nullptr,
+                            const dpgo_staircase_options_t *opt = nullptr, long long max_bytes = 0,
+                            std::vector<Scalar> *log = nullptr, Matrix *Y = nullptr) const {
+    dpgo_staircase_options_t o;
+    dpgo_staircase_options_default(&o);
+    if (opt) o = *opt;
+    Xhat = X;
+    const int cap = X.cols() + 1;
+    if (log) log->assign((size_t)cap * 10, 0.0);
+    if (Y) Y->resize(X.rows(), 2 * X.cols());
+    dpgo_staircase_result_t r = {};
+    const int rc = dpgo_group_staircase(h_, X.data(), X.rows(), &o, max_bytes, Xhat.data(), Xhat.rows(), Y ? Y->data() : nullptr,
+                                        Y ? Y->rows() : 0, log ? log->data() : nullptr, log ? cap : 0, &r);
+    if (log) log->resize(rc == 0 ? (size_t)std::min(cap, r.levels) * 10 : 0);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_STAIR_SOLVED;
+  }
   const Graph &graph() const { return *graph_; }
   dpgo_group_t *handle() const { return h_; }
 
