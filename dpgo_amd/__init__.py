@@ -223,6 +223,10 @@ SYMBOLS = {
     "dpgo_debug_spd_solver_free": (None, [C.c_void_p]),
     "dpgo_debug_p2p_plan": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
+    "dpgo_group_debug_stpcg": (C.c_int, [C.c_void_p, _IP, C.c_int, _DP, C.c_int, _DP, C.c_int, C.c_double, _DP, C.c_int, _DP]),
+    "dpgo_group_debug_seg_layout": (C.c_int, [C.c_void_p, _IP, _IP, _IP]),
+    "dpgo_group_debug_cg_scalars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _DP, C.POINTER(C.c_ulonglong), _DP, _DP, _DP,
+                                              C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
     "dpgo_pcm_options_default": (None, [C.c_void_p]),
     "dpgo_pcm_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "dpgo_pcm_free": (None, [C.c_void_p]),
@@ -761,6 +765,18 @@ class SpdSolverDebug:
             raise RuntimeError("not positive definite" if rc == 1 else "dpgo_debug_spd_solver_refactor failed")
 
 
+CG_DEBUG_KINDS = ("begin_host", "begin_device", "scal0", "scal1", "scal_begin")
+CG_RECORD_FIELDS = ("sk_M_pk", "sk_M_2", "pk_M_2", "rv", "Delta", "Delta_2", "target", "h_M_norm", "c1", "cr", "al", "kap", "be",
+                    "cg_it", "max_it", "live", "stop_ord")
+
+
+class CgDebugLaunch(C.Structure):
+    """dpgo_cg_debug_launch_t"""
+    _fields_ = [("kind", C.c_int), ("use_precon", C.c_int), ("max_it", C.c_int), ("slots", C.c_int), ("bits", C.c_ulonglong),
+                ("grad_tol", C.c_double), ("pgrad_tol", C.c_double), ("kappa", C.c_double), ("theta", C.c_double),
+                ("rv", _DP), ("Delta", _DP), ("target", _DP), ("partials", _DP)]
+
+
 class NodeGroup:
     """The DPGOHash objects of the nodes hosted by one GPU (one process)."""
 
@@ -1191,6 +1207,94 @@ class NodeGroup:
         out = np.zeros((out_rows, self.d), order="F")
         if lib().dpgo_group_debug_apply(self._h, k, op.encode(), _dp(X), ld, _dp(out), out.shape[0]) != 0:
             raise RuntimeError("debug_apply(%s) failed" % op)
+        return out
+
+
+    def debug_stpcg(self, locals_, YG, Delta, device_start, fill=0.0):
+        """Debug: one truncated CG of a refinement round on given points (dpgo_group_debug_stpcg).  locals_: the nodes that
+        take part; YG: per node of the group (all of them) the stacked [Y ; g], 2 (d+1) n0 x d; Delta: one radius per node of
+        the group; device_start: the first round's start (True) or a later round's (False).  Returns a list with one dict per
+        node of the group: s, hs, grad ((d+1) n0 x d each; `fill` everywhere for a node outside locals_), sums (6), h_M_norm,
+        cg_it, stop_ord, active, live, Delta."""
+        L, d = len(self.node_ids), self.d
+        rows = [(d + 1) * self.sizes[a][0] for a in range(L)]
+        if len(YG) != L or any(np.shape(YG[a]) != (2 * rows[a], d) for a in range(L)):
+            raise ValueError("debug_stpcg: one [Y ; g] of 2 (d+1) n0 rows per node of the group")
+        X = np.asfortranarray(np.vstack([np.asarray(m, np.float64) for m in YG]))
+        out = np.zeros((3 * sum(rows), d), order="F")
+        sc = np.zeros((L, 12))
+        ids = np.asarray(list(locals_), np.int32)
+        Dl = np.ascontiguousarray(np.asarray(Delta, np.float64))
+        if Dl.shape != (L,):
+            raise ValueError("debug_stpcg: one radius per node of the group")
+        if lib().dpgo_group_debug_stpcg(self._h, _ip(ids), len(ids), _dp(X), X.shape[0], _dp(Dl), int(bool(device_start)),
+                                        float(fill), _dp(out), out.shape[0], _dp(sc)) != 0:
+            raise RuntimeError("dpgo_group_debug_stpcg failed")
+        res, r0 = [], 0
+        for a in range(L):
+            R0 = rows[a]
+            res.append(dict(s=out[r0:r0 + R0].copy(), hs=out[r0 + R0:r0 + 2 * R0].copy(), grad=out[r0 + 2 * R0:r0 + 3 * R0].copy(),
+                            sums=sc[a, :6].copy(), h_M_norm=float(sc[a, 6]), cg_it=int(sc[a, 7]), stop_ord=int(sc[a, 8]),
+                            active=int(sc[a, 9]), live=int(sc[a, 10]), Delta=float(sc[a, 11])))
+            r0 += 3 * R0
+        return res
+
+    def debug_seg_layout(self):
+        """Debug: (nseg_all, own_ptr, nbr_ptr) -- the segment table the partial sums are laid out by: node a's own segments
+        are [own_ptr[a], own_ptr[a+1]), its neighbour segments [nbr_ptr[a], nbr_ptr[a+1])."""
+        L = len(self.node_ids)
+        n, own, nbr = C.c_int(0), np.zeros(L + 1, np.int32), np.zeros(L + 1, np.int32)
+        if lib().dpgo_group_debug_seg_layout(self._h, C.byref(n), _ip(own), _ip(nbr)) != 0:
+            raise RuntimeError("dpgo_group_debug_seg_layout failed")
+        return n.value, own, nbr
+
+    def debug_cg_scalars(self, script):
+        """Debug: the scalar kernels of the truncated CG on given partial sums (dpgo_group_debug_cg_scalars).  script: a list
+        of dicts, each one launch: kind ("begin_host", "begin_device", "scal0", "scal1", "scal_begin"); bits, max_it, Delta
+        (per node) for the begin kinds; rv, target (per node) for begin_host; use_precon, grad_tol, pgrad_tol, kappa, theta
+        for begin_device and scal_begin; partials (slots, nseg_all), optional.  Returns one dict per launch: records (a
+        list of dicts with CG_RECORD_FIELDS, the four counters as ints), masks (three ints), cg_summary (L, 3), tnt_summary
+        and dev_tnt (L, 7), flag (the host flag's value), seq (the last sequence number given out), arrived."""
+        L, n = len(self.node_ids), len(script)
+        nseg_all = self.debug_seg_layout()[0]
+        arr, keep = (CgDebugLaunch * max(n, 1))(), []
+
+        def per_node(q, key):
+            v = np.ascontiguousarray(np.asarray(q.get(key, np.zeros(L)), np.float64))
+            if v.shape != (L,):
+                raise ValueError("debug_cg_scalars: %s takes one value per node" % key)
+            keep.append(v)
+            return v.ctypes.data_as(_DP)
+
+        for i, q in enumerate(script):
+            a = arr[i]
+            a.kind = CG_DEBUG_KINDS.index(q["kind"])
+            a.bits, a.use_precon, a.max_it = int(q.get("bits", 0)), int(q.get("use_precon", 0)), int(q.get("max_it", 0))
+            a.grad_tol, a.pgrad_tol = float(q.get("grad_tol", 0.0)), float(q.get("pgrad_tol", 0.0))
+            a.kappa, a.theta = float(q.get("kappa", 0.0)), float(q.get("theta", 0.0))
+            a.rv, a.Delta, a.target = per_node(q, "rv"), per_node(q, "Delta"), per_node(q, "target")
+            a.slots, a.partials = 0, None
+            if q.get("partials") is not None:
+                P = np.ascontiguousarray(np.asarray(q["partials"], np.float64))
+                if P.ndim != 2 or P.shape[1] != nseg_all:
+                    raise ValueError("debug_cg_scalars: partials are (slots, nseg_all = %d)" % nseg_all)
+                keep.append(P)
+                a.slots, a.partials = P.shape[0], P.ctypes.data_as(_DP)
+        nf = len(CG_RECORD_FIELDS)
+        rec, masks = np.zeros((n, L, nf)), np.zeros((n, 3), np.uint64)
+        cgs, tnt, dev = np.zeros((n, L, 4)), np.zeros((n, L, 8)), np.zeros((n, L, 8))
+        seq, arrived = np.zeros((n, 2), np.uint64), np.zeros(n, np.uint32)
+        if lib().dpgo_group_debug_cg_scalars(self._h, arr, n, _dp(rec), masks.ctypes.data_as(C.POINTER(C.c_ulonglong)), _dp(cgs),
+                                             _dp(tnt), _dp(dev), seq.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                             arrived.ctypes.data_as(C.POINTER(C.c_uint))) != 0:
+            raise RuntimeError("dpgo_group_debug_cg_scalars failed")
+        out = []
+        for i in range(n):
+            records = [{f: (int(rec[i, a, k]) if k >= nf - 4 else float(rec[i, a, k])) for k, f in enumerate(CG_RECORD_FIELDS)}
+                       for a in range(L)]
+            out.append(dict(records=records, masks=[int(m) for m in masks[i]], cg_summary=cgs[i, :, :3].copy(),
+                            tnt_summary=tnt[i, :, :7].copy(), dev_tnt=dev[i, :, :7].copy(), flag=int(seq[i, 0]), seq=int(seq[i, 1]),
+                            arrived=int(arrived[i])))
         return out
 
 

@@ -935,6 +935,35 @@ int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const dou
   return guarded([&] { return h->grp->debug_apply(local, op, in, ld_in, out, ld_out); });
 }
 
+int dpgo_group_debug_seg_layout(dpgo_group_t *h, int *nseg_all, int *own_ptr, int *nbr_ptr) {
+  if (!h) return -1;
+  return guarded([&] { return h->grp->debug_seg_layout(nseg_all, own_ptr, nbr_ptr); });
+}
+
+int dpgo_group_debug_stpcg(dpgo_group_t *h, const int *locals, int n, const double *in, int ld_in, const double *Delta,
+                           int device_start, double fill, double *out, int ld_out, double *scalars) {
+  if (!h || !locals || n <= 0) return -1;
+  return guarded([&] {
+    return h->grp->debug_stpcg(std::vector<int>(locals, locals + n), in, ld_in, Delta, device_start != 0, fill, out, ld_out, scalars);
+  });
+}
+
+int dpgo_group_debug_cg_scalars(dpgo_group_t *h, const dpgo_cg_debug_launch_t *script, int n, double *records,
+                                unsigned long long *masks, double *cg_summary, double *tnt_summary, double *dev_tnt,
+                                unsigned long long *seq, unsigned *arrived) {
+  if (!h || (n > 0 && !script)) return -1;
+  return guarded([&] {
+    std::vector<dpgo::Group::CgDebugLaunch> sc(n);
+    for (int i = 0; i < n; i++) {
+      const dpgo_cg_debug_launch_t &q = script[i];
+      sc[i].kind = q.kind; sc[i].bits = q.bits; sc[i].use_precon = q.use_precon; sc[i].max_it = q.max_it;
+      sc[i].grad_tol = q.grad_tol; sc[i].pgrad_tol = q.pgrad_tol; sc[i].kappa = q.kappa; sc[i].theta = q.theta;
+      sc[i].rv = q.rv; sc[i].Delta = q.Delta; sc[i].target = q.target; sc[i].partials = q.partials; sc[i].slots = q.slots;
+    }
+    return h->grp->debug_cg_scalars(sc.data(), n, records, masks, cg_summary, tnt_summary, dev_tnt, seq, arrived);
+  });
+}
+
 // ---- boundary: DPGOStar::evaluate_f / evaluate_grad, set_options / options, problem() accessors, g2o export ----
 int dpgo_group_evaluate(dpgo_group_t *h, const double *X, int ld, double *F, double *grad_sqnorm, double *grad, int ldg) {
   if (!h || !X) return -1;

@@ -1191,6 +1191,29 @@ std::vector<int> Group::rescale_device(const std::vector<int> &set) {
 
 namespace dpgo {
 
+void Group::put_rows(int a, double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t) {
+  const int n0 = info_[a].n[0];
+  std::vector<double> rec((size_t)n0 * RS_, 0.0);
+  for (int k = 0; k < n0; k++)
+    for (int c = 0; c < d_; c++) {
+      if (has_t) rec[(size_t)k * RS_ + c] = X[(size_t)c * ld + row_t0 + k];
+      for (int r = 0; r < d_; r++) rec[(size_t)k * RS_ + d_ + r * d_ + c] = X[(size_t)c * ld + row_r0 + k * d_ + r];
+    }
+  (void)hipMemcpy(dev + (size_t)own_off_[a] * RS_, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
+}
+
+void Group::get_rows(int a, const double *dev, double *X, int ld, int row_t0, int row_r0, bool has_t) {
+  const int n0 = info_[a].n[0];
+  std::vector<double> rec((size_t)n0 * RS_);
+  sync();
+  (void)hipMemcpy(rec.data(), dev + (size_t)own_off_[a] * RS_, sizeof(double) * rec.size(), hipMemcpyDeviceToHost);
+  for (int k = 0; k < n0; k++)
+    for (int c = 0; c < d_; c++) {
+      if (has_t) X[(size_t)c * ld + row_t0 + k] = rec[(size_t)k * RS_ + c];
+      for (int r = 0; r < d_; r++) X[(size_t)c * ld + row_r0 + k * d_ + r] = rec[(size_t)k * RS_ + d_ + r * d_ + c];
+    }
+}
+
 // Single operators on reference-layout inputs, for the parity tests.  Each enqueues the launches the iteration uses for it
 // (tnt.cpp, update(), iterate()).  "op" runs under the node's own mask (the compacted live-segment mapping, live_mask);
 // "op:all" under the whole group's (the whole-grid mapping of the iteration's common case), with the other nodes' rows zero.
@@ -1210,25 +1233,8 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
     for (int b = 0; b < num_local(); b++) all[b] = b;
     set_mask(all);
   } else set_mask({a});
-  auto put_own = [&](double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t) {
-    std::vector<double> rec((size_t)n0 * RS_, 0.0);
-    for (int k = 0; k < n0; k++)
-      for (int c = 0; c < d_; c++) {
-        if (has_t) rec[(size_t)k * RS_ + c] = X[(size_t)c * ld + row_t0 + k];
-        for (int r = 0; r < d_; r++) rec[(size_t)k * RS_ + d_ + r * d_ + c] = X[(size_t)c * ld + row_r0 + k * d_ + r];
-      }
-    (void)hipMemcpy(dev + (size_t)own_off_[a] * RS_, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice);
-  };
-  auto get_own = [&](const double *dev, double *X, int ld, int row_t0, int row_r0, bool has_t) {
-    std::vector<double> rec((size_t)n0 * RS_);
-    sync();
-    (void)hipMemcpy(rec.data(), dev + (size_t)own_off_[a] * RS_, sizeof(double) * rec.size(), hipMemcpyDeviceToHost);
-    for (int k = 0; k < n0; k++)
-      for (int c = 0; c < d_; c++) {
-        if (has_t) X[(size_t)c * ld + row_t0 + k] = rec[(size_t)k * RS_ + c];
-        for (int r = 0; r < d_; r++) X[(size_t)c * ld + row_r0 + k * d_ + r] = rec[(size_t)k * RS_ + d_ + r * d_ + c];
-      }
-  };
+  auto put_own = [&](double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t) { put_rows(a, dev, X, ld, row_t0, row_r0, has_t); };
+  auto get_own = [&](const double *dev, double *X, int ld, int row_t0, int row_r0, bool has_t) { get_rows(a, dev, X, ld, row_t0, row_r0, has_t); };
   double *A = tmp_[0].p, *Bv = tmp_[1].p, *C = tmp_[2].p;
   if (op == "project") {
     (void)hipMemset(A + (size_t)own_off_[a] * RS_, 0, sizeof(double) * n0 * RS_);
@@ -1317,6 +1323,78 @@ int Group::debug_apply(int a, const char *op_c, const double *in, int ld_in, dou
   } else {
     fprintf(stderr, "[dpgo_amd] ERROR: debug_apply: unknown operator %s\n", op_c);
     return -1;
+  }
+  return 0;
+}
+
+
+int Group::debug_seg_layout(int *nseg_all, int *own_ptr, int *nbr_ptr) const {
+  const int L = num_local();
+  if (nseg_all) *nseg_all = T_.nseg_all;
+  if (own_ptr) HIP_CHECK(hipMemcpy(own_ptr, T_.own_ptr, sizeof(int) * (L + 1), hipMemcpyDeviceToHost));
+  if (nbr_ptr) HIP_CHECK(hipMemcpy(nbr_ptr, T_.nbr_ptr, sizeof(int) * (L + 1), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The CG's scalar kernels on given partial sums, for tests/test_gpu_cg_scalars.py: every launch is the one tnt.cpp makes
+// (later_round, enqueue_device_start, step_a, step_b, scal_begin) with the vectors' passes left out -- their sums are handed in.
+int Group::debug_cg_scalars(const CgDebugLaunch *script, int n, double *records, unsigned long long *masks, double *cg_summary,
+                            double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived) {
+  finish_update();
+  const int L = num_local();
+  if (!script || n < 0 || !records || !masks || !cg_summary || !tnt_summary || !dev_tnt || !seq || !arrived) return -1;
+  for (int i = 0; i < n; i++) {
+    const CgDebugLaunch &q = script[i];
+    const bool begins = q.kind == CG_DBG_BEGIN_HOST || q.kind == CG_DBG_BEGIN_DEVICE || q.kind == CG_DBG_SCAL_BEGIN;
+    if (q.kind < 0 || q.kind >= CG_DBG_KINDS || q.slots < 0 || q.slots > MAX_SLOTS || (q.slots > 0 && !q.partials)) return -1;
+    if (begins && (q.max_it < 0 || (q.bits & ~all_bits()) || !q.Delta)) return -1;
+    if (q.kind == CG_DBG_BEGIN_HOST && (!q.rv || !q.target)) return -1;
+  }
+  sync();
+  std::vector<CgNode> rec(L);
+  for (int i = 0; i < n; i++) {
+    const CgDebugLaunch &q = script[i];
+    if (q.slots > 0)
+      HIP_CHECK(hipMemcpy(partials_.p, q.partials, sizeof(double) * (size_t)q.slots * T_.nseg_all, hipMemcpyHostToDevice));
+    bool flagged = true;
+    if (q.kind == CG_DBG_BEGIN_HOST) {
+      CgStart cs;
+      for (int a = 0; a < MAX_LOCAL_NODES; a++) {
+        cs.rv[a] = a < L ? q.rv[a] : 0.0;
+        cs.Delta[a] = a < L ? q.Delta[a] : 0.0;
+        cs.target[a] = a < L ? q.target[a] : 0.0;
+      }
+      launch_cg_begin(st_, L, q.bits, cs, q.max_it, cg_.p, dmask_.p);
+      flagged = false;
+    } else if (q.kind == CG_DBG_SCAL0 || q.kind == CG_DBG_SCAL1) {
+      launch_cg_scal(st_, T_, L, q.kind == CG_DBG_SCAL0 ? 0 : 1, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
+    } else {
+      const TntStart start = {.nnodes = L, .bits = q.bits, .use_precon = q.use_precon != 0, .max_it = q.max_it,
+                              .grad_tol = q.grad_tol, .pgrad_tol = q.pgrad_tol, .kappa = q.kappa, .theta = q.theta, .Delta = q.Delta,
+                              .partials = partials_.p, .cg = cg_.p, .dmask = dmask_.p, .host_tnt = h_tnt_};
+      if (q.kind == CG_DBG_BEGIN_DEVICE) {
+        launch_tnt_begin(st_, T_, start);
+        flagged = false;
+      } else launch_cg_scal_begin(st_, T_, start, h_cg_, sched_.flag(), dev_tnt_.p, 0, h_upd_);
+    }
+    if (flagged) wait_flag(sched_.last_seq());
+    HIP_CHECK(hipStreamSynchronize(st_));
+    HIP_CHECK(hipMemcpy(rec.data(), cg_.p, sizeof(CgNode) * L, hipMemcpyDeviceToHost));
+    for (int a = 0; a < L; a++) {
+      const CgNode &c = rec[a];
+      const double w[CG_DBG_RECORD] = {c.sk_M_pk, c.sk_M_2, c.pk_M_2, c.rv, c.Delta, c.Delta_2, c.target, c.h_M_norm, c.c1, c.cr,
+                                       c.al, c.kap, c.be, (double)c.cg_it, (double)c.max_it, (double)c.live, (double)c.stop_ord};
+      std::copy(w, w + CG_DBG_RECORD, records + ((size_t)i * L + a) * CG_DBG_RECORD);
+    }
+    NodeBits m[3];
+    HIP_CHECK(hipMemcpy(m, dmask_.p, sizeof(m), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) masks[(size_t)i * 3 + k] = m[k];
+    std::copy(h_cg_, h_cg_ + (size_t)L * CG_SUMMARY, cg_summary + (size_t)i * L * CG_SUMMARY);
+    std::copy(h_tnt_, h_tnt_ + (size_t)L * TNT_SUMMARY, tnt_summary + (size_t)i * L * TNT_SUMMARY);
+    HIP_CHECK(hipMemcpy(dev_tnt + (size_t)i * L * TNT_SUMMARY, dev_tnt_.p, sizeof(double) * L * TNT_SUMMARY, hipMemcpyDeviceToHost));
+    seq[(size_t)i * 2] = sched_.flag_value();
+    seq[(size_t)i * 2 + 1] = sched_.last_seq();
+    arrived[i] = sched_.arrived_count();
   }
   return 0;
 }

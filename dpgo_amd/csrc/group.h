@@ -249,6 +249,32 @@ class Group {
 
   // test hooks (tests/ compare single operators with the oracle)
   int debug_apply(int local, const char *op, const double *in, int ld_in, double *out, int ld_out);
+  // The scalar kernels of the truncated CG on GIVEN partial sums: a script of launches, each through its production launcher
+  // (launch_cg_begin, launch_tnt_begin, launch_cg_scal, launch_cg_scal_begin) on the group's own segment table, records,
+  // masks, pinned summaries and flag; the state after every launch is read back.  Nothing here computes: the entry feeds
+  // inputs and reads state.
+  enum CgDebugKind { CG_DBG_BEGIN_HOST = 0, CG_DBG_BEGIN_DEVICE, CG_DBG_SCAL0, CG_DBG_SCAL1, CG_DBG_SCAL_BEGIN, CG_DBG_KINDS };
+  struct CgDebugLaunch {
+    int kind = 0;
+    NodeBits bits = 0;                                        // the candidates (the begin kinds)
+    int use_precon = 0, max_it = 0;
+    double grad_tol = 0, pgrad_tol = 0, kappa = 0, theta = 0; // (begin_device, scal_begin)
+    const double *rv = nullptr, *Delta = nullptr, *target = nullptr;   // per local node; rv and target: begin_host only
+    const double *partials = nullptr;                         // slots x nseg_all, copied into the partial sums before the launch
+    int slots = 0;
+  };
+  static constexpr int CG_DBG_RECORD = 17;   // a CgNode as doubles, in the order of its fields
+  // per launch i: records[i][node][CG_DBG_RECORD], masks[i][3], cg_summary[i][node][CG_SUMMARY], tnt_summary and dev_tnt
+  // [i][node][TNT_SUMMARY] (pinned / device), seq[i][2] = the host flag's value once the launch is over and the last sequence
+  // number given out, arrived[i] = the flag's arrival counter
+  int debug_cg_scalars(const CgDebugLaunch *script, int n, double *records, unsigned long long *masks, double *cg_summary,
+                       double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived);
+  // One CG of a refinement round on given points, linear terms and radii (tnt.cpp), through TntRun's own pieces
+  static constexpr int STPCG_DBG_SCALARS = 12;
+  int debug_stpcg(const std::vector<int> &nodes, const double *in, int ld_in, const double *Delta, bool device_start, double fill,
+                  double *out, int ld_out, double *scalars);
+  // the segment table the partial sums are laid out by: nseg_all, and per node its own / neighbour segments [ptr[a], ptr[a+1])
+  int debug_seg_layout(int *nseg_all, int *own_ptr, int *nbr_ptr) const;
   const NodeOperators &host_ops(int local) const { return ops_[local]; }
   const SpdFactor &factor_tt() const { return Ltt_.F; }
   const SpdFactor &factor_rr() const { return Lrr_.F; }
@@ -465,6 +491,11 @@ class Group {
   DevBuf<double> GXc_, GXp_;
   bool keep_gx() const { return opt_.loss != 0 && !dynamic(); }
   DevBuf<double> tmp_[14];                                       // P0 rows, TNT work vectors
+  DevBuf<double> dbg_X_, dbg_g_;                                 // debug_stpcg's point and linear term (allocated by its first call)
+  // own rows of node a between a device record array and a reference-layout matrix (column-major, leading dimension ld;
+  // translations from row row_t0, rotation rows from row_r0): the debug entries' upload / download
+  void put_rows(int a, double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t);
+  void get_rows(int a, const double *dev, double *X, int ld, int row_t0, int row_r0, bool has_t);
   hipEvent_t xchg_done_ = nullptr;   // pending boundary exchange (not owned)
   void join_exchange();              // the group's stream waits for it
   struct ChordalState;

@@ -33,6 +33,12 @@ bool Schedule::close(double seconds) {
   return idle;
 }
 
+unsigned Schedule::arrived_count() const {
+  unsigned v = 0;
+  HIP_CHECK(hipMemcpy(&v, arrived_.p, sizeof(v), hipMemcpyDeviceToHost));
+  return v;
+}
+
 void Schedule::wait(unsigned long long seq) {
   const auto t0 = std::chrono::steady_clock::now();
   struct Acc {   // (what the host-bound test and DPGO_HOST_TIMING need: the time spent in here)

@@ -73,6 +73,9 @@ class Schedule {
     return ReadbackFlag{arrived_.p, host_flag_, seq, dev_seq_.p};
   }
   unsigned long long last_seq() const { return seq_; }   // the last sequence number given out (or counted for a replay)
+  // (test hooks, Group::debug_cg_scalars: the value the host's flag holds now; the arrival counter, read with a copy)
+  unsigned long long flag_value() const { return __atomic_load_n(host_flag_, __ATOMIC_ACQUIRE); }
+  unsigned arrived_count() const;
   // Wait until the kernel that raises the flag to `seq` (or a later one of the in-order stream) has run: seeing the flag
   // means everything enqueued before that kernel is done.
   void wait(unsigned long long seq);

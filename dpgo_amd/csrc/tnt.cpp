@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "group.h"
 
@@ -133,7 +134,9 @@ struct Group::TntRun {
   bool first_round_host();
   void begin_round();
   void later_round();
+  void host_cg_start();
   void finish_round(bool more_steps, bool unasked);
+  void finish_cg(bool more_steps);
   void remaining_cg_steps();
   void trial_of_rest();
   void accept_steps(bool unasked);
@@ -438,7 +441,15 @@ void Group::TntRun::publish() {
 // are TntConst::Delta0.  With `spec` the trial point of the nodes whose CG ends at step 1 follows unasked.
 void Group::TntRun::enqueue_device_start(int nslots, bool plan_spec) {
   const NodeBits bits_nodes = bitsA;
-  G.segment(20, bits_nodes, {K(X), kg, kga, kvar, spec ? 1ull : 0ull, (unsigned long long)nslots, plan_spec ? 1ull : 0ull}, [&] {
+  // (the radii travel by value: part of the key.  run_tnt() starts every node at Delta0; debug_stpcg() takes them as given)
+  unsigned long long kdelta = 1469598103934665603ull;
+  for (int a : nodes) {
+    unsigned long long w;
+    static_assert(sizeof(w) == sizeof(double), "");
+    std::memcpy(&w, &S[a].Delta, sizeof(w));
+    kdelta = (kdelta ^ w) * 1099511628211ull;
+  }
+  G.segment(20, bits_nodes, {K(X), kg, kga, kvar, spec ? 1ull : 0ull, (unsigned long long)nslots, plan_spec ? 1ull : 0ull, kdelta}, [&] {
     G.cur_mask_ = G.live_mask(bits_nodes, nullptr);
     const bool have_sums = quad_model(X, base_ready);
     norms_enqueue(true, have_sums);
@@ -509,6 +520,12 @@ void Group::TntRun::begin_round() {
 // A later round of the candidates A, started on the host from the norms it has read (norms)
 void Group::TntRun::later_round() {
   begin_round();
+  host_cg_start();
+  finish_round(any_live(1), false);
+}
+
+// The CG of the candidates A started on the host: its start values from the norms read back, and its first step, awaited
+void Group::TntRun::host_cg_start() {
   G.set_mask(A);
   bitsA = G.cur_mask_.v;
   // p_0 = -v_0, v_0 = P(grad): a node whose step was rejected starts from the same gradient (pk was overwritten), one whose
@@ -528,22 +545,13 @@ void Group::TntRun::later_round() {
   step_a(true);
   seqA = G.sched_.last_seq();
   G.wait_flag(seqA);
-  finish_round(any_live(1), false);
 }
 
-// What both kinds of round share once the first CG step is in: the remaining steps, the trial points of the nodes that
-// have not had theirs, the acceptance tests, the accepted steps and the new models.  unasked: the first step's trial
-// points were enqueued behind it without waiting (spec)
+// What both kinds of round share once the first CG step is in: the remaining steps (finish_cg); then the trial points of the
+// nodes that have not had theirs, the acceptance tests, the accepted steps and the new models.  unasked: the first step's
+// trial points were enqueued behind it without waiting (spec)
 void Group::TntRun::finish_round(bool more_steps, bool unasked) {
-  if (more_steps) remaining_cg_steps();
-  for (int a : A) {
-    if (!tried[a]) {
-      S[a].h_M_norm = cgs(a, 1);
-      S[a].cg_it = (int)cgs(a, 2);
-    }
-    S[a].cg = false;
-    S[a].inner_total += S[a].cg_it;
-  }
+  finish_cg(more_steps);
   trial_of_rest();
   acc.clear();
   requad.clear();
@@ -554,6 +562,19 @@ void Group::TntRun::finish_round(bool more_steps, bool unasked) {
     G.copy_rows(nabla, nprop, false, 0);   // the model gradient at the accepted point
     launch_tangent_rot(G.lc(), {.X = X, .in = nabla, .out = grad});
     norms(requad, false, false);
+  }
+}
+
+// ... where the CG ends: the steps after the first, and what the host keeps of every candidate's CG
+void Group::TntRun::finish_cg(bool more_steps) {
+  if (more_steps) remaining_cg_steps();
+  for (int a : A) {
+    if (!tried[a]) {
+      S[a].h_M_norm = cgs(a, 1);
+      S[a].cg_it = (int)cgs(a, 2);
+    }
+    S[a].cg = false;
+    S[a].inner_total += S[a].cg_it;
   }
 }
 
@@ -617,6 +638,92 @@ bool Group::run_tnt(const std::vector<int> &nodes, double *X, const double *g, c
   if (deferred_slots_) fetch(deferred_slots_, false);
   run.publish();
   return true;
+}
+
+// One CG of a refinement round, and nothing after it, on given points, linear terms and radii: for tests/test_gpu_stpcg.py.
+// The same pieces in the same order as a round of run_tnt(): the model gradient and the norms, then the host start
+// (host_cg_start: a later round's) or the device start (enqueue_device_start: the first round's, without the unasked trial
+// point), then finish_cg.  in: per node of the GROUP, in order, [Y ; g] ((d+1) n0 rows each, debug_apply's layout); out: per
+// node [s ; H s ; grad]; the rows of the nodes outside `nodes` are set to `fill` beforehand in every work vector and
+// must come back as they were.  scalars: STPCG_DBG_SCALARS per node -- the six start sums, h_M_norm, cg_it, stop_ord, active,
+// live, Delta (zeros for a node outside `nodes`).
+int Group::debug_stpcg(const std::vector<int> &nodes, const double *in, int ld_in, const double *Delta, bool device_start,
+                       double fill, double *out, int ld_out, double *scalars) {
+  finish_update();
+  const int L = num_local();
+  if (nodes.empty() || !in || !Delta || !out || !scalars) return -1;
+  NodeBits bits = 0;
+  for (int a : nodes) {
+    if (a < 0 || a >= L || ((bits >> a) & 1ull)) return -1;
+    bits |= 1ull << a;
+  }
+  sched_.flush_deferred();
+  sync();
+  const size_t nrec = (size_t)P0_ * RS_;
+  if (dbg_X_.n != nrec) { dbg_X_.alloc(nrec); dbg_g_.alloc(nrec); }
+  {   // the work vectors: zero on the rows of `nodes`, `fill` elsewhere
+    std::vector<double> init(nrec, fill);
+    for (int a : nodes) std::fill(init.begin() + (size_t)own_off_[a] * RS_, init.begin() + (size_t)own_off_[a + 1] * RS_, 0.0);
+    for (auto &t : tmp_) HIP_CHECK(hipMemcpy(t.p, init.data(), sizeof(double) * std::min(nrec, t.n), hipMemcpyHostToDevice));
+  }
+  std::vector<int> row0(L + 1, 0);
+  for (int a = 0; a < L; a++) row0[a + 1] = row0[a] + (d_ + 1) * info_[a].n[0];
+  for (int a = 0; a < L; a++) {
+    const int n0 = info_[a].n[0], R0 = (d_ + 1) * n0;
+    put_rows(a, dbg_X_.p, in, ld_in, 2 * row0[a], 2 * row0[a] + n0, true);
+    put_rows(a, dbg_g_.p, in, ld_in, 2 * row0[a] + R0, 2 * row0[a] + R0 + n0, true);
+  }
+  std::fill(scalars, scalars + (size_t)L * STPCG_DBG_SCALARS, 0.0);
+  const bool speculate = tnt_speculate_;
+  tnt_speculate_ = false;   // (the trial point is not part of this)
+  struct Restore { bool &b; bool v; ~Restore() { b = v; } } restore{tnt_speculate_, speculate};
+  TntRun run(*this, nodes, dbg_X_.p, dbg_g_.p, dbg_g_.p, false, nullptr);
+  set_mask(nodes);
+  for (int a : nodes) run.S[a].Delta = Delta[a];
+  auto sums_from = [&](int a, const double *six) { std::copy(six, six + 6, scalars + (size_t)a * STPCG_DBG_SCALARS); };
+  if (device_start) {
+    run.bitsA = cur_mask_.v;
+    run.enqueue_device_start(0, false);
+    run.seqA = sched_.last_seq();
+    run.select_candidates(false);
+    run.begin_round();
+    wait_flag(run.seqA);
+    run.read_device_verdicts();
+    for (int a : nodes) sums_from(a, h_tnt_ + a * TNT_SUMMARY);
+    run.finish_cg(run.any_live(1));
+  } else {
+    const bool have_sums = run.quad_model(run.X, false);
+    run.norms(nodes, true, have_sums);
+    for (int a : nodes) {
+      const double six[6] = {scal(a, 0), scal(a, 1), scal(a, 2), scal(a, 3), run.use_precon ? scal(a, MAX_DOTS) : 0.0,
+                             run.use_precon ? scal(a, MAX_DOTS + 1) : 0.0};
+      sums_from(a, six);
+    }
+    if (run.select_candidates(true)) {
+      run.begin_round();
+      run.host_cg_start();
+      run.finish_cg(run.any_live(1));
+    }
+  }
+  sync();
+  std::vector<CgNode> rec(L);
+  HIP_CHECK(hipMemcpy(rec.data(), cg_.p, sizeof(CgNode) * L, hipMemcpyDeviceToHost));
+  std::vector<char> active(L, 0);
+  for (int a : run.A) active[a] = 1;
+  for (int a : nodes) {
+    double *w = scalars + (size_t)a * STPCG_DBG_SCALARS;
+    if (active[a]) {
+      w[6] = run.S[a].h_M_norm; w[7] = run.S[a].cg_it; w[8] = rec[a].stop_ord; w[10] = rec[a].live; w[11] = rec[a].Delta;
+    }
+    w[9] = active[a];
+  }
+  for (int a = 0; a < L; a++) {
+    const int n0 = info_[a].n[0], R0 = (d_ + 1) * n0;
+    get_rows(a, run.sk, out, ld_out, 3 * row0[a], 3 * row0[a] + n0, true);
+    get_rows(a, run.hh, out, ld_out, 3 * row0[a] + R0, 3 * row0[a] + R0 + n0, true);
+    get_rows(a, run.grad, out, ld_out, 3 * row0[a] + 2 * R0, 3 * row0[a] + 2 * R0 + n0, true);
+  }
+  return 0;
 }
 
 }  // namespace dpgo

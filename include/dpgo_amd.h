@@ -801,6 +801,42 @@ int dpgo_debug_p2p_plan(int rank, int nranks, const int *exp_counts, const int *
  *  layouts.  A suffix ":all" runs the operator under the whole group's launch mask. */
 int dpgo_group_debug_apply(dpgo_group_t *grp, int local, const char *op, const double *in, int ld_in,
                            double *out, int ld_out);
+/* Device: the scalar kernels of the truncated CG (the step length, the boundary / negative-curvature / kernel exits, the
+ * stopping tests, the three device masks) on GIVEN partial sums.  A script of n launches, each made by its production
+ * launcher on the group's own records, masks, pinned summaries and read-back flag:
+ *   kind 0 begin_host  (bits, rv, Delta, target, max_it)           the start values of a later round
+ *        1 begin_device (bits, Delta, use_precon, max_it, the tolerances; sums in slots 0..3 and 6, 7)
+ *        2 scal0 / 3 scal1   phase 0 (slots 0..3) / phase 1 (slot 0) of a CG step
+ *        4 scal_begin   begin_device and phase 0 in one launch (the step's four sums from slot 16 on)
+ * partials: slots x nseg_all doubles (slot-major), copied over the partial sums before the launch (slots = 0: left alone);
+ * dpgo_group_debug_seg_layout gives nseg_all and, per local node a, its own segments [own_ptr[a], own_ptr[a+1]) and
+ * neighbour segments [nbr_ptr[a], nbr_ptr[a+1]).  rv, Delta, target: one double per local node.
+ * Read back after every launch i (L = the group's nodes): records[i][a][17] -- sk_M_pk, sk_M_2, pk_M_2, rv, Delta, Delta_2,
+ * target, h_M_norm, c1, cr, al, kap, be, cg_it, max_it, live, stop_ord --, masks[i][3], cg_summary[i][a][4] (stop ordinal or
+ * 1e18 while live, h_M_norm, cg_it, unused), tnt_summary[i][a][8] and dev_tnt[i][a][8] (the six start sums, active, unused:
+ * pinned and device copies), seq[i][2] (the flag's value, the last sequence number given out), arrived[i] (the flag's
+ * arrival counter: 0 between launches). */
+typedef struct dpgo_cg_debug_launch {
+  int kind, use_precon, max_it, slots;
+  unsigned long long bits;
+  double grad_tol, pgrad_tol, kappa, theta;
+  const double *rv, *Delta, *target, *partials;
+} dpgo_cg_debug_launch_t;
+int dpgo_group_debug_seg_layout(dpgo_group_t *grp, int *nseg_all, int *own_ptr, int *nbr_ptr);
+int dpgo_group_debug_cg_scalars(dpgo_group_t *grp, const dpgo_cg_debug_launch_t *script, int n, double *records,
+                                unsigned long long *masks, double *cg_summary, double *tnt_summary, double *dev_tnt,
+                                unsigned long long *seq, unsigned *arrived);
+/* Device: ONE truncated CG of a refinement round, and nothing after it, on given points: the model gradient and the norms,
+ * the start on the host (device_start = 0: a later round's) or on the device (1: the first round's), the CG steps -- the pieces
+ * dpgo_group_iterate's refinement is made of, in its order, with the group's options (max_tCG_iterations, STPCG_kappa,
+ * STPCG_theta, the gradient tolerances, the preconditioner).  locals: the n nodes that take part.  in: for EVERY node of the
+ * group, in order, [Y ; g] stacked ((d+1) n0 rows each: translations, then rotation rows); Delta: one radius per node of the
+ * group.  out: for every node [s ; H s ; grad] (3 (d+1) n0 rows); the work vectors' rows of the nodes outside `locals` are
+ * set to `fill` before the run and come back in `out`.  scalars: 12 per node -- |grad|^2, <Y, nabla>, <Y, g>, <Y, g>,
+ * |P grad|^2, <grad, P grad> (the last two 0 without a preconditioner), h_M_norm, cg_it, stop_ord, active, live, Delta
+ * (zeros for a node outside `locals`; h_M_norm .. Delta zero for a node that failed a gradient test). */
+int dpgo_group_debug_stpcg(dpgo_group_t *grp, const int *locals, int n, const double *in, int ld_in, const double *Delta,
+                           int device_start, double fill, double *out, int ld_out, double *scalars);
 
 #ifdef __cplusplus
 }

@@ -46,8 +46,16 @@ class TNTParams:
 
 
 def stpcg(g, H, inner, Delta, max_iterations=1000, kappa_fgr=0.1, theta=0.5,
-          P=None, epsilon=1e-8, trace=None):
-    """IterativeSolvers.h:166-426.  Returns (s, update_step_M_norm, num_iterations)."""
+          P=None, epsilon=1e-8, trace=None, decisions=None):
+    """IterativeSolvers.h:166-426.  Returns (s, update_step_M_norm, num_iterations).
+
+    decisions (optional list): every comparison the run takes is appended as (what, iteration, lhs, rhs, scale) -- scale:
+    the magnitude the rounding of lhs - rhs lives on (for the sign test of an inner product <a, b>: |a| |b|) -- and its exit
+    as ("exit", iteration, kind, None, None), kind one of "target", "limit", "kernel", "curvature", "boundary"."""
+    def took(what, a, b, scale=None):
+        if decisions is not None:
+            decisions.append((what, it, a, b, (max(abs(a), abs(b)) if scale is None else scale) if b is not None else None))
+
     s_k = 0 * g
     r_k = g.copy()
     v_k = r_k if P is None else P(r_k)
@@ -60,20 +68,29 @@ def stpcg(g, H, inner, Delta, max_iterations=1000, kappa_fgr=0.1, theta=0.5,
     target = r0_norm * min(kappa_fgr, r0_norm ** theta)
     it = 0
     while it < max_iterations:
+        took("sqrt(rv) <= target", _sqrt(inner(r_k, v_k)), target)
         if _sqrt(inner(r_k, v_k)) <= target:                    # :290
+            took("exit", "target", None)
             break
         Hp = H(p_k)
         kappa_k = inner(p_k, Hp)
+        took("|Hp| / |p| < eps", _sqrt(inner(Hp, Hp)) / _sqrt(inner(p_k, p_k)), epsilon)
         if _sqrt(inner(Hp, Hp)) / _sqrt(inner(p_k, p_k)) < epsilon:   # :305-338
+            took("<p, r> < 0", inner(p_k, r_k), 0.0, _sqrt(inner(p_k, p_k)) * _sqrt(inner(r_k, r_k)))
             if inner(p_k, r_k) < 0:
                 p_k = -p_k
                 sk_M_pk = -sk_M_pk
             sigma = (-sk_M_pk + _sqrt(sk_M_pk * sk_M_pk + pk_M_2 * (Delta_2 - sk_M_2))) / pk_M_2
+            took("exit", "kernel", None)
             return s_k + sigma * p_k, Delta, it
         alpha = inner(r_k, v_k) / kappa_k
         skp1_M_2 = sk_M_2 + 2 * alpha * sk_M_pk + alpha * alpha * pk_M_2
+        took("kappa_k <= 0", kappa_k, 0.0, _sqrt(inner(p_k, p_k)) * _sqrt(inner(Hp, Hp)))
+        if kappa_k > 0:
+            took("skp1 > Delta_2", skp1_M_2, Delta_2)
         if kappa_k <= 0 or skp1_M_2 > Delta_2:                      # :347-362
             sigma = (-sk_M_pk + _sqrt(sk_M_pk * sk_M_pk + pk_M_2 * (Delta_2 - sk_M_2))) / pk_M_2
+            took("exit", "curvature" if kappa_k <= 0 else "boundary", None)
             return s_k + sigma * p_k, Delta, it
         s_k = s_k + alpha * p_k
         r_k = r_k + alpha * Hp
@@ -87,6 +104,8 @@ def stpcg(g, H, inner, Delta, max_iterations=1000, kappa_fgr=0.1, theta=0.5,
         if trace is not None:
             trace.append((alpha, beta))
         it += 1
+    else:
+        took("exit", "limit", None)
     return s_k, _sqrt(sk_M_2), it
 
 

@@ -9,6 +9,8 @@ tolerances are derived from the operation (u = 2^-53):
              error against the oracle's solve <= 10 kappa_1 u |x| (kappa_1 from onenormest on the oracle's factor)
   composite: the solve's forward bound carried through the operator that follows, plus the product bounds
   sums:      the fused dot products against numpy dots of the returned vectors at 1e-13 of sum |a_i b_i|
+  proximal:  the rotations at 1e-12 per entry (the projected matrix's singular values asserted within 1e3 of each other
+             from the oracle's), the translations at the product bound of the rows of N and T that form them
 """
 import os
 
@@ -82,6 +84,10 @@ class Ref:
         self.d, self.n0, self.n1 = p.d, p.n[0], p.n[1]
         m = p.mat
         self.Gtt, self.GtR, self.GRt, self.GRR, self.G = m.Gtt, m.GtR, m.GRt, m.GRR, m.G
+        # the proximal step's T, N and V = H_RR - H_Rt T H_tR (the oracle keeps V for the robust losses only; the device's
+        # step is the general one, DPGOProblem.cpp:618-629, for every loss)
+        self.T, self.N = m.T, sp.csr_matrix(m.N)
+        self.V = m.V if loss != LOSS_NONE else (m.H[self.n0:, self.n0:] - m.H[self.n0:, :self.n0] @ (sp.diags(m.T) @ m.H[:self.n0, self.n0:])).tocsr()
         # edge contributions per row of G: every incident measurement adds one term to each entry of the pose's diagonal
         # block row (d + 1 of them), and one more for the regulariser
         ti, _, tj, _, bi, bj = og.local_rows(p.info, meas_a, self.d)
@@ -130,7 +136,16 @@ def _inputs(rng, ref):
     r = np.zeros_like(Y)
     r[n0:] = tangent_proj(R, rng.standard_normal(R.shape), d)
     Z = rng.standard_normal(((d + 1) * (n0 + ref.n1), d))
-    return dict(Y=Y, const=const, mixed=mixed, g=g, Ydot=Ydot, r=r, Z=Z)
+    # the proximal step's Df: random translation rows; rotation rows chosen so that the matrix it projects,
+    # M = -Df_R + N^T Df_t + V R0, is s_p (Q_p + 0.3 E_p) per pose -- Q_p a rotation, |E_p| <= 1 entrywise / d: singular values within
+    # [0.7, 1.3] s_p, s_p the size of the terms that cancel to it (so the cancellation costs no more than the terms' rounding)
+    Dfp = rng.standard_normal(((d + 1) * n0, d))
+    R0 = Z[n0:n0 + d * n0]
+    rest = ref.N.T @ Dfp[:n0] + ref.V @ R0
+    sc = np.repeat(np.maximum(1.0, _block_norms(rest, d)), d)[:, None]
+    Mstar = sc * (project_to_SOdn(rng.standard_normal((d * n0, d)), d) + 0.3 * rng.uniform(-1, 1, (d * n0, d)) / d)
+    Dfp[n0:] = rest - Mstar
+    return dict(Y=Y, const=const, mixed=mixed, g=g, Ydot=Ydot, r=r, Z=Z, Dfp=Dfp)
 
 
 def run_ops(grp, a, suffix, ref, x, jacobi=False):
@@ -153,7 +168,7 @@ def run_ops(grp, a, suffix, ref, x, jacobi=False):
     out["precon"] = op("precon", np.vstack([x["Y"], x["r"]]), R0 + 1)
     out["retract"] = op("retract", np.vstack([x["Y"], x["Ydot"], x["g"]]), R0)
     out["project"] = op("project", x["mixed"][n0:], d * n0)
-    out["proximal"] = op("proximal", np.vstack([x["Z"], x["g"]]), R0)
+    out["proximal"] = op("proximal", np.vstack([x["Z"], x["Dfp"]]), R0)
     return out
 
 
@@ -232,6 +247,26 @@ def check_ops(ref, x, out, jacobi=False, jacobi_diag=None):
     tref = ref.p.recover_translations(T[n0:], x["g"])
     e_t = ref.tdot_bound(_prod_bound(ref.GtR, T[n0:], x["g"][:n0], ref.terms[:n0]), tref)
     assert np.linalg.norm(T[:n0] - tref) <= e_t, ("retract t", np.linalg.norm(T[:n0] - tref), e_t)
+    # ---- proximal: R = proj(M), M = -Df_R + N^T Df_t + V R0; t = t0 - N (R - R0) - T Df_t
+    Z, Df = x["Z"], x["Dfp"]
+    t0, R0z = Z[:n0], Z[n0:n0 + d * n0]
+    M = -Df[n0:] + ref.N.T @ Df[:n0] + ref.V @ R0z
+    Rp = project_to_SOdn(M, d)
+    tp = t0 - ref.N @ (Rp - R0z) - ref.T[:, None] * Df[:n0]
+    if not ref.p.trivial:   # (the oracle's own statement of the step, where it takes this branch)
+        assert np.array_equal(ref.p.proximal(Z, Df), np.vstack([tp, Rp]))
+    # the conditioning of what is projected, from the oracle's singular values: the smallest at least 1e-3 of the largest
+    sv = np.linalg.svd(M.reshape(n0, d, d), compute_uv=False)
+    assert np.all(sv[:, -1] >= 1e-3 * sv[:, 0]), ("proximal conditioning", (sv[:, -1] / sv[:, 0]).min())
+    X = out["proximal"]
+    # the rotations: 1e-12 per entry, as for retract
+    assert np.abs(X[n0:] - Rp).max() <= 1e-12, ("proximal R", np.abs(X[n0:] - Rp).max())
+    # the translations: the product bound of the rows of N and T that form them (d + 2 terms per entry, both sides), plus the
+    # rotations' 1e-12 carried through |N|
+    aN = abs(ref.N)
+    tb = 2 * (d + 2) * U * (np.abs(t0) + aN @ np.abs(X[n0:] - R0z) + np.abs(ref.T[:, None] * Df[:n0])) \
+        + np.asarray(aN.sum(axis=1)) * 1e-12
+    assert np.all(np.abs(X[:n0] - tp) <= tb), ("proximal t", (np.abs(X[:n0] - tp) / tb).max())
     # ---- project (the existing op; here for the whole-mask launch): nearest rotations, orthonormal
     Q = out["project"].reshape(n0, d, d)
     np.testing.assert_allclose(np.einsum("nij,nkj->nik", Q, Q), np.broadcast_to(np.eye(d), Q.shape), atol=1e-13)
