@@ -225,6 +225,11 @@ SYMBOLS = {
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_group_debug_stpcg": (C.c_int, [C.c_void_p, _IP, C.c_int, _DP, C.c_int, _DP, C.c_int, C.c_double, _DP, C.c_int, _DP]),
     "dpgo_group_debug_seg_layout": (C.c_int, [C.c_void_p, _IP, _IP, _IP]),
+    "dpgo_group_debug_inter_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dpgo_group_debug_inter_iterate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dpgo_group_debug_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _DP, _DP]),
+    "dpgo_group_debug_edge_offsets": (C.c_int, [C.c_void_p, _IP]),
+    "dpgo_group_debug_rescale": (C.c_int, [C.c_void_p, _DP, _DP, _IP, C.c_int, _IP, C.c_int, _IP, _DP, _DP, _IP]),
     "dpgo_group_debug_cg_scalars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _DP, C.POINTER(C.c_ulonglong), _DP, _DP, _DP,
                                               C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
     "dpgo_pcm_options_default": (None, [C.c_void_p]),
@@ -777,6 +782,19 @@ class CgDebugLaunch(C.Structure):
                 ("rv", _DP), ("Delta", _DP), ("target", _DP), ("partials", _DP)]
 
 
+class InterUpdateDebug(C.Structure):
+    """dpgo_inter_update_debug_t"""
+    _fields_ = [(k, C.c_int) for k in ("local", "whole", "quad", "with_Df", "nrecv")] + \
+               [(k, _DP) for k in ("Z", "Zprev", "DfE_old", "GX", "X", "Znbr", "recv")] + [("nsrc", _IP)] + \
+               [(k, _DP) for k in ("DfE", "g", "w", "sums", "Df", "Z_after", "Znbr_after")]
+
+
+class InterIterateDebug(C.Structure):
+    """dpgo_inter_iterate_debug_t"""
+    _fields_ = [(k, C.c_int) for k in ("local", "whole", "fused", "prox", "gamma_dev")] + \
+               [(k, _DP) for k in ("Zc", "Zp", "GXc", "GXp", "Xref", "gamma", "Y", "g", "Df", "Xout", "Xref_after", "sums")]
+
+
 class NodeGroup:
     """The DPGOHash objects of the nodes hosted by one GPU (one process)."""
 
@@ -1238,6 +1256,121 @@ class NodeGroup:
                             active=int(sc[a, 9]), live=int(sc[a, 10]), Delta=float(sc[a, 11])))
             r0 += 3 * R0
         return res
+
+    def _mat(self, X, rows, what):
+        """A reference-layout operand as a Fortran-contiguous float64 matrix of exactly `rows` rows (kept alive by the caller)."""
+        X = np.asfortranarray(np.asarray(X, np.float64))
+        if X.shape != (rows, self.d):
+            raise ValueError("%s: %d x %d expected, got %s" % (what, rows, self.d, X.shape))
+        return X
+
+    def debug_edge_offsets(self):
+        """Debug: first inter-node edge of every node of the group among the group's edges (len(node_ids) + 1 entries)."""
+        o = np.zeros(len(self.node_ids) + 1, np.int32)
+        if lib().dpgo_group_debug_edge_offsets(self._h, _ip(o)) != 0:
+            raise RuntimeError("dpgo_group_debug_edge_offsets failed")
+        return o
+
+    def debug_inter_update(self, k, Z, Zprev=None, DfE_old=None, GX=None, X=None, Znbr=None, recv=None, nsrc=None, whole=False,
+                           sentinel=None, fused_Df=True):
+        """Debug: update()'s inter-edge pass of node k at Z (dpgo_group_debug_inter_update; robust losses).  Z, Zprev, DfE_old,
+        Znbr: (d+1)(n0+n1) x d, reference layout; GX, X: (d+1) n0 x d.  Zprev and DfE_old: the quad term; GX and X: the fused
+        Dfobj (fused_Df=False: by the launch of its own behind the pass); Znbr: the halo copy -- Z's neighbour rows are then pre-filled with `sentinel` (if given) since the pass must not
+        read them; recv ((d+1) nrecv x d) and nsrc (n1 slots, -1: not delivered): the lazy unpack.  Returns a dict: DfE, g, w,
+        sums (slots 0..4), Df (with GX), Z_after, Znbr_after."""
+        d = self.d
+        n0, n1 = self.sizes[k][0], self.sizes[k][1]
+        own, all_ = (d + 1) * n0, (d + 1) * (n0 + n1)
+        q, keep = InterUpdateDebug(), []
+
+        def put(name, M, rows):
+            if M is None:
+                return
+            M = self._mat(M, rows, name)
+            keep.append(M)
+            setattr(q, name, _dp(M))
+
+        Z = np.array(Z, np.float64, order="F")
+        if Znbr is not None and sentinel is not None:
+            Z[own:] = sentinel
+        q.local, q.whole, q.quad, q.with_Df = k, int(bool(whole)), int(Zprev is not None), (0 if GX is None else (1 if fused_Df else 2))
+        put("Z", Z, all_); put("Zprev", Zprev, all_); put("DfE_old", DfE_old, all_); put("Znbr", Znbr, all_)
+        put("GX", GX, own); put("X", X, own)
+        if recv is not None:
+            recv = np.asfortranarray(np.asarray(recv, np.float64))
+            q.nrecv = recv.shape[0] // (d + 1)
+            put("recv", recv, (d + 1) * q.nrecv)
+            ns = np.ascontiguousarray(np.asarray(nsrc, np.int32))
+            if ns.shape != (n1,):
+                raise ValueError("nsrc: one slot per neighbour row")
+            keep.append(ns)
+            q.nsrc = _ip(ns)
+        m1 = int(np.diff(self.debug_edge_offsets())[k])
+        out = dict(DfE=np.zeros((all_, d), order="F"), g=np.zeros((own, d), order="F"), w=np.zeros(max(m1, 1)), sums=np.zeros(5),
+                   Df=np.zeros((own, d), order="F"), Z_after=np.zeros((all_, d), order="F"), Znbr_after=np.zeros((all_, d), order="F"))
+        for name, M in out.items():
+            setattr(q, name, _dp(M))
+        if lib().dpgo_group_debug_inter_update(self._h, C.byref(q)) != 0:
+            raise RuntimeError("dpgo_group_debug_inter_update failed")
+        out["w"] = out["w"][:m1]
+        if GX is None:
+            del out["Df"]
+        return out
+
+    def debug_inter_iterate(self, k, Zc, Zp, gamma, GXc=None, GXp=None, Xref=None, fused=True, prox=False, gamma_dev=False,
+                            whole=False):
+        """Debug: iterate()'s inter-edge pass of node k at Y = Zc + gamma[k] (Zc - Zp) (dpgo_group_debug_inter_iterate), enqueued as
+        the iteration enqueues it.  gamma: one per node of the group; GXc, GXp: the kept products (a statically scaled group needs
+        them); prox (with Xref): the proximal half step.  Returns a dict: Y, g, Df, sums (<Y, g>, |Xout - Xref|^2), Xout, Xref."""
+        d = self.d
+        n0, n1 = self.sizes[k][0], self.sizes[k][1]
+        own, all_ = (d + 1) * n0, (d + 1) * (n0 + n1)
+        q, keep = InterIterateDebug(), []
+        q.local, q.whole, q.fused, q.prox, q.gamma_dev = k, int(bool(whole)), int(bool(fused)), int(bool(prox)), int(bool(gamma_dev))
+        for name, M, rows in (("Zc", Zc, all_), ("Zp", Zp, all_), ("GXc", GXc, own), ("GXp", GXp, own), ("Xref", Xref, own)):
+            if M is not None:
+                M = self._mat(M, rows, name)
+                keep.append(M)
+                setattr(q, name, _dp(M))
+        gam = np.ascontiguousarray(np.asarray(gamma, np.float64))
+        if gam.shape != (len(self.node_ids),):
+            raise ValueError("gamma: one per node of the group")
+        q.gamma = _dp(gam)
+        out = dict(Y=np.zeros((all_, d), order="F"), g=np.zeros((own, d), order="F"), Df=np.zeros((own, d), order="F"),
+                   Xout=np.zeros((own, d), order="F"), Xref_after=np.zeros((own, d), order="F"), sums=np.zeros(2))
+        for name, M in out.items():
+            setattr(q, name, _dp(M))
+        if lib().dpgo_group_debug_inter_iterate(self._h, C.byref(q)) != 0:
+            raise RuntimeError("dpgo_group_debug_inter_iterate failed")
+        return out
+
+    def debug_cost(self, k, Z, eform=False, whole=False):
+        """Debug: k_cost's two slots of node k at Z ((d+1)(n0+n1) x d): (intra-node edges' costs, inter-node edges' rho)."""
+        n0, n1 = self.sizes[k][0], self.sizes[k][1]
+        Z = self._mat(Z, (self.d + 1) * (n0 + n1), "Z")
+        sums = np.zeros(2)
+        if lib().dpgo_group_debug_cost(self._h, k, int(bool(whole)), int(bool(eform)), _dp(Z), _dp(sums)) != 0:
+            raise RuntimeError("dpgo_group_debug_cost failed")
+        return sums
+
+    def debug_rescale(self, w, scale, count, max_rescale_count, nodes):
+        """Debug: the Dynamic rescale's test on given edge weights, scales (one per inter-node edge of the group:
+        debug_edge_offsets) and counters (one per node), over the node set `nodes`, then the rescale of the flagged nodes
+        (dpgo_group_debug_rescale).  Returns a dict: rescaled (how many), flags, host_flags, scale, count."""
+        L = len(self.node_ids)
+        m = int(self.debug_edge_offsets()[-1])
+        w = np.ascontiguousarray(np.asarray(w, np.float64))
+        scale = np.ascontiguousarray(np.asarray(scale, np.float64))
+        count = np.ascontiguousarray(np.asarray(count, np.int32))
+        nodes = np.ascontiguousarray(np.asarray(list(nodes), np.int32))
+        if w.shape != (m,) or scale.shape != (m,) or count.shape != (L,):
+            raise ValueError("debug_rescale: one weight and scale per inter-node edge of the group, one counter per node")
+        flags, hf, so, co = np.zeros(L, np.int32), np.zeros(L), np.zeros(max(m, 1)), np.zeros(L, np.int32)
+        n = lib().dpgo_group_debug_rescale(self._h, _dp(w), _dp(scale), _ip(count), int(max_rescale_count), _ip(nodes), len(nodes),
+                                           _ip(flags), _dp(hf), _dp(so), _ip(co))
+        if n < 0:
+            raise RuntimeError("dpgo_group_debug_rescale failed")
+        return dict(rescaled=n, flags=flags, host_flags=hf, scale=so[:m], count=co)
 
     def debug_seg_layout(self):
         """Debug: (nseg_all, own_ptr, nbr_ptr) -- the segment table the partial sums are laid out by: node a's own segments

@@ -935,6 +935,48 @@ int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const dou
   return guarded([&] { return h->grp->debug_apply(local, op, in, ld_in, out, ld_out); });
 }
 
+int dpgo_group_debug_inter_update(dpgo_group_t *h, const dpgo_inter_update_debug_t *q) {
+  if (!h || !q) return -1;
+  return guarded([&] {
+    dpgo::Group::InterUpdateDebug a;
+    a.local = q->local; a.whole = q->whole; a.quad = q->quad; a.with_Df = q->with_Df; a.nrecv = q->nrecv;
+    a.Z = q->Z; a.Zprev = q->Zprev; a.DfE_old = q->DfE_old; a.GX = q->GX; a.X = q->X; a.Znbr = q->Znbr; a.recv = q->recv; a.nsrc = q->nsrc;
+    a.DfE = q->DfE; a.g = q->g; a.w = q->w; a.sums = q->sums; a.Df = q->Df; a.Z_after = q->Z_after; a.Znbr_after = q->Znbr_after;
+    return h->grp->debug_inter_update(a);
+  });
+}
+
+int dpgo_group_debug_inter_iterate(dpgo_group_t *h, const dpgo_inter_iterate_debug_t *q) {
+  if (!h || !q) return -1;
+  return guarded([&] {
+    dpgo::Group::InterIterateDebug a;
+    a.local = q->local; a.whole = q->whole; a.fused = q->fused; a.prox = q->prox; a.gamma_dev = q->gamma_dev;
+    a.Zc = q->Zc; a.Zp = q->Zp; a.GXc = q->GXc; a.GXp = q->GXp; a.Xref = q->Xref; a.gamma = q->gamma;
+    a.Y = q->Y; a.g = q->g; a.Df = q->Df; a.Xout = q->Xout; a.Xref_after = q->Xref_after; a.sums = q->sums;
+    return h->grp->debug_inter_iterate(a);
+  });
+}
+
+int dpgo_group_debug_cost(dpgo_group_t *h, int local, int whole, int eform, const double *Z, double *sums) {
+  if (!h) return -1;
+  return guarded([&] { return h->grp->debug_cost(local, whole, eform, Z, sums); });
+}
+
+int dpgo_group_debug_edge_offsets(const dpgo_group_t *h, int *edge_offsets) {
+  if (!h || !edge_offsets) return -1;
+  const std::vector<int> &o = h->grp->debug_edge_offsets();
+  for (size_t k = 0; k < o.size(); k++) edge_offsets[k] = o[k];
+  return 0;
+}
+
+int dpgo_group_debug_rescale(dpgo_group_t *h, const double *w, const double *scale, const int *count, int max_rescale_count,
+                             const int *nodes, int n, int *flags, double *host_flags, double *scale_out, int *count_out) {
+  if (!h) return -1;
+  return guarded([&] {
+    return h->grp->debug_rescale(w, scale, count, max_rescale_count, nodes, n, flags, host_flags, scale_out, count_out);
+  });
+}
+
 int dpgo_group_debug_seg_layout(dpgo_group_t *h, int *nseg_all, int *own_ptr, int *nbr_ptr) {
   if (!h) return -1;
   return guarded([&] { return h->grp->debug_seg_layout(nseg_all, own_ptr, nbr_ptr); });

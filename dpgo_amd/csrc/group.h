@@ -273,6 +273,36 @@ class Group {
   static constexpr int STPCG_DBG_SCALARS = 12;
   int debug_stpcg(const std::vector<int> &nodes, const double *in, int ld_in, const double *Delta, bool device_start, double fill,
                   double *out, int ld_out, double *scalars);
+  // The inter-edge pass, the objective and the Dynamic rescale on GIVEN inputs (debug_inter.cpp; tests/test_gpu_inter.py,
+  // tests/test_gpu_rescale_ops.py): each enqueues the launch the iteration makes -- update_inter_pass, prepare_extrapolated (+ the
+  // proximal step amm_head() adds where the pass did not take it), launch_cost, launch_rescale_decide + rescale_device -- on the
+  // group's own records and operators.  Matrices are reference layout, column-major, contiguous: "all" = (d+1)(n0+n1) x d (own
+  // and neighbour rows of node `local`), "own" = (d+1) n0 x d.  `whole`: under the whole group's mask, the other nodes' rows zero.
+  // They overwrite the group's iterates (DfE, and debug_inter_iterate the whole history): not for a group that iterates on.
+  struct InterUpdateDebug {
+    int local = 0, whole = 0, quad = 0, with_Df = 0;
+    const double *Z = nullptr, *Zprev = nullptr, *DfE_old = nullptr;   // all
+    const double *GX = nullptr, *X = nullptr;                          // own (with_Df)
+    const double *Znbr = nullptr;                                      // all (halo: its neighbour rows are the ones read)
+    const double *recv = nullptr; int nrecv = 0; const int *nsrc = nullptr;   // lazy: (d+1) nrecv x d, and n1 slots (-1: not delivered)
+    double *DfE = nullptr, *g = nullptr, *w = nullptr, *sums = nullptr, *Df = nullptr;   // all, own, m1, 5 (slots 0..4), own
+    double *Z_after = nullptr, *Znbr_after = nullptr;                  // all
+  };
+  int debug_inter_update(const InterUpdateDebug &q);
+  struct InterIterateDebug {
+    int local = 0, whole = 0, fused = 1, prox = 0, gamma_dev = 0;
+    const double *Zc = nullptr, *Zp = nullptr;                         // all
+    const double *GXc = nullptr, *GXp = nullptr, *Xref = nullptr;      // own
+    const double *gamma = nullptr;                                     // one per node of the group
+    double *Y = nullptr, *g = nullptr, *Df = nullptr, *Xout = nullptr, *Xref_after = nullptr, *sums = nullptr;   // all, own x4, 2 (<Y, g>, |Xout - Xref|^2)
+  };
+  int debug_inter_iterate(const InterIterateDebug &q);
+  int debug_cost(int local, int whole, int eform, const double *Z, double *sums);   // Z: all; sums: k_cost's two slots
+  // w, scale: one per inter-node edge of the GROUP (node a's from debug_edge_offsets()[a]); count: one per node; nodes: the set.
+  // Out: flags / host_flags / count_out per node, scale_out per edge.  Returns the number of rescaled nodes, -1 on an error.
+  int debug_rescale(const double *w, const double *scale, const int *count, int max_rescale_count, const int *nodes, int n,
+                    int *flags, double *host_flags, double *scale_out, int *count_out);
+  const std::vector<int> &debug_edge_offsets() const { return e_off_; }
   // the segment table the partial sums are laid out by: nseg_all, and per node its own / neighbour segments [ptr[a], ptr[a+1])
   int debug_seg_layout(int *nseg_all, int *own_ptr, int *nbr_ptr) const;
   const NodeOperators &host_ops(int local) const { return ops_[local]; }
@@ -421,7 +451,8 @@ class Group {
   double *upd_slots() const { return partials_.p + (size_t)UPD_SLOT0 * T_.nseg_all; }   // update()'s own partial-sum slots
   // the stated sequence (m: the nodes, possibly under the gate's word; r: the roles)
   void update_product(const NodeMask &m, const UpdateRoles &r, bool from_xak, bool carry_tail);   // G X and <X, 1/2 G X> (slot 5)
-  void update_inter_pass(const NodeMask &m, const UpdateRoles &r, bool quad, bool with_Df, const double *lazy_recv);
+  void update_inter_pass(const NodeMask &m, const UpdateRoles &r, bool quad, bool with_Df, const double *lazy_recv,
+                         double *wout = nullptr);   // wout: the weights go there (a test hook; else to e_w_ with Dynamic rescale)
   void update_reduce(int nslots, const double *pupd);   // the closing reduction into h_upd_
   // The host-side facts of one update() call, computed once (plan_update); the phases below run over it
   struct UpdatePlan {
@@ -496,6 +527,10 @@ class Group {
   // translations from row row_t0, rotation rows from row_r0): the debug entries' upload / download
   void put_rows(int a, double *dev, const double *X, int ld, int row_t0, int row_r0, bool has_t);
   void get_rows(int a, const double *dev, double *X, int ld, int row_t0, int row_r0, bool has_t);
+  // ... and its neighbour rows (dev: an array over own AND neighbour rows)
+  void put_nbr_rows(int a, double *dev, const double *X, int ld, int row_t0, int row_r0);
+  void get_nbr_rows(int a, const double *dev, double *X, int ld, int row_t0, int row_r0);
+  DevBuf<double> dbg_all_[4], dbg_w_;                            // the debug inter-edge entries' operands over all rows, and the weights
   hipEvent_t xchg_done_ = nullptr;   // pending boundary exchange (not owned)
   void join_exchange();              // the group's stream waits for it
   struct ChordalState;

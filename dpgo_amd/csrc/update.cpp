@@ -49,11 +49,11 @@ void Group::update_product(const NodeMask &m, const UpdateRoles &r, bool from_xa
 
 // the inter-edge pass: slots 0, 1 and 2 = <X, g>; quad: a later iteration (the majorisation gap against X[iter-1]);
 // with_Df: Dfobj and |grad F|^2 (slot 4) on the way; lazy_recv: the receive buffer of a lazy unpack
-void Group::update_inter_pass(const NodeMask &m, const UpdateRoles &r, bool quad, bool with_Df, const double *lazy_recv) {
+void Group::update_inter_pass(const NodeMask &m, const UpdateRoles &r, bool quad, bool with_Df, const double *lazy_recv, double *wout) {
   InterEdgesDev E = E_;
   if (lazy_recv) { E.recv = lazy_recv; E.nsrc = recv_nsrc_.p; }
   InterUpdate up = {.quad = quad, .Z = r.zc, .Zprev = r.zp, .Qdiag = Qd_.p, .Ddiag = Dd_.p, .DfE = DfE_.p, .g = r.gc,
-                    .partials = r.pupd, .wout = dynamic() ? e_w_.p : nullptr, .Znbr = r.xk};
+                    .partials = r.pupd, .wout = wout ? wout : (dynamic() ? e_w_.p : nullptr), .Znbr = r.xk};
   if (with_Df) { up.GX = r.gx; up.X = r.xak; up.Df = r.dfc; up.gn_slot = 4; }
   launch_inter_update(lc(m), E, opt_.loss, opt_.loss_reg, up);
 }

@@ -180,6 +180,100 @@ def ladder(d=3, seed=7):
                 tau=rng.uniform(1.0, 100.0, M), outlier=np.zeros(M, bool))
 
 
+INTER_LADDER_SIZES = (70, 1, 64, 65)       # own poses of the nodes of inter_ladder(); node 0 holds the ladder and the hub
+INTER_LADDER_NBRS = (65, 1, 63, 64)        # ... and their neighbour rows (n1)
+INTER_LADDER_SPAN = 130
+INTER_LADDER_TOP = 40
+INTER_LADDER_HUB = 41                      # the hub pose of node 0
+INTER_LADDER_HUB_INCIDENCES = 300
+INTER_LADDER_KINK = 48                     # edges whose noise is set so that s lands within 10 % of `kink` (half on each side)
+
+
+def _small_rotations_d(rng, sigma, d):
+    """exp of a rotation vector (d = 3) / angle (d = 2) with N(0, sigma_e^2) entries, one per entry of sigma."""
+    if d == 3:
+        return _exp_so3(sigma[:, None] * rng.standard_normal((len(sigma), 3)))
+    th = sigma * rng.standard_normal(len(sigma))
+    c, s = np.cos(th), np.sin(th)
+    return np.stack([np.stack([c, -s], 1), np.stack([s, c], 1)], 1)
+
+
+def inter_ladder(d=3, seed=11, kink=0.25):
+    """A 4-node SE(d) graph whose INTER-node incidence lists cover what the inter-edge kernels split differently (for
+    operator tests of the inter-edge pass, the objective and the Dynamic rescale).
+
+    Node 0 (ids 0..69): own pose k <= 40 has exactly k inter-node incidences (0: the empty chain), even ones as the tail of
+    an edge into node 2, odd ones as the head of an edge out of node 3 (written reversed: I > J); poses divisible by 4 carry
+    one pair twice (parallel edges).  Pose 41 is the hub: 300 incidences, both roles, three of them with the single pose of
+    node 1 (both directions and a parallel pair).  Poses 63, 64, 65 and 69 (the 64-row segment boundary and the last own row)
+    have one incidence of each role.  Node 0 has well over 256 inter-node edges.
+    Node 1: one pose, no intra-node edge, one neighbour row.  Node 2 (64 poses): every inter-node incidence is a head.
+    Node 3 (65 poses): every one a tail.  Own sizes INTER_LADDER_SIZES, neighbour rows INTER_LADDER_NBRS.
+
+    Measurements are formed from ground-truth poses (random rotations, translations uniform in [0, 10)^d): R_e = R_i^T R_j
+    E_e, t_e = R_i^T (t_j - t_i) + n_e with E_e = exp(N(0, sigma_e^2)), n_e ~ N(0, sigma_e^2 I) and sigma_e log-uniform over
+    1e-8 .. 1e1, so that every edge's residual at the ground truth is its own noise.  INTER_LADDER_KINK of the inter-node
+    edges instead carry an exact rotation and a translation error of length sqrt(s / tau) with s / kink = 1 -+ [0.001, 0.1]:
+    they sit on both sides of the Huber kink of loss_reg = kink.  tau, kappa uniform in [1, 100].
+    Returns the dict of grid() plus num_nodes, Rg, tg (the ground truth) and sigma (the per-edge noise level; for the kink
+    edges sqrt(s / tau))."""
+    rng = np.random.default_rng(seed)
+    nn, S = len(INTER_LADDER_SIZES), INTER_LADDER_SPAN
+    N = nn * S
+    b1, b2, b3 = S, 2 * S, 3 * S
+    I, J = [], []
+
+    def add(i, j):
+        I.append(i); J.append(j)
+
+    # intra-node chains (every own pose is used; node 1 has none), some reversed
+    for a in (0, 2, 3):
+        for k in range(INTER_LADDER_SIZES[a] - 1):
+            add(a * S + k + 1, a * S + k) if k % 5 == 0 else add(a * S + k, a * S + k + 1)
+    n_intra = len(I)
+
+    def incidence(k, j, slot):
+        if j % 2 == 0:
+            add(k, b2 + slot % 32)        # tail role in node 0, head in node 2
+        else:
+            add(b3 + slot % 32, k)        # head role in node 0, tail in node 3 (reversed)
+
+    for k in range(1, INTER_LADDER_TOP + 1):
+        for j in range(k):
+            incidence(k, j, 7 * k + (0 if (k % 4 == 0 and j == 2) else j))
+    hub = INTER_LADDER_HUB
+    add(b1, hub); add(hub, b1); add(b1, hub)
+    for j in range(INTER_LADDER_HUB_INCIDENCES - 3):
+        incidence(hub, j, 3 * j + j // 64)
+    for k in (63, 64, 65, INTER_LADDER_SIZES[0] - 1):
+        incidence(k, 0, k); incidence(k, 1, k)
+    # node 3 -> node 2: 18 further poses of node 3 as neighbours of node 2, 20 of node 2 as neighbours of node 3
+    for i in range(18):
+        add(b3 + 32 + i, b2 + 32 + i)
+    add(b3 + 32, b2 + 50); add(b3 + 32, b2 + 51); add(b3 + 33, b2 + 33)   # (the last one parallel)
+    I = np.asarray(I, np.int64)
+    J = np.asarray(J, np.int64)
+    M = len(I)
+    Rg = _random_rotations_d(rng, N, d)
+    tg = rng.uniform(0.0, 10.0, (N, d))
+    tau = rng.uniform(1.0, 100.0, M)
+    kappa = rng.uniform(1.0, 100.0, M)
+    sigma = 10.0 ** rng.uniform(-8.0, 1.0, M)
+    Rt = np.einsum("eba,ebc->eac", Rg[I], Rg[J])
+    tt = np.einsum("eba,eb->ea", Rg[I], tg[J] - tg[I])
+    R = Rt @ _small_rotations_d(rng, sigma, d)
+    t = tt + sigma[:, None] * rng.standard_normal((M, d))
+    sel = n_intra + rng.choice(M - n_intra, INTER_LADDER_KINK, replace=False)
+    off = rng.uniform(0.001, 0.1, INTER_LADDER_KINK) * np.where(np.arange(INTER_LADDER_KINK) % 2 == 0, 1.0, -1.0)
+    dirs = rng.standard_normal((INTER_LADDER_KINK, d))
+    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    sigma[sel] = np.sqrt(kink * (1.0 + off) / tau[sel])
+    R[sel] = Rt[sel]
+    t[sel] = tt[sel] + sigma[sel, None] * dirs
+    return dict(d=d, num_poses=N, num_nodes=nn, I=I, J=J, R=R, t=t, kappa=kappa, tau=tau, outlier=np.zeros(M, bool),
+                Rg=Rg, tg=tg, sigma=sigma)
+
+
 def two_node(m, poses_per_node=256, seed=1, sigma_t=0.05, sigma_r=0.02, outlier_frac=0.1, extent=10.0):
     """A two-node SE(3) graph with m inter-node edges (the PCM test and benchmark instance).  Ground-truth poses:
     random rotations, translations uniform in [0, extent)^3; node 0 holds poses [0, P), node 1 [P, 2P) (the

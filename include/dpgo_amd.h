@@ -837,6 +837,43 @@ int dpgo_group_debug_cg_scalars(dpgo_group_t *grp, const dpgo_cg_debug_launch_t 
  * (zeros for a node outside `locals`; h_M_norm .. Delta zero for a node that failed a gradient test). */
 int dpgo_group_debug_stpcg(dpgo_group_t *grp, const int *locals, int n, const double *in, int ld_in, const double *Delta,
                            int device_start, double fill, double *out, int ld_out, double *scalars);
+/* Device: the robust inter-edge pass (k_inter), the objective (k_cost) and the Dynamic rescale on GIVEN inputs, each through
+ * the launch the iteration makes (tests/test_gpu_inter.py, tests/test_gpu_rescale_ops.py).  Matrices are reference layout,
+ * column-major and contiguous: "all" = (d+1)(n0+n1) x d -- own and neighbour rows of node `local`, [t_own ; R_own ; t_nbr ;
+ * R_nbr] --, "own" = (d+1) n0 x d.  whole = 1: under the whole group's launch mask, the other nodes' rows zero.  Robust losses
+ * only.  The entries overwrite the group's iterates; use them on a group that does not iterate afterwards.
+ * inter_update: update()'s pass at Z.  quad: the majorisation gap against Zprev and the previous DfE (DfE_old); with_Df: Dfobj =
+ *   GX + g, its tangent projection at X and |grad F|^2 (sums[4]) -- 1: inside the pass, 2: by k_tangent_full behind it; Znbr (optional, all): the neighbour rows are read from it
+ *   and copied into Z on the way (the halo copy); recv / nrecv / nsrc (optional, with Znbr): a lazy unpack -- recv holds nrecv
+ *   poses ((d+1) nrecv x d: translations, then rotation blocks), nsrc[r] the slot of neighbour row r or -1.  Out: DfE (all),
+ *   g (own), w (one weight per inter-node edge of the node, in the order of its measurements), sums[5] (slots 0..4: sum rho,
+ *   the quad term, <z, g>, unused, |grad F|^2), Df (own, with_Df), Z_after / Znbr_after (all, optional): what the pass left.
+ * inter_iterate: iterate()'s pass at Y = Zc + gamma[node] (Zc - Zp), as prepare_extrapolated enqueues it.  fused = 1: the
+ *   extrapolation inside the pass (and, with the kept products GXc / GXp of a statically scaled group, Df; with prox the
+ *   proximal half step on it); fused = 0: the extrapolation, the pass and the proximal step as launches of their own.
+ *   gamma_dev = 1: the gammas are read from device memory.  Out: Y (all; a fused pass stores its own rows only), g, Df (own),
+ *   Xout and Xref_after (own, with prox: proximal(Y, Df), and Xref with Xout's rotations), sums[2] = <Y, g>, |Xout - Xref|^2.
+ * cost: k_cost at Z (all): sums[2] = the intra-node edges' costs, the inter-node edges' rho; eform 1: the data-matrix form.
+ * rescale (Rescale::Dynamic groups): w, scale: one per inter-node edge of the GROUP (node a's start at edge_offsets[a]); count:
+ *   one per node; nodes: the set that is tested.  Runs the test, then the rescale of the flagged nodes (the block-diagonal
+ *   terms, the factorisation of G_tt, the solve's panels).  Returns the number of rescaled nodes, -1 on an error. */
+typedef struct dpgo_inter_update_debug {
+  int local, whole, quad, with_Df, nrecv;
+  const double *Z, *Zprev, *DfE_old, *GX, *X, *Znbr, *recv;
+  const int *nsrc;
+  double *DfE, *g, *w, *sums, *Df, *Z_after, *Znbr_after;
+} dpgo_inter_update_debug_t;
+typedef struct dpgo_inter_iterate_debug {
+  int local, whole, fused, prox, gamma_dev;
+  const double *Zc, *Zp, *GXc, *GXp, *Xref, *gamma;
+  double *Y, *g, *Df, *Xout, *Xref_after, *sums;
+} dpgo_inter_iterate_debug_t;
+int dpgo_group_debug_inter_update(dpgo_group_t *grp, const dpgo_inter_update_debug_t *q);
+int dpgo_group_debug_inter_iterate(dpgo_group_t *grp, const dpgo_inter_iterate_debug_t *q);
+int dpgo_group_debug_cost(dpgo_group_t *grp, int local, int whole, int eform, const double *Z, double *sums);
+int dpgo_group_debug_edge_offsets(const dpgo_group_t *grp, int *edge_offsets);   /* num_local + 1 ints */
+int dpgo_group_debug_rescale(dpgo_group_t *grp, const double *w, const double *scale, const int *count, int max_rescale_count,
+                             const int *nodes, int n, int *flags, double *host_flags, double *scale_out, int *count_out);
 
 #ifdef __cplusplus
 }

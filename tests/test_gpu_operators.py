@@ -78,9 +78,12 @@ def _assert_sums(got, pairs, what):
 class Ref:
     """The oracle's operators of one node, the RegularizedCholesky shift formed with the device's lambda_max."""
 
-    def __init__(self, meas_a, a, loss, opt, lam_dev, precon_rr=True):
+    def __init__(self, meas_a, a, loss, opt, lam_dev, precon_rr=True, scale=None):
+        """scale (one per inter-node edge of the node): the Rescale::Dynamic surrogate at these scales (update_quadratic_mat)."""
         self.p = p = DPGOProblem(a, meas_a, opt.regularizer, loss, opt.reg_Cholesky_precon_max_condition_number, opt.loss_reg,
-                                 preconditioner=0)
+                                 preconditioner=0, dynamic=scale is not None)
+        if scale is not None:
+            p.update_quadratic_mat(scale)
         self.d, self.n0, self.n1 = p.d, p.n[0], p.n[1]
         m = p.mat
         self.Gtt, self.GtR, self.GRt, self.GRR, self.G = m.Gtt, m.GtR, m.GRt, m.GRR, m.G
