@@ -265,6 +265,12 @@ SYMBOLS = {
                                          C.POINTER(C.c_longlong)]),
     "dpgo_group_cert_apply": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_debug_rayleigh_ritz": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _IP]),
+    "dpgo_group_debug_cert_gram": (C.c_int, [C.c_void_p, _DP, _DP, _DP, _DP, _DP, _DP, _DP, C.c_int, _DP, _DP]),
+    "dpgo_group_debug_cert_update": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dpgo_group_debug_cert_nbr_rows": (C.c_int, [C.c_void_p]),
+    "dpgo_group_debug_cert_precon": (C.c_int, [C.c_void_p, _DP]),
+    "dpgo_group_debug_cert_trace": (C.c_int, [C.c_void_p, C.c_int]),
+    "dpgo_group_debug_cert_trace_get": (C.c_int, [C.c_void_p, _DP, C.c_longlong, _IP, C.POINTER(C.c_longlong)]),
     "dpgo_edge_eval_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "dpgo_edge_eval_free": (None, [C.c_void_p]),
     "dpgo_edge_eval_run": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP, C.c_void_p]),
@@ -787,6 +793,12 @@ class InterUpdateDebug(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("local", "whole", "quad", "with_Df", "nrecv")] + \
                [(k, _DP) for k in ("Z", "Zprev", "DfE_old", "GX", "X", "Znbr", "recv")] + [("nsrc", _IP)] + \
                [(k, _DP) for k in ("DfE", "g", "w", "sums", "Df", "Z_after", "Znbr_after")]
+
+
+class CertUpdateDebug(C.Structure):
+    """dpgo_cert_update_debug_t"""
+    _fields_ = [(k, _DP) for k in ("C", "theta", "V", "W", "P", "SV", "SW", "SP")] + [("ld", C.c_int), ("precondition", C.c_int),
+               ("nbr_fill", C.c_double)] + [(k, _DP) for k in ("V_out", "W_out", "P_out", "SV_out", "SW_out", "SP_out", "sums", "nbr")]
 
 
 class InterIterateDebug(C.Structure):
@@ -1371,6 +1383,82 @@ class NodeGroup:
         if n < 0:
             raise RuntimeError("dpgo_group_debug_rescale failed")
         return dict(rescaled=n, flags=flags, host_flags=hf, scale=so[:m], count=co)
+
+    def _cert_blocks(self, names, mats):
+        rows = (self.d + 1) * self.graph.num_poses
+        out = []
+        for name, M in zip(names, mats):
+            M = np.asfortranarray(np.asarray(M, np.float64))
+            if M.shape != (rows, self.d):
+                raise ValueError("%s must be %r" % (name, (rows, self.d)))
+            out.append(M)
+        return rows, out
+
+    def debug_cert_gram(self, X, V, W, P, SV, SP, MW=None):
+        """Debug: one launch of k_cert_gram and one of k_cert_reduce on given blocks, as the certificate's search makes them
+        (dpgo_group_debug_cert_gram).  Lambda is that of X; the buffer of S W takes MW (= M W), or with MW None the product
+        M W the loop forms.  Returns (sums, SW): the raw host sums -- the upper triangles of B^T B and of B^T (S B), row-major,
+        then 2 d slots the launch does not write -- and the finished S W."""
+        rows, (X, V, W, P, SV, SP) = self._cert_blocks(("X", "V", "W", "P", "SV", "SP"), (X, V, W, P, SV, SP))
+        mw = None
+        if MW is not None:
+            MW = self._cert_blocks(("MW",), (MW,))[1][0]
+            mw = _dp(MW)
+        d = self.d
+        sums, SW = np.zeros(3 * d * (3 * d + 1) + 2 * d), np.zeros((rows, d), order="F")
+        if lib().dpgo_group_debug_cert_gram(self._h, _dp(X), _dp(V), _dp(W), _dp(P), _dp(SV), _dp(SP), mw, rows, _dp(sums), _dp(SW)) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_gram failed")
+        return sums, SW
+
+    def debug_cert_update(self, C_, theta, V, W, P, SV, SW, SP, precondition, nbr_fill=0.0):
+        """Debug: one launch of k_cert_update and one of k_cert_reduce on given blocks (dpgo_group_debug_cert_update).  C_: 3d x d
+        (the rows of V, W, P), theta: d.  Returns a dict: V, W, P, SV, SW, SP (the buffers afterwards), rr, vv (the launch's
+        sums |R'_j|^2, |V'_j|^2) and nbr ((3, P1, (d+1) d): the neighbour records of V, W, P, which were nbr_fill before)."""
+        d = self.d
+        rows, ins = self._cert_blocks(("V", "W", "P", "SV", "SW", "SP"), (V, W, P, SV, SW, SP))
+        Cm = np.ascontiguousarray(np.asarray(C_, np.float64))
+        th = np.ascontiguousarray(np.asarray(theta, np.float64))
+        if Cm.shape != (3 * d, d) or th.shape != (d,):
+            raise ValueError("debug_cert_update: C is 3d x d, theta has d entries")
+        p1 = lib().dpgo_group_debug_cert_nbr_rows(self._h)
+        out = dict((k, np.zeros((rows, d), order="F")) for k in ("V", "W", "P", "SV", "SW", "SP"))
+        sums, nbr = np.zeros(3 * d * (3 * d + 1) + 2 * d), np.zeros((3, max(p1, 0), (d + 1) * d))
+        q = CertUpdateDebug()
+        q.C, q.theta = _dp(Cm), _dp(th)
+        for k, M in zip(("V", "W", "P", "SV", "SW", "SP"), ins):
+            setattr(q, k, _dp(M))
+            setattr(q, k + "_out", _dp(out[k]))
+        q.ld, q.precondition, q.nbr_fill, q.sums, q.nbr = rows, int(bool(precondition)), float(nbr_fill), _dp(sums), _dp(nbr)
+        if lib().dpgo_group_debug_cert_update(self._h, C.byref(q)) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_update failed")
+        nt2 = 3 * d * (3 * d + 1)
+        out.update(rr=sums[nt2:nt2 + d].copy(), vv=sums[nt2 + d:].copy(), nbr=nbr)
+        return out
+
+    def debug_cert_precon(self):
+        """Debug: the block-Jacobi blocks T_p the certificate's search applies, (N, d+1, d+1) by global pose."""
+        T = np.zeros((self.graph.num_poses, self.d + 1, self.d + 1))
+        if lib().dpgo_group_debug_cert_precon(self._h, _dp(T)) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_precon failed")
+        return T
+
+    def debug_cert_trace(self, on):
+        """Debug: switch the trace of the certificate's search on or off (off is the default)."""
+        if lib().dpgo_group_debug_cert_trace(self._h, int(bool(on))) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_trace failed")
+
+    def debug_cert_trace_get(self):
+        """Debug: the passes of the last traced search, a list of dicts: sums, nblk, used, theta (d), C (3d x d), refresh."""
+        d = self.d
+        ln, cnt = C.c_int(0), C.c_longlong(0)
+        if lib().dpgo_group_debug_cert_trace_get(self._h, None, 0, C.byref(ln), C.byref(cnt)) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_trace_get failed")
+        rec = np.zeros((cnt.value, ln.value))
+        if cnt.value and lib().dpgo_group_debug_cert_trace_get(self._h, _dp(rec), rec.size, C.byref(ln), C.byref(cnt)) != 0:
+            raise RuntimeError("dpgo_group_debug_cert_trace_get failed")
+        ns = 3 * d * (3 * d + 1) + 2 * d
+        return [dict(sums=r[:ns].copy(), nblk=int(r[ns]), used=int(r[ns + 1]), theta=r[ns + 2:ns + 2 + d].copy(),
+                     C=r[ns + 2 + d:ns + 2 + d + 3 * d * d].reshape(3 * d, d).copy(), refresh=bool(r[-1])) for r in rec]
 
     def debug_seg_layout(self):
         """Debug: (nseg_all, own_ptr, nbr_ptr) -- the segment table the partial sums are laid out by: node a's own segments

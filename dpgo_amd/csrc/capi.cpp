@@ -977,6 +977,48 @@ int dpgo_group_debug_rescale(dpgo_group_t *h, const double *w, const double *sca
   });
 }
 
+int dpgo_group_debug_cert_gram(dpgo_group_t *h, const double *X, const double *V, const double *W, const double *P,
+                               const double *SV, const double *SP, const double *MW, int ld, double *sums, double *SW) {
+  if (!h || !h->grp || !X) return -1;
+  return guarded([&] { return h->grp->debug_cert_gram(X, V, W, P, SV, SP, MW, ld, sums, SW); });
+}
+
+int dpgo_group_debug_cert_update(dpgo_group_t *h, const dpgo_cert_update_debug_t *q) {
+  if (!h || !h->grp || !q) return -1;
+  return guarded([&] {
+    dpgo::Group::CertUpdateDebug a;
+    a.C = q->C; a.theta = q->theta; a.V = q->V; a.W = q->W; a.P = q->P; a.SV = q->SV; a.SW = q->SW; a.SP = q->SP;
+    a.ld = q->ld; a.precondition = q->precondition; a.nbr_fill = q->nbr_fill;
+    a.out[0] = q->V_out; a.out[1] = q->W_out; a.out[2] = q->P_out; a.out[3] = q->SV_out; a.out[4] = q->SW_out; a.out[5] = q->SP_out;
+    a.sums = q->sums; a.nbr = q->nbr;
+    return h->grp->debug_cert_update(a);
+  });
+}
+
+int dpgo_group_debug_cert_nbr_rows(const dpgo_group_t *h) { return h && h->grp ? h->grp->debug_cert_nbr_rows() : -1; }
+
+int dpgo_group_debug_cert_precon(dpgo_group_t *h, double *T) {
+  if (!h || !h->grp || !T) return -1;
+  return guarded([&] { return h->grp->debug_cert_precon(T); });
+}
+
+int dpgo_group_debug_cert_trace(dpgo_group_t *h, int on) {
+  if (!h || !h->grp) return -1;
+  h->grp->debug_cert_trace(on != 0);
+  return 0;
+}
+
+int dpgo_group_debug_cert_trace_get(const dpgo_group_t *h, double *records, long long cap, int *record_len, long long *count) {
+  if (!h || !h->grp || !record_len || !count) return -1;
+  const std::vector<double> &t = h->grp->debug_cert_trace_records();
+  *record_len = h->grp->cert_trace_len();
+  *count = (long long)t.size() / *record_len;
+  if (!records) return 0;   // (the sizes alone)
+  if (cap < (long long)t.size()) return -1;
+  std::copy(t.begin(), t.end(), records);
+  return 0;
+}
+
 int dpgo_group_debug_seg_layout(dpgo_group_t *h, int *nseg_all, int *own_ptr, int *nbr_ptr) {
   if (!h) return -1;
   return guarded([&] { return h->grp->debug_seg_layout(nseg_all, own_ptr, nbr_ptr); });

@@ -174,6 +174,12 @@ int Group::cert_begin(const double *X, int ld) {
     fprintf(stderr, "[dpgo_amd] ERROR: certificate: inconsistent size of X.\n");
     return -1;
   }
+  return cert_ready();
+}
+
+// ... and the part of it that does not depend on X
+int Group::cert_ready() {
+  const int N = num_poses_global_;
   if (opt_.loss != 0) {
     fprintf(stderr, "[dpgo_amd] ERROR: certificate: the group was created with a robust loss; the certificate is that of the "
                     "trivial loss (create a group with LOSS_NONE and max_iterations = 0).\n");
@@ -205,10 +211,11 @@ int Group::cert_begin(const double *X, int ld) {
   return 0;
 }
 
-// a global (d+1)N x d matrix (reference layout) into the own rows of a record array; the neighbour rows follow by the halo copy
-void Group::cert_upload(const double *M, int ld, int ncols, double *dev_all) {
+// a global (d+1)N x d matrix (reference layout) into the own rows of a record array; the neighbour rows (zeroed here unless
+// the array has none: with_nbr = false) follow by the halo copy
+void Group::cert_upload(const double *M, int ld, int ncols, double *dev_all, bool with_nbr) {
   const int N = num_poses_global_;
-  std::vector<double> rec((size_t)(P0_ + P1_) * RS_, 0.0);
+  std::vector<double> rec((size_t)(P0_ + (with_nbr ? P1_ : 0)) * RS_, 0.0);
   for (int row = 0; row < P0_; row++) {
     const int g = cert_->gid[row];
     double *r = &rec[(size_t)row * RS_];
@@ -627,6 +634,7 @@ int Group::cert_search(const CertOptions &o, const double *V0, int ldv0, CertRes
   HIP_CHECK(hipMemsetAsync(c.SP.p, 0, sizeof(double) * c.SP.n, st_));
 
   const double *h = c.h_sums;
+  if (cert_trace_on_) cert_trace_.clear();
   double theta0 = 0;
   bool have_norms = false, have_W = false, drop_P = true;   // (the first Rayleigh-Ritz step sees V alone, the second [V W])
   std::vector<double> xg(rows), sx(rows);
@@ -661,6 +669,7 @@ int Group::cert_search(const CertOptions &o, const double *V0, int ldv0, CertRes
       for (int j = 0; j < d; j++) K.theta[j] = th[j];
       launch_cert_update(lc(all), K, o.precondition ? c.Tp.p : nullptr, c.V.p, c.W.p, c.P.p, c.SV.p, c.SW.p, c.SP.p,
                          c.partials.p);
+      if (cert_trace_on_) cert_trace_pass(h, nblk, used, K);
       res.iterations++;
       theta0 = th[0];
       have_norms = true;
@@ -670,6 +679,7 @@ int Group::cert_search(const CertOptions &o, const double *V0, int ldv0, CertRes
       if (o.refresh_every > 0 && res.iterations % o.refresh_every == 0) {
         cert_apply_S(c.V.p, c.SV.p);
         cert_apply_S(c.P.p, c.SP.p);
+        if (cert_trace_on_) cert_trace_.back() = 1.0;
       }
     }
     // the returned vector: column 0 of V, normalised; theta and the residual from one fresh product S x

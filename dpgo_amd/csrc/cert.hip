@@ -93,7 +93,9 @@ __device__ __forceinline__ void lambda_block(const double *x, const double *mx, 
 #pragma unroll
     for (int s = 0; s < D; s++) L[r * D + s] = 0.5 * (P[r * D + s] + P[s * D + r]);
 }
-// out.Y = mv.Y - L v.Y (rotation rows); out.x = mv.x
+// out.Y = mv.Y - L v.Y (rotation rows); out.x = mv.x.  The d products are summed first and subtracted once: the error is
+// d u |L| |v| + u |out|.  Subtracting them from mv one fma at a time rounds every partial result, d u |out| + 2 (d - 1) u |L| |v|,
+// which is up to d times more where |mv| is large against |L| |v| (tests/test_gpu_cert_search.py: test_gram_finishes_S_W).
 template <int D>
 __device__ __forceinline__ void sub_lambda(const double *L, const double *v, const double *mv, double *out) {
 #pragma unroll
@@ -102,10 +104,10 @@ __device__ __forceinline__ void sub_lambda(const double *L, const double *v, con
   for (int r = 0; r < D; r++)
 #pragma unroll
     for (int c = 0; c < D; c++) {
-      double a = mv[D + r * D + c];
+      double t = L[r * D] * v[D + c];
 #pragma unroll
-      for (int k = 0; k < D; k++) a = fma(-L[r * D + k], v[D + k * D + c], a);
-      out[D + r * D + c] = a;
+      for (int k = 1; k < D; k++) t = fma(L[r * D + k], v[D + k * D + c], t);
+      out[D + r * D + c] = mv[D + r * D + c] - t;
     }
 }
 

@@ -303,6 +303,30 @@ class Group {
   int debug_rescale(const double *w, const double *scale, const int *count, int max_rescale_count, const int *nodes, int n,
                     int *flags, double *host_flags, double *scale_out, int *count_out);
   const std::vector<int> &debug_edge_offsets() const { return e_off_; }
+  // The kernels of the certificate's search on GIVEN inputs (debug_cert.cpp; tests/test_gpu_cert_search.py): each copies
+  // reference-layout matrices ((d+1)N x d, column-major, leading dimension ld) into CertState's buffers with cert_upload, makes
+  // the launch cert_search makes -- launch_cert_gram / launch_cert_update, then launch_cert_reduce over all cert_nsums(d)
+  // sums -- and reads the results back with cert_download.  Nothing here computes.  Preconditions of certify.
+  // gram: cert_prepare(X) for Lambda; S W's buffer takes MW, or (MW null) cert_apply_M(W) as in the loop.  sums: the
+  // cert_nsums(d) host sums as k_cert_reduce left them (both upper triangles in cert_tri order first); SW: the finished S W
+  int debug_cert_gram(const double *X, const double *V, const double *W, const double *P, const double *SV, const double *SP,
+                      const double *MW, int ld, double *sums, double *SW);
+  // update: C 3d x d row-major and theta[d] go into a CertCoef; precondition: cert_build_precon() and its T_p, else null.
+  // The neighbour rows of V, W, P are set to nbr_fill before the launch and handed back raw in nbr (3 P1 RS doubles: V's,
+  // W's, P's records).  out: V', W', P', SV', SW (as the launch left it), SP', each (d+1)N x d with ld; sums: cert_nsums(d)
+  struct CertUpdateDebug {
+    const double *C = nullptr, *theta = nullptr, *V = nullptr, *W = nullptr, *P = nullptr, *SV = nullptr, *SW = nullptr, *SP = nullptr;
+    int ld = 0, precondition = 0;
+    double nbr_fill = 0;
+    double *out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, *sums = nullptr, *nbr = nullptr;
+  };
+  int debug_cert_update(const CertUpdateDebug &q);
+  int debug_cert_nbr_rows() const { return P1_; }
+  int debug_cert_precon(double *T);   // the T_p cert_build_precon uploaded: N blocks (d+1) x (d+1) row-major by global pose
+  // the trace of the production search: on / off (off: cert_search is what it is without); the records of the last search
+  void debug_cert_trace(bool on) { cert_trace_on_ = on; cert_trace_.clear(); }
+  int cert_trace_len() const { return cert_nsums(d_) + 2 + d_ + 3 * d_ * d_ + 1; }
+  const std::vector<double> &debug_cert_trace_records() const { return cert_trace_; }
   // the segment table the partial sums are laid out by: nseg_all, and per node its own / neighbour segments [ptr[a], ptr[a+1])
   int debug_seg_layout(int *nseg_all, int *own_ptr, int *nbr_ptr) const;
   const NodeOperators &host_ops(int local) const { return ops_[local]; }
@@ -539,8 +563,9 @@ class Group {
   CertState *cert_ = nullptr;
   void cert_release();
   int cert_begin(const double *X, int ld);
+  int cert_ready();   // cert_begin without the check of X: the group's loss and nodes, the optimiser's pending work, the buffers
   int cert_prepare(const double *X, int ld, double *stationarity);
-  void cert_upload(const double *M, int ld, int ncols, double *dev_all);
+  void cert_upload(const double *M, int ld, int ncols, double *dev_all, bool with_nbr = true);
   void cert_download(const double *dev_own, double *M, int ld, int ncols);
   void cert_apply_M(double *in_all, double *out_own);
   void cert_apply_S(double *in_all, double *out_own);
@@ -549,6 +574,11 @@ class Group {
   int cert_factor_setup(long long max_factor_bytes, CertFactor &out);   // 0: ready to factor, 1: SKIPPED, -1: error
   int cert_factor_numeric(double eta, CertFactor &out);                 // S + eta I from the Lambda in place, factored
   int cert_search(const CertOptions &o, const double *V0, int ldv0, CertResult &res, double *x, int ldx);   // LOBPCG, likewise
+  // debug_cert_trace: one record of cert_trace_len() doubles per pass of cert_search's inner loop that reached its update
+  // (debug_cert.cpp); off, cert_search does not touch it
+  bool cert_trace_on_ = false;
+  std::vector<double> cert_trace_;
+  void cert_trace_pass(const double *sums, int nblk, int used, const CertCoef &K);
   int verify_lambda(const CertOptions &o, long long max_factor_bytes, double stationarity, CertResult &res, double *x, int ldx,
                     CertFactor &fac);
   struct StairState;  // the staircase's lifted vectors (stair.cpp), allocated by the first call that is not refused

@@ -874,6 +874,35 @@ int dpgo_group_debug_cost(dpgo_group_t *grp, int local, int whole, int eform, co
 int dpgo_group_debug_edge_offsets(const dpgo_group_t *grp, int *edge_offsets);   /* num_local + 1 ints */
 int dpgo_group_debug_rescale(dpgo_group_t *grp, const double *w, const double *scale, const int *count, int max_rescale_count,
                              const int *nodes, int n, int *flags, double *host_flags, double *scale_out, int *count_out);
+/* Device: the kernels of the certificate's LOBPCG search (k_cert_gram, k_cert_update, k_cert_reduce) and the host's block-Jacobi
+ * preconditioner on GIVEN inputs, each through the launch dpgo_group_certify's loop makes (tests/test_gpu_cert_search.py).
+ * Matrices are (d+1)N x d in the layout of X, column-major with leading dimension ld.  Same restrictions as dpgo_group_certify.
+ * cert_gram: Lambda from X; the buffer of S W takes MW (= M W), or, MW null, the product M W the loop forms.  One gram launch,
+ *   one reduction.  sums: 2 ntri + 2 d doubles, ntri = 3d (3d + 1) / 2 -- the row-major upper triangles of B^T B, then of
+ *   B^T (S B) (entry (a, c), a <= c: B_a^T (S B)_c; B = [V W P], S B = [SV SW SP]), then 2 d the launch does not write; SW:
+ *   the finished S W = M W - [0 ; Lambda W_Y].
+ * cert_update: C (3d x d row-major: the rows of V, W, P) and theta[d]; precondition 1: W' = T_p R', 0: W' = R'.  One update
+ *   launch, one reduction.  The outputs are the six buffers afterwards (SW is read only); sums as above, the last 2 d are
+ *   |R'_j|^2 and |V'_j|^2; the neighbour records of V, W, P (dpgo_group_debug_cert_nbr_rows() of (d+1) d doubles each, which
+ *   the launch must leave alone) are set to nbr_fill before it and come back raw in nbr (three runs: V's, W's, P's).
+ * cert_precon: the blocks T_p the search applies, N x (d+1) x (d+1) by global pose (slot 0 the translation).
+ * cert_trace: with on = 1 every later search of the group (certify, verify, the staircase's) records one entry per pass of
+ *   its loop that reached the update -- the sums it read, nblk, used, theta[d], the C it passed on (3d x d), and 1.0 where a
+ *   refresh of S V, S P followed: record_len = 2 ntri + 2 d + 2 + d + 3 d d + 1 doubles --; cert_trace_get hands out the
+ *   records of the last search (records null: the sizes alone).  Off (the default) the search does nothing for it. */
+typedef struct dpgo_cert_update_debug {
+  const double *C, *theta, *V, *W, *P, *SV, *SW, *SP;
+  int ld, precondition;
+  double nbr_fill;
+  double *V_out, *W_out, *P_out, *SV_out, *SW_out, *SP_out, *sums, *nbr;
+} dpgo_cert_update_debug_t;
+int dpgo_group_debug_cert_gram(dpgo_group_t *grp, const double *X, const double *V, const double *W, const double *P,
+                               const double *SV, const double *SP, const double *MW, int ld, double *sums, double *SW);
+int dpgo_group_debug_cert_update(dpgo_group_t *grp, const dpgo_cert_update_debug_t *q);
+int dpgo_group_debug_cert_nbr_rows(const dpgo_group_t *grp);
+int dpgo_group_debug_cert_precon(dpgo_group_t *grp, double *T);
+int dpgo_group_debug_cert_trace(dpgo_group_t *grp, int on);
+int dpgo_group_debug_cert_trace_get(const dpgo_group_t *grp, double *records, long long cap, int *record_len, long long *count);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,45 @@ def status_of(theta, residual, S_norm_est, eta, tau):
     return UNDECIDED
 
 
+def tri_index(n, a, c):
+    """Position of entry (a, c), a <= c, in the device's row-major upper triangle of an n x n matrix (cert_tri, cert.h)."""
+    return a * n - a * (a - 1) // 2 + (c - a)
+
+
+def upper_triangles(G, A):
+    """Both Gram matrices as the device ships them: the upper triangles of B^T B and of B^T (S B), row-major, in that order."""
+    iu = np.triu_indices(G.shape[0])
+    return np.concatenate([G[iu], A[iu]])
+
+
+def gram_step(M, Lam, V, W, P, SV, SP, d, MW=None, dtype=np.float64):
+    """The products one pass of the loop reads, in `dtype`: S W = M W - [0 ; Lambda W_Y] (M W given as MW, or formed here),
+    G = B^T B and A = B^T (S B) with B = [V W P], S B = [SV SW SP].  A is NOT symmetrised: entry (a, c) is B_a^T (S B)_c,
+    which is what the device sums for a <= c.  Returns (G, A, SW)."""
+    V, W, P, SV, SP = (np.asarray(Z, dtype=dtype) for Z in (V, W, P, SV, SP))
+    N = V.shape[0] // (d + 1)
+    nc = W.shape[1]
+    if MW is None:
+        MW = (M if dtype == np.float64 else sp.csr_matrix(M).astype(dtype)) @ W
+    SW = np.array(MW, dtype=dtype)
+    SW[N:] = SW[N:] - (np.asarray(Lam, dtype=dtype) @ W[N:].reshape(N, d, nc)).reshape(N * d, nc)
+    Bb, SB = np.hstack([V, W, P]), np.hstack([SV, SW, SP])
+    return Bb.T @ Bb, Bb.T @ SB, SW
+
+
+def update_step(C, theta, V, W, P, SV, SW, SP, T, d, dtype=np.float64):
+    """The recurrences of one pass, in `dtype`: C is 3d x d (rows of V, W, P), T the block-Jacobi blocks or None.
+    P' = W C_w + P C_p, V' = V C_v + P', the same for S V', S P'; R' = S V' - V' diag(theta); W' = T R' (R' without T).
+    Returns a dict with V, W, P, SV, SP, R and the stopping test's sums rr[j] = |R'_j|^2, vv[j] = |V'_j|^2."""
+    C, theta, V, W, P, SV, SW, SP = (np.asarray(Z, dtype=dtype) for Z in (C, theta, V, W, P, SV, SW, SP))
+    Pn = W @ C[d:2 * d] + P @ C[2 * d:]
+    SPn = SW @ C[d:2 * d] + SP @ C[2 * d:]
+    Vn, SVn = V @ C[:d] + Pn, SV @ C[:d] + SPn
+    R = SVn - Vn * theta[None, :]
+    Wn = apply_block_jacobi(np.asarray(T, dtype=dtype), R, d) if T is not None else R
+    return dict(V=Vn, W=Wn, P=Pn, SV=SVn, SP=SPn, R=R, rr=np.sum(R * R, axis=0), vv=np.sum(Vn * Vn, axis=0))
+
+
 def lobpcg(M, X, d, V0, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True, stop_on_negative=True, refresh_every=50,
            seed=0):
     """The search as the device runs it: same recurrences, the stopping test one product late, theta / residual of the
@@ -136,10 +175,7 @@ def lobpcg(M, X, d, V0, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True, s
     it, theta0, have_norms, have_W, drop_P = 0, 0.0, False, False, True
     while True:
         while it < max_iters:
-            if have_W:
-                SW = S(W)
-            Bb, SB = np.hstack([V, W, P]), np.hstack([SV, SW, SP])
-            G, A = Bb.T @ Bb, Bb.T @ SB
+            G, A, SW = gram_step(M, Lam, V, W, P, SV, SP, d, MW=None if have_W else SW)   # (no W yet: W = M W = 0)
             if have_norms and r0 <= tau * (Sn + abs(theta0)) * x0:
                 break
             nblk = 1 if not have_W else (2 if drop_P else 3)
@@ -148,13 +184,9 @@ def lobpcg(M, X, d, V0, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True, s
             res["restarts"] += used < nblk
             Cf = np.zeros((3 * d, d))
             Cf[:n] = C
-            Pn = W @ Cf[d:2 * d] + P @ Cf[2 * d:]
-            SPn = SW @ Cf[d:2 * d] + SP @ Cf[2 * d:]
-            V, SV = V @ Cf[:d] + Pn, SV @ Cf[:d] + SPn
-            P, SP = Pn, SPn
-            R = SV - V * th[None, :]
-            W = apply_block_jacobi(T, R, d) if precondition else R
-            r0, x0 = np.linalg.norm(R[:, 0]), np.linalg.norm(V[:, 0])
+            new = update_step(Cf, th, V, W, P, SV, SW, SP, T, d)
+            V, W, P, SV, SP = (new[k] for k in ("V", "W", "P", "SV", "SP"))
+            r0, x0 = np.linalg.norm(new["R"][:, 0]), np.linalg.norm(V[:, 0])
             it += 1
             theta0, have_norms = th[0], True
             drop_P, have_W = not have_W, True
