@@ -213,6 +213,15 @@ SYMBOLS = {
     "dpgo_debug_spd_selinv_free": (None, [C.c_void_p]),
     "dpgo_debug_spd_vsolve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _IP, _DP]),
     "dpgo_debug_spd_vsolve_chunk": (C.c_int, [C.c_int]),
+    "dpgo_group_pair_covariance": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _IP, C.c_int, _DP, _DP, _DP, _DP,
+                                             C.c_void_p]),
+    "dpgo_graph_pair_covariance_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                        C.c_longlong, _IP, C.c_int, _DP, _DP, _DP, _DP, C.c_void_p, C.c_void_p]),
+    "dpgo_debug_pairs_vsolve_baseline": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, _DP]),
+    "dpgo_debug_pairs_plan": (C.c_int, [C.c_int, C.c_int, _IP, C.c_int, _IP, _IP, _IP]),
+    "dpgo_debug_pairs_gate": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_spd_msolve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _DP, C.c_int,
+                                        C.c_int, _DP, _IP, _DP]),
     "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
                                                C.POINTER(C.c_void_p)]),
     "dpgo_debug_spd_solver_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), _IP, _IP, _IP, _IP, _IP, _IP]),
@@ -686,6 +695,51 @@ def spd_vsolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor
 VSOLVE_FILL = np.array([0x7ff8_0000_beef_0002], np.uint64).view(np.float64)[0]
 
 
+def spd_msolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor_values=None, chunk=None, ldx=None):
+    """A^-1 rhs for a block of plain vectors, rhs n x k (test hook, dpgo_debug_spd_msolve): spd_factor, then spd_msolve_device
+    on the factor as the numeric phase leaves it where there is a HIP device and host is not asked for, else
+    spd_solve_host(F, X, k).  refactor_values: as for spd_vsolve_debug.  chunk: for the length of the call, the rows of a
+    front's input block the device stages at a time (spd_msolve_chunk; default 32).  ldx >= k: the row length of the array
+    the solve works in (default k).
+
+    Returns a dict: status (0; 1: not positive definite, and then nothing was solved), on_device, pivot_min, pivot_max, out (the
+    solution n x k, None when not solved), out_again (a second call's), raw (3 x n x ldx: the arrays the hook was handed,
+    filled with VSOLVE_FILL first -- what it did not write is still there, the columns k ... ldx on the device included), and
+    with refactor_values status2, pivot_min2, pivot_max2, out2."""
+    A = A_csr.tocsr()
+    A.sort_indices()
+    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    n = A.shape[0]
+    b = np.ascontiguousarray(rhs, np.float64)
+    if b.ndim != 2 or b.shape[0] != n or b.shape[1] < 1:
+        raise ValueError("rhs must be n x k with k >= 1")
+    k = b.shape[1]
+    ldx = k if ldx is None else int(ldx)
+    if ldx < k:
+        raise ValueError("ldx must be at least k")
+    val2 = None
+    if refactor_values is not None:
+        val2 = np.ascontiguousarray(refactor_values, np.float64)
+        if val2.shape != val.shape:
+            raise ValueError("refactor_values must have one value per stored entry of A")
+    raw = np.full((3, n, ldx), VSOLVE_FILL)
+    status = np.zeros(2, np.int32)
+    piv = np.zeros(4)
+    rc = lib().dpgo_debug_spd_msolve(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
+                                     int(collapse), int(block), int(bool(host)), 0 if chunk is None else int(chunk), _dp(b), k,
+                                     ldx, _dp(raw), _ip(status), _dp(piv))
+    if rc < 0:
+        raise RuntimeError("spd_msolve_debug failed")
+    ok = status[0] == 0
+    out = {"status": int(status[0]), "on_device": rc == 1, "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
+           "out": raw[0, :, :k].copy() if ok else None, "out_again": raw[1, :, :k].copy() if ok else None, "raw": raw}
+    if refactor_values is not None:
+        out.update(status2=int(status[1]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
+                   out2=raw[2, :, :k].copy() if status[1] == 0 else None)
+    return out
+
+
 class SpdSolverDebug:
     """The device multifrontal solve on a given CSR matrix (test hook, dpgo_debug_spd_solver_*): spd_factor and
     SpdSolverDev::upload(dof, d, node_of_unknown) as a group runs them for G_tt (dof 1) and G_RR + lambda I (dof d), then
@@ -1086,6 +1140,32 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_covariance failed (robust loss, a group that does not host every node, an anchor or "
                                "pair outside the graph, a pair that is not an edge, or bad sizes)")
         return marg, cross, r
+
+    def pair_covariance(self, X, pairs, anchor=0, candidates=None, max_bytes=0, threshold=None):
+        """Joint covariances of arbitrary pose pairs at X and the loop-closure gate (dpgo_group_pair_covariance): the columns
+        of the inverse of `covariance`'s anchored Hessian that belong to the poses of `pairs` ((npairs, 2) global poses, any
+        two: no edge needed, p == q and the anchor allowed), solved for on the device.  candidates: None, or one candidate
+        measurement per pair as a tuple (R (npairs, d, d), t (npairs, d), kappa (npairs), tau (npairs)).
+        Returns a dict: joint (npairs, 3, dof, dof): Sigma_pp, Sigma_pq (rows of p, columns of q, as covariance's cross),
+        Sigma_qq; rel (npairs, dof, dof): the covariance of T_p^-1 T_q in covariance's perturbation; result (PairsResult); and
+        with candidates d2 (npairs), not_pd (npairs, bool), residual (npairs, dof) -- d2 = r' (rel + Omega^-1)^-1 r with
+        Omega = blkdiag(tau I, 2 kappa I); with `threshold` (the chi-square quantile of your choice, dof degrees of freedom)
+        also accept = d2 <= threshold where the innovation covariance is positive definite.  outcome PAIRS_OK, PAIRS_NOT_PD
+        (zero outputs) or PAIRS_SKIPPED (more device bytes than max_bytes, when > 0, or than half of what is free).  No block
+        of a selected inversion is stored: this may run where covariance is SKIPPED."""
+        X, ld = _fcol(X)
+        d = self.d
+        dof = d + d * (d - 1) // 2
+        P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+        cand = None if candidates is None else pack_candidates(d, len(P), *candidates)
+        joint, rel = np.zeros((len(P), 3, dof, dof)), np.zeros((len(P), dof, dof))
+        gate = np.zeros((len(P), 2 + dof))
+        r = PairsResult()
+        if lib().dpgo_group_pair_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P),
+                                            None if cand is None else _dp(cand), _dp(joint), _dp(rel), _dp(gate), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_pair_covariance failed (robust loss, a group that does not host every node, an anchor "
+                               "or pose outside the graph, a candidate weight that is not positive, or bad sizes)")
+        return pairs_output(joint, rel, gate, r, cand is not None, threshold)
 
     def polish(self, X, anchor=0, max_bytes=0, **opts):
         """Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored
@@ -1758,6 +1838,67 @@ class CovResult(C.Structure):
                 ("factor_ms", C.c_double), ("selinv_ms", C.c_double), ("selinv_flops", C.c_double)]
 
 
+PAIRS_OK, PAIRS_NOT_PD, PAIRS_SKIPPED = 0, 1, 2
+PAIRS_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+
+
+class PairsResult(C.Structure):
+    """dpgo_pairs_result_t: the outcome of NodeGroup.pair_covariance, the sizes of its factorisation, the unit columns it
+    solved, in how many batches, and the host milliseconds of its three phases."""
+    _fields_ = [("outcome", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("columns", C.c_int), ("batches", C.c_int), ("reserved", C.c_int), ("device_bytes", C.c_longlong),
+                ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("stationarity", C.c_double), ("symbolic_s", C.c_double),
+                ("factor_ms", C.c_double), ("solve_ms", C.c_double), ("gate_ms", C.c_double), ("solve_flops", C.c_double),
+                ("factor_bytes", C.c_double)]
+
+
+def pack_candidates(d, npairs, R, t, kappa, tau):
+    """(npairs, d^2 + d + 2): R row-major, t, kappa, tau per candidate, as dpgo_group_pair_covariance reads them."""
+    out = np.zeros((npairs, d * d + d + 2))
+    out[:, :d * d] = np.asarray(R, np.float64).reshape(npairs, d * d)
+    out[:, d * d:d * d + d] = np.asarray(t, np.float64).reshape(npairs, d)
+    out[:, d * d + d] = np.asarray(kappa, np.float64).reshape(npairs)
+    out[:, d * d + d + 1] = np.asarray(tau, np.float64).reshape(npairs)
+    return out
+
+
+def pairs_output(joint, rel, gate, result, gated, threshold):
+    out = {"joint": joint, "rel": rel, "result": result}
+    if gated:
+        out.update(d2=gate[:, 0].copy(), not_pd=gate[:, 1] != 0, residual=gate[:, 2:].copy())
+        if threshold is not None:
+            out["accept"] = (~out["not_pd"]) & (out["d2"] <= float(threshold)) & (result.outcome == PAIRS_OK)
+    return out
+
+
+def pairs_plan_debug(dof, anchor, pairs):
+    """The column plan of a pair_covariance call (test hook, dpgo_debug_pairs_plan; no device): a dict with poses (the distinct
+    non-anchor poses, ascending), pair_col ((npairs, 2): the first column of p and q, -1 for the anchor), columns, batches,
+    kb."""
+    P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    poses, cols, sizes = np.zeros(max(2 * len(P), 1), np.int32), np.zeros((max(len(P), 1), 2), np.int32), np.zeros(4, np.int32)
+    if lib().dpgo_debug_pairs_plan(int(dof), int(anchor), _ip(P) if len(P) else None, len(P), _ip(poses), _ip(cols), _ip(sizes)) != 0:
+        raise RuntimeError("dpgo_debug_pairs_plan failed")
+    return {"poses": poses[:sizes[0]].copy(), "pair_col": cols[:len(P)].copy(), "columns": int(sizes[1]), "batches": int(sizes[2]),
+            "kb": int(sizes[3])}
+
+
+def pairs_gate_debug(d, recp, recq, joint, candidate=None):
+    """The arithmetic of one pair on the host (test hook, dpgo_debug_pairs_gate; no device), the code the device runs per
+    pair.  recp / recq: the pose records ((d + 1) x d: t, then R^T); joint (3, dof, dof); candidate: None or (R, t, kappa,
+    tau).  Returns (rel, None) or (rel, (d2, not_pd, residual))."""
+    dof = d + d * (d - 1) // 2
+    recp, recq = np.ascontiguousarray(recp, np.float64), np.ascontiguousarray(recq, np.float64)
+    joint = np.ascontiguousarray(joint, np.float64)
+    if recp.size != (d + 1) * d or recq.size != (d + 1) * d or joint.size != 3 * dof * dof:
+        raise ValueError("pairs_gate_debug: bad sizes")
+    cand = None if candidate is None else pack_candidates(d, 1, *candidate)
+    rel, gate = np.zeros((dof, dof)), np.zeros(2 + dof)
+    if lib().dpgo_debug_pairs_gate(int(d), _dp(recp), _dp(recq), _dp(joint), None if cand is None else _dp(cand), _dp(rel), _dp(gate)) != 0:
+        raise RuntimeError("dpgo_debug_pairs_gate failed (d, or a candidate weight that is not positive)")
+    return rel, (None if cand is None else (float(gate[0]), bool(gate[1]), gate[2:].copy()))
+
+
 POLISH_CONVERGED, POLISH_MAX_STEPS, POLISH_STALLED, POLISH_SKIPPED = 0, 1, 2, 3
 POLISH_NAMES = {0: "CONVERGED", 1: "MAX_STEPS", 2: "STALLED", 3: "SKIPPED"}
 
@@ -2061,3 +2202,25 @@ def covariance_reweighted(graph, X, loss, loss_reg=0.25, anchor=0, pairs=None, m
                                               _dp(cross) if len(P) else None, C.byref(r), C.byref(s)) != 0:
         raise RuntimeError("dpgo_graph_covariance_reweighted failed (no HIP device, a short X, a bad loss, or a pair that is no edge)")
     return marg, cross, r, s
+
+
+def pair_covariance_reweighted(graph, X, loss, pairs, loss_reg=0.25, anchor=0, candidates=None, max_bytes=0, threshold=None,
+                               device=0):
+    """NodeGroup.pair_covariance for the RE-WEIGHTED problem at X (dpgo_graph_pair_covariance_reweighted), by
+    covariance_reweighted's recipe and with its caveat.  Returns pair_covariance's dict with summary (EdgeSummary) added."""
+    X, ld = _fcol(X)
+    d = graph.d
+    dof = d + d * (d - 1) // 2
+    P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    cand = None if candidates is None else pack_candidates(d, len(P), *candidates)
+    joint, rel, gate = np.zeros((len(P), 3, dof, dof)), np.zeros((len(P), dof, dof)), np.zeros((len(P), 2 + dof))
+    r, s = PairsResult(), EdgeSummary()
+    if lib().dpgo_graph_pair_covariance_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), int(anchor),
+                                                   int(max_bytes), _ip(P) if len(P) else None, len(P),
+                                                   None if cand is None else _dp(cand), _dp(joint), _dp(rel), _dp(gate),
+                                                   C.byref(r), C.byref(s)) != 0:
+        raise RuntimeError("dpgo_graph_pair_covariance_reweighted failed (no HIP device, a short X, a bad loss, a pose outside the "
+                           "graph, or a candidate weight that is not positive)")
+    out = pairs_output(joint, rel, gate, r, cand is not None, threshold)
+    out["summary"] = s
+    return out

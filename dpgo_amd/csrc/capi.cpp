@@ -15,6 +15,7 @@
 #include "comm.h"
 #include "edges.h"
 #include "group.h"
+#include "pairs_math.h"
 #include "pcm.h"
 
 namespace dpgo {
@@ -777,6 +778,91 @@ int dpgo_debug_spd_vsolve(int n, const int *ptr, const int *col, const double *v
     auto solve_host = [&](int k) {
       std::copy(rhs, rhs + n, out + (size_t)k * n);
       dpgo::spd_solve_host(F, out + (size_t)k * n, 1);
+    };
+    const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
+    status[0] = spd_debug_status(rc, F);
+    pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
+    if (status[0] < 0) return -1;
+    if (rc == 0) { solve_host(0); solve_host(1); }
+    if (refactor_val) {
+      A.val.assign(refactor_val, refactor_val + ptr[n]);
+      const int rc2 = dpgo::spd_refactor(A, F);
+      status[1] = spd_debug_status(rc2, F);
+      pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
+      if (status[1] < 0) return -1;
+      if (rc2 == 0) solve_host(2);
+    }
+    return 0;
+  });
+}
+
+// ---- test hook: the device solve for a block of plain vectors (spd.h: spd_msolve_*) ----
+int dpgo_debug_spd_msolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, int chunk, const double *rhs, int k, int ldx, double *out,
+                          int *status, double *pivots) {
+  if (!ptr || !col || !val || !rhs || !out || !status || !pivots || n <= 0 || leaf < 1 || block < 1 || collapse < 0 ||
+      n % block != 0 || ptr[0] != 0 || k < 1 || ldx < k)
+    return -1;
+  for (int i = 0; i < n; i++)
+    if (ptr[i + 1] < ptr[i]) return -1;
+  for (int e = 0; e < ptr[n]; e++)
+    if (col[e] < 0 || col[e] >= n) return -1;
+  return guarded([&] {
+    dpgo::CsrMatrix A;
+    A.n = n;
+    A.ptr.assign(ptr, ptr + n + 1);
+    A.col.assign(col, col + ptr[n]);
+    A.val.assign(val, val + ptr[n]);
+    struct Holder {
+      dpgo::SpdFactor F;
+      double *d_x = nullptr;
+      int chunk_before = 0;
+      bool chunk_set = false;
+      ~Holder() {
+        if (chunk_set) dpgo::spd_msolve_chunk(chunk_before);
+        if (d_x) (void)hipFree(d_x);
+        dpgo::spd_release_device(F);
+        dpgo::spd_release_numeric(F);
+      }
+    } H;
+    dpgo::SpdFactor &F = H.F;
+    const bool on_device = !host && spd_debug_device_numeric();
+    F.quiet = true;
+    status[0] = status[1] = -1;
+    std::fill(pivots, pivots + 4, 0.0);
+    const size_t cnt = (size_t)n * ldx, nb = sizeof(double) * cnt;
+    if (on_device) {
+      F.keep_numeric = true;
+      if (chunk > 0) { H.chunk_before = dpgo::spd_msolve_chunk(chunk); H.chunk_set = true; }
+      if (hipMalloc((void **)&H.d_x, nb) != hipSuccess) return -1;
+      // part j of out <- the n x ldx array the solve was handed (the caller's fill with rhs in its first k columns), solved
+      auto solve = [&](int j) -> int {
+        std::vector<double> X(out + j * cnt, out + (j + 1) * cnt);
+        for (int i = 0; i < n; i++) std::copy(rhs + (size_t)i * k, rhs + (size_t)(i + 1) * k, X.begin() + (size_t)i * ldx);
+        if (hipMemcpy(H.d_x, X.data(), nb, hipMemcpyHostToDevice) != hipSuccess) return -1;
+        if (dpgo::spd_msolve_device(F, H.d_x, k, ldx) != 0 || hipDeviceSynchronize() != hipSuccess) return -1;
+        return hipMemcpy(out + j * cnt, H.d_x, nb, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+      };
+      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
+      status[0] = spd_debug_status(rc, F);
+      pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
+      if (status[0] < 0 || !F.numeric) return -1;
+      if (rc == 0 && (solve(0) != 0 || solve(1) != 0)) return -1;
+      if (rc != 0 && dpgo::spd_msolve_device(F, H.d_x, k, ldx) != -1) return -1;   // (a failed factorisation solves nothing)
+      if (refactor_val) {
+        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
+        const int rc2 = dpgo::spd_refactor_device(F);
+        status[1] = spd_debug_status(rc2, F);
+        pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
+        if (status[1] < 0) return -1;
+        if (rc2 == 0 && solve(2) != 0) return -1;
+      }
+      return 1;
+    }
+    auto solve_host = [&](int j) {
+      std::vector<double> X(rhs, rhs + (size_t)n * k);
+      dpgo::spd_solve_host(F, X.data(), k);
+      for (int i = 0; i < n; i++) std::copy(X.begin() + (size_t)i * k, X.begin() + (size_t)(i + 1) * k, out + j * cnt + (size_t)i * ldx);
     };
     const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
     status[0] = spd_debug_status(rc, F);
@@ -1700,6 +1786,78 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
   dpgo_group_free(grp);
   dpgo_graph_free(gw);
   return rc == 0 ? 0 : -1;
+}
+
+// ---- joint covariances of arbitrary pose pairs and the gate (pairs.h) ----
+int dpgo_group_pair_covariance(dpgo_group_t *h, const double *X, int ld, int anchor, long long max_bytes, const int *pairs,
+                               int npairs, const double *candidates, double *joint, double *rel, double *gate,
+                               dpgo_pairs_result_t *result) {
+  if (!h || !h->grp || !X || !result || npairs < 0 || (npairs > 0 && (!pairs || !joint || !rel)) || (candidates && !gate)) return -1;
+  return guarded([&] {
+    dpgo::PairsResult r;
+    const int rc = h->grp->pair_covariance(X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, r);
+    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
+    result->max_front = r.max_front; result->columns = r.columns; result->batches = r.batches; result->reserved = 0;
+    result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
+    result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s; result->factor_ms = r.factor_ms;
+    result->solve_ms = r.solve_ms; result->gate_ms = r.gate_ms; result->solve_flops = r.solve_flops;
+    result->factor_bytes = r.factor_bytes;
+    return rc;
+  });
+}
+
+int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                          int anchor, long long max_bytes, const int *pairs, int npairs, const double *candidates,
+                                          double *joint, double *rel, double *gate, dpgo_pairs_result_t *result,
+                                          dpgo_edge_summary_t *edge_summary) {
+  if (!g || !X || !result || npairs < 0 || (npairs > 0 && (!pairs || !joint || !rel)) || (candidates && !gate)) return -1;
+  const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
+  std::vector<double> w((size_t)std::max(m, 1));
+  dpgo_edge_eval_t *ev = nullptr;
+  dpgo_graph_t *gw = nullptr;
+  dpgo_group_t *grp = nullptr;
+  int rc = dpgo_edge_eval_create(g, device, &ev);
+  if (rc == 0) rc = dpgo_edge_eval_run(ev, X, ld, loss, loss_reg, nullptr, nullptr, nullptr, w.data(), edge_summary);
+  dpgo_edge_eval_free(ev);
+  if (rc == 0) rc = dpgo_graph_scale_edges(g, w.data(), &gw);
+  if (rc == 0) {
+    dpgo_options_t opt;
+    dpgo_options_driver(&opt, 0, 1);
+    opt.max_iterations = 0;
+    std::vector<int> ids(nn);
+    std::iota(ids.begin(), ids.end(), 0);
+    rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
+  }
+  if (rc == 0) rc = dpgo_group_pair_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, result);
+  dpgo_group_free(grp);
+  dpgo_graph_free(gw);
+  return rc == 0 ? 0 : -1;
+}
+
+int dpgo_debug_pairs_vsolve_baseline(dpgo_group_t *h, const double *X, int ld, int anchor, int ncols, double *ms) {
+  if (!h || !h->grp || !X || !ms || ncols < 1) return -1;
+  return guarded([&] { return h->grp->pairs_vsolve_baseline(X, ld, anchor, ncols, ms); });
+}
+
+int dpgo_debug_pairs_plan(int dof, int anchor, const int *pairs, int npairs, int *poses, int *pair_col, int *sizes) {
+  if (dof < 1 || npairs < 0 || (npairs > 0 && (!pairs || !poses || !pair_col)) || !sizes) return -1;
+  return guarded([&] {
+    const dpgo::PairsPlan pl = dpgo::pairs_plan(dof, anchor, pairs, npairs);
+    std::copy(pl.poses.begin(), pl.poses.end(), poses);
+    std::copy(pl.pair_col.begin(), pl.pair_col.end(), pair_col);
+    sizes[0] = (int)pl.poses.size(); sizes[1] = pl.columns; sizes[2] = pl.batches; sizes[3] = pl.kb;
+    return 0;
+  });
+}
+
+int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const double *joint, const double *cand, double *rel,
+                          double *gate) {
+  if ((d != 2 && d != 3) || !recp || !recq || !joint || !rel || (cand && !gate)) return -1;
+  if (cand && (!(cand[d * d + d] > 0) || !(cand[d * d + d + 1] > 0))) return -1;
+  const int DD = d == 3 ? 36 : 9;
+  if (d == 3) dpgo::pairs_one<3>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
+  else dpgo::pairs_one<2>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
+  return 0;
 }
 
 // ---- Newton polish (polish.h) ----

@@ -38,6 +38,14 @@
 //              one more line on stdout
 //                  staircase: <outcome> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
 //              the result files then hold its Xhat; the same reasons as --polish when it is not computed
+//              --gate_candidates FILE --gate_report FILE (likewise; both or neither)  beside --covariance, for the trivial loss
+//              and a world of one rank: FILE is a .g2o of candidate edges p -> q, read by the loader's edge parser; every
+//              candidate is tested against the final X with dpgo_group_pair_covariance (pose 0 the anchor), one line per
+//              candidate in the report,
+//                  p q d2 dof not_pd  S[0][0] S[0][1] ... S[dof-1][dof-1]   (the upper triangle of Sigma_rel, 17 digits)
+//              and one more line on stdout
+//                  gate: <outcome> <candidates> <columns> <batches> <device_bytes> <pivot_min> <stationarity>
+//              (NOT_PD or SKIPPED: the report is not written); the same reasons as --covariance when it is not computed
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -75,7 +83,7 @@ int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false;
-  std::string edge_report, covariance;
+  std::string edge_report, covariance, gate_candidates, gate_report;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -102,6 +110,8 @@ int main(int argc, char **argv) {
     else if (a.compare(0, 20, "--verify_reweighted=") == 0) verify_reweighted = parse_bool(argv[i] + 20);
     else if (const char *v = val("--edge_report")) edge_report = v;
     else if (const char *v = val("--covariance")) covariance = v;
+    else if (const char *v = val("--gate_candidates")) gate_candidates = v;
+    else if (const char *v = val("--gate_report")) gate_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
@@ -362,6 +372,61 @@ int main(int argc, char **argv) {
           fprintf(f, "%d", p);
           for (int a = 0; a < dof; a++)
             for (int b = a; b < dof; b++) fprintf(f, " %.17g", marg[((size_t)p * dof + a) * dof + b]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+    }
+  }
+  if (!gate_candidates.empty() || !gate_report.empty()) {
+    if (gate_candidates.empty() || gate_report.empty()) {
+      fprintf(stderr, "--gate_candidates and --gate_report go together.\n");
+      return -1;
+    }
+    if (loss != 0) {
+      if (root) printf("gate: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("gate: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      dpgo_graph_t *cg = nullptr;
+      int cd = 0, cN = 0, cn = 0, m = 0;
+      if (dpgo_read_g2o(gate_candidates.c_str(), 1, &cg) != 0 || dpgo_graph_info(cg, &cd, &cN, &cn, &m) != 0 || cd != d || cN > N) {
+        fprintf(stderr, "Cannot use the candidates in %s (unreadable, another dimension, or a pose that is not in the graph).\n",
+                gate_candidates.c_str());
+        dpgo_graph_free(cg);
+        return -1;
+      }
+      const int dof = d + d * (d - 1) / 2, nc = d * d + d + 2;
+      std::vector<int> I(m), J(m), pairs((size_t)2 * m);
+      std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m), cand((size_t)m * nc);
+      const int got = dpgo_graph_edges(cg, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data());
+      dpgo_graph_free(cg);
+      if (got != 0) {
+        fprintf(stderr, "Cannot read the edges of %s.\n", gate_candidates.c_str());
+        return -1;
+      }
+      for (int k = 0; k < m; k++) {
+        pairs[2 * k] = I[k]; pairs[2 * k + 1] = J[k];
+        std::copy(&R[(size_t)k * d * d], &R[(size_t)(k + 1) * d * d], &cand[(size_t)k * nc]);
+        std::copy(&t[(size_t)k * d], &t[(size_t)(k + 1) * d], &cand[(size_t)k * nc + d * d]);
+        cand[(size_t)k * nc + d * d + d] = kappa[k];
+        cand[(size_t)k * nc + d * d + d + 1] = tau[k];
+      }
+      std::vector<double> Xc((size_t)ld * d, 0.0), joint((size_t)m * 3 * dof * dof), rel((size_t)m * dof * dof), gate((size_t)m * (2 + dof));
+      dpgo_pairs_result_t pr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_pair_covariance(grp, Xc.data(), ld, 0, 0, pairs.data(), m, cand.data(), joint.data(), rel.data(), gate.data(), &pr) != 0)
+        return -1;
+      printf("gate: %s %d %d %d %lld %.16g %.16g\n",
+             pr.outcome == DPGO_PAIRS_OK ? "OK" : pr.outcome == DPGO_PAIRS_NOT_PD ? "NOT_PD" : "SKIPPED", m, pr.columns, pr.batches,
+             pr.device_bytes, pr.pivot_min, pr.stationarity);
+      if (pr.outcome == DPGO_PAIRS_OK) {
+        FILE *f = fopen(gate_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", gate_report.c_str()); return -1; }
+        for (int k = 0; k < m; k++) {
+          fprintf(f, "%d %d %.17g %d %d", I[k], J[k], gate[(size_t)k * (2 + dof)], dof, gate[(size_t)k * (2 + dof) + 1] != 0.0 ? 1 : 0);
+          for (int a = 0; a < dof; a++)
+            for (int b = a; b < dof; b++) fprintf(f, " %.17g", rel[((size_t)k * dof + a) * dof + b]);
           fprintf(f, "\n");
         }
         fclose(f);

@@ -30,6 +30,7 @@
 #include "cov.h"
 #include "graph.h"
 #include "kernels.h"
+#include "pairs.h"
 #include "polish.h"
 #include "schedule.h"
 #include "settings.h"
@@ -197,6 +198,14 @@ class Group {
   // SKIPPED; log (optional, log_cap rows of POLISH_LOG_COLS doubles): one row per iteration
   int polish(const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout, int ldout, double *log,
              int log_cap, PolishResult &out);
+  // ---- joint covariances of arbitrary pose pairs and the loop-closure gate (pairs.h, pairs.cpp): the covariance's factor,
+  // the columns of H^-1 of the poses asked for by spd_msolve_device.  pairs: npairs x 2 global poses, any two; candidates
+  // (optional): npairs x (d^2 + d + 2) doubles, R~ row-major, t~, kappa, tau; joint: npairs x 3 x dof^2 (S_pp, S_pq, S_qq);
+  // rel: npairs x dof^2; gate (with candidates): npairs x (2 + dof) doubles, d^2, not_pd, the residual
+  int pair_covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs, const double *candidates,
+                      double *joint, double *rel, double *gate, PairsResult &out);
+  // measurement: ncols unit columns solved one at a time with spd_vsolve_device on the same factor; ms: of the solves
+  int pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms);
   // ---- the Riemannian staircase (stair.h, stair.cpp): TNT at rank r, verify on Lambda(Y), the escape along the certificate's
   // direction, the rounding, the polish.  X: global (d+1)N x d; Xhat (ldx >= (d+1) N): the result, written unless SKIPPED; Y
   // (optional, (d+1)N x 2d): the final lifted point; log (optional, log_cap rows of STAIR_LOG_COLS doubles): one row per level
@@ -601,6 +610,7 @@ class Group {
   int cov_analyse(CovResult &out);                      // the pattern and the symbolic analysis (first call), the sizes
   int cov_setup(long long max_bytes, CovResult &out);   // 0: ready, 1: SKIPPED, -1: error
   int polish_setup(long long max_bytes, PolishResult &out);   // likewise, for what polish allocates (polish.cpp)
+  int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out);   // likewise (pairs.cpp)
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

@@ -174,6 +174,31 @@ int spd_vsolve_chunk(int chunk);
 int spd_vsolve_device(SpdFactor &F, double *x, void *stream = nullptr);
 void spd_vsolve_release(SpdFactor &F);
 
+// The device solve for a BLOCK of plain vectors: X (n x k row-major on the device, row length ldx >= k) <- A^-1 X, on dev_W /
+// dev_WT as above.  The recursion is spd_vsolve_device's, column block by column block, and with k columns both sweeps are
+// products of dense blocks -- (w + u) x w by w x k forward, w x (w + u) by (w + u) x k backward -- on
+// v_mfma_f64_16x16x4_f64.  The columns are taken in batches of at most 64, in tiles of 16; a tail batch is padded with zero
+// columns that are never stored into X, and the entries X(i, k ... ldx) are not touched.  A workgroup takes 64 rows of one
+// front (16 per wave) and stages the front's assembled input block through LDS 32 rows at a time, the next slab's loads in
+// flight behind the products.  Y and the update block have buffers of their own (n kb and total_upd kb doubles,
+// kb = 16 ceil(min(k, 64) / 16)); the descriptors and the pull lists are spd_vsolve_device's, built by whichever call comes
+// first.  No atomics, and no workgroup reads what another of its launch writes: the same bits on every call.  Every output
+// entry is ONE sum over the front's depth in ascending order, four terms per instruction, whatever the column: a column's bits
+// depend neither on k, nor on its position in a tile or a batch, nor on the other columns.
+//   spd_msolve_bytes    device bytes the first spd_msolve_device with batches of kb columns allocates: Y, the update block,
+//                       its row items, and spd_vsolve_bytes for the shared lists (counted whether they exist or not)
+//   spd_msolve_device   preconditions and return value as spd_vsolve_device (-1, and nothing computed, otherwise; also for
+//                       k < 1 or ldx < k); returns once it is enqueued
+//   spd_msolve_release  frees what it allocated (not the shared lists: spd_vsolve_release); spd_release_numeric does so too
+//   spd_msolve_chunk    how many rows of the assembled input block the launches stage at a time: 1 ... 32, anything else: 32,
+//                       the default and the height of the LDS array; returns the value before.  Process-wide; for the tests.
+//                       A slab is padded with zero rows to a multiple of four, so a multiple of 4 gives the bits of the
+//                       default (every instruction sums the same four terms).
+int64_t spd_msolve_bytes(const SpdFactor &F, int kb);
+int spd_msolve_chunk(int chunk);
+int spd_msolve_device(SpdFactor &F, double *X, int k, int ldx, void *stream = nullptr);
+void spd_msolve_release(SpdFactor &F);
+
 // Host solve (setup paths and tests): X (n x ncols, row-major) <- A^-1 X.
 void spd_solve_host(const SpdFactor &F, double *X, int ncols);
 

@@ -907,6 +907,126 @@ __global__ __launch_bounds__(256) void k_vs_backward(const VsolveDesc *__restric
     if (lane == 0 && r < f.w) x[piv_idx[f.piv_ptr + r]] = v;
   }
 }
+
+// ---- the solve for a block of plain vectors (spd.h: spd_msolve_*): the same recursion with v_mfma_f64_16x16x4_f64 ----
+constexpr int MS_ROWS = 64;            // rows of one front per workgroup: one 16-row MFMA tile per wave
+constexpr int MS_SLAB = 32;            // rows of a front's assembled input block staged in LDS at a time; a launch may ask for fewer
+constexpr int MS_COLS = 64;            // right-hand sides per batch: up to four column tiles of 16
+constexpr int MS_LDA = MS_SLAB + 1;    // row lengths in LDS: the factor's tile as in k_si_abt, ...
+constexpr int MS_LDB = MS_COLS + 16;   // ... the input slab so that the four depths one instruction reads lie 32 banks apart
+int ms_chunk = MS_SLAB;                // spd_msolve_chunk: what the launches ask for
+
+// acc[ct] += A[r0 + 16 wave ... + 16, 0 ... kend) B[0 ... kend, 16 ct ... + 16): A row-major in global memory (`rows` rows of
+// length lda), B handed out entry by entry by loadb(k, column).  Both go through LDS `chunk` depths at a time, the next
+// slab's loads in flight behind the products; a slab is padded with zeros to a multiple of four depths.  Every entry of
+// acc is one chain of instructions over k in ascending order, four depths each, and an instruction's entry (i, j) is a
+// function of row i of A and column j of B alone: a column's bits depend on nothing but that column.
+template <int NT, class LoadB>
+__device__ __forceinline__ void ms_product(const double *__restrict__ A, int lda, int r0, int rows, int kend, int chunk,
+                                           double (*As)[MS_LDA], double (*Bs)[MS_LDB], LoadB loadb, v4d (&acc)[NT]) {
+  constexpr int KB = 16 * NT, PA = MS_ROWS * MS_SLAB / 256, PB = MS_SLAB * KB / 256;
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+#pragma unroll
+  for (int ct = 0; ct < NT; ct++) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
+  double pa[PA], pb[PB];
+  auto fetch = [&](int k0) {
+    const int kn = min(chunk, kend - k0);
+#pragma unroll
+    for (int j = 0; j < PA; j++) {
+      const int idx = t + 256 * j, r = r0 + idx / MS_SLAB, k = idx % MS_SLAB;
+      pa[j] = r < rows && k < kn ? A[(long long)r * lda + k0 + k] : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < PB; j++) {
+      const int idx = t + 256 * j, k = idx / KB;
+      pb[j] = k < kn ? loadb(k0 + k, idx % KB) : 0.0;
+    }
+  };
+  fetch(0);
+  for (int k0 = 0; k0 < kend; k0 += chunk) {
+    const int kn4 = (min(chunk, kend - k0) + 3) & ~3;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < PA; j++) {
+      const int idx = t + 256 * j;
+      As[idx / MS_SLAB][idx % MS_SLAB] = pa[j];
+    }
+#pragma unroll
+    for (int j = 0; j < PB; j++) {
+      const int idx = t + 256 * j;
+      Bs[idx / KB][idx % KB] = pb[j];
+    }
+    __syncthreads();
+    if (k0 + chunk < kend) fetch(k0 + chunk);
+#pragma unroll
+    for (int kk = 0; kk < MS_SLAB; kk += 4) {
+      if (kk >= kn4) break;
+      const int kq = kk + (lane >> 4), rr = lane & 15;
+      const double av = As[wv * 16 + rr][kq];
+#pragma unroll
+      for (int ct = 0; ct < NT; ct++) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bs[kq][ct * 16 + rr], acc[ct], 0, 0, 0);
+    }
+  }
+}
+
+// Forward: [Y_s ; Upd_s] = W_s F_s (+ F_s on the update rows) for the fronts of one tree height and the columns
+// c0 ... c0 + nc of X (nc <= 16 NT; the columns beyond are zeros).  items = (front, first row) pairs, one per workgroup.
+// F_s is assembled entry by entry through vs_assembled's lists.  Y (n x kb) and UB (total_upd x kb) are written, X and the
+// children's rows of UB (an earlier launch) are read.
+template <int NT>
+__global__ __launch_bounds__(256) void k_ms_forward(const VsolveDesc *__restrict__ vd, const int *__restrict__ items,
+                                                    const double *__restrict__ W, const int *__restrict__ piv_idx,
+                                                    const int *__restrict__ asm_ptr, const int *__restrict__ asm_src,
+                                                    const double *__restrict__ X, int ldx, int c0, int nc, double *__restrict__ Y,
+                                                    double *UB, int kb, int chunk) {
+  const VsolveDesc f = vd[items[2 * blockIdx.x]];
+  const int r0 = items[2 * blockIdx.x + 1], m = f.w + f.u;
+  __shared__ double As[MS_ROWS][MS_LDA], Bs[MS_SLAB][MS_LDB];
+  auto assembled = [&](int p, int c) {
+    double v = p < f.w && c < nc ? X[(long long)piv_idx[f.piv_ptr + p] * ldx + c0 + c] : 0.0;
+    for (int a = asm_ptr[f.pos_off + p]; a < asm_ptr[f.pos_off + p + 1]; a++) v += UB[(long long)asm_src[a] * kb + c];
+    return v;
+  };
+  v4d acc[NT];
+  ms_product<NT>(W + f.w_off, f.ldw, r0, m, f.w, chunk, As, Bs, assembled, acc);
+  // C/D lay-out of v_mfma_f64_16x16x4_f64: register r of lane l = C[(l >> 4) + 4 r][l & 15]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int ct = 0; ct < NT; ct++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int p = r0 + wv * 16 + (lane >> 4) + 4 * r, c = ct * 16 + (lane & 15);
+      if (p >= m) continue;
+      if (p < f.w) Y[(long long)piv_idx[f.piv_ptr + p] * kb + c] = acc[ct][r];
+      else UB[(long long)(f.ubuf_off + p - f.w) * kb + c] = acc[ct][r] + assembled(p, c);
+    }
+}
+
+// Backward: X_s = WT_s [Y_s ; X(upd_idx)], the fronts of one tree depth, over the rows of WT_s.  Reads Y and the rows of X
+// that fronts of smaller depth have finished, writes the pivots' rows of X in the columns c0 ... c0 + nc and nothing else.
+template <int NT>
+__global__ __launch_bounds__(256) void k_ms_backward(const VsolveDesc *__restrict__ vd, const int *__restrict__ items,
+                                                     const double *__restrict__ WT, const int *__restrict__ piv_idx,
+                                                     const int *__restrict__ upd_idx, const double *__restrict__ Y, double *X, int ldx,
+                                                     int c0, int nc, int kb, int chunk) {
+  const VsolveDesc f = vd[items[2 * blockIdx.x]];
+  const int r0 = items[2 * blockIdx.x + 1], m = f.w + f.u;
+  __shared__ double As[MS_ROWS][MS_LDA], Bs[MS_SLAB][MS_LDB];
+  auto input = [&](int p, int c) {
+    if (p < f.w) return Y[(long long)piv_idx[f.piv_ptr + p] * kb + c];
+    return c < nc ? X[(long long)upd_idx[f.upd_ptr + p - f.w] * ldx + c0 + c] : 0.0;
+  };
+  v4d acc[NT];
+  ms_product<NT>(WT + f.wt_off, f.ldm, r0, f.w, m, chunk, As, Bs, input, acc);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int ct = 0; ct < NT; ct++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int p = r0 + wv * 16 + (lane >> 4) + 4 * r, c = ct * 16 + (lane & 15);
+      if (p < f.w && c < nc) X[(long long)piv_idx[f.piv_ptr + p] * ldx + c0 + c] = acc[ct][r];
+    }
+}
 }  // namespace
 
 // what the first spd_vsolve_device builds and every later one runs
@@ -917,6 +1037,19 @@ struct SpdVsolveCtx {
   double *d_y = nullptr, *d_ub = nullptr;
   ~SpdVsolveCtx() {
     for (void *q : {(void *)d_vd, (void *)d_items, (void *)d_piv, (void *)d_upd, (void *)d_asm_ptr, (void *)d_asm_src, (void *)d_y, (void *)d_ub})
+      if (q) (void)hipFree(q);
+  }
+};
+
+// what the first spd_msolve_device adds to it (the descriptors and the pull lists are SpdVsolveCtx's): its own row items, Y
+// and the update block for `kb` columns -- allocated anew when a call brings a wider batch
+struct SpdMsolveCtx {
+  std::vector<std::pair<int, int>> fwd, bwd;
+  int *d_items = nullptr;
+  double *d_Y = nullptr, *d_UB = nullptr;
+  int kb = 0;
+  ~SpdMsolveCtx() {
+    for (void *q : {(void *)d_items, (void *)d_Y, (void *)d_UB})
       if (q) (void)hipFree(q);
   }
 };
@@ -968,9 +1101,11 @@ struct SpdNumericCtx {
     if (h_io) (void)hipHostFree(h_io);
     delete selinv;
     delete vsolve;
+    delete msolve;
   }
   SpdSelinvCtx *selinv = nullptr;   // spd_selinv_device: built on its first call
   SpdVsolveCtx *vsolve = nullptr;   // spd_vsolve_device: likewise
+  SpdMsolveCtx *msolve = nullptr;   // spd_msolve_device: likewise
   std::vector<int> cmap_host;       // the child -> parent position maps, kept for it (cmap_off[c] = F.ubuf_off[c])
   int build(const CsrMatrix &A, const SpdFactor &F, const std::vector<std::vector<int>> &children);
   // on: the stream to run on (nullptr: the context's own); defer: return once everything is enqueued -- finish() waits
@@ -1565,11 +1700,10 @@ int64_t spd_vsolve_bytes(const SpdFactor &F) {
          (int64_t)sizeof(VsolveDesc) * nt + 8 * vsolve_items(F);
 }
 
-int spd_vsolve_device(SpdFactor &F, double *x, void *stream) {
-  SpdNumericCtx *ctx = F.numeric;
-  if (!x || !ctx || ctx->factor_only || !ctx->d_W || !ctx->d_WT || !ctx->outputs_zeroed) return -1;
-  if (ctx->pending && ctx->finish(F) != 0) return -1;
-  if (F.not_pd) return -1;   // nothing is solved with a factorisation that met a non-positive pivot
+namespace {
+// the descriptors, the pull lists and the row items of spd_vsolve_device: built by its first call, or by spd_msolve_device's,
+// which runs on the same descriptors and lists
+int vsolve_prepare(SpdNumericCtx *ctx, const SpdFactor &F) {
   const int nt = ctx->nt;
   if (!ctx->vsolve) {
     std::unique_ptr<SpdVsolveCtx> vc(new SpdVsolveCtx());
@@ -1647,6 +1781,16 @@ int spd_vsolve_device(SpdFactor &F, double *x, void *stream) {
     FA_OK(hipMemcpy(vc->d_asm_src, asm_src.data(), sizeof(int) * asm_src.size(), hipMemcpyHostToDevice));
     ctx->vsolve = vc.release();
   }
+  return 0;
+}
+}  // namespace
+
+int spd_vsolve_device(SpdFactor &F, double *x, void *stream) {
+  SpdNumericCtx *ctx = F.numeric;
+  if (!x || !ctx || ctx->factor_only || !ctx->d_W || !ctx->d_WT || !ctx->outputs_zeroed) return -1;
+  if (ctx->pending && ctx->finish(F) != 0) return -1;
+  if (F.not_pd) return -1;   // nothing is solved with a factorisation that met a non-positive pivot
+  if (vsolve_prepare(ctx, F) != 0) return -1;
   const SpdVsolveCtx &vc = *ctx->vsolve;
   hipStream_t st = stream ? (hipStream_t)stream : ctx->st;
   for (const auto &L : vc.fwd)
@@ -1671,6 +1815,108 @@ void spd_vsolve_release(SpdFactor &F) {
   if (!F.numeric) return;
   delete F.numeric->vsolve;
   F.numeric->vsolve = nullptr;
+}
+
+// ---- the solve for a block of plain vectors ----
+namespace {
+int64_t msolve_items(const SpdFactor &F) {
+  int64_t items = 0;
+  for (int f = 0; f < F.nfronts; f++) items += (F.w[f] + F.u[f] + MS_ROWS - 1) / MS_ROWS + (F.w[f] + MS_ROWS - 1) / MS_ROWS;
+  return items;
+}
+int msolve_kb(int k) { return 16 * ((std::min(std::max(k, 1), MS_COLS) + 15) / 16); }
+
+template <int NT>
+void msolve_batch(const SpdNumericCtx *ctx, const SpdMsolveCtx &mc, double *X, int ldx, int c0, int nc, hipStream_t st) {
+  const SpdVsolveCtx &vc = *ctx->vsolve;
+  for (const auto &L : mc.fwd)
+    if (L.second > 0)
+      hipLaunchKernelGGL((k_ms_forward<NT>), dim3(L.second), dim3(256), 0, st, vc.d_vd, mc.d_items + 2 * L.first, ctx->d_W, vc.d_piv,
+                         vc.d_asm_ptr, vc.d_asm_src, X, ldx, c0, nc, mc.d_Y, mc.d_UB, mc.kb, ms_chunk);
+  for (const auto &L : mc.bwd)
+    if (L.second > 0)
+      hipLaunchKernelGGL((k_ms_backward<NT>), dim3(L.second), dim3(256), 0, st, vc.d_vd, mc.d_items + 2 * L.first, ctx->d_WT, vc.d_piv,
+                         vc.d_upd, mc.d_Y, X, ldx, c0, nc, mc.kb, ms_chunk);
+}
+}  // namespace
+
+int64_t spd_msolve_bytes(const SpdFactor &F, int kb) {
+  if ((int)F.upd_ptr.size() != F.nfronts + 1 || kb < 1) return 0;
+  return 8 * (int64_t)msolve_kb(kb) * ((int64_t)F.n + F.total_upd) + 8 * msolve_items(F) + spd_vsolve_bytes(F);
+}
+
+int spd_msolve_device(SpdFactor &F, double *X, int k, int ldx, void *stream) {
+  SpdNumericCtx *ctx = F.numeric;
+  if (!X || k < 1 || ldx < k || !ctx || ctx->factor_only || !ctx->d_W || !ctx->d_WT || !ctx->outputs_zeroed) return -1;
+  if (ctx->pending && ctx->finish(F) != 0) return -1;
+  if (F.not_pd) return -1;   // nothing is solved with a factorisation that met a non-positive pivot
+  if (vsolve_prepare(ctx, F) != 0) return -1;
+  const int nt = ctx->nt, kb = msolve_kb(k);
+  if (!ctx->msolve) {
+    std::unique_ptr<SpdMsolveCtx> mc(new SpdMsolveCtx());
+    std::vector<int> height(nt, 0), depth(nt, 0);
+    int maxh = 0, maxd = 0;
+    for (int f = 0; f < nt; f++)   // (vsolve_prepare has checked the post-order)
+      if (F.parent[f] >= 0) height[F.parent[f]] = std::max(height[F.parent[f]], height[f] + 1);
+    for (int f = nt - 1; f >= 0; f--) {
+      if (F.parent[f] >= 0) depth[f] = depth[F.parent[f]] + 1;
+      maxh = std::max(maxh, height[f]);
+      maxd = std::max(maxd, depth[f]);
+    }
+    std::vector<int> items;
+    for (int h = 0; h <= maxh; h++) {
+      const int first = (int)items.size() / 2;
+      for (int f = 0; f < nt; f++)
+        if (height[f] == h)
+          for (int r0 = 0; r0 < F.w[f] + F.u[f]; r0 += MS_ROWS) { items.push_back(f); items.push_back(r0); }
+      mc->fwd.push_back({first, (int)items.size() / 2 - first});
+    }
+    for (int dp = 0; dp <= maxd; dp++) {
+      const int first = (int)items.size() / 2;
+      for (int f = 0; f < nt; f++)
+        if (depth[f] == dp)
+          for (int r0 = 0; r0 < F.w[f]; r0 += MS_ROWS) { items.push_back(f); items.push_back(r0); }
+      mc->bwd.push_back({first, (int)items.size() / 2 - first});
+    }
+    FA_OK(hipMalloc((void **)&mc->d_items, sizeof(int) * std::max<size_t>(items.size(), 2)));
+    if (!items.empty()) FA_OK(hipMemcpy(mc->d_items, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+    ctx->msolve = mc.release();
+  }
+  SpdMsolveCtx &mc = *ctx->msolve;
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->st;
+  if (mc.kb < kb) {   // (a wider batch than any before: what is queued on the narrower buffers ends first)
+    if (mc.kb > 0) FA_OK(hipDeviceSynchronize());
+    if (mc.d_Y) (void)hipFree(mc.d_Y);
+    if (mc.d_UB) (void)hipFree(mc.d_UB);
+    mc.d_Y = mc.d_UB = nullptr;
+    mc.kb = 0;
+    FA_OK(hipMalloc((void **)&mc.d_Y, sizeof(double) * (size_t)kb * std::max(F.n, 1)));
+    FA_OK(hipMalloc((void **)&mc.d_UB, sizeof(double) * (size_t)kb * std::max(F.total_upd, 1)));
+    mc.kb = kb;
+  }
+  for (int c0 = 0; c0 < k; c0 += MS_COLS) {
+    const int nc = std::min(MS_COLS, k - c0);
+    switch ((nc + 15) / 16) {
+      case 1: msolve_batch<1>(ctx, mc, X, ldx, c0, nc, st); break;
+      case 2: msolve_batch<2>(ctx, mc, X, ldx, c0, nc, st); break;
+      case 3: msolve_batch<3>(ctx, mc, X, ldx, c0, nc, st); break;
+      default: msolve_batch<4>(ctx, mc, X, ldx, c0, nc, st); break;
+    }
+  }
+  FA_OK(hipGetLastError());
+  return 0;
+}
+
+int spd_msolve_chunk(int chunk) {
+  const int before = ms_chunk;
+  ms_chunk = chunk >= 1 && chunk <= MS_SLAB ? chunk : MS_SLAB;
+  return before;
+}
+
+void spd_msolve_release(SpdFactor &F) {
+  if (!F.numeric) return;
+  delete F.numeric->msolve;
+  F.numeric->msolve = nullptr;
 }
 
 void spd_release_numeric(SpdFactor &F) {

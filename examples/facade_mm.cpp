@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|staircase]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|staircase|pairs <candidates.g2o>]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -17,6 +17,11 @@
 // and with `staircase` through DPGOHashGroup::riemannian_staircase (trivial loss), one line per row of the result:
 //   staircase: x <row> <the d entries, 17 digits>       then
 //   staircase: <SOLVED|MAX_RANK|SADDLE|SKIPPED|FAILED> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
+// and with `pairs <candidates.g2o>` through DPGOHashGroup::pair_covariances (trivial loss; pose 0 is the anchor): the file's
+// edges p -> q are the pairs and their measurements the candidates; per candidate three lines, all entries with 17 digits,
+//   pairs: joint <k> <the 3 dof^2 entries>     pairs: rel <k> <the dof^2 entries>     pairs: gate <k> <d2 not_pd residual>
+// then   pairs: <OK|NOT_PD|SKIPPED|FAILED> <columns> <batches> <stationarity>; a last call with candidates of the wrong length
+// must fail:   pairs: short candidates <status>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -36,7 +41,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|staircase]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|staircase|pairs <candidates.g2o>]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -159,6 +164,44 @@ int main(int argc, char **argv) {
             : status == DPGO_STAIR_SADDLE ? "SADDLE" : status == DPGO_STAIR_SKIPPED ? "SKIPPED" : "FAILED",
             r.final_rank, r.F_initial, r.F_sdp, r.F_final, r.gap);
     if (status < 0) return 1;
+  }
+  if (argc > 7 && !strcmp(argv[6], "pairs")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d());
+    if (dpgo_hash.gather(X) != 0) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2, nc = d * d + d + 2;
+    auto cg = DPGO::Graph::read_g2o(argv[7], 1);
+    const int m = cg->num_edges();
+    std::vector<int> I(m), J(m), pairs((size_t)2 * m);
+    std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m), cand((size_t)m * nc);
+    if (cg->d() != d || dpgo_graph_edges(cg->handle(), I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data()) != 0) return 1;
+    for (int k = 0; k < m; k++) {
+      pairs[2 * k] = I[k]; pairs[2 * k + 1] = J[k];
+      for (int i = 0; i < d * d; i++) cand[(size_t)k * nc + i] = R[(size_t)k * d * d + i];
+      for (int i = 0; i < d; i++) cand[(size_t)k * nc + d * d + i] = t[(size_t)k * d + i];
+      cand[(size_t)k * nc + d * d + d] = kappa[k];
+      cand[(size_t)k * nc + d * d + d + 1] = tau[k];
+    }
+    std::vector<double> joint, rel, gate;
+    int status = -1;
+    dpgo_pairs_result_t r = {};
+    const bool ok = dpgo_hash.pair_covariances(X, pairs, joint, rel, 0, &r, &status, &cand, &gate);
+    auto line = [&](const char *what, int k, const std::vector<double> &v, int n) {
+      fprintf(stderr, "pairs: %s %d", what, k);
+      for (int i = 0; i < n; i++) fprintf(stderr, " %.17g", v[(size_t)k * n + i]);
+      fprintf(stderr, "\n");
+    };
+    for (int k = 0; ok && k < m; k++) {
+      line("joint", k, joint, 3 * dof * dof);
+      line("rel", k, rel, dof * dof);
+      line("gate", k, gate, 2 + dof);
+    }
+    fprintf(stderr, "pairs: %s %d %d %.10e\n", status == DPGO_PAIRS_OK ? "OK" : status == DPGO_PAIRS_NOT_PD ? "NOT_PD"
+            : status == DPGO_PAIRS_SKIPPED ? "SKIPPED" : "FAILED", r.columns, r.batches, r.stationarity);
+    if (status < 0) return 1;
+    cand.pop_back();
+    int short_status = 0;
+    dpgo_hash.pair_covariances(X, pairs, joint, rel, 0, nullptr, &short_status, &cand, &gate);
+    fprintf(stderr, "pairs: short candidates %d %d\n", short_status, (int)gate.size());
   }
   return 0;
 }

@@ -543,6 +543,59 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
                                      int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                      double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary);
 
+/* ---- joint covariances of arbitrary pose pairs and loop-closure gating -------------------- */
+/* dpgo_group_covariance knows the cross block of an EDGE only.  Here (p, q) are any two poses: with the factor of the same
+ * anchored H, the columns of H^-1 that belong to the poses asked for are solved for on the device (a block solve on the fp64
+ * matrix cores, at most 64 columns per batch) and read at the rows of p and q.  No block of a selected inversion is stored,
+ * so the refusal counts the numeric phase, the solve and the call's own buffers: this may run where dpgo_group_covariance
+ * answers COV_SKIPPED.  Restrictions, anchor and coordinates as for dpgo_group_covariance; the optimiser is not touched.
+ *   pairs       npairs x 2 global poses; p == q, a pose equal to the anchor and repeated pairs are allowed
+ *   candidates  NULL, or npairs x (d^2 + d + 2) doubles: a candidate relative measurement R~ (d x d row-major), t~ (d),
+ *               kappa, tau (> 0, else -1) of every pair -- what a loop-closure edge p -> q would carry
+ *   joint       npairs x 3 x dof^2: Sigma_pp, Sigma_pq, Sigma_qq, row-major.  Sigma_pq has the ROWS of p and the COLUMNS of
+ *               q, Sigma_pq[a][b] = cov(x_p[a], x_q[b]), as `cross` of dpgo_group_covariance.  Blocks that involve the anchor
+ *               are exact zeros; a pair's bits do not depend on what else the call asks for
+ *   rel         npairs x dof^2: the covariance of T_pq = T_p^-1 T_q in the same perturbation (t_pq + dt, R_pq Exp(hat(domega))),
+ *               J Sigma_joint J^T with domega_pq = omega_q - R_pq^T omega_p, dt_pq = R_p^T (dt_q - dt_p) + hat(t_pq) omega_p
+ *   gate        with candidates (else ignored; NULL with candidates: -1), npairs x (2 + dof): d^2 = r^T S^-1 r, not_pd (1.0
+ *               where S is not positive definite, and then d^2 = 0), the residual r = [t_pq - t~ ; vee Log(R~^T R_pq)];
+ *               S = rel + Omega^-1, Omega = blkdiag(tau I_d, 2 kappa I_{dof-d}).  No threshold is applied: compare d^2 with
+ *               the chi-square quantile (dof degrees of freedom) of your choice
+ *   result      outcome PAIRS_OK, PAIRS_NOT_PD (the anchored H is not positive definite; the outputs are zero) or
+ *               PAIRS_SKIPPED (device_bytes above max_bytes (> 0) or above half of the free device memory; the outputs are
+ *               not written, nothing is allocated); columns: unit columns solved (dof per distinct non-anchor pose), batches:
+ *               solves; factor_ms / solve_ms / gate_ms: host milliseconds of the three phases, each ending in a synchronise */
+#define DPGO_PAIRS_OK 0
+#define DPGO_PAIRS_NOT_PD 1
+#define DPGO_PAIRS_SKIPPED 2
+typedef struct dpgo_pairs_result {
+  int outcome, unknowns, fronts, levels, max_front, columns, batches, reserved;
+  long long device_bytes;
+  double pivot_min, pivot_max, stationarity, symbolic_s, factor_ms, solve_ms, gate_ms;
+  double solve_flops;    /* useful flops of the batches: sum over the fronts of 4 (w + u) w, times every batch's columns rounded up to 16 */
+  double factor_bytes;   /* factor bytes the batches stream: 16 sum (w + u) w per batch */
+} dpgo_pairs_result_t;
+int dpgo_group_pair_covariance(dpgo_group_t *grp, const double *X, int ld, int anchor, long long max_bytes, const int *pairs,
+                               int npairs, const double *candidates, double *joint, double *rel, double *gate,
+                               dpgo_pairs_result_t *result);
+/* The same for the RE-WEIGHTED problem at X, by dpgo_graph_covariance_reweighted's recipe. */
+int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                          int anchor, long long max_bytes, const int *pairs, int npairs, const double *candidates,
+                                          double *joint, double *rel, double *gate, dpgo_pairs_result_t *result,
+                                          dpgo_edge_summary_t *edge_summary);
+/* Measurement (tools/pair_bench.py): what there was before the block solve -- the anchored H of X written and factored as
+ * above, then ncols right-hand sides solved ONE AT A TIME with the single-vector device solve on the same factor, ending in
+ * a synchronise; *ms: host milliseconds of the ncols solves.  -1 where the call above would be refused or H is not positive
+ * definite. */
+int dpgo_debug_pairs_vsolve_baseline(dpgo_group_t *grp, const double *X, int ld, int anchor, int ncols, double *ms);
+/* Debug (no device): the column plan of a call -- poses (room for 2 npairs): the distinct non-anchor poses, ascending;
+ * pair_col (2 npairs): the first column of every pair's p and q, -1 for the anchor; sizes[4]: poses, columns, batches, kb. */
+int dpgo_debug_pairs_plan(int dof, int anchor, const int *pairs, int npairs, int *poses, int *pair_col, int *sizes);
+/* Debug (no device): the arithmetic of one pair on the host, the code k_pairs_gate runs -- recp / recq: the pose records
+ * (t, then R^T row-major), joint: 3 dof^2, cand: d^2 + d + 2 doubles or NULL; rel: dof^2, gate: 2 + dof (with cand). */
+int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const double *joint, const double *cand, double *rel,
+                          double *gate);
+
 /* ---- Newton polish: from the point the optimiser stopped at to a critical point ----------- */
 /* AMM-PGO# is a first-order method; the certificate and the covariances above mean something only at a critical point.
  * dpgo_group_polish takes damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored tangent-space Hessian
@@ -753,6 +806,19 @@ int dpgo_debug_spd_vsolve(int n, const int *ptr, const int *col, const double *v
 /* How many entries of a front's input vector spd_vsolve_device stages in LDS at a time: 1 ... 2048, anything else restores the
  * default 2048.  Process-wide; returns the value before.  For the tests: a chunk's edge inside fronts of a few hundred rows. */
 int dpgo_debug_spd_vsolve_chunk(int chunk);
+/* The device solve for a BLOCK of k plain vectors on a given SPD CSR matrix (tests/test_msolve_host.py,
+ * tests/test_gpu_msolve_fronts.py): dpgo_debug_spd_vsolve's sequence with spd_msolve_device(F, X, k, ldx) on the device and
+ * spd_solve_host(F, X, k) on the host.  rhs is n x k row-major.  out holds 3 n ldx doubles, three n x ldx row-major arrays:
+ * the first solution, its repetition, the second values' solution.  On the device each is uploaded as the caller filled it
+ * with rhs written into its first k columns, solved in place and read back whole, so the entries (i, k ... ldx) show what
+ * the solve left there; on the host only the first k columns are written.  A part whose factorisation met a non-positive
+ * pivot is not written.
+ *   chunk       > 0: for the length of the call, how many rows of a front's input block the device stages in LDS at a time
+ *               (spd_msolve_chunk: 1 ... 32, anything above restores the default 32); <= 0: as it is
+ *   status, pivots, the return value: as dpgo_debug_spd_vsolve; -1 also for k < 1 or ldx < k. */
+int dpgo_debug_spd_msolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
+                          int collapse, int block, int host, int chunk, const double *rhs, int k, int ldx, double *out,
+                          int *status, double *pivots);
 /* The device solve on a given matrix (tests/test_gpu_solve_tiles.py): an SpdSolverDev built as a group builds its own --
  * spd_factor(A, F, leaf, collapse, block) with the factor left on the device unless DPGO_SPD_DEVICE_PANELS=0, then
  * upload(dof, d, node_of_unknown) -- and spd_run on it.  The hook calls what exists; it adds nothing to spd_run or the kernels.

@@ -257,6 +257,30 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_COV_OK;
   }
+  // Joint covariances of arbitrary pose pairs and the loop-closure gate (dpgo_group_pair_covariance).  pairs: 2 npairs global
+  // poses, any two (no edge needed).  joint is resized to npairs 3 dof dof doubles (Sigma_pp, Sigma_pq with the rows of p and
+  // the columns of q, Sigma_qq), rel to npairs dof dof (the covariance of T_p^-1 T_q).  candidates / gate (optional, both or
+  // neither): npairs (d d + d + 2) doubles R~ row-major, t~, kappa, tau, and npairs (2 + dof) doubles d^2, not_pd, the
+  // residual.  Returns true for DPGO_PAIRS_OK; status: the DPGO_PAIRS_* outcome, -1 when the call itself failed.
+  bool pair_covariances(const Matrix &X, const std::vector<int> &pairs, std::vector<Scalar> &joint, std::vector<Scalar> &rel,
+                        int anchor = 0, dpgo_pairs_result_t *result = nullptr, int *status = nullptr,
+                        const std::vector<Scalar> *candidates = nullptr, std::vector<Scalar> *gate = nullptr,
+                        long long max_bytes = 0) const {
+    const int d = graph_->d(), npairs = (int)pairs.size() / 2;
+    const int dof = d + d * (d - 1) / 2;
+    joint.assign((size_t)npairs * 3 * dof * dof, 0.0);
+    rel.assign((size_t)npairs * dof * dof, 0.0);
+    const bool gated = candidates && gate && candidates->size() == (size_t)npairs * (d * d + d + 2);
+    if (gate) gate->assign(gated ? (size_t)npairs * (2 + dof) : 0, 0.0);
+    dpgo_pairs_result_t r = {};
+    const int rc = candidates && !gated ? -1
+                                        : dpgo_group_pair_covariance(h_, X.data(), X.rows(), anchor, max_bytes, pairs.data(), npairs,
+                                                                     gated ? candidates->data() : nullptr, joint.data(), rel.data(),
+                                                                     gated ? gate->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_PAIRS_OK;
+  }
   // Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X on the anchored tangent-space Hessian of
   // marginal_covariances, until the tangent gradient is at rounding level or the step budget is spent.  Xout: the new point
   // (X itself when the call is SKIPPED or fails).  opt (optional): the rule's parameters and the anchor; log (optional): per
