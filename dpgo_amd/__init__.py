@@ -261,6 +261,15 @@ SYMBOLS = {
                                                    _IP, C.c_int, _DP, _DP, C.c_void_p, C.c_void_p]),
     "dpgo_polish_options_default": (None, [C.c_void_p]),
     "dpgo_group_polish": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, C.c_void_p]),
+    "dpgo_group_robust_polish": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_longlong,
+                                           _DP, C.c_int, _DP, C.c_int, C.c_void_p, C.c_void_p]),
+    "dpgo_group_robust_covariance": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                               C.c_longlong, _IP, C.c_int, _DP, _DP, C.c_void_p]),
+    "dpgo_group_robust_hessian": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _IP, _IP, _DP,
+                                            C.c_longlong, C.POINTER(C.c_longlong), _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_group_robust_matrix": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
+                                           C.POINTER(C.c_longlong)]),
+    "dpgo_debug_robust_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP]),
     "dpgo_staircase_options_default": (None, [C.c_void_p]),
     "dpgo_group_staircase": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int,
                                        C.c_void_p]),
@@ -1186,6 +1195,76 @@ class NodeGroup:
                                "the graph, or bad sizes or options)")
         rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
         return Xout, r, log[:rows].copy()
+
+    def robust_polish(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, max_bytes=0, graph=None, **opts):
+        """Newton polish of the ROBUST objective F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (dpgo_group_robust_polish):
+        `polish`'s loop with the robust F, gradient and Hessian written on the device.  curvature 1: the true Hessian, with the
+        curvature 2 rho'' of the loss (quadratic convergence); 0: the re-weighted one (an IRLS-Newton step, linear).  The group is
+        a trivial-loss group that hosts every node; graph (default: the group's own) gives the edges and the inter rule.
+        Returns (Xout, PolishResult, log, EdgeSummary of the final point): as `polish`, the F fields the robust F."""
+        X, ld = _fcol(X)
+        o = PolishOptions(anchor=int(anchor), **opts)
+        Xout = np.array(X, order="F")
+        log = np.zeros((max(int(o.max_steps), 0) + 1, 5))
+        r, sm = PolishResult(), EdgeSummary()
+        if lib().dpgo_group_robust_polish(self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature),
+                                          C.byref(o), int(max_bytes), _dp(Xout), Xout.shape[0], _dp(log), len(log), C.byref(r),
+                                          C.byref(sm)) != 0:
+            raise RuntimeError("dpgo_group_robust_polish failed (a robust-loss group, a group that does not host every node, a graph "
+                               "that is not the group's, a bad loss, loss_reg, curvature or anchor, or bad sizes or options)")
+        rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
+        return Xout, r, log[:rows].copy(), sm
+
+    def robust_covariance(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, pairs=None, max_bytes=0, graph=None):
+        """Marginal pose covariances of the ROBUST objective at X (dpgo_group_robust_covariance): `covariance` on the true
+        Hessian (curvature 1) or the re-weighted one (curvature 0).  COV_NOT_PD is a legitimate answer where the negative
+        curvature of the loss wins.  Returns (marginals, cross, CovResult) as `covariance`; stationarity = |S_w X|_F."""
+        X, ld = _fcol(X)
+        dof = self.d + self.d * (self.d - 1) // 2
+        P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+        marg = np.zeros((self.graph.num_poses, dof, dof))
+        cross = np.zeros((len(P), dof, dof))
+        r = CovResult()
+        if lib().dpgo_group_robust_covariance(self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature),
+                                              int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P), _dp(marg),
+                                              _dp(cross) if len(P) else None, C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_robust_covariance failed (a robust-loss group, a group that does not host every node, a "
+                               "graph that is not the group's, a bad loss, loss_reg, curvature, anchor or pair, or bad sizes)")
+        return marg, cross, r
+
+    def robust_hessian(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, graph=None, edges=False):
+        """Debug: the anchored Hessian of the robust objective as the device wrote it (dpgo_group_robust_hessian).  Returns
+        (ptr, col, val, g, F, w, c): the CSR of `cov_hessian`, the tangent gradient (dof N by global pose, zeros on the
+        anchor), the robust F, and per edge the weight w and the curvature c = 2 rho''.  edges=True: (s_rot, s_trans, rho) of
+        every edge are appended as an eighth item -- what EdgeEval.run returns, bit for bit."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        dof = self.d + self.d * (self.d - 1) // 2
+        nnz = C.c_longlong(0)
+        args = (self._h, g_._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature), int(anchor))
+        if lib().dpgo_group_robust_hessian(*args, None, None, None, 0, C.byref(nnz), None, None, None, None, None, None, None) != 0:
+            raise RuntimeError("dpgo_group_robust_hessian failed")
+        n = dof * self.graph.num_poses
+        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+        g, F, w, c = np.zeros(n), C.c_double(0), np.zeros(g_.num_edges), np.zeros(g_.num_edges)
+        per = [np.zeros(g_.num_edges) for _ in range(3)]
+        if lib().dpgo_group_robust_hessian(*args, _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz), _dp(g), C.byref(F), _dp(w),
+                                           _dp(c), *[_dp(a) for a in per]) != 0:
+            raise RuntimeError("dpgo_group_robust_hessian failed")
+        return (ptr, col, val, g, F.value, w, c) + ((tuple(per),) if edges else ())
+
+    def robust_matrix(self, X, loss, loss_reg=0.25, graph=None):
+        """Debug: M_w = sum_e w_e(X) M_e as the device wrote it (dpgo_group_robust_matrix): CSR as `cert_matrix` hands out S."""
+        X, ld = _fcol(X)
+        nnz = C.c_longlong(0)
+        args = (self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg))
+        if lib().dpgo_group_robust_matrix(*args, None, None, None, 0, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_robust_matrix failed")
+        n = (self.d + 1) * self.graph.num_poses
+        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+        if lib().dpgo_group_robust_matrix(*args, _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
+            raise RuntimeError("dpgo_group_robust_matrix failed")
+        return ptr, col, val
 
     def staircase(self, X, max_bytes=0, **opts):
         """The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- TNT at
@@ -2166,6 +2245,19 @@ def edge_eval_host(graph, X, loss=LOSS_NONE, loss_reg=0.25):
     if lib().dpgo_debug_edge_eval_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), *[_dp(a) for a in out], C.byref(s)) != 0:
         raise ValueError("dpgo_debug_edge_eval_host failed (a short X, an unknown loss, or a bad loss_reg)")
     return out[0], out[1], out[2], out[3], s
+
+
+def robust_edge_debug(graph, X, loss=LOSS_NONE, loss_reg=0.25):
+    """Debug, no GPU: the per-edge arithmetic of the robust Hessian's kernels on the host (dpgo_debug_robust_edge_host).
+    Returns (w, c, rows, ghat): the weights, the curvatures c = 2 rho'', the rows (m, 2, d + 1, d) of (M_e X)_i and
+    (M_e X)_j (row 0 the translation's, then the rows of Y), and the tangent gradients (m, 2, dof) of the edge at i and j."""
+    X, ld = _fcol(X)
+    d, m = graph.d, graph.num_edges
+    dof = d + d * (d - 1) // 2
+    w, c, rows, gh = np.zeros(m), np.zeros(m), np.zeros((m, 2, d + 1, d)), np.zeros((m, 2, dof))
+    if lib().dpgo_debug_robust_edge_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), _dp(w), _dp(c), _dp(rows), _dp(gh)) != 0:
+        raise ValueError("dpgo_debug_robust_edge_host failed (a short X, an unknown loss, or a bad loss_reg)")
+    return w, c, rows, gh
 
 
 def verify_reweighted(graph, X, loss, loss_reg=0.25, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True,

@@ -1887,6 +1887,73 @@ int dpgo_group_polish(dpgo_group_t *h, const double *X, int ld, const dpgo_polis
   });
 }
 
+// ---- the robust objective: polish, covariances, the matrices behind them (robust.h) ----
+int dpgo_group_robust_polish(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, int curvature,
+                             const dpgo_polish_options_t *opt, long long max_bytes, double *Xout, int ldout, double *log, int log_cap,
+                             dpgo_polish_result_t *result, dpgo_edge_summary_t *edge_summary) {
+  if (!h || !h->grp || !g || !X || !Xout || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::PolishOptions o;
+    if (opt) { o.max_steps = opt->max_steps; o.max_tries = opt->max_tries; o.rel_tol = opt->rel_tol; o.grad_tol = opt->grad_tol; }
+    dpgo::PolishResult r;
+    dpgo::EdgeSummary s;
+    const int rc = h->grp->robust_polish(g->g, X, ld, loss, loss_reg, curvature, opt ? opt->anchor : 0, o, max_bytes, Xout, ldout, log,
+                                         log_cap, r, edge_summary ? &s : nullptr);
+    result->outcome = r.outcome; result->steps = r.steps; result->factorisations = r.factorisations;
+    result->indefinite = r.indefinite; result->F_initial = r.F_initial; result->F_final = r.F_final;
+    result->grad_initial = r.grad_initial; result->grad_final = r.grad_final; result->hmax = r.hmax;
+    result->mu_final = r.mu_final; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
+    result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels; result->max_front = r.max_front;
+    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
+    result->factor_ms = r.factor_ms; result->solve_ms = r.solve_ms; result->other_ms = r.other_ms;
+    if (rc == 0 && edge_summary && r.outcome != dpgo::POLISH_SKIPPED) {
+      edge_summary->F = s.F; edge_summary->F_intra = s.F_intra; edge_summary->F_inter = s.F_inter;
+      edge_summary->weight_min = s.weight_min; edge_summary->num_inter = s.num_inter;
+      edge_summary->num_downweighted = s.num_downweighted;
+    }
+    return rc;
+  });
+}
+
+int dpgo_group_robust_covariance(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg,
+                                 int curvature, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
+                                 double *cross, dpgo_cov_result_t *result) {
+  if (!h || !h->grp || !g || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
+  return guarded([&] {
+    dpgo::CovResult r;
+    const int rc = h->grp->robust_covariance(g->g, X, ld, loss, loss_reg, curvature, anchor, max_bytes, pairs, npairs, marginals,
+                                             cross, r);
+    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
+    result->max_front = r.max_front; result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min;
+    result->pivot_max = r.pivot_max; result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s;
+    result->numeric_ms = r.numeric_ms; result->factor_ms = r.factor_ms; result->selinv_ms = r.selinv_ms;
+    result->selinv_flops = r.selinv_flops;
+    return rc;
+  });
+}
+
+int dpgo_group_robust_hessian(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, int curvature,
+                              int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz, double *grad, double *F,
+                              double *w, double *c, double *s_rot, double *s_trans, double *rho) {
+  if (!h || !h->grp || !g || !X || !nnz) return -1;
+  return guarded([&] {
+    return h->grp->robust_hessian(g->g, X, ld, loss, loss_reg, curvature, anchor, ptr, col, val, cap, nnz, grad, F, w, c, s_rot, s_trans,
+                                  rho);
+  });
+}
+
+int dpgo_group_robust_matrix(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, int *ptr,
+                             int *col, double *val, long long cap, long long *nnz) {
+  if (!h || !h->grp || !g || !X || !nnz) return -1;
+  return guarded([&] { return h->grp->robust_matrix(g->g, X, ld, loss, loss_reg, ptr, col, val, cap, nnz); });
+}
+
+int dpgo_debug_robust_edge_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *w, double *c,
+                                double *rows, double *ghat) {
+  if (!g) return -1;
+  return guarded([&] { return dpgo::robust_edge_host(g->g, X, ld, loss, loss_reg, w, c, rows, ghat); });
+}
+
 // ---- the Riemannian staircase (stair.h) ----
 void dpgo_staircase_options_default(dpgo_staircase_options_t *opt) {
   if (!opt) return;

@@ -513,7 +513,13 @@ int Group::cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, 
   std::vector<double> v(c.A.col.size());
   HIP_CHECK(hipMemcpyAsync(v.data(), spd_numeric_values(c.F), sizeof(double) * v.size(), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
-  // handed out on GLOBAL poses -- unknown (d+1) g + r, g = gid[p] -- rows in that order, a row's blocks by ascending pose
+  cert_csr_out(v, ptr, col, val);
+  return 0;
+}
+
+// handed out on GLOBAL poses -- unknown (d+1) g + r, g = gid[p] -- rows in that order, a row's blocks by ascending pose
+void Group::cert_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val) {
+  CertState &c = *cert_;
   const int B = B_, BB = B * B, N = P0_;
   std::vector<int> row_of(N), order;
   for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
@@ -535,7 +541,6 @@ int Group::cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, 
       ptr[(size_t)B * g + r + 1] = (int)e;
     }
   }
-  return 0;
 }
 
 static bool cert_options_ok(const CertOptions &o, int rows, const double *V0, int ldv0, const double *x_out, int ldx) {

@@ -89,14 +89,18 @@ int Group::cov_analyse(CovResult &out) {
 }
 
 // The analysis, the refusal, the numeric context (first call that is not refused): cert_factor_setup's rule.
-int Group::cov_setup(long long max_bytes, CovResult &out) {
+int Group::cov_setup(long long max_bytes, CovResult &out, long long extra, long long extra_remain) {
   if (cov_analyse(out) != 0) return -1;
   CovState &s = *cov_;
-  if (max_bytes > 0 && s.bytes > max_bytes) return 1;
-  if (!s.F.numeric) {
+  out.device_bytes = s.bytes + extra;
+  if (max_bytes > 0 && s.bytes + extra > max_bytes) return 1;
+  const long long remain = (s.F.numeric ? 0 : s.bytes) + extra_remain;
+  if (remain > 0) {
     size_t free_b = 0, total_b = 0;
     HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    if ((unsigned long long)s.bytes > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
+    if ((unsigned long long)remain > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
+  }
+  if (!s.F.numeric) {
     s.bcol.upload(s.bcol_h);
     if (spd_prepare_device(s.A, s.F) != 0) {
       fprintf(stderr, "[dpgo_amd] ERROR: covariance: the device state of the factorisation could not be set up.\n");
@@ -141,6 +145,14 @@ int Group::covariance(const double *X, int ld, int anchor, long long max_bytes, 
   const int arow = row_of[anchor];
   const auto t0 = std::chrono::steady_clock::now();
   launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
+  return cov_finish(arow, row_of, pairs, npairs, marginals, cross, out, t0);
+}
+
+int Group::cov_finish(int arow, const std::vector<int> &row_of, const int *pairs, int npairs, double *marginals, double *cross,
+                      CovResult &out, std::chrono::steady_clock::time_point t0) {
+  CertState &c = *cert_;
+  CovState &s = *cov_;
+  const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
   const int rc = spd_refactor_device(s.F, st_, false);   // (returns with the verdict read)
   if (rc != 0 && !s.F.not_pd) {
     fprintf(stderr, "[dpgo_amd] ERROR: covariance: the factorisation failed on the device.\n");
@@ -235,15 +247,25 @@ int Group::cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, 
     fprintf(stderr, "[dpgo_amd] ERROR: covariance: the value array of the factorisation does not fit the device.\n");
     return -1;
   }
-  const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
-  std::vector<int> row_of(N), order;
+  const int N = P0_;
+  std::vector<int> row_of(N);
   for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   cert_prepare(X, ld, nullptr);
   launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, row_of[anchor], spd_numeric_values(s.F));
   std::vector<double> v(s.A.col.size());
   HIP_CHECK(hipMemcpyAsync(v.data(), spd_numeric_values(s.F), sizeof(double) * v.size(), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
-  // handed out on GLOBAL poses -- unknown dof g + a, g = gid[p] -- rows in that order, a row's blocks by ascending pose
+  cov_csr_out(v, ptr, col, val);
+  return 0;
+}
+
+// handed out on GLOBAL poses -- unknown dof g + a, g = gid[p] -- rows in that order, a row's blocks by ascending pose
+void Group::cov_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val) {
+  CertState &c = *cert_;
+  CovState &s = *cov_;
+  const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
+  std::vector<int> row_of(N), order;
+  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   size_t e = 0;
   ptr[0] = 0;
   for (int g = 0; g < N; g++) {
@@ -262,7 +284,6 @@ int Group::cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, 
       ptr[(size_t)dof * g + r + 1] = (int)e;
     }
   }
-  return 0;
 }
 
 }  // namespace dpgo

@@ -45,6 +45,18 @@ struct CovResult {
 };
 
 constexpr int cov_dof(int d) { return d + d * (d - 1) / 2; }
+// B_k(p) = -hat(e_k) Y_p has two non-zero rows: B_k[r1] = Y_p[r2], B_k[r2] = -Y_p[r1]  (d = 3: r1, r2 = k + 1, k + 2 mod 3;
+// d = 2: the one generator, r1 = 0, r2 = 1).  Shared by cov.hip, polish.hip and robust_math.h.
+template <int D>
+__host__ __device__ __forceinline__ void cov_rot_rows(int k, int &r1, int &r2) {
+  if (D == 3) {
+    r1 = k == 2 ? 0 : k + 1;
+    r2 = k == 0 ? 2 : k - 1;
+  } else {
+    r1 = 0;
+    r2 = 1;
+  }
+}
 
 // ---- kernel (cov.hip) ----
 // out = H in the CSR order of the pose-major matrix with dof x dof blocks: the dof^2 nb_p values of pose p's rows are one

@@ -9,19 +9,6 @@
 namespace dpgo {
 namespace {
 
-// B_k(p) = -hat(e_k) Y_p has two non-zero rows: B_k[r1] = Y_p[r2], B_k[r2] = -Y_p[r1]  (d = 3: r1, r2 = k + 1, k + 2 mod 3;
-// d = 2: the one generator, r1 = 0, r2 = 1)
-template <int D>
-__device__ __forceinline__ void rot_rows(int k, int &r1, int &r2) {
-  if (D == 3) {
-    r1 = k == 2 ? 0 : k + 1;
-    r2 = k == 0 ? 2 : k - 1;
-  } else {
-    r1 = 0;
-    r2 = 1;
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void k_cov_hessian(int nposes, const int *__restrict__ bptr, const int *__restrict__ bcol,
                                                      const double *__restrict__ Mval, const double *__restrict__ Lam,
@@ -51,16 +38,16 @@ __global__ __launch_bounds__(256) void k_cov_hessian(int nposes, const int *__re
       h = a == b ? S(0, 0) : 0.0;
     } else if (a < D) {                 // translation a, rotation b - D of q:  sum_r S[0, 1 + r] B_l(q)[r, a]
       int s1, s2;
-      rot_rows<D>(b - D, s1, s2);
+      cov_rot_rows<D>(b - D, s1, s2);
       h = fma(S(0, 1 + s1), Yq[s2 * D + a], -(S(0, 1 + s2) * Yq[s1 * D + a]));
     } else if (b < D) {                 // rotation a - D of p, translation b:  sum_r B_k(p)[r, b] S[1 + r, 0]
       int r1, r2;
-      rot_rows<D>(a - D, r1, r2);
+      cov_rot_rows<D>(a - D, r1, r2);
       h = fma(Yp[r2 * D + b], S(1 + r1, 0), -(Yp[r1 * D + b] * S(1 + r2, 0)));
     } else {                            // tr(B_k(p)^T S[1:, 1:] B_l(q))
       int r1, r2, s1, s2;
-      rot_rows<D>(a - D, r1, r2);
-      rot_rows<D>(b - D, s1, s2);
+      cov_rot_rows<D>(a - D, r1, r2);
+      cov_rot_rows<D>(b - D, s1, s2);
       const double S11 = S(1 + r1, 1 + s1), S12 = S(1 + r1, 1 + s2), S21 = S(1 + r2, 1 + s1), S22 = S(1 + r2, 1 + s2);
       h = 0.0;
 #pragma unroll

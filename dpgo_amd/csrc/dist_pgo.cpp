@@ -32,6 +32,15 @@
 //              the anchor) from the final X, and one more line on stdout
 //                  polish: <outcome> <steps> <factorisations> <indefinite> <F_initial> <F_final> <grad_initial> <grad_final>
 //              the result files then hold the polished X; the same reasons as --covariance when it is not computed
+//              --robust_polish (likewise)  after the loop and ahead of --edge_report / --verify_reweighted / --robust_covariance, which
+//              then act on its point, for a robust --loss and a world of one rank: dpgo_group_robust_polish (the Newton polish of
+//              the robust objective on its true Hessian, pose 0 the anchor) on a second, trivial-loss group of the same graph
+//              built for it (max_iterations = 0; seconds of set-up at 100 000 poses), one more line on stdout
+//                  robust polish: <the fields of polish:>
+//              with the F fields those of the robust objective; the result files then hold the polished X; with the trivial loss
+//              (--polish is the call then) or several ranks a line "robust polish: not computed (...)" that says why not
+//              --robust_covariance FILE (likewise; empty: off)  in --covariance's file format and with its line on stdout under
+//              the prefix "robust covariance:", from dpgo_group_robust_covariance at the final X
 //              --staircase (likewise)  after --polish and ahead of --certify / --verify / --covariance, which then act on its
 //              result, for the trivial loss and a world of one rank: dpgo_group_staircase (the Riemannian staircase: TNT at rank
 //              r, verify, an escape along the certificate's direction, the rounding and a polish) from the point so far, and
@@ -82,8 +91,8 @@ static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strc
 int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
-  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false;
-  std::string edge_report, covariance, gate_candidates, gate_report;
+  bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
+  std::string edge_report, covariance, gate_candidates, gate_report, robust_covariance;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -96,12 +105,18 @@ int main(int argc, char **argv) {
     };
     if (a == "--help") {
       printf("Program options:\n  --dataset arg\n  --num_nodes arg\n  --iters arg (=1000)\n  --dist_init arg (=true)\n"
-             "  --loss arg (=trivial)   trivial, huber or welsch\n  --accelerated arg (=true)\n  --save arg (=true)\n  --gpu arg (=0)\n");
+             "  --loss arg (=trivial)   trivial, huber or welsch\n  --accelerated arg (=true)\n  --save arg (=true)\n  --gpu arg (=0)\n"
+             "  --robust_polish         robust loss, one rank: Newton polish of the robust objective after the loop; builds a second,\n"
+             "                          trivial-loss group of the graph (seconds of set-up at 100 000 poses)\n"
+             "  --robust_covariance arg likewise: marginal covariances on the robust Hessian, written to the file named\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
     else if (a == "--polish") polish = true;
     else if (a.compare(0, 9, "--polish=") == 0) polish = parse_bool(argv[i] + 9);
+    else if (a == "--robust_polish") robust_polish = true;
+    else if (a.compare(0, 16, "--robust_polish=") == 0) robust_polish = parse_bool(argv[i] + 16);
+    else if (const char *v = val("--robust_covariance")) robust_covariance = v;
     else if (a == "--staircase") staircase = true;
     else if (a.compare(0, 12, "--staircase=") == 0) staircase = parse_bool(argv[i] + 12);
     else if (a == "--verify") verify = true;
@@ -267,6 +282,33 @@ int main(int argc, char **argv) {
       if (sr.outcome != DPGO_STAIR_SKIPPED) Xpol.swap(Z);
     }
   }
+  // the robust objective: a trivial-loss group of the same graph, built once for both flags
+  dpgo_group_t *post = nullptr;
+  auto post_group = [&]() -> int {
+    if (post) return 0;
+    dpgo_options_t po;
+    dpgo_options_driver(&po, 0, accelerated);
+    po.max_iterations = 0;
+    return dpgo_group_create(g, ids.data(), per, &po, gpu, &post);
+  };
+  if (robust_polish) {
+    if (loss == 0) {
+      if (root) printf("robust polish: not computed (the loss is trivial: --polish is the call)\n");
+    } else if (world > 1) {
+      if (root) printf("robust polish: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0);
+      dpgo_polish_result_t pr;
+      if (final_point(Xc.data()) != 0 || post_group() != 0 ||
+          dpgo_group_robust_polish(post, g, Xc.data(), ld, loss, opt.loss_reg, 1, nullptr, 0, Z.data(), ld, nullptr, 0, &pr, nullptr) != 0)
+        return -1;
+      printf("robust polish: %s %d %d %d %.17g %.17g %.17g %.17g\n",
+             pr.outcome == DPGO_POLISH_CONVERGED ? "CONVERGED" : pr.outcome == DPGO_POLISH_MAX_STEPS ? "MAX_STEPS"
+             : pr.outcome == DPGO_POLISH_STALLED ? "STALLED" : "SKIPPED",
+             pr.steps, pr.factorisations, pr.indefinite, pr.F_initial, pr.F_final, pr.grad_initial, pr.grad_final);
+      if (pr.outcome != DPGO_POLISH_SKIPPED) Xpol.swap(Z);
+    }
+  }
   if (certify) {
     if (loss != 0) {
       if (root) printf("certificate: not computed (the certificate is that of the trivial loss; --loss %s)\n", loss_type.c_str());
@@ -378,6 +420,35 @@ int main(int argc, char **argv) {
       }
     }
   }
+  if (!robust_covariance.empty()) {
+    if (loss == 0) {
+      if (root) printf("robust covariance: not computed (the loss is trivial: --covariance is the call)\n");
+    } else if (world > 1) {
+      if (root) printf("robust covariance: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      const int dof = d + d * (d - 1) / 2;
+      std::vector<double> Xc((size_t)ld * d, 0.0), marg((size_t)N * dof * dof, 0.0);
+      dpgo_cov_result_t cv;
+      if (final_point(Xc.data()) != 0 || post_group() != 0 ||
+          dpgo_group_robust_covariance(post, g, Xc.data(), ld, loss, opt.loss_reg, 1, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0)
+        return -1;
+      printf("robust covariance: %s %d %d %d %d %lld %.16g %.16g\n",
+             cv.outcome == DPGO_COV_OK ? "OK" : cv.outcome == DPGO_COV_NOT_PD ? "NOT_PD" : "SKIPPED", cv.unknowns, cv.fronts, cv.levels,
+             cv.max_front, cv.device_bytes, cv.pivot_min, cv.stationarity);
+      if (cv.outcome == DPGO_COV_OK) {
+        FILE *f = fopen(robust_covariance.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", robust_covariance.c_str()); return -1; }
+        for (int p = 0; p < N; p++) {
+          fprintf(f, "%d", p);
+          for (int a = 0; a < dof; a++)
+            for (int b = a; b < dof; b++) fprintf(f, " %.17g", marg[((size_t)p * dof + a) * dof + b]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+    }
+  }
+  if (post) dpgo_group_free(post);
   if (!gate_candidates.empty() || !gate_report.empty()) {
     if (gate_candidates.empty() || gate_report.empty()) {
       fprintf(stderr, "--gate_candidates and --gate_report go together.\n");

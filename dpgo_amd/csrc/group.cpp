@@ -501,6 +501,7 @@ Group::~Group() {
   sched_.close(failed_ ? 2.0 : 60.0);
   chordal_release();
   stair_release();
+  robust_release();
   cov_release();
   cert_release();
 }

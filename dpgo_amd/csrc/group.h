@@ -32,6 +32,7 @@
 #include "kernels.h"
 #include "pairs.h"
 #include "polish.h"
+#include "robust.h"
 #include "schedule.h"
 #include "settings.h"
 #include "spd_solve.h"
@@ -198,6 +199,21 @@ class Group {
   // SKIPPED; log (optional, log_cap rows of POLISH_LOG_COLS doubles): one row per iteration
   int polish(const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout, int ldout, double *log,
              int log_cap, PolishResult &out);
+  // ---- the robust objective (robust.h, robust.cpp): the polish and the covariances on the TRUE Hessian of
+  // F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (curvature 1), or on the re-weighted one (curvature 0).  g: a graph of
+  // the group's poses whose every edge is a block of the certificate's pattern (-1 otherwise); the group itself is a
+  // trivial-loss group that hosts every node, as for every call above.  robust_hessian: the anchored H as cov_hessian hands it
+  // out, optionally with grad (dof N by global pose), F and per edge w, c, s_rot, s_trans, rho; robust_matrix: M_w as cert_matrix hands out S
+  int robust_polish(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor,
+                    const PolishOptions &o, long long max_bytes, double *Xout, int ldout, double *log, int log_cap, PolishResult &out,
+                    EdgeSummary *sum);
+  int robust_covariance(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor,
+                        long long max_bytes, const int *pairs, int npairs, double *marginals, double *cross, CovResult &out);
+  int robust_hessian(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, int *ptr, int *col,
+                     double *val, long long cap, long long *nnz, double *grad, double *F, double *w, double *c, double *s_rot,
+                     double *s_trans, double *rho);
+  int robust_matrix(const Graph &g, const double *X, int ld, int loss, double loss_reg, int *ptr, int *col, double *val, long long cap,
+                    long long *nnz);
   // ---- joint covariances of arbitrary pose pairs and the loop-closure gate (pairs.h, pairs.cpp): the covariance's factor,
   // the columns of H^-1 of the poses asked for by spd_msolve_device.  pairs: npairs x 2 global poses, any two; candidates
   // (optional): npairs x (d^2 + d + 2) doubles, R~ row-major, t~, kappa, tau; joint: npairs x 3 x dof^2 (S_pp, S_pq, S_qq);
@@ -608,8 +624,34 @@ class Group {
   void cov_release();
   int cov_begin(const double *X, int ld, int anchor);
   int cov_analyse(CovResult &out);                      // the pattern and the symbolic analysis (first call), the sizes
-  int cov_setup(long long max_bytes, CovResult &out);   // 0: ready, 1: SKIPPED, -1: error
-  int polish_setup(long long max_bytes, PolishResult &out);   // likewise, for what polish allocates (polish.cpp)
+  // 0: ready, 1: SKIPPED, -1: error.  extra / extra_remain: bytes the caller allocates behind the same refusal (robust.cpp) --
+  // all of them, and those still to be allocated
+  int cov_setup(long long max_bytes, CovResult &out, long long extra = 0, long long extra_remain = 0);
+  // likewise, for what polish allocates (polish.cpp)
+  int polish_setup(long long max_bytes, PolishResult &out, long long extra = 0, long long extra_remain = 0);
+  // what is behind the Hessian's launch in covariance: the factorisation, the selected inversion, the read-out (t0: the launch)
+  int cov_finish(int arow, const std::vector<int> &row_of, const int *pairs, int npairs, double *marginals, double *cross,
+                 CovResult &out, std::chrono::steady_clock::time_point t0);
+  // a value array in the order of the certificate's / the covariance's pattern as CSR on global poses (cert_matrix, cov_hessian)
+  void cert_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val);
+  void cov_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val);
+  // The loop of the Newton polish (polish.cpp) on CertState's X, shared by polish and robust_polish.  What differs is launched
+  // by the caller's hooks: point -- M X (or M_w X) into MX, Lambda, g, |g|^2 into slot 0 and F into slot 1 of the partials;
+  // hessian -- H at X into the factorisation's values; trial -- F at the trial point V into slot 2
+  struct PolishHooks {
+    std::function<void()> point, hessian, trial;
+  };
+  int polish_loop(const double *X, int ld, int arow, const PolishOptions &o, const PolishHooks &hooks, double *Xout, int ldout,
+                  double *log, int log_cap, PolishResult &out);
+  struct RobustState;   // the lists and buffers of the robust objective (robust.cpp), allocated by the first call that is not refused
+  RobustState *rob_ = nullptr;
+  void robust_release();
+  int robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who);
+  long long robust_remain() const;
+  void robust_alloc();
+  void robust_eval(const double *Xdev, int loss, double loss_reg, bool with_rows, int fslot);
+  void robust_hessian_launch(int arow, int curvature);
+  void robust_summary(EdgeSummary *sum);
   int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out);   // likewise (pairs.cpp)
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;

@@ -1,7 +1,8 @@
 // Host side of the Newton polish (polish.h): the refusal, and the loop -- the gradient, the Hessian and its shift written on the
 // device, spd_refactor_device, spd_vsolve_device, the retraction, one product with M for F(Z), and a handful of scalars read
 // back per try through the group's read-back flag.  The matrix is the covariance's (cov.cpp): its pattern, its symbolic
-// analysis and its numeric context are shared.  The optimiser's state is not touched (cert_begin).
+// analysis and its numeric context are shared.  The optimiser's state is not touched (cert_begin).  The loop itself is
+// polish_loop: what differs between the trivial loss and the robust objective (robust.cpp) is launched by three hooks.
 #include "polish.h"
 
 #include <algorithm>
@@ -16,7 +17,7 @@ namespace dpgo {
 
 // The analysis (first call), the prediction, the refusal, what polish allocates (first call that is not refused): cov_setup's
 // rule on the bytes of the numeric phase, the vector solve and the three vectors -- not on the blocks of the selected inversion.
-int Group::polish_setup(long long max_bytes, PolishResult &out) {
+int Group::polish_setup(long long max_bytes, PolishResult &out, long long extra, long long extra_remain) {
   CovResult cr;
   if (cov_analyse(cr) != 0) return -1;
   CertState &c = *cert_;
@@ -27,13 +28,13 @@ int Group::polish_setup(long long max_bytes, PolishResult &out) {
   out.fronts = cr.fronts;
   out.levels = cr.levels;
   out.max_front = cr.max_front;
-  out.device_bytes = s.pol_bytes;
+  out.device_bytes = s.pol_bytes + extra;
   out.symbolic_s = cr.symbolic_s;
   out.outcome = POLISH_SKIPPED;
-  if (max_bytes > 0 && s.pol_bytes > max_bytes) return 1;
+  if (max_bytes > 0 && s.pol_bytes + extra > max_bytes) return 1;
   // against the free memory only what is still to be allocated counts: a covariance call may have left the numeric phase
   // and the block-column map, an earlier polish everything
-  long long remain = 0;
+  long long remain = extra_remain;
   if (!s.F.numeric) remain += (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + 4ll * nblk;
   if (!s.pol_g.p) remain += (long long)spd_vsolve_bytes(s.F) + 3ll * 8ll * n;
   if (remain > 0) {
@@ -70,10 +71,31 @@ int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, l
   CertState &c = *cert_;
   CovState &s = *cov_;
   const int N = P0_;
-  const size_t n = (size_t)s.A.n;
   int arow = 0;
   for (int p = 0; p < N; p++)
     if (c.gid[p] == anchor) arow = p;
+  const NodeMask all{all_bits(), nullptr};
+  PolishHooks hooks;
+  hooks.point = [&] {
+    cert_apply_M(c.X.p, c.MX.p);
+    launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
+    launch_polish_grad(lc(all), c.X.p, c.MX.p, arow, s.pol_g.p, 0, 1, c.partials.p);
+  };
+  hooks.hessian = [&] {
+    launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
+  };
+  hooks.trial = [&] {
+    cert_apply_M(c.V.p, c.SV.p);
+    launch_polish_grad(lc(all), c.V.p, c.SV.p, arow, nullptr, -1, 2, c.partials.p);
+  };
+  return polish_loop(X, ld, arow, o, hooks, Xout, ldout, log, log_cap, out);
+}
+
+int Group::polish_loop(const double *X, int ld, int arow, const PolishOptions &o, const PolishHooks &hooks, double *Xout, int ldout,
+                       double *log, int log_cap, PolishResult &out) {
+  CertState &c = *cert_;
+  CovState &s = *cov_;
+  const size_t n = (size_t)s.A.n;
   const NodeMask all{all_bits(), nullptr};
   typedef std::chrono::steady_clock Clock;
   auto ms_since = [](Clock::time_point t) { return 1e3 * std::chrono::duration<double>(Clock::now() - t).count(); };
@@ -84,12 +106,10 @@ int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, l
   out.outcome = POLISH_STALLED;
   for (int k = 0; k <= o.max_steps; k++) {
     // g, |g|, F0, H and hmax at X; the first try's shift rides along
-    cert_apply_M(c.X.p, c.MX.p);
-    launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
-    launch_polish_grad(lc(all), c.X.p, c.MX.p, arow, s.pol_g.p, 0, 1, c.partials.p);
+    hooks.point();
     HIP_CHECK(hipStreamSynchronize(st_));   // (the product and the gradient are other_ms: the clock of factor_ms starts behind them)
     auto t0 = Clock::now();
-    launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
+    hooks.hessian();
     launch_polish_shift(lc(all), c.bptr.p, c.diag_pose.p, arow, mu, true, s.pol_hdiag.p, spd_numeric_values(s.F), 2, c.partials.p);
     launch_polish_reduce(st_, T_, 3, 1u << 2, c.partials.p, c.h_sums, sched_.flag());
     wait_flag(sched_.last_seq());
@@ -142,8 +162,7 @@ int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, l
         return -1;
       }
       launch_polish_retract(lc(all), c.X.p, s.pol_sol.p, s.pol_g.p, arow, c.V.p, 0, 1, c.partials.p);
-      cert_apply_M(c.V.p, c.SV.p);
-      launch_polish_grad(lc(all), c.V.p, c.SV.p, arow, nullptr, -1, 2, c.partials.p);
+      hooks.trial();
       launch_polish_reduce(st_, T_, 3, 0u, c.partials.p, c.h_sums, sched_.flag());
       wait_flag(sched_.last_seq());
       out.solve_ms += ms_since(t0);

@@ -24,18 +24,6 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
-// the two non-zero rows of B_k(p) = -hat(e_k) Y_p (cov.hip): B_k[r1] = Y_p[r2], B_k[r2] = -Y_p[r1]
-template <int D>
-__device__ __forceinline__ void rot_rows(int k, int &r1, int &r2) {
-  if (D == 3) {
-    r1 = k == 2 ? 0 : k + 1;
-    r2 = k == 0 ? 2 : k - 1;
-  } else {
-    r1 = 0;
-    r2 = 1;
-  }
-}
-
 template <int D>
 __global__ __launch_bounds__(SEG_ROWS) void k_polish_grad(const Seg *segs, NodeMask mask, const double *__restrict__ X,
                                                           const double *__restrict__ MX, int anchor, double *__restrict__ g,
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(SEG_ROWS) void k_polish_grad(const Seg *segs, NodeM
 #pragma unroll
     for (int k = 0; k < DOF - D; k++) {
       int r1, r2;
-      rot_rows<D>(k, r1, r2);
+      cov_rot_rows<D>(k, r1, r2);
       double v = 0;
 #pragma unroll
       for (int c = 0; c < D; c++) v = fma(x[D + r2 * D + c], mx[D + r1 * D + c], fma(-x[D + r1 * D + c], mx[D + r2 * D + c], v));

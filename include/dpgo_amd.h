@@ -538,7 +538,8 @@ int dpgo_group_cov_hessian(dpgo_group_t *grp, const double *X, int ld, int ancho
  * dpgo_graph_scale_edges by its weights (frozen at X), a trivial-loss group hosting every node of the scaled graph,
  * dpgo_group_covariance on it, everything released.  This is the covariance of the majorisation-minimisation SURROGATE
  * F_w at its fixed point X -- the information matrix a re-weighted least-squares solver would report -- NOT that of the
- * robust objective, whose true Hessian also has the derivative of the weights.  edge_summary may be NULL. */
+ * robust objective, whose true Hessian also has the derivative of the weights: dpgo_group_robust_covariance (below, behind the
+ * Newton polish) builds that one.  edge_summary may be NULL. */
 int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
                                      int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                      double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary);
@@ -646,6 +647,50 @@ typedef struct dpgo_polish_result {
 void dpgo_polish_options_default(dpgo_polish_options_t *opt);
 int dpgo_group_polish(dpgo_group_t *grp, const double *X, int ld, const dpgo_polish_options_t *opt, long long max_bytes,
                       double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result);
+
+/* ---- the robust objective: a Newton polish and covariances on its TRUE Hessian ---------------- */
+/* dpgo_group_polish and dpgo_group_covariance serve F = 1/2 tr(X^T M X).  Whoever optimised with a robust loss wants a critical
+ * point of   F(X) = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e)   (s_e, rho, the inter rule and delta = loss_reg as in
+ * dpgo_edge_eval_run) and the covariance its Hessian gives.  With w_e = rho'(s_e), c_e = 2 rho''(s_e) (Huber: 0 for s <= delta,
+ * -w / s above; Geman-McClure: -4 w / (s + delta); Welsch: -2 w / delta; 0 on intra edges, under loss 0 and where w_e == 0),
+ * M_e the data matrix of edge e (s_e = tr(X^T M_e X)) and g_e[dof p + a] = tr(E_a(p)^T (M_e X)_p) in the coordinates of
+ * dpgo_group_covariance:
+ *     M_w = sum_e w_e M_e,   g = sum_e w_e g_e,   H = H(S_w) + sum_inter c_e g_e g_e^T,   S_w = M_w - blkdiag(0, Lambda_w(X))
+ * where H(.) is the matrix of dpgo_group_covariance.  curvature = 1: this H; curvature = 0: without the rank-one terms -- the
+ * Hessian of the re-weighted problem, an IRLS-Newton step that converges linearly where curvature 1 converges quadratically.
+ * Everything is written on the device (robust.h: four fp64 kernels, fixed-order sums, the same bits run to run) into the
+ * covariance's factor: pattern, analysis and numeric context are shared with dpgo_group_polish / dpgo_group_covariance.
+ *
+ * grp is a TRIVIAL-LOSS group that HOSTS EVERY NODE of `graph`, as for every call above (-1 otherwise): the loss is an argument
+ * here.  graph must have the group's d and pose count and every edge must be a block of the group's pattern (-1 otherwise) --
+ * the graph the group was created from, as a rule.  -1 also on a loss outside 0..3, loss_reg not finite and positive under a
+ * robust loss, or a curvature outside {0, 1}.  The optimiser's state is not touched.
+ *
+ * dpgo_group_robust_polish: the loop, options, outcomes, log and timers of dpgo_group_polish with the robust F, M_w X and H;
+ *   F_initial / F_final are the robust F; edge_summary (optional) describes the final point.  SKIPPED by dpgo_group_polish's
+ *   rule with the per-edge arrays, M_w and the lists counted in; decided before anything is allocated.
+ * dpgo_group_robust_covariance: dpgo_group_covariance's factorisation, selected inversion and read-out on the robust H;
+ *   stationarity = |S_w X|_F (not computed for SKIPPED).  COV_NOT_PD is a legitimate answer where the negative curvature of the
+ *   loss wins.
+ * dpgo_group_robust_hessian (debug): the anchored H as dpgo_group_cov_hessian hands it out; optionally grad (dof N, by global
+ *   pose, zeros on the anchor), F, and per edge w, c, s_rot, s_trans and rho (num_edges each; every value of
+ *   dpgo_edge_eval_run's bit for bit).
+ * dpgo_group_robust_matrix (debug): M_w as dpgo_group_cert_matrix hands out S.
+ * dpgo_debug_robust_edge_host (no GPU): per edge w, c, rows (2 pose records: (M_e X)_i, (M_e X)_j, each t-row then d rows) and
+ *   ghat (2 dof: g_e at i, at j) through the kernels' own arithmetic; any output may be NULL. */
+int dpgo_group_robust_polish(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                             int curvature, const dpgo_polish_options_t *opt, long long max_bytes, double *Xout, int ldout,
+                             double *log, int log_cap, dpgo_polish_result_t *result, dpgo_edge_summary_t *edge_summary);
+int dpgo_group_robust_covariance(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                                 int curvature, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
+                                 double *cross, dpgo_cov_result_t *result);
+int dpgo_group_robust_hessian(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                              int curvature, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz,
+                              double *grad, double *F, double *w, double *c, double *s_rot, double *s_trans, double *rho);
+int dpgo_group_robust_matrix(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                             int *ptr, int *col, double *val, long long cap, long long *nnz);
+int dpgo_debug_robust_edge_host(const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg, double *w, double *c,
+                                double *rows, double *ghat);
 
 /* ---- the Riemannian staircase: escape a NEGATIVE certificate -------------------------------- */
 /* When dpgo_group_verify says NEGATIVE the point is a saddle or a local minimum of the rank-d problem, and the unit vector x it

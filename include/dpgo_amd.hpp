@@ -302,6 +302,46 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
+  // Newton polish of the ROBUST objective F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (dpgo_group_robust_polish): the loop of
+  // newton_polish with the robust F, gradient and Hessian written on the device.  This group is a trivial-loss group that hosts
+  // every node of its graph; the loss is an argument.  curvature 1: the true Hessian, with the curvature 2 rho'' of the loss;
+  // 0: the re-weighted one.  summary (optional) describes the final point.  Returns, status and the rest as newton_polish.
+  bool robust_newton_polish(const Matrix &X, Loss loss, double loss_reg, Matrix &Xout, dpgo_polish_result_t *result = nullptr,
+                            int *status = nullptr, int curvature = 1, const dpgo_polish_options_t *opt = nullptr,
+                            long long max_bytes = 0, std::vector<Scalar> *log = nullptr, dpgo_edge_summary_t *summary = nullptr) const {
+    dpgo_polish_options_t o;
+    dpgo_polish_options_default(&o);
+    if (opt) o = *opt;
+    Xout = X;
+    const int cap = o.max_steps >= 0 ? o.max_steps + 1 : 0;
+    if (log) log->assign((size_t)cap * 5, 0.0);
+    dpgo_polish_result_t r = {};
+    const int rc = dpgo_group_robust_polish(h_, graph_->handle(), X.data(), X.rows(), (int)loss, loss_reg, curvature, &o, max_bytes,
+                                            Xout.data(), Xout.rows(), log ? log->data() : nullptr, log ? cap : 0, &r, summary);
+    if (log) log->resize(rc == 0 && r.outcome != DPGO_POLISH_SKIPPED ? (size_t)std::min(cap, r.steps + 1) * 5 : 0);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
+  }
+  // Marginal covariances of the robust objective at X (dpgo_group_robust_covariance): marginal_covariances on the true Hessian
+  // (curvature 1) or the re-weighted one (0).  DPGO_COV_NOT_PD is a legitimate answer where the negative curvature of the loss
+  // wins.  Arguments, returns and status as marginal_covariances.
+  bool robust_marginal_covariances(const Matrix &X, Loss loss, double loss_reg, std::vector<Scalar> &marginals, int anchor = 0,
+                                   dpgo_cov_result_t *result = nullptr, int *status = nullptr, int curvature = 1,
+                                   const std::vector<int> *pairs = nullptr, std::vector<Scalar> *cross = nullptr,
+                                   long long max_bytes = 0) const {
+    const int d = graph_->d(), N = graph_->num_poses();
+    const int dof = d + d * (d - 1) / 2, npairs = pairs && cross ? (int)pairs->size() / 2 : 0;
+    marginals.assign((size_t)N * dof * dof, 0.0);
+    if (cross) cross->assign((size_t)npairs * dof * dof, 0.0);
+    dpgo_cov_result_t r = {};
+    const int rc = dpgo_group_robust_covariance(h_, graph_->handle(), X.data(), X.rows(), (int)loss, loss_reg, curvature, anchor,
+                                                max_bytes, npairs ? pairs->data() : nullptr, npairs, marginals.data(),
+                                                npairs ? cross->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_COV_OK;
+  }
   // The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- the reference's
   // truncated-Newton method at rank r, fast_verification at the lifted point, an escape along the certificate's direction one
   // rank up, until the certificate is not NEGATIVE or r = r_max <= 2d; then the rounding and a polish.  Xhat: the result, never
