@@ -330,6 +330,103 @@ def _fcol(X):
     return X, X.shape[0]
 
 
+_LLP = C.POINTER(C.c_longlong)
+
+
+def _dpn(a):
+    """_dp of an optional array."""
+    return None if a is None else _dp(a)
+
+
+def _dof(d):
+    """Tangent dimensions of a pose: d for the translation, d (d - 1) / 2 for the rotation."""
+    return d + d * (d - 1) // 2
+
+
+def _csr_args(A_csr, refactor_values=None):
+    """(n, ptr, col, val, val2) of a scipy matrix as the CSR-taking hooks read it: CSR with sorted indices, int32 and float64;
+    val2: refactor_values as float64, one value per stored entry of A, or None."""
+    A = A_csr.tocsr()
+    A.sort_indices()
+    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
+    val = np.ascontiguousarray(A.data, np.float64)
+    val2 = None
+    if refactor_values is not None:
+        val2 = np.ascontiguousarray(refactor_values, np.float64)
+        if val2.shape != val.shape:
+            raise ValueError("refactor_values must have one value per stored entry of A")
+    return A.shape[0], ptr, col, val, val2
+
+
+def _front_header(get, h):
+    """The first of a front-by-front hook's two calls: (sizes (8), status (4), pivots (4)); the arrays come with the second."""
+    sizes, status, piv = np.zeros(8, np.int64), np.zeros(4, np.int32), np.zeros(4)
+    get(h, sizes.ctypes.data_as(_LLP), _ip(status), _dp(piv), *[None] * 8)
+    return sizes, status, piv
+
+
+def _per_front(w, u, piv_idx, upd_idx):
+    """The flat pivot and update row lists of a factor, cut into one array per front (widths w, update rows u)."""
+    pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+    return ([piv_idx[pp[s]:pp[s + 1]].copy() for s in range(len(w))], [upd_idx[up[s]:up[s + 1]].copy() for s in range(len(w))])
+
+
+def _csr_out(n, what, call, fetch=None):
+    """A CSR matrix of n rows read back from the library: call(None, None, None, 0, nnz) asks for the number of entries,
+    fetch (default: call again) fills (ptr, col, val, cap, nnz).  Returns (ptr, col, val)."""
+    nnz = C.c_longlong(0)
+    if call(None, None, None, 0, C.byref(nnz)) != 0:
+        raise RuntimeError("%s failed" % what)
+    ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
+    if (fetch or call)(_ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
+        raise RuntimeError("%s failed" % what)
+    return ptr, col, val
+
+
+def _cert_args(X, what, eta, tau, max_iters, precondition, stop_on_negative, refresh_every, seed, V0=None):
+    """What certify, verify and verify_reweighted hand the library: (CertOptions, V0 or None, its pointer, its ld); V0 must
+    have the shape of X."""
+    o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
+                    stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
+    if V0 is None:
+        return o, None, None, 0
+    V0 = np.asarray(V0)
+    if V0.shape != X.shape:
+        raise ValueError("%s: V0 must have the shape of X, %r" % (what, X.shape))
+    V0, ldv0 = _fcol(V0)
+    return o, V0, _dp(V0), ldv0
+
+
+def _pairs_arg(pairs, num_poses, dof):
+    """The pairs of a covariance call and the arrays it fills: (marg (N, dof, dof), cross (npairs, dof, dof), the four
+    arguments pairs, npairs, marginals, cross of the C call).  pairs: None or (npairs, 2) global poses."""
+    P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    marg, cross = np.zeros((num_poses, dof, dof)), np.zeros((len(P), dof, dof))
+    return marg, cross, (_ip(P) if len(P) else None, len(P), _dp(marg), _dp(cross) if len(P) else None)
+
+
+def _pair_cov_arg(d, pairs, candidates):
+    """The pairs and candidates of a pair_covariance call and the arrays it fills: (gated, joint, rel, gate, the six
+    arguments pairs, npairs, candidates, joint, rel, gate of the C call)."""
+    dof = _dof(d)
+    P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    cand = None if candidates is None else pack_candidates(d, len(P), *candidates)
+    joint, rel, gate = np.zeros((len(P), 3, dof, dof)), np.zeros((len(P), dof, dof)), np.zeros((len(P), 2 + dof))
+    return cand is not None, joint, rel, gate, (_ip(P) if len(P) else None, len(P), _dpn(cand), _dp(joint), _dp(rel), _dp(gate))
+
+
+def _polish_arg(X, anchor, opts):
+    """What polish and robust_polish hand the library: (X, ld, PolishOptions, Xout starting as X, the log array)."""
+    X, ld = _fcol(X)
+    o = PolishOptions(anchor=int(anchor), **opts)
+    return X, ld, o, np.array(X, order="F"), np.zeros((max(int(o.max_steps), 0) + 1, 5))
+
+
+def _polish_log(log, r):
+    """The rows of the log a polish wrote: one per iteration, none for POLISH_SKIPPED."""
+    return log[:0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)].copy()
+
+
 class Graph:
     """Result of DPGO::read_g2o: measurements partitioned over num_nodes."""
 
@@ -495,14 +592,11 @@ def graph_from_edges(d, num_poses, I, J, R, t, kappa, tau, num_nodes):
 
 def spd_solve_host(A_csr, B, leaf=32):
     """Host multifrontal factor + solve (test hook for the solver set-up path)."""
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-    val = A.data.astype(np.float64)
+    n, ptr, col, val, _ = _csr_args(A_csr)
     X = np.ascontiguousarray(B, np.float64).copy()
     if X.ndim == 1:
         X = X[:, None]
-    if lib().dpgo_debug_spd_solve(A.shape[0], _ip(ptr), _ip(col), _dp(val), _dp(X), X.shape[1], leaf) != 0:
+    if lib().dpgo_debug_spd_solve(n, _ip(ptr), _ip(col), _dp(val), _dp(X), X.shape[1], leaf) != 0:
         raise RuntimeError("spd solve failed")
     return X
 
@@ -529,11 +623,9 @@ def prof_collect_operands():
 
 
 def spd_stats(A_csr, leaf):
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col, val = A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+    n, ptr, col, val, _ = _csr_args(A_csr)
     nnz, lv, mf = C.c_long(), C.c_int(), C.c_int()
-    if lib().dpgo_debug_spd_stats(A.shape[0], _ip(ptr), _ip(col), _dp(val), leaf, C.byref(nnz), C.byref(lv), C.byref(mf)) != 0:
+    if lib().dpgo_debug_spd_stats(n, _ip(ptr), _ip(col), _dp(val), leaf, C.byref(nnz), C.byref(lv), C.byref(mf)) != 0:
         raise RuntimeError("spd_stats failed")
     return nnz.value, lv.value, mf.value
 
@@ -551,27 +643,14 @@ def spd_factor_debug(A_csr, leaf, collapse=1, block=1, factor_only=False, refact
     the per-front arrays w, u, parent, height, ldw, ldm, w_off, wt_off, the lists piv_idx / upd_idx (one array per front),
     W / WT (flat, as SpdFactor holds them; None when the factorisation failed or factor_only), and with refactor_values
     status2, fail_front2, pivot_min2, pivot_max2, W2, WT2."""
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-    val = np.ascontiguousarray(A.data, np.float64)
-    val2 = None
-    if refactor_values is not None:
-        val2 = np.ascontiguousarray(refactor_values, np.float64)
-        if val2.shape != val.shape:
-            raise ValueError("refactor_values must have one value per stored entry of A")
-    n = A.shape[0]
+    n, ptr, col, val, val2 = _csr_args(A_csr, refactor_values)
     h = C.c_void_p()
-    if lib().dpgo_debug_spd_factor(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
-                                   int(collapse), int(block), int(bool(factor_only)), C.byref(h)) != 0:
+    if lib().dpgo_debug_spd_factor(n, _ip(ptr), _ip(col), _dp(val), _dpn(val2), int(leaf), int(collapse), int(block),
+                                   int(bool(factor_only)), C.byref(h)) != 0:
         raise RuntimeError("spd_factor_debug failed")
     try:
         get = lib().dpgo_debug_spd_factor_get
-        sizes = np.zeros(8, np.int64)
-        status = np.zeros(4, np.int32)
-        piv = np.zeros(4)
-        LLP = C.POINTER(C.c_longlong)
-        get(h, sizes.ctypes.data_as(LLP), _ip(status), _dp(piv), None, None, None, None, None, None, None, None)
+        sizes, status, piv = _front_header(get, h)
         nt = int(sizes[0])
         fronts = np.zeros((nt, 6), np.int32)
         offs = np.zeros((nt, 2), np.int64)
@@ -582,17 +661,16 @@ def spd_factor_debug(A_csr, leaf, collapse=1, block=1, factor_only=False, refact
         W2 = np.zeros(int(sizes[2])) if sizes[5] else None
         WT2 = np.zeros(int(sizes[3])) if sizes[5] else None
         opt = lambda a: None if a is None or a.size == 0 else _dp(a)
-        get(h, None, None, None, _ip(fronts), offs.ctypes.data_as(LLP), _ip(piv_idx), _ip(upd_idx), opt(W), opt(WT), opt(W2),
+        get(h, None, None, None, _ip(fronts), offs.ctypes.data_as(_LLP), _ip(piv_idx), _ip(upd_idx), opt(W), opt(WT), opt(W2),
             opt(WT2))
     finally:
         lib().dpgo_debug_spd_factor_free(h)
     w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
-    pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+    piv_lists, upd_lists = _per_front(w, u, piv_idx, upd_idx)
     out = {"status": int(status[0]), "fail_front": int(status[1]), "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
            "on_device": bool(sizes[7]), "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(),
            "height": fronts[:, 3].copy(), "ldw": fronts[:, 4].copy(), "ldm": fronts[:, 5].copy(), "w_off": offs[:, 0].copy(),
-           "wt_off": offs[:, 1].copy(), "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
-           "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)], "W": W, "WT": WT}
+           "wt_off": offs[:, 1].copy(), "piv_idx": piv_lists, "upd_idx": upd_lists, "W": W, "WT": WT}
     if sizes[6]:
         out.update(status2=int(status[2]), fail_front2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
                    W2=W2, WT2=WT2)
@@ -610,46 +688,31 @@ def spd_selinv_debug(A_csr, leaf, collapse=1, block=1, host=False, refactor_valu
     the (w + u) x (w + u) block of A^-1 on [pivots; update rows], None when not inverted), sigma_again (a second call's),
     W_before / W_after (the factor's W ahead of the inversion and from a factorisation of the same values behind it), and
     with refactor_values status2, selinv_status2, pivot_min2, pivot_max2, sigma2."""
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-    val = np.ascontiguousarray(A.data, np.float64)
-    val2 = None
-    if refactor_values is not None:
-        val2 = np.ascontiguousarray(refactor_values, np.float64)
-        if val2.shape != val.shape:
-            raise ValueError("refactor_values must have one value per stored entry of A")
-    n = A.shape[0]
+    n, ptr, col, val, val2 = _csr_args(A_csr, refactor_values)
     h = C.c_void_p()
-    if lib().dpgo_debug_spd_selinv(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
-                                   int(collapse), int(block), int(bool(host)), C.byref(h)) != 0:
+    if lib().dpgo_debug_spd_selinv(n, _ip(ptr), _ip(col), _dp(val), _dpn(val2), int(leaf), int(collapse), int(block),
+                                   int(bool(host)), C.byref(h)) != 0:
         raise RuntimeError("spd_selinv_debug failed")
     try:
         get = lib().dpgo_debug_spd_selinv_get
-        sizes = np.zeros(8, np.int64)
-        status = np.zeros(4, np.int32)
-        piv = np.zeros(4)
-        LLP = C.POINTER(C.c_longlong)
-        get(h, sizes.ctypes.data_as(LLP), _ip(status), _dp(piv), None, None, None, None, None, None, None, None)
+        sizes, status, piv = _front_header(get, h)
         nt = int(sizes[0])
         fronts = np.zeros((nt, 4), np.int32)
         piv_idx = np.zeros(n, np.int32)
         upd_idx = np.zeros(max(int(sizes[1]), 1), np.int32)
         flat = [np.zeros(int(sizes[k])) if sizes[k] else None for k in (3, 4, 5, 6, 6)]
-        opt = lambda a: None if a is None else _dp(a)
-        get(h, None, None, None, _ip(fronts), _ip(piv_idx), _ip(upd_idx), *[opt(a) for a in flat])
+        get(h, None, None, None, _ip(fronts), _ip(piv_idx), _ip(upd_idx), *[_dpn(a) for a in flat])
     finally:
         lib().dpgo_debug_spd_selinv_free(h)
     w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
-    pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+    piv_lists, upd_lists = _per_front(w, u, piv_idx, upd_idx)
     m = (w + u).astype(np.int64)
     so = np.concatenate([[0], np.cumsum(m * m)])
     blocks = lambda a: None if a is None else [a[so[s]:so[s + 1]].reshape(m[s], m[s]) for s in range(nt)]
     out = {"status": int(status[0]), "selinv_status": int(status[1]), "pivot_min": float(piv[0]), "pivot_max": float(piv[1]),
            "on_device": bool(sizes[7]), "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(), "depth": fronts[:, 3].copy(),
-           "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
-           "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)],
-           "sigma": blocks(flat[0]), "sigma_again": blocks(flat[1]), "W_before": flat[3], "W_after": flat[4]}
+           "piv_idx": piv_lists, "upd_idx": upd_lists, "sigma": blocks(flat[0]), "sigma_again": blocks(flat[1]),
+           "W_before": flat[3], "W_after": flat[4]}
     if refactor_values is not None:
         out.update(status2=int(status[2]), selinv_status2=int(status[3]), pivot_min2=float(piv[2]), pivot_max2=float(piv[3]),
                    sigma2=blocks(flat[2]))
@@ -666,26 +729,18 @@ def spd_vsolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor
     Returns a dict: status (0; 1: not positive definite, and then nothing was solved), on_device, pivot_min, pivot_max, out (the
     solution, None when not solved), out_again (a second call's), raw (the 3 n doubles the hook was handed, filled with `fill`
     first -- what it did not write is still there), and with refactor_values status2, pivot_min2, pivot_max2, out2."""
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-    val = np.ascontiguousarray(A.data, np.float64)
-    n = A.shape[0]
+    n = A_csr.shape[0]
     b = np.ascontiguousarray(rhs, np.float64)
     if b.shape != (n,):
         raise ValueError("rhs must have one entry per unknown")
-    val2 = None
-    if refactor_values is not None:
-        val2 = np.ascontiguousarray(refactor_values, np.float64)
-        if val2.shape != val.shape:
-            raise ValueError("refactor_values must have one value per stored entry of A")
+    n, ptr, col, val, val2 = _csr_args(A_csr, refactor_values)
     raw = np.full(3 * n, VSOLVE_FILL)
     status = np.zeros(2, np.int32)
     piv = np.zeros(4)
     before = lib().dpgo_debug_spd_vsolve_chunk(int(chunk)) if chunk is not None else None
     try:
-        rc = lib().dpgo_debug_spd_vsolve(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
-                                         int(collapse), int(block), int(bool(host)), _dp(b), _dp(raw), _ip(status), _dp(piv))
+        rc = lib().dpgo_debug_spd_vsolve(n, _ip(ptr), _ip(col), _dp(val), _dpn(val2), int(leaf), int(collapse), int(block),
+                                         int(bool(host)), _dp(b), _dp(raw), _ip(status), _dp(piv))
     finally:
         if before is not None:
             lib().dpgo_debug_spd_vsolve_chunk(before)
@@ -715,11 +770,7 @@ def spd_msolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor
     solution n x k, None when not solved), out_again (a second call's), raw (3 x n x ldx: the arrays the hook was handed,
     filled with VSOLVE_FILL first -- what it did not write is still there, the columns k ... ldx on the device included), and
     with refactor_values status2, pivot_min2, pivot_max2, out2."""
-    A = A_csr.tocsr()
-    A.sort_indices()
-    ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-    val = np.ascontiguousarray(A.data, np.float64)
-    n = A.shape[0]
+    n = A_csr.shape[0]
     b = np.ascontiguousarray(rhs, np.float64)
     if b.ndim != 2 or b.shape[0] != n or b.shape[1] < 1:
         raise ValueError("rhs must be n x k with k >= 1")
@@ -727,17 +778,13 @@ def spd_msolve_debug(A_csr, rhs, leaf, collapse=1, block=1, host=False, refactor
     ldx = k if ldx is None else int(ldx)
     if ldx < k:
         raise ValueError("ldx must be at least k")
-    val2 = None
-    if refactor_values is not None:
-        val2 = np.ascontiguousarray(refactor_values, np.float64)
-        if val2.shape != val.shape:
-            raise ValueError("refactor_values must have one value per stored entry of A")
+    n, ptr, col, val, val2 = _csr_args(A_csr, refactor_values)
     raw = np.full((3, n, ldx), VSOLVE_FILL)
     status = np.zeros(2, np.int32)
     piv = np.zeros(4)
-    rc = lib().dpgo_debug_spd_msolve(n, _ip(ptr), _ip(col), _dp(val), None if val2 is None else _dp(val2), int(leaf),
-                                     int(collapse), int(block), int(bool(host)), 0 if chunk is None else int(chunk), _dp(b), k,
-                                     ldx, _dp(raw), _ip(status), _dp(piv))
+    rc = lib().dpgo_debug_spd_msolve(n, _ip(ptr), _ip(col), _dp(val), _dpn(val2), int(leaf), int(collapse), int(block),
+                                     int(bool(host)), 0 if chunk is None else int(chunk), _dp(b), k, ldx, _dp(raw), _ip(status),
+                                     _dp(piv))
     if rc < 0:
         raise RuntimeError("spd_msolve_debug failed")
     ok = status[0] == 0
@@ -762,11 +809,7 @@ class SpdSolverDebug:
     refactor()  new values through the kept numeric context, then repack() (keep_numeric=True only)"""
 
     def __init__(self, A_csr, leaf, collapse=1, block=1, d=3, dof=1, node_of_unknown=None, keep_numeric=False):
-        A = A_csr.tocsr()
-        A.sort_indices()
-        n = A.shape[0]
-        ptr, col = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-        val = np.ascontiguousarray(A.data, np.float64)
+        n, ptr, col, val, _ = _csr_args(A_csr)
         node = np.zeros(n, np.int32) if node_of_unknown is None else np.ascontiguousarray(node_of_unknown, np.int32)
         if node.shape != (n,):
             raise ValueError("node_of_unknown must have one entry per unknown")
@@ -789,10 +832,9 @@ class SpdSolverDebug:
 
     def plan(self):
         get = lib().dpgo_debug_spd_solver_plan
-        LLP = C.POINTER(C.c_longlong)
         sizes = np.zeros(8, np.int64)
         flags = np.zeros(8, np.int32)
-        get(self._h, sizes.ctypes.data_as(LLP), _ip(flags), None, None, None, None, None)
+        get(self._h, sizes.ctypes.data_as(_LLP), _ip(flags), None, None, None, None, None)
         nt, nupd, nf, nb, nn = (int(v) for v in sizes[:5])
         L = nf + nb + 3
         levels = np.zeros((L, 3), np.int32)
@@ -804,13 +846,12 @@ class SpdSolverDebug:
         lv = [dict(rows=int(levels[l, 0]), nwide=int(levels[l, 1]), nnarrow=int(levels[l, 2]), wcount=counts[l, :, 0].copy(),
                    ncount=counts[l, :, 1].copy()) for l in range(L)]
         w, u = fronts[:, 0].copy(), fronts[:, 1].copy()
-        pp, up = np.concatenate([[0], np.cumsum(w)]), np.concatenate([[0], np.cumsum(u)])
+        piv_lists, upd_lists = _per_front(w, u, piv_idx, upd_idx)
         return {"fused_root": bool(flags[0]), "root_sym": bool(flags[1]), "root_rows": int(flags[2]),
                 "root_fine_rows": int(flags[3]), "root_fine_below": int(flags[4]), "stream_once": bool(flags[5]),
                 "nnodes": nn, "fwd": lv[:nf], "bwd": lv[nf:nf + nb], "root": lv[-3], "root_fine": lv[-2], "root_rows_level": lv[-1],
                 "nfronts": nt, "w": w, "u": u, "parent": fronts[:, 2].copy(), "height": fronts[:, 3].copy(),
-                "piv_idx": [piv_idx[pp[s]:pp[s + 1]].copy() for s in range(nt)],
-                "upd_idx": [upd_idx[up[s]:up[s + 1]].copy() for s in range(nt)]}
+                "piv_idx": piv_lists, "upd_idx": upd_lists}
 
     def fine_root_for(self, nodes):
         return bool(lib().dpgo_debug_spd_solver_fine_root(self._h, int(nodes)))
@@ -1062,15 +1103,7 @@ class NodeGroup:
         critical point.  The group must have the trivial loss and host every node; the optimiser's state is untouched.
         V0: the initial block ((d+1)N x d), default seeded Gaussians."""
         X, ld = _fcol(X)
-        o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
-                        stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
-        v0, ldv0 = None, 0
-        if V0 is not None:
-            V0 = np.asarray(V0)
-            if V0.shape != X.shape:
-                raise ValueError("certify: V0 must have the shape of X, %r" % (X.shape,))
-            V0, ldv0 = _fcol(V0)
-            v0 = _dp(V0)
+        o, V0, v0, ldv0 = _cert_args(X, "certify", eta, tau, max_iters, precondition, stop_on_negative, refresh_every, seed, V0)
         res = CertResult()
         x = np.zeros(X.shape[0])
         if lib().dpgo_group_certify(self._h, _dp(X), ld, C.byref(o), v0, ldv0, C.byref(res), _dp(x), x.shape[0]) != 0:
@@ -1099,15 +1132,7 @@ class NodeGroup:
         floating-point statement about S(X) and means "global minimum" only where stationarity is small (the header
         include/dpgo_amd.h has the warning example)."""
         X, ld = _fcol(X)
-        o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
-                        stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
-        v0, ldv0 = None, 0
-        if V0 is not None:
-            V0 = np.asarray(V0)
-            if V0.shape != X.shape:
-                raise ValueError("verify: V0 must have the shape of X, %r" % (X.shape,))
-            V0, ldv0 = _fcol(V0)
-            v0 = _dp(V0)
+        o, V0, v0, ldv0 = _cert_args(X, "verify", eta, tau, max_iters, precondition, stop_on_negative, refresh_every, seed, V0)
         res, f = CertResult(), CertFactor()
         x = np.zeros(X.shape[0])
         if lib().dpgo_group_verify(self._h, _dp(X), ld, C.byref(o), int(max_factor_bytes), v0, ldv0, C.byref(res), _dp(x),
@@ -1120,14 +1145,8 @@ class NodeGroup:
         unknowns (d+1) g + r of the global poses g (r = 0 the translation, r = 1..d the rows of Y_g), every stored
         (d+1) x (d+1) block dense."""
         X, ld = _fcol(X)
-        nnz = C.c_longlong(0)
-        if lib().dpgo_group_cert_matrix(self._h, _dp(X), ld, float(eta), None, None, None, 0, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_cert_matrix failed")
-        n = (self.d + 1) * self.graph.num_poses
-        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
-        if lib().dpgo_group_cert_matrix(self._h, _dp(X), ld, float(eta), _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_cert_matrix failed")
-        return ptr, col, val
+        return _csr_out((self.d + 1) * self.graph.num_poses, "dpgo_group_cert_matrix",
+                        lambda *csr: lib().dpgo_group_cert_matrix(self._h, _dp(X), ld, float(eta), *csr))
 
     def covariance(self, X, anchor=0, pairs=None, max_bytes=0):
         """Marginal pose covariances at X (dpgo_group_covariance): the inverse of the Riemannian Hessian in tangent
@@ -1139,13 +1158,9 @@ class NodeGroup:
         (the analysis predicts more device bytes than max_bytes, when > 0, or than half of what is free: nothing of the
         factor was allocated, the predicted sizes are filled in)."""
         X, ld = _fcol(X)
-        dof = self.d + self.d * (self.d - 1) // 2
-        P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
-        marg = np.zeros((self.graph.num_poses, dof, dof))
-        cross = np.zeros((len(P), dof, dof))
+        marg, cross, pair_args = _pairs_arg(pairs, self.graph.num_poses, _dof(self.d))
         r = CovResult()
-        if lib().dpgo_group_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P),
-                                       _dp(marg), _dp(cross) if len(P) else None, C.byref(r)) != 0:
+        if lib().dpgo_group_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), *pair_args, C.byref(r)) != 0:
             raise RuntimeError("dpgo_group_covariance failed (robust loss, a group that does not host every node, an anchor or "
                                "pair outside the graph, a pair that is not an edge, or bad sizes)")
         return marg, cross, r
@@ -1163,18 +1178,12 @@ class NodeGroup:
         (zero outputs) or PAIRS_SKIPPED (more device bytes than max_bytes, when > 0, or than half of what is free).  No block
         of a selected inversion is stored: this may run where covariance is SKIPPED."""
         X, ld = _fcol(X)
-        d = self.d
-        dof = d + d * (d - 1) // 2
-        P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
-        cand = None if candidates is None else pack_candidates(d, len(P), *candidates)
-        joint, rel = np.zeros((len(P), 3, dof, dof)), np.zeros((len(P), dof, dof))
-        gate = np.zeros((len(P), 2 + dof))
+        gated, joint, rel, gate, pair_args = _pair_cov_arg(self.d, pairs, candidates)
         r = PairsResult()
-        if lib().dpgo_group_pair_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P),
-                                            None if cand is None else _dp(cand), _dp(joint), _dp(rel), _dp(gate), C.byref(r)) != 0:
+        if lib().dpgo_group_pair_covariance(self._h, _dp(X), ld, int(anchor), int(max_bytes), *pair_args, C.byref(r)) != 0:
             raise RuntimeError("dpgo_group_pair_covariance failed (robust loss, a group that does not host every node, an anchor "
                                "or pose outside the graph, a candidate weight that is not positive, or bad sizes)")
-        return pairs_output(joint, rel, gate, r, cand is not None, threshold)
+        return pairs_output(joint, rel, gate, r, gated, threshold)
 
     def polish(self, X, anchor=0, max_bytes=0, **opts):
         """Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored
@@ -1184,17 +1193,13 @@ class NodeGroup:
         grad_tol 0).  Returns (Xout, PolishResult, log): the new point (X itself for POLISH_SKIPPED), the result struct, and
         one row per iteration of (F0, |g|, mu at entry, rho of the accepted try, tries).  The optimiser's state is not
         touched."""
-        X, ld = _fcol(X)
-        o = PolishOptions(anchor=int(anchor), **opts)
-        Xout = np.array(X, order="F")
-        log = np.zeros((max(int(o.max_steps), 0) + 1, 5))
+        X, ld, o, Xout, log = _polish_arg(X, anchor, opts)
         r = PolishResult()
         if lib().dpgo_group_polish(self._h, _dp(X), ld, C.byref(o), int(max_bytes), _dp(Xout), Xout.shape[0], _dp(log), len(log),
                                    C.byref(r)) != 0:
             raise RuntimeError("dpgo_group_polish failed (robust loss, a group that does not host every node, an anchor outside "
                                "the graph, or bad sizes or options)")
-        rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
-        return Xout, r, log[:rows].copy()
+        return Xout, r, _polish_log(log, r)
 
     def robust_polish(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, max_bytes=0, graph=None, **opts):
         """Newton polish of the ROBUST objective F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (dpgo_group_robust_polish):
@@ -1202,32 +1207,24 @@ class NodeGroup:
         curvature 2 rho'' of the loss (quadratic convergence); 0: the re-weighted one (an IRLS-Newton step, linear).  The group is
         a trivial-loss group that hosts every node; graph (default: the group's own) gives the edges and the inter rule.
         Returns (Xout, PolishResult, log, EdgeSummary of the final point): as `polish`, the F fields the robust F."""
-        X, ld = _fcol(X)
-        o = PolishOptions(anchor=int(anchor), **opts)
-        Xout = np.array(X, order="F")
-        log = np.zeros((max(int(o.max_steps), 0) + 1, 5))
+        X, ld, o, Xout, log = _polish_arg(X, anchor, opts)
         r, sm = PolishResult(), EdgeSummary()
         if lib().dpgo_group_robust_polish(self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature),
                                           C.byref(o), int(max_bytes), _dp(Xout), Xout.shape[0], _dp(log), len(log), C.byref(r),
                                           C.byref(sm)) != 0:
             raise RuntimeError("dpgo_group_robust_polish failed (a robust-loss group, a group that does not host every node, a graph "
                                "that is not the group's, a bad loss, loss_reg, curvature or anchor, or bad sizes or options)")
-        rows = 0 if r.outcome == POLISH_SKIPPED else min(len(log), r.steps + 1)
-        return Xout, r, log[:rows].copy(), sm
+        return Xout, r, _polish_log(log, r), sm
 
     def robust_covariance(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, pairs=None, max_bytes=0, graph=None):
         """Marginal pose covariances of the ROBUST objective at X (dpgo_group_robust_covariance): `covariance` on the true
         Hessian (curvature 1) or the re-weighted one (curvature 0).  COV_NOT_PD is a legitimate answer where the negative
         curvature of the loss wins.  Returns (marginals, cross, CovResult) as `covariance`; stationarity = |S_w X|_F."""
         X, ld = _fcol(X)
-        dof = self.d + self.d * (self.d - 1) // 2
-        P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
-        marg = np.zeros((self.graph.num_poses, dof, dof))
-        cross = np.zeros((len(P), dof, dof))
+        marg, cross, pair_args = _pairs_arg(pairs, self.graph.num_poses, _dof(self.d))
         r = CovResult()
         if lib().dpgo_group_robust_covariance(self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature),
-                                              int(anchor), int(max_bytes), _ip(P) if len(P) else None, len(P), _dp(marg),
-                                              _dp(cross) if len(P) else None, C.byref(r)) != 0:
+                                              int(anchor), int(max_bytes), *pair_args, C.byref(r)) != 0:
             raise RuntimeError("dpgo_group_robust_covariance failed (a robust-loss group, a group that does not host every node, a "
                                "graph that is not the group's, a bad loss, loss_reg, curvature, anchor or pair, or bad sizes)")
         return marg, cross, r
@@ -1239,32 +1236,22 @@ class NodeGroup:
         every edge are appended as an eighth item -- what EdgeEval.run returns, bit for bit."""
         X, ld = _fcol(X)
         g_ = graph or self.graph
-        dof = self.d + self.d * (self.d - 1) // 2
-        nnz = C.c_longlong(0)
+        n = _dof(self.d) * self.graph.num_poses
         args = (self._h, g_._h, _dp(X), ld, int(loss), float(loss_reg), int(curvature), int(anchor))
-        if lib().dpgo_group_robust_hessian(*args, None, None, None, 0, C.byref(nnz), None, None, None, None, None, None, None) != 0:
-            raise RuntimeError("dpgo_group_robust_hessian failed")
-        n = dof * self.graph.num_poses
-        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
         g, F, w, c = np.zeros(n), C.c_double(0), np.zeros(g_.num_edges), np.zeros(g_.num_edges)
         per = [np.zeros(g_.num_edges) for _ in range(3)]
-        if lib().dpgo_group_robust_hessian(*args, _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz), _dp(g), C.byref(F), _dp(w),
-                                           _dp(c), *[_dp(a) for a in per]) != 0:
-            raise RuntimeError("dpgo_group_robust_hessian failed")
+        ptr, col, val = _csr_out(n, "dpgo_group_robust_hessian",
+                                 lambda *csr: lib().dpgo_group_robust_hessian(*args, *csr, *[None] * 7),
+                                 lambda *csr: lib().dpgo_group_robust_hessian(*args, *csr, _dp(g), C.byref(F), _dp(w), _dp(c),
+                                                                              *[_dp(a) for a in per]))
         return (ptr, col, val, g, F.value, w, c) + ((tuple(per),) if edges else ())
 
     def robust_matrix(self, X, loss, loss_reg=0.25, graph=None):
         """Debug: M_w = sum_e w_e(X) M_e as the device wrote it (dpgo_group_robust_matrix): CSR as `cert_matrix` hands out S."""
         X, ld = _fcol(X)
-        nnz = C.c_longlong(0)
         args = (self._h, (graph or self.graph)._h, _dp(X), ld, int(loss), float(loss_reg))
-        if lib().dpgo_group_robust_matrix(*args, None, None, None, 0, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_robust_matrix failed")
-        n = (self.d + 1) * self.graph.num_poses
-        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
-        if lib().dpgo_group_robust_matrix(*args, _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_robust_matrix failed")
-        return ptr, col, val
+        return _csr_out((self.d + 1) * self.graph.num_poses, "dpgo_group_robust_matrix",
+                        lambda *csr: lib().dpgo_group_robust_matrix(*args, *csr))
 
     def staircase(self, X, max_bytes=0, **opts):
         """The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- TNT at
@@ -1334,15 +1321,8 @@ class NodeGroup:
         val) on the unknowns dof g + a of the global poses g, every stored dof x dof block dense, the anchor's row and
         column those of the identity."""
         X, ld = _fcol(X)
-        dof = self.d + self.d * (self.d - 1) // 2
-        nnz = C.c_longlong(0)
-        if lib().dpgo_group_cov_hessian(self._h, _dp(X), ld, int(anchor), None, None, None, 0, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_cov_hessian failed")
-        n = dof * self.graph.num_poses
-        ptr, col, val = np.zeros(n + 1, np.int32), np.zeros(nnz.value, np.int32), np.zeros(nnz.value)
-        if lib().dpgo_group_cov_hessian(self._h, _dp(X), ld, int(anchor), _ip(ptr), _ip(col), _dp(val), nnz.value, C.byref(nnz)) != 0:
-            raise RuntimeError("dpgo_group_cov_hessian failed")
-        return ptr, col, val
+        return _csr_out(_dof(self.d) * self.graph.num_poses, "dpgo_group_cov_hessian",
+                        lambda *csr: lib().dpgo_group_cov_hessian(self._h, _dp(X), ld, int(anchor), *csr))
 
     def cert_lambda(self, X):
         """compute_Lambda_blocks (SESyncProblem.cpp:375-395): the N symmetric d x d blocks of Lambda(X), (N, d, d)."""
@@ -1966,7 +1946,7 @@ def pairs_gate_debug(d, recp, recq, joint, candidate=None):
     """The arithmetic of one pair on the host (test hook, dpgo_debug_pairs_gate; no device), the code the device runs per
     pair.  recp / recq: the pose records ((d + 1) x d: t, then R^T); joint (3, dof, dof); candidate: None or (R, t, kappa,
     tau).  Returns (rel, None) or (rel, (d2, not_pd, residual))."""
-    dof = d + d * (d - 1) // 2
+    dof = _dof(d)
     recp, recq = np.ascontiguousarray(recp, np.float64), np.ascontiguousarray(recq, np.float64)
     joint = np.ascontiguousarray(joint, np.float64)
     if recp.size != (d + 1) * d or recq.size != (d + 1) * d or joint.size != 3 * dof * dof:
@@ -2253,7 +2233,7 @@ def robust_edge_debug(graph, X, loss=LOSS_NONE, loss_reg=0.25):
     (M_e X)_j (row 0 the translation's, then the rows of Y), and the tangent gradients (m, 2, dof) of the edge at i and j."""
     X, ld = _fcol(X)
     d, m = graph.d, graph.num_edges
-    dof = d + d * (d - 1) // 2
+    dof = _dof(d)
     w, c, rows, gh = np.zeros(m), np.zeros(m), np.zeros((m, 2, d + 1, d)), np.zeros((m, 2, dof))
     if lib().dpgo_debug_robust_edge_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), _dp(w), _dp(c), _dp(rows), _dp(gh)) != 0:
         raise ValueError("dpgo_debug_robust_edge_host failed (a short X, an unknown loss, or a bad loss_reg)")
@@ -2268,8 +2248,7 @@ def verify_reweighted(graph, X, loss, loss_reg=0.25, eta=1e-3, tau=1e-6, max_ite
     the global minimiser of its own quadratic surrogate -- a fixed point of an exact MM step -- NOT that it is the global
     minimum of the robust objective (include/dpgo_amd.h)."""
     X, ld = _fcol(X)
-    o = CertOptions(eta=eta, tau=tau, max_iters=int(max_iters), precondition=int(bool(precondition)),
-                    stop_on_negative=int(bool(stop_on_negative)), refresh_every=int(refresh_every), seed=int(seed))
+    o = _cert_args(X, "verify_reweighted", eta, tau, max_iters, precondition, stop_on_negative, refresh_every, seed)[0]
     res, f, s = CertResult(), CertFactor(), EdgeSummary()
     x = np.zeros(X.shape[0])
     if lib().dpgo_graph_verify_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), C.byref(o),
@@ -2284,14 +2263,10 @@ def covariance_reweighted(graph, X, loss, loss_reg=0.25, anchor=0, pairs=None, m
     graph.  Returns (marginals, cross, CovResult, EdgeSummary).  This is the covariance of the MM surrogate at its fixed
     point, NOT of the robust objective (include/dpgo_amd.h)."""
     X, ld = _fcol(X)
-    d = graph.d
-    dof = d + d * (d - 1) // 2
-    P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
-    marg, cross = np.zeros((graph.num_poses, dof, dof)), np.zeros((len(P), dof, dof))
+    marg, cross, pair_args = _pairs_arg(pairs, graph.num_poses, _dof(graph.d))
     r, s = CovResult(), EdgeSummary()
     if lib().dpgo_graph_covariance_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), int(anchor),
-                                              int(max_bytes), _ip(P) if len(P) else None, len(P), _dp(marg),
-                                              _dp(cross) if len(P) else None, C.byref(r), C.byref(s)) != 0:
+                                              int(max_bytes), *pair_args, C.byref(r), C.byref(s)) != 0:
         raise RuntimeError("dpgo_graph_covariance_reweighted failed (no HIP device, a short X, a bad loss, or a pair that is no edge)")
     return marg, cross, r, s
 
@@ -2301,18 +2276,12 @@ def pair_covariance_reweighted(graph, X, loss, pairs, loss_reg=0.25, anchor=0, c
     """NodeGroup.pair_covariance for the RE-WEIGHTED problem at X (dpgo_graph_pair_covariance_reweighted), by
     covariance_reweighted's recipe and with its caveat.  Returns pair_covariance's dict with summary (EdgeSummary) added."""
     X, ld = _fcol(X)
-    d = graph.d
-    dof = d + d * (d - 1) // 2
-    P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
-    cand = None if candidates is None else pack_candidates(d, len(P), *candidates)
-    joint, rel, gate = np.zeros((len(P), 3, dof, dof)), np.zeros((len(P), dof, dof)), np.zeros((len(P), 2 + dof))
+    gated, joint, rel, gate, pair_args = _pair_cov_arg(graph.d, pairs, candidates)
     r, s = PairsResult(), EdgeSummary()
     if lib().dpgo_graph_pair_covariance_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), int(anchor),
-                                                   int(max_bytes), _ip(P) if len(P) else None, len(P),
-                                                   None if cand is None else _dp(cand), _dp(joint), _dp(rel), _dp(gate),
-                                                   C.byref(r), C.byref(s)) != 0:
+                                                   int(max_bytes), *pair_args, C.byref(r), C.byref(s)) != 0:
         raise RuntimeError("dpgo_graph_pair_covariance_reweighted failed (no HIP device, a short X, a bad loss, a pose outside the "
                            "graph, or a candidate weight that is not positive)")
-    out = pairs_output(joint, rel, gate, r, cand is not None, threshold)
+    out = pairs_output(joint, rel, gate, r, gated, threshold)
     out["summary"] = s
     return out

@@ -1,74 +1,26 @@
-// C ABI (include/dpgo_amd.h) over the C++ host layer.
-#include "../../include/dpgo_amd.h"
+// C ABI (include/dpgo_amd.h) over the C++ host layer: the public entry points -- graphs, groups, the exchange, PCM, the
+// certificate, covariances, the polish, the staircase -- and nothing that touches the device itself.  The test hooks
+// (dpgo_debug_*, dpgo_group_debug_*) are in capi_debug.cpp; what both files share is in capi_util.h.
+#include "capi_util.h"
 
 #include <memory>
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <exception>
+#include <functional>
 #include <map>
 #include <numeric>
 #include <set>
 
 #include "cert.h"
 #include "comm.h"
-#include "edges.h"
-#include "group.h"
-#include "pairs_math.h"
 #include "pcm.h"
 
 namespace dpgo {
 int chordal_initialization(const Graph &g, double *X, int ld);
 }
 
-// No exception leaves the library: a failed HIP call (dpgo::DeviceError) or an allocation failure becomes the
-// reference's `return -1` (+ a line on stderr), never abort() / terminate() in the host process.
-template <class F>
-static int guarded(F &&f) {
-  try {
-    return f();
-  } catch (const std::exception &e) {
-    fprintf(stderr, "[dpgo_amd] ERROR: %s\n", e.what());
-    return -1;
-  } catch (...) {
-    fprintf(stderr, "[dpgo_amd] ERROR: unknown exception\n");
-    return -1;
-  }
-}
-
-struct dpgo_graph {
-  dpgo::Graph g;
-};
-struct dpgo_group {
-  dpgo::Group *grp = nullptr;
-  std::vector<int> all;
-};
-struct dpgo_comm {
-  dpgo::Comm *c = nullptr;
-};
-
-static dpgo::Options to_cpp(const dpgo_options_t &o) {
-  dpgo::Options r;
-  r.scheme = o.scheme; r.regularizer = o.regularizer; r.accepted_delta = o.accepted_delta;
-  r.eta[0] = o.eta[0]; r.eta[1] = o.eta[1]; r.psi = o.psi; r.phi = o.phi;
-  r.max_soft_restart_hits[0] = o.max_soft_restart_hits[0]; r.max_soft_restart_hits[1] = o.max_soft_restart_hits[1];
-  r.oscillation_cnt_period = o.oscillation_cnt_period; r.max_oscillations = o.max_oscillations;
-  r.loss = o.loss; r.loss_reg = o.loss_reg; r.rescale = o.rescale; r.max_rescale_count = o.max_rescale_count;
-  r.grad_norm_tol = o.grad_norm_tol;
-  r.rel_func_decrease_tol = o.rel_func_decrease_tol; r.stepsize_tol = o.stepsize_tol;
-  r.max_iterations = o.max_iterations; r.max_iterations_accepted = o.max_iterations_accepted;
-  r.reg_Cholesky_precon_max_condition_number = o.reg_Cholesky_precon_max_condition_number;
-  r.preconditioned_grad_norm_tol = o.preconditioned_grad_norm_tol; r.max_tCG_iterations = o.max_tCG_iterations;
-  r.STPCG_kappa = o.STPCG_kappa; r.STPCG_theta = o.STPCG_theta; r.preconditioner = o.preconditioner;
-  r.verbose = o.verbose;
-  return r;
-}
-
-extern "C" {
-
-void dpgo_options_default(dpgo_options_t *o) {
-  const dpgo::Options d;
+static void to_c(const dpgo::Options &d, dpgo_options_t *o) {
   o->scheme = d.scheme; o->regularizer = d.regularizer; o->accepted_delta = d.accepted_delta;
   o->eta[0] = d.eta[0]; o->eta[1] = d.eta[1]; o->psi = d.psi; o->phi = d.phi;
   o->max_soft_restart_hits[0] = d.max_soft_restart_hits[0]; o->max_soft_restart_hits[1] = d.max_soft_restart_hits[1];
@@ -82,6 +34,10 @@ void dpgo_options_default(dpgo_options_t *o) {
   o->STPCG_kappa = d.STPCG_kappa; o->STPCG_theta = d.STPCG_theta; o->preconditioner = d.preconditioner;
   o->verbose = d.verbose;
 }
+
+extern "C" {
+
+void dpgo_options_default(dpgo_options_t *o) { to_c(dpgo::Options(), o); }
 
 void dpgo_options_driver(dpgo_options_t *o, int loss, int accelerated) {
   // C++/examples/dist_pgo.cpp:103-120
@@ -158,11 +114,6 @@ int dpgo_graph_edges(const dpgo_graph_t *g, int *I, int *J, double *R, double *t
     if (tau) tau[e] = m.tau;
   }
   return 0;
-}
-
-static int node_info(const dpgo_graph_t *g, int node, dpgo::DataInfo &info) {
-  if (!g || node < 0 || node >= g->g.num_nodes) return -1;
-  return dpgo::generate_data_info(node, g->g.d, g->g.measurements[node], info);
 }
 
 int dpgo_graph_node_sizes(const dpgo_graph_t *g, int node, int *n0, int *n1, int *m0, int *m1) {
@@ -362,67 +313,6 @@ int dpgo_group_results(const dpgo_group_t *h, int local, dpgo_results_t *o) {
   });
 }
 
-// ---- test hooks ----
-static int ref_row(int d, int n0, int n1, int p, int slot) {
-  if (p < n0) return slot == 0 ? p : n0 + p * d + slot - 1;
-  const int k = p - n0;
-  return slot == 0 ? (d + 1) * n0 + k : (d + 1) * n0 + n1 + k * d + slot - 1;
-}
-
-int dpgo_debug_node_matrix(const dpgo_graph_t *g, int node, const dpgo_options_t *opt, const char *name, int *rows,
-                           int *cols, double *vals) {
-  dpgo::DataInfo info;
-  if (node_info(g, node, info) != 0) return -1;
-  dpgo::NodeOperators ops;
-  const bool trivial = opt->loss == 0;
-  if (dpgo::assemble_node(info, opt->regularizer, trivial, ops) != 0) return -1;
-  const int d = info.d, B = d + 1, n0 = info.n[0], n1 = info.n[1];
-  const std::string nm(name);
-  int cnt = 0;
-  auto emit = [&](int p, int q, const double *blk) {
-    for (int r = 0; r < B; r++)
-      for (int c = 0; c < B; c++) {
-        if (blk[r * B + c] == 0.0) continue;
-        if (rows) { rows[cnt] = ref_row(d, n0, n1, p, r); cols[cnt] = ref_row(d, n0, n1, q, c); vals[cnt] = blk[r * B + c]; }
-        cnt++;
-      }
-  };
-  if (nm == "D") {
-    for (int p = 0; p < n0; p++) emit(p, p, &ops.D[(size_t)p * B * B]);
-    return cnt;
-  }
-  const dpgo::BsrMatrix *M = nm == "G" ? &ops.G : nm == "S" ? &ops.S : nm == "P" ? &ops.P : nm == "P0" ? &ops.P0
-                                                                                    : nm == "Q" ? &ops.Q : nullptr;
-  if (!M || M->B == 0) return -1;
-  for (int p = 0; p < M->nrows; p++)
-    for (int k = M->ptr[p]; k < M->ptr[p + 1]; k++) emit(p, M->col[k], &M->val[(size_t)k * B * B]);
-  return cnt;
-}
-
-int dpgo_debug_node_proximal(const dpgo_graph_t *g, int node, const dpgo_options_t *opt, double *T, double *N,
-                             double *V) {
-  dpgo::DataInfo info;
-  if (node_info(g, node, info) != 0) return -1;
-  dpgo::NodeOperators ops;
-  if (dpgo::assemble_node(info, opt->regularizer, opt->loss == 0, ops) != 0) return -1;
-  std::copy(ops.Tinv.begin(), ops.Tinv.end(), T);
-  std::copy(ops.N.begin(), ops.N.end(), N);
-  std::copy(ops.V.begin(), ops.V.end(), V);
-  return 0;
-}
-
-int dpgo_debug_spd_solve(int n, const int *ptr, const int *col, const double *val, double *X, int ncols, int leaf) {
-  dpgo::CsrMatrix A;
-  A.n = n;
-  A.ptr.assign(ptr, ptr + n + 1);
-  A.col.assign(col, col + ptr[n]);
-  A.val.assign(val, val + ptr[n]);
-  dpgo::SpdFactor F;
-  if (dpgo::spd_factor(A, F, leaf) != 0) return -1;
-  dpgo::spd_solve_host(F, X, ncols);
-  return 0;
-}
-
 int dpgo_prof_enable(int on) { dpgo::prof_enable(on != 0); if (on) dpgo::prof_reset(); return 0; }
 int dpgo_prof_num_kinds(void) { return dpgo::PK_COUNT; }
 const char *dpgo_prof_kind_name(int k) {
@@ -447,693 +337,6 @@ int dpgo_group_graph_stats(const dpgo_group_t *h, long *replays, long *captures,
   return 0;
 }
 
-int dpgo_debug_spd_stats(int n, const int *ptr, const int *col, const double *val, int leaf, long *nnz, int *levels,
-                         int *max_front) {
-  dpgo::CsrMatrix A;
-  A.n = n;
-  A.ptr.assign(ptr, ptr + n + 1);
-  A.col.assign(col, col + ptr[n]);
-  A.val.assign(val, val + ptr[n]);
-  dpgo::SpdFactor F;
-  if (dpgo::spd_factor(A, F, leaf) != 0) return -1;
-  if (!dpgo::settings().spd_dump_fronts.empty()) {   // analysis hook: w u height depth per front
-    if (FILE *fp = fopen(dpgo::settings().spd_dump_fronts.c_str(), "w")) {
-      for (int f = 0; f < F.nfronts; f++) fprintf(fp, "%d %d %d %d\n", F.w[f], F.u[f], F.height[f], F.depth[f]);
-      fclose(fp);
-    }
-  }
-  *nnz = (long)F.nnz();
-  *levels = (int)F.by_height.size();
-  *max_front = F.max_front;
-  return 0;
-}
-
-// ---- test hook: the factor itself, front by front ----
-struct dpgo_spd_debug {
-  dpgo::SpdFactor F;
-  int status[2] = {-1, -1}, fail_front[2] = {-1, -1};   // [0] the factorisation, [1] the one through the kept context
-  double pivots[4] = {0, 0, 0, 0};
-  bool has_second = false, factor_only = false, on_device = false;
-  std::vector<int> height;
-  std::vector<double> W, WT, W2, WT2;
-  ~dpgo_spd_debug() {   // (a factor does not release what it owns by itself: spd.h)
-    dpgo::spd_release_device(F);
-    dpgo::spd_release_numeric(F);
-  }
-};
-
-namespace {
-bool spd_debug_device_numeric() {
-  int ndev = 0;
-  return !dpgo::settings().spd_host_factor && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
-}
-// rc of spd_factor / spd_refactor_device -> 0 factored, 1 not positive definite, -1 error
-int spd_debug_status(int rc, const dpgo::SpdFactor &F) { return rc == 0 ? 0 : (F.not_pd ? 1 : -1); }
-// W / WT of F to the host: the host vectors where the numeric phase filled them, else the device copies
-int spd_debug_fetch(const dpgo::SpdFactor &F, std::vector<double> &W, std::vector<double> &WT) {
-  const int nt = F.nfronts;
-  if (!F.dev_W) { W = F.W; WT = F.WT; return 0; }
-  W.assign(F.w_off[nt], 0.0);
-  WT.assign(F.wt_off[nt], 0.0);
-  if (!W.empty() && hipMemcpy(W.data(), F.dev_W, sizeof(double) * W.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (!WT.empty() && hipMemcpy(WT.data(), F.dev_WT, sizeof(double) * WT.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return 0;
-}
-}  // namespace
-
-int dpgo_debug_spd_factor(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
-                          int collapse, int block, int factor_only, dpgo_spd_debug_t **out) {
-  if (!out || !ptr || !col || !val || n <= 0) return -1;
-  *out = nullptr;
-  return guarded([&] {
-    dpgo::CsrMatrix A;
-    A.n = n;
-    A.ptr.assign(ptr, ptr + n + 1);
-    A.col.assign(col, col + ptr[n]);
-    A.val.assign(val, val + ptr[n]);
-    std::unique_ptr<dpgo_spd_debug> h(new dpgo_spd_debug());
-    dpgo::SpdFactor &F = h->F;
-    h->factor_only = factor_only != 0;
-    h->on_device = spd_debug_device_numeric();
-    F.quiet = true;
-    auto record = [&](int k, int rc) {
-      h->status[k] = spd_debug_status(rc, F);
-      h->fail_front[k] = F.not_pd ? F.fail_front : -1;
-      h->pivots[2 * k] = F.pivot_min;
-      h->pivots[2 * k + 1] = F.pivot_max;
-    };
-    if (h->factor_only && h->on_device) {
-      // the certificate's route (cert.cpp): analysis, context, values written on the device, numeric phase from them
-      F.factor_only = true;
-      if (dpgo::spd_symbolic(A, F, leaf, collapse, block) != 0 || dpgo::spd_prepare_device(A, F) != 0) return -1;
-      for (int k = 0; k < (refactor_val ? 2 : 1); k++) {
-        const double *v = k == 0 ? val : refactor_val;
-        if (hipMemcpy(dpgo::spd_numeric_values(F), v, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        record(k, dpgo::spd_refactor_device(F));
-      }
-      h->has_second = refactor_val != nullptr;
-    } else {
-      F.keep_numeric = refactor_val != nullptr && h->on_device;   // (Group::factor_tt for a Dynamic rescale)
-      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/F.keep_numeric);
-      record(0, rc);
-      if (rc == 0 && !h->factor_only && spd_debug_fetch(F, h->W, h->WT) != 0) return -1;
-      if (refactor_val) {   // (also behind a non-positive pivot: the context does not depend on the values)
-        int rc2;
-        if (F.numeric) {   // the kept context: new values on the device, the kernels again
-          if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-          rc2 = dpgo::spd_refactor_device(F);
-        } else {           // no GPU: spd_refactor redoes the factorisation on the host
-          A.val.assign(refactor_val, refactor_val + ptr[n]);
-          rc2 = dpgo::spd_refactor(A, F);
-        }
-        record(1, rc2);
-        h->has_second = true;
-        if (rc2 == 0 && !h->factor_only && spd_debug_fetch(F, h->W2, h->WT2) != 0) return -1;
-      }
-    }
-    if (h->status[0] < 0 || (h->has_second && h->status[1] < 0)) return -1;
-    h->height.assign(F.nfronts, 0);
-    for (int f = 0; f < F.nfronts; f++)
-      if (F.parent[f] >= 0) h->height[F.parent[f]] = std::max(h->height[F.parent[f]], h->height[f] + 1);
-    *out = h.release();
-    return 0;
-  });
-}
-
-int dpgo_debug_spd_factor_get(const dpgo_spd_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
-                              long long *offsets, int *piv_idx, int *upd_idx, double *W, double *WT, double *W2, double *WT2) {
-  if (!h) return -1;
-  const dpgo::SpdFactor &F = h->F;
-  const int nt = F.nfronts;
-  if (sizes) {
-    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = F.w_off[nt]; sizes[3] = F.wt_off[nt];
-    sizes[4] = (long long)h->W.size(); sizes[5] = (long long)h->W2.size(); sizes[6] = h->has_second; sizes[7] = h->on_device;
-  }
-  if (status) { status[0] = h->status[0]; status[1] = h->fail_front[0]; status[2] = h->status[1]; status[3] = h->fail_front[1]; }
-  if (pivots) std::copy(h->pivots, h->pivots + 4, pivots);
-  for (int f = 0; f < nt; f++) {
-    if (fronts) {
-      int *q = fronts + 6 * f;
-      q[0] = F.w[f]; q[1] = F.u[f]; q[2] = F.parent[f]; q[3] = h->height[f]; q[4] = F.ldw[f]; q[5] = F.ldm[f];
-    }
-    if (offsets) { offsets[2 * f] = F.w_off[f]; offsets[2 * f + 1] = F.wt_off[f]; }
-  }
-  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
-  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
-  if (W) std::copy(h->W.begin(), h->W.end(), W);
-  if (WT) std::copy(h->WT.begin(), h->WT.end(), WT);
-  if (W2) std::copy(h->W2.begin(), h->W2.end(), W2);
-  if (WT2) std::copy(h->WT2.begin(), h->WT2.end(), WT2);
-  return 0;
-}
-
-void dpgo_debug_spd_factor_free(dpgo_spd_debug_t *h) { delete h; }
-
-// ---- test hook: selected inversion, front by front ----
-struct dpgo_spd_selinv_debug {
-  dpgo::SpdFactor F;
-  int status[4] = {-1, -1, -1, -1};
-  double pivots[4] = {0, 0, 0, 0};
-  bool on_device = false;
-  std::vector<int> depth;
-  std::vector<double> sigma, sigma_again, sigma2, W_before, W_after;
-  ~dpgo_spd_selinv_debug() {
-    dpgo::spd_release_device(F);
-    dpgo::spd_release_numeric(F);
-  }
-};
-
-int dpgo_debug_spd_selinv(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
-                          int collapse, int block, int host, dpgo_spd_selinv_debug_t **out) {
-  if (!out) return -1;
-  *out = nullptr;
-  if (!ptr || !col || !val || n <= 0 || leaf < 1 || block < 1 || collapse < 0 || n % block != 0 || ptr[0] != 0) return -1;
-  for (int i = 0; i < n; i++)
-    if (ptr[i + 1] < ptr[i]) return -1;
-  for (int e = 0; e < ptr[n]; e++)
-    if (col[e] < 0 || col[e] >= n) return -1;
-  return guarded([&] {
-    dpgo::CsrMatrix A;
-    A.n = n;
-    A.ptr.assign(ptr, ptr + n + 1);
-    A.col.assign(col, col + ptr[n]);
-    A.val.assign(val, val + ptr[n]);
-    std::unique_ptr<dpgo_spd_selinv_debug> h(new dpgo_spd_selinv_debug());
-    dpgo::SpdFactor &F = h->F;
-    h->on_device = !host && spd_debug_device_numeric();
-    F.quiet = true;
-    std::vector<double> WT;
-    // the blocks the device holds, to the host
-    auto fetch_sigma = [&](std::vector<double> &S) -> int {
-      S.assign(dpgo::spd_selinv_offsets(F).back(), 0.0);
-      if (hipDeviceSynchronize() != hipSuccess) return -1;
-      if (!S.empty() && hipMemcpy(S.data(), dpgo::spd_selinv_values(F), sizeof(double) * S.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-      return 0;
-    };
-    if (h->on_device) {
-      F.keep_numeric = true;
-      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
-      h->status[0] = spd_debug_status(rc, F);
-      h->pivots[0] = F.pivot_min; h->pivots[1] = F.pivot_max;
-      if (h->status[0] < 0 || !F.numeric) return -1;
-      if (rc == 0 && spd_debug_fetch(F, h->W_before, WT) != 0) return -1;
-      const int si = dpgo::spd_selinv_device(F);
-      h->status[1] = si == 0 ? 0 : (F.not_pd ? 1 : -1);
-      if (h->status[1] < 0) return -1;
-      if (si == 0) {
-        if (fetch_sigma(h->sigma) != 0 || dpgo::spd_selinv_device(F) != 0 || fetch_sigma(h->sigma_again) != 0) return -1;
-        // the same values through the kept context, behind the inversion
-        if (hipMemcpy(dpgo::spd_numeric_values(F), val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        if (dpgo::spd_refactor_device(F) != 0 || spd_debug_fetch(F, h->W_after, WT) != 0) return -1;
-      }
-      if (refactor_val) {
-        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        const int rc2 = dpgo::spd_refactor_device(F);
-        h->status[2] = spd_debug_status(rc2, F);
-        h->pivots[2] = F.pivot_min; h->pivots[3] = F.pivot_max;
-        if (h->status[2] < 0) return -1;
-        const int si2 = dpgo::spd_selinv_device(F);
-        h->status[3] = si2 == 0 ? 0 : (F.not_pd ? 1 : -1);
-        if (h->status[3] < 0) return -1;
-        if (si2 == 0 && fetch_sigma(h->sigma2) != 0) return -1;
-      }
-    } else {
-      // (with a device and host != 0 the numeric phase still runs where spd_factor puts it; W comes to the host)
-      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
-      h->status[0] = spd_debug_status(rc, F);
-      h->pivots[0] = F.pivot_min; h->pivots[1] = F.pivot_max;
-      if (h->status[0] < 0) return -1;
-      h->status[1] = rc == 0 ? 0 : 1;
-      if (rc == 0) {
-        h->W_before = F.W;
-        if (dpgo::spd_selinv_host(F, F.W.data(), h->sigma) != 0 || dpgo::spd_selinv_host(F, F.W.data(), h->sigma_again) != 0) return -1;
-        h->W_after = F.W;
-      }
-      if (refactor_val) {
-        A.val.assign(refactor_val, refactor_val + ptr[n]);
-        const int rc2 = dpgo::spd_refactor(A, F);
-        h->status[2] = spd_debug_status(rc2, F);
-        h->pivots[2] = F.pivot_min; h->pivots[3] = F.pivot_max;
-        if (h->status[2] < 0) return -1;
-        h->status[3] = rc2 == 0 ? 0 : 1;
-        if (rc2 == 0 && dpgo::spd_selinv_host(F, F.W.data(), h->sigma2) != 0) return -1;
-      }
-    }
-    h->depth.assign(F.nfronts, 0);
-    for (int f = F.nfronts - 1; f >= 0; f--)
-      if (F.parent[f] >= 0) h->depth[f] = h->depth[F.parent[f]] + 1;
-    *out = h.release();
-    return 0;
-  });
-}
-
-int dpgo_debug_spd_selinv_get(const dpgo_spd_selinv_debug_t *h, long long *sizes, int *status, double *pivots, int *fronts,
-                              int *piv_idx, int *upd_idx, double *sigma, double *sigma_again, double *sigma2,
-                              double *W_before, double *W_after) {
-  if (!h) return -1;
-  const dpgo::SpdFactor &F = h->F;
-  const int nt = F.nfronts;
-  if (sizes) {
-    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = dpgo::spd_selinv_offsets(F).back();
-    sizes[3] = (long long)h->sigma.size(); sizes[4] = (long long)h->sigma_again.size(); sizes[5] = (long long)h->sigma2.size();
-    sizes[6] = (long long)std::min(h->W_before.size(), h->W_after.size()); sizes[7] = h->on_device;
-  }
-  if (status) std::copy(h->status, h->status + 4, status);
-  if (pivots) std::copy(h->pivots, h->pivots + 4, pivots);
-  if (fronts)
-    for (int f = 0; f < nt; f++) {
-      int *q = fronts + 4 * f;
-      q[0] = F.w[f]; q[1] = F.u[f]; q[2] = F.parent[f]; q[3] = h->depth[f];
-    }
-  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
-  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
-  if (sigma) std::copy(h->sigma.begin(), h->sigma.end(), sigma);
-  if (sigma_again) std::copy(h->sigma_again.begin(), h->sigma_again.end(), sigma_again);
-  if (sigma2) std::copy(h->sigma2.begin(), h->sigma2.end(), sigma2);
-  if (W_before) std::copy(h->W_before.begin(), h->W_before.end(), W_before);
-  if (W_after) std::copy(h->W_after.begin(), h->W_after.end(), W_after);
-  return 0;
-}
-
-void dpgo_debug_spd_selinv_free(dpgo_spd_selinv_debug_t *h) { delete h; }
-
-// ---- test hook: the device solve for one plain vector (spd.h: spd_vsolve_*) ----
-int dpgo_debug_spd_vsolve_chunk(int chunk) { return dpgo::spd_vsolve_chunk(chunk); }
-
-int dpgo_debug_spd_vsolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
-                          int collapse, int block, int host, const double *rhs, double *out, int *status, double *pivots) {
-  if (!ptr || !col || !val || !rhs || !out || !status || !pivots || n <= 0 || leaf < 1 || block < 1 || collapse < 0 ||
-      n % block != 0 || ptr[0] != 0)
-    return -1;
-  for (int i = 0; i < n; i++)
-    if (ptr[i + 1] < ptr[i]) return -1;
-  for (int e = 0; e < ptr[n]; e++)
-    if (col[e] < 0 || col[e] >= n) return -1;
-  return guarded([&] {
-    dpgo::CsrMatrix A;
-    A.n = n;
-    A.ptr.assign(ptr, ptr + n + 1);
-    A.col.assign(col, col + ptr[n]);
-    A.val.assign(val, val + ptr[n]);
-    struct Holder {
-      dpgo::SpdFactor F;
-      double *d_x = nullptr;
-      ~Holder() {
-        if (d_x) (void)hipFree(d_x);
-        dpgo::spd_release_device(F);
-        dpgo::spd_release_numeric(F);
-      }
-    } H;
-    dpgo::SpdFactor &F = H.F;
-    const bool on_device = !host && spd_debug_device_numeric();
-    F.quiet = true;
-    status[0] = status[1] = -1;
-    std::fill(pivots, pivots + 4, 0.0);
-    const size_t nb = sizeof(double) * (size_t)n;
-    if (on_device) {
-      F.keep_numeric = true;
-      if (hipMalloc((void **)&H.d_x, nb) != hipSuccess) return -1;
-      // out + k n <- A^-1 rhs through spd_vsolve_device
-      auto solve = [&](int k) -> int {
-        if (hipMemcpy(H.d_x, rhs, nb, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        if (dpgo::spd_vsolve_device(F, H.d_x) != 0 || hipDeviceSynchronize() != hipSuccess) return -1;
-        return hipMemcpy(out + (size_t)k * n, H.d_x, nb, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-      };
-      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
-      status[0] = spd_debug_status(rc, F);
-      pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
-      if (status[0] < 0 || !F.numeric) return -1;
-      if (rc == 0 && (solve(0) != 0 || solve(1) != 0)) return -1;
-      if (rc != 0 && dpgo::spd_vsolve_device(F, H.d_x) != -1) return -1;   // (a failed factorisation solves nothing)
-      if (refactor_val) {
-        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        const int rc2 = dpgo::spd_refactor_device(F);
-        status[1] = spd_debug_status(rc2, F);
-        pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
-        if (status[1] < 0) return -1;
-        if (rc2 == 0 && solve(2) != 0) return -1;
-      }
-      return 1;
-    }
-    auto solve_host = [&](int k) {
-      std::copy(rhs, rhs + n, out + (size_t)k * n);
-      dpgo::spd_solve_host(F, out + (size_t)k * n, 1);
-    };
-    const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
-    status[0] = spd_debug_status(rc, F);
-    pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
-    if (status[0] < 0) return -1;
-    if (rc == 0) { solve_host(0); solve_host(1); }
-    if (refactor_val) {
-      A.val.assign(refactor_val, refactor_val + ptr[n]);
-      const int rc2 = dpgo::spd_refactor(A, F);
-      status[1] = spd_debug_status(rc2, F);
-      pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
-      if (status[1] < 0) return -1;
-      if (rc2 == 0) solve_host(2);
-    }
-    return 0;
-  });
-}
-
-// ---- test hook: the device solve for a block of plain vectors (spd.h: spd_msolve_*) ----
-int dpgo_debug_spd_msolve(int n, const int *ptr, const int *col, const double *val, const double *refactor_val, int leaf,
-                          int collapse, int block, int host, int chunk, const double *rhs, int k, int ldx, double *out,
-                          int *status, double *pivots) {
-  if (!ptr || !col || !val || !rhs || !out || !status || !pivots || n <= 0 || leaf < 1 || block < 1 || collapse < 0 ||
-      n % block != 0 || ptr[0] != 0 || k < 1 || ldx < k)
-    return -1;
-  for (int i = 0; i < n; i++)
-    if (ptr[i + 1] < ptr[i]) return -1;
-  for (int e = 0; e < ptr[n]; e++)
-    if (col[e] < 0 || col[e] >= n) return -1;
-  return guarded([&] {
-    dpgo::CsrMatrix A;
-    A.n = n;
-    A.ptr.assign(ptr, ptr + n + 1);
-    A.col.assign(col, col + ptr[n]);
-    A.val.assign(val, val + ptr[n]);
-    struct Holder {
-      dpgo::SpdFactor F;
-      double *d_x = nullptr;
-      int chunk_before = 0;
-      bool chunk_set = false;
-      ~Holder() {
-        if (chunk_set) dpgo::spd_msolve_chunk(chunk_before);
-        if (d_x) (void)hipFree(d_x);
-        dpgo::spd_release_device(F);
-        dpgo::spd_release_numeric(F);
-      }
-    } H;
-    dpgo::SpdFactor &F = H.F;
-    const bool on_device = !host && spd_debug_device_numeric();
-    F.quiet = true;
-    status[0] = status[1] = -1;
-    std::fill(pivots, pivots + 4, 0.0);
-    const size_t cnt = (size_t)n * ldx, nb = sizeof(double) * cnt;
-    if (on_device) {
-      F.keep_numeric = true;
-      if (chunk > 0) { H.chunk_before = dpgo::spd_msolve_chunk(chunk); H.chunk_set = true; }
-      if (hipMalloc((void **)&H.d_x, nb) != hipSuccess) return -1;
-      // part j of out <- the n x ldx array the solve was handed (the caller's fill with rhs in its first k columns), solved
-      auto solve = [&](int j) -> int {
-        std::vector<double> X(out + j * cnt, out + (j + 1) * cnt);
-        for (int i = 0; i < n; i++) std::copy(rhs + (size_t)i * k, rhs + (size_t)(i + 1) * k, X.begin() + (size_t)i * ldx);
-        if (hipMemcpy(H.d_x, X.data(), nb, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        if (dpgo::spd_msolve_device(F, H.d_x, k, ldx) != 0 || hipDeviceSynchronize() != hipSuccess) return -1;
-        return hipMemcpy(out + j * cnt, H.d_x, nb, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-      };
-      const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/true);
-      status[0] = spd_debug_status(rc, F);
-      pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
-      if (status[0] < 0 || !F.numeric) return -1;
-      if (rc == 0 && (solve(0) != 0 || solve(1) != 0)) return -1;
-      if (rc != 0 && dpgo::spd_msolve_device(F, H.d_x, k, ldx) != -1) return -1;   // (a failed factorisation solves nothing)
-      if (refactor_val) {
-        if (hipMemcpy(dpgo::spd_numeric_values(F), refactor_val, sizeof(double) * A.val.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        const int rc2 = dpgo::spd_refactor_device(F);
-        status[1] = spd_debug_status(rc2, F);
-        pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
-        if (status[1] < 0) return -1;
-        if (rc2 == 0 && solve(2) != 0) return -1;
-      }
-      return 1;
-    }
-    auto solve_host = [&](int j) {
-      std::vector<double> X(rhs, rhs + (size_t)n * k);
-      dpgo::spd_solve_host(F, X.data(), k);
-      for (int i = 0; i < n; i++) std::copy(X.begin() + (size_t)i * k, X.begin() + (size_t)(i + 1) * k, out + j * cnt + (size_t)i * ldx);
-    };
-    const int rc = dpgo::spd_factor(A, F, leaf, collapse, block, /*keep_device=*/false);
-    status[0] = spd_debug_status(rc, F);
-    pivots[0] = F.pivot_min; pivots[1] = F.pivot_max;
-    if (status[0] < 0) return -1;
-    if (rc == 0) { solve_host(0); solve_host(1); }
-    if (refactor_val) {
-      A.val.assign(refactor_val, refactor_val + ptr[n]);
-      const int rc2 = dpgo::spd_refactor(A, F);
-      status[1] = spd_debug_status(rc2, F);
-      pivots[2] = F.pivot_min; pivots[3] = F.pivot_max;
-      if (status[1] < 0) return -1;
-      if (rc2 == 0) solve_host(2);
-    }
-    return 0;
-  });
-}
-
-// ---- test hook: the device solve (spd_solve.cpp) on a given matrix ----
-using dpgo::DeviceError;   // (what HIP_CHECK throws)
-struct dpgo_spd_solver_debug {
-  dpgo::SpdSolverDev S;
-  int n = 0, d = 0, dof = 0, nnodes = 1;
-  size_t nval = 0, len = 0;   // stored entries of A; doubles of a record array
-  std::vector<int> height;
-  hipStream_t st = nullptr;
-  dpgo::DevBuf<double> in, out;
-  dpgo::DevBuf<dpgo::NodeBits> word;
-  ~dpgo_spd_solver_debug() { if (st) (void)hipStreamDestroy(st); }
-};
-
-int dpgo_debug_spd_solver_create(int n, const int *ptr, const int *col, const double *val, int leaf, int collapse, int block,
-                                 int d, int dof, const int *node_of_unknown, int keep_numeric, dpgo_spd_solver_debug_t **out) {
-  if (!out) return -1;
-  *out = nullptr;
-  if (!ptr || !col || !val || !node_of_unknown || n <= 0 || (d != 2 && d != 3) || (dof != 1 && dof != d)) return -1;
-  for (int i = 0; i < n; i++)
-    if (node_of_unknown[i] < 0 || node_of_unknown[i] >= dpgo::MAX_LOCAL_NODES) return -1;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -2;   // the solve has no host form
-  const dpgo::Settings &s = dpgo::settings();
-  if (keep_numeric && (!s.spd_device_panels || s.spd_host_factor)) return -1;   // (Group::refactor_tt keeps the context under the same condition)
-  return guarded([&] {
-    dpgo::CsrMatrix A;
-    A.n = n;
-    A.ptr.assign(ptr, ptr + n + 1);
-    A.col.assign(col, col + ptr[n]);
-    A.val.assign(val, val + ptr[n]);
-    std::unique_ptr<dpgo_spd_solver_debug> h(new dpgo_spd_solver_debug());
-    h->n = n; h->d = d; h->dof = dof; h->nval = A.val.size();
-    h->len = (size_t)((n + dof - 1) / dof) * (d + 1) * d;   // (a last record may hold fewer than dof unknowns)
-    std::vector<int> node(node_of_unknown, node_of_unknown + n);
-    for (int a : node) h->nnodes = std::max(h->nnodes, a + 1);
-    dpgo::SpdFactor &F = h->S.F;
-    F.keep_numeric = keep_numeric != 0;
-    if (dpgo::spd_factor(A, F, leaf, collapse, block, s.spd_device_panels) != 0) return -1;
-    h->height.assign(F.nfronts, 0);
-    for (int f = 0; f < F.nfronts; f++)
-      if (F.parent[f] >= 0) h->height[F.parent[f]] = std::max(h->height[F.parent[f]], h->height[f] + 1);
-    h->S.upload(dof, d, node);
-    HIP_CHECK(hipStreamCreate(&h->st));
-    h->in.alloc(h->len);
-    h->out.alloc(h->len);
-    h->word.alloc(1);
-    *out = h.release();
-    return 0;
-  });
-}
-
-int dpgo_debug_spd_solver_plan(const dpgo_spd_solver_debug_t *h, long long *sizes, int *flags, int *levels, int *node_counts,
-                               int *fronts, int *piv_idx, int *upd_idx) {
-  if (!h) return -1;
-  const dpgo::SpdFactor &F = h->S.F;
-  const dpgo::SpdPlanInfo I = h->S.plan_info();
-  const int nt = F.nfronts, nn = h->nnodes;
-  if (sizes) {
-    sizes[0] = nt; sizes[1] = F.upd_ptr[nt]; sizes[2] = (long long)I.fwd.size(); sizes[3] = (long long)I.bwd.size();
-    sizes[4] = nn; sizes[5] = h->n; sizes[6] = (long long)h->len; sizes[7] = (long long)h->nval;
-  }
-  if (flags) {
-    flags[0] = I.fused_root; flags[1] = I.root_sym; flags[2] = I.root.rows; flags[3] = I.root_fine_rows;
-    flags[4] = I.root_fine_below; flags[5] = I.stream_once; flags[6] = h->dof; flags[7] = h->d;
-  }
-  std::vector<const dpgo::SpdPlanInfo::Level *> all;
-  for (const auto &v : I.fwd) all.push_back(&v);
-  for (const auto &v : I.bwd) all.push_back(&v);
-  all.push_back(&I.root); all.push_back(&I.root_fine); all.push_back(&I.root_rows);
-  for (size_t l = 0; l < all.size(); l++) {
-    const dpgo::SpdPlanInfo::Level &v = *all[l];
-    if (levels) { levels[3 * l] = v.rows; levels[3 * l + 1] = v.nwide; levels[3 * l + 2] = v.nnarrow; }
-    if (node_counts)
-      for (int a = 0; a < nn; a++) {   // (a level nobody built -- no fused root, no finer class -- has no nodes: zeros)
-        node_counts[(l * nn + a) * 2] = a < (int)v.wcount.size() ? v.wcount[a] : 0;
-        node_counts[(l * nn + a) * 2 + 1] = a < (int)v.ncount.size() ? v.ncount[a] : 0;
-      }
-  }
-  if (fronts)
-    for (int f = 0; f < nt; f++) { fronts[4 * f] = F.w[f]; fronts[4 * f + 1] = F.u[f]; fronts[4 * f + 2] = F.parent[f]; fronts[4 * f + 3] = h->height[f]; }
-  if (piv_idx) std::copy(F.piv_idx.begin(), F.piv_idx.end(), piv_idx);
-  if (upd_idx) std::copy(F.upd_idx.begin(), F.upd_idx.end(), upd_idx);
-  return 0;
-}
-
-int dpgo_debug_spd_solver_fine_root(const dpgo_spd_solver_debug_t *h, unsigned long long nodes) {
-  if (!h) return -1;
-  return h->S.fine_root_for(nodes) ? 1 : 0;
-}
-
-int dpgo_debug_spd_solver_run(dpgo_spd_solver_debug_t *h, unsigned long long mask_v, const unsigned long long *mask_word,
-                              const unsigned long long *class_of, double scale, int in_place, const double *in, double *out) {
-  if (!h || !in || !out || (scale != 1.0 && scale != -1.0)) return -1;
-  return guarded([&] {
-    // the out array first: what the solve leaves alone is what the caller put there (in place: the in array is both)
-    HIP_CHECK(hipMemcpy(h->in.p, in, sizeof(double) * h->len, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(h->out.p, out, sizeof(double) * h->len, hipMemcpyHostToDevice));
-    dpgo::NodeMask mask{mask_v, nullptr};
-    if (mask_word) {
-      HIP_CHECK(hipMemcpy(h->word.p, mask_word, sizeof(dpgo::NodeBits), hipMemcpyHostToDevice));
-      mask.p = h->word.p;
-    }
-    const dpgo::NodeBits cls = class_of ? *class_of : 0;
-    double *res = in_place ? h->in.p : h->out.p;
-    try {
-      dpgo::spd_run(h->d, h->st, h->S, mask, h->in.p, res, scale, class_of ? &cls : nullptr);
-    } catch (const dpgo::DeviceError &) {
-      return -2;   // spd_run's own refusal (in == out with fused roots); nothing was launched
-    }
-    HIP_CHECK(hipStreamSynchronize(h->st));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpy(out, res, sizeof(double) * h->len, hipMemcpyDeviceToHost));
-    return 0;
-  });
-}
-
-int dpgo_debug_spd_solver_refactor(dpgo_spd_solver_debug_t *h, const double *val) {
-  if (!h || !val) return -1;
-  return guarded([&] {
-    dpgo::SpdFactor &F = h->S.F;
-    double *dst = dpgo::spd_numeric_values(F);
-    if (!dst) return -1;   // (not created with keep_numeric)
-    // what Group::rescale_device does behind k_rescale_apply: the new values are on the device, the numeric phase and the
-    // panels follow on the same stream
-    HIP_CHECK(hipMemcpyAsync(dst, val, sizeof(double) * h->nval, hipMemcpyHostToDevice, h->st));
-    if (dpgo::spd_refactor_device(F, (void *)h->st, true) != 0) return -1;
-    if (h->S.repack(h->st) != 0) return -1;
-    if (dpgo::spd_refactor_finish(F, true) != 0) return F.not_pd ? 1 : -1;
-    HIP_CHECK(hipStreamSynchronize(h->st));
-    return 0;
-  });
-}
-
-void dpgo_debug_spd_solver_free(dpgo_spd_solver_debug_t *h) { delete h; }
-
-int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const double *in, int ld_in, double *out,
-                           int ld_out) {
-  return guarded([&] { return h->grp->debug_apply(local, op, in, ld_in, out, ld_out); });
-}
-
-int dpgo_group_debug_inter_update(dpgo_group_t *h, const dpgo_inter_update_debug_t *q) {
-  if (!h || !q) return -1;
-  return guarded([&] {
-    dpgo::Group::InterUpdateDebug a;
-    a.local = q->local; a.whole = q->whole; a.quad = q->quad; a.with_Df = q->with_Df; a.nrecv = q->nrecv;
-    a.Z = q->Z; a.Zprev = q->Zprev; a.DfE_old = q->DfE_old; a.GX = q->GX; a.X = q->X; a.Znbr = q->Znbr; a.recv = q->recv; a.nsrc = q->nsrc;
-    a.DfE = q->DfE; a.g = q->g; a.w = q->w; a.sums = q->sums; a.Df = q->Df; a.Z_after = q->Z_after; a.Znbr_after = q->Znbr_after;
-    return h->grp->debug_inter_update(a);
-  });
-}
-
-int dpgo_group_debug_inter_iterate(dpgo_group_t *h, const dpgo_inter_iterate_debug_t *q) {
-  if (!h || !q) return -1;
-  return guarded([&] {
-    dpgo::Group::InterIterateDebug a;
-    a.local = q->local; a.whole = q->whole; a.fused = q->fused; a.prox = q->prox; a.gamma_dev = q->gamma_dev;
-    a.Zc = q->Zc; a.Zp = q->Zp; a.GXc = q->GXc; a.GXp = q->GXp; a.Xref = q->Xref; a.gamma = q->gamma;
-    a.Y = q->Y; a.g = q->g; a.Df = q->Df; a.Xout = q->Xout; a.Xref_after = q->Xref_after; a.sums = q->sums;
-    return h->grp->debug_inter_iterate(a);
-  });
-}
-
-int dpgo_group_debug_cost(dpgo_group_t *h, int local, int whole, int eform, const double *Z, double *sums) {
-  if (!h) return -1;
-  return guarded([&] { return h->grp->debug_cost(local, whole, eform, Z, sums); });
-}
-
-int dpgo_group_debug_edge_offsets(const dpgo_group_t *h, int *edge_offsets) {
-  if (!h || !edge_offsets) return -1;
-  const std::vector<int> &o = h->grp->debug_edge_offsets();
-  for (size_t k = 0; k < o.size(); k++) edge_offsets[k] = o[k];
-  return 0;
-}
-
-int dpgo_group_debug_rescale(dpgo_group_t *h, const double *w, const double *scale, const int *count, int max_rescale_count,
-                             const int *nodes, int n, int *flags, double *host_flags, double *scale_out, int *count_out) {
-  if (!h) return -1;
-  return guarded([&] {
-    return h->grp->debug_rescale(w, scale, count, max_rescale_count, nodes, n, flags, host_flags, scale_out, count_out);
-  });
-}
-
-int dpgo_group_debug_cert_gram(dpgo_group_t *h, const double *X, const double *V, const double *W, const double *P,
-                               const double *SV, const double *SP, const double *MW, int ld, double *sums, double *SW) {
-  if (!h || !h->grp || !X) return -1;
-  return guarded([&] { return h->grp->debug_cert_gram(X, V, W, P, SV, SP, MW, ld, sums, SW); });
-}
-
-int dpgo_group_debug_cert_update(dpgo_group_t *h, const dpgo_cert_update_debug_t *q) {
-  if (!h || !h->grp || !q) return -1;
-  return guarded([&] {
-    dpgo::Group::CertUpdateDebug a;
-    a.C = q->C; a.theta = q->theta; a.V = q->V; a.W = q->W; a.P = q->P; a.SV = q->SV; a.SW = q->SW; a.SP = q->SP;
-    a.ld = q->ld; a.precondition = q->precondition; a.nbr_fill = q->nbr_fill;
-    a.out[0] = q->V_out; a.out[1] = q->W_out; a.out[2] = q->P_out; a.out[3] = q->SV_out; a.out[4] = q->SW_out; a.out[5] = q->SP_out;
-    a.sums = q->sums; a.nbr = q->nbr;
-    return h->grp->debug_cert_update(a);
-  });
-}
-
-int dpgo_group_debug_cert_nbr_rows(const dpgo_group_t *h) { return h && h->grp ? h->grp->debug_cert_nbr_rows() : -1; }
-
-int dpgo_group_debug_cert_precon(dpgo_group_t *h, double *T) {
-  if (!h || !h->grp || !T) return -1;
-  return guarded([&] { return h->grp->debug_cert_precon(T); });
-}
-
-int dpgo_group_debug_cert_trace(dpgo_group_t *h, int on) {
-  if (!h || !h->grp) return -1;
-  h->grp->debug_cert_trace(on != 0);
-  return 0;
-}
-
-int dpgo_group_debug_cert_trace_get(const dpgo_group_t *h, double *records, long long cap, int *record_len, long long *count) {
-  if (!h || !h->grp || !record_len || !count) return -1;
-  const std::vector<double> &t = h->grp->debug_cert_trace_records();
-  *record_len = h->grp->cert_trace_len();
-  *count = (long long)t.size() / *record_len;
-  if (!records) return 0;   // (the sizes alone)
-  if (cap < (long long)t.size()) return -1;
-  std::copy(t.begin(), t.end(), records);
-  return 0;
-}
-
-int dpgo_group_debug_seg_layout(dpgo_group_t *h, int *nseg_all, int *own_ptr, int *nbr_ptr) {
-  if (!h) return -1;
-  return guarded([&] { return h->grp->debug_seg_layout(nseg_all, own_ptr, nbr_ptr); });
-}
-
-int dpgo_group_debug_stpcg(dpgo_group_t *h, const int *locals, int n, const double *in, int ld_in, const double *Delta,
-                           int device_start, double fill, double *out, int ld_out, double *scalars) {
-  if (!h || !locals || n <= 0) return -1;
-  return guarded([&] {
-    return h->grp->debug_stpcg(std::vector<int>(locals, locals + n), in, ld_in, Delta, device_start != 0, fill, out, ld_out, scalars);
-  });
-}
-
-int dpgo_group_debug_cg_scalars(dpgo_group_t *h, const dpgo_cg_debug_launch_t *script, int n, double *records,
-                                unsigned long long *masks, double *cg_summary, double *tnt_summary, double *dev_tnt,
-                                unsigned long long *seq, unsigned *arrived) {
-  if (!h || (n > 0 && !script)) return -1;
-  return guarded([&] {
-    std::vector<dpgo::Group::CgDebugLaunch> sc(n);
-    for (int i = 0; i < n; i++) {
-      const dpgo_cg_debug_launch_t &q = script[i];
-      sc[i].kind = q.kind; sc[i].bits = q.bits; sc[i].use_precon = q.use_precon; sc[i].max_it = q.max_it;
-      sc[i].grad_tol = q.grad_tol; sc[i].pgrad_tol = q.pgrad_tol; sc[i].kappa = q.kappa; sc[i].theta = q.theta;
-      sc[i].rv = q.rv; sc[i].Delta = q.Delta; sc[i].target = q.target; sc[i].partials = q.partials; sc[i].slots = q.slots;
-    }
-    return h->grp->debug_cg_scalars(sc.data(), n, records, masks, cg_summary, tnt_summary, dev_tnt, seq, arrived);
-  });
-}
-
 // ---- boundary: DPGOStar::evaluate_f / evaluate_grad, set_options / options, problem() accessors, g2o export ----
 int dpgo_group_evaluate(dpgo_group_t *h, const double *X, int ld, double *F, double *grad_sqnorm, double *grad, int ldg) {
   if (!h || !X) return -1;
@@ -1147,19 +350,7 @@ int dpgo_group_set_options(dpgo_group_t *h, const dpgo_options_t *opt) {
 
 int dpgo_group_get_options(const dpgo_group_t *h, dpgo_options_t *o) {
   if (!h || !o) return -1;
-  const dpgo::Options &d = h->grp->options();
-  o->scheme = d.scheme; o->regularizer = d.regularizer; o->accepted_delta = d.accepted_delta;
-  o->eta[0] = d.eta[0]; o->eta[1] = d.eta[1]; o->psi = d.psi; o->phi = d.phi;
-  o->max_soft_restart_hits[0] = d.max_soft_restart_hits[0]; o->max_soft_restart_hits[1] = d.max_soft_restart_hits[1];
-  o->oscillation_cnt_period = d.oscillation_cnt_period; o->max_oscillations = d.max_oscillations;
-  o->loss = d.loss; o->loss_reg = d.loss_reg; o->rescale = d.rescale; o->max_rescale_count = d.max_rescale_count;
-  o->grad_norm_tol = d.grad_norm_tol;
-  o->rel_func_decrease_tol = d.rel_func_decrease_tol; o->stepsize_tol = d.stepsize_tol;
-  o->max_iterations = d.max_iterations; o->max_iterations_accepted = d.max_iterations_accepted;
-  o->reg_Cholesky_precon_max_condition_number = d.reg_Cholesky_precon_max_condition_number;
-  o->preconditioned_grad_norm_tol = d.preconditioned_grad_norm_tol; o->max_tCG_iterations = d.max_tCG_iterations;
-  o->STPCG_kappa = d.STPCG_kappa; o->STPCG_theta = d.STPCG_theta; o->preconditioner = d.preconditioner;
-  o->verbose = d.verbose;
+  to_c(h->grp->options(), o);
   return 0;
 }
 
@@ -1247,35 +438,6 @@ int dpgo_write_g2o(const dpgo_graph_t *g, const double *X, int ld, const char *f
   return 0;
 }
 
-// test hook: the neighbour-to-neighbour exchange plan of rank `rank` (comm.cpp: p2p_plan) from every rank's exported and
-// needed keys.  exp_counts / need_counts: keys per rank; *_nodes / *_poses: the keys, rank after rank.
-// Out (may be null to query sizes): npeers; per peer 5 ints (rank, send_off, send_cnt, recv_off, recv_cnt); the send and
-// the receive keys (node, pose interleaved).  sizes[0..2] = npeers, send keys, recv keys.
-int dpgo_debug_p2p_plan(int rank, int nranks, const int *exp_counts, const int *exp_nodes, const int *exp_poses,
-                        const int *need_counts, const int *need_nodes, const int *need_poses, int *peers, int *send_keys,
-                        int *recv_keys, int *sizes) {
-  if (nranks < 1 || rank < 0 || rank >= nranks || !exp_counts || !need_counts || !sizes) return -1;
-  return guarded([&] {
-    std::vector<std::vector<dpgo::PoseKey>> ex(nranks), nd(nranks);
-    size_t a = 0, b = 0;
-    for (int r = 0; r < nranks; r++) {
-      for (int k = 0; k < exp_counts[r]; k++, a++) ex[r].push_back({exp_nodes[a], exp_poses[a]});
-      for (int k = 0; k < need_counts[r]; k++, b++) nd[r].push_back({need_nodes[b], need_poses[b]});
-    }
-    const dpgo::P2PPlan P = dpgo::p2p_plan(rank, ex, nd);
-    sizes[0] = (int)P.peers.size(); sizes[1] = (int)P.send_keys.size(); sizes[2] = (int)P.recv_keys.size();
-    if (peers)
-      for (size_t i = 0; i < P.peers.size(); i++) {
-        const auto &q = P.peers[i];
-        const int v[5] = {q.rank, q.send_off, q.send_cnt, q.recv_off, q.recv_cnt};
-        std::copy(v, v + 5, peers + 5 * i);
-      }
-    if (send_keys) for (size_t i = 0; i < P.send_keys.size(); i++) { send_keys[2 * i] = P.send_keys[i].first; send_keys[2 * i + 1] = P.send_keys[i].second; }
-    if (recv_keys) for (size_t i = 0; i < P.recv_keys.size(); i++) { recv_keys[2 * i] = P.recv_keys[i].first; recv_keys[2 * i + 1] = P.recv_keys[i].second; }
-    return 0;
-  });
-}
-
 // ---- RCCL exchange (comm.cpp) ----
 int dpgo_comm_unique_id(void *id128) {
   if (!id128) return -1;
@@ -1321,16 +483,6 @@ int dpgo_comm_exchange_kind(const dpgo_comm_t *c) {
 long dpgo_comm_bytes_sent(const dpgo_comm_t *c) {
   if (!c || !c->c) return -1;
   return (long)c->c->bytes_sent_per_exchange();
-}
-
-int dpgo_debug_comm_p2p_self(dpgo_group_t *h) {
-  if (!h) return -1;
-  return guarded([&] {
-    unsigned char id[128];
-    if (dpgo::Comm::unique_id(id) != 0) return -1;
-    dpgo::Comm c(h->grp, 0, 1, id, /*layout=*/false);   // a communicator of one rank: the group's neighbours need no host
-    return c.p2p_self_check();
-  });
 }
 
 int dpgo_comm_create_self(dpgo_group_t *h, dpgo_comm_t **out) {
@@ -1570,18 +722,26 @@ void dpgo_cert_options_default(dpgo_cert_options_t *o) {
   o->stop_on_negative = c.stop_on_negative; o->refresh_every = c.refresh_every; o->seed = c.seed;
 }
 
+static dpgo::CertOptions to_cpp(const dpgo_cert_options_t &opts) {
+  dpgo::CertOptions o;
+  o.eta = opts.eta; o.tau = opts.tau; o.max_iters = opts.max_iters; o.precondition = opts.precondition;
+  o.stop_on_negative = opts.stop_on_negative; o.refresh_every = opts.refresh_every; o.seed = opts.seed;
+  return o;
+}
+
+static void to_c(const dpgo::CertResult &r, dpgo_cert_result_t *o) {
+  o->status = r.status; o->iterations = r.iterations; o->restarts = r.restarts;
+  o->theta = r.theta; o->residual = r.residual; o->S_norm_est = r.S_norm_est;
+  o->stationarity = r.stationarity;
+}
+
 int dpgo_group_certify(dpgo_group_t *h, const double *X, int ld, const dpgo_cert_options_t *opts, const double *V0, int ldv0,
                        dpgo_cert_result_t *result, double *x, int ldx) {
   if (!h || !h->grp || !X || !opts || !result) return -1;
   return guarded([&] {
-    dpgo::CertOptions o;
-    o.eta = opts->eta; o.tau = opts->tau; o.max_iters = opts->max_iters; o.precondition = opts->precondition;
-    o.stop_on_negative = opts->stop_on_negative; o.refresh_every = opts->refresh_every; o.seed = opts->seed;
     dpgo::CertResult r;
-    const int rc = h->grp->certify(X, ld, o, V0, ldv0, r, x, ldx);
-    result->status = r.status; result->iterations = r.iterations; result->restarts = r.restarts;
-    result->theta = r.theta; result->residual = r.residual; result->S_norm_est = r.S_norm_est;
-    result->stationarity = r.stationarity;
+    const int rc = h->grp->certify(X, ld, to_cpp(*opts), V0, ldv0, r, x, ldx);
+    to_c(r, result);
     return rc;
   });
 }
@@ -1619,15 +779,10 @@ int dpgo_group_verify(dpgo_group_t *h, const double *X, int ld, const dpgo_cert_
                       const double *V0, int ldv0, dpgo_cert_result_t *result, double *x, int ldx, dpgo_cert_factor_t *factor) {
   if (!h || !h->grp || !X || !opts || !result || !factor) return -1;
   return guarded([&] {
-    dpgo::CertOptions o;
-    o.eta = opts->eta; o.tau = opts->tau; o.max_iters = opts->max_iters; o.precondition = opts->precondition;
-    o.stop_on_negative = opts->stop_on_negative; o.refresh_every = opts->refresh_every; o.seed = opts->seed;
     dpgo::CertResult r;
     dpgo::CertFactor f;
-    const int rc = h->grp->verify(X, ld, o, max_factor_bytes, V0, ldv0, r, x, ldx, f);
-    result->status = r.status; result->iterations = r.iterations; result->restarts = r.restarts;
-    result->theta = r.theta; result->residual = r.residual; result->S_norm_est = r.S_norm_est;
-    result->stationarity = r.stationarity;
+    const int rc = h->grp->verify(X, ld, to_cpp(*opts), max_factor_bytes, V0, ldv0, r, x, ldx, f);
+    to_c(r, result);
     put_factor(f, factor);
     return rc;
   });
@@ -1668,24 +823,7 @@ int dpgo_edge_eval_run(dpgo_edge_eval_t *h, const double *X, int ld, int loss, d
   return guarded([&] {
     dpgo::EdgeSummary s;
     const int rc = h->p->run(X, ld, loss, loss_reg, s_rot, s_trans, rho, weight, &s);
-    if (rc == 0 && sum) {
-      sum->F = s.F; sum->F_intra = s.F_intra; sum->F_inter = s.F_inter; sum->weight_min = s.weight_min;
-      sum->num_inter = s.num_inter; sum->num_downweighted = s.num_downweighted;
-    }
-    return rc;
-  });
-}
-
-int dpgo_debug_edge_eval_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *s_rot,
-                              double *s_trans, double *rho, double *weight, dpgo_edge_summary_t *sum) {
-  if (!g) return -1;
-  return guarded([&] {
-    dpgo::EdgeSummary s;
-    const int rc = dpgo::edge_eval_host(g->g, X, ld, loss, loss_reg, s_rot, s_trans, rho, weight, &s);
-    if (rc == 0 && sum) {
-      sum->F = s.F; sum->F_intra = s.F_intra; sum->F_inter = s.F_inter; sum->weight_min = s.weight_min;
-      sum->num_inter = s.num_inter; sum->num_downweighted = s.num_downweighted;
-    }
+    if (rc == 0 && sum) to_c(s, sum);
     return rc;
   });
 }
@@ -1708,14 +846,10 @@ int dpgo_graph_scale_edges(const dpgo_graph_t *g, const double *w, dpgo_graph_t 
   });
 }
 
-int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
-                                 const dpgo_cert_options_t *cert_opts, long long max_factor_bytes,
-                                 dpgo_cert_result_t *cert_result, dpgo_cert_factor_t *cert_factor,
-                                 dpgo_edge_summary_t *edge_summary, double *x, int ldx) {
-  if (!g || !X || !cert_result || !cert_factor) return -1;
-  dpgo_cert_options_t co;
-  dpgo_cert_options_default(&co);
-  if (cert_opts) co = *cert_opts;
+// The re-weighted problem at X: the loss weights w_e(X) of every edge (and their summary), the graph with kappa_e, tau_e
+// scaled by them, a trivial-loss group of all its nodes.  `call` runs on that group; everything is freed again.  0 / -1
+static int with_reweighted_group(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                 dpgo_edge_summary_t *edge_summary, const std::function<int(dpgo_group_t *)> &call) {
   const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
   std::vector<double> w((size_t)std::max(m, 1));
   dpgo_edge_eval_t *ev = nullptr;
@@ -1733,10 +867,23 @@ int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double
     std::iota(ids.begin(), ids.end(), 0);
     rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
   }
-  if (rc == 0) rc = dpgo_group_verify(grp, X, ld, &co, max_factor_bytes, nullptr, 0, cert_result, x, ldx, cert_factor);
+  if (rc == 0) rc = call(grp);
   dpgo_group_free(grp);
   dpgo_graph_free(gw);
   return rc == 0 ? 0 : -1;
+}
+
+int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                 const dpgo_cert_options_t *cert_opts, long long max_factor_bytes,
+                                 dpgo_cert_result_t *cert_result, dpgo_cert_factor_t *cert_factor,
+                                 dpgo_edge_summary_t *edge_summary, double *x, int ldx) {
+  if (!g || !X || !cert_result || !cert_factor) return -1;
+  dpgo_cert_options_t co;
+  dpgo_cert_options_default(&co);
+  if (cert_opts) co = *cert_opts;
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+    return dpgo_group_verify(grp, X, ld, &co, max_factor_bytes, nullptr, 0, cert_result, x, ldx, cert_factor);
+  });
 }
 
 // ---- marginal pose covariances (cov.h) ----
@@ -1746,11 +893,7 @@ int dpgo_group_covariance(dpgo_group_t *h, const double *X, int ld, int anchor, 
   return guarded([&] {
     dpgo::CovResult r;
     const int rc = h->grp->covariance(X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, r);
-    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
-    result->max_front = r.max_front; result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min;
-    result->pivot_max = r.pivot_max; result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s;
-    result->numeric_ms = r.numeric_ms; result->factor_ms = r.factor_ms; result->selinv_ms = r.selinv_ms;
-    result->selinv_flops = r.selinv_flops;
+    to_c(r, result);
     return rc;
   });
 }
@@ -1765,27 +908,9 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
                                      int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                      double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary) {
   if (!g || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
-  const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
-  std::vector<double> w((size_t)std::max(m, 1));
-  dpgo_edge_eval_t *ev = nullptr;
-  dpgo_graph_t *gw = nullptr;
-  dpgo_group_t *grp = nullptr;
-  int rc = dpgo_edge_eval_create(g, device, &ev);
-  if (rc == 0) rc = dpgo_edge_eval_run(ev, X, ld, loss, loss_reg, nullptr, nullptr, nullptr, w.data(), edge_summary);
-  dpgo_edge_eval_free(ev);
-  if (rc == 0) rc = dpgo_graph_scale_edges(g, w.data(), &gw);
-  if (rc == 0) {
-    dpgo_options_t opt;
-    dpgo_options_driver(&opt, 0, 1);
-    opt.max_iterations = 0;
-    std::vector<int> ids(nn);
-    std::iota(ids.begin(), ids.end(), 0);
-    rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
-  }
-  if (rc == 0) rc = dpgo_group_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, result);
-  dpgo_group_free(grp);
-  dpgo_graph_free(gw);
-  return rc == 0 ? 0 : -1;
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+    return dpgo_group_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, result);
+  });
 }
 
 // ---- joint covariances of arbitrary pose pairs and the gate (pairs.h) ----
@@ -1796,12 +921,7 @@ int dpgo_group_pair_covariance(dpgo_group_t *h, const double *X, int ld, int anc
   return guarded([&] {
     dpgo::PairsResult r;
     const int rc = h->grp->pair_covariance(X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, r);
-    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
-    result->max_front = r.max_front; result->columns = r.columns; result->batches = r.batches; result->reserved = 0;
-    result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
-    result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s; result->factor_ms = r.factor_ms;
-    result->solve_ms = r.solve_ms; result->gate_ms = r.gate_ms; result->solve_flops = r.solve_flops;
-    result->factor_bytes = r.factor_bytes;
+    to_c(r, result);
     return rc;
   });
 }
@@ -1811,53 +931,9 @@ int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, con
                                           double *joint, double *rel, double *gate, dpgo_pairs_result_t *result,
                                           dpgo_edge_summary_t *edge_summary) {
   if (!g || !X || !result || npairs < 0 || (npairs > 0 && (!pairs || !joint || !rel)) || (candidates && !gate)) return -1;
-  const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
-  std::vector<double> w((size_t)std::max(m, 1));
-  dpgo_edge_eval_t *ev = nullptr;
-  dpgo_graph_t *gw = nullptr;
-  dpgo_group_t *grp = nullptr;
-  int rc = dpgo_edge_eval_create(g, device, &ev);
-  if (rc == 0) rc = dpgo_edge_eval_run(ev, X, ld, loss, loss_reg, nullptr, nullptr, nullptr, w.data(), edge_summary);
-  dpgo_edge_eval_free(ev);
-  if (rc == 0) rc = dpgo_graph_scale_edges(g, w.data(), &gw);
-  if (rc == 0) {
-    dpgo_options_t opt;
-    dpgo_options_driver(&opt, 0, 1);
-    opt.max_iterations = 0;
-    std::vector<int> ids(nn);
-    std::iota(ids.begin(), ids.end(), 0);
-    rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
-  }
-  if (rc == 0) rc = dpgo_group_pair_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, result);
-  dpgo_group_free(grp);
-  dpgo_graph_free(gw);
-  return rc == 0 ? 0 : -1;
-}
-
-int dpgo_debug_pairs_vsolve_baseline(dpgo_group_t *h, const double *X, int ld, int anchor, int ncols, double *ms) {
-  if (!h || !h->grp || !X || !ms || ncols < 1) return -1;
-  return guarded([&] { return h->grp->pairs_vsolve_baseline(X, ld, anchor, ncols, ms); });
-}
-
-int dpgo_debug_pairs_plan(int dof, int anchor, const int *pairs, int npairs, int *poses, int *pair_col, int *sizes) {
-  if (dof < 1 || npairs < 0 || (npairs > 0 && (!pairs || !poses || !pair_col)) || !sizes) return -1;
-  return guarded([&] {
-    const dpgo::PairsPlan pl = dpgo::pairs_plan(dof, anchor, pairs, npairs);
-    std::copy(pl.poses.begin(), pl.poses.end(), poses);
-    std::copy(pl.pair_col.begin(), pl.pair_col.end(), pair_col);
-    sizes[0] = (int)pl.poses.size(); sizes[1] = pl.columns; sizes[2] = pl.batches; sizes[3] = pl.kb;
-    return 0;
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+    return dpgo_group_pair_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, result);
   });
-}
-
-int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const double *joint, const double *cand, double *rel,
-                          double *gate) {
-  if ((d != 2 && d != 3) || !recp || !recq || !joint || !rel || (cand && !gate)) return -1;
-  if (cand && (!(cand[d * d + d] > 0) || !(cand[d * d + d + 1] > 0))) return -1;
-  const int DD = d == 3 ? 36 : 9;
-  if (d == 3) dpgo::pairs_one<3>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
-  else dpgo::pairs_one<2>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
-  return 0;
 }
 
 // ---- Newton polish (polish.h) ----
@@ -1872,17 +948,9 @@ int dpgo_group_polish(dpgo_group_t *h, const double *X, int ld, const dpgo_polis
                       double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result) {
   if (!h || !h->grp || !X || !Xout || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
   return guarded([&] {
-    dpgo::PolishOptions o;
-    if (opt) { o.max_steps = opt->max_steps; o.max_tries = opt->max_tries; o.rel_tol = opt->rel_tol; o.grad_tol = opt->grad_tol; }
     dpgo::PolishResult r;
-    const int rc = h->grp->polish(X, ld, opt ? opt->anchor : 0, o, max_bytes, Xout, ldout, log, log_cap, r);
-    result->outcome = r.outcome; result->steps = r.steps; result->factorisations = r.factorisations;
-    result->indefinite = r.indefinite; result->F_initial = r.F_initial; result->F_final = r.F_final;
-    result->grad_initial = r.grad_initial; result->grad_final = r.grad_final; result->hmax = r.hmax;
-    result->mu_final = r.mu_final; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
-    result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels; result->max_front = r.max_front;
-    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
-    result->factor_ms = r.factor_ms; result->solve_ms = r.solve_ms; result->other_ms = r.other_ms;
+    const int rc = h->grp->polish(X, ld, opt ? opt->anchor : 0, to_cpp(opt), max_bytes, Xout, ldout, log, log_cap, r);
+    to_c(r, result);
     return rc;
   });
 }
@@ -1893,24 +961,12 @@ int dpgo_group_robust_polish(dpgo_group_t *h, const dpgo_graph_t *g, const doubl
                              dpgo_polish_result_t *result, dpgo_edge_summary_t *edge_summary) {
   if (!h || !h->grp || !g || !X || !Xout || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
   return guarded([&] {
-    dpgo::PolishOptions o;
-    if (opt) { o.max_steps = opt->max_steps; o.max_tries = opt->max_tries; o.rel_tol = opt->rel_tol; o.grad_tol = opt->grad_tol; }
     dpgo::PolishResult r;
     dpgo::EdgeSummary s;
-    const int rc = h->grp->robust_polish(g->g, X, ld, loss, loss_reg, curvature, opt ? opt->anchor : 0, o, max_bytes, Xout, ldout, log,
-                                         log_cap, r, edge_summary ? &s : nullptr);
-    result->outcome = r.outcome; result->steps = r.steps; result->factorisations = r.factorisations;
-    result->indefinite = r.indefinite; result->F_initial = r.F_initial; result->F_final = r.F_final;
-    result->grad_initial = r.grad_initial; result->grad_final = r.grad_final; result->hmax = r.hmax;
-    result->mu_final = r.mu_final; result->pivot_min = r.pivot_min; result->pivot_max = r.pivot_max;
-    result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels; result->max_front = r.max_front;
-    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
-    result->factor_ms = r.factor_ms; result->solve_ms = r.solve_ms; result->other_ms = r.other_ms;
-    if (rc == 0 && edge_summary && r.outcome != dpgo::POLISH_SKIPPED) {
-      edge_summary->F = s.F; edge_summary->F_intra = s.F_intra; edge_summary->F_inter = s.F_inter;
-      edge_summary->weight_min = s.weight_min; edge_summary->num_inter = s.num_inter;
-      edge_summary->num_downweighted = s.num_downweighted;
-    }
+    const int rc = h->grp->robust_polish(g->g, X, ld, loss, loss_reg, curvature, opt ? opt->anchor : 0, to_cpp(opt), max_bytes, Xout,
+                                         ldout, log, log_cap, r, edge_summary ? &s : nullptr);
+    to_c(r, result);
+    if (rc == 0 && edge_summary && r.outcome != dpgo::POLISH_SKIPPED) to_c(s, edge_summary);
     return rc;
   });
 }
@@ -1923,11 +979,7 @@ int dpgo_group_robust_covariance(dpgo_group_t *h, const dpgo_graph_t *g, const d
     dpgo::CovResult r;
     const int rc = h->grp->robust_covariance(g->g, X, ld, loss, loss_reg, curvature, anchor, max_bytes, pairs, npairs, marginals,
                                              cross, r);
-    result->outcome = r.outcome; result->unknowns = r.unknowns; result->fronts = r.fronts; result->levels = r.levels;
-    result->max_front = r.max_front; result->device_bytes = r.device_bytes; result->pivot_min = r.pivot_min;
-    result->pivot_max = r.pivot_max; result->stationarity = r.stationarity; result->symbolic_s = r.symbolic_s;
-    result->numeric_ms = r.numeric_ms; result->factor_ms = r.factor_ms; result->selinv_ms = r.selinv_ms;
-    result->selinv_flops = r.selinv_flops;
+    to_c(r, result);
     return rc;
   });
 }
@@ -1946,12 +998,6 @@ int dpgo_group_robust_matrix(dpgo_group_t *h, const dpgo_graph_t *g, const doubl
                              int *col, double *val, long long cap, long long *nnz) {
   if (!h || !h->grp || !g || !X || !nnz) return -1;
   return guarded([&] { return h->grp->robust_matrix(g->g, X, ld, loss, loss_reg, ptr, col, val, cap, nnz); });
-}
-
-int dpgo_debug_robust_edge_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *w, double *c,
-                                double *rows, double *ghat) {
-  if (!g) return -1;
-  return guarded([&] { return dpgo::robust_edge_host(g->g, X, ld, loss, loss_reg, w, c, rows, ghat); });
 }
 
 // ---- the Riemannian staircase (stair.h) ----
@@ -2007,11 +1053,6 @@ int dpgo_group_stair_retract(dpgo_group_t *h, const double *Y, int ldy, const do
 int dpgo_group_stair_round(dpgo_group_t *h, const double *Y, int ldy, double *B, double *sigma, double *Xhat, int ldx) {
   if (!h || !h->grp || !Y || !B || !sigma || !Xhat) return -1;
   return guarded([&] { return h->grp->stair_round(Y, ldy, B, sigma, Xhat, ldx); });
-}
-
-int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {
-  if (!A || !B || !theta || !C || !used) return -1;
-  return guarded([&] { return dpgo::rayleigh_ritz(ns, nblk, A, B, theta, C, used); });
 }
 
 }  // extern "C"

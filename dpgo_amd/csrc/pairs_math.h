@@ -1,6 +1,6 @@
 // The arithmetic of one pair of poses (pairs.h): the relative pose, the Jacobian of its perturbation, the relative covariance,
 // the residual of a candidate measurement and its Mahalanobis distance.  Plain fp64 in a fixed order, no memory but the
-// caller's arrays: k_pairs_gate (pairs.hip) runs it with one lane per pair, dpgo_debug_pairs_gate (capi.cpp) on the host.
+// caller's arrays: k_pairs_gate (pairs.hip) runs it with one lane per pair, dpgo_debug_pairs_gate (capi_debug.cpp) on the host.
 //
 // A pose record is t (D doubles), then Y = R^T row-major (D x D), as everywhere in the library.
 #pragma once
