@@ -270,6 +270,12 @@ SYMBOLS = {
     "dpgo_group_robust_matrix": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
                                            C.POINTER(C.c_longlong)]),
     "dpgo_debug_robust_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP]),
+    "dpgo_gnc_options_default": (None, [C.c_void_p]),
+    "dpgo_group_gnc": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_void_p, _IP, C.c_longlong, _DP, C.c_int, _DP, _DP, C.c_int,
+                                 C.c_void_p]),
+    "dpgo_group_gnc_eval": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_double, _IP, _DP, _DP, _DP, _DP,
+                                      _DP]),
+    "dpgo_debug_gnc_weight_host": (C.c_int, [C.c_int, C.c_double, C.c_double, _DP, C.c_int, _DP, _DP]),
     "dpgo_staircase_options_default": (None, [C.c_void_p]),
     "dpgo_group_staircase": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int,
                                        C.c_void_p]),
@@ -1216,6 +1222,48 @@ class NodeGroup:
                                "that is not the group's, a bad loss, loss_reg, curvature or anchor, or bad sizes or options)")
         return Xout, r, _polish_log(log, r), sm
 
+    def gnc(self, graph, X, opt=None, robust_set=None, max_bytes=0):
+        """Graduated non-convexity (dpgo_group_gnc): GNC-TLS or GNC-GM outlier rejection on the device.  Level 0 solves with
+        unit weights; every later level re-weights the robust set -- the inter-node edges of `graph`, or the edges with
+        robust_set[e] != 0 -- in closed form from the surrogate rho_mu and solves the weighted problem with `polish`'s loop,
+        while mu walks the surrogate from convex to the truncated (TLS) or Geman-McClure loss.  The group is a trivial-loss
+        group that hosts every node.  opt: GncOptions (None: the defaults).  Returns (Xout, weights, GncResult, log): the
+        point (X itself for GNC_SKIPPED), one weight per edge, the result struct, and one row per level k >= 1 of (mu,
+        F_mu(X_{k-1}), F_w(X_{k-1}), F_w(X_k), F_mu(X_k), inner steps, inner outcome, the counts of w == 0, w == 1 and
+        0 < w < 1 over the robust set)."""
+        X, ld = _fcol(X)
+        o = GncOptions() if opt is None else opt
+        Xout, w = np.array(X, order="F"), np.ones(graph.num_edges)
+        log = np.zeros((max(int(o.max_levels), 0), 10))
+        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
+        if rs is not None and rs.shape != (graph.num_edges,):
+            raise ValueError("gnc: robust_set must have one entry per edge")
+        r = GncResult()
+        if lib().dpgo_group_gnc(self._h, graph._h, _dp(X), ld, C.byref(o), None if rs is None else _ip(rs), int(max_bytes), _dp(Xout),
+                                Xout.shape[0], _dp(w), _dp(log) if len(log) else None, len(log), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_gnc failed (a robust-loss group, a group that does not host every node, a graph that is "
+                               "not the group's, a bad kind, barc2, mu_step, max_levels or anchor, or bad sizes or options)")
+        return Xout, w, r, log[:r.levels].copy()
+
+    def gnc_eval(self, graph, X, kind, mu, barc2, robust_set=None, w_in=None, w_start=None):
+        """Debug: one edge pass of graduated non-convexity at X (dpgo_group_gnc_eval).  w_in None: WEIGH -- the weight array
+        starts as w_start (default: ones) and weight_mu(s_e) is written on the robust set; otherwise FIXED on w_in.  Returns
+        (s_rot, s_trans, w, sums): w the array behind the pass; sums = (sum_{not R} s, sum_R w s, sum_R rho_mu(s), max_R s,
+        min_R w, the counts of w == 0, w == 1, 0 < w < 1 over R)."""
+        X, ld = _fcol(X)
+        m = graph.num_edges
+        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
+        wi = None if w_in is None else np.ascontiguousarray(w_in, np.float64)
+        w = np.ones(m) if w_start is None else np.array(w_start, np.float64)
+        if any(a is not None and a.shape != (m,) for a in (rs, wi, w)):
+            raise ValueError("gnc_eval: robust_set, w_in and w_start must have one entry per edge")
+        sr, st, sums = np.zeros(m), np.zeros(m), np.zeros(8)
+        if lib().dpgo_group_gnc_eval(self._h, graph._h, _dp(X), ld, int(kind), float(mu), float(barc2), None if rs is None else _ip(rs),
+                                     _dpn(wi), _dp(sr), _dp(st), _dp(w), _dp(sums)) != 0:
+            raise RuntimeError("dpgo_group_gnc_eval failed (a robust-loss group, a group that does not host every node, a graph that "
+                               "is not the group's, a bad kind, mu or barc2, or bad sizes)")
+        return sr, st, w, sums
+
     def robust_covariance(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, pairs=None, max_bytes=0, graph=None):
         """Marginal pose covariances of the ROBUST objective at X (dpgo_group_robust_covariance): `covariance` on the true
         Hessian (curvature 1) or the re-weighted one (curvature 0).  COV_NOT_PD is a legitimate answer where the negative
@@ -1985,6 +2033,48 @@ class PolishResult(C.Structure):
                 ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
                 ("device_bytes", C.c_longlong), ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("factor_ms", C.c_double),
                 ("solve_ms", C.c_double), ("other_ms", C.c_double)]
+
+
+GNC_TLS, GNC_GM = 0, 1
+GNC_CONVERGED, GNC_ALL_INLIERS, GNC_MAX_LEVELS, GNC_INNER_FAILED, GNC_SKIPPED = 0, 1, 2, 3, 4
+GNC_NAMES = {0: "CONVERGED", 1: "ALL_INLIERS", 2: "MAX_LEVELS", 3: "INNER_FAILED", 4: "SKIPPED"}
+
+
+class GncOptions(C.Structure):
+    """dpgo_gnc_options_t: kind (GNC_TLS, GNC_GM), barc2, mu_step, max_levels, and inner, the PolishOptions of every inner
+    solve (its anchor included).  Keywords that are fields of PolishOptions go to inner."""
+    _fields_ = [("kind", C.c_int), ("barc2", C.c_double), ("mu_step", C.c_double), ("max_levels", C.c_int), ("inner", PolishOptions)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().dpgo_gnc_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k in dict(PolishOptions._fields_):
+                setattr(self.inner, k, v)
+            elif k in dict(self._fields_) and k != "inner":
+                setattr(self, k, v)
+            else:
+                raise TypeError("GncOptions has no field %r" % k)
+
+
+class GncResult(C.Structure):
+    """dpgo_gnc_result_t: the outcome of NodeGroup.gnc, its levels and inner counts, mu at both ends, F at unit weights at the
+    start and F_w, F_mu at the end, the counts of the final weights over the robust set, the bytes and the times."""
+    _fields_ = [("outcome", C.c_int), ("levels", C.c_int), ("steps", C.c_int), ("factorisations", C.c_int), ("inner_outcome", C.c_int),
+                ("mu_initial", C.c_double), ("mu_final", C.c_double), ("s_max_initial", C.c_double), ("F_initial", C.c_double),
+                ("F_weighted_final", C.c_double), ("F_surrogate_final", C.c_double), ("num_robust", C.c_int), ("num_zero", C.c_int),
+                ("num_one", C.c_int), ("num_between", C.c_int), ("num_outliers", C.c_int), ("device_bytes", C.c_longlong),
+                ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("edge_ms", C.c_double), ("inner_ms", C.c_double)]
+
+
+def gnc_weight_debug(kind, mu, barc2, s):
+    """Debug, no GPU: (w, rho) of graduated non-convexity's surrogate at the values s >= 0, through the kernel's own arithmetic
+    (dpgo_debug_gnc_weight_host)."""
+    s = np.ascontiguousarray(s, np.float64).ravel()
+    w, rho = np.zeros(len(s)), np.zeros(len(s))
+    if lib().dpgo_debug_gnc_weight_host(int(kind), float(mu), float(barc2), _dp(s), len(s), _dp(w), _dp(rho)) != 0:
+        raise ValueError("dpgo_debug_gnc_weight_host failed (a kind outside {0, 1}, mu or barc2 not finite and positive, a negative s)")
+    return w, rho
 
 
 STAIR_SOLVED, STAIR_MAX_RANK, STAIR_SADDLE, STAIR_SKIPPED = 0, 1, 2, 3

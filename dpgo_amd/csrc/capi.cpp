@@ -1000,6 +1000,37 @@ int dpgo_group_robust_matrix(dpgo_group_t *h, const dpgo_graph_t *g, const doubl
   return guarded([&] { return h->grp->robust_matrix(g->g, X, ld, loss, loss_reg, ptr, col, val, cap, nnz); });
 }
 
+// ---- graduated non-convexity (gnc.h) ----
+void dpgo_gnc_options_default(dpgo_gnc_options_t *opt) {
+  if (!opt) return;
+  const dpgo::GncOptions o;
+  opt->kind = o.kind; opt->barc2 = o.barc2; opt->mu_step = o.mu_step; opt->max_levels = o.max_levels;
+  dpgo_polish_options_default(&opt->inner);
+}
+
+int dpgo_group_gnc(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, const dpgo_gnc_options_t *opt,
+                   const int *robust_set, long long max_bytes, double *Xout, int ldout, double *weights, double *log, int log_cap,
+                   dpgo_gnc_result_t *result) {
+  if (!h || !h->grp || !g || !X || !Xout || !weights || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::GncOptions o;
+    if (opt) {
+      o.kind = opt->kind; o.barc2 = opt->barc2; o.mu_step = opt->mu_step; o.max_levels = opt->max_levels;
+      o.inner = to_cpp(&opt->inner); o.anchor = opt->inner.anchor;
+    }
+    dpgo::GncResult r;
+    const int rc = h->grp->gnc(g->g, X, ld, o, robust_set, max_bytes, Xout, ldout, weights, log, log_cap, r);
+    result->outcome = r.outcome; result->levels = r.levels; result->steps = r.steps; result->factorisations = r.factorisations;
+    result->inner_outcome = r.inner_outcome; result->mu_initial = r.mu_initial; result->mu_final = r.mu_final;
+    result->s_max_initial = r.s_max_initial; result->F_initial = r.F_initial; result->F_weighted_final = r.F_weighted_final;
+    result->F_surrogate_final = r.F_surrogate_final; result->num_robust = r.num_robust; result->num_zero = r.num_zero;
+    result->num_one = r.num_one; result->num_between = r.num_between; result->num_outliers = r.num_outliers;
+    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
+    result->edge_ms = r.edge_ms; result->inner_ms = r.inner_ms;
+    return rc;
+  });
+}
+
 // ---- the Riemannian staircase (stair.h) ----
 void dpgo_staircase_options_default(dpgo_staircase_options_t *opt) {
   if (!opt) return;

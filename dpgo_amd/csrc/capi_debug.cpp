@@ -765,6 +765,16 @@ int dpgo_debug_robust_edge_host(const dpgo_graph_t *g, const double *X, int ld, 
   return guarded([&] { return dpgo::robust_edge_host(g->g, X, ld, loss, loss_reg, w, c, rows, ghat); });
 }
 
+int dpgo_group_gnc_eval(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int kind, double mu, double barc2,
+                        const int *robust_set, const double *w_in, double *s_rot, double *s_trans, double *w, double *sums) {
+  if (!h || !h->grp || !g || !X || !s_rot || !s_trans || !w || !sums) return -1;
+  return guarded([&] { return h->grp->gnc_eval(g->g, X, ld, kind, mu, barc2, robust_set, w_in, s_rot, s_trans, w, sums); });
+}
+
+int dpgo_debug_gnc_weight_host(int kind, double mu, double barc2, const double *s, int n, double *w, double *rho) {
+  return guarded([&] { return dpgo::gnc_weight_host(kind, mu, barc2, s, n, w, rho); });
+}
+
 int dpgo_debug_pairs_vsolve_baseline(dpgo_group_t *h, const double *X, int ld, int anchor, int ncols, double *ms) {
   if (!h || !h->grp || !X || !ms || ncols < 1) return -1;
   return guarded([&] { return h->grp->pairs_vsolve_baseline(X, ld, anchor, ncols, ms); });

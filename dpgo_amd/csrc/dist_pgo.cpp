@@ -41,6 +41,15 @@
 //              (--polish is the call then) or several ranks a line "robust polish: not computed (...)" that says why not
 //              --robust_covariance FILE (likewise; empty: off)  in --covariance's file format and with its line on stdout under
 //              the prefix "robust covariance:", from dpgo_group_robust_covariance at the final X
+//              --gnc tls|gm (likewise; empty: off) --gnc_barc2 V (default 4)  after the loop and ahead of --polish / --staircase /
+//              --certify / --verify / --covariance and the robust flags, which then act on its point, for a world of one rank and any
+//              --loss: dpgo_group_gnc (graduated non-convexity, the inter-node edges as the robust set, pose 0 the anchor) on the
+//              second, trivial-loss group of --robust_polish, from the final X, and one more line on stdout
+//                  gnc: <outcome> <levels> <steps> <factorisations> <num_robust> <num_zero> <num_between> <num_outliers>
+//                       <mu_initial> <mu_final> <F_initial> <F_weighted_final> <F_surrogate_final>
+//              the result files then hold its point.  --gnc_report FILE: one line per edge, "i j in_R w s" (17 digits), s at that
+//              point; --gnc_filtered FILE: the graph without the edges of weight 0 (dpgo_graph_filter_edges) with that point, as a
+//              .g2o (dpgo_write_g2o).  With several ranks a line that says why not
 //              --staircase (likewise)  after --polish and ahead of --certify / --verify / --covariance, which then act on its
 //              result, for the trivial loss and a world of one rank: dpgo_group_staircase (the Riemannian staircase: TNT at rank
 //              r, verify, an escape along the certificate's direction, the rounding and a polish) from the point so far, and
@@ -92,7 +101,8 @@ int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
-  std::string edge_report, covariance, gate_candidates, gate_report, robust_covariance;
+  std::string edge_report, covariance, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
+  double gnc_barc2 = 4.0;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -108,7 +118,9 @@ int main(int argc, char **argv) {
              "  --loss arg (=trivial)   trivial, huber or welsch\n  --accelerated arg (=true)\n  --save arg (=true)\n  --gpu arg (=0)\n"
              "  --robust_polish         robust loss, one rank: Newton polish of the robust objective after the loop; builds a second,\n"
              "                          trivial-loss group of the graph (seconds of set-up at 100 000 poses)\n"
-             "  --robust_covariance arg likewise: marginal covariances on the robust Hessian, written to the file named\n");
+             "  --robust_covariance arg likewise: marginal covariances on the robust Hessian, written to the file named\n"
+             "  --gnc arg               tls or gm, one rank: graduated non-convexity after the loop (outlier rejection on the inter-node\n"
+             "                          edges); --gnc_barc2 arg (=4) the inlier threshold, --gnc_report arg / --gnc_filtered arg its files\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
@@ -117,6 +129,10 @@ int main(int argc, char **argv) {
     else if (a == "--robust_polish") robust_polish = true;
     else if (a.compare(0, 16, "--robust_polish=") == 0) robust_polish = parse_bool(argv[i] + 16);
     else if (const char *v = val("--robust_covariance")) robust_covariance = v;
+    else if (const char *v = val("--gnc_barc2")) gnc_barc2 = atof(v);
+    else if (const char *v = val("--gnc_report")) gnc_report = v;
+    else if (const char *v = val("--gnc_filtered")) gnc_filtered = v;
+    else if (const char *v = val("--gnc")) gnc = v;
     else if (a == "--staircase") staircase = true;
     else if (a.compare(0, 12, "--staircase=") == 0) staircase = parse_bool(argv[i] + 12);
     else if (a == "--verify") verify = true;
@@ -246,6 +262,72 @@ int main(int argc, char **argv) {
     }
     return dpgo_group_scatter_global(grp, out, ld);
   };
+  // the robust objective and graduated non-convexity: a trivial-loss group of the same graph, built once for all their flags
+  dpgo_group_t *post = nullptr;
+  auto post_group = [&]() -> int {
+    if (post) return 0;
+    dpgo_options_t po;
+    dpgo_options_driver(&po, 0, accelerated);
+    po.max_iterations = 0;
+    return dpgo_group_create(g, ids.data(), per, &po, gpu, &post);
+  };
+  if (!gnc.empty()) {
+    if (gnc != "tls" && gnc != "gm") {
+      fprintf(stderr, "--gnc takes tls or gm.\n");
+      return -1;
+    }
+    if (world > 1) {
+      if (root) printf("gnc: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0), w(m, 1.0);
+      dpgo_gnc_options_t go;
+      dpgo_gnc_options_default(&go);
+      go.kind = gnc == "tls" ? DPGO_GNC_TLS : DPGO_GNC_GM;
+      go.barc2 = gnc_barc2;
+      dpgo_gnc_result_t gr;
+      if (final_point(Xc.data()) != 0 || post_group() != 0 ||
+          dpgo_group_gnc(post, g, Xc.data(), ld, &go, nullptr, 0, Z.data(), ld, w.data(), nullptr, 0, &gr) != 0)
+        return -1;
+      printf("gnc: %s %d %d %d %d %d %d %d %.17g %.17g %.17g %.17g %.17g\n",
+             gr.outcome == DPGO_GNC_CONVERGED ? "CONVERGED" : gr.outcome == DPGO_GNC_ALL_INLIERS ? "ALL_INLIERS"
+             : gr.outcome == DPGO_GNC_MAX_LEVELS ? "MAX_LEVELS" : gr.outcome == DPGO_GNC_INNER_FAILED ? "INNER_FAILED" : "SKIPPED",
+             gr.levels, gr.steps, gr.factorisations, gr.num_robust, gr.num_zero, gr.num_between, gr.num_outliers, gr.mu_initial,
+             gr.mu_final, gr.F_initial, gr.F_weighted_final, gr.F_surrogate_final);
+      if (gr.outcome != DPGO_GNC_SKIPPED) {
+        if (!gnc_report.empty()) {
+          std::vector<int> I(m), J(m);
+          std::vector<double> sr(m), st(m), wb(m), sums(8);
+          if (dpgo_graph_edges(g, I.data(), J.data(), nullptr, nullptr, nullptr, nullptr) != 0 ||
+              dpgo_group_gnc_eval(post, g, Z.data(), ld, go.kind, gr.mu_final > 0 ? gr.mu_final : 1.0, go.barc2, nullptr, w.data(), sr.data(),
+                                  st.data(), wb.data(), sums.data()) != 0)
+            return -1;
+          std::vector<int> first(nn);
+          for (int a = 0; a < nn; a++) first[a] = dpgo_graph_node_offset(g, a);   // (-1: a node without an edge)
+          auto node_of = [&](int p) {
+            int r = 0;
+            for (int a = 0; a < nn; a++)
+              if (first[a] >= 0 && p >= first[a]) r = a;
+            return r;
+          };
+          FILE *f = fopen(gnc_report.c_str(), "w");
+          if (!f) { fprintf(stderr, "Cannot write %s.\n", gnc_report.c_str()); return -1; }
+          for (int e = 0; e < m; e++)
+            fprintf(f, "%d %d %d %.17g %.17g\n", I[e], J[e], node_of(I[e]) != node_of(J[e]) ? 1 : 0, w[e], sr[e] + st[e]);
+          fclose(f);
+        }
+        if (!gnc_filtered.empty()) {
+          std::vector<unsigned char> keep(m);
+          for (int e = 0; e < m; e++) keep[e] = w[e] != 0.0;
+          dpgo_graph_t *kept = nullptr;
+          if (dpgo_graph_filter_edges(g, keep.data(), &kept) != 0) return -1;
+          const int rc = dpgo_write_g2o(kept, Z.data(), ld, gnc_filtered.c_str());
+          dpgo_graph_free(kept);
+          if (rc != 0) return -1;
+        }
+        Xpol.swap(Z);
+      }
+    }
+  }
   if (polish) {
     if (loss != 0) {
       if (root) printf("polish: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
@@ -254,7 +336,7 @@ int main(int argc, char **argv) {
     } else {
       std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0);
       dpgo_polish_result_t pr;
-      if (dpgo_group_scatter_global(grp, Xc.data(), ld) != 0 ||
+      if (final_point(Xc.data()) != 0 ||
           dpgo_group_polish(grp, Xc.data(), ld, nullptr, 0, Z.data(), ld, nullptr, 0, &pr) != 0)
         return -1;
       printf("polish: %s %d %d %d %.17g %.17g %.17g %.17g\n",
@@ -282,15 +364,6 @@ int main(int argc, char **argv) {
       if (sr.outcome != DPGO_STAIR_SKIPPED) Xpol.swap(Z);
     }
   }
-  // the robust objective: a trivial-loss group of the same graph, built once for both flags
-  dpgo_group_t *post = nullptr;
-  auto post_group = [&]() -> int {
-    if (post) return 0;
-    dpgo_options_t po;
-    dpgo_options_driver(&po, 0, accelerated);
-    po.max_iterations = 0;
-    return dpgo_group_create(g, ids.data(), per, &po, gpu, &post);
-  };
   if (robust_polish) {
     if (loss == 0) {
       if (root) printf("robust polish: not computed (the loss is trivial: --polish is the call)\n");

@@ -31,6 +31,7 @@
 #include "graph.h"
 #include "kernels.h"
 #include "pairs.h"
+#include "gnc.h"
 #include "polish.h"
 #include "robust.h"
 #include "schedule.h"
@@ -214,6 +215,16 @@ class Group {
                      double *s_trans, double *rho);
   int robust_matrix(const Graph &g, const double *X, int ld, int loss, double loss_reg, int *ptr, int *col, double *val, long long cap,
                     long long *nnz);
+  // ---- graduated non-convexity (gnc.h, gnc.cpp): outlier rejection on the robust objective's plan, one polish_loop per level
+  // with the weights of k_gnc_edge.  The restrictions of the robust objective; robust_set (optional, one int per edge): the
+  // edges the loss may touch, instead of the inter rule.  Xout: the point (written unless SKIPPED), weights: num_edges, log
+  // (optional): log_cap rows of GNC_LOG_COLS doubles, one per level k >= 1
+  int gnc(const Graph &g, const double *X, int ld, const GncOptions &o, const int *robust_set, long long max_bytes, double *Xout,
+          int ldout, double *weights, double *log, int log_cap, GncResult &out);
+  // debug: one edge pass at X.  w_in null: WEIGH, the array starting as the caller's w; otherwise FIXED on w_in.  s_rot,
+  // s_trans, w: num_edges each (w: the array behind the pass); sums: the eight of GncSummaryDev as doubles
+  int gnc_eval(const Graph &g, const double *X, int ld, int kind, double mu, double barc2, const int *robust_set, const double *w_in,
+               double *s_rot, double *s_trans, double *w, double *sums);
   // ---- joint covariances of arbitrary pose pairs and the loop-closure gate (pairs.h, pairs.cpp): the covariance's factor,
   // the columns of H^-1 of the poses asked for by spd_msolve_device.  pairs: npairs x 2 global poses, any two; candidates
   // (optional): npairs x (d^2 + d + 2) doubles, R~ row-major, t~, kappa, tau; joint: npairs x 3 x dof^2 (S_pp, S_pq, S_qq);
@@ -646,12 +657,17 @@ class Group {
   struct RobustState;   // the lists and buffers of the robust objective (robust.cpp), allocated by the first call that is not refused
   RobustState *rob_ = nullptr;
   void robust_release();
-  int robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who);
+  int robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who,
+                   const int *robust_set = nullptr);
   long long robust_remain() const;
   void robust_alloc();
   void robust_eval(const double *Xdev, int loss, double loss_reg, bool with_rows, int fslot);
   void robust_hessian_launch(int arow, int curvature);
   void robust_summary(EdgeSummary *sum);
+  // gnc.cpp: the buffers of the edge pass; the pass at a record array of the group (fslot as robust_eval), its summary read back
+  void gnc_alloc();
+  void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
+  void gnc_summary(GncSummaryDev &sd);
   int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out);   // likewise (pairs.cpp)
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;

@@ -12,18 +12,9 @@
 #include "cov_state.h"
 #include "group.h"
 #include "robust_math.h"
+#include "robust_state.h"
 
 namespace dpgo {
-
-struct Group::RobustState {
-  RobustPlan plan;
-  bool on_device = false;
-  long long bytes = 0;   // what robust_alloc allocates for the plan
-  DevBuf<double> rec, out, rows, partials, Mw, sum, grad;   // grad: dof per own row, for robust_hessian's hand-out
-  DevBuf<int64_t> counts;
-  DevBuf<int> inc_ptr, inc, blk_ptr, blk;
-  EdgeSummaryDev *sum_dev() const { return reinterpret_cast<EdgeSummaryDev *>(sum.p); }
-};
 
 void Group::robust_release() {
   delete rob_;
@@ -47,8 +38,10 @@ static bool robust_args_ok(int loss, double loss_reg, int curvature, const char 
 }
 
 // The arguments, the group (cov_begin), the pattern, and the lists of g on the group's unified own rows -- rebuilt only when
-// the records differ from those of the last call.  Nothing is allocated on the device for them here.
-int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who) {
+// the records differ from those of the last call.  Nothing is allocated on the device for them here.  robust_set (optional,
+// one int per edge): overwrites the inter word of the plan's records, which are the key of that comparison.
+int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who,
+                        const int *robust_set) {
   if (!robust_args_ok(loss, loss_reg, curvature, who)) return -1;
   if (cov_begin(X, ld, anchor) != 0) return -1;
   const int N = P0_, m = (int)g.all.size();
@@ -74,6 +67,7 @@ int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, doubl
     std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
     head[0] = row_of[head[0]];
     head[1] = row_of[head[1]];
+    if (robust_set) head[2] = robust_set[e] != 0;   // the caller's robust set instead of the inter rule (gnc.h)
     std::memcpy(&rec[(size_t)e * L], head, sizeof(head));
   }
   if (rob_ && rob_->plan.rec.size() == rec.size() && std::memcmp(rob_->plan.rec.data(), rec.data(), rec.size() * sizeof(double)) == 0)

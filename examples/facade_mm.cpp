@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|staircase|pairs <candidates.g2o>]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -17,6 +17,10 @@
 // and with `robust_polish` (a robust loss) through DPGOHashGroup::robust_newton_polish on a second, trivial-loss group of the same
 // graph (max_iterations = 0: nothing is factored for the optimiser), with the loss and loss_reg of the run; the lines of `polish`
 // with the prefix "robust polish:", the F fields those of the robust objective
+// and with `gnc` (any loss of the run) through DPGOHashGroup::graduated_non_convexity (GNC-TLS, barc2 = 4, the inter-node edges
+// as the robust set) on a second, trivial-loss group of the same graph, one line per edge and one per row of the new point:
+//   gnc: w <edge> <weight, 17 digits>        gnc: x <row> <the d entries, 17 digits>       then
+//   gnc: <CONVERGED|ALL_INLIERS|MAX_LEVELS|INNER_FAILED|SKIPPED|FAILED> <levels> <steps> <factorisations> <num_zero> <num_outliers> <F_initial> <F_weighted_final> <F_surrogate_final>
 // and with `staircase` through DPGOHashGroup::riemannian_staircase (trivial loss), one line per row of the result:
 //   staircase: x <row> <the d entries, 17 digits>       then
 //   staircase: <SOLVED|MAX_RANK|SADDLE|SKIPPED|FAILED> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
@@ -44,7 +48,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|staircase|pairs <candidates.g2o>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -169,6 +173,32 @@ int main(int argc, char **argv) {
             status == DPGO_POLISH_CONVERGED ? "CONVERGED" : status == DPGO_POLISH_MAX_STEPS ? "MAX_STEPS"
             : status == DPGO_POLISH_STALLED ? "STALLED" : status == DPGO_POLISH_SKIPPED ? "SKIPPED" : "FAILED",
             r.steps, r.factorisations, r.indefinite, r.F_initial, r.F_final, r.grad_initial, r.grad_final);
+    if (status < 0) return 1;
+  }
+  if (argc > 6 && !strcmp(argv[6], "gnc")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Z;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    DPGO::Options trivial = DPGO::Options::driver(DPGO::Loss::None, acc);
+    trivial.max_iterations = 0;
+    DPGO::DPGOHashGroup post(graph, all, trivial, 0);
+    int status = -1;
+    dpgo_gnc_result_t r = {};
+    dpgo_gnc_options_t o;
+    dpgo_gnc_options_default(&o);
+    o.barc2 = 4.0;
+    std::vector<double> w;
+    post.graduated_non_convexity(X, Z, w, &r, &status, &o);
+    for (size_t e = 0; status >= 0 && status != DPGO_GNC_SKIPPED && e < w.size(); e++) fprintf(stderr, "gnc: w %zu %.17g\n", e, w[e]);
+    for (int i = 0; status >= 0 && status != DPGO_GNC_SKIPPED && i < Z.rows(); i++) {
+      fprintf(stderr, "gnc: x %d", i);
+      for (int c = 0; c < Z.cols(); c++) fprintf(stderr, " %.17g", Z.data()[(size_t)c * Z.rows() + i]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "gnc: %s %d %d %d %d %d %.17g %.17g %.17g\n",
+            status == DPGO_GNC_CONVERGED ? "CONVERGED" : status == DPGO_GNC_ALL_INLIERS ? "ALL_INLIERS"
+            : status == DPGO_GNC_MAX_LEVELS ? "MAX_LEVELS" : status == DPGO_GNC_INNER_FAILED ? "INNER_FAILED"
+            : status == DPGO_GNC_SKIPPED ? "SKIPPED" : "FAILED",
+            r.levels, r.steps, r.factorisations, r.num_zero, r.num_outliers, r.F_initial, r.F_weighted_final, r.F_surrogate_final);
     if (status < 0) return 1;
   }
   if (argc > 6 && !strcmp(argv[6], "staircase")) {

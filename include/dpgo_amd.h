@@ -692,6 +692,68 @@ int dpgo_group_robust_matrix(dpgo_group_t *grp, const dpgo_graph_t *graph, const
 int dpgo_debug_robust_edge_host(const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg, double *w, double *c,
                                 double *rows, double *ghat);
 
+/* ---- graduated non-convexity: which measurements are outliers, and the solution without them ---- */
+/* GNC-TLS and GNC-GM (Yang, Antonante, Tzoumas, Carlone, RA-L 2020) on the device.  s_e = s_rot + s_trans as dpgo_edge_eval_run
+ * returns them; barc2 > 0 is the inlier threshold on s_e; the robust set R is the edges the loss may touch -- the inter-node
+ * edges (robust_set NULL), or those with robust_set[e] != 0 (num_edges ints, graph order).  Edges outside R keep w_e = 1.
+ *     F_w(X) = 1/2 sum_e w_e s_e,      F_mu(X) = 1/2 sum_{not R} s_e + 1/2 sum_R rho_mu(s_e)
+ *     TLS:  s <= mu/(mu+1) barc2: w = 1, rho = s;   s >= (mu+1)/mu barc2: w = 0, rho = barc2;   otherwise
+ *           w = sqrt(barc2 mu (mu+1) / s) - mu,   rho = 2 sqrt(barc2 mu (mu+1) s) - mu (barc2 + s)
+ *     GM:   delta = mu barc2:  w = delta^2 / (s + delta)^2,   rho = delta s / (s + delta)
+ *     level 0:  w = 1;  X0 = inner(X, w);  s_max = max_R s_e(X0);   R empty -> ALL_INLIERS
+ *     TLS:  2 s_max <= barc2 -> ALL_INLIERS (X0, w = 1);  mu = barc2 / (2 s_max - barc2)        GM:  mu = max(1, 2 s_max / barc2)
+ *     for k = 1 .. max_levels:
+ *         w_R = weight_mu(s(X_{k-1}));  X_k = inner(X_{k-1}, w);   an inner STALLED -> INNER_FAILED (X_{k-1} and its weights returned)
+ *         TLS:  no weight strictly between 0 and 1 -> CONVERGED;  mu = mu_step mu
+ *         GM:   mu == 1 -> CONVERGED;                              mu = max(mu / mu_step, 1)
+ *     k == max_levels without the above -> MAX_LEVELS
+ * inner is the loop of dpgo_group_polish on the weighted problem (weights fixed, options opt->inner with its anchor).  Within a
+ * level F_mu never increases.  A level whose zero weights disconnect the graph makes the Hessian singular; the shift of the
+ * inner loop either copes or stalls, and a stall is INNER_FAILED, an outcome, not an error.
+ * The restrictions of dpgo_group_robust_polish (a TRIVIAL-LOSS group that HOSTS EVERY NODE, every edge of graph a block of the
+ * group's pattern); -1 also for a kind outside {0, 1}, barc2 not finite and positive, mu_step <= 1, max_levels < 1, bad sizes.
+ * The optimiser's state is not touched.
+ *   Xout     (d+1) N x d column-major, ldout >= (d+1) N (not written for SKIPPED); weights: num_edges (likewise)
+ *   log      optional, log_cap rows of 10 doubles, one per level k >= 1: mu, F_mu(X_{k-1}), F_w(X_{k-1}), F_w(X_k), F_mu(X_k),
+ *            inner steps, inner outcome, and the counts of w == 0, w == 1, 0 < w < 1 over R
+ *   result   outcome; levels; steps and factorisations of all inner solves; the last inner outcome; mu at the first and the last
+ *            level; s_max_initial (at X0); F_initial (unit weights at X); F_w and F_mu of the last level at the final point;
+ *            num_robust = |R| and the three counts of the final weights; num_outliers: e in R with s_e > barc2 at the final
+ *            point; device_bytes and symbolic_s as dpgo_group_polish (filled for SKIPPED too); total_ms, edge_ms (the edge
+ *            passes with their read-backs), inner_ms (the inner solves).
+ * SKIPPED by dpgo_group_robust_polish's rule with the arrays of the edge pass counted in; decided before anything is allocated.
+ * dpgo_group_gnc_eval (debug): one edge pass at X.  w_in NULL: WEIGH -- the array starts as the caller's w, weight_mu(s_e) is
+ *   written on R; otherwise FIXED: the array is w_in, read on R.  s_rot, s_trans, w (the array behind the pass): num_edges each;
+ *   sums: sum_{not R} s, sum_R w s, sum_R rho_mu(s), max_R s (0 over an empty R), min_R w (+inf likewise), and the three counts.
+ * dpgo_debug_gnc_weight_host (no GPU): w and rho of n values s >= 0 through the kernel's own arithmetic. */
+#define DPGO_GNC_TLS 0
+#define DPGO_GNC_GM 1
+#define DPGO_GNC_CONVERGED 0
+#define DPGO_GNC_ALL_INLIERS 1
+#define DPGO_GNC_MAX_LEVELS 2
+#define DPGO_GNC_INNER_FAILED 3
+#define DPGO_GNC_SKIPPED 4
+typedef struct dpgo_gnc_options {
+  int kind;                      /* DPGO_GNC_TLS */
+  double barc2, mu_step;         /* 1, 1.4 */
+  int max_levels;                /* 100 */
+  dpgo_polish_options_t inner;   /* dpgo_polish_options_default */
+} dpgo_gnc_options_t;
+typedef struct dpgo_gnc_result {
+  int outcome, levels, steps, factorisations, inner_outcome;
+  double mu_initial, mu_final, s_max_initial, F_initial, F_weighted_final, F_surrogate_final;
+  int num_robust, num_zero, num_one, num_between, num_outliers;
+  long long device_bytes;
+  double symbolic_s, total_ms, edge_ms, inner_ms;
+} dpgo_gnc_result_t;
+void dpgo_gnc_options_default(dpgo_gnc_options_t *opt);
+int dpgo_group_gnc(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, const dpgo_gnc_options_t *opt,
+                   const int *robust_set, long long max_bytes, double *Xout, int ldout, double *weights, double *log, int log_cap,
+                   dpgo_gnc_result_t *result);
+int dpgo_group_gnc_eval(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int kind, double mu, double barc2,
+                        const int *robust_set, const double *w_in, double *s_rot, double *s_trans, double *w, double *sums);
+int dpgo_debug_gnc_weight_host(int kind, double mu, double barc2, const double *s, int n, double *w, double *rho);
+
 /* ---- the Riemannian staircase: escape a NEGATIVE certificate -------------------------------- */
 /* When dpgo_group_verify says NEGATIVE the point is a saddle or a local minimum of the rank-d problem, and the unit vector x it
  * returns is a direction of descent one rank up.  dpgo_group_staircase is the loop of SE-Sync (C++/SESync/src/SESync.cpp:280-440,

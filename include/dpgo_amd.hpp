@@ -323,6 +323,34 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
+  // Graduated non-convexity (dpgo_group_gnc): GNC-TLS / GNC-GM outlier rejection from X on the device.  This group is a
+  // trivial-loss group that hosts every node of its graph.  opt NULL: the defaults (TLS, barc2 1); robust_set (optional, one int
+  // per edge of the graph): the edges the loss may touch, instead of the inter-node ones.  Xout: the point (X itself for
+  // SKIPPED), weights: one per edge (0: rejected under TLS).  log (optional): 10 doubles per level (include/dpgo_amd.h).
+  // Returns true for CONVERGED and ALL_INLIERS; status: the outcome, -1 where the call failed.
+  bool graduated_non_convexity(const Matrix &X, Matrix &Xout, std::vector<Scalar> &weights, dpgo_gnc_result_t *result = nullptr,
+                               int *status = nullptr, const dpgo_gnc_options_t *opt = nullptr,
+                               const std::vector<int> *robust_set = nullptr, long long max_bytes = 0,
+                               std::vector<Scalar> *log = nullptr) const {
+    dpgo_gnc_options_t o;
+    dpgo_gnc_options_default(&o);
+    if (opt) o = *opt;
+    Xout = X;
+    weights.assign((size_t)graph_->num_edges(), 1.0);
+    if (robust_set && (int)robust_set->size() != graph_->num_edges()) {
+      if (status) *status = -1;
+      return false;
+    }
+    const int cap = o.max_levels > 0 ? o.max_levels : 0;
+    if (log) log->assign((size_t)cap * 10, 0.0);
+    dpgo_gnc_result_t r = {};
+    const int rc = dpgo_group_gnc(h_, graph_->handle(), X.data(), X.rows(), &o, robust_set ? robust_set->data() : nullptr, max_bytes,
+                                  Xout.data(), Xout.rows(), weights.data(), log && cap ? log->data() : nullptr, log ? cap : 0, &r);
+    if (log) log->resize(rc == 0 ? (size_t)std::min(cap, r.levels) * 10 : 0);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && (r.outcome == DPGO_GNC_CONVERGED || r.outcome == DPGO_GNC_ALL_INLIERS);
+  }
   // Marginal covariances of the robust objective at X (dpgo_group_robust_covariance): marginal_covariances on the true Hessian
   // (curvature 1) or the re-weighted one (0).  DPGO_COV_NOT_PD is a legitimate answer where the negative curvature of the loss
   // wins.  Arguments, returns and status as marginal_covariances.
