@@ -240,7 +240,9 @@ SYMBOLS = {
     "dpgo_group_debug_edge_offsets": (C.c_int, [C.c_void_p, _IP]),
     "dpgo_group_debug_rescale": (C.c_int, [C.c_void_p, _DP, _DP, _IP, C.c_int, _IP, C.c_int, _IP, _DP, _DP, _IP]),
     "dpgo_group_debug_cg_scalars": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _DP, C.POINTER(C.c_ulonglong), _DP, _DP, _DP,
-                                              C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
+                                              C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint), _DP, C.POINTER(C.c_ulonglong)]),
+    "dpgo_group_debug_star_sums": (C.c_int, [C.c_void_p, _DP, C.c_uint, _DP, C.POINTER(C.c_ulonglong)]),
+    "dpgo_group_debug_gated_update": (C.c_int, [C.c_void_p, C.c_ulonglong, _IP]),
     "dpgo_pcm_options_default": (None, [C.c_void_p]),
     "dpgo_pcm_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "dpgo_pcm_free": (None, [C.c_void_p]),
@@ -886,7 +888,11 @@ class SpdSolverDebug:
             raise RuntimeError("not positive definite" if rc == 1 else "dpgo_debug_spd_solver_refactor failed")
 
 
-CG_DEBUG_KINDS = ("begin_host", "begin_device", "scal0", "scal1", "scal_begin")
+CG_DEBUG_KINDS = ("begin_host", "begin_device", "scal0", "scal1", "scal_begin", "reduce_gate", "reduce")
+GATE_OPTIONS = ("max_it", "max_acc", "max_hits0", "max_hits1", "rel_tol", "step_tol", "psi", "phi")   # of a reduce_gate launch
+GATE_NODE_SCALARS = ("f", "Fk0", "Fk1", "fobj", "hits0", "hits1")                                     # ... one per local node
+GATED_BUFFERS = ("Xk", "Zc", "Zp", "gc", "gp", "Dfc", "Dfp", "GXc", "GXp", "partials", "DfE", "e_w")                             # debug_gated_update
+MAX_SLOTS = 32
 CG_RECORD_FIELDS = ("sk_M_pk", "sk_M_2", "pk_M_2", "rv", "Delta", "Delta_2", "target", "h_M_norm", "c1", "cr", "al", "kap", "be",
                     "cg_it", "max_it", "live", "stop_ord")
 
@@ -895,7 +901,14 @@ class CgDebugLaunch(C.Structure):
     """dpgo_cg_debug_launch_t"""
     _fields_ = [("kind", C.c_int), ("use_precon", C.c_int), ("max_it", C.c_int), ("slots", C.c_int), ("bits", C.c_ulonglong),
                 ("grad_tol", C.c_double), ("pgrad_tol", C.c_double), ("kappa", C.c_double), ("theta", C.c_double),
-                ("rv", _DP), ("Delta", _DP), ("target", _DP), ("partials", _DP)]
+                ("rv", _DP), ("Delta", _DP), ("target", _DP), ("partials", _DP), ("gate", C.c_void_p)]
+
+
+class GateDebug(C.Structure):
+    """dpgo_gate_debug_t"""
+    _fields_ = [(k, C.c_int) for k in ("nslots", "max_it", "max_acc", "max_hits0", "max_hits1")] + \
+               [(k, C.c_double) for k in ("rel_tol", "step_tol", "psi", "phi")] + \
+               [(k, _DP) for k in ("f", "Fk0", "Fk1", "fobj")] + [("hits0", _IP), ("hits1", _IP)]
 
 
 class InterUpdateDebug(C.Structure):
@@ -1660,19 +1673,23 @@ class NodeGroup:
         """Debug: the scalar kernels of the truncated CG on given partial sums (dpgo_group_debug_cg_scalars).  script: a list
         of dicts, each one launch: kind ("begin_host", "begin_device", "scal0", "scal1", "scal_begin"); bits, max_it, Delta
         (per node) for the begin kinds; rv, target (per node) for begin_host; use_precon, grad_tol, pgrad_tol, kappa, theta
-        for begin_device and scal_begin; partials (slots, nseg_all), optional.  Returns one dict per launch: records (a
+        for begin_device and scal_begin; partials (slots, nseg_all), optional.  kind "reduce_gate": the trial point's
+        reduction with the gate of a speculative update, gate = dict(nslots, GATE_OPTIONS, GATE_NODE_SCALARS per node); kind
+        "reduce": the plain own-row reduction of gate["nslots"] sums.  Returns one dict per launch: records (a
         list of dicts with CG_RECORD_FIELDS, the four counters as ints), masks (three ints), cg_summary (L, 3), tnt_summary
-        and dev_tnt (L, 7), flag (the host flag's value), seq (the last sequence number given out), arrived."""
+        and dev_tnt (L, 7), flag (the host flag's value), seq (the last sequence number given out), arrived; after a
+        reduce_gate or a reduce also host_scalars and dev_sums (L, MAX_SLOTS), go (the gate's word) and h_gate (its pinned
+        verdict)."""
         L, n = len(self.node_ids), len(script)
         nseg_all = self.debug_seg_layout()[0]
         arr, keep = (CgDebugLaunch * max(n, 1))(), []
 
-        def per_node(q, key):
-            v = np.ascontiguousarray(np.asarray(q.get(key, np.zeros(L)), np.float64))
+        def per_node(q, key, dtype=np.float64, ptr=_DP):
+            v = np.ascontiguousarray(np.asarray(q.get(key, np.zeros(L)), dtype))
             if v.shape != (L,):
                 raise ValueError("debug_cg_scalars: %s takes one value per node" % key)
             keep.append(v)
-            return v.ctypes.data_as(_DP)
+            return v.ctypes.data_as(ptr)
 
         for i, q in enumerate(script):
             a = arr[i]
@@ -1681,20 +1698,33 @@ class NodeGroup:
             a.grad_tol, a.pgrad_tol = float(q.get("grad_tol", 0.0)), float(q.get("pgrad_tol", 0.0))
             a.kappa, a.theta = float(q.get("kappa", 0.0)), float(q.get("theta", 0.0))
             a.rv, a.Delta, a.target = per_node(q, "rv"), per_node(q, "Delta"), per_node(q, "target")
-            a.slots, a.partials = 0, None
+            a.slots, a.partials, a.gate = 0, None, None
             if q.get("partials") is not None:
                 P = np.ascontiguousarray(np.asarray(q["partials"], np.float64))
                 if P.ndim != 2 or P.shape[1] != nseg_all:
                     raise ValueError("debug_cg_scalars: partials are (slots, nseg_all = %d)" % nseg_all)
                 keep.append(P)
                 a.slots, a.partials = P.shape[0], P.ctypes.data_as(_DP)
+            if q.get("gate") is not None:
+                g, G = q["gate"], GateDebug()
+                G.nslots = int(g["nslots"])
+                for k in GATE_OPTIONS:
+                    setattr(G, k, g.get(k, 0))
+                if q["kind"] == "reduce_gate":
+                    for k in GATE_NODE_SCALARS:
+                        ints = k.startswith("hits")
+                        setattr(G, k, per_node(g, k, np.int32 if ints else np.float64, _IP if ints else _DP))
+                keep.append(G)
+                a.gate = C.addressof(G)
         nf = len(CG_RECORD_FIELDS)
         rec, masks = np.zeros((n, L, nf)), np.zeros((n, 3), np.uint64)
         cgs, tnt, dev = np.zeros((n, L, 4)), np.zeros((n, L, 8)), np.zeros((n, L, 8))
         seq, arrived = np.zeros((n, 2), np.uint64), np.zeros(n, np.uint32)
-        if lib().dpgo_group_debug_cg_scalars(self._h, arr, n, _dp(rec), masks.ctypes.data_as(C.POINTER(C.c_ulonglong)), _dp(cgs),
-                                             _dp(tnt), _dp(dev), seq.ctypes.data_as(C.POINTER(C.c_ulonglong)),
-                                             arrived.ctypes.data_as(C.POINTER(C.c_uint))) != 0:
+        gsums, gwords = np.zeros((n, 2, L, MAX_SLOTS)), np.zeros((n, 2), np.uint64)
+        _ULP = C.POINTER(C.c_ulonglong)
+        if lib().dpgo_group_debug_cg_scalars(self._h, arr, n, _dp(rec), masks.ctypes.data_as(_ULP), _dp(cgs),
+                                             _dp(tnt), _dp(dev), seq.ctypes.data_as(_ULP),
+                                             arrived.ctypes.data_as(C.POINTER(C.c_uint)), _dp(gsums), gwords.ctypes.data_as(_ULP)) != 0:
             raise RuntimeError("dpgo_group_debug_cg_scalars failed")
         out = []
         for i in range(n):
@@ -1703,7 +1733,32 @@ class NodeGroup:
             out.append(dict(records=records, masks=[int(m) for m in masks[i]], cg_summary=cgs[i, :, :3].copy(),
                             tnt_summary=tnt[i, :, :7].copy(), dev_tnt=dev[i, :, :7].copy(), flag=int(seq[i, 0]), seq=int(seq[i, 1]),
                             arrived=int(arrived[i])))
+            if script[i]["kind"] in ("reduce_gate", "reduce"):
+                out[-1].update(host_scalars=gsums[i, 0].copy(), dev_sums=gsums[i, 1].copy(), go=int(gwords[i, 0]),
+                               h_gate=float(gwords[i, 1:2].view(np.float64)[0]))
         return out
+
+    def debug_star_sums(self, partials, valid):
+        """Debug: AMM-PGO*'s master sums on given partial sums (dpgo_group_debug_star_sums).  partials: (MAX_SLOTS, nseg_all);
+        valid: bit q = sum q was produced.  Returns dict(dev (4), host (4), flag, seq)."""
+        nseg_all = self.debug_seg_layout()[0]
+        P = np.ascontiguousarray(np.asarray(partials, np.float64))
+        if P.shape != (MAX_SLOTS, nseg_all):
+            raise ValueError("debug_star_sums: partials are (%d, nseg_all = %d)" % (MAX_SLOTS, nseg_all))
+        out, seq = np.zeros(8), np.zeros(2, np.uint64)
+        if lib().dpgo_group_debug_star_sums(self._h, _dp(P), int(valid), _dp(out), seq.ctypes.data_as(C.POINTER(C.c_ulonglong))) != 0:
+            raise RuntimeError("dpgo_group_debug_star_sums failed")
+        return dict(dev=out[:4].copy(), host=out[4:].copy(), flag=int(seq[0]), seq=int(seq[1]))
+
+    def debug_gated_update(self, go_word):
+        """Debug: the launches of an update enqueued ahead of the host's decision under the gate word go_word, 0 or all ones
+        (dpgo_group_debug_gated_update); the group's state is put back afterwards.  Returns {buffer: dict(untouched,
+        same_as_ungated)} for the buffers of GATED_BUFFERS the group has; same_as_ungated is None for go_word = 0."""
+        rep = np.full(3 * len(GATED_BUFFERS), -7, np.int32)
+        if lib().dpgo_group_debug_gated_update(self._h, int(go_word) & 0xFFFFFFFFFFFFFFFF, _ip(rep)) != 0:
+            raise RuntimeError("dpgo_group_debug_gated_update failed")
+        return {k: dict(untouched=bool(rep[3 * i + 1]), same_as_ungated=None if rep[3 * i + 2] < 0 else bool(rep[3 * i + 2]))
+                for i, k in enumerate(GATED_BUFFERS) if rep[3 * i]}
 
 
 class Comm:

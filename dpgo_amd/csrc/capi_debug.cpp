@@ -693,18 +693,36 @@ int dpgo_group_debug_stpcg(dpgo_group_t *h, const int *locals, int n, const doub
 
 int dpgo_group_debug_cg_scalars(dpgo_group_t *h, const dpgo_cg_debug_launch_t *script, int n, double *records,
                                 unsigned long long *masks, double *cg_summary, double *tnt_summary, double *dev_tnt,
-                                unsigned long long *seq, unsigned *arrived) {
+                                unsigned long long *seq, unsigned *arrived, double *gate_sums, unsigned long long *gate_words) {
   if (!h || (n > 0 && !script)) return -1;
   return guarded([&] {
     std::vector<dpgo::Group::CgDebugLaunch> sc(n);
+    std::vector<dpgo::Group::GateDebug> gates(n);
     for (int i = 0; i < n; i++) {
       const dpgo_cg_debug_launch_t &q = script[i];
+      if (const dpgo_gate_debug_t *g = q.gate) {
+        dpgo::Group::GateDebug &o = gates[i];
+        o.nslots = g->nslots; o.max_it = g->max_it; o.max_acc = g->max_acc; o.max_hits0 = g->max_hits0; o.max_hits1 = g->max_hits1;
+        o.rel_tol = g->rel_tol; o.step_tol = g->step_tol; o.psi = g->psi; o.phi = g->phi;
+        o.f = g->f; o.Fk0 = g->Fk0; o.Fk1 = g->Fk1; o.fobj = g->fobj; o.hits0 = g->hits0; o.hits1 = g->hits1;
+        sc[i].gate = &o;
+      }
       sc[i].kind = q.kind; sc[i].bits = q.bits; sc[i].use_precon = q.use_precon; sc[i].max_it = q.max_it;
       sc[i].grad_tol = q.grad_tol; sc[i].pgrad_tol = q.pgrad_tol; sc[i].kappa = q.kappa; sc[i].theta = q.theta;
       sc[i].rv = q.rv; sc[i].Delta = q.Delta; sc[i].target = q.target; sc[i].partials = q.partials; sc[i].slots = q.slots;
     }
-    return h->grp->debug_cg_scalars(sc.data(), n, records, masks, cg_summary, tnt_summary, dev_tnt, seq, arrived);
+    return h->grp->debug_cg_scalars(sc.data(), n, records, masks, cg_summary, tnt_summary, dev_tnt, seq, arrived, gate_sums, gate_words);
   });
+}
+
+int dpgo_group_debug_star_sums(dpgo_group_t *h, const double *partials, unsigned valid, double *out, unsigned long long *seq) {
+  if (!h || !h->grp || !partials || !out || !seq || (valid & ~0x3fu)) return -1;
+  return guarded([&] { return h->grp->debug_star_sums(partials, valid, out, seq); });
+}
+
+int dpgo_group_debug_gated_update(dpgo_group_t *h, unsigned long long go_word, int *report) {
+  if (!h || !h->grp || !report || (go_word != 0 && go_word != ~0ull)) return -1;
+  return guarded([&] { return h->grp->debug_gated_update(go_word, report); });
 }
 
 // ---- the exchange (comm.cpp) ----

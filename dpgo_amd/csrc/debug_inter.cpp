@@ -226,4 +226,61 @@ int Group::debug_rescale(const double *w, const double *scale, const int *count,
   return (int)changed.size();
 }
 
+// speculate_update()'s continuation under a given gate word (group.h): what a closed gate leaves untouched, what an open
+// one does against the same launches without a gate.  Between iterate() and update() the
+// buffers take the roles of the accepted step, as they do when speculate_update() enqueues these launches; behind update()
+// the roles they have now (the launches then repeat what update() did).  Which of the two: whether the nodes are `updated`.
+int Group::debug_gated_update(NodeBits go_word, int *report) {
+  finish_update();
+  if (!report || (go_word != 0 && go_word != ~0ull)) return -1;
+  if (opt_.loss == 0 || dynamic() || !fused_ || !keep_gx() || star_ || spec_upd_.on || pending_recv_ || xchg_done_ ||
+      sched_.has_deferred() || num_local() == 0)
+    return -1;
+  int updated = 0;
+  for (int a = 0; a < num_local(); a++) {
+    if (res_[a].iters < 1) return -1;
+    updated += res_[a].updated != 0;
+  }
+  if (updated != 0 && updated != num_local()) return -1;
+  flush_pending_tail();
+  sync();
+  const UpdateRoles r = updated == 0 ? roles_accepted(Xak_.p) : roles_now();
+  DevBuf<double> *bufs[GATED_BUFFERS] = {&Xk_, &Zc_, &Zp_, &gc_, &gp_, &Dfc_, &Dfp_, &GXc_, &GXp_, &partials_, &DfE_, &e_w_};
+  std::vector<std::vector<double>> saved(GATED_BUFFERS), gated(GATED_BUFFERS), plain(GATED_BUFFERS);
+  const auto read = [&](std::vector<std::vector<double>> &to) {
+    sync();
+    for (int k = 0; k < GATED_BUFFERS; k++) {
+      to[k].resize(bufs[k]->n);
+      if (bufs[k]->n > 0) HIP_CHECK(hipMemcpy(to[k].data(), bufs[k]->p, sizeof(double) * bufs[k]->n, hipMemcpyDeviceToHost));
+    }
+  };
+  const auto restore = [&] {
+    sync();
+    for (int k = 0; k < GATED_BUFFERS; k++)
+      if (bufs[k]->n > 0) HIP_CHECK(hipMemcpy(bufs[k]->p, saved[k].data(), sizeof(double) * bufs[k]->n, hipMemcpyHostToDevice));
+  };
+  const auto same = [](const std::vector<double> &x, const std::vector<double> &y) {
+    return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), sizeof(double) * x.size()) == 0);
+  };
+  NodeBits go_saved = 0;
+  HIP_CHECK(hipMemcpy(&go_saved, go_.p, sizeof(NodeBits), hipMemcpyDeviceToHost));
+  read(saved);
+  HIP_CHECK(hipMemcpy(go_.p, &go_word, sizeof(NodeBits), hipMemcpyHostToDevice));
+  update_continuation(r, go_.p);
+  read(gated);
+  restore();
+  if (go_word != 0) {
+    update_continuation(r, nullptr);
+    read(plain);
+    restore();
+  }
+  HIP_CHECK(hipMemcpy(go_.p, &go_saved, sizeof(NodeBits), hipMemcpyHostToDevice));
+  for (int k = 0; k < GATED_BUFFERS; k++) {
+    report[3 * k] = bufs[k]->n > 0;
+    report[3 * k + 1] = same(gated[k], saved[k]);
+    report[3 * k + 2] = go_word != 0 ? (int)same(gated[k], plain[k]) : -1;
+  }
+  return 0;
+}
+
 }  // namespace dpgo

@@ -1339,8 +1339,11 @@ int Group::debug_seg_layout(int *nseg_all, int *own_ptr, int *nbr_ptr) const {
 
 // The CG's scalar kernels on given partial sums, for tests/test_gpu_cg_scalars.py: every launch is the one tnt.cpp makes
 // (later_round, enqueue_device_start, step_a, step_b, scal_begin) with the vectors' passes left out -- their sums are handed in.
+// reduce_gate / reduce: the trial point's reduction with the gate of a speculative update (speculate_update's launch, the gate's
+// scalars and options from the script), and launch_reduce over own rows on the same sums (tests/test_gpu_gate.py).
 int Group::debug_cg_scalars(const CgDebugLaunch *script, int n, double *records, unsigned long long *masks, double *cg_summary,
-                            double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived) {
+                            double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived, double *gate_sums,
+                            unsigned long long *gate_words) {
   finish_update();
   const int L = num_local();
   if (!script || n < 0 || !records || !masks || !cg_summary || !tnt_summary || !dev_tnt || !seq || !arrived) return -1;
@@ -1350,6 +1353,11 @@ int Group::debug_cg_scalars(const CgDebugLaunch *script, int n, double *records,
     if (q.kind < 0 || q.kind >= CG_DBG_KINDS || q.slots < 0 || q.slots > MAX_SLOTS || (q.slots > 0 && !q.partials)) return -1;
     if (begins && (q.max_it < 0 || (q.bits & ~all_bits()) || !q.Delta)) return -1;
     if (q.kind == CG_DBG_BEGIN_HOST && (!q.rv || !q.target)) return -1;
+    if (q.kind == CG_DBG_REDUCE_GATE || q.kind == CG_DBG_REDUCE) {
+      const GateDebug *g = q.gate;
+      if (!g || !gate_sums || !gate_words || g->nslots <= 0 || g->nslots > MAX_SLOTS || L == 0) return -1;
+      if (q.kind == CG_DBG_REDUCE_GATE && (!g->f || !g->Fk0 || !g->Fk1 || !g->fobj || !g->hits0 || !g->hits1)) return -1;
+    }
   }
   sync();
   std::vector<CgNode> rec(L);
@@ -1369,6 +1377,16 @@ int Group::debug_cg_scalars(const CgDebugLaunch *script, int n, double *records,
       flagged = false;
     } else if (q.kind == CG_DBG_SCAL0 || q.kind == CG_DBG_SCAL1) {
       launch_cg_scal(st_, T_, L, q.kind == CG_DBG_SCAL0 ? 0 : 1, partials_.p, cg_.p, dmask_.p, h_cg_, sched_.flag());
+    } else if (q.kind == CG_DBG_REDUCE) {
+      launch_reduce(st_, T_, L, false, q.gate->nslots, partials_.p, h_scal_, sched_.flag());
+    } else if (q.kind == CG_DBG_REDUCE_GATE) {
+      const GateDebug &g = *q.gate;
+      Options o = opt_;
+      o.max_iterations = g.max_it; o.max_iterations_accepted = g.max_acc;
+      o.max_soft_restart_hits[0] = g.max_hits0; o.max_soft_restart_hits[1] = g.max_hits1;
+      o.rel_func_decrease_tol = g.rel_tol; o.stepsize_tol = g.step_tol; o.psi = g.psi; o.phi = g.phi;
+      const AmmGate G = amm_gate(L, o, [&g](int a) { return GateNode{g.f[a], g.Fk0[a], g.Fk1[a], g.fobj[a], g.hits0[a], g.hits1[a]}; });
+      launch_reduce_gate(st_, T_, L, g.nslots, partials_.p, h_scal_, sched_.flag(), dev_sums_.p, G, dev_tnt_.p, cg_.p, go_.p, h_gate_);
     } else {
       const TntStart start = {.nnodes = L, .bits = q.bits, .use_precon = q.use_precon != 0, .max_it = q.max_it,
                               .grad_tol = q.grad_tol, .pgrad_tol = q.pgrad_tol, .kappa = q.kappa, .theta = q.theta, .Delta = q.Delta,
@@ -1396,7 +1414,35 @@ int Group::debug_cg_scalars(const CgDebugLaunch *script, int n, double *records,
     seq[(size_t)i * 2] = sched_.flag_value();
     seq[(size_t)i * 2 + 1] = sched_.last_seq();
     arrived[i] = sched_.arrived_count();
+    if (q.kind == CG_DBG_REDUCE_GATE || q.kind == CG_DBG_REDUCE) {
+      const size_t ns = (size_t)L * MAX_SLOTS;
+      std::copy(h_scal_, h_scal_ + ns, gate_sums + (size_t)i * 2 * ns);
+      HIP_CHECK(hipMemcpy(gate_sums + ((size_t)i * 2 + 1) * ns, dev_sums_.p, sizeof(double) * ns, hipMemcpyDeviceToHost));
+      NodeBits go = 0;
+      HIP_CHECK(hipMemcpy(&go, go_.p, sizeof(go), hipMemcpyDeviceToHost));
+      gate_words[(size_t)i * 2] = go;
+      static_assert(sizeof(unsigned long long) == sizeof(double), "");
+      std::memcpy(&gate_words[(size_t)i * 2 + 1], h_gate_, sizeof(double));
+    }
   }
+  return 0;
+}
+
+// AMM-PGO*'s master sums on given partial sums, for tests/test_gpu_star_sums.py: the two launches star_sums() ends with
+int Group::debug_star_sums(const double *partials, unsigned valid, double *out, unsigned long long *seq) {
+  finish_update();
+  if (!partials || !out || !seq || (valid & ~0x3fu) || num_local() == 0) return -1;
+  sync();
+  if (star_vals_.n == 0) star_vals_.alloc(8);
+  HIP_CHECK(hipMemcpy(partials_.p, partials, sizeof(double) * (size_t)MAX_SLOTS * T_.nseg_all, hipMemcpyHostToDevice));
+  launch_star_sums(st_, T_, num_local(), valid, star_slots(), partials_.p, star_vals_.p);
+  launch_publish(st_, star_vals_.p, 4, h_scal_, sched_.flag());
+  wait_flag(sched_.last_seq());
+  std::copy(h_scal_, h_scal_ + 4, out + 4);
+  HIP_CHECK(hipStreamSynchronize(st_));
+  HIP_CHECK(hipMemcpy(out, star_vals_.p, sizeof(double) * 4, hipMemcpyDeviceToHost));
+  seq[0] = sched_.flag_value();
+  seq[1] = sched_.last_seq();
   return 0;
 }
 
@@ -1422,6 +1468,15 @@ void Group::enqueue_objective(const double *X_own, int slot0) {
   launch_cost(lc(), Ei_, E_, opt_.loss == 0, opt_.loss, opt_.loss_reg, Tall_.p, partials_.p, slot0);
 }
 
+// Where star_sums() keeps its six partial sums.  update() and evaluate_global() reduce slots 0..2 over ALL rows and count on the
+// neighbour segments of slot 2 never having been written; k_cost writes every segment of its two slots.  So the first point's
+// pair is 0, 1 (as it always was) and the second point's pair the last two slots, which nobody else touches; the distances are
+// own-row sums.
+const int *Group::star_slots() {
+  static const int slots[6] = {0, 1, MAX_SLOTS - 2, MAX_SLOTS - 1, 4, 5};
+  return slots;
+}
+
 // Everything the master's tests of one AMM-PGO* iteration need (DPGOStar.cpp:147-192), enqueued back to back and read
 // ONCE: the passes leave their partial sums in slots 0..5, k_star_sums folds them over the nodes on the device, the sum
 // over the groups -- if there are several -- is an all-reduce on the same stream (set_device_allreduce) or, for a host
@@ -1433,10 +1488,7 @@ int Group::star_sums(const double *X1_own, const double *X2_own, const double *r
   for (int a = 0; a < num_local(); a++) all[a] = a;
   set_mask(all);
   if (star_vals_.n == 0) star_vals_.alloc(8);
-  // Slots: update() and evaluate_global() reduce slots 0..2 over ALL rows and count on the neighbour segments of slot 2
-  // never having been written; k_cost writes every segment of its two slots.  So the first point's pair is 0, 1 (as it
-  // always was) and the second point's pair the last two slots, which nobody else touches; the distances are own-row sums.
-  static const int slots[6] = {0, 1, MAX_SLOTS - 2, MAX_SLOTS - 1, 4, 5};
+  const int *slots = star_slots();
   unsigned valid = 0;
   if (F1) { enqueue_objective(X1_own, slots[0]); valid |= 0x3; }
   if (X2_own && F2) { enqueue_objective(X2_own, slots[2]); valid |= 0xc; }

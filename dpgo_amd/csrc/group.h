@@ -289,8 +289,20 @@ class Group {
   // (launch_cg_begin, launch_tnt_begin, launch_cg_scal, launch_cg_scal_begin) on the group's own segment table, records,
   // masks, pinned summaries and flag; the state after every launch is read back.  Nothing here computes: the entry feeds
   // inputs and reads state.
-  enum CgDebugKind { CG_DBG_BEGIN_HOST = 0, CG_DBG_BEGIN_DEVICE, CG_DBG_SCAL0, CG_DBG_SCAL1, CG_DBG_SCAL_BEGIN, CG_DBG_KINDS };
+  // ... and the trial point's reduction with the gate of a speculative update behind the steps (tests/test_gpu_gate.py):
+  // reduce_gate is launch_reduce_gate as speculate_update() makes it -- the group's own partial sums, pinned scalars, flag,
+  // device sums, refinement start (what the script's scal_begin left), CG records, gate word and pinned verdict -- with the
+  // per-node scalars and the options of the gate handed in; reduce is launch_reduce(own rows) on the same sums, for comparison
+  enum CgDebugKind { CG_DBG_BEGIN_HOST = 0, CG_DBG_BEGIN_DEVICE, CG_DBG_SCAL0, CG_DBG_SCAL1, CG_DBG_SCAL_BEGIN, CG_DBG_REDUCE_GATE,
+                     CG_DBG_REDUCE, CG_DBG_KINDS };
+  struct GateDebug {   // (reduce_gate; reduce reads nslots only)
+    int nslots = 0, max_it = 0, max_acc = 0, max_hits0 = 0, max_hits1 = 0;
+    double rel_tol = 0, step_tol = 0, psi = 0, phi = 0;
+    const double *f = nullptr, *Fk0 = nullptr, *Fk1 = nullptr, *fobj = nullptr;   // per local node
+    const int *hits0 = nullptr, *hits1 = nullptr;
+  };
   struct CgDebugLaunch {
+    const GateDebug *gate = nullptr;
     int kind = 0;
     NodeBits bits = 0;                                        // the candidates (the begin kinds)
     int use_precon = 0, max_it = 0;
@@ -303,8 +315,25 @@ class Group {
   // per launch i: records[i][node][CG_DBG_RECORD], masks[i][3], cg_summary[i][node][CG_SUMMARY], tnt_summary and dev_tnt
   // [i][node][TNT_SUMMARY] (pinned / device), seq[i][2] = the host flag's value once the launch is over and the last sequence
   // number given out, arrived[i] = the flag's arrival counter
+  // where the script has a reduce_gate or a reduce: gate_sums[i][2][node][MAX_SLOTS] (the pinned scalars, the device copy)
+  // and gate_words[i][2] (the gate's word, the bits of the pinned verdict)
   int debug_cg_scalars(const CgDebugLaunch *script, int n, double *records, unsigned long long *masks, double *cg_summary,
-                       double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived);
+                       double *tnt_summary, double *dev_tnt, unsigned long long *seq, unsigned *arrived, double *gate_sums,
+                       unsigned long long *gate_words);
+  // AMM-PGO*'s master sums on given partial sums (MAX_SLOTS x nseg_all): launch_star_sums with star_sums()'s slot table and
+  // launch_publish on the group's flag, as star_sums() makes them.  out[0..3]: the device values, out[4..7]: the pinned ones;
+  // seq[2]: the flag's value, the last sequence number given out
+  int debug_star_sums(const double *partials, unsigned valid, double *out, unsigned long long *seq);
+  // The launches speculate_update() enqueues behind its gate (update_continuation) under a GIVEN gate word, 0 or all ones, on a
+  // group whose every node is past its first iteration (robust loss, Static rescale): between iterate() and update() with the
+  // buffers in the roles of the accepted step (roles_accepted, what speculate_update() hands them), behind update() in the
+  // roles they have now (roles_now).  Every buffer the launches may write is saved before and put back afterwards: the group can
+  // go on.  report[3 k + 0..2] for buffer k of GATED_BUFFERS (Xk, X[iter], X[iter-1], g, g[iter-1], Dfobj, Dfobj[iter-1], G X,
+  // G X[iter-1], the partial sums, DfobjE, the edge weights): present; bit-identical to the saved copy after the gated launches;
+  // (all ones only, else -1) the gated launches' result bit-identical to that of the same launches without a gate from the
+  // same saved state
+  static constexpr int GATED_BUFFERS = 12;
+  int debug_gated_update(NodeBits go_word, int *report);
   // One CG of a refinement round on given points, linear terms and radii (tnt.cpp), through TntRun's own pieces
   static constexpr int STPCG_DBG_SCALARS = 12;
   int debug_stpcg(const std::vector<int> &nodes, const double *in, int ld_in, const double *Delta, bool device_start, double fill,
@@ -501,6 +530,11 @@ class Group {
   unsigned long long spec_verdict_seq_ = 0;
   bool spec_update_possible(const double *xprop) const;
   void speculate_update(const double *xprop, int nslots_trial);   // run_tnt: the trial point's reduction + gate, then the continuation
+  // what the gate gets by value: the options it tests against and, per node, the scalars of the last update()
+  // (speculate_update: opt_ and res_; debug_cg_scalars: the script's)
+  void update_continuation(const UpdateRoles &r, const NodeBits *gate);   // the launches speculate_update() enqueues behind the gate
+  struct GateNode { double f, Fk0, Fk1, fobj; int hits0, hits1; };
+  static AmmGate amm_gate(int L, const Options &o, const std::function<GateNode(int)> &node);
   void check_gate(bool host_common);
   // update()'s closing reduction is only read by the host, late (finish_update): where the read-back is deferred the
   // reduction is not launched at all but rides on the next refinement's k_cg_scal_begin (one workgroup per node anyway),
@@ -707,6 +741,7 @@ class Group {
   double global_objective(const double *X_own);           // F at the point whose own rows are X_own
   // the master's numbers in ONE read-back: F(X1) [, F(X2)] [, |X1 - ref|^2, |X2 - ref|^2] (null pointers: not wanted)
   int star_sums(const double *X1_own, const double *X2_own, const double *ref_own, double *F1, double *F2, double *d1, double *d2);
+  static const int *star_slots();   // the six partial-sum slots star_sums() hands k_star_sums
   void enqueue_objective(const double *X_own, int slot0);   // k_cost partials of the point into slots slot0, slot0 + 1
 
   void upload_bsr(const std::vector<const BsrMatrix *> &per_node, bool rows_all, BsrBufs &out);

@@ -76,30 +76,43 @@ bool Group::spec_update_possible(const double *xprop) const {
   return true;
 }
 
+AmmGate Group::amm_gate(int L, const Options &o, const std::function<GateNode(int)> &node) {
+  AmmGate G;
+  G.nnodes = L; G.ds = 2 * MAX_DOTS; G.max_it = o.max_iterations; G.max_acc = o.max_iterations_accepted;
+  G.max_hits0 = o.max_soft_restart_hits[0]; G.max_hits1 = o.max_soft_restart_hits[1];
+  G.sqrt_eps = TntConst::sqrt_eps(); G.eta1 = TntConst::eta1;
+  G.rel_tol = o.rel_func_decrease_tol; G.step_tol = o.stepsize_tol; G.psi = o.psi; G.phi = o.phi;
+  for (int a = 0; a < MAX_LOCAL_NODES; a++) {
+    const GateNode n = a < L ? node(a) : GateNode{0.0, 0.0, 0.0, 0.0, 0, 0};
+    G.f[a] = n.f; G.Fk0[a] = n.Fk0; G.Fk1[a] = n.Fk1; G.fobj[a] = n.fobj;
+    G.hits0[a] = n.hits0; G.hits1[a] = n.hits1;
+  }
+  return G;
+}
+
+// the launches of the common course behind the gate: the local halo copy, then update()'s later-iteration product (with
+// iterate()'s tail) and inter-edge pass, all under the device word `gate` (null: unconditionally -- a test hook's comparison)
+void Group::update_continuation(const UpdateRoles &r, const NodeBits *gate) {
+  const NodeMask m{all_bits(), gate};
+  if (gather_dst_.n > 0) launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, r.xak, r.xk, gate);
+  update_product(m, r, true, true);
+  update_inter_pass(m, r, true, true, nullptr);
+}
+
 void Group::speculate_update(const double *xprop, int nslots_trial) {
   spec_upd_ = SpecUpdate();
   const int L = num_local();
-  AmmGate G;
-  G.nnodes = L; G.ds = 2 * MAX_DOTS; G.max_it = opt_.max_iterations; G.max_acc = opt_.max_iterations_accepted;
-  G.max_hits0 = opt_.max_soft_restart_hits[0]; G.max_hits1 = opt_.max_soft_restart_hits[1];
-  G.sqrt_eps = TntConst::sqrt_eps(); G.eta1 = TntConst::eta1;
-  G.rel_tol = opt_.rel_func_decrease_tol; G.step_tol = opt_.stepsize_tol; G.psi = opt_.psi; G.phi = opt_.phi;
-  for (int a = 0; a < MAX_LOCAL_NODES; a++) {
-    const bool in = a < L;
-    G.f[a] = in ? res_[a].f : 0.0; G.Fk0[a] = in ? res_[a].Fk[0] : 0.0; G.Fk1[a] = in ? res_[a].Fk[1] : 0.0;
-    G.fobj[a] = in ? res_[a].fobj : 0.0;
-    G.hits0[a] = in ? res_[a].soft_restart_hits[0] : 0; G.hits1[a] = in ? res_[a].soft_restart_hits[1] : 0;
-  }
+  const AmmGate G = amm_gate(L, opt_, [this](int a) {
+    const NodeResults &r = res_[a];
+    return GateNode{r.f, r.Fk[0], r.Fk[1], r.fobj, r.soft_restart_hits[0], r.soft_restart_hits[1]};
+  });
   // the trial point's sums to the host (k_reduce's work, its flag) and the gate's verdict, one launch
   launch_reduce_gate(st_, T_, L, nslots_trial, partials_.p, h_scal_, sched_.flag(), dev_sums_.p, G, dev_tnt_.p, cg_.p, go_.p, h_gate_);
   spec_upd_.seq_trial = sched_.last_seq();
   // the common course from here: iterate()'s tail and the local halo copy, then update()'s later-iteration sequence for the
   // static robust surrogate, all under the gate's word
   const UpdateRoles r = roles_accepted(xprop);
-  const NodeMask m{all_bits(), go_.p};
-  if (gather_dst_.n > 0) launch_copy_indexed(d_, st_, (int)gather_dst_.n, gather_dst_.p, gather_src_.p, r.xak, r.xk, go_.p);
-  update_product(m, r, true, true);
-  update_inter_pass(m, r, true, true, nullptr);
+  update_continuation(r, go_.p);
   // (the closing reduction: left to the next refinement where update() itself would leave it, group.h: UpdLazy)
   spec_upd_.lazy = lazy_update_reduce();
   if (!spec_upd_.lazy) update_reduce(6, r.pupd);

@@ -988,17 +988,49 @@ int dpgo_group_debug_apply(dpgo_group_t *grp, int local, const char *op, const d
  * target, h_M_norm, c1, cr, al, kap, be, cg_it, max_it, live, stop_ord --, masks[i][3], cg_summary[i][a][4] (stop ordinal or
  * 1e18 while live, h_M_norm, cg_it, unused), tnt_summary[i][a][8] and dev_tnt[i][a][8] (the six start sums, active, unused:
  * pinned and device copies), seq[i][2] (the flag's value, the last sequence number given out), arrived[i] (the flag's
- * arrival counter: 0 between launches). */
+ * arrival counter: 0 between launches).
+ *   kind 5 reduce_gate  the trial point's reduction with the gate of a speculative update behind it, as the iteration launches
+ *                       it: gate->nslots sums per node over own rows to the pinned scalars and to their device copy, then the
+ *                       gate's verdict from those sums, the refinement's start (what an earlier scal_begin of the script left
+ *                       in device memory) and the CG records, against the per-node scalars (f, Fk0, Fk1, fobj, hits0, hits1:
+ *                       one per local node) and the options in *gate
+ *        6 reduce       the plain reduction over own rows of gate->nslots sums per node (the rest of *gate is not read)
+ * After a launch of kind 5 or 6: gate_sums[i][2][a][32] (the pinned scalars, the device copy) and gate_words[i][2] (the gate's
+ * device word -- all ones or 0 --, the bits of its pinned verdict, 1.0 or 0.0); both may be NULL in a script without such a launch. */
+typedef struct dpgo_gate_debug {
+  int nslots, max_it, max_acc, max_hits0, max_hits1;
+  double rel_tol, step_tol, psi, phi;
+  const double *f, *Fk0, *Fk1, *fobj;
+  const int *hits0, *hits1;
+} dpgo_gate_debug_t;
 typedef struct dpgo_cg_debug_launch {
   int kind, use_precon, max_it, slots;
   unsigned long long bits;
   double grad_tol, pgrad_tol, kappa, theta;
   const double *rv, *Delta, *target, *partials;
+  const dpgo_gate_debug_t *gate;   /* kinds 5 and 6 */
 } dpgo_cg_debug_launch_t;
 int dpgo_group_debug_seg_layout(dpgo_group_t *grp, int *nseg_all, int *own_ptr, int *nbr_ptr);
 int dpgo_group_debug_cg_scalars(dpgo_group_t *grp, const dpgo_cg_debug_launch_t *script, int n, double *records,
                                 unsigned long long *masks, double *cg_summary, double *tnt_summary, double *dev_tnt,
-                                unsigned long long *seq, unsigned *arrived);
+                                unsigned long long *seq, unsigned *arrived, double *gate_sums, unsigned long long *gate_words);
+/* Device: AMM-PGO*'s master sums (k_star_sums, k_publish) on GIVEN partial sums, through the two launches the master's read-back
+ * ends with.  partials: 32 x nseg_all doubles (slot-major), copied over the partial sums; valid: bit q (q < 6) = sum q was
+ * produced, the six sums being in slots 0, 1, 30, 31, 4, 5.  out[0..3]: F1, F2, d1, d2 as they are in device memory, out[4..7]:
+ * as published to the host; seq[2]: the flag's value, the last sequence number given out.  -1: a null pointer, bits of `valid`
+ * above 5. */
+int dpgo_group_debug_star_sums(dpgo_group_t *grp, const double *partials, unsigned valid, double *out, unsigned long long *seq);
+/* Device: the launches an update enqueued ahead of the host's decision consists of -- the local halo copy, the product with G,
+ * the inter-edge pass -- under a GIVEN gate word (0: they must fall through; all ones: they run), with the group's buffers in
+ * the roles of the accepted step when called between dpgo_group_iterate and dpgo_group_update (as the iteration enqueues
+ * them), in their present roles behind an update (the launches then repeat it).  For a group with a robust loss and Static
+ * rescale whose every node is past its first iteration; every buffer the launches may write is saved before and put back
+ * afterwards, so the group can go on.  report: 3 ints for each of 12 buffers (Xk, X[iter], X[iter-1], g, g[iter-1], Dfobj,
+ * Dfobj[iter-1], G X, G X[iter-1], the partial sums, DfobjE, the edge weights): the buffer exists; it is bit-identical to the
+ * saved copy after the gated launches; the gated launches' result is bit-identical to that of the same launches without a
+ * gate from the same state (all ones only, else -1).  -1: a null pointer, a word other than 0 / all ones, a group in another
+ * state. */
+int dpgo_group_debug_gated_update(dpgo_group_t *grp, unsigned long long go_word, int *report);
 /* Device: ONE truncated CG of a refinement round, and nothing after it, on given points: the model gradient and the norms,
  * the start on the host (device_start = 0: a later round's) or on the device (1: the first round's), the CG steps -- the pieces
  * dpgo_group_iterate's refinement is made of, in its order, with the group's options (max_tCG_iterations, STPCG_kappa,

@@ -1,6 +1,8 @@
 """The CSR reader of the test hooks (capi_debug.cpp: read_csr), through every hook that takes a matrix and runs without a
 device: a malformed matrix is refused with -1 before anything is written, a well-formed one goes through with host=1.
-dpgo_debug_spd_solver_create is not here: it answers -2 without a device before it reads the matrix."""
+dpgo_debug_spd_solver_create is not here: it answers -2 without a device before it reads the matrix.
+At the end: the hooks that work on a group (the gate's launch kinds of dpgo_group_debug_cg_scalars, dpgo_group_debug_star_sums,
+dpgo_group_debug_gated_update) answer -1 on the host and write nothing."""
 import ctypes as C
 
 import numpy as np
@@ -97,3 +99,50 @@ def test_the_well_formed_matrix_goes_through_on_the_host(hook):
         x = outputs[0].reshape(-1)[:N * (1 if hook == "vsolve" else 2)].reshape(N, -1)
         rhs = UNTOUCHED if hook == "solve" else 1.0           # (dpgo_debug_spd_solve works in place: what X held)
         np.testing.assert_allclose(A @ x, rhs, rtol=1e-14, atol=0)
+
+
+# ---- the hooks of the speculative update's gate, the master's sums and the gated launches (capi_debug.cpp): they work on a
+# group, which only a device can hold; on the host their argument checks answer -1 before anything is touched.  (The checks
+# that need a group to compare with -- bits outside it, nslots outside (0, MAX_SLOTS] -- are in tests/test_gpu_gate.py.)
+def _gate_script(nslots=15, n=1):
+    L = 1
+    keep = [np.zeros(L), np.zeros(L, np.int32)]
+    g = dpgo_amd.GateDebug()
+    g.nslots = nslots
+    for k in ("f", "Fk0", "Fk1", "fobj"):
+        setattr(g, k, _dp(keep[0]))
+    g.hits0 = g.hits1 = _ip(keep[1])
+    arr = (dpgo_amd.CgDebugLaunch * n)()
+    arr[0].kind = dpgo_amd.CG_DEBUG_KINDS.index("reduce_gate")
+    arr[0].gate = C.addressof(g)
+    return arr, keep + [g]
+
+
+@pytest.mark.parametrize("case", ["no group", "no group, no script", "no group, nslots = 0", "no group, nslots = 33"])
+def test_the_gate_hook_refuses_on_the_host(case):
+    arr, keep = _gate_script({"no group, nslots = 0": 0, "no group, nslots = 33": 33}.get(case, 15))
+    out = [np.full(64, UNTOUCHED) for _ in range(5)]
+    words = [np.full(8, 7, np.uint64) for _ in range(3)]
+    arrived = np.full(2, 7, np.uint32)
+    U = C.POINTER(C.c_ulonglong)
+    rc = dpgo_amd.lib().dpgo_group_debug_cg_scalars(None, None if "no script" in case else arr, 1, _dp(out[0]), words[0].ctypes.data_as(U),
+                                                    _dp(out[1]), _dp(out[2]), _dp(out[3]), words[1].ctypes.data_as(U),
+                                                    arrived.ctypes.data_as(C.POINTER(C.c_uint)), _dp(out[4]), words[2].ctypes.data_as(U))
+    assert rc == -1
+    assert all(np.all(a == UNTOUCHED) for a in out) and all(np.all(w == 7) for w in words) and np.all(arrived == 7)
+
+
+@pytest.mark.parametrize("valid", [0x3f, 0x40, 0xffffffff])
+@pytest.mark.parametrize("null", ["group", "group and partials", "group and out"])
+def test_the_star_sums_hook_refuses_on_the_host(null, valid):
+    P, out, seq = np.zeros((32, 4)), np.full(8, UNTOUCHED), np.full(2, 7, np.uint64)
+    rc = dpgo_amd.lib().dpgo_group_debug_star_sums(None, None if "partials" in null else _dp(P), valid, None if "out" in null else _dp(out),
+                                                   seq.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+    assert rc == -1 and np.all(out == UNTOUCHED) and np.all(seq == 7)
+
+
+@pytest.mark.parametrize("word", [0, 1, 0xFFFFFFFFFFFFFFFF])
+def test_the_gated_update_hook_refuses_on_the_host(word):
+    rep = np.full(36, -7, np.int32)
+    assert dpgo_amd.lib().dpgo_group_debug_gated_update(None, word, _ip(rep)) == -1 and np.all(rep == -7)
+    assert dpgo_amd.lib().dpgo_group_debug_gated_update(None, word, None) == -1
