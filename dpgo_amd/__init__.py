@@ -220,6 +220,9 @@ SYMBOLS = {
     "dpgo_debug_pairs_vsolve_baseline": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, _DP]),
     "dpgo_debug_pairs_plan": (C.c_int, [C.c_int, C.c_int, _IP, C.c_int, _IP, _IP, _IP]),
     "dpgo_debug_pairs_gate": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_group_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _DP, C.c_int, C.c_int, _DP, _DP,
+                                         C.c_void_p]),
+    "dpgo_debug_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP]),
     "dpgo_debug_spd_msolve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _DP, C.c_int,
                                         C.c_int, _DP, _IP, _DP]),
     "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
@@ -1204,6 +1207,33 @@ class NodeGroup:
                                "or pose outside the graph, a candidate weight that is not positive, or bad sizes)")
         return pairs_output(joint, rel, gate, r, gated, threshold)
 
+    def sensitivity(self, X, upstream, anchor=0, max_bytes=0, graph=None, want_adjoint=False):
+        """Measurement sensitivities at X by implicit differentiation on the device (dpgo_group_sensitivity): for k scalars
+        L_l(X*) whose tangent gradients at X are the columns of `upstream` ((dof N, k), or (dof N,) for one; by global pose, in
+        `covariance`'s coordinates: see tangent_gradient and unit_upstream), the adjoints lambda_l = H^-1 c_l on `covariance`'s
+        anchored Hessian and, for every edge of `graph` (default: the group's own, which fixes the edge order),
+        dL_l / d(kappa, tau, t~[0..d), eta[0..dof - d)) with t~ + dt~ and R~ <- R~ Exp(hat(eta)).  X should be a critical point
+        (`polish`): result.stationarity says whether it is.  Returns (SensResult, sens) with sens (k, num_edges, 2 + dof), and
+        with want_adjoint also lambda (dof N, k), zeros on the anchor.  outcome SENS_OK, SENS_NOT_PD (zero outputs) or
+        SENS_SKIPPED (more device bytes than max_bytes, when > 0, or than half of what is free; zero outputs).  A column's
+        bits do not depend on the other columns of the call.  Trivial-loss groups that host every node."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        n = _dof(self.d) * self.graph.num_poses
+        U_ = np.asarray(upstream, np.float64)
+        U_ = np.asfortranarray(U_.reshape(-1, 1) if U_.ndim == 1 else U_)
+        if U_.ndim != 2 or U_.shape[0] != n or U_.shape[1] < 1:
+            raise ValueError("sensitivity: upstream must be (dof N, k) with k >= 1")
+        k = U_.shape[1]
+        sens = np.zeros((k, g_.num_edges, 2 + _dof(self.d)))
+        adj = np.zeros((n, k), order="F") if want_adjoint else None
+        r = SensResult()
+        if lib().dpgo_group_sensitivity(self._h, g_._h, _dp(X), ld, int(anchor), int(max_bytes), _dp(U_), n, k, _dpn(adj), _dp(sens),
+                                        C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_sensitivity failed (robust loss, a group that does not host every node, a graph that is "
+                               "not the group's, an anchor outside the graph, an upstream entry that is not finite, or bad sizes)")
+        return (r, sens, adj) if want_adjoint else (r, sens)
+
     def polish(self, X, anchor=0, max_bytes=0, **opts):
         """Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored
         tangent-space Hessian of `covariance`, factored and solved on the device -- until the tangent gradient is at rounding
@@ -2059,6 +2089,70 @@ def pairs_gate_debug(d, recp, recq, joint, candidate=None):
     if lib().dpgo_debug_pairs_gate(int(d), _dp(recp), _dp(recq), _dp(joint), None if cand is None else _dp(cand), _dp(rel), _dp(gate)) != 0:
         raise RuntimeError("dpgo_debug_pairs_gate failed (d, or a candidate weight that is not positive)")
     return rel, (None if cand is None else (float(gate[0]), bool(gate[1]), gate[2:].copy()))
+
+
+SENS_OK, SENS_NOT_PD, SENS_SKIPPED = 0, 1, 2
+SENS_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+
+
+class SensResult(C.Structure):
+    """dpgo_sens_result_t: the outcome of NodeGroup.sensitivity, the sizes of its factorisation, the columns it solved, in how
+    many batches, for how many edges, and the host milliseconds of its three phases."""
+    _fields_ = [("outcome", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("columns", C.c_int), ("batches", C.c_int), ("edges", C.c_int), ("device_bytes", C.c_longlong),
+                ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("stationarity", C.c_double), ("symbolic_s", C.c_double),
+                ("factor_ms", C.c_double), ("solve_ms", C.c_double), ("edge_ms", C.c_double)]
+
+
+def sens_edge_debug(graph, X, lam):
+    """Debug, no GPU: the per-edge arithmetic of the sensitivities' kernel on the host (dpgo_debug_sens_edge_host) for one
+    adjoint `lam` (dof N by global pose, used as given).  Returns (sens, phi): (num_edges, 2 + dof) in NodeGroup.sensitivity's
+    order, and phi_e = lam_i' ghat_e(i) + lam_j' ghat_e(j) per edge."""
+    X, ld = _fcol(X)
+    dof, m = _dof(graph.d), graph.num_edges
+    lam = np.ascontiguousarray(lam, np.float64)
+    if lam.shape != (dof * graph.num_poses,):
+        raise ValueError("sens_edge_debug: lam must have dof N entries")
+    sens, phi = np.zeros((m, 2 + dof)), np.zeros(m)
+    if lib().dpgo_debug_sens_edge_host(graph._h, _dp(X), ld, _dp(lam), _dp(sens), _dp(phi)) != 0:
+        raise ValueError("dpgo_debug_sens_edge_host failed (a short X, or an edge outside the graph)")
+    return sens, phi
+
+
+def _hat_generators(d):
+    if d == 2:
+        return [np.array([[0.0, -1.0], [1.0, 0.0]])]
+    return [np.array([[0.0, 0, 0], [0, 0, -1], [0, 1, 0]]), np.array([[0.0, 0, 1], [0, 0, 0], [-1, 0, 0]]),
+            np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 0]])]
+
+
+def tangent_gradient(X, G):
+    """The tangent gradient (dof N, by global pose, `covariance`'s coordinates) of a scalar whose ambient gradient at X is G,
+    an array shaped like X ((d+1)N x d: row p the derivative in t_p, rows N + d p ... in the rows of Y_p = R_p^T):
+    c_p[a < d] = G_t[p, a], c_p[d + k] = <G_R, R_p hat(e_k)> = <G_Y, -hat(e_k) Y_p>.  What NodeGroup.sensitivity takes as
+    a column of `upstream`."""
+    X, G = np.asarray(X, np.float64), np.asarray(G, np.float64)
+    d = X.shape[1]
+    if G.shape != X.shape or X.shape[0] % (d + 1):
+        raise ValueError("tangent_gradient: G must be shaped like X, (d+1)N x d")
+    N, dof = X.shape[0] // (d + 1), _dof(d)
+    Y, GY = X[N:].reshape(N, d, d), G[N:].reshape(N, d, d)
+    c = np.zeros((N, dof))
+    c[:, :d] = G[:N]
+    for k, E in enumerate(_hat_generators(d)):
+        c[:, d + k] = -np.einsum("rq,pqc,prc->p", E, Y, GY)
+    return c.reshape(-1)
+
+
+def unit_upstream(N, d, pose):
+    """(dof N, dof): the dof unit columns of one pose -- NodeGroup.sensitivity with them gives the influence of every
+    measurement on each tangent coordinate of that pose."""
+    dof = _dof(d)
+    if not 0 <= pose < N:
+        raise ValueError("unit_upstream: the pose is not in the graph")
+    U_ = np.zeros((dof * N, dof), order="F")
+    U_[dof * pose:dof * pose + dof] = np.eye(dof)
+    return U_
 
 
 POLISH_CONVERGED, POLISH_MAX_STEPS, POLISH_STALLED, POLISH_SKIPPED = 0, 1, 2, 3

@@ -936,6 +936,18 @@ int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, con
   });
 }
 
+// ---- measurement sensitivities (sens.h) ----
+int dpgo_group_sensitivity(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
+                           const double *upstream, int ldu, int k, double *adjoint, double *sens, dpgo_sens_result_t *result) {
+  if (!h || !h->grp || !g || !X || !upstream || !sens || !result || k < 1) return -1;
+  return guarded([&] {
+    dpgo::SensResult r;
+    const int rc = h->grp->sensitivity(g->g, X, ld, anchor, max_bytes, upstream, ldu, k, adjoint, sens, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
 // ---- Newton polish (polish.h) ----
 void dpgo_polish_options_default(dpgo_polish_options_t *opt) {
   if (!opt) return;

@@ -765,7 +765,7 @@ int dpgo_debug_comm_p2p_self(dpgo_group_t *h) {
   });
 }
 
-// ---- host forms of device arithmetic, and the pieces of pair_covariance (edges.h, robust.h, pairs.h, cert.h) ----
+// ---- host forms of device arithmetic, and the pieces of pair_covariance (edges.h, robust.h, pairs.h, sens.h, cert.h) ----
 int dpgo_debug_edge_eval_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, double *s_rot,
                               double *s_trans, double *rho, double *weight, dpgo_edge_summary_t *sum) {
   if (!g) return -1;
@@ -817,6 +817,11 @@ int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const d
   if (d == 3) dpgo::pairs_one<3>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
   else dpgo::pairs_one<2>(recp, recq, joint, joint + DD, joint + 2 * DD, cand, rel, gate);
   return 0;
+}
+
+int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, const double *lambda, double *sens, double *phi) {
+  if (!g) return -1;
+  return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });
 }
 
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {

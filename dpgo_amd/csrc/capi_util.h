@@ -89,6 +89,14 @@ inline void to_c(const dpgo::PairsResult &r, dpgo_pairs_result_t *o) {
   o->factor_bytes = r.factor_bytes;
 }
 
+inline void to_c(const dpgo::SensResult &r, dpgo_sens_result_t *o) {
+  o->outcome = r.outcome; o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels;
+  o->max_front = r.max_front; o->columns = r.columns; o->batches = r.batches; o->edges = r.edges;
+  o->device_bytes = r.device_bytes; o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max;
+  o->stationarity = r.stationarity; o->symbolic_s = r.symbolic_s; o->factor_ms = r.factor_ms;
+  o->solve_ms = r.solve_ms; o->edge_ms = r.edge_ms;
+}
+
 inline void to_c(const dpgo::PolishResult &r, dpgo_polish_result_t *o) {
   o->outcome = r.outcome; o->steps = r.steps; o->factorisations = r.factorisations;
   o->indefinite = r.indefinite; o->F_initial = r.F_initial; o->F_final = r.F_final;

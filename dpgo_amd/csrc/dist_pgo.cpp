@@ -56,6 +56,12 @@
 //              one more line on stdout
 //                  staircase: <outcome> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
 //              the result files then hold its Xhat; the same reasons as --polish when it is not computed
+//              --sensitivity_pose P --sensitivity_report FILE (likewise; both or neither)  behind --polish, on the polished
+//              point, for the trivial loss and a world of one rank: dpgo_group_sensitivity with the dof unit columns of pose P
+//              (pose 0 the anchor) -- how every measurement moves that pose -- one more line on stdout
+//                  sensitivity: <outcome> <P> <edges> <columns> <batches> <device_bytes> <pivot_min> <stationarity>
+//              and, for OK, one line per edge in FILE: e i j inter, then dof x (2 + dof) values, row a the derivatives of
+//              coordinate a of the pose in (kappa, tau, t~, eta); "sensitivity: not computed (...)" says why not
 //              --gate_candidates FILE --gate_report FILE (likewise; both or neither)  beside --covariance, for the trivial loss
 //              and a world of one rank: FILE is a .g2o of candidate edges p -> q, read by the loader's edge parser; every
 //              candidate is tested against the final X with dpgo_group_pair_covariance (pose 0 the anchor), one line per
@@ -102,6 +108,8 @@ int main(int argc, char **argv) {
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
   std::string edge_report, covariance, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
+  std::string sensitivity_report;
+  int sensitivity_pose = -1;
   double gnc_barc2 = 4.0;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
@@ -143,6 +151,8 @@ int main(int argc, char **argv) {
     else if (const char *v = val("--covariance")) covariance = v;
     else if (const char *v = val("--gate_candidates")) gate_candidates = v;
     else if (const char *v = val("--gate_report")) gate_report = v;
+    else if (const char *v = val("--sensitivity_pose")) sensitivity_pose = atoi(v);
+    else if (const char *v = val("--sensitivity_report")) sensitivity_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
     else if (const char *v = val("--num_nodes")) num_nodes = atoi(v);
     else if (const char *v = val("--iters")) iters = atoi(v);
@@ -571,6 +581,53 @@ int main(int argc, char **argv) {
           fprintf(f, "%d %d %.17g %d %d", I[k], J[k], gate[(size_t)k * (2 + dof)], dof, gate[(size_t)k * (2 + dof) + 1] != 0.0 ? 1 : 0);
           for (int a = 0; a < dof; a++)
             for (int b = a; b < dof; b++) fprintf(f, " %.17g", rel[((size_t)k * dof + a) * dof + b]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+    }
+  }
+  if (sensitivity_pose >= 0 || !sensitivity_report.empty()) {
+    if (sensitivity_pose < 0 || sensitivity_pose >= N || sensitivity_report.empty()) {
+      fprintf(stderr, "--sensitivity_pose (a pose of the graph) and --sensitivity_report go together.\n");
+      return -1;
+    }
+    if (loss != 0) {
+      if (root) printf("sensitivity: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("sensitivity: not computed (the group must host every node; %d ranks)\n", world);
+    } else if (!polish) {
+      if (root) printf("sensitivity: not computed (it is taken at a critical point: --polish)\n");
+    } else {
+      int gd = 0, gN = 0, gn = 0, m = 0;
+      if (dpgo_graph_info(g, &gd, &gN, &gn, &m) != 0) return -1;
+      const int dof = d + d * (d - 1) / 2, no = 2 + dof;
+      const size_t n = (size_t)dof * N;
+      std::vector<int> I(m), J(m);
+      std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m);
+      if (dpgo_graph_edges(g, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data()) != 0) return -1;
+      // the dof unit columns of the pose: row a of the report's block of an edge is d x_pose[a] / d (kappa, tau, t~, eta)
+      std::vector<double> Xc((size_t)ld * d, 0.0), up(n * dof, 0.0), sens((size_t)dof * m * no, 0.0);
+      for (int a = 0; a < dof; a++) up[(size_t)a * n + (size_t)dof * sensitivity_pose + a] = 1.0;
+      dpgo_sens_result_t sr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_sensitivity(grp, g, Xc.data(), ld, 0, 0, up.data(), (int)n, dof, nullptr, sens.data(), &sr) != 0)
+        return -1;
+      printf("sensitivity: %s %d %d %d %d %lld %.16g %.16g\n",
+             sr.outcome == DPGO_SENS_OK ? "OK" : sr.outcome == DPGO_SENS_NOT_PD ? "NOT_PD" : "SKIPPED", sensitivity_pose, sr.edges,
+             sr.columns, sr.batches, sr.device_bytes, sr.pivot_min, sr.stationarity);
+      if (sr.outcome == DPGO_SENS_OK) {
+        auto node_of = [&](int p) {
+          int a = 0;
+          while (a + 1 < num_nodes && dpgo_graph_node_offset(g, a + 1) <= p) a++;
+          return a;
+        };
+        FILE *f = fopen(sensitivity_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", sensitivity_report.c_str()); return -1; }
+        for (int e = 0; e < m; e++) {
+          fprintf(f, "%d %d %d %d", e, I[e], J[e], node_of(I[e]) != node_of(J[e]) ? 1 : 0);
+          for (int a = 0; a < dof; a++)
+            for (int b = 0; b < no; b++) fprintf(f, " %.17g", sens[((size_t)a * m + e) * no + b]);
           fprintf(f, "\n");
         }
         fclose(f);

@@ -35,6 +35,7 @@
 #include "polish.h"
 #include "robust.h"
 #include "schedule.h"
+#include "sens.h"
 #include "settings.h"
 #include "spd_solve.h"
 #include "stair.h"
@@ -233,6 +234,11 @@ class Group {
                       double *joint, double *rel, double *gate, PairsResult &out);
   // measurement: ncols unit columns solved one at a time with spd_vsolve_device on the same factor; ms: of the solves
   int pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms);
+  // ---- measurement sensitivities (sens.h, sens.cpp): the covariance's factor, the adjoints H^-1 c of k upstream gradients by
+  // spd_msolve_device, and per edge of g the derivative of each L_l in (kappa, tau, t~, R~).  g: as for the robust objective;
+  // upstream: (dof N) x k column-major by global pose (ldu >= dof N); adjoint (optional): (dof N) x k; sens: k x num_edges x (2 + dof)
+  int sensitivity(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, const double *upstream, int ldu, int k,
+                  double *adjoint, double *sens, SensResult &out);
   // ---- the Riemannian staircase (stair.h, stair.cpp): TNT at rank r, verify on Lambda(Y), the escape along the certificate's
   // direction, the rounding, the polish.  X: global (d+1)N x d; Xhat (ldx >= (d+1) N): the result, written unless SKIPPED; Y
   // (optional, (d+1)N x 2d): the final lifted point; log (optional, log_cap rows of STAIR_LOG_COLS doubles): one row per level
@@ -703,6 +709,8 @@ class Group {
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
   void gnc_summary(GncSummaryDev &sd);
   int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out);   // likewise (pairs.cpp)
+  // a graph checked against the group; rec: its edge records in graph order, heads on unified own rows (robust.cpp; sens.cpp too)
+  int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec);
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

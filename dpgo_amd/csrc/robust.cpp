@@ -37,13 +37,9 @@ static bool robust_args_ok(int loss, double loss_reg, int curvature, const char 
   return true;
 }
 
-// The arguments, the group (cov_begin), the pattern, and the lists of g on the group's unified own rows -- rebuilt only when
-// the records differ from those of the last call.  Nothing is allocated on the device for them here.  robust_set (optional,
-// one int per edge): overwrites the inter word of the plan's records, which are the key of that comparison.
-int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who,
-                        const int *robust_set) {
-  if (!robust_args_ok(loss, loss_reg, curvature, who)) return -1;
-  if (cov_begin(X, ld, anchor) != 0) return -1;
+// The graph against the group (behind cert_begin): its dimension, its poses, and -- with the certificate's pattern built -- its
+// edge records in graph order with the heads on unified own rows.  Shared with sens.cpp.
+int Group::graph_records_own(const Graph &g, const char *who, std::vector<double> &rec) {
   const int N = P0_, m = (int)g.all.size();
   if (g.d != d_ || g.num_poses != N || m == 0) {
     fprintf(stderr, "[dpgo_amd] ERROR: %s: the graph is not one of the group's poses (d %d / %d, poses %d / %d).\n", who, g.d, d_,
@@ -60,16 +56,35 @@ int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, doubl
   std::vector<int> row_of(N);
   for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   const int L = edge_rec_doubles(d_);
-  std::vector<double> rec;
   edge_records(g, rec);
   for (int e = 0; e < m; e++) {   // the heads on unified own rows
     int head[4];
     std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
     head[0] = row_of[head[0]];
     head[1] = row_of[head[1]];
-    if (robust_set) head[2] = robust_set[e] != 0;   // the caller's robust set instead of the inter rule (gnc.h)
     std::memcpy(&rec[(size_t)e * L], head, sizeof(head));
   }
+  return 0;
+}
+
+// The arguments, the group (cov_begin), the pattern, and the lists of g on the group's unified own rows -- rebuilt only when
+// the records differ from those of the last call.  Nothing is allocated on the device for them here.  robust_set (optional,
+// one int per edge): overwrites the inter word of the plan's records, which are the key of that comparison.
+int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, const char *who,
+                        const int *robust_set) {
+  if (!robust_args_ok(loss, loss_reg, curvature, who)) return -1;
+  if (cov_begin(X, ld, anchor) != 0) return -1;
+  std::vector<double> rec;
+  if (graph_records_own(g, who, rec) != 0) return -1;
+  const int N = P0_, m = (int)g.all.size(), L = edge_rec_doubles(d_);
+  CertState &c = *cert_;
+  if (robust_set)
+    for (int e = 0; e < m; e++) {   // the caller's robust set instead of the inter rule (gnc.h)
+      int head[4];
+      std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
+      head[2] = robust_set[e] != 0;
+      std::memcpy(&rec[(size_t)e * L], head, sizeof(head));
+    }
   if (rob_ && rob_->plan.rec.size() == rec.size() && std::memcmp(rob_->plan.rec.data(), rec.data(), rec.size() * sizeof(double)) == 0)
     return 0;
   RobustPlan pl;

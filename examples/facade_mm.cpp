@@ -29,6 +29,11 @@
 //   pairs: joint <k> <the 3 dof^2 entries>     pairs: rel <k> <the dof^2 entries>     pairs: gate <k> <d2 not_pd residual>
 // then   pairs: <OK|NOT_PD|SKIPPED|FAILED> <columns> <batches> <stationarity>; a last call with candidates of the wrong length
 // must fail:   pairs: short candidates <status>
+// and with `sensitivity <pose>` through DPGOHashGroup::newton_polish and DPGOHashGroup::measurement_sensitivities (trivial
+// loss; pose 0 is the anchor) with the dof unit columns of the pose: per edge one line, all entries with 17 digits,
+//   sensitivity: e <edge> <the dof x (2 + dof) entries, row a the derivatives of coordinate a of the pose>
+// then   sensitivity: <OK|NOT_PD|SKIPPED|FAILED> <edges> <columns> <batches>; a last call with an upstream of the wrong length
+// must fail:   sensitivity: short upstream <status> <size of sens>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -48,7 +53,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -255,6 +260,31 @@ int main(int argc, char **argv) {
     int short_status = 0;
     dpgo_hash.pair_covariances(X, pairs, joint, rel, 0, nullptr, &short_status, &cand, &gate);
     fprintf(stderr, "pairs: short candidates %d %d\n", short_status, (int)gate.size());
+  }
+  if (argc > 7 && !strcmp(argv[6], "sensitivity")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2, no = 2 + dof, m = graph->num_edges(), pose = atoi(argv[7]);
+    if (pose < 0 || pose >= graph->num_poses() || !dpgo_hash.newton_polish(X, Xp)) return 1;
+    const size_t n = (size_t)dof * graph->num_poses();
+    std::vector<double> up(n * dof, 0.0), sens;
+    for (int a = 0; a < dof; a++) up[(size_t)a * n + (size_t)dof * pose + a] = 1.0;
+    int status = -1;
+    dpgo_sens_result_t r = {};
+    const bool ok = dpgo_hash.measurement_sensitivities(Xp, up, sens, 0, &r, &status);
+    for (int e = 0; ok && e < m; e++) {
+      fprintf(stderr, "sensitivity: e %d", e);
+      for (int a = 0; a < dof; a++)
+        for (int b = 0; b < no; b++) fprintf(stderr, " %.17g", sens[((size_t)a * m + e) * no + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "sensitivity: %s %d %d %d\n", status == DPGO_SENS_OK ? "OK" : status == DPGO_SENS_NOT_PD ? "NOT_PD"
+            : status == DPGO_SENS_SKIPPED ? "SKIPPED" : "FAILED", r.edges, r.columns, r.batches);
+    if (status < 0) return 1;
+    up.pop_back();
+    int short_status = 0;
+    dpgo_hash.measurement_sensitivities(Xp, up, sens, 0, nullptr, &short_status);
+    fprintf(stderr, "sensitivity: short upstream %d %d\n", short_status, (int)sens.size());
   }
   return 0;
 }

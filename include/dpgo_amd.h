@@ -597,6 +597,43 @@ int dpgo_debug_pairs_plan(int dof, int anchor, const int *pairs, int npairs, int
 int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const double *joint, const double *cand, double *rel,
                           double *gate);
 
+/* ---- measurement sensitivities: implicit differentiation of the solution ------------------ */
+/* How does the solution depend on the measurements it was computed from?  At a critical point X* the implicit function
+ * theorem gives dX* / dtheta = -H^-1 d_theta g, with H the anchored tangent-space Hessian of dpgo_group_covariance and g the
+ * tangent gradient.  For k scalars L_l(X*) whose tangent gradients at X* are the columns c_l of `upstream`, the adjoints
+ * lambda_l = H^-1 c_l are solved for on the device (the factor and the block solve of dpgo_group_pair_covariance, at most 64
+ * columns per batch), and one kernel gives, for EVERY edge e and every l,
+ *     dL_l / dtheta_e = -d phi_e / d theta_e,    phi_e(lambda; theta_e) = D_lambda (1/2 tau |t_j - t_i - R_i t~|^2 + 1/2 kappa |R_j - R_i R~|_F^2)
+ * -- the mixed second derivative of the edge's own term.  Restrictions, anchor and coordinates as for dpgo_group_covariance;
+ * X should be a critical point (dpgo_group_polish): `stationarity` reports |S X|_F, nothing is enforced.  The optimiser is not
+ * touched.  The robust objective is out of scope; the re-weighted problem is reached through dpgo_graph_scale_edges.
+ *   graph       the graph the group was created from (or one of the same poses whose every edge is a block of the group's
+ *               pattern: the rule of dpgo_group_robust_polish, -1 otherwise); it fixes the order of the edges in `sens`
+ *   upstream    (dof N) x k column-major, ldu >= dof N, by global pose: entry dof p + a of a column is the derivative of L along
+ *               coordinate a of pose p (a < d: t_p + dt in the world frame; the rest: R_p <- R_p Exp(hat(omega))).  The anchor's
+ *               rows are ignored.  A non-finite entry: -1
+ *   adjoint     NULL, or (dof N) x k column-major: lambda_l by global pose, exact zeros on the anchor
+ *   sens        k x num_edges x (2 + dof): [l][e][d/dkappa, d/dtau, d/dt~[0..d), d/deta[0..dof-d)], with t~ + dt~ (raw entries)
+ *               and R~ <- R~ Exp(hat(eta)).  Column l's bits do not depend on k, on its position or on the other columns
+ *   result      outcome SENS_OK, SENS_NOT_PD (the anchored H is not positive definite; the outputs are zero) or SENS_SKIPPED
+ *               (device_bytes above max_bytes (> 0) or above half of the free device memory; the outputs are not written,
+ *               nothing is allocated); columns: k, batches: block solves, edges: num_edges; factor_ms / solve_ms / edge_ms:
+ *               host milliseconds of the factorisation, of the batches' uploads, solves and adjoint read-outs, and of the
+ *               edge kernel with the copies of its output, each ending in a synchronise */
+#define DPGO_SENS_OK 0
+#define DPGO_SENS_NOT_PD 1
+#define DPGO_SENS_SKIPPED 2
+typedef struct dpgo_sens_result {
+  int outcome, unknowns, fronts, levels, max_front, columns, batches, edges;
+  long long device_bytes;
+  double pivot_min, pivot_max, stationarity, symbolic_s, factor_ms, solve_ms, edge_ms;
+} dpgo_sens_result_t;
+int dpgo_group_sensitivity(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, long long max_bytes,
+                           const double *upstream, int ldu, int k, double *adjoint, double *sens, dpgo_sens_result_t *result);
+/* Debug (no device): the arithmetic of k_sens_edge on the host for one adjoint -- lambda: dof N by global pose (used as given:
+ * no anchor is struck out); sens: num_edges x (2 + dof) in the order above; phi: num_edges (phi_e) or NULL. */
+int dpgo_debug_sens_edge_host(const dpgo_graph_t *graph, const double *X, int ld, const double *lambda, double *sens, double *phi);
+
 /* ---- Newton polish: from the point the optimiser stopped at to a critical point ----------- */
 /* AMM-PGO# is a first-order method; the certificate and the covariances above mean something only at a critical point.
  * dpgo_group_polish takes damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored tangent-space Hessian

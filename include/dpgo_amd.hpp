@@ -281,6 +281,29 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_PAIRS_OK;
   }
+  // Measurement sensitivities by implicit differentiation (dpgo_group_sensitivity): upstream holds k tangent gradients of
+  // scalars L_l(X), (dof N) x k column-major by global pose in marginal_covariances' coordinates; sens is resized to
+  // k num_edges (2 + dof) doubles, [l][e][d/dkappa, d/dtau, d/dt~, d/deta] with the edges in the graph's order; adjoint
+  // (optional) to (dof N) k: lambda_l = H^-1 c_l, zeros on the anchor.  X should be a critical point (newton_polish).  Returns
+  // true for DPGO_SENS_OK; status: the DPGO_SENS_* outcome, -1 when the call itself failed (robust loss, a group that does not
+  // host every node, an upstream of the wrong size or with an entry that is not finite).
+  bool measurement_sensitivities(const Matrix &X, const std::vector<Scalar> &upstream, std::vector<Scalar> &sens, int anchor = 0,
+                                 dpgo_sens_result_t *result = nullptr, int *status = nullptr, std::vector<Scalar> *adjoint = nullptr,
+                                 long long max_bytes = 0) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2, m = graph_->num_edges();
+    const size_t n = (size_t)dof * graph_->num_poses();
+    const int k = n ? (int)(upstream.size() / n) : 0;
+    const bool sized = k >= 1 && upstream.size() == n * (size_t)k;
+    sens.assign(sized ? (size_t)k * m * (2 + dof) : 0, 0.0);
+    if (adjoint) adjoint->assign(sized ? n * (size_t)k : 0, 0.0);
+    dpgo_sens_result_t r = {};
+    const int rc = !sized ? -1
+                          : dpgo_group_sensitivity(h_, graph_->handle(), X.data(), X.rows(), anchor, max_bytes, upstream.data(), (int)n, k,
+                                                   adjoint ? adjoint->data() : nullptr, sens.data(), &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_SENS_OK;
+  }
   // Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X on the anchored tangent-space Hessian of
   // marginal_covariances, until the tangent gradient is at rounding level or the step budget is spent.  Xout: the new point
   // (X itself when the call is SKIPPED or fails).  opt (optional): the rule's parameters and the anchor; log (optional): per
