@@ -275,6 +275,9 @@ SYMBOLS = {
     "dpgo_group_robust_matrix": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
                                            C.POINTER(C.c_longlong)]),
     "dpgo_debug_robust_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP]),
+    "dpgo_group_robust_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong, _DP,
+                                                C.c_int, C.c_int, _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_debug_robust_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "dpgo_gnc_options_default": (None, [C.c_void_p]),
     "dpgo_group_gnc": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_void_p, _IP, C.c_longlong, _DP, C.c_int, _DP, _DP, C.c_int,
                                  C.c_void_p]),
@@ -1319,6 +1322,34 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_robust_covariance failed (a robust-loss group, a group that does not host every node, a "
                                "graph that is not the group's, a bad loss, loss_reg, curvature, anchor or pair, or bad sizes)")
         return marg, cross, r
+
+    def robust_sensitivity(self, X, upstream, loss, loss_reg=0.25, anchor=0, max_bytes=0, graph=None, want_adjoint=False):
+        """Measurement sensitivities at a critical point X of the ROBUST objective (dpgo_group_robust_sensitivity), the loss
+        threshold delta = loss_reg one more parameter: `sensitivity` with the adjoints lambda_l = H^-1 c_l on the TRUE robust
+        Hessian of `robust_covariance` (curvature 1) and, per edge, dL_l/dtheta_e = -[w_e d phi_e/d theta_e + (c_e / 2) phi_e
+        d s_e/d theta_e].  X should come from `robust_polish` with the same loss and loss_reg: result.stationarity = |S_w X|_F.
+        Returns (SensResult, sens, dloss_reg) with sens (k, num_edges, 3 + dof) -- dL_l/d(kappa, tau, t~, eta) and, last, the
+        edge's term of dL_l/d delta -- and dloss_reg (k,) = dL_l/d delta, those terms summed in edge order; with want_adjoint
+        also lambda (dof N, k).  Intra edges carry `sensitivity`'s values, an edge whose weight is exactly 0 exact zeros;
+        LOSS_NONE gives `sensitivity`'s values and zero delta terms.  SENS_NOT_PD (zero outputs) is a legitimate answer under
+        Geman-McClure and Welsch; SENS_SKIPPED as in `sensitivity`.  A column's bits do not depend on the other columns."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        n = _dof(self.d) * self.graph.num_poses
+        U_ = np.asarray(upstream, np.float64)
+        U_ = np.asfortranarray(U_.reshape(-1, 1) if U_.ndim == 1 else U_)
+        if U_.ndim != 2 or U_.shape[0] != n or U_.shape[1] < 1:
+            raise ValueError("robust_sensitivity: upstream must be (dof N, k) with k >= 1")
+        k = U_.shape[1]
+        sens, dreg = np.zeros((k, g_.num_edges, 3 + _dof(self.d))), np.zeros(k)
+        adj = np.zeros((n, k), order="F") if want_adjoint else None
+        r = SensResult()
+        if lib().dpgo_group_robust_sensitivity(self._h, g_._h, _dp(X), ld, int(loss), float(loss_reg), int(anchor), int(max_bytes),
+                                               _dp(U_), n, k, _dpn(adj), _dp(sens), _dp(dreg), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_robust_sensitivity failed (a robust-loss group, a group that does not host every node, a "
+                               "graph that is not the group's, a bad loss, loss_reg or anchor, an upstream entry that is not "
+                               "finite, or bad sizes)")
+        return (r, sens, dreg, adj) if want_adjoint else (r, sens, dreg)
 
     def robust_hessian(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, graph=None, edges=False):
         """Debug: the anchored Hessian of the robust objective as the device wrote it (dpgo_group_robust_hessian).  Returns
@@ -2477,6 +2508,22 @@ def robust_edge_debug(graph, X, loss=LOSS_NONE, loss_reg=0.25):
     if lib().dpgo_debug_robust_edge_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), _dp(w), _dp(c), _dp(rows), _dp(gh)) != 0:
         raise ValueError("dpgo_debug_robust_edge_host failed (a short X, an unknown loss, or a bad loss_reg)")
     return w, c, rows, gh
+
+
+def robust_sens_edge_debug(graph, X, lam, loss=LOSS_NONE, loss_reg=0.25):
+    """Debug, no GPU: the per-edge arithmetic of the robust sensitivities' kernels on the host
+    (dpgo_debug_robust_sens_edge_host) for one adjoint `lam` (dof N by global pose, used as given).  Returns (sens, phi):
+    (num_edges, 3 + dof) in NodeGroup.robust_sensitivity's order, and phi_e per edge."""
+    X, ld = _fcol(X)
+    dof, m = _dof(graph.d), graph.num_edges
+    lam = np.ascontiguousarray(lam, np.float64)
+    if lam.shape != (dof * graph.num_poses,):
+        raise ValueError("robust_sens_edge_debug: lam must have dof N entries")
+    sens, phi = np.zeros((m, 3 + dof)), np.zeros(m)
+    if lib().dpgo_debug_robust_sens_edge_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), _dp(lam), _dp(sens), _dp(phi)) != 0:
+        raise ValueError("dpgo_debug_robust_sens_edge_host failed (a short X, an edge outside the graph, an unknown loss, or a bad "
+                         "loss_reg)")
+    return sens, phi
 
 
 def verify_reweighted(graph, X, loss, loss_reg=0.25, eta=1e-3, tau=1e-6, max_iters=2000, precondition=True,

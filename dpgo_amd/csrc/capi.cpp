@@ -996,6 +996,19 @@ int dpgo_group_robust_covariance(dpgo_group_t *h, const dpgo_graph_t *g, const d
   });
 }
 
+int dpgo_group_robust_sensitivity(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, int anchor,
+                                  long long max_bytes, const double *upstream, int ldu, int k, double *adjoint, double *sens,
+                                  double *dloss_reg, dpgo_sens_result_t *result) {
+  if (!h || !h->grp || !g || !X || !upstream || !sens || !dloss_reg || !result || k < 1) return -1;
+  return guarded([&] {
+    dpgo::SensResult r;
+    const int rc = h->grp->robust_sensitivity(g->g, X, ld, loss, loss_reg, anchor, max_bytes, upstream, ldu, k, adjoint, sens,
+                                              dloss_reg, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
 int dpgo_group_robust_hessian(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, int curvature,
                               int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz, double *grad, double *F,
                               double *w, double *c, double *s_rot, double *s_trans, double *rho) {

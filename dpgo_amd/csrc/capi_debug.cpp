@@ -824,6 +824,12 @@ int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, co
   return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });
 }
 
+int dpgo_debug_robust_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, const double *lambda,
+                                     double *sens, double *phi) {
+  if (!g) return -1;
+  return guarded([&] { return dpgo::robust_sens_edge_host(g->g, X, ld, loss, loss_reg, lambda, sens, phi); });
+}
+
 int dpgo_debug_rayleigh_ritz(int ns, int nblk, const double *A, const double *B, double *theta, double *C, int *used) {
   if (!A || !B || !theta || !C || !used) return -1;
   return guarded([&] { return dpgo::rayleigh_ritz(ns, nblk, A, B, theta, C, used); });

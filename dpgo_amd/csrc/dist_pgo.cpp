@@ -62,6 +62,10 @@
 //                  sensitivity: <outcome> <P> <edges> <columns> <batches> <device_bytes> <pivot_min> <stationarity>
 //              and, for OK, one line per edge in FILE: e i j inter, then dof x (2 + dof) values, row a the derivatives of
 //              coordinate a of the pose in (kappa, tau, t~, eta); "sensitivity: not computed (...)" says why not
+//              With a robust --loss behind --robust_polish (one rank): dpgo_group_robust_sensitivity with the run's loss and
+//              loss_reg on the robust polish's point and group; the line's prefix is "robust sensitivity:", every row of FILE
+//              has dof x (3 + dof) values -- one more per row, the edge's term of the derivative in the loss threshold -- and
+//              a last line "delta" with the dof values of d x_pose / d delta
 //              --gate_candidates FILE --gate_report FILE (likewise; both or neither)  beside --covariance, for the trivial loss
 //              and a world of one rank: FILE is a .g2o of candidate edges p -> q, read by the loader's edge parser; every
 //              candidate is tested against the final X with dpgo_group_pair_covariance (pose 0 the anchor), one line per
@@ -531,7 +535,6 @@ int main(int argc, char **argv) {
       }
     }
   }
-  if (post) dpgo_group_free(post);
   if (!gate_candidates.empty() || !gate_report.empty()) {
     if (gate_candidates.empty() || gate_report.empty()) {
       fprintf(stderr, "--gate_candidates and --gate_report go together.\n");
@@ -592,7 +595,46 @@ int main(int argc, char **argv) {
       fprintf(stderr, "--sensitivity_pose (a pose of the graph) and --sensitivity_report go together.\n");
       return -1;
     }
-    if (loss != 0) {
+    if (loss != 0 && robust_polish && world == 1) {
+      // the robust objective at the robust polish's point: one more value per row, the edge's term of d/ddelta, and a last line
+      // "delta" with the dof values of d x_pose / d delta
+      int gd = 0, gN = 0, gn = 0, m = 0;
+      if (dpgo_graph_info(g, &gd, &gN, &gn, &m) != 0) return -1;
+      const int dof = d + d * (d - 1) / 2, no = 3 + dof;
+      const size_t n = (size_t)dof * N;
+      std::vector<int> I(m), J(m);
+      std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m);
+      if (dpgo_graph_edges(g, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data()) != 0) return -1;
+      std::vector<double> Xc((size_t)ld * d, 0.0), up(n * dof, 0.0), sens((size_t)dof * m * no, 0.0), dreg(dof, 0.0);
+      for (int a = 0; a < dof; a++) up[(size_t)a * n + (size_t)dof * sensitivity_pose + a] = 1.0;
+      dpgo_sens_result_t sr;
+      if (final_point(Xc.data()) != 0 || post_group() != 0 ||
+          dpgo_group_robust_sensitivity(post, g, Xc.data(), ld, loss, opt.loss_reg, 0, 0, up.data(), (int)n, dof, nullptr, sens.data(),
+                                        dreg.data(), &sr) != 0)
+        return -1;
+      printf("robust sensitivity: %s %d %d %d %d %lld %.16g %.16g\n",
+             sr.outcome == DPGO_SENS_OK ? "OK" : sr.outcome == DPGO_SENS_NOT_PD ? "NOT_PD" : "SKIPPED", sensitivity_pose, sr.edges,
+             sr.columns, sr.batches, sr.device_bytes, sr.pivot_min, sr.stationarity);
+      if (sr.outcome == DPGO_SENS_OK) {
+        auto node_of = [&](int p) {
+          int a = 0;
+          while (a + 1 < num_nodes && dpgo_graph_node_offset(g, a + 1) <= p) a++;
+          return a;
+        };
+        FILE *f = fopen(sensitivity_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", sensitivity_report.c_str()); return -1; }
+        for (int e = 0; e < m; e++) {
+          fprintf(f, "%d %d %d %d", e, I[e], J[e], node_of(I[e]) != node_of(J[e]) ? 1 : 0);
+          for (int a = 0; a < dof; a++)
+            for (int b = 0; b < no; b++) fprintf(f, " %.17g", sens[((size_t)a * m + e) * no + b]);
+          fprintf(f, "\n");
+        }
+        fprintf(f, "delta");
+        for (int a = 0; a < dof; a++) fprintf(f, " %.17g", dreg[a]);
+        fprintf(f, "\n");
+        fclose(f);
+      }
+    } else if (loss != 0) {
       if (root) printf("sensitivity: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
     } else if (world > 1) {
       if (root) printf("sensitivity: not computed (the group must host every node; %d ranks)\n", world);
@@ -634,6 +676,7 @@ int main(int argc, char **argv) {
       }
     }
   }
+  if (post) dpgo_group_free(post);
   if (save) {
     std::fill(X.begin(), X.end(), 0.0);
     final_point(X.data());

@@ -34,6 +34,7 @@
 #include "gnc.h"
 #include "polish.h"
 #include "robust.h"
+#include "rsens.h"
 #include "schedule.h"
 #include "sens.h"
 #include "settings.h"
@@ -239,6 +240,11 @@ class Group {
   // upstream: (dof N) x k column-major by global pose (ldu >= dof N); adjoint (optional): (dof N) x k; sens: k x num_edges x (2 + dof)
   int sensitivity(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, const double *upstream, int ldu, int k,
                   double *adjoint, double *sens, SensResult &out);
+  // ---- ... of the ROBUST objective (rsens.h, rsens.cpp): the same on the true robust Hessian (robust_covariance's, curvature 1)
+  // with the loss threshold one more parameter.  sens: k x num_edges x (3 + dof), the last entry the edge's term of dL/ddelta;
+  // dloss_reg: k, their sums over the edges
+  int robust_sensitivity(const Graph &g, const double *X, int ld, int loss, double loss_reg, int anchor, long long max_bytes,
+                         const double *upstream, int ldu, int k, double *adjoint, double *sens, double *dloss_reg, SensResult &out);
   // ---- the Riemannian staircase (stair.h, stair.cpp): TNT at rank r, verify on Lambda(Y), the escape along the certificate's
   // direction, the rounding, the polish.  X: global (d+1)N x d; Xhat (ldx >= (d+1) N): the result, written unless SKIPPED; Y
   // (optional, (d+1)N x 2d): the final lifted point; log (optional, log_cap rows of STAIR_LOG_COLS doubles): one row per level
@@ -708,7 +714,8 @@ class Group {
   void gnc_alloc();
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
   void gnc_summary(GncSummaryDev &sd);
-  int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out);   // likewise (pairs.cpp)
+  // likewise (pairs.cpp); own_remain: those of own_bytes still to be allocated, as cov_setup's extra_remain (< 0: all of them)
+  int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out, long long own_remain = -1);
   // a graph checked against the group; rec: its edge records in graph order, heads on unified own rows (robust.cpp; sens.cpp too)
   int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec);
   bool star_ = false;

@@ -34,7 +34,7 @@ PairsPlan pairs_plan(int dof, int anchor, const int *pairs, int npairs) {
 // The analysis (first call), the prediction, the refusal, the numeric context (first call that is not refused): polish_setup's
 // rule on the bytes of the numeric phase, the block solve and this call's own buffers -- not on the blocks of the selected
 // inversion.
-int Group::pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out) {
+int Group::pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out, long long own_remain) {
   CovResult cr;
   if (cov_analyse(cr) != 0) return -1;
   CertState &c = *cert_;
@@ -52,7 +52,7 @@ int Group::pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsRe
   if (max_bytes > 0 && out.device_bytes > max_bytes) return 1;
   // against the free memory: the numeric phase only where no earlier call has left it (the solve's buffers are counted
   // whether an earlier call has left them or not)
-  const long long remain = (s.F.numeric ? 0 : numeric) + solve + own_bytes;
+  const long long remain = (s.F.numeric ? 0 : numeric) + solve + (own_remain < 0 ? own_bytes : own_remain);
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   if ((unsigned long long)remain > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)

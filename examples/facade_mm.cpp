@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -34,6 +34,12 @@
 //   sensitivity: e <edge> <the dof x (2 + dof) entries, row a the derivatives of coordinate a of the pose>
 // then   sensitivity: <OK|NOT_PD|SKIPPED|FAILED> <edges> <columns> <batches>; a last call with an upstream of the wrong length
 // must fail:   sensitivity: short upstream <status> <size of sens>
+// and with `robust_sensitivity <pose>` (a robust loss) through DPGOHashGroup::robust_newton_polish and
+// DPGOHashGroup::robust_measurement_sensitivities on a second, trivial-loss group of the same graph, with the loss and loss_reg
+// of the run and the dof unit columns of the pose: per edge one line, all entries with 17 digits,
+//   robust sensitivity: e <edge> <the dof x (3 + dof) entries, the last of a row the edge's term of d/dloss_reg>
+// then   robust sensitivity: delta <the dof values of d x_pose / d loss_reg>
+// then   robust sensitivity: <OK|NOT_PD|SKIPPED|FAILED> <edges> <columns> <batches>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -53,7 +59,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -285,6 +291,38 @@ int main(int argc, char **argv) {
     int short_status = 0;
     dpgo_hash.measurement_sensitivities(Xp, up, sens, 0, nullptr, &short_status);
     fprintf(stderr, "sensitivity: short upstream %d %d\n", short_status, (int)sens.size());
+  }
+  if (argc > 7 && !strcmp(argv[6], "robust_sensitivity")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    DPGO::Options trivial = DPGO::Options::driver(DPGO::Loss::None, acc);
+    trivial.max_iterations = 0;
+    DPGO::DPGOHashGroup post(graph, all, trivial, 0);
+    const double loss_reg = DPGO::Options::driver(l, acc).loss_reg;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2, no = 3 + dof, m = graph->num_edges(), pose = atoi(argv[7]);
+    int polished = -1;
+    post.robust_newton_polish(X, l, loss_reg, Xp, nullptr, &polished);   // (Xp is X itself where the polish is SKIPPED)
+    if (pose < 0 || pose >= graph->num_poses() || polished < 0) return 1;
+    const size_t n = (size_t)dof * graph->num_poses();
+    std::vector<double> up(n * dof, 0.0), sens, dreg;
+    for (int a = 0; a < dof; a++) up[(size_t)a * n + (size_t)dof * pose + a] = 1.0;
+    int status = -1;
+    dpgo_sens_result_t r = {};
+    const bool ok = post.robust_measurement_sensitivities(Xp, l, loss_reg, up, sens, dreg, 0, &r, &status);
+    for (int e = 0; ok && e < m; e++) {
+      fprintf(stderr, "robust sensitivity: e %d", e);
+      for (int a = 0; a < dof; a++)
+        for (int b = 0; b < no; b++) fprintf(stderr, " %.17g", sens[((size_t)a * m + e) * no + b]);
+      fprintf(stderr, "\n");
+    }
+    if (ok) {
+      fprintf(stderr, "robust sensitivity: delta");
+      for (int a = 0; a < dof; a++) fprintf(stderr, " %.17g", dreg[a]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "robust sensitivity: %s %d %d %d\n", status == DPGO_SENS_OK ? "OK" : status == DPGO_SENS_NOT_PD ? "NOT_PD"
+            : status == DPGO_SENS_SKIPPED ? "SKIPPED" : "FAILED", r.edges, r.columns, r.batches);
+    if (status < 0) return 1;
   }
   return 0;
 }

@@ -606,7 +606,8 @@ int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const d
  *     dL_l / dtheta_e = -d phi_e / d theta_e,    phi_e(lambda; theta_e) = D_lambda (1/2 tau |t_j - t_i - R_i t~|^2 + 1/2 kappa |R_j - R_i R~|_F^2)
  * -- the mixed second derivative of the edge's own term.  Restrictions, anchor and coordinates as for dpgo_group_covariance;
  * X should be a critical point (dpgo_group_polish): `stationarity` reports |S X|_F, nothing is enforced.  The optimiser is not
- * touched.  The robust objective is out of scope; the re-weighted problem is reached through dpgo_graph_scale_edges.
+ * touched.  The robust objective has a call of its own, dpgo_group_robust_sensitivity (below, behind the Newton polish); the
+ * re-weighted problem is reached through dpgo_graph_scale_edges.
  *   graph       the graph the group was created from (or one of the same poses whose every edge is a block of the group's
  *               pattern: the rule of dpgo_group_robust_polish, -1 otherwise); it fixes the order of the edges in `sens`
  *   upstream    (dof N) x k column-major, ldu >= dof N, by global pose: entry dof p + a of a column is the derivative of L along
@@ -713,6 +714,17 @@ int dpgo_group_polish(dpgo_group_t *grp, const double *X, int ld, const dpgo_pol
  *   pose, zeros on the anchor), F, and per edge w, c, s_rot, s_trans and rho (num_edges each; every value of
  *   dpgo_edge_eval_run's bit for bit).
  * dpgo_group_robust_matrix (debug): M_w as dpgo_group_cert_matrix hands out S.
+ * dpgo_group_robust_sensitivity: dpgo_group_sensitivity at a critical point of the robust objective, the loss threshold delta =
+ *   loss_reg one more parameter.  The adjoints are lambda_l = H^-1 c_l on the TRUE robust Hessian (curvature 1), and with
+ *   phi_e = D_lambda (1/2 s_e):  dL/dtheta_e = -[w_e d phi_e/d theta_e + (c_e / 2) phi_e d s_e/d theta_e],
+ *   dL/ddelta = -sum_inter (d w_e/d delta) phi_e.  upstream, adjoint, anchor, max_bytes and result as for
+ *   dpgo_group_sensitivity (stationarity = |S_w X|_F, not computed for SKIPPED; device_bytes counts the robust buffers too);
+ *   sens: k x num_edges x (3 + dof), [l][e][d/dkappa, d/dtau, d/dt~, d/deta, the edge's term of d/ddelta]; dloss_reg: k doubles,
+ *   dL_l/ddelta -- the last entries summed over the edges in ascending order.  Intra edges carry dpgo_group_sensitivity's
+ *   values; an edge whose weight is exactly 0 gives exact zeros; loss 0 gives dpgo_group_sensitivity's values and zero delta
+ *   terms.  SENS_NOT_PD is a legitimate answer under Geman-McClure and Welsch.
+ * dpgo_debug_robust_sens_edge_host (no GPU): the kernels' arithmetic for one adjoint lambda (dof N by global pose, used as
+ *   given); sens: num_edges x (3 + dof), phi: num_edges or NULL.
  * dpgo_debug_robust_edge_host (no GPU): per edge w, c, rows (2 pose records: (M_e X)_i, (M_e X)_j, each t-row then d rows) and
  *   ghat (2 dof: g_e at i, at j) through the kernels' own arithmetic; any output may be NULL. */
 int dpgo_group_robust_polish(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
@@ -721,6 +733,11 @@ int dpgo_group_robust_polish(dpgo_group_t *grp, const dpgo_graph_t *graph, const
 int dpgo_group_robust_covariance(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
                                  int curvature, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                  double *cross, dpgo_cov_result_t *result);
+int dpgo_group_robust_sensitivity(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                                  int anchor, long long max_bytes, const double *upstream, int ldu, int k, double *adjoint,
+                                  double *sens, double *dloss_reg, dpgo_sens_result_t *result);
+int dpgo_debug_robust_sens_edge_host(const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
+                                     const double *lambda, double *sens, double *phi);
 int dpgo_group_robust_hessian(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg,
                               int curvature, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz,
                               double *grad, double *F, double *w, double *c, double *s_rot, double *s_trans, double *rho);

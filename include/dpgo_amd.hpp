@@ -393,6 +393,31 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_COV_OK;
   }
+  // Measurement sensitivities of the robust objective (dpgo_group_robust_sensitivity): measurement_sensitivities at a critical
+  // point of the robust objective (robust_newton_polish with the same loss and loss_reg), the adjoints on its true Hessian, the
+  // loss threshold one more parameter.  sens is resized to k num_edges (3 + dof): [l][e][d/dkappa, d/dtau, d/dt~, d/deta, the
+  // edge's term of d/dloss_reg]; dloss_reg to k: dL_l/dloss_reg.  DPGO_SENS_NOT_PD is a legitimate answer under Geman-McClure and
+  // Welsch.  Other arguments, returns and status as measurement_sensitivities.
+  bool robust_measurement_sensitivities(const Matrix &X, Loss loss, double loss_reg, const std::vector<Scalar> &upstream,
+                                        std::vector<Scalar> &sens, std::vector<Scalar> &dloss_reg, int anchor = 0,
+                                        dpgo_sens_result_t *result = nullptr, int *status = nullptr,
+                                        std::vector<Scalar> *adjoint = nullptr, long long max_bytes = 0) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2, m = graph_->num_edges();
+    const size_t n = (size_t)dof * graph_->num_poses();
+    const int k = n ? (int)(upstream.size() / n) : 0;
+    const bool sized = k >= 1 && upstream.size() == n * (size_t)k;
+    sens.assign(sized ? (size_t)k * m * (3 + dof) : 0, 0.0);
+    dloss_reg.assign(sized ? (size_t)k : 0, 0.0);
+    if (adjoint) adjoint->assign(sized ? n * (size_t)k : 0, 0.0);
+    dpgo_sens_result_t r = {};
+    const int rc = !sized ? -1
+                          : dpgo_group_robust_sensitivity(h_, graph_->handle(), X.data(), X.rows(), (int)loss, loss_reg, anchor, max_bytes,
+                                                          upstream.data(), (int)n, k, adjoint ? adjoint->data() : nullptr, sens.data(),
+                                                          dloss_reg.data(), &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_SENS_OK;
+  }
   // The Riemannian staircase (dpgo_group_staircase): from X -- usually a point whose certificate is NEGATIVE -- the reference's
   // truncated-Newton method at rank r, fast_verification at the lifted point, an escape along the certificate's direction one
   // rank up, until the certificate is not NEGATIVE or r = r_max <= 2d; then the rounding and a polish.  Xhat: the result, never
