@@ -233,6 +233,8 @@ SYMBOLS = {
                                             C.c_double, C.c_int, _DP, _DP]),
     "dpgo_debug_spd_solver_refactor": (C.c_int, [C.c_void_p, _DP]),
     "dpgo_debug_spd_solver_free": (None, [C.c_void_p]),
+    "dpgo_debug_spd_panel_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, _DP, C.c_int, _DP, C.c_longlong,
+                                            C.POINTER(C.c_longlong)]),
     "dpgo_debug_p2p_plan": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP, _IP]),
     "dpgo_group_debug_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, _DP, C.c_int, _DP, C.c_int]),
     "dpgo_group_debug_stpcg": (C.c_int, [C.c_void_p, _IP, C.c_int, _DP, C.c_int, _DP, C.c_int, C.c_double, _DP, C.c_int, _DP]),
@@ -892,6 +894,24 @@ class SpdSolverDebug:
         rc = lib().dpgo_debug_spd_solver_refactor(self._h, _dp(v))
         if rc != 0:
             raise RuntimeError("not positive definite" if rc == 1 else "dpgo_debug_spd_solver_refactor failed")
+
+
+def spd_panel_pack_debug(src, rows, pairs=True, mat_off=0, fill=0.0):
+    """One solve tile's panel from the host packer of SpdSolverDev::upload (test hook, dpgo_debug_spd_panel_pack; no GPU).
+    src: len x count, entry (k, r) of the tile; rows: the tile height of its class (64, 16 or 8).  Returns (panel, info):
+    the array of mat_off + panel doubles, filled with `fill` before the packer ran, and a dict ld, pair_kq, mat_off, doubles
+    as the tile's descriptor reports them."""
+    a = np.ascontiguousarray(src, np.float64)
+    if a.ndim != 2:
+        raise ValueError("src must be len x count")
+    info = np.zeros(4, np.int64)
+    args = (int(rows), a.shape[1], a.shape[0], int(bool(pairs)), int(mat_off))
+    if lib().dpgo_debug_spd_panel_pack(*args, None, 0, None, 0, info.ctypes.data_as(_LLP)) != 0:
+        raise ValueError("dpgo_debug_spd_panel_pack refused the tile")
+    panel = np.full(int(mat_off) + int(info[3]), float(fill))
+    if lib().dpgo_debug_spd_panel_pack(*args, _dp(a), a.shape[1], _dp(panel), panel.size, info.ctypes.data_as(_LLP)) != 0:
+        raise RuntimeError("dpgo_debug_spd_panel_pack failed")
+    return panel, {"ld": int(info[0]), "pair_kq": int(info[1]), "mat_off": int(info[2]), "doubles": int(info[3])}
 
 
 CG_DEBUG_KINDS = ("begin_host", "begin_device", "scal0", "scal1", "scal_begin", "reduce_gate", "reduce")

@@ -588,6 +588,17 @@ int dpgo_debug_spd_solver_refactor(dpgo_spd_solver_debug_t *h, const double *val
 
 void dpgo_debug_spd_solver_free(dpgo_spd_solver_debug_t *h) { delete h; }
 
+int dpgo_debug_spd_panel_pack(int rows, int count, int len, int pairs, long long mat_off, const double *src, int src_ld,
+                              double *panel, long long cap, long long *info) {
+  if ((rows != 64 && rows != 16 && rows != 8) || count < 1 || count > rows || len < 1 || mat_off < 0 || !info) return -1;
+  const dpgo::SpdItem it = dpgo::spd_panel_item(rows, count, pairs != 0, mat_off);
+  info[0] = it.ld; info[1] = it.pair_kq; info[2] = it.mat_off; info[3] = dpgo::spd_panel_doubles(it, len);
+  if (!panel) return 0;
+  if (!src || src_ld < count || cap < mat_off + info[3]) return -1;
+  dpgo::spd_pack_panel_host(it, dpgo::PanelSrc{0, src_ld, len}, src, panel);
+  return 0;
+}
+
 // ---- the group's hooks (group.h: debug_*; debug_inter.cpp, debug_cert.cpp) ----
 int dpgo_group_debug_apply(dpgo_group_t *h, int local, const char *op, const double *in, int ld_in, double *out,
                            int ld_out) {

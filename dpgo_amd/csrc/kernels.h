@@ -19,6 +19,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include "spd_panel.h"
 
 namespace dpgo {
 
@@ -428,8 +429,8 @@ struct alignas(16) SpdItem {
   int front, first, count, w;            // first row (forward) / pivot column (backward) of the tile, rows in it
   int u, ld, piv_ptr, upd_ptr;           // ld: doubles between consecutive rows of the tile's panel
   int pos_off, ubuf_off, node, pad0;    // node: local node the front belongs to (launch masks)
-  int64_t mat_off;                       // offset of the tile's panel
-  int pad1, pad2;
+  int64_t mat_off;                       // offset of the tile's panel (16-byte aligned)
+  int pair_kq, pad2;                     // layout of the panel (spd_panel.h): 0 plain, else paired for that many lanes per row
 };
 static_assert(sizeof(SpdItem) == 64 && offsetof(SpdItem, mat_off) == 48, "SpdItem is loaded as four int4");
 
@@ -442,6 +443,7 @@ struct SpdDev {
   const SpdItem *root_items = nullptr;   // the fused root tiles (k_spd_level MODE 2) and their panels
   const double *Wroot = nullptr;
   double *ubuf = nullptr;
+  int pairs = 0;                  // the panels of the 64- and 16-row classes are in the paired layout (spd_panel.h)
 };
 // One level of the forward / backward sweep.  The tiles of a level are stored node by node -- a node's wide tiles
 // (`rows` = 64 or 16 high, one workgroup each, longest first), then its narrow ones (one wave each) -- and a launch
@@ -460,7 +462,8 @@ struct SpdLevelMap {
 // vec is a record array: forward reads the right-hand side from vec and writes y to ytmp (n x d, the pivots
 // of a front consecutive); backward reads ytmp and writes scale * A^-1 b into vec (scale must be +1 or -1).
 // Panels of the solve tiles from a factor that is still on the device (front-major W / WT, spd_dev.hip): tile i copies
-// len rows of `count` entries, src_ld apart, starting at src + src_off, to panels + items[i].mat_off (rows items[i].ld apart).
+// len rows of `count` entries, src_ld apart, starting at src + src_off, to panels + items[i].mat_off (entry (k, r) at
+// spd_panel_index(items[i].pair_kq, items[i].ld, k, r): spd_panel.h).
 struct PanelSrc { long long src_off; int src_ld; int len; };
 void launch_pack_panels(hipStream_t st, const SpdItem *items, const PanelSrc *srcs, int ntiles, const double *src, double *panels);
 // measurement builds (-DSPD_TRACE) only: where the solve tiles write their phase timestamps (6 per tile); no-op otherwise

@@ -1853,22 +1853,41 @@ __device__ __forceinline__ void pull_updates(const SpdDev &S, int pos, double (&
   }
 }
 
-// The streaming dot products of one chunk: acc[c] += sum_k W[k][lane] f[k][c], k = kq, kq + KQ, ... < kn, the
-// panel rows ld doubles apart.  Two half-batches of HB loads alternate: the loads of the next half are issued
-// before the products of the current one, so a lane always has HB..2 HB loads in flight (a single batch that is
+// The streaming dot products of one chunk: acc[c] += sum_k W[k][r] f[k][c], k = kq, kq + KQ, ... < kn; `wp`: the chunk's
+// first panel row.  Two half-batches of HB entries alternate: the loads of the next half are issued
+// before the products of the current one, so a lane always has HB..2 HB entries in flight (a single batch that is
 // waited for as a whole drains to zero between batches).  `pre`: the first half-batch, issued by stream_first()
 // before the chunk's input vector was gathered.
-template <int D, int KQ, bool NT, int HB, typename PT>
-__device__ __forceinline__ bool stream_first(const PT *wp, int ld, int kq, int kn, double (&a)[HB]) {
-  const bool full = kq + (HB - 1) * KQ < kn;
-  if (full) {
+// PAIRS (spd_panel.h): a lane's entries k and k + KQ are neighbours in memory, HB / 2 loads of 16 bytes per half-batch
+// (buffer entries 2 q, 2 q + 1 = the load's halves: the same entries in the same registers as without, consumed in the
+// same ascending k).  A chunk starts at a multiple of 2 KQ, so its first group starts at wp as its first row does.
+template <typename PT> struct SpdPair { typedef PT type __attribute__((ext_vector_type(2))); };
+template <int KQ, bool NT, int HB, bool PAIRS, typename PT>
+__device__ __forceinline__ void stream_load(const PT *wp, int ld, int r, int kq, int k, double (&a)[HB]) {
+  if constexpr (PAIRS) {
+    static_assert(HB % 2 == 0, "a half-batch is whole pairs");
+    static_assert(8 % (2 * KQ) == 0, "a pair group must not straddle two chunks (spd_chunk: chunk starts are multiples of 8)");
+    typedef typename SpdPair<PT>::type P2;
 #pragma unroll
-    for (int q = 0; q < HB; q++) a[q] = LDW(wp + (size_t)(kq + q * KQ) * ld);
+    for (int q = 0; q < HB / 2; q++) {
+      const P2 *p = reinterpret_cast<const P2 *>(wp + (size_t)(k + kq + 2 * q * KQ) * ld + 2 * r);
+      const P2 v = NT ? __builtin_nontemporal_load(p) : *p;
+      a[2 * q] = (double)v.x;
+      a[2 * q + 1] = (double)v.y;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < HB; q++) a[q] = LDW(wp + (size_t)(k + q * KQ) * ld + r);
   }
+}
+template <int D, int KQ, bool NT, int HB, bool PAIRS, typename PT>
+__device__ __forceinline__ bool stream_first(const PT *wp, int ld, int r, int kq, int kn, double (&a)[HB]) {
+  const bool full = kq + (HB - 1) * KQ < kn;
+  if (full) stream_load<KQ, NT, HB, PAIRS, PT>(wp, ld, r, kq, kq, a);
   return full;
 }
-template <int D, int KQ, bool NT, int HB, typename PT>
-__device__ __forceinline__ void stream_rest(const PT *wp, int ld, int kq, int kn, const double *fw, bool have,
+template <int D, int KQ, bool NT, int HB, bool PAIRS, typename PT>
+__device__ __forceinline__ void stream_rest(const PT *wp, int ld, int r, int kq, int kn, const double *fw, bool have,
                                             double (&a)[HB], double (&acc)[D]) {
   double b[HB];
   int kk = kq;
@@ -1879,8 +1898,7 @@ __device__ __forceinline__ void stream_rest(const PT *wp, int ld, int kq, int kn
   _Pragma("unroll") for (int q = 0; q < HB; q++)                                            \
       _Pragma("unroll") for (int c = 0; c < D; c++) acc[c] = fma(buf[q], fw[((k0) + q * KQ) * D + c], acc[c]);
 #endif
-#define SPD_LOAD(buf, k0) \
-  _Pragma("unroll") for (int q = 0; q < HB; q++) buf[q] = LDW(wp + (size_t)((k0) + q * KQ) * ld);
+#define SPD_LOAD(buf, k0) stream_load<KQ, NT, HB, PAIRS, PT>(wp, ld, r, kq, k0, buf);
   while (have) {
     int k2 = kk + HB * KQ;
     bool more = k2 + (HB - 1) * KQ < kn;
@@ -1899,8 +1917,21 @@ __device__ __forceinline__ void stream_rest(const PT *wp, int ld, int kq, int kn
 #undef SPD_FMA
 #undef SPD_LOAD
   if (kk < kn) {   // the rest: one predicated half-batch (independent loads, never one at a time)
+    if constexpr (PAIRS) {
+      // a pair is loaded where its first entry exists (its second is then an entry or a zero of the panel's padding)
+      typedef typename SpdPair<PT>::type P2;
 #pragma unroll
-    for (int q = 0; q < HB; q++) b[q] = kk + q * KQ < kn ? LDW(wp + (size_t)(kk + q * KQ) * ld) : 0.0;
+      for (int q = 0; q < HB / 2; q++) {
+        const P2 *p = reinterpret_cast<const P2 *>(wp + (size_t)(kk + kq + 2 * q * KQ) * ld + 2 * r);
+        P2 v = {(PT)0, (PT)0};
+        if (kk + 2 * q * KQ < kn) v = NT ? __builtin_nontemporal_load(p) : *p;
+        b[2 * q] = (double)v.x;
+        b[2 * q + 1] = (double)v.y;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < HB; q++) b[q] = kk + q * KQ < kn ? LDW(wp + (size_t)(kk + q * KQ) * ld + r) : 0.0;
+    }
 #pragma unroll
     for (int q = 0; q < HB; q++)
       if (kk + q * KQ < kn) {
@@ -1923,7 +1954,7 @@ __device__ __forceinline__ int spd_chunk(int len) {
 // its forward step y = L11^-1 f is followed at once by its backward step x = L11^-T y: the tile streams rows of the
 // explicit product L11^-T L11^-1 (= the inverse of the root's Schur complement, S.Wroot) and writes scale * x straight
 // into `out` -- one launch instead of two, the same bytes (w^2 entries against two triangles).
-template <int D, int DOF, int NW, int SPD_CH, int ROWS, bool NT, bool ROOT = false, typename PT = double>
+template <int D, int DOF, int NW, int SPD_CH, int ROWS, bool NT, bool PAIRS, bool ROOT = false, typename PT = double>
 __device__ __forceinline__ void spd_fwd_tile(const SpdDev &S, const SpdItem &it, const double *vec, double *ytmp,
                                              double *fw, double *red, const int wv, const int lane,
                                              int trace_slot = 0, unsigned long long trace_t0 = 0, double *out = nullptr,
@@ -1937,7 +1968,7 @@ __device__ __forceinline__ void spd_fwd_tile(const SpdDev &S, const SpdItem &it,
   const int p = it.first + r;
   const bool valid = r < it.count;
   const int w = it.w;
-  const PT *WT = reinterpret_cast<const PT *>(ROOT ? S.Wroot : S.WT) + it.mat_off + r;   // the tile's panel: [k][r], rows ldm apart
+  const PT *WT = reinterpret_cast<const PT *>(ROOT ? S.Wroot : S.WT) + it.mat_off;   // the tile's panel: entry (k, r) at spd_panel_index (plain: [k][r], rows ldm apart)
   const int ldm = it.ld;
   const int *piv = S.piv_idx + it.piv_ptr;
   const int pos0 = it.pos_off;
@@ -1959,7 +1990,7 @@ __device__ __forceinline__ void spd_fwd_tile(const SpdDev &S, const SpdItem &it,
     const PT *wp = WT + (size_t)k0 * ldm;
     double w0[HB];
     bool have0 = false;
-    if (PRE && valid) have0 = stream_first<D, KQ, NT, HB, PT>(wp, ldm, kq, kn, w0);
+    if (PRE && valid) have0 = stream_first<D, KQ, NT, HB, PAIRS, PT>(wp, ldm, r, kq, kn, w0);
     for (int kk = lane; kk < kn; kk += 64) {
       const int k = k0 + kk;
       double v[D];
@@ -1980,8 +2011,8 @@ __device__ __forceinline__ void spd_fwd_tile(const SpdDev &S, const SpdItem &it,
     if (tr[2] == 0) SPD_T(2)
 #endif
     if (valid) {
-      if (!PRE) have0 = stream_first<D, KQ, NT, HB, PT>(wp, ldm, kq, kn, w0);
-      stream_rest<D, KQ, NT, HB, PT>(wp, ldm, kq, kn, fw, have0, w0, acc);
+      if (!PRE) have0 = stream_first<D, KQ, NT, HB, PAIRS, PT>(wp, ldm, r, kq, kn, w0);
+      stream_rest<D, KQ, NT, HB, PAIRS, PT>(wp, ldm, r, kq, kn, fw, have0, w0, acc);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -2036,7 +2067,7 @@ __device__ __forceinline__ void spd_fwd_tile(const SpdDev &S, const SpdItem &it,
   SPD_TRACE_FLUSH(wv == 0 && lane == 0)
 }
 
-template <int D, int DOF, int NW, int SPD_CH, int ROWS, bool NT, typename PT = double>
+template <int D, int DOF, int NW, int SPD_CH, int ROWS, bool NT, bool PAIRS, typename PT = double>
 __device__ __forceinline__ void spd_bwd_tile(const SpdDev &S, const SpdItem &it, double scale, const double *ytmp,
                                              double *vec, double *fw, double *red, const int wv, const int lane,
                                              int trace_slot = 0, unsigned long long trace_t0 = 0) {
@@ -2048,7 +2079,7 @@ __device__ __forceinline__ void spd_bwd_tile(const SpdDev &S, const SpdItem &it,
   const int k = it.first + r;
   const bool valid = r < it.count;
   const int w = it.w, m = w + it.u;
-  const PT *W = reinterpret_cast<const PT *>(S.W) + it.mat_off + r;     // the tile's panel: [p - first][r], rows ldw apart
+  const PT *W = reinterpret_cast<const PT *>(S.W) + it.mat_off;     // the tile's panel: entry (p - first, r) at spd_panel_index (plain: [p - first][r], rows ldw apart)
   const int ldw = it.ld;
   const int *piv = S.piv_idx + it.piv_ptr;
   const int *upd = S.upd_idx + it.upd_ptr;
@@ -2062,7 +2093,7 @@ __device__ __forceinline__ void spd_bwd_tile(const SpdDev &S, const SpdItem &it,
     const PT *wp = W + (size_t)(p0 - it.first) * ldw;
     double w0[HB];
     bool have0 = false;
-    if (PRE && valid) have0 = stream_first<D, KQ, NT, HB, PT>(wp, ldw, kq, pn, w0);
+    if (PRE && valid) have0 = stream_first<D, KQ, NT, HB, PAIRS, PT>(wp, ldw, r, kq, pn, w0);
     for (int pp = lane; pp < pn; pp += 64) {
       const int p = p0 + pp;
       // ancestors' entries were scaled when they were written: undo by linearity (scale is +-1)
@@ -2081,8 +2112,8 @@ __device__ __forceinline__ void spd_bwd_tile(const SpdDev &S, const SpdItem &it,
     if (tr[2] == 0) SPD_T(2)
 #endif
     if (valid) {
-      if (!PRE) have0 = stream_first<D, KQ, NT, HB, PT>(wp, ldw, kq, pn, w0);
-      stream_rest<D, KQ, NT, HB, PT>(wp, ldw, kq, pn, fw, have0, w0, acc);
+      if (!PRE) have0 = stream_first<D, KQ, NT, HB, PAIRS, PT>(wp, ldw, r, kq, pn, w0);
+      stream_rest<D, KQ, NT, HB, PAIRS, PT>(wp, ldw, r, kq, pn, fw, have0, w0, acc);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -2122,7 +2153,8 @@ __device__ __forceinline__ void spd_bwd_tile(const SpdDev &S, const SpdItem &it,
 // One level of a sweep in one launch.  A workgroup (8 waves) takes a PACK: either one tile of a wide front,
 // shared by the 8 waves (ROWS-row tiles), or up to 8 tiles of narrow fronts (reduction length <= 96), one
 // per wave.  Wide packs come first, longest first; the narrow ones fill the tail of the launch.
-template <int D, int DOF, int ROWS, int MODE, bool NT, typename PT = double>   // MODE 0: forward level, 1: backward level, 2: the roots (fused); PT: panel storage
+// PAIRS: the panels are in the paired layout (spd_panel.h), for the wide tiles' class and the narrow tiles alike
+template <int D, int DOF, int ROWS, int MODE, bool NT, bool PAIRS, typename PT = double>   // MODE 0: forward level, 1: backward level, 2: the roots (fused); PT: panel storage
 __global__ __launch_bounds__(64 * SPD_NW(ROWS), ROWS == 64 ? SPD_WPE : 4) void k_spd_level(SpdDev S, NodeMask mask, SpdLevelMap M,
                                                                                       double scale, double *vec, double *ytmp) {
   constexpr int CH = 128, NW = SPD_NW(ROWS);
@@ -2149,15 +2181,15 @@ __global__ __launch_bounds__(64 * SPD_NW(ROWS), ROWS == 64 ? SPD_WPE : 4) void k
   if (!is_wide) {
     const int t = M.nstart[j] + r * NW + wv;
     const SpdItem it = load_item(items + t);
-    if constexpr (MODE == 0) spd_fwd_tile<D, DOF, 1, CH, 64, NT, false, PT>(S, it, vec, ytmp, f[wv], red, 0, lane SPD_TRACE_ARGS(t));
-    else if constexpr (MODE == 1) spd_bwd_tile<D, DOF, 1, CH, 64, NT, PT>(S, it, scale, ytmp, vec, f[wv], red, 0, lane SPD_TRACE_ARGS(t));
-    else spd_fwd_tile<D, DOF, 1, CH, 64, NT, true, PT>(S, it, vec, nullptr, f[wv], red, 0, lane SPD_TRACE_ARGS(t), ytmp, scale);
+    if constexpr (MODE == 0) spd_fwd_tile<D, DOF, 1, CH, 64, NT, PAIRS, false, PT>(S, it, vec, ytmp, f[wv], red, 0, lane SPD_TRACE_ARGS(t));
+    else if constexpr (MODE == 1) spd_bwd_tile<D, DOF, 1, CH, 64, NT, PAIRS, PT>(S, it, scale, ytmp, vec, f[wv], red, 0, lane SPD_TRACE_ARGS(t));
+    else spd_fwd_tile<D, DOF, 1, CH, 64, NT, PAIRS, true, PT>(S, it, vec, nullptr, f[wv], red, 0, lane SPD_TRACE_ARGS(t), ytmp, scale);
   } else {
     const int t = M.wstart[j] + r;
     const SpdItem it = load_item(items + t);
-    if constexpr (MODE == 0) spd_fwd_tile<D, DOF, NW, CH, ROWS, NT, false, PT>(S, it, vec, ytmp, f[wv], red, wv, lane SPD_TRACE_ARGS(t));
-    else if constexpr (MODE == 1) spd_bwd_tile<D, DOF, NW, CH, ROWS, NT, PT>(S, it, scale, ytmp, vec, f[wv], red, wv, lane SPD_TRACE_ARGS(t));
-    else spd_fwd_tile<D, DOF, NW, CH, ROWS, NT, true, PT>(S, it, vec, nullptr, f[wv], red, wv, lane SPD_TRACE_ARGS(t), ytmp, scale);
+    if constexpr (MODE == 0) spd_fwd_tile<D, DOF, NW, CH, ROWS, NT, PAIRS, false, PT>(S, it, vec, ytmp, f[wv], red, wv, lane SPD_TRACE_ARGS(t));
+    else if constexpr (MODE == 1) spd_bwd_tile<D, DOF, NW, CH, ROWS, NT, PAIRS, PT>(S, it, scale, ytmp, vec, f[wv], red, wv, lane SPD_TRACE_ARGS(t));
+    else spd_fwd_tile<D, DOF, NW, CH, ROWS, NT, PAIRS, true, PT>(S, it, vec, nullptr, f[wv], red, wv, lane SPD_TRACE_ARGS(t), ytmp, scale);
   }
 #undef SPD_TRACE_ARGS
 }
@@ -2989,7 +3021,7 @@ __global__ __launch_bounds__(256) void k_pack_panels(const SpdItem *items, const
   const int cnt = it.count, total = ps.len * cnt;
   for (int i = threadIdx.x; i < total; i += 256) {
     const int k = i / cnt, r = i - k * cnt;
-    out[(size_t)k * it.ld + r] = in[(size_t)k * ps.src_ld + r];
+    out[spd_panel_index(it.pair_kq, it.ld, k, r)] = in[(size_t)k * ps.src_ld + r];
   }
 }
 // The dense product behind the fused root tiles: P = L11^-T L11^-1, P[k][c] = sum_{j >= max(k, c)} Linv[j][k] Linv[j][c],
@@ -3083,24 +3115,29 @@ void launch_spd_level(int d, int dof, hipStream_t st, const SpdDev &S, int mode,
   const int npacks = M.wide_wgs + M.narrow_wgs;
   if (npacks == 0 || M.nlive == 0) return;
   ProfScope ps(mode == 1 ? PK_SPD_BWD : PK_SPD_FWD, st, level_bytes);
-#define SPD_LAUNCH3(DOFV, ROWSV, NTV, PTV)                                                                       \
+#define SPD_LAUNCH3(DOFV, ROWSV, NTV, PRV, PTV)                                                                      \
   do {                                                                                                         \
     if (mode == 0)                                                                                             \
-      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 0, NTV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp);  \
+      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 0, NTV, PRV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp);  \
     else if (mode == 1)                                                                                        \
-      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 1, NTV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp); \
+      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 1, NTV, PRV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp); \
     else                                                                                                       \
-      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 2, NTV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp); \
+      hipLaunchKernelGGL((k_spd_level<D, DOFV, ROWSV, 2, NTV, PRV, PTV>), dim3(npacks), dim3(64 * SPD_NW(ROWSV)), 0, st, S, mask, M, scale, vec, ytmp); \
   } while (0)
-#define SPD_LAUNCH2(DOFV, ROWSV, NTV) SPD_LAUNCH3(DOFV, ROWSV, NTV, double)
+#define SPD_LAUNCH2(DOFV, ROWSV, NTV)                      \
+  do {                                                     \
+    if (S.pairs) SPD_LAUNCH3(DOFV, ROWSV, NTV, true, double); \
+    else SPD_LAUNCH3(DOFV, ROWSV, NTV, false, double);     \
+  } while (0)
 #define SPD_LAUNCH(DOFV, ROWSV)                \
   do {                                         \
     if (stream_once) SPD_LAUNCH2(DOFV, ROWSV, true); \
     else SPD_LAUNCH2(DOFV, ROWSV, false);      \
   } while (0)
-/* 8-row tiles exist for the fused roots only (a single root front per GPU: twice the workgroups on it), fp64 panels */
+/* 8-row tiles exist for the fused roots only (a single root front per GPU: twice the workgroups on it), fp64 panels in the
+   plain layout (a pair group of 16 entries would straddle the chunks of the reduction) */
 #define SPD_ROOT8(DOFV, NTV) \
-  hipLaunchKernelGGL((k_spd_level<D, DOFV, 8, 2, NTV, double>), dim3(npacks), dim3(64 * SPD_NW(8)), 0, st, S, mask, M, scale, vec, ytmp)
+  hipLaunchKernelGGL((k_spd_level<D, DOFV, 8, 2, NTV, false, double>), dim3(npacks), dim3(64 * SPD_NW(8)), 0, st, S, mask, M, scale, vec, ytmp)
 #define SPD_PICK(DOFV)                  \
   do {                                  \
     if (rows == 8) {                    \

@@ -27,6 +27,7 @@ Settings read() {
   get("DPGO_SPD_FINE_ROOT", s.spd_fine_root);
   get("DPGO_SPD_FINE_ROOT8", s.spd_fine_root8);
   get("DPGO_SPD_KEEP_MB", s.spd_keep_mb);
+  get("DPGO_SPD_PANEL_PAIRS", s.spd_panel_pairs);
   get("DPGO_SPD_LEAF_RR", s.spd_leaf_rr);
   get("DPGO_SPD_COLLAPSE_RR", s.spd_collapse_rr);
   get("DPGO_SPD_LEAF_TT", s.spd_leaf_tt);

@@ -30,7 +30,8 @@ struct Settings {
   int spd_fine_root = 192;                // DPGO_SPD_FINE_ROOT (192): fused roots below this many 64-row tiles take 16-row tiles
   int spd_fine_root8 = 64;                // DPGO_SPD_FINE_ROOT8 (64): ... and below this many, 8-row tiles
   long long spd_keep_mb = 200;            // DPGO_SPD_KEEP_MB (200): panels up to this many MiB stay in the Infinity Cache between solves
-  int spd_leaf_rr = 96;                   // DPGO_SPD_LEAF_RR (96): leaf size of the nested dissection of G_RR + lambda I
+  bool spd_panel_pairs = true;            // DPGO_SPD_PANEL_PAIRS (1): panels of the 64- and 16-row tiles paired for 16-byte loads (spd_panel.h); 0: plain
+  int spd_leaf_rr = 96;                  // DPGO_SPD_LEAF_RR (96): leaf size of the nested dissection of G_RR + lambda I
   int spd_collapse_rr = 0;                // DPGO_SPD_COLLAPSE_RR (0): merged tree levels of G_RR; 0: by the solve's cost model
   std::optional<int> spd_leaf_tt;         // DPGO_SPD_LEAF_TT (128; 64 for a Dynamic group): leaf size of G_tt
   std::optional<int> spd_collapse_tt;     // DPGO_SPD_COLLAPSE_TT (0 = cost model; 1 for a Dynamic group): merged tree levels of G_tt

@@ -78,16 +78,29 @@ struct SpdSolverDev::Plan {
 
 namespace {
 // The descriptor of a tile of front f: rows (forward, roots) / pivot columns (backward) first .. first + count; its panel
-// starts at mat_off, rows ld doubles apart
-SpdItem spd_item(const SpdFactor &F, int f, int first, int count, int ld, int64_t mat_off, int node) {
+// starts at mat_off, rows ld doubles apart, entries where spd_panel_index(pair_kq, ...) puts them (spd_panel.h)
+SpdItem spd_item(const SpdFactor &F, int f, int first, int count, int ld, int64_t mat_off, int node, int pair_kq = 0) {
   SpdItem it{};
   it.front = f; it.first = first; it.count = count; it.w = F.w[f];
   it.u = F.u[f]; it.ld = ld; it.piv_ptr = F.piv_ptr[f]; it.upd_ptr = F.upd_ptr[f];
   it.pos_off = F.pos_off[f]; it.ubuf_off = F.ubuf_off[f];
-  it.node = node; it.mat_off = mat_off;
+  it.node = node; it.mat_off = mat_off; it.pair_kq = pair_kq;
   return it;
 }
 }  // namespace
+
+SpdItem spd_panel_item(int rows, int count, bool pairs, int64_t mat_off) {
+  SpdItem it{};
+  it.count = count; it.ld = spd_panel_ld(rows, count); it.pair_kq = spd_pair_kq(pairs, rows); it.mat_off = mat_off;
+  return it;
+}
+int64_t spd_panel_doubles(const SpdItem &it, int64_t len) { return spd_panel_len(it.pair_kq, len) * it.ld; }
+void spd_pack_panel_host(const SpdItem &it, const PanelSrc &ps, const double *factor, double *panels) {
+  const double *src = factor + ps.src_off;
+  double *dst = panels + it.mat_off;
+  for (int64_t k = 0; k < ps.len; k++)
+    for (int r = 0; r < it.count; r++) dst[spd_panel_index(it.pair_kq, it.ld, k, r)] = src[(size_t)k * ps.src_ld + r];
+}
 
 SpdSolverDev::SpdSolverDev() : plan_(new Plan) {}
 SpdSolverDev::~SpdSolverDev() { spd_release_device(F); spd_release_numeric(F); }
@@ -122,6 +135,8 @@ const double *SpdSolverDev::Plan::stage_roots(const SpdFactor &F, const std::vec
 //   backward tile (pivot columns k0 .. k0+count, rows p >= k0):              panel[p - k0][r] = W_s[p][k0 + r]
 // (rows of a panel are ld = count rounded up to 16 doubles apart).  The zero triangle of L11^-1 is simply not
 // stored, a wave's consecutive loads are consecutive in memory, and every tile is a pure sequential stream.
+// With DPGO_SPD_PANEL_PAIRS (the default) the panels of the 64- and 16-row classes hold the two entries a lane consumes
+// one after the other side by side (spd_panel.h: panel[k][r] above is entry (k, r) of that map): 16-byte loads.
 // Within a launch the tiles are ordered by decreasing length, so the long ones start first and the short
 // ones fill the tail.
 void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_unknown) {
@@ -193,7 +208,8 @@ void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_un
   int nnodes = 1;
   for (int a : node_of_unknown) nnodes = std::max(nnodes, a + 1);
   auto node_of_front = [&](int f) { return node_of_unknown[F.piv_idx[F.piv_ptr[f]]]; };   // a front never spans two nodes (they are disconnected)
-  struct Tile { int f, first, count; int64_t len; };   // len: panel rows
+  struct Tile { int f, first, count; int64_t len; int rows; };   // len: panel rows; rows: tile height of its class (64: also the narrow tiles)
+  P.dev.pairs = s.spd_panel_pairs ? 1 : 0;
   auto sweep = [&](bool fwd, std::vector<Plan::Level> &out_levels, DevBuf<SpdItem> &items_dev, DevBuf<double> &panels_dev) {
     const auto &levels = fwd ? F.by_height : F.by_depth;
     std::vector<Tile> tiles;
@@ -230,7 +246,7 @@ void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_un
               const int cnt = std::min(th, ext - r);
               // forward: columns k < kend of rows r..; backward: rows p >= r of columns r..
               const int64_t len = fwd ? ((r + th <= w) ? r + th : w) : (m - r);
-              tiles.push_back({f, r, cnt, len});
+              tiles.push_back({f, r, cnt, len, th});
             }
           }
           std::stable_sort(tiles.begin() + begin, tiles.end(), [](const Tile &x, const Tile &y) { return x.len * x.count > y.len * y.count; });
@@ -246,17 +262,18 @@ void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_un
     int64_t total = 0;
     for (size_t i = 0; i < tiles.size(); i++) {
       const Tile &t = tiles[i];
-      const int ld = (t.count + 15) / 16 * 16;
-      items[i] = spd_item(F, t.f, t.first, t.count, ld, total, node_of_front(t.f));
+      const SpdItem lay = spd_panel_item(t.rows, t.count, P.dev.pairs != 0, total);
+      items[i] = spd_item(F, t.f, t.first, t.count, lay.ld, total, node_of_front(t.f), lay.pair_kq);
       if (fwd) srcs[i] = PanelSrc{(long long)(F.wt_off[t.f] + t.first), F.ldm[t.f], (int)t.len};
       else srcs[i] = PanelSrc{(long long)(F.w_off[t.f] + (int64_t)t.first * F.ldw[t.f] + t.first), F.ldw[t.f], (int)t.len};
-      total += t.len * ld;
+      total += spd_panel_doubles(items[i], t.len);
     }
     if (s.spd_dump) {
-      int64_t used = 0;
-      for (const Tile &t : tiles) used += t.len * t.count;
-      fprintf(stderr, "[spd] dof %d %s panels: %.1f MB stored, %.1f MB of entries (padding %.1f %%), %zu tiles\n", dof, fwd ? "fwd" : "bwd",
-              total * 8e-6, used * 8e-6, 100.0 * (total - used) / std::max<int64_t>(used, 1), tiles.size());
+      int64_t used = 0, plain = 0;
+      for (const Tile &t : tiles) { used += t.len * t.count; plain += t.len * ((t.count + 15) / 16 * 16); }
+      fprintf(stderr, "[spd] dof %d %s panels: %.1f MB stored, %.1f MB of entries (padding %.1f %%, of it %.2f %% whole pad rows of the paired layout), %zu tiles\n",
+              dof, fwd ? "fwd" : "bwd", total * 8e-6, used * 8e-6, 100.0 * (total - used) / std::max<int64_t>(used, 1),
+              100.0 * (total - plain) / std::max<int64_t>(used, 1), tiles.size());
     }
     items_dev.upload(items);
     if (F.dev_W && F.dev_WT) {
@@ -272,13 +289,7 @@ void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_un
     std::vector<double> panels((size_t)std::max<int64_t>(total, 1), 0.0);
     const double *factor = fwd ? F.WT.data() : F.W.data();
 #pragma omp parallel for schedule(dynamic, 16)
-    for (size_t i = 0; i < tiles.size(); i++) {
-      const SpdItem &it = items[i];
-      const double *src = factor + srcs[i].src_off;
-      double *dst = panels.data() + it.mat_off;
-      for (int64_t k = 0; k < srcs[i].len; k++)
-        for (int r = 0; r < it.count; r++) dst[k * it.ld + r] = src[(size_t)k * srcs[i].src_ld + r];
-    }
+    for (size_t i = 0; i < tiles.size(); i++) spd_pack_panel_host(items[i], srcs[i], factor, panels.data());
     panels_dev.upload(panels);
   };
   sweep(true, P.fwd_levels, P.fwd_items, P.WT);
@@ -294,10 +305,11 @@ void SpdSolverDev::upload(int dof, int dcols, const std::vector<int> &node_of_un
       for (int f : roots) {
         if (node_of_front(f) != a) continue;
         for (int r = 0; r < F.w[f]; r += rows) {
-          const int count = std::min(rows, F.w[f] - r), ld = rows == 8 ? 8 : (count + 15) / 16 * 16;   // (8-row tiles: a wave's load spans 8 consecutive 64-byte rows)
-          items.push_back(spd_item(F, f, r, count, ld, total, a));
+          const int count = std::min(rows, F.w[f] - r);
+          const SpdItem lay = spd_panel_item(rows, count, P.dev.pairs != 0, total);   // (8-row tiles: plain)
+          items.push_back(spd_item(F, f, r, count, lay.ld, total, a, lay.pair_kq));
           srcs.push_back(PanelSrc{(long long)(p_off[f] + r), F.w[f], F.w[f]});   // columns r.. of the dense w x w product
-          total += (int64_t)F.w[f] * ld;
+          total += spd_panel_doubles(items.back(), F.w[f]);
         }
         lev.node_bytes[a] += 8.0 * (double)F.w[f] * F.w[f] + 2.0 * 8.0 * dcols * F.w[f];
       }

@@ -20,6 +20,13 @@ void spd_profile(int d, hipStream_t st, SpdSolverDev &S, double *vec);
 // a warning on stderr when F's pivots span so many orders of magnitude that its solves lose digits
 void warn_conditioning(const char *what, const SpdFactor &F);
 
+// The descriptor's layout fields (ld, pair_kq, mat_off) of a tile with `count` rows in the class of `rows`-high tiles, as
+// upload() sets them; the doubles its panel of `len` entries per row takes; and upload()'s host packer for one tile (what
+// k_pack_panels does on the device): the entries of `factor` that `ps` names, to panels + it.mat_off
+SpdItem spd_panel_item(int rows, int count, bool pairs, int64_t mat_off);
+int64_t spd_panel_doubles(const SpdItem &it, int64_t len);
+void spd_pack_panel_host(const SpdItem &it, const PanelSrc &ps, const double *factor, double *panels);
+
 // What upload() decided, for the tests to read back (dpgo_debug_spd_solver_plan): a launch's tile class and counts
 struct SpdPlanInfo {
   struct Level { int rows = 0, nwide = 0, nnarrow = 0; std::vector<int> wcount, ncount; };   // (wcount / ncount: per local node)

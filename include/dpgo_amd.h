@@ -1012,6 +1012,13 @@ int dpgo_debug_spd_solver_run(dpgo_spd_solver_debug_t *h, unsigned long long mas
                               const unsigned long long *class_of, double scale, int in_place, const double *in, double *out);
 int dpgo_debug_spd_solver_refactor(dpgo_spd_solver_debug_t *h, const double *val);
 void dpgo_debug_spd_solver_free(dpgo_spd_solver_debug_t *h);
+/* Host: one solve tile's panel as SpdSolverDev::upload's host packer lays it out.  The tile has `count` rows in the class of
+ * `rows`-high tiles (64, 16 or 8: 1, 4 or 8 lanes per row) and `len` entries per row; entry (k, r) is src[k * src_ld + r];
+ * pairs: what DPGO_SPD_PANEL_PAIRS would be.  info[4] = the descriptor's ld, its pair_kq (0: plain layout, else lanes per
+ * row of the paired one), its mat_off (the one given), doubles of the panel.  panel (may be NULL to query info): at least
+ * mat_off + info[3] doubles; the packer writes the entries and nothing else.  Returns 0, -1 on a bad argument. */
+int dpgo_debug_spd_panel_pack(int rows, int count, int len, int pairs, long long mat_off, const double *src, int src_ld,
+                              double *panel, long long cap, long long *info);
 /* Host: the neighbour-to-neighbour exchange plan of `rank` (what dpgo_comm_exchange uses with more than one rank) from
  * every rank's exported and needed (node, pose) keys (dpgo_graph_exchange_plan of its nodes): per peer 5 ints (rank,
  * send_off, send_cnt, recv_off, recv_cnt), the send and receive keys (node, pose interleaved, concatenated over the peers
