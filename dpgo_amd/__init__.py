@@ -223,6 +223,12 @@ SYMBOLS = {
     "dpgo_group_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _DP, C.c_int, C.c_int, _DP, _DP,
                                          C.c_void_p]),
     "dpgo_debug_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP]),
+    "dpgo_group_edge_reliability": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, C.c_int, _IP, C.c_int, _DP,
+                                              _DP, _DP, C.c_void_p]),
+    "dpgo_graph_edge_reliability_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong,
+                                                         C.c_int, _IP, C.c_int, _DP, _DP, _DP, C.c_void_p, C.c_void_p]),
+    "dpgo_debug_rely_edge_host": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_rely_edge": (C.c_int, [C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP]),
     "dpgo_debug_spd_msolve": (C.c_int, [C.c_int, _IP, _IP, _DP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _DP, C.c_int,
                                         C.c_int, _DP, _IP, _DP]),
     "dpgo_debug_spd_solver_create": (C.c_int, [C.c_int, _IP, _IP, _DP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _IP, C.c_int,
@@ -1257,6 +1263,28 @@ class NodeGroup:
                                "not the group's, an anchor outside the graph, an upstream entry that is not finite, or bad sizes)")
         return (r, sens, adj) if want_adjoint else (r, sens)
 
+    def edge_reliability(self, X, edges=None, anchor=0, method=0, max_bytes=0, graph=None):
+        """Per-edge reliability at X (dpgo_group_edge_reliability): for every edge of `graph` (default: the group's own, which
+        numbers the edges), or for the listed indices -- any order, repeats allowed -- the leave-one-out chi-square d2_loo =
+        r' C^-1 r on the residual covariance C = Omega^-1 - Sigma_rel, the residual r_loo the edge would have at the solution
+        of the graph without it, the influence of removing it, the redundancy numbers and d2_own = r' Omega r, from the blocks
+        the selected inversion leaves on the device (method RELY_SELINV), from `pair_covariance`'s block solves (RELY_SOLVE),
+        or from whichever is not refused (RELY_AUTO, the default).  X should be a critical point (`polish`).  Returns a dict:
+        records (n, 6 + 2 dof) as the C ABI lays them out; its columns d2_loo, flag (int: 0, 1 = C not positive definite and
+        d2_loo, influence, r_loo zero, 2 = an edge without weight, all zero), redundancy, redundancy_trans, d2_own, influence,
+        residual (n, dof), r_loo (n, dof); rel (n, dof, dof); joint (n, 3, dof, dof) as `pair_covariance`; result (RelyResult).
+        outcome RELY_OK, RELY_NOT_PD (zero outputs) or RELY_SKIPPED (zero outputs, both byte predictions filled).  No threshold
+        is applied.  Trivial-loss groups that host every node."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        records, rel, joint, edge_args = _rely_arg(g_, edges)
+        r = RelyResult()
+        if lib().dpgo_group_edge_reliability(self._h, g_._h, _dp(X), ld, int(anchor), int(max_bytes), int(method), *edge_args,
+                                             _dp(records), _dp(rel), _dp(joint), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_edge_reliability failed (robust loss, a group that does not host every node, a graph that "
+                               "is not the group's, an anchor or an edge index outside the graph, an unknown method, or bad sizes)")
+        return rely_output(g_.d, records, rel, joint, r)
+
     def polish(self, X, anchor=0, max_bytes=0, **opts):
         """Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored
         tangent-space Hessian of `covariance`, factored and solved on the device -- until the tangent gradient is at rounding
@@ -2155,6 +2183,63 @@ class SensResult(C.Structure):
                 ("factor_ms", C.c_double), ("solve_ms", C.c_double), ("edge_ms", C.c_double)]
 
 
+RELY_OK, RELY_NOT_PD, RELY_SKIPPED = 0, 1, 2
+RELY_AUTO, RELY_SELINV, RELY_SOLVE = 0, 1, 2
+RELY_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+RELY_METHOD_NAMES = {0: "AUTO", 1: "SELINV", 2: "SOLVE"}
+
+
+class RelyResult(C.Structure):
+    """dpgo_rely_result_t: the outcome of NodeGroup.edge_reliability, the method it ran, the sizes of its factorisation, how many
+    edges were listed, flagged (C not positive definite) and unweighted, the sum of the redundancies in list order, the bytes
+    either method would allocate, and the host milliseconds of its three phases."""
+    _fields_ = [("outcome", C.c_int), ("method_used", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int),
+                ("max_front", C.c_int), ("edges", C.c_int), ("flagged", C.c_int), ("unweighted", C.c_int), ("columns", C.c_int),
+                ("batches", C.c_int), ("reserved", C.c_int), ("device_bytes", C.c_longlong), ("device_bytes_selinv", C.c_longlong),
+                ("device_bytes_solve", C.c_longlong), ("redundancy_sum", C.c_double), ("pivot_min", C.c_double),
+                ("pivot_max", C.c_double), ("stationarity", C.c_double), ("symbolic_s", C.c_double), ("factor_ms", C.c_double),
+                ("inverse_ms", C.c_double), ("edge_ms", C.c_double)]
+
+
+def _rely_arg(graph, edges):
+    """The arrays of an edge_reliability call: (records, rel, joint, (edges pointer or None, count))."""
+    dof = _dof(graph.d)
+    if edges is None:
+        n, args = graph.num_edges, (None, 0)
+    else:
+        E = np.ascontiguousarray(np.asarray(edges).reshape(-1), np.int32)
+        n, args = len(E), (_ip(E), len(E))   # (the pointer keeps E alive)
+    return np.zeros((n, 6 + 2 * dof)), np.zeros((n, dof, dof)), np.zeros((n, 3, dof, dof)), args
+
+
+def rely_output(d, records, rel, joint, result):
+    dof = _dof(d)
+    return dict(records=records, d2_loo=records[:, 0], flag=records[:, 1].astype(np.int64), redundancy=records[:, 2],
+                redundancy_trans=records[:, 3], d2_own=records[:, 4], influence=records[:, 5], residual=records[:, 6:6 + dof],
+                r_loo=records[:, 6 + dof:], rel=rel, joint=joint, result=result)
+
+
+def rely_edge_debug(d, rel, r, kappa, tau, device=None):
+    """The record arithmetic of NodeGroup.edge_reliability on given arrays (test hooks): rel (n, dof, dof), r (n, dof), kappa, tau
+    (n).  device None: on the host (dpgo_debug_rely_edge_host; no GPU); an int: k_rely_edge alone on that HIP device
+    (dpgo_debug_rely_edge).  Returns records (n, 6 + 2 dof)."""
+    dof = _dof(d)
+    rel = np.ascontiguousarray(rel, np.float64).reshape(-1, dof, dof)
+    n = rel.shape[0]
+    r = np.ascontiguousarray(r, np.float64).reshape(-1, dof)
+    kappa, tau = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,))) for v in (kappa, tau))
+    if d not in (2, 3) or r.shape[0] != n:
+        raise ValueError("rely_edge_debug: bad sizes")
+    rec = np.zeros((n, 6 + 2 * dof))
+    if device is None:
+        rc = lib().dpgo_debug_rely_edge_host(int(d), n, _dp(rel), _dp(r), _dp(kappa), _dp(tau), _dp(rec))
+    else:
+        rc = lib().dpgo_debug_rely_edge(int(device), int(d), n, _dp(rel), _dp(r), _dp(kappa), _dp(tau), _dp(rec))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_rely_edge failed")
+    return rec
+
+
 def sens_edge_debug(graph, X, lam):
     """Debug, no GPU: the per-edge arithmetic of the sensitivities' kernel on the host (dpgo_debug_sens_edge_host) for one
     adjoint `lam` (dof N by global pose, used as given).  Returns (sens, phi): (num_edges, 2 + dof) in NodeGroup.sensitivity's
@@ -2589,5 +2674,22 @@ def pair_covariance_reweighted(graph, X, loss, pairs, loss_reg=0.25, anchor=0, c
         raise RuntimeError("dpgo_graph_pair_covariance_reweighted failed (no HIP device, a short X, a bad loss, a pose outside the "
                            "graph, or a candidate weight that is not positive)")
     out = pairs_output(joint, rel, gate, r, gated, threshold)
+    out["summary"] = s
+    return out
+
+
+def edge_reliability_reweighted(graph, X, loss, loss_reg=0.25, edges=None, anchor=0, method=0, max_bytes=0, device=0):
+    """NodeGroup.edge_reliability for the RE-WEIGHTED problem at X (dpgo_graph_edge_reliability_reweighted), by
+    covariance_reweighted's recipe and with its caveat: the records describe the MM surrogate, not the robust objective.  Returns
+    edge_reliability's dict with summary (EdgeSummary) added."""
+    X, ld = _fcol(X)
+    records, rel, joint, edge_args = _rely_arg(graph, edges)
+    r, s = RelyResult(), EdgeSummary()
+    if lib().dpgo_graph_edge_reliability_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), int(anchor),
+                                                    int(max_bytes), int(method), *edge_args, _dp(records), _dp(rel), _dp(joint),
+                                                    C.byref(r), C.byref(s)) != 0:
+        raise RuntimeError("dpgo_graph_edge_reliability_reweighted failed (no HIP device, a short X, a bad loss, an edge index "
+                           "outside the graph, or an unknown method)")
+    out = rely_output(graph.d, records, rel, joint, r)
     out["summary"] = s
     return out

@@ -847,9 +847,9 @@ int dpgo_graph_scale_edges(const dpgo_graph_t *g, const double *w, dpgo_graph_t 
 }
 
 // The re-weighted problem at X: the loss weights w_e(X) of every edge (and their summary), the graph with kappa_e, tau_e
-// scaled by them, a trivial-loss group of all its nodes.  `call` runs on that group; everything is freed again.  0 / -1
+// scaled by them, a trivial-loss group of all its nodes.  `call` runs on that group and that graph; everything is freed again.  0 / -1
 static int with_reweighted_group(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
-                                 dpgo_edge_summary_t *edge_summary, const std::function<int(dpgo_group_t *)> &call) {
+                                 dpgo_edge_summary_t *edge_summary, const std::function<int(dpgo_group_t *, const dpgo_graph_t *)> &call) {
   const int m = (int)g->g.all.size(), nn = g->g.num_nodes;
   std::vector<double> w((size_t)std::max(m, 1));
   dpgo_edge_eval_t *ev = nullptr;
@@ -867,7 +867,7 @@ static int with_reweighted_group(const dpgo_graph_t *g, int device, const double
     std::iota(ids.begin(), ids.end(), 0);
     rc = dpgo_group_create(gw, ids.data(), nn, &opt, device, &grp);
   }
-  if (rc == 0) rc = call(grp);
+  if (rc == 0) rc = call(grp, gw);
   dpgo_group_free(grp);
   dpgo_graph_free(gw);
   return rc == 0 ? 0 : -1;
@@ -881,7 +881,7 @@ int dpgo_graph_verify_reweighted(const dpgo_graph_t *g, int device, const double
   dpgo_cert_options_t co;
   dpgo_cert_options_default(&co);
   if (cert_opts) co = *cert_opts;
-  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *) {
     return dpgo_group_verify(grp, X, ld, &co, max_factor_bytes, nullptr, 0, cert_result, x, ldx, cert_factor);
   });
 }
@@ -908,7 +908,7 @@ int dpgo_graph_covariance_reweighted(const dpgo_graph_t *g, int device, const do
                                      int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
                                      double *cross, dpgo_cov_result_t *result, dpgo_edge_summary_t *edge_summary) {
   if (!g || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
-  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *) {
     return dpgo_group_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, result);
   });
 }
@@ -931,7 +931,7 @@ int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, con
                                           double *joint, double *rel, double *gate, dpgo_pairs_result_t *result,
                                           dpgo_edge_summary_t *edge_summary) {
   if (!g || !X || !result || npairs < 0 || (npairs > 0 && (!pairs || !joint || !rel)) || (candidates && !gate)) return -1;
-  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp) {
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *) {
     return dpgo_group_pair_covariance(grp, X, ld, anchor, max_bytes, pairs, npairs, candidates, joint, rel, gate, result);
   });
 }
@@ -945,6 +945,29 @@ int dpgo_group_sensitivity(dpgo_group_t *h, const dpgo_graph_t *g, const double 
     const int rc = h->grp->sensitivity(g->g, X, ld, anchor, max_bytes, upstream, ldu, k, adjoint, sens, r);
     to_c(r, result);
     return rc;
+  });
+}
+
+// ---- per-edge reliability (rely.h) ----
+int dpgo_group_edge_reliability(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
+                                int method, const int *edges, int nedges, double *records, double *rel, double *joint,
+                                dpgo_rely_result_t *result) {
+  if (!h || !h->grp || !g || !X || !records || !result || (edges && nedges < 0)) return -1;
+  return guarded([&] {
+    dpgo::RelyResult r;
+    const int rc = h->grp->edge_reliability(g->g, X, ld, anchor, max_bytes, method, edges, nedges, records, rel, joint, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+int dpgo_graph_edge_reliability_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                           int anchor, long long max_bytes, int method, const int *edges, int nedges, double *records,
+                                           double *rel, double *joint, dpgo_rely_result_t *result, dpgo_edge_summary_t *edge_summary) {
+  if (!g || !X || !records || !result || (edges && nedges < 0)) return -1;
+  // (the scaled graph has the edges of g in g's order, so the list means the same on both)
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *gw) {
+    return dpgo_group_edge_reliability(grp, gw, X, ld, anchor, max_bytes, method, edges, nedges, records, rel, joint, result);
   });
 }
 

@@ -835,6 +835,19 @@ int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, co
   return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });
 }
 
+int dpgo_debug_rely_edge_host(int d, int n, const double *rel, const double *r, const double *kappa, const double *tau,
+                              double *records) {
+  return guarded([&] { return dpgo::rely_edge_host(d, n, rel, r, kappa, tau, records); });
+}
+
+int dpgo_debug_rely_edge(int device, int d, int n, const double *rel, const double *r, const double *kappa, const double *tau,
+                         double *records) {
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    return dpgo::rely_edge_device(d, n, rel, r, kappa, tau, records);
+  });
+}
+
 int dpgo_debug_robust_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, int loss, double loss_reg, const double *lambda,
                                      double *sens, double *phi) {
   if (!g) return -1;

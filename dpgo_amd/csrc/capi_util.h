@@ -97,6 +97,16 @@ inline void to_c(const dpgo::SensResult &r, dpgo_sens_result_t *o) {
   o->solve_ms = r.solve_ms; o->edge_ms = r.edge_ms;
 }
 
+inline void to_c(const dpgo::RelyResult &r, dpgo_rely_result_t *o) {
+  o->outcome = r.outcome; o->method_used = r.method_used; o->unknowns = r.unknowns; o->fronts = r.fronts;
+  o->levels = r.levels; o->max_front = r.max_front; o->edges = r.edges; o->flagged = r.flagged;
+  o->unweighted = r.unweighted; o->columns = r.columns; o->batches = r.batches; o->reserved = 0;
+  o->device_bytes = r.device_bytes; o->device_bytes_selinv = r.device_bytes_selinv;
+  o->device_bytes_solve = r.device_bytes_solve; o->redundancy_sum = r.redundancy_sum;
+  o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max; o->stationarity = r.stationarity;
+  o->symbolic_s = r.symbolic_s; o->factor_ms = r.factor_ms; o->inverse_ms = r.inverse_ms; o->edge_ms = r.edge_ms;
+}
+
 inline void to_c(const dpgo::PolishResult &r, dpgo_polish_result_t *o) {
   o->outcome = r.outcome; o->steps = r.steps; o->factorisations = r.factorisations;
   o->indefinite = r.indefinite; o->F_initial = r.F_initial; o->F_final = r.F_final;

@@ -66,6 +66,13 @@
 //              loss_reg on the robust polish's point and group; the line's prefix is "robust sensitivity:", every row of FILE
 //              has dof x (3 + dof) values -- one more per row, the edge's term of the derivative in the loss threshold -- and
 //              a last line "delta" with the dof values of d x_pose / d delta
+//              --edge_reliability FILE (likewise; empty: off)  behind --polish, on the polished point, for the trivial loss and a
+//              world of one rank: dpgo_group_edge_reliability of every edge (pose 0 the anchor, DPGO_RELY_AUTO) -- how well each
+//              measurement is checked by the others and whether it agrees with them -- one more line on stdout
+//                  reliability: <outcome> <method> <edges> <flagged> <unweighted> <redundancy_sum> <device_bytes> <pivot_min> <stationarity>
+//              and, for OK, one line per edge in FILE (17 digits):
+//                  e p q redundancy redundancy_trans d2_own d2_loo flag influence
+//              "reliability: not computed (...)" says why not
 //              --gate_candidates FILE --gate_report FILE (likewise; both or neither)  beside --covariance, for the trivial loss
 //              and a world of one rank: FILE is a .g2o of candidate edges p -> q, read by the loader's edge parser; every
 //              candidate is tested against the final X with dpgo_group_pair_covariance (pose 0 the anchor), one line per
@@ -111,7 +118,7 @@ int main(int argc, char **argv) {
   std::string dataset, loss_type = "trivial";
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
-  std::string edge_report, covariance, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
+  std::string edge_report, covariance, edge_reliability, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
   std::string sensitivity_report;
   int sensitivity_pose = -1;
   double gnc_barc2 = 4.0;
@@ -132,7 +139,9 @@ int main(int argc, char **argv) {
              "                          trivial-loss group of the graph (seconds of set-up at 100 000 poses)\n"
              "  --robust_covariance arg likewise: marginal covariances on the robust Hessian, written to the file named\n"
              "  --gnc arg               tls or gm, one rank: graduated non-convexity after the loop (outlier rejection on the inter-node\n"
-             "                          edges); --gnc_barc2 arg (=4) the inlier threshold, --gnc_report arg / --gnc_filtered arg its files\n");
+             "                          edges); --gnc_barc2 arg (=4) the inlier threshold, --gnc_report arg / --gnc_filtered arg its files\n"
+             "  --edge_reliability arg  trivial loss, one rank, behind --polish: redundancy and leave-one-out chi-square of every edge,\n"
+             "                          written to the file named\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
@@ -153,6 +162,7 @@ int main(int argc, char **argv) {
     else if (a.compare(0, 20, "--verify_reweighted=") == 0) verify_reweighted = parse_bool(argv[i] + 20);
     else if (const char *v = val("--edge_report")) edge_report = v;
     else if (const char *v = val("--covariance")) covariance = v;
+    else if (const char *v = val("--edge_reliability")) edge_reliability = v;
     else if (const char *v = val("--gate_candidates")) gate_candidates = v;
     else if (const char *v = val("--gate_report")) gate_report = v;
     else if (const char *v = val("--sensitivity_pose")) sensitivity_pose = atoi(v);
@@ -671,6 +681,40 @@ int main(int argc, char **argv) {
           for (int a = 0; a < dof; a++)
             for (int b = 0; b < no; b++) fprintf(f, " %.17g", sens[((size_t)a * m + e) * no + b]);
           fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+    }
+  }
+  if (!edge_reliability.empty()) {
+    if (loss != 0) {
+      if (root) printf("reliability: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("reliability: not computed (the group must host every node; %d ranks)\n", world);
+    } else if (!polish) {
+      if (root) printf("reliability: not computed (it is taken at a critical point: --polish)\n");
+    } else {
+      int gd = 0, gN = 0, gn = 0, m = 0;
+      if (dpgo_graph_info(g, &gd, &gN, &gn, &m) != 0) return -1;
+      const int dof = d + d * (d - 1) / 2, w = 6 + 2 * dof;
+      std::vector<int> I(m), J(m);
+      std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m);
+      if (dpgo_graph_edges(g, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data()) != 0) return -1;
+      std::vector<double> Xc((size_t)ld * d, 0.0), rec((size_t)m * w, 0.0);
+      dpgo_rely_result_t rr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_edge_reliability(grp, g, Xc.data(), ld, 0, 0, DPGO_RELY_AUTO, nullptr, 0, rec.data(), nullptr, nullptr, &rr) != 0)
+        return -1;
+      printf("reliability: %s %s %d %d %d %.17g %lld %.16g %.16g\n",
+             rr.outcome == DPGO_RELY_OK ? "OK" : rr.outcome == DPGO_RELY_NOT_PD ? "NOT_PD" : "SKIPPED",
+             rr.method_used == DPGO_RELY_SELINV ? "SELINV" : rr.method_used == DPGO_RELY_SOLVE ? "SOLVE" : "AUTO", rr.edges, rr.flagged,
+             rr.unweighted, rr.redundancy_sum, rr.device_bytes, rr.pivot_min, rr.stationarity);
+      if (rr.outcome == DPGO_RELY_OK) {
+        FILE *f = fopen(edge_reliability.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", edge_reliability.c_str()); return -1; }
+        for (int e = 0; e < m; e++) {
+          const double *q = &rec[(size_t)e * w];
+          fprintf(f, "%d %d %d %.17g %.17g %.17g %.17g %d %.17g\n", e, I[e], J[e], q[2], q[3], q[4], q[0], (int)q[1], q[5]);
         }
         fclose(f);
       }

@@ -33,6 +33,7 @@
 #include "pairs.h"
 #include "gnc.h"
 #include "polish.h"
+#include "rely.h"
 #include "robust.h"
 #include "rsens.h"
 #include "schedule.h"
@@ -240,6 +241,12 @@ class Group {
   // upstream: (dof N) x k column-major by global pose (ldu >= dof N); adjoint (optional): (dof N) x k; sens: k x num_edges x (2 + dof)
   int sensitivity(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, const double *upstream, int ldu, int k,
                   double *adjoint, double *sens, SensResult &out);
+  // ---- per-edge reliability (rely.h, rely.cpp): the covariance's factor, the three blocks of every listed edge by the selected
+  // inversion or by the pair covariances' batches, one record per listed edge.  g: as for the sensitivities; edges (optional):
+  // nedges indices into g's edges, any order, repeats allowed -- null: all of them; rec: one row of rely_width(d) doubles per
+  // listed edge; rel (optional): dof^2 per listed edge; joint (optional): 3 dof^2
+  int edge_reliability(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, int method, const int *edges,
+                       int nedges, double *rec, double *rel, double *joint, RelyResult &out);
   // ---- ... of the ROBUST objective (rsens.h, rsens.cpp): the same on the true robust Hessian (robust_covariance's, curvature 1)
   // with the loss threshold one more parameter.  sens: k x num_edges x (3 + dof), the last entry the edge's term of dL/ddelta;
   // dloss_reg: k, their sums over the edges
@@ -716,6 +723,9 @@ class Group {
   void gnc_summary(GncSummaryDev &sd);
   // likewise (pairs.cpp); own_remain: those of own_bytes still to be allocated, as cov_setup's extra_remain (< 0: all of them)
   int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out, long long own_remain = -1);
+  // the batches of a plan behind a factorisation: joint (device, zeroed by the caller) <- the blocks of the pairs (pairs.cpp)
+  int pairs_solve_joint(const PairsPlan &pl, const std::vector<int> &row_of, int npairs, const int *d_prow, double *d_joint,
+                        const char *who);
   // a graph checked against the group; rec: its edge records in graph order, heads on unified own rows (robust.cpp; sens.cpp too)
   int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec);
   bool star_ = false;

@@ -66,6 +66,37 @@ int Group::pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsRe
   return 0;
 }
 
+// The batches of a column plan behind a factorisation that succeeded: per batch the unit right-hand sides, the block solve and the
+// gather of the blocks whose columns it holds.  d_prow (2 npairs unified own rows) and d_joint (npairs x 3 dof^2, zeroed by the
+// caller: the anchor's blocks) are the caller's, on the device, where joint stays; returns behind a synchronise.
+int Group::pairs_solve_joint(const PairsPlan &pl, const std::vector<int> &row_of, int npairs, const int *d_prow, double *d_joint,
+                             const char *who) {
+  CovState &s = *cov_;
+  const int dof = cov_dof(d_);
+  const long long n = (long long)dof * P0_;
+  std::vector<int> col_unknown((size_t)std::max(pl.columns, 1), 0);
+  for (int i = 0; i < (int)pl.poses.size(); i++)
+    for (int a = 0; a < dof; a++) col_unknown[(size_t)dof * i + a] = dof * row_of[pl.poses[i]] + a;
+  DevBuf<int> d_pcol, d_unk;
+  DevBuf<double> d_Xb;
+  d_pcol.upload(pl.pair_col);
+  d_unk.upload(col_unknown);
+  d_Xb.alloc((size_t)n * pl.kb, false);
+  for (int b = 0; b < pl.batches; b++) {
+    const int c0 = b * PAIRS_BATCH, nc = std::min(PAIRS_BATCH, pl.columns - c0);
+    HIP_CHECK(hipMemsetAsync(d_Xb.p, 0, sizeof(double) * (size_t)n * pl.kb, st_));
+    launch_pairs_rhs(st_, d_unk.p, c0, nc, d_Xb.p, pl.kb);
+    if (spd_msolve_device(s.F, d_Xb.p, nc, pl.kb, st_) != 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: %s: the solve failed on the device.\n", who);
+      return -1;
+    }
+    launch_pairs_gather(st_, dof, npairs, d_prow, d_pcol.p, c0, nc, d_Xb.p, pl.kb, d_joint);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st_));
+  return 0;
+}
+
 int Group::pair_covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs,
                            const double *candidates, double *joint, double *rel, double *gate, PairsResult &out) {
   out = PairsResult();
@@ -132,35 +163,19 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
     return 0;
   }
   t0 = Clock::now();
-  // this call's buffers: the batch, the pairs' rows and columns, the unknown of every column, the outputs
-  std::vector<int> prow((size_t)2 * npairs), col_unknown((size_t)std::max(pl.columns, 1), 0);
+  // this call's buffers: the pairs' rows, the outputs (the batch and the plan's lists: pairs_solve_joint)
+  std::vector<int> prow((size_t)2 * npairs);
   for (int k = 0; k < 2 * npairs; k++) prow[k] = row_of[pairs[k]];
-  for (int i = 0; i < (int)pl.poses.size(); i++)
-    for (int a = 0; a < dof; a++) col_unknown[(size_t)dof * i + a] = dof * row_of[pl.poses[i]] + a;
-  DevBuf<int> d_prow, d_pcol, d_unk;
-  DevBuf<double> d_Xb, d_joint, d_rel, d_gate, d_cand;
+  DevBuf<int> d_prow;
+  DevBuf<double> d_joint, d_rel, d_gate, d_cand;
   d_prow.upload(prow);
-  d_pcol.upload(pl.pair_col);
-  d_unk.upload(col_unknown);
-  d_Xb.alloc((size_t)n * pl.kb, false);
   d_joint.alloc((size_t)npairs * 3 * DD);   // (zeroed: the anchor's blocks)
   d_rel.alloc((size_t)npairs * DD);
   if (candidates) {
     d_cand.upload(std::vector<double>(candidates, candidates + (size_t)npairs * ncand));
     d_gate.alloc((size_t)npairs * ngate);
   }
-  for (int b = 0; b < pl.batches; b++) {
-    const int c0 = b * PAIRS_BATCH, nc = std::min(PAIRS_BATCH, pl.columns - c0);
-    HIP_CHECK(hipMemsetAsync(d_Xb.p, 0, sizeof(double) * (size_t)n * pl.kb, st_));
-    launch_pairs_rhs(st_, d_unk.p, c0, nc, d_Xb.p, pl.kb);
-    if (spd_msolve_device(s.F, d_Xb.p, nc, pl.kb, st_) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: pair_covariance: the solve failed on the device.\n");
-      return -1;
-    }
-    launch_pairs_gather(st_, dof, npairs, d_prow.p, d_pcol.p, c0, nc, d_Xb.p, pl.kb, d_joint.p);
-  }
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(st_));
+  if (pairs_solve_joint(pl, row_of, npairs, d_prow.p, d_joint.p, "pair_covariance") != 0) return -1;
   out.solve_ms = ms_since(t0);
   t0 = Clock::now();
   launch_pairs_gate(d, st_, npairs, d_prow.p, d_joint.p, c.X.p, candidates ? d_cand.p : nullptr, d_rel.p, candidates ? d_gate.p : nullptr);

@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -40,6 +40,11 @@
 //   robust sensitivity: e <edge> <the dof x (3 + dof) entries, the last of a row the edge's term of d/dloss_reg>
 // then   robust sensitivity: delta <the dof values of d x_pose / d loss_reg>
 // then   robust sensitivity: <OK|NOT_PD|SKIPPED|FAILED> <edges> <columns> <batches>
+// and with `reliability` through DPGOHashGroup::newton_polish and DPGOHashGroup::edge_reliability (trivial loss; pose 0 is the
+// anchor; every edge): per edge one line, all entries with 17 digits,
+//   reliability: e <edge> <the 6 + 2 dof entries of its record>
+// then   reliability: <OK|NOT_PD|SKIPPED|FAILED> <SELINV|SOLVE|AUTO> <edges> <flagged> <unweighted> <redundancy_sum, 17 digits>; a
+// last call with an edge index outside the graph must fail:   reliability: bad edge <status>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -59,7 +64,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -291,6 +296,28 @@ int main(int argc, char **argv) {
     int short_status = 0;
     dpgo_hash.measurement_sensitivities(Xp, up, sens, 0, nullptr, &short_status);
     fprintf(stderr, "sensitivity: short upstream %d %d\n", short_status, (int)sens.size());
+  }
+  if (argc > 6 && !strcmp(argv[6], "reliability")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0 || !dpgo_hash.newton_polish(X, Xp)) return 1;
+    const int d = graph->d(), w = 6 + 2 * (d + d * (d - 1) / 2), m = graph->num_edges();
+    std::vector<double> rec;
+    int status = -1;
+    dpgo_rely_result_t r = {};
+    const bool ok = dpgo_hash.edge_reliability(Xp, rec, 0, &r, &status);
+    for (int e = 0; ok && e < m; e++) {
+      fprintf(stderr, "reliability: e %d", e);
+      for (int b = 0; b < w; b++) fprintf(stderr, " %.17g", rec[(size_t)e * w + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "reliability: %s %s %d %d %d %.17g\n", status == DPGO_RELY_OK ? "OK" : status == DPGO_RELY_NOT_PD ? "NOT_PD"
+            : status == DPGO_RELY_SKIPPED ? "SKIPPED" : "FAILED", r.method_used == DPGO_RELY_SELINV ? "SELINV"
+            : r.method_used == DPGO_RELY_SOLVE ? "SOLVE" : "AUTO", r.edges, r.flagged, r.unweighted, r.redundancy_sum);
+    if (status < 0) return 1;
+    const std::vector<int> bad = {0, m};
+    int bad_status = 0;
+    dpgo_hash.edge_reliability(Xp, rec, 0, nullptr, &bad_status, &bad);
+    fprintf(stderr, "reliability: bad edge %d\n", bad_status);
   }
   if (argc > 7 && !strcmp(argv[6], "robust_sensitivity")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;

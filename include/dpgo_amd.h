@@ -635,6 +635,63 @@ int dpgo_group_sensitivity(dpgo_group_t *grp, const dpgo_graph_t *graph, const d
  * no anchor is struck out); sens: num_edges x (2 + dof) in the order above; phi: num_edges (phi_e) or NULL. */
 int dpgo_debug_sens_edge_host(const dpgo_graph_t *graph, const double *X, int ld, const double *lambda, double *sens, double *phi);
 
+/* ---- per-edge reliability: redundancy numbers and the leave-one-out chi-square ------------ */
+/* How well is each measurement of the graph checked by the others, and does it agree with them?  The gate of
+ * dpgo_group_pair_covariance answers for a CANDIDATE: for an edge that is already in the graph its d^2 counts the edge twice.
+ * With rel = J Sigma_joint J^T, r and Omega = blkdiag(tau I_d, 2 kappa I_{dof-d}) as there -- the edge's own (R~, t~, kappa, tau)
+ * taken as the candidate -- the quantities of an existing edge are built on the residual covariance C = Omega^-1 - rel:
+ *     d2_loo = r^T C^-1 r (Baarda / Pope data snooping; compare with a chi-square quantile of dof degrees of freedom; 1/2 d2_loo
+ *     is the first-order drop of the optimum when the edge is removed),  r_loo = Omega^-1 C^-1 r (the residual the edge would have
+ *     at the solution of the graph without it),  influence = z^T rel z with z = C^-1 r (the H-norm squared of the displacement of
+ *     that solution),  redundancy = dof - sum_i Omega_ii rel_ii,  redundancy_trans = d - tau sum_{i<d} rel_ii,  d2_own = r^T Omega r.
+ * No threshold is applied.  Restrictions, anchor and coordinates as for dpgo_group_covariance; X should be a critical point
+ * (dpgo_group_polish); the optimiser is not touched.
+ *   graph       as for dpgo_group_sensitivity (-1 otherwise); it numbers the edges
+ *   method      DPGO_RELY_SELINV: the selected inversion of dpgo_group_covariance, every listed edge's three blocks gathered from
+ *               it on the device; DPGO_RELY_SOLVE: the block solves of dpgo_group_pair_covariance on the distinct poses of the
+ *               listed edges; DPGO_RELY_AUTO: SELINV where its bytes are not refused, otherwise SOLVE, otherwise SKIPPED
+ *   edges       NULL (every edge of the graph, nedges ignored), or nedges indices into the graph's edges: any order, repeats
+ *               allowed; an index outside the graph: -1
+ *   records     one row per listed edge, 6 + 2 dof doubles: d2_loo, flag, redundancy, redundancy_trans, d2_own, influence, r[dof],
+ *               r_loo[dof].  flag 0: C is positive definite (every pivot of its Cholesky factor positive).  1: it is not (no
+ *               redundancy, or the Gauss-Newton model does not hold at X): d2_loo, influence, r_loo are exact zeros, the rest is
+ *               filled.  2: kappa or tau of the edge is not > 0 (dpgo_graph_scale_edges can leave that): zeros but the flag
+ *   rel, joint  NULL, or per listed edge dof^2 / 3 dof^2 doubles as dpgo_group_pair_covariance hands them out
+ *   result      outcome RELY_OK, RELY_NOT_PD (the anchored H is not positive definite; the outputs are zero) or RELY_SKIPPED (the
+ *               bytes of the method above max_bytes (> 0) or above half of the free device memory; the outputs are not written,
+ *               nothing is allocated); device_bytes_selinv / device_bytes_solve: what either method would allocate, filled for
+ *               SKIPPED too, device_bytes: of method_used; edges: listed, flagged: flag 1, unweighted: flag 2; redundancy_sum:
+ *               the records' redundancy summed in list order, flag-2 edges left out (dof (m - N + 1) over a whole graph with
+ *               zero residuals); columns / batches: of the SOLVE plan; factor_ms / inverse_ms / edge_ms: host milliseconds of
+ *               the factorisation, of the inversion and the gather (or the batches), and of the two edge kernels with the
+ *               copies of their output, each ending in a synchronise */
+#define DPGO_RELY_OK 0
+#define DPGO_RELY_NOT_PD 1
+#define DPGO_RELY_SKIPPED 2
+#define DPGO_RELY_AUTO 0
+#define DPGO_RELY_SELINV 1
+#define DPGO_RELY_SOLVE 2
+typedef struct dpgo_rely_result {
+  int outcome, method_used, unknowns, fronts, levels, max_front, edges, flagged, unweighted, columns, batches, reserved;
+  long long device_bytes, device_bytes_selinv, device_bytes_solve;
+  double redundancy_sum, pivot_min, pivot_max, stationarity, symbolic_s, factor_ms, inverse_ms, edge_ms;
+} dpgo_rely_result_t;
+int dpgo_group_edge_reliability(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, long long max_bytes,
+                                int method, const int *edges, int nedges, double *records, double *rel, double *joint,
+                                dpgo_rely_result_t *result);
+/* The same for the RE-WEIGHTED problem at X, by dpgo_graph_covariance_reweighted's recipe: the loss weights frozen at X, a
+ * trivial-loss group of the scaled graph.  It describes the MM surrogate, not the robust objective.  edge_summary may be NULL. */
+int dpgo_graph_edge_reliability_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                           int anchor, long long max_bytes, int method, const int *edges, int nedges, double *records,
+                                           double *rel, double *joint, dpgo_rely_result_t *result, dpgo_edge_summary_t *edge_summary);
+/* Debug (no device): the arithmetic of one record on the host, the code k_rely_edge runs, for n edges -- rel: n x dof^2, r: n x dof,
+ * kappa, tau: n each; records: n x (6 + 2 dof). */
+int dpgo_debug_rely_edge_host(int d, int n, const double *rel, const double *r, const double *kappa, const double *tau,
+                              double *records);
+/* Debug: k_rely_edge alone on the same arrays (host pointers), on HIP device `device`. */
+int dpgo_debug_rely_edge(int device, int d, int n, const double *rel, const double *r, const double *kappa, const double *tau,
+                         double *records);
+
 /* ---- Newton polish: from the point the optimiser stopped at to a critical point ----------- */
 /* AMM-PGO# is a first-order method; the certificate and the covariances above mean something only at a critical point.
  * dpgo_group_polish takes damped Riemannian Newton steps from X -- Levenberg-Marquardt on the anchored tangent-space Hessian

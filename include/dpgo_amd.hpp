@@ -304,6 +304,31 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_SENS_OK;
   }
+  // Per-edge reliability (dpgo_group_edge_reliability): for every edge of the graph, or for the listed indices into its edges
+  // (any order, repeats allowed; null: all), one record of 6 + 2 dof doubles -- d2_loo, flag, redundancy, redundancy_trans,
+  // d2_own, influence, r[dof], r_loo[dof] -- the leave-one-out chi-square of an edge that is already in the graph, the residual
+  // it would have without it, and how well the other measurements check it.  method: DPGO_RELY_AUTO / SELINV / SOLVE.  X
+  // should be a critical point (newton_polish).  Returns true for DPGO_RELY_OK; status: the DPGO_RELY_* outcome, -1 when the
+  // call itself failed (robust loss, a group that does not host every node, an edge index outside the graph, an unknown method).
+  bool edge_reliability(const Matrix &X, std::vector<Scalar> &records, int anchor = 0, dpgo_rely_result_t *result = nullptr,
+                        int *status = nullptr, const std::vector<int> *edges = nullptr, int method = DPGO_RELY_AUTO,
+                        long long max_bytes = 0, std::vector<Scalar> *rel = nullptr, std::vector<Scalar> *joint = nullptr) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2;
+    const size_t n = edges ? edges->size() : (size_t)graph_->num_edges();
+    records.assign(n * (6 + 2 * dof), 0.0);
+    if (rel) rel->assign(n * dof * dof, 0.0);
+    if (joint) joint->assign(n * 3 * dof * dof, 0.0);
+    const int none = 0;   // (an empty list is a list: neither its pointer nor that of its records may be null)
+    Scalar no_record = 0;
+    dpgo_rely_result_t r = {};
+    const int rc = dpgo_group_edge_reliability(h_, graph_->handle(), X.data(), X.rows(), anchor, max_bytes, method,
+                                               edges ? (edges->empty() ? &none : edges->data()) : nullptr, edges ? (int)edges->size() : 0,
+                                               records.empty() ? &no_record : records.data(),
+                                               rel ? rel->data() : nullptr, joint ? joint->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_RELY_OK;
+  }
   // Newton polish (dpgo_group_polish): damped Riemannian Newton steps from X on the anchored tangent-space Hessian of
   // marginal_covariances, until the tangent gradient is at rounding level or the step budget is spent.  Xout: the new point
   // (X itself when the call is SKIPPED or fails).  opt (optional): the rule's parameters and the anchor; log (optional): per
