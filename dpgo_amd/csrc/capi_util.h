@@ -72,47 +72,46 @@ inline void to_c(const dpgo::EdgeSummary &s, dpgo_edge_summary_t *o) {
   o->num_inter = s.num_inter; o->num_downweighted = s.num_downweighted;
 }
 
+// the analysis' numbers (hess.h), which the five result structs below carry under the same names
+template <class C>
+inline void analysis_to_c(const dpgo::HessAnalysis &r, C *o) {
+  o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels; o->max_front = r.max_front;
+  o->device_bytes = r.device_bytes; o->symbolic_s = r.symbolic_s; o->pivot_min = r.pivot_min;
+  o->pivot_max = r.pivot_max; o->factor_ms = r.factor_ms;
+}
+
 inline void to_c(const dpgo::CovResult &r, dpgo_cov_result_t *o) {
-  o->outcome = r.outcome; o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels;
-  o->max_front = r.max_front; o->device_bytes = r.device_bytes; o->pivot_min = r.pivot_min;
-  o->pivot_max = r.pivot_max; o->stationarity = r.stationarity; o->symbolic_s = r.symbolic_s;
-  o->numeric_ms = r.numeric_ms; o->factor_ms = r.factor_ms; o->selinv_ms = r.selinv_ms;
-  o->selinv_flops = r.selinv_flops;
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->stationarity = r.stationarity; o->numeric_ms = r.numeric_ms;
+  o->selinv_ms = r.selinv_ms; o->selinv_flops = r.selinv_flops;
 }
 
 inline void to_c(const dpgo::PairsResult &r, dpgo_pairs_result_t *o) {
-  o->outcome = r.outcome; o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels;
-  o->max_front = r.max_front; o->columns = r.columns; o->batches = r.batches; o->reserved = 0;
-  o->device_bytes = r.device_bytes; o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max;
-  o->stationarity = r.stationarity; o->symbolic_s = r.symbolic_s; o->factor_ms = r.factor_ms;
-  o->solve_ms = r.solve_ms; o->gate_ms = r.gate_ms; o->solve_flops = r.solve_flops;
-  o->factor_bytes = r.factor_bytes;
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->columns = r.columns; o->batches = r.batches; o->reserved = 0;
+  o->stationarity = r.stationarity; o->solve_ms = r.solve_ms; o->gate_ms = r.gate_ms;
+  o->solve_flops = r.solve_flops; o->factor_bytes = r.factor_bytes;
 }
 
 inline void to_c(const dpgo::SensResult &r, dpgo_sens_result_t *o) {
-  o->outcome = r.outcome; o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels;
-  o->max_front = r.max_front; o->columns = r.columns; o->batches = r.batches; o->edges = r.edges;
-  o->device_bytes = r.device_bytes; o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max;
-  o->stationarity = r.stationarity; o->symbolic_s = r.symbolic_s; o->factor_ms = r.factor_ms;
-  o->solve_ms = r.solve_ms; o->edge_ms = r.edge_ms;
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->columns = r.columns; o->batches = r.batches; o->edges = r.edges;
+  o->stationarity = r.stationarity; o->solve_ms = r.solve_ms; o->edge_ms = r.edge_ms;
 }
 
 inline void to_c(const dpgo::RelyResult &r, dpgo_rely_result_t *o) {
-  o->outcome = r.outcome; o->method_used = r.method_used; o->unknowns = r.unknowns; o->fronts = r.fronts;
-  o->levels = r.levels; o->max_front = r.max_front; o->edges = r.edges; o->flagged = r.flagged;
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->method_used = r.method_used; o->edges = r.edges; o->flagged = r.flagged;
   o->unweighted = r.unweighted; o->columns = r.columns; o->batches = r.batches; o->reserved = 0;
-  o->device_bytes = r.device_bytes; o->device_bytes_selinv = r.device_bytes_selinv;
-  o->device_bytes_solve = r.device_bytes_solve; o->redundancy_sum = r.redundancy_sum;
-  o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max; o->stationarity = r.stationarity;
-  o->symbolic_s = r.symbolic_s; o->factor_ms = r.factor_ms; o->inverse_ms = r.inverse_ms; o->edge_ms = r.edge_ms;
+  o->device_bytes_selinv = r.device_bytes_selinv; o->device_bytes_solve = r.device_bytes_solve;
+  o->redundancy_sum = r.redundancy_sum; o->stationarity = r.stationarity;
+  o->inverse_ms = r.inverse_ms; o->edge_ms = r.edge_ms;
 }
 
 inline void to_c(const dpgo::PolishResult &r, dpgo_polish_result_t *o) {
+  analysis_to_c(r, o);
   o->outcome = r.outcome; o->steps = r.steps; o->factorisations = r.factorisations;
   o->indefinite = r.indefinite; o->F_initial = r.F_initial; o->F_final = r.F_final;
   o->grad_initial = r.grad_initial; o->grad_final = r.grad_final; o->hmax = r.hmax;
-  o->mu_final = r.mu_final; o->pivot_min = r.pivot_min; o->pivot_max = r.pivot_max;
-  o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels; o->max_front = r.max_front;
-  o->device_bytes = r.device_bytes; o->symbolic_s = r.symbolic_s; o->total_ms = r.total_ms;
-  o->factor_ms = r.factor_ms; o->solve_ms = r.solve_ms; o->other_ms = r.other_ms;
+  o->mu_final = r.mu_final; o->total_ms = r.total_ms; o->solve_ms = r.solve_ms; o->other_ms = r.other_ms;
 }

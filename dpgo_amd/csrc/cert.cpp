@@ -355,6 +355,8 @@ void Group::cert_build_pattern() {
   CertState &c = *cert_;
   if (c.have_pattern) return;
   const int B = B_, BB = B * B, N = P0_;
+  c.row_of.resize(N);
+  for (int p = 0; p < N; p++) c.row_of[c.gid[p]] = p;
   std::vector<int> nbr_row(std::max(P1_, 1), -1);   // neighbour record -> the unified own row of the pose it copies
   for (int a = 0; a < num_local(); a++)
     for (int k = 0; k < info_[a].n[1]; k++) {
@@ -417,6 +419,17 @@ void Group::cert_build_pattern() {
   c.diag_pose.upload(diag);
   c.Mval.upload(Mval);
   c.have_pattern = true;
+}
+
+int Group::own_row(int global_pose) const { return cert_->row_of[global_pose]; }
+
+// the block of the pattern that holds (p, q), unified own rows; -1: none
+int Group::cert_block_of(int p, int q) const {
+  const CertState &c = *cert_;
+  const int B = B_, b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
+  for (int j = 0; j < nb; j++)
+    if (c.A.col[(size_t)B * B * b0 + (size_t)j * B] / B == q) return b0 + j;
+  return -1;
 }
 
 // The analysis (first call), the prediction, the refusal, the numeric context (first call that is not refused).
@@ -521,12 +534,11 @@ int Group::cert_matrix(const double *X, int ld, double eta, int *ptr, int *col, 
 void Group::cert_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val) {
   CertState &c = *cert_;
   const int B = B_, BB = B * B, N = P0_;
-  std::vector<int> row_of(N), order;
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
+  std::vector<int> order;
   size_t e = 0;
   ptr[0] = 0;
   for (int g = 0; g < N; g++) {
-    const int p = row_of[g], b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
+    const int p = own_row(g), b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
     const size_t base = (size_t)BB * b0;
     auto pose_of = [&](int j) { return c.gid[c.A.col[base + (size_t)j * B] / B]; };
     order.resize(nb);

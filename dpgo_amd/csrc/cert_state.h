@@ -15,6 +15,7 @@ struct Group::CertState {
   double *h_sums = nullptr;             // pinned: what k_cert_reduce writes
   bool have_Tp = false;
   std::vector<int> gid;                 // unified own row -> global pose
+  std::vector<int> row_of;              // ... and back (Group::own_row), with the pattern (cert_build_pattern)
   // STEP 1: the pattern of S on the unknowns (d+1) p + r (p the unified own row), M's values in that order, the factor
   CsrMatrix A;                          // ptr / col only: the values are written on the device
   std::vector<int> bptr_h;

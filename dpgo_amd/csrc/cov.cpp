@@ -1,6 +1,6 @@
 // Host side of the marginal pose covariances (cov.h): the pattern of the tangent-space Hessian from the certificate's walk,
-// its multifrontal analysis, the refusal, and the calls that write H on the device (k_cov_hessian), factor it
-// (spd_refactor_device) and invert it inside the factor's pattern (spd_selinv_device).  The optimiser's state is not
+// its multifrontal analysis, the parts of its refusal, and the calls that write H on the device (k_cov_hessian), factor it
+// (hess.cpp: hess_factor) and invert it inside the factor's pattern (spd_selinv_device).  The optimiser's state is not
 // touched: own factor, own buffers, behind finish_update() / join_exchange() (cert_begin), released in the group's teardown.
 #include "cov.h"
 
@@ -30,8 +30,9 @@ int Group::cov_begin(const double *X, int ld, int anchor) {
   return 0;
 }
 
-// The analysis (first call) and what it predicts: the pattern of H from the certificate's, its multifrontal analysis.
-int Group::cov_analyse(CovResult &out) {
+// The analysis (first call) and its numbers: the pattern of H from the certificate's, its multifrontal analysis.  device_bytes is
+// the caller's refusal's to fill (hess_reserve).
+int Group::cov_analyse(HessAnalysis &out) {
   CertState &c = *cert_;
   CovState &s = *cov_;
   cert_build_pattern();
@@ -70,7 +71,8 @@ int Group::cov_analyse(CovResult &out) {
         s.piv_front[s.F.piv_idx[s.F.piv_ptr[f] + k]] = f;
         s.piv_loc[s.F.piv_idx[s.F.piv_ptr[f] + k]] = k;
       }
-    s.bytes = (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + (long long)spd_selinv_bytes(s.F) + 4ll * (long long)nblk;
+    s.numeric_bytes = (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + 4ll * (long long)nblk;
+    s.selinv_bytes = (long long)spd_selinv_bytes(s.F);
     s.symbolic_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     out.symbolic_s = s.symbolic_s;
     s.have_symbolic = true;
@@ -79,35 +81,39 @@ int Group::cov_analyse(CovResult &out) {
   out.fronts = s.F.nfronts;
   out.levels = (int)s.F.by_height.size();
   out.max_front = s.F.max_front;
-  out.device_bytes = s.bytes;
+  return 0;
+}
+
+// The analysis and the refusal of covariance, robust_covariance and the two read-backs: the numeric phase, the blocks of the
+// selected inversion -- still to allocate only where the numeric phase is, whether an earlier call has left them or not -- and the
+// caller's extra bytes (robust.cpp).
+int Group::cov_setup(long long max_bytes, CovResult &out, HessPart extra) {
+  if (cov_analyse(out) != 0) return -1;
+  CovState &s = *cov_;
   for (int f = 0; f < s.F.nfronts; f++) {
     const double w = s.F.w[f], u = s.F.u[f];
     out.selinv_flops += 2 * u * u * w + 2 * u * w * w + w * w * w;
   }
-  out.outcome = COV_SKIPPED;
-  return 0;
+  return hess_reserve(max_bytes, "covariance", {s.numeric_part(), {s.selinv_bytes, s.F.numeric ? 0 : s.selinv_bytes}, extra}, out);
 }
 
-// The analysis, the refusal, the numeric context (first call that is not refused): cert_factor_setup's rule.
-int Group::cov_setup(long long max_bytes, CovResult &out, long long extra, long long extra_remain) {
-  if (cov_analyse(out) != 0) return -1;
-  CovState &s = *cov_;
-  out.device_bytes = s.bytes + extra;
-  if (max_bytes > 0 && s.bytes + extra > max_bytes) return 1;
-  const long long remain = (s.F.numeric ? 0 : s.bytes) + extra_remain;
-  if (remain > 0) {
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    if ((unsigned long long)remain > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
-  }
-  if (!s.F.numeric) {
-    s.bcol.upload(s.bcol_h);
-    if (spd_prepare_device(s.A, s.F) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: covariance: the device state of the factorisation could not be set up.\n");
-      return -1;
+bool Group::pairs_args_ok(const char *who, const int *pairs, int npairs) const {
+  for (int k = 0; k < 2 * npairs; k++)
+    if (pairs[k] < 0 || pairs[k] >= P0_) {
+      fprintf(stderr, "[dpgo_amd] ERROR: %s: pair %d names a pose that is not in the graph.\n", who, k / 2);
+      return false;
     }
-  }
-  return 0;
+  return true;
+}
+
+// edges lie inside the selected pattern; anything else does not
+bool Group::pairs_are_edges(const char *who, const int *pairs, int npairs) const {
+  for (int k = 0; k < npairs; k++)
+    if (cert_block_of(own_row(pairs[2 * k]), own_row(pairs[2 * k + 1])) < 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: %s: pair %d (%d, %d) is not an edge of the graph.\n", who, k, pairs[2 * k], pairs[2 * k + 1]);
+      return false;
+    }
+  return true;
 }
 
 int Group::covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs, double *marginals,
@@ -118,52 +124,33 @@ int Group::covariance(const double *X, int ld, int anchor, long long max_bytes, 
     return -1;
   }
   if (cov_begin(X, ld, anchor) != 0) return -1;
-  CertState &c = *cert_;
-  CovState &s = *cov_;
-  const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
-  for (int k = 0; k < 2 * npairs; k++)
-    if (pairs[k] < 0 || pairs[k] >= N) {
-      fprintf(stderr, "[dpgo_amd] ERROR: covariance: pair %d names a pose that is not in the graph.\n", k / 2);
-      return -1;
-    }
+  if (!pairs_args_ok("covariance", pairs, npairs)) return -1;
   const int ready = cov_setup(max_bytes, out);
-  if (ready < 0) return -1;
-  for (int k = 0; k < npairs; k++) {   // edges lie inside the selected pattern; anything else does not
-    const int p = row_of[pairs[2 * k]], q = row_of[pairs[2 * k + 1]];
-    const int *b0 = &s.bcol_h[c.bptr_h[p]], *b1 = &s.bcol_h[c.bptr_h[p + 1]];
-    if (std::find(b0, b1, q) == b1) {
-      fprintf(stderr, "[dpgo_amd] ERROR: covariance: pair %d (%d, %d) is not an edge of the graph.\n", k, pairs[2 * k], pairs[2 * k + 1]);
-      return -1;
-    }
-  }
+  if (ready < 0 || !pairs_are_edges("covariance", pairs, npairs)) return -1;
   cert_prepare(X, ld, &out.stationarity);
   if (ready != 0) return 0;   // SKIPPED, with what the analysis predicts
-  std::fill(marginals, marginals + (size_t)N * DD, 0.0);
-  if (npairs) std::fill(cross, cross + (size_t)npairs * DD, 0.0);
-  const int arow = row_of[anchor];
-  const auto t0 = std::chrono::steady_clock::now();
-  launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
-  return cov_finish(arow, row_of, pairs, npairs, marginals, cross, out, t0);
+  return cov_finish([&] { launch_cov_hessian_at(own_row(anchor)); }, own_row(anchor), pairs, npairs, marginals, cross, out);
 }
 
-int Group::cov_finish(int arow, const std::vector<int> &row_of, const int *pairs, int npairs, double *marginals, double *cross,
-                      CovResult &out, std::chrono::steady_clock::time_point t0) {
+// k_cov_hessian on the certificate's M, Lambda and X into the factorisation's values
+void Group::launch_cov_hessian_at(int arow) {
+  CertState &c = *cert_;
+  CovState &s = *cov_;
+  launch_cov_hessian(d_, st_, P0_, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
+}
+
+int Group::cov_finish(const std::function<void()> &write_H, int arow, const int *pairs, int npairs, double *marginals, double *cross,
+                      CovResult &out) {
   CertState &c = *cert_;
   CovState &s = *cov_;
   const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
-  const int rc = spd_refactor_device(s.F, st_, false);   // (returns with the verdict read)
-  if (rc != 0 && !s.F.not_pd) {
-    fprintf(stderr, "[dpgo_amd] ERROR: covariance: the factorisation failed on the device.\n");
-    return -1;
-  }
-  out.pivot_max = s.F.pivot_max;
-  out.pivot_min = s.F.pivot_max > 0 ? s.F.pivot_min : 0.0;
-  const auto t1 = std::chrono::steady_clock::now();
-  out.factor_ms = 1e3 * std::chrono::duration<double>(t1 - t0).count();
+  const std::vector<int> &row_of = c.row_of;
+  std::fill(marginals, marginals + (size_t)N * DD, 0.0);
+  if (npairs) std::fill(cross, cross + (size_t)npairs * DD, 0.0);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = hess_factor("covariance", write_H, out);
+  if (rc < 0) return -1;
   if (rc != 0) {
-    HIP_CHECK(hipStreamSynchronize(st_));
     out.numeric_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     out.outcome = COV_NOT_PD;
     return 0;
@@ -232,7 +219,6 @@ int Group::cov_finish(int arow, const std::vector<int> &row_of, const int *pairs
 
 int Group::cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz) {
   if (!nnz || cov_begin(X, ld, anchor) != 0) return -1;
-  CertState &c = *cert_;
   CovState &s = *cov_;
   CovResult r;
   const int ready = cov_setup(0, r);
@@ -247,11 +233,8 @@ int Group::cov_hessian(const double *X, int ld, int anchor, int *ptr, int *col, 
     fprintf(stderr, "[dpgo_amd] ERROR: covariance: the value array of the factorisation does not fit the device.\n");
     return -1;
   }
-  const int N = P0_;
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   cert_prepare(X, ld, nullptr);
-  launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, row_of[anchor], spd_numeric_values(s.F));
+  launch_cov_hessian_at(own_row(anchor));
   std::vector<double> v(s.A.col.size());
   HIP_CHECK(hipMemcpyAsync(v.data(), spd_numeric_values(s.F), sizeof(double) * v.size(), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
@@ -264,12 +247,11 @@ void Group::cov_csr_out(const std::vector<double> &v, int *ptr, int *col, double
   CertState &c = *cert_;
   CovState &s = *cov_;
   const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
-  std::vector<int> row_of(N), order;
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
+  std::vector<int> order;
   size_t e = 0;
   ptr[0] = 0;
   for (int g = 0; g < N; g++) {
-    const int p = row_of[g], b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
+    const int p = own_row(g), b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
     const size_t base = (size_t)DD * b0;
     auto pose_of = [&](int j) { return c.gid[s.bcol_h[b0 + j]]; };
     order.resize(nb);

@@ -27,21 +27,21 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hess.h"
+
 namespace dpgo {
 
 enum { COV_OK = 0, COV_NOT_PD = 1, COV_SKIPPED = 2 };
 
-// unknowns, fronts, levels, max_front and device_bytes (the numeric phase with its W / WT panels, the blocks of the selected
-// inversion, the maps) come from the symbolic analysis and are filled for SKIPPED too; symbolic_s: host seconds of the
-// analysis (0 after the first call of a group); numeric_ms: host milliseconds from the launch of k_cov_hessian to the
-// blocks of the inverse, ending in a synchronise.
-struct CovResult {
-  int outcome = COV_SKIPPED, unknowns = 0, fronts = 0, levels = 0, max_front = 0;
-  long long device_bytes = 0;
-  double pivot_min = 0, pivot_max = 0, stationarity = 0, symbolic_s = 0, numeric_ms = 0;
-  // numeric_ms taken apart -- factor_ms: k_cov_hessian and the factorisation up to its verdict, selinv_ms: the selected
+// The analysis' numbers (hess.h); device_bytes: the numeric phase with its W / WT panels, the blocks of the selected inversion,
+// the maps.  numeric_ms: host milliseconds from the launch of k_cov_hessian to the blocks of the inverse, ending in a
+// synchronise.
+struct CovResult : HessAnalysis {
+  int outcome = COV_SKIPPED;
+  double stationarity = 0, numeric_ms = 0;
+  // numeric_ms taken apart -- factor_ms (hess.h): k_cov_hessian and the factorisation up to its verdict, selinv_ms: the selected
   // inversion up to a synchronise -- and the useful flops of its products, sum over the fronts of 2 u^2 w + 2 u w^2 + w^3
-  double factor_ms = 0, selinv_ms = 0, selinv_flops = 0;
+  double selinv_ms = 0, selinv_flops = 0;
 };
 
 constexpr int cov_dof(int d) { return d + d * (d - 1) / 2; }

@@ -16,11 +16,13 @@ struct Group::CovState {
   std::vector<int> piv_front, piv_loc;   // per unknown: the front that eliminates it, its position among that front's pivots
   bool have_symbolic = false;
   double symbolic_s = 0;
-  long long bytes = 0;
+  // what the refusals count (hess.h: HessPart): the numeric phase with its W / WT panels and the block-column map, which the
+  // first call that is not refused leaves on the device; the blocks of the selected inversion
+  long long numeric_bytes = 0, selinv_bytes = 0;
+  HessPart numeric_part() const { return {numeric_bytes, F.numeric ? 0 : numeric_bytes}; }
   // the Newton polish (polish.cpp): the tangent gradient, the right-hand side / solution of a step, the unshifted diagonal of
-  // H -- dof doubles per own row each -- and what it counts for its refusal
+  // H -- dof doubles per own row each
   DevBuf<double> pol_g, pol_sol, pol_hdiag;
-  long long pol_bytes = 0;
   ~CovState() {
     spd_release_numeric(F);
     spd_release_device(F);

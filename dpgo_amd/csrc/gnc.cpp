@@ -66,7 +66,7 @@ int Group::gnc(const Graph &g, const double *X, int ld, const GncOptions &o, con
   PolishResult pr;
   {
     const RobustState &r0 = *rob_;
-    const int ready = polish_setup(max_bytes, pr, r0.bytes + r0.gnc_bytes(), robust_remain() + (r0.gnc_on_device ? 0 : r0.gnc_bytes()));
+    const int ready = polish_setup(max_bytes, pr, {r0.bytes + r0.gnc_bytes(), robust_remain() + (r0.gnc_on_device ? 0 : r0.gnc_bytes())});
     out.device_bytes = pr.device_bytes;
     out.symbolic_s = pr.symbolic_s;
     if (ready < 0) return -1;
@@ -80,9 +80,7 @@ int Group::gnc(const Graph &g, const double *X, int ld, const GncOptions &o, con
   CertState &c = *cert_;
   CovState &s = *cov_;
   RobustState &r = *rob_;
-  int arow = 0;
-  for (int p = 0; p < P0_; p++)
-    if (c.gid[p] == o.anchor) arow = p;
+  const int arow = own_row(o.anchor);
   const NodeMask all{all_bits(), nullptr};
   const size_t m = (size_t)r.plan.m;
   const int d = d_, L = edge_rec_doubles(d);
@@ -220,17 +218,9 @@ int Group::gnc_eval(const Graph &g, const double *X, int ld, int kind, double mu
                     double *s_rot, double *s_trans, double *w, double *sums) {
   if (!X || !s_rot || !s_trans || !w || !sums || !gnc_args_ok(kind, mu, barc2, "gnc eval")) return -1;
   if (robust_begin(g, X, ld, 0, 1.0, 0, 0, "gnc eval", robust_set) != 0) return -1;
-  {
-    const RobustState &r0 = *rob_;
-    const long long remain = robust_remain() + (r0.gnc_on_device ? 0 : r0.gnc_bytes());
-    if (remain > 0) {
-      size_t free_b = 0, total_b = 0;
-      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      if ((unsigned long long)remain > free_b / 2) {
-        fprintf(stderr, "[dpgo_amd] ERROR: gnc eval: the buffers do not fit the device.\n");
-        return -1;
-      }
-    }
+  if (!device_has_room(robust_remain() + (rob_->gnc_on_device ? 0 : rob_->gnc_bytes()))) {
+    fprintf(stderr, "[dpgo_amd] ERROR: gnc eval: the buffers do not fit the device.\n");
+    return -1;
   }
   robust_alloc();
   gnc_alloc();

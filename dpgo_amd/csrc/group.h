@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cmath>
 #include <functional>
+#include <initializer_list>
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -687,15 +688,31 @@ class Group {
   CovState *cov_ = nullptr;
   void cov_release();
   int cov_begin(const double *X, int ld, int anchor);
-  int cov_analyse(CovResult &out);                      // the pattern and the symbolic analysis (first call), the sizes
-  // 0: ready, 1: SKIPPED, -1: error.  extra / extra_remain: bytes the caller allocates behind the same refusal (robust.cpp) --
-  // all of them, and those still to be allocated
-  int cov_setup(long long max_bytes, CovResult &out, long long extra = 0, long long extra_remain = 0);
-  // likewise, for what polish allocates (polish.cpp)
-  int polish_setup(long long max_bytes, PolishResult &out, long long extra = 0, long long extra_remain = 0);
-  // what is behind the Hessian's launch in covariance: the factorisation, the selected inversion, the read-out (t0: the launch)
-  int cov_finish(int arow, const std::vector<int> &row_of, const int *pairs, int npairs, double *marginals, double *cross,
-                 CovResult &out, std::chrono::steady_clock::time_point t0);
+  int cov_analyse(HessAnalysis &out);   // the pattern and the symbolic analysis (first call), the sizes
+  // What every consumer of the factor shares (hess.cpp).  hess_reserve, the one refusal, behind cov_analyse: 0 ready (the
+  // numeric context set up on its first use), 1 SKIPPED, -1 error; device_bytes <- the sum of the parts.  hess_factor, the one
+  // verdict: write_H launched, the factorisation, the pivots, factor_ms: 0 factored, 1 NOT_PD (synchronised), -1 error;
+  // hess_refactor: its part from the factorisation to the pivots, which polish_loop's own loop shares
+  bool device_has_room(long long remain);
+  int hess_reserve(long long max_bytes, const char *who, std::initializer_list<HessPart> parts, HessAnalysis &out);
+  int hess_refactor(const char *who, HessAnalysis &out);
+  int hess_factor(const char *who, const std::function<void()> &write_H, HessAnalysis &out);
+  // the maps of the certificate's pattern (cert.cpp, behind cert_build_pattern): global pose -> unified own row; the block
+  // that holds (p, q), -1: none
+  int own_row(int global_pose) const;
+  int cert_block_of(int p, int q) const;
+  // the callers' refusals, each the analysis and its list of parts; extra: bytes the caller allocates behind the same refusal
+  // (robust.cpp, gnc.cpp).  cov_setup: with the blocks of the selected inversion (cov.cpp); polish_setup: with the vector solve
+  // and polish's vectors, which it allocates (polish.cpp)
+  int cov_setup(long long max_bytes, CovResult &out, HessPart extra = {0, 0});
+  int polish_setup(long long max_bytes, HessAnalysis &out, HessPart extra = {0, 0});
+  // the pair arguments of covariance, robust_covariance and pair_covariance: poses of the graph; edges of it (cov.cpp)
+  bool pairs_args_ok(const char *who, const int *pairs, int npairs) const;
+  bool pairs_are_edges(const char *who, const int *pairs, int npairs) const;
+  void launch_cov_hessian_at(int arow);   // k_cov_hessian on the certificate's M, Lambda, X into the factor's values
+  // covariance's tail: write_H and the factorisation (hess_factor), the selected inversion, the read-out
+  int cov_finish(const std::function<void()> &write_H, int arow, const int *pairs, int npairs, double *marginals, double *cross,
+                 CovResult &out);
   // a value array in the order of the certificate's / the covariance's pattern as CSR on global poses (cert_matrix, cov_hessian)
   void cert_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val);
   void cov_csr_out(const std::vector<double> &v, int *ptr, int *col, double *val);
@@ -715,19 +732,29 @@ class Group {
   long long robust_remain() const;
   void robust_alloc();
   void robust_eval(const double *Xdev, int loss, double loss_reg, bool with_rows, int fslot);
+  void robust_point(const double *X, int ld, int loss, double loss_reg, double *stationarity);   // null: no reduction, no wait
   void robust_hessian_launch(int arow, int curvature);
   void robust_summary(EdgeSummary *sum);
   // gnc.cpp: the buffers of the edge pass; the pass at a record array of the group (fslot as robust_eval), its summary read back
   void gnc_alloc();
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
   void gnc_summary(GncSummaryDev &sd);
-  // likewise (pairs.cpp); own_remain: those of own_bytes still to be allocated, as cov_setup's extra_remain (< 0: all of them)
-  int pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out, long long own_remain = -1);
+  // the refusal of the block solves with kb columns (pairs.cpp); own: the call's buffers
+  int pairs_setup(long long max_bytes, HessPart own, int kb, HessAnalysis &out);
   // the batches of a plan behind a factorisation: joint (device, zeroed by the caller) <- the blocks of the pairs (pairs.cpp)
-  int pairs_solve_joint(const PairsPlan &pl, const std::vector<int> &row_of, int npairs, const int *d_prow, double *d_joint,
-                        const char *who);
-  // a graph checked against the group; rec: its edge records in graph order, heads on unified own rows (robust.cpp; sens.cpp too)
-  int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec);
+  int pairs_solve_joint(const PairsPlan &pl, int npairs, const int *d_prow, double *d_joint, const char *who);
+  // a graph checked against the group and its pattern; rec: its edge records in graph order, heads on unified own rows; eb:
+  // the four blocks of every edge (robust.cpp; sens.cpp and rely.cpp too)
+  int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec, std::vector<int> *eb = nullptr);
+  // what sensitivity and robust_sensitivity share (sens.cpp): the upstream checked and the sizes (returns the batch array's row
+  // length, -1: error), and the batch loop, whose per-batch edge step is the caller's
+  struct SensBatch {
+    int b, c0, nc, kb;    // the batch, its first column, its columns, the row length of Xb
+    const double *Xb;     // the solved columns (device)
+  };
+  int sens_begin(const char *who, const double *upstream, int ldu, int k, SensResult &out);
+  int sens_batches(const char *who, int anchor, const double *upstream, int ldu, int k, double *adjoint,
+                   const std::function<void(const SensBatch &)> &edge, SensResult &out);
   bool star_ = false;
   double *coll_send_ = nullptr, *coll_gathered_ = nullptr;
   AllGatherFn coll_allgather_ = nullptr;

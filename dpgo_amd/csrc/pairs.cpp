@@ -1,5 +1,5 @@
-// Host side of the joint pair covariances (pairs.h): the column plan, the refusal, and the loop -- H written on the device
-// (k_cov_hessian), factored (spd_refactor_device), the unit columns of the poses asked for solved batch by batch
+// Host side of the joint pair covariances (pairs.h): the column plan, the parts of the refusal, and the loop -- H written on the
+// device (k_cov_hessian) and factored (hess.cpp: hess_factor), the unit columns of the poses asked for solved batch by batch
 // (spd_msolve_device), the blocks gathered, the relative covariance and the gate of every pair.  The matrix is the
 // covariance's (cov.cpp): its pattern, its symbolic analysis and its numeric context are shared.  The optimiser's state is not
 // touched (cert_begin).
@@ -31,47 +31,21 @@ PairsPlan pairs_plan(int dof, int anchor, const int *pairs, int npairs) {
   return pl;
 }
 
-// The analysis (first call), the prediction, the refusal, the numeric context (first call that is not refused): polish_setup's
-// rule on the bytes of the numeric phase, the block solve and this call's own buffers -- not on the blocks of the selected
-// inversion.
-int Group::pairs_setup(long long max_bytes, long long own_bytes, int kb, PairsResult &out, long long own_remain) {
-  CovResult cr;
-  if (cov_analyse(cr) != 0) return -1;
-  CertState &c = *cert_;
-  CovState &s = *cov_;
-  const long long nblk = c.bptr_h[P0_];
-  const long long numeric = (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + 4ll * nblk;
-  const long long solve = (long long)spd_msolve_bytes(s.F, kb);
-  out.unknowns = cr.unknowns;
-  out.fronts = cr.fronts;
-  out.levels = cr.levels;
-  out.max_front = cr.max_front;
-  out.symbolic_s = cr.symbolic_s;
-  out.device_bytes = numeric + solve + own_bytes;
-  out.outcome = PAIRS_SKIPPED;
-  if (max_bytes > 0 && out.device_bytes > max_bytes) return 1;
-  // against the free memory: the numeric phase only where no earlier call has left it (the solve's buffers are counted
-  // whether an earlier call has left them or not)
-  const long long remain = (s.F.numeric ? 0 : numeric) + solve + (own_remain < 0 ? own_bytes : own_remain);
-  size_t free_b = 0, total_b = 0;
-  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  if ((unsigned long long)remain > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
-  if (!s.F.numeric) {
-    s.bcol.upload(s.bcol_h);
-    if (spd_prepare_device(s.A, s.F) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: pair_covariance: the device state of the factorisation could not be set up.\n");
-      return -1;
-    }
-  }
-  return 0;
+// The analysis and the refusal of the block solves (pair_covariance, sensitivity, robust_sensitivity): the numeric phase, the
+// block solve of kb columns -- counted as still to allocate whether an earlier call has left its buffers or not -- and the
+// call's own buffers; not the blocks of the selected inversion.
+int Group::pairs_setup(long long max_bytes, HessPart own, int kb, HessAnalysis &out) {
+  if (cov_analyse(out) != 0) return -1;
+  const long long solve = (long long)spd_msolve_bytes(cov_->F, kb);
+  return hess_reserve(max_bytes, "pair_covariance", {cov_->numeric_part(), {solve, solve}, own}, out);
 }
 
 // The batches of a column plan behind a factorisation that succeeded: per batch the unit right-hand sides, the block solve and the
 // gather of the blocks whose columns it holds.  d_prow (2 npairs unified own rows) and d_joint (npairs x 3 dof^2, zeroed by the
 // caller: the anchor's blocks) are the caller's, on the device, where joint stays; returns behind a synchronise.
-int Group::pairs_solve_joint(const PairsPlan &pl, const std::vector<int> &row_of, int npairs, const int *d_prow, double *d_joint,
-                             const char *who) {
+int Group::pairs_solve_joint(const PairsPlan &pl, int npairs, const int *d_prow, double *d_joint, const char *who) {
   CovState &s = *cov_;
+  const std::vector<int> &row_of = cert_->row_of;
   const int dof = cov_dof(d_);
   const long long n = (long long)dof * P0_;
   std::vector<int> col_unknown((size_t)std::max(pl.columns, 1), 0);
@@ -108,11 +82,7 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
   CertState &c = *cert_;
   CovState &s = *cov_;
   const int d = d_, dof = cov_dof(d), DD = dof * dof, N = P0_, ncand = d * d + d + 2, ngate = 2 + dof;
-  for (int k = 0; k < 2 * npairs; k++)
-    if (pairs[k] < 0 || pairs[k] >= N) {
-      fprintf(stderr, "[dpgo_amd] ERROR: pair_covariance: pair %d names a pose that is not in the graph.\n", k / 2);
-      return -1;
-    }
+  if (!pairs_args_ok("pair_covariance", pairs, npairs)) return -1;
   if (candidates)
     for (int k = 0; k < npairs; k++) {
       const double kappa = candidates[(size_t)k * ncand + d * d + d], tau = candidates[(size_t)k * ncand + d * d + d + 1];
@@ -127,7 +97,7 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
   const long long n = (long long)dof * N;
   const long long own = 8ll * (n * pl.kb + (long long)npairs * (4 * DD + (candidates ? ncand + ngate : 0))) +
                         4ll * (4ll * npairs + pl.columns);
-  const int ready = pairs_setup(max_bytes, own, pl.kb, out);
+  const int ready = pairs_setup(max_bytes, {own, own}, pl.kb, out);
   if (ready < 0) return -1;
   for (int b = 0; b < pl.batches; b++) {
     const int nc = std::min(PAIRS_BATCH, pl.columns - b * PAIRS_BATCH);
@@ -139,33 +109,16 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
   std::fill(joint, joint + (size_t)npairs * 3 * DD, 0.0);
   std::fill(rel, rel + (size_t)npairs * DD, 0.0);
   if (candidates) std::fill(gate, gate + (size_t)npairs * ngate, 0.0);
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   typedef std::chrono::steady_clock Clock;
   auto ms_since = [](Clock::time_point t) { return 1e3 * std::chrono::duration<double>(Clock::now() - t).count(); };
+  const int rc = hess_factor("pair_covariance", [&] { launch_cov_hessian_at(own_row(anchor)); }, out);
+  if (rc < 0) return -1;
+  out.outcome = rc != 0 ? PAIRS_NOT_PD : PAIRS_OK;
+  if (rc != 0 || npairs == 0) return 0;
   auto t0 = Clock::now();
-  launch_cov_hessian(d, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, row_of[anchor], spd_numeric_values(s.F));
-  const int rc = spd_refactor_device(s.F, st_, false);   // (returns with the verdict read)
-  if (rc != 0 && !s.F.not_pd) {
-    fprintf(stderr, "[dpgo_amd] ERROR: pair_covariance: the factorisation failed on the device.\n");
-    return -1;
-  }
-  out.pivot_max = s.F.pivot_max;
-  out.pivot_min = s.F.pivot_max > 0 ? s.F.pivot_min : 0.0;
-  out.factor_ms = ms_since(t0);
-  if (rc != 0) {
-    HIP_CHECK(hipStreamSynchronize(st_));
-    out.outcome = PAIRS_NOT_PD;
-    return 0;
-  }
-  if (npairs == 0) {
-    out.outcome = PAIRS_OK;
-    return 0;
-  }
-  t0 = Clock::now();
   // this call's buffers: the pairs' rows, the outputs (the batch and the plan's lists: pairs_solve_joint)
   std::vector<int> prow((size_t)2 * npairs);
-  for (int k = 0; k < 2 * npairs; k++) prow[k] = row_of[pairs[k]];
+  for (int k = 0; k < 2 * npairs; k++) prow[k] = own_row(pairs[k]);
   DevBuf<int> d_prow;
   DevBuf<double> d_joint, d_rel, d_gate, d_cand;
   d_prow.upload(prow);
@@ -175,7 +128,7 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
     d_cand.upload(std::vector<double>(candidates, candidates + (size_t)npairs * ncand));
     d_gate.alloc((size_t)npairs * ngate);
   }
-  if (pairs_solve_joint(pl, row_of, npairs, d_prow.p, d_joint.p, "pair_covariance") != 0) return -1;
+  if (pairs_solve_joint(pl, npairs, d_prow.p, d_joint.p, "pair_covariance") != 0) return -1;
   out.solve_ms = ms_since(t0);
   t0 = Clock::now();
   launch_pairs_gate(d, st_, npairs, d_prow.p, d_joint.p, c.X.p, candidates ? d_cand.p : nullptr, d_rel.p, candidates ? d_gate.p : nullptr);
@@ -191,17 +144,12 @@ int Group::pair_covariance(const double *X, int ld, int anchor, long long max_by
 
 int Group::pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms) {
   if (cov_begin(X, ld, anchor) != 0) return -1;
-  CertState &c = *cert_;
   CovState &s = *cov_;
-  const int dof = cov_dof(d_), N = P0_;
   PairsResult r;
-  const long long n = (long long)dof * N;
-  if (pairs_setup(0, 8 * n, 16, r) != 0) return -1;
+  const long long n = (long long)cov_dof(d_) * P0_;
+  if (pairs_setup(0, {8 * n, 8 * n}, 16, r) != 0) return -1;
   cert_prepare(X, ld, nullptr);
-  int arow = 0;
-  for (int p = 0; p < N; p++)
-    if (c.gid[p] == anchor) arow = p;
-  launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
+  launch_cov_hessian_at(own_row(anchor));
   if (spd_refactor_device(s.F, st_, false) != 0) return -1;
   DevBuf<double> x;
   x.alloc((size_t)n);

@@ -27,6 +27,8 @@
 
 #include <vector>
 
+#include "hess.h"
+
 namespace dpgo {
 
 enum { PAIRS_OK = 0, PAIRS_NOT_PD = 1, PAIRS_SKIPPED = 2 };
@@ -38,10 +40,9 @@ constexpr int PAIRS_BATCH = 64;   // columns per spd_msolve_device call
 // unit columns (dof per distinct non-anchor pose), batches: spd_msolve_device calls.  factor_ms: k_cov_hessian and the
 // factorisation up to its verdict; solve_ms: the batches (right-hand sides, solves, gathers) up to a synchronise; gate_ms:
 // k_pairs_gate and the copies to the host.
-struct PairsResult {
-  int outcome = PAIRS_SKIPPED, unknowns = 0, fronts = 0, levels = 0, max_front = 0, columns = 0, batches = 0;
-  long long device_bytes = 0;
-  double pivot_min = 0, pivot_max = 0, stationarity = 0, symbolic_s = 0, factor_ms = 0, solve_ms = 0, gate_ms = 0;
+struct PairsResult : HessAnalysis {
+  int outcome = PAIRS_SKIPPED, columns = 0, batches = 0;
+  double stationarity = 0, solve_ms = 0, gate_ms = 0;
   // what the batches cost by count: the useful flops of the two sweeps, sum over the fronts of 4 (w + u) w times the columns of
   // every batch rounded up to 16, and the factor bytes they stream, 16 sum (w + u) w per batch (W forward, WT backward)
   double solve_flops = 0, factor_bytes = 0;

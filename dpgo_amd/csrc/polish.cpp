@@ -1,5 +1,5 @@
-// Host side of the Newton polish (polish.h): the refusal, and the loop -- the gradient, the Hessian and its shift written on the
-// device, spd_refactor_device, spd_vsolve_device, the retraction, one product with M for F(Z), and a handful of scalars read
+// Host side of the Newton polish (polish.h): the parts of the refusal, and the loop -- the gradient, the Hessian and its shift
+// written on the device, the factorisation (hess.cpp: hess_refactor), spd_vsolve_device, the retraction, one product with M for F(Z), and a handful of scalars read
 // back per try through the group's read-back flag.  The matrix is the covariance's (cov.cpp): its pattern, its symbolic
 // analysis and its numeric context are shared.  The optimiser's state is not touched (cert_begin).  The loop itself is
 // polish_loop: what differs between the trivial loss and the robust objective (robust.cpp) is launched by three hooks.
@@ -15,44 +15,17 @@
 
 namespace dpgo {
 
-// The analysis (first call), the prediction, the refusal, what polish allocates (first call that is not refused): cov_setup's
-// rule on the bytes of the numeric phase, the vector solve and the three vectors -- not on the blocks of the selected inversion.
-int Group::polish_setup(long long max_bytes, PolishResult &out, long long extra, long long extra_remain) {
-  CovResult cr;
-  if (cov_analyse(cr) != 0) return -1;
-  CertState &c = *cert_;
+// The analysis and the refusal of polish, robust_polish and gnc, then what polish allocates (first call that is not refused):
+// the numeric phase, the vector solve with the three vectors -- still to allocate where no earlier polish has left them -- and
+// the caller's extra bytes (robust.cpp, gnc.cpp); not the blocks of the selected inversion.
+int Group::polish_setup(long long max_bytes, HessAnalysis &out, HessPart extra) {
+  if (cov_analyse(out) != 0) return -1;
   CovState &s = *cov_;
-  const long long n = s.A.n, nblk = c.bptr_h[P0_];
-  s.pol_bytes = (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + (long long)spd_vsolve_bytes(s.F) + 4ll * nblk + 3ll * 8ll * n;
-  out.unknowns = cr.unknowns;
-  out.fronts = cr.fronts;
-  out.levels = cr.levels;
-  out.max_front = cr.max_front;
-  out.device_bytes = s.pol_bytes + extra;
-  out.symbolic_s = cr.symbolic_s;
-  out.outcome = POLISH_SKIPPED;
-  if (max_bytes > 0 && s.pol_bytes + extra > max_bytes) return 1;
-  // against the free memory only what is still to be allocated counts: a covariance call may have left the numeric phase
-  // and the block-column map, an earlier polish everything
-  long long remain = extra_remain;
-  if (!s.F.numeric) remain += (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + 4ll * nblk;
-  if (!s.pol_g.p) remain += (long long)spd_vsolve_bytes(s.F) + 3ll * 8ll * n;
-  if (remain > 0) {
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    if ((unsigned long long)remain > free_b / 2) return 1;   // (nothing that cannot fit is asked of a shared device)
-  }
-  if (!s.F.numeric) {
-    s.bcol.upload(s.bcol_h);
-    if (spd_prepare_device(s.A, s.F) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: polish: the device state of the factorisation could not be set up.\n");
-      return -1;
-    }
-  }
-  if (!s.pol_g.p) {
+  const long long n = s.A.n, vectors = (long long)spd_vsolve_bytes(s.F) + 3ll * 8ll * n;
+  const int ready = hess_reserve(max_bytes, "polish", {s.numeric_part(), {vectors, s.pol_g.p ? 0 : vectors}, extra}, out);
+  if (ready == 0 && !s.pol_g.p)
     for (DevBuf<double> *b : {&s.pol_g, &s.pol_sol, &s.pol_hdiag}) b->alloc((size_t)std::max<long long>(n, 1));
-  }
-  return 0;
+  return ready;
 }
 
 int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout, int ldout,
@@ -70,10 +43,7 @@ int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, l
   if (ready != 0) return 0;   // SKIPPED, with what the analysis predicts
   CertState &c = *cert_;
   CovState &s = *cov_;
-  const int N = P0_;
-  int arow = 0;
-  for (int p = 0; p < N; p++)
-    if (c.gid[p] == anchor) arow = p;
+  const int arow = own_row(anchor);
   const NodeMask all{all_bits(), nullptr};
   PolishHooks hooks;
   hooks.point = [&] {
@@ -81,9 +51,7 @@ int Group::polish(const double *X, int ld, int anchor, const PolishOptions &o, l
     launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
     launch_polish_grad(lc(all), c.X.p, c.MX.p, arow, s.pol_g.p, 0, 1, c.partials.p);
   };
-  hooks.hessian = [&] {
-    launch_cov_hessian(d_, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
-  };
+  hooks.hessian = [&] { launch_cov_hessian_at(arow); };
   hooks.trial = [&] {
     cert_apply_M(c.V.p, c.SV.p);
     launch_polish_grad(lc(all), c.V.p, c.SV.p, arow, nullptr, -1, 2, c.partials.p);
@@ -141,15 +109,10 @@ int Group::polish_loop(const double *X, int ld, int arow, const PolishOptions &o
       tries++;
       t0 = Clock::now();
       if (t > 0) launch_polish_shift(lc(all), c.bptr.p, c.diag_pose.p, arow, mu, false, s.pol_hdiag.p, spd_numeric_values(s.F), 2, c.partials.p);
-      const int rc = spd_refactor_device(s.F, st_, false);   // (returns with the verdict read)
+      const int rc = hess_refactor("polish", out);   // (the shift sits between the write and the factorisation: no hess_factor)
       out.factor_ms += ms_since(t0);
       out.factorisations++;
-      if (rc != 0 && !s.F.not_pd) {
-        fprintf(stderr, "[dpgo_amd] ERROR: polish: the factorisation failed on the device.\n");
-        return -1;
-      }
-      out.pivot_max = s.F.pivot_max;
-      out.pivot_min = s.F.pivot_max > 0 ? s.F.pivot_min : 0.0;
+      if (rc < 0) return -1;
       if (rc != 0) {
         if (mu == 0) out.indefinite++;
         mu = std::max(10 * mu, 1e-3 * hmax);

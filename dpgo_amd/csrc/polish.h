@@ -36,6 +36,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hess.h"
 #include "kernels.h"
 
 namespace dpgo {
@@ -52,12 +53,10 @@ struct PolishOptions {
 // SKIPPED too.  total_ms: host milliseconds of the loop; factor_ms: k_cov_hessian and the first shift from their launch
 // (behind a synchronise) to the read-back, the later shifts and every factorisation up to its verdict; solve_ms: the vector
 // solves with the retraction, the product and the read-back behind them; other_ms: the rest.
-struct PolishResult {
+struct PolishResult : HessAnalysis {
   int outcome = POLISH_SKIPPED, steps = 0, factorisations = 0, indefinite = 0;
-  double F_initial = 0, F_final = 0, grad_initial = 0, grad_final = 0, hmax = 0, mu_final = 0, pivot_min = 0, pivot_max = 0;
-  int unknowns = 0, fronts = 0, levels = 0, max_front = 0;
-  long long device_bytes = 0;
-  double symbolic_s = 0, total_ms = 0, factor_ms = 0, solve_ms = 0, other_ms = 0;
+  double F_initial = 0, F_final = 0, grad_initial = 0, grad_final = 0, hmax = 0, mu_final = 0;
+  double total_ms = 0, solve_ms = 0, other_ms = 0;
 };
 
 constexpr int POLISH_LOG_COLS = 5;   // per iteration k: F0, |g|, mu at entry, rho of the accepted try, tries

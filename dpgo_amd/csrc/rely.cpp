@@ -1,5 +1,5 @@
 // Host side of the per-edge reliability (rely.h): the graph against the group, the listed edges, the two predictions and the
-// refusal, and the call -- H written on the device (k_cov_hessian), factored (spd_refactor_device), the three blocks of every
+// refusal, and the call -- H written on the device (k_cov_hessian) and factored (hess.cpp: hess_factor), the three blocks of every
 // listed edge gathered out of the selected inversion (spd_selinv_device, k_rely_gather) or solved for batch by batch
 // (pairs.cpp: pairs_solve_joint), the relative covariance and the residual of every edge (k_pairs_gate), its record
 // (k_rely_edge).  The matrix, its symbolic analysis and its numeric context are the covariance's (cov.cpp), the edge records
@@ -34,21 +34,8 @@ int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor,
   std::vector<double> rec;
   if (graph_records_own(g, "edge_reliability", rec) != 0) return -1;
   CertState &c = *cert_;
-  const int d = d_, dof = cov_dof(d), DD = dof * dof, N = P0_, m = (int)g.all.size(), L = edge_rec_doubles(d), B = B_, BB = B * B;
+  const int d = d_, dof = cov_dof(d), DD = dof * dof, N = P0_, m = (int)g.all.size(), L = edge_rec_doubles(d);
   const int NC = d * d + d + 2, NG = 2 + dof, W = rely_width(d), NL = rely_map_ints(dof);
-  for (int e = 0; e < m; e++) {   // every edge a block of the group's pattern: robust_begin's rule
-    int i, j;
-    bool inter;
-    edge_head(&rec[(size_t)e * L], i, j, inter);
-    const int b0 = c.bptr_h[i], nb = c.bptr_h[i + 1] - b0;
-    bool found = false;
-    for (int b = 0; b < nb && !found; b++) found = c.A.col[(size_t)BB * b0 + (size_t)b * B] / B == j;
-    if (!found) {
-      fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: edge %d (%d, %d) is no block of the group's pattern.\n", e, g.all[e].ipose,
-              g.all[e].jpose);
-      return -1;
-    }
-  }
   const int nl = edges ? nedges : m;
   for (int k = 0; k < nl; k++)
     if (edges && (edges[k] < 0 || edges[k] >= m)) {
@@ -77,75 +64,48 @@ int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor,
     cand.insert(cand.end(), q + 2, q + 2 + NC);
   }
   const int nu = (int)live.size();
-  // ---- the two predictions and the refusal (cov.cpp: cov_setup, pairs.cpp: pairs_setup, with this call's buffers) ----
-  CovResult cr;
-  if (cov_analyse(cr) != 0) return -1;
+  // ---- the two predictions and the refusal: either method's parts, with this call's buffers ----
+  if (cov_analyse(out) != 0) return -1;
   CovState &s = *cov_;
   const PairsPlan pl = pairs_plan(dof, anchor, pairs.data(), nu);
-  const long long n = (long long)dof * N, nblk = c.bptr_h[N];
-  const long long numeric = (long long)spd_numeric_bytes(s.F, (long long)s.A.col.size()) + 4ll * nblk;
-  const long long selinv = (long long)spd_selinv_bytes(s.F), solve = (long long)spd_msolve_bytes(s.F, pl.kb);
+  const long long n = (long long)dof * N;
+  const long long selinv = s.selinv_bytes, solve = (long long)spd_msolve_bytes(s.F, pl.kb);
   const long long common = 8ll * nu * (4 * DD + NC + NG + W) + 4ll * 2 * nu;
   const long long own_selinv = common + 8ll * 3 * nu + 4ll * NL * nu;
   const long long own_solve = common + 8ll * n * pl.kb + 4ll * (2ll * nu + pl.columns);
-  out.unknowns = cr.unknowns;
-  out.fronts = cr.fronts;
-  out.levels = cr.levels;
-  out.max_front = cr.max_front;
-  out.symbolic_s = cr.symbolic_s;
   out.columns = pl.columns;
   out.batches = pl.batches;
-  out.device_bytes_selinv = numeric + selinv + own_selinv;
-  out.device_bytes_solve = numeric + solve + own_solve;
-  size_t free_b = 0, total_b = 0;
-  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  auto refused = [&](int meth) {   // (nothing that cannot fit is asked of a shared device)
-    const long long bytes = meth == RELY_SELINV ? out.device_bytes_selinv : out.device_bytes_solve;
-    if (max_bytes > 0 && bytes > max_bytes) return true;
-    const long long remain = (s.F.numeric ? 0 : numeric) + (meth == RELY_SELINV ? (spd_selinv_values(s.F) ? 0 : selinv) + own_selinv
-                                                                                : solve + own_solve);
-    return (unsigned long long)remain > free_b / 2;
+  out.device_bytes_selinv = s.numeric_bytes + selinv + own_selinv;
+  out.device_bytes_solve = s.numeric_bytes + solve + own_solve;
+  // SELINV: the blocks of the selected inversion are still to allocate where no earlier call has left them; SOLVE: the block
+  // solve's buffers whether an earlier call has left them or not (pairs_setup)
+  auto reserve = [&](int meth) {
+    if (meth == RELY_SELINV)
+      return hess_reserve(max_bytes, "edge_reliability",
+                          {s.numeric_part(), {selinv, spd_selinv_values(s.F) ? 0 : selinv}, {own_selinv, own_selinv}}, out);
+    return hess_reserve(max_bytes, "edge_reliability", {s.numeric_part(), {solve, solve}, {own_solve, own_solve}}, out);
   };
-  int use = method;
-  bool skip;
-  if (method == RELY_AUTO) {
-    use = !refused(RELY_SELINV) ? RELY_SELINV : RELY_SOLVE;
-    skip = use == RELY_SOLVE && refused(RELY_SOLVE);
-    if (skip) use = out.device_bytes_selinv <= out.device_bytes_solve ? RELY_SELINV : RELY_SOLVE;
-  } else {
-    skip = refused(method);
+  // AUTO: SELINV where it is not refused, SOLVE where that is not; both refused: the smaller prediction is reported
+  int use = method == RELY_AUTO ? RELY_SELINV : method, ready = reserve(use);
+  if (method == RELY_AUTO && ready == 1) {
+    use = RELY_SOLVE;
+    ready = reserve(use);
+    if (ready == 1) use = out.device_bytes_selinv <= out.device_bytes_solve ? RELY_SELINV : RELY_SOLVE;
   }
-  out.method_used = skip ? method : use;
+  if (ready < 0) return -1;
+  out.method_used = ready != 0 ? method : use;
   out.device_bytes = use == RELY_SELINV ? out.device_bytes_selinv : out.device_bytes_solve;
-  if (!skip && !s.F.numeric) {
-    s.bcol.upload(s.bcol_h);
-    if (spd_prepare_device(s.A, s.F) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: the device state of the factorisation could not be set up.\n");
-      return -1;
-    }
-  }
   cert_prepare(X, ld, &out.stationarity);
-  if (skip) return 0;   // SKIPPED, with what the analysis and the sizes predict
+  if (ready != 0) return 0;   // SKIPPED, with what the analysis and the sizes predict
   std::fill(rec_out, rec_out + (size_t)nl * W, 0.0);
   if (rel) std::fill(rel, rel + (size_t)nl * DD, 0.0);
   if (joint) std::fill(joint, joint + (size_t)nl * 3 * DD, 0.0);
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
-  const int arow = row_of[anchor];
+  const int arow = own_row(anchor);
   typedef std::chrono::steady_clock Clock;
   auto ms_since = [](Clock::time_point t) { return 1e3 * std::chrono::duration<double>(Clock::now() - t).count(); };
-  auto t0 = Clock::now();
-  launch_cov_hessian(d, st_, N, c.bptr.p, s.bcol.p, c.Mval.p, c.Lam.p, c.X.p, arow, spd_numeric_values(s.F));
-  const int rc = spd_refactor_device(s.F, st_, false);   // (returns with the verdict read)
-  if (rc != 0 && !s.F.not_pd) {
-    fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: the factorisation failed on the device.\n");
-    return -1;
-  }
-  out.pivot_max = s.F.pivot_max;
-  out.pivot_min = s.F.pivot_max > 0 ? s.F.pivot_min : 0.0;
-  out.factor_ms = ms_since(t0);
+  const int rc = hess_factor("edge_reliability", [&] { launch_cov_hessian_at(arow); }, out);
+  if (rc < 0) return -1;
   if (rc != 0) {
-    HIP_CHECK(hipStreamSynchronize(st_));
     out.outcome = RELY_NOT_PD;
     return 0;
   }
@@ -154,7 +114,7 @@ int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor,
     else rec_out[(size_t)k * W + 1] = (double)RELY_FLAG_UNWEIGHTED;
   }
   if (nu > 0) {
-    t0 = Clock::now();
+    auto t0 = Clock::now();
     DevBuf<int> d_prow;
     DevBuf<double> d_joint, d_rel, d_gate, d_cand, d_rec;
     d_prow.upload(prow);
@@ -223,7 +183,7 @@ int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor,
       launch_rely_gather(st_, dof, nu, d_off.p, d_loc.p, spd_selinv_values(s.F), d_joint.p);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(st_));
-    } else if (pairs_solve_joint(pl, row_of, nu, d_prow.p, d_joint.p, "edge_reliability") != 0) {
+    } else if (pairs_solve_joint(pl, nu, d_prow.p, d_joint.p, "edge_reliability") != 0) {
       return -1;
     }
     out.inverse_ms = ms_since(t0);

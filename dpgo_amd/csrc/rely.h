@@ -36,6 +36,8 @@
 
 #include <cstdint>
 
+#include "hess.h"
+
 namespace dpgo {
 
 struct Graph;
@@ -52,11 +54,10 @@ enum { RELY_AUTO = 0, RELY_SELINV = 1, RELY_SOLVE = 2 };
 // list order on the host, flag-2 edges left out.  factor_ms: k_cov_hessian and the factorisation up to its verdict;
 // inverse_ms: the selected inversion and k_rely_gather, or the batches, up to a synchronise; edge_ms: k_pairs_gate, k_rely_edge
 // and the copies to the host.
-struct RelyResult {
-  int outcome = RELY_SKIPPED, method_used = RELY_AUTO, unknowns = 0, fronts = 0, levels = 0, max_front = 0, edges = 0, flagged = 0,
-      unweighted = 0, columns = 0, batches = 0;
-  long long device_bytes = 0, device_bytes_selinv = 0, device_bytes_solve = 0;
-  double redundancy_sum = 0, pivot_min = 0, pivot_max = 0, stationarity = 0, symbolic_s = 0, factor_ms = 0, inverse_ms = 0, edge_ms = 0;
+struct RelyResult : HessAnalysis {
+  int outcome = RELY_SKIPPED, method_used = RELY_AUTO, edges = 0, flagged = 0, unweighted = 0, columns = 0, batches = 0;
+  long long device_bytes_selinv = 0, device_bytes_solve = 0;
+  double redundancy_sum = 0, stationarity = 0, inverse_ms = 0, edge_ms = 0;
 };
 
 constexpr int rely_width(int d) { return 6 + 2 * (d + d * (d - 1) / 2); }

@@ -1,6 +1,6 @@
-// Host side of the robust objective (robust.h): the lists of a (group, graph), the refusal, and the calls that put the robust
-// F, M_w X and the true Hessian under the polish's loop (polish.cpp: polish_loop) and the covariance's tail (cov.cpp:
-// cov_finish).  The optimiser's state is not touched (cert_begin); the certificate's M is never written.
+// Host side of the robust objective (robust.h): the lists of a (group, graph), its part of the refusals, the robust point, and
+// the calls that put the robust F, M_w X and the true Hessian under the polish's loop (polish.cpp: polish_loop) and the
+// covariance's tail (cov.cpp: cov_finish).  The optimiser's state is not touched (cert_begin); the certificate's M is never written.
 #include "robust.h"
 
 #include <algorithm>
@@ -38,8 +38,9 @@ static bool robust_args_ok(int loss, double loss_reg, int curvature, const char 
 }
 
 // The graph against the group (behind cert_begin): its dimension, its poses, and -- with the certificate's pattern built -- its
-// edge records in graph order with the heads on unified own rows.  Shared with sens.cpp.
-int Group::graph_records_own(const Graph &g, const char *who, std::vector<double> &rec) {
+// edge records in graph order with the heads on unified own rows, every edge a block of the group's pattern.  eb (optional): per
+// edge its blocks (i, i), (i, j), (j, i), (j, j).  Shared with sens.cpp and rely.cpp.
+int Group::graph_records_own(const Graph &g, const char *who, std::vector<double> &rec, std::vector<int> *eb) {
   const int N = P0_, m = (int)g.all.size();
   if (g.d != d_ || g.num_poses != N || m == 0) {
     fprintf(stderr, "[dpgo_amd] ERROR: %s: the graph is not one of the group's poses (d %d / %d, poses %d / %d).\n", who, g.d, d_,
@@ -51,18 +52,24 @@ int Group::graph_records_own(const Graph &g, const char *who, std::vector<double
       fprintf(stderr, "[dpgo_amd] ERROR: %s: an edge names a pose outside the graph, or one pose twice.\n", who);
       return -1;
     }
-  CertState &c = *cert_;
   cert_build_pattern();
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
   const int L = edge_rec_doubles(d_);
   edge_records(g, rec);
+  if (eb) eb->resize(4 * (size_t)m);
   for (int e = 0; e < m; e++) {   // the heads on unified own rows
     int head[4];
     std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
-    head[0] = row_of[head[0]];
-    head[1] = row_of[head[1]];
+    const int pq[2] = {head[0] = own_row(head[0]), head[1] = own_row(head[1])};
     std::memcpy(&rec[(size_t)e * L], head, sizeof(head));
+    for (int ab = 0; ab < 4; ab++) {
+      const int k = cert_block_of(pq[ab / 2], pq[ab % 2]);
+      if (k < 0) {
+        fprintf(stderr, "[dpgo_amd] ERROR: %s: edge %d (%d, %d) is no block of the group's pattern.\n", who, e, g.all[e].ipose,
+                g.all[e].jpose);
+        return -1;
+      }
+      if (eb) (*eb)[4 * (size_t)e + ab] = k;
+    }
   }
   return 0;
 }
@@ -75,7 +82,8 @@ int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, doubl
   if (!robust_args_ok(loss, loss_reg, curvature, who)) return -1;
   if (cov_begin(X, ld, anchor) != 0) return -1;
   std::vector<double> rec;
-  if (graph_records_own(g, who, rec) != 0) return -1;
+  std::vector<int> eb;   // per edge: its blocks (i, i), (i, j), (j, i), (j, j)
+  if (graph_records_own(g, who, rec, &eb) != 0) return -1;
   const int N = P0_, m = (int)g.all.size(), L = edge_rec_doubles(d_);
   CertState &c = *cert_;
   if (robust_set)
@@ -92,34 +100,15 @@ int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, doubl
   pl.N = N;
   pl.m = m;
   pl.nb = (m + EDGE_BLOCK - 1) / EDGE_BLOCK;
-  // the block of the pattern that holds (p, q): the columns of a block row are the unified own rows, ascending
   const size_t nblk = c.bptr_h[N];
-  const int B = B_, BB = B * B;
-  auto block_of = [&](int p, int q) -> int {
-    const int b0 = c.bptr_h[p], nb = c.bptr_h[p + 1] - b0;
-    for (int j = 0; j < nb; j++)
-      if (c.A.col[(size_t)BB * b0 + (size_t)j * B] / B == q) return b0 + j;
-    return -1;
-  };
+  const int BB = B_ * B_;
   std::vector<int> ninc(N + 1, 0), nbl(nblk + 1, 0);
-  std::vector<int> eb(4 * (size_t)m);   // per edge: its blocks (i, i), (i, j), (j, i), (j, j)
   for (int e = 0; e < m; e++) {
     int head[4];
     std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
-    const int pq[2] = {head[0], head[1]};
-    for (int a = 0; a < 2; a++)
-      for (int b = 0; b < 2; b++) {
-        const int k = block_of(pq[a], pq[b]);
-        if (k < 0) {
-          fprintf(stderr, "[dpgo_amd] ERROR: %s: edge %d (%d, %d) is no block of the group's pattern.\n", who, e, g.all[e].ipose,
-                  g.all[e].jpose);
-          return -1;
-        }
-        eb[4 * (size_t)e + 2 * a + b] = k;
-        nbl[k + 1]++;
-      }
-    ninc[pq[0] + 1]++;
-    ninc[pq[1] + 1]++;
+    for (int ab = 0; ab < 4; ab++) nbl[eb[4 * (size_t)e + ab] + 1]++;
+    ninc[head[0] + 1]++;
+    ninc[head[1] + 1]++;
   }
   for (int p = 0; p < N; p++) ninc[p + 1] += ninc[p];
   for (size_t k = 0; k < nblk; k++) nbl[k + 1] += nbl[k];
@@ -178,6 +167,22 @@ void Group::robust_eval(const double *Xdev, int loss, double loss_reg, bool with
                      nseg);
 }
 
+// The robust point: X uploaded, the edge pass with its rows, M_w X gathered, Lambda_w; with `stationarity` also |S_w X|_F, read
+// back (a wait).
+void Group::robust_point(const double *X, int ld, int loss, double loss_reg, double *stationarity) {
+  CertState &c = *cert_;
+  RobustState &r = *rob_;
+  const NodeMask all{all_bits(), nullptr};
+  cert_upload(X, ld, d_, c.X.p);
+  robust_eval(c.X.p, loss, loss_reg, true, -1);
+  launch_robust_gather(lc(all), r.inc_ptr.p, r.inc.p, r.out.p + 3 * (size_t)r.plan.m, r.rows.p, c.MX.p);
+  launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
+  if (!stationarity) return;
+  launch_cert_reduce(st_, T_, 1, c.partials.p, c.h_sums, sched_.flag());
+  wait_flag(sched_.last_seq());
+  *stationarity = std::sqrt(c.h_sums[0]);
+}
+
 // M_w from the weights of the last robust_eval, H(S_w) on it and on Lambda_w, the rank-one terms behind it
 void Group::robust_hessian_launch(int arow, int curvature) {
   CertState &c = *cert_;
@@ -215,16 +220,14 @@ int Group::robust_polish(const Graph &g, const double *X, int ld, int loss, doub
     return -1;
   }
   if (robust_begin(g, X, ld, loss, loss_reg, curvature, anchor, "robust polish") != 0) return -1;
-  const int ready = polish_setup(max_bytes, out, rob_->bytes, robust_remain());
+  const int ready = polish_setup(max_bytes, out, {rob_->bytes, robust_remain()});
   if (ready < 0) return -1;
   if (ready != 0) return 0;   // SKIPPED, with what the analysis predicts
   robust_alloc();
   CertState &c = *cert_;
   CovState &s = *cov_;
   RobustState &r = *rob_;
-  int arow = 0;
-  for (int p = 0; p < P0_; p++)
-    if (c.gid[p] == anchor) arow = p;
+  const int arow = own_row(anchor);
   const NodeMask all{all_bits(), nullptr};
   const int m = r.plan.m;
   PolishHooks hooks;
@@ -253,44 +256,14 @@ int Group::robust_covariance(const Graph &g, const double *X, int ld, int loss, 
     return -1;
   }
   if (robust_begin(g, X, ld, loss, loss_reg, curvature, anchor, "robust covariance") != 0) return -1;
-  CertState &c = *cert_;
-  CovState &s = *cov_;
-  const int dof = cov_dof(d_), DD = dof * dof, N = P0_;
-  std::vector<int> row_of(N);
-  for (int p = 0; p < N; p++) row_of[c.gid[p]] = p;
-  for (int k = 0; k < 2 * npairs; k++)
-    if (pairs[k] < 0 || pairs[k] >= N) {
-      fprintf(stderr, "[dpgo_amd] ERROR: robust covariance: pair %d names a pose that is not in the graph.\n", k / 2);
-      return -1;
-    }
-  const int ready = cov_setup(max_bytes, out, rob_->bytes, robust_remain());
-  if (ready < 0) return -1;
-  for (int k = 0; k < npairs; k++) {
-    const int p = row_of[pairs[2 * k]], q = row_of[pairs[2 * k + 1]];
-    const int *b0 = &s.bcol_h[c.bptr_h[p]], *b1 = &s.bcol_h[c.bptr_h[p + 1]];
-    if (std::find(b0, b1, q) == b1) {
-      fprintf(stderr, "[dpgo_amd] ERROR: robust covariance: pair %d (%d, %d) is not an edge of the graph.\n", k, pairs[2 * k],
-              pairs[2 * k + 1]);
-      return -1;
-    }
-  }
+  if (!pairs_args_ok("robust covariance", pairs, npairs)) return -1;
+  const int ready = cov_setup(max_bytes, out, {rob_->bytes, robust_remain()});
+  if (ready < 0 || !pairs_are_edges("robust covariance", pairs, npairs)) return -1;
   if (ready != 0) return 0;   // SKIPPED: nothing allocated, the stationarity not computed
   robust_alloc();
-  RobustState &r = *rob_;
-  const NodeMask all{all_bits(), nullptr};
-  const int arow = row_of[anchor], m = r.plan.m;
-  cert_upload(X, ld, d_, c.X.p);
-  robust_eval(c.X.p, loss, loss_reg, true, -1);
-  launch_robust_gather(lc(all), r.inc_ptr.p, r.inc.p, r.out.p + 3 * (size_t)m, r.rows.p, c.MX.p);
-  launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
-  launch_cert_reduce(st_, T_, 1, c.partials.p, c.h_sums, sched_.flag());
-  wait_flag(sched_.last_seq());
-  out.stationarity = std::sqrt(c.h_sums[0]);   // |S_w X|_F
-  std::fill(marginals, marginals + (size_t)N * DD, 0.0);
-  if (npairs) std::fill(cross, cross + (size_t)npairs * DD, 0.0);
-  const auto t0 = std::chrono::steady_clock::now();
-  robust_hessian_launch(arow, curvature);
-  return cov_finish(arow, row_of, pairs, npairs, marginals, cross, out, t0);
+  robust_point(X, ld, loss, loss_reg, &out.stationarity);
+  const int arow = own_row(anchor);
+  return cov_finish([&] { robust_hessian_launch(arow, curvature); }, arow, pairs, npairs, marginals, cross, out);
 }
 
 int Group::robust_hessian(const Graph &g, const double *X, int ld, int loss, double loss_reg, int curvature, int anchor, int *ptr,
@@ -300,7 +273,7 @@ int Group::robust_hessian(const Graph &g, const double *X, int ld, int loss, dou
   CertState &c = *cert_;
   CovState &s = *cov_;
   CovResult cr;
-  const int ready = cov_setup(0, cr, rob_->bytes, robust_remain());
+  const int ready = cov_setup(0, cr, {rob_->bytes, robust_remain()});
   if (ready < 0) return -1;
   *nnz = (long long)s.A.col.size();
   if (!ptr && !col && !val) return 0;   // (the size alone)
@@ -315,14 +288,8 @@ int Group::robust_hessian(const Graph &g, const double *X, int ld, int loss, dou
   robust_alloc();
   RobustState &r = *rob_;
   const NodeMask all{all_bits(), nullptr};
-  const int dof = cov_dof(d_), N = P0_, m = r.plan.m;
-  int arow = 0;
-  for (int p = 0; p < N; p++)
-    if (c.gid[p] == anchor) arow = p;
-  cert_upload(X, ld, d_, c.X.p);
-  robust_eval(c.X.p, loss, loss_reg, true, -1);
-  launch_robust_gather(lc(all), r.inc_ptr.p, r.inc.p, r.out.p + 3 * (size_t)m, r.rows.p, c.MX.p);
-  launch_cert_lambda(lc(all), c.X.p, c.MX.p, c.Lam.p, nullptr, c.partials.p);
+  const int dof = cov_dof(d_), N = P0_, m = r.plan.m, arow = own_row(anchor);
+  robust_point(X, ld, loss, loss_reg, nullptr);   // (no reduction: the stationarity is not handed out)
   launch_polish_grad(lc(all), c.X.p, c.MX.p, arow, r.grad.p, 0, 3, c.partials.p);
   robust_hessian_launch(arow, curvature);
   std::vector<double> v(s.A.col.size()), gh((size_t)dof * N), eo(5 * (size_t)m);
@@ -353,14 +320,9 @@ int Group::robust_matrix(const Graph &g, const double *X, int ld, int loss, doub
     fprintf(stderr, "[dpgo_amd] ERROR: robust matrix: room for %lld entries is needed.\n", *nnz);
     return -1;
   }
-  const long long remain = robust_remain();
-  if (remain > 0) {
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    if ((unsigned long long)remain > free_b / 2) {
-      fprintf(stderr, "[dpgo_amd] ERROR: robust matrix: the buffers do not fit the device.\n");
-      return -1;
-    }
+  if (!device_has_room(robust_remain())) {
+    fprintf(stderr, "[dpgo_amd] ERROR: robust matrix: the buffers do not fit the device.\n");
+    return -1;
   }
   robust_alloc();
   RobustState &r = *rob_;

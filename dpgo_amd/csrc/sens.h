@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "hess.h"
+
 namespace dpgo {
 
 struct Graph;
@@ -33,10 +35,9 @@ constexpr int SENS_BATCH = 64;   // columns per spd_msolve_device call
 // batch, one batch of upstream, one batch of per-edge output, the edge records, the row lists).  columns: k, batches:
 // spd_msolve_device calls, edges: of the graph.  factor_ms: k_cov_hessian and the factorisation up to its verdict; solve_ms:
 // the uploads, right-hand sides, solves and adjoint read-outs of all batches; edge_ms: k_sens_edge and the copies of its output.
-struct SensResult {
-  int outcome = SENS_SKIPPED, unknowns = 0, fronts = 0, levels = 0, max_front = 0, columns = 0, batches = 0, edges = 0;
-  long long device_bytes = 0;
-  double pivot_min = 0, pivot_max = 0, stationarity = 0, symbolic_s = 0, factor_ms = 0, solve_ms = 0, edge_ms = 0;
+struct SensResult : HessAnalysis {
+  int outcome = SENS_SKIPPED, columns = 0, batches = 0, edges = 0;
+  double stationarity = 0, solve_ms = 0, edge_ms = 0;
 };
 
 // ---- kernels (sens.hip) ----
