@@ -220,6 +220,14 @@ SYMBOLS = {
     "dpgo_debug_pairs_vsolve_baseline": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, _DP]),
     "dpgo_debug_pairs_plan": (C.c_int, [C.c_int, C.c_int, _IP, C.c_int, _IP, _IP, _IP]),
     "dpgo_debug_pairs_gate": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_group_joint_marginal": (C.c_int, [C.c_void_p, _DP, C.c_int, _IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, _DP, _DP,
+                                            _DP, C.c_void_p]),
+    "dpgo_graph_joint_marginal_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, _IP, C.c_int, C.c_int,
+                                                       C.c_int, C.c_int, C.c_longlong, _DP, _DP, _DP, C.c_void_p, C.c_void_p]),
+    "dpgo_debug_marg_plan": (C.c_int, [C.c_int, C.c_int, _IP, C.c_int, _IP, _IP, _IP]),
+    "dpgo_debug_marg_rel_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _DP, _DP, _DP]),
+    "dpgo_debug_marg_rel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP]),
+    "dpgo_debug_marg_dense": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, C.c_void_p]),
     "dpgo_group_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _DP, C.c_int, C.c_int, _DP, _DP,
                                          C.c_void_p]),
     "dpgo_debug_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP]),
@@ -425,6 +433,22 @@ def _pairs_arg(pairs, num_poses, dof):
     P = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
     marg, cross = np.zeros((num_poses, dof, dof)), np.zeros((len(P), dof, dof))
     return marg, cross, (_ip(P) if len(P) else None, len(P), _dp(marg), _dp(cross) if len(P) else None)
+
+
+def _marg_arg(d, keep, base, want_info):
+    """The arrays of a joint_marginal call: (cov, info, logdet, order, (keep pointer, K, base as the C ABI takes it)); the
+    arrays have the size of a VALID call -- the library checks the list itself."""
+    K = np.ascontiguousarray(np.asarray(keep).reshape(-1), np.int32)
+    if len(K) < 1:
+        raise ValueError("joint_marginal: keep is empty")
+    dof = _dof(d)
+    b = -1 if base is None else int(base)
+    if b < -1:
+        raise ValueError("joint_marginal: base is negative")
+    order = K.copy() if b < 0 else K[K != b].copy()
+    n = max(dof * (len(K) - (0 if b < 0 else 1)), 1)
+    cov, info, logdet = np.zeros((n, n)), np.zeros((n, n)), np.zeros(1)
+    return cov, info, logdet, order, (_ip(K), len(K), b, K)
 
 
 def _pair_cov_arg(d, pairs, candidates):
@@ -1235,6 +1259,27 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_pair_covariance failed (robust loss, a group that does not host every node, an anchor "
                                "or pose outside the graph, a candidate weight that is not positive, or bad sizes)")
         return pairs_output(joint, rel, gate, r, gated, threshold)
+
+    def joint_marginal(self, X, keep, anchor=0, base=None, want_info=True, max_bytes=0):
+        """The joint marginal of a SET of poses at X (dpgo_group_joint_marginal): `keep` lists distinct global poses in any
+        order, and the outputs follow that order.  base None: the absolute form, cov = (H^-1)_KK of `covariance`'s anchored
+        Hessian, n = dof K (the anchor may not be kept: raises).  base a member of keep (K >= 2): the relative form, the joint
+        covariance of T_base^-1 T_k of the other kept poses in list order, n = dof (K - 1), in pair_covariance's perturbation
+        of a relative pose; the anchor may then be kept, or be the base.  X should be a critical point (polish).
+        Returns a dict: cov (n, n), symmetric bit for bit; info (n, n) = cov^-1 and logdet = log det cov with want_info (else
+        None) -- in the absolute form info is the Schur complement of the anchored Hessian onto keep; order: the poses of the
+        dof-blocks of cov; result (MargResult).  outcome MARG_OK, MARG_NOT_PD (zero outputs) or MARG_SKIPPED (more device bytes
+        than max_bytes, when > 0, or than half of what is free); result.info_not_pd: cov is delivered, info and logdet are
+        zeros."""
+        X, ld = _fcol(X)
+        cov, info, logdet, order, args = _marg_arg(self.d, keep, base, want_info)
+        r = MargResult()
+        if lib().dpgo_group_joint_marginal(self._h, _dp(X), ld, args[0], args[1], int(anchor), args[2], int(bool(want_info)),
+                                           int(max_bytes), _dp(cov), _dp(info), _dp(logdet), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_joint_marginal failed (robust loss, a group that does not host every node, an anchor or "
+                               "pose outside the graph, a pose kept twice, the anchor kept without a base, or a base that is "
+                               "not one of at least two kept poses)")
+        return marg_output(cov, info, logdet, order, r, want_info)
 
     def sensitivity(self, X, upstream, anchor=0, max_bytes=0, graph=None, want_adjoint=False):
         """Measurement sensitivities at X by implicit differentiation on the device (dpgo_group_sensitivity): for k scalars
@@ -2123,6 +2168,73 @@ class PairsResult(C.Structure):
                 ("factor_bytes", C.c_double)]
 
 
+MARG_OK, MARG_NOT_PD, MARG_SKIPPED = 0, 1, 2
+MARG_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+
+
+class MargResult(C.Structure):
+    """dpgo_marg_result_t: the outcome of NodeGroup.joint_marginal, the sizes of the factorisation of H, the order n of the
+    dense problem, the unit columns solved, in how many batches, the pivots of the dense factorisation and the host
+    milliseconds of the three phases."""
+    _fields_ = [("outcome", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("info_not_pd", C.c_int), ("n", C.c_int), ("columns", C.c_int), ("batches", C.c_int), ("reserved", C.c_int),
+                ("device_bytes", C.c_longlong), ("pivot_min", C.c_double), ("pivot_max", C.c_double),
+                ("dense_pivot_min", C.c_double), ("dense_pivot_max", C.c_double), ("stationarity", C.c_double),
+                ("symbolic_s", C.c_double), ("factor_ms", C.c_double), ("solve_ms", C.c_double), ("dense_ms", C.c_double)]
+
+
+def marg_output(cov, info, logdet, order, result, want_info):
+    return {"cov": cov, "info": info if want_info else None, "logdet": float(logdet[0]) if want_info else None, "order": order,
+            "result": result}
+
+
+def marg_plan_debug(dof, anchor, keep):
+    """The column plan of a joint_marginal call (test hook, dpgo_debug_marg_plan; no device): a dict with poses (the kept poses
+    other than the anchor, in LIST order), col ((K,): the first column of every kept pose, -1 for the anchor), columns,
+    batches, kb."""
+    K = np.ascontiguousarray(np.asarray(keep).reshape(-1), np.int32)
+    poses, col, sizes = np.zeros(max(len(K), 1), np.int32), np.zeros(max(len(K), 1), np.int32), np.zeros(4, np.int32)
+    if lib().dpgo_debug_marg_plan(int(dof), int(anchor), _ip(K) if len(K) else None, len(K), _ip(poses), _ip(col), _ip(sizes)) != 0:
+        raise RuntimeError("dpgo_debug_marg_plan failed")
+    return {"poses": poses[:sizes[0]].copy(), "col": col[:len(K)].copy(), "columns": int(sizes[1]), "batches": int(sizes[2]),
+            "kb": int(sizes[3])}
+
+
+def marg_rel_debug(d, X, sigma, base_pos, device=None):
+    """The relative form's arithmetic on GIVEN arrays (test hooks): X (K, (d + 1) d) the kept poses' records (t, then R^T
+    row-major), sigma (dof K, dof K) their joint covariance in list order, base_pos the base's position in the list.  device
+    None: marg_math.h on the host (dpgo_debug_marg_rel_host; no GPU); an int: k_marg_rel alone on that HIP device
+    (dpgo_debug_marg_rel).  Returns cov (dof (K - 1), dof (K - 1))."""
+    dof = _dof(d)
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, (d + 1) * d)
+    K = X.shape[0]
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    if d not in (2, 3) or K < 2 or sigma.shape != (dof * K, dof * K) or not 0 <= int(base_pos) < K:
+        raise ValueError("marg_rel_debug: bad sizes")
+    cov = np.zeros((dof * (K - 1), dof * (K - 1)))
+    if device is None:
+        rc = lib().dpgo_debug_marg_rel_host(int(d), K, int(base_pos), _dp(X), _dp(sigma), _dp(cov))
+    else:
+        rc = lib().dpgo_debug_marg_rel(int(device), int(d), K, int(base_pos), _dp(X), _dp(sigma), _dp(cov))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_marg_rel failed")
+    return cov
+
+
+def marg_dense_debug(A, device=0):
+    """The dense tail of joint_marginal on a GIVEN symmetric matrix (test hook, dpgo_debug_marg_dense): the gather in batches of
+    64 columns, the one-front factorisation, its inverse and the log-determinant.  Returns a dict: cov (the gathered copy of
+    A), info (A^-1), logdet (log det A), result (MargResult; info_not_pd: info and logdet are zeros)."""
+    A = np.ascontiguousarray(A, np.float64)
+    n = A.shape[0]
+    if A.ndim != 2 or A.shape != (n, n) or n < 1:
+        raise ValueError("marg_dense_debug: A is not square")
+    cov, info, logdet, r = np.zeros((n, n)), np.zeros((n, n)), np.zeros(1), MargResult()
+    if lib().dpgo_debug_marg_dense(int(device), n, _dp(A), _dp(cov), _dp(info), _dp(logdet), C.byref(r)) != 0:
+        raise RuntimeError("dpgo_debug_marg_dense failed")
+    return {"cov": cov, "info": info, "logdet": float(logdet[0]), "result": r}
+
+
 def pack_candidates(d, npairs, R, t, kappa, tau):
     """(npairs, d^2 + d + 2): R row-major, t, kappa, tau per candidate, as dpgo_group_pair_covariance reads them."""
     out = np.zeros((npairs, d * d + d + 2))
@@ -2674,6 +2786,21 @@ def pair_covariance_reweighted(graph, X, loss, pairs, loss_reg=0.25, anchor=0, c
         raise RuntimeError("dpgo_graph_pair_covariance_reweighted failed (no HIP device, a short X, a bad loss, a pose outside the "
                            "graph, or a candidate weight that is not positive)")
     out = pairs_output(joint, rel, gate, r, gated, threshold)
+    out["summary"] = s
+    return out
+
+
+def joint_marginal_reweighted(graph, X, loss, keep, loss_reg=0.25, anchor=0, base=None, want_info=True, max_bytes=0, device=0):
+    """NodeGroup.joint_marginal for the RE-WEIGHTED problem at X (dpgo_graph_joint_marginal_reweighted), by
+    covariance_reweighted's recipe and with its caveat.  Returns joint_marginal's dict with summary (EdgeSummary) added."""
+    X, ld = _fcol(X)
+    cov, info, logdet, order, args = _marg_arg(graph.d, keep, base, want_info)
+    r, s = MargResult(), EdgeSummary()
+    if lib().dpgo_graph_joint_marginal_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), args[0], args[1],
+                                                  int(anchor), args[2], int(bool(want_info)), int(max_bytes), _dp(cov), _dp(info),
+                                                  _dp(logdet), C.byref(r), C.byref(s)) != 0:
+        raise RuntimeError("dpgo_graph_joint_marginal_reweighted failed (no HIP device, a short X, a bad loss, or a bad pose list)")
+    out = marg_output(cov, info, logdet, order, r, want_info)
     out["summary"] = s
     return out
 

@@ -936,6 +936,29 @@ int dpgo_graph_pair_covariance_reweighted(const dpgo_graph_t *g, int device, con
   });
 }
 
+// ---- joint marginals of a pose set (marg.h) ----
+int dpgo_group_joint_marginal(dpgo_group_t *h, const double *X, int ld, const int *keep, int nkeep, int anchor, int base,
+                              int want_info, long long max_bytes, double *cov, double *info, double *logdet,
+                              dpgo_marg_result_t *result) {
+  if (!h || !h->grp || !X || !result || !keep || nkeep < 1 || !cov || !logdet || (want_info && !info)) return -1;
+  return guarded([&] {
+    dpgo::MargResult r;
+    const int rc = h->grp->joint_marginal(X, ld, keep, nkeep, anchor, base, want_info != 0, max_bytes, cov, info, logdet, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+int dpgo_graph_joint_marginal_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                         const int *keep, int nkeep, int anchor, int base, int want_info, long long max_bytes,
+                                         double *cov, double *info, double *logdet, dpgo_marg_result_t *result,
+                                         dpgo_edge_summary_t *edge_summary) {
+  if (!g || !X || !result || !keep || nkeep < 1 || !cov || !logdet || (want_info && !info)) return -1;
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *) {
+    return dpgo_group_joint_marginal(grp, X, ld, keep, nkeep, anchor, base, want_info, max_bytes, cov, info, logdet, result);
+  });
+}
+
 // ---- measurement sensitivities (sens.h) ----
 int dpgo_group_sensitivity(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
                            const double *upstream, int ldu, int k, double *adjoint, double *sens, dpgo_sens_result_t *result) {

@@ -830,6 +830,39 @@ int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const d
   return 0;
 }
 
+int dpgo_debug_marg_plan(int dof, int anchor, const int *keep, int nkeep, int *poses, int *col, int *sizes) {
+  if (dof < 1 || nkeep < 1 || !keep || !poses || !col || !sizes) return -1;
+  return guarded([&] {
+    const dpgo::MargPlan pl = dpgo::marg_plan(dof, anchor, keep, nkeep);
+    std::copy(pl.poses.begin(), pl.poses.end(), poses);
+    std::copy(pl.col.begin(), pl.col.end(), col);
+    sizes[0] = (int)pl.poses.size(); sizes[1] = pl.columns; sizes[2] = pl.batches; sizes[3] = pl.kb;
+    return 0;
+  });
+}
+
+int dpgo_debug_marg_rel_host(int d, int nkeep, int base_pos, const double *X, const double *sigma, double *cov) {
+  return guarded([&] { return dpgo::marg_rel_host(d, nkeep, base_pos, X, sigma, cov); });
+}
+
+int dpgo_debug_marg_rel(int device, int d, int nkeep, int base_pos, const double *X, const double *sigma, double *cov) {
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    return dpgo::marg_rel_device(d, nkeep, base_pos, X, sigma, cov);
+  });
+}
+
+int dpgo_debug_marg_dense(int device, int n, const double *A, double *cov, double *info, double *logdet, dpgo_marg_result_t *result) {
+  if (n < 1 || !A || !cov || !info || !logdet || !result) return -1;
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    dpgo::MargResult r;
+    const int rc = dpgo::marg_dense_device(n, A, cov, info, logdet, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
 int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, const double *lambda, double *sens, double *phi) {
   if (!g) return -1;
   return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });

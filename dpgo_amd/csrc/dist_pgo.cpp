@@ -81,6 +81,14 @@
 //              and one more line on stdout
 //                  gate: <outcome> <candidates> <columns> <batches> <device_bytes> <pivot_min> <stationarity>
 //              (NOT_PD or SKIPPED: the report is not written); the same reasons as --covariance when it is not computed
+//              --marginal_set FILE --marginal_report FILE [--marginal_base P] (likewise; the two files both or neither)  for the
+//              trivial loss and a world of one rank, on the final point -- the polished one behind --polish, where it belongs:
+//              FILE lists one pose id per line, the kept set in that order; dpgo_group_joint_marginal (pose 0 the anchor)
+//              gives the set's joint covariance, its inverse and log-determinant -- with --marginal_base P, a member of the
+//              set, those of the relative poses T_P^-1 T_k.  The report (17 digits): a line "n <n> logdet <logdet>", a line
+//              with the poses of the dof-blocks in order, n rows of cov, n rows of info; and one more line on stdout
+//                  marginal: <outcome> <poses> <n> <columns> <batches> <device_bytes> <info_not_pd> <logdet> <stationarity>
+//              (NOT_PD or SKIPPED: the report is not written); "marginal: not computed (...)" says why not
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -119,8 +127,8 @@ int main(int argc, char **argv) {
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
   std::string edge_report, covariance, edge_reliability, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
-  std::string sensitivity_report;
-  int sensitivity_pose = -1;
+  std::string sensitivity_report, marginal_set, marginal_report;
+  int sensitivity_pose = -1, marginal_base = -1;
   double gnc_barc2 = 4.0;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
@@ -141,7 +149,10 @@ int main(int argc, char **argv) {
              "  --gnc arg               tls or gm, one rank: graduated non-convexity after the loop (outlier rejection on the inter-node\n"
              "                          edges); --gnc_barc2 arg (=4) the inlier threshold, --gnc_report arg / --gnc_filtered arg its files\n"
              "  --edge_reliability arg  trivial loss, one rank, behind --polish: redundancy and leave-one-out chi-square of every edge,\n"
-             "                          written to the file named\n");
+             "                          written to the file named\n"
+             "  --marginal_set arg      trivial loss, one rank: a file of pose ids, one per line; with --marginal_report arg the joint\n"
+             "                          covariance, information matrix and log-determinant of that set at the final point are written\n"
+             "                          there; --marginal_base arg: a member of the set, for the relative form\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
@@ -165,6 +176,9 @@ int main(int argc, char **argv) {
     else if (const char *v = val("--edge_reliability")) edge_reliability = v;
     else if (const char *v = val("--gate_candidates")) gate_candidates = v;
     else if (const char *v = val("--gate_report")) gate_report = v;
+    else if (const char *v = val("--marginal_set")) marginal_set = v;
+    else if (const char *v = val("--marginal_report")) marginal_report = v;
+    else if (const char *v = val("--marginal_base")) marginal_base = atoi(v);
     else if (const char *v = val("--sensitivity_pose")) sensitivity_pose = atoi(v);
     else if (const char *v = val("--sensitivity_report")) sensitivity_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
@@ -716,6 +730,49 @@ int main(int argc, char **argv) {
           const double *q = &rec[(size_t)e * w];
           fprintf(f, "%d %d %d %.17g %.17g %.17g %.17g %d %.17g\n", e, I[e], J[e], q[2], q[3], q[4], q[0], (int)q[1], q[5]);
         }
+        fclose(f);
+      }
+    }
+  }
+  if (!marginal_set.empty() || !marginal_report.empty()) {
+    if (marginal_set.empty() || marginal_report.empty()) {
+      fprintf(stderr, "--marginal_set and --marginal_report go together.\n");
+      return -1;
+    }
+    if (loss != 0) {
+      if (root) printf("marginal: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("marginal: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      std::vector<int> keep;
+      FILE *in = fopen(marginal_set.c_str(), "r");
+      if (!in) { fprintf(stderr, "Cannot read %s.\n", marginal_set.c_str()); return -1; }
+      for (int p; fscanf(in, "%d", &p) == 1;) keep.push_back(p);
+      fclose(in);
+      const int K = (int)keep.size(), dof = d + d * (d - 1) / 2, n = dof * (K - (marginal_base >= 0 ? 1 : 0));
+      if (K < 1 || n < 1) { fprintf(stderr, "%s holds no kept set.\n", marginal_set.c_str()); return -1; }
+      std::vector<double> Xc((size_t)ld * d, 0.0), cov((size_t)n * n, 0.0), info((size_t)n * n, 0.0);
+      double logdet = 0.0;
+      dpgo_marg_result_t mr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_joint_marginal(grp, Xc.data(), ld, keep.data(), K, 0, marginal_base, 1, 0, cov.data(), info.data(), &logdet, &mr) != 0)
+        return -1;
+      printf("marginal: %s %d %d %d %d %lld %d %.17g %.16g\n",
+             mr.outcome == DPGO_MARG_OK ? "OK" : mr.outcome == DPGO_MARG_NOT_PD ? "NOT_PD" : "SKIPPED", K, mr.n, mr.columns, mr.batches,
+             mr.device_bytes, mr.info_not_pd, logdet, mr.stationarity);
+      if (mr.outcome == DPGO_MARG_OK) {
+        FILE *f = fopen(marginal_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", marginal_report.c_str()); return -1; }
+        fprintf(f, "n %d logdet %.17g\n", n, logdet);
+        bool first = true;
+        for (int p : keep)
+          if (p != marginal_base) { fprintf(f, "%s%d", first ? "" : " ", p); first = false; }
+        fprintf(f, "\n");
+        for (const std::vector<double> *M : {&cov, &info})
+          for (int i = 0; i < n; i++) {
+            for (int j = 0; j < n; j++) fprintf(f, "%s%.17g", j ? " " : "", (*M)[(size_t)i * n + j]);
+            fprintf(f, "\n");
+          }
         fclose(f);
       }
     }

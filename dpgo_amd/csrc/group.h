@@ -31,6 +31,7 @@
 #include "cov.h"
 #include "graph.h"
 #include "kernels.h"
+#include "marg.h"
 #include "pairs.h"
 #include "gnc.h"
 #include "polish.h"
@@ -235,6 +236,11 @@ class Group {
   // rel: npairs x dof^2; gate (with candidates): npairs x (2 + dof) doubles, d^2, not_pd, the residual
   int pair_covariance(const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs, const double *candidates,
                       double *joint, double *rel, double *gate, PairsResult &out);
+  // ---- joint marginals of a pose set (marg.h, marg.cpp): the covariance's factor, the columns of H^-1 of the K kept poses,
+  // Sigma_KK in LIST order; base < 0: the absolute form (n = dof K), otherwise the covariance of T_base^-1 T_k (n = dof (K - 1)).
+  // cov, info (with want_info): n x n row-major; logdet: log det cov (with want_info)
+  int joint_marginal(const double *X, int ld, const int *keep, int K, int anchor, int base, bool want_info, long long max_bytes,
+                     double *cov, double *info, double *logdet, MargResult &out);
   // measurement: ncols unit columns solved one at a time with spd_vsolve_device on the same factor; ms: of the solves
   int pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms);
   // ---- measurement sensitivities (sens.h, sens.cpp): the covariance's factor, the adjoints H^-1 c of k upstream gradients by
@@ -739,6 +745,8 @@ class Group {
   void gnc_alloc();
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
   void gnc_summary(GncSummaryDev &sd);
+  MargCache *marg_ = nullptr;   // the dense factors of joint_marginal, one per order (marg.cpp), allocated by the first call
+  void marg_release();
   // the refusal of the block solves with kb columns (pairs.cpp); own: the call's buffers
   int pairs_setup(long long max_bytes, HessPart own, int kb, HessAnalysis &out);
   // the batches of a plan behind a factorisation: joint (device, zeroed by the caller) <- the blocks of the pairs (pairs.cpp)

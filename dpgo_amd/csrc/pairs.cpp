@@ -26,8 +26,7 @@ PairsPlan pairs_plan(int dof, int anchor, const int *pairs, int npairs) {
     if (pairs[k] != anchor)
       pl.pair_col[k] = dof * (int)(std::lower_bound(pl.poses.begin(), pl.poses.end(), pairs[k]) - pl.poses.begin());
   pl.columns = dof * (int)pl.poses.size();
-  pl.batches = (pl.columns + PAIRS_BATCH - 1) / PAIRS_BATCH;
-  pl.kb = 16 * ((std::min(std::max(pl.columns, 1), PAIRS_BATCH) + 15) / 16);
+  pairs_plan_sizes(pl.columns, &pl.batches, &pl.kb);
   return pl;
 }
 

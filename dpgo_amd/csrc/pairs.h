@@ -56,6 +56,12 @@ struct PairsPlan {
   int columns = 0, batches = 0, kb = 0;   // kb: the row length of the batch array, 16 ceil(min(columns, 64) / 16)
 };
 PairsPlan pairs_plan(int dof, int anchor, const int *pairs, int npairs);
+// the batches and the batch array's row length of a plan with that many columns (marg.h's plan shares it)
+inline void pairs_plan_sizes(int columns, int *batches, int *kb) {
+  *batches = (columns + PAIRS_BATCH - 1) / PAIRS_BATCH;
+  const int widest = columns < 1 ? 1 : columns < PAIRS_BATCH ? columns : PAIRS_BATCH;
+  *kb = 16 * ((widest + 15) / 16);
+}
 
 // ---- kernels (pairs.hip) ----
 // Xb (n x ldx, zeroed by the caller): column j < nc <- the unit vector of unknown col_unknown[c0 + j]

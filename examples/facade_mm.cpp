@@ -29,6 +29,12 @@
 //   pairs: joint <k> <the 3 dof^2 entries>     pairs: rel <k> <the dof^2 entries>     pairs: gate <k> <d2 not_pd residual>
 // then   pairs: <OK|NOT_PD|SKIPPED|FAILED> <columns> <batches> <stationarity>; a last call with candidates of the wrong length
 // must fail:   pairs: short candidates <status>
+// and with `marginal <poses.txt> [base]` through DPGOHashGroup::newton_polish and DPGOHashGroup::joint_marginal (trivial loss;
+// pose 0 is the anchor): the file lists one pose id per line, the kept set in that order; with a base (a member of the set) the
+// relative form.  Per row of the n x n matrices one line each, all entries with 17 digits,
+//   marginal: cov <row> <the n entries>      marginal: info <row> <the n entries>
+// then   marginal: <OK|NOT_PD|SKIPPED|FAILED> <n> <columns> <batches> <info_not_pd> <logdet, 17 digits>; a last call with the
+// first pose listed twice must fail:   marginal: repeated pose <status>
 // and with `sensitivity <pose>` through DPGOHashGroup::newton_polish and DPGOHashGroup::measurement_sensitivities (trivial
 // loss; pose 0 is the anchor) with the dof unit columns of the pose: per edge one line, all entries with 17 digits,
 //   sensitivity: e <edge> <the dof x (2 + dof) entries, row a the derivatives of coordinate a of the pose>
@@ -271,6 +277,34 @@ int main(int argc, char **argv) {
     int short_status = 0;
     dpgo_hash.pair_covariances(X, pairs, joint, rel, 0, nullptr, &short_status, &cand, &gate);
     fprintf(stderr, "pairs: short candidates %d %d\n", short_status, (int)gate.size());
+  }
+  if (argc > 7 && !strcmp(argv[6], "marginal")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0 || !dpgo_hash.newton_polish(X, Xp)) return 1;
+    std::vector<int> keep;
+    FILE *in = fopen(argv[7], "r");
+    if (!in) return 1;
+    for (int p; fscanf(in, "%d", &p) == 1;) keep.push_back(p);
+    fclose(in);
+    const int base = argc > 8 ? atoi(argv[8]) : -1;
+    std::vector<double> cov, info;
+    double logdet = 0.0;
+    int status = -1;
+    dpgo_marg_result_t r = {};
+    const bool ok = dpgo_hash.joint_marginal(Xp, keep, cov, &info, &logdet, 0, base, &r, &status);
+    for (int w = 0; ok && w < 2; w++)
+      for (int i = 0; i < r.n; i++) {
+        fprintf(stderr, "marginal: %s %d", w ? "info" : "cov", i);
+        for (int j = 0; j < r.n; j++) fprintf(stderr, " %.17g", (w ? info : cov)[(size_t)i * r.n + j]);
+        fprintf(stderr, "\n");
+      }
+    fprintf(stderr, "marginal: %s %d %d %d %d %.17g\n", status == DPGO_MARG_OK ? "OK" : status == DPGO_MARG_NOT_PD ? "NOT_PD"
+            : status == DPGO_MARG_SKIPPED ? "SKIPPED" : "FAILED", r.n, r.columns, r.batches, r.info_not_pd, logdet);
+    if (status < 0) return 1;
+    keep.push_back(keep[0]);
+    int twice_status = 0;
+    dpgo_hash.joint_marginal(Xp, keep, cov, &info, &logdet, 0, base, nullptr, &twice_status);
+    fprintf(stderr, "marginal: repeated pose %d\n", twice_status);
   }
   if (argc > 7 && !strcmp(argv[6], "sensitivity")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;

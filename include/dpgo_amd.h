@@ -597,6 +597,57 @@ int dpgo_debug_pairs_plan(int dof, int anchor, const int *pairs, int npairs, int
 int dpgo_debug_pairs_gate(int d, const double *recp, const double *recq, const double *joint, const double *cand, double *rel,
                           double *gate);
 
+/* ---- joint marginals of a pose set: covariance and information ---------------------------- */
+/* What does the graph know about a SET of poses together?  keep lists nkeep distinct global poses in any order; with the factor
+ * of the same anchored H the columns of H^-1 of the kept poses are solved for (the batches of dpgo_group_pair_covariance) and
+ * read at the kept rows: Sigma_KK, in the order of the LIST.  Restrictions, anchor and coordinates as for
+ * dpgo_group_covariance; X should be a critical point (dpgo_group_polish); the optimiser is not touched.
+ *   base < 0    the absolute form: n = dof nkeep, cov = Sigma_KK with the anchor held fixed.  The anchor may not be kept (-1):
+ *               its block is exactly zero and no information form exists
+ *   base >= 0   the relative form: base is one of at least two kept poses (else -1), n = dof (nkeep - 1), cov = J Sigma_KK J^T:
+ *               the joint covariance of T_base^-1 T_k of the other kept poses in list order, in dpgo_group_pair_covariance's
+ *               perturbation of T_pq (for nkeep = 2 this is its `rel`).  The anchor may be kept or be the base: its blocks of
+ *               Sigma_KK are zeros.  To first order at a critical point this does not depend on the anchor
+ *   cov         n x n row-major, symmetric bit for bit; the lower entries of the absolute form are the bits of
+ *               dpgo_group_pair_covariance's joint blocks
+ *   info        with want_info (else ignored): cov^-1, n x n, symmetric bit for bit -- in the absolute form the Schur complement
+ *               of the anchored H onto the kept poses.  A dense factor of order n by the multifrontal kernels (one front) and
+ *               its selected inverse; kept with the group per n
+ *   logdet      with want_info: log det cov (the set's differential entropy up to constants); 0 otherwise
+ *   result      outcome MARG_OK, MARG_NOT_PD (the anchored H is not positive definite; the outputs are zero) or MARG_SKIPPED
+ *               (device_bytes above max_bytes (> 0) or above half of the free device memory; the outputs are not written,
+ *               nothing is allocated); info_not_pd: the factorisation of cov met a non-positive pivot -- cov is delivered,
+ *               info and logdet are zeros; n, columns, batches: filled for SKIPPED too; dense_pivot_min / max: of cov's
+ *               factorisation; factor_ms / solve_ms / dense_ms: host milliseconds of the three phases */
+#define DPGO_MARG_OK 0
+#define DPGO_MARG_NOT_PD 1
+#define DPGO_MARG_SKIPPED 2
+typedef struct dpgo_marg_result {
+  int outcome, unknowns, fronts, levels, max_front, info_not_pd, n, columns, batches, reserved;
+  long long device_bytes;
+  double pivot_min, pivot_max, dense_pivot_min, dense_pivot_max, stationarity, symbolic_s, factor_ms, solve_ms, dense_ms;
+} dpgo_marg_result_t;
+int dpgo_group_joint_marginal(dpgo_group_t *grp, const double *X, int ld, const int *keep, int nkeep, int anchor, int base,
+                              int want_info, long long max_bytes, double *cov, double *info, double *logdet,
+                              dpgo_marg_result_t *result);
+/* The same for the RE-WEIGHTED problem at X, by dpgo_graph_covariance_reweighted's recipe and with its caveat. */
+int dpgo_graph_joint_marginal_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                         const int *keep, int nkeep, int anchor, int base, int want_info, long long max_bytes,
+                                         double *cov, double *info, double *logdet, dpgo_marg_result_t *result,
+                                         dpgo_edge_summary_t *edge_summary);
+/* Debug (no device): the column plan of a call -- poses (room for nkeep): the kept poses other than the anchor, in list order;
+ * col (nkeep): the first column of every kept pose, -1 for the anchor; sizes[4]: poses, columns, batches, kb. */
+int dpgo_debug_marg_plan(int dof, int anchor, const int *keep, int nkeep, int *poses, int *col, int *sizes);
+/* Debug: the relative covariance from a GIVEN Sigma_KK ((dof nkeep)^2, list order) and the kept poses' records X (nkeep x
+ * (d + 1) d: t, then R^T row-major); base_pos: the base's position in the list; cov: (dof (nkeep - 1))^2.  _host: the shared
+ * arithmetic on the host (no device); the other: the kernel on the same inputs.  The two agree bit for bit. */
+int dpgo_debug_marg_rel_host(int d, int nkeep, int base_pos, const double *X, const double *sigma, double *cov);
+int dpgo_debug_marg_rel(int device, int d, int nkeep, int base_pos, const double *X, const double *sigma, double *cov);
+/* Debug: the gather (batches of 64 columns), the dense factorisation, the inverse and the log-determinant on a GIVEN dense
+ * symmetric matrix A of order n, no graph: cov <- the gathered copy of A, info <- A^-1, *logdet <- log det A; result: n,
+ * columns, batches, info_not_pd (then info and logdet are zeros), the dense pivots, device_bytes of the dense factor. */
+int dpgo_debug_marg_dense(int device, int n, const double *A, double *cov, double *info, double *logdet, dpgo_marg_result_t *result);
+
 /* ---- measurement sensitivities: implicit differentiation of the solution ------------------ */
 /* How does the solution depend on the measurements it was computed from?  At a critical point X* the implicit function
  * theorem gives dX* / dtheta = -H^-1 d_theta g, with H the anchored tangent-space Hessian of dpgo_group_covariance and g the

@@ -281,6 +281,29 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_PAIRS_OK;
   }
+  // The joint marginal of a SET of poses (dpgo_group_joint_marginal).  keep: distinct global poses in any order; the outputs
+  // follow that order.  base < 0: the absolute form, cov = (H^-1)_KK, n = dof K (the anchor may not be kept); base a member of
+  // keep: the covariance of T_base^-1 T_k of the others, n = dof (K - 1).  cov is resized to n n doubles (row-major, symmetric
+  // bit for bit); info (optional) to n n: cov^-1, and then *logdet (optional) = log det cov.  X should be a critical point
+  // (newton_polish).  Returns true for DPGO_MARG_OK; status: the DPGO_MARG_* outcome, -1 when the call itself failed (a pose
+  // outside the graph or kept twice, the anchor kept without a base, a base that is not one of at least two kept poses).
+  bool joint_marginal(const Matrix &X, const std::vector<int> &keep, std::vector<Scalar> &cov, std::vector<Scalar> *info = nullptr,
+                      Scalar *logdet = nullptr, int anchor = 0, int base = -1, dpgo_marg_result_t *result = nullptr,
+                      int *status = nullptr, long long max_bytes = 0) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2, K = (int)keep.size();
+    const size_t n = (size_t)dof * (size_t)std::max(K - (base >= 0 ? 1 : 0), 0);
+    cov.assign(n * n, 0.0);
+    if (info) info->assign(n * n, 0.0);
+    Scalar ld = 0.0;
+    dpgo_marg_result_t r = {};
+    const int rc = K < 1 || n < 1 ? -1
+                                  : dpgo_group_joint_marginal(h_, X.data(), X.rows(), keep.data(), K, anchor, base, info ? 1 : 0, max_bytes,
+                                                              cov.data(), info ? info->data() : nullptr, &ld, &r);
+    if (logdet) *logdet = ld;
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_MARG_OK;
+  }
   // Measurement sensitivities by implicit differentiation (dpgo_group_sensitivity): upstream holds k tangent gradients of
   // scalars L_l(X), (dof N) x k column-major by global pose in marginal_covariances' coordinates; sens is resized to
   // k num_edges (2 + dof) doubles, [l][e][d/dkappa, d/dtau, d/dt~, d/deta] with the edges in the graph's order; adjoint
