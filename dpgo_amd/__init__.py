@@ -228,6 +228,15 @@ SYMBOLS = {
     "dpgo_debug_marg_rel_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _DP, _DP, _DP]),
     "dpgo_debug_marg_rel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP]),
     "dpgo_debug_marg_dense": (C.c_int, [C.c_int, C.c_int, _DP, _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_group_candidate_set": (C.c_int, [C.c_void_p, _DP, C.c_int, _IP, C.c_int, _DP, C.c_int, C.c_int, C.c_double, C.c_int,
+                                           C.c_longlong, _DP, _DP, _DP, _DP, _DP, _IP, _DP, _IP, C.c_void_p]),
+    "dpgo_graph_candidate_set_reweighted": (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int, C.c_int, C.c_double, _IP, C.c_int, _DP,
+                                                      C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong, _DP, _DP, _DP, _DP, _DP,
+                                                      _IP, _DP, _IP, C.c_void_p, C.c_void_p]),
+    "dpgo_debug_cand_innov_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _IP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_cand_innov": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _IP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_cand_select_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _IP, _DP, _DP, _IP]),
+    "dpgo_debug_cand_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _IP, _DP, _DP, _IP]),
     "dpgo_group_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _DP, C.c_int, C.c_int, _DP, _DP,
                                          C.c_void_p]),
     "dpgo_debug_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP]),
@@ -449,6 +458,36 @@ def _marg_arg(d, keep, base, want_info):
     n = max(dof * (len(K) - (0 if b < 0 else 1)), 1)
     cov, info, logdet = np.zeros((n, n)), np.zeros((n, n)), np.zeros(1)
     return cov, info, logdet, order, (_ip(K), len(K), b, K)
+
+
+def _cand_pack(d, m, candidates):
+    """(m, d^2 + d + 2) from a tuple (R, t, kappa, tau) (pack_candidates) or an array already in that layout."""
+    if isinstance(candidates, tuple):
+        return pack_candidates(d, m, *candidates)
+    cand = np.ascontiguousarray(candidates, np.float64).reshape(m, -1)
+    if cand.shape[1] != d * d + d + 2:
+        raise ValueError("candidates: %d values per candidate, not d^2 + d + 2" % cand.shape[1])
+    return cand
+
+
+def _cand_arg(d, pairs, candidates, budget, want_joint, want_cov):
+    """The arrays of a candidate_set call, sized for a VALID call -- the library checks the pairs and weights itself: (a dict of
+    the arrays, the arguments pairs, ncand, candidates and, after the scalars the caller puts between, cov ... poses)."""
+    P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+    m, budget = len(P), int(budget)
+    if m < 1:
+        raise ValueError("candidate_set: no candidates")
+    if budget < 0:
+        raise ValueError("candidate_set: the budget is negative")
+    n = _dof(d) * m
+    a = {"cand": _cand_pack(d, m, candidates), "pairs": P, "cov": np.zeros((n, n)) if want_cov else None,
+         "S": np.zeros((n, n)) if want_cov else None, "residual": np.zeros(n), "info": np.zeros((n, n)) if want_joint else None,
+         "scalars": np.zeros(5), "selected": np.full(max(budget, 1), -1, np.int32), "steps": np.zeros((max(budget, 1), 4)),
+         "poses": np.zeros(2 * m, np.int32), "budget": budget}
+    head = (_ip(P), m, _dp(a["cand"]))
+    tail = (_dpn(a["cov"]), _dpn(a["S"]), _dp(a["residual"]), _dpn(a["info"]), _dp(a["scalars"]), _ip(a["selected"]), _dp(a["steps"]),
+            _ip(a["poses"]))
+    return a, head, tail
 
 
 def _pair_cov_arg(d, pairs, candidates):
@@ -1280,6 +1319,34 @@ class NodeGroup:
                                "pose outside the graph, a pose kept twice, the anchor kept without a base, or a base that is "
                                "not one of at least two kept poses)")
         return marg_output(cov, info, logdet, order, r, want_info)
+
+    def candidate_set(self, X, pairs, candidates, anchor=0, budget=0, d2_max=0.0, want_joint=True, want_cov=True, max_bytes=0):
+        """Joint compatibility and budgeted selection of loop-closure candidates at X (dpgo_group_candidate_set).  pairs (m, 2):
+        global poses, p != q; a pair may repeat, pairs may share poses, either end may be the anchor.  candidates: the tuple
+        (R, t, kappa, tau) of pair_covariance, or (m, d^2 + d + 2) in pack_candidates' layout.  X should be a critical point
+        (polish).  With n = dof m, returns a dict:
+          cov, S         (n, n) with want_cov (else None): J Sigma_KK J^T -- its diagonal blocks are pair_covariance's rel -- and
+                         cov + blkdiag(Omega_i^-1); symmetric bit for bit
+          residual       (n,): pair_covariance's residuals, stacked
+          info, logdet, d2_joint, gain_all   with want_joint (else None; zeros under result.joint_not_pd): S^-1, log det S,
+                         r^T S^-1 r -- the candidates' compatibility with the graph TOGETHER -- and the information they would
+                         add together, 1/2 (log det S - sum log det Omega_i^-1)
+          selected       (n_selected,): with budget > 0 the greedy choice by conditional information gain, in order; a candidate
+                         is eligible iff its conditional covariance is positive definite and (d2_max <= 0 or its CONDITIONAL
+                         d2 <= d2_max); ties go to the lowest index
+          steps          (n_selected, 4): index, gain, d2, the number of eligible candidates at that step
+          gain_selected, d2_selected   the sums over the steps: 1/2 (log det S_sel - log det R_sel) and r_sel^T S_sel^-1 r_sel
+          poses          the distinct end poses in order of first appearance
+          result         CandResult; outcome CAND_OK, CAND_NOT_PD (zero outputs) or CAND_SKIPPED (more device bytes than
+                         max_bytes, when > 0, or than half of what is free)."""
+        X, ld = _fcol(X)
+        a, head, tail = _cand_arg(self.d, pairs, candidates, budget, want_joint, want_cov)
+        r = CandResult()
+        if lib().dpgo_group_candidate_set(self._h, _dp(X), ld, *head, int(anchor), a["budget"], float(d2_max), int(bool(want_joint)),
+                                          int(max_bytes), *tail, C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_candidate_set failed (robust loss, a group that does not host every node, an anchor or "
+                               "pose outside the graph, a candidate that joins a pose to itself, or a weight that is not positive)")
+        return cand_output(a, r, want_joint)
 
     def sensitivity(self, X, upstream, anchor=0, max_bytes=0, graph=None, want_adjoint=False):
         """Measurement sensitivities at X by implicit differentiation on the device (dpgo_group_sensitivity): for k scalars
@@ -2235,6 +2302,87 @@ def marg_dense_debug(A, device=0):
     return {"cov": cov, "info": info, "logdet": float(logdet[0]), "result": r}
 
 
+CAND_OK, CAND_NOT_PD, CAND_SKIPPED = 0, 1, 2
+CAND_NAMES = {0: "OK", 1: "NOT_PD", 2: "SKIPPED"}
+
+
+class CandResult(C.Structure):
+    """dpgo_cand_result_t: the outcome of NodeGroup.candidate_set, the sizes of the factorisation of H, the order n = dof m of the
+    joint problem, the distinct end poses, the unit columns solved and in how many batches, how many candidates were chosen,
+    the pivots of the dense factorisation of S and the host milliseconds of the four phases."""
+    _fields_ = [("outcome", C.c_int), ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("joint_not_pd", C.c_int), ("n", C.c_int), ("poses", C.c_int), ("columns", C.c_int), ("batches", C.c_int),
+                ("n_selected", C.c_int), ("reserved", C.c_int), ("device_bytes", C.c_longlong), ("pivot_min", C.c_double),
+                ("pivot_max", C.c_double), ("dense_pivot_min", C.c_double), ("dense_pivot_max", C.c_double),
+                ("stationarity", C.c_double), ("symbolic_s", C.c_double), ("factor_ms", C.c_double), ("solve_ms", C.c_double),
+                ("dense_ms", C.c_double), ("select_ms", C.c_double)]
+
+
+def cand_output(a, r, want_joint):
+    k = r.n_selected
+    sc = a["scalars"]
+    return {"cov": a["cov"], "S": a["S"], "residual": a["residual"], "info": a["info"] if want_joint else None,
+            "logdet": float(sc[0]) if want_joint else None, "d2_joint": float(sc[1]) if want_joint else None,
+            "gain_all": float(sc[2]) if want_joint else None, "selected": a["selected"][:k].copy(), "steps": a["steps"][:k].copy(),
+            "gain_selected": float(sc[3]), "d2_selected": float(sc[4]), "poses": a["poses"][:r.poses].copy(), "result": r}
+
+
+def cand_innov_debug(d, X, sigma, kpos, candidates, device=None):
+    """The block arithmetic of candidate_set on GIVEN arrays (test hooks): X (K, (d + 1) d) the records of the listed poses (t,
+    then R^T row-major), sigma (dof K, dof K) their joint covariance in list order, kpos (m, 2) the positions of every
+    candidate's ends in the list, candidates as candidate_set's.  device None: cand_math.h on the host
+    (dpgo_debug_cand_innov_host; no GPU); an int: k_cand_innov and k_cand_resid alone on that HIP device.  Returns a dict: cov,
+    S (dof m, dof m), residual (dof m,)."""
+    dof = _dof(d)
+    X = np.ascontiguousarray(X, np.float64).reshape(-1, (d + 1) * d)
+    K = X.shape[0]
+    sigma = np.ascontiguousarray(sigma, np.float64)
+    kp = np.ascontiguousarray(np.asarray(kpos).reshape(-1, 2), np.int32)
+    m = len(kp)
+    if d not in (2, 3) or m < 1 or K < 2 or sigma.shape != (dof * K, dof * K) or kp.min() < 0 or kp.max() >= K:
+        raise ValueError("cand_innov_debug: bad sizes")
+    cand = _cand_pack(d, m, candidates)
+    n = dof * m
+    cov, S, r = np.zeros((n, n)), np.zeros((n, n)), np.zeros(n)
+    if device is None:
+        rc = lib().dpgo_debug_cand_innov_host(int(d), m, K, _ip(kp), _dp(X), _dp(sigma), _dp(cand), _dp(cov), _dp(S), _dp(r))
+    else:
+        rc = lib().dpgo_debug_cand_innov(int(device), int(d), m, K, _ip(kp), _dp(X), _dp(sigma), _dp(cand), _dp(cov), _dp(S), _dp(r))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_cand_innov failed")
+    return {"cov": cov, "S": S, "residual": r}
+
+
+def cand_select_debug(d, S, r, weights, budget, d2_max=0.0, device=None, selected=None, steps=None):
+    """The selection of candidate_set on a GIVEN S (dof m, dof m), r (dof m,) and weights (m, 2: kappa, tau), no graph (test hooks).
+    device None: the same steps on the host (dpgo_debug_cand_select_host; no GPU); an int: k_cand_score / k_cand_update on that
+    HIP device.  selected (budget,) and steps (budget, 4) start as given (default -1 and zeros): only the chosen steps are
+    written, entries from n_selected on keep their values.  Returns a dict: selected, steps (whole arrays), n_selected,
+    gain_selected, d2_selected."""
+    dof = _dof(d)
+    S = np.ascontiguousarray(S, np.float64)
+    r = np.ascontiguousarray(r, np.float64).reshape(-1)
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1, 2)
+    m, budget = len(w), int(budget)
+    if d not in (2, 3) or m < 1 or budget < 0 or S.shape != (dof * m, dof * m) or r.shape != (dof * m,):
+        raise ValueError("cand_select_debug: bad sizes")
+    sel = np.full(max(budget, 1), -1, np.int32) if selected is None else np.ascontiguousarray(selected, np.int32).copy()
+    stp = np.zeros((max(budget, 1), 4)) if steps is None else np.ascontiguousarray(steps, np.float64).copy()
+    if len(sel) < max(budget, 1) or stp.shape != (len(sel), 4):
+        raise ValueError("cand_select_debug: selected / steps are shorter than the budget")
+    sums, nsel = np.zeros(2), np.zeros(1, np.int32)
+    if device is None:
+        rc = lib().dpgo_debug_cand_select_host(int(d), m, budget, float(d2_max), _dp(S), _dp(r), _dp(w), _ip(sel), _dp(stp), _dp(sums),
+                                               _ip(nsel))
+    else:
+        rc = lib().dpgo_debug_cand_select(int(device), int(d), m, budget, float(d2_max), _dp(S), _dp(r), _dp(w), _ip(sel), _dp(stp),
+                                          _dp(sums), _ip(nsel))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_cand_select failed (a weight that is not positive, or bad sizes)")
+    return {"selected": sel[:budget], "steps": stp[:budget], "n_selected": int(nsel[0]), "gain_selected": float(sums[0]),
+            "d2_selected": float(sums[1])}
+
+
 def pack_candidates(d, npairs, R, t, kappa, tau):
     """(npairs, d^2 + d + 2): R row-major, t, kappa, tau per candidate, as dpgo_group_pair_covariance reads them."""
     out = np.zeros((npairs, d * d + d + 2))
@@ -2801,6 +2949,23 @@ def joint_marginal_reweighted(graph, X, loss, keep, loss_reg=0.25, anchor=0, bas
                                                   _dp(logdet), C.byref(r), C.byref(s)) != 0:
         raise RuntimeError("dpgo_graph_joint_marginal_reweighted failed (no HIP device, a short X, a bad loss, or a bad pose list)")
     out = marg_output(cov, info, logdet, order, r, want_info)
+    out["summary"] = s
+    return out
+
+
+def candidate_set_reweighted(graph, X, loss, pairs, candidates, loss_reg=0.25, anchor=0, budget=0, d2_max=0.0, want_joint=True,
+                             want_cov=True, max_bytes=0, device=0):
+    """NodeGroup.candidate_set for the RE-WEIGHTED problem at X (dpgo_graph_candidate_set_reweighted), by
+    pair_covariance_reweighted's recipe and with its caveat.  Returns candidate_set's dict with summary (EdgeSummary) added."""
+    X, ld = _fcol(X)
+    a, head, tail = _cand_arg(graph.d, pairs, candidates, budget, want_joint, want_cov)
+    r, s = CandResult(), EdgeSummary()
+    if lib().dpgo_graph_candidate_set_reweighted(graph._h, int(device), _dp(X), ld, int(loss), float(loss_reg), *head, int(anchor),
+                                                 a["budget"], float(d2_max), int(bool(want_joint)), int(max_bytes), *tail,
+                                                 C.byref(r), C.byref(s)) != 0:
+        raise RuntimeError("dpgo_graph_candidate_set_reweighted failed (no HIP device, a short X, a bad loss, a pose outside the "
+                           "graph, a candidate that joins a pose to itself, or a weight that is not positive)")
+    out = cand_output(a, r, want_joint)
     out["summary"] = s
     return out
 

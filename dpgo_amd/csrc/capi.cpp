@@ -959,6 +959,35 @@ int dpgo_graph_joint_marginal_reweighted(const dpgo_graph_t *g, int device, cons
   });
 }
 
+// ---- joint compatibility and budgeted selection of loop-closure candidates (cand.h) ----
+int dpgo_group_candidate_set(dpgo_group_t *h, const double *X, int ld, const int *pairs, int ncand, const double *candidates,
+                             int anchor, int budget, double d2_max, int want_joint, long long max_bytes, double *cov, double *S,
+                             double *residual, double *info, double *scalars, int *selected, double *steps, int *poses,
+                             dpgo_cand_result_t *result) {
+  if (!h || !h->grp || !X || !result) return -1;
+  return guarded([&] {
+    dpgo::CandResult r;
+    dpgo::CandOut o;
+    o.cov = cov; o.S = S; o.residual = residual; o.info = info; o.scalars = scalars; o.selected = selected; o.steps = steps;
+    o.poses = poses;
+    const int rc = h->grp->candidate_set(X, ld, pairs, ncand, candidates, anchor, budget, d2_max, want_joint != 0, max_bytes, o, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+int dpgo_graph_candidate_set_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                        const int *pairs, int ncand, const double *candidates, int anchor, int budget, double d2_max,
+                                        int want_joint, long long max_bytes, double *cov, double *S, double *residual, double *info,
+                                        double *scalars, int *selected, double *steps, int *poses, dpgo_cand_result_t *result,
+                                        dpgo_edge_summary_t *edge_summary) {
+  if (!g || !X || !result) return -1;
+  return with_reweighted_group(g, device, X, ld, loss, loss_reg, edge_summary, [&](dpgo_group_t *grp, const dpgo_graph_t *) {
+    return dpgo_group_candidate_set(grp, X, ld, pairs, ncand, candidates, anchor, budget, d2_max, want_joint, max_bytes, cov, S,
+                                    residual, info, scalars, selected, steps, poses, result);
+  });
+}
+
 // ---- measurement sensitivities (sens.h) ----
 int dpgo_group_sensitivity(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
                            const double *upstream, int ldu, int k, double *adjoint, double *sens, dpgo_sens_result_t *result) {

@@ -863,6 +863,32 @@ int dpgo_debug_marg_dense(int device, int n, const double *A, double *cov, doubl
   });
 }
 
+int dpgo_debug_cand_innov_host(int d, int ncand, int nposes, const int *kpos, const double *X, const double *sigma,
+                               const double *candidates, double *cov, double *S, double *residual) {
+  return guarded([&] { return dpgo::cand_innov_host(d, ncand, nposes, kpos, X, sigma, candidates, cov, S, residual); });
+}
+
+int dpgo_debug_cand_innov(int device, int d, int ncand, int nposes, const int *kpos, const double *X, const double *sigma,
+                          const double *candidates, double *cov, double *S, double *residual) {
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    return dpgo::cand_innov_device(d, ncand, nposes, kpos, X, sigma, candidates, cov, S, residual);
+  });
+}
+
+int dpgo_debug_cand_select_host(int d, int ncand, int budget, double d2_max, const double *S, const double *r, const double *weights,
+                                int *selected, double *steps, double *sums, int *n_selected) {
+  return guarded([&] { return dpgo::cand_select_host(d, ncand, budget, d2_max, S, r, weights, selected, steps, sums, n_selected); });
+}
+
+int dpgo_debug_cand_select(int device, int d, int ncand, int budget, double d2_max, const double *S, const double *r,
+                           const double *weights, int *selected, double *steps, double *sums, int *n_selected) {
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    return dpgo::cand_select_device(d, ncand, budget, d2_max, S, r, weights, selected, steps, sums, n_selected);
+  });
+}
+
 int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, const double *lambda, double *sens, double *phi) {
   if (!g) return -1;
   return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });

@@ -72,7 +72,7 @@ inline void to_c(const dpgo::EdgeSummary &s, dpgo_edge_summary_t *o) {
   o->num_inter = s.num_inter; o->num_downweighted = s.num_downweighted;
 }
 
-// the analysis' numbers (hess.h), which the six result structs below carry under the same names
+// the analysis' numbers (hess.h), which the seven result structs below carry under the same names
 template <class C>
 inline void analysis_to_c(const dpgo::HessAnalysis &r, C *o) {
   o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels; o->max_front = r.max_front;
@@ -97,6 +97,14 @@ inline void to_c(const dpgo::MargResult &r, dpgo_marg_result_t *o) {
   analysis_to_c(r, o);
   o->outcome = r.outcome; o->info_not_pd = r.info_not_pd; o->n = r.n; o->columns = r.columns; o->batches = r.batches;
   o->reserved = 0; o->stationarity = r.stationarity; o->solve_ms = r.solve_ms; o->dense_ms = r.dense_ms;
+  o->dense_pivot_min = r.dense_pivot_min; o->dense_pivot_max = r.dense_pivot_max;
+}
+
+inline void to_c(const dpgo::CandResult &r, dpgo_cand_result_t *o) {
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->joint_not_pd = r.joint_not_pd; o->n = r.n; o->poses = r.poses; o->columns = r.columns;
+  o->batches = r.batches; o->n_selected = r.n_selected; o->reserved = 0; o->stationarity = r.stationarity;
+  o->solve_ms = r.solve_ms; o->dense_ms = r.dense_ms; o->select_ms = r.select_ms;
   o->dense_pivot_min = r.dense_pivot_min; o->dense_pivot_max = r.dense_pivot_max;
 }
 

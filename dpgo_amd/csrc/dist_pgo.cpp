@@ -89,6 +89,16 @@
 //              with the poses of the dof-blocks in order, n rows of cov, n rows of info; and one more line on stdout
 //                  marginal: <outcome> <poses> <n> <columns> <batches> <device_bytes> <info_not_pd> <logdet> <stationarity>
 //              (NOT_PD or SKIPPED: the report is not written); "marginal: not computed (...)" says why not
+//              --select_candidates FILE --select_report FILE [--select_budget K] [--select_d2_max V] (likewise; the two files both
+//              or neither)  for the trivial loss and a world of one rank, on the final point -- the polished one behind --polish:
+//              FILE is a .g2o of candidate edges, read as --gate_candidates reads it; dpgo_group_candidate_set (pose 0 the
+//              anchor) judges them TOGETHER -- d2_joint = r^T S^-1 r, gain_all -- and chooses at most K (default: all) by
+//              conditional information gain, a candidate being eligible while its conditional d2 <= V (default 0: no gate).
+//              The report (17 digits): a line "n <n> logdet <logdet> d2_joint <d2> gain_all <gain>", a line "selected <k>
+//              gain <gain_selected> d2 <d2_selected>", k lines "<candidate> <p> <q> <gain> <d2> <eligible>", n rows of S, n rows
+//              of S^-1; and one more line on stdout
+//                  candidates: <outcome> <candidates> <n> <poses> <columns> <batches> <device_bytes> <joint_not_pd> <selected> <d2_joint> <gain_all> <stationarity>
+//              (NOT_PD or SKIPPED: the report is not written); "candidates: not computed (...)" says why not
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -127,9 +137,9 @@ int main(int argc, char **argv) {
   int num_nodes = -1, iters = 1000, gpu = -1;
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
   std::string edge_report, covariance, edge_reliability, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
-  std::string sensitivity_report, marginal_set, marginal_report;
-  int sensitivity_pose = -1, marginal_base = -1;
-  double gnc_barc2 = 4.0;
+  std::string sensitivity_report, marginal_set, marginal_report, select_candidates, select_report;
+  int sensitivity_pose = -1, marginal_base = -1, select_budget = -1;
+  double gnc_barc2 = 4.0, select_d2_max = 0.0;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
   for (int i = 1; i < argc; i++) {
@@ -152,7 +162,10 @@ int main(int argc, char **argv) {
              "                          written to the file named\n"
              "  --marginal_set arg      trivial loss, one rank: a file of pose ids, one per line; with --marginal_report arg the joint\n"
              "                          covariance, information matrix and log-determinant of that set at the final point are written\n"
-             "                          there; --marginal_base arg: a member of the set, for the relative form\n");
+             "                          there; --marginal_base arg: a member of the set, for the relative form\n"
+             "  --select_candidates arg trivial loss, one rank: a .g2o of candidate edges; with --select_report arg their joint\n"
+             "                          compatibility and the greedy choice of --select_budget arg (= all) of them by information\n"
+             "                          gain, gated by --select_d2_max arg (= 0: no gate), are written there\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
@@ -179,6 +192,10 @@ int main(int argc, char **argv) {
     else if (const char *v = val("--marginal_set")) marginal_set = v;
     else if (const char *v = val("--marginal_report")) marginal_report = v;
     else if (const char *v = val("--marginal_base")) marginal_base = atoi(v);
+    else if (const char *v = val("--select_candidates")) select_candidates = v;
+    else if (const char *v = val("--select_report")) select_report = v;
+    else if (const char *v = val("--select_budget")) select_budget = atoi(v);
+    else if (const char *v = val("--select_d2_max")) select_d2_max = atof(v);
     else if (const char *v = val("--sensitivity_pose")) sensitivity_pose = atoi(v);
     else if (const char *v = val("--sensitivity_report")) sensitivity_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
@@ -769,6 +786,68 @@ int main(int argc, char **argv) {
           if (p != marginal_base) { fprintf(f, "%s%d", first ? "" : " ", p); first = false; }
         fprintf(f, "\n");
         for (const std::vector<double> *M : {&cov, &info})
+          for (int i = 0; i < n; i++) {
+            for (int j = 0; j < n; j++) fprintf(f, "%s%.17g", j ? " " : "", (*M)[(size_t)i * n + j]);
+            fprintf(f, "\n");
+          }
+        fclose(f);
+      }
+    }
+  }
+  if (!select_candidates.empty() || !select_report.empty()) {
+    if (select_candidates.empty() || select_report.empty()) {
+      fprintf(stderr, "--select_candidates and --select_report go together.\n");
+      return -1;
+    }
+    if (loss != 0) {
+      if (root) printf("candidates: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("candidates: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      dpgo_graph_t *cg = nullptr;
+      int cd = 0, cN = 0, cn = 0, m = 0;
+      if (dpgo_read_g2o(select_candidates.c_str(), 1, &cg) != 0 || dpgo_graph_info(cg, &cd, &cN, &cn, &m) != 0 || cd != d || cN > N || m < 1) {
+        fprintf(stderr, "Cannot use the candidates in %s (unreadable, empty, another dimension, or a pose that is not in the graph).\n",
+                select_candidates.c_str());
+        dpgo_graph_free(cg);
+        return -1;
+      }
+      const int dof = d + d * (d - 1) / 2, nc = d * d + d + 2, n = dof * m, budget = select_budget < 0 ? m : select_budget;
+      std::vector<int> I(m), J(m), pairs((size_t)2 * m);
+      std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m), cand((size_t)m * nc);
+      const int got = dpgo_graph_edges(cg, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data());
+      dpgo_graph_free(cg);
+      if (got != 0) {
+        fprintf(stderr, "Cannot read the edges of %s.\n", select_candidates.c_str());
+        return -1;
+      }
+      for (int k = 0; k < m; k++) {
+        pairs[2 * k] = I[k]; pairs[2 * k + 1] = J[k];
+        std::copy(&R[(size_t)k * d * d], &R[(size_t)(k + 1) * d * d], &cand[(size_t)k * nc]);
+        std::copy(&t[(size_t)k * d], &t[(size_t)(k + 1) * d], &cand[(size_t)k * nc + d * d]);
+        cand[(size_t)k * nc + d * d + d] = kappa[k];
+        cand[(size_t)k * nc + d * d + d + 1] = tau[k];
+      }
+      std::vector<double> Xc((size_t)ld * d, 0.0), S((size_t)n * n), res((size_t)n), info((size_t)n * n), steps((size_t)4 * std::max(budget, 1));
+      std::vector<int> selected((size_t)std::max(budget, 1), -1), poses((size_t)2 * m);
+      double sc[5] = {0, 0, 0, 0, 0};
+      dpgo_cand_result_t cr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_candidate_set(grp, Xc.data(), ld, pairs.data(), m, cand.data(), 0, budget, select_d2_max, 1, 0, nullptr, S.data(),
+                                   res.data(), info.data(), sc, selected.data(), steps.data(), poses.data(), &cr) != 0)
+        return -1;
+      printf("candidates: %s %d %d %d %d %d %lld %d %d %.17g %.17g %.16g\n",
+             cr.outcome == DPGO_CAND_OK ? "OK" : cr.outcome == DPGO_CAND_NOT_PD ? "NOT_PD" : "SKIPPED", m, cr.n, cr.poses, cr.columns,
+             cr.batches, cr.device_bytes, cr.joint_not_pd, cr.n_selected, sc[1], sc[2], cr.stationarity);
+      if (cr.outcome == DPGO_CAND_OK) {
+        FILE *f = fopen(select_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", select_report.c_str()); return -1; }
+        fprintf(f, "n %d logdet %.17g d2_joint %.17g gain_all %.17g\n", n, sc[0], sc[1], sc[2]);
+        fprintf(f, "selected %d gain %.17g d2 %.17g\n", cr.n_selected, sc[3], sc[4]);
+        for (int k = 0; k < cr.n_selected; k++)
+          fprintf(f, "%d %d %d %.17g %.17g %d\n", selected[k], I[selected[k]], J[selected[k]], steps[4 * (size_t)k + 1],
+                  steps[4 * (size_t)k + 2], (int)steps[4 * (size_t)k + 3]);
+        for (const std::vector<double> *M : {&S, &info})
           for (int i = 0; i < n; i++) {
             for (int j = 0; j < n; j++) fprintf(f, "%s%.17g", j ? " " : "", (*M)[(size_t)i * n + j]);
             fprintf(f, "\n");

@@ -28,6 +28,7 @@
 
 #include "assemble.h"
 #include "cert.h"
+#include "cand.h"
 #include "cov.h"
 #include "graph.h"
 #include "kernels.h"
@@ -241,6 +242,11 @@ class Group {
   // cov, info (with want_info): n x n row-major; logdet: log det cov (with want_info)
   int joint_marginal(const double *X, int ld, const int *keep, int K, int anchor, int base, bool want_info, long long max_bytes,
                      double *cov, double *info, double *logdet, MargResult &out);
+  // ---- joint compatibility and budgeted selection of loop-closure candidates (cand.h, cand.cpp): Sigma_KK of the candidates'
+  // end poses by joint_marginal's batches, the joint innovation covariance S, its inverse and r^T S^-1 r (want_joint), and the
+  // greedy selection of at most `budget` candidates by conditional information gain on the device
+  int candidate_set(const double *X, int ld, const int *pairs, int m, const double *candidates, int anchor, int budget, double d2_max,
+                    bool want_joint, long long max_bytes, const CandOut &o, CandResult &out);
   // measurement: ncols unit columns solved one at a time with spd_vsolve_device on the same factor; ms: of the solves
   int pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms);
   // ---- measurement sensitivities (sens.h, sens.cpp): the covariance's factor, the adjoints H^-1 c of k upstream gradients by
@@ -747,6 +753,8 @@ class Group {
   void gnc_summary(GncSummaryDev &sd);
   MargCache *marg_ = nullptr;   // the dense factors of joint_marginal, one per order (marg.cpp), allocated by the first call
   void marg_release();
+  // the batches of a column plan behind a factorisation: Sigma_KK of the kept poses into g1 / g2 (device), d_prow <- their records
+  int marg_sigma(const MargPlan &pl, const int *keep, int K, double *g1, double *g2, DevBuf<int> &d_prow, const char *who);
   // the refusal of the block solves with kb columns (pairs.cpp); own: the call's buffers
   int pairs_setup(long long max_bytes, HessPart own, int kb, HessAnalysis &out);
   // the batches of a plan behind a factorisation: joint (device, zeroed by the caller) <- the blocks of the pairs (pairs.cpp)

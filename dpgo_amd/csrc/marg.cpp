@@ -104,6 +104,46 @@ void Group::marg_release() {
   marg_ = nullptr;
 }
 
+// The batches of a column plan behind a factorisation that succeeded (joint_marginal, candidate_set): per batch the unit
+// right-hand sides, the block solve and the gather of Sigma_KK's entries whose columns it holds, into g1 and (optional) g2 (device,
+// (dof K)^2, the anchor's blocks zeroed by the caller).  d_prow <- the record of every kept pose; returns behind a synchronise.
+int Group::marg_sigma(const MargPlan &pl, const int *keep, int K, double *g1, double *g2, DevBuf<int> &d_prow, const char *who) {
+  CovState &s = *cov_;
+  const int dof = cov_dof(d_);
+  const long long ns = (long long)dof * K, nh = (long long)dof * P0_;
+  // the lists: per row / column of Sigma_KK the unknown of H and the plan's column (-1: the anchor), per kept pose its record
+  std::vector<int> row_unk((size_t)ns, -1), col_of((size_t)ns, -1), prow((size_t)K), col_unknown((size_t)std::max(pl.columns, 1), 0);
+  for (int i = 0; i < K; i++) {
+    prow[i] = own_row(keep[i]);
+    if (pl.col[i] < 0) continue;
+    for (int a = 0; a < dof; a++) {
+      row_unk[(size_t)dof * i + a] = dof * prow[i] + a;
+      col_of[(size_t)dof * i + a] = pl.col[i] + a;
+      col_unknown[(size_t)pl.col[i] + a] = dof * prow[i] + a;
+    }
+  }
+  DevBuf<int> d_row, d_colof, d_unk;
+  DevBuf<double> d_Xb;
+  d_row.upload(row_unk);
+  d_colof.upload(col_of);
+  d_prow.upload(prow);
+  d_unk.upload(col_unknown);
+  d_Xb.alloc((size_t)nh * pl.kb, false);
+  for (int b = 0; b < pl.batches; b++) {
+    const int c0 = b * PAIRS_BATCH, nc = std::min(PAIRS_BATCH, pl.columns - c0);
+    HIP_CHECK(hipMemsetAsync(d_Xb.p, 0, sizeof(double) * (size_t)nh * pl.kb, st_));
+    launch_pairs_rhs(st_, d_unk.p, c0, nc, d_Xb.p, pl.kb);
+    if (spd_msolve_device(s.F, d_Xb.p, nc, pl.kb, st_) != 0) {
+      fprintf(stderr, "[dpgo_amd] ERROR: %s: the solve failed on the device.\n", who);
+      return -1;
+    }
+    launch_marg_gather(st_, (int)ns, d_row.p, d_colof.p, c0, nc, d_Xb.p, pl.kb, g1, g2);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st_));   // (the batch block and the lists are this function's)
+  return 0;
+}
+
 int Group::joint_marginal(const double *X, int ld, const int *keep, int K, int anchor, int base, bool want_info, long long max_bytes,
                           double *cov, double *info, double *logdet, MargResult &out) {
   out = MargResult();
@@ -170,40 +210,15 @@ int Group::joint_marginal(const double *X, int ld, const int *keep, int K, int a
   if (rc != 0) return 0;
   auto t0 = Clock::now();
   if (D && marg_dense_prepare(*D) != 0) return -1;
-  // the lists: per row / column of Sigma_KK the unknown of H and the plan's column (-1: the anchor), per kept pose its record
-  std::vector<int> row_unk((size_t)ns, -1), col_of((size_t)ns, -1), prow((size_t)K), col_unknown((size_t)std::max(pl.columns, 1), 0);
-  for (int i = 0; i < K; i++) {
-    prow[i] = own_row(keep[i]);
-    if (pl.col[i] < 0) continue;
-    for (int a = 0; a < dof; a++) {
-      row_unk[(size_t)dof * i + a] = dof * prow[i] + a;
-      col_of[(size_t)dof * i + a] = pl.col[i] + a;
-      col_unknown[(size_t)pl.col[i] + a] = dof * prow[i] + a;
-    }
-  }
-  DevBuf<int> d_row, d_colof, d_prow, d_unk;
-  DevBuf<double> d_Xb, d_sig, d_cov, d_info;
-  d_row.upload(row_unk);
-  d_colof.upload(col_of);
-  d_prow.upload(prow);
-  d_unk.upload(col_unknown);
-  d_Xb.alloc((size_t)nh * pl.kb, false);
+  DevBuf<int> d_prow;
+  DevBuf<double> d_sig, d_cov, d_info;
   d_cov.alloc((size_t)(n * n));
   if (relative) d_sig.alloc((size_t)(ns * ns));   // (zeroed: the anchor's blocks)
   if (want_info) d_info.alloc((size_t)(n * n) + 1);
   double *dense_val = D ? spd_numeric_values(D->F) : nullptr;
   // the absolute form gathers straight into the dense factor's value array (CSR order == row-major) and into cov
   double *g1 = relative ? d_sig.p : (dense_val ? dense_val : d_cov.p), *g2 = relative || !dense_val ? nullptr : d_cov.p;
-  for (int b = 0; b < pl.batches; b++) {
-    const int c0 = b * PAIRS_BATCH, nc = std::min(PAIRS_BATCH, pl.columns - c0);
-    HIP_CHECK(hipMemsetAsync(d_Xb.p, 0, sizeof(double) * (size_t)nh * pl.kb, st_));
-    launch_pairs_rhs(st_, d_unk.p, c0, nc, d_Xb.p, pl.kb);
-    if (spd_msolve_device(s.F, d_Xb.p, nc, pl.kb, st_) != 0) {
-      fprintf(stderr, "[dpgo_amd] ERROR: joint_marginal: the solve failed on the device.\n");
-      return -1;
-    }
-    launch_marg_gather(st_, (int)ns, d_row.p, d_colof.p, c0, nc, d_Xb.p, pl.kb, g1, g2);
-  }
+  if (marg_sigma(pl, keep, K, g1, g2, d_prow, "joint_marginal") != 0) return -1;
   if (relative) launch_marg_rel(d, st_, K, bpos, d_prow.p, c.X.p, d_sig.p, d_cov.p, dense_val);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(cov, d_cov.p, sizeof(double) * (size_t)(n * n), hipMemcpyDeviceToHost, st_));

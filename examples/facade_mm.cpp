@@ -35,6 +35,13 @@
 //   marginal: cov <row> <the n entries>      marginal: info <row> <the n entries>
 // then   marginal: <OK|NOT_PD|SKIPPED|FAILED> <n> <columns> <batches> <info_not_pd> <logdet, 17 digits>; a last call with the
 // first pose listed twice must fail:   marginal: repeated pose <status>
+// and with `candidates <candidates.g2o> <budget>` through DPGOHashGroup::newton_polish and DPGOHashGroup::candidate_set (trivial
+// loss; pose 0 is the anchor): the file holds candidate edges between poses of the graph.  Per row of the n x n matrices one
+// line each, all entries with 17 digits,
+//   candidates: S <row> <the n entries>      candidates: info <row> <the n entries>
+// per chosen candidate   candidates: step <k> <index> <gain> <d2> <eligible>
+// then   candidates: <OK|NOT_PD|SKIPPED|FAILED> <n> <poses> <selected> <logdet> <d2_joint> <gain_all> <gain_selected> <d2_selected>;
+// a last call with the first candidate joining a pose to itself must fail:   candidates: self pair <status>
 // and with `sensitivity <pose>` through DPGOHashGroup::newton_polish and DPGOHashGroup::measurement_sensitivities (trivial
 // loss; pose 0 is the anchor) with the dof unit columns of the pose: per edge one line, all entries with 17 digits,
 //   sensitivity: e <edge> <the dof x (2 + dof) entries, row a the derivatives of coordinate a of the pose>
@@ -305,6 +312,44 @@ int main(int argc, char **argv) {
     int twice_status = 0;
     dpgo_hash.joint_marginal(Xp, keep, cov, &info, &logdet, 0, base, nullptr, &twice_status);
     fprintf(stderr, "marginal: repeated pose %d\n", twice_status);
+  }
+  if (argc > 8 && !strcmp(argv[6], "candidates")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0 || !dpgo_hash.newton_polish(X, Xp)) return 1;
+    const int d = graph->d(), nc = d * d + d + 2;
+    auto cg = DPGO::Graph::read_g2o(argv[7], 1);
+    const int m = cg->num_edges();
+    std::vector<int> I(m), J(m), pairs((size_t)2 * m);
+    std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m), cand((size_t)m * nc);
+    if (cg->d() != d || m < 1 || dpgo_graph_edges(cg->handle(), I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data()) != 0) return 1;
+    for (int k = 0; k < m; k++) {
+      pairs[2 * k] = I[k]; pairs[2 * k + 1] = J[k];
+      std::copy(&R[(size_t)k * d * d], &R[(size_t)(k + 1) * d * d], &cand[(size_t)k * nc]);
+      std::copy(&t[(size_t)k * d], &t[(size_t)(k + 1) * d], &cand[(size_t)k * nc + d * d]);
+      cand[(size_t)k * nc + d * d + d] = kappa[k];
+      cand[(size_t)k * nc + d * d + d + 1] = tau[k];
+    }
+    std::vector<double> S, res, info, steps;
+    std::vector<int> selected;
+    double sc[5];
+    int status = -1;
+    dpgo_cand_result_t r = {};
+    const bool ok = dpgo_hash.candidate_set(Xp, pairs, cand, atoi(argv[8]), S, res, selected, steps, sc, &info, 0.0, 0, &r, &status);
+    for (int w = 0; ok && w < 2; w++)
+      for (int i = 0; i < r.n; i++) {
+        fprintf(stderr, "candidates: %s %d", w ? "info" : "S", i);
+        for (int j = 0; j < r.n; j++) fprintf(stderr, " %.17g", (w ? info : S)[(size_t)i * r.n + j]);
+        fprintf(stderr, "\n");
+      }
+    for (size_t k = 0; ok && k < selected.size(); k++)
+      fprintf(stderr, "candidates: step %d %d %.17g %.17g %d\n", (int)k, selected[k], steps[4 * k + 1], steps[4 * k + 2], (int)steps[4 * k + 3]);
+    fprintf(stderr, "candidates: %s %d %d %d %.17g %.17g %.17g %.17g %.17g\n", status == DPGO_CAND_OK ? "OK" : status == DPGO_CAND_NOT_PD ? "NOT_PD"
+            : status == DPGO_CAND_SKIPPED ? "SKIPPED" : "FAILED", r.n, r.poses, r.n_selected, sc[0], sc[1], sc[2], sc[3], sc[4]);
+    if (status < 0) return 1;
+    pairs[1] = pairs[0];
+    int self_status = 0;
+    dpgo_hash.candidate_set(Xp, pairs, cand, 1, S, res, selected, steps, sc, &info, 0.0, 0, nullptr, &self_status);
+    fprintf(stderr, "candidates: self pair %d\n", self_status);
   }
   if (argc > 7 && !strcmp(argv[6], "sensitivity")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;

@@ -648,6 +648,65 @@ int dpgo_debug_marg_rel(int device, int d, int nkeep, int base_pos, const double
  * columns, batches, info_not_pd (then info and logdet are zeros), the dense pivots, device_bytes of the dense factor. */
 int dpgo_debug_marg_dense(int device, int n, const double *A, double *cov, double *info, double *logdet, dpgo_marg_result_t *result);
 
+/* ---- joint compatibility and budgeted selection of loop-closure candidates ---------------- */
+/* dpgo_group_pair_covariance gates ONE candidate at a time.  Here ncand candidates are judged together, in its perturbation and
+ * sign conventions.  pairs[ncand][2]: global poses, p != q (-1); a pair may repeat, pairs may share poses, either end may be the
+ * anchor.  candidates[ncand][d^2 + d + 2]: R~, t~, kappa, tau, both weights positive (-1).  Restrictions, anchor and coordinates
+ * as for dpgo_group_covariance; X should be a critical point (dpgo_group_polish); the optimiser is not touched.
+ *   K           the distinct end poses in order of first appearance (p_0, q_0, p_1, ...); n = dof ncand
+ *   cov         (optional) n x n row-major: J Sigma_KK J^T, the joint covariance of the candidates' predicted relative poses;
+ *               symmetric bit for bit; its diagonal blocks are dpgo_group_pair_covariance's `rel`
+ *   S           (optional) n x n: cov + blkdiag(Omega_i^-1), Omega_i = blkdiag(tau_i I_d, 2 kappa_i I_{dof - d})
+ *   residual    n: the stacked residuals of dpgo_group_pair_covariance's gate
+ *   info        with want_joint (else ignored): S^-1 by the dense factor of dpgo_group_joint_marginal, kept with the group per n
+ *   scalars[5]  logdet S, d2_joint = r^T S^-1 r, gain_all = 1/2 (logdet S - sum_i log det Omega_i^-1) (zeros without
+ *               want_joint or with joint_not_pd), gain_selected, d2_selected (the sums over the chosen steps)
+ *   budget      > 0: the greedy selection of at most budget candidates by conditional information gain
+ *               gain_i = 1/2 (log det C_i - log det Omega_i^-1), C_i the candidate's innovation covariance given the candidates
+ *               already chosen; eligible iff C_i is positive definite and (d2_max <= 0 or the CONDITIONAL d2_i <= d2_max); ties go
+ *               to the lowest index.  The loop runs on the device with no host round trip between steps and stops at the first
+ *               step without an eligible candidate.  gain_selected = 1/2 (log det S_sel - log det R_sel) and
+ *               d2_selected = r_sel^T S_sel^-1 r_sel of the chosen principal submatrix
+ *   selected    budget ints: the chosen candidates in order, -1 past n_selected
+ *   steps       budget x 4: index, gain, d2, the number of eligible candidates at that step; zeros past n_selected
+ *   poses       room for 2 ncand ints: K, the first result->poses entries
+ *   result      outcome CAND_OK, CAND_NOT_PD (the anchored H is not positive definite; the outputs are zero) or CAND_SKIPPED
+ *               (device_bytes above max_bytes (> 0) or above half of the free device memory; only poses is written, nothing is
+ *               allocated); joint_not_pd: the factorisation of S met a non-positive pivot -- info and scalars[0..2] are zeros,
+ *               the selection still ran; n, poses, columns, batches: filled for SKIPPED too */
+#define DPGO_CAND_OK 0
+#define DPGO_CAND_NOT_PD 1
+#define DPGO_CAND_SKIPPED 2
+typedef struct dpgo_cand_result {
+  int outcome, unknowns, fronts, levels, max_front, joint_not_pd, n, poses, columns, batches, n_selected, reserved;
+  long long device_bytes;
+  double pivot_min, pivot_max, dense_pivot_min, dense_pivot_max, stationarity, symbolic_s, factor_ms, solve_ms, dense_ms, select_ms;
+} dpgo_cand_result_t;
+int dpgo_group_candidate_set(dpgo_group_t *grp, const double *X, int ld, const int *pairs, int ncand, const double *candidates,
+                             int anchor, int budget, double d2_max, int want_joint, long long max_bytes, double *cov, double *S,
+                             double *residual, double *info, double *scalars, int *selected, double *steps, int *poses,
+                             dpgo_cand_result_t *result);
+/* The same for the RE-WEIGHTED problem at X, by dpgo_graph_pair_covariance_reweighted's recipe and with its caveat. */
+int dpgo_graph_candidate_set_reweighted(const dpgo_graph_t *g, int device, const double *X, int ld, int loss, double loss_reg,
+                                        const int *pairs, int ncand, const double *candidates, int anchor, int budget, double d2_max,
+                                        int want_joint, long long max_bytes, double *cov, double *S, double *residual, double *info,
+                                        double *scalars, int *selected, double *steps, int *poses, dpgo_cand_result_t *result,
+                                        dpgo_edge_summary_t *edge_summary);
+/* Debug: the block kernel on a GIVEN Sigma_KK ((dof nposes)^2, list order), the listed poses' records X (nposes x (d + 1) d) and
+ * kpos[ncand][2], the positions of every candidate's ends in the list: cov (optional), S ((dof ncand)^2), residual (dof ncand).
+ * _host: the shared arithmetic on the host (no device); the other: the kernels.  cov and S agree bit for bit. */
+int dpgo_debug_cand_innov_host(int d, int ncand, int nposes, const int *kpos, const double *X, const double *sigma,
+                               const double *candidates, double *cov, double *S, double *residual);
+int dpgo_debug_cand_innov(int device, int d, int ncand, int nposes, const int *kpos, const double *X, const double *sigma,
+                          const double *candidates, double *cov, double *S, double *residual);
+/* Debug: the selection on a GIVEN S ((dof ncand)^2), r and weights[ncand][2] (kappa, tau), no graph.  selected (budget) and steps
+ * (budget x 4) are read AND written: only the chosen steps are written, entries from *n_selected on keep the caller's values.
+ * sums[2]: gain_selected, d2_selected.  _host: the same steps on the host (no device). */
+int dpgo_debug_cand_select_host(int d, int ncand, int budget, double d2_max, const double *S, const double *r, const double *weights,
+                                int *selected, double *steps, double *sums, int *n_selected);
+int dpgo_debug_cand_select(int device, int d, int ncand, int budget, double d2_max, const double *S, const double *r,
+                           const double *weights, int *selected, double *steps, double *sums, int *n_selected);
+
 /* ---- measurement sensitivities: implicit differentiation of the solution ------------------ */
 /* How does the solution depend on the measurements it was computed from?  At a critical point X* the implicit function
  * theorem gives dX* / dtheta = -H^-1 d_theta g, with H the anchored tangent-space Hessian of dpgo_group_covariance and g the

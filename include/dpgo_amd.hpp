@@ -304,6 +304,39 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_MARG_OK;
   }
+  // Joint compatibility and budgeted selection of loop-closure candidates (dpgo_group_candidate_set).  pairs: 2 m global poses,
+  // p != q; candidates: m (d^2 + d + 2) doubles, R~, t~, kappa, tau as for pair_covariances.  S is resized to n n doubles,
+  // n = dof m: the joint innovation covariance; residual to n; info (optional) to n n: S^-1, and then scalars[0..2] = log det S,
+  // d2_joint, gain_all; selected to the chosen candidates in order (at most budget of them, by conditional information gain,
+  // gated by d2_max > 0 on the conditional d2), steps to 4 doubles per choice: index, gain, d2, eligible; scalars[3..4] =
+  // gain_selected, d2_selected.  X should be a critical point (newton_polish).  Returns true for DPGO_CAND_OK; status: the
+  // DPGO_CAND_* outcome, -1 when the call itself failed (a pose outside the graph, p == q, a weight that is not positive).
+  bool candidate_set(const Matrix &X, const std::vector<int> &pairs, const std::vector<Scalar> &candidates, int budget,
+                     std::vector<Scalar> &S, std::vector<Scalar> &residual, std::vector<int> &selected, std::vector<Scalar> &steps,
+                     Scalar scalars[5], std::vector<Scalar> *info = nullptr, Scalar d2_max = 0.0, int anchor = 0,
+                     dpgo_cand_result_t *result = nullptr, int *status = nullptr, long long max_bytes = 0) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2, m = (int)pairs.size() / 2;
+    const size_t n = (size_t)dof * (size_t)m, nb = (size_t)std::max(budget, 1);
+    S.assign(n * n, 0.0);
+    residual.assign(n, 0.0);
+    if (info) info->assign(n * n, 0.0);
+    selected.assign(nb, -1);
+    steps.assign(4 * nb, 0.0);
+    std::vector<int> poses(2 * (size_t)std::max(m, 1));
+    for (int k = 0; k < 5; k++) scalars[k] = 0.0;
+    dpgo_cand_result_t r = {};
+    const bool sized = m >= 1 && budget >= 0 && candidates.size() == (size_t)m * (size_t)(d * d + d + 2);
+    const int rc = !sized ? -1
+                          : dpgo_group_candidate_set(h_, X.data(), X.rows(), pairs.data(), m, candidates.data(), anchor, budget, d2_max,
+                                                     info ? 1 : 0, max_bytes, nullptr, S.data(), residual.data(),
+                                                     info ? info->data() : nullptr, scalars, selected.data(), steps.data(),
+                                                     poses.data(), &r);
+    selected.resize(rc == 0 ? (size_t)r.n_selected : 0);
+    steps.resize(4 * selected.size());
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_CAND_OK;
+  }
   // Measurement sensitivities by implicit differentiation (dpgo_group_sensitivity): upstream holds k tangent gradients of
   // scalars L_l(X), (dof N) x k column-major by global pose in marginal_covariances' coordinates; sens is resized to
   // k num_edges (2 + dof) doubles, [l][e][d/dkappa, d/dtau, d/dt~, d/deta] with the edges in the graph's order; adjoint
