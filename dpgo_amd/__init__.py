@@ -291,6 +291,14 @@ SYMBOLS = {
                                                    _IP, C.c_int, _DP, _DP, C.c_void_p, C.c_void_p]),
     "dpgo_polish_options_default": (None, [C.c_void_p]),
     "dpgo_group_polish": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, C.c_void_p]),
+    "dpgo_modes_options_default": (None, [C.c_void_p]),
+    "dpgo_group_hessian_modes": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, _DP, _DP, _DP, _DP, _DP,
+                                           C.c_void_p]),
+    "dpgo_debug_modes_init": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, _DP]),
+    "dpgo_debug_modes_gram": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_modes_update": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_modes_ritz_host": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP, _IP]),
+    "dpgo_debug_modes_ritz": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _IP]),
     "dpgo_group_robust_polish": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_longlong,
                                            _DP, C.c_int, _DP, C.c_int, C.c_void_p, C.c_void_p]),
     "dpgo_group_robust_covariance": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
@@ -1412,6 +1420,34 @@ class NodeGroup:
             raise RuntimeError("dpgo_group_polish failed (robust loss, a group that does not host every node, an anchor outside "
                                "the graph, or bad sizes or options)")
         return Xout, r, _polish_log(log, r)
+
+    def hessian_modes(self, X, k, anchor=0, max_bytes=0, **opts):
+        """The k smallest eigenpairs of `covariance`'s anchored Hessian H at X (dpgo_group_hessian_modes): shift-invert block
+        subspace iteration with Rayleigh-Ritz on the covariance's factor.  An indefinite H is an input -- the factor is that of
+        H + mu I, the values are those of H -- and at a polished minimum 1 / values[0] is the largest eigenvalue of the
+        covariance.  1 <= k <= 60, k <= dof (N - 1).  opts: the fields of ModesOptions (guard 4, max_iters 100, max_tries 8,
+        want_escape 0, rel_tol 1e-8, shift 0, seed 1).  Returns a dict:
+          values     (k,): lambda_j ascending;  residuals (k,): |H v_j - lambda_j v_j| from the iteration's recurrence
+          vectors    (k, dof N): row j the unit vector v_j, pose-major by global pose, zeros on the anchor
+          energy     (k, N): |v_j|^2 per pose; rows sum to 1
+          X_escape   with want_escape: where lambda_0 < 0 a lower point along v_0 (result.escaped, F_escape, escape_alpha),
+                     otherwise X; None without
+          result     ModesResult; outcome MODES_CONVERGED, MODES_MAX_ITERS (the last iteration's pairs), MODES_STALLED or
+                     MODES_SKIPPED (more device bytes than max_bytes, when > 0, or than half of what is free).
+        The optimiser's state is not touched."""
+        X, ld = _fcol(X)
+        k = int(k)
+        o = ModesOptions(**opts)
+        N, dof = self.graph.num_poses, _dof(self.d)
+        kk = max(k, 1)
+        values, residuals, vectors, energy = np.zeros(kk), np.zeros(kk), np.zeros((kk, dof * N)), np.zeros((kk, N))
+        Xe = np.array(X, order="F") if o.want_escape else None
+        r = ModesResult()
+        if lib().dpgo_group_hessian_modes(self._h, _dp(X), ld, int(anchor), k, C.byref(o), int(max_bytes), _dp(values), _dp(residuals),
+                                          _dp(vectors), _dp(energy), _dpn(Xe), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_hessian_modes failed (robust loss, a group that does not host every node, an anchor outside "
+                               "the graph, k outside 1 ... min(60, dof (N - 1)), or bad sizes or options)")
+        return {"values": values, "residuals": residuals, "vectors": vectors, "energy": energy, "X_escape": Xe, "result": r}
 
     def robust_polish(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, max_bytes=0, graph=None, **opts):
         """Newton polish of the ROBUST objective F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (dpgo_group_robust_polish):
@@ -2578,6 +2614,108 @@ class PolishResult(C.Structure):
                 ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
                 ("device_bytes", C.c_longlong), ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("factor_ms", C.c_double),
                 ("solve_ms", C.c_double), ("other_ms", C.c_double)]
+
+
+MODES_CONVERGED, MODES_MAX_ITERS, MODES_STALLED, MODES_SKIPPED = 0, 1, 2, 3
+MODES_NAMES = {0: "CONVERGED", 1: "MAX_ITERS", 2: "STALLED", 3: "SKIPPED"}
+
+
+class ModesOptions(C.Structure):
+    """dpgo_modes_options_t: guard, max_iters, max_tries, want_escape, rel_tol, shift, seed."""
+    _fields_ = [("guard", C.c_int), ("max_iters", C.c_int), ("max_tries", C.c_int), ("want_escape", C.c_int),
+                ("rel_tol", C.c_double), ("shift", C.c_double), ("seed", C.c_ulonglong)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().dpgo_modes_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("ModesOptions has no field %r" % k)
+            setattr(self, k, v)
+
+
+class ModesResult(C.Structure):
+    """dpgo_modes_result_t: the outcome of NodeGroup.hessian_modes, its counts, the shift, F at X and at the escape point, the
+    sizes of the factorisation and the host milliseconds of the phases."""
+    _fields_ = [("outcome", C.c_int), ("iterations", C.c_int), ("factorisations", C.c_int), ("shift_tries", C.c_int),
+                ("block", C.c_int), ("negative", C.c_int), ("escaped", C.c_int), ("reserved", C.c_int),
+                ("unknowns", C.c_int), ("fronts", C.c_int), ("levels", C.c_int), ("max_front", C.c_int),
+                ("device_bytes", C.c_longlong), ("mu", C.c_double), ("hmax", C.c_double), ("stationarity", C.c_double),
+                ("escape_alpha", C.c_double), ("F", C.c_double), ("F_escape", C.c_double), ("pivot_min", C.c_double),
+                ("pivot_max", C.c_double), ("symbolic_s", C.c_double), ("factor_ms", C.c_double), ("solve_ms", C.c_double),
+                ("gram_ms", C.c_double), ("ritz_ms", C.c_double), ("update_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+def _modes_blocks(b, *arrays):
+    """The (n, ld) row-major blocks of a modes_*_debug call and their shape: (n, ld, the arrays as contiguous float64)."""
+    out = [np.ascontiguousarray(a, np.float64) for a in arrays]
+    n, ld = out[0].shape
+    if any(a.shape != (n, ld) for a in out) or ld < b or b not in (16, 32, 48, 64) or n < 1:
+        raise ValueError("modes debug: blocks must be (n, ld) with ld >= b, b in {16, 32, 48, 64}")
+    return n, ld, out
+
+
+def modes_init_debug(V, b, seed=1, anchor_row0=-1, dof=0, device=0):
+    """k_modes_init on a GIVEN array (test hook): V (n, ld) -- its columns 0 ... b are overwritten with the start block, entry
+    (i, j) a pure function of (seed, i, j) in (-1, 1), zeros on the rows anchor_row0 ... anchor_row0 + dof; everything else
+    keeps the caller's values.  Returns the new array."""
+    n, ld, (V,) = _modes_blocks(b, V)
+    V = V.copy()
+    rc = lib().dpgo_debug_modes_init(int(device), n, int(b), ld, int(anchor_row0), int(dof), int(seed), _dp(V))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_modes_init failed (%d; -2: a write outside the array)" % rc)
+    return V
+
+
+def modes_gram_debug(W, V, b, device=0):
+    """k_modes_gram and k_modes_reduce on GIVEN blocks W, V (n, ld) (test hook): (G, T), b x b each -- W'W and the mirrored
+    lower triangle of W'V over the columns 0 ... b."""
+    n, ld, (W, V) = _modes_blocks(b, W, V)
+    G, T = np.zeros((b, b)), np.zeros((b, b))
+    rc = lib().dpgo_debug_modes_gram(int(device), n, int(b), ld, _dp(W), _dp(V), _dp(G), _dp(T))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_modes_gram failed (%d; -2: a write outside the arrays)" % rc)
+    return G, T
+
+
+def modes_update_debug(W, V, Cm, theta, b, anchor_row0=-1, dof=0, device=0):
+    """k_modes_update and k_modes_reduce on GIVEN blocks (test hook): returns (V' = W C on the columns 0 ... b with zeros on the
+    anchor's rows -- the other columns keep V's values --, rr (b,), vv (b,)): the column sums of (V C - (W C) diag(theta))^2 and
+    of (W C)^2."""
+    n, ld, (W, V) = _modes_blocks(b, W, V)
+    V = V.copy()
+    Cm = np.ascontiguousarray(Cm, np.float64)
+    theta = np.ascontiguousarray(theta, np.float64)
+    if Cm.shape != (b, b) or theta.shape != (b,):
+        raise ValueError("modes_update_debug: C must be (b, b) and theta (b,)")
+    rr, vv = np.zeros(b), np.zeros(b)
+    rc = lib().dpgo_debug_modes_update(int(device), n, int(b), ld, int(anchor_row0), int(dof), _dp(W), _dp(V), _dp(Cm), _dp(theta),
+                                       _dp(rr), _dp(vv))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_modes_update failed (%d; -2: a write outside the arrays)" % rc)
+    return V, rr, vv
+
+
+def modes_ritz_debug(G=None, T=None, W=None, V=None, b=None, device=0):
+    """The host's eigenproblem of hessian_modes (test hook).  With G, T (b, b; the lower triangles are read): modes_ritz alone, no
+    GPU (dpgo_debug_modes_ritz_host).  With W, V (n, ld) and b: the Gram matrices on the device first.  Returns (theta (used,)
+    ascending, C (b, b) with C'GC = I on the first `used` columns and e_j / sqrt(G_jj) on the others, used)."""
+    used = C.c_int(0)
+    if G is not None:
+        G = np.ascontiguousarray(G, np.float64)
+        T = np.ascontiguousarray(T, np.float64)
+        b = G.shape[0]
+        if G.shape != (b, b) or T.shape != (b, b):
+            raise ValueError("modes_ritz_debug: G and T must be (b, b)")
+        theta, Cm = np.zeros(b), np.zeros((b, b))
+        rc = lib().dpgo_debug_modes_ritz_host(b, _dp(G), _dp(T), _dp(theta), _dp(Cm), C.byref(used))
+    else:
+        n, ld, (W, V) = _modes_blocks(b, W, V)
+        theta, Cm = np.zeros(b), np.zeros((b, b))
+        rc = lib().dpgo_debug_modes_ritz(int(device), n, int(b), ld, _dp(W), _dp(V), _dp(theta), _dp(Cm), C.byref(used))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_modes_ritz failed (%d: bad sizes, or not one column of G has a positive diagonal entry)" % rc)
+    return theta[:used.value].copy(), Cm, used.value
 
 
 GNC_TLS, GNC_GM = 0, 1

@@ -1,5 +1,5 @@
 // C ABI (include/dpgo_amd.h) over the C++ host layer: the public entry points -- graphs, groups, the exchange, PCM, the
-// certificate, covariances, the polish, the staircase -- and nothing that touches the device itself.  The test hooks
+// certificate, covariances, the polish, the Hessian modes, the staircase -- and nothing that touches the device itself.  The test hooks
 // (dpgo_debug_*, dpgo_group_debug_*) are in capi_debug.cpp; what both files share is in capi_util.h.
 #include "capi_util.h"
 
@@ -1037,6 +1037,26 @@ int dpgo_group_polish(dpgo_group_t *h, const double *X, int ld, const dpgo_polis
   return guarded([&] {
     dpgo::PolishResult r;
     const int rc = h->grp->polish(X, ld, opt ? opt->anchor : 0, to_cpp(opt), max_bytes, Xout, ldout, log, log_cap, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+// ---- Hessian modes (modes.h) ----
+void dpgo_modes_options_default(dpgo_modes_options_t *opt) {
+  if (!opt) return;
+  const dpgo::ModesOptions o;
+  opt->guard = o.guard; opt->max_iters = o.max_iters; opt->max_tries = o.max_tries; opt->want_escape = o.want_escape;
+  opt->rel_tol = o.rel_tol; opt->shift = o.shift; opt->seed = o.seed;
+}
+
+int dpgo_group_hessian_modes(dpgo_group_t *h, const double *X, int ld, int anchor, int k, const dpgo_modes_options_t *opts,
+                             long long max_bytes, double *values, double *residuals, double *vectors, double *energy,
+                             double *X_escape, dpgo_modes_result_t *result) {
+  if (!h || !h->grp || !X || !values || !residuals || !vectors || !energy || !result) return -1;
+  return guarded([&] {
+    dpgo::ModesResult r;
+    const int rc = h->grp->hessian_modes(X, ld, anchor, k, to_cpp(opts), max_bytes, values, residuals, vectors, energy, X_escape, r);
     to_c(r, result);
     return rc;
   });

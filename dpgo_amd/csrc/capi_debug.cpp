@@ -889,6 +889,106 @@ int dpgo_debug_cand_select(int device, int d, int ncand, int budget, double d2_m
   });
 }
 
+// ---- the kernels of the Hessian modes on the caller's arrays (modes.h).  The device copies stand between two guard runs of
+// MODES_GUARD doubles that must come back untouched (-2 otherwise) ----
+namespace {
+constexpr size_t MODES_GUARD = 64;
+const double MODES_SENTINEL = -7.25e300;
+struct GuardedBlock {
+  dpgo::DevBuf<double> buf;
+  size_t n = 0;
+  void put(const double *src, size_t count) {
+    n = count;
+    std::vector<double> h(count + 2 * MODES_GUARD, MODES_SENTINEL);
+    std::copy(src, src + count, h.begin() + MODES_GUARD);
+    buf.upload(h);
+  }
+  double *p() { return buf.p + MODES_GUARD; }
+  bool get(double *dst) {   // false: a guard was written
+    std::vector<double> h;
+    buf.download(h);
+    bool ok = true;
+    for (size_t i = 0; i < MODES_GUARD; i++) ok = ok && h[i] == MODES_SENTINEL && h[MODES_GUARD + n + i] == MODES_SENTINEL;
+    if (dst) std::copy(h.begin() + MODES_GUARD, h.begin() + MODES_GUARD + n, dst);
+    return ok;
+  }
+};
+static bool modes_shape_ok(long long n, int b, int ld) { return n >= 1 && n <= (1ll << 40) && b >= 16 && b <= dpgo::MODES_MAX_B && b % 16 == 0 && ld >= b; }
+}  // namespace
+
+int dpgo_debug_modes_init(int device, long long n, int b, int ld, int anchor_row0, int dof, unsigned long long seed, double *V) {
+  if (!modes_shape_ok(n, b, ld) || !V) return -1;
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    GuardedBlock v;
+    v.put(V, (size_t)n * ld);
+    dpgo::launch_modes_init(nullptr, n, b, ld, anchor_row0, dof, seed, nullptr, 1, v.p());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return v.get(V) ? 0 : -2;
+  });
+}
+
+int dpgo_debug_modes_gram(int device, long long n, int b, int ld, const double *W, const double *V, double *G, double *T) {
+  if (!modes_shape_ok(n, b, ld) || !W || !V || !G || !T) return -1;
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    GuardedBlock w, v;
+    w.put(W, (size_t)n * ld);
+    v.put(V, (size_t)n * ld);
+    dpgo::DevBuf<double> part, packed;
+    part.alloc((size_t)dpgo::modes_partials(n, b), false);
+    packed.alloc((size_t)b * (b + 1));
+    dpgo::launch_modes_gram(nullptr, n, b, ld, w.p(), v.p(), part.p);
+    dpgo::launch_modes_reduce_gram(nullptr, dpgo::modes_workgroups(n), b, part.p, packed.p, dpgo::ReadbackFlag{nullptr, nullptr, 0, nullptr});
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<double> h;
+    packed.download(h);
+    dpgo::modes_unpack(b, h.data(), G, T);
+    return w.get(nullptr) && v.get(nullptr) ? 0 : -2;
+  });
+}
+
+int dpgo_debug_modes_update(int device, long long n, int b, int ld, int anchor_row0, int dof, const double *W, double *V,
+                            const double *C, const double *theta, double *rr, double *vv) {
+  if (!modes_shape_ok(n, b, ld) || !W || !V || !C || !theta || !rr || !vv) return -1;
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    GuardedBlock w, v;
+    w.put(W, (size_t)n * ld);
+    v.put(V, (size_t)n * ld);
+    std::vector<double> ct(C, C + (size_t)b * b);
+    ct.insert(ct.end(), theta, theta + b);
+    dpgo::DevBuf<double> cdev, part, sums;
+    cdev.upload(ct);
+    part.alloc((size_t)dpgo::modes_partials(n, b), false);
+    sums.alloc((size_t)2 * b);
+    dpgo::launch_modes_update(nullptr, n, b, ld, anchor_row0, dof, w.p(), v.p(), cdev.p, cdev.p + (size_t)b * b, part.p);
+    dpgo::launch_modes_reduce(nullptr, dpgo::modes_workgroups(n), 2 * b, 2 * b, part.p, sums.p, dpgo::ReadbackFlag{nullptr, nullptr, 0, nullptr});
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<double> h;
+    sums.download(h);
+    std::copy(h.begin(), h.begin() + b, rr);
+    std::copy(h.begin() + b, h.end(), vv);
+    const bool ok_w = w.get(nullptr);
+    return v.get(V) && ok_w ? 0 : -2;
+  });
+}
+
+int dpgo_debug_modes_ritz_host(int b, const double *G, const double *T, double *theta, double *C, int *used) {
+  return guarded([&] { return dpgo::modes_ritz(b, G, T, theta, C, used); });
+}
+
+int dpgo_debug_modes_ritz(int device, long long n, int b, int ld, const double *W, const double *V, double *theta, double *C, int *used) {
+  if (!theta || !C || !used) return -1;
+  std::vector<double> G((size_t)std::max(b, 1) * std::max(b, 1)), T(G.size());
+  const int rc = dpgo_debug_modes_gram(device, n, b, ld, W, V, G.data(), T.data());
+  if (rc != 0) return rc;
+  return guarded([&] { return dpgo::modes_ritz(b, G.data(), T.data(), theta, C, used); });
+}
+
 int dpgo_debug_sens_edge_host(const dpgo_graph_t *g, const double *X, int ld, const double *lambda, double *sens, double *phi) {
   if (!g) return -1;
   return guarded([&] { return dpgo::sens_edge_host(g->g, X, ld, lambda, sens, phi); });

@@ -72,7 +72,7 @@ inline void to_c(const dpgo::EdgeSummary &s, dpgo_edge_summary_t *o) {
   o->num_inter = s.num_inter; o->num_downweighted = s.num_downweighted;
 }
 
-// the analysis' numbers (hess.h), which the seven result structs below carry under the same names
+// the analysis' numbers (hess.h), which the eight result structs below carry under the same names
 template <class C>
 inline void analysis_to_c(const dpgo::HessAnalysis &r, C *o) {
   o->unknowns = r.unknowns; o->fronts = r.fronts; o->levels = r.levels; o->max_front = r.max_front;
@@ -129,4 +129,22 @@ inline void to_c(const dpgo::PolishResult &r, dpgo_polish_result_t *o) {
   o->indefinite = r.indefinite; o->F_initial = r.F_initial; o->F_final = r.F_final;
   o->grad_initial = r.grad_initial; o->grad_final = r.grad_final; o->hmax = r.hmax;
   o->mu_final = r.mu_final; o->total_ms = r.total_ms; o->solve_ms = r.solve_ms; o->other_ms = r.other_ms;
+}
+
+inline dpgo::ModesOptions to_cpp(const dpgo_modes_options_t *opt) {
+  dpgo::ModesOptions o;
+  if (opt) {
+    o.guard = opt->guard; o.max_iters = opt->max_iters; o.max_tries = opt->max_tries; o.want_escape = opt->want_escape;
+    o.rel_tol = opt->rel_tol; o.shift = opt->shift; o.seed = opt->seed;
+  }
+  return o;
+}
+
+inline void to_c(const dpgo::ModesResult &r, dpgo_modes_result_t *o) {
+  analysis_to_c(r, o);
+  o->outcome = r.outcome; o->iterations = r.iterations; o->factorisations = r.factorisations; o->shift_tries = r.shift_tries;
+  o->block = r.block; o->negative = r.negative; o->escaped = r.escaped; o->reserved = 0;
+  o->mu = r.mu; o->hmax = r.hmax; o->stationarity = r.stationarity; o->escape_alpha = r.escape_alpha; o->F = r.F;
+  o->F_escape = r.F_escape; o->solve_ms = r.solve_ms; o->gram_ms = r.gram_ms; o->ritz_ms = r.ritz_ms;
+  o->update_ms = r.update_ms; o->total_ms = r.total_ms;
 }

@@ -21,7 +21,7 @@ struct Group::CovState {
   long long numeric_bytes = 0, selinv_bytes = 0;
   HessPart numeric_part() const { return {numeric_bytes, F.numeric ? 0 : numeric_bytes}; }
   // the Newton polish (polish.cpp): the tangent gradient, the right-hand side / solution of a step, the unshifted diagonal of
-  // H -- dof doubles per own row each
+  // H -- dof doubles per own row each; the Hessian modes (modes.cpp) shift with the same diagonal and escape along g
   DevBuf<double> pol_g, pol_sol, pol_hdiag;
   ~CovState() {
     spd_release_numeric(F);

@@ -99,6 +99,16 @@
 //              of S^-1; and one more line on stdout
 //                  candidates: <outcome> <candidates> <n> <poses> <columns> <batches> <device_bytes> <joint_not_pd> <selected> <d2_joint> <gain_all> <stationarity>
 //              (NOT_PD or SKIPPED: the report is not written); "candidates: not computed (...)" says why not
+//              --hessian_modes K --modes_report FILE [--modes_escape] (likewise; K and FILE both or neither)  behind --polish and
+//              ahead of --staircase / --certify / --verify / --covariance, for the trivial loss and a world of one rank:
+//              dpgo_group_hessian_modes (pose 0 the anchor) gives the K smallest eigenpairs of the anchored Hessian at the
+//              point so far -- at a saddle how negative the curvature is and along which poses, at a minimum 1 / lambda_0, the
+//              largest eigenvalue of the covariance.  The report (17 digits): a line "k <K> n <n> mu <mu> hmax <hmax>", then per
+//              pair a line "<j> <lambda_j> <residual_j> <the pose with the largest share of |v_j|^2> <that share>" and a line
+//              with the n entries of v_j; and one more line on stdout
+//                  modes: <outcome> <iterations> <factorisations> <shift_tries> <block> <negative> <lambda_0> <mu> <device_bytes> <escaped> <F> <F_escape>
+//              (STALLED or SKIPPED: the report is not written).  With --modes_escape and lambda_0 < 0 the lower point along
+//              v_0 becomes the point every later step acts on and the result files hold; "modes: not computed (...)" says why not
 //   options    the hard-coded overrides of :103-120 (dpgo_options_driver)
 //   loop       iterate -> gather -> communicate -> update, timing iterate + update only (:492-531)
 //   stdout     "<iter>: <fobj> <grad>" with 20 digits, then the final summary         (:493-494, 533-536)
@@ -138,7 +148,9 @@ int main(int argc, char **argv) {
   bool dist_init = true, accelerated = true, save = true, certify = false, verify = false, verify_reweighted = false, polish = false, staircase = false, robust_polish = false;
   std::string edge_report, covariance, edge_reliability, gate_candidates, gate_report, robust_covariance, gnc, gnc_report, gnc_filtered;
   std::string sensitivity_report, marginal_set, marginal_report, select_candidates, select_report;
-  int sensitivity_pose = -1, marginal_base = -1, select_budget = -1;
+  std::string modes_report;
+  int sensitivity_pose = -1, marginal_base = -1, select_budget = -1, hessian_modes = 0;
+  bool modes_escape = false;
   double gnc_barc2 = 4.0, select_d2_max = 0.0;
   int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
   std::string rdv;
@@ -165,7 +177,10 @@ int main(int argc, char **argv) {
              "                          there; --marginal_base arg: a member of the set, for the relative form\n"
              "  --select_candidates arg trivial loss, one rank: a .g2o of candidate edges; with --select_report arg their joint\n"
              "                          compatibility and the greedy choice of --select_budget arg (= all) of them by information\n"
-             "                          gain, gated by --select_d2_max arg (= 0: no gate), are written there\n");
+             "                          gain, gated by --select_d2_max arg (= 0: no gate), are written there\n"
+             "  --hessian_modes arg     trivial loss, one rank: the arg (1 ... 60) smallest eigenpairs of the anchored Hessian at the\n"
+             "                          final point (behind --polish: the polished one), written to --modes_report arg; with\n"
+             "                          --modes_escape a lower point along the most negative mode replaces the point\n");
       return 0;
     } else if (a == "--certify") certify = true;
     else if (a.compare(0, 10, "--certify=") == 0) certify = parse_bool(argv[i] + 10);
@@ -196,6 +211,10 @@ int main(int argc, char **argv) {
     else if (const char *v = val("--select_report")) select_report = v;
     else if (const char *v = val("--select_budget")) select_budget = atoi(v);
     else if (const char *v = val("--select_d2_max")) select_d2_max = atof(v);
+    else if (const char *v = val("--hessian_modes")) hessian_modes = atoi(v);
+    else if (const char *v = val("--modes_report")) modes_report = v;
+    else if (a == "--modes_escape") modes_escape = true;
+    else if (a.compare(0, 15, "--modes_escape=") == 0) modes_escape = parse_bool(argv[i] + 15);
     else if (const char *v = val("--sensitivity_pose")) sensitivity_pose = atoi(v);
     else if (const char *v = val("--sensitivity_report")) sensitivity_report = v;
     else if (const char *v = val("--dataset")) dataset = v;
@@ -399,6 +418,49 @@ int main(int argc, char **argv) {
              : pr.outcome == DPGO_POLISH_STALLED ? "STALLED" : "SKIPPED",
              pr.steps, pr.factorisations, pr.indefinite, pr.F_initial, pr.F_final, pr.grad_initial, pr.grad_final);
       if (pr.outcome != DPGO_POLISH_SKIPPED) Xpol.swap(Z);
+    }
+  }
+  if (hessian_modes != 0 || !modes_report.empty()) {
+    if (hessian_modes == 0 || modes_report.empty()) {
+      fprintf(stderr, "--hessian_modes and --modes_report go together.\n");
+      return -1;
+    }
+    if (loss != 0) {
+      if (root) printf("modes: not computed (the Hessian is that of the trivial loss; --loss %s)\n", loss_type.c_str());
+    } else if (world > 1) {
+      if (root) printf("modes: not computed (the group must host every node; %d ranks)\n", world);
+    } else {
+      const int dof = d + d * (d - 1) / 2, n = dof * N, k = hessian_modes, kk = std::max(k, 1);
+      std::vector<double> Xc((size_t)ld * d, 0.0), Z((size_t)ld * d, 0.0), val((size_t)kk), res((size_t)kk), vec((size_t)kk * n),
+          en((size_t)kk * N);
+      dpgo_modes_options_t mo;
+      dpgo_modes_options_default(&mo);
+      mo.want_escape = modes_escape ? 1 : 0;
+      dpgo_modes_result_t mr;
+      if (final_point(Xc.data()) != 0 ||
+          dpgo_group_hessian_modes(grp, Xc.data(), ld, 0, k, &mo, 0, val.data(), res.data(), vec.data(), en.data(), Z.data(), &mr) != 0) {
+        fprintf(stderr, "--hessian_modes takes 1 ... 60, at most dof (num_poses - 1).\n");
+        return -1;
+      }
+      printf("modes: %s %d %d %d %d %d %.17g %.17g %lld %d %.17g %.17g\n",
+             mr.outcome == DPGO_MODES_CONVERGED ? "CONVERGED" : mr.outcome == DPGO_MODES_MAX_ITERS ? "MAX_ITERS"
+             : mr.outcome == DPGO_MODES_STALLED ? "STALLED" : "SKIPPED",
+             mr.iterations, mr.factorisations, mr.shift_tries, mr.block, mr.negative, val[0], mr.mu, mr.device_bytes, mr.escaped, mr.F,
+             mr.F_escape);
+      if (mr.outcome == DPGO_MODES_CONVERGED || mr.outcome == DPGO_MODES_MAX_ITERS) {
+        FILE *f = fopen(modes_report.c_str(), "w");
+        if (!f) { fprintf(stderr, "Cannot write %s.\n", modes_report.c_str()); return -1; }
+        fprintf(f, "k %d n %d mu %.17g hmax %.17g\n", k, n, mr.mu, mr.hmax);
+        for (int j = 0; j < k; j++) {
+          const double *e = &en[(size_t)j * N];
+          const int top = (int)(std::max_element(e, e + N) - e);
+          fprintf(f, "%d %.17g %.17g %d %.17g\n", j, val[j], res[j], top, e[top]);
+          for (int i = 0; i < n; i++) fprintf(f, "%s%.17g", i ? " " : "", vec[(size_t)j * n + i]);
+          fprintf(f, "\n");
+        }
+        fclose(f);
+      }
+      if (mr.escaped) Xpol.swap(Z);
     }
   }
   if (staircase) {

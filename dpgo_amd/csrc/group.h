@@ -35,6 +35,7 @@
 #include "marg.h"
 #include "pairs.h"
 #include "gnc.h"
+#include "modes.h"
 #include "polish.h"
 #include "rely.h"
 #include "robust.h"
@@ -247,6 +248,11 @@ class Group {
   // greedy selection of at most `budget` candidates by conditional information gain on the device
   int candidate_set(const double *X, int ld, const int *pairs, int m, const double *candidates, int anchor, int budget, double d2_max,
                     bool want_joint, long long max_bytes, const CandOut &o, CandResult &out);
+  // ---- Hessian modes (modes.h, modes.cpp): the k smallest eigenpairs of the anchored H by shift-invert block subspace iteration
+  // on the covariance's factor.  values, residuals: k; vectors: k x (dof N), row j the unit vector v_j by global pose; energy:
+  // k x N, |v_j|^2 per pose; X_escape (with want_escape, leading dimension ld): a lower point along v_0 where lambda_0 < 0, else X
+  int hessian_modes(const double *X, int ld, int anchor, int k, const ModesOptions &o, long long max_bytes, double *values,
+                    double *residuals, double *vectors, double *energy, double *X_escape, ModesResult &out);
   // measurement: ncols unit columns solved one at a time with spd_vsolve_device on the same factor; ms: of the solves
   int pairs_vsolve_baseline(const double *X, int ld, int anchor, int ncols, double *ms);
   // ---- measurement sensitivities (sens.h, sens.cpp): the covariance's factor, the adjoints H^-1 c of k upstream gradients by
@@ -736,6 +742,14 @@ class Group {
   };
   int polish_loop(const double *X, int ld, int arow, const PolishOptions &o, const PolishHooks &hooks, double *Xout, int ldout,
                   double *log, int log_cap, PolishResult &out);
+  // The loop of the Hessian modes (modes.cpp) on CertState's X, behind cov_begin.  What depends on the objective is launched by
+  // the caller's hooks, each handed the anchor's own row: hessian -- H at X into the factorisation's values; trial -- F at the
+  // trial point V into slot 2 of the certificate's partials
+  struct ModesHooks {
+    std::function<void(int)> hessian, trial;
+  };
+  int modes_loop(const double *X, int ld, int anchor, int k, const ModesOptions &o, long long max_bytes, const ModesHooks &hooks,
+                 double *values, double *residuals, double *vectors, double *energy, double *X_escape, ModesResult &out);
   struct RobustState;   // the lists and buffers of the robust objective (robust.cpp), allocated by the first call that is not refused
   RobustState *rob_ = nullptr;
   void robust_release();

@@ -1,5 +1,5 @@
 // What every consumer of the anchored tangent-space Hessian's factor (CovState::F, cov_state.h) shares: covariance,
-// pair_covariance, joint_marginal, candidate_set, sensitivity, robust_sensitivity, edge_reliability, polish / robust_polish / gnc, robust_covariance and the
+// pair_covariance, joint_marginal, candidate_set, sensitivity, robust_sensitivity, edge_reliability, polish / robust_polish / gnc, hessian_modes, robust_covariance and the
 // read-backs cov_hessian / robust_hessian.  Stated once, in hess.cpp:
 //
 //  * the analysis' numbers (HessAnalysis, the base of every result struct; Group::cov_analyse in cov.cpp fills it);
@@ -7,7 +7,7 @@
 //  * the verdict (Group::hess_factor, and the part of it polish_loop's own loop shares, Group::hess_refactor).
 //
 // The callers differ in their parts only -- see the "still to allocate" terms at cov_setup, polish_setup, pairs_setup,
-// edge_reliability, joint_marginal and candidate_set.
+// edge_reliability, joint_marginal, candidate_set and modes_loop.
 #pragma once
 
 namespace dpgo {

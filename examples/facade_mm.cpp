@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -42,6 +42,11 @@
 // per chosen candidate   candidates: step <k> <index> <gain> <d2> <eligible>
 // then   candidates: <OK|NOT_PD|SKIPPED|FAILED> <n> <poses> <selected> <logdet> <d2_joint> <gain_all> <gain_selected> <d2_selected>;
 // a last call with the first candidate joining a pose to itself must fail:   candidates: self pair <status>
+// and with `modes <k>` through DPGOHashGroup::newton_polish and DPGOHashGroup::hessian_modes (trivial loss; pose 0 is the anchor):
+// per eigenpair one line, all entries with 17 digits,
+//   modes: v <j> <lambda_j> <residual_j> <the dof N entries of v_j by global pose>
+// then   modes: <CONVERGED|MAX_ITERS|STALLED|SKIPPED|FAILED> <iterations> <factorisations> <shift_tries> <block> <negative> <mu> <hmax>;
+// a last call with k = 61 must fail:   modes: k = 61 <status>
 // and with `sensitivity <pose>` through DPGOHashGroup::newton_polish and DPGOHashGroup::measurement_sensitivities (trivial
 // loss; pose 0 is the anchor) with the dof unit columns of the pose: per edge one line, all entries with 17 digits,
 //   sensitivity: e <edge> <the dof x (2 + dof) entries, row a the derivatives of coordinate a of the pose>
@@ -77,7 +82,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -350,6 +355,27 @@ int main(int argc, char **argv) {
     int self_status = 0;
     dpgo_hash.candidate_set(Xp, pairs, cand, 1, S, res, selected, steps, sc, &info, 0.0, 0, nullptr, &self_status);
     fprintf(stderr, "candidates: self pair %d\n", self_status);
+  }
+  if (argc > 7 && !strcmp(argv[6], "modes")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;
+    if (dpgo_hash.gather(X) != 0 || !dpgo_hash.newton_polish(X, Xp)) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2, N = graph->num_poses(), k = atoi(argv[7]);
+    std::vector<double> values, vectors, residuals, energy;
+    int status = -1;
+    dpgo_modes_result_t r = {};
+    const bool ok = dpgo_hash.hessian_modes(Xp, k, values, vectors, &residuals, &energy, nullptr, 0, &r, &status);
+    for (int j = 0; ok && j < k; j++) {
+      fprintf(stderr, "modes: v %d %.17g %.17g", j, values[j], residuals[j]);
+      for (int i = 0; i < dof * N; i++) fprintf(stderr, " %.17g", vectors[(size_t)j * dof * N + i]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "modes: %s %d %d %d %d %d %.17g %.17g\n", status == DPGO_MODES_CONVERGED ? "CONVERGED" : status == DPGO_MODES_MAX_ITERS ? "MAX_ITERS"
+            : status == DPGO_MODES_STALLED ? "STALLED" : status == DPGO_MODES_SKIPPED ? "SKIPPED" : "FAILED", r.iterations, r.factorisations,
+            r.shift_tries, r.block, r.negative, r.mu, r.hmax);
+    if (status < 0) return 1;
+    int wide_status = 0;
+    dpgo_hash.hessian_modes(Xp, 61, values, vectors, nullptr, nullptr, nullptr, 0, nullptr, &wide_status);
+    fprintf(stderr, "modes: k = 61 %d\n", wide_status);
   }
   if (argc > 7 && !strcmp(argv[6], "sensitivity")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;

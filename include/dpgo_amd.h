@@ -853,6 +853,68 @@ void dpgo_polish_options_default(dpgo_polish_options_t *opt);
 int dpgo_group_polish(dpgo_group_t *grp, const double *X, int ld, const dpgo_polish_options_t *opt, long long max_bytes,
                       double *Xout, int ldout, double *log, int log_cap, dpgo_polish_result_t *result);
 
+/* ---- Hessian modes: the weakest eigenpairs of the anchored Hessian -------------------------- */
+/* Which global directions does the graph determine worst, and -- where H is not positive definite -- how negative is the
+ * curvature, along which poses, and which way is down?  The k smallest eigenpairs (lambda_j, v_j) of the anchored
+ * tangent-space Hessian H of dpgo_group_covariance (the anchor's identity block excluded: every v_j is zero on its rows), by
+ * shift-invert block subspace iteration with Rayleigh-Ritz on the covariance's factor: A = H + mu I is factored with mu = 0
+ * (or opts->shift), on a non-positive pivot with mu = max(10 mu, 1e-3 hmax) at most max_tries times; a block of
+ * b = 16 ceil((k + guard) / 16) <= 64 columns is solved in one batch of the block solve per iteration, the Ritz pairs of A on
+ * A^-1 V come from two b x b Gram matrices, and lambda_j = theta_j - mu.  At a polished minimum 1 / values[0] is the largest
+ * eigenvalue of the covariance.  An indefinite H is an input here, not a refusal.  Restrictions, anchor and coordinates as for
+ * dpgo_group_covariance; the optimiser is not touched.
+ *   k           1 ... 60 and at most n - dof, n = dof N (-1 otherwise)
+ *   values      k: lambda_j ascending;  residuals  k: |H v_j - lambda_j v_j| from the iteration's own recurrence
+ *   vectors     k x n row-major: row j the unit vector v_j, pose-major by global pose
+ *   energy      k x N: |v_j|^2 restricted to pose p -- where the mode lives; every row sums to 1
+ *   X_escape    with want_escape (else ignored, may be NULL): (d+1)N x d, leading dimension ld.  Where lambda_0 < 0: with g the
+ *               tangent gradient, s = -sign(g'v_0) (+1 at zero), alpha_0 = 0.5 / |v_0|_inf and
+ *               pred(alpha) = alpha |g'v_0| + 1/2 alpha^2 |lambda_0|, alpha is halved up to 30 times until
+ *               F(retract(X, alpha s v_0)) <= F(X) - 0.1 pred(alpha): that point, result->F_escape and escape_alpha, escaped = 1;
+ *               otherwise X itself and escaped = 0
+ *   result      outcome CONVERGED (every |R_j| <= rel_tol hmax, j < k), MAX_ITERS (the pairs and residuals of the last
+ *               iteration are delivered), STALLED (no shift made H + mu I positive definite within max_tries, or fewer than k
+ *               columns of the block stayed independent) or SKIPPED (device_bytes -- the numeric phase, one batch of the block
+ *               solve, the two blocks, the partial sums and polish's three vectors -- above max_bytes (> 0), or what is still
+ *               to allocate above half of the free device memory: nothing is allocated, the predictions are filled);
+ *               negative: converged lambda_j < 0; shift_tries: factorisations that met a non-positive pivot */
+#define DPGO_MODES_CONVERGED 0
+#define DPGO_MODES_MAX_ITERS 1
+#define DPGO_MODES_STALLED 2
+#define DPGO_MODES_SKIPPED 3
+typedef struct dpgo_modes_options {
+  int guard, max_iters, max_tries, want_escape;   /* 4 (at least 4), 100, 8, 0 */
+  double rel_tol, shift;                          /* 1e-8, 0 */
+  unsigned long long seed;                        /* 1: of the start block */
+} dpgo_modes_options_t;
+typedef struct dpgo_modes_result {
+  int outcome, iterations, factorisations, shift_tries, block, negative, escaped, reserved;
+  int unknowns, fronts, levels, max_front;
+  long long device_bytes;
+  double mu, hmax, stationarity, escape_alpha, F, F_escape, pivot_min, pivot_max, symbolic_s;
+  double factor_ms, solve_ms, gram_ms, ritz_ms, update_ms, total_ms;
+} dpgo_modes_result_t;
+void dpgo_modes_options_default(dpgo_modes_options_t *opt);
+int dpgo_group_hessian_modes(dpgo_group_t *grp, const double *X, int ld, int anchor, int k, const dpgo_modes_options_t *opts,
+                             long long max_bytes, double *values, double *residuals, double *vectors, double *energy,
+                             double *X_escape, dpgo_modes_result_t *result);
+/* Debug: the kernels of the iteration on the caller's arrays, no graph.  V, W: n x b row-major with row length ld >= b,
+ * b in {16, 32, 48, 64}; the columns b ... ld are neither read nor written.  anchor_row0 / dof: the anchor's rows
+ * anchor_row0 ... anchor_row0 + dof (anchor_row0 < 0: none).
+ *   init    V <- the start block: entry (i, j) a pure function of (seed, i, j), in (-1, 1); zeros on the anchor's rows
+ *   gram    G, T (b x b row-major, symmetric bit for bit): W'W and the mirrored lower triangle of W'V
+ *   update  V <- W C in place (C b x b row-major, theta b), zeros on the anchor's rows; rr, vv (b each): the column sums of
+ *           (V_old C - (W C) diag(theta))^2 and of (W C)^2
+ *   ritz    (_host: no device) T c = theta G c on the lower triangles: theta (b) ascending on the first *used entries, C (b x b)
+ *           with C'GC = I on those columns; a pivot of the scaled G below 1e-12 drops the trailing columns */
+int dpgo_debug_modes_init(int device, long long n, int b, int ld, int anchor_row0, int dof, unsigned long long seed, double *V);
+int dpgo_debug_modes_gram(int device, long long n, int b, int ld, const double *W, const double *V, double *G, double *T);
+int dpgo_debug_modes_update(int device, long long n, int b, int ld, int anchor_row0, int dof, const double *W, double *V,
+                            const double *C, const double *theta, double *rr, double *vv);
+int dpgo_debug_modes_ritz_host(int b, const double *G, const double *T, double *theta, double *C, int *used);
+int dpgo_debug_modes_ritz(int device, long long n, int b, int ld, const double *W, const double *V, double *theta, double *C,
+                          int *used);   /* the Gram matrices of W, V on the device, then the host's eigenproblem */
+
 /* ---- the robust objective: a Newton polish and covariances on its TRUE Hessian ---------------- */
 /* dpgo_group_polish and dpgo_group_covariance serve F = 1/2 tr(X^T M X).  Whoever optimised with a robust loss wants a critical
  * point of   F(X) = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e)   (s_e, rho, the inter rule and delta = loss_reg as in

@@ -406,6 +406,36 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
+  // Hessian modes (dpgo_group_hessian_modes): the k smallest eigenpairs of marginal_covariances' anchored Hessian by shift-invert
+  // block subspace iteration on its factor; an indefinite Hessian is an input (the factor is that of H + mu I).  values and
+  // residuals are resized to k, vectors to k dof N (row j the unit vector v_j by global pose), energy to k N (|v_j|^2 per pose).
+  // X_escape (optional; sets want_escape): where values[0] < 0 a lower point along v_0, otherwise X.  At a polished minimum
+  // 1 / values[0] is the largest eigenvalue of the covariance.  Returns true for DPGO_MODES_CONVERGED; status: the DPGO_MODES_*
+  // outcome, -1 when the call itself failed (robust loss, a group that does not host every node, a bad anchor, k outside
+  // 1 ... min(60, dof (N - 1))).
+  bool hessian_modes(const Matrix &X, int k, std::vector<Scalar> &values, std::vector<Scalar> &vectors,
+                     std::vector<Scalar> *residuals = nullptr, std::vector<Scalar> *energy = nullptr, Matrix *X_escape = nullptr,
+                     int anchor = 0, dpgo_modes_result_t *result = nullptr, int *status = nullptr,
+                     const dpgo_modes_options_t *opt = nullptr, long long max_bytes = 0) const {
+    dpgo_modes_options_t o;
+    dpgo_modes_options_default(&o);
+    if (opt) o = *opt;
+    o.want_escape = X_escape ? 1 : 0;
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2, N = (int)X.rows() / (d + 1), kk = std::max(k, 1);
+    std::vector<Scalar> res_own, en_own;
+    std::vector<Scalar> &res = residuals ? *residuals : res_own, &en = energy ? *energy : en_own;
+    values.assign((size_t)kk, 0.0);
+    res.assign((size_t)kk, 0.0);
+    vectors.assign((size_t)kk * dof * N, 0.0);
+    en.assign((size_t)kk * N, 0.0);
+    if (X_escape) *X_escape = X;
+    dpgo_modes_result_t r = {};
+    const int rc = dpgo_group_hessian_modes(h_, X.data(), X.rows(), anchor, k, &o, max_bytes, values.data(), res.data(), vectors.data(),
+                                            en.data(), X_escape ? X_escape->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_MODES_CONVERGED;
+  }
   // Newton polish of the ROBUST objective F = 1/2 sum_intra s_e + 1/2 sum_inter rho(s_e) (dpgo_group_robust_polish): the loop of
   // newton_polish with the robust F, gradient and Hessian written on the device.  This group is a trivial-loss group that hosts
   // every node of its graph; the loss is an argument.  curvature 1: the true Hessian, with the curvature 2 rho'' of the loss;
