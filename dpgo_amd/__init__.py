@@ -308,6 +308,19 @@ SYMBOLS = {
     "dpgo_group_robust_matrix": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _IP, _IP, _DP, C.c_longlong,
                                            C.POINTER(C.c_longlong)]),
     "dpgo_debug_robust_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP, _DP]),
+    "dpgo_graph_from_edges_info": (C.c_int, [C.c_int, C.c_int, C.c_int, _IP, _IP, _DP, _DP, _DP, _DP, _DP, C.c_int,
+                                             C.POINTER(C.c_void_p)]),
+    "dpgo_graph_edge_information": (C.c_int, [C.c_void_p, _DP, _IP]),
+    "dpgo_group_ml_polish": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int,
+                                       C.c_void_p]),
+    "dpgo_group_ml_covariance": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _IP, C.c_int, _DP, _DP,
+                                           C.c_void_p]),
+    "dpgo_group_ml_hessian": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, _IP, _IP, _DP, C.c_longlong,
+                                        C.POINTER(C.c_longlong), _DP, _DP]),
+    "dpgo_group_ml_eval": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, C.POINTER(C.c_longlong), _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_group_debug_ml_hessian_guarded": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_int, C.c_double, _DP, _DP,
+                                                      C.c_longlong]),
+    "dpgo_debug_ml_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_longlong)]),
     "dpgo_group_robust_sensitivity": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_int, C.c_longlong, _DP,
                                                 C.c_int, C.c_int, _DP, _DP, _DP, C.c_void_p]),
     "dpgo_debug_robust_sens_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
@@ -542,6 +555,15 @@ class Graph:
         lib().dpgo_graph_edges(self._h, _ip(I), _ip(J), _dp(R), _dp(t), _dp(kap), _dp(tau))
         return I, J, R, t, kap, tau
 
+    def edge_information(self):
+        """Every edge's information matrix (dpgo_graph_edge_information): (Omega (m, dof, dof), has).  has False: the graph
+        keeps none of its own (it was built from arrays without them) and Omega is Omega_iso = diag(tau I_d, 2 kappa I)."""
+        dof = _dof(self.d)
+        om, has = np.zeros((self.num_edges, dof, dof)), np.zeros(1, np.int32)
+        if lib().dpgo_graph_edge_information(self._h, _dp(om), _ip(has)) != 0:
+            raise ValueError("dpgo_graph_edge_information failed")
+        return om, bool(has[0])
+
     def node_sizes(self, node):
         v = [C.c_int() for _ in range(4)]
         if lib().dpgo_graph_node_sizes(self._h, node, *[C.byref(x) for x in v]) != 0:
@@ -672,15 +694,28 @@ def read_g2o(filename, num_nodes):
     return Graph(h)
 
 
-def graph_from_edges(d, num_poses, I, J, R, t, kappa, tau, num_nodes):
+def graph_from_edges(d, num_poses, I, J, R, t, kappa, tau, num_nodes, info=None):
+    """The graph of measurements in memory.  info (optional, (m, dof, dof)): every edge's full information matrix, which the
+    graph then keeps for the maximum-likelihood refinement (dpgo_graph_from_edges_info); kappa and tau stay the caller's."""
     I, J = np.ascontiguousarray(I, np.int32), np.ascontiguousarray(J, np.int32)
     R, t = np.ascontiguousarray(R, np.float64), np.ascontiguousarray(t, np.float64)
     kappa, tau = np.ascontiguousarray(kappa, np.float64), np.ascontiguousarray(tau, np.float64)
     h = C.c_void_p()
-    if lib().dpgo_graph_from_edges(d, num_poses, len(I), _ip(I), _ip(J), _dp(R), _dp(t), _dp(kappa), _dp(tau),
-                                   int(num_nodes), C.byref(h)) != 0:
+    if info is None:
+        rc = lib().dpgo_graph_from_edges(d, num_poses, len(I), _ip(I), _ip(J), _dp(R), _dp(t), _dp(kappa), _dp(tau),
+                                         int(num_nodes), C.byref(h))
+    else:
+        info = np.ascontiguousarray(info, np.float64)
+        if info.shape != (len(I), _dof(d), _dof(d)):
+            raise ValueError("graph_from_edges: info must be (m, dof, dof)")
+        rc = lib().dpgo_graph_from_edges_info(d, num_poses, len(I), _ip(I), _ip(J), _dp(R), _dp(t), _dp(kappa), _dp(tau),
+                                              _dp(info), int(num_nodes), C.byref(h))
+    if rc != 0:
         raise ValueError("graph_from_edges failed")
     return Graph(h)
+
+
+Graph.from_edges = staticmethod(graph_from_edges)
 
 
 def spd_solve_host(A_csr, B, leaf=32):
@@ -1563,6 +1598,74 @@ class NodeGroup:
                                  lambda *csr: lib().dpgo_group_robust_hessian(*args, *csr, _dp(g), C.byref(F), _dp(w), _dp(c),
                                                                               *[_dp(a) for a in per]))
         return (ptr, col, val, g, F.value, w, c) + ((tuple(per),) if edges else ())
+
+    def ml_polish(self, X, anchor=0, max_bytes=0, graph=None, **opts):
+        """Maximum-likelihood refinement on the full information matrices (dpgo_group_ml_polish): `polish`'s loop on
+        F_ml = 1/2 sum_e r_e' Omega_e r_e with r_e = (R~^T (R_i^T (t_j - t_i) - t~), Log(R~^T R_i^T R_j)) and the Gauss-Newton
+        Hessian sum J' Omega J -- what g2o, GTSAM and Ceres minimise on the same file.  Start it from the isotropic polished
+        point.  The group is a trivial-loss group that hosts every node; graph (default: the group's own) gives the edges and
+        their Omega (Graph.edge_information).  Returns (Xout, MlResult, log): as `polish`, the F fields F_ml."""
+        X, ld, o, Xout, log = _polish_arg(X, anchor, opts)
+        r = MlResult()
+        if lib().dpgo_group_ml_polish(self._h, (graph or self.graph)._h, _dp(X), ld, C.byref(o), int(max_bytes), _dp(Xout),
+                                      Xout.shape[0], _dp(log), len(log), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_ml_polish failed (a robust-loss group, a group that does not host every node, a graph "
+                               "that is not the group's, an anchor outside it, an information matrix that is not symmetric "
+                               "positive definite, or bad sizes or options)")
+        return Xout, r, _polish_log(log, r.polish)
+
+    def ml_covariance(self, X, anchor=0, pairs=None, max_bytes=0, graph=None):
+        """Marginal pose covariances of the maximum-likelihood objective at X (dpgo_group_ml_covariance): `covariance` on
+        H = sum J' Omega J, the Fisher information -- the marginals g2o and GTSAM hand out.  Returns and outcomes as
+        `covariance`; result.stationarity is the norm of the tangent gradient of F_ml."""
+        X, ld = _fcol(X)
+        marg, cross, pair_args = _pairs_arg(pairs, self.graph.num_poses, _dof(self.d))
+        r = CovResult()
+        if lib().dpgo_group_ml_covariance(self._h, (graph or self.graph)._h, _dp(X), ld, int(anchor), int(max_bytes), *pair_args,
+                                          C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_ml_covariance failed (a robust-loss group, a group that does not host every node, a "
+                               "graph that is not the group's, an anchor or pair outside it, a pair that is not an edge, or an "
+                               "information matrix that is not symmetric positive definite)")
+        return marg, cross, r
+
+    def ml_hessian(self, X, anchor=0, graph=None):
+        """Debug: the anchored Gauss-Newton Hessian of F_ml as the device wrote it (dpgo_group_ml_hessian).  Returns (ptr,
+        col, val, g, F): the CSR of `cov_hessian`, the tangent gradient (dof N by global pose, zeros on the anchor), F_ml."""
+        X, ld = _fcol(X)
+        n = _dof(self.d) * self.graph.num_poses
+        args = (self._h, (graph or self.graph)._h, _dp(X), ld, int(anchor))
+        g, F = np.zeros(n), C.c_double(0)
+        ptr, col, val = _csr_out(n, "dpgo_group_ml_hessian", lambda *csr: lib().dpgo_group_ml_hessian(*args, *csr, None, None),
+                                 lambda *csr: lib().dpgo_group_ml_hessian(*args, *csr, _dp(g), C.byref(F)))
+        return ptr, col, val, g, F.value
+
+    def ml_hessian_guarded(self, X, nnz, anchor=0, graph=None, pad=64, sentinel=-7.25e-300):
+        """Debug: k_ml_hessian on a sentinel-padded array of the call's own (dpgo_group_debug_ml_hessian_guarded).  nnz: the
+        length of `ml_hessian`'s val.  Returns (guards (2, pad) as the device left them, val in `ml_hessian`'s order)."""
+        X, ld = _fcol(X)
+        guards, val = np.zeros((2, int(pad))), np.zeros(int(nnz))
+        if lib().dpgo_group_debug_ml_hessian_guarded(self._h, (graph or self.graph)._h, _dp(X), ld, int(anchor), int(pad),
+                                                     float(sentinel), _dp(guards), _dp(val), len(val)) != 0:
+            raise RuntimeError("dpgo_group_debug_ml_hessian_guarded failed")
+        return guards, val
+
+    def ml_eval(self, X, graph=None, full=False):
+        """F_ml and the per-edge residuals at X on the device (dpgo_group_ml_eval).  Returns (F, r (m, dof), chi2 (m),
+        near_pi): chi2_e = r_e' Omega_e r_e, F = 1/2 sum chi2 in the device's order of summation.  full=True (debug): a fifth
+        item, the dict of what else the edge pass left on the device -- wr (m, dof), grad (m, 2, dof), Ji, Jj, Wi, Wj (m, dof,
+        dof; W = Omega J)."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        F, near = C.c_double(0), C.c_longlong(0)
+        dof = _dof(self.d)
+        r, chi2 = np.zeros((g_.num_edges, dof)), np.zeros(g_.num_edges)
+        wr, grad, jw = np.zeros((g_.num_edges, dof)), np.zeros((g_.num_edges, 2, dof)), np.zeros((g_.num_edges, 4, dof, dof))
+        more = (_dp(wr), _dp(grad), _dp(jw)) if full else (None, None, None)
+        if lib().dpgo_group_ml_eval(self._h, g_._h, _dp(X), ld, C.byref(F), C.byref(near), _dp(r), _dp(chi2), *more) != 0:
+            raise RuntimeError("dpgo_group_ml_eval failed (a robust-loss group, a group that does not host every node, a graph that "
+                               "is not the group's, or an information matrix that is not symmetric positive definite)")
+        out = (F.value, r, chi2, near.value)
+        return out + (dict(wr=wr, grad=grad, Ji=jw[:, 0], Jj=jw[:, 1], Wi=jw[:, 2], Wj=jw[:, 3]),) if full else out
 
     def robust_matrix(self, X, loss, loss_reg=0.25, graph=None):
         """Debug: M_w = sum_e w_e(X) M_e as the device wrote it (dpgo_group_robust_matrix): CSR as `cert_matrix` hands out S."""
@@ -2616,6 +2719,17 @@ class PolishResult(C.Structure):
                 ("solve_ms", C.c_double), ("other_ms", C.c_double)]
 
 
+class MlResult(C.Structure):
+    """dpgo_ml_result_t: `polish` (a PolishResult, whose fields read through), near_pi at the final point, and
+    chi2_initial / chi2_final = 2 F_ml at both ends."""
+    _fields_ = [("polish", PolishResult), ("near_pi", C.c_longlong), ("chi2_initial", C.c_double), ("chi2_final", C.c_double)]
+
+    def __getattr__(self, name):   # (only reached where the struct itself has no such field)
+        if name != "polish" and name in dict(PolishResult._fields_):
+            return getattr(self.polish, name)
+        raise AttributeError(name)
+
+
 MODES_CONVERGED, MODES_MAX_ITERS, MODES_STALLED, MODES_SKIPPED = 0, 1, 2, 3
 MODES_NAMES = {0: "CONVERGED", 1: "MAX_ITERS", 2: "STALLED", 3: "SKIPPED"}
 
@@ -3011,6 +3125,23 @@ def robust_edge_debug(graph, X, loss=LOSS_NONE, loss_reg=0.25):
     if lib().dpgo_debug_robust_edge_host(graph._h, _dp(X), ld, int(loss), float(loss_reg), _dp(w), _dp(c), _dp(rows), _dp(gh)) != 0:
         raise ValueError("dpgo_debug_robust_edge_host failed (a short X, an unknown loss, or a bad loss_reg)")
     return w, c, rows, gh
+
+
+def ml_edge_debug(graph, X):
+    """Debug, no GPU: the per-edge arithmetic of the maximum-likelihood kernels on the host (dpgo_debug_ml_edge_host).
+    Returns a dict: r, wr (m, dof), chi2 (m), Ji, Jj (m, dof, dof: rows r, columns the pose's unknowns), grad (m, 2, dof:
+    J_i' Omega r, J_j' Omega r), blocks (m, 4, dof, dof: the edge's terms of (i, i), (i, j), (j, i), (j, j)), near_pi."""
+    X, ld = _fcol(X)
+    m, dof = graph.num_edges, _dof(graph.d)
+    o = {"r": np.zeros((m, dof)), "wr": np.zeros((m, dof)), "chi2": np.zeros(m), "Ji": np.zeros((m, dof, dof)),
+         "Jj": np.zeros((m, dof, dof)), "grad": np.zeros((m, 2, dof)), "blocks": np.zeros((m, 4, dof, dof))}
+    near = C.c_longlong(0)
+    if lib().dpgo_debug_ml_edge_host(graph._h, _dp(X), ld, *[_dp(o[k]) for k in ("r", "wr", "chi2", "Ji", "Jj", "grad", "blocks")],
+                                     C.byref(near)) != 0:
+        raise ValueError("dpgo_debug_ml_edge_host failed (a short X, an edge outside the graph, or an information matrix of edge "
+                         "... that is not symmetric positive definite: see stderr)")
+    o["near_pi"] = near.value
+    return o
 
 
 def robust_sens_edge_debug(graph, X, lam, loss=LOSS_NONE, loss_reg=0.25):

@@ -64,8 +64,9 @@ int dpgo_read_g2o(const char *filename, int num_nodes, dpgo_graph_t **out) {
   return 0;
 }
 
-int dpgo_graph_from_edges(int d, int num_poses, int m, const int *I, const int *J, const double *R, const double *t,
-                          const double *kappa, const double *tau, int num_nodes, dpgo_graph_t **out) {
+// dpgo_graph_from_edges and dpgo_graph_from_edges_info (info null: the graph keeps no Omega)
+static int graph_from_arrays(int d, int num_poses, int m, const int *I, const int *J, const double *R, const double *t,
+                             const double *kappa, const double *tau, const double *info, int num_nodes, dpgo_graph_t **out) {
   *out = nullptr;
   if ((d != 2 && d != 3) || m <= 0 || num_poses <= 0 || num_nodes < 1 || !I || !J || !R || !t || !kappa || !tau) return -1;
   for (int e = 0; e < m; e++)
@@ -85,8 +86,34 @@ int dpgo_graph_from_edges(int d, int num_poses, int m, const int *I, const int *
     for (int k = 0; k < d; k++) mm.t[k] = t[(size_t)e * d + k];
     mm.kappa = kappa[e]; mm.tau = tau[e];
   }
+  if (info) g->g.info.assign(info, info + (size_t)m * dpgo::graph_dof(d) * dpgo::graph_dof(d));
   if (dpgo::partition(g->g, num_nodes) != 0) { delete g; *out = nullptr; return -1; }
   *out = g;
+  return 0;
+}
+
+int dpgo_graph_from_edges(int d, int num_poses, int m, const int *I, const int *J, const double *R, const double *t,
+                          const double *kappa, const double *tau, int num_nodes, dpgo_graph_t **out) {
+  if (!out) return -1;
+  return graph_from_arrays(d, num_poses, m, I, J, R, t, kappa, tau, nullptr, num_nodes, out);
+}
+
+int dpgo_graph_from_edges_info(int d, int num_poses, int m, const int *I, const int *J, const double *R, const double *t,
+                               const double *kappa, const double *tau, const double *info, int num_nodes, dpgo_graph_t **out) {
+  if (!out) return -1;
+  *out = nullptr;
+  if (!info) return -1;
+  return graph_from_arrays(d, num_poses, m, I, J, R, t, kappa, tau, info, num_nodes, out);
+}
+
+int dpgo_graph_edge_information(const dpgo_graph_t *g, double *out, int *has) {
+  if (!g) return -1;
+  if (has) *has = g->g.has_info() ? 1 : 0;
+  if (out) {
+    std::vector<double> om;
+    dpgo::graph_information(g->g, om);
+    std::copy(om.begin(), om.end(), out);
+  }
   return 0;
 }
 
@@ -701,8 +728,12 @@ int dpgo_graph_filter_edges(const dpgo_graph_t *g, const unsigned char *keep, dp
     auto *f = new dpgo_graph();
     f->g.d = g->g.d;
     f->g.num_poses = g->g.num_poses;
+    const size_t DD = (size_t)dpgo::graph_dof(g->g.d) * dpgo::graph_dof(g->g.d);
     for (size_t e = 0; e < g->g.all.size(); e++)
-      if (keep[e]) f->g.all.push_back(g->g.all[e]);
+      if (keep[e]) {
+        f->g.all.push_back(g->g.all[e]);
+        if (g->g.has_info()) f->g.info.insert(f->g.info.end(), g->g.info.begin() + e * DD, g->g.info.begin() + (e + 1) * DD);
+      }
     if (dpgo::partition(f->g, g->g.num_nodes) != 0) {
       fprintf(stderr, "[dpgo_amd] ERROR: dpgo_graph_filter_edges: no edge kept.\n");
       delete f;
@@ -1118,6 +1149,44 @@ int dpgo_group_robust_matrix(dpgo_group_t *h, const dpgo_graph_t *g, const doubl
                              int *col, double *val, long long cap, long long *nnz) {
   if (!h || !h->grp || !g || !X || !nnz) return -1;
   return guarded([&] { return h->grp->robust_matrix(g->g, X, ld, loss, loss_reg, ptr, col, val, cap, nnz); });
+}
+
+// ---- maximum-likelihood refinement on the full information matrices (ml.h) ----
+int dpgo_group_ml_polish(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, const dpgo_polish_options_t *opt,
+                         long long max_bytes, double *Xout, int ldout, double *log, int log_cap, dpgo_ml_result_t *result) {
+  if (!h || !h->grp || !g || !X || !Xout || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::MlResult r;
+    const int rc = h->grp->ml_polish(g->g, X, ld, opt ? opt->anchor : 0, to_cpp(opt), max_bytes, Xout, ldout, log, log_cap, r);
+    to_c(r, &result->polish);
+    result->near_pi = r.near_pi;
+    result->chi2_initial = r.chi2_initial;
+    result->chi2_final = r.chi2_final;
+    return rc;
+  });
+}
+
+int dpgo_group_ml_covariance(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
+                             const int *pairs, int npairs, double *marginals, double *cross, dpgo_cov_result_t *result) {
+  if (!h || !h->grp || !g || !X || !marginals || !result || npairs < 0 || (npairs > 0 && (!pairs || !cross))) return -1;
+  return guarded([&] {
+    dpgo::CovResult r;
+    const int rc = h->grp->ml_covariance(g->g, X, ld, anchor, max_bytes, pairs, npairs, marginals, cross, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+int dpgo_group_ml_hessian(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, int *ptr, int *col, double *val,
+                          long long cap, long long *nnz, double *grad, double *F) {
+  if (!h || !h->grp || !g || !X || !nnz) return -1;
+  return guarded([&] { return h->grp->ml_hessian(g->g, X, ld, anchor, ptr, col, val, cap, nnz, grad, F); });
+}
+
+int dpgo_group_ml_eval(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, double *F, long long *near_pi, double *r,
+                       double *chi2, double *wr, double *grad, double *jw) {
+  if (!h || !h->grp || !g || !X) return -1;
+  return guarded([&] { return h->grp->ml_eval(g->g, X, ld, F, near_pi, r, chi2, wr, grad, jw); });
 }
 
 // ---- graduated non-convexity (gnc.h) ----

@@ -794,6 +794,18 @@ int dpgo_debug_robust_edge_host(const dpgo_graph_t *g, const double *X, int ld, 
   return guarded([&] { return dpgo::robust_edge_host(g->g, X, ld, loss, loss_reg, w, c, rows, ghat); });
 }
 
+int dpgo_group_debug_ml_hessian_guarded(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, int pad,
+                                        double sentinel, double *guards, double *val, long long cap) {
+  if (!h || !h->grp || !g || !X || !guards || !val) return -1;
+  return guarded([&] { return h->grp->ml_hessian_guarded(g->g, X, ld, anchor, pad, sentinel, guards, val, cap); });
+}
+
+int dpgo_debug_ml_edge_host(const dpgo_graph_t *g, const double *X, int ld, double *r, double *wr, double *chi2, double *Ji,
+                            double *Jj, double *grad, double *blocks, long long *near_pi) {
+  if (!g) return -1;
+  return guarded([&] { return dpgo::ml_edge_host(g->g, X, ld, r, wr, chi2, Ji, Jj, grad, blocks, near_pi); });
+}
+
 int dpgo_group_gnc_eval(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int kind, double mu, double barc2,
                         const int *robust_set, const double *w_in, double *s_rot, double *s_trans, double *w, double *sums) {
   if (!h || !h->grp || !g || !X || !s_rot || !s_trans || !w || !sums) return -1;

@@ -26,11 +26,13 @@
 //   --hessian_modes K --modes_report FILE [--modes_escape]                                          step_modes
 //   --staircase                                                                                     step_staircase
 //   --robust_polish                                                                                 step_robust_polish
+//   --ml_polish                                                                                     step_ml_polish
 //   --certify                                                                                       step_certify
 //   --verify                                                                                        step_verify
 //   --edge_report FILE, --verify_reweighted                                                         step_edges
 //   --covariance FILE                                                                               step_covariance
 //   --robust_covariance FILE                                                                        step_robust_covariance
+//   --ml_covariance FILE, --ml_report FILE                                                          step_ml_covariance, step_ml_report
 //   --gate_candidates FILE --gate_report FILE                                                       step_gate
 //   --sensitivity_pose P --sensitivity_report FILE                                                  step_sensitivity
 //   --edge_reliability FILE                                                                         step_reliability
@@ -63,9 +65,9 @@ struct Args {
   bool dist_init = true, accelerated = true, save = true;
   // the steps after the loop
   std::string gnc, gnc_report, gnc_filtered, modes_report, edge_report, covariance, robust_covariance, gate_candidates, gate_report,
-      sensitivity_report, edge_reliability, marginal_set, marginal_report, select_candidates, select_report;
-  bool polish = false, modes_escape = false, staircase = false, robust_polish = false, certify = false, verify = false,
-       verify_reweighted = false;
+      sensitivity_report, edge_reliability, marginal_set, marginal_report, select_candidates, select_report, ml_covariance, ml_report;
+  bool polish = false, modes_escape = false, staircase = false, robust_polish = false, ml_polish = false, certify = false,
+       verify = false, verify_reweighted = false;
   int hessian_modes = 0, sensitivity_pose = -1, marginal_base = -1, select_budget = -1;
   double gnc_barc2 = 4.0, select_d2_max = 0.0;
 };
@@ -130,7 +132,8 @@ static int parse_args(int argc, char **argv, Args &a) {
       val("--sensitivity_report", a.sensitivity_report), val("--edge_reliability", a.edge_reliability),
       val("--marginal_set", a.marginal_set), val("--marginal_report", a.marginal_report), val("--marginal_base", a.marginal_base),
       val("--select_candidates", a.select_candidates), val("--select_report", a.select_report), val("--select_budget", a.select_budget),
-      val("--select_d2_max", a.select_d2_max)};
+      val("--select_d2_max", a.select_d2_max), on("--ml_polish", a.ml_polish), val("--ml_covariance", a.ml_covariance),
+      val("--ml_report", a.ml_report)};
   if (getenv("RANK")) a.rank = atoi(getenv("RANK"));
   if (getenv("WORLD_SIZE")) a.world = atoi(getenv("WORLD_SIZE"));
   for (int i = 1; i < argc; i++) {
@@ -659,6 +662,74 @@ static int covariance(Run &r, bool robust, const std::string &file) {
 static int step_covariance(Run &r) { return r.a.covariance.empty() ? 0 : covariance(r, false, r.a.covariance); }
 static int step_robust_covariance(Run &r) { return r.a.robust_covariance.empty() ? 0 : covariance(r, true, r.a.robust_covariance); }
 
+// The maximum-likelihood refinement on the file's full information matrices, for any --loss and a world of one rank; on the
+// group that iterated for the trivial loss, on the second, trivial-loss group of --robust_polish otherwise.
+static dpgo_group_t *ml_group(Run &r) {
+  if (r.a.loss == 0) return r.grp;
+  return r.post_group() == 0 ? r.post : nullptr;
+}
+
+// --ml_polish (likewise)  behind --polish / --robust_polish and ahead of every later step, which then acts on its point:
+// dpgo_group_ml_polish (pose 0 the anchor) from the final X, and one more line on stdout
+//     ml polish: <the fields of polish:> <chi2_initial> <chi2_final> <near_pi>
+// with the F fields F_ml; the result files then hold the refined X; with several ranks a line that says why not
+static int step_ml_polish(Run &r) {
+  if (!r.a.ml_polish || r.refused("ml polish")) return 0;
+  std::vector<double> Xc, Z(r.point_size(), 0.0);
+  dpgo_ml_result_t mr;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0) return -1;
+  if (dpgo_group_ml_polish(grp, r.g, Xc.data(), r.ld, nullptr, 0, Z.data(), r.ld, nullptr, 0, &mr) != 0) return -1;
+  const dpgo_polish_result_t &pr = mr.polish;
+  printf("ml polish: %s %d %d %d %.17g %.17g %.17g %.17g %.17g %.17g %lld\n", polish_name(pr.outcome), pr.steps, pr.factorisations,
+         pr.indefinite, pr.F_initial, pr.F_final, pr.grad_initial, pr.grad_final, mr.chi2_initial, mr.chi2_final, mr.near_pi);
+  if (pr.outcome != DPGO_POLISH_SKIPPED) r.Xnow.swap(Z);
+  return 0;
+}
+
+// --ml_covariance FILE (likewise; empty: off)  in --covariance's file format and with its line on stdout under the prefix
+// "ml covariance:", from dpgo_group_ml_covariance at the final X: the marginals of the Fisher information sum J' Omega J
+static int step_ml_covariance(Run &r) {
+  if (r.a.ml_covariance.empty() || r.refused("ml covariance")) return 0;
+  const int dof = r.dof;
+  std::vector<double> Xc, marg((size_t)r.N * dof * dof, 0.0);
+  dpgo_cov_result_t cv;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0) return -1;
+  if (dpgo_group_ml_covariance(grp, r.g, Xc.data(), r.ld, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0) return -1;
+  printf("ml covariance: %s %d %d %d %d %lld %.16g %.16g\n", cov_name(cv.outcome), cv.unknowns, cv.fronts, cv.levels, cv.max_front,
+         cv.device_bytes, cv.pivot_min, cv.stationarity);
+  if (cv.outcome != DPGO_COV_OK) return 0;
+  FILE *f = open_report(r.a.ml_covariance.c_str());
+  if (!f) return -1;
+  for (int p = 0; p < r.N; p++) {
+    fprintf(f, "%d", p);
+    write_upper(f, &marg[(size_t)p * dof * dof], dof);
+    fprintf(f, "\n");
+  }
+  fclose(f);
+  return 0;
+}
+
+// --ml_report FILE (likewise; empty: off)  from dpgo_group_ml_eval at the final X: one header line
+//     # F_ml <F_ml> chi2_total <2 F_ml> edges <m> near_pi <count>
+// then per edge of the graph, in its order,   i j chi2     (17 digits)
+static int step_ml_report(Run &r) {
+  if (r.a.ml_report.empty() || r.refused("ml report")) return 0;
+  std::vector<double> Xc, chi2(r.graph_edges, 0.0);
+  double F = 0;
+  long long near = 0;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0 || r.load_edges() != 0) return -1;
+  if (dpgo_group_ml_eval(grp, r.g, Xc.data(), r.ld, &F, &near, nullptr, chi2.data(), nullptr, nullptr, nullptr) != 0) return -1;
+  FILE *f = open_report(r.a.ml_report.c_str());
+  if (!f) return -1;
+  fprintf(f, "# F_ml %.17g chi2_total %.17g edges %d near_pi %lld\n", F, 2 * F, r.graph_edges, near);
+  for (int e = 0; e < r.graph_edges; e++) fprintf(f, "%d %d %.17g\n", r.I[e], r.J[e], chi2[e]);
+  fclose(f);
+  return 0;
+}
+
 // A .g2o of candidate edges p -> q, read by the loader's edge parser, as dpgo_group_pair_covariance and
 // dpgo_group_candidate_set take it: pairs (p, q) and per candidate R, t, kappa, tau.
 struct Candidates {
@@ -913,9 +984,9 @@ int main(int argc, char **argv) {
   std::vector<double> X;
   std::vector<std::vector<double>> results;
   if (setup(r) != 0 || initialise(r, X) != 0 || solve(r, results) != 0) return -1;
-  for (int (*step)(Run &) : {step_gnc, step_polish, step_modes, step_staircase, step_robust_polish, step_certify, step_verify, step_edges,
-                             step_covariance, step_robust_covariance, step_gate, step_sensitivity, step_reliability, step_marginal,
-                             step_candidates})
+  for (int (*step)(Run &) : {step_gnc, step_polish, step_modes, step_staircase, step_robust_polish, step_ml_polish, step_certify,
+                             step_verify, step_edges, step_covariance, step_robust_covariance, step_ml_covariance, step_ml_report,
+                             step_gate, step_sensitivity, step_reliability, step_marginal, step_candidates})
     if (step(r) != 0) return -1;
   if (r.post) dpgo_group_free(r.post);
   if (a.save && save(r, X, results) != 0) return -1;

@@ -52,13 +52,14 @@ static double trace_inv3(const double a[9]) {
   return (c00 + c11 + c22) / det;
 }
 
-int read_g2o_file(const std::string &filename, int &num_poses, int &d, measurements_t &out) {
+int read_g2o_file(const std::string &filename, int &num_poses, int &d, measurements_t &out, std::vector<double> *info) {
   std::ifstream in(filename);
   if (!in.is_open()) {
     fprintf(stderr, "[dpgo_amd] ERROR: cannot open %s\n", filename.c_str());
     return -1;
   }
   out.clear();
+  if (info) info->clear();
   num_poses = 0;
   d = 0;
   std::string line, token;
@@ -80,6 +81,7 @@ int read_g2o_file(const std::string &filename, int &num_poses, int &d, measureme
       m.tau = 2.0 / ((I11 + I22) / det);
       m.kappa = I33;
       d = 2;
+      if (info) info->insert(info->end(), {I11, I12, I13, I12, I22, I23, I13, I23, I33});
     } else if (token == "EDGE_SE3:QUAT") {
       double dx, dy, dz, qx, qy, qz, qw, I[21];
       ss >> m.ipose >> m.jpose >> dx >> dy >> dz >> qx >> qy >> qz >> qw;
@@ -99,6 +101,12 @@ int read_g2o_file(const std::string &filename, int &num_poses, int &d, measureme
       m.tau = 3.0 / trace_inv3(tc);            // :107-109
       m.kappa = 3.0 / (2.0 * trace_inv3(rc));  // :114-116
       d = 3;
+      if (info) {   // the upper triangle row by row, mirrored
+        const size_t base = info->size();
+        info->resize(base + 36);
+        for (int r = 0, k = 0; r < 6; r++)
+          for (int c = r; c < 6; c++, k++) (*info)[base + 6 * r + c] = (*info)[base + 6 * c + r] = I[k];
+      }
     } else if (token == "VERTEX_SE2" || token == "VERTEX_SE3:QUAT") {
       continue;
     } else {
@@ -148,7 +156,7 @@ int partition(Graph &g, int num_nodes) {
 }
 
 int read_g2o(const std::string &filename, int num_nodes, Graph &g) {
-  if (read_g2o_file(filename, g.num_poses, g.d, g.all) != 0) return -1;
+  if (read_g2o_file(filename, g.num_poses, g.d, g.all, &g.info) != 0) return -1;
   return partition(g, num_nodes);
 }
 
@@ -170,7 +178,24 @@ int scale_edges(const Graph &g, const double *w, Graph &out) {
     out.all[e].kappa *= w[e];
     out.all[e].tau *= w[e];
   }
+  out.info = g.info;
+  if (g.has_info()) {
+    const size_t DD = (size_t)graph_dof(g.d) * graph_dof(g.d);
+    for (size_t e = 0; e < out.all.size(); e++)
+      for (size_t k = 0; k < DD; k++) out.info[e * DD + k] *= w[e];
+  }
   return partition(out, g.num_nodes);
+}
+
+void graph_information(const Graph &g, std::vector<double> &out) {
+  if (g.has_info()) {
+    out = g.info;
+    return;
+  }
+  const int d = g.d, dof = graph_dof(d);
+  out.assign(g.all.size() * (size_t)dof * dof, 0.0);
+  for (size_t e = 0; e < g.all.size(); e++)
+    for (int k = 0; k < dof; k++) out[(e * dof + k) * dof + k] = k < d ? g.all[e].tau : 2.0 * g.all[e].kappa;
 }
 
 int DataInfo::tail(const Measurement &mm) const {

@@ -31,14 +31,24 @@ struct Graph {
   measurements_t all;                          // file order, global pose ids in ipose/jpose, node = 0
   std::vector<measurements_t> measurements;    // per node, inter-node edges duplicated on both endpoints
   std::vector<std::map<int, int>> g_index;     // per node: local pose id -> global pose id
+  // The measurements' full information matrices (ml.h), a side array in the order of `all`: m x dof^2 row-major, dof =
+  // d + d (d - 1) / 2, translation first, then rotation, as the file has them.  Empty: the graph has none (built from arrays
+  // without them), and whoever asks gets Omega_iso = diag(tau I_d, 2 kappa I) (graph_information).
+  std::vector<double> info;
+  bool has_info() const { return !info.empty(); }
 };
+constexpr int graph_dof(int d) { return d + d * (d - 1) / 2; }
+// Omega_e of every edge, m x dof^2: the side array, or Omega_iso where the graph has none
+void graph_information(const Graph &g, std::vector<double> &out);
 
 // Parse a .g2o file (EDGE_SE2 / EDGE_SE3:QUAT; VERTEX_* ignored).  Returns 0 / -1.
-int read_g2o_file(const std::string &filename, int &num_poses, int &d, measurements_t &out);
+// info (optional): per edge the file's information matrix, its upper triangle symmetrised, dof^2 doubles row-major.
+int read_g2o_file(const std::string &filename, int &num_poses, int &d, measurements_t &out, std::vector<double> *info = nullptr);
 // Partition `all` into num_nodes contiguous ranges (DPGO_utils.cpp:147-158).
 int partition(Graph &g, int num_nodes);
 int read_g2o(const std::string &filename, int num_nodes, Graph &g);
-// g with kappa_e, tau_e multiplied by w[e] >= 0 (same poses, partition, R, t, edge order); -1 on a bad weight.
+// g with kappa_e, tau_e (and Omega_e, where g has it) multiplied by w[e] >= 0 (same poses, partition, R, t, edge order); -1 on
+// a bad weight.
 int scale_edges(const Graph &g, const double *w, Graph &out);
 
 // generate_data_info (DPGO_utils.cpp:326-438).

@@ -502,6 +502,7 @@ Group::~Group() {
   chordal_release();
   stair_release();
   robust_release();
+  ml_release();
   marg_release();
   cov_release();
   cert_release();

@@ -33,6 +33,7 @@
 #include "graph.h"
 #include "kernels.h"
 #include "marg.h"
+#include "ml.h"
 #include "pairs.h"
 #include "gnc.h"
 #include "modes.h"
@@ -222,6 +223,22 @@ class Group {
                      double *s_trans, double *rho);
   int robust_matrix(const Graph &g, const double *X, int ld, int loss, double loss_reg, int *ptr, int *col, double *val, long long cap,
                     long long *nnz);
+  // ---- maximum-likelihood refinement on the full information matrices (ml.h, ml.cpp): polish's loop and covariance's tail on
+  // F_ml = 1/2 sum r' Omega r and its Gauss-Newton Hessian.  g: as for the robust objective, with its Omega (or Omega_iso),
+  // every Omega_e symmetric positive definite (-1 otherwise, the edge named).  ml_hessian: the anchored H as cov_hessian hands
+  // it out, optionally with grad (dof N by global pose) and F; ml_eval: F_ml, near_pi and per edge r (dof), chi2, and (debug) what else
+  // the edge pass left: wr (dof), grad (2 dof), jw (ml_jw_doubles)
+  int ml_polish(const Graph &g, const double *X, int ld, int anchor, const PolishOptions &o, long long max_bytes, double *Xout,
+                int ldout, double *log, int log_cap, MlResult &out);
+  int ml_covariance(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs,
+                    double *marginals, double *cross, CovResult &out);
+  int ml_hessian(const Graph &g, const double *X, int ld, int anchor, int *ptr, int *col, double *val, long long cap, long long *nnz,
+                 double *grad, double *F);
+  // debug: k_ml_hessian on a sentinel-padded array of its own; guards: 2 pad doubles, val: the values in ml_hessian's order
+  int ml_hessian_guarded(const Graph &g, const double *X, int ld, int anchor, int pad, double sentinel, double *guards, double *val,
+                         long long cap);
+  int ml_eval(const Graph &g, const double *X, int ld, double *F, long long *near_pi, double *r, double *chi2, double *wr, double *grad,
+              double *jw);
   // ---- graduated non-convexity (gnc.h, gnc.cpp): outlier rejection on the robust objective's plan, one polish_loop per level
   // with the weights of k_gnc_edge.  The restrictions of the robust objective; robust_set (optional, one int per edge): the
   // edges the loss may touch, instead of the inter rule.  Xout: the point (written unless SKIPPED), weights: num_edges, log
@@ -765,6 +782,15 @@ class Group {
   void gnc_alloc();
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
   void gnc_summary(GncSummaryDev &sd);
+  struct MlState;   // the lists and buffers of the maximum-likelihood objective (ml.cpp), allocated by the first call that is not refused
+  MlState *ml_ = nullptr;
+  void ml_release();
+  int ml_begin(const Graph &g, const double *X, int ld, int anchor, const char *who);
+  long long ml_remain() const;
+  void ml_alloc();
+  void ml_edge_pass(const double *Xdev, bool full, int fslot);   // fslot >= 0: F into that slot of the certificate's partial sums
+  void ml_point(int arow, double *g, int slot_g2, int fslot);     // the full edge pass at CertState's X and the gather into g
+  void ml_hessian_launch(int arow);
   MargCache *marg_ = nullptr;   // the dense factors of joint_marginal, one per order (marg.cpp), allocated by the first call
   void marg_release();
   // the batches of a column plan behind a factorisation: Sigma_KK of the kept poses into g1 / g2 (device), d_prow <- their records

@@ -74,6 +74,39 @@ int Group::graph_records_own(const Graph &g, const char *who, std::vector<double
   return 0;
 }
 
+// The lists of a plan from the records (heads on unified own rows) and every edge's four blocks: ascending e, so every list comes
+// out in edge order.  Shared with ml.cpp.
+void robust_plan_lists(int d, int N, std::vector<double> &&rec, const std::vector<int> &eb, size_t nblk, RobustPlan &pl) {
+  const int L = edge_rec_doubles(d), m = (int)(rec.size() / L);
+  pl.d = d;
+  pl.N = N;
+  pl.m = m;
+  pl.nb = (m + EDGE_BLOCK - 1) / EDGE_BLOCK;
+  std::vector<int> ninc(N + 1, 0), nbl(nblk + 1, 0);
+  for (int e = 0; e < m; e++) {
+    int head[4];
+    std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
+    for (int ab = 0; ab < 4; ab++) nbl[eb[4 * (size_t)e + ab] + 1]++;
+    ninc[head[0] + 1]++;
+    ninc[head[1] + 1]++;
+  }
+  for (int p = 0; p < N; p++) ninc[p + 1] += ninc[p];
+  for (size_t k = 0; k < nblk; k++) nbl[k + 1] += nbl[k];
+  pl.inc_ptr = ninc;
+  pl.blk_ptr = nbl;
+  pl.inc.resize(2 * (size_t)m);
+  pl.blk.resize(4 * (size_t)m);
+  std::vector<int> fi(ninc.begin(), ninc.end() - 1), fb(nbl.begin(), nbl.end() - 1);
+  for (int e = 0; e < m; e++) {
+    int head[4];
+    std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
+    pl.inc[fi[head[0]]++] = 2 * e;
+    pl.inc[fi[head[1]]++] = 2 * e + 1;
+    for (int ab = 0; ab < 4; ab++) pl.blk[fb[eb[4 * (size_t)e + ab]]++] = 4 * e + ab;
+  }
+  pl.rec = std::move(rec);
+}
+
 // The arguments, the group (cov_begin), the pattern, and the lists of g on the group's unified own rows -- rebuilt only when
 // the records differ from those of the last call.  Nothing is allocated on the device for them here.  robust_set (optional,
 // one int per edge): overwrites the inter word of the plan's records, which are the key of that comparison.
@@ -95,36 +128,10 @@ int Group::robust_begin(const Graph &g, const double *X, int ld, int loss, doubl
     }
   if (rob_ && rob_->plan.rec.size() == rec.size() && std::memcmp(rob_->plan.rec.data(), rec.data(), rec.size() * sizeof(double)) == 0)
     return 0;
-  RobustPlan pl;
-  pl.d = d_;
-  pl.N = N;
-  pl.m = m;
-  pl.nb = (m + EDGE_BLOCK - 1) / EDGE_BLOCK;
   const size_t nblk = c.bptr_h[N];
   const int BB = B_ * B_;
-  std::vector<int> ninc(N + 1, 0), nbl(nblk + 1, 0);
-  for (int e = 0; e < m; e++) {
-    int head[4];
-    std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
-    for (int ab = 0; ab < 4; ab++) nbl[eb[4 * (size_t)e + ab] + 1]++;
-    ninc[head[0] + 1]++;
-    ninc[head[1] + 1]++;
-  }
-  for (int p = 0; p < N; p++) ninc[p + 1] += ninc[p];
-  for (size_t k = 0; k < nblk; k++) nbl[k + 1] += nbl[k];
-  pl.inc_ptr = ninc;
-  pl.blk_ptr = nbl;
-  pl.inc.resize(2 * (size_t)m);
-  pl.blk.resize(4 * (size_t)m);
-  std::vector<int> fi(ninc.begin(), ninc.end() - 1), fb(nbl.begin(), nbl.end() - 1);
-  for (int e = 0; e < m; e++) {   // ascending e: every list comes out in edge order
-    int head[4];
-    std::memcpy(head, &rec[(size_t)e * L], sizeof(head));
-    pl.inc[fi[head[0]]++] = 2 * e;
-    pl.inc[fi[head[1]]++] = 2 * e + 1;
-    for (int ab = 0; ab < 4; ab++) pl.blk[fb[eb[4 * (size_t)e + ab]]++] = 4 * e + ab;
-  }
-  pl.rec = std::move(rec);
+  RobustPlan pl;
+  robust_plan_lists(d_, N, std::move(rec), eb, nblk, pl);
   // a new graph: the old buffers go, the next call that is not refused allocates
   delete rob_;
   rob_ = new RobustState();

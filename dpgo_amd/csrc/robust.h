@@ -43,6 +43,10 @@ struct RobustPlan {
   std::vector<int> blk_ptr, blk;  // block of the certificate's pattern -> 4 e + 2 role(row) + role(column), ascending
 };
 
+// pl <- the lists of the records rec (heads on unified own rows; moved into the plan) with eb, per edge its blocks (i, i), (i, j),
+// (j, i), (j, j) among the pattern's nblk (robust.cpp; the maximum-likelihood objective's plan is built by it too, ml.cpp)
+void robust_plan_lists(int d, int N, std::vector<double> &&rec, const std::vector<int> &eb, size_t nblk, RobustPlan &pl);
+
 // device (robust.hip); everything is enqueued on st
 // out: 5 arrays of m doubles (s_rot, s_trans, rho, w, c); rows (null: not computed): 2 pose records per edge, (M_e X)_i then
 // (M_e X)_j; the summary goes to sum, and F = F_intra + F_inter to fslot[0] with fslot[1 .. nslot) zeroed (null: neither)

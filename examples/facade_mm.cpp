@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -14,6 +14,9 @@
 // and with `polish` through DPGOHashGroup::newton_polish (trivial loss; pose 0 is the anchor), one line per row of the new point:
 //   polish: x <row> <the d entries, 17 digits>       then
 //   polish: <CONVERGED|MAX_STEPS|STALLED|SKIPPED|FAILED> <steps> <factorisations> <indefinite> <F_initial> <F_final> <grad_initial> <grad_final>
+// and with `ml_polish` through DPGOHashGroup::newton_polish and, from its point, DPGOHashGroup::ml_polish (trivial loss; pose 0 is
+// the anchor; the file's information matrices): the lines of `polish` with the prefix "ml polish:", the F fields F_ml
+// then through DPGOHashGroup::ml_marginal_covariances at the refined point the lines of `covariance` with the prefix "ml covariance:"
 // and with `robust_polish` (a robust loss) through DPGOHashGroup::robust_newton_polish on a second, trivial-loss group of the same
 // graph (max_iterations = 0: nothing is factored for the optimiser), with the loss and loss_reg of the run; the lines of `polish`
 // with the prefix "robust polish:", the F fields those of the robust objective
@@ -82,7 +85,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -188,6 +191,39 @@ int main(int argc, char **argv) {
             : status == DPGO_POLISH_STALLED ? "STALLED" : status == DPGO_POLISH_SKIPPED ? "SKIPPED" : "FAILED",
             r.steps, r.factorisations, r.indefinite, r.F_initial, r.F_final, r.grad_initial, r.grad_final);
     if (status < 0) return 1;
+  }
+  if (argc > 6 && !strcmp(argv[6], "ml_polish")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp, Z;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    int status = -1;
+    dpgo_ml_result_t r = {};
+    dpgo_hash.newton_polish(X, Xp);   // (Xp is X itself where the polish is SKIPPED)
+    dpgo_hash.ml_polish(Xp, Z, &r, &status);
+    for (int i = 0; status >= 0 && status != DPGO_POLISH_SKIPPED && i < Z.rows(); i++) {
+      fprintf(stderr, "ml polish: x %d", i);
+      for (int c = 0; c < Z.cols(); c++) fprintf(stderr, " %.17g", Z.data()[(size_t)c * Z.rows() + i]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "ml polish: %s %d %d %d %.17g %.17g %.17g %.17g\n",
+            status == DPGO_POLISH_CONVERGED ? "CONVERGED" : status == DPGO_POLISH_MAX_STEPS ? "MAX_STEPS"
+            : status == DPGO_POLISH_STALLED ? "STALLED" : status == DPGO_POLISH_SKIPPED ? "SKIPPED" : "FAILED",
+            r.polish.steps, r.polish.factorisations, r.polish.indefinite, r.polish.F_initial, r.polish.F_final, r.polish.grad_initial,
+            r.polish.grad_final);
+    if (status < 0) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2;
+    std::vector<double> marg;
+    int cstatus = -1;
+    dpgo_cov_result_t cr = {};
+    const bool ok = dpgo_hash.ml_marginal_covariances(Z, marg, 0, &cr, &cstatus);
+    for (int p = 0; ok && p < graph->num_poses(); p++) {
+      fprintf(stderr, "ml covariance: %d", p);
+      for (int a = 0; a < dof; a++)
+        for (int b = a; b < dof; b++) fprintf(stderr, " %.17g", marg[((size_t)p * dof + a) * dof + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "ml covariance: %s %d %d %.10e\n", cstatus == DPGO_COV_OK ? "OK" : cstatus == DPGO_COV_NOT_PD ? "NOT_PD"
+            : cstatus == DPGO_COV_SKIPPED ? "SKIPPED" : "FAILED", cr.fronts, cr.levels, cr.stationarity);
+    if (cstatus < 0) return 1;
   }
   if (argc > 6 && !strcmp(argv[6], "robust_polish")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Z;

@@ -97,6 +97,16 @@ void dpgo_graph_free(dpgo_graph_t *g);
 int dpgo_graph_info(const dpgo_graph_t *g, int *d, int *num_poses, int *num_nodes, int *num_edges);
 /* copies the parsed measurements (file order); any output pointer may be NULL */
 int dpgo_graph_edges(const dpgo_graph_t *g, int *I, int *J, double *R, double *t, double *kappa, double *tau);
+/* The measurements' full information matrices, which the maximum-likelihood refinement (dpgo_group_ml_polish, below) uses.
+ * A graph read from a file keeps every edge's Omega (the file's upper triangle, symmetrised; dof x dof, dof = d + d (d - 1) / 2,
+ * translation first, then rotation); dpgo_graph_from_edges keeps none; dpgo_graph_from_edges_info is its sibling with
+ * info: m x dof^2 doubles, row-major, used as given.  kappa and tau are not derived from info: both are the caller's.
+ * dpgo_graph_edge_information: out (num_edges x dof^2, or NULL) <- every edge's Omega, for a graph without one Omega_iso =
+ * diag(tau I_d, 2 kappa I); *has (or NULL) <- whether the graph keeps its own.  dpgo_graph_filter_edges carries Omega along,
+ * dpgo_graph_scale_edges carries it along times w_e. */
+int dpgo_graph_from_edges_info(int d, int num_poses, int m, const int *I, const int *J, const double *R, const double *t,
+                               const double *kappa, const double *tau, const double *info, int num_nodes, dpgo_graph_t **out);
+int dpgo_graph_edge_information(const dpgo_graph_t *g, double *out, int *has);
 /* DPGOProblem::n() / m() -- C++/DPGO/include/DPGO/DPGOProblem.h:241-248 (host only) */
 int dpgo_graph_node_sizes(const dpgo_graph_t *g, int node, int *n0, int *n1, int *m0, int *m1);
 /* neighbour ordering of generate_data_info (C++/DPGO/src/DPGO_utils.cpp:400-418): n1 (node, pose) pairs */
@@ -974,6 +984,56 @@ int dpgo_group_robust_matrix(dpgo_group_t *grp, const dpgo_graph_t *graph, const
                              int *ptr, int *col, double *val, long long cap, long long *nnz);
 int dpgo_debug_robust_edge_host(const dpgo_graph_t *graph, const double *X, int ld, int loss, double loss_reg, double *w, double *c,
                                 double *rows, double *ghat);
+
+/* ---- maximum-likelihood refinement on the full information matrices, with its covariances ---- */
+/* Everything above lives in the isotropic chordal model: the loader reduces every Omega_e to kappa_e, tau_e.  g2o, GTSAM and
+ * Ceres minimise 1/2 sum r' Omega r with the file's Omega and hand out (J' Omega J)^-1.  For an edge e = (i -> j) with measurement
+ * (R~, t~) and information Omega_e (dpgo_graph_edge_information):
+ *     r_t = R~^T (R_i^T (t_j - t_i) - t~),   r_R = Log(R~^T R_i^T R_j)   (rotation vector; d = 2: the angle in (-pi, pi])
+ *     F_ml(X) = 1/2 sum_e r_e' Omega_e r_e,   chi2_e = r_e' Omega_e r_e
+ * in the unknowns and with the anchor convention of dpgo_group_covariance.  The gradient uses the exact Jacobians of r; the
+ * Hessian is the GAUSS-NEWTON one, H = sum_e J_e' Omega_e J_e -- the Fisher information; the second-order term is left out on
+ * purpose.  H is positive semidefinite by construction: NOT_PD means a rank-deficient graph.  The usual recipe is a solve in the
+ * isotropic model (the optimiser, dpgo_group_polish), then this refinement from its point.
+ *
+ * The group is a TRIVIAL-LOSS group that HOSTS EVERY NODE, graph a graph of its poses whose every edge is a block of its
+ * pattern, the anchor a pose of it, every Omega_e symmetric positive definite (checked on the host, the edge named): -1
+ * otherwise.  The optimiser's state is not touched.  Edges whose rotation residual is within 1e-3 of pi are counted (near_pi);
+ * their values are not specified further.
+ *
+ * dpgo_group_ml_polish: the loop, options, outcomes, log and timers of dpgo_group_polish with F_ml, its gradient and H;
+ *   result->polish: as dpgo_group_polish fills it, the F fields F_ml; chi2_initial / chi2_final = 2 F_ml at both ends; near_pi
+ *   at the final point.  SKIPPED by dpgo_group_polish's rule with the arrays of the edge pass counted in.
+ * dpgo_group_ml_covariance: dpgo_group_covariance's factorisation, selected inversion, formats and outcomes on H;
+ *   result->stationarity is the norm of the tangent gradient of F_ml.
+ * dpgo_group_ml_hessian (debug): the anchored H as dpgo_group_cov_hessian hands it out; optionally grad (dof N, by global
+ *   pose, zeros on the anchor) and F.
+ * dpgo_group_ml_eval: F_ml, near_pi and per edge r (num_edges x dof) and chi2 (num_edges); for the tests also what else the
+ *   edge pass left on the device: wr = Omega r (dof), grad (2 dof: the edge's gradient terms of i, of j), jw (4 dof^2:
+ *   J_i, J_j, Omega J_i, Omega J_j, each row-major); any output may be NULL.
+ * dpgo_debug_ml_edge_host (no GPU): the kernels' arithmetic per edge in graph order: r, wr = Omega r (dof), chi2, Ji, Jj
+ *   (dof^2 row-major: rows r, columns the pose's unknowns), grad (2 dof: J_i' Omega r, J_j' Omega r), blocks (4 dof^2: the edge's
+ *   terms of (i, i), (i, j), (j, i), (j, j)); any output may be NULL. */
+typedef struct dpgo_ml_result {
+  dpgo_polish_result_t polish;
+  long long near_pi;
+  double chi2_initial, chi2_final;
+} dpgo_ml_result_t;
+int dpgo_group_ml_polish(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, const dpgo_polish_options_t *opt,
+                         long long max_bytes, double *Xout, int ldout, double *log, int log_cap, dpgo_ml_result_t *result);
+int dpgo_group_ml_covariance(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, long long max_bytes,
+                             const int *pairs, int npairs, double *marginals, double *cross, dpgo_cov_result_t *result);
+int dpgo_group_ml_hessian(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, int *ptr, int *col,
+                          double *val, long long cap, long long *nnz, double *grad, double *F);
+int dpgo_group_ml_eval(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, double *F, long long *near_pi,
+                       double *r, double *chi2, double *wr, double *grad, double *jw);
+/* debug: k_ml_hessian on an array of the call's own -- pad doubles of `sentinel`, the nnz values (sentinels before the launch),
+ * pad more -- instead of the factorisation's.  guards: the 2 pad doubles around the values as the device left them; val (cap >=
+ * nnz of dpgo_group_ml_hessian): the values in that call's order. */
+int dpgo_group_debug_ml_hessian_guarded(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, int pad,
+                                        double sentinel, double *guards, double *val, long long cap);
+int dpgo_debug_ml_edge_host(const dpgo_graph_t *graph, const double *X, int ld, double *r, double *wr, double *chi2, double *Ji,
+                            double *Jj, double *grad, double *blocks, long long *near_pi);
 
 /* ---- graduated non-convexity: which measurements are outliers, and the solution without them ---- */
 /* GNC-TLS and GNC-GM (Yang, Antonante, Tzoumas, Carlone, RA-L 2020) on the device.  s_e = s_rot + s_trans as dpgo_edge_eval_run

@@ -457,6 +457,43 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_POLISH_CONVERGED;
   }
+  // Maximum-likelihood refinement on the measurements' full information matrices (dpgo_group_ml_polish): the loop of newton_polish
+  // on F_ml = 1/2 sum r' Omega r with its Gauss-Newton Hessian -- what g2o, GTSAM and Ceres minimise on the same file.  Start it
+  // from newton_polish's point.  The graph's Omega is the file's (Omega_iso for a graph built from arrays without).  Returns,
+  // status and the rest as newton_polish; result->polish carries its fields.
+  bool ml_polish(const Matrix &X, Matrix &Xout, dpgo_ml_result_t *result = nullptr, int *status = nullptr,
+                 const dpgo_polish_options_t *opt = nullptr, long long max_bytes = 0, std::vector<Scalar> *log = nullptr) const {
+    dpgo_polish_options_t o;
+    dpgo_polish_options_default(&o);
+    if (opt) o = *opt;
+    Xout = X;
+    const int cap = o.max_steps >= 0 ? o.max_steps + 1 : 0;
+    if (log) log->assign((size_t)cap * 5, 0.0);
+    dpgo_ml_result_t r = {};
+    const int rc = dpgo_group_ml_polish(h_, graph_->handle(), X.data(), X.rows(), &o, max_bytes, Xout.data(), Xout.rows(),
+                                        log ? log->data() : nullptr, log ? cap : 0, &r);
+    if (log) log->resize(rc == 0 && r.polish.outcome != DPGO_POLISH_SKIPPED ? (size_t)std::min(cap, r.polish.steps + 1) * 5 : 0);
+    if (status) *status = rc == 0 ? r.polish.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.polish.outcome == DPGO_POLISH_CONVERGED;
+  }
+  // Marginal covariances of the maximum-likelihood objective at X (dpgo_group_ml_covariance): marginal_covariances on
+  // H = sum J' Omega J, the Fisher information.  Arguments, returns and status as marginal_covariances.
+  bool ml_marginal_covariances(const Matrix &X, std::vector<Scalar> &marginals, int anchor = 0, dpgo_cov_result_t *result = nullptr,
+                               int *status = nullptr, const std::vector<int> *pairs = nullptr, std::vector<Scalar> *cross = nullptr,
+                               long long max_bytes = 0) const {
+    const int d = graph_->d(), N = graph_->num_poses();
+    const int dof = d + d * (d - 1) / 2, npairs = pairs && cross ? (int)pairs->size() / 2 : 0;
+    marginals.assign((size_t)N * dof * dof, 0.0);
+    if (cross) cross->assign((size_t)npairs * dof * dof, 0.0);
+    dpgo_cov_result_t r = {};
+    const int rc = dpgo_group_ml_covariance(h_, graph_->handle(), X.data(), X.rows(), anchor, max_bytes,
+                                            npairs ? pairs->data() : nullptr, npairs, marginals.data(),
+                                            npairs ? cross->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_COV_OK;
+  }
   // Graduated non-convexity (dpgo_group_gnc): GNC-TLS / GNC-GM outlier rejection from X on the device.  This group is a
   // trivial-loss group that hosts every node of its graph.  opt NULL: the defaults (TLS, barc2 1); robust_set (optional, one int
   // per edge of the graph): the edges the loss may touch, instead of the inter-node ones.  Xout: the point (X itself for
