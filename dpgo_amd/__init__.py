@@ -330,6 +330,14 @@ SYMBOLS = {
     "dpgo_group_gnc_eval": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_double, _IP, _DP, _DP, _DP, _DP,
                                       _DP]),
     "dpgo_debug_gnc_weight_host": (C.c_int, [C.c_int, C.c_double, C.c_double, _DP, C.c_int, _DP, _DP]),
+    "dpgo_group_ml_gnc": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_void_p, _IP, C.c_longlong, _DP, C.c_int, _DP, _DP,
+                                    C.c_int, C.c_void_p]),
+    "dpgo_group_ml_gnc_eval": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_double, C.c_double, _IP, _DP, C.c_int,
+                                         _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_group_debug_ml_gnc_hessian": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, _IP, _DP, _IP, _IP, _DP,
+                                                  C.c_longlong, C.POINTER(C.c_longlong), _DP]),
+    "dpgo_debug_ml_gnc_edge_host": (C.c_int, [C.c_void_p, _DP, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_longlong)]),
     "dpgo_staircase_options_default": (None, [C.c_void_p]),
     "dpgo_group_staircase": (C.c_int, [C.c_void_p, _DP, C.c_int, C.c_void_p, C.c_longlong, _DP, C.c_int, _DP, C.c_int, _DP, C.c_int,
                                        C.c_void_p]),
@@ -1667,6 +1675,72 @@ class NodeGroup:
         out = (F.value, r, chi2, near.value)
         return out + (dict(wr=wr, grad=grad, Ji=jw[:, 0], Jj=jw[:, 1], Wi=jw[:, 2], Wj=jw[:, 3]),) if full else out
 
+    def ml_gnc(self, graph, X, opt=None, robust_set=None, max_bytes=0):
+        """Graduated non-convexity on the full information matrices (dpgo_group_ml_gnc): `gnc`'s levels on chi2_e =
+        r_e' Omega_e r_e of `ml_polish`'s objective, so that opt.barc2 is a chi2_dof quantile (dof 3 for d = 2, 6 for d = 3:
+        16.266 / 22.458 at 0.999) whatever the noise of an edge.  The robust set is the inter-node edges of `graph`, or the
+        edges with robust_set[e] != 0.  Every level solves the weighted problem with `ml_polish`'s loop; an inner MAX_STEPS
+        is normal (Gauss-Newton converges linearly while the weighted residuals are large) and only an inner STALLED fails the
+        call's level.  An edge of weight exactly 0 contributes exact zeros by selection.  opt: GncOptions (None: the
+        defaults).  Returns (Xout, weights, MlGncResult, log) as `gnc` does, F and s on chi2; result.near_pi counts the
+        edges with w > 0 whose rotation residual is within 1e-3 of pi at the final point, near_pi_all every such edge."""
+        X, ld = _fcol(X)
+        o = GncOptions() if opt is None else opt
+        Xout, w = np.array(X, order="F"), np.ones(graph.num_edges)
+        log = np.zeros((max(int(o.max_levels), 0), 10))
+        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
+        if rs is not None and rs.shape != (graph.num_edges,):
+            raise ValueError("ml_gnc: robust_set must have one entry per edge")
+        r = MlGncResult()
+        if lib().dpgo_group_ml_gnc(self._h, graph._h, _dp(X), ld, C.byref(o), None if rs is None else _ip(rs), int(max_bytes),
+                                   _dp(Xout), Xout.shape[0], _dp(w), _dp(log) if len(log) else None, len(log), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_ml_gnc failed (a robust-loss group, a group that does not host every node, a graph that "
+                               "is not the group's, an information matrix that is not symmetric positive definite, a bad kind, "
+                               "barc2, mu_step, max_levels or anchor, or bad sizes or options)")
+        return Xout, w, r, log[:r.levels].copy()
+
+    def ml_gnc_eval(self, graph, X, kind, mu, barc2, robust_set=None, w_in=None, w_start=None, full=False):
+        """Debug: one edge pass of `ml_gnc` at X (dpgo_group_ml_gnc_eval).  w_in None: WEIGH -- the weight array starts as
+        w_start (default: ones) and weight_mu(chi2_e) is written on the robust set; otherwise FIXED on w_in.  Returns (chi2, w,
+        sums): chi2 unweighted, w the array behind the pass, sums = (sum_{not R} chi2, sum_R w chi2, sum_R rho_mu(chi2),
+        max_R chi2, min_R w, the counts of w == 0, w == 1, 0 < w < 1 over R, near_pi over w > 0, near_pi over every edge).
+        full=True: a fourth item, the dict of what else the pass left on the device -- r, wr = w Omega r (m, dof), grad (m, 2,
+        dof), Ji, Jj, Wi, Wj (m, dof, dof; W = w Omega J; all four zero where w == 0)."""
+        X, ld = _fcol(X)
+        m, dof = graph.num_edges, _dof(self.d)
+        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
+        wi = None if w_in is None else np.ascontiguousarray(w_in, np.float64)
+        w = np.ones(m) if w_start is None else np.array(w_start, np.float64)
+        if any(a is not None and a.shape != (m,) for a in (rs, wi, w)):
+            raise ValueError("ml_gnc_eval: robust_set, w_in and w_start must have one entry per edge")
+        chi2, sums = np.zeros(m), np.zeros(10)
+        r, wr, grad, jw = np.zeros((m, dof)), np.zeros((m, dof)), np.zeros((m, 2, dof)), np.zeros((m, 4, dof, dof))
+        more = (_dp(r), _dp(wr), _dp(grad), _dp(jw)) if full else (None,) * 4
+        if lib().dpgo_group_ml_gnc_eval(self._h, graph._h, _dp(X), ld, int(kind), float(mu), float(barc2),
+                                        None if rs is None else _ip(rs), _dpn(wi), int(bool(full)), _dp(chi2), _dp(w), _dp(sums),
+                                        *more) != 0:
+            raise RuntimeError("dpgo_group_ml_gnc_eval failed (a robust-loss group, a group that does not host every node, a graph "
+                               "that is not the group's, an information matrix that is not symmetric positive definite, a bad "
+                               "kind, mu or barc2, or bad sizes)")
+        out = (chi2, w, sums)
+        return out + (dict(r=r, wr=wr, grad=grad, Ji=jw[:, 0], Jj=jw[:, 1], Wi=jw[:, 2], Wj=jw[:, 3]),) if full else out
+
+    def ml_gnc_hessian(self, graph, X, w, robust_set=None, anchor=0):
+        """Debug: the weighted gradient g_w and the anchored Gauss-Newton Hessian H_w of `ml_gnc` for the given weights as
+        the device wrote them (dpgo_group_debug_ml_gnc_hessian).  Returns (ptr, col, val, g) as `ml_hessian` does."""
+        X, ld = _fcol(X)
+        n = _dof(self.d) * self.graph.num_poses
+        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
+        wi = np.ascontiguousarray(w, np.float64)
+        if wi.shape != (graph.num_edges,) or (rs is not None and rs.shape != wi.shape):
+            raise ValueError("ml_gnc_hessian: w and robust_set must have one entry per edge")
+        args = (self._h, graph._h, _dp(X), ld, int(anchor), None if rs is None else _ip(rs), _dp(wi))
+        g = np.zeros(n)
+        ptr, col, val = _csr_out(n, "dpgo_group_debug_ml_gnc_hessian",
+                                 lambda *csr: lib().dpgo_group_debug_ml_gnc_hessian(*args, *csr, None),
+                                 lambda *csr: lib().dpgo_group_debug_ml_gnc_hessian(*args, *csr, _dp(g)))
+        return ptr, col, val, g
+
     def robust_matrix(self, X, loss, loss_reg=0.25, graph=None):
         """Debug: M_w = sum_e w_e(X) M_e as the device wrote it (dpgo_group_robust_matrix): CSR as `cert_matrix` hands out S."""
         X, ld = _fcol(X)
@@ -2864,6 +2938,18 @@ class GncResult(C.Structure):
                 ("symbolic_s", C.c_double), ("total_ms", C.c_double), ("edge_ms", C.c_double), ("inner_ms", C.c_double)]
 
 
+class MlGncResult(C.Structure):
+    """dpgo_ml_gnc_result_t: `gnc` (a GncResult, whose fields read through) on chi2 -- s_max_initial = max_R chi2 at X0,
+    num_outliers the edges of R with chi2 > barc2 at the final point -- then near_pi, the edges with w > 0 within 1e-3 of pi at
+    the final point, and near_pi_all, every such edge."""
+    _fields_ = [("gnc", GncResult), ("near_pi", C.c_longlong), ("near_pi_all", C.c_longlong)]
+
+    def __getattr__(self, name):   # (only reached where the struct itself has no such field)
+        if name != "gnc" and name in dict(GncResult._fields_):
+            return getattr(self.gnc, name)
+        raise AttributeError(name)
+
+
 def gnc_weight_debug(kind, mu, barc2, s):
     """Debug, no GPU: (w, rho) of graduated non-convexity's surrogate at the values s >= 0, through the kernel's own arithmetic
     (dpgo_debug_gnc_weight_host)."""
@@ -3141,6 +3227,26 @@ def ml_edge_debug(graph, X):
         raise ValueError("dpgo_debug_ml_edge_host failed (a short X, an edge outside the graph, or an information matrix of edge "
                          "... that is not symmetric positive definite: see stderr)")
     o["near_pi"] = near.value
+    return o
+
+
+def ml_gnc_edge_debug(graph, X, w):
+    """Debug, no GPU: the per-edge arithmetic of `ml_gnc`'s weighted edge pass on the host (dpgo_debug_ml_gnc_edge_host) for
+    the weights w (one per edge, each in [0, 1]).  Returns a dict: r, wr = w Omega r (m, dof), chi2 (m, unweighted), grad (m, 2,
+    dof), Ji, Jj, Wi, Wj (m, dof, dof; W = w Omega J; the four are zero where w == 0), near_pi (over w > 0), near_pi_all."""
+    X, ld = _fcol(X)
+    m, dof = graph.num_edges, _dof(graph.d)
+    w = np.ascontiguousarray(w, np.float64)
+    if w.shape != (m,):
+        raise ValueError("ml_gnc_edge_debug: w must have one entry per edge")
+    o = {"r": np.zeros((m, dof)), "wr": np.zeros((m, dof)), "chi2": np.zeros(m), "grad": np.zeros((m, 2, dof))}
+    jw = np.zeros((m, 4, dof, dof))
+    near, near_all = C.c_longlong(0), C.c_longlong(0)
+    if lib().dpgo_debug_ml_gnc_edge_host(graph._h, _dp(X), ld, _dp(w), *[_dp(o[k]) for k in ("r", "wr", "chi2", "grad")], _dp(jw),
+                                         C.byref(near), C.byref(near_all)) != 0:
+        raise ValueError("dpgo_debug_ml_gnc_edge_host failed (a short X, an edge outside the graph, a weight outside [0, 1], or an "
+                         "information matrix that is not symmetric positive definite: see stderr)")
+    o.update(Ji=jw[:, 0], Jj=jw[:, 1], Wi=jw[:, 2], Wj=jw[:, 3], near_pi=near.value, near_pi_all=near_all.value)
     return o
 
 

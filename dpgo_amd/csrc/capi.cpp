@@ -1197,25 +1197,49 @@ void dpgo_gnc_options_default(dpgo_gnc_options_t *opt) {
   dpgo_polish_options_default(&opt->inner);
 }
 
+static void to_c(const dpgo::GncResult &r, dpgo_gnc_result_t *result) {
+  result->outcome = r.outcome; result->levels = r.levels; result->steps = r.steps; result->factorisations = r.factorisations;
+  result->inner_outcome = r.inner_outcome; result->mu_initial = r.mu_initial; result->mu_final = r.mu_final;
+  result->s_max_initial = r.s_max_initial; result->F_initial = r.F_initial; result->F_weighted_final = r.F_weighted_final;
+  result->F_surrogate_final = r.F_surrogate_final; result->num_robust = r.num_robust; result->num_zero = r.num_zero;
+  result->num_one = r.num_one; result->num_between = r.num_between; result->num_outliers = r.num_outliers;
+  result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
+  result->edge_ms = r.edge_ms; result->inner_ms = r.inner_ms;
+}
+
+static dpgo::GncOptions to_cpp(const dpgo_gnc_options_t *opt) {
+  dpgo::GncOptions o;
+  if (opt) {
+    o.kind = opt->kind; o.barc2 = opt->barc2; o.mu_step = opt->mu_step; o.max_levels = opt->max_levels;
+    o.inner = to_cpp(&opt->inner); o.anchor = opt->inner.anchor;
+  }
+  return o;
+}
+
 int dpgo_group_gnc(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, const dpgo_gnc_options_t *opt,
                    const int *robust_set, long long max_bytes, double *Xout, int ldout, double *weights, double *log, int log_cap,
                    dpgo_gnc_result_t *result) {
   if (!h || !h->grp || !g || !X || !Xout || !weights || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
   return guarded([&] {
-    dpgo::GncOptions o;
-    if (opt) {
-      o.kind = opt->kind; o.barc2 = opt->barc2; o.mu_step = opt->mu_step; o.max_levels = opt->max_levels;
-      o.inner = to_cpp(&opt->inner); o.anchor = opt->inner.anchor;
-    }
+    const dpgo::GncOptions o = to_cpp(opt);
     dpgo::GncResult r;
     const int rc = h->grp->gnc(g->g, X, ld, o, robust_set, max_bytes, Xout, ldout, weights, log, log_cap, r);
-    result->outcome = r.outcome; result->levels = r.levels; result->steps = r.steps; result->factorisations = r.factorisations;
-    result->inner_outcome = r.inner_outcome; result->mu_initial = r.mu_initial; result->mu_final = r.mu_final;
-    result->s_max_initial = r.s_max_initial; result->F_initial = r.F_initial; result->F_weighted_final = r.F_weighted_final;
-    result->F_surrogate_final = r.F_surrogate_final; result->num_robust = r.num_robust; result->num_zero = r.num_zero;
-    result->num_one = r.num_one; result->num_between = r.num_between; result->num_outliers = r.num_outliers;
-    result->device_bytes = r.device_bytes; result->symbolic_s = r.symbolic_s; result->total_ms = r.total_ms;
-    result->edge_ms = r.edge_ms; result->inner_ms = r.inner_ms;
+    to_c(r, result);
+    return rc;
+  });
+}
+
+// ---- graduated non-convexity on the maximum-likelihood objective (ml_gnc.h) ----
+int dpgo_group_ml_gnc(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, const dpgo_gnc_options_t *opt,
+                      const int *robust_set, long long max_bytes, double *Xout, int ldout, double *weights, double *log, int log_cap,
+                      dpgo_ml_gnc_result_t *result) {
+  if (!h || !h->grp || !g || !X || !Xout || !weights || !result || log_cap < 0 || (log_cap > 0 && !log)) return -1;
+  return guarded([&] {
+    dpgo::MlGncResult r;
+    const int rc = h->grp->ml_gnc(g->g, X, ld, to_cpp(opt), robust_set, max_bytes, Xout, ldout, weights, log, log_cap, r);
+    to_c(r, &result->gnc);
+    result->near_pi = r.near_pi;
+    result->near_pi_all = r.near_pi_all;
     return rc;
   });
 }

@@ -816,6 +816,27 @@ int dpgo_debug_gnc_weight_host(int kind, double mu, double barc2, const double *
   return guarded([&] { return dpgo::gnc_weight_host(kind, mu, barc2, s, n, w, rho); });
 }
 
+int dpgo_group_ml_gnc_eval(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int kind, double mu, double barc2,
+                           const int *robust_set, const double *w_in, int full, double *chi2, double *w, double *sums, double *r,
+                           double *wr, double *grad, double *jw) {
+  if (!h || !h->grp || !g || !X || !chi2 || !w || !sums) return -1;
+  return guarded([&] {
+    return h->grp->ml_gnc_eval(g->g, X, ld, kind, mu, barc2, robust_set, w_in, full != 0, chi2, w, sums, r, wr, grad, jw);
+  });
+}
+
+int dpgo_group_debug_ml_gnc_hessian(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, const int *robust_set,
+                                    const double *w_in, int *ptr, int *col, double *val, long long cap, long long *nnz, double *grad) {
+  if (!h || !h->grp || !g || !X || !w_in || !nnz) return -1;
+  return guarded([&] { return h->grp->ml_gnc_hessian(g->g, X, ld, anchor, robust_set, w_in, ptr, col, val, cap, nnz, grad); });
+}
+
+int dpgo_debug_ml_gnc_edge_host(const dpgo_graph_t *g, const double *X, int ld, const double *w, double *r, double *wr, double *chi2,
+                                double *grad, double *jw, long long *near_pi, long long *near_pi_all) {
+  if (!g) return -1;
+  return guarded([&] { return dpgo::ml_gnc_edge_host(g->g, X, ld, w, r, wr, chi2, grad, jw, near_pi, near_pi_all); });
+}
+
 int dpgo_debug_pairs_vsolve_baseline(dpgo_group_t *h, const double *X, int ld, int anchor, int ncols, double *ms) {
   if (!h || !h->grp || !X || !ms || ncols < 1) return -1;
   return guarded([&] { return h->grp->pairs_vsolve_baseline(X, ld, anchor, ncols, ms); });

@@ -27,6 +27,7 @@
 //   --staircase                                                                                     step_staircase
 //   --robust_polish                                                                                 step_robust_polish
 //   --ml_polish                                                                                     step_ml_polish
+//   --ml_gnc tls|gm [--ml_gnc_barc2 V] [--ml_gnc_report FILE]                                       step_ml_gnc
 //   --certify                                                                                       step_certify
 //   --verify                                                                                        step_verify
 //   --edge_report FILE, --verify_reweighted                                                         step_edges
@@ -65,11 +66,12 @@ struct Args {
   bool dist_init = true, accelerated = true, save = true;
   // the steps after the loop
   std::string gnc, gnc_report, gnc_filtered, modes_report, edge_report, covariance, robust_covariance, gate_candidates, gate_report,
-      sensitivity_report, edge_reliability, marginal_set, marginal_report, select_candidates, select_report, ml_covariance, ml_report;
+      sensitivity_report, edge_reliability, marginal_set, marginal_report, select_candidates, select_report, ml_covariance, ml_report,
+      ml_gnc, ml_gnc_report;
   bool polish = false, modes_escape = false, staircase = false, robust_polish = false, ml_polish = false, certify = false,
        verify = false, verify_reweighted = false;
   int hessian_modes = 0, sensitivity_pose = -1, marginal_base = -1, select_budget = -1;
-  double gnc_barc2 = 4.0, select_d2_max = 0.0;
+  double gnc_barc2 = 4.0, select_d2_max = 0.0, ml_gnc_barc2 = 0.0;   // (ml_gnc_barc2 0: the chi2_dof quantile at 0.999)
 };
 
 static bool parse_bool(const char *s) { return !(strcmp(s, "false") == 0 || strcmp(s, "0") == 0); }
@@ -133,7 +135,8 @@ static int parse_args(int argc, char **argv, Args &a) {
       val("--marginal_set", a.marginal_set), val("--marginal_report", a.marginal_report), val("--marginal_base", a.marginal_base),
       val("--select_candidates", a.select_candidates), val("--select_report", a.select_report), val("--select_budget", a.select_budget),
       val("--select_d2_max", a.select_d2_max), on("--ml_polish", a.ml_polish), val("--ml_covariance", a.ml_covariance),
-      val("--ml_report", a.ml_report)};
+      val("--ml_report", a.ml_report), val("--ml_gnc", a.ml_gnc), val("--ml_gnc_barc2", a.ml_gnc_barc2),
+      val("--ml_gnc_report", a.ml_gnc_report)};
   if (getenv("RANK")) a.rank = atoi(getenv("RANK"));
   if (getenv("WORLD_SIZE")) a.world = atoi(getenv("WORLD_SIZE"));
   for (int i = 1; i < argc; i++) {
@@ -191,6 +194,13 @@ struct Run {
   std::vector<double> Xnow;      // the point a step after the loop has put in the optimiser's place (empty: none has)
   std::vector<int> I, J;         // the graph's edges in file order, and whether each joins two nodes: see load_edges()
   std::vector<unsigned char> inter;
+  dpgo_graph_t *ml_kept = nullptr;   // behind --ml_gnc: the graph without the edges of weight 0, for --ml_covariance / --ml_report
+  std::vector<int> ml_kept_edges;    // their numbers in the graph
+
+  // the graph the maximum-likelihood covariance and report act on, and the graph's number of its edge e
+  dpgo_graph_t *ml_graph() const { return ml_kept ? ml_kept : g; }
+  int ml_edges() const { return ml_kept ? (int)ml_kept_edges.size() : graph_edges; }
+  int ml_edge(int e) const { return ml_kept ? ml_kept_edges[e] : e; }
 
   explicit Run(const Args &args) : a(args) {}
 
@@ -687,8 +697,69 @@ static int step_ml_polish(Run &r) {
   return 0;
 }
 
+// --ml_gnc tls|gm (likewise; empty: off) --ml_gnc_barc2 V (default: the chi2_dof quantile at 0.999, 16.266 for d = 2 and 22.458
+// for d = 3)  behind --ml_polish and ahead of every later step, which then acts on its point: dpgo_group_ml_gnc (graduated
+// non-convexity on chi2_e = r_e' Omega_e r_e with the file's information matrices, the inter-node edges as the robust set, pose 0
+// the anchor) from the final X, and one more line on stdout, in gnc:'s format with the two near_pi counts behind it
+//     ml gnc: <outcome> <levels> <steps> <factorisations> <num_robust> <num_zero> <num_between> <num_outliers>
+//             <mu_initial> <mu_final> <F_initial> <F_weighted_final> <F_surrogate_final> <near_pi> <near_pi_all>
+// --ml_gnc_report FILE: one header line
+//     # ml_gnc <outcome> barc2 <V> edges <m> robust <num_robust> zero <num_zero> outliers <num_outliers>
+// then per edge, in the graph's order,   i j in_R w chi2   (17 digits), chi2 at that point.  --ml_covariance and --ml_report
+// behind it act on the graph without the edges of weight 0 (dpgo_graph_filter_edges): the covariance of the inlier set.
+// (No filtered .g2o is written: the g2o writer does not export Omega.)
+static int step_ml_gnc(Run &r) {
+  const Args &a = r.a;
+  if (a.ml_gnc.empty()) return 0;
+  if (a.ml_gnc != "tls" && a.ml_gnc != "gm") {
+    fprintf(stderr, "--ml_gnc takes tls or gm.\n");
+    return -1;
+  }
+  if (r.refused("ml gnc")) return 0;
+  const int m = r.graph_edges, ld = r.ld;
+  std::vector<double> Xc, Z(r.point_size(), 0.0), w(m, 1.0);
+  dpgo_gnc_options_t go;
+  dpgo_gnc_options_default(&go);
+  go.kind = a.ml_gnc == "tls" ? DPGO_GNC_TLS : DPGO_GNC_GM;
+  go.barc2 = a.ml_gnc_barc2 > 0 ? a.ml_gnc_barc2 : (r.d == 2 ? 16.266 : 22.458);
+  dpgo_ml_gnc_result_t mr;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0) return -1;
+  if (dpgo_group_ml_gnc(grp, r.g, Xc.data(), ld, &go, nullptr, 0, Z.data(), ld, w.data(), nullptr, 0, &mr) != 0) return -1;
+  const dpgo_gnc_result_t &gr = mr.gnc;
+  printf("ml gnc: %s %d %d %d %d %d %d %d %.17g %.17g %.17g %.17g %.17g %lld %lld\n", gnc_name(gr.outcome), gr.levels, gr.steps,
+         gr.factorisations, gr.num_robust, gr.num_zero, gr.num_between, gr.num_outliers, gr.mu_initial, gr.mu_final, gr.F_initial,
+         gr.F_weighted_final, gr.F_surrogate_final, mr.near_pi, mr.near_pi_all);
+  if (gr.outcome == DPGO_GNC_SKIPPED) return 0;
+  if (!a.ml_gnc_report.empty()) {
+    std::vector<double> chi2(m), wb(m), sums(10);
+    if (r.load_edges() != 0 ||
+        dpgo_group_ml_gnc_eval(grp, r.g, Z.data(), ld, go.kind, gr.mu_final > 0 ? gr.mu_final : 1.0, go.barc2, nullptr, w.data(), 0,
+                               chi2.data(), wb.data(), sums.data(), nullptr, nullptr, nullptr, nullptr) != 0)
+      return -1;
+    FILE *f = open_report(a.ml_gnc_report.c_str());
+    if (!f) return -1;
+    fprintf(f, "# ml_gnc %s barc2 %.17g edges %d robust %d zero %d outliers %d\n", gnc_name(gr.outcome), go.barc2, m, gr.num_robust,
+            gr.num_zero, gr.num_outliers);
+    for (int e = 0; e < m; e++) fprintf(f, "%d %d %d %.17g %.17g\n", r.I[e], r.J[e], (int)r.inter[e], w[e], chi2[e]);
+    fclose(f);
+  }
+  std::vector<unsigned char> keep(m);
+  if (r.ml_kept) dpgo_graph_free(r.ml_kept);
+  r.ml_kept = nullptr;
+  r.ml_kept_edges.clear();
+  for (int e = 0; e < m; e++) {
+    keep[e] = w[e] > 0.0;
+    if (keep[e]) r.ml_kept_edges.push_back(e);
+  }
+  if ((int)r.ml_kept_edges.size() < m && dpgo_graph_filter_edges(r.g, keep.data(), &r.ml_kept) != 0) return -1;
+  r.Xnow.swap(Z);
+  return 0;
+}
+
 // --ml_covariance FILE (likewise; empty: off)  in --covariance's file format and with its line on stdout under the prefix
-// "ml covariance:", from dpgo_group_ml_covariance at the final X: the marginals of the Fisher information sum J' Omega J
+// "ml covariance:", from dpgo_group_ml_covariance at the final X: the marginals of the Fisher information sum J' Omega J (behind
+// --ml_gnc: over the edges of positive weight)
 static int step_ml_covariance(Run &r) {
   if (r.a.ml_covariance.empty() || r.refused("ml covariance")) return 0;
   const int dof = r.dof;
@@ -696,7 +767,7 @@ static int step_ml_covariance(Run &r) {
   dpgo_cov_result_t cv;
   dpgo_group_t *grp = ml_group(r);
   if (!grp || r.point(Xc) != 0) return -1;
-  if (dpgo_group_ml_covariance(grp, r.g, Xc.data(), r.ld, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0) return -1;
+  if (dpgo_group_ml_covariance(grp, r.ml_graph(), Xc.data(), r.ld, 0, 0, nullptr, 0, marg.data(), nullptr, &cv) != 0) return -1;
   printf("ml covariance: %s %d %d %d %d %lld %.16g %.16g\n", cov_name(cv.outcome), cv.unknowns, cv.fronts, cv.levels, cv.max_front,
          cv.device_bytes, cv.pivot_min, cv.stationarity);
   if (cv.outcome != DPGO_COV_OK) return 0;
@@ -713,19 +784,20 @@ static int step_ml_covariance(Run &r) {
 
 // --ml_report FILE (likewise; empty: off)  from dpgo_group_ml_eval at the final X: one header line
 //     # F_ml <F_ml> chi2_total <2 F_ml> edges <m> near_pi <count>
-// then per edge of the graph, in its order,   i j chi2     (17 digits)
+// then per edge of the graph, in its order,   i j chi2     (17 digits); behind --ml_gnc: of the graph without the edges of weight 0
 static int step_ml_report(Run &r) {
   if (r.a.ml_report.empty() || r.refused("ml report")) return 0;
-  std::vector<double> Xc, chi2(r.graph_edges, 0.0);
+  const int m = r.ml_edges();
+  std::vector<double> Xc, chi2(m, 0.0);
   double F = 0;
   long long near = 0;
   dpgo_group_t *grp = ml_group(r);
   if (!grp || r.point(Xc) != 0 || r.load_edges() != 0) return -1;
-  if (dpgo_group_ml_eval(grp, r.g, Xc.data(), r.ld, &F, &near, nullptr, chi2.data(), nullptr, nullptr, nullptr) != 0) return -1;
+  if (dpgo_group_ml_eval(grp, r.ml_graph(), Xc.data(), r.ld, &F, &near, nullptr, chi2.data(), nullptr, nullptr, nullptr) != 0) return -1;
   FILE *f = open_report(r.a.ml_report.c_str());
   if (!f) return -1;
-  fprintf(f, "# F_ml %.17g chi2_total %.17g edges %d near_pi %lld\n", F, 2 * F, r.graph_edges, near);
-  for (int e = 0; e < r.graph_edges; e++) fprintf(f, "%d %d %.17g\n", r.I[e], r.J[e], chi2[e]);
+  fprintf(f, "# F_ml %.17g chi2_total %.17g edges %d near_pi %lld\n", F, 2 * F, m, near);
+  for (int e = 0; e < m; e++) fprintf(f, "%d %d %.17g\n", r.I[r.ml_edge(e)], r.J[r.ml_edge(e)], chi2[e]);
   fclose(f);
   return 0;
 }
@@ -984,10 +1056,11 @@ int main(int argc, char **argv) {
   std::vector<double> X;
   std::vector<std::vector<double>> results;
   if (setup(r) != 0 || initialise(r, X) != 0 || solve(r, results) != 0) return -1;
-  for (int (*step)(Run &) : {step_gnc, step_polish, step_modes, step_staircase, step_robust_polish, step_ml_polish, step_certify,
-                             step_verify, step_edges, step_covariance, step_robust_covariance, step_ml_covariance, step_ml_report,
-                             step_gate, step_sensitivity, step_reliability, step_marginal, step_candidates})
+  for (int (*step)(Run &) : {step_gnc, step_polish, step_modes, step_staircase, step_robust_polish, step_ml_polish, step_ml_gnc,
+                             step_certify, step_verify, step_edges, step_covariance, step_robust_covariance, step_ml_covariance,
+                             step_ml_report, step_gate, step_sensitivity, step_reliability, step_marginal, step_candidates})
     if (step(r) != 0) return -1;
+  if (r.ml_kept) dpgo_graph_free(r.ml_kept);
   if (r.post) dpgo_group_free(r.post);
   if (a.save && save(r, X, results) != 0) return -1;
   if (r.comm) dpgo_comm_free(r.comm);

@@ -16,7 +16,7 @@
 
 namespace dpgo {
 
-static bool gnc_args_ok(int kind, double mu, double barc2, const char *who) {
+bool gnc_args_ok(int kind, double mu, double barc2, const char *who) {
   if (kind != GNC_TLS && kind != GNC_GM) {
     fprintf(stderr, "[dpgo_amd] ERROR: %s: kind %d is neither 0 (TLS) nor 1 (GM).\n", who, kind);
     return false;

@@ -92,6 +92,9 @@ void launch_gnc_edge(int d, hipStream_t st, int m, const double *rec, const doub
                      double *w, double *s_out, double *rows, double *partials, long long *counts, GncSummaryDev *sum, double *fslot,
                      int nslot);
 
+// Host: kind in {TLS, GM}, mu and barc2 finite and positive; otherwise false, with a line on stderr that names `who` (shared
+// with ml_gnc.cpp)
+bool gnc_args_ok(int kind, double mu, double barc2, const char *who);
 // Host, debug (no GPU): gnc_weight_rho (gnc_math.h) on n values of s
 int gnc_weight_host(int kind, double mu, double c2, const double *s, int n, double *w, double *rho);
 

@@ -36,6 +36,7 @@
 #include "ml.h"
 #include "pairs.h"
 #include "gnc.h"
+#include "ml_gnc.h"
 #include "modes.h"
 #include "polish.h"
 #include "rely.h"
@@ -239,6 +240,19 @@ class Group {
                          long long cap);
   int ml_eval(const Graph &g, const double *X, int ld, double *F, long long *near_pi, double *r, double *chi2, double *wr, double *grad,
               double *jw);
+  // ---- graduated non-convexity on the maximum-likelihood objective (ml_gnc.h, ml_gnc.cpp): GNC-TLS / GNC-GM on chi2_e =
+  // r_e' Omega_e r_e, one polish_loop per level on (F_w, g_w, H_w) with the weights of k_ml_gnc_edge.  The restrictions and the
+  // refusals of ml_polish and of gnc; barc2 is a threshold on chi2.  weights: num_edges; log: log_cap rows of GNC_LOG_COLS.
+  int ml_gnc(const Graph &g, const double *X, int ld, const GncOptions &o, const int *robust_set, long long max_bytes, double *Xout,
+             int ldout, double *weights, double *log, int log_cap, MlGncResult &out);
+  // debug: one FULL edge pass at X.  w_in null: WEIGH, the array starting as the caller's w; otherwise FIXED on w_in.  chi2, w:
+  // num_edges each (w: the array behind the pass); sums: the ML_GNC_SUMS of MlGncSummaryDev as doubles; full: also what else the
+  // pass left, as ml_eval hands it out (any of r, wr, grad, jw may be null)
+  int ml_gnc_eval(const Graph &g, const double *X, int ld, int kind, double mu, double barc2, const int *robust_set, const double *w_in,
+                  bool full, double *chi2, double *w, double *sums, double *r, double *wr, double *grad, double *jw);
+  // debug: g_w and the anchored H_w of the weights w_in (FIXED) as ml_hessian hands out g and H
+  int ml_gnc_hessian(const Graph &g, const double *X, int ld, int anchor, const int *robust_set, const double *w_in, int *ptr, int *col,
+                     double *val, long long cap, long long *nnz, double *grad);
   // ---- graduated non-convexity (gnc.h, gnc.cpp): outlier rejection on the robust objective's plan, one polish_loop per level
   // with the weights of k_gnc_edge.  The restrictions of the robust objective; robust_set (optional, one int per edge): the
   // edges the loss may touch, instead of the inter rule.  Xout: the point (written unless SKIPPED), weights: num_edges, log
@@ -791,6 +805,12 @@ class Group {
   void ml_edge_pass(const double *Xdev, bool full, int fslot);   // fslot >= 0: F into that slot of the certificate's partial sums
   void ml_point(int arow, double *g, int slot_g2, int fslot);     // the full edge pass at CertState's X and the gather into g
   void ml_hessian_launch(int arow);
+  // ml_gnc.cpp: the buffers of the weighted edge pass; the robust set of a call, uploaded (returns |R|); the pass at a record
+  // array of the group (full: the per-edge arrays and summary [0], else summary [1]; fslot as ml_edge_pass); a summary read back
+  void ml_gnc_alloc();
+  int ml_gnc_set(const int *robust_set, std::vector<int> &in_R);
+  void ml_gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool full, int fslot);
+  void ml_gnc_summary(MlGncSummaryDev &sd, bool full);
   MargCache *marg_ = nullptr;   // the dense factors of joint_marginal, one per order (marg.cpp), allocated by the first call
   void marg_release();
   // the batches of a column plan behind a factorisation: Sigma_KK of the kept poses into g1 / g2 (device), d_prow <- their records

@@ -13,21 +13,9 @@
 #include "edge_math.h"
 #include "group.h"
 #include "ml_math.h"
+#include "ml_state.h"
 
 namespace dpgo {
-
-struct Group::MlState {
-  RobustPlan plan;             // the records and the lists (robust.h)
-  std::vector<double> omega;   // m x dof^2: the graph's, or Omega_iso
-  bool on_device = false;
-  long long bytes = 0;         // what ml_alloc allocates for the plan
-  DevBuf<double> rec, om, r, wr, chi2, ge, jw, partials, sum, grad;
-  DevBuf<int64_t> counts;
-  DevBuf<int> inc_ptr, inc, blk_ptr, blk;
-  // two summaries: [0] of the last full edge pass (a point), [1] of the last trial pass, which must not overwrite it
-  MlSummaryDev *sum_dev(bool full = true) const { return reinterpret_cast<MlSummaryDev *>(sum.p) + (full ? 0 : 1); }
-  MlEdgeOut out() const { return {r.p, wr.p, chi2.p, ge.p, jw.p}; }
-};
 
 void Group::ml_release() {
   delete ml_;

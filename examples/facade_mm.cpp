@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -24,6 +24,10 @@
 // as the robust set) on a second, trivial-loss group of the same graph, one line per edge and one per row of the new point:
 //   gnc: w <edge> <weight, 17 digits>        gnc: x <row> <the d entries, 17 digits>       then
 //   gnc: <CONVERGED|ALL_INLIERS|MAX_LEVELS|INNER_FAILED|SKIPPED|FAILED> <levels> <steps> <factorisations> <num_zero> <num_outliers> <F_initial> <F_weighted_final> <F_surrogate_final>
+// and with `ml_gnc <tls|gm> <barc2>` (any loss of the run) through DPGOHashGroup::ml_graduated_non_convexity -- the same levels on
+// chi2_e = r_e' Omega_e r_e with the file's information matrices, barc2 a chi2 quantile -- on a second, trivial-loss group:
+//   ml gnc: w <edge> <weight, 17 digits>        ml gnc: x <row> <the d entries, 17 digits>       then
+//   ml gnc: <outcome as gnc> <levels> <steps> <factorisations> <num_zero> <num_outliers> <F_initial> <F_weighted_final> <F_surrogate_final> <near_pi> <near_pi_all>
 // and with `staircase` through DPGOHashGroup::riemannian_staircase (trivial loss), one line per row of the result:
 //   staircase: x <row> <the d entries, 17 digits>       then
 //   staircase: <SOLVED|MAX_RANK|SADDLE|SKIPPED|FAILED> <final_rank> <F_initial> <F_sdp> <F_final> <gap>
@@ -68,6 +72,7 @@
 // last call with an edge index outside the graph must fail:   reliability: bad edge <status>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -85,7 +90,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -269,6 +274,34 @@ int main(int argc, char **argv) {
             : status == DPGO_GNC_MAX_LEVELS ? "MAX_LEVELS" : status == DPGO_GNC_INNER_FAILED ? "INNER_FAILED"
             : status == DPGO_GNC_SKIPPED ? "SKIPPED" : "FAILED",
             r.levels, r.steps, r.factorisations, r.num_zero, r.num_outliers, r.F_initial, r.F_weighted_final, r.F_surrogate_final);
+    if (status < 0) return 1;
+  }
+  if (argc > 8 && !strcmp(argv[6], "ml_gnc")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Z;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    DPGO::Options trivial = DPGO::Options::driver(DPGO::Loss::None, acc);
+    trivial.max_iterations = 0;
+    DPGO::DPGOHashGroup post(graph, all, trivial, 0);
+    int status = -1;
+    dpgo_ml_gnc_result_t r = {};
+    dpgo_gnc_options_t o;
+    dpgo_gnc_options_default(&o);
+    o.kind = !strcmp(argv[7], "gm") ? DPGO_GNC_GM : DPGO_GNC_TLS;
+    o.barc2 = atof(argv[8]);
+    std::vector<double> w;
+    post.ml_graduated_non_convexity(X, Z, w, &r, &status, &o);
+    for (size_t e = 0; status >= 0 && status != DPGO_GNC_SKIPPED && e < w.size(); e++) fprintf(stderr, "ml gnc: w %zu %.17g\n", e, w[e]);
+    for (int i = 0; status >= 0 && status != DPGO_GNC_SKIPPED && i < Z.rows(); i++) {
+      fprintf(stderr, "ml gnc: x %d", i);
+      for (int c = 0; c < Z.cols(); c++) fprintf(stderr, " %.17g", Z.data()[(size_t)c * Z.rows() + i]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "ml gnc: %s %d %d %d %d %d %.17g %.17g %.17g %lld %lld\n",
+            status == DPGO_GNC_CONVERGED ? "CONVERGED" : status == DPGO_GNC_ALL_INLIERS ? "ALL_INLIERS"
+            : status == DPGO_GNC_MAX_LEVELS ? "MAX_LEVELS" : status == DPGO_GNC_INNER_FAILED ? "INNER_FAILED"
+            : status == DPGO_GNC_SKIPPED ? "SKIPPED" : "FAILED",
+            r.gnc.levels, r.gnc.steps, r.gnc.factorisations, r.gnc.num_zero, r.gnc.num_outliers, r.gnc.F_initial, r.gnc.F_weighted_final,
+            r.gnc.F_surrogate_final, r.near_pi, r.near_pi_all);
     if (status < 0) return 1;
   }
   if (argc > 6 && !strcmp(argv[6], "staircase")) {

@@ -1097,6 +1097,51 @@ int dpgo_group_gnc_eval(dpgo_group_t *grp, const dpgo_graph_t *graph, const doub
                         const int *robust_set, const double *w_in, double *s_rot, double *s_trans, double *w, double *sums);
 int dpgo_debug_gnc_weight_host(int kind, double mu, double barc2, const double *s, int n, double *w, double *rho);
 
+/* ---- graduated non-convexity on the full information matrices: outlier rejection on chi2 ---- */
+/* dpgo_group_gnc thresholds the isotropic s_e and ignores Omega_e.  Here GNC-TLS and GNC-GM run on the maximum-likelihood
+ * objective of dpgo_group_ml_polish, with r_e, Omega_e, the unknowns, the anchor and near_pi as defined there:
+ *     s_e := chi2_e = r_e' Omega_e r_e,   barc2 > 0 the caller's threshold on chi2_e -- a chi2_dof quantile, dof = 3 (d = 2) or
+ *     6 (d = 3): 16.266 / 22.458 at 0.999.  (The library has no quantile function.)
+ *     F_w(X) = 1/2 sum_e w_e chi2_e,   F_mu(X) = 1/2 sum_{not R} chi2_e + 1/2 sum_R rho_mu(chi2_e)
+ *     g_w = sum_e w_e J_e' Omega_e r_e,   H_w = sum_e w_e J_e' Omega_e J_e   (Gauss-Newton)
+ * The robust set R, the weight and rho_mu, the levels, mu's schedule, the outcomes, the options, the log's ten columns and the
+ * timers are dpgo_group_gnc's, with chi2 for s; within a level F_mu never increases.  inner is the loop of dpgo_group_ml_polish
+ * on (F_w, g_w, H_w) with fixed weights.  Two differences:
+ *   1. An inner MAX_STEPS is normal and NOT a failure: H_w is Gauss-Newton, and at the early levels, where the weighted
+ *      residuals at the minimum are large, the inner loop converges linearly.  Only an inner STALLED is INNER_FAILED.
+ *   2. An edge whose weight is exactly 0 contributes exact zeros to g_w, H_w and F_w by selection, not by multiplication: an
+ *      outlier's rotation residual may sit within 1e-3 of pi, where the edge's values are not specified further.  near_pi
+ *      counts the edges with w_e > 0 at the final point, near_pi_all every edge.
+ * The restrictions of dpgo_group_ml_polish and the argument checks of dpgo_group_gnc: -1 otherwise.  SKIPPED by
+ * dpgo_group_ml_polish's rule with the weights, the robust set and the partial sums counted in; decided before anything is
+ * allocated.  The optimiser's state is not touched.
+ *   result->gnc   as dpgo_group_gnc fills it: s_max_initial = max_R chi2 at X0, num_outliers = e in R with chi2_e > barc2 at the
+ *                 final point, the F fields on chi2
+ * dpgo_group_ml_gnc_eval (debug): one edge pass at X.  w_in NULL: WEIGH -- the array starts as the caller's w, weight_mu(chi2_e)
+ *   is written on R; otherwise FIXED: the array is w_in, read on R.  chi2 (unweighted), w (the array behind the pass):
+ *   num_edges each; sums (10): sum_{not R} chi2, sum_R w chi2, sum_R rho_mu(chi2), max_R chi2 (0 over an empty R), min_R w
+ *   (+inf likewise), the counts of w == 0, w == 1, 0 < w < 1 over R, near_pi over w > 0, near_pi over every edge.  full != 0:
+ *   also r (dof), wr = w Omega r (dof), grad (2 dof: the edge's weighted gradient terms of i, of j) and jw (4 dof^2: J_i, J_j,
+ *   w Omega J_i, w Omega J_j; all zeros where w == 0), each optional.
+ * dpgo_group_debug_ml_gnc_hessian (debug): g_w and the anchored H_w of the weights w_in as dpgo_group_ml_hessian hands out its own.
+ * dpgo_debug_ml_gnc_edge_host (no GPU): the kernel's arithmetic per edge in graph order given w (num_edges, each in [0, 1]):
+ *   r, wr, chi2, grad, jw as above, near_pi over w > 0 and near_pi_all; any output may be NULL. */
+typedef struct dpgo_ml_gnc_result {
+  dpgo_gnc_result_t gnc;
+  long long near_pi, near_pi_all;
+} dpgo_ml_gnc_result_t;
+int dpgo_group_ml_gnc(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, const dpgo_gnc_options_t *opt,
+                      const int *robust_set, long long max_bytes, double *Xout, int ldout, double *weights, double *log, int log_cap,
+                      dpgo_ml_gnc_result_t *result);
+int dpgo_group_ml_gnc_eval(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int kind, double mu, double barc2,
+                           const int *robust_set, const double *w_in, int full, double *chi2, double *w, double *sums, double *r,
+                           double *wr, double *grad, double *jw);
+int dpgo_group_debug_ml_gnc_hessian(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor,
+                                    const int *robust_set, const double *w_in, int *ptr, int *col, double *val, long long cap,
+                                    long long *nnz, double *grad);
+int dpgo_debug_ml_gnc_edge_host(const dpgo_graph_t *graph, const double *X, int ld, const double *w, double *r, double *wr,
+                                double *chi2, double *grad, double *jw, long long *near_pi, long long *near_pi_all);
+
 /* ---- the Riemannian staircase: escape a NEGATIVE certificate -------------------------------- */
 /* When dpgo_group_verify says NEGATIVE the point is a saddle or a local minimum of the rank-d problem, and the unit vector x it
  * returns is a direction of descent one rank up.  dpgo_group_staircase is the loop of SE-Sync (C++/SESync/src/SESync.cpp:280-440,

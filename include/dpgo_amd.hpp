@@ -522,6 +522,34 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && (r.outcome == DPGO_GNC_CONVERGED || r.outcome == DPGO_GNC_ALL_INLIERS);
   }
+  // Graduated non-convexity on the measurements' full information matrices (dpgo_group_ml_gnc): graduated_non_convexity's
+  // levels on chi2_e = r_e' Omega_e r_e of ml_polish's objective, so that opt->barc2 is a chi2_dof quantile (dof 3 for d = 2, 6
+  // for d = 3: 16.266 / 22.458 at 0.999).  An inner MAX_STEPS is normal; an edge of weight exactly 0 contributes exact zeros.
+  // Arguments, returns and status as graduated_non_convexity; result->gnc carries its fields, result->near_pi the edges with
+  // w > 0 within 1e-3 of pi at the final point.
+  bool ml_graduated_non_convexity(const Matrix &X, Matrix &Xout, std::vector<Scalar> &weights, dpgo_ml_gnc_result_t *result = nullptr,
+                                  int *status = nullptr, const dpgo_gnc_options_t *opt = nullptr,
+                                  const std::vector<int> *robust_set = nullptr, long long max_bytes = 0,
+                                  std::vector<Scalar> *log = nullptr) const {
+    dpgo_gnc_options_t o;
+    dpgo_gnc_options_default(&o);
+    if (opt) o = *opt;
+    Xout = X;
+    weights.assign((size_t)graph_->num_edges(), 1.0);
+    if (robust_set && (int)robust_set->size() != graph_->num_edges()) {
+      if (status) *status = -1;
+      return false;
+    }
+    const int cap = o.max_levels > 0 ? o.max_levels : 0;
+    if (log) log->assign((size_t)cap * 10, 0.0);
+    dpgo_ml_gnc_result_t r = {};
+    const int rc = dpgo_group_ml_gnc(h_, graph_->handle(), X.data(), X.rows(), &o, robust_set ? robust_set->data() : nullptr, max_bytes,
+                                     Xout.data(), Xout.rows(), weights.data(), log && cap ? log->data() : nullptr, log ? cap : 0, &r);
+    if (log) log->resize(rc == 0 ? (size_t)std::min(cap, r.gnc.levels) * 10 : 0);
+    if (status) *status = rc == 0 ? r.gnc.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && (r.gnc.outcome == DPGO_GNC_CONVERGED || r.gnc.outcome == DPGO_GNC_ALL_INLIERS);
+  }
   // Marginal covariances of the robust objective at X (dpgo_group_robust_covariance): marginal_covariances on the true Hessian
   // (curvature 1) or the re-weighted one (0).  DPGO_COV_NOT_PD is a legitimate answer where the negative curvature of the loss
   // wins.  Arguments, returns and status as marginal_covariances.
