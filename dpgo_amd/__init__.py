@@ -1516,18 +1516,22 @@ class NodeGroup:
         point (X itself for GNC_SKIPPED), one weight per edge, the result struct, and one row per level k >= 1 of (mu,
         F_mu(X_{k-1}), F_w(X_{k-1}), F_w(X_k), F_mu(X_k), inner steps, inner outcome, the counts of w == 0, w == 1 and
         0 < w < 1 over the robust set)."""
+        return self._gnc_call("gnc", GncResult(), graph, X, opt, robust_set, max_bytes, "a bad kind, barc2, mu_step, max_levels or anchor")
+
+    def _gnc_call(self, name, r, graph, X, opt, robust_set, max_bytes, bad):
+        # what `gnc` and `ml_gnc` share: the outputs, the robust set's check, the call and its error (bad: what it may refuse)
         X, ld = _fcol(X)
         o = GncOptions() if opt is None else opt
         Xout, w = np.array(X, order="F"), np.ones(graph.num_edges)
         log = np.zeros((max(int(o.max_levels), 0), 10))
         rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
         if rs is not None and rs.shape != (graph.num_edges,):
-            raise ValueError("gnc: robust_set must have one entry per edge")
-        r = GncResult()
-        if lib().dpgo_group_gnc(self._h, graph._h, _dp(X), ld, C.byref(o), None if rs is None else _ip(rs), int(max_bytes), _dp(Xout),
-                                Xout.shape[0], _dp(w), _dp(log) if len(log) else None, len(log), C.byref(r)) != 0:
-            raise RuntimeError("dpgo_group_gnc failed (a robust-loss group, a group that does not host every node, a graph that is "
-                               "not the group's, a bad kind, barc2, mu_step, max_levels or anchor, or bad sizes or options)")
+            raise ValueError("%s: robust_set must have one entry per edge" % name)
+        fn = getattr(lib(), "dpgo_group_" + name)
+        if fn(self._h, graph._h, _dp(X), ld, C.byref(o), None if rs is None else _ip(rs), int(max_bytes), _dp(Xout), Xout.shape[0],
+              _dp(w), _dp(log) if len(log) else None, len(log), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_%s failed (a robust-loss group, a group that does not host every node, a graph that is "
+                               "not the group's, %s, or bad sizes or options)" % (name, bad))
         return Xout, w, r, log[:r.levels].copy()
 
     def gnc_eval(self, graph, X, kind, mu, barc2, robust_set=None, w_in=None, w_start=None):
@@ -1535,19 +1539,25 @@ class NodeGroup:
         starts as w_start (default: ones) and weight_mu(s_e) is written on the robust set; otherwise FIXED on w_in.  Returns
         (s_rot, s_trans, w, sums): w the array behind the pass; sums = (sum_{not R} s, sum_R w s, sum_R rho_mu(s), max_R s,
         min_R w, the counts of w == 0, w == 1, 0 < w < 1 over R)."""
+        m = graph.num_edges
+        head, w = self._gnc_eval_args("gnc_eval", graph, X, kind, mu, barc2, robust_set, w_in, w_start)
+        sr, st, sums = np.zeros(m), np.zeros(m), np.zeros(8)
+        if lib().dpgo_group_gnc_eval(*head, _dp(sr), _dp(st), _dp(w), _dp(sums)) != 0:
+            raise RuntimeError("dpgo_group_gnc_eval failed (a robust-loss group, a group that does not host every node, a graph that "
+                               "is not the group's, a bad kind, mu or barc2, or bad sizes)")
+        return sr, st, w, sums
+
+    def _gnc_eval_args(self, name, graph, X, kind, mu, barc2, robust_set, w_in, w_start):
+        # what `gnc_eval` and `ml_gnc_eval` share: the call's arguments up to and including w_in, and the weight array behind the
+        # pass (a pointer of ndarray.ctypes.data_as holds a reference to its array, so the copies made here outlive the call)
         X, ld = _fcol(X)
         m = graph.num_edges
         rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
         wi = None if w_in is None else np.ascontiguousarray(w_in, np.float64)
         w = np.ones(m) if w_start is None else np.array(w_start, np.float64)
         if any(a is not None and a.shape != (m,) for a in (rs, wi, w)):
-            raise ValueError("gnc_eval: robust_set, w_in and w_start must have one entry per edge")
-        sr, st, sums = np.zeros(m), np.zeros(m), np.zeros(8)
-        if lib().dpgo_group_gnc_eval(self._h, graph._h, _dp(X), ld, int(kind), float(mu), float(barc2), None if rs is None else _ip(rs),
-                                     _dpn(wi), _dp(sr), _dp(st), _dp(w), _dp(sums)) != 0:
-            raise RuntimeError("dpgo_group_gnc_eval failed (a robust-loss group, a group that does not host every node, a graph that "
-                               "is not the group's, a bad kind, mu or barc2, or bad sizes)")
-        return sr, st, w, sums
+            raise ValueError("%s: robust_set, w_in and w_start must have one entry per edge" % name)
+        return (self._h, graph._h, _dp(X), ld, int(kind), float(mu), float(barc2), None if rs is None else _ip(rs), _dpn(wi)), w
 
     def robust_covariance(self, X, loss, loss_reg=0.25, curvature=1, anchor=0, pairs=None, max_bytes=0, graph=None):
         """Marginal pose covariances of the ROBUST objective at X (dpgo_group_robust_covariance): `covariance` on the true
@@ -1684,20 +1694,9 @@ class NodeGroup:
         call's level.  An edge of weight exactly 0 contributes exact zeros by selection.  opt: GncOptions (None: the
         defaults).  Returns (Xout, weights, MlGncResult, log) as `gnc` does, F and s on chi2; result.near_pi counts the
         edges with w > 0 whose rotation residual is within 1e-3 of pi at the final point, near_pi_all every such edge."""
-        X, ld = _fcol(X)
-        o = GncOptions() if opt is None else opt
-        Xout, w = np.array(X, order="F"), np.ones(graph.num_edges)
-        log = np.zeros((max(int(o.max_levels), 0), 10))
-        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
-        if rs is not None and rs.shape != (graph.num_edges,):
-            raise ValueError("ml_gnc: robust_set must have one entry per edge")
-        r = MlGncResult()
-        if lib().dpgo_group_ml_gnc(self._h, graph._h, _dp(X), ld, C.byref(o), None if rs is None else _ip(rs), int(max_bytes),
-                                   _dp(Xout), Xout.shape[0], _dp(w), _dp(log) if len(log) else None, len(log), C.byref(r)) != 0:
-            raise RuntimeError("dpgo_group_ml_gnc failed (a robust-loss group, a group that does not host every node, a graph that "
-                               "is not the group's, an information matrix that is not symmetric positive definite, a bad kind, "
-                               "barc2, mu_step, max_levels or anchor, or bad sizes or options)")
-        return Xout, w, r, log[:r.levels].copy()
+        return self._gnc_call("ml_gnc", MlGncResult(), graph, X, opt, robust_set, max_bytes,
+                              "an information matrix that is not symmetric positive definite, a bad kind, barc2, mu_step, "
+                              "max_levels or anchor")
 
     def ml_gnc_eval(self, graph, X, kind, mu, barc2, robust_set=None, w_in=None, w_start=None, full=False):
         """Debug: one edge pass of `ml_gnc` at X (dpgo_group_ml_gnc_eval).  w_in None: WEIGH -- the weight array starts as
@@ -1706,19 +1705,12 @@ class NodeGroup:
         max_R chi2, min_R w, the counts of w == 0, w == 1, 0 < w < 1 over R, near_pi over w > 0, near_pi over every edge).
         full=True: a fourth item, the dict of what else the pass left on the device -- r, wr = w Omega r (m, dof), grad (m, 2,
         dof), Ji, Jj, Wi, Wj (m, dof, dof; W = w Omega J; all four zero where w == 0)."""
-        X, ld = _fcol(X)
         m, dof = graph.num_edges, _dof(self.d)
-        rs = None if robust_set is None else np.ascontiguousarray(robust_set, np.int32)
-        wi = None if w_in is None else np.ascontiguousarray(w_in, np.float64)
-        w = np.ones(m) if w_start is None else np.array(w_start, np.float64)
-        if any(a is not None and a.shape != (m,) for a in (rs, wi, w)):
-            raise ValueError("ml_gnc_eval: robust_set, w_in and w_start must have one entry per edge")
+        head, w = self._gnc_eval_args("ml_gnc_eval", graph, X, kind, mu, barc2, robust_set, w_in, w_start)
         chi2, sums = np.zeros(m), np.zeros(10)
         r, wr, grad, jw = np.zeros((m, dof)), np.zeros((m, dof)), np.zeros((m, 2, dof)), np.zeros((m, 4, dof, dof))
         more = (_dp(r), _dp(wr), _dp(grad), _dp(jw)) if full else (None,) * 4
-        if lib().dpgo_group_ml_gnc_eval(self._h, graph._h, _dp(X), ld, int(kind), float(mu), float(barc2),
-                                        None if rs is None else _ip(rs), _dpn(wi), int(bool(full)), _dp(chi2), _dp(w), _dp(sums),
-                                        *more) != 0:
+        if lib().dpgo_group_ml_gnc_eval(*head, int(bool(full)), _dp(chi2), _dp(w), _dp(sums), *more) != 0:
             raise RuntimeError("dpgo_group_ml_gnc_eval failed (a robust-loss group, a group that does not host every node, a graph "
                                "that is not the group's, an information matrix that is not symmetric positive definite, a bad "
                                "kind, mu or barc2, or bad sizes)")

@@ -8,6 +8,8 @@
 
 #include <cstdio>
 
+#include "wave_reduce.h"
+
 namespace dpgo {
 namespace {
 
@@ -30,12 +32,6 @@ __device__ __forceinline__ void store_rec(double *p, const double (&r)[N]) {
   for (int k = 0; k < N / 2; k++) q[k] = make_double2(r[2 * k], r[2 * k + 1]);
 }
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return ((m.p ? (m.v & *m.p) : m.v) >> node) & 1ull; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // Sums of N = 3 * 2^k values per lane over the 64 lanes of a wave with N + O(1) shuffles instead of 6 N: while the count
 // is even, the lanes of a pair (l, l ^ OFF) split it -- the lower lane keeps the first half of the sums, the upper lane

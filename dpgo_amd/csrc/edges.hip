@@ -12,26 +12,11 @@
 
 #include "edge_math.h"
 #include "edges.h"
+#include "wave_reduce.h"
 
 namespace dpgo {
 
 namespace {
-
-__device__ __forceinline__ double edge_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double edge_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ long long edge_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 template <int D>
 __global__ __launch_bounds__(EDGE_BLOCK) void k_edge_eval(int m, const double2 *__restrict__ rec,
@@ -75,9 +60,9 @@ __global__ __launch_bounds__(EDGE_BLOCK) void k_edge_eval(int m, const double2 *
     down = w < 1.0;
   }
   const long long n_inter = __popcll(__ballot(is_inter)), n_down = __popcll(__ballot(down));
-  f_intra = edge_wave_sum(f_intra);
-  f_inter = edge_wave_sum(f_inter);
-  wmin = edge_wave_min(wmin);
+  f_intra = wave_sum(f_intra);
+  f_inter = wave_sum(f_inter);
+  wmin = wave_min(wmin);
   if (threadIdx.x == 0) {
     const size_t nb = gridDim.x, bk = blockIdx.x;
     partials[bk] = f_intra;
@@ -101,11 +86,11 @@ __global__ __launch_bounds__(64) void k_edge_final(int nb, const double *__restr
     ni += counts[k];
     nd += counts[(size_t)nb + k];
   }
-  fi = edge_wave_sum(fi);
-  fe = edge_wave_sum(fe);
-  wmin = edge_wave_min(wmin);
-  ni = edge_wave_sum(ni);
-  nd = edge_wave_sum(nd);
+  fi = wave_sum(fi);
+  fe = wave_sum(fe);
+  wmin = wave_min(wmin);
+  ni = wave_sum(ni);
+  nd = wave_sum(nd);
   if (lane == 0) {
     sum->F_intra = 0.5 * fi;
     sum->F_inter = 0.5 * fe;

@@ -39,17 +39,28 @@
 // Connectivity.  A level whose zero weights disconnect the graph makes H singular.  The Levenberg-Marquardt shift then
 // either copes or stalls; a stall is INNER_FAILED, an outcome, not an error.
 //
-// Two kernels (gnc.hip), fp64, fixed-order sums, no atomics: the same bits run to run.
+// The outer loop is stated once, for this objective and for the maximum-likelihood one (ml_gnc.h): Group::gnc_loop (gnc.cpp)
+// owns the option check, level 0, the ALL_INLIERS test, the mu schedule, the levels with their log rows, the failure return
+// and the read-out into a GncResult.  What an objective is to it is a GncObjective (group.h), a plain struct the caller
+// fills: the edge pass, its summary read back, what forms the gradient behind the point pass, the Hessian launch, the device
+// weight array, the host mask of R, the download of the per-edge s, and two named differences of behaviour.
+//
+// Two kernels (gnc.hip), fp64, fixed-order sums (wave_reduce.h), no atomics: the same bits run to run.
 //   k_gnc_edge   one lane per edge in graph order, EDGE_BLOCK per workgroup, records and poses read as 16-byte units as in
 //                k_robust_edge: s_rot, s_trans through edge_lane<D> under loss 0; WEIGH: w = weight_mu(s) written for e in R
 //                (the array is not touched elsewhere); FIXED: w read from the array for e in R; 1 outside R in both; behind a
-//                flag the rows (M_e X)_i, (M_e X)_j through robust_rows<D>.  Per workgroup, by wave shuffle, one partial each:
-//                sum_{not R} s, sum_R w s, sum_R rho_mu(s), max_R s, min_R w, and the counts of w == 0, w == 1, 0 < w < 1 over R.
-//   k_gnc_final  one wave over the partials in strided order (as k_robust_final): the summary, and optionally F_w into a slot
-//                of the certificate's partial sums, where polish_loop's reduction looks (fslot / nslot as launch_robust_edge).
+//                flag the rows (M_e X)_i, (M_e X)_j through robust_rows<D>.  Per workgroup, by wave shuffle, one partial each
+//                (gnc_partials.h, shared with k_ml_gnc_edge): sum_{not R} s, sum_R w s, sum_R rho_mu(s), max_R s, min_R w, and
+//                the counts of w == 0, w == 1, 0 < w < 1 over R.
+//   k_gnc_final<NC>  one wave over the partials in strided order (as k_robust_final) and over NC counts per workgroup: the
+//                summary, and optionally F_w into a slot of the certificate's partial sums, where polish_loop's reduction looks
+//                (fslot / nslot as launch_robust_edge).  NC = 3 here; 5 behind k_ml_gnc_edge, the two near-pi counts after the
+//                three (launch_gnc_final serves both).
 // R-membership of an edge is the inter word of the plan's own copy of its record (robust_begin's robust_set overwrites it).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 #include "edges.h"
 #include "polish.h"
@@ -83,7 +94,21 @@ struct GncSummaryDev {
   double sum_out, sum_ws, sum_rho, s_max, w_min;
   long long num_zero, num_one, num_between;
 };
-constexpr int GNC_PARTIAL_SLOTS = 5, GNC_COUNT_SLOTS = 3;   // per workgroup, in the order of the struct
+static_assert(sizeof(GncSummaryDev) == 64, "five sums, three counts");
+// per workgroup, in the order of the struct; the maximum-likelihood pass has two more counts (ml_gnc.h: MlGncSummaryDev)
+constexpr int GNC_PARTIAL_SLOTS = 5, GNC_COUNT_SLOTS = 3, ML_GNC_COUNT_SLOTS = GNC_COUNT_SLOTS + 2;
+// the bytes of a pass's reduction: the partials and ncounts counts of nb workgroups, and nsum summaries
+constexpr long long gnc_reduce_bytes(int nb, int ncounts, int nsum) {
+  return 8ll * (GNC_PARTIAL_SLOTS + ncounts) * nb + (long long)nsum * ((long long)sizeof(GncSummaryDev) + 8ll * (ncounts - GNC_COUNT_SLOTS));
+}
+
+// A summary on the host, of either objective: what gnc_loop works on.  The near-pi counts stay zero for this objective.
+struct GncSummary {
+  GncSummaryDev sums = {};
+  long long near_pi = 0, near_pi_all = 0;
+};
+constexpr int GNC_SUMS = 8, ML_GNC_SUMS = 10;   // a summary as doubles, in the order of the struct (gnc_eval; ml_gnc_eval)
+void gnc_summary_doubles(const GncSummary &q, int n, double *sums);   // its first n fields
 
 // device (gnc.hip); enqueued on st.  s_out: 2 arrays of m doubles (s_rot, s_trans); w: m doubles (weigh: written on R, read
 // nowhere; else read on R); rows (null: not computed): as launch_robust_edge; partials: 5 nb doubles, counts: 3 nb;
@@ -91,10 +116,17 @@ constexpr int GNC_PARTIAL_SLOTS = 5, GNC_COUNT_SLOTS = 3;   // per workgroup, in
 void launch_gnc_edge(int d, hipStream_t st, int m, const double *rec, const double *X, int kind, double mu, double c2, bool weigh,
                      double *w, double *s_out, double *rows, double *partials, long long *counts, GncSummaryDev *sum, double *fslot,
                      int nslot);
+// the final wave alone, behind an edge kernel that left 5 nb partials and ncounts nb counts (3, or 5: then sum is the head of an
+// MlGncSummaryDev, whose two counts follow it); launch_gnc_edge and launch_ml_gnc_edge end with it
+void launch_gnc_final(hipStream_t st, int nb, int ncounts, const double *partials, const long long *counts, GncSummaryDev *sum,
+                      double *fslot, int nslot);
 
 // Host: kind in {TLS, GM}, mu and barc2 finite and positive; otherwise false, with a line on stderr that names `who` (shared
 // with ml_gnc.cpp)
 bool gnc_args_ok(int kind, double mu, double barc2, const char *who);
+// Host: in_R <- per edge of the m records rec (edges.h) whether it is in R: robust_set[e] != 0, or the record's inter word when
+// robust_set is null.  Returns |R|.
+int gnc_robust_mask(int d, int m, const double *rec, const int *robust_set, std::vector<int> &in_R);
 // Host, debug (no GPU): gnc_weight_rho (gnc_math.h) on n values of s
 int gnc_weight_host(int kind, double mu, double c2, const double *s, int n, double *w, double *rho);
 

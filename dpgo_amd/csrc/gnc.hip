@@ -1,36 +1,17 @@
 // The kernels of graduated non-convexity for gfx950 (gnc.h): the edge pass with weights from the surrogate or from an array,
 // and its final wave.  fp64 throughout, no fast-math; every sum runs in a fixed order (the lanes of a wave by shuffle, the
-// workgroups' partials strided in one final wave): the same bits run to run, no atomics, no LDS, no inline assembly.
+// workgroups' partials strided in one final wave; wave_reduce.h): the same bits run to run, no atomics, no LDS, no inline
+// assembly.
 #include "gnc.h"
 
 #include <cmath>
 
 #include "gnc_math.h"
+#include "gnc_partials.h"
 #include "robust_math.h"
 
 namespace dpgo {
 namespace {
-
-__device__ __forceinline__ double gnc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double gnc_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double gnc_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ long long gnc_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 template <int D>
 __global__ __launch_bounds__(EDGE_BLOCK) void k_gnc_edge(int m, const double2 *__restrict__ rec, const double2 *__restrict__ poses,
@@ -96,48 +77,33 @@ __global__ __launch_bounds__(EDGE_BLOCK) void k_gnc_edge(int m, const double2 *_
       f_out = s;
     }
   }
-  const long long n_zero = __popcll(__ballot(zero)), n_one = __popcll(__ballot(one)), n_between = __popcll(__ballot(between));
-  f_out = gnc_wave_sum(f_out);
-  f_ws = gnc_wave_sum(f_ws);
-  f_rho = gnc_wave_sum(f_rho);
-  smax = gnc_wave_max(smax);
-  wmin = gnc_wave_min(wmin);
-  if (threadIdx.x == 0) {
-    const size_t nb = gridDim.x, bk = blockIdx.x;
-    partials[bk] = f_out;
-    partials[nb + bk] = f_ws;
-    partials[2 * nb + bk] = f_rho;
-    partials[3 * nb + bk] = smax;
-    partials[4 * nb + bk] = wmin;
-    counts[bk] = n_zero;
-    counts[nb + bk] = n_one;
-    counts[2 * nb + bk] = n_between;
-  }
+  gnc_store_partials(f_out, f_ws, f_rho, smax, wmin, partials, counts, zero, one, between);
 }
 
+// NC counts per workgroup; the NC - 3 past num_between follow the struct (MlGncSummaryDev and its static_asserts, ml_gnc.h)
+template <int NC>
 __global__ __launch_bounds__(64) void k_gnc_final(int nb, const double *__restrict__ partials, const long long *__restrict__ counts,
                                                   GncSummaryDev *__restrict__ sum, double *__restrict__ fslot, int nslot) {
+  static_assert(NC >= GNC_COUNT_SLOTS, "the three counts of GncSummaryDev come first");
   const int lane = threadIdx.x;
   double fo = 0, fw = 0, fr = 0, smax = 0, wmin = INFINITY;
-  long long nz = 0, no = 0, nbt = 0;
+  long long n[NC] = {};
   for (int k = lane; k < nb; k += 64) {
     fo += partials[k];
     fw += partials[(size_t)nb + k];
     fr += partials[2 * (size_t)nb + k];
     smax = fmax(smax, partials[3 * (size_t)nb + k]);
     wmin = fmin(wmin, partials[4 * (size_t)nb + k]);
-    nz += counts[k];
-    no += counts[(size_t)nb + k];
-    nbt += counts[2 * (size_t)nb + k];
+#pragma unroll
+    for (int c = 0; c < NC; c++) n[c] += counts[c * (size_t)nb + k];
   }
-  fo = gnc_wave_sum(fo);
-  fw = gnc_wave_sum(fw);
-  fr = gnc_wave_sum(fr);
-  smax = gnc_wave_max(smax);
-  wmin = gnc_wave_min(wmin);
-  nz = gnc_wave_sum(nz);
-  no = gnc_wave_sum(no);
-  nbt = gnc_wave_sum(nbt);
+  fo = wave_sum(fo);
+  fw = wave_sum(fw);
+  fr = wave_sum(fr);
+  smax = wave_max(smax);
+  wmin = wave_min(wmin);
+#pragma unroll
+  for (int c = 0; c < NC; c++) n[c] = wave_sum(n[c]);
   if (fslot)
     for (int k = lane == 0 ? 64 : lane; k < nslot; k += 64) fslot[k] = 0.0;
   if (lane == 0) {
@@ -146,9 +112,12 @@ __global__ __launch_bounds__(64) void k_gnc_final(int nb, const double *__restri
     sum->sum_rho = fr;
     sum->s_max = smax;
     sum->w_min = wmin;
-    sum->num_zero = nz;
-    sum->num_one = no;
-    sum->num_between = nbt;
+    sum->num_zero = n[0];
+    sum->num_one = n[1];
+    sum->num_between = n[2];
+    long long *more = reinterpret_cast<long long *>(sum + 1);
+#pragma unroll
+    for (int c = GNC_COUNT_SLOTS; c < NC; c++) more[c - GNC_COUNT_SLOTS] = n[c];
     if (fslot) fslot[0] = 0.5 * fo + 0.5 * fw;
   }
 }
@@ -166,7 +135,15 @@ void launch_gnc_edge(int d, hipStream_t st, int m, const double *rec, const doub
   else
     hipLaunchKernelGGL(k_gnc_edge<2>, dim3(nb), dim3(EDGE_BLOCK), 0, st, m, (const double2 *)rec, (const double2 *)X, kind, mu, c2,
                        weigh ? 1 : 0, w, s_out, rows, partials, counts);
-  hipLaunchKernelGGL(k_gnc_final, dim3(1), dim3(64), 0, st, nb, partials, counts, sum, fslot, nslot);
+  launch_gnc_final(st, nb, GNC_COUNT_SLOTS, partials, counts, sum, fslot, nslot);
+}
+
+void launch_gnc_final(hipStream_t st, int nb, int ncounts, const double *partials, const long long *counts, GncSummaryDev *sum,
+                      double *fslot, int nslot) {
+  if (ncounts == GNC_COUNT_SLOTS)
+    hipLaunchKernelGGL(k_gnc_final<GNC_COUNT_SLOTS>, dim3(1), dim3(64), 0, st, nb, partials, counts, sum, fslot, nslot);
+  else
+    hipLaunchKernelGGL(k_gnc_final<ML_GNC_COUNT_SLOTS>, dim3(1), dim3(64), 0, st, nb, partials, counts, sum, fslot, nslot);
 }
 
 }  // namespace dpgo

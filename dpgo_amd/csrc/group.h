@@ -773,6 +773,29 @@ class Group {
   };
   int polish_loop(const double *X, int ld, int arow, const PolishOptions &o, const PolishHooks &hooks, double *Xout, int ldout,
                   double *log, int log_cap, PolishResult &out);
+  // The outer loop of graduated non-convexity (gnc.h; gnc.cpp), shared by gnc and ml_gnc, behind the caller's begin, refusal and
+  // allocation: the option check (who names the caller), level 0, the levels and the read-out into out, Xout, weights and log;
+  // last (optional): the summary the result's sums were read from.  What an objective is to it, filled by the caller:
+  struct GncObjective {
+    // the edge pass at a device point with the weights written (weigh) or read; per_edge: with what only a point needs (gnc:
+    // the rows; ml_gnc: FULL); fslot as robust_eval
+    std::function<void(const double *Xdev, double mu, bool weigh, bool per_edge, int fslot)> pass;
+    std::function<void(GncSummary &q, bool per_edge)> summary;   // of the last pass with that per_edge, read back (synchronises)
+    std::function<void()> gradient;   // behind the point pass at CertState's X: g, |g|^2 into slot 0 of the partials
+    std::function<void()> hessian;    // H_w at CertState's X into the factorisation's values
+    std::function<void(double *s)> edge_s;   // m doubles: s_e as the last per-edge-writing pass left it (synchronises)
+    double *wdev = nullptr;           // the weight array behind the pass, m doubles
+    std::vector<int> in_R;            // per edge: in the robust set
+    int num_robust = 0;               // |R|
+    // Whether the pass at a failure must write per-edge output.  ml_gnc: yes -- chi2 per edge comes from a FULL pass only.
+    // gnc: no -- every pass of it writes s_rot and s_trans, and the rows are of no use there.
+    bool failure_per_edge = false;
+    // Whether a stall at level 0 is evaluated (a pass at X with unit weights, whose sums and counts the result reports) or
+    // returned as it is, those fields zero.  ml_gnc evaluates, gnc does not: both as they were written, kept.
+    bool level0_stall_evaluated = false;
+  };
+  int gnc_loop(const char *who, const double *X, int ld, const GncOptions &o, const GncObjective &ob, double *Xout, int ldout,
+               double *weights, double *log, int log_cap, GncResult &out, GncSummary *last = nullptr);
   // The loop of the Hessian modes (modes.cpp) on CertState's X, behind cov_begin.  What depends on the objective is launched by
   // the caller's hooks, each handed the anchor's own row: hessian -- H at X into the factorisation's values; trial -- F at the
   // trial point V into slot 2 of the certificate's partials
@@ -795,7 +818,7 @@ class Group {
   // gnc.cpp: the buffers of the edge pass; the pass at a record array of the group (fslot as robust_eval), its summary read back
   void gnc_alloc();
   void gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool with_rows, int fslot);
-  void gnc_summary(GncSummaryDev &sd);
+  void gnc_summary(GncSummary &q);
   struct MlState;   // the lists and buffers of the maximum-likelihood objective (ml.cpp), allocated by the first call that is not refused
   MlState *ml_ = nullptr;
   void ml_release();
@@ -810,7 +833,7 @@ class Group {
   void ml_gnc_alloc();
   int ml_gnc_set(const int *robust_set, std::vector<int> &in_R);
   void ml_gnc_pass(const double *Xdev, int kind, double mu, double c2, bool weigh, bool full, int fslot);
-  void ml_gnc_summary(MlGncSummaryDev &sd, bool full);
+  void ml_gnc_summary(GncSummary &q, bool full);
   MargCache *marg_ = nullptr;   // the dense factors of joint_marginal, one per order (marg.cpp), allocated by the first call
   void marg_release();
   // the batches of a column plan behind a factorisation: Sigma_KK of the kept poses into g1 / g2 (device), d_prow <- their records

@@ -13,6 +13,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "wave_reduce.h"
+
 namespace dpgo {
 // what k_inter does on the way, instead of a launch of its own: the fusion fields of InterUpdate (GX, X, Df, gn_slot) or of
 // InterIterate (the rest), as the kernel takes them
@@ -36,12 +38,6 @@ struct Dim {
 // the nodes a launch works on: the by-value bits, and-ed with the device-resident mask when there is one
 __device__ __forceinline__ NodeBits mask_bits(const NodeMask &m) { return m.p ? (m.v & *m.p) : m.v; }
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return (mask_bits(m) >> node) & 1ull; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // Sum NS per-thread values over a 256-thread workgroup and store to dst[s * stride].  Callers store only for segments of
 // nodes inside the launch mask: a masked launch must leave the partials of the other nodes alone (a second, narrower

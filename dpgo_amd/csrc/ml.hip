@@ -9,22 +9,12 @@
 #include "cov.h"
 #include "edge_math.h"
 #include "ml_math.h"
+#include "wave_reduce.h"
 
 namespace dpgo {
 namespace {
 
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return ((m.p ? (m.v & *m.p) : m.v) >> node) & 1ull; }
-
-__device__ __forceinline__ double ml_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long ml_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // FULL: r, Omega r, chi2, the gradient terms and the record [J_i | J_j | Omega J_i | Omega J_j] are written; otherwise F_ml
 // and near_pi alone (the trial point)
@@ -87,7 +77,7 @@ __global__ __launch_bounds__(EDGE_BLOCK) void k_ml_edge(int m, const double2 *__
     }
   }
   const long long n_near = __popcll(__ballot(near));
-  chi2 = ml_wave_sum(chi2);
+  chi2 = wave_sum(chi2);
   if (threadIdx.x == 0) {
     partials[blockIdx.x] = chi2;
     counts[blockIdx.x] = n_near;
@@ -105,8 +95,8 @@ __global__ __launch_bounds__(64) void k_ml_final(int nb, const double *__restric
     f += partials[k];
     nn += counts[k];
   }
-  f = ml_wave_sum(f);
-  nn = ml_wave_sum(nn);
+  f = wave_sum(f);
+  nn = wave_sum(nn);
   if (fslot)
     for (int k = lane == 0 ? 64 : lane; k < nslot; k += 64) fslot[k] = 0.0;
   if (lane == 0) {
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(SEG_ROWS) void k_ml_gather(const Seg *segs, NodeMas
       g2 = fma(acc[k], acc[k], g2);
     }
   }
-  g2 = ml_wave_sum(g2);
+  g2 = wave_sum(g2);
   if (threadIdx.x == 0) partial[(size_t)slot_g2 * nseg + blockIdx.x] = g2;
 }
 

@@ -1,13 +1,10 @@
-// Host side of graduated non-convexity on the maximum-likelihood objective (ml_gnc.h): the outer loop of gnc.cpp on chi2.  The
-// plan, the lists, Omega's check and the refusal are the ML objective's (ml.cpp); the inner solve is polish_loop (polish.cpp),
-// once per level, with the weights of k_ml_gnc_edge held fixed; the gather and the Hessian kernel are ml.hip's, unchanged.  The
-// optimiser's state is not touched (cert_begin).
+// Host side of graduated non-convexity on the maximum-likelihood objective (ml_gnc.h): what this objective is to gnc.cpp's outer
+// loop (gnc_loop), on chi2.  The plan, the lists, Omega's check and the refusal are the ML objective's (ml.cpp); the inner solve
+// is polish_loop (polish.cpp), once per level, with the weights of k_ml_gnc_edge held fixed; the gather and the Hessian kernel
+// are ml.hip's, unchanged.  The optimiser's state is not touched (cert_begin).
 #include "ml_gnc.h"
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstring>
 
 #include "cert_state.h"
 #include "cov_state.h"
@@ -24,27 +21,17 @@ void Group::ml_gnc_alloc() {
   if (n.gnc_on_device) return;
   n.gnc_w.alloc((size_t)n.plan.m);
   n.gnc_in_R.alloc((size_t)n.plan.m);
-  n.gnc_partials.alloc((size_t)ML_GNC_PARTIAL_SLOTS * n.plan.nb);
+  n.gnc_partials.alloc((size_t)GNC_PARTIAL_SLOTS * n.plan.nb);
   n.gnc_counts.alloc((size_t)ML_GNC_COUNT_SLOTS * n.plan.nb);
   n.gnc_sum.alloc(2 * sizeof(MlGncSummaryDev) / sizeof(double));
   n.gnc_on_device = true;
 }
 
-// R of this call: robust_set, or the inter word of the plan's records; uploaded (the stream is synchronised).  Returns |R|.
+// R of this call (gnc_robust_mask on the plan's records), uploaded (the stream is synchronised).  Returns |R|.
 int Group::ml_gnc_set(const int *robust_set, std::vector<int> &in_R) {
   MlState &n = *ml_;
-  const size_t m = (size_t)n.plan.m;
-  const int L = edge_rec_doubles(d_);
-  in_R.resize(m);
-  int count = 0;
-  for (size_t e = 0; e < m; e++) {
-    int i, j;
-    bool f;
-    edge_head(&n.plan.rec[e * L], i, j, f);
-    in_R[e] = robust_set ? robust_set[e] != 0 : f;
-    count += in_R[e];
-  }
-  HIP_CHECK(hipMemcpyAsync(n.gnc_in_R.p, in_R.data(), sizeof(int) * m, hipMemcpyHostToDevice, st_));
+  const int count = gnc_robust_mask(d_, n.plan.m, n.plan.rec.data(), robust_set, in_R);
+  HIP_CHECK(hipMemcpyAsync(n.gnc_in_R.p, in_R.data(), sizeof(int) * in_R.size(), hipMemcpyHostToDevice, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
   return count;
 }
@@ -57,22 +44,18 @@ void Group::ml_gnc_pass(const double *Xdev, int kind, double mu, double c2, bool
                      fslot >= 0 ? cert_->partials.p + (size_t)fslot * nseg : nullptr, nseg);
 }
 
-void Group::ml_gnc_summary(MlGncSummaryDev &sd, bool full) {
+void Group::ml_gnc_summary(GncSummary &q, bool full) {
+  MlGncSummaryDev sd;
   HIP_CHECK(hipMemcpyAsync(&sd, ml_->gnc_sum_dev(full), sizeof(sd), hipMemcpyDeviceToHost, st_));
   HIP_CHECK(hipStreamSynchronize(st_));
+  q.sums = sd.gnc;
+  q.near_pi = sd.near_pi;
+  q.near_pi_all = sd.near_pi_all;
 }
 
 int Group::ml_gnc(const Graph &g, const double *X, int ld, const GncOptions &o, const int *robust_set, long long max_bytes, double *Xout,
                   int ldout, double *weights, double *log, int log_cap, MlGncResult &out) {
   out = MlGncResult();
-  const int rows = (d_ + 1) * num_poses_global_;
-  const PolishOptions &po = o.inner;
-  if (!gnc_args_ok(o.kind, 1.0, o.barc2, "ml gnc")) return -1;
-  if (!X || !Xout || !weights || ld < rows || ldout < rows || !(o.mu_step > 1) || !std::isfinite(o.mu_step) || o.max_levels < 1 ||
-      po.max_steps < 0 || po.max_tries < 1 || !(po.rel_tol >= 0) || !(po.grad_tol >= 0) || log_cap < 0 || (log_cap > 0 && !log)) {
-    fprintf(stderr, "[dpgo_amd] ERROR: ml gnc: bad options or inconsistent size of the output.\n");
-    return -1;
-  }
   if (ml_begin(g, X, ld, o.anchor, "ml gnc") != 0) return -1;
   PolishResult pr;
   {
@@ -85,142 +68,31 @@ int Group::ml_gnc(const Graph &g, const double *X, int ld, const GncOptions &o, 
   }
   ml_alloc();
   ml_gnc_alloc();
-  typedef std::chrono::steady_clock Clock;
-  auto ms_since = [](Clock::time_point t) { return 1e3 * std::chrono::duration<double>(Clock::now() - t).count(); };
-  const auto t_start = Clock::now();
   CertState &c = *cert_;
   CovState &s = *cov_;
   MlState &n = *ml_;
   const int arow = own_row(o.anchor);
   const NodeMask all{all_bits(), nullptr};
-  const size_t m = (size_t)n.plan.m;
-  const int d = d_;
-  const double c2 = o.barc2;
-  double *wdev = n.gnc_w.p;
-  std::vector<int> in_R;
-  std::vector<double> w_cur(m, 1.0), w_prev(m, 1.0), Xa((size_t)rows * d), Xb((size_t)rows * d);
-  HIP_CHECK(hipMemcpyAsync(wdev, w_cur.data(), sizeof(double) * m, hipMemcpyHostToDevice, st_));
-  out.num_robust = ml_gnc_set(robust_set, in_R);   // (synchronises)
-  double mu = 1.0;   // (level 0: the surrogate's sum is not used)
-  PolishHooks hooks;
-  hooks.point = [&] {
-    ml_gnc_pass(c.X.p, o.kind, mu, c2, false, true, 1);
-    launch_ml_gather(lc(all), n.inc_ptr.p, n.inc.p, n.ge.p, arow, s.pol_g.p, 0, c.partials.p);
+  GncObjective ob;
+  ob.wdev = n.gnc_w.p;
+  ob.num_robust = ml_gnc_set(robust_set, ob.in_R);
+  ob.pass = [&](const double *Xdev, double mu, bool weigh, bool full, int fslot) {
+    ml_gnc_pass(Xdev, o.kind, mu, o.barc2, weigh, full, fslot);
   };
-  hooks.hessian = [&] { ml_hessian_launch(arow); };
-  hooks.trial = [&] { ml_gnc_pass(c.V.p, o.kind, mu, c2, false, false, 2); };
-  // one inner solve from `from` into `to`; the counts and the time are added up
-  auto inner = [&](const double *from, int ldf, double *to, PolishResult &res) -> int {
-    res = PolishResult();
-    const int rc = polish_loop(from, ldf, arow, po, hooks, to, rows, nullptr, 0, res);
-    out.steps += res.steps;
-    out.factorisations += res.factorisations;
-    out.inner_outcome = res.outcome;
-    out.inner_ms += res.total_ms;
-    return rc;
-  };
-  // The sums of q describe the returned pair.  chi2 per edge is what the last FULL pass left: on every exit of polish_loop but
-  // STALLED that pass ran at the point the loop hands out (ml.cpp: ml_polish), and the evaluation passes write none.
-  auto read_final = [&](const MlGncSummaryDev &q) {
-    out.F_weighted_final = 0.5 * (q.sum_out + q.sum_ws);
-    out.F_surrogate_final = 0.5 * (q.sum_out + q.sum_rho);
-    out.num_zero = (int)q.num_zero;
-    out.num_one = (int)q.num_one;
-    out.num_between = (int)q.num_between;
-    out.near_pi = q.near_pi;
-    out.near_pi_all = q.near_pi_all;
-    std::vector<double> sv(m);
-    HIP_CHECK(hipMemcpyAsync(sv.data(), n.chi2.p, sizeof(double) * m, hipMemcpyDeviceToHost, st_));
+  ob.summary = [&](GncSummary &q, bool full) { ml_gnc_summary(q, full); };
+  ob.gradient = [&] { launch_ml_gather(lc(all), n.inc_ptr.p, n.inc.p, n.ge.p, arow, s.pol_g.p, 0, c.partials.p); };
+  ob.hessian = [&] { ml_hessian_launch(arow); };
+  ob.edge_s = [&](double *sv) {
+    HIP_CHECK(hipMemcpyAsync(sv, n.chi2.p, sizeof(double) * n.plan.m, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
-    out.num_outliers = 0;
-    for (size_t e = 0; e < m; e++) out.num_outliers += in_R[e] && sv[e] > c2;
   };
-  auto finish = [&](int outcome, const std::vector<double> &Xh, int ldh, const std::vector<double> &wh) {
-    out.outcome = outcome;
-    for (int col = 0; col < d; col++) std::memcpy(Xout + (size_t)col * ldout, Xh.data() + (size_t)col * ldh, sizeof(double) * rows);
-    std::copy(wh.begin(), wh.end(), weights);
-    out.total_ms = ms_since(t_start);
-    return 0;
-  };
-  // X_{k-1} and the weights it was solved with, after an inner stall: a FULL pass there, so that chi2 is that point's too
-  auto failed = [&](const std::vector<double> &Xh, int ldh, const std::vector<double> &wh) {
-    MlGncSummaryDev q;
-    HIP_CHECK(hipMemcpyAsync(wdev, wh.data(), sizeof(double) * m, hipMemcpyHostToDevice, st_));
-    cert_upload(Xh.data(), ldh, d_, c.X.p);
-    ml_gnc_pass(c.X.p, o.kind, mu, c2, false, true, -1);
-    ml_gnc_summary(q, true);
-    read_final(q);
-    return finish(GNC_INNER_FAILED, Xh, ldh, wh);
-  };
-  // level 0
-  PolishResult res;
-  if (inner(X, ld, Xa.data(), res) != 0) return -1;
-  out.F_initial = res.F_initial;
-  if (res.outcome == POLISH_STALLED) {
-    for (int col = 0; col < d; col++) std::memcpy(Xa.data() + (size_t)col * rows, X + (size_t)col * ld, sizeof(double) * rows);
-    return failed(Xa, rows, w_cur);
-  }
-  MlGncSummaryDev sd;
-  auto t0 = Clock::now();
-  ml_gnc_pass(c.X.p, o.kind, mu, c2, false, false, -1);   // (polish_loop leaves its final point in CertState's X)
-  ml_gnc_summary(sd, false);
-  out.edge_ms += ms_since(t0);
-  const double s_max0 = sd.s_max;
-  out.s_max_initial = s_max0;
-  if (out.num_robust == 0 || (o.kind == GNC_TLS && 2 * s_max0 <= c2)) {
-    read_final(sd);
-    out.F_surrogate_final = out.F_weighted_final;   // (unit weights: no surrogate was formed)
-    return finish(GNC_ALL_INLIERS, Xa, rows, w_cur);
-  }
-  mu = o.kind == GNC_TLS ? c2 / (2 * s_max0 - c2) : std::max(1.0, 2 * s_max0 / c2);
-  out.mu_initial = mu;
-  std::vector<double> *Xprev = &Xa, *Xnext = &Xb;
-  int outcome = GNC_MAX_LEVELS;
-  for (int k = 1; k <= o.max_levels; k++) {
-    t0 = Clock::now();
-    w_prev = w_cur;
-    ml_gnc_pass(c.X.p, o.kind, mu, c2, true, false, -1);   // WEIGH at X_{k-1}
-    HIP_CHECK(hipMemcpyAsync(w_cur.data(), wdev, sizeof(double) * m, hipMemcpyDeviceToHost, st_));
-    MlGncSummaryDev sw;
-    ml_gnc_summary(sw, false);
-    out.edge_ms += ms_since(t0);
-    double *row = k - 1 < log_cap ? log + (size_t)(k - 1) * GNC_LOG_COLS : nullptr;
-    if (row) {
-      row[0] = mu;
-      row[1] = 0.5 * (sw.sum_out + sw.sum_rho);
-      row[2] = 0.5 * (sw.sum_out + sw.sum_ws);
-      row[3] = row[4] = row[5] = 0.0;
-      row[6] = POLISH_STALLED;
-      row[7] = (double)sw.num_zero;
-      row[8] = (double)sw.num_one;
-      row[9] = (double)sw.num_between;
-    }
-    out.levels = k;
-    out.mu_final = mu;
-    if (inner(Xprev->data(), rows, Xnext->data(), res) != 0) return -1;
-    if (row) {
-      row[5] = res.steps;
-      row[6] = res.outcome;
-    }
-    // (an inner MAX_STEPS is a level like any other: its point is the last accepted one, and F_w has not increased)
-    if (res.outcome == POLISH_STALLED) return failed(*Xprev, rows, w_prev);
-    t0 = Clock::now();
-    ml_gnc_pass(c.X.p, o.kind, mu, c2, false, false, -1);   // evaluation only, the same mu, at X_k
-    ml_gnc_summary(sd, false);
-    out.edge_ms += ms_since(t0);
-    if (row) {
-      row[3] = 0.5 * (sd.sum_out + sd.sum_ws);
-      row[4] = 0.5 * (sd.sum_out + sd.sum_rho);
-    }
-    std::swap(Xprev, Xnext);
-    if (o.kind == GNC_TLS ? sw.num_between == 0 : mu == 1.0) {
-      outcome = GNC_CONVERGED;
-      break;
-    }
-    mu = o.kind == GNC_TLS ? o.mu_step * mu : std::max(mu / o.mu_step, 1.0);
-  }
-  read_final(sd);
-  return finish(outcome, *Xprev, rows, w_cur);
+  ob.failure_per_edge = true;
+  ob.level0_stall_evaluated = true;
+  GncSummary last;
+  const int rc = gnc_loop("ml gnc", X, ld, o, ob, Xout, ldout, weights, log, log_cap, out, &last);
+  out.near_pi = last.near_pi;
+  out.near_pi_all = last.near_pi_all;
+  return rc;
 }
 
 int Group::ml_gnc_eval(const Graph &g, const double *X, int ld, int kind, double mu, double barc2, const int *robust_set,
@@ -251,11 +123,9 @@ int Group::ml_gnc_eval(const Graph &g, const double *X, int ld, int kind, double
     if (grad) HIP_CHECK(hipMemcpyAsync(grad, n.ge.p, sizeof(double) * 2 * m * dof, hipMemcpyDeviceToHost, st_));
     if (jw) HIP_CHECK(hipMemcpyAsync(jw, n.jw.p, sizeof(double) * m * ml_jw_doubles(d_), hipMemcpyDeviceToHost, st_));
   }
-  MlGncSummaryDev sd;
+  GncSummary sd;
   ml_gnc_summary(sd, true);   // (synchronises)
-  const double v[ML_GNC_SUMS] = {sd.sum_out, sd.sum_ws, sd.sum_rho, sd.s_max, sd.w_min, (double)sd.num_zero, (double)sd.num_one,
-                                 (double)sd.num_between, (double)sd.near_pi, (double)sd.near_pi_all};
-  std::copy(v, v + ML_GNC_SUMS, sums);
+  gnc_summary_doubles(sd, ML_GNC_SUMS, sums);
   return 0;
 }
 

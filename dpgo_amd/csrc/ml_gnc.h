@@ -17,27 +17,11 @@
 //
 // weight_mu and rho_mu are gnc_math.h's gnc_weight_rho, unchanged, applied to s = chi2 (gnc.h writes the formulas out).
 //
-//     level 0:  w = 1;  X0 = inner(X, w);  s_max = max_{e in R} chi2_e(X0)
-//               R empty -> ALL_INLIERS
-//     TLS:      2 s_max <= c2 -> ALL_INLIERS (X0 returned, w = 1);  mu = c2 / (2 s_max - c2)
-//     GM:       mu = max(1, 2 s_max / c2)
-//     for k = 1 .. max_levels:
-//         w_R = weight_mu(chi2(X_{k-1}));  record F_mu(X_{k-1}) and F_w(X_{k-1});  counts of w == 0, w == 1, 0 < w < 1 over R
-//         X_k = inner(X_{k-1}, w);  an inner STALLED -> INNER_FAILED (X_{k-1} and the weights it was solved with returned)
-//         evaluation-only pass at the same mu on X_k:  F_w(X_k), F_mu(X_k), s_max
-//         TLS:  no weight strictly between 0 and 1 -> CONVERGED;   mu = mu_step mu
-//         GM:   mu == 1 -> CONVERGED;                              mu = max(mu / mu_step, 1)
-//     k == max_levels without the above -> MAX_LEVELS
+// The levels, the mu schedule, the outcomes and the invariant (within a level F_mu never increases while the inner solve does
+// not increase F_w) are gnc.h's with s = chi2: the same loop runs them (Group::gnc_loop, gnc.cpp).  inner is polish_loop
+// (polish.h) on (F_w, g_w, H_w) with fixed weights.
 //
-// inner is polish_loop (polish.h) on (F_w, g_w, H_w) with fixed weights.  An inner STALLED at level 0 is INNER_FAILED too,
-// with X itself and unit weights returned.
-//
-// The invariant.  rho_mu(s) = min_w [w s + Phi_mu(w)] (Black-Rangarajan duality, Phi_mu as in gnc.h), attained at
-// w = weight_mu(s).  With w_k = weight_mu(chi2(X_{k-1})):
-//     F_mu(X_k) <= F_{w_k}(X_k) + 1/2 sum_R Phi(w_k) <= F_{w_k}(X_{k-1}) + 1/2 sum_R Phi(w_k) = F_mu(X_{k-1})
-// whenever the inner solve does not increase F_w: within a level F_mu never increases.
-//
-// Two differences from gnc.h.
+// Four differences from gnc.h; the last two are named fields of the objective's description (GncObjective, group.h).
 //  1. An inner MAX_STEPS is normal and is not a failure.  H_w is Gauss-Newton: at the early levels the weighted residuals at
 //     the minimum are large, and the inner loop converges linearly (ml_polish needs 92 steps on tinyGrid3D).  The level's point
 //     is then the last accepted one -- F_w has not increased, which is all the invariant needs.  Only an inner STALLED is
@@ -51,11 +35,16 @@
 //     formulas give for it; were it not, sum_R rho_mu (F_mu: F_surrogate_final and the log's columns 1 and 4) and that edge's
 //     weight would not be finite either, while g_w, H_w and F_w of the edges with w > 0 stay untouched.  max_R chi2 drops a
 //     NaN (fmax).  near_pi > 0 in the result is the caller's flag for this.
+//  3. The pass at a failure writes per-edge output.  chi2 per edge is written by a FULL pass only, and num_outliers is read
+//     from it: after an inner STALLED the point handed back (X_{k-1}, or X at level 0) gets a FULL pass.  gnc.h's pass writes
+//     s_rot and s_trans whatever its flags, so its failure pass leaves the rows off.
+//  4. A level-0 stall is evaluated.  INNER_FAILED at level 0 comes back with F_weighted_final, F_surrogate_final, the counts,
+//     num_outliers and near_pi of (X, w = 1) at mu = 1; gnc.h returns without a pass and leaves them zero.
 //
 // Connectivity: as gnc.h.  A level whose zero weights disconnect the graph makes H_w singular; the Levenberg-Marquardt shift
 // either copes or stalls; a stall is INNER_FAILED, an outcome, not an error.
 //
-// Two kernels (ml_gnc.hip), fp64, fixed-order sums, no floating-point atomics, no LDS: the same bits run to run.
+// One kernel (ml_gnc.hip), fp64, fixed-order sums (wave_reduce.h), no floating-point atomics, no LDS: the same bits run to run.
 //   k_ml_gnc_edge<D, FULL>  one lane per edge in graph order, EDGE_BLOCK per workgroup, records and poses read as 16-byte units
 //                as in k_ml_edge; ml_residual<D> and ml_weigh<D> give chi2.  WEIGH: w = weight_mu(chi2) written for e in R (the
 //                array is not touched elsewhere); FIXED: w read for e in R; 1 outside R in both.  R-membership is an array of
@@ -63,13 +52,15 @@
 //                FULL writes r, chi2 (unweighted) and, through ml_gnc_edge_out, wr = w (Omega r), the gradient terms and the
 //                record [J_i | J_j | w Omega J_i | w Omega J_j] in ml_jw_doubles layout, so that launch_ml_gather and
 //                launch_ml_hessian serve unchanged and H_w inherits k_ml_hessian's bitwise symmetry.  FULL off is the trial
-//                point: sums only.  Per workgroup, by wave shuffle, one partial each: sum_{not R} chi2, sum_R w chi2,
-//                sum_R rho_mu(chi2), max_R chi2, min_R w; the counts of w == 0, w == 1, 0 < w < 1 over R; near_pi over
-//                w > 0, and over all edges.
-//   k_ml_gnc_final  one wave over the partials in strided order: the summary, and optionally F_w into a slot of the
-//                certificate's partial sums with the rest of the slot zeroed, as k_ml_final / k_gnc_final do.
+//                point: sums only.  Per workgroup, by wave shuffle (gnc_partials.h, shared with k_gnc_edge), one partial each:
+//                sum_{not R} chi2, sum_R w chi2, sum_R rho_mu(chi2), max_R chi2, min_R w; the counts of w == 0, w == 1,
+//                0 < w < 1 over R; near_pi over w > 0, and over all edges.
+// The final wave is gnc.hip's k_gnc_final<5> (launch_gnc_final): the summary, and optionally F_w into a slot of the
+// certificate's partial sums with the rest of the slot zeroed, as k_ml_final does.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "gnc.h"
 #include "ml.h"
@@ -82,13 +73,15 @@ struct MlGncResult : GncResult {
   long long near_pi = 0, near_pi_all = 0;
 };
 
-// What the final pass leaves on the device: GncSummaryDev's fields on chi2, then the two near_pi counts.
+// What the final pass leaves on the device: GncSummaryDev on chi2, then the two near_pi counts, where k_gnc_final<5> writes its
+// counts past the third.
 struct MlGncSummaryDev {
-  double sum_out, sum_ws, sum_rho, s_max, w_min;
-  long long num_zero, num_one, num_between, near_pi, near_pi_all;
+  GncSummaryDev gnc;
+  long long near_pi, near_pi_all;
 };
-constexpr int ML_GNC_PARTIAL_SLOTS = 5, ML_GNC_COUNT_SLOTS = 5;   // per workgroup, in the order of the struct
-constexpr int ML_GNC_SUMS = 10;                                   // the summary as doubles (ml_gnc_eval)
+static_assert(sizeof(MlGncSummaryDev) == 80 && offsetof(MlGncSummaryDev, gnc) == 0 && offsetof(MlGncSummaryDev, near_pi) == 64 &&
+                  offsetof(MlGncSummaryDev, near_pi_all) == 72,
+              "the two counts follow GncSummaryDev directly");
 
 // device (ml_gnc.hip); enqueued on st.  in_R: m ints; w: m doubles (weigh: written on R, read nowhere; else read on R); out as
 // launch_ml_edge (out.r == nullptr: the trial point, nothing per edge is written); partials: 5 nb doubles, counts: 5 nb,

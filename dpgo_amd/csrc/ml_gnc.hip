@@ -1,7 +1,7 @@
 // The kernels of graduated non-convexity on the maximum-likelihood objective for gfx950 (ml_gnc.h): the weighted edge pass,
-// with weights from the surrogate or from an array, and its final wave.  fp64 throughout, no fast-math; every sum runs in a
-// fixed order (the lanes of a wave by shuffle in ml_wave_sum's order, the workgroups' partials strided in one final wave):
-// the same bits run to run, no floating-point atomics, no LDS, no inline assembly.
+// with weights from the surrogate or from an array; its tail is gnc_partials.h's and its final wave gnc.hip's.  fp64 throughout,
+// no fast-math; every sum runs in a fixed order (the lanes of a wave by shuffle, wave_reduce.h; the workgroups' partials
+// strided in one final wave): the same bits run to run, no floating-point atomics, no LDS, no inline assembly.
 #include "ml_gnc.h"
 
 #include <cmath>
@@ -9,31 +9,11 @@
 #include "cov.h"
 #include "edge_math.h"
 #include "gnc_math.h"
+#include "gnc_partials.h"
 #include "ml_gnc_math.h"
 
 namespace dpgo {
 namespace {
-
-__device__ __forceinline__ double mg_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double mg_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double mg_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ long long mg_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // FULL: r, chi2, w (Omega r), the weighted gradient terms and the record [J_i | J_j | w Omega J_i | w Omega J_j] are written;
 // otherwise the sums alone (the trial point)
@@ -97,70 +77,7 @@ __global__ __launch_bounds__(EDGE_BLOCK) void k_ml_gnc_edge(int m, const double2
                          out.g + ((size_t)2 * e + 1) * DOF, out.jw + (size_t)e * 4 * DD);
     }
   }
-  const long long n_zero = __popcll(__ballot(zero)), n_one = __popcll(__ballot(one)), n_between = __popcll(__ballot(between));
-  const long long n_near_w = __popcll(__ballot(near_w)), n_near_all = __popcll(__ballot(near_all));
-  f_out = mg_wave_sum(f_out);
-  f_ws = mg_wave_sum(f_ws);
-  f_rho = mg_wave_sum(f_rho);
-  smax = mg_wave_max(smax);
-  wmin = mg_wave_min(wmin);
-  if (threadIdx.x == 0) {
-    const size_t nb = gridDim.x, bk = blockIdx.x;
-    partials[bk] = f_out;
-    partials[nb + bk] = f_ws;
-    partials[2 * nb + bk] = f_rho;
-    partials[3 * nb + bk] = smax;
-    partials[4 * nb + bk] = wmin;
-    counts[bk] = n_zero;
-    counts[nb + bk] = n_one;
-    counts[2 * nb + bk] = n_between;
-    counts[3 * nb + bk] = n_near_w;
-    counts[4 * nb + bk] = n_near_all;
-  }
-}
-
-__global__ __launch_bounds__(64) void k_ml_gnc_final(int nb, const double *__restrict__ partials, const long long *__restrict__ counts,
-                                                     MlGncSummaryDev *__restrict__ sum, double *__restrict__ fslot, int nslot) {
-  const int lane = threadIdx.x;
-  double fo = 0, fw = 0, fr = 0, smax = 0, wmin = INFINITY;
-  long long nz = 0, no = 0, nbt = 0, nw = 0, na = 0;
-  for (int k = lane; k < nb; k += 64) {
-    fo += partials[k];
-    fw += partials[(size_t)nb + k];
-    fr += partials[2 * (size_t)nb + k];
-    smax = fmax(smax, partials[3 * (size_t)nb + k]);
-    wmin = fmin(wmin, partials[4 * (size_t)nb + k]);
-    nz += counts[k];
-    no += counts[(size_t)nb + k];
-    nbt += counts[2 * (size_t)nb + k];
-    nw += counts[3 * (size_t)nb + k];
-    na += counts[4 * (size_t)nb + k];
-  }
-  fo = mg_wave_sum(fo);
-  fw = mg_wave_sum(fw);
-  fr = mg_wave_sum(fr);
-  smax = mg_wave_max(smax);
-  wmin = mg_wave_min(wmin);
-  nz = mg_wave_sum(nz);
-  no = mg_wave_sum(no);
-  nbt = mg_wave_sum(nbt);
-  nw = mg_wave_sum(nw);
-  na = mg_wave_sum(na);
-  if (fslot)
-    for (int k = lane == 0 ? 64 : lane; k < nslot; k += 64) fslot[k] = 0.0;
-  if (lane == 0) {
-    sum->sum_out = fo;
-    sum->sum_ws = fw;
-    sum->sum_rho = fr;
-    sum->s_max = smax;
-    sum->w_min = wmin;
-    sum->num_zero = nz;
-    sum->num_one = no;
-    sum->num_between = nbt;
-    sum->near_pi = nw;
-    sum->near_pi_all = na;
-    if (fslot) fslot[0] = 0.5 * fo + 0.5 * fw;
-  }
+  gnc_store_partials(f_out, f_ws, f_rho, smax, wmin, partials, counts, zero, one, between, near_w, near_all);
 }
 
 template <int D, bool FULL>
@@ -184,7 +101,7 @@ void launch_ml_gnc_edge(int d, hipStream_t st, int m, const double *rec, const d
     if (out.r) launch_edge<2, true>(st, nb, m, rec, omega, X, in_R, kind, mu, c2, weigh, w, out, partials, counts);
     else launch_edge<2, false>(st, nb, m, rec, omega, X, in_R, kind, mu, c2, weigh, w, out, partials, counts);
   }
-  hipLaunchKernelGGL(k_ml_gnc_final, dim3(1), dim3(64), 0, st, nb, partials, counts, sum, fslot, nslot);
+  launch_gnc_final(st, nb, ML_GNC_COUNT_SLOTS, partials, counts, &sum->gnc, fslot, nslot);
 }
 
 }  // namespace dpgo

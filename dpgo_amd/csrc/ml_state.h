@@ -24,9 +24,7 @@ struct Group::MlState {
   DevBuf<double> gnc_w, gnc_partials, gnc_sum;
   DevBuf<int> gnc_in_R;
   DevBuf<int64_t> gnc_counts;
-  long long gnc_bytes() const {
-    return 12ll * plan.m + 8ll * (ML_GNC_PARTIAL_SLOTS + ML_GNC_COUNT_SLOTS) * plan.nb + 2ll * (long long)sizeof(MlGncSummaryDev);
-  }
+  long long gnc_bytes() const { return 12ll * plan.m + gnc_reduce_bytes(plan.nb, ML_GNC_COUNT_SLOTS, 2); }
   long long gnc_remain() const { return gnc_on_device ? 0 : gnc_bytes(); }
   MlGncSummaryDev *gnc_sum_dev(bool full = true) const { return reinterpret_cast<MlGncSummaryDev *>(gnc_sum.p) + (full ? 0 : 1); }
 };

@@ -7,22 +7,12 @@
 #include "polish.h"
 
 #include "cov.h"
+#include "wave_reduce.h"
 
 namespace dpgo {
 namespace {
 
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return ((m.p ? (m.v & *m.p) : m.v) >> node) & 1ull; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
 
 template <int D>
 __global__ __launch_bounds__(SEG_ROWS) void k_polish_grad(const Seg *segs, NodeMask mask, const double *__restrict__ X,

@@ -8,27 +8,12 @@
 
 #include "cov.h"
 #include "robust_math.h"
+#include "wave_reduce.h"
 
 namespace dpgo {
 namespace {
 
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return ((m.p ? (m.v & *m.p) : m.v) >> node) & 1ull; }
-
-__device__ __forceinline__ double rb_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double rb_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ long long rb_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // k_edge_eval (edges.hip) on the group's record array of X, with c_e and, behind with_rows, the rows of M_e X
 template <int D>
@@ -88,9 +73,9 @@ __global__ __launch_bounds__(EDGE_BLOCK) void k_robust_edge(int m, const double2
     down = w < 1.0;
   }
   const long long n_inter = __popcll(__ballot(is_inter)), n_down = __popcll(__ballot(down));
-  f_intra = rb_wave_sum(f_intra);
-  f_inter = rb_wave_sum(f_inter);
-  wmin = rb_wave_min(wmin);
+  f_intra = wave_sum(f_intra);
+  f_inter = wave_sum(f_inter);
+  wmin = wave_min(wmin);
   if (threadIdx.x == 0) {
     const size_t nb = gridDim.x, bk = blockIdx.x;
     partials[bk] = f_intra;
@@ -114,11 +99,11 @@ __global__ __launch_bounds__(64) void k_robust_final(int nb, const double *__res
     ni += counts[k];
     nd += counts[(size_t)nb + k];
   }
-  fi = rb_wave_sum(fi);
-  fe = rb_wave_sum(fe);
-  wmin = rb_wave_min(wmin);
-  ni = rb_wave_sum(ni);
-  nd = rb_wave_sum(nd);
+  fi = wave_sum(fi);
+  fe = wave_sum(fe);
+  wmin = wave_min(wmin);
+  ni = wave_sum(ni);
+  nd = wave_sum(nd);
   if (fslot)
     for (int k = lane == 0 ? 64 : lane; k < nslot; k += 64) fslot[k] = 0.0;
   if (lane == 0) {

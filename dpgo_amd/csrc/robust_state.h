@@ -19,7 +19,7 @@ struct Group::RobustState {
   bool gnc_on_device = false;
   DevBuf<double> gnc_partials, gnc_sum;
   DevBuf<int64_t> gnc_counts;
-  long long gnc_bytes() const { return 8ll * (GNC_PARTIAL_SLOTS + GNC_COUNT_SLOTS) * plan.nb + (long long)sizeof(GncSummaryDev); }
+  long long gnc_bytes() const { return gnc_reduce_bytes(plan.nb, GNC_COUNT_SLOTS, 1); }
   GncSummaryDev *gnc_sum_dev() const { return reinterpret_cast<GncSummaryDev *>(gnc_sum.p); }
 };
 

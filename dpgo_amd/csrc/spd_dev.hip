@@ -32,6 +32,7 @@
 
 #include "settings.h"
 #include "spd.h"
+#include "wave_reduce.h"
 
 namespace dpgo {
 
@@ -810,12 +811,6 @@ constexpr int VS_ROWS = 32;      // rows of one front per workgroup: eight per w
 constexpr int VS_CHUNK = 2048;   // doubles of a front's input vector staged in LDS at a time (16 KiB); a launch may ask for fewer
 int vs_chunk = VS_CHUNK;         // spd_vsolve_chunk: what the launches ask for
 
-__device__ __forceinline__ double vs_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // position p of front f's assembled vector: the right-hand side on a pivot, plus the children's update rows in list order
 __device__ __forceinline__ double vs_assembled(const VsolveDesc &f, int p, const int *__restrict__ piv_idx,
                                                const int *__restrict__ asm_ptr, const int *__restrict__ asm_src,
@@ -860,7 +855,7 @@ __global__ __launch_bounds__(256) void k_vs_forward(const VsolveDesc *__restrict
 #pragma unroll
   for (int i = 0; i < RW; i++) {
     const int p = r0 + wv * RW + i;
-    const double v = vs_wave_sum(acc[i]);
+    const double v = wave_sum(acc[i]);
     if (lane == 0 && p < m) {
       if (p < f.w) y[piv_idx[f.piv_ptr + p]] = v;
       else ub[f.ubuf_off + p - f.w] = v + vs_assembled(f, p, piv_idx, asm_ptr, asm_src, x, ub);
@@ -903,7 +898,7 @@ __global__ __launch_bounds__(256) void k_vs_backward(const VsolveDesc *__restric
 #pragma unroll
   for (int i = 0; i < RW; i++) {
     const int r = r0 + wv * RW + i;
-    const double v = vs_wave_sum(acc[i]);
+    const double v = wave_sum(acc[i]);
     if (lane == 0 && r < f.w) x[piv_idx[f.piv_ptr + r]] = v;
   }
 }

@@ -8,16 +8,12 @@
 // segments in order (k_polish_reduce): the same bits run to run, no atomics.
 #include "stair.h"
 
+#include "wave_reduce.h"
+
 namespace dpgo {
 namespace {
 
 __device__ __forceinline__ bool node_on(const NodeMask &m, int node) { return ((m.p ? (m.v & *m.p) : m.v) >> node) & 1ull; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
 
 // a pose's block of a lifted array: t (2d), then the rows of Y (d x 2d, row-major)
 template <int D>

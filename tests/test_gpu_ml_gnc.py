@@ -184,6 +184,31 @@ def test_a_rank_deficient_level_is_an_outcome():
     assert ok[2].outcome == dpgo_amd.GNC_CONVERGED and np.all(ok[1][-2:] == 0) and np.all(np.isfinite(ok[0]))
 
 
+def test_a_level_zero_stall_is_evaluated():
+    """test_ml_gnc_host.LEVEL0_STALL: with max_tries = 1 the unit-weight solve stalls before any level.  INNER_FAILED at level 0
+    with X itself and unit weights, the counts of the restatement -- and, unlike NodeGroup.gnc, with the sums, the counts and
+    near_pi of one FULL pass at (X, w = 1, mu = 1): the bits of ml_gnc_eval there, which is the same kernel at the same point."""
+    E, X, R, _, rs, G, grp = objects("m2_40")
+    d, m = E["d"], len(E["I"])
+    c2 = mgi.C2[d]
+    want = mgr.run(E, X, gr.TLS, c2, R, mu_step=mgi.MU_STEP, max_tries=1)
+    assert want["outcome"] == gr.INNER_FAILED and want["levels"] == 0 and want["inner"] == [nr.STALLED]
+    Xd, w, res, log = grp.ml_gnc(G, X, options(d, gr.TLS, max_tries=1), robust_set=rs)
+    chi2, _, sums = grp.ml_gnc_eval(G, X, gr.TLS, 1.0, c2, robust_set=rs, w_in=np.ones(m))
+    print("level-0 stall: %s, level %d, inner %d, %d steps, %d factorisations (restated %d, %d); F_w %.17g (eval %.17g), "
+          "outliers %d (eval %d), near_pi %d / %d (eval %d / %d)"
+          % (dpgo_amd.GNC_NAMES[res.outcome], res.levels, res.inner_outcome, res.steps, res.factorisations, want["steps"],
+             want["factorisations"], res.F_weighted_final, 0.5 * (sums[0] + sums[1]), res.num_outliers, int(np.sum(R & (chi2 > c2))),
+             res.near_pi, res.near_pi_all, int(sums[8]), int(sums[9])))
+    assert res.outcome == dpgo_amd.GNC_INNER_FAILED and res.levels == 0 and res.inner_outcome == dpgo_amd.POLISH_STALLED
+    assert len(log) == 0 and np.array_equal(Xd, X) and np.all(w == 1.0)
+    assert (res.steps, res.factorisations) == (want["steps"], want["factorisations"])
+    assert res.num_robust == R.sum() and res.num_one == res.num_robust and (res.num_zero, res.num_between) == (0, 0)
+    assert res.near_pi == res.near_pi_all and (res.near_pi, res.near_pi_all) == (int(sums[8]), int(sums[9]))
+    assert res.F_weighted_final == 0.5 * (sums[0] + sums[1])
+    assert res.num_outliers == int(np.sum(R & (chi2 > c2)))
+
+
 def test_skipped_allocates_nothing():
     E, X, R, _, rs, G, _ = objects("m3_24")
     grp = ops.group_of(E, 1)

@@ -1,5 +1,5 @@
 """The weighted edge pass of graduated non-convexity on the maximum-likelihood objective on the device
-(dpgo_amd/csrc/ml_gnc.hip: k_ml_gnc_edge, k_ml_gnc_final) through NodeGroup.ml_gnc_eval, against the long-double restatement
+(dpgo_amd/csrc/ml_gnc.hip: k_ml_gnc_edge; gnc.hip: k_gnc_final) through NodeGroup.ml_gnc_eval, against the long-double restatement
 (tests/ml_gnc_restatement.py) within the bounds tests/test_ml_gnc_host.py states -- ml_restatement.edge_bounds with the
 constants of tests/test_ml_host.py, gnc_restatement.w_bound, and  w bound(q) + bound(w) |q| + u |w q|  -- and no others.
 

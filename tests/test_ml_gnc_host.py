@@ -148,6 +148,22 @@ def test_committed_runs_meet_the_conditions_and_the_invariant(name, kind):
         assert log[-1, 0] == 1.0 and np.all(log[:-1, 0] > 1.0)
 
 
+LEVEL0_STALL = dict(name="m2_40", kind=mgr.TLS, max_tries=1)   # tests/test_gpu_ml_gnc.py runs the device on the same input
+
+
+@pytest.mark.parametrize("start", ["X", "perturbed"])
+def test_level_zero_stall_of_the_restatement(start):
+    """With one try per step the unit-weight solve of m2_40 stalls before any level: INNER_FAILED at level 0 with the start
+    itself and unit weights, from the case's start and from the perturbed one alike -- the input of the device's test of that
+    path."""
+    E, X, R, _, _ = mgi.case(LEVEL0_STALL["name"])
+    X0 = X if start == "X" else mgi.perturbed(X)
+    run = mgr.run(E, X0, LEVEL0_STALL["kind"], mgi.C2[E["d"]], R, mu_step=mgi.MU_STEP, max_tries=LEVEL0_STALL["max_tries"])
+    assert run["outcome"] == mgr.INNER_FAILED and run["levels"] == 0 and run["inner"] == [nr.STALLED] and len(run["log"]) == 0
+    assert (run["steps"], run["factorisations"]) == (14, 15)
+    assert np.array_equal(run["X"], X0) and np.all(run["w"] == 1.0)
+
+
 @pytest.mark.parametrize("name", ["m3_24", "m2_40"])
 def test_weighted_gradient_is_the_central_difference_of_F_w(name):
     """g_w'v, g_w assembled from the host twin's gradient terms, against (F_w(retract(X, h v)) - F_w(retract(X, -h v))) / 2h with
