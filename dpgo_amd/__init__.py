@@ -315,6 +315,12 @@ SYMBOLS = {
                                        C.c_void_p]),
     "dpgo_group_ml_covariance": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _IP, C.c_int, _DP, _DP,
                                            C.c_void_p]),
+    "dpgo_group_ml_edge_reliability": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, C.c_int, _IP, C.c_int,
+                                                 _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_group_ml_pair_gate": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, C.c_longlong, _IP, C.c_int, _DP, _DP, _DP,
+                                          _DP, _DP, _DP, C.c_void_p]),
+    "dpgo_debug_ml_rely_edge_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "dpgo_debug_ml_rely_edge": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
     "dpgo_group_ml_hessian": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, C.c_int, _IP, _IP, _DP, C.c_longlong,
                                         C.POINTER(C.c_longlong), _DP, _DP]),
     "dpgo_group_ml_eval": (C.c_int, [C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, C.POINTER(C.c_longlong), _DP, _DP, _DP, _DP, _DP]),
@@ -1646,6 +1652,48 @@ class NodeGroup:
                                "information matrix that is not symmetric positive definite)")
         return marg, cross, r
 
+    def ml_edge_reliability(self, X, edges=None, anchor=0, method=0, max_bytes=0, graph=None):
+        """`edge_reliability` on the full information matrices (dpgo_group_ml_edge_reliability): the Hessian is
+        H = sum J' Omega J with the graph's Omega, rel = J Sigma_joint J' with the exact Jacobians of the ML residual, and
+        d2_loo = r' (Omega^-1 - rel)^-1 r, r_loo, influence, the redundancies and d2_own = chi2_e are measured in Omega -- a
+        chi-square quantity of dof degrees of freedom for anisotropic noise.  X should be an `ml_polish` point.  Returns
+        `edge_reliability`'s dict (flag 2 does not occur); result.stationarity is the norm of the tangent gradient of F_ml, and
+        the redundancies sum to dof (m - N + 1)."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        records, rel, joint, edge_args = _rely_arg(g_, edges)
+        r = RelyResult()
+        if lib().dpgo_group_ml_edge_reliability(self._h, g_._h, _dp(X), ld, int(anchor), int(max_bytes), int(method), *edge_args,
+                                                _dp(records), _dp(rel), _dp(joint), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_ml_edge_reliability failed (a robust-loss group, a group that does not host every node, a "
+                               "graph that is not the group's, an anchor or an edge index outside it, an unknown method, or an "
+                               "information matrix that is not symmetric positive definite)")
+        return rely_output(g_.d, records, rel, joint, r)
+
+    def ml_pair_gate(self, X, pairs, candidates, anchor=0, max_bytes=0, threshold=None, graph=None):
+        """The loop-closure gate of `pair_covariance` on the full information matrices (dpgo_group_ml_pair_gate): for every
+        pair (p, q) -- p == q and the anchor allowed -- with candidates = (R (n, d, d), t (n, d), info (n, dof, dof), each
+        symmetric positive definite), d2 = r' (rel + info^-1)^-1 r with the ML residual r and rel = J Sigma_joint J' on
+        H = sum J' Omega J.  Returns `pair_covariance`'s dict (joint, rel, result, d2, not_pd, residual; accept with a
+        threshold)."""
+        X, ld = _fcol(X)
+        g_ = graph or self.graph
+        d, dof = g_.d, _dof(g_.d)
+        P = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)
+        n = len(P)
+        R, t, info = candidates
+        R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(n, d * d))
+        t = np.ascontiguousarray(np.asarray(t, np.float64).reshape(n, d))
+        info = np.ascontiguousarray(np.asarray(info, np.float64).reshape(n, dof * dof))
+        joint, rel, gate = np.zeros((n, 3, dof, dof)), np.zeros((n, dof, dof)), np.zeros((n, 2 + dof))
+        r = PairsResult()
+        if lib().dpgo_group_ml_pair_gate(self._h, g_._h, _dp(X), ld, int(anchor), int(max_bytes), _ip(P) if n else None, n, _dp(R),
+                                         _dp(t), _dp(info), _dp(joint), _dp(rel), _dp(gate), C.byref(r)) != 0:
+            raise RuntimeError("dpgo_group_ml_pair_gate failed (a robust-loss group, a group that does not host every node, a graph "
+                               "that is not the group's, an anchor or a pair outside it, or an information matrix -- the graph's or "
+                               "a candidate's -- that is not symmetric positive definite)")
+        return pairs_output(joint, rel, gate, r, True, threshold)
+
     def ml_hessian(self, X, anchor=0, graph=None):
         """Debug: the anchored Gauss-Newton Hessian of F_ml as the device wrote it (dpgo_group_ml_hessian).  Returns (ptr,
         col, val, g, F): the CSR of `cov_hessian`, the tangent gradient (dof N by global pose, zeros on the anchor), F_ml."""
@@ -2703,6 +2751,30 @@ def rely_edge_debug(d, rel, r, kappa, tau, device=None):
     if rc != 0:
         raise RuntimeError("dpgo_debug_rely_edge failed")
     return rec
+
+
+def ml_rely_edge_debug(d, J, joint, omega, r, sign=-1, device=None):
+    """The arithmetic of NodeGroup.ml_edge_reliability (sign -1) and ml_pair_gate (sign +1) on given arrays (test hooks): J
+    (n, 2, dof, dof) = [J_p | J_q], joint (n, 3, dof, dof), omega (n, dof, dof), r (n, dof).  device None: on the host
+    (dpgo_debug_ml_rely_edge_host; no GPU); an int: k_ml_rel and k_ml_rely_edge alone on that HIP device
+    (dpgo_debug_ml_rely_edge).  Returns (rel (n, dof, dof), records (n, 6 + 2 dof) or (n, 2 + dof))."""
+    dof = _dof(d)
+    J = np.ascontiguousarray(J, np.float64).reshape(-1, 2, dof, dof)
+    n = J.shape[0]
+    joint = np.ascontiguousarray(joint, np.float64).reshape(-1, 3, dof, dof)
+    omega = np.ascontiguousarray(omega, np.float64).reshape(-1, dof, dof)
+    r = np.ascontiguousarray(r, np.float64).reshape(-1, dof)
+    if d not in (2, 3) or joint.shape[0] != n or omega.shape[0] != n or r.shape[0] != n:
+        raise ValueError("ml_rely_edge_debug: bad sizes")
+    rel, rec = np.zeros((n, dof, dof)), np.zeros((n, 6 + 2 * dof if sign < 0 else 2 + dof))
+    if device is None:
+        rc = lib().dpgo_debug_ml_rely_edge_host(int(d), n, int(sign), _dp(J), _dp(joint), _dp(omega), _dp(r), _dp(rel), _dp(rec))
+    else:
+        rc = lib().dpgo_debug_ml_rely_edge(int(device), int(d), n, int(sign), _dp(J), _dp(joint), _dp(omega), _dp(r), _dp(rel),
+                                           _dp(rec))
+    if rc != 0:
+        raise RuntimeError("dpgo_debug_ml_rely_edge failed (bad sizes, a sign that is not +-1, or an omega that is not positive definite)")
+    return rel, rec
 
 
 def sens_edge_debug(graph, X, lam):

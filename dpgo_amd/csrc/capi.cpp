@@ -1177,6 +1177,32 @@ int dpgo_group_ml_covariance(dpgo_group_t *h, const dpgo_graph_t *g, const doubl
   });
 }
 
+// ---- edge reliability and candidate gating on the full information matrices (ml_rely.h) ----
+int dpgo_group_ml_edge_reliability(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
+                                   int method, const int *edges, int nedges, double *records, double *rel, double *joint,
+                                   dpgo_rely_result_t *result) {
+  if (!h || !h->grp || !g || !X || !records || !result || (edges && nedges < 0)) return -1;
+  return guarded([&] {
+    dpgo::RelyResult r;
+    const int rc = h->grp->ml_edge_reliability(g->g, X, ld, anchor, max_bytes, method, edges, nedges, records, rel, joint, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
+int dpgo_group_ml_pair_gate(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, long long max_bytes,
+                            const int *pairs, int npairs, const double *cand_R, const double *cand_t, const double *cand_info,
+                            double *joint, double *rel, double *gate, dpgo_pairs_result_t *result) {
+  if (!h || !h->grp || !g || !X || !result || npairs < 0) return -1;
+  if (npairs > 0 && (!pairs || !cand_R || !cand_t || !cand_info || !joint || !rel || !gate)) return -1;
+  return guarded([&] {
+    dpgo::PairsResult r;
+    const int rc = h->grp->ml_pair_gate(g->g, X, ld, anchor, max_bytes, pairs, npairs, cand_R, cand_t, cand_info, joint, rel, gate, r);
+    to_c(r, result);
+    return rc;
+  });
+}
+
 int dpgo_group_ml_hessian(dpgo_group_t *h, const dpgo_graph_t *g, const double *X, int ld, int anchor, int *ptr, int *col, double *val,
                           long long cap, long long *nnz, double *grad, double *F) {
   if (!h || !h->grp || !g || !X || !nnz) return -1;

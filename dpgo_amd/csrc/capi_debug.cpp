@@ -10,6 +10,7 @@
 
 #include "cert.h"
 #include "comm.h"
+#include "ml_rely.h"
 #include "pairs_math.h"
 
 // A CSR matrix handed over the C ABI, checked and copied into A: n > 0, no null array, ptr from 0 and monotone, every column
@@ -1037,6 +1038,22 @@ int dpgo_debug_rely_edge(int device, int d, int n, const double *rel, const doub
   return guarded([&] {
     if (hipSetDevice(device) != hipSuccess) return -1;
     return dpgo::rely_edge_device(d, n, rel, r, kappa, tau, records);
+  });
+}
+
+int dpgo_debug_ml_rely_edge_host(int d, int n, int sign, const double *J, const double *joint, const double *omega, const double *r,
+                                 double *rel, double *records) {
+  return guarded([&] { return dpgo::ml_rely_edge_host(d, n, sign, J, joint, omega, r, rel, records); });
+}
+
+int dpgo_debug_ml_rely_edge(int device, int d, int n, int sign, const double *J, const double *joint, const double *omega,
+                            const double *r, double *rel, double *records) {
+  return guarded([&] {
+    if (hipSetDevice(device) != hipSuccess) {
+      (void)hipGetLastError();   // (the refusal is this call's: no later launch check may find it)
+      return -1;
+    }
+    return dpgo::ml_rely_edge_device(d, n, sign, J, joint, omega, r, rel, records);
   });
 }
 

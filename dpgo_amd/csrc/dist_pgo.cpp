@@ -34,6 +34,8 @@
 //   --covariance FILE                                                                               step_covariance
 //   --robust_covariance FILE                                                                        step_robust_covariance
 //   --ml_covariance FILE, --ml_report FILE                                                          step_ml_covariance, step_ml_report
+//   --ml_edge_reliability FILE                                                                      step_ml_reliability
+//   --ml_gate_candidates FILE --ml_gate_report FILE                                                 step_ml_gate
 //   --gate_candidates FILE --gate_report FILE                                                       step_gate
 //   --sensitivity_pose P --sensitivity_report FILE                                                  step_sensitivity
 //   --edge_reliability FILE                                                                         step_reliability
@@ -67,7 +69,7 @@ struct Args {
   // the steps after the loop
   std::string gnc, gnc_report, gnc_filtered, modes_report, edge_report, covariance, robust_covariance, gate_candidates, gate_report,
       sensitivity_report, edge_reliability, marginal_set, marginal_report, select_candidates, select_report, ml_covariance, ml_report,
-      ml_gnc, ml_gnc_report;
+      ml_gnc, ml_gnc_report, ml_edge_reliability, ml_gate_candidates, ml_gate_report;
   bool polish = false, modes_escape = false, staircase = false, robust_polish = false, ml_polish = false, certify = false,
        verify = false, verify_reweighted = false;
   int hessian_modes = 0, sensitivity_pose = -1, marginal_base = -1, select_budget = -1;
@@ -136,7 +138,8 @@ static int parse_args(int argc, char **argv, Args &a) {
       val("--select_candidates", a.select_candidates), val("--select_report", a.select_report), val("--select_budget", a.select_budget),
       val("--select_d2_max", a.select_d2_max), on("--ml_polish", a.ml_polish), val("--ml_covariance", a.ml_covariance),
       val("--ml_report", a.ml_report), val("--ml_gnc", a.ml_gnc), val("--ml_gnc_barc2", a.ml_gnc_barc2),
-      val("--ml_gnc_report", a.ml_gnc_report)};
+      val("--ml_gnc_report", a.ml_gnc_report), val("--ml_edge_reliability", a.ml_edge_reliability),
+      val("--ml_gate_candidates", a.ml_gate_candidates), val("--ml_gate_report", a.ml_gate_report)};
   if (getenv("RANK")) a.rank = atoi(getenv("RANK"));
   if (getenv("WORLD_SIZE")) a.world = atoi(getenv("WORLD_SIZE"));
   for (int i = 1; i < argc; i++) {
@@ -810,8 +813,10 @@ struct Candidates {
   std::vector<double> cand;
 };
 
-// `reasons` is the caller's list of what makes the file unusable, for its error; at least min_count candidates.
-static int load_candidates(const Run &r, const std::string &file, int min_count, const char *reasons, Candidates &c) {
+// `reasons` is the caller's list of what makes the file unusable, for its error; at least min_count candidates.  info
+// (optional): the candidates' information matrices as the file has them (dof^2 each; Omega_iso for a file without).
+static int load_candidates(const Run &r, const std::string &file, int min_count, const char *reasons, Candidates &c,
+                           std::vector<double> *info = nullptr) {
   const int d = r.d, nc = d * d + d + 2;
   dpgo_graph_t *cg = nullptr;
   int cd = 0, cN = 0, cn = 0, m = 0;
@@ -825,7 +830,11 @@ static int load_candidates(const Run &r, const std::string &file, int min_count,
   c.cand.resize((size_t)m * nc);
   std::vector<int> I(m), J(m);
   std::vector<double> R((size_t)m * d * d), t((size_t)m * d), kappa(m), tau(m);
-  const int got = dpgo_graph_edges(cg, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data());
+  int got = dpgo_graph_edges(cg, I.data(), J.data(), R.data(), t.data(), kappa.data(), tau.data());
+  if (got == 0 && info) {
+    info->assign((size_t)m * r.dof * r.dof, 0.0);
+    got = dpgo_graph_edge_information(cg, info->data(), nullptr);
+  }
   dpgo_graph_free(cg);
   if (got != 0) {
     fprintf(stderr, "Cannot read the edges of %s.\n", file.c_str());
@@ -870,6 +879,85 @@ static int step_gate(Run &r) {
          pr.stationarity);
   if (pr.outcome != DPGO_PAIRS_OK) return 0;
   FILE *f = open_report(a.gate_report.c_str());
+  if (!f) return -1;
+  for (int k = 0; k < m; k++) {
+    const double *gk = &gate[(size_t)k * (2 + dof)];
+    fprintf(f, "%d %d %.17g %d %d", c.pairs[2 * k], c.pairs[2 * k + 1], gk[0], dof, gk[1] != 0.0 ? 1 : 0);
+    write_upper(f, &rel[(size_t)k * dof * dof], dof);
+    fprintf(f, "\n");
+  }
+  fclose(f);
+  return 0;
+}
+
+// --ml_edge_reliability FILE (for any --loss and a world of one rank; empty: off)  at the final X -- behind --ml_polish its
+// point: dpgo_group_ml_edge_reliability of every edge (pose 0 the anchor, DPGO_RELY_AUTO) on the file's information matrices;
+// behind --ml_gnc of the graph without the edges of weight 0, as --ml_covariance.  One more line on stdout
+//     ml reliability: <outcome> <method> <edges> <flagged> <redundancy_sum> <device_bytes> <pivot_min> <stationarity>
+// and, for OK, one line per edge in FILE, in --edge_reliability's format (17 digits; e: the edge's index in the whole graph):
+//     e p q redundancy redundancy_trans d2_own d2_loo flag influence
+static int step_ml_reliability(Run &r) {
+  const Args &a = r.a;
+  if (a.ml_edge_reliability.empty() || r.refused("ml reliability")) return 0;
+  const int m = r.ml_edges(), w = 6 + 2 * r.dof;
+  std::vector<double> Xc, rec((size_t)std::max(m, 1) * w, 0.0);
+  dpgo_rely_result_t rr;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0 || r.load_edges() != 0) return -1;
+  if (dpgo_group_ml_edge_reliability(grp, r.ml_graph(), Xc.data(), r.ld, 0, 0, DPGO_RELY_AUTO, nullptr, 0, rec.data(), nullptr, nullptr,
+                                     &rr) != 0)
+    return -1;
+  printf("ml reliability: %s %s %d %d %.17g %lld %.16g %.16g\n", rely_name(rr.outcome), rely_method_name(rr.method_used), rr.edges,
+         rr.flagged, rr.redundancy_sum, rr.device_bytes, rr.pivot_min, rr.stationarity);
+  if (rr.outcome != DPGO_RELY_OK) return 0;
+  FILE *f = open_report(a.ml_edge_reliability.c_str());
+  if (!f) return -1;
+  for (int e = 0; e < m; e++) {
+    const double *q = &rec[(size_t)e * w];
+    fprintf(f, "%d %d %d %.17g %.17g %.17g %.17g %d %.17g\n", r.ml_edge(e), r.I[r.ml_edge(e)], r.J[r.ml_edge(e)], q[2], q[3], q[4], q[0],
+            (int)q[1], q[5]);
+  }
+  fclose(f);
+  return 0;
+}
+
+// --ml_gate_candidates FILE --ml_gate_report FILE (likewise; both or neither)  FILE is a .g2o of candidate edges p -> q, read as
+// --gate_candidates reads it, with its information matrices kept; every candidate is tested against the final X with
+// dpgo_group_ml_pair_gate (pose 0 the anchor; behind --ml_gnc against the graph without the edges of weight 0), one line per
+// candidate in the report, in --gate_report's format,
+//     p q d2 dof not_pd  S[0][0] S[0][1] ... S[dof-1][dof-1]   (the upper triangle of rel, 17 digits)
+// and one more line on stdout
+//     ml gate: <outcome> <candidates> <columns> <batches> <device_bytes> <pivot_min> <stationarity>
+// (NOT_PD or SKIPPED: the report is not written)
+static int step_ml_gate(Run &r) {
+  const Args &a = r.a;
+  if (a.ml_gate_candidates.empty() && a.ml_gate_report.empty()) return 0;
+  if (a.ml_gate_candidates.empty() || a.ml_gate_report.empty()) {
+    fprintf(stderr, "--ml_gate_candidates and --ml_gate_report go together.\n");
+    return -1;
+  }
+  if (r.refused("ml gate")) return 0;
+  Candidates c;
+  std::vector<double> info;
+  if (load_candidates(r, a.ml_gate_candidates, 0, "unreadable, another dimension, or a pose that is not in the graph", c, &info) != 0)
+    return -1;
+  const int d = r.d, dof = r.dof, m = c.m, nc = d * d + d + 2;
+  std::vector<double> Xc, cR((size_t)m * d * d), ct((size_t)m * d), joint((size_t)m * 3 * dof * dof), rel((size_t)m * dof * dof),
+      gate((size_t)m * (2 + dof));
+  for (int k = 0; k < m; k++) {
+    std::copy_n(&c.cand[(size_t)k * nc], d * d, &cR[(size_t)k * d * d]);
+    std::copy_n(&c.cand[(size_t)k * nc + d * d], d, &ct[(size_t)k * d]);
+  }
+  dpgo_pairs_result_t pr;
+  dpgo_group_t *grp = ml_group(r);
+  if (!grp || r.point(Xc) != 0) return -1;
+  if (dpgo_group_ml_pair_gate(grp, r.ml_graph(), Xc.data(), r.ld, 0, 0, c.pairs.data(), m, cR.data(), ct.data(), info.data(), joint.data(),
+                              rel.data(), gate.data(), &pr) != 0)
+    return -1;
+  printf("ml gate: %s %d %d %d %lld %.16g %.16g\n", pairs_name(pr.outcome), m, pr.columns, pr.batches, pr.device_bytes, pr.pivot_min,
+         pr.stationarity);
+  if (pr.outcome != DPGO_PAIRS_OK) return 0;
+  FILE *f = open_report(a.ml_gate_report.c_str());
   if (!f) return -1;
   for (int k = 0; k < m; k++) {
     const double *gk = &gate[(size_t)k * (2 + dof)];
@@ -1058,7 +1146,7 @@ int main(int argc, char **argv) {
   if (setup(r) != 0 || initialise(r, X) != 0 || solve(r, results) != 0) return -1;
   for (int (*step)(Run &) : {step_gnc, step_polish, step_modes, step_staircase, step_robust_polish, step_ml_polish, step_ml_gnc,
                              step_certify, step_verify, step_edges, step_covariance, step_robust_covariance, step_ml_covariance,
-                             step_ml_report, step_gate, step_sensitivity, step_reliability, step_marginal, step_candidates})
+                             step_ml_report, step_ml_reliability, step_ml_gate, step_gate, step_sensitivity, step_reliability, step_marginal, step_candidates})
     if (step(r) != 0) return -1;
   if (r.ml_kept) dpgo_graph_free(r.ml_kept);
   if (r.post) dpgo_group_free(r.post);

@@ -240,6 +240,15 @@ class Group {
                          long long cap);
   int ml_eval(const Graph &g, const double *X, int ld, double *F, long long *near_pi, double *r, double *chi2, double *wr, double *grad,
               double *jw);
+  // ---- edge reliability and candidate gating on the full information matrices (ml_rely.h, ml_rely.cpp): edge_reliability's
+  // arguments, list semantics, methods and outputs on H = sum J' Omega J with the graph's Omega, stationarity = |g_ml|; and
+  // pair_covariance's gate (SOLVE only) for candidates (R~, t~, Omega): cand_R npairs x d^2 row-major, cand_t npairs x d,
+  // cand_info npairs x dof^2, each symmetric positive definite (-1 otherwise, the candidate named).  The restrictions of ml_covariance.
+  int ml_edge_reliability(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, int method, const int *edges,
+                          int nedges, double *rec, double *rel, double *joint, RelyResult &out);
+  int ml_pair_gate(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, const int *pairs, int npairs,
+                   const double *cand_R, const double *cand_t, const double *cand_info, double *joint, double *rel, double *gate,
+                   PairsResult &out);
   // ---- graduated non-convexity on the maximum-likelihood objective (ml_gnc.h, ml_gnc.cpp): GNC-TLS / GNC-GM on chi2_e =
   // r_e' Omega_e r_e, one polish_loop per level on (F_w, g_w, H_w) with the weights of k_ml_gnc_edge.  The restrictions and the
   // refusals of ml_polish and of gnc; barc2 is a threshold on chi2.  weights: num_edges; log: log_cap rows of GNC_LOG_COLS.
@@ -828,6 +837,7 @@ class Group {
   void ml_edge_pass(const double *Xdev, bool full, int fslot);   // fslot >= 0: F into that slot of the certificate's partial sums
   void ml_point(int arow, double *g, int slot_g2, int fslot);     // the full edge pass at CertState's X and the gather into g
   void ml_hessian_launch(int arow);
+  double ml_stationarity(const double *X, int ld, int arow);   // X uploaded, the full edge pass and the gather: |g_ml| (ml_rely.cpp)
   // ml_gnc.cpp: the buffers of the weighted edge pass; the robust set of a call, uploaded (returns |R|); the pass at a record
   // array of the group (full: the per-edge arrays and summary [0], else summary [1]; fslot as ml_edge_pass); a summary read back
   void ml_gnc_alloc();
@@ -842,6 +852,10 @@ class Group {
   int pairs_setup(long long max_bytes, HessPart own, int kb, HessAnalysis &out);
   // the batches of a plan behind a factorisation: joint (device, zeroed by the caller) <- the blocks of the pairs (pairs.cpp)
   int pairs_solve_joint(const PairsPlan &pl, int npairs, const int *d_prow, double *d_joint, const char *who);
+  // the three blocks of nu listed edges behind a factorisation, by the selected inversion's gather map or by the batches
+  // (rely.cpp; edge_reliability and ml_edge_reliability share it)
+  int rely_joint(int use, const PairsPlan &pl, int nu, const std::vector<int> &prow, int arow, const int *d_prow, double *d_joint,
+                 const char *who);
   // a graph checked against the group and its pattern; rec: its edge records in graph order, heads on unified own rows; eb:
   // the four blocks of every edge (robust.cpp; sens.cpp and rely.cpp too)
   int graph_records_own(const Graph &g, const char *who, std::vector<double> &rec, std::vector<int> *eb = nullptr);

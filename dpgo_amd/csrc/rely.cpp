@@ -19,6 +19,78 @@
 
 namespace dpgo {
 
+// The three blocks S_pp, S_pq, S_qq of nu listed edges behind a factorisation that succeeded, into d_joint (device, nu x 3 dof^2,
+// zeroed by the caller: the anchor's blocks under SOLVE): gathered out of the selected inversion (RELY_SELINV) or solved for
+// batch by batch (pairs_solve_joint).  prow: the unified own rows of every edge's two poses, d_prow the same on the device.
+// Returns behind a synchronise.  edge_reliability and ml_edge_reliability (ml_rely.cpp) share it.
+int Group::rely_joint(int use, const PairsPlan &pl, int nu, const std::vector<int> &prow, int arow, const int *d_prow, double *d_joint,
+                      const char *who) {
+  if (use != RELY_SELINV) return pairs_solve_joint(pl, nu, d_prow, d_joint, who);
+  CertState &c = *cert_;
+  CovState &s = *cov_;
+  const int dof = cov_dof(d_), NL = rely_map_ints(dof);
+  if (spd_selinv_device(s.F, st_) != 0) {
+    fprintf(stderr, "[dpgo_amd] ERROR: %s: the selected inversion failed on the device.\n", who);
+    return -1;
+  }
+  // the map: a pose's dof unknowns are pivots of one front, whose S_pp holds its marginal; the block of an edge lies in the
+  // front of whichever pose is eliminated first, whose update rows hold the other (cov.cpp: cov_finish)
+  const SpdFactor &F = s.F;
+  const std::vector<int64_t> foff = spd_selinv_offsets(F);
+  std::vector<int64_t> off((size_t)3 * nu, -1);
+  std::vector<int> loc((size_t)NL * nu, 0);
+  for (int k = 0; k < nu; k++) {
+    const int p = prow[2 * k], q = prow[2 * k + 1];
+    int *l = &loc[(size_t)NL * k];
+    const int fp = s.piv_front[dof * p], fq = s.piv_front[dof * q], fx = std::min(fp, fq);
+    for (int a = 0; a < dof; a++) {
+      if (s.piv_front[dof * p + a] != fp || s.piv_front[dof * q + a] != fq) {
+        fprintf(stderr, "[dpgo_amd] ERROR: %s: the unknowns of a pose are spread over two fronts.\n", who);
+        return -1;
+      }
+      l[3 + a] = s.piv_loc[dof * p + a];
+      l[3 + dof + a] = s.piv_loc[dof * q + a];
+    }
+    l[0] = F.w[fp] + F.u[fp];
+    l[1] = F.w[fx] + F.u[fx];
+    l[2] = F.w[fq] + F.u[fq];
+    if (p != arow) off[(size_t)3 * k] = foff[fp];
+    if (q != arow) off[(size_t)3 * k + 2] = foff[fq];
+    if (p == arow || q == arow) continue;
+    const int w = F.w[fx], u = F.u[fx];
+    const int *up = u ? &F.upd_idx[F.upd_ptr[fx]] : nullptr;
+    for (int side = 0; side < 2; side++) {
+      const int pose = side == 0 ? p : q;
+      for (int a = 0; a < dof; a++) {
+        const int v = dof * pose + a;
+        int lv = -1;
+        if (s.piv_front[v] == fx) lv = s.piv_loc[v];
+        else {
+          const int *it = std::lower_bound(up, up + u, v);
+          if (it != up + u && *it == v) lv = w + (int)(it - up);
+          else
+            for (int t = 0; t < u && lv < 0; t++)   // (update rows that are not ascending)
+              if (up[t] == v) lv = w + t;
+        }
+        if (lv < 0 || lv >= w + u) {
+          fprintf(stderr, "[dpgo_amd] ERROR: %s: edge (%d, %d) lies outside the factor's pattern.\n", who, c.gid[p], c.gid[q]);
+          return -1;
+        }
+        l[3 + (2 + side) * dof + a] = lv;
+      }
+    }
+    off[(size_t)3 * k + 1] = foff[fx];
+  }
+  DevBuf<int64_t> d_off;
+  DevBuf<int> d_loc;
+  d_off.upload(off);
+  d_loc.upload(loc);
+  launch_rely_gather(st_, dof, nu, d_off.p, d_loc.p, spd_selinv_values(s.F), d_joint);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st_));
+  return 0;
+}
+
 int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor, long long max_bytes, int method, const int *edges,
                             int nedges, double *rec_out, double *rel, double *joint, RelyResult &out) {
   out = RelyResult();
@@ -123,69 +195,7 @@ int Group::edge_reliability(const Graph &g, const double *X, int ld, int anchor,
     d_rel.alloc((size_t)nu * DD, false);
     d_gate.alloc((size_t)nu * NG, false);
     d_rec.alloc((size_t)nu * W, false);
-    if (use == RELY_SELINV) {
-      if (spd_selinv_device(s.F, st_) != 0) {
-        fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: the selected inversion failed on the device.\n");
-        return -1;
-      }
-      // the map: a pose's dof unknowns are pivots of one front, whose S_pp holds its marginal; the block of an edge lies in the
-      // front of whichever pose is eliminated first, whose update rows hold the other (cov.cpp: cov_finish)
-      const SpdFactor &F = s.F;
-      const std::vector<int64_t> foff = spd_selinv_offsets(F);
-      std::vector<int64_t> off((size_t)3 * nu, -1);
-      std::vector<int> loc((size_t)NL * nu, 0);
-      for (int k = 0; k < nu; k++) {
-        const int p = prow[2 * k], q = prow[2 * k + 1];
-        int *l = &loc[(size_t)NL * k];
-        const int fp = s.piv_front[dof * p], fq = s.piv_front[dof * q], fx = std::min(fp, fq);
-        for (int a = 0; a < dof; a++) {
-          if (s.piv_front[dof * p + a] != fp || s.piv_front[dof * q + a] != fq) {
-            fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: the unknowns of a pose are spread over two fronts.\n");
-            return -1;
-          }
-          l[3 + a] = s.piv_loc[dof * p + a];
-          l[3 + dof + a] = s.piv_loc[dof * q + a];
-        }
-        l[0] = F.w[fp] + F.u[fp];
-        l[1] = F.w[fx] + F.u[fx];
-        l[2] = F.w[fq] + F.u[fq];
-        if (p != arow) off[(size_t)3 * k] = foff[fp];
-        if (q != arow) off[(size_t)3 * k + 2] = foff[fq];
-        if (p == arow || q == arow) continue;
-        const int w = F.w[fx], u = F.u[fx];
-        const int *up = u ? &F.upd_idx[F.upd_ptr[fx]] : nullptr;
-        for (int side = 0; side < 2; side++) {
-          const int pose = side == 0 ? p : q;
-          for (int a = 0; a < dof; a++) {
-            const int v = dof * pose + a;
-            int lv = -1;
-            if (s.piv_front[v] == fx) lv = s.piv_loc[v];
-            else {
-              const int *it = std::lower_bound(up, up + u, v);
-              if (it != up + u && *it == v) lv = w + (int)(it - up);
-              else
-                for (int t = 0; t < u && lv < 0; t++)   // (update rows that are not ascending)
-                  if (up[t] == v) lv = w + t;
-            }
-            if (lv < 0 || lv >= w + u) {
-              fprintf(stderr, "[dpgo_amd] ERROR: edge_reliability: edge (%d, %d) lies outside the factor's pattern.\n", c.gid[p], c.gid[q]);
-              return -1;
-            }
-            l[3 + (2 + side) * dof + a] = lv;
-          }
-        }
-        off[(size_t)3 * k + 1] = foff[fx];
-      }
-      DevBuf<int64_t> d_off;
-      DevBuf<int> d_loc;
-      d_off.upload(off);
-      d_loc.upload(loc);
-      launch_rely_gather(st_, dof, nu, d_off.p, d_loc.p, spd_selinv_values(s.F), d_joint.p);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipStreamSynchronize(st_));
-    } else if (pairs_solve_joint(pl, nu, d_prow.p, d_joint.p, "edge_reliability") != 0) {
-      return -1;
-    }
+    if (rely_joint(use, pl, nu, prow, arow, d_prow.p, d_joint.p, "edge_reliability") != 0) return -1;
     out.inverse_ms = ms_since(t0);
     t0 = Clock::now();
     launch_pairs_gate(d, st_, nu, d_prow.p, d_joint.p, c.X.p, d_cand.p, d_rel.p, d_gate.p);

@@ -1,6 +1,6 @@
 // The reference driver's main loop (C++/examples/dist_pgo.cpp:446-531) written against the C++ facade
 // include/dpgo_amd.hpp: read_g2o -> chordal init -> { iterate; communicate; update } with all nodes on GPU 0.
-//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]
+//   facade_mm <file.g2o> <num_nodes> <iters> [loss: trivial|huber|gm|welsch] [accelerated: 0|1] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability|ml_reliability]
 //   facade_mm --info <file.g2o> <num_nodes>        (host only: partition sizes, no GPU needed)
 // Prints "<iter>: <2F> <2|grad F|>" like the reference (dist_pgo.cpp:493-494).  With a sixth argument `certify` the final
 // point goes through DPGOHashGroup::verify_solution and the outcome is printed to STDERR (stdout stays the trace):
@@ -70,6 +70,13 @@
 //   reliability: e <edge> <the 6 + 2 dof entries of its record>
 // then   reliability: <OK|NOT_PD|SKIPPED|FAILED> <SELINV|SOLVE|AUTO> <edges> <flagged> <unweighted> <redundancy_sum, 17 digits>; a
 // last call with an edge index outside the graph must fail:   reliability: bad edge <status>
+// and with `ml_reliability` through DPGOHashGroup::newton_polish, ::ml_polish and, at its point, ::ml_edge_reliability (every edge,
+// on the file's information matrices) and ::ml_pair_gate with every edge of the graph as its own candidate: per edge two lines,
+// all entries with 17 digits,
+//   ml reliability: e <edge> <the 6 + 2 dof entries of its record>
+//   ml gate: e <edge> <d2> <not_pd> <the dof entries of the residual>
+// then   ml reliability: <OK|NOT_PD|SKIPPED|FAILED> <SELINV|SOLVE|AUTO> <edges> <flagged> <redundancy_sum, 17 digits>
+// and    ml gate: <OK|NOT_PD|SKIPPED|FAILED> <columns> <batches>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -90,7 +97,7 @@ int main(int argc, char **argv) {
     return 0;
   }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability]\n", argv[0]);
+    fprintf(stderr, "usage: %s <file.g2o> <num_nodes> <iters> [loss] [accelerated] [certify|verify|reweighted|covariance|polish|ml_polish|robust_polish|gnc|ml_gnc <tls|gm> <barc2>|staircase|pairs <candidates.g2o>|modes <k>|sensitivity <pose>|robust_sensitivity <pose>|reliability|ml_reliability]\n", argv[0]);
     return 2;
   }
   const int num_nodes = atoi(argv[2]), iters = atoi(argv[3]);
@@ -492,6 +499,48 @@ int main(int argc, char **argv) {
     int bad_status = 0;
     dpgo_hash.edge_reliability(Xp, rec, 0, nullptr, &bad_status, &bad);
     fprintf(stderr, "reliability: bad edge %d\n", bad_status);
+  }
+  if (argc > 6 && !strcmp(argv[6], "ml_reliability")) {
+    DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp, Z;
+    if (dpgo_hash.gather(X) != 0) return 1;
+    dpgo_hash.newton_polish(X, Xp);   // (Xp is X itself where the polish is SKIPPED)
+    int pstatus = -1;
+    dpgo_hash.ml_polish(Xp, Z, nullptr, &pstatus);
+    if (pstatus < 0) return 1;
+    const int d = graph->d(), dof = d + d * (d - 1) / 2, w = 6 + 2 * dof, m = graph->num_edges();
+    std::vector<double> rec;
+    int status = -1;
+    dpgo_rely_result_t r = {};
+    const bool ok = dpgo_hash.ml_edge_reliability(Z, rec, 0, &r, &status);
+    for (int e = 0; ok && e < m; e++) {
+      fprintf(stderr, "ml reliability: e %d", e);
+      for (int b = 0; b < w; b++) fprintf(stderr, " %.17g", rec[(size_t)e * w + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "ml reliability: %s %s %d %d %.17g\n", status == DPGO_RELY_OK ? "OK" : status == DPGO_RELY_NOT_PD ? "NOT_PD"
+            : status == DPGO_RELY_SKIPPED ? "SKIPPED" : "FAILED", r.method_used == DPGO_RELY_SELINV ? "SELINV"
+            : r.method_used == DPGO_RELY_SOLVE ? "SOLVE" : "AUTO", r.edges, r.flagged, r.redundancy_sum);
+    if (status < 0) return 1;
+    // every edge of the graph as a candidate of its own
+    std::vector<int> I(m), J(m), pairs((size_t)2 * m);
+    std::vector<double> cR((size_t)m * d * d), ct((size_t)m * d), kappa(m), tau(m), info((size_t)m * dof * dof), gate, joint, rel;
+    if (dpgo_graph_edges(graph->handle(), I.data(), J.data(), cR.data(), ct.data(), kappa.data(), tau.data()) != 0) return 1;
+    if (dpgo_graph_edge_information(graph->handle(), info.data(), nullptr) != 0) return 1;
+    for (int e = 0; e < m; e++) {
+      pairs[(size_t)2 * e] = I[e];
+      pairs[(size_t)2 * e + 1] = J[e];
+    }
+    int gstatus = -1;
+    dpgo_pairs_result_t gr = {};
+    const bool gok = dpgo_hash.ml_pair_gate(Z, pairs, cR, ct, info, gate, joint, rel, 0, &gr, &gstatus);
+    for (int e = 0; gok && e < m; e++) {
+      fprintf(stderr, "ml gate: e %d", e);
+      for (int b = 0; b < 2 + dof; b++) fprintf(stderr, " %.17g", gate[(size_t)e * (2 + dof) + b]);
+      fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "ml gate: %s %d %d\n", gstatus == DPGO_PAIRS_OK ? "OK" : gstatus == DPGO_PAIRS_NOT_PD ? "NOT_PD"
+            : gstatus == DPGO_PAIRS_SKIPPED ? "SKIPPED" : "FAILED", gr.columns, gr.batches);
+    if (gstatus < 0) return 1;
   }
   if (argc > 7 && !strcmp(argv[6], "robust_sensitivity")) {
     DPGO::Matrix X((graph->d() + 1) * graph->num_poses(), graph->d()), Xp;

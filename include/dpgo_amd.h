@@ -1035,6 +1035,35 @@ int dpgo_group_debug_ml_hessian_guarded(dpgo_group_t *grp, const dpgo_graph_t *g
 int dpgo_debug_ml_edge_host(const dpgo_graph_t *graph, const double *X, int ld, double *r, double *wr, double *chi2, double *Ji,
                             double *Jj, double *grad, double *blocks, long long *near_pi);
 
+/* ---- edge reliability and candidate gating on the full information matrices ---- */
+/* dpgo_group_edge_reliability's and the gate of dpgo_group_pair_covariance's questions asked of F_ml: H = sum J' Omega J with
+ * the graph's Omega, rel = J Sigma_joint J' with the exact Jacobians of the ML residual, and the statistics measured in Omega --
+ * d2_loo = r' (Omega^-1 - rel)^-1 r for an edge of the graph, d2 = r' (rel + Omega^-1)^-1 r for a candidate -- evaluated in a
+ * whitened form that never inverts Omega.  Both are chi-square quantities of dof degrees of freedom for anisotropic and
+ * translation-rotation coupled noise.  The restrictions and the refusals are dpgo_group_ml_covariance's; stationarity is the norm
+ * of the tangent gradient of F_ml; SKIPPED allocates nothing and leaves the stationarity 0.
+ *
+ * dpgo_group_ml_edge_reliability: the arguments, list semantics (any order, repeats allowed; NULL: every edge), methods, records
+ *   (6 + 2 dof doubles; flag 2 does not occur), rel, joint and result of dpgo_group_edge_reliability.  The redundancies of all
+ *   edges sum to dof (m - N + 1) at any point.
+ * dpgo_group_ml_pair_gate: npairs candidates (p -> q) -- p == q and the anchor allowed -- with measurement cand_R (npairs x d^2,
+ *   row-major), cand_t (npairs x d) and information cand_info (npairs x dof^2, symmetric positive definite: -1 otherwise, the
+ *   candidate named).  joint, rel as dpgo_group_pair_covariance; gate: npairs x (2 + dof): d2, not_pd, the ML residual.  A
+ *   candidate that copies an edge of the graph has that edge's residual bit for bit.
+ * dpgo_debug_ml_rely_edge_host (no device) / dpgo_debug_ml_rely_edge: the arithmetic alone for n edges -- J: n x 2 dof^2
+ *   ([J_p | J_q], each dof x dof row-major), joint: n x 3 dof^2, omega: n x dof^2, r: n x dof, sign -1 (reliability records,
+ *   n x (6 + 2 dof)) or +1 (gate records, n x (2 + dof)); rel: n x dof^2.  -1: bad sizes or an omega that is not positive definite. */
+int dpgo_group_ml_edge_reliability(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor,
+                                   long long max_bytes, int method, const int *edges, int nedges, double *records, double *rel,
+                                   double *joint, dpgo_rely_result_t *result);
+int dpgo_group_ml_pair_gate(dpgo_group_t *grp, const dpgo_graph_t *graph, const double *X, int ld, int anchor, long long max_bytes,
+                            const int *pairs, int npairs, const double *cand_R, const double *cand_t, const double *cand_info,
+                            double *joint, double *rel, double *gate, dpgo_pairs_result_t *result);
+int dpgo_debug_ml_rely_edge_host(int d, int n, int sign, const double *J, const double *joint, const double *omega, const double *r,
+                                 double *rel, double *records);
+int dpgo_debug_ml_rely_edge(int device, int d, int n, int sign, const double *J, const double *joint, const double *omega,
+                            const double *r, double *rel, double *records);
+
 /* ---- graduated non-convexity: which measurements are outliers, and the solution without them ---- */
 /* GNC-TLS and GNC-GM (Yang, Antonante, Tzoumas, Carlone, RA-L 2020) on the device.  s_e = s_rot + s_trans as dpgo_edge_eval_run
  * returns them; barc2 > 0 is the inlier threshold on s_e; the robust set R is the edges the loss may touch -- the inter-node

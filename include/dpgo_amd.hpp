@@ -494,6 +494,51 @@ class DPGOHashGroup {
     if (result) *result = r;
     return rc == 0 && r.outcome == DPGO_COV_OK;
   }
+  // Per-edge reliability on the full information matrices (dpgo_group_ml_edge_reliability): edge_reliability on
+  // H = sum J' Omega J with the statistics measured in the graph's Omega, so that d2_loo is a chi-square quantity of dof degrees
+  // of freedom for anisotropic noise.  X should be ml_polish's point.  Arguments, records, returns and status as edge_reliability.
+  bool ml_edge_reliability(const Matrix &X, std::vector<Scalar> &records, int anchor = 0, dpgo_rely_result_t *result = nullptr,
+                           int *status = nullptr, const std::vector<int> *edges = nullptr, int method = DPGO_RELY_AUTO,
+                           long long max_bytes = 0, std::vector<Scalar> *rel = nullptr, std::vector<Scalar> *joint = nullptr) const {
+    const int d = graph_->d(), dof = d + d * (d - 1) / 2;
+    const size_t n = edges ? edges->size() : (size_t)graph_->num_edges();
+    records.assign(n * (6 + 2 * dof), 0.0);
+    if (rel) rel->assign(n * dof * dof, 0.0);
+    if (joint) joint->assign(n * 3 * dof * dof, 0.0);
+    const int none = 0;   // (an empty list is a list: neither its pointer nor that of its records may be null)
+    Scalar no_record = 0;
+    dpgo_rely_result_t r = {};
+    const int rc = dpgo_group_ml_edge_reliability(h_, graph_->handle(), X.data(), X.rows(), anchor, max_bytes, method,
+                                                  edges ? (edges->empty() ? &none : edges->data()) : nullptr,
+                                                  edges ? (int)edges->size() : 0, records.empty() ? &no_record : records.data(),
+                                                  rel ? rel->data() : nullptr, joint ? joint->data() : nullptr, &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_RELY_OK;
+  }
+  // The loop-closure gate on the full information matrices (dpgo_group_ml_pair_gate).  pairs: 2 npairs global poses (p == q and
+  // the anchor allowed); cand_R: npairs d d doubles, row-major; cand_t: npairs d; cand_info: npairs dof dof, each symmetric
+  // positive definite.  gate is resized to npairs (2 + dof) doubles -- d2 = r' (rel + info^-1)^-1 r, not_pd, the ML residual --
+  // joint and rel as pair_covariances.  Returns true for DPGO_PAIRS_OK; status: the outcome, -1 when the call itself failed.
+  bool ml_pair_gate(const Matrix &X, const std::vector<int> &pairs, const std::vector<Scalar> &cand_R, const std::vector<Scalar> &cand_t,
+                    const std::vector<Scalar> &cand_info, std::vector<Scalar> &gate, std::vector<Scalar> &joint, std::vector<Scalar> &rel,
+                    int anchor = 0, dpgo_pairs_result_t *result = nullptr, int *status = nullptr, long long max_bytes = 0) const {
+    const int d = graph_->d(), npairs = (int)pairs.size() / 2;
+    const int dof = d + d * (d - 1) / 2;
+    joint.assign((size_t)npairs * 3 * dof * dof, 0.0);
+    rel.assign((size_t)npairs * dof * dof, 0.0);
+    gate.assign((size_t)npairs * (2 + dof), 0.0);
+    const bool sized = cand_R.size() == (size_t)npairs * d * d && cand_t.size() == (size_t)npairs * d &&
+                       cand_info.size() == (size_t)npairs * dof * dof;
+    dpgo_pairs_result_t r = {};
+    const int rc = !sized ? -1
+                          : dpgo_group_ml_pair_gate(h_, graph_->handle(), X.data(), X.rows(), anchor, max_bytes, pairs.data(), npairs,
+                                                    cand_R.data(), cand_t.data(), cand_info.data(), joint.data(), rel.data(),
+                                                    gate.data(), &r);
+    if (status) *status = rc == 0 ? r.outcome : -1;
+    if (result) *result = r;
+    return rc == 0 && r.outcome == DPGO_PAIRS_OK;
+  }
   // Graduated non-convexity (dpgo_group_gnc): GNC-TLS / GNC-GM outlier rejection from X on the device.  This group is a
   // trivial-loss group that hosts every node of its graph.  opt NULL: the defaults (TLS, barc2 1); robust_set (optional, one int
   // per edge of the graph): the edges the loss may touch, instead of the inter-node ones.  Xout: the point (X itself for
